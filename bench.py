@@ -26,6 +26,13 @@ reduction.  What shards, per config:
   c5  latent-parallel STRONG scaling: 16 latents over the ranks, one all-reduce of the (mean_f, var_f) exchange buffer per step.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line: the headline `value` (iter/s), `ms_per_step`, and what the
+timed steps themselves measured (the dominant kernel's roofline from HIP events inside the timed region, collective accounting).
+--full adds everything that takes runs of its own: the split-overlap A/B (N > 1), isolated launches, the MFMA issue-rate and
+sustained-clock runs, the hyper-on iteration and streaming prediction (--no-extras: without them), time to ELBO tolerance
+(--no-elbo-tol) and the CPU baseline (--no-cpu-baseline).  --dump-outputs DIR writes the posterior the timed steps left
+(dump_outputs); the inputs depend on the arguments alone (fixed seeds), so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -90,7 +97,42 @@ def parse():
     p.add_argument("--collective", default="rccl", choices=["rccl", "torch"],
                    help="N > 1: who issues the all-reduces: libagp_hip.so through its own RCCL communicator (default) or a "
                         "callback into torch.distributed (diagnostic)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: split-overlap A/B, isolated launches, MFMA issue-rate and sustained "
+                        "clock runs, hyper-on iteration, streaming prediction, time to ELBO tolerance, CPU baseline (the --no-* "
+                        "options switch parts of it off)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the variational posterior they left (mu, Sigma per latent; A of the "
+                        "multi-output model) as DIR/<name>.npy")
     return p.parse_args()
+
+
+DUMP_BYTES = 60 << 20  # data of all --dump-outputs files together: under 64 MB with room for the .npy headers
+
+
+def dump_outputs(out_dir, model, n_written):
+    """--dump-outputs: what a caller of the timed path reads from the model after its last step -- mu and Sigma of every latent
+    this rank holds (global latent index in the name; the model's float type) and, for the multi-output model, the mixing weights
+    A -- as <out_dir>/<name>.npy.  n_written: latents written by all ranks together.  A Sigma larger than its share of DUMP_BYTES
+    is written as `Sigma_latent<k>_sample.npy`: a fixed, seeded sample of its entries (the same flat indices in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    m, es = model.m, np.dtype(model.T).itemsize
+    A = model.get_A() if hasattr(model, "get_A") else None
+    fixed = n_written * m * es + (A.nbytes if A is not None else 0)
+    per_sigma = max(1, (DUMP_BYTES - fixed) // (es * max(n_written, 1)))
+    pick = None
+    if m * m > per_sigma:
+        pick = np.sort(np.random.default_rng(2024).choice(m * m, per_sigma, replace=False))
+    for i in range(model.n_latent):
+        k = model.latent_offset + i
+        mu, Sig, _, _ = model.get_state(i)
+        np.save(os.path.join(out_dir, f"mu_latent{k}.npy"), mu)
+        if pick is None:
+            np.save(os.path.join(out_dir, f"Sigma_latent{k}.npy"), Sig)
+        else:
+            np.save(os.path.join(out_dir, f"Sigma_latent{k}_sample.npy"), Sig.reshape(-1)[pick])
+    if A is not None:
+        np.save(os.path.join(out_dir, "A.npy"), A)
 
 
 def rff_latent(X, D, g, dev, R=256):
@@ -504,12 +546,16 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if share else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # the state the timed steps left, before any section below steps the model again (batch-parallel ranks hold the same state:
+    # rank 0 writes it; latent-parallel ranks write the latents they own)
+    if a.dump_outputs and (rank == 0 or mode == "latent"):
+        dump_outputs(a.dump_outputs, model, model.n_latent_total if mode == "latent" and world > 1 else model.n_latent)
 
     # ---- A/B of the batch-parallel step's collective (outside the timed region above): the same loop once more with
     # AGP_SPLIT_OVERLAP flipped -- the statistics travelling in block-column groups on the communicator's own stream, the next
     # task-graph launch starting on the first group.  The library reads the variable at every step.
     overlap_ab = None
-    if comm is not None and mode == "batch" and os.environ.get("AGP_BENCH_NO_OVERLAP_AB") != "1":
+    if a.full and comm is not None and mode == "batch" and os.environ.get("AGP_BENCH_NO_OVERLAP_AB") != "1":
         keep = os.environ.get("AGP_SPLIT_OVERLAP")
         flipped = "0" if keep == "1" else "1"
         os.environ["AGP_SPLIT_OVERLAP"] = flipped
@@ -584,7 +630,7 @@ def main():
     # beyond the task graph the live number above is taken while the next minibatch's kappa GEMM runs on the prefetch stream
     # (the two share the CUs): a few extra steps without the prefetch give the factorisation on its own
     isolated = None
-    if not dag and comm is None:
+    if a.full and not dag and comm is None:
         model._chk(L.agp_svgp_timing_enable(h, 1))
         for j in range(3):
             if use_multi:
@@ -715,7 +761,7 @@ def main():
     # launch is the split one (chain kernel + tile kernel) the traffic is that of the merged instantiation of the same task graph.
     if world == 1 and comm is None:
         roofline.update(_pmc_traffic(a.config, roofline["kernel"], step_inst=True))
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         # measured MFMA ceiling (issue-rate microbenchmark inside the library)
         pk = C.c_double()
         if L.agp_mfma_peak(model._ctx, capi.F32 if f32 else capi.F64, C.byref(pk)) == 0:
@@ -725,7 +771,7 @@ def main():
 
     single_latent = cfg["lik"] in ("logistic", "studentt")
     # ---- extras (rank 0, single GPU, single-latent configs): hyper-parameter step and streaming prediction ----
-    if rank == 0 and world == 1 and single_latent and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and single_latent and not a.no_extras:
         cfg_h = dict(cfg)
         kern = {"sqexp": AGP.SqExponentialKernel, "matern52": AGP.Matern52Kernel}[cfg["kernel"]]()
         lik_h = AGP.LogisticLikelihood() if cfg["lik"] == "logistic" else AGP.StudentTLikelihood(3.0)
@@ -860,7 +906,7 @@ def main():
             out["predict_roofline"] = {"error": repr(ex)}
 
     # ---- time to ELBO tolerance (build-defined, SURVEY.md 8d: the reference has no stopping rule) ----
-    if not a.no_elbo_tol and rank == 0 and world == 1 and single_latent:
+    if a.full and not a.no_elbo_tol and rank == 0 and world == 1 and single_latent:
         EVAL = 8192
         eval_idx = torch.as_tensor(np.random.default_rng(77).choice(N, EVAL, replace=False).astype(np.int64), device=dev)
         model2 = build_model(AGP, cfg, ell, Z, B, 0, 1, local_rank, mode)
@@ -992,7 +1038,7 @@ def main():
     # The register-only MFMA issue loop for 3 s with the engine clock and socket power sampled at >= 10 Hz while it runs
     # (tools/clock_sampler.py): what "sustained" means on this box.  The clock the rate itself implies (every SIMD issuing back to
     # back: 256 CUs x 4 SIMDs x 2048 flop per 64-cycle v_mfma_f64_16x16x4, half the cycles in fp32) is printed next to it.
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         pk = C.c_double()
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -1035,7 +1081,7 @@ def main():
             out["mfma_sustained"] = {"error": repr(ex)}
 
     # ---- CPU baseline: the oracle (numpy/scipy LAPACK) on the host cores, same workload, bounded sample ----
-    if not a.no_cpu_baseline and rank == 0 and world == 1:
+    if a.full and not a.no_cpu_baseline and rank == 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(a, cfg, ell, Z, X, yh, idx_np, out)
 
     # RCCL writes its version banner through C stdio (buffered when stdout is a pipe; it would come out at exit, after the JSON
@@ -1057,7 +1103,7 @@ def main():
 
 def cpu_baseline(a, cfg, ell, Z, X, yh, idx_np, out):
     """The NumPy/SciPy (OpenBLAS) oracle on the GPU box's host cores: same config, same index stream, a bounded sample."""
-    from threadpoolctl import threadpool_limits
+    from threadpoolctl import threadpool_info, threadpool_limits
 
     from oracle import agp_ref as R
 
@@ -1110,9 +1156,13 @@ def cpu_baseline(a, cfg, ell, Z, X, yh, idx_np, out):
         else:
             r.update_parameters(Xh[ib], ytr[ib])
 
-    # pick the BLAS thread count that is fastest on this host for these LAPACK calls
+    # pick the BLAS thread count that is fastest on this host for these LAPACK calls -- at most as many threads as the BLAS pools
+    # were started with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS): OpenBLAS cannot grow its pool past that size, asking it to
+    # crashes the process inside LAPACK
+    pools = [p["num_threads"] for p in threadpool_info() if p.get("user_api") == "blas"]
+    cap = min([avail] + pools)
     best_thr, best_t = 1, float("inf")
-    for thr in sorted({t for t in (8, 16, 32, 64, avail) if t <= avail}):
+    for thr in sorted({t for t in (8, 16, 32, 64, cap) if t <= cap}):
         with threadpool_limits(limits=thr):
             r = fresh_ref()
             one(r, 0)
@@ -1153,7 +1203,7 @@ def cpu_baseline(a, cfg, ell, Z, X, yh, idx_np, out):
         "single_thread_value": one_thr,
         "kind": "port",
         "sample": f"{n_cpu} iterations of the same workload ({out['config']['workload']}) with the NumPy/SciPy(OpenBLAS) oracle "
-                  f"(GEMM-form distances, best of {{8,16,32,64,all}} BLAS threads; host has {avail} cores), {tcpu:.1f} s of CPU "
+                  f"(GEMM-form distances, best of {{8,16,32,64,all}} BLAS threads up to the pool's {cap}; host has {avail} cores), {tcpu:.1f} s of CPU "
                   f"work" + (f"; {min(cfg['K'], cfg['c5_latents'])} of the 16 latents, like the GPU line" if lik == "mo" else ""),
     }
     # the same rule on the same index stream needs the same number of iterations: extrapolated where running it would take many

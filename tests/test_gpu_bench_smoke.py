@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("steps,warmup", [(20, 5), (3, 1)])
 def test_bench_line_with_short_runs(built, steps, warmup):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-                        "--cpu-seconds", "1", "--cpu-elbo-seconds", "0", "--no-elbo-tol"], capture_output=True, text=True,
+                        "--full", "--cpu-seconds", "1", "--cpu-elbo-seconds", "0", "--no-elbo-tol"], capture_output=True, text=True,
                        timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -26,6 +26,29 @@ def test_bench_line_with_short_runs(built, steps, warmup):
     assert d["ms_per_step_with_hyper_update"] > 0 and d["hyper_roofline"]["frac"] > 0
 
 
+def test_plain_bench_line_and_dumped_outputs(built, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the headline fields and none of the --full sections, and
+    --dump-outputs writes the posterior of the timed steps as float .npy files within 64 MB."""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["metric"] == "cavi_iters_per_sec" and d["unit"] == "iter/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=2e-3)
+    for k in ("cpu_baseline", "time_to_elbo_tol_s", "hyper_roofline", "predict_roofline", "mfma_sustained"):
+        assert k not in d, k
+    import numpy as np
+
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["Sigma_latent0.npy", "mu_latent0.npy"], files
+    mu, Sig = np.load(out / "mu_latent0.npy"), np.load(out / "Sigma_latent0.npy")
+    assert mu.dtype == np.float64 and mu.shape == (1024,) and Sig.shape == (1024, 1024)
+    assert np.all(np.isfinite(mu)) and np.all(np.isfinite(Sig)) and np.allclose(Sig, Sig.T) and np.all(np.diag(Sig) > 0)
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+
+
 @pytest.mark.parametrize("config,extra", [("c2", []), ("c4", ["--m", "256", "--batch", "256", "--N", "20000"])])
 def test_bench_starts_its_own_ranks(built, config, extra):
     """`python bench.py --gpus 2` -- the shape of the driver's command, no launcher around it -- starts two ranks itself
@@ -35,7 +58,7 @@ def test_bench_starts_its_own_ranks(built, config, extra):
     env = dict(os.environ, AGP_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--config", config,
-                        "--no-cpu-baseline", "--no-elbo-tol", "--no-extras"] + extra, capture_output=True, text=True, timeout=1500,
+                        "--full", "--no-cpu-baseline", "--no-elbo-tol", "--no-extras"] + extra, capture_output=True, text=True, timeout=1500,
                        cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]

@@ -126,7 +126,7 @@ def test_label_errors_mirror_treat_labels(mods):
     assert st == 6, capi.ERR_NAMES.get(st, st)  # AGP_ERR_LABELS
 
 
-def test_get_matrix_capacity_and_last_batch(mods):
+def test_get_matrix_capacity_and_last_batch(mods, tmp_path):
     """B-sized exports follow the LAST batch the handle saw (an ELBO on a larger set counts) and the library
     refuses a smaller buffer instead of overrunning it; alpha is state and is exported by capacity."""
     AGP, R, capi, torch = mods
@@ -150,7 +150,7 @@ def test_get_matrix_capacity_and_last_batch(mods):
     assert m.get_matrix(capi.VEC_THETA, 0).shape == (400,)
     alpha = m.get_matrix(capi.VEC_ALPHA, 0, B)  # state: any capacity up to max_batch
     assert alpha.shape == (B,) and np.all(alpha > 1.0)
-    AGP.save_trained_model("/tmp/agp_capacity_test.npz", m)  # used to overrun a 64-element buffer after the ELBO call
+    AGP.save_trained_model(str(tmp_path / "agp_capacity_test.npz"), m)  # used to overrun a 64-element buffer after the ELBO call
 
 
 def test_predict_f_full_covariance(mods):

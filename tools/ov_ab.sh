@@ -1,7 +1,7 @@
 # Development aid: A/B of AGP_SPLIT_OVERLAP on ONE GPU with stand-in collectives (AGP_FORCE_SPLIT=1 AGP_BENCH_FAKE_ALLREDUCE_US):
 # bench.py runs its timed loop once per setting of the flag in one process (collective.split_overlap_ab).
 cd /root/repo
-B="python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-elbo-tol --no-extras"
+B="python bench.py --steps 300 --warmup 30 --full --no-cpu-baseline --no-elbo-tol --no-extras"
 for us in ${@:-40 60 100}; do
   AGP_FORCE_SPLIT=1 AGP_BENCH_FAKE_ALLREDUCE_US=$us timeout 300 $B 2>/dev/null | tail -1 | python -c "
 import sys, json

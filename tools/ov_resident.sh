@@ -4,7 +4,7 @@
 # communicator's own stream next to the task-graph launch whose tile workgroups wait at their arrival gates.
 # usage: bash tools/ov_resident.sh            -> stdout (copy to profiles/r05_split_overlap_resident_standin.txt)
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-B="python bench.py --warmup 30 --no-cpu-baseline --no-elbo-tol --no-extras"
+B="python bench.py --warmup 30 --full --no-cpu-baseline --no-elbo-tol --no-extras"
 line() { python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); c = d['collective']; ab = c.get('split_overlap_ab') or {}

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = sys.argv[2] if len(sys.argv) > 2 else "c2"
 TAG = sys.argv[3] if len(sys.argv) > 3 else f"r06_{CFG}"
 OUT = os.path.join(ROOT, "gpurun_out", f"pmc_{TAG}")
-CMD = ["python", os.path.join(ROOT, "bench.py"), "--config", CFG, "--no-cpu-baseline", "--no-elbo-tol", "--steps",
+CMD = ["python", os.path.join(ROOT, "bench.py"), "--config", CFG, "--full", "--no-cpu-baseline", "--no-elbo-tol", "--steps",
        "10" if CFG == "c5" else "40", "--warmup", "4" if CFG == "c5" else "10"]
 if CFG == "hyper":  # the reference's default mode: hyper-parameter step every iteration (tools/prof_hyper.py, C2 shape)
     CMD = ["python", os.path.join(ROOT, "tools", "prof_hyper.py")]
@@ -78,7 +78,7 @@ def parse():
 def mfma():
     """MFMA utilisation per kernel: one more --pmc pass with SQ_VALU_MFMA_BUSY_CYCLES; the counter sums busy cycles over all SIMDs,
     so it is put in proportion to the kernel's duration and to the same ratio of k_mfma_peak (back-to-back MFMAs on every SIMD of
-    the chip, part of every bench.py run) instead of to an assumed clock: util = (busy / us) / (busy / us of k_mfma_peak)."""
+    the chip, part of every bench.py --full run) instead of to an assumed clock: util = (busy / us) / (busy / us of k_mfma_peak)."""
     env = dict(os.environ, TMPDIR="/tmp")
     ctr = "SQ_VALU_MFMA_BUSY_CYCLES"
     d = os.path.join(OUT, f"bench_{ctr}")
