@@ -1559,6 +1559,7 @@ struct Svgp : SvgpBase {
     return AGP_OK;
   }
   agp_status step_finish() override {
+    if (full) return vgp_step_finish();
     if (pro_allowed() && chol_use_dag(ctx, mp / TILE, rup64(B_last) / TILE + 1, 1) && mp / TILE <= 32) {
       Latent& g = lat[0];
       g.C_valid = false;
@@ -1644,6 +1645,17 @@ struct Svgp : SvgpBase {
       ctx->err = "RobbinsMonro: kappa in (0.5,1], tau > 0";  // optimisers.jl:7-8
       return AGP_ERR_INVALID;
     }
+    full = (desc.flags & AGP_FLAG_FULL) != 0;
+    if (full) {  // VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85
+      if (desc.stochastic || Bmax != m || lp.kind == AGP_LIK_MULTIOUTPUT || desc.latent_offset != 0) {
+        ctx->err = "AGP_FLAG_FULL: the full model takes AnalyticVI, max_batch = m = N and all of its latents on one handle";
+        return AGP_ERR_INVALID;
+      }
+      if (lp.kind == AGP_LIK_GAUSSIAN) {  // VGP.jl:54-56
+        ctx->err = "For a Gaussian Likelihood you should directly use the `GP` model or the `SVGP` model for large datasets";
+        return AGP_ERR_UNSUPPORTED;
+      }
+    }
     lat.resize(nl);
     const int64_t mm = mp * mp;
     for (auto& g : lat) {
@@ -1660,10 +1672,12 @@ struct Svgp : SvgpBase {
       AGPCHK(dmalloc(ctx, &g.v, mp));
       AGPCHK(dmalloc(ctx, &g.Sigma, mm));
       AGPCHK(dmalloc(ctx, &g.mu, mp));
-      AGPCHK(dmalloc(ctx, &g.Knm, Bp * mp));
-      AGPCHK(dmalloc(ctx, &g.kappa, Bp * mp));
-      AGPCHK(dmalloc(ctx, &g.Wbuf, (Bp + TILE) * mp));
-      AGPCHK(dmalloc(ctx, &g.pk, (2 * mp / TILE) * Bp));
+      if (!full) {  // (kappa = I: the full model has no K_nm, kappa, K~ and takes only the [eta1' ; 0] block of Wbuf)
+        AGPCHK(dmalloc(ctx, &g.Knm, Bp * mp));
+        AGPCHK(dmalloc(ctx, &g.kappa, Bp * mp));
+        AGPCHK(dmalloc(ctx, &g.pk, (2 * mp / TILE) * Bp));
+      }
+      AGPCHK(dmalloc(ctx, &g.Wbuf, ((full ? 0 : Bp) + TILE) * mp));
       AGPCHK(dmalloc(ctx, &g.DgK, mp * TILE));
       AGPCHK(dmalloc(ctx, &g.DgA, mp * TILE));
       AGPCHK(upload_scales(g));
@@ -1687,7 +1701,7 @@ struct Svgp : SvgpBase {
     AGPCHK(dmalloc(ctx, &beta, Bp));
     AGPCHK(dmalloc(ctx, &gsum, Bp));
     AGPCHK(dmalloc(ctx, &alpha_save, Bp));
-    AGPCHK(dmalloc(ctx, &stats, nl * stats_stride()));
+    if (!full) AGPCHK(dmalloc(ctx, &stats, nl * stats_stride()));
     AGPCHK(dmalloc(ctx, &Tw, mm));
     AGPCHK(dmalloc(ctx, &Tw2, mm));
     AGPCHK(dmalloc(ctx, &tmpv, mp));
@@ -1748,6 +1762,7 @@ struct Svgp : SvgpBase {
     if (pf_done) dcheck(hipEventDestroy(pf_done), __LINE__);
     for (auto e : step_done)
       if (e) dcheck(hipEventDestroy(e), __LINE__);
+    if (vgp_part) dfree(vgp_part);
     T* ps[] = {rbuf2, wbuf2, pw0, pw1, Kt, muf, varf, cbuf, theta, gamma, rbuf, wbuf, alpha, beta, gsum, alpha_save, emuf,
                evarf, stats, Tw, Tw2, tmpv, lr_dev, Kstar, ppm, ppv, pmu, pvar};
     for (T* p : ps)
@@ -2164,9 +2179,212 @@ struct Svgp : SvgpBase {
     return AGP_OK;
   }
 
+  // ---- full model (AGP_FLAG_FULL: VGP, kappa = I, m = N, Z = the training inputs) -----------------------------------------
+  bool full = false;
+  T* vgp_part = nullptr;  // [2][ns][mp] partial column sums of k_vgp_colstats
+  int vgp_ns = 0;
+  // factor -2 eta2 with its inverse Xa and v = Xa eta1 (the [eta1' ; 0] extension block of the factorisation) -- no Sigma, no kappa
+  // rows: the blocked / task-graph factorisation with its X = L^-1 output; a lost task-graph dependency is redone by its plain
+  // in-stream fallback (k_chol_safe), which rebuilds A = -2 eta2 and the eta1 row from the same sources
+  agp_status vgp_factor(Latent& g) {
+    if (g.la_state != 0) {  // La holds a factor: rebuild -2 eta2
+      hipLaunchKernelGGL((k_copy2d<T>), grid2(mp, mp), blk2, 0, st(), (const T*)g.eta2, mp, mp, mp, g.La, mp, mp, mp, T(1), T(-2));
+      LAUNCHCHK(ctx);
+    }
+    SafeSrc<T> src{};
+    src.Bq = 0;
+    src.eta1[0] = g.eta1;
+    src.eta2[0] = g.eta2;
+    src.want_x = 1;
+    AGPCHK(timing_begin());
+    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, 1, 1, info_dev, m, (const T*)g.eta1, false, &src));
+    AGPCHK(timing_end(chol_use_dag(ctx, mp / TILE, 1) ? 1 : chol_launch_count(mp / TILE, 1)));
+    g.la_state = 1;
+    g.xa_valid = true;
+    g.xa_epoch += 1;
+    g.sigma_epoch = -1;
+    HIPCHK(ctx, hipMemcpyAsync(g.v, g.Wbuf, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
+    g.v_epoch = g.xa_epoch;
+    return AGP_OK;
+  }
+  // update_parameters!(::VGP) first half (training.jl:140-144): local_updates! on mean_f = mu, var_f = diag Sigma of the current
+  // posterior (latentgp.jl:171-189).  The factor of -2 eta2 and its inverse come from the factorisation (or from the last
+  // materialize(), which left them); mu and diag Sigma from one pass over the lower triangle of Xa (k_vgp_colstats), which feeds the
+  // point-wise likelihood update directly.  The whole training set every time: idx = NULL, B = N.
+  agp_status vgp_step_local(const void* y, const int64_t* idx, int64_t B, double rho, bool fresh) {
+    if (idx != nullptr || B != m) {
+      ctx->err = "full model (AGP_FLAG_FULL): steps and ELBO evaluations run on the whole training set (idx = NULL, B = N = m)";
+      return AGP_ERR_BAD_BATCH;
+    }
+    if (!y) return AGP_ERR_INVALID;
+    lsm_finished = false;
+    for (auto& g : lat) g.C_valid = false;
+    refresh_lazy = !fresh;
+    const agp_status rks = refresh_K();
+    refresh_lazy = false;
+    AGPCHK(rks);
+    AGPCHK(run_deferred_safe());
+    const int64_t ntc = mp / TILE;
+    const int ns = (int)std::max<int64_t>(1, std::min<int64_t>(ntc, (2048 + ntc - 1) / ntc));
+    if (!vgp_part || ns > vgp_ns) {
+      if (vgp_part) dfree(vgp_part);
+      vgp_part = nullptr;
+      AGPCHK(dmalloc(ctx, &vgp_part, 2 * (int64_t)ns * mp));
+      vgp_ns = ns;
+    }
+    const int64_t rows = (mp + ns - 1) / ns;
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      if (!(g.la_state == 1 && g.xa_valid)) AGPCHK(vgp_factor(g));
+      if (g.v_epoch != g.xa_epoch) {
+        hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xa, mp, mp, (const T*)g.eta1, g.v);
+        g.v_epoch = g.xa_epoch;
+      }
+      hipLaunchKernelGGL((k_vgp_colstats<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), mp, (const T*)g.Xa,
+                         (const T*)g.v, rows, vgp_part, vgp_part + (int64_t)ns * mp);
+      hipLaunchKernelGGL((k_vgp_local<T>), grid1(m), dim3(256), 0, st(), m, mp, ns, (const T*)vgp_part,
+                         (const T*)(vgp_part + (int64_t)ns * mp), (T)rho, lp, (const T*)y, Kt + l * Bp, muf + l * Bp,
+                         varf + l * Bp, cbuf + l * Bp, theta + l * Bp, rbuf + l * Bp, wbuf + l * Bp, (const T*)lam_dev,
+                         gamma + l * Bp);
+      LAUNCHCHK(ctx);
+    }
+    AGPCHK(lik_tail(y, idx, B, rho, fresh));
+    x_last = Zdummy();
+    y_last = y;
+    idx_last = nullptr;
+    B_last = B;
+    ldx_last = D;
+    rho_last = rho;
+    return AGP_OK;
+  }
+  const void* Zdummy() const { return (const void*)lat[0].Z; }
+  // natural_gradient! + global_update! of the full model (analyticVI.jl:126-140, inference.jl:25-28): eta and La = -2 eta2 by one
+  // streaming pass (k_vgp_eta); the factorisation itself is left to whoever needs the new posterior next (the next step's local
+  // phase, materialize())
+  agp_status vgp_step_finish() {
+    AGPCHK(lsm_finish());
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      hipLaunchKernelGGL((k_vgp_eta<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp,
+                         (const T*)kinv_step(g), (const T*)(rbuf + l * Bp), (const T*)(wbuf + l * Bp), (const T*)kinv_mu0_step(g),
+                         g.eta2, g.La, g.eta1);
+      LAUNCHCHK(ctx);
+      g.la_state = 0;
+      g.xa_valid = false;
+      g.C_valid = false;
+      g.post_valid = false;
+      g.pred_valid = g.predvar_valid = false;
+    }
+    n_opt += 1;
+    return AGP_OK;
+  }
+  // mean_f / var_f under the UPDATED posterior for objective(model, state, y): mu and diag Sigma of the materialised posterior
+  agp_status vgp_posterior_f() {
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      AGPCHK(materialize(g));
+      hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)g.Sigma, (const T*)g.mu, emuf + l * Bp,
+                         evarf + l * Bp);
+      LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  }
+  // update_hyperparameters!(::VGP) (autotuning.jl:49-85): only the Gaussian KL depends on the kernel; G_K from K^-1, Apred and
+  // K^-1 (mu - mu0) (k_vgp_gK), then the backward pass through kernelmatrix(k, X) with both operands X (G_K symmetric: twice the
+  // second-argument part).  X is never optimised: no dZ.
+  agp_status vgp_hypergrad(int l, double* dvar, double* dscale, void* dZ_out) {
+    if (l < 0 || l >= nl || B_last <= 0) return AGP_ERR_INVALID;
+    if (dZ_out) {
+      ctx->err = "full model (AGP_FLAG_FULL): the training inputs are not optimised (no dZ)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    Latent& g = lat[l];
+    if (g.k.kind == AGP_K_EXPONENTIAL) {
+      ctx->err = "hyper-gradient: ExponentialKernel is not differentiable at zero distance";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    AGPCHK(hyper_alloc());
+    AGPCHK(refresh_K());
+    AGPCHK(ensure_pred(g, true));  // Sigma, mu, K^-1 mu, Apred = K^-1 - K^-1 Sigma K^-1
+    n_hgrad += 1;
+    hipLaunchKernelGGL((k_vgp_gK<T>), grid2(mp, mp), blk2, 0, st(), m, mp, (const T*)g.Apred, (const T*)g.apred,
+                       (const T*)g.kinv_mu0, Tw2);
+    tw2_kis_of = -1;
+    dim3 gk((unsigned)(mp / TILE), (unsigned)(mp / HB_RT));
+    const int64_t tiles = (int64_t)gk.x * gk.y;
+    hipLaunchKernelGGL((k_kernel_backward<T>), gk, dim3(NTHREADS), 0, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m,
+                       (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind, kvar(g), (const T*)Tw2, mp, hy_pvar, hy_pscale,
+                       hy_pZ, mp);
+    hipLaunchKernelGGL((k_hyper_reduce<T>), dim3((unsigned)(D + 1 + (m * D + 255) / 256)), dim3(256), 0, st(), tiles, D,
+                       (const double*)hy_pvar, (const double*)hy_pscale, hy_g, 1.0, 1, (int64_t)gk.y, m, mp, (const T*)hy_pZ,
+                       hy_dZ, T(2), (const T*)nullptr, (int64_t)0, 0.0);
+    LAUNCHCHK(ctx);
+    if (hy_grad_on_device_only) return AGP_OK;
+    std::vector<double> hg(1 + D);
+    HIPCHK(ctx, hipMemcpyAsync(hg.data(), hy_g, sizeof(double) * (1 + D), hipMemcpyDeviceToHost, st()));
+    HIPCHK(ctx, hipStreamSynchronize(st()));
+    if (dvar) *dvar = hg[0];
+    if (dscale)
+      for (int64_t d = 0; d < D; ++d) dscale[d] = hg[1 + d];
+    hy_last = hg;
+    return AGP_OK;
+  }
+
+  // the likelihood updates that need more than one point (lambda of Poisson / Heteroscedastic, the optimised Gaussian noise): after the
+  // point-wise part, on mean_f / var_f of the batch
+  agp_status lik_tail(const void* y, const int64_t* idx, int64_t B, double rho, bool fresh) {
+    if (lp.kind == AGP_LIK_GAUSSIAN && lp.noise_dev) {  // sigma2 step, then theta / gradients with the new sigma2  gaussian.jl:56-72
+      const int nb = (int)((B + 255) / 256);
+      // a fresh evaluation (external ELBO: new local variables, ELBO.jl:32-47) steps sigma2 from a NEW optimiser state and throws
+      // that state away, as the reference does; the training state is left alone
+      double* ad = fresh ? noise_adam + 3 : noise_adam;
+      if (fresh) HIPCHK(ctx, hipMemsetAsync(ad, 0, sizeof(double) * 3, st()));
+      hipLaunchKernelGGL((k_noise_partial<T>), dim3(nb), dim3(256), 0, st(), B, (const T*)y, idx, (const T*)muf, (const T*)varf,
+                         lam_part);
+      if (lam_deferred) {
+        hipLaunchKernelGGL(k_lambda_reduce, dim3(1), dim3(256), 0, st(), nb, 1, (const double*)lam_part, (double)B, scal_dev + 60);
+      } else {
+        hipLaunchKernelGGL((k_noise_finish<T>), dim3(1), dim3(256), 0, st(), nb, (const double*)lam_part, (double)B,
+                           (const double*)nullptr, noise_eta, 0.9, 0.999, 1e-8, ad, lam_dev);
+        hipLaunchKernelGGL((k_gauss_grads<T>), dim3(nb), dim3(256), 0, st(), B, (T)rho, (const T*)y, idx, (const T*)lam_dev, theta,
+                           cbuf, rbuf, wbuf);
+      }
+      LAUNCHCHK(ctx);
+    } else if (lp.kind == AGP_LIK_POISSON) {  // lambda <- sum(y) / sum E[logistic(f)]   poisson.jl:78
+      if (gh_n <= 0) {
+        ctx->err = "PoissonLikelihood: install the Gauss-Hermite rule first (agp_svgp_set_quadrature)";
+        return AGP_ERR_INVALID;
+      }
+      const int nb = (int)((B + 255) / 256);
+      hipLaunchKernelGGL((k_poisson_partial<T>), dim3(nb), dim3(256), 0, st(), B, (const T*)y, idx, (const T*)muf,
+                         (const T*)varf, gh_n, (const double*)gh_dev, (const double*)(gh_dev + gh_n), lam_part);
+      if (lam_deferred)  // batch-sharded: the sums travel first (cavi_step_multi), lambda_finish_reduced() follows
+        hipLaunchKernelGGL(k_lambda_reduce, dim3(1), dim3(256), 0, st(), nb, 2, (const double*)lam_part, (double)B, scal_dev + 60);
+      else
+        hipLaunchKernelGGL((k_lambda_finish<T>), dim3(1), dim3(256), 0, st(), nb, 2, (const double*)lam_part, 0, (double)B,
+                           lam_dev);
+      LAUNCHCHK(ctx);
+    } else if (lp.kind == AGP_LIK_HETEROSCEDASTIC) {  // heteroscedastic.jl:71-129
+      const int nb = (int)((B + 255) / 256);
+      hipLaunchKernelGGL((k_hetero_local<T>), dim3(nb), dim3(256), 0, st(), B, Bp, (const T*)y, idx, (const T*)muf,
+                         (const T*)varf, (const T*)lam_dev, cbuf, gamma, theta, lam_part);
+      if (lam_deferred) {
+        hipLaunchKernelGGL(k_lambda_reduce, dim3(1), dim3(256), 0, st(), nb, 1, (const double*)lam_part, (double)B, scal_dev + 60);
+      } else {
+        hipLaunchKernelGGL((k_lambda_finish<T>), dim3(1), dim3(256), 0, st(), nb, 1, (const double*)lam_part, 1, (double)B,
+                           lam_dev);
+        hipLaunchKernelGGL((k_hetero_grads<T>), dim3(nb), dim3(256), 0, st(), B, Bp, (T)rho, (const T*)y, idx,
+                           (const T*)lam_dev, (const T*)gamma, theta, rbuf, wbuf);
+      }
+      LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  }
+
   // compute_kappa + mean_f/var_f + local update
   agp_status step_local(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho,
                         bool fresh) override {
+    if (full) return vgp_step_local(y, idx, B, rho, fresh);
     AGPCHK(check_batch(B));
     if (!x || !y || ldx < D) return AGP_ERR_INVALID;
     lsm_finished = false;
@@ -2459,51 +2677,7 @@ struct Svgp : SvgpBase {
                          rbuf + l0 * Bp, wbuf + l0 * Bp, Bp, flags_dev, (const T*)lam_dev, gamma + l0 * Bp);
       LAUNCHCHK(ctx);
     }
-    if (lp.kind == AGP_LIK_GAUSSIAN && lp.noise_dev) {  // sigma2 step, then theta / gradients with the new sigma2  gaussian.jl:56-72
-      const int nb = (int)((B + 255) / 256);
-      // a fresh evaluation (external ELBO: new local variables, ELBO.jl:32-47) steps sigma2 from a NEW optimiser state and throws
-      // that state away, as the reference does; the training state is left alone
-      double* ad = fresh ? noise_adam + 3 : noise_adam;
-      if (fresh) HIPCHK(ctx, hipMemsetAsync(ad, 0, sizeof(double) * 3, st()));
-      hipLaunchKernelGGL((k_noise_partial<T>), dim3(nb), dim3(256), 0, st(), B, (const T*)y, idx, (const T*)muf, (const T*)varf,
-                         lam_part);
-      if (lam_deferred) {
-        hipLaunchKernelGGL(k_lambda_reduce, dim3(1), dim3(256), 0, st(), nb, 1, (const double*)lam_part, (double)B, scal_dev + 60);
-      } else {
-        hipLaunchKernelGGL((k_noise_finish<T>), dim3(1), dim3(256), 0, st(), nb, (const double*)lam_part, (double)B,
-                           (const double*)nullptr, noise_eta, 0.9, 0.999, 1e-8, ad, lam_dev);
-        hipLaunchKernelGGL((k_gauss_grads<T>), dim3(nb), dim3(256), 0, st(), B, (T)rho, (const T*)y, idx, (const T*)lam_dev, theta,
-                           cbuf, rbuf, wbuf);
-      }
-      LAUNCHCHK(ctx);
-    } else if (lp.kind == AGP_LIK_POISSON) {  // lambda <- sum(y) / sum E[logistic(f)]   poisson.jl:78
-      if (gh_n <= 0) {
-        ctx->err = "PoissonLikelihood: install the Gauss-Hermite rule first (agp_svgp_set_quadrature)";
-        return AGP_ERR_INVALID;
-      }
-      const int nb = (int)((B + 255) / 256);
-      hipLaunchKernelGGL((k_poisson_partial<T>), dim3(nb), dim3(256), 0, st(), B, (const T*)y, idx, (const T*)muf,
-                         (const T*)varf, gh_n, (const double*)gh_dev, (const double*)(gh_dev + gh_n), lam_part);
-      if (lam_deferred)  // batch-sharded: the sums travel first (cavi_step_multi), lambda_finish_reduced() follows
-        hipLaunchKernelGGL(k_lambda_reduce, dim3(1), dim3(256), 0, st(), nb, 2, (const double*)lam_part, (double)B, scal_dev + 60);
-      else
-        hipLaunchKernelGGL((k_lambda_finish<T>), dim3(1), dim3(256), 0, st(), nb, 2, (const double*)lam_part, 0, (double)B,
-                           lam_dev);
-      LAUNCHCHK(ctx);
-    } else if (lp.kind == AGP_LIK_HETEROSCEDASTIC) {  // heteroscedastic.jl:71-129
-      const int nb = (int)((B + 255) / 256);
-      hipLaunchKernelGGL((k_hetero_local<T>), dim3(nb), dim3(256), 0, st(), B, Bp, (const T*)y, idx, (const T*)muf,
-                         (const T*)varf, (const T*)lam_dev, cbuf, gamma, theta, lam_part);
-      if (lam_deferred) {
-        hipLaunchKernelGGL(k_lambda_reduce, dim3(1), dim3(256), 0, st(), nb, 1, (const double*)lam_part, (double)B, scal_dev + 60);
-      } else {
-        hipLaunchKernelGGL((k_lambda_finish<T>), dim3(1), dim3(256), 0, st(), nb, 1, (const double*)lam_part, 1, (double)B,
-                           lam_dev);
-        hipLaunchKernelGGL((k_hetero_grads<T>), dim3(nb), dim3(256), 0, st(), B, Bp, (T)rho, (const T*)y, idx,
-                           (const T*)lam_dev, (const T*)gamma, theta, rbuf, wbuf);
-      }
-      LAUNCHCHK(ctx);
-    }
+    AGPCHK(lik_tail(y, idx, B, rho, fresh));
     x_last = x;
     y_last = y;
     idx_last = idx;
@@ -2581,6 +2755,7 @@ struct Svgp : SvgpBase {
 
   // gradient of the hyper objective w.r.t. (variance, per-dimension scales, Z) of latent l, on the batch of the last step
   agp_status hypergrad(int l, double* dvar, double* dscale, void* dZ_out) override {
+    if (full) return vgp_hypergrad(l, dvar, dscale, dZ_out);
     if (l < 0 || l >= nl || !x_last || B_last <= 0) return AGP_ERR_INVALID;
     Latent& g = lat[l];
     if (g.k.kind == AGP_K_EXPONENTIAL) {
@@ -3193,6 +3368,7 @@ struct Svgp : SvgpBase {
   }
   // mean_f / var_f of the owned latents on the last batch with the CURRENT posterior -> emuf / evarf (analyticVI.jl:260-266)
   agp_status posterior_f(int64_t B) {
+    if (full) return vgp_posterior_f();
     const int64_t Bq = rup64(B);
     for (int l = 0; l < nl; ++l) {
       Latent& g = lat[l];
@@ -5289,6 +5465,10 @@ agp_status agp_svgp_create(agp_ctx* ctx, const agp_svgp_desc* desc, agp_svgp** o
   DevGuard guard(ctx->device);
   *out = nullptr;
   SvgpBase* impl = nullptr;
+  if ((desc->flags & AGP_FLAG_FULL) && desc->dtype != AGP_F64) {
+    ctx->err = "AGP_FLAG_FULL: the full model is Float64 only";
+    return AGP_ERR_UNSUPPORTED;
+  }
   if (desc->dtype == AGP_F64) impl = new Svgp<double>();
   else if (desc->dtype == AGP_F32) impl = new Svgp<float>();
   else return AGP_ERR_INVALID;
@@ -5321,6 +5501,13 @@ agp_status agp_svgp_destroy(agp_svgp* h) {
 #define HCHKF(h) \
   HCHK(h);       \
   AGPCHK((h)->impl->flush())
+// entry points that have no meaning for a full model (AGP_FLAG_FULL): refused, nothing done
+static agp_status full_refused(agp_svgp* h, const char* what) {
+  h->impl->ctx->err = std::string("full model (AGP_FLAG_FULL): ") + what + " is not supported";
+  return AGP_ERR_UNSUPPORTED;
+}
+#define FULLNO(h, what) \
+  if ((h)->impl->desc.flags & AGP_FLAG_FULL) return full_refused((h), (what))
 
 agp_status agp_svgp_set_kernel(agp_svgp* h, int32_t latent, const agp_kernel_desc* k) {
   HCHKF(h);
@@ -5383,19 +5570,23 @@ agp_status agp_svgp_hyper_counters(agp_svgp* h, int64_t* n_grad_host, int64_t* n
 agp_status agp_svgp_step_local(agp_svgp* h, const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B,
                                double rho) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_step_local");
   return h->impl->step_local(x, ldx, y, idx, B, rho, false);
 }
 agp_status agp_svgp_prefetch(agp_svgp* h, const void* x, int64_t ldx, const int64_t* idx, int64_t B) {
   HCHK(h);
+  FULLNO(h, "agp_svgp_prefetch");
   return h->impl->prefetch(x, ldx, idx, B);
 }
 agp_status agp_svgp_set_multioutput(agp_svgp* h, int32_t n_task, const agp_lik_desc* liks_host, const double* A_host,
                                     double adam_eta, double adam_b1, double adam_b2, double adam_eps) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_set_multioutput");
   return h->impl->set_multioutput(n_task, liks_host, A_host, adam_eta, adam_b1, adam_b2, adam_eps);
 }
 agp_status agp_svgp_get_A(agp_svgp* h, double* A_host) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_get_A");
   return h->impl->get_A(A_host);
 }
 agp_status agp_svgp_elbo_terms(agp_svgp* h, double* terms_host) {
@@ -5404,27 +5595,33 @@ agp_status agp_svgp_elbo_terms(agp_svgp* h, double* terms_host) {
 }
 agp_status agp_svgp_set_batch_shard(agp_svgp* h, int32_t rank, int32_t world) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_set_batch_shard");
   return h->impl->set_batch_shard(rank, world);
 }
 agp_status agp_svgp_mo_shard(agp_svgp* h, int32_t q_total) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_mo_shard");
   return h->impl->mo_shard(q_total);
 }
 agp_status agp_svgp_mo_fbuf_ptr(agp_svgp* h, void** ptr, int64_t* count) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_mo_fbuf_ptr");
   return h->impl->mo_fbuf_ptr(ptr, count);
 }
 agp_status agp_svgp_mo_mix(agp_svgp* h) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_mo_mix");
   return h->impl->mo_mix();
 }
 agp_status agp_svgp_mo_refresh_f(agp_svgp* h) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_mo_refresh_f");
   return h->impl->mo_refresh_f();
 }
 agp_status agp_svgp_mo_predict_from_f(agp_svgp* h, int64_t n_t, int32_t mode, void* out0, void* out1,
                                       const double* gh_nodes_host, const double* gh_weights_host, int32_t n_nodes) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_mo_predict_from_f");
   return h->impl->mo_predict_from_f(n_t, mode, out0, out1, gh_nodes_host, gh_weights_host, n_nodes);
 }
 agp_status agp_svgp_elbo_enqueue(agp_svgp* h, const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho,
@@ -5445,6 +5642,7 @@ agp_status agp_svgp_hyper_rule(agp_svgp* h, int32_t kernel_rule, double kernel_r
 agp_status agp_svgp_hyper_configure(agp_svgp* h, int32_t opt_kernel, double kernel_eta, int32_t opt_Z, double z_eta,
                                     double adam_b1, double adam_b2, double adam_eps) {
   HCHKF(h);
+  if (opt_Z) FULLNO(h, "optimising the training inputs (opt_Z)");
   return h->impl->hyper_configure(opt_kernel, kernel_eta, opt_Z, z_eta, adam_b1, adam_b2, adam_eps);
 }
 agp_status agp_svgp_hypergrad(agp_svgp* h, int32_t latent, double* dvariance_host, double* dscale_host, void* dZ) {
@@ -5461,18 +5659,22 @@ agp_status agp_svgp_get_kernel(agp_svgp* h, int32_t latent, double* variance_hos
 }
 agp_status agp_svgp_lsm_gamma(agp_svgp* h) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_lsm_gamma");
   return h->impl->lsm_gamma();
 }
 agp_status agp_svgp_lsm_alpha(agp_svgp* h) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_lsm_alpha");
   return h->impl->lsm_alpha();
 }
 agp_status agp_svgp_lsm_gsum_ptr(agp_svgp* h, void** ptr, int64_t* count) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_lsm_gsum_ptr");
   return h->impl->lsm_gsum_ptr(ptr, count);
 }
 agp_status agp_svgp_step_stats(agp_svgp* h) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_step_stats");
   return h->impl->step_stats(false);
 }
 #ifdef AGP_DEBUG_PTRS
@@ -5490,10 +5692,12 @@ int agp_debug_dag_diag(agp_ctx* c, unsigned long long* out8) {
 #endif
 agp_status agp_svgp_stats_ptr(agp_svgp* h, void** ptr, int64_t* count) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_stats_ptr");
   return h->impl->stats_ptr(ptr, count);
 }
 agp_status agp_svgp_step_global(agp_svgp* h) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_step_global");
   return h->impl->step_global(false);
 }
 agp_status agp_svgp_timing_enable(agp_svgp* h, int32_t on) {
@@ -5528,6 +5732,7 @@ agp_status agp_svgp_set_state(agp_svgp* h, int32_t latent, const void* eta1, con
 }
 agp_status agp_svgp_get_matrix(agp_svgp* h, int32_t latent, int32_t which, void* out, int64_t ldo, int64_t cap) {
   HCHKF(h);
+  if (which == AGP_MAT_KNM || which == AGP_MAT_KAPPA) FULLNO(h, "K_nm / kappa (kappa = I)");
   return h->impl->get_matrix(latent, which, out, ldo, cap);
 }
 agp_status agp_svgp_last_batch(agp_svgp* h, int64_t* B_host) {
@@ -5562,15 +5767,18 @@ agp_status agp_svgp_predict_y(agp_svgp* h, const void* xt, int64_t ldx, int64_t 
 agp_status agp_svgp_set_online_prior(agp_svgp* h, int32_t latent, const void* za, int64_t ldza, int64_t ma, const void* invDa,
                                      int64_t ldi, const void* prev_eta1, double prevLa) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_set_online_prior");
   return h->impl->set_online_prior(latent, za, ldza, ma, invDa, ldi, prev_eta1, prevLa);
 }
 agp_status agp_svgp_online_snapshot(agp_svgp* h, int32_t latent, void* invDa_out, int64_t ldi, void* eta1_out,
                                     double* prevLa_host) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_online_snapshot");
   return h->impl->online_snapshot(latent, invDa_out, ldi, eta1_out, prevLa_host);
 }
 agp_status agp_svgp_adopt_local(agp_svgp* dst, agp_svgp* src) {
   HCHKF(dst);
+  FULLNO(dst, "agp_svgp_adopt_local");
   if (!src || !src->impl) return AGP_ERR_INVALID;
   AGPCHK(src->impl->flush());
   return dst->impl->adopt_local(src->impl);
@@ -5578,6 +5786,7 @@ agp_status agp_svgp_adopt_local(agp_svgp* dst, agp_svgp* src) {
 agp_status agp_svgp_online_first_step(agp_svgp* h_new, agp_svgp* h_old, const void* x, int64_t ldx, const void* y,
                                       int64_t B) {
   HCHKF(h_new);
+  FULLNO(h_new, "agp_svgp_online_first_step");
   if (!h_old || !h_old->impl) return AGP_ERR_INVALID;
   AGPCHK(h_old->impl->flush());
   SvgpBase *n = h_new->impl, *o = h_old->impl;
@@ -5599,6 +5808,7 @@ agp_status agp_svgp_online_first_step(agp_svgp* h_new, agp_svgp* h_old, const vo
 agp_status agp_svgp_hyper_apply(agp_svgp* h, int32_t latent, const double* dvariance_host, const double* dscale_host,
                                 const void* dZ) {
   HCHKF(h);
+  if (dZ) FULLNO(h, "a dZ gradient");
   return h->impl->hyper_apply(latent, dvariance_host, dscale_host, dZ);
 }
 agp_status agp_svgp_hyper_opt_state(agp_svgp* h, int32_t latent, int32_t set, double* k_m_host, double* k_v_host,
@@ -5890,21 +6100,25 @@ agp_status agp_comm_stats(agp_comm* cm, int64_t* n_calls_host, int64_t* bytes_ho
 agp_status agp_svgp_cavi_step_multi(agp_svgp* h, agp_comm* comm, int32_t mode, const void* x, int64_t ldx, const void* y,
                                     const int64_t* idx, int64_t B, double rho) {
   HCHK(h);  // (no flush: like agp_svgp_cavi_step, the step takes a pending natural-gradient step itself -- as its prologue)
+  FULLNO(h, "agp_svgp_cavi_step_multi");
   h->impl->n_steps += 1;
   return h->impl->cavi_step_multi(comm, mode, x, ldx, y, idx, B, rho);
 }
 agp_status agp_svgp_elbo_multi(agp_svgp* h, agp_comm* comm, int32_t mode, double* elbo_host) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_elbo_multi");
   return h->impl->elbo_multi(comm, mode, elbo_host);
 }
 agp_status agp_svgp_hyper_step_multi(agp_svgp* h, agp_comm* comm, int32_t tied) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_hyper_step_multi");
   return h->impl->hyper_step_multi(comm, tied);
 }
 agp_status agp_svgp_predict_multi(agp_svgp* h, agp_comm* comm, int32_t what, const void* xt, int64_t ldx, int64_t n_t,
                                   void* mu_out, void* var_out, const double* gh_nodes_host, const double* gh_weights_host,
                                   int32_t n_nodes) {
   HCHKF(h);
+  FULLNO(h, "agp_svgp_predict_multi");
   if (n_t == 0) return AGP_OK;  // no test points: nothing to write (the reference returns empty arrays)
   return h->impl->predict_multi(comm, what, xt, ldx, n_t, mu_out, var_out, gh_nodes_host, gh_weights_host, n_nodes);
 }

@@ -602,6 +602,11 @@ struct RowstatsBatch {
   const T* kd_ptr[ROWSTATS_MAXB];
   int use_kt[ROWSTATS_MAXB];   // K~ kept from the previous full-batch step
 };
+template <typename T>
+__device__ __forceinline__ void lik_local_point(int64_t i, T mu, T var, T rho, const LikParams<T>& lp, const T* __restrict__ y,
+                                                const int64_t* __restrict__ idx, T* __restrict__ c, T* __restrict__ theta,
+                                                T* __restrict__ r, T* __restrict__ w, const T* __restrict__ lam,
+                                                T* __restrict__ gamma, const T* yi_pre);
 // what one thread does for row i once the three row sums are known (s0 = sum_j W_ij^2, s1 = sum_j W_ij v_j, sk = sum of the K~
 // slices): K~ / mean_f / var_f and the likelihood's local update + expectation gradients.  Shared by the row-statistics kernels and
 // by the epilogue of the CAVI step's task-graph launch (agp_chol.h, round 3).  The output pointers are those of the row's latent.
@@ -620,6 +625,16 @@ __device__ __forceinline__ void rowstats_finish(int64_t i, T s0, T s1, T sk, T k
   Kt[i] = kt;
   muf[i] = mu;
   varf[i] = var;
+  lik_local_point<T>(i, mu, var, rho, lp, y, idx, c, theta, r, w, lam, gamma, yi_pre);
+}
+
+// the likelihood's local update + expectation gradients of point i from its (mean_f, var_f): the part of rowstats_finish that the
+// full model (AGP_FLAG_FULL: mean_f = mu, var_f = diag Sigma, k_vgp_local) shares with the sparse one
+template <typename T>
+__device__ __forceinline__ void lik_local_point(int64_t i, T mu, T var, T rho, const LikParams<T>& lp, const T* __restrict__ y,
+                                                const int64_t* __restrict__ idx, T* __restrict__ c, T* __restrict__ theta,
+                                                T* __restrict__ r, T* __restrict__ w, const T* __restrict__ lam,
+                                                T* __restrict__ gamma, const T* yi_pre) {
   if (lp.kind == LIK_LSM) {
     c[i] = sqrt(mu * mu + var);  // logisticsoftmax.jl:62-64
     return;
@@ -1632,4 +1647,112 @@ __global__ void k_proba_lsm(int64_t n, int nl, int64_t ldm, const T* __restrict_
   }
 }
 
+// ---- full model (AGP_FLAG_FULL: VGP(X, y, kernel, likelihood, AnalyticVI()), src/models/VGP.jl; kappa = I, m = N) ------------
+// natural_gradient!(::VarLatent) (analyticVI.jl:126-140; rho and the Descent(1) step drop out):
+//   eta1 = grad_E_mu + K \ mu0 ;  eta2 = -(Diagonal(grad_E_Sigma) + inv(K) / 2)
+// written together with La = -2 eta2 = inv(K) + 2 Diagonal(grad_E_Sigma), the next step's factorisation input: one streaming pass
+// over the two mp x mp matrices (r = grad_E_mu, w = grad_E_Sigma of the step's local update; the padding is the identity of
+// VarPosterior's initial state).  Grid (mp / 256, mp): one row per blockIdx.y.
+template <typename T>
+__global__ __launch_bounds__(256) void k_vgp_eta(int64_t m, int64_t mp, const T* __restrict__ Kinv, const T* __restrict__ r,
+                                                 const T* __restrict__ w, const T* __restrict__ kinv_mu0, T* __restrict__ eta2,
+                                                 T* __restrict__ La, T* __restrict__ eta1) {
+  const int64_t i = blockIdx.y;
+  const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (j >= mp) return;
+  T a;
+  if (i < m && j < m)
+    a = Kinv[i * mp + j] + (i == j ? T(2) * w[i] : T(0));
+  else
+    a = i == j ? T(1) : T(0);
+  La[i * mp + j] = a;
+  eta2[i * mp + j] = T(-0.5) * a;
+  if (i == 0) eta1[j] = j < m ? r[j] + (kinv_mu0 ? kinv_mu0[j] : T(0)) : T(0);
+}
+
+// mean_f = mu = Xa' v and var_f = diag Sigma = column sums of Xa .^ 2, with Xa = chol(-2 eta2)^-1 (lower) and v = Xa eta1
+// (inference.jl:25-28, latentgp.jl:171-189): the lower triangle of Xa is streamed once.  Workgroup = 64 columns x 4 row phases of one
+// row slice (blockIdx.y); slices above the column tile are skipped, the strict upper triangle is never read.  Partial sums per
+// (slice, column): p0 = sum Xa^2, p1 = sum Xa v (k_vgp_local adds the slices).
+template <typename T>
+__global__ __launch_bounds__(256) void k_vgp_colstats(int64_t mp, const T* __restrict__ X, const T* __restrict__ v,
+                                                      int64_t rows_per_slice, T* __restrict__ p0, T* __restrict__ p1) {
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t c0 = (int64_t)blockIdx.x * 64, col = c0 + tx;
+  const int64_t s = blockIdx.y;
+  int64_t jlo = s * rows_per_slice;
+  const int64_t jhi = jlo + rows_per_slice < mp ? jlo + rows_per_slice : mp;
+  if (jlo < c0) jlo = c0;
+  T a0 = T(0), a1 = T(0), b0 = T(0), b1 = T(0);
+  int64_t j = jlo + ty;
+  for (; j + 4 < jhi; j += 8) {  // two independent accumulator pairs
+    const T x0 = j >= col ? X[j * mp + col] : T(0);
+    const T x1 = j + 4 >= col ? X[(j + 4) * mp + col] : T(0);
+    a0 += x0 * x0;
+    b0 += x0 * v[j];
+    a1 += x1 * x1;
+    b1 += x1 * v[j + 4];
+  }
+  if (j < jhi) {
+    const T x0 = j >= col ? X[j * mp + col] : T(0);
+    a0 += x0 * x0;
+    b0 += x0 * v[j];
+  }
+  __shared__ T sa[4][64], sb[4][64];
+  sa[ty][tx] = a0 + a1;
+  sb[ty][tx] = b0 + b1;
+  __syncthreads();
+  if (ty != 0) return;
+  p0[s * mp + col] = (sa[0][tx] + sa[1][tx]) + (sa[2][tx] + sa[3][tx]);
+  p1[s * mp + col] = (sb[0][tx] + sb[1][tx]) + (sb[2][tx] + sb[3][tx]);
+}
+
+// ... the slices summed, then the point's local update (lik_local_point, as the sparse step's rowstats_finish): mean_f, var_f and
+// the local variables / expectation gradients of the m training points.  K~ = 0 (Kt) for the ELBO and get_matrix readers.
+template <typename T>
+__global__ void k_vgp_local(int64_t m, int64_t mp, int ns, const T* __restrict__ p0, const T* __restrict__ p1, T rho,
+                            LikParams<T> lp, const T* __restrict__ y, T* __restrict__ Kt, T* __restrict__ muf,
+                            T* __restrict__ varf, T* __restrict__ c, T* __restrict__ theta, T* __restrict__ r, T* __restrict__ w,
+                            const T* __restrict__ lam, T* __restrict__ gamma) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  T a = T(0), b = T(0);
+  for (int s = 0; s < ns; ++s) {
+    a += p0[s * mp + i];
+    b += p1[s * mp + i];
+  }
+  Kt[i] = T(0);
+  muf[i] = b;
+  varf[i] = a;
+  lik_local_point<T>(i, b, a, rho, lp, y, (const int64_t*)nullptr, c, theta, r, w, lam, gamma, (const T*)nullptr);
+}
+
+// Adjoint of K of the full model's ELBO: only GaussianKL(mu, mu0, Sigma, K) (KLdivergences.jl:11-18) depends on K, so
+//   G_K = (K^-1 (Sigma + d d') K^-1 - K^-1) / 2 = -Apred / 2 + a a' / 2,  a = K^-1 mu - K^-1 mu0,  Apred = K^-1 - K^-1 Sigma K^-1
+// (autotuning.jl:49-85; the kernel backward pass through kernelmatrix(k, X) then runs with both operands X)
+template <typename T>
+__global__ void k_vgp_gK(int64_t m, int64_t mp, const T* __restrict__ Apred, const T* __restrict__ a, const T* __restrict__ a0,
+                         T* __restrict__ out) {
+  const int64_t i = blockIdx.y * (int64_t)blockDim.y + threadIdx.y;
+  const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= mp || j >= mp) return;
+  T v = T(0);
+  if (i < m && j < m) {
+    const T ai = a[i] - (a0 ? a0[i] : T(0)), aj = a[j] - (a0 ? a0[j] : T(0));
+    v = T(-0.5) * Apred[i * mp + j] + T(0.5) * ai * aj;
+  }
+  out[i * mp + j] = v;
+}
+
+// diag Sigma and mu of a materialised posterior into the ELBO's (mean_f, var_f) buffers (the full model's mean_f / var_f)
+template <typename T>
+__global__ void k_vgp_diag(int64_t m, int64_t mp, const T* __restrict__ Sigma, const T* __restrict__ mu, T* __restrict__ mf,
+                           T* __restrict__ vf) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  mf[i] = mu[i];
+  vf[i] = Sigma[i * mp + i];
+}
+
 }  // namespace agp
+

@@ -96,11 +96,15 @@ def save_trained_model(filename: str, model: SVGP) -> None:
         raise RuntimeError("the model has no device state yet: train it first")
     model._pull_hypers()
     model._pull_lik_state()
+    from .vgp import VGP
+
     mo = isinstance(model, MOSVGP)
+    full = isinstance(model, VGP)
     inf = model.inference
     opt = inf.optimiser or RobbinsMonro()
     meta = {
-        "class": "MOSVGP" if mo else "SVGP",
+        # a VGP is rebuilt as a VGP (prior K + jitt I on its own training set), never as an SVGP with Z = X
+        "class": "MOSVGP" if mo else "VGP" if full else "SVGP",
         "kernels": [_kernel_spec(k) for k in model.kernels],
         "likelihood": [_lik_spec(l) for l in model.likelihood.likelihoods] if mo else _lik_spec(model.likelihood),
         "stochastic": bool(inf.stoch), "batchsize": int(inf.batchsize), "n_iter": int(inf.n_iter),
@@ -136,6 +140,8 @@ def save_trained_model(filename: str, model: SVGP) -> None:
         arrays["lsm_alpha"] = model.get_matrix(capi.VEC_ALPHA, 0, min(int(inf.batchsize), model._max_batch))
     if isinstance(model.mean, (list, np.ndarray)):
         arrays["mean_vec"] = np.asarray(model.mean, dtype=np.float64)
+    if full:  # the training set (Z_0 is X; y as the caller gave it)
+        arrays["vgp_y"] = np.asarray(model.y)
     np.savez_compressed(filename, **arrays)
 
 
@@ -168,6 +174,11 @@ def load_trained_model(filename: str, *, device=None):
         # (files written before round 6 carry no "a_opt": the model's default ADAM(0.01), MOSVGP.jl:42, as for a fresh model)
         a_opt = _opt_from(meta["a_opt"]) if "a_opt" in meta else None
         model = MOSVGP(kernels, [_lik_from(d) for d in meta["likelihood"]], inf, Zs, A=g["A"], Aoptimiser=a_opt, **kw)
+    elif meta["class"] == "VGP":
+        from .vgp import VGP
+
+        model = VGP(Zs[0], g["vgp_y"], kernels, _lik_from(meta["likelihood"]), inf, optimiser=kw["optimiser"],
+                    atfrequency=kw["atfrequency"], mean=mean, T=T, device=device)
     else:
         model = SVGP(kernels, _lik_from(meta["likelihood"]), inf, Zs, **kw)
     inf.n_iter = meta["n_iter"]

@@ -13,6 +13,7 @@ HIP stream.  There is no CPU path: constructing a device handle without a GPU ra
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import Callable, Optional, Sequence
 
@@ -294,7 +295,7 @@ class SVGP:
         opt = self.inference.optimiser or RobbinsMonro()
         d.rm_kappa, d.rm_tau = opt.kappa, opt.tau
         d.elbo_mode = capi.ELBO_REFERENCE if self.elbo_mode == "reference" else capi.ELBO_CORRECTED
-        d.flags = capi.FLAG_STALE_K if self.reference_compat_stale_K else 0
+        d.flags = (capi.FLAG_STALE_K if self.reference_compat_stale_K else 0) | getattr(self, "_desc_flags", 0)
         h = C.c_void_p()
         self._chk(L.agp_svgp_create(ctx, C.byref(d), C.byref(h)))
         self._h = h
@@ -563,10 +564,12 @@ class MOSVGP(SVGP):
 
 
 # ---- training (src/training/training.jl:13-111) ------------------------------------------------------------------
+@functools.singledispatch
 def train_(model: SVGP, X, y, iterations: int = 100, *, callback: Optional[Callable] = None, convergence=None,
            state: Optional[State] = None, obsdim: int = 1, idx_stream: Optional[Sequence] = None):
     """train!(model, X, y, iterations; callback, state, obsdim).  Runs a FIXED number of iterations like the
-    reference (ϵ / convergence are never read there, training.jl:48,93-94).
+    reference (ϵ / convergence are never read there, training.jl:48,93-94).  Dispatches on the model type like the reference's
+    method table: a VGP takes train!(model, iterations) (vgp.py).
 
     idx_stream: optional pre-generated minibatch indices (one int array per iteration) replacing
     StatsBase.sample(1:N, B; replace=false) (training.jl:51-53) so runs are reproducible across back-ends.
@@ -826,10 +829,11 @@ class SideObjective:
         return out.value
 
 
+@functools.singledispatch
 def ELBO(model: SVGP, X, y, *, obsdim: int = 1, rho: Optional[float] = None) -> float:
     """External ELBO(model, X, y) (src/functions/ELBO.jl:28-47): fresh local variables on (X, y), one local update.
     rho defaults to the reference's behaviour (the ρ left by the last train!, Appendix A Q13); pass rho=1 for the
-    properly scaled full-data ELBO."""
+    properly scaled full-data ELBO.  (A VGP: ELBO(model), vgp.py.)"""
     L = capi.lib()
     Xd = model._upload(X, obsdim)
     yt = model._treat(y)

@@ -106,7 +106,24 @@ enum { AGP_ELBO_CORRECTED = 0, AGP_ELBO_REFERENCE = 1 };
  * src/functions/ELBO.jl:15-21).  With the flag a hyper step leaves the step-side matrices (L, inv(K), K\mu0) as they are and
  * only an explicit agp_svgp_refresh_K (what the host calls where train! starts and ends) recomputes them; without it
  * (default) K is refreshed before the next step. */
-enum { AGP_FLAG_STALE_K = 1 };
+enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2 };
+/* AGP_FLAG_FULL: the handle is the full (non-sparse) model VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85 --
+ * one latent of dimension N per n_latent(likelihood), kappa = I, prior K + jitt I on the training inputs themselves.  Create it with
+ * m = max_batch = N, stochastic = 0, dtype AGP_F64 (other types: AGP_ERR_UNSUPPORTED); a Gaussian likelihood is refused with
+ * AGP_ERR_UNSUPPORTED (VGP.jl:54-56).  agp_svgp_set_Z installs the training inputs X.  The entry points keep their meaning:
+ *   cavi_step       idx = NULL, B = N (else AGP_ERR_BAD_BATCH); x is not read (the inputs are those of set_Z).  local_updates! on
+ *                   mean_f = mu, var_f = diag Sigma (latentgp.jl:171-189), then eta1 = grad_E_mu + K \ mu0,
+ *                   eta2 = -(Diagonal(grad_E_Sigma) + inv(K)/2) (analyticVI.jl:126-140); Sigma = -inv(eta2)/2, mu = Sigma eta1 by a
+ *                   Cholesky of -2 eta2 (inference.jl:25-28).  rho is ignored.
+ *   elbo            fresh_local = 0 (objective after a step) and 1 (fresh local variables), idx = NULL, B = N: expectation at
+ *                   (mu, diag Sigma) - GaussianKL(mu, mu0, Sigma, K) - AugmentedKL (analyticVI.jl:255-274, KLdivergences.jl:11-18)
+ *   get/set_state, get_matrix (AGP_MAT_KNM / AGP_MAT_KAPPA: AGP_ERR_UNSUPPORTED; AGP_VEC_KTILDE reads 0), refresh_K,
+ *   set_prior_mean, get/set_lik_param, init_state, invalidate_data: as for SVGP, with Z = X
+ *   hyper_step / hypergrad  gradient of the Gaussian KL w.r.t. the kernel parameters (autotuning.jl:49-85): the adjoint of K is
+ *                   (K^-1 (Sigma + d d') K^-1 - K^-1) / 2, d = mu - mu0; X is never optimised (dZ / opt_Z: AGP_ERR_UNSUPPORTED)
+ *   predict_f / predict_f_cov / predict_y / proba_y  the generic _predict_f with Zviews(m) = X (predictions.jl:25-50)
+ * Refused with AGP_ERR_UNSUPPORTED, doing nothing: the phase entry points (step_local, lsm_*, step_stats, stats_ptr, step_global),
+ * prefetch, batch sharding, every *_multi call, the online entry points, multi-output. */
 
 /* matrices readable through agp_svgp_get_matrix (for parity tests and the shim's state export) */
 enum {

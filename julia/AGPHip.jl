@@ -75,6 +75,7 @@ struct SvgpDesc
     flags::Int32                 # AGP_FLAG_STALE_K = 1 : reference_compat_stale_K (training.jl:187-208, SURVEY Appendix A Q1)
 end
 const AGP_FLAG_STALE_K = Int32(1)
+const AGP_FLAG_FULL = Int32(2)     # VGP: the full model, kappa = I, m = N, Z = the training inputs (agp_hip.h)
 const AGP_SHARD_LATENT, AGP_SHARD_BATCH = Int32(0), Int32(1)
 
 struct AGPError <: Exception
@@ -167,6 +168,9 @@ mutable struct HipModel{T,M<:AGP.AbstractGPModel{T}}
 end
 
 is_mo(hm::HipModel) = hm.model isa AGP.MOSVGP
+is_full(hm::HipModel) = hm.model isa AGP.VGP
+# the inputs the handle's "inducing points" are: Z of a sparse latent, the training inputs of a VGP (Zviews(m::VGP), VGP.jl:90)
+zview(hm::HipModel, gp) = is_full(hm) ? AGP.input(hm.model.data) : AGP.Zview(gp)
 nlat(hm::HipModel) = length(hm.latent_range)
 
 """
@@ -177,7 +181,8 @@ Wrap a reference model.  Nothing is allocated on the device until data arrive (`
 """
 function HipModel(model::M; reference_compat_stale_K::Bool=false,
                   latent_range::UnitRange{Int}=1:length(model.f)) where {T,M<:AGP.AbstractGPModel{T}}
-    model isa Union{SVGP,AGP.MOSVGP} || error("only SVGP / MOSVGP run on the HIP path")
+    model isa Union{SVGP,AGP.MOSVGP,AGP.VGP} || error("only SVGP / MOSVGP / VGP run on the HIP path")
+    model isa AGP.VGP && T != Float64 && error("VGP runs in Float64 only on the HIP path")
     AGP.inference(model) isa AnalyticVI || error("The inference object should be of type `AnalyticVI`")   # SVGP.jl:45-47
     return HipModel{T,M}(model, C_NULL, C_NULL, C_NULL, AGP_SHARD_LATENT, latent_range, 0, nothing, nothing, 0, nothing,
                          reference_compat_stale_K, Int32(0), Int32(1), Any[])
@@ -211,14 +216,16 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
     hm.h == C_NULL || ccall((:agp_svgp_destroy, libagp), Int32, (Ptr{Cvoid},), hm.h)
     inf = AGP.inference(model)
     gp1 = model.f[first(hm.latent_range)]
-    D = length(first(AGP.Zview(gp1)))
+    D = length(first(zview(hm, gp1)))
     m = AGP.dim(gp1)
+    is_full(hm) && (maxbatch = m)                            # a VGP steps on its whole training set (idx = NULL, B = N = m)
     stoch = AGP.is_stochastic(inf)
     rm = stoch ? inf.vi_opt.optimiser : nothing             # RobbinsMonro(κ, τ), optimisers.jl:1-19
     stoch && !(rm isa AGP.RobbinsMonro) && error("only RobbinsMonro is wired on this path (ALRSVI is dead code in the reference)")
     ld = is_mo(hm) ? LikDesc(4, 1, 0.0, 0.0) : lik_desc(AGP.likelihood(model))
     desc = SvgpDesc(T == Float64 ? 0 : 1, nlat(hm), first(hm.latent_range) - 1, stoch ? 1 : 0, m, D, maxbatch, ld, 0.0,
-                    stoch ? rm.κ : 0.51, stoch ? rm.τ : 1.0, 0, hm.stale_K ? AGP_FLAG_STALE_K : Int32(0))
+                    stoch ? rm.κ : 0.51, stoch ? rm.τ : 1.0, 0,
+                    (hm.stale_K ? AGP_FLAG_STALE_K : Int32(0)) | (is_full(hm) ? AGP_FLAG_FULL : Int32(0)))
     h = Ref{Ptr{Cvoid}}()
     check(ctx, ccall((:agp_svgp_create, libagp), Int32, (Ptr{Cvoid}, Ref{SvgpDesc}, Ptr{Ptr{Cvoid}}), ctx, desc, h))
     hm.h, hm.maxbatch = h[], maxbatch
@@ -226,11 +233,11 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
         gp = model.f[q]
         kd, keep = kernel_desc(AGP.kernel(gp), D)
         GC.@preserve keep check(ctx, ccall((:agp_svgp_set_kernel, libagp), Int32, (Ptr{Cvoid}, Int32, Ref{KernelDesc}), hm.h, i - 1, kd))
-        Zd = ROCArray{T}(reduce(hcat, AGP.Zview(gp)))       # D x m, point-major
+        Zd = ROCArray{T}(reduce(hcat, zview(hm, gp)))       # D x m, point-major
         check(ctx, ccall((:agp_svgp_set_Z, libagp), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64), hm.h, i - 1, pointer(Zd), D))
         μ₀ = AGP.pr_mean(gp)
         if !(μ₀ isa AGP.ZeroMean)   # (with an optimiser the FIRST HYPER STEP errors, like the reference's own broken update: update_hyperparameters!)
-            v = ROCArray{T}(μ₀(AGP.Zview(gp)))
+            v = ROCArray{T}(μ₀(zview(hm, gp)))
             check(ctx, ccall((:agp_svgp_set_prior_mean, libagp), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}), hm.h, i - 1, pointer(v)))
         end
         AMDGPU.synchronize()
@@ -253,7 +260,7 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
                          hm.h, AGP.pred_nodes, AGP.pred_weights, length(AGP.pred_nodes)))
     end
     # hyper-parameter optimisers: SVGP(...; optimiser, Zoptimiser) (SVGP.jl:39-42, default ADAM(0.01) / nothing)
-    ko, zo = AGP.opt(gp1), AGP.Zopt(gp1)
+    ko, zo = AGP.opt(gp1), is_full(hm) ? nothing : AGP.Zopt(gp1)   # (the inputs of a VGP are never optimised)
     if ko !== nothing || zo !== nothing
         # the reference hands whatever Optimisers.jl rule it is given to Optimisers.apply (autotuning_utils.jl:47-82); the device
         # carries ADAM, Descent and Momentum (agp_svgp_hyper_rule), anything else is refused here rather than silently replaced
@@ -996,5 +1003,24 @@ function ELBO(model::HipSVGP, X::AbstractMatrix, y::AbstractArray; backend::Symb
     return ELBO(TWINS[model], X, y; kw...)
 end
 objective(model::HipSVGP, state::HipModel, y=nothing) = objective(state)    # the state train! returned IS the device twin
+
+# VGP{T,L,<:AnalyticVI} (src/models/VGP.jl): train!(model, iterations) on the model's own data (training.jl:113-120) through the
+# same ABI, on a handle created with AGP_FLAG_FULL; predictions and the ELBO look the twin up like the sparse models'.
+const HipVGP{T} = AGP.VGP{T,<:Any,<:AnalyticVI}
+twin(model::HipVGP) = get!(() -> HipModel(model), TWINS, model)
+function train!(model::HipVGP, iterations::Int; backend::Symbol=BACKEND[], kwargs...)
+    backend === :cpu && return invoke(train!, Tuple{AGP.AbstractGPModel,Int}, model, iterations; kwargs...)
+    X = reduce(hcat, AGP.input(model.data))'                     # N x D
+    _, state = train!(twin(model), X, AGP.output(model.data), iterations; kwargs...)
+    return model, state
+end
+for f in (:predict_f, :predict_y, :proba_y)
+    @eval function $f(model::HipVGP, X_test::AbstractMatrix, state=nothing; backend::Symbol=BACKEND[], kw...)
+        (backend === :cpu || !has_twin(model)) &&
+            return invoke($f, Tuple{AGP.AbstractGPModel,AbstractMatrix,Any}, model, X_test, state; kw...)
+        return $f(TWINS[model], X_test; kw...)
+    end
+end
+objective(model::HipVGP, state::HipModel, y=nothing) = objective(state)
 
 end # module
