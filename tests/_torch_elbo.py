@@ -73,6 +73,23 @@ def autograd_hypergrad(kind, lik, X, y, Z, scale, variance, mu, Sigma, mu0, loca
     return float(var.grad), sc.grad.numpy().copy(), Zt.grad.numpy().copy(), float(val.detach())
 
 
+def neg_kl_hypergrad(kind, X, scale, variance, mu, mu0, Sigma, jitter=1e-4):
+    """the full model's hyper objective (VGP: only GaussianKL(mu, mu0, Sigma, K) depends on the kernel, KLdivergences.jl:11-18):
+    -> (d variance, d scales[D]) of -GaussianKL by reverse-mode AD, K = kernel_matrix(X, X) + jitter I"""
+    D = X.shape[1]
+    s = torch.tensor(np.broadcast_to(np.asarray(scale, dtype=np.float64), (D,)).copy(), requires_grad=True)
+    v = torch.tensor(float(variance), dtype=torch.float64, requires_grad=True)
+    Xt = torch.tensor(np.asarray(X, dtype=np.float64))
+    K = kernel_matrix(kind, Xt, Xt, s, v) + jitter * torch.eye(len(X), dtype=torch.float64)
+    Lk = torch.linalg.cholesky(K)
+    S = torch.tensor(np.asarray(Sigma, dtype=np.float64))
+    d = torch.tensor(np.asarray(mu, dtype=np.float64) - np.asarray(mu0, dtype=np.float64))
+    kl = 0.5 * (2 * torch.log(torch.diagonal(Lk)).sum() - torch.logdet(S) + torch.trace(torch.cholesky_solve(S, Lk))
+                + (d @ torch.cholesky_solve(d[:, None], Lk))[0] - len(X))
+    (-kl).backward()
+    return v.grad.item(), s.grad.numpy().copy()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # The augmented logistic-softmax bound, written down from the paper (Galy-Fajou, Wenzel, Donner, Opper: "Multi-Class Gaussian Process
 # Classification Made Conjugate", 2019), NOT from src/likelihood/logisticsoftmax.jl or from the oracle:

@@ -31,7 +31,13 @@ def env(built):
     return dict(AGP=AGP, capi=capi, R=R)
 
 
-def _case(env, likname, N, D=3, seed=3, optimiser=False, mean=None):
+KERNELS = {"sqexponential": "SqExponentialKernel", "matern52": "Matern52Kernel", "matern32": "Matern32Kernel",
+           "exponential": "ExponentialKernel"}
+
+
+def _case(env, likname, N, D=3, seed=3, optimiser=False, mean=None, kind="sqexponential", scale=2.0):
+    """kind: a KERNELS key; scale: a number (ScaleTransform) or D numbers (ARDTransform); mean: None, a number (ConstantMean) or
+    N numbers (EmpiricalMean).  The kernel is 1.5 * kind o transform on both sides."""
     from _vgp_ref import VGPRef
 
     AGP, R = env["AGP"], env["R"]
@@ -39,10 +45,13 @@ def _case(env, likname, N, D=3, seed=3, optimiser=False, mean=None):
     X = rng.random((N, D))
     f = np.sin(3 * X[:, 0]) + X[:, 1] ** 2 - 0.7
     y = labels(likname, f, X, rng)
-    k = 1.5 * (AGP.SqExponentialKernel() @ AGP.ScaleTransform(2.0))
+    tr = AGP.ScaleTransform(scale) if np.isscalar(scale) else AGP.ARDTransform(scale)
+    k = 1.5 * (getattr(AGP, KERNELS[kind])() @ tr)
     model = AGP.VGP(X, y, k, agp_lik(AGP, likname), AGP.AnalyticVI(), optimiser=optimiser, mean=mean)
     lr = oracle_lik(R, likname)
-    ref = VGPRef(R.Kernel("sqexponential", 2.0, 1.5), lr, X, mu0=None if mean is None else np.full(N, mean))
+    mu0 = None if mean is None else np.full(N, mean) if np.isscalar(mean) else np.asarray(mean, dtype=np.float64)
+    rscale = scale if np.isscalar(scale) else np.asarray(scale, dtype=np.float64).copy()
+    ref = VGPRef(R.Kernel(kind, rscale, 1.5), lr, X, mu0=mu0)
     return X, R.treat_labels(y, lr), model, ref
 
 

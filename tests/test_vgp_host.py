@@ -102,3 +102,110 @@ def test_flag_in_header_and_binding():
     h = open(os.path.join(ROOT, "include", "agp_hip.h")).read()
     assert re.search(r"AGP_FLAG_FULL = 2", h)
     assert capi.FLAG_FULL == 2
+
+
+# ---- the generalised hyper-gradient and the prior mean of the restatement ------------------------------------------------------
+HKINDS = ["sqexponential", "matern52", "matern32"]
+
+
+def _trained(likname, kind, scale, N=40, seed=4, mu0=None, steps=3):
+    rng = np.random.default_rng(seed)
+    X = rng.random((N, 3))
+    f = np.sin(3 * X[:, 0]) + X[:, 1] ** 2 - 0.7
+    lik = oracle_lik(R, likname)
+    y = R.treat_labels(labels(likname, f, X, rng), lik)
+    ref = VGPRef(R.Kernel(kind, scale, 1.5), lik, X, mu0=mu0)
+    for _ in range(steps):
+        ref.step(y)
+    return X, y, ref
+
+
+@pytest.mark.parametrize("kind", HKINDS)
+@pytest.mark.parametrize("ard", [False, True])
+def test_hyper_grad_matches_autograd(kind, ard):
+    from _torch_elbo import neg_kl_hypergrad
+
+    scale = np.array([1.3, 2.2, 0.7]) if ard else 2.0
+    X, y, ref = _trained("logistic", kind, scale, mu0=np.linspace(-0.3, 0.4, 40))
+    dv, ds = ref.hyper_grad(0)
+    av, as_ = neg_kl_hypergrad(kind, X, scale, 1.5, ref.mu[0], ref.mu0[0], ref.Sigma[0])
+    assert ds.shape == (3,)
+    assert abs(dv - av) < 1e-10 * max(1.0, abs(av)), (dv, av)
+    assert np.max(np.abs(ds - as_)) < 1e-10 * max(1.0, np.max(np.abs(as_))), (ds, as_)
+
+
+def test_hyper_grad_se_scalar_is_the_closed_form():
+    """SE with a ScaleTransform: d variance = sum(G o K~) / variance, d s = -s sum(G o K~ o d2), K~ = K - jitt I (the form the
+    restatement had before it took any kernel)"""
+    X, y, ref = _trained("logistic", "sqexponential", 2.0, mu0=np.full(40, 0.2))
+    G = ref.kl_grad_K(0)
+    Kb = ref.K - 1e-4 * np.eye(len(X))
+    d2 = np.sum((X[:, None, :] - X[None, :, :]) ** 2, axis=-1)
+    dv, ds = ref.hyper_grad(0)
+    assert dv == pytest.approx(float(np.sum(G * Kb) / 1.5), rel=1e-12)
+    assert float(np.sum(ds)) == pytest.approx(float(np.sum(G * Kb * (-2.0 * d2))), rel=1e-12)
+
+
+def test_exponential_hyper_grad_is_refused():
+    X, y, ref = _trained("logistic", "exponential", 2.0, steps=1)
+    with pytest.raises(ValueError):
+        ref.hyper_grad(0)
+
+
+@pytest.mark.parametrize("likname", ["logistic", "logisticsoftmax"])
+def test_step_eta1_carries_the_prior_mean(likname):
+    """natural_gradient!(::VarLatent): eta1 = grad_E_mu + K \\ mu0, checked with a direct solve"""
+    rng = np.random.default_rng(8)
+    mu0 = 0.5 * rng.standard_normal(40)
+    X, y, ref = _trained(likname, "matern52", 1.7, mu0=mu0, steps=2)
+    ref.step(y)
+    g1 = R.grad_E_mu(ref.lik, y, ref.lv)  # the local variables of this step
+    K = R.Kernel("matern52", 1.7, 1.5).matrix(X) + 1e-4 * np.eye(len(X))
+    for k in range(ref.nl):
+        want = g1[k] + np.linalg.solve(K, mu0)
+        assert np.max(np.abs(ref.eta1[k] - want)) < 1e-9 * np.max(np.abs(want))
+        assert np.max(np.abs(ref.mu0[k] - mu0)) == 0.0
+
+
+def test_every_latent_owns_its_kernel_and_is_stepped():
+    """latentgp.jl:34-36: a deep copy of the kernel per latent; the hyper step moves each with that latent's own gradient"""
+    X, y, ref = _trained("logisticsoftmax", "sqexponential", np.array([1.5, 2.5, 1.0]), steps=1)
+    assert len({id(k) for k in ref.kernels}) == 3
+    grads = [ref.hyper_grad(k) for k in range(3)]
+    ref.hyper_step(R.Adam(0.01))
+    for k in range(3):
+        ker = ref.kernels[k]
+        # the first ADAM step moves each log parameter by eta * sign(gradient)
+        assert np.log(ker.sigma2 / 1.5) == pytest.approx(0.01 * np.sign(grads[k][0]), rel=1e-6)
+        assert np.allclose(np.log(ker.scale / np.array([1.5, 2.5, 1.0])), 0.01 * np.sign(grads[k][1]), rtol=1e-6)
+    assert grads[1][0] != grads[0][0] and not np.array_equal(ref.Ks[1], ref.Ks[0])
+
+
+def test_restatement_keeps_the_se_latent0_trajectory():
+    """The hyper trajectory of SE with a scalar scale (what test_vgp_hyper_trajectory compares with) through the per-latent
+    restatement equals the one of the single-kernel form: variance, scale and ELBO trace after 8 iterations"""
+    X, y, ref = _trained("logistic", "sqexponential", 2.0, N=50, steps=0)
+    el = []
+    ref.train(y, 8, opt=R.Adam(0.01), callback=lambda r: el.append(r.elbo(y)))
+    # the single-kernel form, inline: the same loop with the SE closed form on one shared K
+    ker = R.Kernel("sqexponential", 2.0, 1.5)
+    o = VGPRef(ker, R.LogisticLikelihood(), X)
+    opt, st, el2 = R.Adam(0.01), [None, None], []
+    for it in range(8):
+        o.step(y)
+        el2.append(o.elbo(y))
+        if it >= 3 and it + 1 != 8:
+            G = o.kl_grad_K(0)
+            Kb = o.K - 1e-4 * np.eye(len(X))
+            d2 = np.sum((X[:, None, :] - X[None, :, :]) ** 2, axis=-1)
+            k0 = o.kernels[0]
+            gv, gs = float(np.sum(G * Kb) / k0.sigma2), float(np.sum(G * Kb * (-k0.scale * d2)))
+            st = [opt.init(np.zeros(1)), opt.init(np.zeros(1))] if st[0] is None else st
+            st[0], dv = opt.apply(st[0], np.array([k0.sigma2 * gv]))
+            st[1], ds = opt.apply(st[1], np.array([k0.scale * gs]))
+            k0.sigma2 = float(np.exp(np.log(k0.sigma2) + dv[0]))
+            k0.scale = float(np.exp(np.log(k0.scale) + ds[0]))
+            o.refresh_K()
+    assert ref.kernel.sigma2 == pytest.approx(o.kernels[0].sigma2, rel=1e-12)
+    assert ref.kernel.scale == pytest.approx(o.kernels[0].scale, rel=1e-12)
+    assert np.allclose(el, el2, rtol=1e-12, atol=0)
