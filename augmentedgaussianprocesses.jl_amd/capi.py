@@ -31,6 +31,7 @@ OPT_ADAM, OPT_DESCENT, OPT_MOMENTUM = 0, 1, 2  # agp_svgp_hyper_rule
 ELBO_CORRECTED, ELBO_REFERENCE = 0, 1
 FLAG_STALE_K = 1  # reference_compat_stale_K
 FLAG_FULL = 2  # the full model VGP (kappa = I, m = N): agp_svgp_desc.flags, include/agp_hip.h
+FLAG_EXACT = 4  # exact GP regression GP(X, y, kernel) with Analytic(), together with FLAG_FULL (gp.py)
 SHARD_LATENT, SHARD_BATCH = 0, 1
 COMM_ID_BYTES = 128
 # int32_t (*agp_allreduce_fn)(void* user, void* buf, int64_t count, int32_t dtype, void* hip_stream)

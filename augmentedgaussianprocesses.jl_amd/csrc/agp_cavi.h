@@ -793,6 +793,20 @@ __global__ void k_noise_partial(int64_t B, const T* __restrict__ y, const int64_
   s = block_sum<double>(s, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
+// one ADAM ascent step on log sigma2 with the gradient g = d objective / d log sigma2 (state adam = [m, v, t]; Optimisers.ADAM):
+// shared by the likelihood's noise step below and the exact GP's (k_gp_finish)
+template <typename T>
+__device__ __forceinline__ void noise_adam_ascent(double g, double eta, double b1, double b2, double eps, double* __restrict__ adam,
+                                                  T* __restrict__ sigma2) {
+  const double s2 = (double)sigma2[0];
+  const double t = adam[2] + 1.0;
+  const double m = b1 * adam[0] + (1.0 - b1) * g, v = b2 * adam[1] + (1.0 - b2) * g * g;
+  adam[0] = m;
+  adam[1] = v;
+  adam[2] = t;
+  const double mh = m / (1.0 - pow(b1, t)), vh = v / (1.0 - pow(b2, t));
+  sigma2[0] = (T)exp(log(s2) + eta * mh / (sqrt(vh) + eps));
+}
 // S = sum of part[0 .. nparts) ; Bn_ptr (nullable): the batch size as a device double (after an all-reduce over the shards)
 template <typename T>
 __global__ void k_noise_finish(int nparts, const double* __restrict__ part, double Bn, const double* __restrict__ Bn_ptr, double eta,
@@ -803,14 +817,7 @@ __global__ void k_noise_finish(int nparts, const double* __restrict__ part, doub
   s = block_sum<double>(s, red);
   if (threadIdx.x != 0) return;
   const double s2 = (double)sigma2[0], n = Bn_ptr ? Bn_ptr[0] : Bn;
-  const double g = (s / s2 - n) / 2.0;
-  const double t = adam[2] + 1.0;
-  const double m = b1 * adam[0] + (1.0 - b1) * g, v = b2 * adam[1] + (1.0 - b2) * g * g;
-  adam[0] = m;
-  adam[1] = v;
-  adam[2] = t;
-  const double mh = m / (1.0 - pow(b1, t)), vh = v / (1.0 - pow(b2, t));
-  sigma2[0] = (T)exp(log(s2) + eta * mh / (sqrt(vh) + eps));
+  noise_adam_ascent<T>((s / s2 - n) / 2.0, eta, b1, b2, eps, adam, sigma2);
 }
 template <typename T>
 __global__ void k_gauss_grads(int64_t B, T rho, const T* __restrict__ y, const int64_t* __restrict__ idx,
@@ -1752,6 +1759,88 @@ __global__ void k_vgp_diag(int64_t m, int64_t mp, const T* __restrict__ Sigma, c
   if (i >= m) return;
   mf[i] = mu[i];
   vf[i] = Sigma[i * mp + i];
+}
+
+// ---- exact GP (AGP_FLAG_FULL | AGP_FLAG_EXACT: GP(X, y, kernel) with Analytic(), src/models/GP.jl, src/inference/analytic.jl) ---
+// The factorisation input La = Sigma = K + sigma2 I (utils.jl:108; K already carries jitt I and the identity in its padding), with
+// sigma2 read from the device likelihood word, and -- when r is given -- r = y - mu0 (analytic.jl:40) for the [r' ; 0] extension row
+// of the factorisation.  Also materialises Sigma itself (r = NULL, sigma2 = the recorded one).  Grid (mp / 256, mp): one row per blockIdx.y.
+template <typename T>
+__global__ __launch_bounds__(256) void k_gp_shift(int64_t m, int64_t mp, const T* __restrict__ K, const T* __restrict__ sigma2,
+                                                  const T* __restrict__ y, const T* __restrict__ mu0, T* __restrict__ La,
+                                                  T* __restrict__ r, T* __restrict__ s2_used) {
+  const int64_t i = blockIdx.y;
+  const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (j >= mp) return;
+  const T s2 = sigma2[0];
+  La[i * mp + j] = K[i * mp + j] + (i == j && i < m ? s2 : T(0));
+  if (r && i == 0) r[j] = j < m ? y[j] - (mu0 ? mu0[j] : T(0)) : T(0);
+  if (s2_used && i == 0 && j == 0) s2_used[0] = s2;  // (the sigma2 this Sigma was formed with: Sigma itself is materialised later)
+}
+
+// k_gp_finish, stage 1: the slices of k_vgp_colstats summed into alpha = L^-T (L^-1 r) = Sigma^-1 r and diag Sigma^-1 (column sums
+// of squares of L^-1), and per-block partial sums of the six scalars of log p and the noise gradient:
+//   part[q][block], q = 0: alpha' alpha  1: tr Sigma^-1  2: r' alpha  3: sum log L_ii  4: mu0' alpha  5: ||L^-1 mu0||^2
+// (4 and 5 only for the reference's y' Sigma^-1 y with a prior mean: m0v = L^-1 mu0 is then given)
+template <typename T>
+__global__ void k_gp_partial(int64_t m, int64_t mp, int ns, const T* __restrict__ p0, const T* __restrict__ p1,
+                             const T* __restrict__ r, const T* __restrict__ Dg, const T* __restrict__ mu0, const T* __restrict__ m0v,
+                             T* __restrict__ alpha, T* __restrict__ dinv, double* __restrict__ part) {
+  __shared__ double red[16];
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  double q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (i < m) {
+    T a = T(0), b = T(0);
+    for (int s = 0; s < ns; ++s) {
+      a += p0[s * mp + i];
+      b += p1[s * mp + i];
+    }
+    alpha[i] = b;
+    dinv[i] = a;
+    q[0] = (double)b * (double)b;
+    q[1] = (double)a;
+    q[2] = (double)r[i] * (double)b;
+    q[3] = log((double)Dg[(i / TILE) * TILE * TILE + (i % TILE) * (TILE + 1)]);
+    if (m0v) {
+      q[4] = (double)mu0[i] * (double)b;
+      q[5] = (double)m0v[i] * (double)m0v[i];
+    }
+  } else if (i < mp) {
+    alpha[i] = T(0);
+    dinv[i] = T(0);
+  }
+  for (int k = 0; k < 6; ++k) {
+    const double v = block_sum<double>(q[k], red);
+    if (threadIdx.x == 0) part[k * gridDim.x + blockIdx.x] = v;
+  }
+}
+
+// stage 2 (one workgroup): the partial sums in block order, then
+//   log p = -(Q + 2 sum log L_ii + N log 2 pi) / 2   (log_py, GP.jl:87-92), Q = r' alpha, or y' Sigma^-1 y = r' alpha + 2 mu0' alpha +
+//           ||L^-1 mu0||^2 in the reference's form (G3)
+//   out = [alpha' alpha, tr Sigma^-1, r' alpha, sum log L_ii, log p]
+// and, with adam != NULL, the noise step of analytic.jl:42-49: g = (alpha' alpha - tr Sigma^-1) / 2 (the reference: ||alpha||_2 in
+// place of alpha' alpha, G2), one ADAM ascent step on log sigma2 with the gradient g sigma2
+template <typename T>
+__global__ void k_gp_finish(int nparts, const double* __restrict__ part, int64_t n, int ref_norm, double eta, double* __restrict__ adam,
+                            T* __restrict__ sigma2, double* __restrict__ out) {
+  __shared__ double red[16];
+  double q[6];
+  for (int k = 0; k < 6; ++k) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nparts; b += blockDim.x) s += part[k * nparts + b];
+    q[k] = block_sum<double>(s, red);
+  }
+  if (threadIdx.x != 0) return;
+  const double quad = q[2] + 2.0 * q[4] + q[5];
+  out[0] = q[0];
+  out[1] = q[1];
+  out[2] = q[2];
+  out[3] = q[3];
+  out[4] = -(quad + 2.0 * q[3] + (double)n * log(2.0 * 3.14159265358979323846)) / 2.0;
+  if (!adam) return;
+  const double g = ((ref_norm ? sqrt(q[0]) : q[0]) - q[1]) / 2.0;
+  noise_adam_ascent<T>(g * (double)sigma2[0], eta, 0.9, 0.999, 1e-8, adam, sigma2);
 }
 
 }  // namespace agp

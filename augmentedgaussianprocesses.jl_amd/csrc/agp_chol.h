@@ -1042,6 +1042,10 @@ struct SafeSrc {
   int64_t mz = 0, ldz = 0, Dz = 0;
   int kkind = 0;
   T kvariance = T(1), kjitter = T(0);  // kvariance < 0: read kscales[Dz]
+  // gpK: the exact GP's Sigma = K + sigma2 I from K (leading dimension ld, jitter and padding included) and the device word of
+  // sigma2 (gps2), identity in the padding (i, j >= mz); the [r' ; 0] extension row comes from eta1[0] as above
+  const T* gpK = nullptr;
+  const T* gps2 = nullptr;
   // split launch (k_chol_dag ROLE 1 / 2): the chain kernel(s) of the launch have counted themselves out when *chain_done >= chain_want
   const int32_t* chain_done = nullptr;
   int32_t chain_want = 0;
@@ -1143,6 +1147,12 @@ __device__ __forceinline__ bool chol_safe_body(const CholBatch<T>& bt, const Saf
           v = var * safe_kernel_base<T>(src.kkind, d2) + (i == j ? src.kjitter : T(0));
         }
         A[i * ld + j] = v;
+      }
+    } else if (src.gpK) {
+      const T s2 = src.gps2[0];
+      for (int64_t e = g0; e < n * n; e += gsz) {
+        const int64_t i = e / n, j = e % n;
+        A[i * ld + j] = src.gpK[i * ld + j] + (i == j && i < src.mz ? s2 : T(0));
       }
     } else {
       for (int64_t e = g0; e < n * n; e += gsz) A[(e / n) * ld + (e % n)] = T(-2) * src.eta2[q][(e / n) * ld + (e % n)];

@@ -96,15 +96,17 @@ def save_trained_model(filename: str, model: SVGP) -> None:
         raise RuntimeError("the model has no device state yet: train it first")
     model._pull_hypers()
     model._pull_lik_state()
+    from .gp import GP
     from .vgp import VGP
 
     mo = isinstance(model, MOSVGP)
-    full = isinstance(model, VGP)
+    exact = isinstance(model, GP)
+    full = isinstance(model, VGP) or exact
     inf = model.inference
     opt = inf.optimiser or RobbinsMonro()
     meta = {
         # a VGP is rebuilt as a VGP (prior K + jitt I on its own training set), never as an SVGP with Z = X
-        "class": "MOSVGP" if mo else "VGP" if full else "SVGP",
+        "class": "MOSVGP" if mo else "GP" if exact else "VGP" if full else "SVGP",
         "kernels": [_kernel_spec(k) for k in model.kernels],
         "likelihood": [_lik_spec(l) for l in model.likelihood.likelihoods] if mo else _lik_spec(model.likelihood),
         "stochastic": bool(inf.stoch), "batchsize": int(inf.batchsize), "n_iter": int(inf.n_iter),
@@ -124,8 +126,10 @@ def save_trained_model(filename: str, model: SVGP) -> None:
     model._chk(capi.lib().agp_svgp_get_opt_state(model._h, C.byref(n_opt)))
     arrays = {"meta": np.array(json.dumps(meta)), "n_opt": np.array(n_opt.value)}
     for l in range(model.n_latent):
-        mu, Sig, e1, e2 = model.get_state(l)
-        arrays[f"eta1_{l}"], arrays[f"eta2_{l}"], arrays[f"Z_{l}"] = e1, e2, model.Zs[l]
+        arrays[f"Z_{l}"] = model.Zs[l]
+        if not exact:  # (a GP's posterior follows from the kernel, sigma2 and y: it is rebuilt on load)
+            mu, Sig, e1, e2 = model.get_state(l)
+            arrays[f"eta1_{l}"], arrays[f"eta2_{l}"] = e1, e2
     if mo:
         arrays["A"] = model.get_A()
     if model.k_opt is not None:
@@ -174,6 +178,14 @@ def load_trained_model(filename: str, *, device=None):
         # (files written before round 6 carry no "a_opt": the model's default ADAM(0.01), MOSVGP.jl:42, as for a fresh model)
         a_opt = _opt_from(meta["a_opt"]) if "a_opt" in meta else None
         model = MOSVGP(kernels, [_lik_from(d) for d in meta["likelihood"]], inf, Zs, A=g["A"], Aoptimiser=a_opt, **kw)
+    elif meta["class"] == "GP":
+        from .gp import GP
+
+        ld = meta["likelihood"]
+        model = GP(Zs[0], g["vgp_y"], kernels[0], noise=ld["sigma2"],
+                   opt_noise=ADAM(ld["noise_eta"]) if ld.get("noise_eta") else False, optimiser=kw["optimiser"] or False,
+                   atfrequency=kw["atfrequency"], mean=mean, elbo_mode=meta["elbo_mode"], T=T, device=device, _initial_train=False)
+        inf = model.inference  # (Analytic(), the GP's own)
     elif meta["class"] == "VGP":
         from .vgp import VGP
 
@@ -184,7 +196,8 @@ def load_trained_model(filename: str, *, device=None):
     inf.n_iter = meta["n_iter"]
     h = model._ensure_handle(max(meta["batchsize"], 1))
     for l in range(nl):
-        model.set_state(l, g[f"eta1_{l}"], g[f"eta2_{l}"])
+        if f"eta1_{l}" in g.files:
+            model.set_state(l, g[f"eta1_{l}"], g[f"eta2_{l}"])
     model._chk(capi.lib().agp_svgp_set_opt_state(h, int(g["n_opt"])))
     for l in range(nl):
         if f"kopt_m_{l}" in g.files and model.k_opt is not None:
@@ -201,5 +214,7 @@ def load_trained_model(filename: str, *, device=None):
         a = torch.as_tensor(g["lsm_alpha"], dtype=model.tdtype, device=model._dev()).contiguous()
         model._chk(capi.lib().agp_svgp_set_lsm_alpha(h, C.c_void_p(a.data_ptr()), a.numel()))
         model._chk(capi.lib().agp_ctx_sync(model._ctx))
+    if meta["class"] == "GP":
+        model._bind()
     model.trained = True
     return model

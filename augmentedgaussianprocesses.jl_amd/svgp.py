@@ -122,6 +122,23 @@ class AnalyticVI:
         return f"Analytic{' Stochastic' if self.stoch else ''} Variational Inference"
 
 
+class Analytic:
+    """Analytic(; ϵ=1e-5) -- the closed-form posterior of exact GP regression (analytic.jl:1-30); ϵ is not read.  Not a variational
+    inference: only GP takes it (gp.py); SVGP, MOSVGP and VGP refuse it as the reference does."""
+
+    def __init__(self, epsilon: float = 1e-5):
+        self.eps = float(epsilon)
+        self.n_iter = 0
+        self.stoch = False  # (the attributes train_ reads, with their full-batch values)
+        self.batchsize = 0
+        self.rho = 1.0
+        self.HyperParametersUpdated = False
+        self.optimiser = None
+
+    def __repr__(self):
+        return "Analytic Inference"
+
+
 def AnalyticSVI(nMinibatch: int, eps: float = 1e-5, optimiser: Optional[RobbinsMonro] = None) -> AnalyticVI:
     """AnalyticSVI(nMinibatch; ϵ=1e-5, optimiser=RobbinsMonro())  analyticVI.jl:48-52."""
     opt = optimiser if optimiser is not None else RobbinsMonro()
@@ -149,7 +166,8 @@ class SVGP:
                  mean=None, Zoptimiser=False, T=np.float64, device: Optional[int] = None, seed: Optional[int] = None,
                  elbo_mode: str = "corrected", latent_slice: Optional[tuple] = None,
                  reference_compat_stale_K: bool = False, jitter: Optional[float] = None):
-        if not isinstance(inference, AnalyticVI):
+        exact = (getattr(self, "_desc_flags", 0) & capi.FLAG_EXACT) != 0  # (GP: Analytic() on a full handle, gp.py)
+        if not (isinstance(inference, Analytic) if exact else isinstance(inference, AnalyticVI)):
             raise TypeError("The inference object should be of type `VariationalInference` : either `AnalyticVI` or "
                             "`NumericalVI`")  # SVGP.jl:45-47 (only AnalyticVI exists on this path)
         # inside one train! the reference keeps the Cholesky of K_ZZ of the first iteration even after
@@ -684,8 +702,9 @@ def train_(model: SVGP, X, y, iterations: int = 100, *, callback: Optional[Calla
 
 
 def _hyper_step_guard(model):
-    """update_hyperparameters! with a non-zero prior mean: the reference's prior-mean update cannot run (see SVGP.__init__)"""
-    if model.mean is not None:
+    """update_hyperparameters! with a non-zero prior mean: the reference's prior-mean update cannot run (see SVGP.__init__).  (A GP
+    takes no prior-mean step at all: its gradient is `nothing` there, autotuning.jl:5-37.)"""
+    if model.mean is not None and not getattr(model, "_mean_fixed", False):
         raise NotImplementedError("a non-zero prior mean together with hyper-parameter optimisation is not wired: the "
                                   "reference's prior-mean update (autotuning.jl:104-106) is broken; pass optimiser=False, "
                                   "Zoptimiser=False or mean=None")

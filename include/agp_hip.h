@@ -106,7 +106,7 @@ enum { AGP_ELBO_CORRECTED = 0, AGP_ELBO_REFERENCE = 1 };
  * src/functions/ELBO.jl:15-21).  With the flag a hyper step leaves the step-side matrices (L, inv(K), K\mu0) as they are and
  * only an explicit agp_svgp_refresh_K (what the host calls where train! starts and ends) recomputes them; without it
  * (default) K is refreshed before the next step. */
-enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2 };
+enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4 };
 /* AGP_FLAG_FULL: the handle is the full (non-sparse) model VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85 --
  * one latent of dimension N per n_latent(likelihood), kappa = I, prior K + jitt I on the training inputs themselves.  Create it with
  * m = max_batch = N, stochastic = 0, dtype AGP_F64 (other types: AGP_ERR_UNSUPPORTED); a Gaussian likelihood is refused with
@@ -124,6 +124,26 @@ enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2 };
  *   predict_f / predict_f_cov / predict_y / proba_y  the generic _predict_f with Zviews(m) = X (predictions.jl:25-50)
  * Refused with AGP_ERR_UNSUPPORTED, doing nothing: the phase entry points (step_local, lsm_*, step_stats, stats_ptr, step_global),
  * prefetch, batch sharding, every *_multi call, the online entry points, multi-output. */
+/* AGP_FLAG_EXACT (only together with AGP_FLAG_FULL): exact GP regression GP(X, y, kernel; noise, opt_noise) with Analytic()
+ * inference  src/models/GP.jl:37-92, src/inference/analytic.jl:36-51.  Float64, n_latent = 1, a Gaussian likelihood (lik.p0 = sigma2,
+ * lik.p1 = the ADAM rate of opt_noise or 0); anything else AGP_ERR_UNSUPPORTED.  elbo_mode AGP_ELBO_REFERENCE reproduces the
+ * reference's three defects (G1 no kernel gradient, G2 ||alpha||_2 in the noise gradient, G3 y in place of y - mu0 in log p).
+ *   cavi_step       idx = NULL, B = N, y = the targets (x is not read).  Sigma = K + sigma2 I (K + jitt I refreshed only when the
+ *                   kernel moved), alpha = Sigma \ (y - mu0), log p; then, with opt_noise, one ADAM ascent step on log sigma2 with
+ *                   the gradient (alpha' alpha - tr Sigma^-1) sigma2 / 2.  No host synchronisation.  rho is ignored.
+ *   elbo            log p = -((y - mu0)' Sigma^-1 (y - mu0) + log det Sigma + N log 2 pi) / 2 of the stored posterior (GP.jl:87-92);
+ *                   x, idx, B, rho and fresh_local are not read; y binds the targets when no step has been taken yet (a reloaded
+ *                   model), else it is not read either
+ *   refresh_K       compute_Ks + post_step!: K, then Sigma and alpha with the current sigma2 (what train! does where it ends)
+ *   get_state       mu <- alpha, sigma <- Sigma; eta1 / eta2 must be NULL (else AGP_ERR_UNSUPPORTED).  set_state: AGP_ERR_UNSUPPORTED
+ *   get_lik_param   sigma2 (synchronises)
+ *   hyper_step / hypergrad / hyper_apply  d log p / d theta = tr((alpha alpha' - Sigma^-1) dK/dtheta) / 2 at the Sigma of the
+ *                   last step.  The reference mode: hypergrad returns zeros, and neither hyper_step nor hyper_apply (whatever
+ *                   gradient the caller supplies) steps the kernel or its optimiser state.  ExponentialKernel: AGP_ERR_UNSUPPORTED;
+ *                   no dZ
+ *   predict_f / predict_f_cov / predict_y / proba_y  mu* = K*n alpha, var* = k** + jitt - diag(K*n Sigma^-1 Kn*) (predictions.jl:6-23);
+ *                   proba_y adds sigma2
+ * Refused with AGP_ERR_UNSUPPORTED on top of AGP_FLAG_FULL's list: get_matrix, elbo_enqueue, elbo_terms. */
 
 /* matrices readable through agp_svgp_get_matrix (for parity tests and the shim's state export) */
 enum {

@@ -76,6 +76,7 @@ struct SvgpDesc
 end
 const AGP_FLAG_STALE_K = Int32(1)
 const AGP_FLAG_FULL = Int32(2)     # VGP: the full model, kappa = I, m = N, Z = the training inputs (agp_hip.h)
+const AGP_FLAG_EXACT = Int32(4)    # GP: exact regression with Analytic(), together with AGP_FLAG_FULL (agp_hip.h)
 const AGP_SHARD_LATENT, AGP_SHARD_BATCH = Int32(0), Int32(1)
 
 struct AGPError <: Exception
@@ -168,22 +169,27 @@ mutable struct HipModel{T,M<:AGP.AbstractGPModel{T}}
 end
 
 is_mo(hm::HipModel) = hm.model isa AGP.MOSVGP
-is_full(hm::HipModel) = hm.model isa AGP.VGP
+is_full(hm::HipModel) = hm.model isa Union{AGP.VGP,AGP.GP}
+is_exact(hm::HipModel) = hm.model isa AGP.GP
+# the latents of a model: a tuple / vector of them (SVGP, MOSVGP, VGP: `m.f`), or the single LatentGP of a GP (`f::LatentGP`, GP.jl:28)
+latents(m::AGP.AbstractGPModel) = m.f
+latents(m::AGP.GP) = (m.f,)
 # the inputs the handle's "inducing points" are: Z of a sparse latent, the training inputs of a VGP (Zviews(m::VGP), VGP.jl:90)
 zview(hm::HipModel, gp) = is_full(hm) ? AGP.input(hm.model.data) : AGP.Zview(gp)
 nlat(hm::HipModel) = length(hm.latent_range)
 
 """
     HipModel(model::Union{SVGP,MOSVGP}; device=AMDGPU.device_id()-1, reference_compat_stale_K=false,
-             latent_range=1:length(model.f))
+             latent_range=1:length(latents(model)))
 
 Wrap a reference model.  Nothing is allocated on the device until data arrive (`train!`, `ELBO`, `predict_*`).
 """
 function HipModel(model::M; reference_compat_stale_K::Bool=false,
-                  latent_range::UnitRange{Int}=1:length(model.f)) where {T,M<:AGP.AbstractGPModel{T}}
-    model isa Union{SVGP,AGP.MOSVGP,AGP.VGP} || error("only SVGP / MOSVGP / VGP run on the HIP path")
-    model isa AGP.VGP && T != Float64 && error("VGP runs in Float64 only on the HIP path")
-    AGP.inference(model) isa AnalyticVI || error("The inference object should be of type `AnalyticVI`")   # SVGP.jl:45-47
+                  latent_range::UnitRange{Int}=1:length(latents(model))) where {T,M<:AGP.AbstractGPModel{T}}
+    model isa Union{SVGP,AGP.MOSVGP,AGP.VGP,AGP.GP} || error("only SVGP / MOSVGP / VGP / GP run on the HIP path")
+    model isa Union{AGP.VGP,AGP.GP} && T != Float64 && error("VGP / GP run in Float64 only on the HIP path")
+    AGP.inference(model) isa Union{AnalyticVI,AGP.Analytic} ||
+        error("The inference object should be of type `AnalyticVI`")   # SVGP.jl:45-47
     return HipModel{T,M}(model, C_NULL, C_NULL, C_NULL, AGP_SHARD_LATENT, latent_range, 0, nothing, nothing, 0, nothing,
                          reference_compat_stale_K, Int32(0), Int32(1), Any[])
 end
@@ -215,7 +221,7 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
     old = hm.h == C_NULL ? nothing : (pull_posterior!(hm); opt_state(hm))
     hm.h == C_NULL || ccall((:agp_svgp_destroy, libagp), Int32, (Ptr{Cvoid},), hm.h)
     inf = AGP.inference(model)
-    gp1 = model.f[first(hm.latent_range)]
+    gp1 = latents(model)[first(hm.latent_range)]
     D = length(first(zview(hm, gp1)))
     m = AGP.dim(gp1)
     is_full(hm) && (maxbatch = m)                            # a VGP steps on its whole training set (idx = NULL, B = N = m)
@@ -225,12 +231,13 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
     ld = is_mo(hm) ? LikDesc(4, 1, 0.0, 0.0) : lik_desc(AGP.likelihood(model))
     desc = SvgpDesc(T == Float64 ? 0 : 1, nlat(hm), first(hm.latent_range) - 1, stoch ? 1 : 0, m, D, maxbatch, ld, 0.0,
                     stoch ? rm.κ : 0.51, stoch ? rm.τ : 1.0, 0,
-                    (hm.stale_K ? AGP_FLAG_STALE_K : Int32(0)) | (is_full(hm) ? AGP_FLAG_FULL : Int32(0)))
+                    (hm.stale_K ? AGP_FLAG_STALE_K : Int32(0)) | (is_full(hm) ? AGP_FLAG_FULL : Int32(0)) |
+                    (is_exact(hm) ? AGP_FLAG_EXACT : Int32(0)))
     h = Ref{Ptr{Cvoid}}()
     check(ctx, ccall((:agp_svgp_create, libagp), Int32, (Ptr{Cvoid}, Ref{SvgpDesc}, Ptr{Ptr{Cvoid}}), ctx, desc, h))
     hm.h, hm.maxbatch = h[], maxbatch
     for (i, q) in enumerate(hm.latent_range)
-        gp = model.f[q]
+        gp = latents(model)[q]
         kd, keep = kernel_desc(AGP.kernel(gp), D)
         GC.@preserve keep check(ctx, ccall((:agp_svgp_set_kernel, libagp), Int32, (Ptr{Cvoid}, Int32, Ref{KernelDesc}), hm.h, i - 1, kd))
         Zd = ROCArray{T}(reduce(hcat, zview(hm, gp)))       # D x m, point-major
@@ -245,7 +252,7 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
     if is_mo(hm)
         liks = collect(AGP.likelihood(model))
         lds = [lik_desc(l) for l in liks]
-        Q = length(model.f)
+        Q = length(latents(model))
         A = Matrix{Float64}(undef, length(liks), Q)          # model.A[t][j][q]; nf_per_task == 1 on this path
         for t in 1:length(liks), q in 1:Q
             A[t, q] = model.A[t][1][q]
@@ -291,8 +298,9 @@ opt_state(hm::HipModel) = (n = Ref{Int64}(); ccall((:agp_svgp_get_opt_state, lib
 
 # (μ, Σ, η₁, η₂) device -> the reference's VarPosterior (posterior.jl:21-27), e.g. at the end of train!
 function pull_posterior!(hm::HipModel{T}) where {T}
+    is_exact(hm) && return pull_gp_posterior!(hm)
     for (i, q) in enumerate(hm.latent_range)
-        gp = hm.model.f[q]
+        gp = latents(hm.model)[q]
         m = AGP.dim(gp)
         μ = ROCVector{T}(undef, m); η₁ = ROCVector{T}(undef, m)
         Σ = ROCMatrix{T}(undef, m, m); η₂ = ROCMatrix{T}(undef, m, m)
@@ -307,7 +315,7 @@ end
 # the reference's (η₁, η₂) -> device (a model trained on the CPU continues on the GPU)
 function push_posterior!(hm::HipModel{T}) where {T}
     for (i, q) in enumerate(hm.latent_range)
-        gp = hm.model.f[q]
+        gp = latents(hm.model)[q]
         η₁ = ROCArray{T}(AGP.nat1(gp)); η₂ = ROCArray{T}(Matrix(AGP.nat2(gp)))
         check(hm.ctx, ccall((:agp_svgp_set_state, libagp), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}), hm.h, i - 1, pointer(η₁), pointer(η₂)))
     end
@@ -317,12 +325,14 @@ end
 # kernel parameters / Z (device, after hyper steps) -> the reference objects; λ of Poisson / Heteroscedastic likewise
 function pull_hypers!(hm::HipModel{T}) where {T}
     for (i, q) in enumerate(hm.latent_range)
-        gp = hm.model.f[q]
-        (AGP.opt(gp) === nothing && AGP.Zopt(gp) === nothing) && continue
-        D = length(first(AGP.Zview(gp))); m = AGP.dim(gp)
+        gp = latents(hm.model)[q]
+        zopt = is_full(hm) ? nothing : AGP.Zopt(gp)          # (the inputs of a VGP / GP are never optimised)
+        (AGP.opt(gp) === nothing && zopt === nothing) && continue
+        D = length(first(zview(hm, gp))); m = AGP.dim(gp)
         σ² = Ref{Float64}(); sc = Vector{Float64}(undef, D)
         check(hm.ctx, ccall((:agp_svgp_get_kernel, libagp), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}, Ptr{Float64}), hm.h, i - 1, σ², sc))
         pull_kernel!(AGP.kernel(gp), σ²[], sc)
+        is_full(hm) && continue
         Zd = ROCMatrix{T}(undef, D, m)
         check(hm.ctx, ccall((:agp_svgp_get_Z, libagp), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64), hm.h, i - 1, pointer(Zd), D))
         Zh = Array(Zd)
@@ -342,7 +352,7 @@ function pull_hypers!(hm::HipModel{T}) where {T}
         l.σ² .= v[]
     end
     if is_mo(hm)
-        liks = AGP.likelihood(hm.model); Q = length(hm.model.f)
+        liks = AGP.likelihood(hm.model); Q = length(latents(hm.model))
         A = Matrix{Float64}(undef, Q, length(liks))          # row-major n_task x Q on the C side
         check(hm.ctx, ccall((:agp_svgp_get_A, libagp), Int32, (Ptr{Cvoid}, Ptr{Float64}), hm.h, A))
         for t in 1:length(liks), q in 1:Q
@@ -386,7 +396,7 @@ function update_parameters!(hm::HipModel{T}, idx, ρ::Real) where {T}
     hm.last_idx = idd
     B = idx === nothing ? hm.N : length(idx)
     idp = idd === nothing ? Ptr{Int64}(C_NULL) : pointer(idd)
-    st = if hm.comm == C_NULL && nlat(hm) == length(hm.model.f)
+    st = if hm.comm == C_NULL && nlat(hm) == length(latents(hm.model))
         ccall((:agp_svgp_cavi_step, libagp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int64, Float64),
               hm.h, pointer(hm.X), D, pointer(hm.y), idp, B, ρ)
     else
@@ -410,7 +420,8 @@ end
 
 # update_hyperparameters!(m, state, x, y) (autotuning.jl:86-140) on the minibatch of the last step
 function update_hyperparameters!(hm::HipModel; tied::Bool=false)
-    any(gp -> !(AGP.pr_mean(gp) isa AGP.ZeroMean), hm.model.f[hm.latent_range]) &&
+    # (a GP's prior mean is never stepped: its update_hyperparameters! has no prior-mean part, autotuning.jl:5-37)
+    !is_exact(hm) && any(gp -> !(AGP.pr_mean(gp) isa AGP.ZeroMean), latents(hm.model)[hm.latent_range]) &&
         error("a non-zero prior mean with hyper-parameter optimisation is not wired: the reference's own prior-mean update " *
               "(autotuning.jl:104-106 vs src/mean/constantmean.jl:31) cannot run")
     st = hm.comm == C_NULL && !tied ? ccall((:agp_svgp_hyper_step, libagp), Int32, (Ptr{Cvoid},), hm.h) :
@@ -465,7 +476,7 @@ function train!(hm::HipModel{T}, X::AbstractArray, y, iterations::Int=100; callb
     end
     check(hm.ctx, ccall((:agp_svgp_refresh_K, libagp), Int32, (Ptr{Cvoid},), hm.h))
     ρ = AGP.is_stochastic(model) ? N / B : 1.0
-    hyper_on = any(gp -> AGP.opt(gp) !== nothing || AGP.Zopt(gp) !== nothing, model.f)
+    hyper_on = any(gp -> AGP.opt(gp) !== nothing || (!is_full(hm) && AGP.Zopt(gp) !== nothing), latents(model))
     # minibatch of iteration `it` on the device: the reference's sample(1:N, B; replace=false) (training.jl:51-53), drawn in the
     # same order, one iteration ahead of its use so that the look-ahead can run next to the current step
     function draw(it)
@@ -478,8 +489,8 @@ function train!(hm::HipModel{T}, X::AbstractArray, y, iterations::Int=100; callb
         return device_indices(idx)
     end
     if AGP.verbose(model) > 0   # training.jl:35-38
-        @info "Starting training $model with $N samples, $(size(hm.Xd, 1)) features and $(length(model.f)) latent GP" *
-              (length(model.f) > 1 ? "s" : "")
+        @info "Starting training $model with $N samples, $(size(hm.Xd, 1)) features and $(length(latents(model))) latent GP" *
+              (length(latents(model)) > 1 ? "s" : "")
     end
     local_iter = 1
     # progress reporting of the reference (training.jl:46,71-90): ProgressMeter with (:iter, :ELBO); the ELBO is
@@ -491,6 +502,11 @@ function train!(hm::HipModel{T}, X::AbstractArray, y, iterations::Int=100; callb
     function report(it)
         prog === nothing && return
         (AGP.verbose(model) > 2 || it % 10 == 0) || return
+        if is_exact(hm)   # log p of a GP is read synchronously: an exact handle refuses agp_svgp_elbo_enqueue
+            AGP.verbose(model) == 2 && ProgressMeter.update!(prog, it - 1)
+            ProgressMeter.next!(prog; showvalues=[(:iter, it), (:ELBO, objective(hm))])
+            return
+        end
         tk = objective_enqueue(hm)
         if pending_elbo !== nothing
             elbo = objective_fetch(hm, pending_elbo[1])
@@ -622,8 +638,8 @@ mutable struct SideObjective{T}
 end
 
 function SideObjective(hm::HipModel{T}, max_eval_batch::Int; ring::Int=4) where {T}
-    (length(hm.model.f) == 1 && !is_mo(hm)) || error("SideObjective: single-latent SVGP models")
-    all(gp -> AGP.opt(gp) === nothing && AGP.Zopt(gp) === nothing, hm.model.f) ||
+    (length(latents(hm.model)) == 1 && !is_mo(hm) && !is_exact(hm)) || error("SideObjective: single-latent SVGP models")
+    all(gp -> AGP.opt(gp) === nothing && AGP.Zopt(gp) === nothing, latents(hm.model)) ||
         error("SideObjective: kernels and inducing points must be fixed (optimiser=false, Zoptimiser=false)")
     hm.h != C_NULL || error("SideObjective: the model has no device state yet")
     stream = AMDGPU.HIPStream()
@@ -634,7 +650,7 @@ function SideObjective(hm::HipModel{T}, max_eval_batch::Int; ring::Int=4) where 
         check(shadow.ctx, ccall((:agp_svgp_refresh_K, libagp), Int32, (Ptr{Cvoid},), shadow.h))
     end
     AMDGPU.synchronize(stream)
-    m = AGP.dim(hm.model.f[1])
+    m = AGP.dim(latents(hm.model)[1])
     slots = [(ROCVector{T}(undef, m), ROCMatrix{T}(undef, m, m), AMDGPU.HIP.HIPEvent(stream), AMDGPU.HIP.HIPEvent(stream)) for _ in 1:ring]
     return SideObjective{T}(hm, shadow, stream, slots, 0)
 end
@@ -1022,5 +1038,37 @@ for f in (:predict_f, :predict_y, :proba_y)
     end
 end
 objective(model::HipVGP, state::HipModel, y=nothing) = objective(state)
+
+# GP{T,<:GaussianLikelihood,<:Analytic} (src/models/GP.jl): exact regression on a handle created with AGP_FLAG_FULL | AGP_FLAG_EXACT.
+# The posterior comes back as (alpha, Sigma) -- agp_svgp_get_state with eta1 = eta2 = NULL -- and log p is the handle's ELBO.
+const HipGP{T} = AGP.GP{T,<:GaussianLikelihood,<:AGP.Analytic}
+twin(model::HipGP) = get!(() -> HipModel(model), TWINS, model)
+function pull_gp_posterior!(hm::HipModel{T}) where {T}
+    f = only(latents(hm.model))
+    N = AGP.dim(f)
+    α, Σ = ROCArray{T}(undef, N), ROCArray{T}(undef, N, N)
+    check(hm.ctx, ccall((:agp_svgp_get_state, libagp), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        hm.h, 0, pointer(α), pointer(Σ), C_NULL, C_NULL))
+    AMDGPU.synchronize()
+    f.post.α = Array(α)
+    f.post.Σ = cholesky(Symmetric(Array(Σ)))   # Posterior.Σ is a Cholesky{T,Matrix{T}} (posterior.jl:8-12)
+    return nothing
+end
+function train!(model::HipGP, iterations::Int; backend::Symbol=BACKEND[], kwargs...)
+    backend === :cpu && return invoke(train!, Tuple{AGP.AbstractGPModel,Int}, model, iterations; kwargs...)
+    X = reduce(hcat, AGP.input(model.data))'                     # N x D
+    _, state = train!(twin(model), X, AGP.output(model.data), iterations; kwargs...)
+    return model, state
+end
+for f in (:predict_f, :predict_y, :proba_y)
+    @eval function $f(model::HipGP, X_test::AbstractMatrix, state=nothing; backend::Symbol=BACKEND[], kw...)
+        (backend === :cpu || !has_twin(model)) &&
+            return invoke($f, Tuple{AGP.AbstractGPModel,AbstractMatrix,Any}, model, X_test, state; kw...)
+        return $f(TWINS[model], X_test; kw...)
+    end
+end
+objective(model::HipGP, state::HipModel, y=nothing) = objective(state)
+objective(model::HipGP, state, y) = has_twin(model) ? objective(TWINS[model]) : AGP.log_py(model, y)
+ELBO(model::HipGP) = has_twin(model) ? objective(TWINS[model]) : AGP.log_py(model, AGP.output(model.data))
 
 end # module
