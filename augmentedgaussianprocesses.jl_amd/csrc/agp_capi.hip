@@ -1559,11 +1559,6 @@ struct Svgp : SvgpBase {
     return AGP_OK;
   }
   agp_status step_finish() override {
-    if (exact) {  // (the whole Analytic step ran in step_local)
-      n_opt += 1;
-      return AGP_OK;
-    }
-    if (full) return vgp_step_finish();
     if (pro_allowed() && chol_use_dag(ctx, mp / TILE, rup64(B_last) / TILE + 1, 1) && mp / TILE <= 32) {
       Latent& g = lat[0];
       g.C_valid = false;
@@ -1607,7 +1602,11 @@ struct Svgp : SvgpBase {
   // (round 4 measured the hyper-gradient's small launches on a side stream next to the products: 1063 -> 1077 us, every cross-stream
   //  event costs the waiting stream 7 - 12 us; removed in round 5, docs/DESIGN_LOG.md)
 
-  agp_status init() override {
+ protected:
+  bool sparse_bufs = true;  // K_nm, kappa, the K~ partials, the kappa rows of Wbuf, stats: none in the full model (Vgp, kappa = I)
+ public:
+  // the descriptor's checks, before anything is allocated; a full model (Vgp, Gp) adds its own after these
+  virtual agp_status check_desc() {
     m = desc.m;
     D = desc.D;
     nl = desc.n_latent;
@@ -1649,22 +1648,11 @@ struct Svgp : SvgpBase {
       ctx->err = "RobbinsMonro: kappa in (0.5,1], tau > 0";  // optimisers.jl:7-8
       return AGP_ERR_INVALID;
     }
-    full = (desc.flags & AGP_FLAG_FULL) != 0;
-    exact = (desc.flags & AGP_FLAG_EXACT) != 0;
-    if (exact && (!full || lp.kind != AGP_LIK_GAUSSIAN || nl != 1)) {  // GP(X, y, kernel): GP.jl:37-65
-      ctx->err = "AGP_FLAG_EXACT: exact GP regression takes AGP_FLAG_FULL, one latent and a Gaussian likelihood";
-      return AGP_ERR_UNSUPPORTED;
-    }
-    if (full) {  // VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85
-      if (desc.stochastic || Bmax != m || lp.kind == AGP_LIK_MULTIOUTPUT || desc.latent_offset != 0) {
-        ctx->err = "AGP_FLAG_FULL: the full model takes AnalyticVI, max_batch = m = N and all of its latents on one handle";
-        return AGP_ERR_INVALID;
-      }
-      if (lp.kind == AGP_LIK_GAUSSIAN && !exact) {  // VGP.jl:54-56
-        ctx->err = "For a Gaussian Likelihood you should directly use the `GP` model or the `SVGP` model for large datasets";
-        return AGP_ERR_UNSUPPORTED;
-      }
-    }
+    return AGP_OK;
+  }
+
+  agp_status init() override {
+    AGPCHK(check_desc());
     lat.resize(nl);
     const int64_t mm = mp * mp;
     for (auto& g : lat) {
@@ -1681,12 +1669,12 @@ struct Svgp : SvgpBase {
       AGPCHK(dmalloc(ctx, &g.v, mp));
       AGPCHK(dmalloc(ctx, &g.Sigma, mm));
       AGPCHK(dmalloc(ctx, &g.mu, mp));
-      if (!full) {  // (kappa = I: the full model has no K_nm, kappa, K~ and takes only the [eta1' ; 0] block of Wbuf)
+      if (sparse_bufs) {  // (kappa = I: the full model has no K_nm, kappa, K~ and takes only the [eta1' ; 0] block of Wbuf)
         AGPCHK(dmalloc(ctx, &g.Knm, Bp * mp));
         AGPCHK(dmalloc(ctx, &g.kappa, Bp * mp));
         AGPCHK(dmalloc(ctx, &g.pk, (2 * mp / TILE) * Bp));
       }
-      AGPCHK(dmalloc(ctx, &g.Wbuf, ((full ? 0 : Bp) + TILE) * mp));
+      AGPCHK(dmalloc(ctx, &g.Wbuf, ((sparse_bufs ? Bp : 0) + TILE) * mp));
       AGPCHK(dmalloc(ctx, &g.DgK, mp * TILE));
       AGPCHK(dmalloc(ctx, &g.DgA, mp * TILE));
       AGPCHK(upload_scales(g));
@@ -1710,7 +1698,7 @@ struct Svgp : SvgpBase {
     AGPCHK(dmalloc(ctx, &beta, Bp));
     AGPCHK(dmalloc(ctx, &gsum, Bp));
     AGPCHK(dmalloc(ctx, &alpha_save, Bp));
-    if (!full) AGPCHK(dmalloc(ctx, &stats, nl * stats_stride()));
+    if (sparse_bufs) AGPCHK(dmalloc(ctx, &stats, nl * stats_stride()));
     AGPCHK(dmalloc(ctx, &Tw, mm));
     AGPCHK(dmalloc(ctx, &Tw2, mm));
     AGPCHK(dmalloc(ctx, &tmpv, mp));
@@ -1733,13 +1721,6 @@ struct Svgp : SvgpBase {
     hipLaunchKernelGGL((k_fill<T>), grid1(Bp), dim3(256), 0, st(), alpha, Bp, kk);
     hipLaunchKernelGGL((k_fill<T>), grid1(Bp), dim3(256), 0, st(), beta, Bp, kk);
     LAUNCHCHK(ctx);
-    if (exact) {
-      AGPCHK(dmalloc(ctx, &gp_dinv, mp));
-      AGPCHK(dmalloc(ctx, &gp_m0v, mp));
-      AGPCHK(dmalloc(ctx, &gp_s2, 1));
-      AGPCHK(dmalloc(ctx, &gp_part, 6 * ((mp + 255) / 256)));
-      AGPCHK(dmalloc(ctx, &gp_out, 8));
-    }
     n_opt = 1;
     return AGP_OK;
   }
@@ -1778,11 +1759,6 @@ struct Svgp : SvgpBase {
     if (pf_done) dcheck(hipEventDestroy(pf_done), __LINE__);
     for (auto e : step_done)
       if (e) dcheck(hipEventDestroy(e), __LINE__);
-    if (vgp_part) dfree(vgp_part);
-    for (T* p : {gp_dinv, gp_m0v, gp_s2})
-      if (p) dfree(p);
-    for (double* p : {gp_part, gp_out})
-      if (p) dfree(p);
     T* ps[] = {rbuf2, wbuf2, pw0, pw1, Kt, muf, varf, cbuf, theta, gamma, rbuf, wbuf, alpha, beta, gsum, alpha_save, emuf,
                evarf, stats, Tw, Tw2, tmpv, lr_dev, Kstar, ppm, ppv, pmu, pvar};
     for (T* p : ps)
@@ -1919,7 +1895,6 @@ struct Svgp : SvgpBase {
 
   // compute_K : cholesky(kernelmatrix(k, Z) + jitt*I) ; inv(K)      latentgp.jl:205-207, analyticVI.jl:179
   agp_status refresh_K() override {
-    if (exact) return gp_refresh_K();
     bool any = false;
     if (pend.on)  // the pending natural-gradient step belongs to the kernel matrices it was computed with
       for (auto& g : lat)
@@ -2188,10 +2163,6 @@ struct Svgp : SvgpBase {
   // compute_K where train! starts and ends (training.jl:41-43,107): with AGP_FLAG_STALE_K this is the only thing that ends
   // the staleness; without the flag it is plain refresh_K
   agp_status refresh_K_explicit() override {
-    if (exact) {  // compute_Ks + post_step! (training.jl:107-108, GP.jl:80-85): K, then Sigma and alpha with the current sigma2
-      AGPCHK(gp_refresh_K());
-      return (gp_have_r && !(gp_valid && gp_s2_fresh)) ? gp_factor(nullptr, false) : AGP_OK;
-    }
     for (auto& g : lat) g.stale_on = false;
     return refresh_K();
   }
@@ -2201,358 +2172,6 @@ struct Svgp : SvgpBase {
       ctx->err = "The size of mini-batch " + std::to_string(B) + " is incorrect (negative or bigger than max_batch)";
       return AGP_ERR_BAD_BATCH;
     }
-    return AGP_OK;
-  }
-
-  // ---- full model (AGP_FLAG_FULL: VGP, kappa = I, m = N, Z = the training inputs) -----------------------------------------
-  bool full = false;
-  T* vgp_part = nullptr;  // [2][ns][mp] partial column sums of k_vgp_colstats
-  int vgp_ns = 0;
-  // factor -2 eta2 with its inverse Xa and v = Xa eta1 (the [eta1' ; 0] extension block of the factorisation) -- no Sigma, no kappa
-  // rows: the blocked / task-graph factorisation with its X = L^-1 output; a lost task-graph dependency is redone by its plain
-  // in-stream fallback (k_chol_safe), which rebuilds A = -2 eta2 and the eta1 row from the same sources
-  agp_status vgp_factor(Latent& g) {
-    if (g.la_state != 0) {  // La holds a factor: rebuild -2 eta2
-      hipLaunchKernelGGL((k_copy2d<T>), grid2(mp, mp), blk2, 0, st(), (const T*)g.eta2, mp, mp, mp, g.La, mp, mp, mp, T(1), T(-2));
-      LAUNCHCHK(ctx);
-    }
-    SafeSrc<T> src{};
-    src.Bq = 0;
-    src.eta1[0] = g.eta1;
-    src.eta2[0] = g.eta2;
-    src.want_x = 1;
-    AGPCHK(timing_begin());
-    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, 1, 1, info_dev, m, (const T*)g.eta1, false, &src));
-    AGPCHK(timing_end(chol_use_dag(ctx, mp / TILE, 1) ? 1 : chol_launch_count(mp / TILE, 1)));
-    g.la_state = 1;
-    g.xa_valid = true;
-    g.xa_epoch += 1;
-    g.sigma_epoch = -1;
-    HIPCHK(ctx, hipMemcpyAsync(g.v, g.Wbuf, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
-    g.v_epoch = g.xa_epoch;
-    return AGP_OK;
-  }
-  // update_parameters!(::VGP) first half (training.jl:140-144): local_updates! on mean_f = mu, var_f = diag Sigma of the current
-  // posterior (latentgp.jl:171-189).  The factor of -2 eta2 and its inverse come from the factorisation (or from the last
-  // materialize(), which left them); mu and diag Sigma from one pass over the lower triangle of Xa (k_vgp_colstats), which feeds the
-  // point-wise likelihood update directly.  The whole training set every time: idx = NULL, B = N.
-  agp_status vgp_step_local(const void* y, const int64_t* idx, int64_t B, double rho, bool fresh) {
-    if (idx != nullptr || B != m) {
-      ctx->err = "full model (AGP_FLAG_FULL): steps and ELBO evaluations run on the whole training set (idx = NULL, B = N = m)";
-      return AGP_ERR_BAD_BATCH;
-    }
-    if (!y) return AGP_ERR_INVALID;
-    lsm_finished = false;
-    for (auto& g : lat) g.C_valid = false;
-    refresh_lazy = !fresh;
-    const agp_status rks = refresh_K();
-    refresh_lazy = false;
-    AGPCHK(rks);
-    AGPCHK(run_deferred_safe());
-    const int64_t ntc = mp / TILE;
-    const int ns = (int)std::max<int64_t>(1, std::min<int64_t>(ntc, (2048 + ntc - 1) / ntc));
-    if (!vgp_part || ns > vgp_ns) {
-      if (vgp_part) dfree(vgp_part);
-      vgp_part = nullptr;
-      AGPCHK(dmalloc(ctx, &vgp_part, 2 * (int64_t)ns * mp));
-      vgp_ns = ns;
-    }
-    const int64_t rows = (mp + ns - 1) / ns;
-    for (int l = 0; l < nl; ++l) {
-      Latent& g = lat[l];
-      if (!(g.la_state == 1 && g.xa_valid)) AGPCHK(vgp_factor(g));
-      if (g.v_epoch != g.xa_epoch) {
-        hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xa, mp, mp, (const T*)g.eta1, g.v);
-        g.v_epoch = g.xa_epoch;
-      }
-      hipLaunchKernelGGL((k_vgp_colstats<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), mp, (const T*)g.Xa,
-                         (const T*)g.v, rows, vgp_part, vgp_part + (int64_t)ns * mp);
-      hipLaunchKernelGGL((k_vgp_local<T>), grid1(m), dim3(256), 0, st(), m, mp, ns, (const T*)vgp_part,
-                         (const T*)(vgp_part + (int64_t)ns * mp), (T)rho, lp, (const T*)y, Kt + l * Bp, muf + l * Bp,
-                         varf + l * Bp, cbuf + l * Bp, theta + l * Bp, rbuf + l * Bp, wbuf + l * Bp, (const T*)lam_dev,
-                         gamma + l * Bp);
-      LAUNCHCHK(ctx);
-    }
-    AGPCHK(lik_tail(y, idx, B, rho, fresh));
-    x_last = Zdummy();
-    y_last = y;
-    idx_last = nullptr;
-    B_last = B;
-    ldx_last = D;
-    rho_last = rho;
-    return AGP_OK;
-  }
-  const void* Zdummy() const { return (const void*)lat[0].Z; }
-  // natural_gradient! + global_update! of the full model (analyticVI.jl:126-140, inference.jl:25-28): eta and La = -2 eta2 by one
-  // streaming pass (k_vgp_eta); the factorisation itself is left to whoever needs the new posterior next (the next step's local
-  // phase, materialize())
-  agp_status vgp_step_finish() {
-    AGPCHK(lsm_finish());
-    for (int l = 0; l < nl; ++l) {
-      Latent& g = lat[l];
-      hipLaunchKernelGGL((k_vgp_eta<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp,
-                         (const T*)kinv_step(g), (const T*)(rbuf + l * Bp), (const T*)(wbuf + l * Bp), (const T*)kinv_mu0_step(g),
-                         g.eta2, g.La, g.eta1);
-      LAUNCHCHK(ctx);
-      g.la_state = 0;
-      g.xa_valid = false;
-      g.C_valid = false;
-      g.post_valid = false;
-      g.pred_valid = g.predvar_valid = false;
-    }
-    n_opt += 1;
-    return AGP_OK;
-  }
-  // mean_f / var_f under the UPDATED posterior for objective(model, state, y): mu and diag Sigma of the materialised posterior
-  agp_status vgp_posterior_f() {
-    for (int l = 0; l < nl; ++l) {
-      Latent& g = lat[l];
-      AGPCHK(materialize(g));
-      hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)g.Sigma, (const T*)g.mu, emuf + l * Bp,
-                         evarf + l * Bp);
-      LAUNCHCHK(ctx);
-    }
-    return AGP_OK;
-  }
-  // update_hyperparameters!(::VGP) (autotuning.jl:49-85): only the Gaussian KL depends on the kernel; G_K from K^-1, Apred and
-  // K^-1 (mu - mu0) (k_vgp_gK), then the backward pass through kernelmatrix(k, X) with both operands X (G_K symmetric: twice the
-  // second-argument part).  X is never optimised: no dZ.
-  agp_status vgp_hypergrad(int l, double* dvar, double* dscale, void* dZ_out) {
-    if (l < 0 || l >= nl || B_last <= 0) return AGP_ERR_INVALID;
-    if (dZ_out) {
-      ctx->err = "full model (AGP_FLAG_FULL): the training inputs are not optimised (no dZ)";
-      return AGP_ERR_UNSUPPORTED;
-    }
-    Latent& g = lat[l];
-    if (g.k.kind == AGP_K_EXPONENTIAL) {
-      ctx->err = "hyper-gradient: ExponentialKernel is not differentiable at zero distance";
-      return AGP_ERR_UNSUPPORTED;
-    }
-    AGPCHK(hyper_alloc());
-    AGPCHK(refresh_K());
-    AGPCHK(ensure_pred(g, true));  // Sigma, mu, K^-1 mu, Apred = K^-1 - K^-1 Sigma K^-1
-    n_hgrad += 1;
-    hipLaunchKernelGGL((k_vgp_gK<T>), grid2(mp, mp), blk2, 0, st(), m, mp, (const T*)g.Apred, (const T*)g.apred,
-                       (const T*)g.kinv_mu0, Tw2);
-    tw2_kis_of = -1;
-    dim3 gk((unsigned)(mp / TILE), (unsigned)(mp / HB_RT));
-    const int64_t tiles = (int64_t)gk.x * gk.y;
-    hipLaunchKernelGGL((k_kernel_backward<T>), gk, dim3(NTHREADS), 0, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m,
-                       (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind, kvar(g), (const T*)Tw2, mp, hy_pvar, hy_pscale,
-                       hy_pZ, mp);
-    hipLaunchKernelGGL((k_hyper_reduce<T>), dim3((unsigned)(D + 1 + (m * D + 255) / 256)), dim3(256), 0, st(), tiles, D,
-                       (const double*)hy_pvar, (const double*)hy_pscale, hy_g, 1.0, 1, (int64_t)gk.y, m, mp, (const T*)hy_pZ,
-                       hy_dZ, T(2), (const T*)nullptr, (int64_t)0, 0.0);
-    LAUNCHCHK(ctx);
-    if (hy_grad_on_device_only) return AGP_OK;
-    std::vector<double> hg(1 + D);
-    HIPCHK(ctx, hipMemcpyAsync(hg.data(), hy_g, sizeof(double) * (1 + D), hipMemcpyDeviceToHost, st()));
-    HIPCHK(ctx, hipStreamSynchronize(st()));
-    if (dvar) *dvar = hg[0];
-    if (dscale)
-      for (int64_t d = 0; d < D; ++d) dscale[d] = hg[1 + d];
-    hy_last = hg;
-    return AGP_OK;
-  }
-
-  // ---- exact GP (AGP_FLAG_FULL | AGP_FLAG_EXACT: GP(X, y, kernel) with Analytic(), src/models/GP.jl, analytic.jl) ------------
-  // K + jitt I is kept unfactored in g.L (refreshed only when the kernel moved: numerically the reference's recompute every
-  // iteration).  A step factors Sigma = K + sigma2 I in g.La with its inverse g.Xa = L^-1 and the extension row r = y - mu0 (g.eta1),
-  // whose image v = L^-1 r lands in g.v; alpha = Sigma^-1 r goes to g.mu, diag Sigma^-1 to gp_dinv, log p to gp_out[4], and the
-  // sigma2 the factor used to gp_s2.  Sigma^-1 (g.Apred) and Sigma (g.Sigma) are formed on demand, once per factor.
-  bool exact = false;
-  bool gp_have_r = false;       // g.eta1 holds r (from the first step)
-  bool gp_valid = false;        // the factor, alpha and log p belong to the current K
-  bool gp_s2_fresh = false;     // ... and to the current sigma2 (no noise step since)
-  bool gp_sinv_valid = false, gp_sigma_valid = false;
-  T* gp_dinv = nullptr;         // diag Sigma^-1
-  T* gp_m0v = nullptr;          // L^-1 mu0 (the reference's y' Sigma^-1 y with a prior mean)
-  T* gp_s2 = nullptr;           // sigma2 of the current factor
-  double* gp_part = nullptr;    // [6][nb] partial sums of k_gp_partial
-  double* gp_out = nullptr;     // [alpha' alpha, tr Sigma^-1, r' alpha, sum log L_ii, log p]
-  bool gp_ref() const { return desc.elbo_mode == AGP_ELBO_REFERENCE; }
-
-  // compute_Ks (training.jl:167-171, latentgp.jl:201-203): K = kernelmatrix(k, X) + jitt I, identity in the padding
-  agp_status gp_refresh_K() {
-    Latent& g = lat[0];
-    if (!g.K_stale) return AGP_OK;
-    AGPCHK(ensure_zsc(g));
-    (void)launch_kernelmatrix<T>(ctx, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m, (const T*)g.Z, D, m, D,
-                                 (const T*)g.scales, g.k.kind, kvar(g), g.L, mp, mp, mp, 1, (T)jitter, (const T*)nullptr, (T*)nullptr,
-                                 (int64_t)0, 0, (const T*)g.Zsc, (const T*)g.zn);
-    LAUNCHCHK(ctx);
-    g.K_stale = false;
-    gp_valid = false;
-    gp_sinv_valid = gp_sigma_valid = false;
-    g.pred_valid = g.predvar_valid = false;
-    return AGP_OK;
-  }
-
-  // analytic_updates (analytic.jl:36-51) / post_step! (GP.jl:80-85): Sigma = K + sigma2 I, alpha = Sigma \ (y - mu0), log p; with
-  // noise_step (and opt_noise) the ADAM step on log sigma2 that follows.  y = NULL: r from the last step.  No host synchronisation.
-  agp_status gp_factor(const T* y, bool noise_step) {
-    if (!y && !gp_have_r) {
-      ctx->err = "exact GP (AGP_FLAG_EXACT): no step has been taken yet (the targets arrive with agp_svgp_cavi_step)";
-      return AGP_ERR_INVALID;
-    }
-    AGPCHK(gp_refresh_K());
-    Latent& g = lat[0];
-    const int64_t ntc = mp / TILE;
-    const int ns = (int)std::max<int64_t>(1, std::min<int64_t>(ntc, (2048 + ntc - 1) / ntc));
-    if (!vgp_part || ns > vgp_ns) {
-      if (vgp_part) dfree(vgp_part);
-      vgp_part = nullptr;
-      AGPCHK(dmalloc(ctx, &vgp_part, 2 * (int64_t)ns * mp));
-      vgp_ns = ns;
-    }
-    hipLaunchKernelGGL((k_gp_shift<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp, (const T*)g.L,
-                       (const T*)lam_dev, y, (const T*)g.mu0, g.La, y ? g.eta1 : (T*)nullptr, gp_s2);
-    LAUNCHCHK(ctx);
-    if (y) gp_have_r = true;
-    // a lost task-graph dependency: the in-stream fallback rebuilds Sigma from K and the sigma2 word, the row from r
-    SafeSrc<T> src{};
-    src.Bq = 0;
-    src.eta1[0] = g.eta1;
-    src.want_x = 1;
-    src.gpK = g.L;
-    src.gps2 = lam_dev;
-    src.mz = m;
-    AGPCHK(timing_begin());
-    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, 1, 1, info_dev, m, (const T*)g.eta1, false, &src));
-    AGPCHK(timing_end(chol_use_dag(ctx, mp / TILE, 1) ? 1 : chol_launch_count(mp / TILE, 1)));
-    HIPCHK(ctx, hipMemcpyAsync(g.v, g.Wbuf, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
-    const bool ref_m0 = gp_ref() && g.mu0;
-    if (ref_m0)
-      hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xa, mp, mp, (const T*)g.mu0, gp_m0v);
-    const int64_t rows = (mp + ns - 1) / ns;
-    hipLaunchKernelGGL((k_vgp_colstats<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), mp, (const T*)g.Xa, (const T*)g.v,
-                       rows, vgp_part, vgp_part + (int64_t)ns * mp);
-    const int nb = (int)((mp + 255) / 256);
-    hipLaunchKernelGGL((k_gp_partial<T>), dim3(nb), dim3(256), 0, st(), m, mp, ns, (const T*)vgp_part,
-                       (const T*)(vgp_part + (int64_t)ns * mp), (const T*)g.eta1, (const T*)g.DgA, (const T*)g.mu0,
-                       ref_m0 ? (const T*)gp_m0v : (const T*)nullptr, g.mu, gp_dinv, gp_part);
-    const bool step_noise = noise_step && lp.noise_dev;
-    hipLaunchKernelGGL((k_gp_finish<T>), dim3(1), dim3(256), 0, st(), nb, (const double*)gp_part, m, gp_ref() ? 1 : 0, noise_eta,
-                       step_noise ? noise_adam : (double*)nullptr, lam_dev, gp_out);
-    LAUNCHCHK(ctx);
-    gp_valid = true;
-    gp_s2_fresh = !step_noise;
-    gp_sinv_valid = gp_sigma_valid = false;
-    g.pred_valid = g.predvar_valid = false;
-    return AGP_OK;
-  }
-  agp_status gp_step(const void* y, const int64_t* idx, int64_t B) {
-    if (idx != nullptr || B != m) {
-      ctx->err = "exact GP (AGP_FLAG_EXACT): steps run on the whole training set (idx = NULL, B = N = m)";
-      return AGP_ERR_BAD_BATCH;
-    }
-    if (!y) return AGP_ERR_INVALID;
-    AGPCHK(gp_factor((const T*)y, true));
-    x_last = Zdummy();
-    y_last = y;
-    idx_last = nullptr;
-    B_last = B;
-    ldx_last = D;
-    rho_last = 1.0;
-    return AGP_OK;
-  }
-  // Sigma^-1 = L^-T L^-1 of the current factor (the predictor's Apred, the hyper-gradient's)
-  agp_status gp_sinv() {
-    Latent& g = lat[0];
-    if (!gp_valid) AGPCHK(gp_factor(nullptr, false));
-    if (gp_sinv_valid) return AGP_OK;
-    if (!g.Apred) AGPCHK(dmalloc(ctx, &g.Apred, mp * mp));
-    AGPCHK(xtx_padded<T>(ctx, g.Xa, mp, mp, g.Apred, mp));
-    gp_sinv_valid = true;
-    return AGP_OK;
-  }
-  // predictions.jl:6-23: mu* = K*n alpha (mu0 not added back), var* = k** + jitt - diag(K*n Sigma^-1 Kn*): the streaming predictor
-  // with apred = alpha, Apred = Sigma^-1
-  agp_status gp_ensure_pred(Latent& g, bool need_var) {
-    if (!gp_valid) AGPCHK(gp_factor(nullptr, false));
-    if (!g.apred) AGPCHK(dmalloc(ctx, &g.apred, mp));
-    if (!g.pred_valid) {
-      HIPCHK(ctx, hipMemcpyAsync(g.apred, g.mu, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
-      g.pred_valid = true;
-    }
-    if (need_var && !g.predvar_valid) {
-      AGPCHK(gp_sinv());
-      g.predvar_valid = true;
-    }
-    return AGP_OK;
-  }
-  // objective(m::GP, _, y) = log_py (GP.jl:87-92) of the stored posterior.  y binds the targets of a handle that has taken no step
-  // yet (a reloaded model: post_step! with the restored sigma2); afterwards it is not read.
-  agp_status gp_logp(const T* y, double* out) {
-    if (!out) return AGP_ERR_INVALID;
-    if (y && !gp_have_r) AGPCHK(gp_factor(y, false));
-    else if (!gp_valid) AGPCHK(gp_factor(nullptr, false));
-    HIPCHK(ctx, hipMemcpyAsync(out, gp_out + 4, sizeof(double), hipMemcpyDeviceToHost, st()));
-    HIPCHK(ctx, hipStreamSynchronize(st()));
-    return AGP_OK;
-  }
-  // mu <- alpha, sigma <- Sigma (the posterior of GP.jl: Posterior(Sigma, alpha)); there are no natural parameters
-  agp_status gp_get_state(void* mu, void* sigma, void* eta1, void* eta2) {
-    if (eta1 || eta2) {
-      ctx->err = "exact GP (AGP_FLAG_EXACT): the posterior has no natural parameters (eta1 / eta2 must be NULL)";
-      return AGP_ERR_UNSUPPORTED;
-    }
-    Latent& g = lat[0];
-    if ((mu || sigma) && !gp_valid) AGPCHK(gp_factor(nullptr, false));
-    if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, g.mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
-    if (sigma) {
-      if (!gp_sigma_valid) {
-        hipLaunchKernelGGL((k_gp_shift<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp, (const T*)g.L,
-                           (const T*)gp_s2, (const T*)nullptr, (const T*)nullptr, g.Sigma, (T*)nullptr, (T*)nullptr);
-        LAUNCHCHK(ctx);
-        gp_sigma_valid = true;
-      }
-      HIPCHK(ctx, hipMemcpy2DAsync(sigma, sizeof(T) * m, g.Sigma, sizeof(T) * mp, sizeof(T) * m, m, hipMemcpyDeviceToDevice, st()));
-    }
-    return AGP_OK;
-  }
-  // G1 corrected: d log p / d theta = tr((alpha alpha' - Sigma^-1) dK/dtheta) / 2 at the Sigma of the last step -- the adjoint of K
-  // G_K = (alpha alpha' - Sigma^-1) / 2 (k_vgp_gK with Apred = Sigma^-1, a = alpha), then the backward pass through
-  // kernelmatrix(k, X) with both operands X as for VGP.  Reference mode: the reference's gradient is `nothing` (zeros here).
-  agp_status gp_hypergrad(int l, double* dvar, double* dscale, void* dZ_out) {
-    if (l != 0 || B_last <= 0) return AGP_ERR_INVALID;
-    if (dZ_out) {
-      ctx->err = "full model (AGP_FLAG_FULL): the training inputs are not optimised (no dZ)";
-      return AGP_ERR_UNSUPPORTED;
-    }
-    Latent& g = lat[0];
-    if (g.k.kind == AGP_K_EXPONENTIAL) {
-      ctx->err = "hyper-gradient: ExponentialKernel is not differentiable at zero distance";
-      return AGP_ERR_UNSUPPORTED;
-    }
-    if (gp_ref()) {
-      if (dvar) *dvar = 0.0;
-      if (dscale)
-        for (int64_t d = 0; d < D; ++d) dscale[d] = 0.0;
-      return AGP_OK;
-    }
-    AGPCHK(hyper_alloc());
-    AGPCHK(gp_sinv());
-    n_hgrad += 1;
-    hipLaunchKernelGGL((k_vgp_gK<T>), grid2(mp, mp), blk2, 0, st(), m, mp, (const T*)g.Apred, (const T*)g.mu, (const T*)nullptr, Tw2);
-    tw2_kis_of = -1;
-    dim3 gk((unsigned)(mp / TILE), (unsigned)(mp / HB_RT));
-    const int64_t tiles = (int64_t)gk.x * gk.y;
-    hipLaunchKernelGGL((k_kernel_backward<T>), gk, dim3(NTHREADS), 0, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m,
-                       (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind, kvar(g), (const T*)Tw2, mp, hy_pvar, hy_pscale,
-                       hy_pZ, mp);
-    hipLaunchKernelGGL((k_hyper_reduce<T>), dim3((unsigned)(D + 1 + (m * D + 255) / 256)), dim3(256), 0, st(), tiles, D,
-                       (const double*)hy_pvar, (const double*)hy_pscale, hy_g, 1.0, 1, (int64_t)gk.y, m, mp, (const T*)hy_pZ,
-                       hy_dZ, T(2), (const T*)nullptr, (int64_t)0, 0.0);
-    LAUNCHCHK(ctx);
-    if (hy_grad_on_device_only) return AGP_OK;
-    std::vector<double> hg(1 + D);
-    HIPCHK(ctx, hipMemcpyAsync(hg.data(), hy_g, sizeof(double) * (1 + D), hipMemcpyDeviceToHost, st()));
-    HIPCHK(ctx, hipStreamSynchronize(st()));
-    if (dvar) *dvar = hg[0];
-    if (dscale)
-      for (int64_t d = 0; d < D; ++d) dscale[d] = hg[1 + d];
-    hy_last = hg;
     return AGP_OK;
   }
 
@@ -2610,8 +2229,6 @@ struct Svgp : SvgpBase {
   // compute_kappa + mean_f/var_f + local update
   agp_status step_local(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho,
                         bool fresh) override {
-    if (exact) return gp_step(y, idx, B);
-    if (full) return vgp_step_local(y, idx, B, rho, fresh);
     AGPCHK(check_batch(B));
     if (!x || !y || ldx < D) return AGP_ERR_INVALID;
     lsm_finished = false;
@@ -2982,8 +2599,6 @@ struct Svgp : SvgpBase {
 
   // gradient of the hyper objective w.r.t. (variance, per-dimension scales, Z) of latent l, on the batch of the last step
   agp_status hypergrad(int l, double* dvar, double* dscale, void* dZ_out) override {
-    if (exact) return gp_hypergrad(l, dvar, dscale, dZ_out);
-    if (full) return vgp_hypergrad(l, dvar, dscale, dZ_out);
     if (l < 0 || l >= nl || !x_last || B_last <= 0) return AGP_ERR_INVALID;
     Latent& g = lat[l];
     if (g.k.kind == AGP_K_EXPONENTIAL) {
@@ -3258,7 +2873,11 @@ struct Svgp : SvgpBase {
     }
     LAUNCHCHK(ctx);
     if (dZ_out) HIPCHK(ctx, hipMemcpyAsync(dZ_out, hy_dZ, sizeof(T) * m * D, hipMemcpyDeviceToDevice, st()));
-    if (hy_grad_on_device_only) return AGP_OK;  // the training loop: the gradient stays in hy_g / hy_dZ for the device-side ADAM
+    return hypergrad_to_host(dvar, dscale);
+  }
+  // hy_g -> dvar / dscale, hy_last (the training loop's hyper step keeps it on the device for ADAM: hy_grad_on_device_only)
+  agp_status hypergrad_to_host(double* dvar, double* dscale) {
+    if (hy_grad_on_device_only) return AGP_OK;
     std::vector<double> hg(1 + D);
     HIPCHK(ctx, hipMemcpyAsync(hg.data(), hy_g, sizeof(double) * (1 + D), hipMemcpyDeviceToHost, st()));
     HIPCHK(ctx, hipStreamSynchronize(st()));
@@ -3438,7 +3057,6 @@ struct Svgp : SvgpBase {
   bool hyper_multi_ok = false;
   agp_status hyper_step() override {
     if (!hy_k && !hy_z) return AGP_OK;
-    if (exact && gp_ref()) return AGP_OK;  // G1: the reference's kernel gradient is `nothing` -- kernel and optimiser state untouched
     if (bs_world > 1 && !hyper_multi_ok) {
       // every rank would step its kernel / Z with the gradient of its own shard and the replicas would drift apart
       ctx->err = "batch-sharded handle: take the hyper step through agp_svgp_hyper_step_multi (the gradient is all-reduced)";
@@ -3461,7 +3079,6 @@ struct Svgp : SvgpBase {
   agp_status hyper_apply(int l, const double* dvar, const double* dscale, const void* dZ) override {
     if (l < 0 || l >= nl || !dvar || !dscale) return AGP_ERR_INVALID;
     if (!hy_k && !hy_z) return AGP_OK;
-    if (exact && gp_ref()) return AGP_OK;  // G1 as in hyper_step: a caller-supplied gradient moves nothing either
     std::vector<double> hg(1 + D);
     hg[0] = *dvar;
     for (int64_t d = 0; d < D; ++d) hg[1 + d] = dscale[d];
@@ -3597,8 +3214,7 @@ struct Svgp : SvgpBase {
     return publish_f(emuf, evarf, 2);
   }
   // mean_f / var_f of the owned latents on the last batch with the CURRENT posterior -> emuf / evarf (analyticVI.jl:260-266)
-  agp_status posterior_f(int64_t B) {
-    if (full) return vgp_posterior_f();
+  virtual agp_status posterior_f(int64_t B) {
     const int64_t Bq = rup64(B);
     for (int l = 0; l < nl; ++l) {
       Latent& g = lat[l];
@@ -4193,7 +3809,6 @@ struct Svgp : SvgpBase {
 
   agp_status elbo(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho, int fresh,
                   double* out) override {
-    if (exact) return gp_logp((const T*)y, out);
     AGPCHK(check_batch(B));
     const bool lsm = lp.kind == AGP_LIK_LOGISTICSOFTMAX;
     const T* mf;
@@ -4426,7 +4041,6 @@ struct Svgp : SvgpBase {
 
   agp_status get_state(int l, void* mu, void* sigma, void* eta1, void* eta2) override {
     if (l < 0 || l >= nl) return AGP_ERR_INVALID;
-    if (exact) return gp_get_state(mu, sigma, eta1, eta2);
     Latent& g = lat[l];
     if (mu || sigma) AGPCHK(materialize(g));
     if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, g.mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
@@ -4441,10 +4055,6 @@ struct Svgp : SvgpBase {
   }
 
   agp_status set_state(int l, const void* eta1, const void* eta2) override {
-    if (exact) {
-      ctx->err = "exact GP (AGP_FLAG_EXACT): the posterior follows from K, sigma2 and y; it has no natural parameters to set";
-      return AGP_ERR_UNSUPPORTED;
-    }
     if (l < 0 || l >= nl || !eta1 || !eta2) return AGP_ERR_INVALID;
     Latent& g = lat[l];
     HIPCHK(ctx, hipMemsetAsync(g.eta1, 0, sizeof(T) * mp, st()));
@@ -4547,8 +4157,7 @@ struct Svgp : SvgpBase {
   }
 
   // ---- prediction (predictions.jl:25-50) -------------------------------------------------------------------
-  agp_status ensure_pred(Latent& g, bool need_var) {
-    if (exact) return gp_ensure_pred(g, need_var);
+  virtual agp_status ensure_pred(Latent& g, bool need_var) {
     AGPCHK(refresh_K());
     AGPCHK(materialize(g));
     if (!g.apred) {
@@ -4738,7 +4347,6 @@ struct Svgp : SvgpBase {
       return AGP_ERR_INVALID;
     hipLaunchKernelGGL((k_fill<T>), dim3(1), dim3(64), 0, st(), lam_dev, (int64_t)1, (T)v);
     LAUNCHCHK(ctx);
-    gp_s2_fresh = false;
     return AGP_OK;
   }
 
@@ -5167,6 +4775,395 @@ struct Svgp : SvgpBase {
       hipLaunchKernelGGL((k_proba_lsm<T>), grid1(nt), dim3(256), 0, st(), nt, nl, nt, (const T*)pmu, (T*)o0);
     }
     LAUNCHCHK(ctx);
+    return AGP_OK;
+  }
+};
+
+// ---- full model (AGP_FLAG_FULL: VGP, kappa = I, m = N, Z = the training inputs) -------------------------------------------
+// VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85, Float64 only: the SVGP handle without K_nm, kappa, K~
+struct Vgp : Svgp<double> {
+  using T = double;
+  T* vgp_part = nullptr;  // [2][ns][mp] partial column sums of k_vgp_colstats (colstats_part)
+  Vgp() { sparse_bufs = false; }
+  ~Vgp() override {
+    if (vgp_part) dfree(vgp_part);
+  }
+  // what a full model takes: AnalyticVI, max_batch = m = N and all of its latents on this handle
+  agp_status check_full() {
+    if (desc.stochastic || Bmax != m || lp.kind == AGP_LIK_MULTIOUTPUT || desc.latent_offset != 0) {
+      ctx->err = "AGP_FLAG_FULL: the full model takes AnalyticVI, max_batch = m = N and all of its latents on one handle";
+      return AGP_ERR_INVALID;
+    }
+    return AGP_OK;
+  }
+  agp_status check_desc() override {
+    AGPCHK(Svgp<T>::check_desc());
+    AGPCHK(check_full());
+    if (lp.kind == AGP_LIK_GAUSSIAN) {  // VGP.jl:54-56
+      ctx->err = "For a Gaussian Likelihood you should directly use the `GP` model or the `SVGP` model for large datasets";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    return AGP_OK;
+  }
+  // the ns row slices of a k_vgp_colstats pass (fixed by mp) and their partial sums in vgp_part (allocated by the first pass)
+  agp_status colstats_part(int* ns) {
+    const int64_t ntc = mp / TILE;
+    *ns = (int)std::max<int64_t>(1, std::min<int64_t>(ntc, (2048 + ntc - 1) / ntc));
+    if (!vgp_part) AGPCHK(dmalloc(ctx, &vgp_part, 2 * (int64_t)*ns * mp));
+    return AGP_OK;
+  }
+  void record_batch(const void* y, double rho) {  // every step's batch: the whole training set (x = Z, idx = NULL, B = N)
+    x_last = lat[0].Z;
+    y_last = y;
+    idx_last = nullptr;
+    B_last = m;
+    ldx_last = D;
+    rho_last = rho;
+  }
+  // factor -2 eta2 with its inverse Xa and v = Xa eta1 (the [eta1' ; 0] extension block of the factorisation) -- no Sigma, no kappa
+  // rows: the blocked / task-graph factorisation with its X = L^-1 output; a lost task-graph dependency is redone by its plain
+  // in-stream fallback (k_chol_safe), which rebuilds A = -2 eta2 and the eta1 row from the same sources
+  agp_status vgp_factor(Latent& g) {
+    if (g.la_state != 0) {  // La holds a factor: rebuild -2 eta2
+      hipLaunchKernelGGL((k_copy2d<T>), grid2(mp, mp), blk2, 0, st(), (const T*)g.eta2, mp, mp, mp, g.La, mp, mp, mp, T(1), T(-2));
+      LAUNCHCHK(ctx);
+    }
+    SafeSrc<T> src{};
+    src.Bq = 0;
+    src.eta1[0] = g.eta1;
+    src.eta2[0] = g.eta2;
+    src.want_x = 1;
+    AGPCHK(timing_begin());
+    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, 1, 1, info_dev, m, (const T*)g.eta1, false, &src));
+    AGPCHK(timing_end(chol_use_dag(ctx, mp / TILE, 1) ? 1 : chol_launch_count(mp / TILE, 1)));
+    g.la_state = 1;
+    g.xa_valid = true;
+    g.xa_epoch += 1;
+    g.sigma_epoch = -1;
+    HIPCHK(ctx, hipMemcpyAsync(g.v, g.Wbuf, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
+    g.v_epoch = g.xa_epoch;
+    return AGP_OK;
+  }
+  // update_parameters!(::VGP) first half (training.jl:140-144): local_updates! on mean_f = mu, var_f = diag Sigma of the current
+  // posterior (latentgp.jl:171-189).  The factor of -2 eta2 and its inverse come from the factorisation (or from the last
+  // materialize(), which left them); mu and diag Sigma from one pass over the lower triangle of Xa (k_vgp_colstats), which feeds the
+  // point-wise likelihood update directly.  The whole training set every time: idx = NULL, B = N.
+  agp_status step_local(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, double rho, bool fresh) override {
+    if (idx != nullptr || B != m) {
+      ctx->err = "full model (AGP_FLAG_FULL): steps and ELBO evaluations run on the whole training set (idx = NULL, B = N = m)";
+      return AGP_ERR_BAD_BATCH;
+    }
+    if (!y) return AGP_ERR_INVALID;
+    lsm_finished = false;
+    for (auto& g : lat) g.C_valid = false;
+    refresh_lazy = !fresh;
+    const agp_status rks = refresh_K();
+    refresh_lazy = false;
+    AGPCHK(rks);
+    AGPCHK(run_deferred_safe());
+    int ns = 0;
+    AGPCHK(colstats_part(&ns));
+    const int64_t ntc = mp / TILE, rows = (mp + ns - 1) / ns;
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      if (!(g.la_state == 1 && g.xa_valid)) AGPCHK(vgp_factor(g));
+      if (g.v_epoch != g.xa_epoch) {
+        hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xa, mp, mp, (const T*)g.eta1, g.v);
+        g.v_epoch = g.xa_epoch;
+      }
+      hipLaunchKernelGGL((k_vgp_colstats<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), mp, (const T*)g.Xa,
+                         (const T*)g.v, rows, vgp_part, vgp_part + (int64_t)ns * mp);
+      hipLaunchKernelGGL((k_vgp_local<T>), grid1(m), dim3(256), 0, st(), m, mp, ns, (const T*)vgp_part,
+                         (const T*)(vgp_part + (int64_t)ns * mp), (T)rho, lp, (const T*)y, Kt + l * Bp, muf + l * Bp,
+                         varf + l * Bp, cbuf + l * Bp, theta + l * Bp, rbuf + l * Bp, wbuf + l * Bp, (const T*)lam_dev,
+                         gamma + l * Bp);
+      LAUNCHCHK(ctx);
+    }
+    AGPCHK(lik_tail(y, idx, B, rho, fresh));
+    record_batch(y, rho);
+    return AGP_OK;
+  }
+  // natural_gradient! + global_update! of the full model (analyticVI.jl:126-140, inference.jl:25-28): eta and La = -2 eta2 by one
+  // streaming pass (k_vgp_eta); the factorisation itself is left to whoever needs the new posterior next (the next step's local
+  // phase, materialize())
+  agp_status step_finish() override {
+    AGPCHK(lsm_finish());
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      hipLaunchKernelGGL((k_vgp_eta<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp,
+                         (const T*)kinv_step(g), (const T*)(rbuf + l * Bp), (const T*)(wbuf + l * Bp), (const T*)kinv_mu0_step(g),
+                         g.eta2, g.La, g.eta1);
+      LAUNCHCHK(ctx);
+      g.la_state = 0;
+      g.xa_valid = false;
+      g.C_valid = false;
+      g.post_valid = false;
+      g.pred_valid = g.predvar_valid = false;
+    }
+    n_opt += 1;
+    return AGP_OK;
+  }
+  // mean_f / var_f under the UPDATED posterior for objective(model, state, y): mu and diag Sigma of the materialised posterior
+  agp_status posterior_f(int64_t) override {
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      AGPCHK(materialize(g));
+      hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)g.Sigma, (const T*)g.mu, emuf + l * Bp,
+                         evarf + l * Bp);
+      LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  }
+  // update_hyperparameters!(::VGP) (autotuning.jl:49-85): only the Gaussian KL depends on the kernel, through Apred and K^-1 (mu - mu0).
+  // X is never optimised: no dZ.
+  agp_status hypergrad(int l, double* dvar, double* dscale, void* dZ_out) override {
+    AGPCHK(check_hypergrad(l, dZ_out));
+    Latent& g = lat[l];
+    AGPCHK(hyper_alloc());
+    AGPCHK(refresh_K());
+    AGPCHK(ensure_pred(g, true));  // Sigma, mu, K^-1 mu, Apred = K^-1 - K^-1 Sigma K^-1
+    return kernel_grad(g, g.Apred, g.apred, g.kinv_mu0, dvar, dscale);
+  }
+  // what the hyper-gradient of a full model refuses: an unknown latent, no step yet, dZ, the ExponentialKernel
+  agp_status check_hypergrad(int l, const void* dZ_out) {
+    if (l < 0 || l >= nl || B_last <= 0) return AGP_ERR_INVALID;
+    if (dZ_out) {
+      ctx->err = "full model (AGP_FLAG_FULL): the training inputs are not optimised (no dZ)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    if (lat[l].k.kind == AGP_K_EXPONENTIAL) {
+      ctx->err = "hyper-gradient: ExponentialKernel is not differentiable at zero distance";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    return AGP_OK;
+  }
+  // G_K = ((a - a0)(a - a0)' - Apred) / 2, a0 = kinv_mu0 or 0 (k_vgp_gK), then the backward pass through kernelmatrix(k, X) with
+  // both operands X (G_K symmetric: twice the second-argument part) and its reduction into hy_g
+  agp_status kernel_grad(Latent& g, const T* Apred, const T* a, const T* kinv_mu0, double* dvar, double* dscale) {
+    n_hgrad += 1;
+    hipLaunchKernelGGL((k_vgp_gK<T>), grid2(mp, mp), blk2, 0, st(), m, mp, Apred, a, kinv_mu0, Tw2);
+    tw2_kis_of = -1;
+    dim3 gk((unsigned)(mp / TILE), (unsigned)(mp / HB_RT));
+    const int64_t tiles = (int64_t)gk.x * gk.y;
+    hipLaunchKernelGGL((k_kernel_backward<T>), gk, dim3(NTHREADS), 0, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m,
+                       (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind, kvar(g), (const T*)Tw2, mp, hy_pvar, hy_pscale,
+                       hy_pZ, mp);
+    hipLaunchKernelGGL((k_hyper_reduce<T>), dim3((unsigned)(D + 1 + (m * D + 255) / 256)), dim3(256), 0, st(), tiles, D,
+                       (const double*)hy_pvar, (const double*)hy_pscale, hy_g, 1.0, 1, (int64_t)gk.y, m, mp, (const T*)hy_pZ,
+                       hy_dZ, T(2), (const T*)nullptr, (int64_t)0, 0.0);
+    LAUNCHCHK(ctx);
+    return hypergrad_to_host(dvar, dscale);
+  }
+};
+
+// ---- exact GP (AGP_FLAG_FULL | AGP_FLAG_EXACT: GP(X, y, kernel) with Analytic(), src/models/GP.jl, analytic.jl) ------------
+// K + jitt I is kept unfactored in g.L (refreshed only when the kernel moved: numerically the reference's recompute every
+// iteration).  A step factors Sigma = K + sigma2 I in g.La with its inverse g.Xa = L^-1 and the extension row r = y - mu0 (g.eta1),
+// whose image v = L^-1 r lands in g.v; alpha = Sigma^-1 r goes to g.mu, diag Sigma^-1 to gp_dinv, log p to gp_out[4], and the
+// sigma2 the factor used to gp_s2.  Sigma^-1 (g.Apred) and Sigma (g.Sigma) are formed on demand, once per factor.
+struct Gp : Vgp {
+  bool gp_have_r = false;       // g.eta1 holds r (from the first step)
+  bool gp_valid = false;        // the factor, alpha and log p belong to the current K
+  bool gp_s2_fresh = false;     // ... and to the current sigma2 (no noise step since)
+  bool gp_sinv_valid = false, gp_sigma_valid = false;
+  T* gp_dinv = nullptr;         // diag Sigma^-1
+  T* gp_m0v = nullptr;          // L^-1 mu0 (the reference's y' Sigma^-1 y with a prior mean)
+  T* gp_s2 = nullptr;           // sigma2 of the current factor
+  double* gp_part = nullptr;    // [6][nb] partial sums of k_gp_partial
+  double* gp_out = nullptr;     // [alpha' alpha, tr Sigma^-1, r' alpha, sum log L_ii, log p]
+  bool gp_ref() const { return desc.elbo_mode == AGP_ELBO_REFERENCE; }
+  ~Gp() override {
+    for (T* p : {gp_dinv, gp_m0v, gp_s2})
+      if (p) dfree(p);
+    for (double* p : {gp_part, gp_out})
+      if (p) dfree(p);
+  }
+  // the generic checks, then GP(X, y, kernel)'s, then the shape of a full model
+  agp_status check_desc() override {
+    AGPCHK(Svgp<T>::check_desc());
+    if (lp.kind != AGP_LIK_GAUSSIAN || nl != 1) {  // GP(X, y, kernel): GP.jl:37-65
+      ctx->err = "AGP_FLAG_EXACT: exact GP regression takes AGP_FLAG_FULL, one latent and a Gaussian likelihood";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    return check_full();
+  }
+  agp_status init() override {
+    AGPCHK(Vgp::init());
+    AGPCHK(dmalloc(ctx, &gp_dinv, mp));
+    AGPCHK(dmalloc(ctx, &gp_m0v, mp));
+    AGPCHK(dmalloc(ctx, &gp_s2, 1));
+    AGPCHK(dmalloc(ctx, &gp_part, 6 * ((mp + 255) / 256)));
+    AGPCHK(dmalloc(ctx, &gp_out, 8));
+    return AGP_OK;
+  }
+  // compute_Ks (training.jl:167-171, latentgp.jl:201-203): K = kernelmatrix(k, X) + jitt I, identity in the padding
+  agp_status refresh_K() override {
+    Latent& g = lat[0];
+    if (!g.K_stale) return AGP_OK;
+    AGPCHK(ensure_zsc(g));
+    (void)launch_kernelmatrix<T>(ctx, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m, (const T*)g.Z, D, m, D,
+                                 (const T*)g.scales, g.k.kind, kvar(g), g.L, mp, mp, mp, 1, (T)jitter, (const T*)nullptr, (T*)nullptr,
+                                 (int64_t)0, 0, (const T*)g.Zsc, (const T*)g.zn);
+    LAUNCHCHK(ctx);
+    g.K_stale = false;
+    gp_valid = false;
+    gp_sinv_valid = gp_sigma_valid = false;
+    g.pred_valid = g.predvar_valid = false;
+    return AGP_OK;
+  }
+  // compute_Ks + post_step! (training.jl:107-108, GP.jl:80-85): K, then Sigma and alpha with the current sigma2
+  agp_status refresh_K_explicit() override {
+    AGPCHK(refresh_K());
+    return (gp_have_r && !(gp_valid && gp_s2_fresh)) ? gp_factor(nullptr, false) : AGP_OK;
+  }
+
+  // analytic_updates (analytic.jl:36-51) / post_step! (GP.jl:80-85): Sigma = K + sigma2 I, alpha = Sigma \ (y - mu0), log p; with
+  // noise_step (and opt_noise) the ADAM step on log sigma2 that follows.  y = NULL: r from the last step.  No host synchronisation.
+  agp_status gp_factor(const T* y, bool noise_step) {
+    if (!y && !gp_have_r) {
+      ctx->err = "exact GP (AGP_FLAG_EXACT): no step has been taken yet (the targets arrive with agp_svgp_cavi_step)";
+      return AGP_ERR_INVALID;
+    }
+    AGPCHK(refresh_K());
+    Latent& g = lat[0];
+    int ns = 0;
+    AGPCHK(colstats_part(&ns));
+    const int64_t ntc = mp / TILE;
+    hipLaunchKernelGGL((k_gp_shift<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp, (const T*)g.L,
+                       (const T*)lam_dev, y, (const T*)g.mu0, g.La, y ? g.eta1 : (T*)nullptr, gp_s2);
+    LAUNCHCHK(ctx);
+    if (y) gp_have_r = true;
+    // a lost task-graph dependency: the in-stream fallback rebuilds Sigma from K and the sigma2 word, the row from r
+    SafeSrc<T> src{};
+    src.Bq = 0;
+    src.eta1[0] = g.eta1;
+    src.want_x = 1;
+    src.gpK = g.L;
+    src.gps2 = lam_dev;
+    src.mz = m;
+    AGPCHK(timing_begin());
+    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, 1, 1, info_dev, m, (const T*)g.eta1, false, &src));
+    AGPCHK(timing_end(chol_use_dag(ctx, mp / TILE, 1) ? 1 : chol_launch_count(mp / TILE, 1)));
+    HIPCHK(ctx, hipMemcpyAsync(g.v, g.Wbuf, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
+    const bool ref_m0 = gp_ref() && g.mu0;
+    if (ref_m0)
+      hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xa, mp, mp, (const T*)g.mu0, gp_m0v);
+    const int64_t rows = (mp + ns - 1) / ns;
+    hipLaunchKernelGGL((k_vgp_colstats<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), mp, (const T*)g.Xa, (const T*)g.v,
+                       rows, vgp_part, vgp_part + (int64_t)ns * mp);
+    const int nb = (int)((mp + 255) / 256);
+    hipLaunchKernelGGL((k_gp_partial<T>), dim3(nb), dim3(256), 0, st(), m, mp, ns, (const T*)vgp_part,
+                       (const T*)(vgp_part + (int64_t)ns * mp), (const T*)g.eta1, (const T*)g.DgA, (const T*)g.mu0,
+                       ref_m0 ? (const T*)gp_m0v : (const T*)nullptr, g.mu, gp_dinv, gp_part);
+    const bool step_noise = noise_step && lp.noise_dev;
+    hipLaunchKernelGGL((k_gp_finish<T>), dim3(1), dim3(256), 0, st(), nb, (const double*)gp_part, m, gp_ref() ? 1 : 0, noise_eta,
+                       step_noise ? noise_adam : (double*)nullptr, lam_dev, gp_out);
+    LAUNCHCHK(ctx);
+    gp_valid = true;
+    gp_s2_fresh = !step_noise;
+    gp_sinv_valid = gp_sigma_valid = false;
+    g.pred_valid = g.predvar_valid = false;
+    return AGP_OK;
+  }
+  agp_status step_local(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, double, bool) override {
+    if (idx != nullptr || B != m) {
+      ctx->err = "exact GP (AGP_FLAG_EXACT): steps run on the whole training set (idx = NULL, B = N = m)";
+      return AGP_ERR_BAD_BATCH;
+    }
+    if (!y) return AGP_ERR_INVALID;
+    AGPCHK(gp_factor((const T*)y, true));
+    record_batch(y, 1.0);
+    return AGP_OK;
+  }
+  agp_status step_finish() override {  // (the whole Analytic step ran in step_local)
+    n_opt += 1;
+    return AGP_OK;
+  }
+  // Sigma^-1 = L^-T L^-1 of the current factor (the predictor's Apred, the hyper-gradient's)
+  agp_status gp_sinv() {
+    Latent& g = lat[0];
+    if (!gp_valid) AGPCHK(gp_factor(nullptr, false));
+    if (gp_sinv_valid) return AGP_OK;
+    if (!g.Apred) AGPCHK(dmalloc(ctx, &g.Apred, mp * mp));
+    AGPCHK(xtx_padded<T>(ctx, g.Xa, mp, mp, g.Apred, mp));
+    gp_sinv_valid = true;
+    return AGP_OK;
+  }
+  // predictions.jl:6-23: mu* = K*n alpha (mu0 not added back), var* = k** + jitt - diag(K*n Sigma^-1 Kn*): the streaming predictor
+  // with apred = alpha, Apred = Sigma^-1
+  agp_status ensure_pred(Latent& g, bool need_var) override {
+    if (!gp_valid) AGPCHK(gp_factor(nullptr, false));
+    if (!g.apred) AGPCHK(dmalloc(ctx, &g.apred, mp));
+    if (!g.pred_valid) {
+      HIPCHK(ctx, hipMemcpyAsync(g.apred, g.mu, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
+      g.pred_valid = true;
+    }
+    if (need_var && !g.predvar_valid) {
+      AGPCHK(gp_sinv());
+      g.predvar_valid = true;
+    }
+    return AGP_OK;
+  }
+  // objective(m::GP, _, y) = log_py (GP.jl:87-92) of the stored posterior.  y binds the targets of a handle that has taken no step
+  // yet (a reloaded model: post_step! with the restored sigma2); afterwards it is not read.
+  agp_status elbo(const void*, int64_t, const void* y, const int64_t*, int64_t, double, int, double* out) override {
+    if (!out) return AGP_ERR_INVALID;
+    if (y && !gp_have_r) AGPCHK(gp_factor((const T*)y, false));
+    else if (!gp_valid) AGPCHK(gp_factor(nullptr, false));
+    HIPCHK(ctx, hipMemcpyAsync(out, gp_out + 4, sizeof(double), hipMemcpyDeviceToHost, st()));
+    HIPCHK(ctx, hipStreamSynchronize(st()));
+    return AGP_OK;
+  }
+  // mu <- alpha, sigma <- Sigma (the posterior of GP.jl: Posterior(Sigma, alpha)); there are no natural parameters
+  agp_status get_state(int l, void* mu, void* sigma, void* eta1, void* eta2) override {
+    if (l < 0 || l >= nl) return AGP_ERR_INVALID;
+    if (eta1 || eta2) {
+      ctx->err = "exact GP (AGP_FLAG_EXACT): the posterior has no natural parameters (eta1 / eta2 must be NULL)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    Latent& g = lat[0];
+    if ((mu || sigma) && !gp_valid) AGPCHK(gp_factor(nullptr, false));
+    if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, g.mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
+    if (sigma) {
+      if (!gp_sigma_valid) {
+        hipLaunchKernelGGL((k_gp_shift<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp, (const T*)g.L,
+                           (const T*)gp_s2, (const T*)nullptr, (const T*)nullptr, g.Sigma, (T*)nullptr, (T*)nullptr);
+        LAUNCHCHK(ctx);
+        gp_sigma_valid = true;
+      }
+      HIPCHK(ctx, hipMemcpy2DAsync(sigma, sizeof(T) * m, g.Sigma, sizeof(T) * mp, sizeof(T) * m, m, hipMemcpyDeviceToDevice, st()));
+    }
+    return AGP_OK;
+  }
+  agp_status set_state(int, const void*, const void*) override {
+    ctx->err = "exact GP (AGP_FLAG_EXACT): the posterior follows from K, sigma2 and y; it has no natural parameters to set";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  // G1 corrected: d log p / d theta = tr((alpha alpha' - Sigma^-1) dK/dtheta) / 2 at the Sigma of the last step (kernel_grad with
+  // Apred = Sigma^-1, a = alpha).  Reference mode: the reference's gradient is `nothing` (zeros here).
+  agp_status hypergrad(int l, double* dvar, double* dscale, void* dZ_out) override {
+    AGPCHK(check_hypergrad(l, dZ_out));
+    if (gp_ref()) {
+      if (dvar) *dvar = 0.0;
+      if (dscale)
+        for (int64_t d = 0; d < D; ++d) dscale[d] = 0.0;
+      return AGP_OK;
+    }
+    AGPCHK(hyper_alloc());
+    AGPCHK(gp_sinv());
+    Latent& g = lat[0];
+    return kernel_grad(g, g.Apred, g.mu, nullptr, dvar, dscale);
+  }
+  // G1 in the reference mode: the kernel gradient is `nothing` -- kernel and optimiser state untouched, a caller-supplied gradient
+  // moves nothing either (after the argument checks of every handle)
+  agp_status hyper_step() override { return gp_ref() ? AGP_OK : Vgp::hyper_step(); }
+  agp_status hyper_apply(int l, const double* dvar, const double* dscale, const void* dZ) override {
+    if (!gp_ref()) return Vgp::hyper_apply(l, dvar, dscale, dZ);
+    return (l < 0 || l >= nl || !dvar || !dscale) ? AGP_ERR_INVALID : AGP_OK;
+  }
+  agp_status set_lik_param(double v) override {
+    AGPCHK(Vgp::set_lik_param(v));
+    gp_s2_fresh = false;  // (the closing refresh_K_explicit refactors with the new sigma2)
     return AGP_OK;
   }
 };
@@ -5711,7 +5708,8 @@ agp_status agp_svgp_create(agp_ctx* ctx, const agp_svgp_desc* desc, agp_svgp** o
     ctx->err = "AGP_FLAG_EXACT: exact GP regression is a full model (AGP_FLAG_FULL | AGP_FLAG_EXACT)";
     return AGP_ERR_UNSUPPORTED;
   }
-  if (desc->dtype == AGP_F64) impl = new Svgp<double>();
+  if (desc->flags & AGP_FLAG_FULL) impl = (desc->flags & AGP_FLAG_EXACT) ? new Gp() : new Vgp();
+  else if (desc->dtype == AGP_F64) impl = new Svgp<double>();
   else if (desc->dtype == AGP_F32) impl = new Svgp<float>();
   else return AGP_ERR_INVALID;
   impl->ctx = ctx;

@@ -235,6 +235,18 @@ def test_gp_refusals(env):
     assert L.agp_svgp_elbo_terms(h, out) == UNSUPPORTED
     with pytest.raises(ValueError, match="Gaussian Likelihood you should directly use the `GP` model"):
         AGP.VGP(X, y, AGP.SqExponentialKernel(), AGP.GaussianLikelihood(0.1), AGP.AnalyticVI())
+    # agp_svgp_create's refusals of exact descriptors (Logistic unless lik is given): the generic latent count answers first and
+    # writes no message; the exact model's check comes before the full model's
+    from test_gpu_vgp import create_status
+
+    G, FE = capi.LikDesc(capi.LIK_GAUSSIAN, 1, 0.05, 0.0), capi.FLAG_FULL | capi.FLAG_EXACT
+    for fields, status, msg in [(dict(flags=capi.FLAG_EXACT, lik=G), 5, "exact GP regression is a full model"),
+                                (dict(flags=FE), 5, "one latent and a Gaussian likelihood"),
+                                (dict(flags=FE, max_batch=32), 5, "one latent and a Gaussian likelihood"),
+                                (dict(flags=FE, lik=G, n_latent=2), 1, None),
+                                (dict(flags=FE, lik=G, max_batch=32), 1, "max_batch = m = N")]:
+        st, err = create_status(capi, **fields)
+        assert st == status and (msg in err if msg else err == ""), (fields, st, err)
 
 
 _CHILD = r"""

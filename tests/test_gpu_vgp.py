@@ -261,6 +261,37 @@ def test_vgp_refusals_and_unsupported(env):
     # nothing changed: the model still trains
     AGP.train_(m, 1, state=True)
     assert np.isfinite(AGP.objective(m))
+    # agp_svgp_create refuses these full descriptors; the generic checks (here nu) answer before the full model's own
+    G, ST = capi.LikDesc(capi.LIK_GAUSSIAN, 1, 0.1, 0.0), capi.LikDesc(capi.LIK_STUDENTT, 1, 0.4, 1.0)
+    for fields, status, msg in [(dict(dtype=capi.F32), 5, "the full model is Float64 only"),
+                                (dict(stochastic=1, rm_kappa=0.75, rm_tau=1.0), 1, "max_batch = m = N"),
+                                (dict(max_batch=32), 1, "max_batch = m = N"),
+                                (dict(latent_offset=1), 1, "max_batch = m = N"),
+                                (dict(lik=G), 5, "Gaussian Likelihood you should directly use the `GP` model"),
+                                (dict(lik=G, max_batch=32), 1, "max_batch = m = N"),
+                                (dict(lik=ST, max_batch=32), 1, "nu should be greater than 0.5")]:
+        st, err = create_status(capi, **fields)
+        assert st == status and msg in err, (fields, st, err)
+
+
+def create_status(capi, **fields):
+    """agp_svgp_create on a fresh context with a 64-point Logistic VGP descriptor, `fields` set on top -> (status, agp_last_error)"""
+    import torch
+
+    L = capi.lib()
+    ctx, h = C.c_void_p(), C.c_void_p()
+    assert L.agp_ctx_create(0, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(ctx)) == 0
+    try:
+        d = capi.SvgpDesc(dtype=capi.F64, n_latent=1, m=64, D=2, max_batch=64, lik=capi.LikDesc(capi.LIK_LOGISTIC, 1, 0.0, 0.0),
+                          flags=capi.FLAG_FULL)
+        for k, v in fields.items():
+            setattr(d, k, v)
+        st = L.agp_svgp_create(ctx, C.byref(d), C.byref(h))
+        if h.value:
+            L.agp_svgp_destroy(h)
+        return st, L.agp_last_error(ctx).decode()
+    finally:
+        L.agp_ctx_destroy(ctx)
 
 
 def test_vgp_8192(env):
