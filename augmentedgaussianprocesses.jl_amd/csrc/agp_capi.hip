@@ -68,7 +68,46 @@ struct agp_ctx {
   int32_t chain_exits = 0;
   int chain_state = 0;  // 0 not tried, 1 usable, -1 not available (the two streams do not run kernels side by side) / switched off
   int32_t chain_seq = 0;
+  // development aid (builds with -DAGP_STEP_TRACE, run with AGP_STEP_TRACE=<file>): a ring of STRACE_RECS stamp records, one per
+  // CAVI-step launch with a prologue (agp_chol.h, STRACE_*), written to the file by agp_ctx_destroy
+  unsigned long long* strace = nullptr;
+  unsigned long long* strace_last = nullptr;  // the record of the last launch (its deferred fallback stamps into it)
+  int64_t strace_n = 0;
 };
+
+#ifdef AGP_STEP_TRACE
+constexpr int64_t STRACE_RECS = 1024;
+static unsigned long long* step_trace_next(agp_ctx* c) {
+  static const char* path = getenv("AGP_STEP_TRACE");
+  if (!path || !path[0]) return nullptr;
+  const size_t bytes = sizeof(unsigned long long) * STRACE_SLOTS * STRACE_RECS;
+  if (!c->strace) {
+    if (hipMalloc((void**)&c->strace, bytes) != hipSuccess) return c->strace = nullptr;
+    (void)hipMemsetAsync(c->strace, 0, bytes, c->stream);
+  }
+  return c->strace + (c->strace_n++ % STRACE_RECS) * STRACE_SLOTS;
+}
+static void step_trace_dump(agp_ctx* c) {
+  const char* path = getenv("AGP_STEP_TRACE");
+  if (!c->strace || !path) return;
+  const int64_t n = std::min<int64_t>(c->strace_n, STRACE_RECS);
+  std::vector<unsigned long long> h((size_t)(STRACE_SLOTS * STRACE_RECS));
+  (void)hipDeviceSynchronize();
+  (void)hipMemcpy(h.data(), c->strace, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  if (FILE* f = fopen(path, "wb")) {  // records oldest first: [n, slots] as int64, then n x slots stamps
+    const int64_t hdr[2] = {n, STRACE_SLOTS};
+    fwrite(hdr, sizeof(hdr), 1, f);
+    for (int64_t i = c->strace_n - n; i < c->strace_n; ++i)
+      fwrite(h.data() + (i % STRACE_RECS) * STRACE_SLOTS, sizeof(unsigned long long), STRACE_SLOTS, f);
+    fclose(f);
+  }
+  (void)hipFree(c->strace);
+  c->strace = nullptr;
+}
+#else
+static unsigned long long* step_trace_next(agp_ctx*) { return nullptr; }
+static void step_trace_dump(agp_ctx*) {}
+#endif
 
 #define HIPCHK(ctx, expr)                                                                       \
   do {                                                                                          \
@@ -297,10 +336,19 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_safe_rowstats(CholBatch<T> bt,
                                                                 T* __restrict__ w, int* __restrict__ flags,
                                                                 const T* __restrict__ lam, T* __restrict__ gamma,
                                                                 int rows_done = 0, const int32_t* __restrict__ pf_word = nullptr,
-                                                                int32_t pf_want = 0) {
+                                                                int32_t pf_want = 0, const T* __restrict__ s00_kap = nullptr,
+                                                                int64_t s00_ldk = 0, int64_t s00_K = 0,
+                                                                const T* __restrict__ s00_w = nullptr, T* __restrict__ pre = nullptr,
+                                                                unsigned long long* trace = nullptr) {
   __shared__ __attribute__((aligned(16))) T sm[3 * TILE * LDP];
   __shared__ __attribute__((aligned(16))) T sc[SC_ELEMS];
   __shared__ T piv[TILE];
+#ifdef AGP_STEP_TRACE
+  if (trace && threadIdx.x == 0 && blockIdx.x < 256) trace[STRACE_SAFE0 + blockIdx.x] = wall_clock64();
+  StraceExit strace_exit{(trace && blockIdx.x < 256) ? trace + STRACE_SAFE1 + blockIdx.x : nullptr};
+#else
+  (void)trace;
+#endif
   const bool ran = chol_safe_body<T>(bt, src, 1, ld, ldx, lde, ne, nt, info, nvalid, bar, retries, sm, sc, piv);
   // (after a fallback the last grid barrier of the column loop has made every workgroup's tiles visible)
   // rows_done (round 3): the task-graph launch finished its rows itself (EpiArgs, agp_chol.h) -- unless it was aborted and re-run here
@@ -309,6 +357,13 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_safe_rowstats(CholBatch<T> bt,
     for (int64_t i = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); i < B; i += nwave)
       rowstats_row<T>(i, threadIdx.x & 63, 0, B, nslices, rb, ldp, ldw, cols, jitter, rho, lp, y, idx, Kt, muf, varf, cb, theta, r,
                       w, (int64_t)0, flags, lam, gamma);
+  }
+  // pre: the first three tiles of S = kappa' diag(w) kappa of the pending natural-gradient step (kappa s00_kap, weights s00_w = the
+  // w of the launch in front) for the head of the next launch (ProArgs::pre).  Not where this launch re-ran the fallback: its rows
+  // above are not visible to the other workgroups yet, and the next launch's three tiles form their products themselves
+  if (pro_pre_on<T>() && pre) {
+    if (!ran) pro_pre_prepare<T>(s00_kap, s00_ldk, s00_K, s00_w, pre, sm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) pre[PRO_PRE_VALID] = ran ? T(0) : T(1);
   }
   // pf_word (round 3): this launch was deferred to the head of the NEXT step and also carries that step's wait for its look-ahead
   // (one wave polls the look-ahead's "done" word; in the steady state it is set long before)
@@ -576,17 +631,20 @@ struct ProHost {
   int32_t arrive_want = 0;
   unsigned char grp[32] = {};
   T* Cout = nullptr;                           // ProArgs::Cout
+  const T* pre = nullptr;                      // ProArgs::pre
 };
 // k-slices per block column of the prologue's product: a tile of block column c has to be there when the chain reaches the
 // column (about tau * c after the start, tau = 17.8 us f64 / 14 us f32 per block column), a 64-row chunk of the product costs a
-// workgroup about tc = 2.7 / 1.6 us; columns 0 and 1 feed the chain at once and are split as far as it pays (8).
-static void pro_ks_table(int64_t nt, int64_t nq, bool f64, unsigned char* ks, unsigned char* kf) {
-  const double tc = f64 ? 2.7 : 1.6, tau = f64 ? 17.8 : 14.0;
+// workgroup about tc = 2.7 / 1.6 us; columns 0 and 1 feed the chain at once and are split as far as it pays (8).  pre: the
+// chain's first tiles were prepared by the launch in front (ProArgs::pre), so it reaches every column ~10 us sooner (measured at
+// C2: factor(0) done 20 instead of 30 us after the start; with the old table the feeders of block column 4 came 2.8 us late)
+static void pro_ks_table(int64_t nt, int64_t nq, bool f64, unsigned char* ks, unsigned char* kf, bool pre = false) {
+  const double tc = f64 ? 2.7 : 1.6, tau = f64 ? 17.8 : 14.0, head = pre ? 24.0 : 12.0;
   for (int64_t c = 0; c < nt && c < 32; ++c) {
     int want;
     if (c == 0) want = 8;
     else if (c == 1) want = f64 ? 4 : 8;
-    else want = (int)std::ceil((double)nq * (tc + 0.3) / (tau * (double)c - 12.0));
+    else want = (int)std::ceil((double)nq * (tc + 0.3) / std::max(tau * (double)c - head, 1.0));
     want = std::max(1, std::min<int>(want, (int)std::min<int64_t>(8, nq)));
     // the tiles next to the diagonal (ProArgs::kf) take the same split as their column (a finer one was measured at 32 block
     // columns, docs/DESIGN_LOG.md, and not adopted)
@@ -638,7 +696,7 @@ static agp_status potrf_fused(agp_ctx* c, T* A, int64_t ld, int64_t n, T* X, int
       if (pro->packed)
         for (int64_t cc = 0; cc < nt; ++cc) pa.ks[cc] = pa.kf[cc] = 1;  // nothing to compute: no helpers
       else
-        pro_ks_table(nt, pro->Kdim / TILE, sizeof(T) == 8, pa.ks, pa.kf);
+        pro_ks_table(nt, pro->Kdim / TILE, sizeof(T) == 8, pa.ks, pa.kf, pro->pre != nullptr);
       for (int64_t cc = 0; cc < nt; ++cc) nhelp += pro_nhelp(nt, cc, pa.ks[cc], pa.kf[cc]);
     }
     const int64_t nf = ((nt + ne + nx) * nt + 3 * nt + 1 + nhelp) * DAG_FS;
@@ -715,6 +773,7 @@ static agp_status potrf_fused(agp_ctx* c, T* A, int64_t ld, int64_t n, T* X, int
       pa.lr = pro->lr;
       pa.packed = pro->packed;
       pa.Cout = pro->Cout;
+      pa.pre = pro->pre;
       pa.tred = pro->tred;
       pa.arrive = pro->arrive;
       pa.arrive_want = pro->arrive_want;
@@ -728,7 +787,9 @@ static agp_status potrf_fused(agp_ctx* c, T* A, int64_t ld, int64_t n, T* X, int
         pa.nfill = 64;
         c->h_dirty[other].on = false;
       }
-      unsigned long long* const ptrace = nullptr;  // (wall-clock stamps of the prologue, PRO_TS in agp_chol.h: a development aid)
+      // (wall-clock stamps of the prologue and the step boundary, PRO_TS / STRACE in agp_chol.h: a development aid)
+      unsigned long long* const ptrace = step_inst ? step_trace_next(c) : nullptr;
+      c->strace_last = ptrace;
       constexpr unsigned lds_pad = 0;
       if (step_inst && chain_split_wanted(ntiles + nhelp, true, sizeof(T) == 8) && chain_split_ready(c)) {  // chain kernel + tile kernel (k_chol_dag, ROLE)
         // No event joins the chain stream behind a split launch (see chain_split_arm): correct only as long as the chain kernel
@@ -1499,15 +1560,36 @@ struct Svgp : SvgpBase {
     const int64_t* idx = nullptr;
     T *r = nullptr, *w = nullptr;
     unsigned grid = 1;
+    unsigned long long* trace = nullptr;  // (AGP_STEP_TRACE: the stamp record of the launch this one stands behind)
   } sdef;
-  agp_status run_deferred_safe(const int32_t* pf_word = nullptr, int32_t pf_want = 0) {
+  // The first tiles of the pending natural-gradient step's product, prepared by the deferred launch for the head of the next
+  // task-graph launch (ProArgs::pre: partial tiles + a validity element); s00_for names the pending step they belong to (kappa, w)
+  // -- only the launch that immediately follows uses them, every other consumer of the pending step computes as before
+  T* s00buf = nullptr;
+  struct {
+    bool on = false;
+    const T *kap = nullptr, *w = nullptr;
+    int64_t K = 0;
+  } s00_for;
+  agp_status run_deferred_safe(const int32_t* pf_word = nullptr, int32_t pf_want = 0, bool want_s00 = false) {
     if (!sdef.on) return AGP_OK;
     sdef.on = false;
+    s00_for.on = false;
+    // (the pending step is this launch's own: w is the row statistics' output the fallback would redo)
+    const bool s00 = pro_pre_on<T>() && want_s00 && pend.on && !pendp.on && pend.w == sdef.w && pend.Bq >= TILE && pend.Bq % TILE == 0;
+    if (s00 && !s00buf) AGPCHK(dmalloc<T>(ctx, &s00buf, PRO_PRE_VALID + 16));
     hipLaunchKernelGGL((k_safe_rowstats<T>), dim3(sdef.grid), dim3(CHOL_THREADS), 0, st(), sdef.bt, sdef.src, mp, mp, mp, sdef.ne,
                        sdef.nt, info_dev, m, ctx->safe_bar, ctx->safe_retries, sdef.B, sdef.ns, sdef.rb, ldp, mp, mp, (T)jitter,
                        sdef.rho, lp, sdef.y, sdef.idx, Kt, muf, varf, cbuf, theta, sdef.r, sdef.w, flags_dev, (const T*)lam_dev,
-                       gamma, 1, pf_word, pf_want);
+                       gamma, 1, pf_word, pf_want, s00 ? pend.kap : nullptr, (int64_t)mp, s00 ? pend.Bq : 0,
+                       s00 ? (const T*)pend.w : nullptr, s00 ? s00buf : nullptr, sdef.trace);
     LAUNCHCHK(ctx);
+    if (s00) {
+      s00_for.on = true;
+      s00_for.kap = pend.kap;
+      s00_for.w = pend.w;
+      s00_for.K = pend.Bq;
+    }
     return AGP_OK;
   }
   bool epi_allowed() const {
@@ -1536,6 +1618,7 @@ struct Svgp : SvgpBase {
   }
   agp_status flush() override {
     AGPCHK(run_deferred_safe());
+    s00_for.on = false;
     if (!pend.on && !pendp.on) return AGP_OK;
     Latent& g = lat[0];
     g.C_valid = false;
@@ -1563,6 +1646,7 @@ struct Svgp : SvgpBase {
       Latent& g = lat[0];
       g.C_valid = false;
       pend.on = true;
+      s00_for.on = false;  // (whatever was prepared belongs to an earlier pending step)
       pend.Bq = rup64(B_last);
       pend.lr = (T)cur_lr();
       pend.kap = g.kappa;
@@ -1760,7 +1844,7 @@ struct Svgp : SvgpBase {
     for (auto e : step_done)
       if (e) dcheck(hipEventDestroy(e), __LINE__);
     T* ps[] = {rbuf2, wbuf2, pw0, pw1, Kt, muf, varf, cbuf, theta, gamma, rbuf, wbuf, alpha, beta, gsum, alpha_save, emuf,
-               evarf, stats, Tw, Tw2, tmpv, lr_dev, Kstar, ppm, ppv, pmu, pvar};
+               evarf, stats, Tw, Tw2, tmpv, lr_dev, Kstar, ppm, ppv, pmu, pvar, s00buf};
     for (T* p : ps)
       if (p) dfree(p);
     T* hps[] = {hyH1, hyH2, hyH3, hy_gmu, hy_gs, hy_muf, hy_pZ, hy_dZ, hyKap, hyKnm, hy_upart, hy_pZ2};
@@ -2251,6 +2335,14 @@ struct Svgp : SvgpBase {
       if (chol_use_dag(ctx, mp / TILE, Bq / TILE + 1, q)) dag_nb = q;
     // single latent on the task graph: the launch itself tells the look-ahead stream that the step
     // before has released its kappa buffers (DagSync) -- no event record on this stream
+    // a pending natural-gradient step rides on this step's task-graph launch when this is the steady state of a training loop
+    // (kappa of the minibatch already there -- look-ahead or kept --, one latent on the task graph); otherwise it is taken now
+    const bool take_pend = (pend.on || pendp.on) && !fresh && nl == 1 && dag_nb > 0 &&
+                           (prefetched || (reuse && lat[0].kappa_valid)) && pro_allowed() && mp / TILE <= 32 &&
+                           (pendp.on || pend.Bq >= TILE);
+    // ... with the row statistics as its epilogue: then the previous step's deferred launch, whichever call below enqueues it, also
+    // prepares the head of this one (ProArgs::pre) -- in every protocol alike, so that the trajectory does not depend on which
+    const bool pre_want = take_pend && in_cavi_step && epi_allowed();
     StepSync ssync{};
     const bool sync_step = sig_state == 1 && !fresh && nl == 1 && dag_nb > 0 &&
                            !(lat[0].la_state == 1 && lat[0].xa_valid);
@@ -2261,31 +2353,28 @@ struct Svgp : SvgpBase {
       // the release of the previous step's kappa buffers becomes an event here, before anything of this step is enqueued (the
       // look-ahead waiting for it is meant to run next to this step's factorisation).  The previous step's deferred fallback goes
       // first: if it really re-runs it rewrites that step's Wbuf and reads its pk -- the buffers this event releases
-      AGPCHK(run_deferred_safe());
+      AGPCHK(run_deferred_safe(nullptr, 0, pre_want));
       slot_kind[rel_slot] = 0;
       HIPCHK(ctx, hipEventRecord(step_done[rel_slot], st()));
       rel_pending = false;
     }
-    // a pending natural-gradient step rides on this step's task-graph launch when this is the steady state of a training loop
-    // (kappa of the minibatch already there -- look-ahead or kept --, one latent on the task graph); otherwise it is taken now
     bool use_pro = false;
     if (pend.on || pendp.on) {
-      use_pro = !fresh && nl == 1 && dag_nb > 0 && (prefetched || (reuse && lat[0].kappa_valid)) && pro_allowed() &&
-                mp / TILE <= 32 && (pendp.on || pend.Bq >= TILE);
+      use_pro = take_pend;
       if (!use_pro) AGPCHK(flush());
     }
     // the row statistics of this step as the epilogue of its task-graph launch, the launch's fallback deferred to the next step
-    const bool use_epi = use_pro && in_cavi_step && epi_allowed();
+    const bool use_epi = pre_want;
     if (prefetched) {  // kappa of this minibatch was produced on the prefetch stream: adopt those buffers
       if (sig_state == 1) {  // (the look-ahead's completion word is polled in-stream; without signal memory: an event wait)
         if (sdef.on) {  // the previous step's deferred fallback launch carries this step's wait for its look-ahead
-          AGPCHK(run_deferred_safe((const int32_t*)sig[1], pf_seq));
+          AGPCHK(run_deferred_safe((const int32_t*)sig[1], pf_seq, use_epi));
         } else {
           hipLaunchKernelGGL(k_wait_ge_fast, dim3(1), dim3(64), 0, st(), (const int32_t*)sig[1], pf_seq, info_dev);
           LAUNCHCHK(ctx);
         }
       } else {
-        AGPCHK(run_deferred_safe());
+        AGPCHK(run_deferred_safe(nullptr, 0, use_epi));
         HIPCHK(ctx, hipStreamWaitEvent(st(), pf_done, 0));
       }
       for (auto& g : lat) {
@@ -2301,7 +2390,7 @@ struct Svgp : SvgpBase {
       }
       pf_valid = false;
     }
-    AGPCHK(run_deferred_safe());  // (full-batch steps: no look-ahead to wait for)
+    AGPCHK(run_deferred_safe(nullptr, 0, use_epi));  // (full-batch steps: no look-ahead to wait for)
     CholBatch<T> merged_bt{};  // single latent on the task graph: fallback + row statistics share a launch (k_safe_rowstats)
     SafeSrc<T> merged_src{};
     bool merged_safe = false;
@@ -2413,6 +2502,8 @@ struct Svgp : SvgpBase {
               ph.kap = pend.kap;
               ph.Kdim = pend.Bq;
               ph.w = pend.w;
+              if (use_epi && s00_for.on && s00_for.kap == pend.kap && s00_for.w == pend.w && s00_for.K == pend.Bq)
+                ph.pre = s00buf;  // prepared by the deferred launch just enqueued (run_deferred_safe)
               ph.r = pend.r;
               ph.Kinv = pend.Kinv;
               ph.kinv_mu0 = pend.kinv_mu0;
@@ -2452,6 +2543,7 @@ struct Svgp : SvgpBase {
           AGPCHK(potrf_fused<T>(ctx, bt.A[0], mp, mp, bt.X[0], mp, bt.Dg[0], bt.E[0], mp, nel, 0, info_dev, m,
                                 (const T*)lat[todo[l0]].eta1, false, &src, &defer, sync_step ? &ssync : nullptr,
                                 use_pro ? &ph : nullptr, use_epi ? &ea : nullptr));
+          s00_for.on = false;
           if (use_pro) {  // the launch has taken the pending step (had it been refused, the step would still be pending for flush())
             pend.on = pendp.on = pendp.overlap = false;
             n_prologue += 1;
@@ -2507,6 +2599,7 @@ struct Svgp : SvgpBase {
           sdef.r = rbuf;
           sdef.w = wbuf;
           sdef.grid = g1;
+          sdef.trace = ctx->strace_last;
           continue;
         }
         hipLaunchKernelGGL((k_safe_rowstats<T>), dim3(g1), dim3(CHOL_THREADS), 0, st(), merged_bt, merged_src, mp, mp, mp, ne_, nt_,
@@ -3643,6 +3736,7 @@ struct Svgp : SvgpBase {
     }
     if (use_pro) {  // taken by the launch (a refused launch leaves it pending for flush())
       pend.on = false;
+      s00_for.on = false;
       n_prologue += 1;
       if (ph.Cout) {
         g.C_valid = true;
@@ -3701,8 +3795,10 @@ struct Svgp : SvgpBase {
         rel_pending = true;
         rel_slot = step_parity ^ 1;
       } else {
-        // (the step's deferred fallback, if it re-runs, rewrites the step's Wbuf and reads its pk: before the event releases them)
-        AGPCHK(run_deferred_safe());
+        // (the step's deferred fallback, if it re-runs, rewrites the step's Wbuf and reads its pk: before the event releases them;
+        //  it also prepares the head of the next launch, as the word protocol's deferred launch would -- ProArgs::pre -- in case
+        //  that launch takes the pending step: the trajectory must not depend on the protocol)
+        AGPCHK(run_deferred_safe(nullptr, 0, true));
         slot_kind[step_parity ^ 1] = 0;
         HIPCHK(ctx, hipEventRecord(step_done[step_parity ^ 1], st()));
       }
@@ -4612,6 +4708,7 @@ struct Svgp : SvgpBase {
     if (merge) {
       Latent& g = lat[0];
       pendp.on = true;
+      s00_for.on = false;
       pendp.overlap = overlap;
       pendp.epoch = arrive_epoch;
       pendp.cm = cm;
@@ -5195,6 +5292,7 @@ agp_status agp_ctx_create(int32_t device, void* hip_stream, agp_ctx** out) {
 agp_status agp_ctx_destroy(agp_ctx* ctx) {
   if (!ctx) return AGP_OK;
   DevGuard guard(ctx->device);
+  step_trace_dump(ctx);
   if (ctx->tri_scratch || ctx->dag_flags || ctx->hset[0]) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->dag_flags) (void)hipFree(ctx->dag_flags);

@@ -1686,7 +1686,71 @@ struct ProArgs {
   // hyper-parameter iteration (round 4): C = S + K^-1 / 4 of the step, S = kappa' diag(w) kappa, both triangles (ld = ldm).  The
   // hyper-gradient's G_K then needs ONE m^3 product, C (Sigma K^-1), where it took kappa' H and K^-1 Sigma K^-1 (hypergrad)
   T* Cout = nullptr;
+  // (nullable) the chain's first three tiles of S = kappa' diag(w) kappa -- (0, 0), (1, 0), (1, 1): the head of the launch and
+  // the two feeders of block column 1 -- prepared by the launch in front of this one (pro_pre_prepare, k_safe_rowstats) as
+  // PRO_PRE_KS partial tiles each, then a validity element (1: prepared; 0: that launch re-ran the task graph's fallback, so its w
+  // was not final where the product read it).  The three tiles add their partials instead of forming a k-slice and waiting for
+  // helpers -- the head of the chain shrinks to "load, add, eta step" -- and, where the partials are not valid, form the whole
+  // product themselves; their helpers have nothing to do either way.
+  const T* pre = nullptr;
 };
+
+// ProArgs::pre: tile (R, c) in {(0, 0), (1, 0), (1, 1)} -> slot 0, 1, 2; partial q of slot s at (s * PRO_PRE_KS + q) * 64 * 64.
+// fp64 only (the fp32 split tile kernel is at its 128-register bound already: the partials in flight made it spill)
+constexpr int PRO_PRE_KS = 4, PRO_PRE_VALID = 3 * PRO_PRE_KS * TILE * TILE;
+template <typename T>
+constexpr bool pro_pre_on() { return sizeof(T) == 8; }
+__host__ __device__ __forceinline__ bool pro_pre_tile(int64_t R, int64_t c) { return R <= 1 && c <= 1; }
+// The partials, for ProArgs::pre: 3 tiles x PRO_PRE_KS row quarters x sixteen 16 x 16 blocks = 192 units of work, one per
+// workgroup of a grid of any size (grid-stride).  In a unit every wave takes a contiguous eighth of its rows straight from memory
+// into the matrix unit (A[i][k] = w_k kappa(k, R0 + i), B[k][j] = kappa(k, c0 + j)), and the eight partial blocks are then added in
+// wave order; the consumer adds the PRO_PRE_KS partials in their order: a fixed summation order, bitwise reproducible.
+// red: 8 * 256 elements of LDS.
+template <typename T>
+__device__ __forceinline__ void pro_pre_prepare(const T* __restrict__ kap, int64_t ldk, int64_t K, const T* __restrict__ w,
+                                                T* __restrict__ out, T* red) {
+  typedef typename Mfma<T>::acc_t acc_t;
+  constexpr int NW = CHOL_THREADS / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int u = blockIdx.x; u < 3 * PRO_PRE_KS * 16; u += gridDim.x) {
+    const int sl = u / (PRO_PRE_KS * 16), q = (u / 16) % PRO_PRE_KS, bi = (u >> 2) & 3, bj = u & 3;
+    const int64_t R0 = sl == 0 ? 0 : TILE, c0 = sl == 2 ? TILE : 0;
+    if (R0 + TILE > ldk) continue;  // (one block column: no tiles (1, 0), (1, 1); workgroup-uniform)
+    const int64_t kq0 = K * q / PRO_PRE_KS, kq1 = K * (q + 1) / PRO_PRE_KS;
+    const int64_t k0 = kq0 + (kq1 - kq0) * wave / NW, k1 = kq0 + (kq1 - kq0) * (wave + 1) / NW;
+    const T* __restrict__ pa = kap + R0 + 16 * bi + (lane & 15);
+    const T* __restrict__ pb = kap + c0 + 16 * bj + (lane & 15);
+    acc_t acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = T(0);
+    // (32 rows per round: every load of a round is issued before its first product -- one memory round trip per round, not per
+    //  four rows; wave-uniform trip count, rows past k1 read row k0 and contribute zero)
+    constexpr int U = 8;
+    for (int64_t kb = k0; kb < k1; kb += 4 * U) {
+      T av[U], bv[U], wv[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        const int64_t kk = kb + 4 * j + (lane >> 4), kc = kk < k1 ? kk : k0;
+        wv[j] = kk < k1 ? w[kc] : T(0);
+        av[j] = pa[kc * ldk];
+        bv[j] = pb[kc * ldk];
+      }
+#pragma unroll
+      for (int j = 0; j < U; ++j) acc = Mfma<T>::mma(wv[j] * av[j], bv[j], acc);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave * 256 + Mfma<T>::row(lane, r) * 16 + (lane & 15)] = acc[r];
+    __syncthreads();
+    if (threadIdx.x < 256) {
+      const int e = threadIdx.x;
+      T v = red[e];
+#pragma unroll
+      for (int o = 1; o < NW; ++o) v += red[o * 256 + e];
+      out[(int64_t)(sl * PRO_PRE_KS + q) * TILE * TILE + (16 * bi + (e >> 4)) * TILE + 16 * bj + (e & 15)] = v;
+    }
+    __syncthreads();
+  }
+}
 
 // The gate of AGP_SPLIT_OVERLAP.  It is NOT one of the task graph's abortable waits: what it waits for was enqueued before this
 // launch and depends on nothing in it, and a workgroup that gave up here would leave its tile of eta2 un-stepped for the in-stream
@@ -1801,6 +1865,28 @@ struct ProdArgs {
   int32_t* status = nullptr;
 };
 
+// Development aid, compiled in only with -DAGP_STEP_TRACE (agp_capi.hip: AGP_STEP_TRACE=<file> then names the dump): wall-clock
+// stamps (100 MHz) across the boundary between two CAVI-step launches with a prologue, one record of STRACE_SLOTS words per launch.
+//   [0, 2048)     PRO_TS's points (below), X_{nt-1} published (STRACE_XPUB), per extension row R of the last block column
+//                 (STRACE_EXT + 4 (R - nt) + q): q = 0 X seen, 1 W stored and signalled, 2 v tile read (epilogue), 3 rows finished;
+//                 refill workgroup b: start STRACE_FILL0 + b, end STRACE_FILL1 + b
+//   [2048, 4096)  start, [4096, 6144) exit of workgroup b (b < 2048)
+//   [6144, 6400)  start, [6400, 6656) end of workgroup b of the deferred fallback / row-statistics launch behind it (k_safe_rowstats)
+constexpr int STRACE_SLOTS = 8192, STRACE_XPUB = 600, STRACE_EXT = 1100, STRACE_FILL0 = 1400, STRACE_FILL1 = 1500, STRACE_WG0 = 2048,
+              STRACE_WG1 = 4096, STRACE_MAXWG = 2048, STRACE_SAFE0 = 6144, STRACE_SAFE1 = 6400;
+#ifdef AGP_STEP_TRACE
+struct StraceExit {  // stamps the exit of its workgroup, whichever return it leaves by
+  unsigned long long* p;
+  __device__ ~StraceExit() {
+    if (p && threadIdx.x == 0) *p = wall_clock64();
+  }
+};
+#define STRACE(i) \
+  if (PRO && ROLE == 0 && trace && threadIdx.x == 0) trace[i] = wall_clock64()
+#else
+#define STRACE(i)
+#endif
+
 template <typename T, bool FUSED, bool BATCH = false, bool TRACE = false, bool STEP = false, bool PRO = false, int ROLE = 0>
 __global__ __launch_bounds__(CHOL_THREADS, (dag_min_waves<T, ROLE, PRO>()))
 void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ldx,
@@ -1887,6 +1973,10 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   T* bufA = sm;
   T* bufB = sm + TILE * LDP;
   const int tid = threadIdx.x;
+#ifdef AGP_STEP_TRACE
+  StraceExit strace_exit{(PRO && ROLE == 0 && trace && bidx < STRACE_MAXWG) ? trace + STRACE_WG1 + bidx : nullptr};
+  if (bidx < STRACE_MAXWG) STRACE(STRACE_WG0 + bidx);
+#endif
   // column-major tile numbering: column c holds its diagonal tile, rows c+1..nt-1, then the ne extension blocks
   // (PRO: the (nt - c)(ks[c] - 1) helper workgroups of a column come right before its tiles; refill workgroups after everything)
   int64_t b = bidx, c = 0;
@@ -1906,7 +1996,9 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
     for (;;) {
       if (c == nt) {  // trailing workgroups: the hand-over set the launch before this one used gets its sentinels back
         const T sv = __builtin_bit_cast(T, Sent<T>::bits);
+        if (b < 64) STRACE(STRACE_FILL0 + b);
         for (int64_t i = b * CHOL_THREADS + tid; i < pro.fill_n; i += (int64_t)pro.nfill * CHOL_THREADS) pro.fill[i] = sv;
+        if (b < 64) STRACE(STRACE_FILL1 + b);
         return;
       }
       const int64_t nh = pro_nhelp(nt, c, pro.ks[c], pro.kf[c]), ntile = nt - c + ne + (nx ? c + 1 : 0);
@@ -1937,6 +2029,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
     const int ksc = near ? kfc : kso;
     const int64_t bo = near ? b : b - nn * (kfc - 1);
     const int64_t tb = (near ? 0 : nn) + bo / (ksc - 1), sl = 1 + bo % (ksc - 1), nq = pro.Kdim / TILE;
+    if (pro_pre_on<T>() && pro.pre && pro_pre_tile(c + tb, c)) return;  // their tile does not wait for them (ProArgs::pre)
     Acc8<T> S;
     S.zero();
     if (c == 0 && b == 0) PRO_TS(1024);
@@ -2041,12 +2134,35 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   } else if (PRO && !ext) {
     // ---- prologue of a matrix tile: S(R, c) (own k-slice + the helpers' partial tiles), the eta2 step, A = -2 eta2 -> acc
     const int64_t ntc_ = nt - c, nn_ = ntc_ < PRO_NEAR ? ntc_ : PRO_NEAR;
-    const int ksc = b < nn_ ? pro.kf[c] : pro.ks[c];
+    const bool pre = pro_pre_on<T>() && pro.pre && pro_pre_tile(R, c);  // prepared by the launch in front (ProArgs::pre): no helpers
+    const int ksc = pre ? 1 : b < nn_ ? pro.kf[c] : pro.ks[c];
     const int64_t nq = pro.Kdim / TILE;
     const int tsb = chain ? 0 : (R < 4 && c < 4) ? 64 + 8 * (4 * (int)R + (int)c) : 2040;
     PRO_TS(tsb);
     acc.zero();
-    pro_slice<T>(pro.kap, pro.ldk, pro.w, R * TILE, c0, 0, nq / ksc, sm, acc);
+    if (pre && pro.pre[PRO_PRE_VALID] == T(1)) {
+      const T* __restrict__ pp = pro.pre + (R + c) * PRO_PRE_KS * TILE * TILE;
+      T pv[PRO_PRE_KS][8];  // (all loads in flight before the first add)
+      int e = 0;
+      acc8_foreach<T>(acc, [&](int r, int cc, T& val) {
+        (void)val;
+#pragma unroll
+        for (int q = 0; q < PRO_PRE_KS; ++q) pv[q][e] = pp[q * TILE * TILE + r * TILE + cc];
+        ++e;
+      });
+      e = 0;
+      acc8_foreach<T>(acc, [&](int r, int cc, T& val) {
+        (void)r;
+        (void)cc;
+        T v = pv[0][e];
+#pragma unroll
+        for (int q = 1; q < PRO_PRE_KS; ++q) v += pv[q][e];
+        val = v;
+        ++e;
+      });
+    } else {  // (pre not valid: the whole product, ksc = 1)
+      pro_slice<T>(pro.kap, pro.ldk, pro.w, R * TILE, c0, 0, nq / ksc, sm, acc);
+    }
     if (pro.packed) {  // the reduced statistic of this tile (what k_eta2_from_packed reads)
       if (pro.arrive) pro_arrival_gate(pro.arrive, pro.grp[c], pro.arrive_want, info);
       const T* __restrict__ tp = pro.packed + pack_index(R, c, nt) * (TILE * TILE);
@@ -2245,6 +2361,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
         }
         dag_signal(xready + k * DAG_FS, epoch);
         DAG_TRC(k, 3);
+        STRACE(STRACE_XPUB);
         if (ROLE == 1) chain_count_out(sync);
         return;
       }
@@ -2402,6 +2519,9 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   }
   if (!dag_wait(xready + c * DAG_FS, nullptr, epoch, abortf, info, &wait_ok)) return;
   DAG_TR(2);
+  const bool strace_row = ext && !idr && c == nt - 1 && R - nt < 64;  // (AGP_STEP_TRACE: the boundary's extension rows)
+  (void)strace_row;
+  if (strace_row) STRACE(STRACE_EXT + 4 * (R - nt));
   load_tile_lds_hv<T>(HX + c * SLOT, bufB);
   __syncthreads();
   DAG_TR(6);
@@ -2423,6 +2543,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   DAG_TR(7);
   dag_signal(ready + (R * nt + c) * DAG_FS, epoch);
   DAG_TR(3);
+  if (strace_row) STRACE(STRACE_EXT + 4 * (R - nt) + 1);
   if (epi_row) {
     // own tile W(R, nt-1) (still in the accumulators) through LDS, the last piece of v from the tile of the [eta1' ; 0] row in
     // this block column (solved by its own workgroup at about the same time: its slot validates itself), then the 64 rows
@@ -2430,6 +2551,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
     acc8_foreach<T>(out, [&](int r, int cc, T& val) { bufA[r * LDP + cc] = val; });
     __syncthreads();
     epi_acc(bufA, HL + ((nt + ne - 1) * nt + c) * SLOT);
+    STRACE(STRACE_EXT + 4 * (R - nt) + 2);
     const int64_t i = (R - nt) * TILE + er;
     T sk = epi_sk;
 #pragma unroll
@@ -2443,6 +2565,10 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       rowstats_finish<T>(i, epi_ss, epi_dt, sk, kd, epi.use_kt, epi.jitter, epi.rho, epi.lp, epi.y, epi.idx, epi.Kt, epi.muf,
                          epi.varf, epi.cb, epi.theta, epi.r, epi.w, epi.flags, epi.lam, epi.gamma, &epi_y);
     }
+#ifdef AGP_STEP_TRACE
+    __syncthreads();  // every row of the block is finished
+    STRACE(STRACE_EXT + 4 * (R - nt) + 3);
+#endif
   }
 #undef DAG_TR
 #undef DAG_TRC

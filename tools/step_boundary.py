@@ -1,0 +1,117 @@
+"""Development aid: the boundary between two C2 step launches, from device wall-clock stamps.
+
+    (build the library with -DAGP_STEP_TRACE)
+    python tools/step_boundary.py run  DUMP [--steps N] [--warmup W]    C2-shaped training with AGP_STEP_TRACE=DUMP
+    python tools/step_boundary.py table DUMP [DUMP2 ...]                  the stamp table (agp_chol.h, STRACE_*)
+
+`run` trains the bench's C2 model (bench.make_data / bench.build_model, look-ahead on, as bench.py does) and destroys the context,
+which writes the dump.  `table` averages the last launches of each dump; every time is in us relative to the end of the chain's
+last tile elimination, factor(nt - 1), of the same launch ("next" rows: of the launch before)."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+XPUB, EXT, FILL0, FILL1, WG0, WG1, SAFE0, SAFE1 = 600, 1100, 1400, 1500, 2048, 4096, 6144, 6400
+
+
+def run(dump, steps, warm):
+    import ctypes as C
+
+    import torch
+
+    sys.path.insert(0, ROOT)
+    os.environ["AGP_STEP_TRACE"] = os.path.abspath(dump)
+    import bench
+    import agp_amd as AGP
+    from agp_amd import capi
+    from agp_amd import parallel as P
+
+    L = capi.lib()
+    dev = torch.device("cuda", 0)
+    cfg = dict(bench.CONFIGS["c2"])
+    N, m, B = cfg["N"], cfg["m"], cfg["B"]
+    X, yh, ell = bench.make_data(cfg, 1234, dev)
+    rng = np.random.default_rng(4321)
+    Z = X[torch.as_tensor(rng.permutation(N)[:m], device=dev)].cpu().numpy().astype(np.float64)
+    total = steps + warm
+    idx_all = torch.as_tensor(np.stack([rng.choice(N, B, replace=False) for _ in range(total)]).astype(np.int64), device=dev)
+    model = bench.build_model(AGP, cfg, ell, Z, B, 0, 1, 0, "batch")
+    model.inference.rho = N / B
+    eng = P.HipEngine(model, B).bind_data(X, yh)
+    h = eng.h
+    xp, yp, ld = C.c_void_p(eng._X.data_ptr()), C.c_void_p(eng._y.data_ptr()), eng._X.stride(0)
+    for i in range(total):
+        st = L.agp_svgp_cavi_step(h, xp, ld, yp, C.c_void_p(idx_all[i].data_ptr()), B, N / B)
+        if st != 0:
+            capi.check(model._ctx, st)
+        if i + 1 < total:
+            L.agp_svgp_prefetch(h, xp, ld, C.c_void_p(idx_all[i + 1].data_ptr()), B)
+    model._chk(L.agp_svgp_check_status(h))
+    fb = C.c_int64(0)
+    model._chk(L.agp_ctx_task_graph_fallbacks(model._ctx, C.byref(fb)))
+    torch.cuda.synchronize()
+    print(f"[step_boundary] {total} steps, task_graph_fallbacks {fb.value}", flush=True)
+    capi.lib().agp_svgp_destroy(model._h)
+    model._h = None
+    capi.lib().agp_ctx_destroy(model._ctx)
+    model._ctx = None
+
+
+def load(dump):
+    with open(dump, "rb") as f:
+        n, slots = np.fromfile(f, dtype=np.int64, count=2)
+        r = np.fromfile(f, dtype=np.uint64, count=int(n * slots)).reshape(int(n), int(slots)).astype(np.float64)
+    r[r == 0] = np.nan
+    return r
+
+
+def table(dumps, last=200, nt=16, ne=17):
+    rows = []
+    for dump in dumps:
+        r = load(dump)[-last - 1:]
+        cur, prev = r[1:], r[:-1]
+        f_end = cur[:, 512 + nt - 1]  # factor(nt - 1) done
+        us = lambda a: (a - f_end[:, None] if a.ndim == 2 else a - f_end) * 0.01  # 100 MHz ticks -> us
+        pf_end = prev[:, 512 + nt - 1]
+        pus = lambda a: (a - pf_end[:, None] if a.ndim == 2 else a - pf_end) * 0.01
+
+        def med(x):
+            x = x[np.isfinite(x)]
+            return float(np.median(x)) if x.size else float("nan")
+
+        out = [f"== {os.path.basename(dump)}: {len(cur)} launches; median us relative to factor({nt - 1}) done =="]
+        out.append(f"  launch t:   first workgroup start           {med(np.nanmin(us(cur[:, WG0:WG1]), axis=1)):8.2f}")
+        out.append(f"              chain start (tile 0,0)          {med(us(cur[:, 0])):8.2f}")
+        out.append(f"              tile (0,0) ready (eta2 step)    {med(us(cur[:, 4])):8.2f}")
+        out.append(f"              factor(0) done                  {med(us(cur[:, 512])):8.2f}")
+        out.append(f"              factor({nt - 1}) done                 {0.0:8.2f}")
+        out.append(f"              X_{nt - 1} published                 {med(us(cur[:, XPUB])):8.2f}")
+        ext = lambda q: us(cur[:, EXT + 4 * np.arange(ne) + q])
+        for q, what in enumerate(("X seen", "W stored + signalled", "v tile read (epilogue)", "rows finished")):
+            e = ext(q)
+            if q >= 2:
+                e = e[:, :ne - 1]  # (the [eta1' ; 0] row has no epilogue)
+            out.append(f"              ext rows (R,{nt - 1}) {what:<23} first {med(np.nanmin(e, axis=1)):8.2f}  last "
+                       f"{med(np.nanmax(e, axis=1)):8.2f}")
+        out.append(f"              refill workgroups start / end   {med(np.nanmin(us(cur[:, FILL0:FILL0 + 64]), axis=1)):8.2f} "
+                   f"{med(np.nanmax(us(cur[:, FILL1:FILL1 + 64]), axis=1)):8.2f}")
+        out.append(f"              last workgroup exit             {med(np.nanmax(us(cur[:, WG1:SAFE0]), axis=1)):8.2f}")
+        out.append(f"  behind it:  k_safe_rowstats start / end    {med(np.nanmin(us(cur[:, SAFE0:SAFE1]), axis=1)):8.2f} "
+                   f"{med(np.nanmax(us(cur[:, SAFE1:SAFE1 + 256]), axis=1)):8.2f}")
+        out.append(f"  launch t+1: first workgroup start           {med(np.nanmin(pus(cur[:, WG0:WG1]), axis=1)):8.2f}")
+        out.append(f"              tile (0,0) ready (eta2 step)    {med(pus(cur[:, 4])):8.2f}")
+        out.append(f"              factor(0) done                  {med(pus(cur[:, 512])):8.2f}")
+        rows += out
+    return "\n".join(rows)
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "run":
+        a = sys.argv[2:]
+        steps = int(a[a.index("--steps") + 1]) if "--steps" in a else 200
+        warm = int(a[a.index("--warmup") + 1]) if "--warmup" in a else 20
+        run(a[0], steps, warm)
+    else:
+        print(table(sys.argv[2:]))
