@@ -4196,6 +4196,13 @@ struct Svgp : SvgpBase {
   }
 
   agp_status get_matrix(int l, int which, void* out, int64_t ldo, int64_t cap) override {
+    if (mo && (which == AGP_VEC_THETA || which == AGP_VEC_C)) {
+      // multi-output (MOSVGP, MOVGP): the local variables belong to the task likelihoods, `l` counts the tasks
+      if (l < 0 || l >= nT || !out || B_last <= 0 || cap < B_last) return AGP_ERR_INVALID;
+      HIPCHK(ctx, hipMemcpyAsync(out, (which == AGP_VEC_THETA ? mo_th : mo_cc) + (int64_t)l * Bp, sizeof(T) * B_last,
+                                 hipMemcpyDeviceToDevice, st()));
+      return AGP_OK;
+    }
     if (l < 0 || l >= nl || !out || cap <= 0) return AGP_ERR_INVALID;
     Latent& g = lat[l];
     const int64_t B = B_last;
@@ -4880,14 +4887,15 @@ struct Svgp : SvgpBase {
 // VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85, Float64 only: the SVGP handle without K_nm, kappa, K~
 struct Vgp : Svgp<double> {
   using T = double;
-  T* vgp_part = nullptr;  // [2][ns][mp] partial column sums of k_vgp_colstats (colstats_part)
+  T* vgp_part = nullptr;  // [part_sets()][2][ns][mp] partial column sums of k_vgp_colstats (colstats_part)
+  virtual int part_sets() const { return 1; }  // one set serves every latent in turn (Vgp, Gp); one per latent in Movgp
   Vgp() { sparse_bufs = false; }
   ~Vgp() override {
     if (vgp_part) dfree(vgp_part);
   }
   // what a full model takes: AnalyticVI, max_batch = m = N and all of its latents on this handle
   agp_status check_full() {
-    if (desc.stochastic || Bmax != m || lp.kind == AGP_LIK_MULTIOUTPUT || desc.latent_offset != 0) {
+    if (desc.stochastic || Bmax != m || desc.latent_offset != 0) {
       ctx->err = "AGP_FLAG_FULL: the full model takes AnalyticVI, max_batch = m = N and all of its latents on one handle";
       return AGP_ERR_INVALID;
     }
@@ -4906,7 +4914,7 @@ struct Vgp : Svgp<double> {
   agp_status colstats_part(int* ns) {
     const int64_t ntc = mp / TILE;
     *ns = (int)std::max<int64_t>(1, std::min<int64_t>(ntc, (2048 + ntc - 1) / ntc));
-    if (!vgp_part) AGPCHK(dmalloc(ctx, &vgp_part, 2 * (int64_t)*ns * mp));
+    if (!vgp_part) AGPCHK(dmalloc(ctx, &vgp_part, 2 * (int64_t)*ns * mp * part_sets()));
     return AGP_OK;
   }
   void record_batch(const void* y, double rho) {  // every step's batch: the whole training set (x = Z, idx = NULL, B = N)
@@ -4941,11 +4949,9 @@ struct Vgp : Svgp<double> {
     g.v_epoch = g.xa_epoch;
     return AGP_OK;
   }
-  // update_parameters!(::VGP) first half (training.jl:140-144): local_updates! on mean_f = mu, var_f = diag Sigma of the current
-  // posterior (latentgp.jl:171-189).  The factor of -2 eta2 and its inverse come from the factorisation (or from the last
-  // materialize(), which left them); mu and diag Sigma from one pass over the lower triangle of Xa (k_vgp_colstats), which feeds the
-  // point-wise likelihood update directly.  The whole training set every time: idx = NULL, B = N.
-  agp_status step_local(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, double rho, bool fresh) override {
+  // what every local phase of a full model starts with: the whole training set (idx = NULL, B = N), the kernel matrices when the
+  // kernel moved, the previous step's deferred fallback
+  agp_status step_begin(const void* y, const int64_t* idx, int64_t B, bool fresh) {
     if (idx != nullptr || B != m) {
       ctx->err = "full model (AGP_FLAG_FULL): steps and ELBO evaluations run on the whole training set (idx = NULL, B = N = m)";
       return AGP_ERR_BAD_BATCH;
@@ -4957,19 +4963,33 @@ struct Vgp : Svgp<double> {
     const agp_status rks = refresh_K();
     refresh_lazy = false;
     AGPCHK(rks);
-    AGPCHK(run_deferred_safe());
+    return run_deferred_safe();
+  }
+  // one latent's factor of -2 eta2 with its inverse when it is not at hand, v = Xa eta1, and the k_vgp_colstats pass into the ns
+  // slices part[0][ns][mp] (sum Xa^2) and part[1][ns][mp] (sum Xa v)
+  agp_status colstats(Latent& g, int ns, T* part) {
+    const int64_t ntc = mp / TILE, rows = (mp + ns - 1) / ns;
+    if (!(g.la_state == 1 && g.xa_valid)) AGPCHK(vgp_factor(g));
+    if (g.v_epoch != g.xa_epoch) {
+      hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xa, mp, mp, (const T*)g.eta1, g.v);
+      g.v_epoch = g.xa_epoch;
+    }
+    hipLaunchKernelGGL((k_vgp_colstats<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), mp, (const T*)g.Xa,
+                       (const T*)g.v, rows, part, part + (int64_t)ns * mp);
+    LAUNCHCHK(ctx);
+    return AGP_OK;
+  }
+  // update_parameters!(::VGP) first half (training.jl:140-144): local_updates! on mean_f = mu, var_f = diag Sigma of the current
+  // posterior (latentgp.jl:171-189).  The factor of -2 eta2 and its inverse come from the factorisation (or from the last
+  // materialize(), which left them); mu and diag Sigma from one pass over the lower triangle of Xa (k_vgp_colstats), which feeds the
+  // point-wise likelihood update directly.  The whole training set every time: idx = NULL, B = N.
+  agp_status step_local(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, double rho, bool fresh) override {
+    AGPCHK(step_begin(y, idx, B, fresh));
     int ns = 0;
     AGPCHK(colstats_part(&ns));
-    const int64_t ntc = mp / TILE, rows = (mp + ns - 1) / ns;
     for (int l = 0; l < nl; ++l) {
       Latent& g = lat[l];
-      if (!(g.la_state == 1 && g.xa_valid)) AGPCHK(vgp_factor(g));
-      if (g.v_epoch != g.xa_epoch) {
-        hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xa, mp, mp, (const T*)g.eta1, g.v);
-        g.v_epoch = g.xa_epoch;
-      }
-      hipLaunchKernelGGL((k_vgp_colstats<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), mp, (const T*)g.Xa,
-                         (const T*)g.v, rows, vgp_part, vgp_part + (int64_t)ns * mp);
+      AGPCHK(colstats(g, ns, vgp_part));
       hipLaunchKernelGGL((k_vgp_local<T>), grid1(m), dim3(256), 0, st(), m, mp, ns, (const T*)vgp_part,
                          (const T*)(vgp_part + (int64_t)ns * mp), (T)rho, lp, (const T*)y, Kt + l * Bp, muf + l * Bp,
                          varf + l * Bp, cbuf + l * Bp, theta + l * Bp, rbuf + l * Bp, wbuf + l * Bp, (const T*)lam_dev,
@@ -5051,6 +5071,39 @@ struct Vgp : Svgp<double> {
     LAUNCHCHK(ctx);
     return hypergrad_to_host(dvar, dscale);
   }
+};
+
+// ---- multi-output full model (AGP_FLAG_FULL with AGP_LIK_MULTIOUTPUT: MOVGP, src/models/MOVGP.jl) ------------------------------
+// MOVGP(X, y, kernel, likelihoods, AnalyticVI(), num_latent): Q full latents on the training inputs, mixed by A into one output per
+// task (update_parameters!(::MOVGP), training.jl:146-151).  The posterior side of a step is Vgp's, latent by latent; the likelihood
+// side is the multi-output machinery of the sparse model (mo_local: update_A!, the mixed local updates, r / w per latent), fed with
+// mean_f[q] = mu_q, var_f[q] = diag Sigma_q.  ELBO, predictions, hyper step (only the Gaussian KL depends on a latent's kernel),
+// state export: the inherited ones, which reach this class through step_local / posterior_f / hypergrad.
+struct Movgp : Vgp {
+  agp_status check_desc() override {
+    AGPCHK(Svgp<T>::check_desc());
+    return check_full();
+  }
+  // update_A! on (mu_q, diag Sigma_q) of the current posterior and the local variables of the step before, the local update of every
+  // task on the mixed (sum_q A_tq mu_q, sum_q A_tq^2 diag Sigma_q), then the mixed gradients per latent (analyticVI.jl:48-111)
+  agp_status step_local(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, double rho, bool fresh) override {
+    if (!mo) {
+      ctx->err = "multi-output handle: call agp_svgp_set_multioutput first";
+      return AGP_ERR_INVALID;
+    }
+    AGPCHK(step_begin(y, idx, B, fresh));
+    int ns = 0;
+    AGPCHK(colstats_part(&ns));
+    const int64_t set = 2 * (int64_t)ns * mp;
+    for (int l = 0; l < nl; ++l) AGPCHK(colstats(lat[l], ns, vgp_part + l * set));
+    hipLaunchKernelGGL((k_movgp_fstats<T>), dim3((unsigned)((m + 255) / 256), (unsigned)nl), dim3(256), 0, st(), m, mp, ns,
+                       (const T*)vgp_part, Bp, muf, varf);
+    LAUNCHCHK(ctx);
+    AGPCHK(mo_local(y, nullptr, m, rho, !fresh, muf, varf));
+    record_batch(y, rho);
+    return AGP_OK;
+  }
+  int part_sets() const override { return nl; }  // k_movgp_fstats reads every latent's slices
 };
 
 // ---- exact GP (AGP_FLAG_FULL | AGP_FLAG_EXACT: GP(X, y, kernel) with Analytic(), src/models/GP.jl, analytic.jl) ------------
@@ -5806,7 +5859,8 @@ agp_status agp_svgp_create(agp_ctx* ctx, const agp_svgp_desc* desc, agp_svgp** o
     ctx->err = "AGP_FLAG_EXACT: exact GP regression is a full model (AGP_FLAG_FULL | AGP_FLAG_EXACT)";
     return AGP_ERR_UNSUPPORTED;
   }
-  if (desc->flags & AGP_FLAG_FULL) impl = (desc->flags & AGP_FLAG_EXACT) ? new Gp() : new Vgp();
+  if (desc->flags & AGP_FLAG_EXACT) impl = new Gp();
+  else if (desc->flags & AGP_FLAG_FULL) impl = desc->lik.kind == AGP_LIK_MULTIOUTPUT ? new Movgp() : new Vgp();
   else if (desc->dtype == AGP_F64) impl = new Svgp<double>();
   else if (desc->dtype == AGP_F32) impl = new Svgp<float>();
   else return AGP_ERR_INVALID;
@@ -5846,6 +5900,10 @@ static agp_status full_refused(agp_svgp* h, const char* what) {
 }
 #define FULLNO(h, what) \
   if ((h)->impl->desc.flags & AGP_FLAG_FULL) return full_refused((h), (what))
+// ... the mixing weights' entry points: refused unless the full model is the multi-output one (Movgp)
+#define FULLNO_SINGLE(h, what)                                                                                  \
+  if (((h)->impl->desc.flags & AGP_FLAG_FULL) && (h)->impl->desc.lik.kind != AGP_LIK_MULTIOUTPUT) \
+  return full_refused((h), (what))
 // ... and those that have none for exact GP regression (AGP_FLAG_EXACT) on top of them
 static agp_status exact_refused(agp_svgp* h, const char* what) {
   h->impl->ctx->err = std::string("exact GP (AGP_FLAG_EXACT): ") + what + " is not supported";
@@ -5926,12 +5984,12 @@ agp_status agp_svgp_prefetch(agp_svgp* h, const void* x, int64_t ldx, const int6
 agp_status agp_svgp_set_multioutput(agp_svgp* h, int32_t n_task, const agp_lik_desc* liks_host, const double* A_host,
                                     double adam_eta, double adam_b1, double adam_b2, double adam_eps) {
   HCHKF(h);
-  FULLNO(h, "agp_svgp_set_multioutput");
+  FULLNO_SINGLE(h, "agp_svgp_set_multioutput");
   return h->impl->set_multioutput(n_task, liks_host, A_host, adam_eta, adam_b1, adam_b2, adam_eps);
 }
 agp_status agp_svgp_get_A(agp_svgp* h, double* A_host) {
   HCHKF(h);
-  FULLNO(h, "agp_svgp_get_A");
+  FULLNO_SINGLE(h, "agp_svgp_get_A");
   return h->impl->get_A(A_host);
 }
 agp_status agp_svgp_elbo_terms(agp_svgp* h, double* terms_host) {

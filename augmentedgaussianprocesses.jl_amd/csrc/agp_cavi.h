@@ -1734,6 +1734,26 @@ __global__ void k_vgp_local(int64_t m, int64_t mp, int ns, const T* __restrict__
   lik_local_point<T>(i, b, a, rho, lp, y, (const int64_t*)nullptr, c, theta, r, w, lam, gamma, (const T*)nullptr);
 }
 
+// Multi-output full model (MOVGP, src/models/MOVGP.jl): the slices of the k_vgp_colstats passes of ALL Q latents summed by one launch
+// into mean_f[q] = mu_q, var_f[q] = diag Sigma_q (the summation order of k_vgp_local); the likelihood side is the mixing kernels'
+// (k_mo_gradA, k_mo_local).  part = [Q][2][ns][mp]: per latent p0 then p1.  Grid (m / 256, Q).
+template <typename T>
+__global__ void k_movgp_fstats(int64_t m, int64_t mp, int ns, const T* __restrict__ part, int64_t ldb, T* __restrict__ muf,
+                               T* __restrict__ varf) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t q = blockIdx.y;
+  if (i >= m) return;
+  const T* p0 = part + q * 2 * ns * mp;
+  const T* p1 = p0 + (int64_t)ns * mp;
+  T a = T(0), b = T(0);
+  for (int s = 0; s < ns; ++s) {
+    a += p0[s * mp + i];
+    b += p1[s * mp + i];
+  }
+  muf[q * ldb + i] = b;
+  varf[q * ldb + i] = a;
+}
+
 // Adjoint of K of the full model's ELBO: only GaussianKL(mu, mu0, Sigma, K) (KLdivergences.jl:11-18) depends on K, so
 //   G_K = (K^-1 (Sigma + d d') K^-1 - K^-1) / 2 = -Apred / 2 + a a' / 2,  a = K^-1 mu - K^-1 mu0,  Apred = K^-1 - K^-1 Sigma K^-1
 // (autotuning.jl:49-85; the kernel backward pass through kernelmatrix(k, X) then runs with both operands X)

@@ -97,16 +97,17 @@ def save_trained_model(filename: str, model: SVGP) -> None:
     model._pull_hypers()
     model._pull_lik_state()
     from .gp import GP
+    from .movgp import MOVGP
     from .vgp import VGP
 
     mo = isinstance(model, MOSVGP)
     exact = isinstance(model, GP)
-    full = isinstance(model, VGP) or exact
+    full = isinstance(model, (VGP, MOVGP)) or exact
     inf = model.inference
     opt = inf.optimiser or RobbinsMonro()
     meta = {
         # a VGP is rebuilt as a VGP (prior K + jitt I on its own training set), never as an SVGP with Z = X
-        "class": "MOSVGP" if mo else "GP" if exact else "VGP" if full else "SVGP",
+        "class": "MOVGP" if mo and full else "MOSVGP" if mo else "GP" if exact else "VGP" if full else "SVGP",
         "kernels": [_kernel_spec(k) for k in model.kernels],
         "likelihood": [_lik_spec(l) for l in model.likelihood.likelihoods] if mo else _lik_spec(model.likelihood),
         "stochastic": bool(inf.stoch), "batchsize": int(inf.batchsize), "n_iter": int(inf.n_iter),
@@ -145,7 +146,11 @@ def save_trained_model(filename: str, model: SVGP) -> None:
     if isinstance(model.mean, (list, np.ndarray)):
         arrays["mean_vec"] = np.asarray(model.mean, dtype=np.float64)
     if full:  # the training set (Z_0 is X; y as the caller gave it)
-        arrays["vgp_y"] = np.asarray(model.y)
+        if mo:  # (one vector per task, each with the caller's own dtype: Bool labels, integer counts, reals)
+            for t, yt in enumerate(model.y):
+                arrays[f"vgp_y_{t}"] = np.asarray(yt)
+        else:
+            arrays["vgp_y"] = np.asarray(model.y)
     np.savez_compressed(filename, **arrays)
 
 
@@ -178,6 +183,12 @@ def load_trained_model(filename: str, *, device=None):
         # (files written before round 6 carry no "a_opt": the model's default ADAM(0.01), MOSVGP.jl:42, as for a fresh model)
         a_opt = _opt_from(meta["a_opt"]) if "a_opt" in meta else None
         model = MOSVGP(kernels, [_lik_from(d) for d in meta["likelihood"]], inf, Zs, A=g["A"], Aoptimiser=a_opt, **kw)
+    elif meta["class"] == "MOVGP":
+        from .movgp import MOVGP
+
+        a_opt = _opt_from(meta["a_opt"])
+        model = MOVGP(Zs[0], [g[f"vgp_y_{t}"] for t in range(len(meta["likelihood"]))], kernels, [_lik_from(d) for d in meta["likelihood"]], inf, nl, A=g["A"],
+                      Aoptimiser=a_opt, optimiser=kw["optimiser"], atfrequency=kw["atfrequency"], mean=mean, T=T, device=device)
     elif meta["class"] == "GP":
         from .gp import GP
 

@@ -15,6 +15,29 @@ from .likelihoods import GaussianLikelihood
 from .svgp import ADAM, ELBO, SVGP, AnalyticVI, train_
 
 
+def full_model_args(name, sparse, inference, X, obsdim, optimiser, mean, T):
+    """What the constructors of the full models (VGP, MOVGP) share: the refusals (AnalyticSVI, a float type other than Float64, an
+    EmpiricalMean of another length than N), X as a contiguous (N, D) array, and the optimiser default ADAM(0.01) for None / True
+    (VGP.jl:63, MOVGP.jl:57; the SVGP constructor maps False to "off").  `sparse`: the model to name for AnalyticSVI.
+    Returns (X, optimiser)."""
+    if getattr(inference, "stoch", False):
+        # the reference constructs the model with AnalyticSVI, but natural_gradient!(::VarLatent) cannot run on a minibatch
+        raise ValueError(f"{name} takes the full data set every iteration: use AnalyticVI(), or {sparse} for AnalyticSVI")
+    if np.dtype(T) != np.dtype(np.float64):
+        raise NotImplementedError(f"{name} runs in Float64 only (the full N x N factorisation has no Float32 path)")
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    if obsdim == 2:
+        X = X.T
+    X = np.ascontiguousarray(X)
+    if optimiser is None or optimiser is True:
+        optimiser = ADAM(0.01)
+    if mean is not None and not np.isscalar(mean) and len(mean) != X.shape[0]:
+        raise ValueError("an EmpiricalMean needs one value per training point")
+    return X, optimiser
+
+
 class VGP(SVGP):
     """VGP(X, y, kernel, likelihood, inference; verbose=0, optimiser=ADAM(0.01), atfrequency=1, mean=ZeroMean(), obsdim=1).
 
@@ -27,24 +50,10 @@ class VGP(SVGP):
         if not isinstance(inference, AnalyticVI):  # VGP.jl:51
             raise TypeError("The inference object should be of type `VariationalInference` : either `AnalyticVI` or "
                             "`NumericalVI`")
-        if inference.stoch:
-            # the reference constructs VGP with AnalyticSVI, but natural_gradient!(::VarLatent) cannot run on a minibatch
-            raise ValueError("VGP takes the full data set every iteration: use AnalyticVI(), or SVGP for AnalyticSVI")
         if isinstance(likelihood, GaussianLikelihood):  # VGP.jl:54-56
             raise ValueError("For a Gaussian Likelihood you should directly use the `GP` model or the `SVGP` model for "
                              "large datasets")
-        if np.dtype(T) != np.dtype(np.float64):
-            raise NotImplementedError("VGP runs in Float64 only (the full N x N factorisation has no Float32 path)")
-        X = np.asarray(X, dtype=np.float64)
-        if X.ndim == 1:
-            X = X[:, None]
-        if obsdim == 2:
-            X = X.T
-        X = np.ascontiguousarray(X)
-        if optimiser is None or optimiser is True:
-            optimiser = ADAM(0.01)  # VGP.jl:63 (SVGP's constructor below maps False to "off")
-        if mean is not None and not np.isscalar(mean) and len(mean) != X.shape[0]:
-            raise ValueError("an EmpiricalMean needs one value per training point")
+        X, optimiser = full_model_args("VGP", "SVGP", inference, X, obsdim, optimiser, mean, T)
         self._desc_flags = capi.FLAG_FULL
         super().__init__(kernel, likelihood, inference, X, verbose=verbose, optimiser=optimiser, atfrequency=atfrequency,
                          mean=mean, Zoptimiser=False, T=T, device=device)
@@ -88,7 +97,7 @@ def _train_vgp(model: VGP, *args, iterations: Optional[int] = None, callback=Non
             iterations = args[2]
         if not (np.shape(X) == model.X.shape and np.array_equal(np.asarray(X, dtype=np.float64), model.X)
                 and np.array_equal(np.asarray(y), np.asarray(model.y))):
-            raise ValueError("a VGP trains on the data it was built with: train_(model, iterations)")
+            raise ValueError(f"a {type(model).__name__} trains on the data it was built with: train_(model, iterations)")
     elif args:
         raise TypeError("train_(model::VGP, iterations)")
     if iterations is None:

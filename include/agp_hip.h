@@ -123,7 +123,25 @@ enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4 };
  *                   (K^-1 (Sigma + d d') K^-1 - K^-1) / 2, d = mu - mu0; X is never optimised (dZ / opt_Z: AGP_ERR_UNSUPPORTED)
  *   predict_f / predict_f_cov / predict_y / proba_y  the generic _predict_f with Zviews(m) = X (predictions.jl:25-50)
  * Refused with AGP_ERR_UNSUPPORTED, doing nothing: the phase entry points (step_local, lsm_*, step_stats, stats_ptr, step_global),
- * prefetch, batch sharding, every *_multi call, the online entry points, multi-output. */
+ * prefetch, batch sharding, every *_multi call, the online entry points, the latent-sharded multi-output calls (mo_shard,
+ * mo_fbuf_ptr, mo_mix, mo_refresh_f, mo_predict_from_f); set_multioutput / get_A unless the likelihood is AGP_LIK_MULTIOUTPUT.
+ *
+ * AGP_FLAG_FULL with lik.kind = AGP_LIK_MULTIOUTPUT is MOVGP(X, y, kernel, likelihoods, AnalyticVI(), num_latent)
+ * src/models/MOVGP.jl:46-126 -- n_latent = num_latent full latents on the training inputs (agp_svgp_set_Z installs X for every
+ * latent; latent_offset = 0: all of them on one handle), mixed by A into one output per task.  agp_svgp_set_multioutput installs the
+ * task likelihoods, A and the A optimiser exactly as for MOSVGP (a Gaussian task is allowed); targets are point-major
+ * y[i * n_task + t].  What differs from VGP above:
+ *   cavi_step       update_parameters!(::MOVGP) (training.jl:146-151): update_A! on mean_f_q = mu_q, var_f_q = diag Sigma_q of the
+ *                   current posterior and the local variables of the step before, the local update of every task on the mixed
+ *                   (sum_q A_tq mu_q, sum_q A_tq^2 diag Sigma_q), the mixed gradients per latent (analyticVI.jl:48-111), then
+ *                   VGP's eta1 / eta2 for every latent at once
+ *   elbo            sum_t expectation_t at the mixed (mean_f, var_f) - sum_q GaussianKL_q - sum_t AugmentedKL_t (analyticVI.jl:277-297)
+ *   hyper_step / hypergrad  per latent as for VGP: only the Gaussian KL depends on a latent's kernel (autotuning.jl:48-84)
+ *   predict_*       the multi-output _predict_f (predictions.jl:52-92) with Zviews(m) = X: out[n_task][n_t], means mixed by A,
+ *                   variances and full covariances by A^2
+ *   get_matrix      AGP_VEC_MEAN_F / AGP_VEC_VAR_F per latent (mu_q, diag Sigma_q as the last local phase saw them);
+ *                   AGP_VEC_THETA / AGP_VEC_C count `latent` over the TASKS, as on every multi-output handle (below)
+ * AGP_FLAG_EXACT with a multi-output likelihood: AGP_ERR_UNSUPPORTED. */
 /* AGP_FLAG_EXACT (only together with AGP_FLAG_FULL): exact GP regression GP(X, y, kernel; noise, opt_noise) with Analytic()
  * inference  src/models/GP.jl:37-92, src/inference/analytic.jl:36-51.  Float64, n_latent = 1, a Gaussian likelihood (lik.p0 = sigma2,
  * lik.p1 = the ADAM rate of opt_noise or 0); anything else AGP_ERR_UNSUPPORTED.  elbo_mode AGP_ELBO_REFERENCE reproduces the
@@ -155,7 +173,9 @@ enum {
   AGP_VEC_MEAN_F = 5, /* B   kappa*mu   (value used by the last local update)     (latentgp.jl:179) */
   AGP_VEC_VAR_F = 6,  /* B                                                        (latentgp.jl:189) */
   AGP_VEC_THETA = 7,  /* B   local variable theta                                 (likelihood local_updates!) */
-  AGP_VEC_C = 8,      /* B   local variable c (Laplace: b).  Heteroscedastic: latent 0 -> phi, latent 1 -> c */
+  AGP_VEC_C = 8,      /* B   local variable c (Laplace: b).  Heteroscedastic: latent 0 -> phi, latent 1 -> c.
+                       *     Multi-output handles (MOSVGP, MOVGP, after set_multioutput): the local variables belong to the task
+                       *     likelihoods, so for AGP_VEC_THETA / AGP_VEC_C `latent` counts the tasks, 0 <= latent < n_task */
   AGP_VEC_GAMMA = 9,  /* B   LogisticSoftMax gamma_k ; Poisson gamma ; Heteroscedastic: latent 0 -> gamma, latent 1 -> sigg */
   AGP_VEC_ALPHA = 10  /* B   LogisticSoftMax alpha (shared by all latents) */
 };

@@ -168,10 +168,10 @@ mutable struct HipModel{T,M<:AGP.AbstractGPModel{T}}
     keep::Vector{Any}              # index buffers a queued look-ahead / pending step may still read (two generations)
 end
 
-is_mo(hm::HipModel) = hm.model isa AGP.MOSVGP
-is_full(hm::HipModel) = hm.model isa Union{AGP.VGP,AGP.GP}
+is_mo(hm::HipModel) = hm.model isa Union{AGP.MOSVGP,AGP.MOVGP}
+is_full(hm::HipModel) = hm.model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP}   # (a MOVGP is both: IsMultiOutput and IsFull, MOVGP.jl:121-122)
 is_exact(hm::HipModel) = hm.model isa AGP.GP
-# the latents of a model: a tuple / vector of them (SVGP, MOSVGP, VGP: `m.f`), or the single LatentGP of a GP (`f::LatentGP`, GP.jl:28)
+# the latents of a model: a tuple / vector of them (SVGP, MOSVGP, VGP, MOVGP: `m.f`), or the single LatentGP of a GP (`f::LatentGP`, GP.jl:28)
 latents(m::AGP.AbstractGPModel) = m.f
 latents(m::AGP.GP) = (m.f,)
 # the inputs the handle's "inducing points" are: Z of a sparse latent, the training inputs of a VGP (Zviews(m::VGP), VGP.jl:90)
@@ -186,8 +186,8 @@ Wrap a reference model.  Nothing is allocated on the device until data arrive (`
 """
 function HipModel(model::M; reference_compat_stale_K::Bool=false,
                   latent_range::UnitRange{Int}=1:length(latents(model))) where {T,M<:AGP.AbstractGPModel{T}}
-    model isa Union{SVGP,AGP.MOSVGP,AGP.VGP,AGP.GP} || error("only SVGP / MOSVGP / VGP / GP run on the HIP path")
-    model isa Union{AGP.VGP,AGP.GP} && T != Float64 && error("VGP / GP run in Float64 only on the HIP path")
+    model isa Union{SVGP,AGP.MOSVGP,AGP.VGP,AGP.GP,AGP.MOVGP} || error("only SVGP / MOSVGP / VGP / GP / MOVGP run on the HIP path")
+    model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP} && T != Float64 && error("VGP / GP / MOVGP run in Float64 only on the HIP path")
     AGP.inference(model) isa Union{AnalyticVI,AGP.Analytic} ||
         error("The inference object should be of type `AnalyticVI`")   # SVGP.jl:45-47
     return HipModel{T,M}(model, C_NULL, C_NULL, C_NULL, AGP_SHARD_LATENT, latent_range, 0, nothing, nothing, 0, nothing,
@@ -1038,6 +1038,26 @@ for f in (:predict_f, :predict_y, :proba_y)
     end
 end
 objective(model::HipVGP, state::HipModel, y=nothing) = objective(state)
+
+# MOVGP{T,L,<:AnalyticVI} (src/models/MOVGP.jl): the multi-output full model, train!(model, iterations) on its own data; the handle
+# is created with AGP_FLAG_FULL and the multi-output likelihood (is_full and is_mo both hold: the inputs of every latent are the
+# training inputs, the targets go up point-major, A travels through agp_svgp_set_multioutput / agp_svgp_get_A as for MOSVGP).
+const HipMOVGP{T} = AGP.MOVGP{T,<:Any,<:AnalyticVI}
+twin(model::HipMOVGP) = get!(() -> HipModel(model), TWINS, model)
+function train!(model::HipMOVGP, iterations::Int; backend::Symbol=BACKEND[], kwargs...)
+    backend === :cpu && return invoke(train!, Tuple{AGP.AbstractGPModel,Int}, model, iterations; kwargs...)
+    X = reduce(hcat, AGP.input(model.data))'                     # N x D
+    _, state = train!(twin(model), X, AGP.output(model.data), iterations; kwargs...)
+    return model, state
+end
+for f in (:predict_f, :predict_y, :proba_y)
+    @eval function $f(model::HipMOVGP, X_test::AbstractMatrix, state=nothing; backend::Symbol=BACKEND[], kw...)
+        (backend === :cpu || !has_twin(model)) &&
+            return invoke($f, Tuple{AGP.AbstractGPModel,AbstractMatrix,Any}, model, X_test, state; kw...)
+        return $f(TWINS[model], X_test; kw...)
+    end
+end
+objective(model::HipMOVGP, state::HipModel, y=nothing) = objective(state)
 
 # GP{T,<:GaussianLikelihood,<:Analytic} (src/models/GP.jl): exact regression on a handle created with AGP_FLAG_FULL | AGP_FLAG_EXACT.
 # The posterior comes back as (alpha, Sigma) -- agp_svgp_get_state with eta1 = eta2 = NULL -- and log p is the handle's ELBO.
