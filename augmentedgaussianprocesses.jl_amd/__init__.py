@@ -51,6 +51,7 @@ from .svgp import (  # noqa: F401
 from .vgp import VGP, n_latent  # noqa: F401
 from .gp import GP, Analytic  # noqa: F401
 from .movgp import MOVGP  # noqa: F401
+from .mcgp import MCGP, GibbsSampling, sample, sample_local  # noqa: F401
 from .capi import AGPError  # noqa: F401
 from .persistence import load_trained_model, save_trained_model  # noqa: F401
 from .inducingpoints import KmeansAlg, RandomSubset, inducingpoints  # noqa: F401

@@ -16,6 +16,7 @@
 #include "agp_hyper.h"
 #include "agp_kmeans.h"
 #include "agp_linalg.h"
+#include "agp_rand.h"
 
 using namespace agp;
 
@@ -1272,6 +1273,18 @@ struct SvgpBase {
   virtual agp_status adopt_local(SvgpBase* src) = 0;
   virtual agp_status get_lik_param(double* out) = 0;
   virtual agp_status set_lik_param(double v) = 0;
+  // Gibbs sampling (AGP_FLAG_SAMPLED: Mcgp); every other handle refuses
+  agp_status not_sampled(const char* what) {
+    ctx->err = std::string(what) + ": the handle is not a Gibbs-sampled model (AGP_FLAG_FULL | AGP_FLAG_SAMPLED)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  virtual agp_status gibbs_sample(const void*, int64_t, int64_t, int64_t, uint64_t, void*, int64_t) {
+    return not_sampled("agp_svgp_gibbs_sample");
+  }
+  virtual agp_status gibbs_counter(int, int64_t*) { return not_sampled("agp_svgp_gibbs_counter"); }
+  virtual agp_status predict_samples(const void*, int64_t, int64_t, const void*, int64_t, int64_t, int, void*, void*) {
+    return not_sampled("agp_svgp_predict_samples");
+  }
   int64_t n_opt = 1;  // RobbinsMonro counter (optimisers.jl:12)
   bool in_cavi_step = false;  // step_local is running as the first half of agp_svgp_cavi_step (its tail may then be deferred)
   int64_t n_prologue = 0;  // CAVI steps whose natural-gradient part rode on the next step's task-graph launch (agp_svgp_step_counters)
@@ -3836,6 +3849,14 @@ struct Svgp : SvgpBase {
       ctx->err = "class label outside the likelihood's classes";  // multiclass.jl:81-83
       return AGP_ERR_LABELS;
     }
+    if (flags & FLAG_BAD_COUNT) {
+      ctx->err = "Gibbs sampling: the targets of a NegBinomial likelihood must be non-negative integers (PolyaGamma(y + r, |f|))";
+      return AGP_ERR_LABELS;
+    }
+    if (flags & FLAG_RNG_BOUND) {
+      ctx->err = "Gibbs sampling: a variate sampler ran into its iteration bound (agp_rand.h); the chain is not valid from there";
+      return AGP_ERR_HIP;
+    }
     if (info == -2) {
       ctx->err = "the look-ahead stream waited about a minute for a CAVI step that never started (k_wait_ge)";
       return AGP_ERR_HIP;
@@ -5318,6 +5339,216 @@ struct Gp : Vgp {
   }
 };
 
+// ---- Gibbs-sampled full model (AGP_FLAG_FULL | AGP_FLAG_SAMPLED: MCGP(X, y, kernel, likelihood, GibbsSampling())) --------------
+// src/models/MCGP.jl, src/inference/gibbssampling.jl, src/training/sampling.jl.  The state of the chain is f (kept in g.mu) and the
+// sweep counter t.  One sweep: k_gibbs_local draws the local variables at f and writes theta and the expectation gradients where
+// k_vgp_local writes them; k_vgp_eta forms eta1 and -2 eta2 = inv(K) + 2 Diagonal(grad_E_Sigma); Vgp::vgp_factor leaves Xa = L^-1 and
+// v = Xa eta1; k_gibbs_f / k_gibbs_fsum draw f = Xa' (v + z) ~ N(Sigma eta1, Sigma).  Nothing between sweeps waits for the host.
+struct Mcgp : Vgp {
+  int64_t gibbs_t = 0;    // sweeps taken so far: the counter word of the next sweep's draws
+  bool swept = false;     // Xa belongs to a sweep (else Sigma = I, latentgp.jl:81-86)
+  T *mc_Fs = nullptr, *mc_G = nullptr, *mc_Fstar = nullptr;  // prediction: padded samples, F K^-1, F* of one block of test points
+  int64_t mc_sp = 0;
+  static constexpr int64_t MC_MAX_SAMPLES = 65536;  // (the workspace holds F K^-1 for all samples of a call: 2 x 8 N bytes each)
+  ~Mcgp() override {
+    for (T* p : {mc_Fs, mc_G, mc_Fstar})
+      if (p) dfree(p);
+  }
+  static const char* supported() { return "Gibbs sampling on the device runs for the Logistic, StudentT and NegBinomial likelihoods"; }
+  agp_status check_desc() override {
+    AGPCHK(Svgp<T>::check_desc());
+    AGPCHK(check_full());
+    if (lp.kind == AGP_LIK_GAUSSIAN) {  // MCGP.jl:54-56
+      ctx->err = "For a Gaussian Likelihood you should directly use the `GP` model or the `SVGP` model for large datasets";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    if (lp.kind != AGP_LIK_LOGISTIC && lp.kind != AGP_LIK_STUDENTT && lp.kind != AGP_LIK_NEGBINOMIAL) {
+      ctx->err = std::string("AGP_FLAG_SAMPLED: ") + supported() +
+                 " (Laplace, BayesianSVM, Poisson, Heteroscedastic, LogisticSoftMax and multi-output models are not sampled yet)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    if (lp.kind == AGP_LIK_NEGBINOMIAL && desc.lik.p0 != std::floor(desc.lik.p0)) {  // Int(l.r), negativebinomial.jl:87
+      ctx->err = "InexactError: the Gibbs sampler of NegBinomialLikelihood(r) draws PolyaGamma(y + Int(r), |f|): r must be an integer";
+      return AGP_ERR_INVALID;
+    }
+    return AGP_OK;
+  }
+  agp_status init() override {
+    AGPCHK(Vgp::init());
+    HIPCHK(ctx, hipMemsetAsync(lat[0].mu, 0, sizeof(T) * mp, st()));  // f = 0
+    return AGP_OK;
+  }
+  agp_status sampled_refused(const char* what) {
+    ctx->err = std::string("Gibbs-sampled model (AGP_FLAG_SAMPLED): ") + what +
+               " is not supported (the chain is advanced by agp_svgp_gibbs_sample and read by agp_svgp_predict_samples; "
+               "objective(::MCGP) = NaN and the reference never tunes its kernel)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  agp_status step_local(const void*, int64_t, const void*, const int64_t*, int64_t, double, bool) override {
+    return sampled_refused("agp_svgp_cavi_step");
+  }
+  agp_status elbo(const void*, int64_t, const void*, const int64_t*, int64_t, double, int, double*) override {
+    return sampled_refused("agp_svgp_elbo");
+  }
+  agp_status elbo_enqueue(const void*, int64_t, const void*, const int64_t*, int64_t, double, int, int32_t*) override {
+    return sampled_refused("agp_svgp_elbo_enqueue");
+  }
+  agp_status elbo_terms(double*) override { return sampled_refused("agp_svgp_elbo_terms"); }
+  agp_status hypergrad(int, double*, double*, void*) override { return sampled_refused("agp_svgp_hypergrad"); }
+  agp_status hyper_step() override { return sampled_refused("agp_svgp_hyper_step"); }
+  agp_status hyper_apply(int, const double*, const double*, const void*) override { return sampled_refused("agp_svgp_hyper_apply"); }
+  agp_status hyper_configure(int, double, int, double, double, double, double) override {
+    return sampled_refused("agp_svgp_hyper_configure");
+  }
+  agp_status hyper_rule(int, double, int, double) override { return sampled_refused("agp_svgp_hyper_rule"); }
+  agp_status predict_f(const void*, int64_t, int64_t, void*, void*) override { return sampled_refused("agp_svgp_predict_f"); }
+  agp_status predict_f_cov(const void*, int64_t, int64_t, void*, void*) override { return sampled_refused("agp_svgp_predict_f_cov"); }
+  agp_status predict_y(const void*, int64_t, int64_t, void*) override { return sampled_refused("agp_svgp_predict_y"); }
+  agp_status proba_y(const void*, int64_t, int64_t, const double*, const double*, int, void*, void*) override {
+    return sampled_refused("agp_svgp_proba_y");
+  }
+
+  // one sweep at counter gibbs_t (AbstractMCMC.step, sampling.jl:36-75); keep: the sweep's row of the caller's store, or NULL
+  agp_status sweep(const T* y, uint64_t seed, T* keep) {
+    Latent& g = lat[0];
+    const uint32_t t = (uint32_t)gibbs_t;
+    int ns = 0;
+    AGPCHK(colstats_part(&ns));
+    hipLaunchKernelGGL((k_gibbs_local<T>), grid1(m), dim3(256), 0, st(), m, lp, y, (const T*)g.mu, seed, t, theta, cbuf, rbuf, wbuf,
+                       flags_dev);
+    hipLaunchKernelGGL((k_vgp_eta<T>), dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, st(), m, mp,
+                       (const T*)kinv_step(g), (const T*)rbuf, (const T*)wbuf, (const T*)kinv_mu0_step(g), g.eta2, g.La, g.eta1);
+    LAUNCHCHK(ctx);
+    g.la_state = 0;
+    g.xa_valid = false;
+    AGPCHK(vgp_factor(g));
+    const int64_t ntc = mp / TILE, rows = (mp + ns - 1) / ns;
+    hipLaunchKernelGGL((k_gibbs_f<T>), dim3((unsigned)ntc, (unsigned)ns), dim3(256), 0, st(), m, mp, (const T*)g.Xa, (const T*)g.v,
+                       rows, seed, t, vgp_part, flags_dev);
+    hipLaunchKernelGGL((k_gibbs_fsum<T>), grid1(m), dim3(256), 0, st(), m, mp, ns, (const T*)vgp_part, g.mu, keep);
+    LAUNCHCHK(ctx);
+    gibbs_t += 1;
+    swept = true;
+    return AGP_OK;
+  }
+  agp_status gibbs_sample(const void* y, int64_t n_samples, int64_t discard_initial, int64_t thinning, uint64_t seed, void* store,
+                          int64_t lds) override {
+    if (!y || !store || n_samples < 1 || discard_initial < 0 || thinning < 1 || lds < m) {
+      ctx->err = "agp_svgp_gibbs_sample: y and store must be given, n_samples >= 1, discard_initial >= 0, thinning >= 1, lds >= N";
+      return AGP_ERR_INVALID;
+    }
+    const int64_t total = discard_initial + 1 + (n_samples - 1) * thinning;
+    if (gibbs_t + total > (int64_t)0xFFFFFFFFll) {
+      ctx->err = "agp_svgp_gibbs_sample: the sweep counter is one 32-bit word of the generator's counter";
+      return AGP_ERR_INVALID;
+    }
+    AGPCHK(refresh_K());
+    for (int64_t s = 1; s <= total; ++s) {
+      const int64_t k = s - discard_initial - 1;
+      const bool kept = k >= 0 && k % thinning == 0;
+      AGPCHK(sweep((const T*)y, seed, kept ? (T*)store + (k / thinning) * lds : (T*)nullptr));
+    }
+    record_batch(y, 1.0);
+    return AGP_OK;
+  }
+  agp_status gibbs_counter(int set, int64_t* t) override {
+    if (!t) return AGP_ERR_INVALID;
+    if (set) {
+      if (*t < 0 || *t > (int64_t)0xFFFFFFFFll) return AGP_ERR_INVALID;
+      gibbs_t = *t;
+    } else {
+      *t = gibbs_t;
+    }
+    return AGP_OK;
+  }
+  // mu <- f, sigma <- Sigma = inv(2 Diagonal(grad_E_Sigma) + inv(K)) of the last sweep (I before the first); no natural parameters
+  agp_status get_state(int l, void* mu, void* sigma, void* eta1, void* eta2) override {
+    if (l != 0) return AGP_ERR_INVALID;
+    if (eta1 || eta2) {
+      ctx->err = "Gibbs-sampled model (AGP_FLAG_SAMPLED): the state is a sample, not a variational posterior (eta1 / eta2 must be NULL)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    Latent& g = lat[0];
+    if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, g.mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
+    if (sigma) {
+      if (swept)
+        AGPCHK(xtx_padded<T>(ctx, g.Xa, mp, mp, g.Sigma, mp));
+      else
+        hipLaunchKernelGGL((k_set_identity<T>), grid2(mp, mp), blk2, 0, st(), g.Sigma, mp, mp, T(1));
+      LAUNCHCHK(ctx);
+      HIPCHK(ctx, hipMemcpy2DAsync(sigma, sizeof(T) * m, g.Sigma, sizeof(T) * mp, sizeof(T) * m, m, hipMemcpyDeviceToDevice, st()));
+    }
+    return AGP_OK;
+  }
+  // installs f, the state the chain continues from (eta1 = f, eta2 = NULL): what a reloaded model needs next to the sweep counter
+  agp_status set_state(int l, const void* f, const void* eta2) override {
+    if (l != 0 || !f) return AGP_ERR_INVALID;
+    if (eta2) {
+      ctx->err = "Gibbs-sampled model (AGP_FLAG_SAMPLED): set_state installs f (eta1 = f); eta2 must be NULL";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(lat[0].mu, f, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
+    return AGP_OK;
+  }
+
+  // _predict_f(::MCGP) / proba_y(::MCGP) (predictions.jl:94-130, 260-276): F* = K*n (K \ F) for all kept samples, block of test
+  // points by block (K*n is never held whole), then mean / variance over the samples per test point (k_mcgp_pred_finish)
+  agp_status predict_samples(const void* xt, int64_t ldx, int64_t nt, const void* store, int64_t lds, int64_t S, int mode,
+                             void* out0, void* out1) override {
+    if (!xt || nt <= 0 || ldx < D || !store || lds < m || S < 1 || !out0 || mode < 0 || mode > 2 || (mode != 0 && !out1)) {
+      ctx->err = "agp_svgp_predict_samples: xt, store and out0 must be given (out1 too unless mode = 0), n_t > 0, ldx >= D, lds >= N, "
+                 "n_samples >= 1, mode 0, 1 or 2";
+      return AGP_ERR_INVALID;
+    }
+    if (S > MC_MAX_SAMPLES) {
+      ctx->err = "agp_svgp_predict_samples: at most " + std::to_string(MC_MAX_SAMPLES) + " samples per call (got " +
+                 std::to_string(S) + "): thin the store or predict from a part of it";
+      return AGP_ERR_INVALID;
+    }
+    if (mode == 2 && lp.kind != AGP_LIK_LOGISTIC) {
+      ctx->err = "agp_svgp_predict_samples: mode 2 (mean and variance of logistic(f*) over the samples) is proba_y of the Bernoulli "
+                 "likelihood (predictions.jl:266-276); other likelihoods take compute_proba on the moments of mode 1";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    Latent& g = lat[0];
+    AGPCHK(params_to_host(g));
+    AGPCHK(ensure_pred_ws(0, true));
+    AGPCHK(refresh_K());
+    AGPCHK(ensure_zsc(g));
+    const int64_t Sp = rup64(S), CH = pred_chunk;
+    if (Sp > mc_sp) {
+      for (T** p : {&mc_Fs, &mc_G, &mc_Fstar}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+      }
+      mc_sp = 0;
+      AGPCHK(dmalloc(ctx, &mc_Fs, Sp * mp));
+      AGPCHK(dmalloc(ctx, &mc_G, Sp * mp));
+      AGPCHK(dmalloc(ctx, &mc_Fstar, CH * Sp));
+      mc_sp = Sp;
+    }
+    HIPCHK(ctx, hipMemsetAsync(mc_Fs, 0, sizeof(T) * mc_sp * mp, st()));
+    HIPCHK(ctx, hipMemcpy2DAsync(mc_Fs, sizeof(T) * mp, store, sizeof(T) * lds, sizeof(T) * m, S, hipMemcpyDeviceToDevice, st()));
+    // G = F K^-1 (rows = samples; K^-1 symmetric)
+    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, mc_Fs, mp, g.Kinv, mp, Sp, mp, mp, 0, mc_G, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+    for (int64_t s = 0; s < nt; s += CH) {
+      const int64_t nc = (nt - s) < CH ? (nt - s) : CH, nq = rup64(nc);
+      (void)launch_kernelmatrix<T>(ctx, st(), (const T*)xt + s * ldx, ldx, (const int64_t*)nullptr, nc, (const T*)g.Z, D, m, D,
+                                   (const T*)g.scales, g.k.kind, kvar(g), Kstar, mp, nq, mp, 0, T(0), (const T*)nullptr, (T*)nullptr,
+                                   (int64_t)0, 0, (const T*)g.Zsc, (const T*)g.zn);
+      LAUNCHCHK(ctx);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, Kstar, mp, mc_G, mp, nq, Sp, mp, 0, mc_Fstar, Sp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+      if (mode == 1)
+        AGPCHK((gemm_nt<T, EPI_ROWDOT>(ctx, Kstar, mp, g.Kinv, mp, nq, mp, mp, 0, nullptr, 0, Kstar, mp, nullptr, ppv, nullptr, CH)));
+      hipLaunchKernelGGL((k_mcgp_pred_finish<T>), grid1(nc), dim3(256), 0, st(), nc, (int)S, (const T*)mc_Fstar, Sp, mode,
+                         (int)(2 * mp / TILE), (const T*)ppv, CH, (T)g.k.variance, (T)jitter, (T*)out0 + s,
+                         out1 ? (T*)out1 + s : (T*)nullptr);
+      LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  }
+};
+
 // ================================================================================================================
 // C entry points
 // ================================================================================================================
@@ -5859,7 +6090,13 @@ agp_status agp_svgp_create(agp_ctx* ctx, const agp_svgp_desc* desc, agp_svgp** o
     ctx->err = "AGP_FLAG_EXACT: exact GP regression is a full model (AGP_FLAG_FULL | AGP_FLAG_EXACT)";
     return AGP_ERR_UNSUPPORTED;
   }
-  if (desc->flags & AGP_FLAG_EXACT) impl = new Gp();
+  if ((desc->flags & AGP_FLAG_SAMPLED) && (!(desc->flags & AGP_FLAG_FULL) || (desc->flags & AGP_FLAG_EXACT))) {
+    ctx->err = std::string("AGP_FLAG_SAMPLED: Gibbs sampling runs on the full model (AGP_FLAG_FULL | AGP_FLAG_SAMPLED, without "
+                           "AGP_FLAG_EXACT); ") + Mcgp::supported();
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if (desc->flags & AGP_FLAG_SAMPLED) impl = new Mcgp();
+  else if (desc->flags & AGP_FLAG_EXACT) impl = new Gp();
   else if (desc->flags & AGP_FLAG_FULL) impl = desc->lik.kind == AGP_LIK_MULTIOUTPUT ? new Movgp() : new Vgp();
   else if (desc->dtype == AGP_F64) impl = new Svgp<double>();
   else if (desc->dtype == AGP_F32) impl = new Svgp<float>();
@@ -6170,6 +6407,69 @@ agp_status agp_svgp_predict_y(agp_svgp* h, const void* xt, int64_t ldx, int64_t 
   if (n_t == 0) return AGP_OK;  // no test points: nothing to write (the reference returns empty arrays)
   return h->impl->predict_y(xt, ldx, n_t, y_out);
 }
+
+// ---- Gibbs sampling (AGP_FLAG_FULL | AGP_FLAG_SAMPLED) -----------------------------------------------------------------------
+agp_status agp_svgp_gibbs_sample(agp_svgp* h, const void* y, int64_t n_samples, int64_t discard_initial, int64_t thinning,
+                                 uint64_t seed, void* store, int64_t lds) {
+  HCHK(h);
+  return h->impl->gibbs_sample(y, n_samples, discard_initial, thinning, seed, store, lds);
+}
+agp_status agp_svgp_gibbs_counter(agp_svgp* h, int32_t set, int64_t* t_host) {
+  HCHK(h);
+  return h->impl->gibbs_counter(set, t_host);
+}
+agp_status agp_svgp_predict_samples(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, const void* store, int64_t lds,
+                                    int64_t n_samples, int32_t mode, void* out0, void* out1) {
+  HCHK(h);
+  if (n_t == 0) return AGP_OK;
+  return h->impl->predict_samples(xt, ldx, n_t, store, lds, n_samples, mode, out0, out1);
+}
+agp_status agp_sample_local(agp_ctx* ctx, const agp_lik_desc* lik, const void* y, const void* f, int64_t n, uint64_t seed,
+                            int64_t t, void* theta_out, void* aux_out) {
+  if (!ctx || !lik || !y || !f || !theta_out || n < 0 || n > (int64_t)0xFFFFFFFFll || t < 0 || t > (int64_t)0xFFFFFFFFll)
+    return AGP_ERR_INVALID;
+  if (lik->kind != AGP_LIK_LOGISTIC && lik->kind != AGP_LIK_STUDENTT && lik->kind != AGP_LIK_NEGBINOMIAL) {
+    ctx->err = std::string("agp_sample_local: ") + Mcgp::supported();
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if ((lik->kind == AGP_LIK_STUDENTT && !(lik->p0 > 0.5)) ||
+      (lik->kind == AGP_LIK_NEGBINOMIAL && !(lik->p0 > 0 && lik->p0 == std::floor(lik->p0)))) {
+    ctx->err = "agp_sample_local: StudentT needs nu > 0.5, NegBinomial a positive integer r";
+    return AGP_ERR_INVALID;
+  }
+  if (n == 0) return AGP_OK;
+  DevGuard guard(ctx->device);
+  int* flag = nullptr;
+  AGPCHK(dmalloc(ctx, &flag, 1));
+  LikParams<double> lp{};
+  lp.kind = lik->kind;
+  lp.p0 = lik->p0;
+  lp.p1 = lik->p1;
+  int host = 0;
+  hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL((k_gibbs_local<double>), grid1(n), dim3(256), 0, ctx->stream, n, lp, (const double*)y, (const double*)f, seed,
+                       (uint32_t)t, (double*)theta_out, (double*)aux_out, (double*)nullptr, (double*)nullptr, flag);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(flag);
+  if (e != hipSuccess) {
+    ctx->err = std::string("agp_sample_local: ") + hipGetErrorString(e);
+    return AGP_ERR_HIP;
+  }
+  if (host & FLAG_BAD_COUNT) {
+    ctx->err = "agp_sample_local: the targets of a NegBinomial likelihood must be non-negative integers (PolyaGamma(y + r, |f|))";
+    return AGP_ERR_LABELS;
+  }
+  if (host & FLAG_RNG_BOUND) {
+    ctx->err = "agp_sample_local: a variate sampler ran into its iteration bound (agp_rand.h)";
+    return AGP_ERR_HIP;
+  }
+  return AGP_OK;
+}
+
 agp_status agp_svgp_set_online_prior(agp_svgp* h, int32_t latent, const void* za, int64_t ldza, int64_t ma, const void* invDa,
                                      int64_t ldi, const void* prev_eta1, double prevLa) {
   HCHKF(h);

@@ -97,17 +97,19 @@ def save_trained_model(filename: str, model: SVGP) -> None:
     model._pull_hypers()
     model._pull_lik_state()
     from .gp import GP
+    from .mcgp import MCGP
     from .movgp import MOVGP
     from .vgp import VGP
 
     mo = isinstance(model, MOSVGP)
     exact = isinstance(model, GP)
-    full = isinstance(model, (VGP, MOVGP)) or exact
+    sampled = isinstance(model, MCGP)
+    full = isinstance(model, (VGP, MOVGP)) or exact or sampled
     inf = model.inference
     opt = inf.optimiser or RobbinsMonro()
     meta = {
         # a VGP is rebuilt as a VGP (prior K + jitt I on its own training set), never as an SVGP with Z = X
-        "class": "MOVGP" if mo and full else "MOSVGP" if mo else "GP" if exact else "VGP" if full else "SVGP",
+        "class": "MCGP" if sampled else "MOVGP" if mo and full else "MOSVGP" if mo else "GP" if exact else "VGP" if full else "SVGP",
         "kernels": [_kernel_spec(k) for k in model.kernels],
         "likelihood": [_lik_spec(l) for l in model.likelihood.likelihoods] if mo else _lik_spec(model.likelihood),
         "stochastic": bool(inf.stoch), "batchsize": int(inf.batchsize), "n_iter": int(inf.n_iter),
@@ -119,6 +121,9 @@ def save_trained_model(filename: str, model: SVGP) -> None:
         # reloaded model silently froze A; its moments restart, like the Z optimiser's
         "a_opt": _opt_spec(getattr(model, "A_opt", None)) if mo else None,
     }
+    if sampled:  # the sampler's settings, the seed of the chain and its sweep counter: a loaded model continues the chain
+        meta["gibbs"] = {"nBurnin": inf.nBurnin, "thinning": inf.thinning, "eps": inf.eps, "seed": model.seed,
+                         "sweeps": model.sweep_counter()}
     import ctypes as C
 
     from . import capi
@@ -128,7 +133,11 @@ def save_trained_model(filename: str, model: SVGP) -> None:
     arrays = {"meta": np.array(json.dumps(meta)), "n_opt": np.array(n_opt.value)}
     for l in range(model.n_latent):
         arrays[f"Z_{l}"] = model.Zs[l]
-        if not exact:  # (a GP's posterior follows from the kernel, sigma2 and y: it is rebuilt on load)
+        if sampled:  # (the state of the chain is the sample f; Sigma follows from the next sweep)
+            arrays["gibbs_f"] = model.get_state(l)[0]
+            if inf.sample_store is not None:
+                arrays["gibbs_store"] = inf.sample_store
+        elif not exact:  # (a GP's posterior follows from the kernel, sigma2 and y: it is rebuilt on load)
             mu, Sig, e1, e2 = model.get_state(l)
             arrays[f"eta1_{l}"], arrays[f"eta2_{l}"] = e1, e2
     if mo:
@@ -197,6 +206,16 @@ def load_trained_model(filename: str, *, device=None):
                    opt_noise=ADAM(ld["noise_eta"]) if ld.get("noise_eta") else False, optimiser=kw["optimiser"] or False,
                    atfrequency=kw["atfrequency"], mean=mean, elbo_mode=meta["elbo_mode"], T=T, device=device, _initial_train=False)
         inf = model.inference  # (Analytic(), the GP's own)
+    elif meta["class"] == "MCGP":
+        from .mcgp import MCGP, GibbsSampling
+
+        gb = meta["gibbs"]
+        inf = GibbsSampling(gb["nBurnin"], gb["thinning"], gb["eps"])
+        model = MCGP(Zs[0], g["vgp_y"], kernels[0], _lik_from(meta["likelihood"]), inf, optimiser=kw["optimiser"],
+                     atfrequency=kw["atfrequency"], mean=mean, T=T, device=device)
+        model.seed = gb["seed"]
+        if "gibbs_store" in g.files:
+            inf.sample_store = g["gibbs_store"]
     elif meta["class"] == "VGP":
         from .vgp import VGP
 
@@ -206,6 +225,9 @@ def load_trained_model(filename: str, *, device=None):
         model = SVGP(kernels, _lik_from(meta["likelihood"]), inf, Zs, **kw)
     inf.n_iter = meta["n_iter"]
     h = model._ensure_handle(max(meta["batchsize"], 1))
+    if meta["class"] == "MCGP":
+        model.set_f(g["gibbs_f"])
+        model.set_sweep_counter(meta["gibbs"]["sweeps"])
     for l in range(nl):
         if f"eta1_{l}" in g.files:
             model.set_state(l, g[f"eta1_{l}"], g[f"eta2_{l}"])

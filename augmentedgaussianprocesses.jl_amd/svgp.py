@@ -167,7 +167,10 @@ class SVGP:
                  elbo_mode: str = "corrected", latent_slice: Optional[tuple] = None,
                  reference_compat_stale_K: bool = False, jitter: Optional[float] = None):
         exact = (getattr(self, "_desc_flags", 0) & capi.FLAG_EXACT) != 0  # (GP: Analytic() on a full handle, gp.py)
-        if not (isinstance(inference, Analytic) if exact else isinstance(inference, AnalyticVI)):
+        sampled = getattr(self, "_inference_type", None)  # (MCGP: GibbsSampling on a full handle, mcgp.py, which checks it)
+        if sampled is not None and isinstance(inference, sampled):
+            pass
+        elif not (isinstance(inference, Analytic) if exact else isinstance(inference, AnalyticVI)):
             raise TypeError("The inference object should be of type `VariationalInference` : either `AnalyticVI` or "
                             "`NumericalVI`")  # SVGP.jl:45-47 (only AnalyticVI exists on this path)
         # inside one train! the reference keeps the Cholesky of K_ZZ of the first iteration even after
@@ -710,8 +713,10 @@ def _hyper_step_guard(model):
                                   "Zoptimiser=False or mean=None")
 
 
+@functools.singledispatch
 def objective(model: SVGP, state: Optional[State] = None, y=None) -> float:
-    """objective(model, state, y) = ELBO(model, state, y) on the last minibatch (SVGP.jl:90, analyticVI.jl:255-274)."""
+    """objective(model, state, y) = ELBO(model, state, y) on the last minibatch (SVGP.jl:90, analyticVI.jl:255-274).
+    (An MCGP: its own method, mcgp.py.)"""
     L = capi.lib()
     Xd, yd, N = model._data
     out = C.c_double()
@@ -903,10 +908,11 @@ def _predict_f_fullcov(model: SVGP, X_test, obsdim: int = 1):
     return mu_np[0], cov_np[0]
 
 
+@functools.singledispatch
 def predict_f(model: SVGP, X_test, state: Optional[State] = None, *, cov: bool = False, diag: bool = True,
               obsdim: int = 1):
     """predict_f(model, X_test; cov=false, diag=true)  predictions.jl:141-164.  diag=False returns the full covariance
-    (not streamed: K*m is materialised, n_t <= 8192)."""
+    (not streamed: K*m is materialised, n_t <= 8192).  An MCGP: mean (and variance) over its samples (its own method, mcgp.py)."""
     if cov and not diag:
         return _predict_f_fullcov(model, X_test, obsdim)
     mu, var = _predict_f(model, X_test, cov, obsdim)
@@ -922,6 +928,7 @@ def predict_f(model: SVGP, X_test, state: Optional[State] = None, *, cov: bool =
     return mu_np[0], var.cpu().numpy()[0]
 
 
+@functools.singledispatch
 def predict_y(model: SVGP, X_test, state: Optional[State] = None, *, obsdim: int = 1):
     """predict_y  predictions.jl:178-198: regression mean / Bool (μ_f > 0) / most likely class label."""
     torch = _torch()
@@ -964,6 +971,7 @@ def _gauss_hermite():
     return _GH
 
 
+@functools.singledispatch
 def proba_y(model: SVGP, X_test, state: Optional[State] = None, *, obsdim: int = 1):
     """proba_y  predictions.jl:225-247: (mean, var) for regression, (p, var) for Bernoulli, dict class -> p for
     multi-class."""

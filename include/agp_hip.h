@@ -106,7 +106,7 @@ enum { AGP_ELBO_CORRECTED = 0, AGP_ELBO_REFERENCE = 1 };
  * src/functions/ELBO.jl:15-21).  With the flag a hyper step leaves the step-side matrices (L, inv(K), K\mu0) as they are and
  * only an explicit agp_svgp_refresh_K (what the host calls where train! starts and ends) recomputes them; without it
  * (default) K is refreshed before the next step. */
-enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4 };
+enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4, AGP_FLAG_SAMPLED = 8 };
 /* AGP_FLAG_FULL: the handle is the full (non-sparse) model VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85 --
  * one latent of dimension N per n_latent(likelihood), kappa = I, prior K + jitt I on the training inputs themselves.  Create it with
  * m = max_batch = N, stochastic = 0, dtype AGP_F64 (other types: AGP_ERR_UNSUPPORTED); a Gaussian likelihood is refused with
@@ -162,6 +162,24 @@ enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4 };
  *   predict_f / predict_f_cov / predict_y / proba_y  mu* = K*n alpha, var* = k** + jitt - diag(K*n Sigma^-1 Kn*) (predictions.jl:6-23);
  *                   proba_y adds sigma2
  * Refused with AGP_ERR_UNSUPPORTED on top of AGP_FLAG_FULL's list: get_matrix, elbo_enqueue, elbo_terms. */
+/* AGP_FLAG_SAMPLED (only together with AGP_FLAG_FULL, never with AGP_FLAG_EXACT): the Gibbs-sampled full model
+ * MCGP(X, y, kernel, likelihood, GibbsSampling())  src/models/MCGP.jl:37-92, src/inference/gibbssampling.jl, src/training/sampling.jl.
+ * Float64, one latent, likelihoods AGP_LIK_LOGISTIC, AGP_LIK_STUDENTT, AGP_LIK_NEGBINOMIAL (r an integer: Int(l.r),
+ * negativebinomial.jl:87; otherwise AGP_ERR_INVALID).  A Gaussian likelihood is refused with the reference's message (MCGP.jl:54-56),
+ * every other likelihood with AGP_ERR_UNSUPPORTED.  The handle's state is the current sample f (f = 0, Sigma = I at creation,
+ * latentgp.jl:81-86) and the sweep counter t (0 at creation).  The chain is advanced by agp_svgp_gibbs_sample and read by
+ * agp_svgp_predict_samples (below, "Gibbs sampling").  The other entry points:
+ *   get_state       mu <- f, sigma <- Sigma = inv(2 Diagonal(grad_E_Sigma) + inv(K)) of the last sweep (I before the first);
+ *                   eta1 / eta2 must be NULL (else AGP_ERR_UNSUPPORTED)
+ *   set_state       eta1 = f installs the sample the chain continues from (a reloaded model), eta2 must be NULL
+ *   get_matrix      AGP_VEC_THETA the local variables theta of the last sweep; AGP_VEC_C |f| as that sweep saw it (StudentT: the
+ *                   InverseGamma draw omega = 1 / theta)
+ *   set_Z, set_kernel, set_prior_mean, refresh_K, init_state, invalidate_data, get_lik_param: as for VGP.  The chain's state -- f,
+ *                   Sigma of the last sweep and the sweep counter -- belongs to the model like VGP's posterior: init_state keeps it
+ *                   (a new chain: a new handle, or set_state(f = 0) and agp_svgp_gibbs_counter(set = 1, 0))
+ * Refused with AGP_ERR_UNSUPPORTED on top of AGP_FLAG_FULL's list: cavi_step, elbo, elbo_enqueue, elbo_terms (objective(::MCGP) =
+ * NaN, MCGP.jl:91), hypergrad, hyper_step, hyper_apply, hyper_configure, hyper_rule (the reference never tunes an MCGP's kernel),
+ * predict_f, predict_f_cov, predict_y, proba_y (they have no sample store: agp_svgp_predict_samples). */
 
 /* matrices readable through agp_svgp_get_matrix (for parity tests and the shim's state export) */
 enum {
@@ -522,6 +540,75 @@ agp_status agp_svgp_set_lik_param(agp_svgp* h, double value);
  * LogisticSoftMax -> out0 = T[n_t][K] normalised logistic(mu_f) (multiclass.jl:96-117), out1 unused. */
 agp_status agp_svgp_proba_y(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, const double* gh_nodes_host,
                             const double* gh_weights_host, int32_t n_nodes, void* out0, void* out1);
+
+/* ---- Gibbs sampling (AGP_FLAG_FULL | AGP_FLAG_SAMPLED) ----------------------------------------------------------------------
+ * One sweep at counter t, for the single latent (sampling.jl:36-75, gibbssampling.jl:44-60):
+ *     theta_i ~ p(omega_i | f_i, y_i)                      sample_local!   logistic.jl:53-60: PG(1, |f_i|) ; negativebinomial.jl:83-90:
+ *                                                          PG(y_i + r, |f_i|) ; studentt.jl:84-92: omega_i ~ InverseGamma((nu + 1) / 2,
+ *                                                          ((f_i - y_i)^2 + sigma^2 nu) / 2), theta_i = 1 / omega_i
+ *     Sigma = inv(2 Diagonal(grad_E_Sigma) + inv(K))       sample_global!  with grad_E_mu, grad_E_Sigma = theta / 2 of the likelihood
+ *     f ~ N(Sigma (grad_E_mu + K \ mu0), Sigma)            as f = Xa' (Xa eta1 + z), Xa = chol(Sigma^-1)^-1 (lower), z ~ N(0, I)
+ *
+ * RANDOM STREAMS -- the contract that lets a host program reproduce a chain (tests/_mcgp_ref.py does).
+ *   Generator: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85, ten rounds).
+ *   Key (k0, k1) = (seed & 0xffffffff, seed >> 32).  Counter (c0, c1, c2, c3) = (i, t, stream, j): i the 0-based point index, t the
+ *   sweep counter, stream 0 = the local variables of point i, stream 1 = the normal draw z_i, j = 0, 1, 2, ... the block number.
+ *   Block j yields the words (w0, w1, w2, w3) and from them two uniforms, u_2j from (w0, w1) and u_2j+1 from (w2, w3):
+ *       k = (hi >> 5) << 26 | (lo >> 6)   (53 bits),   u = (k + 0.5) 2^-53,   so 0 < u < 1.
+ *   A stream is consumed strictly in the order u_0, u_1, u_2, ...  Derived variates:
+ *       Exponential  E = -log(u)                                (one uniform)
+ *       Normal       N = sqrt(-2 log a) cos(2 pi b)             (two uniforms a then b; the sine value is NOT used;
+ *                                                                2 pi = 6.283185307179586 multiplied onto b in double)
+ *   z_i of sweep t = Normal from stream 1 (block 0 only).  All comparisons below are in double, NaN-free.
+ *   PG(1, c) -- Devroye's alternating series as sample_pg1 states it (ComplementaryDistributions/polyagamma.jl:139-166), T = 0.64:
+ *       z = |c| / 2, K = pi^2 / 8 + z^2 / 2, r = mass_texpon(z) = 1 / (1 + (4 / pi)(exp(x0 - z + logPhi(b)) + exp(x0 + z + logPhi(a)))),
+ *       x0 = log K + K T, b = 1.25 (T z - 1), a = -1.25 (T z + 1), logPhi(x) = log(erfcx(-x / sqrt 2) / 2) - x^2 / 2 for x < 0 and
+ *       log1p(-erfc(x / sqrt 2) / 2) otherwise.
+ *       repeat:  u = U; if r > u: x = T + E / K, else x = TIG(z)
+ *                S = a(0, x); y = U S; for n = 1, 2, ...: n odd: S -= a(n, x), accept (return x / 4) unless y > S;
+ *                                                         n even: S += a(n, x), reject (repeat) if y > S
+ *       a(n, x) = k exp(-k^2 x / 2) for x > T, else exp(-1.5 (log(pi / 2) + log x) + log k - 2 (n + 1/2)^2 / x), k = (n + 1/2) pi.
+ *       TIG(z), mu = 1 / z (z = 0: infinity):
+ *         mu > T:  repeat { repeat { E = Exp, E' = Exp } while E^2 > 2 E' / T;  x = T / (1 + E T)^2;  u = U } while u > exp(-z^2 x / 2)
+ *         else:    repeat { Y = N^2; w = mu Y; x = mu + mu w / 2 - (mu / 2) sqrt(4 w + w^2); u = U; if u > mu / (mu + x): x = mu^2 / x }
+ *                  while x > T
+ *   PG(b, c), integer b >= 1: r once, then the sum of b draws of PG(1, c) from the same stream, one after the other
+ *       (draw_sum, polyagamma.jl:59-61); b = y_i + r of the NegBinomial likelihood, at most 65536.
+ *   InverseGamma(alpha, beta) = beta / G, G ~ Gamma(alpha, 1) by Marsaglia & Tsang: a' = alpha + 1 if alpha < 1 else alpha,
+ *       d = a' - 1/3, c = 1 / sqrt(9 d);  repeat { z = N; v1 = 1 + c z; if v1 <= 0 continue; v = v1^3; u = U;
+ *       accept if u < 1 - 0.0331 z^4, else accept if log u < z^2 / 2 + d (1 - v + log v) };  G = d v;  if alpha < 1: G *= exp(log(U) / alpha).
+ *   Every loop has an iteration bound (1000 rounds, 64 series terms) that a correct sampler does not reach; reaching it latches a
+ *   failure that agp_svgp_check_status reports as AGP_ERR_HIP.
+ *
+ * agp_svgp_gibbs_sample runs discard_initial + 1 + (n_samples - 1) * thinning sweeps and keeps sweep
+ *   discard_initial + 1 + k * thinning (1-based within the call), k = 0 .. n_samples - 1, writing the kept f into store[k][0 .. N)
+ *   (device, leading dimension lds >= N).  This kept-sweep convention is OURS: the reference delegates it to AbstractMCMC.jl, which is
+ *   not part of its sources (mcmcsample keeps the first sample after discard_initial and every thinning-th after it).  y: T[N] as for
+ *   cavi_step (NegBinomial: integer counts).  The whole chain is enqueued without a host synchronisation between sweeps (the first
+ *   call refreshes K, which synchronises once); failures -- a non-SPD matrix, a loop bound -- are latched and reported by
+ *   agp_svgp_check_status.  The sweep counter t lives in the handle and continues over calls: with one seed, two calls of S sweeps
+ *   give bit for bit the chain of one call of 2 S (the reference's cat = true).  t + sweeps must stay below 2^32.
+ * agp_svgp_gibbs_counter reads (set = 0) or sets (set = 1) the sweep counter (save / load).
+ * agp_sample_local is sample_local! on caller-supplied f outside any model -- the same kernel: theta_out[i] (and aux_out[i], nullable:
+ *   |f_i|, StudentT omega_i) drawn from stream 0 of (seed, t, i).  Float64 device pointers; lik->kind one of the three likelihoods
+ *   above; synchronises and reports a loop bound itself.  With AGP_LIK_LOGISTIC it is the reference's exported PolyaGamma(1, c) sampler.
+ * agp_svgp_predict_samples is _predict_f(::MCGP) / proba_y(::MCGP) (predictions.jl:94-130, 260-276) on a store of n_samples kept
+ *   samples (device, [n_samples][lds]): F* = K*n (K \ F) for all samples (_sample_f), test points in blocks of the handle's
+ *   prediction workspace (K*n is never held whole), then per test point, over the samples:
+ *     mode 0  out0 = mean f*
+ *     mode 1  out0 = mean f*, out1 = k** + jitt - diag(K*n K^-1 Kn*) + var f*      (the intended form of predictions.jl:115)
+ *     mode 2  out0, out1 = mean and variance of logistic(f*)                        (AGP_LIK_LOGISTIC only)
+ *   var is the sample variance (n - 1; NaN for one sample).  out0 / out1: T[n_t].  At most 65536 samples per call (AGP_ERR_INVALID
+ *   with a message beyond: the workspace holds F K^-1 of every sample of a call).
+ * NegBinomial targets must be non-negative integers: anything else is latched by the sweep (and reported by agp_sample_local) as
+ *   AGP_ERR_LABELS. */
+agp_status agp_svgp_gibbs_sample(agp_svgp* h, const void* y, int64_t n_samples, int64_t discard_initial, int64_t thinning,
+                                 uint64_t seed, void* store, int64_t lds);
+agp_status agp_svgp_gibbs_counter(agp_svgp* h, int32_t set, int64_t* t_host);
+agp_status agp_sample_local(agp_ctx* ctx, const agp_lik_desc* lik, const void* y, const void* f, int64_t n, uint64_t seed, int64_t t,
+                            void* theta_out, void* aux_out);
+agp_status agp_svgp_predict_samples(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, const void* store, int64_t lds,
+                                    int64_t n_samples, int32_t mode, void* out0, void* out1);
 
 /* ---- multi-GPU: one process per GPU, collectives behind the ABI --------------------------------
  * The path shards in two ways and both reduce to in-place SUM all-reduces of library-owned device buffers:

@@ -34,6 +34,7 @@ using AugmentedGaussianProcesses
 using KernelFunctions
 using LinearAlgebra
 using StatsBase: sample, Weights
+import StatsBase: sample               # (extended for MCGP below)
 using Random
 using Optimisers
 import ProgressMeter                      # (a dependency of the reference: train!'s progress reporting, training.jl:46,71-90)
@@ -77,6 +78,7 @@ end
 const AGP_FLAG_STALE_K = Int32(1)
 const AGP_FLAG_FULL = Int32(2)     # VGP: the full model, kappa = I, m = N, Z = the training inputs (agp_hip.h)
 const AGP_FLAG_EXACT = Int32(4)    # GP: exact regression with Analytic(), together with AGP_FLAG_FULL (agp_hip.h)
+const AGP_FLAG_SAMPLED = Int32(8)  # MCGP: Gibbs sampling of the augmented full model, together with AGP_FLAG_FULL (agp_hip.h)
 const AGP_SHARD_LATENT, AGP_SHARD_BATCH = Int32(0), Int32(1)
 
 struct AGPError <: Exception
@@ -169,8 +171,9 @@ mutable struct HipModel{T,M<:AGP.AbstractGPModel{T}}
 end
 
 is_mo(hm::HipModel) = hm.model isa Union{AGP.MOSVGP,AGP.MOVGP}
-is_full(hm::HipModel) = hm.model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP}   # (a MOVGP is both: IsMultiOutput and IsFull, MOVGP.jl:121-122)
+is_full(hm::HipModel) = hm.model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP,AGP.MCGP}   # (a MOVGP is both: IsMultiOutput and IsFull, MOVGP.jl:121-122)
 is_exact(hm::HipModel) = hm.model isa AGP.GP
+is_sampled(hm::HipModel) = hm.model isa AGP.MCGP
 # the latents of a model: a tuple / vector of them (SVGP, MOSVGP, VGP, MOVGP: `m.f`), or the single LatentGP of a GP (`f::LatentGP`, GP.jl:28)
 latents(m::AGP.AbstractGPModel) = m.f
 latents(m::AGP.GP) = (m.f,)
@@ -186,10 +189,11 @@ Wrap a reference model.  Nothing is allocated on the device until data arrive (`
 """
 function HipModel(model::M; reference_compat_stale_K::Bool=false,
                   latent_range::UnitRange{Int}=1:length(latents(model))) where {T,M<:AGP.AbstractGPModel{T}}
-    model isa Union{SVGP,AGP.MOSVGP,AGP.VGP,AGP.GP,AGP.MOVGP} || error("only SVGP / MOSVGP / VGP / GP / MOVGP run on the HIP path")
-    model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP} && T != Float64 && error("VGP / GP / MOVGP run in Float64 only on the HIP path")
-    AGP.inference(model) isa Union{AnalyticVI,AGP.Analytic} ||
-        error("The inference object should be of type `AnalyticVI`")   # SVGP.jl:45-47
+    model isa Union{SVGP,AGP.MOSVGP,AGP.VGP,AGP.GP,AGP.MOVGP,AGP.MCGP} ||
+        error("only SVGP / MOSVGP / VGP / GP / MOVGP / MCGP run on the HIP path")
+    model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP,AGP.MCGP} && T != Float64 && error("VGP / GP / MOVGP / MCGP run in Float64 only on the HIP path")
+    AGP.inference(model) isa (model isa AGP.MCGP ? AGP.GibbsSampling : Union{AnalyticVI,AGP.Analytic}) ||
+        error("The inference object should be of type `AnalyticVI` (MCGP: `GibbsSampling`)")   # SVGP.jl:45-47, MCGP.jl:51-53
     return HipModel{T,M}(model, C_NULL, C_NULL, C_NULL, AGP_SHARD_LATENT, latent_range, 0, nothing, nothing, 0, nothing,
                          reference_compat_stale_K, Int32(0), Int32(1), Any[])
 end
@@ -225,14 +229,14 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
     D = length(first(zview(hm, gp1)))
     m = AGP.dim(gp1)
     is_full(hm) && (maxbatch = m)                            # a VGP steps on its whole training set (idx = NULL, B = N = m)
-    stoch = AGP.is_stochastic(inf)
+    stoch = !is_sampled(hm) && AGP.is_stochastic(inf)
     rm = stoch ? inf.vi_opt.optimiser : nothing             # RobbinsMonro(κ, τ), optimisers.jl:1-19
     stoch && !(rm isa AGP.RobbinsMonro) && error("only RobbinsMonro is wired on this path (ALRSVI is dead code in the reference)")
     ld = is_mo(hm) ? LikDesc(4, 1, 0.0, 0.0) : lik_desc(AGP.likelihood(model))
     desc = SvgpDesc(T == Float64 ? 0 : 1, nlat(hm), first(hm.latent_range) - 1, stoch ? 1 : 0, m, D, maxbatch, ld, 0.0,
                     stoch ? rm.κ : 0.51, stoch ? rm.τ : 1.0, 0,
                     (hm.stale_K ? AGP_FLAG_STALE_K : Int32(0)) | (is_full(hm) ? AGP_FLAG_FULL : Int32(0)) |
-                    (is_exact(hm) ? AGP_FLAG_EXACT : Int32(0)))
+                    (is_exact(hm) ? AGP_FLAG_EXACT : Int32(0)) | (is_sampled(hm) ? AGP_FLAG_SAMPLED : Int32(0)))
     h = Ref{Ptr{Cvoid}}()
     check(ctx, ccall((:agp_svgp_create, libagp), Int32, (Ptr{Cvoid}, Ref{SvgpDesc}, Ptr{Ptr{Cvoid}}), ctx, desc, h))
     hm.h, hm.maxbatch = h[], maxbatch
@@ -268,6 +272,7 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
     end
     # hyper-parameter optimisers: SVGP(...; optimiser, Zoptimiser) (SVGP.jl:39-42, default ADAM(0.01) / nothing)
     ko, zo = AGP.opt(gp1), is_full(hm) ? nothing : AGP.Zopt(gp1)   # (the inputs of a VGP are never optimised)
+    is_sampled(hm) && (ko = nothing)                               # (the kernel of an MCGP is never tuned; the handle refuses the call)
     if ko !== nothing || zo !== nothing
         # the reference hands whatever Optimisers.jl rule it is given to Optimisers.apply (autotuning_utils.jl:47-82); the device
         # carries ADAM, Descent and Momentum (agp_svgp_hyper_rule), anything else is refused here rather than silently replaced
@@ -1090,5 +1095,80 @@ end
 objective(model::HipGP, state::HipModel, y=nothing) = objective(state)
 objective(model::HipGP, state, y) = has_twin(model) ? objective(TWINS[model]) : AGP.log_py(model, y)
 ELBO(model::HipGP) = has_twin(model) ? objective(TWINS[model]) : AGP.log_py(model, AGP.output(model.data))
+
+# MCGP{T,L,<:GibbsSampling} (src/models/MCGP.jl, src/training/sampling.jl): sample(model, n) on a handle created with
+# AGP_FLAG_FULL | AGP_FLAG_SAMPLED.  The whole chain is enqueued by agp_svgp_gibbs_sample; the kept samples come back as the
+# reference's sample_store (a vector over samples of a vector over latents of f), which the predictors read through
+# agp_svgp_predict_samples.  `seed` (default: drawn from Random.GLOBAL_RNG at the first call) and the sweep counter of the handle make
+# successive calls one chain (cat = true).  Never run: there is no Julia toolchain in the test environment.
+const HipMCGP{T} = AGP.MCGP{T,<:Any,<:AGP.GibbsSampling}
+const MCGP_SEED = IdDict{Any,UInt64}()
+twin(model::HipMCGP) = get!(() -> HipModel(model), TWINS, model)
+function sample(model::HipMCGP{T}, N::Int; thinning::Int=AGP.inference(model).thinning, discard_initial::Int=AGP.inference(model).nBurnin,
+                cat::Bool=true, seed=nothing, backend::Symbol=BACKEND[], kwargs...) where {T}
+    backend === :cpu && return invoke(sample, Tuple{AGP.MCGP,Int}, model, N; thinning, discard_initial, cat, kwargs...)
+    hm = twin(model)
+    X = reduce(hcat, AGP.input(model.data))'                     # N x D
+    hm.X === nothing && upload!(hm, X, AGP.output(model.data))
+    ensure_handle!(hm, hm.N)
+    s = seed === nothing ? get!(() -> rand(UInt64), MCGP_SEED, model) : (MCGP_SEED[model] = UInt64(seed))
+    store = ROCMatrix{T}(undef, hm.N, N)                         # column k == kept sample k (ABI: T[n_samples][lds])
+    check(hm.ctx, ccall((:agp_svgp_gibbs_sample, libagp), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, UInt64, Ptr{Cvoid}, Int64),
+                        hm.h, pointer(hm.y), N, discard_initial, thinning, s, pointer(store), hm.N))
+    check(hm.ctx, ccall((:agp_svgp_check_status, libagp), Int32, (Ptr{Cvoid},), hm.h))
+    F = Array(store)
+    samples = [[F[:, k]] for k in 1:N]
+    inf = AGP.inference(model)
+    inf.n_iter += discard_initial + 1 + (N - 1) * thinning
+    inf.sample_store = (!cat || isempty(inf.sample_store)) ? samples : vcat(inf.sample_store, samples)   # bundle_samples, sampling.jl:77-88
+    only(model.f).post.f .= F[:, end]
+    return samples
+end
+function sweep_counter(model::HipMCGP)
+    t = Ref{Int64}(0)
+    hm = twin(model)
+    check(hm.ctx, ccall((:agp_svgp_gibbs_counter, libagp), Int32, (Ptr{Cvoid}, Int32, Ref{Int64}), hm.h, 0, t))
+    return t[]
+end
+# sample_local! on given f outside any model: theta (and omega of the StudentT likelihood) for (seed, t)
+function sample_local(hm::HipModel{T}, lik, y::AbstractVector, f::AbstractVector, seed::Integer, t::Integer=0) where {T}
+    ctx = ensure_ctx!(hm)
+    yd, fd = ROCVector{Float64}(y), ROCVector{Float64}(f)
+    θ, aux = similar(fd), similar(fd)
+    check(ctx, ccall((:agp_sample_local, libagp), Int32,
+                     (Ptr{Cvoid}, Ref{LikDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, UInt64, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx, lik_desc(lik), pointer(yd), pointer(fd), length(fd), UInt64(seed), t, pointer(θ), pointer(aux)))
+    return Array(θ), Array(aux)
+end
+# mode 0: mean f*; 1: mean and variance (predictions.jl:94-118, intended form); 2: mean and variance of logistic(f*) (:266-276)
+function _predict_samples(model::HipMCGP{T}, X_test::AbstractMatrix, mode::Int; obsdim::Int=1) where {T}
+    hm = twin(model)
+    store = AGP.inference(model).sample_store
+    isempty(store) && error("the model holds no samples yet: call sample(model, n) first")
+    ensure_handle!(hm, hm.N)
+    Sd = ROCMatrix{T}(reduce(hcat, first.(store)))               # N x n_samples
+    Xd = ROCArray{T}(obsdim == 1 ? permutedims(X_test) : X_test)
+    D, nt = size(Xd)
+    o0, o1 = ROCVector{T}(undef, nt), ROCVector{T}(undef, nt)
+    check(hm.ctx, ccall((:agp_svgp_predict_samples, libagp), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                        hm.h, pointer(Xd), D, nt, pointer(Sd), size(Sd, 1), size(Sd, 2), mode, pointer(o0), mode == 0 ? C_NULL : pointer(o1)))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    return Array(o0), Array(o1)
+end
+function predict_f(model::HipMCGP, X_test::AbstractMatrix, state=nothing; cov::Bool=false, diag::Bool=true, backend::Symbol=BACKEND[], kw...)
+    (backend === :cpu || !has_twin(model)) &&
+        return invoke(predict_f, Tuple{AGP.AbstractGPModel,AbstractMatrix,Any}, model, X_test, state; cov, diag, kw...)
+    cov && !diag && error("MCGP: the full covariance over the samples is not formed on the device")
+    μ, σ² = _predict_samples(model, X_test, cov ? 1 : 0; kw...)
+    return cov ? (μ, σ²) : μ
+end
+function proba_y(model::HipMCGP{T,<:AGP.BernoulliLikelihood}, X_test::AbstractMatrix, state=nothing; backend::Symbol=BACKEND[], kw...) where {T}
+    (backend === :cpu || !has_twin(model)) &&
+        return invoke(proba_y, Tuple{AGP.MCGP,AbstractMatrix,Any}, model, X_test, state; kw...)
+    return _predict_samples(model, X_test, 2; kw...)
+end
+objective(model::HipMCGP, state::HipModel, y=nothing) = NaN      # MCGP.jl:91
 
 end # module
