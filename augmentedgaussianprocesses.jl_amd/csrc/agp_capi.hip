@@ -5643,12 +5643,17 @@ static agp_status bb_kernelmatrix(agp_ctx* ctx, const agp_kernel_desc* k, const 
   const void* yy = sym ? x : y;
   const int64_t pp = sym ? n : p, ldyy = sym ? ldx : ldy;
   dim3 g((unsigned)((pp + TILE - 1) / TILE), (unsigned)((n + TILE - 1) / TILE));
-  (void)launch_kernelmatrix<T>(ctx, ctx->stream, (const T*)x, ldx, idx, n, (const T*)yy, ldyy,
+  const int slices = launch_kernelmatrix<T>(ctx, ctx->stream, (const T*)x, ldx, idx, n, (const T*)yy, ldyy,
                      pp, D, (const T*)ds, k->kind, (T)k->variance, (T*)out, ldo, n, pp, 0, T(0), (const T*)nullptr,
                      (T*)nullptr, (int64_t)0);
   hipError_t e = hipGetLastError();
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
   (void)hipFree(ds);
+  if (slices < 0) {  // the scratch for the scaled Y side could not be allocated: nothing was launched
+    ctx->err = "agp_kernelmatrix: out of device memory";
+    return AGP_ERR_NOMEM;
+  }
+  if (e == hipSuccess) e = es;
   if (e != hipSuccess) {
     ctx->err = hipGetErrorString(e);
     return AGP_ERR_HIP;
@@ -5990,6 +5995,12 @@ agp_status agp_kernelmatrix(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* 
                             const int64_t* idx, const void* y, int64_t p, int64_t ldy, int64_t D, void* out,
                             int64_t ldo) {
   if (!ctx || !k || !x || !out || n <= 0 || D <= 0) return AGP_ERR_INVALID;
+  if (k->ard && !k->ard_scales_host) return AGP_ERR_INVALID;
+  // leading dimensions are in elements and at least the row width (include/agp_hip.h, "Layout"); the symmetric form is n x n
+  if (ldx < D || (y ? (p <= 0 || ldy < D || ldo < p) : ldo < n)) {
+    ctx->err = "agp_kernelmatrix: ldx >= D, and with y: p > 0, ldy >= D, ldo >= p; without y: ldo >= n";
+    return AGP_ERR_INVALID;
+  }
   DISPATCH(dtype, bb_kernelmatrix<double>(ctx, k, x, n, ldx, idx, y, p, ldy, D, out, ldo),
            bb_kernelmatrix<float>(ctx, k, x, n, ldx, idx, y, p, ldy, D, out, ldo));
 }
@@ -6010,6 +6021,10 @@ agp_status agp_spd_inverse(agp_ctx* ctx, int32_t dtype, const void* a, int64_t l
 agp_status agp_solve_right_spd(agp_ctx* ctx, int32_t dtype, const void* a, int64_t lda, int64_t n, const void* b,
                                int64_t ldb, int64_t r, void* x, int64_t ldx, int32_t* info_host) {
   if (!ctx || !a || !b || !x || n <= 0 || r <= 0) return AGP_ERR_INVALID;
+  if (lda < n || ldb < n || ldx < n) {
+    ctx->err = "agp_solve_right_spd: lda, ldb and ldx must be at least n";
+    return AGP_ERR_INVALID;
+  }
   DISPATCH(dtype, bb_solve_right<double>(ctx, a, lda, n, b, ldb, r, x, ldx, info_host),
            bb_solve_right<float>(ctx, a, lda, n, b, ldb, r, x, ldx, info_host));
 }

@@ -254,10 +254,25 @@ agp_status agp_ctx_sync(agp_ctx* ctx);
 agp_status agp_ctx_task_graph_fallbacks(agp_ctx* ctx, int64_t* n_host);
 const char* agp_last_error(agp_ctx* ctx);
 
+/* ---- Layout: leading dimensions, padding, alignment (every entry point; pinned by tests/test_gpu_abi_layout.py) -----------
+ *   - A leading dimension (ldx, ldy, ldo, lda, ldi, ldb, ldz, ldc, lds, ldza) counts ELEMENTS of T, not bytes, and must be at
+ *     least the width of a row of its matrix: element (r, c) is base[r * ld + c], 0 <= c < width.  A smaller one is refused
+ *     with AGP_ERR_INVALID before any buffer of the caller is read or written; the context / handle stays usable.
+ *   - The ld - width elements behind every row, and everything in front of the first and behind the last element of a vector or
+ *     matrix, are NEVER READ and NEVER WRITTEN -- they may hold NaN, or somebody else's data (a view into a larger array).
+ *     Outputs are written in exactly rows x width elements, whatever the library pads to internally (tiles of 64).
+ *   - A pointer needs the alignment of its element type only (8 bytes for double, 4 for float and int32, 8 for int64).  16-byte
+ *     vector loads are used where base, leading dimension and width allow them, element loads elsewhere; the values are the same
+ *     bit for bit either way, and do not depend on ld or on the base address.
+ *   - Vectors (y, idx, mu0, mu, eta1, labels, counts, the B-sized outputs of get_matrix, predict outputs T[..][n_t]) are dense. */
+
 /* ---- building blocks (unit parity) ---------------------------------------------------------------- */
 /* kernelmatrix(k, X, Y) / kernelmatrix(k, X) (y == NULL -> symmetric)   src/gpblocks/latentgp.jl:206,210
  * idx (nullable, int64[n]) gathers rows of X: row i of the result uses X[idx[i]] (the view(X, minibatch) of
- * src/training/training.jl:54).  out is n x p row-major with leading dimension ldo. */
+ * src/training/training.jl:54).  out is n x p row-major with leading dimension ldo >= p.
+ * Symmetric form (y == NULL; p and ldy are not read): out is n x n, ldo >= n, out[i][j] = k(X[idx ? idx[i] : i], X[j]) -- idx
+ * gathers the ROWS only, the columns are always x[0 .. n)  (kernelmatrix(k, X[idx]) needs a gathered copy of X).
+ * Refused with AGP_ERR_INVALID: n <= 0, D <= 0, ldx < D, and with y: p <= 0, ldy < D, ldo < p; without y: ldo < n. */
 agp_status agp_kernelmatrix(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n,
                             int64_t ldx, const int64_t* idx, const void* y, int64_t p, int64_t ldy, int64_t D,
                             void* out, int64_t ldo);
@@ -268,7 +283,8 @@ agp_status agp_potrf_jitter(agp_ctx* ctx, int32_t dtype, void* a, int64_t lda, i
 /* inv(A) for SPD A via Cholesky (inv(K::Cholesky) analyticVI.jl:179 ; -inv(eta2)/2 inference.jl:26) */
 agp_status agp_spd_inverse(agp_ctx* ctx, int32_t dtype, const void* a, int64_t lda, int64_t n, void* ainv,
                            int64_t ldi, double* logdet_host, int32_t* info_host);
-/* X = B / cholesky(A)  (Knm / K, two triangular solves in the reference, latentgp.jl:211); b is r x n */
+/* X = B / cholesky(A)  (Knm / K, two triangular solves in the reference, latentgp.jl:211); a is n x n (lda >= n), b and x are
+ * r x n (ldb >= n, ldx >= n; r may exceed n) */
 agp_status agp_solve_right_spd(agp_ctx* ctx, int32_t dtype, const void* a, int64_t lda, int64_t n, const void* b,
                                int64_t ldb, int64_t r, void* x, int64_t ldx, int32_t* info_host);
 /* ---- inducing-point selection (the step before the path) ----------------------------------------------------------------
