@@ -39,6 +39,10 @@ from .svgp import (  # noqa: F401
     AnalyticSVI,
     AnalyticVI,
     RobbinsMonro,
+    NumericalSVI,
+    NumericalVI,
+    QuadratureSVI,
+    QuadratureVI,
     objective,
     objective_enqueue,
     objective_fetch,
@@ -52,6 +56,7 @@ from .vgp import VGP, n_latent  # noqa: F401
 from .gp import GP, Analytic  # noqa: F401
 from .movgp import MOVGP  # noqa: F401
 from .mcgp import MCGP, GibbsSampling, sample, sample_local  # noqa: F401
+from .nvi import gauss_hermite_rule, quad_expectations  # noqa: F401
 from .capi import AGPError  # noqa: F401
 from .persistence import load_trained_model, save_trained_model  # noqa: F401
 from .inducingpoints import KmeansAlg, RandomSubset, inducingpoints  # noqa: F401

@@ -33,6 +33,7 @@ FLAG_STALE_K = 1  # reference_compat_stale_K
 FLAG_FULL = 2  # the full model VGP (kappa = I, m = N): agp_svgp_desc.flags, include/agp_hip.h
 FLAG_EXACT = 4  # exact GP regression GP(X, y, kernel) with Analytic(), together with FLAG_FULL (gp.py)
 FLAG_SAMPLED = 8  # the Gibbs-sampled full model MCGP, together with FLAG_FULL (mcgp.py)
+FLAG_NUMERICAL = 16  # numerical inference QuadratureVI: with FLAG_FULL the full model VGP, alone the sparse model SVGP (nvi.py)
 SHARD_LATENT, SHARD_BATCH = 0, 1
 COMM_ID_BYTES = 128
 # int32_t (*agp_allreduce_fn)(void* user, void* buf, int64_t count, int32_t dtype, void* hip_stream)
@@ -169,6 +170,11 @@ SYMBOLS = {
     "agp_svgp_gibbs_counter": (_I32, [_VP, _I32, _PI64]),
     "agp_sample_local": (_I32, [_VP, C.POINTER(LikDesc), _VP, _VP, _I64, C.c_uint64, _I64, _VP, _VP]),
     "agp_svgp_predict_samples": (_I32, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I32, _VP, _VP]),
+    "agp_svgp_nvi_configure": (_I32, [_VP, _I32, _PDBL, _PDBL, _I32, _I32, _DBL, _DBL, _DBL, _DBL]),
+    "agp_svgp_nvi_step": (_I32, [_VP, _VP, _I64, _VP, _VP, _I64, _DBL]),
+    "agp_svgp_nvi_info": (_I32, [_VP, _I32, _PDBL, _PI64, _PI64]),
+    "agp_svgp_nvi_state": (_I32, [_VP, _I32, _I32, _VP, _VP, _PI64]),
+    "agp_quad_expectations": (_I32, [_VP, C.POINTER(LikDesc), _VP, _VP, _VP, _I64, _PDBL, _PDBL, _I32, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 #include "agp_hyper.h"
 #include "agp_kmeans.h"
 #include "agp_linalg.h"
+#include "agp_nvi.h"
 #include "agp_rand.h"
 
 using namespace agp;
@@ -1285,6 +1286,19 @@ struct SvgpBase {
   virtual agp_status predict_samples(const void*, int64_t, int64_t, const void*, int64_t, int64_t, int, void*, void*) {
     return not_sampled("agp_svgp_predict_samples");
   }
+  // numerical inference (AGP_FLAG_NUMERICAL: Nvgp, Nsvgp); every other handle refuses
+  agp_status not_numerical(const char* what) {
+    ctx->err = std::string(what) + ": the handle does not run numerical inference (AGP_FLAG_NUMERICAL, with or without AGP_FLAG_FULL)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  virtual agp_status nvi_configure(int, const double*, const double*, int, int, double, double, double, double) {
+    return not_numerical("agp_svgp_nvi_configure");
+  }
+  virtual agp_status nvi_step(const void*, int64_t, const void*, const int64_t*, int64_t, double) {
+    return not_numerical("agp_svgp_nvi_step");
+  }
+  virtual agp_status nvi_info(int, double*, int64_t*, int64_t*) { return not_numerical("agp_svgp_nvi_info"); }
+  virtual agp_status nvi_state(int, int, void*, void*, int64_t*) { return not_numerical("agp_svgp_nvi_state"); }
   int64_t n_opt = 1;  // RobbinsMonro counter (optimisers.jl:12)
   bool in_cavi_step = false;  // step_local is running as the first half of agp_svgp_cavi_step (its tail may then be deferred)
   int64_t n_prologue = 0;  // CAVI steps whose natural-gradient part rode on the next step's task-graph launch (agp_svgp_step_counters)
@@ -5549,6 +5563,456 @@ struct Mcgp : Vgp {
   }
 };
 
+// ---- numerical inference on the full model (AGP_FLAG_FULL | AGP_FLAG_NUMERICAL: VGP(X, y, kernel, likelihood, QuadratureVI())) ----
+// src/inference/numericalVI.jl, src/inference/quadratureVI.jl.  The state is (mu, Sigma) itself -- kept in g.mu / g.Sigma with
+// g.post_valid always set, so predictions read it where materialize() would have left it -- and the optimiser moments of both.
+// One step (nvi_step): k_vgp_diag + k_quad_local give g, h at the current posterior; k_nvi_grad_mu forms the gradient of eta1 and
+// the rule's d mu; the gradient of eta2 is, in natural mode, (Sigma Diagonal(h) - Sigma K^-1) Sigma + Sigma (two gemm_nt, no inverse of
+// Sigma), in classical mode Diagonal(h / 2) - (K^-1 - Sigma^-1) / 2 with Sigma^-1 from the inverse factor of the accepted Sigma;
+// k_nvi_grad_sigma applies the rule on the upper triangle and mirrors it; the backtracking forms Sigma + alpha D (k_nvi_candidate),
+// factors it (potrf_fused) and reads the pivot status on the HOST once per attempt.  The accepted factor stays in nv_F / nv_Dg
+// (log det Sigma of the ELBO) and nv_X (its inverse, classical mode).
+static double nvi_lconst(int kind, double p0) {
+  if (kind == AGP_LIK_STUDENTT)  // studentt.jl:43-46 as written: Gamma(alpha) / (sqrt(nu pi) Gamma(nu / 2)), alpha = (nu + 1) / 2
+    return std::lgamma(0.5 * (p0 + 1.0)) - 0.5 * std::log(p0 * 3.141592653589793) - std::lgamma(0.5 * p0);
+  if (kind == AGP_LIK_LAPLACE) return -std::log(2.0 * p0);
+  return 0.0;
+}
+static bool nvi_lik_ok(int kind) { return kind == AGP_LIK_LOGISTIC || kind == AGP_LIK_STUDENTT || kind == AGP_LIK_LAPLACE; }
+static const char* nvi_supported() {
+  return "quadrature inference on the device runs for the Logistic, StudentT and Laplace likelihoods, Float64, one latent, on the "
+         "full model (AGP_FLAG_FULL | AGP_FLAG_NUMERICAL) and the sparse model (AGP_FLAG_NUMERICAL)";
+}
+
+struct Nvgp : Vgp {
+  bool configured = false, natural = true;
+  int nn = 0;
+  NviRule rule{};
+  double* quad_dev = nullptr;  // [nodes | weights]
+  int64_t nv_t = 0;            // steps taken: ADAM's t of both states
+  double alpha_last = 1.0;
+  int64_t halvings_total = 0, rejected_total = 0;
+  T *nv_K = nullptr, *nv_A = nullptr, *nv_D = nullptr, *nv_C = nullptr, *nv_F = nullptr, *nv_X = nullptr, *nv_Dg = nullptr,
+    *nv_dmu = nullptr;
+  double *mom_mu = nullptr, *mom_S = nullptr;  // [2][mp], [2][mp][mp]: Momentum's vel / ADAM's m, then ADAM's v
+  int32_t* nv_info = nullptr;
+  bool factor_valid = false, nvK_valid = false;
+  ~Nvgp() override {
+    for (T* p : {nv_K, nv_A, nv_D, nv_C, nv_F, nv_X, nv_Dg, nv_dmu})
+      if (p) dfree(p);
+    for (double* p : {mom_mu, mom_S, quad_dev})
+      if (p) dfree(p);
+    if (nv_info) dfree(nv_info);
+  }
+  agp_status check_desc() override {
+    AGPCHK(Svgp<T>::check_desc());
+    AGPCHK(check_full());
+    if (lp.kind == AGP_LIK_GAUSSIAN) {  // test/likelihood/gaussian.jl:38,59
+      ctx->err = "The GaussianLikelihood is not compatible with QuadratureVI: use AnalyticVI (the expectations are closed-form)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    if (!nvi_lik_ok(lp.kind) || nl != 1) {
+      ctx->err = std::string("AGP_FLAG_NUMERICAL: ") + nvi_supported();
+      return AGP_ERR_UNSUPPORTED;
+    }
+    return AGP_OK;
+  }
+  agp_status init() override {
+    AGPCHK(Vgp::init());
+    const int64_t mm = mp * mp;
+    for (T** p : {&nv_K, &nv_A, &nv_D, &nv_C, &nv_F, &nv_X}) AGPCHK(dmalloc(ctx, p, mm));
+    AGPCHK(dmalloc(ctx, &nv_Dg, mp * TILE));
+    AGPCHK(dmalloc(ctx, &nv_dmu, mp));
+    AGPCHK(dmalloc(ctx, &mom_mu, 2 * mp));
+    AGPCHK(dmalloc(ctx, &mom_S, 2 * mm));
+    AGPCHK(dmalloc(ctx, &nv_info, 1));
+    Latent& g = lat[0];
+    HIPCHK(ctx, hipMemsetAsync(g.mu, 0, sizeof(T) * mp, st()));  // VarPosterior{T}(dim): mu = 0, Sigma = I (posterior.jl:29-37)
+    hipLaunchKernelGGL((k_set_identity<T>), grid2(mp, mp), blk2, 0, st(), g.Sigma, mp, mp, T(1));
+    LAUNCHCHK(ctx);
+    g.post_valid = true;
+    return zero_moments();
+  }
+  agp_status zero_moments() {
+    HIPCHK(ctx, hipMemsetAsync(mom_mu, 0, sizeof(double) * 2 * mp, st()));
+    HIPCHK(ctx, hipMemsetAsync(mom_S, 0, sizeof(double) * 2 * mp * mp, st()));
+    nv_t = 0;
+    return AGP_OK;
+  }
+  agp_status numerical_refused(const char* what) {
+    ctx->err = std::string("numerical inference (AGP_FLAG_NUMERICAL): ") + what +
+               " is not supported (the posterior moves by agp_svgp_nvi_step; the hyper-parameter step through the quadrature ELBO "
+               "is not built)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  agp_status step_local(const void*, int64_t, const void*, const int64_t*, int64_t, double, bool) override {
+    return numerical_refused("agp_svgp_cavi_step");
+  }
+  agp_status hypergrad(int, double*, double*, void*) override { return numerical_refused("agp_svgp_hypergrad"); }
+  agp_status hyper_step() override { return numerical_refused("agp_svgp_hyper_step"); }
+  agp_status hyper_apply(int, const double*, const double*, const void*) override { return numerical_refused("agp_svgp_hyper_apply"); }
+  agp_status hyper_configure(int, double, int, double, double, double, double) override {
+    return numerical_refused("agp_svgp_hyper_configure");
+  }
+  agp_status hyper_rule(int, double, int, double) override { return numerical_refused("agp_svgp_hyper_rule"); }
+
+  agp_status nvi_configure(int n, const double* nodes, const double* weights, int nat, int opt_kind, double eta, double p1,
+                           double p2, double eps) override {
+    if (n < 1 || n > 4096 || !nodes || !weights || !(eta > 0) ||
+        (opt_kind != AGP_OPT_ADAM && opt_kind != AGP_OPT_DESCENT && opt_kind != AGP_OPT_MOMENTUM)) {
+      ctx->err = "agp_svgp_nvi_configure: 1 <= n <= 4096 nodes and weights, eta > 0, opt_kind one of AGP_OPT_ADAM / DESCENT / MOMENTUM";
+      return AGP_ERR_INVALID;
+    }
+    if ((opt_kind == AGP_OPT_MOMENTUM && !(p1 >= 0 && p1 < 1)) ||
+        (opt_kind == AGP_OPT_ADAM && !(p1 >= 0 && p1 < 1 && p2 >= 0 && p2 < 1 && eps >= 0))) {
+      ctx->err = "agp_svgp_nvi_configure: Momentum takes 0 <= rho < 1 (p1), ADAM 0 <= beta1, beta2 < 1 (p1, p2) and eps >= 0";
+      return AGP_ERR_INVALID;
+    }
+    if (n != nn) {
+      if (quad_dev) dfree(quad_dev);
+      quad_dev = nullptr;
+      nn = 0;
+      AGPCHK(dmalloc(ctx, &quad_dev, 2 * (int64_t)n));
+      nn = n;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(quad_dev, nodes, sizeof(double) * n, hipMemcpyHostToDevice, st()));
+    HIPCHK(ctx, hipMemcpyAsync(quad_dev + n, weights, sizeof(double) * n, hipMemcpyHostToDevice, st()));
+    HIPCHK(ctx, hipStreamSynchronize(st()));  // (the caller's arrays may go away)
+    if (natural != (nat != 0)) factor_valid = false;  // classical mode keeps the inverse factor as well
+    natural = nat != 0;
+    rule.kind = opt_kind;
+    rule.eta = eta;
+    rule.p1 = p1;
+    rule.p2 = p2;
+    rule.eps = eps;
+    rule.c1 = rule.c2 = 1.0;
+    configured = true;
+    return AGP_OK;
+  }
+  agp_status need_config(const char* what) {
+    if (configured) return AGP_OK;
+    ctx->err = std::string(what) + ": install the quadrature rule and the optimiser first (agp_svgp_nvi_configure)";
+    return AGP_ERR_INVALID;
+  }
+  // K + jitt I unfactored (the natural gradient of eta1 multiplies by it) next to the factor, inverse and log det of refresh_K
+  agp_status ensure_K() {
+    Latent& g = lat[0];
+    const bool stale = g.K_stale;
+    AGPCHK(refresh_K());
+    if (stale || !nvK_valid) {
+      AGPCHK(ensure_zsc(g));
+      (void)launch_kernelmatrix<T>(ctx, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m, (const T*)g.Z, D, m, D,
+                                   (const T*)g.scales, g.k.kind, kvar(g), nv_K, mp, mp, mp, 1, (T)jitter, (const T*)nullptr, (T*)nullptr,
+                                   (int64_t)0, 0, (const T*)g.Zsc, (const T*)g.zn);
+      LAUNCHCHK(ctx);
+      nvK_valid = true;
+    }
+    return AGP_OK;
+  }
+  // factor Sigma + alpha D (nv_F, diagonal tiles nv_Dg; with its inverse nv_X in classical mode); *info: 0, or the leading minor
+  // that is not positive.  Sigma + alpha D itself is left in nv_C (keep_c).
+  agp_status factor_candidate(const T* Dm, T alpha, bool keep_c, int32_t* info) {
+    Latent& g = lat[0];
+    const int do_x = natural ? 0 : 1;
+    for (int pass = 0; pass < 2; ++pass) {
+      HIPCHK(ctx, hipMemsetAsync(nv_info, 0, sizeof(int32_t), st()));
+      hipLaunchKernelGGL((k_nvi_candidate<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, (const T*)g.Sigma, Dm, alpha,
+                         keep_c ? nv_C : (T*)nullptr, nv_F);
+      LAUNCHCHK(ctx);
+      AGPCHK(potrf_fused<T>(ctx, nv_F, mp, mp, nv_X, mp, nv_Dg, (T*)nullptr, 0, 0, do_x, nv_info, m));
+      HIPCHK(ctx, hipMemcpyAsync(info, nv_info, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
+      HIPCHK(ctx, hipStreamSynchronize(st()));
+      if (*info != -1 || pass == 1) break;
+      bool lost = false;  // the task graph lost a tile dependency: plain launches from here on, the candidate is formed again
+      AGPCHK(dag_lost_dependency(ctx, nv_info, &lost));
+      if (!lost) break;
+    }
+    if (*info < 0) {
+      ctx->err = "numerical inference: the factorisation of Sigma + alpha dSigma aborted (a tile dependency never arrived)";
+      return AGP_ERR_HIP;
+    }
+    return AGP_OK;
+  }
+  agp_status ensure_factor() {
+    if (factor_valid) return AGP_OK;
+    int32_t info = 0;
+    AGPCHK(factor_candidate((const T*)lat[0].Sigma, T(0), false, &info));
+    if (info != 0) {
+      ctx->err = "PosDefException: Sigma is not positive definite; leading minor " + std::to_string(info);
+      return AGP_ERR_NOT_POSDEF;
+    }
+    factor_valid = true;
+    return AGP_OK;
+  }
+  agp_status check_whole_set(const void* y, const int64_t* idx, int64_t B) {
+    if (idx != nullptr || B != m) {
+      ctx->err = "full model (AGP_FLAG_FULL): steps and ELBO evaluations run on the whole training set (idx = NULL, B = N = m)";
+      return AGP_ERR_BAD_BATCH;
+    }
+    if (!y) {
+      ctx->err = "numerical inference: y must be given";
+      return AGP_ERR_INVALID;
+    }
+    return AGP_OK;
+  }
+  void quad_local(int64_t B, const T* y, const int64_t* idx, const T* mf, const T* vf, T* ell, T* gq, T* hq) {
+    hipLaunchKernelGGL((k_quad_local<T>), grid1(B), dim3(256), 0, st(), B, lp, nvi_lconst(lp.kind, desc.lik.p0), y, idx, mf, vf,
+                       (const double*)quad_dev, (const double*)(quad_dev + nn), nn, ell, gq, hq);
+  }
+
+  // variational_updates + global_update! (numericalVI.jl:101-179) for the single latent; rho = 1 on the full model
+  agp_status nvi_step(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, double rho) override {
+    AGPCHK(need_config("agp_svgp_nvi_step"));
+    AGPCHK(check_whole_set(y, idx, B));
+    if (rho != 1.0) {
+      ctx->err = "agp_svgp_nvi_step: the full model takes rho = 1";
+      return AGP_ERR_INVALID;
+    }
+    Latent& g = lat[0];
+    AGPCHK(ensure_K());
+    if (!natural) AGPCHK(ensure_factor());
+    hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)g.Sigma, (const T*)g.mu, muf, varf);
+    quad_local(m, (const T*)y, nullptr, muf, varf, Kt, rbuf, wbuf);
+    LAUNCHCHK(ctx);
+    AGPCHK(update_from(rbuf, nullptr, wbuf));
+    record_batch(y, 1.0);
+    return AGP_OK;
+  }
+  // the optimiser step on mu and Sigma and the backtracking, from u = rho kappa' g (the full model: g), the data term P2 of the
+  // gradient of eta2 (sparse model: rho W Diagonal(h) W' or rho kappa' Diagonal(h) kappa, m x m; the full model: NULL) and h (the
+  // full model's diagonal data term; NULL with P2)
+  agp_status update_from(const T* u, const T* P2, const T* hd) {
+    Latent& g = lat[0];
+    const int64_t t1 = nv_t + 1;  // (the counter moves once both rules have been applied: it never runs ahead of the moments)
+    if (rule.kind == AGP_OPT_ADAM) {
+      rule.c1 = 1.0 - std::pow(rule.p1, (double)t1);
+      rule.c2 = 1.0 - std::pow(rule.p2, (double)t1);
+    }
+    hipLaunchKernelGGL((k_nvi_grad_mu<T>), grid1(m * 64), dim3(256), 0, st(), m, mp, natural ? 1 : 0,
+                       (const T*)(natural ? nv_K : g.Kinv), u, (const T*)g.mu, (const T*)g.mu0, rule, mom_mu, mom_mu + mp, nv_dmu);
+    LAUNCHCHK(ctx);
+    const int64_t mm = mp * mp;
+    if (natural) {
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, g.Sigma, mp, g.Kinv, mp, mp, mp, mp, 0, nv_A, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+      hipLaunchKernelGGL((k_nvi_left<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, (const T*)g.Sigma, hd, nv_A);
+      LAUNCHCHK(ctx);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, nv_A, mp, g.Sigma, mp, mp, mp, mp, 0, nv_C, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+      hipLaunchKernelGGL((k_nvi_grad_sigma<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, 1, (const T*)nv_C, (const T*)nullptr, P2,
+                         (const T*)g.Sigma, hd, rule, mom_S, mom_S + mm, nv_D);
+    } else {
+      AGPCHK(xtx_padded<T>(ctx, nv_X, mp, mp, nv_A, mp));  // Sigma^-1 from the inverse factor of the accepted Sigma
+      hipLaunchKernelGGL((k_nvi_grad_sigma<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, 0, (const T*)g.Kinv, (const T*)nv_A, P2,
+                         (const T*)g.Sigma, hd, rule, mom_S, mom_S + mm, nv_D);
+    }
+    hipLaunchKernelGGL((k_nvi_add<T>), grid1(m), dim3(256), 0, st(), m, g.mu, (const T*)nv_dmu);
+    LAUNCHCHK(ctx);
+    nv_t = t1;
+    // alpha = 1; while !isposdef(Sigma + alpha Symmetric(dSigma)) && alpha > 1e-8: alpha /= 2; alpha > 1e-8 ? accept : Sigma unchanged
+    // (the attempt at the first alpha <= 1e-8 cannot change the outcome and is not made)
+    double a = 1.0;
+    bool accepted = false;
+    factor_valid = false;
+    while (a > 1e-8) {
+      int32_t info = 0;
+      AGPCHK(factor_candidate((const T*)nv_D, (T)a, true, &info));
+      if (info == 0) {
+        accepted = true;
+        break;
+      }
+      a *= 0.5;
+      halvings_total += 1;
+    }
+    alpha_last = a;
+    if (accepted) {
+      std::swap(g.Sigma, nv_C);  // the accepted candidate becomes Sigma (both are handle-owned mp x mp buffers: no copy)
+      factor_valid = true;
+    } else {
+      rejected_total += 1;  // (mu has moved already, numericalVI.jl:166)
+    }
+    g.pred_valid = g.predvar_valid = false;
+    if (tw2_kis_of == 0) tw2_kis_of = -1;
+    n_steps += 1;
+    return AGP_OK;
+  }
+  agp_status nvi_info(int l, double* a_last, int64_t* halvings, int64_t* rejected) override {
+    if (l != 0) return AGP_ERR_INVALID;
+    if (a_last) *a_last = alpha_last;
+    if (halvings) *halvings = halvings_total;
+    if (rejected) *rejected = rejected_total;
+    return AGP_OK;
+  }
+  // the optimiser moments [2][m] and [2][m][m] (device, contiguous) and the step counter: what a saved model continues from
+  agp_status nvi_state(int l, int set, void* mmu, void* msig, int64_t* t) override {
+    if (l != 0 || !mmu || !msig || !t) return AGP_ERR_INVALID;
+    const int64_t mm = mp * mp;
+    for (int s = 0; s < 2; ++s) {
+      if (set) {
+        if (*t < 0) return AGP_ERR_INVALID;
+        HIPCHK(ctx, hipMemcpyAsync(mom_mu + s * mp, (const double*)mmu + s * m, sizeof(double) * m, hipMemcpyDeviceToDevice, st()));
+        HIPCHK(ctx, hipMemcpy2DAsync(mom_S + s * mm, sizeof(double) * mp, (const double*)msig + s * m * m, sizeof(double) * m,
+                                     sizeof(double) * m, m, hipMemcpyDeviceToDevice, st()));
+      } else {
+        HIPCHK(ctx, hipMemcpyAsync((double*)mmu + s * m, mom_mu + s * mp, sizeof(double) * m, hipMemcpyDeviceToDevice, st()));
+        HIPCHK(ctx, hipMemcpy2DAsync((double*)msig + s * m * m, sizeof(double) * m, mom_S + s * mm, sizeof(double) * mp,
+                                     sizeof(double) * m, m, hipMemcpyDeviceToDevice, st()));
+      }
+    }
+    if (set) nv_t = *t;
+    else *t = nv_t;
+    return AGP_OK;
+  }
+  // mean_f, var_f of the batch under the current posterior; the full model: mu and diag Sigma on the whole training set
+  virtual agp_status batch_moments(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, T* mf, T* vf) {
+    AGPCHK(check_whole_set(y, idx, B));
+    Latent& g = lat[0];
+    hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)g.Sigma, (const T*)g.mu, mf, vf);
+    LAUNCHCHK(ctx);
+    return AGP_OK;
+  }
+  // ELBO = rho sum_i sum_j w_j l(y_i, f_ij) - GaussianKL at the current posterior (numericalVI.jl:193-206); there are no local
+  // variables, so fresh_local changes nothing
+  agp_status elbo(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho, int, double* out) override {
+    if (!out) return AGP_ERR_INVALID;
+    AGPCHK(need_config("agp_svgp_elbo"));
+    Latent& g = lat[0];
+    AGPCHK(ensure_K());
+    AGPCHK(ensure_factor());
+    AGPCHK(batch_moments(x, ldx, y, idx, B, emuf, evarf));
+    quad_local(B, (const T*)y, idx, emuf, evarf, theta, rbuf2, wbuf2);
+    hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(1024), 0, st(), (const double*)theta, B, scal_dev);
+    hipLaunchKernelGGL((k_logdiag_sum<T>), dim3(1), dim3(1024), 0, st(), (const T*)nv_Dg, m, scal_dev + 2);
+    LAUNCHCHK(ctx);
+    AGPCHK(frob_dot((const T*)g.Kinv, (const T*)g.Sigma, mp, m, scal_dev + 3));
+    hipLaunchKernelGGL((k_axpby<T>), grid1(mp), dim3(256), 0, st(), mp, T(1), (const T*)g.mu, T(-1), (const T*)g.mu0, tmpv);
+    hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xk, mp, mp, (const T*)tmpv, pw0);
+    hipLaunchKernelGGL((k_sumsq<T>), dim3(1), dim3(1024), 0, st(), (const T*)pw0, mp, scal_dev + 4);
+    LAUNCHCHK(ctx);
+    double h[5];
+    HIPCHK(ctx, hipMemcpyAsync(h, scal_dev, sizeof(double) * 5, hipMemcpyDeviceToHost, st()));
+    HIPCHK(ctx, hipStreamSynchronize(st()));
+    AGPCHK(resolve_logdet(g));
+    e_data = h[0];
+    kl_aug = 0.0;
+    kl_gauss_last = 0.5 * (2.0 * g.half_logdetK - 2.0 * h[2] + h[3] + h[4] - (double)m);
+    *out = rho * e_data - kl_gauss_last;
+    return AGP_OK;
+  }
+  // mu, Sigma of the posterior; there are no natural parameters on this handle
+  agp_status get_state(int l, void* mu, void* sigma, void* eta1, void* eta2) override {
+    if (l != 0) return AGP_ERR_INVALID;
+    if (eta1 || eta2) {
+      ctx->err = "numerical inference (AGP_FLAG_NUMERICAL): the state is (mu, Sigma) (eta1 / eta2 must be NULL)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    Latent& g = lat[0];
+    if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, g.mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
+    if (sigma)
+      HIPCHK(ctx, hipMemcpy2DAsync(sigma, sizeof(T) * m, g.Sigma, sizeof(T) * mp, sizeof(T) * m, m, hipMemcpyDeviceToDevice, st()));
+    return AGP_OK;
+  }
+  // installs (mu, Sigma) (eta1 = mu, eta2 = Sigma: T[m], T[m][m]); Sigma must be positive definite
+  agp_status set_state(int l, const void* mu, const void* sigma) override {
+    if (l != 0 || !mu || !sigma) return AGP_ERR_INVALID;
+    Latent& g = lat[0];
+    HIPCHK(ctx, hipMemsetAsync(g.mu, 0, sizeof(T) * mp, st()));
+    HIPCHK(ctx, hipMemcpyAsync(g.mu, mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
+    hipLaunchKernelGGL((k_copy2d<T>), grid2(mp, mp), blk2, 0, st(), (const T*)sigma, m, m, m, g.Sigma, mp, mp, mp, T(1), T(1));
+    LAUNCHCHK(ctx);
+    g.pred_valid = g.predvar_valid = false;
+    if (tw2_kis_of == 0) tw2_kis_of = -1;
+    factor_valid = false;
+    return ensure_factor();
+  }
+  // init_state(model): new optimiser states (states.jl:50-84); the posterior belongs to the model and is kept
+  agp_status init_state() override {
+    AGPCHK(Vgp::init_state());
+    return zero_moments();
+  }
+};
+
+// ---- numerical inference on the sparse model (AGP_FLAG_NUMERICAL without AGP_FLAG_FULL: SVGP(kernel, likelihood, QuadratureVI() /
+// QuadratureSVI(B), Z)) --------------------------------------------------------------------------------------------------------------
+// Nvgp's state, optimiser, backtracking, ELBO tail and predictions on m inducing points; what differs is the batch side.  Per step:
+// K_nm (launch_kernelmatrix on x[idx]), kappa = K_nm K^-1 and kappa' = K^-1 K_mn (two gemm_nt; K^-1 is symmetric), Wt = Sigma kappa'
+// (m x B), K~, mean_f = kappa mu and var_f = diag(kappa Sigma kappa') + K~ (k_nvi_fstats), the quadrature on the batch, u = rho kappa' g
+// (k_nvi_kappat_g) and the data term of the gradient of eta2 as one product S Diagonal(rho h) S' with S = Wt (natural) or kappa'
+// (classical) (k_nvi_scale_cols + gemm_nt), then Nvgp::update_from.  The kernel matrices are recomputed every step: nothing is cached
+// between steps and there is no look-ahead.
+struct Nsvgp : Nvgp {
+  T *ns_Knm = nullptr, *ns_kap = nullptr, *ns_kapt = nullptr, *ns_Wt = nullptr, *ns_S2 = nullptr, *ns_u = nullptr;
+  T* ns_P2 = nullptr;  // the data term of the gradient of eta2, m x m (a buffer of its own: nv_F holds the kept factor)
+  ~Nsvgp() override {
+    for (T* p : {ns_Knm, ns_kap, ns_kapt, ns_Wt, ns_S2, ns_u, ns_P2})
+      if (p) dfree(p);
+  }
+  agp_status check_desc() override {
+    AGPCHK(Svgp<T>::check_desc());
+    if (desc.latent_offset != 0) return AGP_ERR_INVALID;
+    if (lp.kind == AGP_LIK_GAUSSIAN) {  // test/likelihood/gaussian.jl:38,59
+      ctx->err = "The GaussianLikelihood is not compatible with QuadratureVI: use AnalyticVI (the expectations are closed-form)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    if (!nvi_lik_ok(lp.kind) || nl != 1) {
+      ctx->err = std::string("AGP_FLAG_NUMERICAL: ") + nvi_supported();
+      return AGP_ERR_UNSUPPORTED;
+    }
+    return AGP_OK;
+  }
+  agp_status init() override {
+    AGPCHK(Nvgp::init());
+    for (T** p : {&ns_Knm, &ns_kap, &ns_kapt, &ns_Wt, &ns_S2}) AGPCHK(dmalloc(ctx, p, Bp * mp));
+    AGPCHK(dmalloc(ctx, &ns_u, mp));
+    AGPCHK(dmalloc(ctx, &ns_P2, mp * mp));
+    return AGP_OK;
+  }
+  // K_nm, kappa, kappa', Wt of the batch and its mean_f / var_f
+  agp_status batch_moments(const void* x, int64_t ldx, const void* y, const int64_t*idx, int64_t B, T* mf, T* vf) override {
+    if (!x || !y || ldx < D) {
+      ctx->err = "numerical inference on the sparse model: x and y must be given, ldx >= D";
+      return AGP_ERR_INVALID;
+    }
+    AGPCHK(check_batch(B));
+    Latent& g = lat[0];
+    AGPCHK(params_to_host(g));
+    AGPCHK(ensure_zsc(g));
+    const int64_t Bq = rup64(B);
+    (void)launch_kernelmatrix<T>(ctx, st(), (const T*)x, ldx, idx, B, (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind, kvar(g),
+                                 ns_Knm, mp, Bq, mp, 0, T(0), (const T*)nullptr, (T*)nullptr, (int64_t)0, 0, (const T*)g.Zsc,
+                                 (const T*)g.zn);
+    LAUNCHCHK(ctx);
+    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, ns_Knm, mp, g.Kinv, mp, Bq, mp, mp, 0, ns_kap, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, g.Kinv, mp, ns_Knm, mp, mp, Bq, mp, 0, ns_kapt, Bp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, g.Sigma, mp, ns_kap, mp, mp, Bq, mp, 0, ns_Wt, Bp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+    hipLaunchKernelGGL((k_nvi_fstats<T>), grid1(B * 64), dim3(256), 0, st(), B, m, mp, Bp, (const T*)ns_kap, (const T*)ns_Knm,
+                       (const T*)ns_Wt, (const T*)g.mu, (T)(g.k.variance + jitter), mf, vf);
+    LAUNCHCHK(ctx);
+    return AGP_OK;
+  }
+  agp_status nvi_step(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho) override {
+    AGPCHK(need_config("agp_svgp_nvi_step"));
+    if (!(rho > 0)) return AGP_ERR_INVALID;
+    AGPCHK(ensure_K());
+    if (!natural) AGPCHK(ensure_factor());
+    AGPCHK(batch_moments(x, ldx, y, idx, B, muf, varf));
+    quad_local(B, (const T*)y, idx, muf, varf, Kt, rbuf, wbuf);
+    const int64_t Bq = rup64(B);
+    hipLaunchKernelGGL((k_nvi_kappat_g<T>), grid1(mp * 64), dim3(256), 0, st(), m, mp, B, Bp, (const T*)ns_kapt, (const T*)rbuf, (T)rho,
+                       ns_u);
+    const T* S = natural ? ns_Wt : ns_kapt;
+    hipLaunchKernelGGL((k_nvi_scale_cols<T>), grid2(mp, Bq), blk2, 0, st(), m, B, mp, Bq, Bp, S, (const T*)wbuf, (T)rho, ns_S2);
+    LAUNCHCHK(ctx);
+    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, ns_S2, Bp, S, Bp, mp, mp, Bq, 0, ns_P2, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+    AGPCHK(update_from(ns_u, ns_P2, nullptr));
+    x_last = x;
+    y_last = y;
+    idx_last = idx;
+    B_last = B;
+    ldx_last = ldx;
+    rho_last = rho;
+    return AGP_OK;
+  }
+};
+
 // ================================================================================================================
 // C entry points
 // ================================================================================================================
@@ -6110,7 +6574,12 @@ agp_status agp_svgp_create(agp_ctx* ctx, const agp_svgp_desc* desc, agp_svgp** o
                            "AGP_FLAG_EXACT); ") + Mcgp::supported();
     return AGP_ERR_UNSUPPORTED;
   }
-  if (desc->flags & AGP_FLAG_SAMPLED) impl = new Mcgp();
+  if ((desc->flags & AGP_FLAG_NUMERICAL) && ((desc->flags & (AGP_FLAG_EXACT | AGP_FLAG_SAMPLED)) || desc->dtype != AGP_F64)) {
+    ctx->err = std::string("AGP_FLAG_NUMERICAL: ") + nvi_supported() + " (never with AGP_FLAG_EXACT or AGP_FLAG_SAMPLED)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if (desc->flags & AGP_FLAG_NUMERICAL) impl = (desc->flags & AGP_FLAG_FULL) ? new Nvgp() : new Nsvgp();
+  else if (desc->flags & AGP_FLAG_SAMPLED) impl = new Mcgp();
   else if (desc->flags & AGP_FLAG_EXACT) impl = new Gp();
   else if (desc->flags & AGP_FLAG_FULL) impl = desc->lik.kind == AGP_LIK_MULTIOUTPUT ? new Movgp() : new Vgp();
   else if (desc->dtype == AGP_F64) impl = new Svgp<double>();
@@ -6147,11 +6616,14 @@ agp_status agp_svgp_destroy(agp_svgp* h) {
   AGPCHK((h)->impl->flush())
 // entry points that have no meaning for a full model (AGP_FLAG_FULL): refused, nothing done
 static agp_status full_refused(agp_svgp* h, const char* what) {
-  h->impl->ctx->err = std::string("full model (AGP_FLAG_FULL): ") + what + " is not supported";
+  h->impl->ctx->err = std::string((h)->impl->desc.flags & AGP_FLAG_FULL ? "full model (AGP_FLAG_FULL): "
+                                                                          : "numerical inference (AGP_FLAG_NUMERICAL): ") +
+                      what + " is not supported";
   return AGP_ERR_UNSUPPORTED;
 }
+// (... nor for a handle that runs numerical inference, full or sparse: it has no CAVI phases, look-ahead, shards or kappa buffers)
 #define FULLNO(h, what) \
-  if ((h)->impl->desc.flags & AGP_FLAG_FULL) return full_refused((h), (what))
+  if ((h)->impl->desc.flags & (AGP_FLAG_FULL | AGP_FLAG_NUMERICAL)) return full_refused((h), (what))
 // ... the mixing weights' entry points: refused unless the full model is the multi-output one (Movgp)
 #define FULLNO_SINGLE(h, what)                                                                                  \
   if (((h)->impl->desc.flags & AGP_FLAG_FULL) && (h)->impl->desc.lik.kind != AGP_LIK_MULTIOUTPUT) \
@@ -6480,6 +6952,62 @@ agp_status agp_sample_local(agp_ctx* ctx, const agp_lik_desc* lik, const void* y
   }
   if (host & FLAG_RNG_BOUND) {
     ctx->err = "agp_sample_local: a variate sampler ran into its iteration bound (agp_rand.h)";
+    return AGP_ERR_HIP;
+  }
+  return AGP_OK;
+}
+
+// ---- numerical inference (AGP_FLAG_FULL | AGP_FLAG_NUMERICAL) ------------------------------------------------------------------
+agp_status agp_svgp_nvi_configure(agp_svgp* h, int32_t n, const double* nodes_host, const double* weights_host, int32_t natural,
+                                  int32_t opt_kind, double eta, double p1, double p2, double eps) {
+  HCHK(h);
+  return h->impl->nvi_configure(n, nodes_host, weights_host, natural, opt_kind, eta, p1, p2, eps);
+}
+agp_status agp_svgp_nvi_step(agp_svgp* h, const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho) {
+  HCHK(h);
+  return h->impl->nvi_step(x, ldx, y, idx, B, rho);
+}
+agp_status agp_svgp_nvi_info(agp_svgp* h, int32_t latent, double* alpha_last_host, int64_t* halvings_total_host,
+                             int64_t* rejected_total_host) {
+  HCHK(h);
+  return h->impl->nvi_info(latent, alpha_last_host, halvings_total_host, rejected_total_host);
+}
+agp_status agp_svgp_nvi_state(agp_svgp* h, int32_t latent, int32_t set, void* mom_mu, void* mom_sigma, int64_t* t_host) {
+  HCHK(h);
+  return h->impl->nvi_state(latent, set, mom_mu, mom_sigma, t_host);
+}
+agp_status agp_quad_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void* y, const void* mu, const void* var, int64_t n_pts,
+                                 const double* nodes_host, const double* weights_host, int32_t n, void* ell, void* g, void* h) {
+  if (!ctx || !lik || !y || !mu || !var || !nodes_host || !weights_host || !ell || !g || !h || n_pts < 0 || n < 1 || n > 4096)
+    return AGP_ERR_INVALID;
+  if (!nvi_lik_ok(lik->kind)) {
+    ctx->err = std::string("agp_quad_expectations: ") + nvi_supported();
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if ((lik->kind == AGP_LIK_STUDENTT && !(lik->p0 > 0.5 && lik->p1 > 0)) || (lik->kind == AGP_LIK_LAPLACE && !(lik->p0 > 0))) {
+    ctx->err = "agp_quad_expectations: StudentT needs nu > 0.5 and sigma > 0, Laplace beta > 0";
+    return AGP_ERR_INVALID;
+  }
+  if (n_pts == 0) return AGP_OK;
+  DevGuard guard(ctx->device);
+  double* q = nullptr;
+  AGPCHK(dmalloc(ctx, &q, 2 * (int64_t)n));
+  LikParams<double> lp{};
+  lp.kind = lik->kind;
+  lp.p0 = lik->p0;
+  lp.p1 = lik->p1;
+  hipError_t e = hipMemcpyAsync(q, nodes_host, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(q + n, weights_host, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL((k_quad_local<double>), grid1(n_pts), dim3(256), 0, ctx->stream, n_pts, lp, nvi_lconst(lik->kind, lik->p0),
+                       (const double*)y, (const int64_t*)nullptr, (const double*)mu, (const double*)var, (const double*)q, (const double*)(q + n), (int)n,
+                       (double*)ell, (double*)g, (double*)h);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(q);
+  if (e != hipSuccess) {
+    ctx->err = std::string("agp_quad_expectations: ") + hipGetErrorString(e);
     return AGP_ERR_HIP;
   }
   return AGP_OK;

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import capi
 from .likelihoods import GaussianLikelihood, LogisticLikelihood, NegBinomialLikelihood, StudentTLikelihood
-from .svgp import ELBO, SVGP, _gauss_hermite, objective, predict_f, predict_y, proba_y, train_
+from .svgp import ELBO, SVGP, _gauss_hermite, objective, predict_f, predict_y, proba_y, refuse_numerical, train_
 from .vgp import full_model_args
 
 
@@ -68,6 +68,7 @@ class MCGP(SVGP):
 
     def __init__(self, X, y, kernel, likelihood, inference, *, verbose: int = 0, optimiser=None, atfrequency: int = 1, mean=None,
                  obsdim: int = 1, T=np.float64, device: Optional[int] = None, seed: Optional[int] = None):
+        refuse_numerical("MCGP", inference)
         if not isinstance(inference, GibbsSampling):  # MCGP.jl:51-53 (HMCSampling does not exist on this path)
             raise TypeError("The inference object should be of type `SamplingInference` : either `GibbsSampling` or `HMCSampling`")
         if isinstance(likelihood, GaussianLikelihood):  # MCGP.jl:54-56

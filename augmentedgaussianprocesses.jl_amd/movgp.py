@@ -11,7 +11,7 @@ from typing import Optional
 import numpy as np
 
 from . import capi
-from .svgp import ELBO, MOSVGP, SVGP, train_
+from .svgp import ELBO, MOSVGP, SVGP, refuse_numerical, train_
 from .vgp import VGP, _elbo_vgp, _train_vgp, full_model_args
 
 
@@ -32,6 +32,7 @@ class MOVGP(MOSVGP):
             raise ValueError("num_latent must be positive")
         if isinstance(kernel, (list, tuple)) and len(kernel) != Q:  # MOVGP.jl:94-95
             raise ValueError("Number of kernels should be equal to the number of tasks")
+        refuse_numerical("MOVGP", inference)
         X, optimiser = full_model_args("MOVGP", "MOSVGP", inference, X, obsdim, optimiser, mean, T)
         self._desc_flags = capi.FLAG_FULL
         super().__init__(kernel, likelihoods, inference, [X] * Q, Aoptimiser=Aoptimiser, A=A, verbose=verbose,

@@ -14,7 +14,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import capi
-from .svgp import SVGP, AnalyticVI, _torch
+from .svgp import SVGP, AnalyticVI, _torch, refuse_numerical
 from .svgp import predict_f as _predict_f_fn
 from .svgp import predict_y as _predict_y_fn
 from .svgp import proba_y as _proba_y_fn
@@ -106,6 +106,7 @@ class OnlineSVGP:
     def __init__(self, kernel, likelihood, inference, Zalg: Optional[OIPS] = None, *, verbose: int = 0, optimiser=False,
                  atfrequency: int = 1, mean=None, Zoptimiser=False, T=np.float64, device: Optional[int] = None,
                  seed: Optional[int] = None, elbo_mode: str = "corrected"):
+        refuse_numerical("OnlineSVGP", inference)
         if not isinstance(inference, AnalyticVI):
             raise TypeError("The inference object should be of type `AnalyticVI`")  # OnlineSVGP.jl:45
         if inference.stoch:

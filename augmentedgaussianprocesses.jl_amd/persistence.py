@@ -124,6 +124,10 @@ def save_trained_model(filename: str, model: SVGP) -> None:
     if sampled:  # the sampler's settings, the seed of the chain and its sweep counter: a loaded model continues the chain
         meta["gibbs"] = {"nBurnin": inf.nBurnin, "thinning": inf.thinning, "eps": inf.eps, "seed": model.seed,
                          "sweeps": model.sweep_counter()}
+    numerical = bool(getattr(model, "_numerical", False))
+    if numerical:  # QuadratureVI: its settings; the state (mu, Sigma, the optimiser's moments, its step counter) goes below
+        meta["nvi"] = {"eps": inf.eps, "nGaussHermite": inf.nGaussHermite, "natural": inf.natural,
+                       "optimiser": _opt_spec(inf.nvi_optimiser)}
     import ctypes as C
 
     from . import capi
@@ -137,6 +141,12 @@ def save_trained_model(filename: str, model: SVGP) -> None:
             arrays["gibbs_f"] = model.get_state(l)[0]
             if inf.sample_store is not None:
                 arrays["gibbs_store"] = inf.sample_store
+        elif numerical:  # a loaded model continues bit for bit (train_(model, n, state=...))
+            from .nvi import get_opt_state
+
+            arrays["nvi_mu"], arrays["nvi_Sigma"] = model.get_state(l)
+            arrays["nvi_mom_mu"], arrays["nvi_mom_sigma"], t = get_opt_state(model)
+            arrays["nvi_t"] = np.array(t)
         elif not exact:  # (a GP's posterior follows from the kernel, sigma2 and y: it is rebuilt on load)
             mu, Sig, e1, e2 = model.get_state(l)
             arrays[f"eta1_{l}"], arrays[f"eta2_{l}"] = e1, e2
@@ -219,15 +229,31 @@ def load_trained_model(filename: str, *, device=None):
     elif meta["class"] == "VGP":
         from .vgp import VGP
 
+        if "nvi" in meta:
+            from .svgp import QuadratureVI
+
+            nv = meta["nvi"]
+            inf = QuadratureVI(nv["eps"], nv["nGaussHermite"], _opt_from(nv["optimiser"]), 0.0, nv["natural"])
         model = VGP(Zs[0], g["vgp_y"], kernels, _lik_from(meta["likelihood"]), inf, optimiser=kw["optimiser"],
                     atfrequency=kw["atfrequency"], mean=mean, T=T, device=device)
     else:
+        if "nvi" in meta:
+            from .svgp import QuadratureVI
+
+            nv = meta["nvi"]
+            inf = QuadratureVI(nv["eps"], nv["nGaussHermite"], _opt_from(nv["optimiser"]), 0.0, nv["natural"],
+                               _stoch=meta["stochastic"], _batchsize=meta["batchsize"])
         model = SVGP(kernels, _lik_from(meta["likelihood"]), inf, Zs, **kw)
     inf.n_iter = meta["n_iter"]
     h = model._ensure_handle(max(meta["batchsize"], 1))
     if meta["class"] == "MCGP":
         model.set_f(g["gibbs_f"])
         model.set_sweep_counter(meta["gibbs"]["sweeps"])
+    if "nvi_mu" in g.files:
+        from .nvi import set_opt_state
+
+        model.set_state(0, g["nvi_mu"], g["nvi_Sigma"])
+        set_opt_state(model, g["nvi_mom_mu"], g["nvi_mom_sigma"], int(g["nvi_t"]))
     for l in range(nl):
         if f"eta1_{l}" in g.files:
             model.set_state(l, g[f"eta1_{l}"], g[f"eta2_{l}"])

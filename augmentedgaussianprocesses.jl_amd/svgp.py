@@ -147,6 +147,94 @@ def AnalyticSVI(nMinibatch: int, eps: float = 1e-5, optimiser: Optional[RobbinsM
     return AnalyticVI(eps, _stoch=True, _batchsize=int(nMinibatch), _optimiser=opt)
 
 
+class QuadratureVI:
+    """QuadratureVI(; ϵ=1e-5, nGaussHermite=100, optimiser=Momentum(1e-5), clipping=0.0, natural=true)  quadratureVI.jl:1-66 --
+    variational inference with the expectations of the log-likelihood and of its derivatives by Gauss-Hermite quadrature, and a
+    (natural) gradient step on (μ, Σ) with positive-definiteness backtracking (numericalVI.jl:101-179).  Runs on VGP and SVGP (nvi.py).
+
+    `clipping` must be 0: the clipping branch of the reference (quadratureVI.jl:121-126) returns values of the opposite sign
+    convention to the unclipped one and is not offered."""
+
+    def __init__(self, eps: float = 1e-5, nGaussHermite: int = 100, optimiser=None, clipping: float = 0.0,
+                 natural: bool = True, *, _stoch=False, _batchsize=0):
+        if clipping != 0:
+            raise NotImplementedError("QuadratureVI: clipping != 0 is not offered (the clipping branch of the reference, "
+                                      "quadratureVI.jl:121-126, returns values of the opposite sign convention)")
+        if optimiser is None:
+            optimiser = Momentum(1e-5)
+        if not isinstance(optimiser, (ADAM, Descent, Momentum)):
+            raise NotImplementedError("QuadratureVI: the optimisers on the device are Descent, Momentum and ADAM")
+        if int(nGaussHermite) < 1:
+            raise ValueError("nGaussHermite must be at least 1")
+        self.eps = float(eps)
+        self.nGaussHermite = int(nGaussHermite)
+        self.nvi_optimiser = optimiser   # the rule on (μ, Σ); `optimiser` below is the attribute train_ reads (Robbins-Monro: none)
+        self.optimiser = None
+        self.clipping = 0.0
+        self.natural = bool(natural)
+        self.n_iter = 0
+        self.stoch = bool(_stoch)
+        self.batchsize = int(_batchsize)
+        self.rho = 1.0
+        self.HyperParametersUpdated = True
+
+    def __repr__(self):  # numericalVI.jl:91-96
+        return f"{'Stochastic numerical' if self.stoch else 'Numerical'} Inference by Quadrature"
+
+
+def QuadratureSVI(nMinibatch: int, eps: float = 1e-5, nGaussHermite: int = 100, optimiser=None, clipping: float = 0.0,
+                  natural: bool = True) -> QuadratureVI:
+    """QuadratureSVI(nMinibatch; ϵ=1e-5, nGaussHermite=100, optimiser=Momentum(1e-5), clipping=0.0, natural=true)
+    quadratureVI.jl:68-88: the stochastic form, minibatches of nMinibatch points with rho = N / nMinibatch.  Runs on SVGP (nvi.py);
+    VGP takes the whole data set and refuses it."""
+    return QuadratureVI(eps, nGaussHermite, optimiser, clipping, natural, _stoch=True, _batchsize=int(nMinibatch))
+
+
+def _numerical(integration_technique, kw, nGaussHermite, optimiser):
+    if str(integration_technique).lstrip(":") == "mc":
+        raise NotImplementedError("NumericalVI(:mc): MCIntegrationVI is not built on this path; use :quad")
+    if str(integration_technique).lstrip(":") != "quad":
+        raise ValueError("Only possible integration techniques are quadrature : :quad or mcmc integration :mc")  # numericalVI.jl:83-87
+    kw.pop("nMC", None)
+    return dict(kw, nGaussHermite=nGaussHermite, optimiser=optimiser if optimiser is not None else Momentum(1e-3))
+
+
+def NumericalVI(integration_technique="quad", eps: float = 1e-5, nMC: int = 1000, nGaussHermite: int = 20, optimiser=None,
+                natural: bool = True) -> QuadratureVI:
+    """NumericalVI(integration_technique=:quad; ϵ=1e-5, nMC=1000, nGaussHermite=20, optimiser=Momentum(1e-3), natural=true)
+    numericalVI.jl:24-52"""
+    return QuadratureVI(**_numerical(integration_technique, dict(eps=eps, natural=natural), nGaussHermite, optimiser))
+
+
+def NumericalSVI(nMinibatch: int, integration_technique="quad", eps: float = 1e-5, nMC: int = 200, nGaussHermite: int = 20,
+                 optimiser=None, natural: bool = True) -> QuadratureVI:
+    """NumericalSVI(nMinibatch, integration_technique=:quad; ...)  numericalVI.jl:54-89"""
+    kw = _numerical(integration_technique, dict(eps=eps, natural=natural), nGaussHermite, optimiser)
+    return QuadratureVI(**kw, _stoch=True, _batchsize=int(nMinibatch))
+
+
+def refuse_numerical(name: str, inference) -> None:
+    """What every model other than SVGP and VGP answers to QuadratureVI / QuadratureSVI: the limit, by name."""
+    if isinstance(inference, QuadratureVI):
+        raise NotImplementedError(f"{name} does not run {inference!r}: QuadratureVI runs on SVGP and VGP, in Float64, for the "
+                                  "Logistic, StudentT and Laplace likelihoods (the multi-output, online and sampled models are "
+                                  "a follow-up)")
+
+
+def check_numerical(name: str, inference, likelihood, optimiser, T) -> None:
+    """What SVGP and VGP refuse with QuadratureVI: a likelihood outside the three, a float type other than Float64, a kernel
+    optimiser (the default included: the hyper-parameter step through the quadrature ELBO is not built)."""
+    if not isinstance(likelihood, (LogisticLikelihood, StudentTLikelihood, LaplaceLikelihood)):
+        # SVGP.jl:48-49 / VGP.jl:57-58; test/likelihood/gaussian.jl:38,59 for the Gaussian likelihood
+        raise RuntimeError(f"The {likelihood} is not compatible or implemented with the {inference} (QuadratureVI runs for "
+                           "the Logistic, StudentT and Laplace likelihoods)")
+    if np.dtype(T) != np.dtype(np.float64):
+        raise NotImplementedError(f"{name} with QuadratureVI runs in Float64 only")
+    if optimiser is not False:
+        raise NotImplementedError(f"{name} with QuadratureVI: the hyper-parameter step through the quadrature ELBO is not "
+                                  "built; pass optimiser=False (the default ADAM(0.01) is not silently switched off)")
+
+
 class State:
     """What train! returns next to the model (states.jl:1-9): a reference to the device-resident state."""
 
@@ -170,9 +258,21 @@ class SVGP:
         sampled = getattr(self, "_inference_type", None)  # (MCGP: GibbsSampling on a full handle, mcgp.py, which checks it)
         if sampled is not None and isinstance(inference, sampled):
             pass
+        elif isinstance(inference, QuadratureVI):
+            # numerical inference: SVGP itself (both forms) and VGP (vgp.py, which has set _numerical and made its own checks)
+            if type(self) is SVGP:
+                check_numerical("SVGP", inference, likelihood, optimiser, T)
+                if Zoptimiser not in (False, None):
+                    raise NotImplementedError("SVGP with QuadratureVI: the inducing points are not optimised; pass Zoptimiser=False")
+                if latent_slice is not None or reference_compat_stale_K:
+                    raise NotImplementedError("SVGP with QuadratureVI: no latent_slice, no reference_compat_stale_K")
+                self._numerical = True
+                self._desc_flags = capi.FLAG_NUMERICAL
+            elif not getattr(self, "_numerical", False):
+                refuse_numerical(type(self).__name__, inference)
         elif not (isinstance(inference, Analytic) if exact else isinstance(inference, AnalyticVI)):
             raise TypeError("The inference object should be of type `VariationalInference` : either `AnalyticVI` or "
-                            "`NumericalVI`")  # SVGP.jl:45-47 (only AnalyticVI exists on this path)
+                            "`NumericalVI`")  # SVGP.jl:45-47 (QuadratureVI: the branch above)
         # inside one train! the reference keeps the Cholesky of K_ZZ of the first iteration even after
         # hyper-parameter steps (training.jl:187-208).  False (default): K is refreshed; True: mirror the reference.
         self.reference_compat_stale_K = bool(reference_compat_stale_K)
@@ -290,6 +390,11 @@ class SVGP:
         carry = {}
         if self._h is not None:
             old = [self.get_state(i) for i in range(self.n_latent)]
+            if getattr(self, "_numerical", False):  # (mu, Sigma) travel as set_state's two arguments, the optimiser state with them
+                from .nvi import get_opt_state
+
+                carry["nvi"] = get_opt_state(self)
+                old = [(None, None, mu, Sig) for mu, Sig in old]
             self._pre_destroy()
             n_opt = C.c_int64()
             self._chk(L.agp_svgp_get_opt_state(self._h, C.byref(n_opt)))
@@ -337,6 +442,10 @@ class SVGP:
             for i, (mu, Sig, e1, e2) in enumerate(old):
                 self.set_state(i, e1, e2)
             self._chk(L.agp_svgp_set_opt_state(h, n_opt.value))
+            if "nvi" in carry:
+                from .nvi import set_opt_state
+
+                set_opt_state(self, *carry["nvi"])
             if "alpha" in carry:
                 a = torch.as_tensor(carry["alpha"], dtype=self.tdtype, device=dev).contiguous()
                 self._chk(L.agp_svgp_set_lsm_alpha(h, C.c_void_p(a.data_ptr()), a.numel()))
@@ -347,6 +456,10 @@ class SVGP:
         return h
 
     def _post_create(self, h):
+        if getattr(self, "_numerical", False):  # QuadratureVI: the rule and the optimiser (nvi.py); nothing else applies
+            from .nvi import configure
+
+            return configure(self, h)
         if isinstance(self.likelihood, PoissonLikelihood):  # the lambda update integrates logistic by Gauss-Hermite
             nodes, weights = _gauss_hermite()
             self._chk(capi.lib().agp_svgp_set_quadrature(h, nodes.ctypes.data_as(C.POINTER(C.c_double)),
@@ -460,10 +573,17 @@ class SVGP:
 
     # ---- state export / import ----------------------------------------------------------------------------
     def get_state(self, latent: int = 0):
-        """(μ, Σ, η₁, η₂) of one latent as numpy arrays (VarPosterior, posterior.jl:21-27)."""
+        """(μ, Σ, η₁, η₂) of one latent as numpy arrays (VarPosterior, posterior.jl:21-27); with QuadratureVI (μ, Σ): the handle
+        keeps no natural parameters."""
         torch = _torch()
         dev = self._dev()
         m = self.m
+        if getattr(self, "_numerical", False):
+            mu = torch.empty(m, dtype=self.tdtype, device=dev)
+            Sig = torch.empty(m, m, dtype=self.tdtype, device=dev)
+            self._chk(capi.lib().agp_svgp_get_state(self._h, latent, C.c_void_p(mu.data_ptr()), C.c_void_p(Sig.data_ptr()), None, None))
+            self._chk(capi.lib().agp_ctx_sync(self._ctx))
+            return mu.cpu().numpy(), Sig.cpu().numpy()
         mu = torch.empty(m, dtype=self.tdtype, device=dev)
         e1 = torch.empty(m, dtype=self.tdtype, device=dev)
         Sig = torch.empty(m, m, dtype=self.tdtype, device=dev)
@@ -521,6 +641,7 @@ class MOSVGP(SVGP):
                  optimiser=False, atfrequency: int = 1, mean=None, Zoptimiser=False, T=np.float64,
                  device: Optional[int] = None, seed: Optional[int] = None, elbo_mode: str = "corrected",
                  latent_slice: Optional[tuple] = None):
+        refuse_numerical(type(self).__name__, inference)
         if not isinstance(inference, AnalyticVI):
             raise TypeError("The inference object should be of type `AnalyticVI`")  # MOSVGP.jl:55
         Zs = [np.asarray(z, dtype=np.float64) for z in Zs]
@@ -595,6 +716,12 @@ def train_(model: SVGP, X, y, iterations: int = 100, *, callback: Optional[Calla
     idx_stream: optional pre-generated minibatch indices (one int array per iteration) replacing
     StatsBase.sample(1:N, B; replace=false) (training.jl:51-53) so runs are reproducible across back-ends.
     """
+    if getattr(model, "_numerical", False):  # QuadratureVI / QuadratureSVI: its own loop (nvi.py)
+        if convergence is not None:
+            raise NotImplementedError("train_ with QuadratureVI: convergence= is not wired")
+        from .nvi import train_numerical
+
+        return train_numerical(model, iterations, X=X, y=y, callback=callback, state=state, obsdim=obsdim, idx_stream=idx_stream)
     torch = _torch()
     L = capi.lib()
     if not iterations > 0:

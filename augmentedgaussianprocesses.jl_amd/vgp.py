@@ -12,7 +12,7 @@ import numpy as np
 
 from . import capi
 from .likelihoods import GaussianLikelihood
-from .svgp import ADAM, ELBO, SVGP, AnalyticVI, train_
+from .svgp import ADAM, ELBO, SVGP, AnalyticVI, QuadratureVI, check_numerical, train_
 
 
 def full_model_args(name, sparse, inference, X, obsdim, optimiser, mean, T):
@@ -43,20 +43,31 @@ class VGP(SVGP):
 
     X: (N, D) array (rows = points; obsdim=2 takes the transposed layout).  `optimiser=True` is ADAM(0.01) (VGP.jl:63, unlike
     SVGP's 0.001).  A Real mean gives ConstantMean, a vector EmpiricalMean (VGP.jl:68-72).  Float64 only.
+
+    inference: AnalyticVI(), or QuadratureVI(...) (nvi.py) for the Logistic, StudentT and Laplace likelihoods.  With QuadratureVI
+    the handle keeps (mu, Sigma) and the optimiser's moments (AGP_FLAG_NUMERICAL), and `optimiser` must be False: the hyper-parameter
+    step through the quadrature ELBO is not built, and the default ADAM(0.01) is refused rather than silently switched off.
     """
 
     def __init__(self, X, y, kernel, likelihood, inference, *, verbose: int = 0, optimiser=None, atfrequency: int = 1,
                  mean=None, obsdim: int = 1, T=np.float64, device: Optional[int] = None):
-        if not isinstance(inference, AnalyticVI):  # VGP.jl:51
+        if not isinstance(inference, (AnalyticVI, QuadratureVI)):  # VGP.jl:51
             raise TypeError("The inference object should be of type `VariationalInference` : either `AnalyticVI` or "
                             "`NumericalVI`")
+        self._numerical = isinstance(inference, QuadratureVI)
+        if self._numerical:
+            check_numerical("VGP", inference, likelihood, optimiser, T)
+            if inference.stoch:
+                raise ValueError("VGP takes the full data set every iteration: use QuadratureVI(), or SVGP for "
+                                 "QuadratureSVI")
         if isinstance(likelihood, GaussianLikelihood):  # VGP.jl:54-56
             raise ValueError("For a Gaussian Likelihood you should directly use the `GP` model or the `SVGP` model for "
                              "large datasets")
         X, optimiser = full_model_args("VGP", "SVGP", inference, X, obsdim, optimiser, mean, T)
-        self._desc_flags = capi.FLAG_FULL
+        self._desc_flags = capi.FLAG_FULL | (capi.FLAG_NUMERICAL if self._numerical else 0)
         super().__init__(kernel, likelihood, inference, X, verbose=verbose, optimiser=optimiser, atfrequency=atfrequency,
                          mean=mean, Zoptimiser=False, T=T, device=device)
+        self.nvi_alphas = []  # QuadratureVI: alpha of every step taken (the backtracking's accepted step length)
         self.X = X
         yt = self._treat(y)
         if len(yt) != X.shape[0]:
@@ -64,7 +75,7 @@ class VGP(SVGP):
         self.y = y
         self.N = X.shape[0]
 
-    def _ensure_handle(self, max_batch: int):
+    def _ensure_handle(self, max_batch: int = 0):
         return super()._ensure_handle(self.N)  # the full model's handle always holds the whole training set
 
     def hypergrad(self, latent: int = 0):
@@ -102,6 +113,12 @@ def _train_vgp(model: VGP, *args, iterations: Optional[int] = None, callback=Non
         raise TypeError("train_(model::VGP, iterations)")
     if iterations is None:
         iterations = 100
+    if getattr(model, "_numerical", False):
+        if convergence is not None:
+            raise NotImplementedError("train_(model::VGP with QuadratureVI): convergence= is not wired")
+        from .nvi import train_numerical
+
+        return train_numerical(model, iterations, callback=callback, state=state)  # (X = None: the model's own data)
     return train_.dispatch(SVGP)(model, model.X, model.y, iterations, callback=callback, state=state,
                                  convergence=convergence)
 

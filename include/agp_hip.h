@@ -106,7 +106,7 @@ enum { AGP_ELBO_CORRECTED = 0, AGP_ELBO_REFERENCE = 1 };
  * src/functions/ELBO.jl:15-21).  With the flag a hyper step leaves the step-side matrices (L, inv(K), K\mu0) as they are and
  * only an explicit agp_svgp_refresh_K (what the host calls where train! starts and ends) recomputes them; without it
  * (default) K is refreshed before the next step. */
-enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4, AGP_FLAG_SAMPLED = 8 };
+enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4, AGP_FLAG_SAMPLED = 8, AGP_FLAG_NUMERICAL = 16 };
 /* AGP_FLAG_FULL: the handle is the full (non-sparse) model VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85 --
  * one latent of dimension N per n_latent(likelihood), kappa = I, prior K + jitt I on the training inputs themselves.  Create it with
  * m = max_batch = N, stochastic = 0, dtype AGP_F64 (other types: AGP_ERR_UNSUPPORTED); a Gaussian likelihood is refused with
@@ -625,6 +625,80 @@ agp_status agp_sample_local(agp_ctx* ctx, const agp_lik_desc* lik, const void* y
                             void* theta_out, void* aux_out);
 agp_status agp_svgp_predict_samples(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, const void* store, int64_t lds,
                                     int64_t n_samples, int32_t mode, void* out0, void* out1);
+
+/* ---- NUMERICAL INFERENCE (AGP_FLAG_NUMERICAL, with AGP_FLAG_FULL or with no other model flag) ---------------------------------------
+ * VGP(X, y, kernel, likelihood, QuadratureVI()) (with AGP_FLAG_FULL) and SVGP(kernel, likelihood, QuadratureVI() / QuadratureSVI(B), Z)
+ * (without)  src/inference/numericalVI.jl, src/inference/quadratureVI.jl.  Float64, one latent,
+ * likelihoods AGP_LIK_LOGISTIC, AGP_LIK_STUDENTT, AGP_LIK_LAPLACE; a Gaussian likelihood is refused as "not compatible"
+ * (test/likelihood/gaussian.jl:38,59), every other likelihood, AGP_F32, AGP_FLAG_EXACT and AGP_FLAG_SAMPLED with
+ * AGP_ERR_UNSUPPORTED.  The formulas below are the full model's (kappa = I, K~ = 0, rho = 1); the sparse model's follow them.  The handle keeps (mu, Sigma) itself (mu = 0, Sigma = I at
+ * creation) and the optimiser's moments of both, not (eta1, eta2).  One step, with (x_j, w_j) the rule the host installed:
+ *     mu_f = mu ; var_f = diag Sigma                                  latentgp.jl:171-189
+ *     f_ij = mu_f,i + sqrt(max(var_f,i, 0)) x_j                       quadratureVI.jl:118
+ *     g_i = sum_j w_j l'(y_i, f_ij) ; h_i = sum_j w_j l''(y_i, f_ij)  (grad_E_mu = g, grad_E_Sigma = h / 2)
+ *     grad_eta1 = g - K^-1 (mu - mu0) ; grad_eta2 = Diagonal(h / 2) - (K^-1 - Sigma^-1) / 2          numericalVI.jl:121-134
+ *     natural:  grad_eta2 <- 2 Sigma grad_eta2 Sigma ; grad_eta1 <- K grad_eta1                      numericalVI.jl:152-156
+ *               formed as (Sigma Diagonal(h) - Sigma K^-1) Sigma + Sigma and K g - (mu - mu0): no inverse of Sigma
+ *     d mu, d Sigma = rule(grad) ; mu <- mu + d mu                                                  numericalVI.jl:158-166
+ *     alpha = 1 ; while Sigma + alpha Symmetric(d Sigma) is not positive definite and alpha > 1e-8: alpha /= 2
+ *     alpha > 1e-8 ? Sigma <- Sigma + alpha Symmetric(d Sigma) : Sigma unchanged (mu has moved)      numericalVI.jl:167-175
+ *   Symmetric reads the upper triangle.  Positive definite = the library's Cholesky factorisation meets no non-positive pivot; the
+ *   status word is read by the host once per attempt, so a step synchronises at least once.  The accepted factor is kept (log det
+ *   Sigma of the ELBO; its inverse gives Sigma^-1 of the classical gradient).
+ *   rule (opt_kind = AGP_OPT_*): Descent d = eta g ; Momentum vel = p1 vel + eta g, d = vel ; ADAM m = p1 m + (1 - p1) g,
+ *   v = p2 v + (1 - p2) g^2, d = eta (m / (1 - p1^t)) / (sqrt(v / (1 - p2^t)) + eps), t = 1, 2, ... the step number.
+ *   The likelihood terms, with three definitions of the reference restated in their intended form (no bug-compatible mode):
+ *     Logistic (y in {-1, 1})   l = -log(1 + exp(-y f)), l' = y sigma(-y f), l'' = -sigma(f) sigma(-f)
+ *                               (logistic.jl:98-100 returns -exp(y f) / logistic(-y f)^2, which grows like exp(3 |f|))
+ *     StudentT (nu, sigma)      the density as written (studentt.jl:43-46), u = (y - f) / sigma, a = (nu + 1) / 2:
+ *                               l = log Gamma(a) - log sqrt(nu pi) - log Gamma(nu / 2) - a log(1 + u^2),
+ *                               l' = 2 a u / (sigma (1 + u^2)), l'' = -2 a (1 - u^2) / (sigma^2 (1 + u^2)^2)
+ *     Laplace (beta)            l = -|y - f| / beta - log(2 beta), l' = sign(y - f) / beta by quadrature;
+ *                               h_i = -(2 / beta) N(y_i; mu_f,i, var_f,i) in closed form (the second derivative is a delta function;
+ *                               laplace.jl:131 returns +1 / sqrt(2 pi var) / beta^2: wrong sign, no exponential); 0 where var_f <= 0
+ *     clipping                  not offered: the clipping branch of quadratureVI.jl:121-126 returns values of the opposite sign
+ *                               convention to the unclipped one
+ * (The entry point that installs the rule is agp_svgp_nvi_configure, not a second form of agp_svgp_set_quadrature: that name is
+ *   taken by the Gauss-Hermite rule of the predictions and of the Poisson likelihood, with another signature.)
+ * agp_svgp_nvi_configure installs the rule of n nodes x_j = sqrt(2) t_j and weights w_j = omega_j / sqrt(pi) ((t, omega) the
+ *   Gauss-Hermite rule; host arrays, copied: the device and a host restatement share them bit for bit), natural != 0 for the natural
+ *   gradient, and the optimiser (eta; p1, p2, eps as above, ignored where the rule has none).  It may be called again at any time; the
+ *   moments are kept.
+ * The sparse model (no AGP_FLAG_FULL; m inducing points, max_batch >= B; desc.stochastic is accepted and not read) sees a minibatch
+ *   through K_nm, kappa = K_nm K^-1, K~ = k_ii + jitt - diag(kappa K_mn) and rho = N / B (latentgp.jl:171-212, numericalVI.jl:136-150):
+ *     mu_f = kappa mu ; var_f = diag(kappa Sigma kappa') + K~
+ *     grad_eta1 = rho kappa' g - K^-1 (mu - mu0) ; grad_eta2 = rho kappa' Diagonal(h / 2) kappa - (K^-1 - Sigma^-1) / 2
+ *     natural: formed as K (rho kappa' g) - (mu - mu0) and rho W Diagonal(h) W' - Sigma K^-1 Sigma + Sigma with W = Sigma kappa'
+ *   The kernel matrices of the batch are recomputed every step and every ELBO evaluation; there is no look-ahead (agp_svgp_prefetch
+ *   is refused like the CAVI phases).  ELBO = rho sum over the batch - GaussianKL.
+ * agp_svgp_nvi_step: the full model takes the whole training set -- y T[N], idx = NULL, B = N, rho = 1 (anything else:
+ *   AGP_ERR_BAD_BATCH / AGP_ERR_INVALID); x is not read (the inputs are the handle's Z) and may be NULL.  The sparse model takes
+ *   (x, ldx, y, idx, B, rho) with the meaning they have for agp_svgp_cavi_step: x T[N][ldx], ldx >= D, y T[N] read at idx (NULL:
+ *   the first B points), B <= max_batch, rho > 0.
+ * agp_svgp_nvi_info reports alpha of the last step, the halvings and the rejected updates (alpha <= 1e-8) since creation.
+ * agp_svgp_nvi_state reads (set = 0) or installs (set = 1) the moments -- mom_mu double[2][N], mom_sigma double[2][N][N], device,
+ *   contiguous; slot 0 Momentum's velocity / ADAM's m, slot 1 ADAM's v; only the upper triangle of a mom_sigma slot is live -- and the
+ *   step counter t.  With get_state / set_state this is everything a saved model continues from bit for bit.
+ * The other entry points on such a handle:
+ *   get_state       mu, sigma; eta1 / eta2 must be NULL (AGP_ERR_UNSUPPORTED)
+ *   set_state       eta1 = mu T[N], eta2 = Sigma T[N][N] (contiguous); Sigma not positive definite: AGP_ERR_NOT_POSDEF
+ *   elbo            rho sum_i sum_j w_j l(y_i, f_ij) - GaussianKL at the current posterior (numericalVI.jl:193-206); fresh_local is
+ *                   ignored (there are no local variables); elbo_enqueue evaluates synchronously; elbo_terms = (sum, KL, 0)
+ *   predict_f / predict_f_cov / predict_y / proba_y, set_kernel, set_prior_mean, refresh_K, check_status: as for VGP
+ *   init_state      new optimiser moments, t = 0; the posterior is kept
+ * Refused with AGP_ERR_UNSUPPORTED on top of AGP_FLAG_FULL's list (which a sparse numerical handle shares: the CAVI phases,
+ * prefetch, shards, K_nm / kappa of get_matrix): cavi_step, hypergrad, hyper_step, hyper_apply, hyper_configure,
+ * hyper_rule (the hyper-parameter step through the quadrature ELBO is not built).
+ * agp_quad_expectations is the quadrature kernel on caller-supplied moments outside any model: ell_i = sum_j w_j l(y_i, f_ij), g_i, h_i
+ *   for n_pts points (y, mu, var, ell, g, h: double[n_pts], device; nodes, weights: double[n], host); synchronises. */
+agp_status agp_svgp_nvi_configure(agp_svgp* h, int32_t n, const double* nodes_host, const double* weights_host, int32_t natural,
+                                  int32_t opt_kind, double eta, double p1, double p2, double eps);
+agp_status agp_svgp_nvi_step(agp_svgp* h, const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho);
+agp_status agp_svgp_nvi_info(agp_svgp* h, int32_t latent, double* alpha_last_host, int64_t* halvings_total_host,
+                             int64_t* rejected_total_host);
+agp_status agp_svgp_nvi_state(agp_svgp* h, int32_t latent, int32_t set, void* mom_mu, void* mom_sigma, int64_t* t_host);
+agp_status agp_quad_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void* y, const void* mu, const void* var, int64_t n_pts,
+                                 const double* nodes_host, const double* weights_host, int32_t n, void* ell, void* g, void* h);
 
 /* ---- multi-GPU: one process per GPU, collectives behind the ABI --------------------------------
  * The path shards in two ways and both reduce to in-place SUM all-reduces of library-owned device buffers:

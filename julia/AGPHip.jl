@@ -79,6 +79,7 @@ const AGP_FLAG_STALE_K = Int32(1)
 const AGP_FLAG_FULL = Int32(2)     # VGP: the full model, kappa = I, m = N, Z = the training inputs (agp_hip.h)
 const AGP_FLAG_EXACT = Int32(4)    # GP: exact regression with Analytic(), together with AGP_FLAG_FULL (agp_hip.h)
 const AGP_FLAG_SAMPLED = Int32(8)  # MCGP: Gibbs sampling of the augmented full model, together with AGP_FLAG_FULL (agp_hip.h)
+const AGP_FLAG_NUMERICAL = Int32(16)  # QuadratureVI (with AGP_FLAG_FULL: VGP; alone: SVGP): the handle keeps (mu, Sigma) and the optimiser's moments (agp_hip.h)
 const AGP_SHARD_LATENT, AGP_SHARD_BATCH = Int32(0), Int32(1)
 
 struct AGPError <: Exception
@@ -174,6 +175,7 @@ is_mo(hm::HipModel) = hm.model isa Union{AGP.MOSVGP,AGP.MOVGP}
 is_full(hm::HipModel) = hm.model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP,AGP.MCGP}   # (a MOVGP is both: IsMultiOutput and IsFull, MOVGP.jl:121-122)
 is_exact(hm::HipModel) = hm.model isa AGP.GP
 is_sampled(hm::HipModel) = hm.model isa AGP.MCGP
+is_numerical(hm::HipModel) = hm.model isa Union{AGP.VGP,SVGP} && AGP.inference(hm.model) isa AGP.QuadratureVI
 # the latents of a model: a tuple / vector of them (SVGP, MOSVGP, VGP, MOVGP: `m.f`), or the single LatentGP of a GP (`f::LatentGP`, GP.jl:28)
 latents(m::AGP.AbstractGPModel) = m.f
 latents(m::AGP.GP) = (m.f,)
@@ -192,8 +194,18 @@ function HipModel(model::M; reference_compat_stale_K::Bool=false,
     model isa Union{SVGP,AGP.MOSVGP,AGP.VGP,AGP.GP,AGP.MOVGP,AGP.MCGP} ||
         error("only SVGP / MOSVGP / VGP / GP / MOVGP / MCGP run on the HIP path")
     model isa Union{AGP.VGP,AGP.GP,AGP.MOVGP,AGP.MCGP} && T != Float64 && error("VGP / GP / MOVGP / MCGP run in Float64 only on the HIP path")
-    AGP.inference(model) isa (model isa AGP.MCGP ? AGP.GibbsSampling : Union{AnalyticVI,AGP.Analytic}) ||
-        error("The inference object should be of type `AnalyticVI` (MCGP: `GibbsSampling`)")   # SVGP.jl:45-47, MCGP.jl:51-53
+    AGP.inference(model) isa (model isa AGP.MCGP ? AGP.GibbsSampling :
+                              model isa Union{AGP.VGP,SVGP} ? Union{AnalyticVI,AGP.QuadratureVI} : Union{AnalyticVI,AGP.Analytic}) ||
+        error("The inference object should be of type `AnalyticVI` (MCGP: `GibbsSampling`; SVGP and VGP also take `QuadratureVI`)")   # SVGP.jl:45-47, MCGP.jl:51-53
+    if model isa Union{AGP.VGP,SVGP} && AGP.inference(model) isa AGP.QuadratureVI   # what the numerical handle refuses (agp_hip.h, "NUMERICAL INFERENCE")
+        model isa AGP.VGP && AGP.is_stochastic(AGP.inference(model)) && error("VGP takes the full data set every iteration: use QuadratureVI()")
+        model isa SVGP && any(gp -> AGP.Zopt(gp) !== nothing, latents(model)) && error("SVGP with QuadratureVI: the inducing points are not optimised; pass Zoptimiser=false")
+        AGP.likelihood(model) isa Union{AGP.LogisticLikelihood,AGP.StudentTLikelihood,AGP.LaplaceLikelihood} ||
+            error("QuadratureVI on the HIP path runs for the Logistic, StudentT and Laplace likelihoods")
+        AGP.inference(model).clipping == 0 || error("QuadratureVI: clipping != 0 is not offered (quadratureVI.jl:121-126)")
+        all(gp -> AGP.opt(gp) === nothing, latents(model)) ||
+            error("QuadratureVI: the hyper-parameter step through the quadrature ELBO is not built; pass optimiser=false")
+    end
     return HipModel{T,M}(model, C_NULL, C_NULL, C_NULL, AGP_SHARD_LATENT, latent_range, 0, nothing, nothing, 0, nothing,
                          reference_compat_stale_K, Int32(0), Int32(1), Any[])
 end
@@ -236,7 +248,8 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
     desc = SvgpDesc(T == Float64 ? 0 : 1, nlat(hm), first(hm.latent_range) - 1, stoch ? 1 : 0, m, D, maxbatch, ld, 0.0,
                     stoch ? rm.κ : 0.51, stoch ? rm.τ : 1.0, 0,
                     (hm.stale_K ? AGP_FLAG_STALE_K : Int32(0)) | (is_full(hm) ? AGP_FLAG_FULL : Int32(0)) |
-                    (is_exact(hm) ? AGP_FLAG_EXACT : Int32(0)) | (is_sampled(hm) ? AGP_FLAG_SAMPLED : Int32(0)))
+                    (is_exact(hm) ? AGP_FLAG_EXACT : Int32(0)) | (is_sampled(hm) ? AGP_FLAG_SAMPLED : Int32(0)) |
+                    (is_numerical(hm) ? AGP_FLAG_NUMERICAL : Int32(0)))
     h = Ref{Ptr{Cvoid}}()
     check(ctx, ccall((:agp_svgp_create, libagp), Int32, (Ptr{Cvoid}, Ref{SvgpDesc}, Ptr{Ptr{Cvoid}}), ctx, desc, h))
     hm.h, hm.maxbatch = h[], maxbatch
@@ -270,6 +283,7 @@ function ensure_handle!(hm::HipModel{T}, maxbatch::Int) where {T}
         check(ctx, ccall((:agp_svgp_set_quadrature, libagp), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32),
                          hm.h, AGP.pred_nodes, AGP.pred_weights, length(AGP.pred_nodes)))
     end
+    is_numerical(hm) && nvi_configure!(hm)
     # hyper-parameter optimisers: SVGP(...; optimiser, Zoptimiser) (SVGP.jl:39-42, default ADAM(0.01) / nothing)
     ko, zo = AGP.opt(gp1), is_full(hm) ? nothing : AGP.Zopt(gp1)   # (the inputs of a VGP are never optimised)
     is_sampled(hm) && (ko = nothing)                               # (the kernel of an MCGP is never tuned; the handle refuses the call)
@@ -304,6 +318,7 @@ opt_state(hm::HipModel) = (n = Ref{Int64}(); ccall((:agp_svgp_get_opt_state, lib
 # (μ, Σ, η₁, η₂) device -> the reference's VarPosterior (posterior.jl:21-27), e.g. at the end of train!
 function pull_posterior!(hm::HipModel{T}) where {T}
     is_exact(hm) && return pull_gp_posterior!(hm)
+    is_numerical(hm) && return pull_nvi_posterior!(hm)
     for (i, q) in enumerate(hm.latent_range)
         gp = latents(hm.model)[q]
         m = AGP.dim(gp)
@@ -401,7 +416,10 @@ function update_parameters!(hm::HipModel{T}, idx, ρ::Real) where {T}
     hm.last_idx = idd
     B = idx === nothing ? hm.N : length(idx)
     idp = idd === nothing ? Ptr{Int64}(C_NULL) : pointer(idd)
-    st = if hm.comm == C_NULL && nlat(hm) == length(latents(hm.model))
+    st = if is_numerical(hm)   # variational_updates of numericalVI.jl:101-119 (the whole training set: idx = NULL, rho = 1)
+        ccall((:agp_svgp_nvi_step, libagp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int64, Float64),
+              hm.h, pointer(hm.X), D, pointer(hm.y), idp, B, ρ)
+    elseif hm.comm == C_NULL && nlat(hm) == length(latents(hm.model))
         ccall((:agp_svgp_cavi_step, libagp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int64, Float64),
               hm.h, pointer(hm.X), D, pointer(hm.y), idp, B, ρ)
     else
@@ -535,7 +553,7 @@ function train!(hm::HipModel{T}, X::AbstractArray, y, iterations::Int=100; callb
         # index buffers stay referenced for two iterations: the look-ahead reads `nxt`, and the step's natural-gradient part is
         # taken by the NEXT launch (it reads device copies only, but the buffer identity is what the look-ahead is recognised by)
         push!(hm.keep, idd); length(hm.keep) > 3 && popfirst!(hm.keep)
-        (nxt === nothing || hyper_now) || prefetch!(hm, nxt)
+        (nxt === nothing || hyper_now || is_numerical(hm)) || prefetch!(hm, nxt)   # (a numerical handle has no look-ahead)
         callback === nothing || callback(hm, hm, AGP.n_iter(model))
         hyper_now && update_hyperparameters!(hm)
         report(local_iter)
@@ -1043,6 +1061,80 @@ for f in (:predict_f, :predict_y, :proba_y)
     end
 end
 objective(model::HipVGP, state::HipModel, y=nothing) = objective(state)
+
+# VGP{T,L,<:QuadratureVI} (src/inference/numericalVI.jl, quadratureVI.jl): the same train!(model, iterations) on a handle created with
+# AGP_FLAG_FULL | AGP_FLAG_NUMERICAL, which keeps (mu, Sigma) and the optimiser's moments; every iteration is one
+# agp_svgp_nvi_step (update_parameters! above), objective(model, state, y) the quadrature ELBO (agp_svgp_elbo).  Three definitions of
+# the reference are restated in their intended form on the device (agp_hip.h, "NUMERICAL INFERENCE"): the CPU backend keeps its own.
+const HipQVGP{T} = AGP.VGP{T,<:Any,<:AGP.QuadratureVI}
+twin(model::HipQVGP) = get!(() -> HipModel(model), TWINS, model)
+# SVGP{T,L,<:QuadratureVI} (QuadratureVI and QuadratureSVI): train!(model, X, y, iterations) is the sparse models' own method
+# (HipSVGP above takes every SVGP); its steps go to agp_svgp_nvi_step with the minibatch indices and rho = N / B
+# (update_parameters!), the handle is created with AGP_FLAG_NUMERICAL alone, the posterior comes back as (mu, Sigma).
+const HipQSVGP{T} = SVGP{T,<:Any,<:AGP.QuadratureVI}
+nvi_info(model::HipQSVGP) = nvi_info_of(TWINS[model])
+twin(model::HipQSVGP) = get!(() -> HipModel(model), TWINS, model)
+function train!(model::HipQSVGP, X::AbstractArray, y::AbstractArray, iterations::Int=100; backend::Symbol=BACKEND[], kwargs...)
+    backend === :cpu &&
+        return invoke(train!, Tuple{AGP.AbstractGPModel,AbstractArray,AbstractArray,Int}, model, X, y, iterations; kwargs...)
+    _, state = train!(twin(model), X, y, iterations; kwargs...)
+    return model, state
+end
+for f in (:predict_f, :predict_y, :proba_y)
+    @eval function $f(model::HipQSVGP, X_test::AbstractMatrix, state=nothing; backend::Symbol=BACKEND[], kw...)
+        (backend === :cpu || !has_twin(model)) &&
+            return invoke($f, Tuple{AGP.AbstractGPModel,AbstractMatrix,Any}, model, X_test, state; kw...)
+        return $f(TWINS[model], X_test; kw...)
+    end
+end
+objective(model::HipQSVGP, state::HipModel, y=nothing) = objective(state)
+# x_j = sqrt(2) t_j, w_j = omega_j / sqrt(pi) (quadratureVI.jl:36-40: the inference object holds them ready-made) and the optimiser
+function nvi_configure!(hm::HipModel)
+    inf = AGP.inference(hm.model)
+    o = inf.vi_opt[1].optimiser
+    kind, p1, p2, ϵ = o isa Optimisers.ADAM ? (0, Float64(o.beta[1]), Float64(o.beta[2]), 1e-8) :
+                      o isa Optimisers.Descent ? (1, 0.0, 0.0, 0.0) :
+                      o isa Optimisers.Momentum ? (2, Float64(o.rho), 0.0, 0.0) :
+                      error("QuadratureVI optimiser $(typeof(o)) is not available on the device (ADAM, Descent, Momentum are)")
+    x, w = Vector{Float64}(inf.nodes), Vector{Float64}(inf.weights)
+    check(hm.ctx, ccall((:agp_svgp_nvi_configure, libagp), Int32,
+                        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Float64, Float64, Float64),
+                        hm.h, length(x), x, w, AGP.isnatural(inf) ? 1 : 0, kind, Float64(o.eta), p1, p2, ϵ))
+    return hm
+end
+# (mu, Sigma) of the device -> the reference object; the natural parameters follow from them (posterior.jl)
+function pull_nvi_posterior!(hm::HipModel{T}) where {T}
+    gp = latents(hm.model)[1]
+    m = AGP.dim(gp)
+    μ = ROCVector{T}(undef, m); Σ = ROCMatrix{T}(undef, m, m)
+    check(hm.ctx, ccall((:agp_svgp_get_state, libagp), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                        hm.h, 0, pointer(μ), pointer(Σ), C_NULL, C_NULL))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    gp.post.μ .= Array(μ)
+    gp.post.Σ.data .= Array(Σ)
+    return hm
+end
+# (alpha of the last step, halvings, rejected updates) of the backtracking since the handle was created
+nvi_info(model::HipQVGP) = nvi_info_of(TWINS[model])
+function nvi_info_of(hm::HipModel)
+    a = Ref{Float64}(); hv = Ref{Int64}(); rj = Ref{Int64}()
+    check(hm.ctx, ccall((:agp_svgp_nvi_info, libagp), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}, Ref{Int64}, Ref{Int64}), hm.h, 0, a, hv, rj))
+    return a[], hv[], rj[]
+end
+function train!(model::HipQVGP, iterations::Int; backend::Symbol=BACKEND[], kwargs...)
+    backend === :cpu && return invoke(train!, Tuple{AGP.AbstractGPModel,Int}, model, iterations; kwargs...)
+    X = reduce(hcat, AGP.input(model.data))'                     # N x D
+    _, state = train!(twin(model), X, AGP.output(model.data), iterations; kwargs...)
+    return model, state
+end
+for f in (:predict_f, :predict_y, :proba_y)
+    @eval function $f(model::HipQVGP, X_test::AbstractMatrix, state=nothing; backend::Symbol=BACKEND[], kw...)
+        (backend === :cpu || !has_twin(model)) &&
+            return invoke($f, Tuple{AGP.AbstractGPModel,AbstractMatrix,Any}, model, X_test, state; kw...)
+        return $f(TWINS[model], X_test; kw...)
+    end
+end
+objective(model::HipQVGP, state::HipModel, y=nothing) = objective(state)
 
 # MOVGP{T,L,<:AnalyticVI} (src/models/MOVGP.jl): the multi-output full model, train!(model, iterations) on its own data; the handle
 # is created with AGP_FLAG_FULL and the multi-output likelihood (is_full and is_mo both hold: the inputs of every latent are the
