@@ -24,6 +24,7 @@ from .likelihoods import (  # noqa: F401
     LaplaceLikelihood,
     LogisticLikelihood,
     LogisticSoftMaxLikelihood,
+    SoftMaxLikelihood,
     NegBinomialLikelihood,
     PoissonLikelihood,
     StudentTLikelihood,
@@ -39,6 +40,8 @@ from .svgp import (  # noqa: F401
     AnalyticSVI,
     AnalyticVI,
     RobbinsMonro,
+    MCIntegrationSVI,
+    MCIntegrationVI,
     NumericalSVI,
     NumericalVI,
     QuadratureSVI,
@@ -56,7 +59,7 @@ from .vgp import VGP, n_latent  # noqa: F401
 from .gp import GP, Analytic  # noqa: F401
 from .movgp import MOVGP  # noqa: F401
 from .mcgp import MCGP, GibbsSampling, sample, sample_local  # noqa: F401
-from .nvi import gauss_hermite_rule, quad_expectations  # noqa: F401
+from .nvi import gauss_hermite_rule, mc_expectations, mc_normals, quad_expectations  # noqa: F401
 from .capi import AGPError  # noqa: F401
 from .persistence import load_trained_model, save_trained_model  # noqa: F401
 from .inducingpoints import KmeansAlg, RandomSubset, inducingpoints  # noqa: F401

@@ -27,6 +27,7 @@ F64, F32 = 0, 1
 K_SQEXP, K_MATERN52, K_MATERN32, K_EXPONENTIAL = 0, 1, 2, 3
 LIK_GAUSSIAN, LIK_LOGISTIC, LIK_STUDENTT, LIK_LOGISTICSOFTMAX, LIK_MULTIOUTPUT = 0, 1, 2, 3, 4
 LIK_LAPLACE, LIK_BAYESIANSVM, LIK_POISSON, LIK_NEGBINOMIAL, LIK_HETEROSCEDASTIC = 5, 6, 7, 8, 9
+LIK_SOFTMAX = 10  # SoftMaxLikelihood: no augmentation, FLAG_MC handles only
 OPT_ADAM, OPT_DESCENT, OPT_MOMENTUM = 0, 1, 2  # agp_svgp_hyper_rule
 ELBO_CORRECTED, ELBO_REFERENCE = 0, 1
 FLAG_STALE_K = 1  # reference_compat_stale_K
@@ -34,6 +35,7 @@ FLAG_FULL = 2  # the full model VGP (kappa = I, m = N): agp_svgp_desc.flags, inc
 FLAG_EXACT = 4  # exact GP regression GP(X, y, kernel) with Analytic(), together with FLAG_FULL (gp.py)
 FLAG_SAMPLED = 8  # the Gibbs-sampled full model MCGP, together with FLAG_FULL (mcgp.py)
 FLAG_NUMERICAL = 16  # numerical inference QuadratureVI: with FLAG_FULL the full model VGP, alone the sparse model SVGP (nvi.py)
+FLAG_MC = 32  # Monte-Carlo integration MCIntegrationVI over K latents, together with FLAG_NUMERICAL (nvi.py)
 SHARD_LATENT, SHARD_BATCH = 0, 1
 COMM_ID_BYTES = 128
 # int32_t (*agp_allreduce_fn)(void* user, void* buf, int64_t count, int32_t dtype, void* hip_stream)
@@ -175,6 +177,9 @@ SYMBOLS = {
     "agp_svgp_nvi_info": (_I32, [_VP, _I32, _PDBL, _PI64, _PI64]),
     "agp_svgp_nvi_state": (_I32, [_VP, _I32, _I32, _VP, _VP, _PI64]),
     "agp_quad_expectations": (_I32, [_VP, C.POINTER(LikDesc), _VP, _VP, _VP, _I64, _PDBL, _PDBL, _I32, _VP, _VP, _VP]),
+    "agp_svgp_mcvi_configure": (_I32, [_VP, _I32, C.c_uint64, _I32, _I32, _DBL, _DBL, _DBL, _DBL]),
+    "agp_mc_normals": (_I32, [_VP, C.c_uint64, _I64, _I32, _I32, _I32, _VP]),
+    "agp_mc_expectations": (_I32, [_VP, C.POINTER(LikDesc), _VP, _VP, _VP, _I64, _I32, _I32, C.c_uint64, _I64, _I32, _VP, _VP, _VP]),
 }
 
 _lib = None

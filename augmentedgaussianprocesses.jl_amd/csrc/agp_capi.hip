@@ -1294,6 +1294,9 @@ struct SvgpBase {
   virtual agp_status nvi_configure(int, const double*, const double*, int, int, double, double, double, double) {
     return not_numerical("agp_svgp_nvi_configure");
   }
+  virtual agp_status mcvi_configure(int, uint64_t, int, int, double, double, double, double) {
+    return not_numerical("agp_svgp_mcvi_configure");
+  }
   virtual agp_status nvi_step(const void*, int64_t, const void*, const int64_t*, int64_t, double) {
     return not_numerical("agp_svgp_nvi_step");
   }
@@ -1732,7 +1735,7 @@ struct Svgp : SvgpBase {
     lp.kind = desc.lik.kind;
     lp.p0 = (T)desc.lik.p0;
     lp.p1 = (T)desc.lik.p1;
-    if (lp.kind < 0 || lp.kind > AGP_LIK_HETEROSCEDASTIC) {
+    if (lp.kind < 0 || (lp.kind > AGP_LIK_HETEROSCEDASTIC && !(lp.kind == AGP_LIK_SOFTMAX && (desc.flags & AGP_FLAG_MC)))) {
       ctx->err = "likelihood not implemented for AnalyticVI on this path";
       return AGP_ERR_UNSUPPORTED;
     }
@@ -1752,7 +1755,7 @@ struct Svgp : SvgpBase {
     }
     if (lp.kind == AGP_LIK_HETEROSCEDASTIC) {  // n_latent(::HeteroscedasticGaussianLikelihood) = 2  heteroscedastic.jl:47
       if (nl != 2 || desc.latent_offset != 0) return AGP_ERR_INVALID;
-    } else if (lp.kind != AGP_LIK_LOGISTICSOFTMAX && lp.kind != AGP_LIK_MULTIOUTPUT && nl != 1) {
+    } else if (lp.kind != AGP_LIK_LOGISTICSOFTMAX && lp.kind != AGP_LIK_SOFTMAX && lp.kind != AGP_LIK_MULTIOUTPUT && nl != 1) {
       return AGP_ERR_INVALID;
     }
     if (desc.stochastic && !(desc.rm_kappa > 0.5 && desc.rm_kappa <= 1.0 && desc.rm_tau > 0)) {
@@ -4910,6 +4913,8 @@ struct Svgp : SvgpBase {
       hipLaunchKernelGGL((k_proba_gh<T>), grid1(nt), dim3(256), 0, st(), nt, (const T*)pmu, (const T*)pvar, nn,
                          (const double*)gh_dev, (const double*)(gh_dev + nn), link, desc.lik.p0,
                          lp.kind == AGP_LIK_POISSON ? (const T*)lam_dev : (const T*)nullptr, (T*)o0, (T*)o1);
+    } else if (lp.kind == AGP_LIK_SOFTMAX) {
+      hipLaunchKernelGGL((k_proba_softmax<T>), grid1(nt), dim3(256), 0, st(), nt, nl, nt, (const T*)pmu, (T*)o0);
     } else {
       hipLaunchKernelGGL((k_proba_lsm<T>), grid1(nt), dim3(256), 0, st(), nt, nl, nt, (const T*)pmu, (T*)o0);
     }
@@ -5583,30 +5588,70 @@ static const char* nvi_supported() {
   return "quadrature inference on the device runs for the Logistic, StudentT and Laplace likelihoods, Float64, one latent, on the "
          "full model (AGP_FLAG_FULL | AGP_FLAG_NUMERICAL) and the sparse model (AGP_FLAG_NUMERICAL)";
 }
+// Monte-Carlo inference (AGP_FLAG_MC on top of AGP_FLAG_NUMERICAL: MCIntegrationVI / MCIntegrationSVI, src/inference/MCVI.jl)
+static bool mc_lik_ok(int kind) { return kind == AGP_LIK_SOFTMAX || kind == AGP_LIK_LOGISTICSOFTMAX; }
+static const char* mc_supported() {
+  return "Monte-Carlo inference on the device runs for the SoftMax and LogisticSoftMax likelihoods, Float64, n_latent = n_class = K "
+         "with 2 <= K <= 64, on the full model (AGP_FLAG_FULL | AGP_FLAG_NUMERICAL | AGP_FLAG_MC) and the sparse model "
+         "(AGP_FLAG_NUMERICAL | AGP_FLAG_MC)";
+}
+// the table eps[nMC][K] of (seed, t, stream) (agp_rand.h)
+static agp_status mc_fill_normals(agp_ctx* ctx, hipStream_t s, uint64_t seed, int64_t t, int stream, int nMC, int K, double* out) {
+  const int64_t n = (int64_t)nMC * K;
+  hipLaunchKernelGGL(k_mc_normals, grid1(n), dim3(256), 0, s, n, seed, (uint32_t)t, (uint32_t)stream, out);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
 
 struct Nvgp : Vgp {
   bool configured = false, natural = true;
   int nn = 0;
   NviRule rule{};
   double* quad_dev = nullptr;  // [nodes | weights]
-  int64_t nv_t = 0;            // steps taken: ADAM's t of both states
-  double alpha_last = 1.0;
-  int64_t halvings_total = 0, rejected_total = 0;
-  T *nv_K = nullptr, *nv_A = nullptr, *nv_D = nullptr, *nv_C = nullptr, *nv_F = nullptr, *nv_X = nullptr, *nv_Dg = nullptr,
-    *nv_dmu = nullptr;
-  double *mom_mu = nullptr, *mom_S = nullptr;  // [2][mp], [2][mp][mp]: Momentum's vel / ADAM's m, then ADAM's v
+  int64_t nv_t = 0;            // steps taken: ADAM's t of both states of every latent, and t of the Monte-Carlo streams
+  // what every latent keeps of its own: K + jitt I unfactored, the accepted factor of Sigma (F, diagonal tiles Dg, inverse X), the
+  // optimiser's moments, and the backtracking's record.  12 m x m matrices per latent with those of the base handle.
+  struct NvLat {
+    T *K = nullptr, *F = nullptr, *X = nullptr, *Dg = nullptr;
+    double *mom_mu = nullptr, *mom_S = nullptr;  // [2][mp], [2][mp][mp]: Momentum's vel / ADAM's m, then ADAM's v
+    double alpha_last = 1.0;
+    int64_t halvings_total = 0, rejected_total = 0;
+    bool factor_valid = false, K_valid = false;
+  };
+  std::vector<NvLat> nvl;
+  int cur = 0;  // the latent that update_from / factor_candidate / ensure_factor work on
+  T *nv_A = nullptr, *nv_D = nullptr, *nv_C = nullptr, *nv_dmu = nullptr;  // scratch, one latent at a time
   int32_t* nv_info = nullptr;
-  bool factor_valid = false, nvK_valid = false;
+  bool mc = false;  // AGP_FLAG_MC: the expectations by Monte-Carlo integration over K latents
+  int nMC = 0;
+  uint64_t mc_seed = 0;
+  double* mc_eps = nullptr;  // [nMC][K], refilled for every step and every ELBO evaluation
   ~Nvgp() override {
-    for (T* p : {nv_K, nv_A, nv_D, nv_C, nv_F, nv_X, nv_Dg, nv_dmu})
+    for (auto& q : nvl) {
+      for (T* p : {q.K, q.F, q.X, q.Dg})
+        if (p) dfree(p);
+      for (double* p : {q.mom_mu, q.mom_S})
+        if (p) dfree(p);
+    }
+    for (T* p : {nv_A, nv_D, nv_C, nv_dmu})
       if (p) dfree(p);
-    for (double* p : {mom_mu, mom_S, quad_dev})
+    for (double* p : {quad_dev, mc_eps})
       if (p) dfree(p);
     if (nv_info) dfree(nv_info);
   }
-  agp_status check_desc() override {
-    AGPCHK(Svgp<T>::check_desc());
-    AGPCHK(check_full());
+  // AGP_FLAG_MC: judged on the descriptor itself, before the checks of the analytic handle
+  agp_status mc_check_desc() {
+    mc = (desc.flags & AGP_FLAG_MC) != 0;
+    if (!mc) return AGP_OK;
+    if (!mc_lik_ok(desc.lik.kind) || desc.n_latent < 2 || desc.n_latent > MC_KMAX || desc.lik.n_class != desc.n_latent ||
+        desc.latent_offset != 0) {
+      ctx->err = std::string("AGP_FLAG_MC: ") + mc_supported();
+      return AGP_ERR_UNSUPPORTED;
+    }
+    return AGP_OK;
+  }
+  agp_status lik_check() {
+    if (mc) return AGP_OK;
     if (lp.kind == AGP_LIK_GAUSSIAN) {  // test/likelihood/gaussian.jl:38,59
       ctx->err = "The GaussianLikelihood is not compatible with QuadratureVI: use AnalyticVI (the expectations are closed-form)";
       return AGP_ERR_UNSUPPORTED;
@@ -5617,25 +5662,38 @@ struct Nvgp : Vgp {
     }
     return AGP_OK;
   }
+  agp_status check_desc() override {
+    AGPCHK(mc_check_desc());
+    AGPCHK(Svgp<T>::check_desc());
+    AGPCHK(check_full());
+    return lik_check();
+  }
   agp_status init() override {
     AGPCHK(Vgp::init());
     const int64_t mm = mp * mp;
-    for (T** p : {&nv_K, &nv_A, &nv_D, &nv_C, &nv_F, &nv_X}) AGPCHK(dmalloc(ctx, p, mm));
-    AGPCHK(dmalloc(ctx, &nv_Dg, mp * TILE));
+    nvl.resize(nl);
+    for (auto& q : nvl) {
+      for (T** p : {&q.K, &q.F, &q.X}) AGPCHK(dmalloc(ctx, p, mm));
+      AGPCHK(dmalloc(ctx, &q.Dg, mp * TILE));
+      AGPCHK(dmalloc(ctx, &q.mom_mu, 2 * mp));
+      AGPCHK(dmalloc(ctx, &q.mom_S, 2 * mm));
+    }
+    for (T** p : {&nv_A, &nv_D, &nv_C}) AGPCHK(dmalloc(ctx, p, mm));
     AGPCHK(dmalloc(ctx, &nv_dmu, mp));
-    AGPCHK(dmalloc(ctx, &mom_mu, 2 * mp));
-    AGPCHK(dmalloc(ctx, &mom_S, 2 * mm));
     AGPCHK(dmalloc(ctx, &nv_info, 1));
-    Latent& g = lat[0];
-    HIPCHK(ctx, hipMemsetAsync(g.mu, 0, sizeof(T) * mp, st()));  // VarPosterior{T}(dim): mu = 0, Sigma = I (posterior.jl:29-37)
-    hipLaunchKernelGGL((k_set_identity<T>), grid2(mp, mp), blk2, 0, st(), g.Sigma, mp, mp, T(1));
-    LAUNCHCHK(ctx);
-    g.post_valid = true;
+    for (auto& g : lat) {
+      HIPCHK(ctx, hipMemsetAsync(g.mu, 0, sizeof(T) * mp, st()));  // VarPosterior{T}(dim): mu = 0, Sigma = I (posterior.jl:29-37)
+      hipLaunchKernelGGL((k_set_identity<T>), grid2(mp, mp), blk2, 0, st(), g.Sigma, mp, mp, T(1));
+      LAUNCHCHK(ctx);
+      g.post_valid = true;
+    }
     return zero_moments();
   }
   agp_status zero_moments() {
-    HIPCHK(ctx, hipMemsetAsync(mom_mu, 0, sizeof(double) * 2 * mp, st()));
-    HIPCHK(ctx, hipMemsetAsync(mom_S, 0, sizeof(double) * 2 * mp * mp, st()));
+    for (auto& q : nvl) {
+      HIPCHK(ctx, hipMemsetAsync(q.mom_mu, 0, sizeof(double) * 2 * mp, st()));
+      HIPCHK(ctx, hipMemsetAsync(q.mom_S, 0, sizeof(double) * 2 * mp * mp, st()));
+    }
     nv_t = 0;
     return AGP_OK;
   }
@@ -5656,18 +5714,40 @@ struct Nvgp : Vgp {
   }
   agp_status hyper_rule(int, double, int, double) override { return numerical_refused("agp_svgp_hyper_rule"); }
 
+  // the optimiser's part of agp_svgp_nvi_configure and agp_svgp_mcvi_configure
+  agp_status check_rule(const char* what, int opt_kind, double eta, double p1, double p2, double eps) {
+    if ((opt_kind == AGP_OPT_MOMENTUM && !(p1 >= 0 && p1 < 1)) ||
+        (opt_kind == AGP_OPT_ADAM && !(p1 >= 0 && p1 < 1 && p2 >= 0 && p2 < 1 && eps >= 0))) {
+      ctx->err = std::string(what) + ": Momentum takes 0 <= rho < 1 (p1), ADAM 0 <= beta1, beta2 < 1 (p1, p2) and eps >= 0";
+      return AGP_ERR_INVALID;
+    }
+    return AGP_OK;
+  }
+  void install_rule(int nat, int opt_kind, double eta, double p1, double p2, double eps) {
+    if (natural != (nat != 0))
+      for (auto& q : nvl) q.factor_valid = false;  // classical mode keeps the inverse factor as well
+    natural = nat != 0;
+    rule.kind = opt_kind;
+    rule.eta = eta;
+    rule.p1 = p1;
+    rule.p2 = p2;
+    rule.eps = eps;
+    rule.c1 = rule.c2 = 1.0;
+    configured = true;
+  }
   agp_status nvi_configure(int n, const double* nodes, const double* weights, int nat, int opt_kind, double eta, double p1,
                            double p2, double eps) override {
+    if (mc) {
+      ctx->err = "agp_svgp_nvi_configure: the handle runs Monte-Carlo integration (AGP_FLAG_MC); configure it with "
+                 "agp_svgp_mcvi_configure";
+      return AGP_ERR_UNSUPPORTED;
+    }
     if (n < 1 || n > 4096 || !nodes || !weights || !(eta > 0) ||
         (opt_kind != AGP_OPT_ADAM && opt_kind != AGP_OPT_DESCENT && opt_kind != AGP_OPT_MOMENTUM)) {
       ctx->err = "agp_svgp_nvi_configure: 1 <= n <= 4096 nodes and weights, eta > 0, opt_kind one of AGP_OPT_ADAM / DESCENT / MOMENTUM";
       return AGP_ERR_INVALID;
     }
-    if ((opt_kind == AGP_OPT_MOMENTUM && !(p1 >= 0 && p1 < 1)) ||
-        (opt_kind == AGP_OPT_ADAM && !(p1 >= 0 && p1 < 1 && p2 >= 0 && p2 < 1 && eps >= 0))) {
-      ctx->err = "agp_svgp_nvi_configure: Momentum takes 0 <= rho < 1 (p1), ADAM 0 <= beta1, beta2 < 1 (p1, p2) and eps >= 0";
-      return AGP_ERR_INVALID;
-    }
+    AGPCHK(check_rule("agp_svgp_nvi_configure", opt_kind, eta, p1, p2, eps));
     if (n != nn) {
       if (quad_dev) dfree(quad_dev);
       quad_dev = nullptr;
@@ -5678,48 +5758,69 @@ struct Nvgp : Vgp {
     HIPCHK(ctx, hipMemcpyAsync(quad_dev, nodes, sizeof(double) * n, hipMemcpyHostToDevice, st()));
     HIPCHK(ctx, hipMemcpyAsync(quad_dev + n, weights, sizeof(double) * n, hipMemcpyHostToDevice, st()));
     HIPCHK(ctx, hipStreamSynchronize(st()));  // (the caller's arrays may go away)
-    if (natural != (nat != 0)) factor_valid = false;  // classical mode keeps the inverse factor as well
-    natural = nat != 0;
-    rule.kind = opt_kind;
-    rule.eta = eta;
-    rule.p1 = p1;
-    rule.p2 = p2;
-    rule.eps = eps;
-    rule.c1 = rule.c2 = 1.0;
-    configured = true;
+    install_rule(nat, opt_kind, eta, p1, p2, eps);
+    return AGP_OK;
+  }
+  agp_status mcvi_configure(int n, uint64_t seed, int nat, int opt_kind, double eta, double p1, double p2, double eps) override {
+    if (!mc) {
+      ctx->err = "agp_svgp_mcvi_configure: the handle runs quadrature (no AGP_FLAG_MC); configure it with agp_svgp_nvi_configure";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    if (n < 1 || n > 65536 || !(eta > 0) ||
+        (opt_kind != AGP_OPT_ADAM && opt_kind != AGP_OPT_DESCENT && opt_kind != AGP_OPT_MOMENTUM)) {
+      ctx->err = "agp_svgp_mcvi_configure: 1 <= nMC <= 65536, eta > 0, opt_kind one of AGP_OPT_ADAM / DESCENT / MOMENTUM";
+      return AGP_ERR_INVALID;
+    }
+    AGPCHK(check_rule("agp_svgp_mcvi_configure", opt_kind, eta, p1, p2, eps));
+    if (n != nMC) {
+      if (mc_eps) dfree(mc_eps);
+      mc_eps = nullptr;
+      nMC = 0;
+      AGPCHK(dmalloc(ctx, &mc_eps, (int64_t)n * nl));
+      nMC = n;
+    }
+    mc_seed = seed;
+    install_rule(nat, opt_kind, eta, p1, p2, eps);
     return AGP_OK;
   }
   agp_status need_config(const char* what) {
     if (configured) return AGP_OK;
-    ctx->err = std::string(what) + ": install the quadrature rule and the optimiser first (agp_svgp_nvi_configure)";
+    ctx->err = std::string(what) + (mc ? ": install nMC, the seed and the optimiser first (agp_svgp_mcvi_configure)"
+                                       : ": install the quadrature rule and the optimiser first (agp_svgp_nvi_configure)");
     return AGP_ERR_INVALID;
   }
+  agp_status check_latent(int l) { return l >= 0 && l < nl ? AGP_OK : AGP_ERR_INVALID; }
   // K + jitt I unfactored (the natural gradient of eta1 multiplies by it) next to the factor, inverse and log det of refresh_K
   agp_status ensure_K() {
-    Latent& g = lat[0];
-    const bool stale = g.K_stale;
+    std::vector<char> stale(nl);
+    for (int l = 0; l < nl; ++l) stale[l] = lat[l].K_stale ? 1 : 0;
     AGPCHK(refresh_K());
-    if (stale || !nvK_valid) {
-      AGPCHK(ensure_zsc(g));
-      (void)launch_kernelmatrix<T>(ctx, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m, (const T*)g.Z, D, m, D,
-                                   (const T*)g.scales, g.k.kind, kvar(g), nv_K, mp, mp, mp, 1, (T)jitter, (const T*)nullptr, (T*)nullptr,
-                                   (int64_t)0, 0, (const T*)g.Zsc, (const T*)g.zn);
-      LAUNCHCHK(ctx);
-      nvK_valid = true;
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      NvLat& q = nvl[l];
+      if (stale[l] || !q.K_valid) {
+        AGPCHK(ensure_zsc(g));
+        (void)launch_kernelmatrix<T>(ctx, st(), (const T*)g.Z, D, (const int64_t*)nullptr, m, (const T*)g.Z, D, m, D,
+                                     (const T*)g.scales, g.k.kind, kvar(g), q.K, mp, mp, mp, 1, (T)jitter, (const T*)nullptr, (T*)nullptr,
+                                     (int64_t)0, 0, (const T*)g.Zsc, (const T*)g.zn);
+        LAUNCHCHK(ctx);
+        q.K_valid = true;
+      }
     }
     return AGP_OK;
   }
-  // factor Sigma + alpha D (nv_F, diagonal tiles nv_Dg; with its inverse nv_X in classical mode); *info: 0, or the leading minor
-  // that is not positive.  Sigma + alpha D itself is left in nv_C (keep_c).
+  // factor Sigma + alpha D of the current latent (F, diagonal tiles Dg; with its inverse X in classical mode); *info: 0, or the
+  // leading minor that is not positive.  Sigma + alpha D itself is left in nv_C (keep_c).
   agp_status factor_candidate(const T* Dm, T alpha, bool keep_c, int32_t* info) {
-    Latent& g = lat[0];
+    Latent& g = lat[cur];
+    NvLat& q = nvl[cur];
     const int do_x = natural ? 0 : 1;
     for (int pass = 0; pass < 2; ++pass) {
       HIPCHK(ctx, hipMemsetAsync(nv_info, 0, sizeof(int32_t), st()));
       hipLaunchKernelGGL((k_nvi_candidate<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, (const T*)g.Sigma, Dm, alpha,
-                         keep_c ? nv_C : (T*)nullptr, nv_F);
+                         keep_c ? nv_C : (T*)nullptr, q.F);
       LAUNCHCHK(ctx);
-      AGPCHK(potrf_fused<T>(ctx, nv_F, mp, mp, nv_X, mp, nv_Dg, (T*)nullptr, 0, 0, do_x, nv_info, m));
+      AGPCHK(potrf_fused<T>(ctx, q.F, mp, mp, q.X, mp, q.Dg, (T*)nullptr, 0, 0, do_x, nv_info, m));
       HIPCHK(ctx, hipMemcpyAsync(info, nv_info, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
       HIPCHK(ctx, hipStreamSynchronize(st()));
       if (*info != -1 || pass == 1) break;
@@ -5734,14 +5835,20 @@ struct Nvgp : Vgp {
     return AGP_OK;
   }
   agp_status ensure_factor() {
-    if (factor_valid) return AGP_OK;
+    NvLat& q = nvl[cur];
+    if (q.factor_valid) return AGP_OK;
     int32_t info = 0;
-    AGPCHK(factor_candidate((const T*)lat[0].Sigma, T(0), false, &info));
+    AGPCHK(factor_candidate((const T*)lat[cur].Sigma, T(0), false, &info));
     if (info != 0) {
       ctx->err = "PosDefException: Sigma is not positive definite; leading minor " + std::to_string(info);
       return AGP_ERR_NOT_POSDEF;
     }
-    factor_valid = true;
+    q.factor_valid = true;
+    return AGP_OK;
+  }
+  agp_status ensure_factors() {
+    for (cur = 0; cur < nl; ++cur) AGPCHK(ensure_factor());
+    cur = 0;
     return AGP_OK;
   }
   agp_status check_whole_set(const void* y, const int64_t* idx, int64_t B) {
@@ -5759,8 +5866,27 @@ struct Nvgp : Vgp {
     hipLaunchKernelGGL((k_quad_local<T>), grid1(B), dim3(256), 0, st(), B, lp, nvi_lconst(lp.kind, desc.lik.p0), y, idx, mf, vf,
                        (const double*)quad_dev, (const double*)(quad_dev + nn), nn, ell, gq, hq);
   }
+  // ell [B], g and h [nl][Bp] of the batch from its moments mf, vf [nl][Bp]: the quadrature for the single latent, or the
+  // Monte-Carlo table of stream 2 at step nv_t + 1 (a step) / stream 3 at nv_t (an ELBO evaluation) over the K latents
+  agp_status local_expectations(int64_t B, const void* y, const int64_t* idx, const T* mf, const T* vf, T* ell, T* gq, T* hq,
+                                bool for_elbo) {
+    if (!mc) {
+      quad_local(B, (const T*)y, idx, mf, vf, ell, gq, hq);
+      return AGP_OK;
+    }
+    const int64_t t = for_elbo ? nv_t : nv_t + 1;
+    if (t > (int64_t)0xFFFFFFFFll) {
+      ctx->err = "Monte-Carlo inference: the step counter must stay below 2^32";
+      return AGP_ERR_INVALID;
+    }
+    AGPCHK(mc_fill_normals(ctx, st(), mc_seed, t, for_elbo ? RNG_STREAM_MC_ELBO : RNG_STREAM_MC_GRAD, nMC, nl, mc_eps));
+    hipLaunchKernelGGL(k_mc_local, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st(), B, (int)lp.kind, nl, nMC, (const int32_t*)y, idx,
+                       (const double*)mf, (const double*)vf, Bp, (const double*)mc_eps, (double*)ell, (double*)gq, (double*)hq, Bp,
+                       flags_dev);
+    return AGP_OK;
+  }
 
-  // variational_updates + global_update! (numericalVI.jl:101-179) for the single latent; rho = 1 on the full model
+  // variational_updates + global_update! (numericalVI.jl:101-179) for every latent; rho = 1 on the full model
   agp_status nvi_step(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, double rho) override {
     AGPCHK(need_config("agp_svgp_nvi_step"));
     AGPCHK(check_whole_set(y, idx, B));
@@ -5768,28 +5894,34 @@ struct Nvgp : Vgp {
       ctx->err = "agp_svgp_nvi_step: the full model takes rho = 1";
       return AGP_ERR_INVALID;
     }
-    Latent& g = lat[0];
     AGPCHK(ensure_K());
-    if (!natural) AGPCHK(ensure_factor());
-    hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)g.Sigma, (const T*)g.mu, muf, varf);
-    quad_local(m, (const T*)y, nullptr, muf, varf, Kt, rbuf, wbuf);
+    if (!natural) AGPCHK(ensure_factors());
+    for (int l = 0; l < nl; ++l)
+      hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)lat[l].Sigma, (const T*)lat[l].mu, muf + l * Bp,
+                         varf + l * Bp);
+    AGPCHK(local_expectations(m, y, nullptr, muf, varf, Kt, rbuf, wbuf, false));
     LAUNCHCHK(ctx);
-    AGPCHK(update_from(rbuf, nullptr, wbuf));
+    for (int l = 0; l < nl; ++l) {
+      cur = l;
+      AGPCHK(update_from(rbuf + l * Bp, nullptr, wbuf + l * Bp, l == nl - 1));
+    }
+    cur = 0;
     record_batch(y, 1.0);
     return AGP_OK;
   }
-  // the optimiser step on mu and Sigma and the backtracking, from u = rho kappa' g (the full model: g), the data term P2 of the
-  // gradient of eta2 (sparse model: rho W Diagonal(h) W' or rho kappa' Diagonal(h) kappa, m x m; the full model: NULL) and h (the
-  // full model's diagonal data term; NULL with P2)
-  agp_status update_from(const T* u, const T* P2, const T* hd) {
-    Latent& g = lat[0];
-    const int64_t t1 = nv_t + 1;  // (the counter moves once both rules have been applied: it never runs ahead of the moments)
+  // the optimiser step on mu and Sigma of the current latent and its backtracking, from u = rho kappa' g (the full model: g), the
+  // data term P2 of the gradient of eta2 (sparse model: rho W Diagonal(h) W' or rho kappa' Diagonal(h) kappa, m x m; the full model:
+  // NULL) and h (the full model's diagonal data term; NULL with P2).  last: the step's last latent -- the shared counter moves
+  agp_status update_from(const T* u, const T* P2, const T* hd, bool last = true) {
+    Latent& g = lat[cur];
+    NvLat& q = nvl[cur];
+    const int64_t t1 = nv_t + 1;  // (the counter moves once every rule has been applied: it never runs ahead of the moments)
     if (rule.kind == AGP_OPT_ADAM) {
       rule.c1 = 1.0 - std::pow(rule.p1, (double)t1);
       rule.c2 = 1.0 - std::pow(rule.p2, (double)t1);
     }
     hipLaunchKernelGGL((k_nvi_grad_mu<T>), grid1(m * 64), dim3(256), 0, st(), m, mp, natural ? 1 : 0,
-                       (const T*)(natural ? nv_K : g.Kinv), u, (const T*)g.mu, (const T*)g.mu0, rule, mom_mu, mom_mu + mp, nv_dmu);
+                       (const T*)(natural ? q.K : g.Kinv), u, (const T*)g.mu, (const T*)g.mu0, rule, q.mom_mu, q.mom_mu + mp, nv_dmu);
     LAUNCHCHK(ctx);
     const int64_t mm = mp * mp;
     if (natural) {
@@ -5798,20 +5930,20 @@ struct Nvgp : Vgp {
       LAUNCHCHK(ctx);
       AGPCHK((gemm_nt<T, EPI_STORE>(ctx, nv_A, mp, g.Sigma, mp, mp, mp, mp, 0, nv_C, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
       hipLaunchKernelGGL((k_nvi_grad_sigma<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, 1, (const T*)nv_C, (const T*)nullptr, P2,
-                         (const T*)g.Sigma, hd, rule, mom_S, mom_S + mm, nv_D);
+                         (const T*)g.Sigma, hd, rule, q.mom_S, q.mom_S + mm, nv_D);
     } else {
-      AGPCHK(xtx_padded<T>(ctx, nv_X, mp, mp, nv_A, mp));  // Sigma^-1 from the inverse factor of the accepted Sigma
+      AGPCHK(xtx_padded<T>(ctx, q.X, mp, mp, nv_A, mp));  // Sigma^-1 from the inverse factor of the accepted Sigma
       hipLaunchKernelGGL((k_nvi_grad_sigma<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, 0, (const T*)g.Kinv, (const T*)nv_A, P2,
-                         (const T*)g.Sigma, hd, rule, mom_S, mom_S + mm, nv_D);
+                         (const T*)g.Sigma, hd, rule, q.mom_S, q.mom_S + mm, nv_D);
     }
     hipLaunchKernelGGL((k_nvi_add<T>), grid1(m), dim3(256), 0, st(), m, g.mu, (const T*)nv_dmu);
     LAUNCHCHK(ctx);
-    nv_t = t1;
+    if (last) nv_t = t1;
     // alpha = 1; while !isposdef(Sigma + alpha Symmetric(dSigma)) && alpha > 1e-8: alpha /= 2; alpha > 1e-8 ? accept : Sigma unchanged
     // (the attempt at the first alpha <= 1e-8 cannot change the outcome and is not made)
     double a = 1.0;
     bool accepted = false;
-    factor_valid = false;
+    q.factor_valid = false;
     while (a > 1e-8) {
       int32_t info = 0;
       AGPCHK(factor_candidate((const T*)nv_D, (T)a, true, &info));
@@ -5820,40 +5952,42 @@ struct Nvgp : Vgp {
         break;
       }
       a *= 0.5;
-      halvings_total += 1;
+      q.halvings_total += 1;
     }
-    alpha_last = a;
+    q.alpha_last = a;
     if (accepted) {
       std::swap(g.Sigma, nv_C);  // the accepted candidate becomes Sigma (both are handle-owned mp x mp buffers: no copy)
-      factor_valid = true;
+      q.factor_valid = true;
     } else {
-      rejected_total += 1;  // (mu has moved already, numericalVI.jl:166)
+      q.rejected_total += 1;  // (mu has moved already, numericalVI.jl:166)
     }
     g.pred_valid = g.predvar_valid = false;
-    if (tw2_kis_of == 0) tw2_kis_of = -1;
-    n_steps += 1;
+    if (tw2_kis_of == cur) tw2_kis_of = -1;
+    if (last) n_steps += 1;
     return AGP_OK;
   }
   agp_status nvi_info(int l, double* a_last, int64_t* halvings, int64_t* rejected) override {
-    if (l != 0) return AGP_ERR_INVALID;
-    if (a_last) *a_last = alpha_last;
-    if (halvings) *halvings = halvings_total;
-    if (rejected) *rejected = rejected_total;
+    AGPCHK(check_latent(l));
+    if (a_last) *a_last = nvl[l].alpha_last;
+    if (halvings) *halvings = nvl[l].halvings_total;
+    if (rejected) *rejected = nvl[l].rejected_total;
     return AGP_OK;
   }
-  // the optimiser moments [2][m] and [2][m][m] (device, contiguous) and the step counter: what a saved model continues from
+  // the optimiser moments [2][m] and [2][m][m] of one latent (device, contiguous) and the shared step counter: what a saved model
+  // continues from
   agp_status nvi_state(int l, int set, void* mmu, void* msig, int64_t* t) override {
-    if (l != 0 || !mmu || !msig || !t) return AGP_ERR_INVALID;
+    if (check_latent(l) != AGP_OK || !mmu || !msig || !t) return AGP_ERR_INVALID;
+    NvLat& q = nvl[l];
     const int64_t mm = mp * mp;
     for (int s = 0; s < 2; ++s) {
       if (set) {
         if (*t < 0) return AGP_ERR_INVALID;
-        HIPCHK(ctx, hipMemcpyAsync(mom_mu + s * mp, (const double*)mmu + s * m, sizeof(double) * m, hipMemcpyDeviceToDevice, st()));
-        HIPCHK(ctx, hipMemcpy2DAsync(mom_S + s * mm, sizeof(double) * mp, (const double*)msig + s * m * m, sizeof(double) * m,
+        HIPCHK(ctx, hipMemcpyAsync(q.mom_mu + s * mp, (const double*)mmu + s * m, sizeof(double) * m, hipMemcpyDeviceToDevice, st()));
+        HIPCHK(ctx, hipMemcpy2DAsync(q.mom_S + s * mm, sizeof(double) * mp, (const double*)msig + s * m * m, sizeof(double) * m,
                                      sizeof(double) * m, m, hipMemcpyDeviceToDevice, st()));
       } else {
-        HIPCHK(ctx, hipMemcpyAsync((double*)mmu + s * m, mom_mu + s * mp, sizeof(double) * m, hipMemcpyDeviceToDevice, st()));
-        HIPCHK(ctx, hipMemcpy2DAsync((double*)msig + s * m * m, sizeof(double) * m, mom_S + s * mm, sizeof(double) * mp,
+        HIPCHK(ctx, hipMemcpyAsync((double*)mmu + s * m, q.mom_mu + s * mp, sizeof(double) * m, hipMemcpyDeviceToDevice, st()));
+        HIPCHK(ctx, hipMemcpy2DAsync((double*)msig + s * m * m, sizeof(double) * m, q.mom_S + s * mm, sizeof(double) * mp,
                                      sizeof(double) * m, m, hipMemcpyDeviceToDevice, st()));
       }
     }
@@ -5861,50 +5995,55 @@ struct Nvgp : Vgp {
     else *t = nv_t;
     return AGP_OK;
   }
-  // mean_f, var_f of the batch under the current posterior; the full model: mu and diag Sigma on the whole training set
+  // mean_f, var_f [nl][Bp] of the batch under the current posterior; the full model: mu and diag Sigma on the whole training set
   virtual agp_status batch_moments(const void*, int64_t, const void* y, const int64_t* idx, int64_t B, T* mf, T* vf) {
     AGPCHK(check_whole_set(y, idx, B));
-    Latent& g = lat[0];
-    hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)g.Sigma, (const T*)g.mu, mf, vf);
+    for (int l = 0; l < nl; ++l)
+      hipLaunchKernelGGL((k_vgp_diag<T>), grid1(m), dim3(256), 0, st(), m, mp, (const T*)lat[l].Sigma, (const T*)lat[l].mu, mf + l * Bp,
+                         vf + l * Bp);
     LAUNCHCHK(ctx);
     return AGP_OK;
   }
-  // ELBO = rho sum_i sum_j w_j l(y_i, f_ij) - GaussianKL at the current posterior (numericalVI.jl:193-206); there are no local
+  // ELBO = rho sum_i ell_i - sum over the latents of GaussianKL at the current posterior (numericalVI.jl:193-206); there are no local
   // variables, so fresh_local changes nothing
   agp_status elbo(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho, int, double* out) override {
     if (!out) return AGP_ERR_INVALID;
     AGPCHK(need_config("agp_svgp_elbo"));
-    Latent& g = lat[0];
     AGPCHK(ensure_K());
-    AGPCHK(ensure_factor());
+    AGPCHK(ensure_factors());
     AGPCHK(batch_moments(x, ldx, y, idx, B, emuf, evarf));
-    quad_local(B, (const T*)y, idx, emuf, evarf, theta, rbuf2, wbuf2);
+    AGPCHK(local_expectations(B, y, idx, emuf, evarf, theta, rbuf2, wbuf2, true));
     hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(1024), 0, st(), (const double*)theta, B, scal_dev);
-    hipLaunchKernelGGL((k_logdiag_sum<T>), dim3(1), dim3(1024), 0, st(), (const T*)nv_Dg, m, scal_dev + 2);
-    LAUNCHCHK(ctx);
-    AGPCHK(frob_dot((const T*)g.Kinv, (const T*)g.Sigma, mp, m, scal_dev + 3));
-    hipLaunchKernelGGL((k_axpby<T>), grid1(mp), dim3(256), 0, st(), mp, T(1), (const T*)g.mu, T(-1), (const T*)g.mu0, tmpv);
-    hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xk, mp, mp, (const T*)tmpv, pw0);
-    hipLaunchKernelGGL((k_sumsq<T>), dim3(1), dim3(1024), 0, st(), (const T*)pw0, mp, scal_dev + 4);
-    LAUNCHCHK(ctx);
-    double h[5];
-    HIPCHK(ctx, hipMemcpyAsync(h, scal_dev, sizeof(double) * 5, hipMemcpyDeviceToHost, st()));
-    HIPCHK(ctx, hipStreamSynchronize(st()));
-    AGPCHK(resolve_logdet(g));
-    e_data = h[0];
+    double kl = 0.0;
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      hipLaunchKernelGGL((k_logdiag_sum<T>), dim3(1), dim3(1024), 0, st(), (const T*)nvl[l].Dg, m, scal_dev + 2);
+      LAUNCHCHK(ctx);
+      AGPCHK(frob_dot((const T*)g.Kinv, (const T*)g.Sigma, mp, m, scal_dev + 3));
+      hipLaunchKernelGGL((k_axpby<T>), grid1(mp), dim3(256), 0, st(), mp, T(1), (const T*)g.mu, T(-1), (const T*)g.mu0, tmpv);
+      hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)g.Xk, mp, mp, (const T*)tmpv, pw0);
+      hipLaunchKernelGGL((k_sumsq<T>), dim3(1), dim3(1024), 0, st(), (const T*)pw0, mp, scal_dev + 4);
+      LAUNCHCHK(ctx);
+      double h[5];
+      HIPCHK(ctx, hipMemcpyAsync(h, scal_dev, sizeof(double) * 5, hipMemcpyDeviceToHost, st()));
+      HIPCHK(ctx, hipStreamSynchronize(st()));
+      AGPCHK(resolve_logdet(g));
+      e_data = h[0];
+      kl += 0.5 * (2.0 * g.half_logdetK - 2.0 * h[2] + h[3] + h[4] - (double)m);
+    }
     kl_aug = 0.0;
-    kl_gauss_last = 0.5 * (2.0 * g.half_logdetK - 2.0 * h[2] + h[3] + h[4] - (double)m);
+    kl_gauss_last = kl;
     *out = rho * e_data - kl_gauss_last;
     return AGP_OK;
   }
   // mu, Sigma of the posterior; there are no natural parameters on this handle
   agp_status get_state(int l, void* mu, void* sigma, void* eta1, void* eta2) override {
-    if (l != 0) return AGP_ERR_INVALID;
+    AGPCHK(check_latent(l));
     if (eta1 || eta2) {
       ctx->err = "numerical inference (AGP_FLAG_NUMERICAL): the state is (mu, Sigma) (eta1 / eta2 must be NULL)";
       return AGP_ERR_UNSUPPORTED;
     }
-    Latent& g = lat[0];
+    Latent& g = lat[l];
     if (mu) HIPCHK(ctx, hipMemcpyAsync(mu, g.mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
     if (sigma)
       HIPCHK(ctx, hipMemcpy2DAsync(sigma, sizeof(T) * m, g.Sigma, sizeof(T) * mp, sizeof(T) * m, m, hipMemcpyDeviceToDevice, st()));
@@ -5912,16 +6051,19 @@ struct Nvgp : Vgp {
   }
   // installs (mu, Sigma) (eta1 = mu, eta2 = Sigma: T[m], T[m][m]); Sigma must be positive definite
   agp_status set_state(int l, const void* mu, const void* sigma) override {
-    if (l != 0 || !mu || !sigma) return AGP_ERR_INVALID;
-    Latent& g = lat[0];
+    if (check_latent(l) != AGP_OK || !mu || !sigma) return AGP_ERR_INVALID;
+    Latent& g = lat[l];
     HIPCHK(ctx, hipMemsetAsync(g.mu, 0, sizeof(T) * mp, st()));
     HIPCHK(ctx, hipMemcpyAsync(g.mu, mu, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
     hipLaunchKernelGGL((k_copy2d<T>), grid2(mp, mp), blk2, 0, st(), (const T*)sigma, m, m, m, g.Sigma, mp, mp, mp, T(1), T(1));
     LAUNCHCHK(ctx);
     g.pred_valid = g.predvar_valid = false;
-    if (tw2_kis_of == 0) tw2_kis_of = -1;
-    factor_valid = false;
-    return ensure_factor();
+    if (tw2_kis_of == l) tw2_kis_of = -1;
+    nvl[l].factor_valid = false;
+    cur = l;
+    const agp_status s = ensure_factor();
+    cur = 0;
+    return s;
   }
   // init_state(model): new optimiser states (states.jl:50-84); the posterior belongs to the model and is kept
   agp_status init_state() override {
@@ -5931,78 +6073,89 @@ struct Nvgp : Vgp {
 };
 
 // ---- numerical inference on the sparse model (AGP_FLAG_NUMERICAL without AGP_FLAG_FULL: SVGP(kernel, likelihood, QuadratureVI() /
-// QuadratureSVI(B), Z)) --------------------------------------------------------------------------------------------------------------
-// Nvgp's state, optimiser, backtracking, ELBO tail and predictions on m inducing points; what differs is the batch side.  Per step:
-// K_nm (launch_kernelmatrix on x[idx]), kappa = K_nm K^-1 and kappa' = K^-1 K_mn (two gemm_nt; K^-1 is symmetric), Wt = Sigma kappa'
-// (m x B), K~, mean_f = kappa mu and var_f = diag(kappa Sigma kappa') + K~ (k_nvi_fstats), the quadrature on the batch, u = rho kappa' g
-// (k_nvi_kappat_g) and the data term of the gradient of eta2 as one product S Diagonal(rho h) S' with S = Wt (natural) or kappa'
-// (classical) (k_nvi_scale_cols + gemm_nt), then Nvgp::update_from.  The kernel matrices are recomputed every step: nothing is cached
-// between steps and there is no look-ahead.
+// QuadratureSVI(B), Z), and with AGP_FLAG_MC MCIntegrationVI() / MCIntegrationSVI(B)) -----------------------------------------------
+// Nvgp's state, optimiser, backtracking, ELBO tail and predictions on m inducing points; what differs is the batch side.  Per step and
+// latent: K_nm (launch_kernelmatrix on x[idx]), kappa = K_nm K^-1 and kappa' = K^-1 K_mn (two gemm_nt; K^-1 is symmetric), Wt = Sigma kappa'
+// (m x B), K~, mean_f = kappa mu and var_f = diag(kappa Sigma kappa') + K~ (k_nvi_fstats); the expectations on the batch (all latents
+// at once); then per latent u = rho kappa' g (k_nvi_kappat_g) and the data term of the gradient of eta2 as one product
+// S Diagonal(rho h) S' with S = Wt (natural) or kappa' (classical) (k_nvi_scale_cols + gemm_nt), then Nvgp::update_from.  kappa' and Wt
+// are kept per latent from the moments to the update; the kernel matrices are recomputed every step: nothing is cached between steps
+// and there is no look-ahead.
 struct Nsvgp : Nvgp {
-  T *ns_Knm = nullptr, *ns_kap = nullptr, *ns_kapt = nullptr, *ns_Wt = nullptr, *ns_S2 = nullptr, *ns_u = nullptr;
-  T* ns_P2 = nullptr;  // the data term of the gradient of eta2, m x m (a buffer of its own: nv_F holds the kept factor)
+  T *ns_Knm = nullptr, *ns_kap = nullptr, *ns_S2 = nullptr, *ns_u = nullptr;
+  std::vector<T*> ns_kapt, ns_Wt;  // per latent
+  T* ns_P2 = nullptr;  // the data term of the gradient of eta2, m x m (a buffer of its own: F holds the kept factor)
   ~Nsvgp() override {
-    for (T* p : {ns_Knm, ns_kap, ns_kapt, ns_Wt, ns_S2, ns_u, ns_P2})
+    for (T* p : {ns_Knm, ns_kap, ns_S2, ns_u, ns_P2})
+      if (p) dfree(p);
+    for (T* p : ns_kapt)
+      if (p) dfree(p);
+    for (T* p : ns_Wt)
       if (p) dfree(p);
   }
   agp_status check_desc() override {
+    AGPCHK(mc_check_desc());
     AGPCHK(Svgp<T>::check_desc());
     if (desc.latent_offset != 0) return AGP_ERR_INVALID;
-    if (lp.kind == AGP_LIK_GAUSSIAN) {  // test/likelihood/gaussian.jl:38,59
-      ctx->err = "The GaussianLikelihood is not compatible with QuadratureVI: use AnalyticVI (the expectations are closed-form)";
-      return AGP_ERR_UNSUPPORTED;
-    }
-    if (!nvi_lik_ok(lp.kind) || nl != 1) {
-      ctx->err = std::string("AGP_FLAG_NUMERICAL: ") + nvi_supported();
-      return AGP_ERR_UNSUPPORTED;
-    }
-    return AGP_OK;
+    return lik_check();
   }
   agp_status init() override {
     AGPCHK(Nvgp::init());
-    for (T** p : {&ns_Knm, &ns_kap, &ns_kapt, &ns_Wt, &ns_S2}) AGPCHK(dmalloc(ctx, p, Bp * mp));
+    for (T** p : {&ns_Knm, &ns_kap, &ns_S2}) AGPCHK(dmalloc(ctx, p, Bp * mp));
+    ns_kapt.assign(nl, nullptr);
+    ns_Wt.assign(nl, nullptr);
+    for (int l = 0; l < nl; ++l) {
+      AGPCHK(dmalloc(ctx, &ns_kapt[l], Bp * mp));
+      AGPCHK(dmalloc(ctx, &ns_Wt[l], Bp * mp));
+    }
     AGPCHK(dmalloc(ctx, &ns_u, mp));
     AGPCHK(dmalloc(ctx, &ns_P2, mp * mp));
     return AGP_OK;
   }
-  // K_nm, kappa, kappa', Wt of the batch and its mean_f / var_f
+  // K_nm, kappa, kappa', Wt of the batch and its mean_f / var_f, latent by latent
   agp_status batch_moments(const void* x, int64_t ldx, const void* y, const int64_t*idx, int64_t B, T* mf, T* vf) override {
     if (!x || !y || ldx < D) {
       ctx->err = "numerical inference on the sparse model: x and y must be given, ldx >= D";
       return AGP_ERR_INVALID;
     }
     AGPCHK(check_batch(B));
-    Latent& g = lat[0];
-    AGPCHK(params_to_host(g));
-    AGPCHK(ensure_zsc(g));
     const int64_t Bq = rup64(B);
-    (void)launch_kernelmatrix<T>(ctx, st(), (const T*)x, ldx, idx, B, (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind, kvar(g),
-                                 ns_Knm, mp, Bq, mp, 0, T(0), (const T*)nullptr, (T*)nullptr, (int64_t)0, 0, (const T*)g.Zsc,
-                                 (const T*)g.zn);
-    LAUNCHCHK(ctx);
-    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, ns_Knm, mp, g.Kinv, mp, Bq, mp, mp, 0, ns_kap, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, g.Kinv, mp, ns_Knm, mp, mp, Bq, mp, 0, ns_kapt, Bp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, g.Sigma, mp, ns_kap, mp, mp, Bq, mp, 0, ns_Wt, Bp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-    hipLaunchKernelGGL((k_nvi_fstats<T>), grid1(B * 64), dim3(256), 0, st(), B, m, mp, Bp, (const T*)ns_kap, (const T*)ns_Knm,
-                       (const T*)ns_Wt, (const T*)g.mu, (T)(g.k.variance + jitter), mf, vf);
-    LAUNCHCHK(ctx);
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      AGPCHK(params_to_host(g));
+      AGPCHK(ensure_zsc(g));
+      (void)launch_kernelmatrix<T>(ctx, st(), (const T*)x, ldx, idx, B, (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind, kvar(g),
+                                   ns_Knm, mp, Bq, mp, 0, T(0), (const T*)nullptr, (T*)nullptr, (int64_t)0, 0, (const T*)g.Zsc,
+                                   (const T*)g.zn);
+      LAUNCHCHK(ctx);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, ns_Knm, mp, g.Kinv, mp, Bq, mp, mp, 0, ns_kap, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, g.Kinv, mp, ns_Knm, mp, mp, Bq, mp, 0, ns_kapt[l], Bp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, g.Sigma, mp, ns_kap, mp, mp, Bq, mp, 0, ns_Wt[l], Bp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+      hipLaunchKernelGGL((k_nvi_fstats<T>), grid1(B * 64), dim3(256), 0, st(), B, m, mp, Bp, (const T*)ns_kap, (const T*)ns_Knm,
+                         (const T*)ns_Wt[l], (const T*)g.mu, (T)(g.k.variance + jitter), mf + l * Bp, vf + l * Bp);
+      LAUNCHCHK(ctx);
+    }
     return AGP_OK;
   }
   agp_status nvi_step(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho) override {
     AGPCHK(need_config("agp_svgp_nvi_step"));
     if (!(rho > 0)) return AGP_ERR_INVALID;
     AGPCHK(ensure_K());
-    if (!natural) AGPCHK(ensure_factor());
+    if (!natural) AGPCHK(ensure_factors());
     AGPCHK(batch_moments(x, ldx, y, idx, B, muf, varf));
-    quad_local(B, (const T*)y, idx, muf, varf, Kt, rbuf, wbuf);
+    AGPCHK(local_expectations(B, y, idx, muf, varf, Kt, rbuf, wbuf, false));
     const int64_t Bq = rup64(B);
-    hipLaunchKernelGGL((k_nvi_kappat_g<T>), grid1(mp * 64), dim3(256), 0, st(), m, mp, B, Bp, (const T*)ns_kapt, (const T*)rbuf, (T)rho,
-                       ns_u);
-    const T* S = natural ? ns_Wt : ns_kapt;
-    hipLaunchKernelGGL((k_nvi_scale_cols<T>), grid2(mp, Bq), blk2, 0, st(), m, B, mp, Bq, Bp, S, (const T*)wbuf, (T)rho, ns_S2);
-    LAUNCHCHK(ctx);
-    AGPCHK((gemm_nt<T, EPI_STORE>(ctx, ns_S2, Bp, S, Bp, mp, mp, Bq, 0, ns_P2, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-    AGPCHK(update_from(ns_u, ns_P2, nullptr));
+    for (int l = 0; l < nl; ++l) {
+      hipLaunchKernelGGL((k_nvi_kappat_g<T>), grid1(mp * 64), dim3(256), 0, st(), m, mp, B, Bp, (const T*)ns_kapt[l],
+                         (const T*)(rbuf + l * Bp), (T)rho, ns_u);
+      const T* S = natural ? ns_Wt[l] : ns_kapt[l];
+      hipLaunchKernelGGL((k_nvi_scale_cols<T>), grid2(mp, Bq), blk2, 0, st(), m, B, mp, Bq, Bp, S, (const T*)(wbuf + l * Bp), (T)rho, ns_S2);
+      LAUNCHCHK(ctx);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, ns_S2, Bp, S, Bp, mp, mp, Bq, 0, ns_P2, mp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+      cur = l;
+      AGPCHK(update_from(ns_u, ns_P2, nullptr, l == nl - 1));
+    }
+    cur = 0;
     x_last = x;
     y_last = y;
     idx_last = idx;
@@ -6575,7 +6728,12 @@ agp_status agp_svgp_create(agp_ctx* ctx, const agp_svgp_desc* desc, agp_svgp** o
     return AGP_ERR_UNSUPPORTED;
   }
   if ((desc->flags & AGP_FLAG_NUMERICAL) && ((desc->flags & (AGP_FLAG_EXACT | AGP_FLAG_SAMPLED)) || desc->dtype != AGP_F64)) {
-    ctx->err = std::string("AGP_FLAG_NUMERICAL: ") + nvi_supported() + " (never with AGP_FLAG_EXACT or AGP_FLAG_SAMPLED)";
+    ctx->err = std::string("AGP_FLAG_NUMERICAL: ") + ((desc->flags & AGP_FLAG_MC) ? mc_supported() : nvi_supported()) +
+               " (never with AGP_FLAG_EXACT or AGP_FLAG_SAMPLED)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if ((desc->flags & AGP_FLAG_MC) && !(desc->flags & AGP_FLAG_NUMERICAL)) {
+    ctx->err = std::string("AGP_FLAG_MC is valid only together with AGP_FLAG_NUMERICAL (with or without AGP_FLAG_FULL); ") + mc_supported();
     return AGP_ERR_UNSUPPORTED;
   }
   if (desc->flags & AGP_FLAG_NUMERICAL) impl = (desc->flags & AGP_FLAG_FULL) ? new Nvgp() : new Nsvgp();
@@ -7009,6 +7167,61 @@ agp_status agp_quad_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const vo
   if (e != hipSuccess) {
     ctx->err = std::string("agp_quad_expectations: ") + hipGetErrorString(e);
     return AGP_ERR_HIP;
+  }
+  return AGP_OK;
+}
+
+// ---- Monte-Carlo integration (AGP_FLAG_NUMERICAL | AGP_FLAG_MC) ------------------------------------------------------------------
+agp_status agp_svgp_mcvi_configure(agp_svgp* h, int32_t nMC, uint64_t seed, int32_t natural, int32_t opt_kind, double eta, double p1,
+                                   double p2, double eps) {
+  HCHK(h);
+  return h->impl->mcvi_configure(nMC, seed, natural, opt_kind, eta, p1, p2, eps);
+}
+static bool mc_table_args_ok(int64_t t, int32_t stream, int32_t nMC, int32_t K) {
+  return t >= 0 && t <= (int64_t)0xFFFFFFFFll && stream >= 0 && nMC >= 1 && nMC <= 65536 && K >= 1 &&
+         (int64_t)nMC * K <= (int64_t)0xFFFFFFFFll;
+}
+agp_status agp_mc_normals(agp_ctx* ctx, uint64_t seed, int64_t t, int32_t stream, int32_t nMC, int32_t K, void* out) {
+  if (!ctx || !out || !mc_table_args_ok(t, stream, nMC, K)) return AGP_ERR_INVALID;
+  DevGuard guard(ctx->device);
+  AGPCHK(mc_fill_normals(ctx, ctx->stream, seed, t, stream, nMC, K, (double*)out));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return AGP_OK;
+}
+agp_status agp_mc_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void* y_class, const void* mu, const void* var,
+                               int64_t n_pts, int32_t K, int32_t nMC, uint64_t seed, int64_t t, int32_t stream, void* ell, void* g,
+                               void* h) {
+  if (!ctx || !lik || !y_class || !mu || !var || !ell || !g || !h || n_pts < 0 || !mc_table_args_ok(t, stream, nMC, K))
+    return AGP_ERR_INVALID;
+  if (!mc_lik_ok(lik->kind) || K < 2 || K > MC_KMAX || lik->n_class != K) {
+    ctx->err = std::string("agp_mc_expectations: ") + mc_supported();
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if (n_pts == 0) return AGP_OK;
+  DevGuard guard(ctx->device);
+  double* tab = nullptr;
+  AGPCHK(dmalloc(ctx, &tab, (int64_t)nMC * K + 1));
+  int* flag = (int*)(tab + (int64_t)nMC * K);
+  int host = 0;
+  hipError_t e = hipMemsetAsync(flag, 0, sizeof(double), ctx->stream);
+  if (e == hipSuccess) {
+    const int64_t n = (int64_t)nMC * K;
+    hipLaunchKernelGGL(k_mc_normals, grid1(n), dim3(256), 0, ctx->stream, n, seed, (uint32_t)t, (uint32_t)stream, tab);
+    hipLaunchKernelGGL(k_mc_local, dim3((unsigned)((n_pts + 3) / 4)), dim3(256), 0, ctx->stream, n_pts, (int)lik->kind, (int)K, (int)nMC,
+                       (const int32_t*)y_class, (const int64_t*)nullptr, (const double*)mu, (const double*)var, n_pts, (const double*)tab,
+                       (double*)ell, (double*)g, (double*)h, n_pts, flag);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(tab);
+  if (e != hipSuccess) {
+    ctx->err = std::string("agp_mc_expectations: ") + hipGetErrorString(e);
+    return AGP_ERR_HIP;
+  }
+  if (host & FLAG_BAD_LABEL) {
+    ctx->err = "agp_mc_expectations: a class index outside [0, K)";
+    return AGP_ERR_LABELS;
   }
   return AGP_OK;
 }

@@ -2,6 +2,8 @@
 // src/inference/quadratureVI.jl): the point-wise expectations, the gradient assembly, the optimiser rules on (mu, Sigma) and the
 // candidate Sigma + alpha Symmetric(dSigma) of the positive-definiteness backtracking.  The m x m products and the factorisation
 // of the candidate are the library's own (gemm_nt, potrf_fused); the steps are Nvgp::nvi_step and Nsvgp::nvi_step (agp_capi.hip).
+// At the end of the file: the expectations by Monte-Carlo integration over K latents (MCIntegrationVI, src/inference/MCVI.jl), which feed
+// the same step once per latent.
 // Three definitions of the reference are restated in their intended form (include/agp_hip.h, "NUMERICAL INFERENCE"):
 //   Logistic  l'' = -sigma(f) sigma(-f)                       (logistic.jl:98-100 grows like exp(3 |f|))
 //   Laplace   E[l''] = -(2 / beta) N(y; mu_f, var_f)          (laplace.jl:131 has the wrong sign and no exponential)
@@ -223,6 +225,117 @@ __global__ __launch_bounds__(256) void k_nvi_kappat_g(int64_t m, int64_t n, int6
     for (int64_t k = lane; k < B; k += 64) s += (double)kapt[row * ld + k] * (double)g[k];
   for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
   if (lane == 0) u[row] = (T)((double)rho * s);
+}
+
+// ---- MC integration (MCIntegrationVI, src/inference/MCVI.jl; include/agp_hip.h, "MC INTEGRATION") ------------------------------------
+// ell_i = mean_s log p(c_i | f_s), g_ik = mean_s d log p / d f_k, h_ik = mean_s d2 log p / d f_k^2 at f_sk = mu_ik + sqrt(max(var_ik, 0)) eps_sk
+// for the SoftMax and the LogisticSoftMax likelihood (softmax.jl:26-48, logisticsoftmax.jl:144-193), from the nMC x K table eps of the
+// step (k_mc_normals).  One wave per point, four points per workgroup.  The lanes of a wave are (draw, latent) pairs: with P the power
+// of two >= K, lane = grp P + k handles latent k of draw s0 + grp, 64 / P draws at a time, so the maximum and the sums over k are P-lane
+// butterflies and every lane owns ONE accumulator of g_k and of h_k -- no per-lane array over k.  The table is staged through LDS in
+// tiles of MC_TILE doubles (whole draws), shared by the four waves.  Summation order: a lane adds its draws in order, then a fixed
+// butterfly over the groups; it depends on (nMC, K) alone, never on the grid.
+// 1 - s_k of the largest entry is formed as (sum of the other entries) / total (the first maximum counts as the largest), which keeps
+// the relative accuracy of g_c and h_k where a class probability approaches one.
+// idx (nullable): the minibatch, the class is read at idx[i].  mu, var: [K][ldp]; g, h: [K][ldo].  flags (nullable): FLAG_BAD_LABEL.
+constexpr int MC_TILE = 2048;
+constexpr int MC_KMAX = 64;
+__global__ __launch_bounds__(256) void k_mc_local(int64_t n, int lik, int K, int nMC, const int32_t* __restrict__ ycls,
+                                                   const int64_t* __restrict__ idx, const double* __restrict__ mu,
+                                                   const double* __restrict__ var, int64_t ldp, const double* __restrict__ eps,
+                                                   double* __restrict__ ell, double* __restrict__ g, double* __restrict__ h, int64_t ldo,
+                                                   int* __restrict__ flags) {
+  __shared__ double tile[MC_TILE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t i = blockIdx.x * (int64_t)4 + wave;
+  const bool active = i < n;  // (wave-uniform; an idle wave still loads its share of the tile and meets the barriers)
+  int P = 2;
+  while (P < K) P <<= 1;
+  const int G = 64 / P, grp = lane / P, k = lane & (P - 1);
+  const bool valid = k < K;
+  const unsigned long long gmask = P == 64 ? ~0ull : ((1ull << P) - 1ull);
+  int cls = -1;
+  double m = 0.0, sd = 0.0;
+  if (active) {
+    cls = ycls[idx ? idx[i] : i];
+    if ((cls < 0 || cls >= K) && flags && lane == 0) atomicOr(flags, FLAG_BAD_LABEL);
+    if (valid) {
+      const double v = var[k * ldp + i];
+      m = mu[k * ldp + i];
+      sd = sqrt(v > 0.0 ? v : 0.0);
+    }
+  }
+  const bool mine = valid && k == cls;
+  const int TS = MC_TILE / K;  // draws per tile (K <= MC_KMAX: at least 32)
+  double ae = 0.0, ag = 0.0, ah = 0.0;
+  for (int t0 = 0; t0 < nMC; t0 += TS) {
+    const int ns = nMC - t0 < TS ? nMC - t0 : TS;
+    __syncthreads();
+    for (int e = threadIdx.x; e < ns * K; e += 256) tile[e] = eps[(int64_t)t0 * K + e];
+    __syncthreads();
+    if (!active) continue;
+    for (int s0 = 0; s0 < ns; s0 += G) {  // (uniform over the wave: every lane takes part in the butterflies)
+      const int s = s0 + grp;
+      const bool on = valid && s < ns;
+      const double f = on ? m + sd * tile[s * K + k] : -__builtin_inf();
+      double M = f;
+      for (int o = P >> 1; o > 0; o >>= 1) M = fmax(M, __shfl_xor(M, o));
+      const unsigned long long tops = (__ballot(on && f == M) >> (grp * P)) & gmask;
+      const bool top = on && k == __ffsll((long long)tops) - 1;
+      if (lik == AGP_LIK_SOFTMAX) {
+        const double e = on ? exp(f - M) : 0.0;  // (the largest: exactly 1)
+        double Sp = top ? 0.0 : e;
+        for (int o = P >> 1; o > 0; o >>= 1) Sp += __shfl_xor(Sp, o);
+        const double S = 1.0 + Sp, sk = e / S, om = top ? Sp / S : 1.0 - sk;
+        if (on) {
+          ag += mine ? om : -sk;
+          ah += -sk * om;
+          if (mine) ae += (f - M) - log1p(Sp);
+        }
+      } else {  // AGP_LIK_LOGISTICSOFTMAX
+        const double ex = exp(-fabs(f)), den = 1.0 + ex;
+        const double sg = on ? (f >= 0.0 ? 1.0 / den : ex / den) : 0.0;   // logistic(f)
+        const double sm = f >= 0.0 ? ex / den : 1.0 / den;                // 1 - logistic(f) = logistic(-f)
+        double Sp = top ? 0.0 : sg, St = top ? sg : 0.0;
+        for (int o = P >> 1; o > 0; o >>= 1) {
+          Sp += __shfl_xor(Sp, o);
+          St += __shfl_xor(St, o);
+        }
+        const double S = St + Sp, sk = sg / S, om = top ? Sp / S : 1.0 - sk;
+        if (on) {
+          const double d = mine ? om : -sk;  // y_k - s_k
+          ag += sm * d;
+          ah += sm * (-sg * d - sk * om * sm);
+          // log s_c: of the largest entry -log1p(others / sg_c) (no cancellation where s_c approaches one), else log sg_c - log S
+          // with log sg_c = -softplus(-f_c)
+          if (mine) ae += top ? -log1p(Sp / sg) : (f >= 0.0 ? -log1p(ex) : f - log1p(ex)) - log(S);
+        }
+      }
+    }
+  }
+  if (!active) return;
+  for (int o = 32; o > 0; o >>= 1) ae += __shfl_xor(ae, o);
+  for (int o = 32; o >= P; o >>= 1) {  // over the groups: the lanes that hold the same latent
+    ag += __shfl_xor(ag, o);
+    ah += __shfl_xor(ah, o);
+  }
+  if (lane == 0) ell[i] = ae / (double)nMC;
+  if (grp == 0 && valid) {
+    g[k * ldo + i] = ag / (double)nMC;
+    h[k * ldo + i] = ah / (double)nMC;
+  }
+}
+
+// SoftMax link on the means only (multiclass.jl:96-117, softmax.jl): out[i][k] row-major n x nl, two passes over k
+template <typename T>
+__global__ void k_proba_softmax(int64_t n, int nl, int64_t ldm, const T* __restrict__ mu, T* __restrict__ out) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double M = (double)mu[i];
+  for (int k = 1; k < nl; ++k) M = fmax(M, (double)mu[k * ldm + i]);
+  double s = 0.0;
+  for (int k = 0; k < nl; ++k) s += exp((double)mu[k * ldm + i] - M);
+  for (int k = 0; k < nl; ++k) out[i * nl + k] = (T)(exp((double)mu[k * ldm + i] - M) / s);
 }
 
 }  // namespace agp

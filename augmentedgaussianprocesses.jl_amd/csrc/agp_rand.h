@@ -74,6 +74,84 @@ struct RngStream {
   __device__ __forceinline__ void bound_hit() { atomicOr(flags, FLAG_RNG_BOUND); }
 };
 
+// ---- the Monte-Carlo table of MCIntegrationVI (include/agp_hip.h, "MC INTEGRATION") ---------------------------------------------------
+// Streams 2 (the gradient draw of step t) and 3 (the ELBO after t steps).  eps[s][k] is the contract's Normal of block 0 at counter
+// (s K + k, t, stream, 0), with log and cos evaluated by the arithmetic below instead of the device's math library: every operation
+// is one IEEE double operation (no contraction), so a host program that follows it gets the table bit for bit (tests/_mcvi_ref.py).
+enum { RNG_STREAM_MC_GRAD = 2, RNG_STREAM_MC_ELBO = 3 };
+// log(a), 0 < a < 1: a = m 2^e with sqrt(1/2) <= m < sqrt(2), log m = 2 atanh(s), s = (m - 1) / (m + 1), |s| < 0.1716: the odd series
+// through s^23 / 23 by Horner in z = s^2, then e ln 2 + log m
+__device__ __forceinline__ double mc_log(double a) {
+#pragma clang fp contract(off)
+  int e;
+  double m = frexp(a, &e);
+  if (m < 0.7071067811865476) {
+    m = m * 2.0;
+    e -= 1;
+  }
+  const double s = (m - 1.0) / (m + 1.0), z = s * s;
+  double p = 1.0 / 23.0;
+  p = p * z + 1.0 / 21.0;
+  p = p * z + 1.0 / 19.0;
+  p = p * z + 1.0 / 17.0;
+  p = p * z + 1.0 / 15.0;
+  p = p * z + 1.0 / 13.0;
+  p = p * z + 1.0 / 11.0;
+  p = p * z + 1.0 / 9.0;
+  p = p * z + 1.0 / 7.0;
+  p = p * z + 1.0 / 5.0;
+  p = p * z + 1.0 / 3.0;
+  p = p * z + 1.0;
+  return (double)e * 0.6931471805599453 + (2.0 * s) * p;
+}
+// cos(2 pi b), 0 < b < 1: folded exactly onto q in [0, 1/8] (1 - b, 1/2 - r, 1/4 - r are exact), then the Taylor polynomial of cos or
+// sin at x = 2 pi q <= pi / 4 through x^16 / x^17 by Horner in x^2
+__device__ __forceinline__ double mc_cos2pi(double b) {
+#pragma clang fp contract(off)
+  double r = b > 0.5 ? 1.0 - b : b;
+  double sign = 1.0;
+  if (r > 0.25) {
+    r = 0.5 - r;
+    sign = -1.0;
+  }
+  double v;
+  if (r > 0.125) {
+    const double x = 6.283185307179586 * (0.25 - r), z = x * x;
+    double p = 1.0 / 355687428096000.0;              // 1 / 17!
+    p = p * z - 1.0 / 1307674368000.0;               // 15!
+    p = p * z + 1.0 / 6227020800.0;                  // 13!
+    p = p * z - 1.0 / 39916800.0;                    // 11!
+    p = p * z + 1.0 / 362880.0;                      // 9!
+    p = p * z - 1.0 / 5040.0;
+    p = p * z + 1.0 / 120.0;
+    p = p * z - 1.0 / 6.0;
+    p = p * z + 1.0;
+    v = x * p;
+  } else {
+    const double x = 6.283185307179586 * r, z = x * x;
+    double p = 1.0 / 20922789888000.0;               // 1 / 16!
+    p = p * z - 1.0 / 87178291200.0;                 // 14!
+    p = p * z + 1.0 / 479001600.0;                   // 12!
+    p = p * z - 1.0 / 3628800.0;                     // 10!
+    p = p * z + 1.0 / 40320.0;
+    p = p * z - 1.0 / 720.0;
+    p = p * z + 1.0 / 24.0;
+    p = p * z - 1.0 / 2.0;
+    p = p * z + 1.0;
+    v = p;
+  }
+  return sign * v;
+}
+// out[i] = the Normal of counter (i, t, stream, 0), i < n = nMC K: the table double[nMC][K], filled once per step or evaluation
+__global__ __launch_bounds__(256) void k_mc_normals(int64_t n, uint64_t seed, uint32_t t, uint32_t stream, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Philox4 b = philox4x32_10((uint32_t)i, t, stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const double u0 = u53(b.w[0], b.w[1]), u1 = u53(b.w[2], b.w[3]);
+  out[i] = sqrt(-2.0 * mc_log(u0)) * mc_cos2pi(u1);
+}
+
 constexpr double PG_T = 0.64;  // polyagamma.jl: pg_t
 
 // log Phi(x) of the standard normal, without underflow in the lower tail

@@ -118,6 +118,17 @@ class LogisticSoftMaxLikelihood(AbstractLikelihood):
         return f"Multiclass Likelihood ({self.n_class} classes, Logistic-SoftMax Link )"
 
 
+class SoftMaxLikelihood(LogisticSoftMaxLikelihood):
+    """SoftMaxLikelihood(num_class | labels)  src/likelihood/softmax.jl:1-24: p(y = i | f) = exp(f_i) / sum_k exp(f_k).  The labels
+    are treated as for LogisticSoftMaxLikelihood (multiclass.jl:1-94).  There is no augmentation for this likelihood: it runs under
+    MCIntegrationVI / MCIntegrationSVI only (nvi.py)."""
+
+    kind = capi.LIK_SOFTMAX
+
+    def __repr__(self):  # multiclass.jl:35-37 with softmax.jl:24
+        return f"Multiclass Likelihood ({self.n_class} classes, SoftMax Link )"
+
+
 class LaplaceLikelihood(AbstractLikelihood):
     """LaplaceLikelihood(β=1.0)  src/likelihood/laplace.jl:17-30 (q(ω) = GIG(a = β⁻², b, p = 1/2))."""
 
@@ -347,6 +358,10 @@ def likelihood_value(l: AbstractLikelihood, y, f) -> float:
         (ff, g), yy = y, f
         var = 1.0 / (l.lam * _logistic(g))
         return _math.exp(-0.5 * (yy - ff) ** 2 / var) / _math.sqrt(2.0 * _math.pi * var)
+    if isinstance(l, SoftMaxLikelihood):  # softmax.jl:11-16, multiclass.jl:31-33: softmax(f)[y]
+        mx = max(f)
+        s = [_math.exp(v - mx) for v in f]
+        return s[int(y) - 1] / sum(s)
     if isinstance(l, LogisticSoftMaxLikelihood):  # logisticsoftmax.jl:29-31, multiclass.jl:31-33: normalize(logistic.(f), 1)[y]
         s = [_logistic(v) for v in f]
         return s[int(y) - 1] / sum(s)

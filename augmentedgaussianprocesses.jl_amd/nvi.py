@@ -1,5 +1,6 @@
 """QuadratureVI -- VGP(X, y, kernel, likelihood, QuadratureVI()) and SVGP(kernel, likelihood, QuadratureVI() / QuadratureSVI(B), Z)
-(src/inference/numericalVI.jl, src/inference/quadratureVI.jl).
+(src/inference/numericalVI.jl, src/inference/quadratureVI.jl) -- and MCIntegrationVI / MCIntegrationSVI on the same two models for the
+multi-class likelihoods SoftMax and LogisticSoftMax (src/inference/MCVI.jl): K latents, each with the single latent's step.
 
 The inference objects (QuadratureVI, QuadratureSVI, NumericalVI, NumericalSVI) live in svgp.py next to AnalyticVI; the models are
 SVGP and VGP themselves, whose device handle is created with AGP_FLAG_NUMERICAL (VGP: | AGP_FLAG_FULL) and keeps (mu, Sigma) and
@@ -45,33 +46,36 @@ def _dptr(a):
 def configure(model, h) -> None:
     """install the quadrature rule and the optimiser of model.inference on a fresh handle"""
     inf = model.inference
-    x, w = gauss_hermite_rule(inf.nGaussHermite)
     kind, eta, p1, p2, eps = rule_args(inf.nvi_optimiser)
+    if getattr(inf, "mc", False):  # MCIntegrationVI: the number of draws and the seed of the table instead of a rule
+        return model._chk(capi.lib().agp_svgp_mcvi_configure(h, inf.nMC, inf.seed, 1 if inf.natural else 0, kind, eta, p1, p2, eps))
+    x, w = gauss_hermite_rule(inf.nGaussHermite)
     model._chk(capi.lib().agp_svgp_nvi_configure(h, len(x), _dptr(x), _dptr(w), 1 if inf.natural else 0, kind, eta, p1, p2, eps))
 
 
-def nvi_info(model):
-    """(alpha of the last step, halvings, rejected updates) of the handle since it was created"""
+def nvi_info(model, latent: int = 0):
+    """(alpha of the last step, halvings, rejected updates) of one latent of the handle since it was created"""
     a, hv, rj = C.c_double(), C.c_int64(), C.c_int64()
-    model._chk(capi.lib().agp_svgp_nvi_info(model._h, 0, C.byref(a), C.byref(hv), C.byref(rj)))
+    model._chk(capi.lib().agp_svgp_nvi_info(model._h, int(latent), C.byref(a), C.byref(hv), C.byref(rj)))
     return a.value, int(hv.value), int(rj.value)
 
 
-def get_opt_state(model):
-    """(mom_mu [2, N], mom_sigma [2, N, N], t): the optimiser's moments of mu and Sigma and its step counter"""
+def get_opt_state(model, latent: int = 0):
+    """(mom_mu [2, N], mom_sigma [2, N, N], t): the optimiser's moments of mu and Sigma of one latent and the step counter (one for
+    all latents)"""
     import torch
 
     N, dev = model.m, model._dev()
     mm = torch.empty(2, N, dtype=torch.float64, device=dev)
     ms = torch.empty(2, N, N, dtype=torch.float64, device=dev)
     t = C.c_int64()
-    model._chk(capi.lib().agp_svgp_nvi_state(model._h, 0, 0, C.c_void_p(mm.data_ptr()), C.c_void_p(ms.data_ptr()),
+    model._chk(capi.lib().agp_svgp_nvi_state(model._h, int(latent), 0, C.c_void_p(mm.data_ptr()), C.c_void_p(ms.data_ptr()),
                                              C.byref(t)))
     model._chk(capi.lib().agp_ctx_sync(model._ctx))
     return mm.cpu().numpy(), ms.cpu().numpy(), int(t.value)
 
 
-def set_opt_state(model, mom_mu, mom_sigma, t: int) -> None:
+def set_opt_state(model, mom_mu, mom_sigma, t: int, latent: int = 0) -> None:
     import torch
 
     N, dev = model.m, model._dev()
@@ -79,7 +83,7 @@ def set_opt_state(model, mom_mu, mom_sigma, t: int) -> None:
     ms = torch.as_tensor(np.asarray(mom_sigma, dtype=np.float64), device=dev).contiguous()
     if tuple(mm.shape) != (2, N) or tuple(ms.shape) != (2, N, N):
         raise ValueError("the optimiser state is (2, N) for mu and (2, N, N) for Sigma")
-    model._chk(capi.lib().agp_svgp_nvi_state(model._h, 0, 1, C.c_void_p(mm.data_ptr()), C.c_void_p(ms.data_ptr()),
+    model._chk(capi.lib().agp_svgp_nvi_state(model._h, int(latent), 1, C.c_void_p(mm.data_ptr()), C.c_void_p(ms.data_ptr()),
                                              C.byref(C.c_int64(int(t)))))
     model._chk(capi.lib().agp_ctx_sync(model._ctx))
 
@@ -89,7 +93,8 @@ def train_numerical(model, iterations: int, *, X=None, y=None, callback: Optiona
     """train!(model, [X, y,] iterations) with QuadratureVI / QuadratureSVI  training.jl:13-111 with variational_updates of
     numericalVI.jl:101-119: a fixed number of steps; a VGP on its own data, an SVGP on (X, y) with minibatches of
     inference.batchsize drawn like AnalyticSVI's (or taken from idx_stream).  Without `state` the optimiser starts anew (init_state,
-    states.jl:50-84), as in the reference; `state=` continues it.  alpha of every step is appended to model.nvi_alphas."""
+    states.jl:50-84), as in the reference; `state=` continues it.  alpha of every step is appended to model.nvi_alphas: a float, or
+    with MCIntegrationVI the K-tuple of the latents' alphas."""
     import torch
 
     L = capi.lib()
@@ -136,8 +141,15 @@ def train_numerical(model, iterations: int, *, X=None, y=None, callback: Optiona
             idx_ptr = C.c_void_p(idx.data_ptr())
         model._chk(L.agp_svgp_nvi_step(h, C.c_void_p(Xd.data_ptr()), Xd.stride(0), C.c_void_p(yd.data_ptr()), idx_ptr, B, inf.rho))
         model._last_idx = idx_ptr
-        model._chk(L.agp_svgp_nvi_info(h, 0, C.byref(a), None, None))
-        model.nvi_alphas.append(a.value)
+        if getattr(inf, "mc", False):
+            al = []
+            for k in range(model.n_latent):
+                model._chk(L.agp_svgp_nvi_info(h, k, C.byref(a), None, None))
+                al.append(a.value)
+            model.nvi_alphas.append(tuple(al))
+        else:
+            model._chk(L.agp_svgp_nvi_info(h, 0, C.byref(a), None, None))
+            model.nvi_alphas.append(a.value)
         model.trained = True
         if callback is not None:
             callback(model, State(model), inf.n_iter)
@@ -181,3 +193,55 @@ def quad_expectations(likelihood, y, mu, var, nodes, weights, *, device: Optiona
         return ell.cpu().numpy(), g.cpu().numpy(), h.cpu().numpy()
     finally:
         L.agp_ctx_destroy(ctx)
+
+
+def _ctx_call(device, fn):
+    """run fn(L, ctx, dev) on a context of its own (the two context-level entry points below)"""
+    import torch
+
+    L = capi.lib()
+    dev = torch.device("cuda", device if device is not None else torch.cuda.current_device())
+    ctx = C.c_void_p()
+    st = L.agp_ctx_create(dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(ctx))
+    if st != capi.AGP_OK:
+        raise capi.AGPError(st, "agp_ctx_create failed")
+    try:
+        return fn(L, ctx, dev)
+    finally:
+        L.agp_ctx_destroy(ctx)
+
+
+def mc_normals(seed: int, t: int, stream: int, nMC: int, K: int, *, device: Optional[int] = None):
+    """the table eps[nMC, K] of standard normals of (seed, t, stream) as the device draws it (agp_mc_normals): stream 2 is the
+    gradient draw of step t, stream 3 the draw of an ELBO evaluated after t steps (include/agp_hip.h, "MC INTEGRATION")"""
+    import torch
+
+    def run(L, ctx, dev):
+        out = torch.empty(int(nMC), int(K), dtype=torch.float64, device=dev)
+        capi.check(ctx, L.agp_mc_normals(ctx, int(seed), int(t), int(stream), int(nMC), int(K), C.c_void_p(out.data_ptr())))
+        return out.cpu().numpy()
+
+    return _ctx_call(device, run)
+
+
+def mc_expectations(likelihood, y_class, mu, var, nMC: int, seed: int, t: int, stream: int = 2, *, device: Optional[int] = None):
+    """(ell [n], g [K, n], h [K, n]): the means over the nMC draws of log p(c_i | f), d log p / d f_k and d2 log p / d f_k^2 at
+    f_sk = mu_ki + sqrt(max(var_ki, 0)) eps_sk for the SoftMax and LogisticSoftMax likelihoods -- the expectation kernel on given
+    moments, outside any model (agp_mc_expectations).  y_class: 0-based class indices [n]; mu, var: [K, n]."""
+    import torch
+
+    def run(L, ctx, dev):
+        yt = torch.as_tensor(np.asarray(y_class, dtype=np.int32), device=dev).contiguous()
+        mt, vt = (torch.as_tensor(np.asarray(a, dtype=np.float64), device=dev).contiguous() for a in (mu, var))
+        if not (yt.ndim == 1 and mt.ndim == 2 and mt.shape == vt.shape and mt.shape[1] == yt.shape[0]):
+            raise ValueError("y_class is a vector of n class indices, mu and var are (K, n)")
+        K, n = mt.shape
+        ell = torch.empty(n, dtype=torch.float64, device=dev)
+        g, h = torch.empty_like(mt), torch.empty_like(mt)
+        d = likelihood.lik_desc()
+        capi.check(ctx, L.agp_mc_expectations(ctx, C.byref(d), C.c_void_p(yt.data_ptr()), C.c_void_p(mt.data_ptr()),
+                                              C.c_void_p(vt.data_ptr()), n, K, int(nMC), int(seed), int(t), int(stream),
+                                              C.c_void_p(ell.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(h.data_ptr())))
+        return ell.cpu().numpy(), g.cpu().numpy(), h.cpu().numpy()
+
+    return _ctx_call(device, run)

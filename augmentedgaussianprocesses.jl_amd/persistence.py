@@ -75,6 +75,8 @@ def _lik_from(d):
         return LK.LogisticLikelihood()
     if t == "StudentTLikelihood":
         return LK.StudentTLikelihood(d["nu"], d["sigma"])
+    if t == "SoftMaxLikelihood":
+        return LK.SoftMaxLikelihood(d["class_mapping"] if d.get("class_mapping") else d["n_class"])
     if t == "LogisticSoftMaxLikelihood":
         return LK.LogisticSoftMaxLikelihood(d["class_mapping"] if d.get("class_mapping") else d["n_class"])
     if t == "LaplaceLikelihood":
@@ -88,6 +90,17 @@ def _lik_from(d):
     if t == "HeteroscedasticLikelihood":
         return LK.HeteroscedasticLikelihood(d["lam"])
     raise ValueError(f"unknown likelihood {t}")
+
+
+def _nvi_from(meta, sparse):
+    """the numerical inference object of a saved model: QuadratureVI, or MCIntegrationVI with its nMC and seed"""
+    from .svgp import MCIntegrationVI, QuadratureVI
+
+    nv = meta["nvi"]
+    kw = dict(_stoch=meta["stochastic"], _batchsize=meta["batchsize"]) if sparse else {}
+    if nv.get("mc"):
+        return MCIntegrationVI(nv["eps"], nv["nMC"], _opt_from(nv["optimiser"]), float(nv["clipping"]), nv["natural"], seed=nv["seed"], **kw)
+    return QuadratureVI(nv["eps"], nv["nGaussHermite"], _opt_from(nv["optimiser"]), 0.0, nv["natural"], **kw)
 
 
 def save_trained_model(filename: str, model: SVGP) -> None:
@@ -126,8 +139,11 @@ def save_trained_model(filename: str, model: SVGP) -> None:
                          "sweeps": model.sweep_counter()}
     numerical = bool(getattr(model, "_numerical", False))
     if numerical:  # QuadratureVI: its settings; the state (mu, Sigma, the optimiser's moments, its step counter) goes below
-        meta["nvi"] = {"eps": inf.eps, "nGaussHermite": inf.nGaussHermite, "natural": inf.natural,
-                       "optimiser": _opt_spec(inf.nvi_optimiser)}
+        meta["nvi"] = {"eps": inf.eps, "natural": inf.natural, "optimiser": _opt_spec(inf.nvi_optimiser)}
+        if getattr(inf, "mc", False):  # MCIntegrationVI: the draws per step and the seed of their table (clipping: stored, not read)
+            meta["nvi"].update(mc=True, nMC=inf.nMC, seed=inf.seed, clipping=repr(inf.clipping))
+        else:
+            meta["nvi"]["nGaussHermite"] = inf.nGaussHermite
     import ctypes as C
 
     from . import capi
@@ -144,8 +160,9 @@ def save_trained_model(filename: str, model: SVGP) -> None:
         elif numerical:  # a loaded model continues bit for bit (train_(model, n, state=...))
             from .nvi import get_opt_state
 
-            arrays["nvi_mu"], arrays["nvi_Sigma"] = model.get_state(l)
-            arrays["nvi_mom_mu"], arrays["nvi_mom_sigma"], t = get_opt_state(model)
+            sfx = "" if l == 0 else f"_{l}"  # (the single latent keeps the names it has always had)
+            arrays["nvi_mu" + sfx], arrays["nvi_Sigma" + sfx] = model.get_state(l)
+            arrays["nvi_mom_mu" + sfx], arrays["nvi_mom_sigma" + sfx], t = get_opt_state(model, latent=l)
             arrays["nvi_t"] = np.array(t)
         elif not exact:  # (a GP's posterior follows from the kernel, sigma2 and y: it is rebuilt on load)
             mu, Sig, e1, e2 = model.get_state(l)
@@ -159,7 +176,7 @@ def save_trained_model(filename: str, model: SVGP) -> None:
             km, kv, ks = (C.c_double * (1 + model.D))(), (C.c_double * (1 + model.D))(), C.c_int32()
             model._chk(capi.lib().agp_svgp_hyper_opt_state(model._h, l, 0, km, kv, C.byref(ks)))
             arrays[f"kopt_m_{l}"], arrays[f"kopt_v_{l}"], arrays[f"kopt_t_{l}"] = np.array(km[:]), np.array(kv[:]), np.array(ks.value)
-    if isinstance(model.likelihood, LK.LogisticSoftMaxLikelihood) and inf.batchsize > 0:
+    if isinstance(model.likelihood, LK.LogisticSoftMaxLikelihood) and inf.batchsize > 0 and not numerical:
         # carried between minibatches; exported by capacity (it is state, not a view of the last batch)
         arrays["lsm_alpha"] = model.get_matrix(capi.VEC_ALPHA, 0, min(int(inf.batchsize), model._max_batch))
     if isinstance(model.mean, (list, np.ndarray)):
@@ -230,19 +247,12 @@ def load_trained_model(filename: str, *, device=None):
         from .vgp import VGP
 
         if "nvi" in meta:
-            from .svgp import QuadratureVI
-
-            nv = meta["nvi"]
-            inf = QuadratureVI(nv["eps"], nv["nGaussHermite"], _opt_from(nv["optimiser"]), 0.0, nv["natural"])
+            inf = _nvi_from(meta, False)
         model = VGP(Zs[0], g["vgp_y"], kernels, _lik_from(meta["likelihood"]), inf, optimiser=kw["optimiser"],
                     atfrequency=kw["atfrequency"], mean=mean, T=T, device=device)
     else:
         if "nvi" in meta:
-            from .svgp import QuadratureVI
-
-            nv = meta["nvi"]
-            inf = QuadratureVI(nv["eps"], nv["nGaussHermite"], _opt_from(nv["optimiser"]), 0.0, nv["natural"],
-                               _stoch=meta["stochastic"], _batchsize=meta["batchsize"])
+            inf = _nvi_from(meta, True)
         model = SVGP(kernels, _lik_from(meta["likelihood"]), inf, Zs, **kw)
     inf.n_iter = meta["n_iter"]
     h = model._ensure_handle(max(meta["batchsize"], 1))
@@ -252,8 +262,10 @@ def load_trained_model(filename: str, *, device=None):
     if "nvi_mu" in g.files:
         from .nvi import set_opt_state
 
-        model.set_state(0, g["nvi_mu"], g["nvi_Sigma"])
-        set_opt_state(model, g["nvi_mom_mu"], g["nvi_mom_sigma"], int(g["nvi_t"]))
+        for l in range(nl):
+            sfx = "" if l == 0 else f"_{l}"
+            model.set_state(l, g["nvi_mu" + sfx], g["nvi_Sigma" + sfx])
+            set_opt_state(model, g["nvi_mom_mu" + sfx], g["nvi_mom_sigma" + sfx], int(g["nvi_t"]), latent=l)
     for l in range(nl):
         if f"eta1_{l}" in g.files:
             model.set_state(l, g[f"eta1_{l}"], g[f"eta2_{l}"])

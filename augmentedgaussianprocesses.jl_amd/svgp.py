@@ -31,6 +31,7 @@ from .likelihoods import (
     GaussianLikelihood,
     LogisticLikelihood,
     LogisticSoftMaxLikelihood,
+    SoftMaxLikelihood,
     StudentTLikelihood,
     class_indices,
     treat_labels,
@@ -190,6 +191,45 @@ def QuadratureSVI(nMinibatch: int, eps: float = 1e-5, nGaussHermite: int = 100, 
     return QuadratureVI(eps, nGaussHermite, optimiser, clipping, natural, _stoch=True, _batchsize=int(nMinibatch))
 
 
+class MCIntegrationVI(QuadratureVI):
+    """MCIntegrationVI(; ϵ=1e-5, nMC=1000, optimiser=Momentum(0.01), clipping=Inf, natural=true)  MCVI.jl:1-74 -- variational
+    inference with the expectations of the log-likelihood and of its derivatives by Monte-Carlo integration: one nMC x K table of
+    standard normals per step, shared by every point of the batch (MCVI.jl:93-107), then for each of the K latents the (natural)
+    gradient step on (μ_k, Σ_k) with its own positive-definiteness backtracking (numericalVI.jl:101-179).  Runs on VGP and SVGP for
+    SoftMaxLikelihood and LogisticSoftMaxLikelihood, in Float64 (nvi.py; include/agp_hip.h, "MC INTEGRATION").
+
+    `seed` is ours: the table of step t is a function of (seed, t) alone (a counter-based generator), so a run is reproducible and
+    a saved model continues bit for bit.  `clipping` is stored as the reference stores it and, as there, read by no MC code: it
+    has no effect.  (It shares QuadratureVI's type because it shares its step, state and save format; `mc` tells them apart.)"""
+
+    mc = True
+
+    def __init__(self, eps: float = 1e-5, nMC: int = 1000, optimiser=None, clipping: float = float("inf"), natural: bool = True,
+                 *, seed: int = 0, _stoch=False, _batchsize=0, _default=None):
+        if int(nMC) < 1 or int(nMC) > 65536:
+            raise ValueError("nMC must be between 1 and 65536")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        super().__init__(eps, 1, optimiser if optimiser is not None else (_default or Momentum(0.01)), 0.0, natural,
+                         _stoch=_stoch, _batchsize=_batchsize)
+        del self.nGaussHermite
+        self.nMC = int(nMC)
+        self.seed = int(seed)
+        self.clipping = float(clipping)
+
+    def __repr__(self):  # numericalVI.jl:91-96
+        return f"{'Stochastic numerical' if self.stoch else 'Numerical'} Inference by Monte Carlo Integration"
+
+
+def MCIntegrationSVI(nMinibatch: int, eps: float = 1e-5, nMC: int = 200, optimiser=None, clipping: float = 0.0,
+                     natural: bool = True, *, seed: int = 0) -> MCIntegrationVI:
+    """MCIntegrationSVI(nMinibatch; ϵ=1e-5, nMC=200, optimiser=Momentum(0.001), clipping=0.0, natural=true)  MCVI.jl:76-91: the
+    stochastic form, minibatches of nMinibatch points with rho = N / nMinibatch.  Runs on SVGP; VGP takes the whole data set and
+    refuses it."""
+    return MCIntegrationVI(eps, nMC, optimiser, clipping, natural, seed=seed, _stoch=True, _batchsize=int(nMinibatch),
+                           _default=Momentum(0.001))
+
+
 def _numerical(integration_technique, kw, nGaussHermite, optimiser):
     if str(integration_technique).lstrip(":") == "mc":
         raise NotImplementedError("NumericalVI(:mc): MCIntegrationVI is not built on this path; use :quad")
@@ -202,7 +242,8 @@ def _numerical(integration_technique, kw, nGaussHermite, optimiser):
 def NumericalVI(integration_technique="quad", eps: float = 1e-5, nMC: int = 1000, nGaussHermite: int = 20, optimiser=None,
                 natural: bool = True) -> QuadratureVI:
     """NumericalVI(integration_technique=:quad; ϵ=1e-5, nMC=1000, nGaussHermite=20, optimiser=Momentum(1e-3), natural=true)
-    numericalVI.jl:24-52"""
+    numericalVI.jl:24-52.  Monte-Carlo integration is not reached through this door (:mc is refused): MCIntegrationVI /
+    MCIntegrationSVI are its entry points."""
     return QuadratureVI(**_numerical(integration_technique, dict(eps=eps, natural=natural), nGaussHermite, optimiser))
 
 
@@ -215,6 +256,9 @@ def NumericalSVI(nMinibatch: int, integration_technique="quad", eps: float = 1e-
 
 def refuse_numerical(name: str, inference) -> None:
     """What every model other than SVGP and VGP answers to QuadratureVI / QuadratureSVI: the limit, by name."""
+    if getattr(inference, "mc", False):
+        raise NotImplementedError(f"{name} does not run {inference!r}: MCIntegrationVI runs on SVGP and VGP, in Float64, for the "
+                                  "SoftMax and LogisticSoftMax likelihoods")
     if isinstance(inference, QuadratureVI):
         raise NotImplementedError(f"{name} does not run {inference!r}: QuadratureVI runs on SVGP and VGP, in Float64, for the "
                                   "Logistic, StudentT and Laplace likelihoods (the multi-output, online and sampled models are "
@@ -223,7 +267,20 @@ def refuse_numerical(name: str, inference) -> None:
 
 def check_numerical(name: str, inference, likelihood, optimiser, T) -> None:
     """What SVGP and VGP refuse with QuadratureVI: a likelihood outside the three, a float type other than Float64, a kernel
-    optimiser (the default included: the hyper-parameter step through the quadrature ELBO is not built)."""
+    optimiser (the default included: the hyper-parameter step through the quadrature ELBO is not built).  MCIntegrationVI: the
+    same, with the SoftMax and LogisticSoftMax likelihoods."""
+    if getattr(inference, "mc", False):
+        if not isinstance(likelihood, LogisticSoftMaxLikelihood):  # (SoftMaxLikelihood is one)  SVGP.jl:48-49 / VGP.jl:57-58
+            raise RuntimeError(f"The {likelihood} is not compatible or implemented with the {inference} (MCIntegrationVI runs for "
+                               "the SoftMax and LogisticSoftMax likelihoods)")
+        if likelihood.n_class > 64:
+            raise NotImplementedError(f"{name} with MCIntegrationVI: at most 64 classes on the device")
+        if np.dtype(T) != np.dtype(np.float64):
+            raise NotImplementedError(f"{name} with MCIntegrationVI runs in Float64 only")
+        if optimiser is not False:
+            raise NotImplementedError(f"{name} with MCIntegrationVI: the hyper-parameter step through the Monte-Carlo ELBO is not "
+                                      "built; pass optimiser=False (the default ADAM(0.01) is not silently switched off)")
+        return
     if not isinstance(likelihood, (LogisticLikelihood, StudentTLikelihood, LaplaceLikelihood)):
         # SVGP.jl:48-49 / VGP.jl:57-58; test/likelihood/gaussian.jl:38,59 for the Gaussian likelihood
         raise RuntimeError(f"The {likelihood} is not compatible or implemented with the {inference} (QuadratureVI runs for "
@@ -262,12 +319,13 @@ class SVGP:
             # numerical inference: SVGP itself (both forms) and VGP (vgp.py, which has set _numerical and made its own checks)
             if type(self) is SVGP:
                 check_numerical("SVGP", inference, likelihood, optimiser, T)
+                iname = "MCIntegrationVI" if getattr(inference, "mc", False) else "QuadratureVI"
                 if Zoptimiser not in (False, None):
-                    raise NotImplementedError("SVGP with QuadratureVI: the inducing points are not optimised; pass Zoptimiser=False")
+                    raise NotImplementedError(f"SVGP with {iname}: the inducing points are not optimised; pass Zoptimiser=False")
                 if latent_slice is not None or reference_compat_stale_K:
-                    raise NotImplementedError("SVGP with QuadratureVI: no latent_slice, no reference_compat_stale_K")
+                    raise NotImplementedError(f"SVGP with {iname}: no latent_slice, no reference_compat_stale_K")
                 self._numerical = True
-                self._desc_flags = capi.FLAG_NUMERICAL
+                self._desc_flags = capi.FLAG_NUMERICAL | (capi.FLAG_MC if getattr(inference, "mc", False) else 0)
             elif not getattr(self, "_numerical", False):
                 refuse_numerical(type(self).__name__, inference)
         elif not (isinstance(inference, Analytic) if exact else isinstance(inference, AnalyticVI)):
@@ -284,6 +342,9 @@ class SVGP:
                                        BayesianSVM, PoissonLikelihood, NegBinomialLikelihood,
                                        HeteroscedasticLikelihood)):
             raise RuntimeError(f"The {likelihood} is not compatible or implemented with the {inference}")  # :48-49
+        if isinstance(likelihood, SoftMaxLikelihood) and not getattr(inference, "mc", False):
+            # implemented(::MultiClassLikelihood{<:SoftMaxLink}, ::MCIntegrationVI) alone is true (softmax.jl:22)
+            raise RuntimeError(f"The {likelihood} is not compatible or implemented with the {inference}")
         if optimiser is None:
             optimiser = ADAM(0.01)                       # SVGP.jl:39
         if isinstance(optimiser, bool):
@@ -393,14 +454,14 @@ class SVGP:
             if getattr(self, "_numerical", False):  # (mu, Sigma) travel as set_state's two arguments, the optimiser state with them
                 from .nvi import get_opt_state
 
-                carry["nvi"] = get_opt_state(self)
+                carry["nvi"] = [get_opt_state(self, latent=i) for i in range(self.n_latent)]
                 old = [(None, None, mu, Sig) for mu, Sig in old]
             self._pre_destroy()
             n_opt = C.c_int64()
             self._chk(L.agp_svgp_get_opt_state(self._h, C.byref(n_opt)))
             # the rest of the training state travels too: LogisticSoftMax alpha (carried between minibatches) and the ADAM
             # moments of the kernel-parameter optimisers (the Z optimiser's device state restarts, like a new parameter array)
-            if isinstance(self.likelihood, LogisticSoftMaxLikelihood):
+            if isinstance(self.likelihood, LogisticSoftMaxLikelihood) and not getattr(self, "_numerical", False):
                 carry["alpha"] = self.get_matrix(capi.VEC_ALPHA, 0, self._max_batch)
             if self.k_opt is not None:
                 carry["adam"] = []
@@ -445,7 +506,8 @@ class SVGP:
             if "nvi" in carry:
                 from .nvi import set_opt_state
 
-                set_opt_state(self, *carry["nvi"])
+                for i, st in enumerate(carry["nvi"]):
+                    set_opt_state(self, *st, latent=i)
             if "alpha" in carry:
                 a = torch.as_tensor(carry["alpha"], dtype=self.tdtype, device=dev).contiguous()
                 self._chk(L.agp_svgp_set_lsm_alpha(h, C.c_void_p(a.data_ptr()), a.numel()))

@@ -44,9 +44,10 @@ class VGP(SVGP):
     X: (N, D) array (rows = points; obsdim=2 takes the transposed layout).  `optimiser=True` is ADAM(0.01) (VGP.jl:63, unlike
     SVGP's 0.001).  A Real mean gives ConstantMean, a vector EmpiricalMean (VGP.jl:68-72).  Float64 only.
 
-    inference: AnalyticVI(), or QuadratureVI(...) (nvi.py) for the Logistic, StudentT and Laplace likelihoods.  With QuadratureVI
-    the handle keeps (mu, Sigma) and the optimiser's moments (AGP_FLAG_NUMERICAL), and `optimiser` must be False: the hyper-parameter
-    step through the quadrature ELBO is not built, and the default ADAM(0.01) is refused rather than silently switched off.
+    inference: AnalyticVI(), QuadratureVI(...) (nvi.py) for the Logistic, StudentT and Laplace likelihoods, or MCIntegrationVI(...)
+    for the SoftMax and LogisticSoftMax likelihoods (K latents).  With either of the two the handle keeps (mu, Sigma) and the
+    optimiser's moments per latent (AGP_FLAG_NUMERICAL), and `optimiser` must be False: the hyper-parameter step through the
+    numerical ELBO is not built, and the default ADAM(0.01) is refused rather than silently switched off.
     """
 
     def __init__(self, X, y, kernel, likelihood, inference, *, verbose: int = 0, optimiser=None, atfrequency: int = 1,
@@ -58,16 +59,17 @@ class VGP(SVGP):
         if self._numerical:
             check_numerical("VGP", inference, likelihood, optimiser, T)
             if inference.stoch:
-                raise ValueError("VGP takes the full data set every iteration: use QuadratureVI(), or SVGP for "
-                                 "QuadratureSVI")
+                raise ValueError("VGP takes the full data set every iteration: use " +
+                                 ("MCIntegrationVI(), or SVGP for MCIntegrationSVI" if getattr(inference, "mc", False)
+                                  else "QuadratureVI(), or SVGP for QuadratureSVI"))
         if isinstance(likelihood, GaussianLikelihood):  # VGP.jl:54-56
             raise ValueError("For a Gaussian Likelihood you should directly use the `GP` model or the `SVGP` model for "
                              "large datasets")
         X, optimiser = full_model_args("VGP", "SVGP", inference, X, obsdim, optimiser, mean, T)
-        self._desc_flags = capi.FLAG_FULL | (capi.FLAG_NUMERICAL if self._numerical else 0)
+        self._desc_flags = capi.FLAG_FULL | (capi.FLAG_NUMERICAL if self._numerical else 0) | (capi.FLAG_MC if getattr(inference, "mc", False) else 0)
         super().__init__(kernel, likelihood, inference, X, verbose=verbose, optimiser=optimiser, atfrequency=atfrequency,
                          mean=mean, Zoptimiser=False, T=T, device=device)
-        self.nvi_alphas = []  # QuadratureVI: alpha of every step taken (the backtracking's accepted step length)
+        self.nvi_alphas = []  # QuadratureVI: alpha of every step taken (the backtracking's accepted step length); MCIntegrationVI: a K-tuple
         self.X = X
         yt = self._treat(y)
         if len(yt) != X.shape[0]:

@@ -89,8 +89,10 @@ enum {
   AGP_LIK_BAYESIANSVM = 6,     /* BayesianSVM()                      bayesiansvm.jl:19-23 */
   AGP_LIK_POISSON = 7,         /* PoissonLikelihood(lambda)          poisson.jl:16-24          p0 = initial lambda (state) */
   AGP_LIK_NEGBINOMIAL = 8,     /* NegBinomialLikelihood(r)           negativebinomial.jl:22-27 p0 = r */
-  AGP_LIK_HETEROSCEDASTIC = 9  /* HeteroscedasticLikelihood(lambda)  heteroscedastic.jl:17-47  p0 = initial lambda (state);
+  AGP_LIK_HETEROSCEDASTIC = 9, /* HeteroscedasticLikelihood(lambda)  heteroscedastic.jl:17-47  p0 = initial lambda (state);
                                   n_latent must be 2 (latent 0 = f, latent 1 = g) */
+  AGP_LIK_SOFTMAX = 10         /* SoftMaxLikelihood(K)               softmax.jl:1-48           p0 unused, n_class = K as for
+                                  LogisticSoftMax; no augmentation: AGP_FLAG_MC handles only ("MC INTEGRATION") */
 };
 
 /* ELBO variants: Appendix-A Q2 of SURVEY.md (src/likelihood/logistic.jl:82 uses dot(theta, mu)) */
@@ -106,7 +108,7 @@ enum { AGP_ELBO_CORRECTED = 0, AGP_ELBO_REFERENCE = 1 };
  * src/functions/ELBO.jl:15-21).  With the flag a hyper step leaves the step-side matrices (L, inv(K), K\mu0) as they are and
  * only an explicit agp_svgp_refresh_K (what the host calls where train! starts and ends) recomputes them; without it
  * (default) K is refreshed before the next step. */
-enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4, AGP_FLAG_SAMPLED = 8, AGP_FLAG_NUMERICAL = 16 };
+enum { AGP_FLAG_STALE_K = 1, AGP_FLAG_FULL = 2, AGP_FLAG_EXACT = 4, AGP_FLAG_SAMPLED = 8, AGP_FLAG_NUMERICAL = 16, AGP_FLAG_MC = 32 };
 /* AGP_FLAG_FULL: the handle is the full (non-sparse) model VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85 --
  * one latent of dimension N per n_latent(likelihood), kappa = I, prior K + jitt I on the training inputs themselves.  Create it with
  * m = max_batch = N, stochastic = 0, dtype AGP_F64 (other types: AGP_ERR_UNSUPPORTED); a Gaussian likelihood is refused with
@@ -628,7 +630,7 @@ agp_status agp_svgp_predict_samples(agp_svgp* h, const void* xt, int64_t ldx, in
 
 /* ---- NUMERICAL INFERENCE (AGP_FLAG_NUMERICAL, with AGP_FLAG_FULL or with no other model flag) ---------------------------------------
  * VGP(X, y, kernel, likelihood, QuadratureVI()) (with AGP_FLAG_FULL) and SVGP(kernel, likelihood, QuadratureVI() / QuadratureSVI(B), Z)
- * (without)  src/inference/numericalVI.jl, src/inference/quadratureVI.jl.  Float64, one latent,
+ * (without)  src/inference/numericalVI.jl, src/inference/quadratureVI.jl.  Float64, one latent (K latents with AGP_FLAG_MC: "MC INTEGRATION" below),
  * likelihoods AGP_LIK_LOGISTIC, AGP_LIK_STUDENTT, AGP_LIK_LAPLACE; a Gaussian likelihood is refused as "not compatible"
  * (test/likelihood/gaussian.jl:38,59), every other likelihood, AGP_F32, AGP_FLAG_EXACT and AGP_FLAG_SAMPLED with
  * AGP_ERR_UNSUPPORTED.  The formulas below are the full model's (kappa = I, K~ = 0, rho = 1); the sparse model's follow them.  The handle keeps (mu, Sigma) itself (mu = 0, Sigma = I at
@@ -699,6 +701,64 @@ agp_status agp_svgp_nvi_info(agp_svgp* h, int32_t latent, double* alpha_last_hos
 agp_status agp_svgp_nvi_state(agp_svgp* h, int32_t latent, int32_t set, void* mom_mu, void* mom_sigma, int64_t* t_host);
 agp_status agp_quad_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void* y, const void* mu, const void* var, int64_t n_pts,
                                  const double* nodes_host, const double* weights_host, int32_t n, void* ell, void* g, void* h);
+
+/* ---- MC INTEGRATION (AGP_FLAG_NUMERICAL | AGP_FLAG_MC, with or without AGP_FLAG_FULL) ---------------------------------------------------
+ * VGP(X, y, kernel, likelihood, MCIntegrationVI()) and SVGP(kernel, likelihood, MCIntegrationVI() / MCIntegrationSVI(B), Z)
+ * src/inference/MCVI.jl, for the multi-class likelihoods AGP_LIK_SOFTMAX (src/likelihood/softmax.jl) and AGP_LIK_LOGISTICSOFTMAX
+ * (src/likelihood/logisticsoftmax.jl:144-193): Float64, n_latent = n_class = K with 2 <= K <= 64 (one wave holds the K latents of a
+ * draw).  AGP_FLAG_MC without AGP_FLAG_NUMERICAL, any other likelihood, K = 1 and AGP_F32 are AGP_ERR_UNSUPPORTED with a message.
+ * The handle is a numerical handle with K latents: each keeps its own (mu_k, Sigma_k), optimiser moments, kept factor, alpha and
+ * counters; the step counter t is shared.  One step, the estimator restated in its intended form:
+ *     f_sk = mu_f,ik + sqrt(max(var_f,ik, 0)) eps_sk ,  s = 1 .. nMC          eps: ONE nMC x K table per step, shared by every point of
+ *                                                                             the batch (grad_expectations!, MCVI.jl:93-107)
+ *     ell_i = (1 / nMC) sum_s log p(c_i | f_s) ;  g_ik = (1 / nMC) sum_s d log p / d f_k ;  h_ik = (1 / nMC) sum_s d2 log p / d f_k^2
+ *     grad_E_mu = g ,  grad_E_Sigma = h / 2                                   (numericalVI.jl:98-99 with nu = -g, lambda = h)
+ *   and every latent k then takes exactly the step of NUMERICAL INFERENCE with (g_.k, h_.k), its own alpha_k included
+ *   (numericalVI.jl:158-179 maps over the latents).  ELBO = rho sum_i ell_i - sum_k GaussianKL_k.
+ *   The closed forms grad_samples! reduces to, with c the class of the point and y its one-hot vector:
+ *     SoftMax          s = softmax(f):  log p = f_c - logsumexp(f) ;  d_k = y_k - s_k ;  d2_k = -s_k (1 - s_k)
+ *     LogisticSoftMax  sg_k = logistic(f_k), s_k = sg_k / sum_j sg_j:  log p = log sg_c - log sum_j sg_j ;
+ *                      d_k = (1 - sg_k)(y_k - s_k) ;  d2_k = (1 - sg_k) [-sg_k (y_k - s_k) - s_k (1 - s_k)(1 - sg_k)]
+ *   evaluated stably: logsumexp subtracts the maximum, log sg(f) = -softplus(-f) (and log s_c = -log1p(sum of the others / sg_c)
+ *   where c is the largest entry), 1 - sg(f) = sg(-f), and 1 - s_k of the largest
+ *   entry is the sum of the OTHER entries over the total (the first maximum counts as the largest), so that ell, g, h keep their
+ *   relative accuracy where a class probability approaches one (|mu| = 30, var = 0).
+ *   clipping of the reference's MCIntegrationVI object is stored there and read by no MC code: it does not reach this library.
+ * RANDOM STREAMS, continued (streams 0 and 1 keep their Gibbs meaning):
+ *   eps_sk of (seed, t, stream) is the Normal of block 0 -- two uniforms (a, b) of the Philox counter (c0, c1, c2, c3) =
+ *   (s K + k, t, stream, 0), key = seed, value sqrt(-2 log a) cos(2 pi b) -- with
+ *     stream 2   the gradient draw of step t; t = 1, 2, ... is the step number, which is also ADAM's t
+ *     stream 3   the draw of an ELBO evaluated after t steps (t = 0 before the first): repeated evaluations of an unchanged model agree
+ *   On these two streams log and cos are not the device's math library but the following double arithmetic, one IEEE operation per
+ *   written operation and no contraction, so that a host program reproduces the table bit for bit (tests/_mcvi_ref.py does):
+ *     log a:  a = m 2^e (frexp), and m < 0.7071067811865476: m = 2 m, e = e - 1;  q = (m - 1) / (m + 1), z = q q,
+ *             P = 1/23; for d = 21, 19, ..., 3, 1: P = P z + 1/d;  log a = e 0.6931471805599453 + (2 q) P
+ *     cos 2 pi b:  r = b > 1/2 ? 1 - b : b;  r > 1/4: r = 1/2 - r and the sign flips;  r > 1/8: x = 6.283185307179586 (1/4 - r),
+ *             z = x x, P = 1/17!; P = P z - 1/15!; P = P z + 1/13!; ... ; P = P z + 1; value x P (the sine series);  else
+ *             x = 6.283185307179586 r, z = x x, P = 1/16!; P = P z - 1/14!; ... ; P = P z + 1 (the cosine series)
+ * agp_svgp_mcvi_configure installs nMC (1 <= nMC <= 65536), the seed, natural != 0 for the natural gradient, and the optimiser, with
+ *   the argument checks of agp_svgp_nvi_configure.  It is refused (AGP_ERR_UNSUPPORTED) on a handle without AGP_FLAG_MC, as
+ *   agp_svgp_nvi_configure is on one with it; agp_svgp_nvi_step before it is AGP_ERR_INVALID.
+ * On such a handle the entry points of NUMERICAL INFERENCE keep their meaning, with
+ *   nvi_step        y int32[N]: the 0-based class index, read at idx (the form the LogisticSoftMax CAVI step takes); an index
+ *                   outside [0, K) is latched and reported by agp_svgp_check_status as AGP_ERR_LABELS
+ *   nvi_info / nvi_state / get_state / set_state    latent in [0, K) (else AGP_ERR_INVALID); t of nvi_state is the shared counter
+ *   elbo            stream 3 at the handle's t
+ *   predict_f       T[K][n_t];  predict_y  int32 argmax_k mu_f,k (the first maximum);  proba_y  out0 T[n_t][K], the link at the mean
+ *                   (multiclass.jl:96-117): softmax(mu_f) / the normalised logistic; out1 is not written
+ * agp_mc_normals writes the table double[nMC][K] of (seed, t, stream) to device memory (0 <= t < 2^32, nMC K < 2^32).
+ * agp_mc_expectations is the expectation kernel on caller-supplied moments outside any model: lik->kind one of the two likelihoods,
+ *   K = lik->n_class in [2, 64], y_class int32[n_pts] (0-based), mu, var, g, h double[K][n_pts], ell double[n_pts], all device;
+ *   synchronises; a class index outside [0, K): AGP_ERR_LABELS.
+ * The kernel: one wave per point, the lanes of a wave are (draw, latent) pairs -- 64 / P draws at a time, P the power of two >= K --
+ *   so max and sum over k are P-lane butterflies and every lane owns one accumulator of g_k and h_k; the table is staged through
+ *   LDS in tiles of 2048 doubles shared by the 4 points of a workgroup.  The order of summation is fixed by (nMC, K) alone. */
+agp_status agp_svgp_mcvi_configure(agp_svgp* h, int32_t nMC, uint64_t seed, int32_t natural, int32_t opt_kind, double eta, double p1,
+                                   double p2, double eps);
+agp_status agp_mc_normals(agp_ctx* ctx, uint64_t seed, int64_t t, int32_t stream, int32_t nMC, int32_t K, void* out);
+agp_status agp_mc_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void* y_class, const void* mu, const void* var,
+                               int64_t n_pts, int32_t K, int32_t nMC, uint64_t seed, int64_t t, int32_t stream, void* ell, void* g,
+                               void* h);
 
 /* ---- multi-GPU: one process per GPU, collectives behind the ABI --------------------------------
  * The path shards in two ways and both reduce to in-place SUM all-reduces of library-owned device buffers:

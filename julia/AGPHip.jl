@@ -80,6 +80,8 @@ const AGP_FLAG_FULL = Int32(2)     # VGP: the full model, kappa = I, m = N, Z = 
 const AGP_FLAG_EXACT = Int32(4)    # GP: exact regression with Analytic(), together with AGP_FLAG_FULL (agp_hip.h)
 const AGP_FLAG_SAMPLED = Int32(8)  # MCGP: Gibbs sampling of the augmented full model, together with AGP_FLAG_FULL (agp_hip.h)
 const AGP_FLAG_NUMERICAL = Int32(16)  # QuadratureVI (with AGP_FLAG_FULL: VGP; alone: SVGP): the handle keeps (mu, Sigma) and the optimiser's moments (agp_hip.h)
+const AGP_FLAG_MC = Int32(32)  # MCIntegrationVI over K latents, together with AGP_FLAG_NUMERICAL (agp_hip.h, "MC INTEGRATION")
+const AGP_LIK_SOFTMAX = Int32(10)  # SoftMaxLikelihood(K): no augmentation, AGP_FLAG_MC handles only (softmax.jl)
 const AGP_SHARD_LATENT, AGP_SHARD_BATCH = Int32(0), Int32(1)
 
 struct AGPError <: Exception
@@ -1101,6 +1103,42 @@ function nvi_configure!(hm::HipModel)
                         (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Float64, Float64, Float64),
                         hm.h, length(x), x, w, AGP.isnatural(inf) ? 1 : 0, kind, Float64(o.eta), p1, p2, ϵ))
     return hm
+end
+# ---- Monte-Carlo integration (MCIntegrationVI / MCIntegrationSVI, src/inference/MCVI.jl): the entry points of a handle created with
+# AGP_FLAG_NUMERICAL | AGP_FLAG_MC (likelihood AGP_LIK_SOFTMAX or the LogisticSoftMax one, n_latent = K) and the two context-level ones.
+# The table of normals of step t is a function of (seed, t) alone (agp_hip.h, "MC INTEGRATION"); nvi_step, nvi_info(latent) and
+# nvi_state(latent) then work per latent.  The models of the reference are not yet dispatched onto these handles by this shim.
+function mcvi_configure!(hm::HipModel, seed::Integer)
+    inf = AGP.inference(hm.model)
+    o = inf.vi_opt[1].optimiser
+    kind, p1, p2, ϵ = o isa Optimisers.ADAM ? (0, Float64(o.beta[1]), Float64(o.beta[2]), 1e-8) :
+                      o isa Optimisers.Descent ? (1, 0.0, 0.0, 0.0) :
+                      o isa Optimisers.Momentum ? (2, Float64(o.rho), 0.0, 0.0) :
+                      error("MCIntegrationVI optimiser $(typeof(o)) is not available on the device (ADAM, Descent, Momentum are)")
+    check(hm.ctx, ccall((:agp_svgp_mcvi_configure, libagp), Int32,
+                        (Ptr{Cvoid}, Int32, UInt64, Int32, Int32, Float64, Float64, Float64, Float64),
+                        hm.h, inf.nMC, UInt64(seed), AGP.isnatural(inf) ? 1 : 0, kind, Float64(o.eta), p1, p2, ϵ))
+    return hm
+end
+# eps[nMC, K] of (seed, t, stream): stream 2 the gradient draw of step t, stream 3 the ELBO after t steps
+function mc_normals(hm::HipModel, seed::Integer, t::Integer, stream::Integer, nMC::Integer, K::Integer)
+    ctx = ensure_ctx!(hm)
+    out = ROCMatrix{Float64}(undef, K, nMC)                      # (column-major K x nMC = the library's double[nMC][K])
+    check(ctx, ccall((:agp_mc_normals, libagp), Int32, (Ptr{Cvoid}, UInt64, Int64, Int32, Int32, Int32, Ptr{Cvoid}),
+                     ctx, UInt64(seed), t, stream, nMC, K, pointer(out)))
+    return permutedims(Array(out))
+end
+# (ell [n], g [n x K], h [n x K]) of the expectation kernel on given moments mu, var [n x K]; y_class 0-based
+function mc_expectations(hm::HipModel, lik::LikDesc, y_class::AbstractVector{<:Integer}, mu::AbstractMatrix, var::AbstractMatrix,
+                         nMC::Integer, seed::Integer, t::Integer, stream::Integer=2)
+    ctx = ensure_ctx!(hm)
+    n, K = size(mu)
+    yd, md, vd = ROCVector{Int32}(y_class), ROCMatrix{Float64}(mu), ROCMatrix{Float64}(var)   # (column-major n x K = double[K][n])
+    ell, g, h = ROCVector{Float64}(undef, n), similar(md), similar(md)
+    check(ctx, ccall((:agp_mc_expectations, libagp), Int32,
+                     (Ptr{Cvoid}, Ref{LikDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, UInt64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx, lik, pointer(yd), pointer(md), pointer(vd), n, K, nMC, UInt64(seed), t, stream, pointer(ell), pointer(g), pointer(h)))
+    return Array(ell), Array(g), Array(h)
 end
 # (mu, Sigma) of the device -> the reference object; the natural parameters follow from them (posterior.jl)
 function pull_nvi_posterior!(hm::HipModel{T}) where {T}
