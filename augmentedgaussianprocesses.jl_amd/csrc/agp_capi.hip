@@ -2696,7 +2696,8 @@ struct Svgp : SvgpBase {
   agp_status hyper_alloc() {
     if (hyH1) return AGP_OK;
     if (D > HB_MAXD) {
-      ctx->err = "hyper-gradient: input dimension above HB_MAXD";
+      ctx->err = "hyper-gradient: input dimension D = " + std::to_string(D) + " is above the supported maximum of " +
+                 std::to_string(HB_MAXD) + " (HB_MAXD, agp_hyper.h)";
       return AGP_ERR_UNSUPPORTED;
     }
     // (partial sums per RT x 64 tile of a backward pass: k_kernel_backward, HB_RT rows per workgroup)

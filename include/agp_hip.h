@@ -372,7 +372,13 @@ agp_status agp_svgp_step_local(agp_svgp* h, const void* x, int64_t ldx, const vo
  *   hyper_configure : optimiser=ADAM(kernel_eta) / Zoptimiser=ADAM(z_eta) of SVGP(...)  (SVGP.jl:39-42); 0 disables
  *   hypergrad       : the gradient only (parity): dscale_host[D] per input dimension (a ScaleTransform's single
  *                     parameter receives their sum), dZ device T[m][D] (nullable)
- *   get_kernel      : current variance and per-dimension scales */
+ *   get_kernel      : current variance and per-dimension scales
+ * Limits of hypergrad / hyper_step (sparse and AGP_FLAG_FULL handles alike): the input dimension D must be at most 64 (the backward
+ * pass through the kernel matrix stages 32 dimensions at a time and keeps two such chunks per tile: HB_MAXD, agp_hyper.h), and the
+ * kernel must be SqExponential, Matern32 or Matern52 (the ExponentialKernel is not differentiable at zero distance).  Otherwise
+ * both return AGP_ERR_UNSUPPORTED with the reason in agp_last_error, before anything is launched: dvariance_host, dscale_host and
+ * dZ are not touched, and the handle goes on taking steps and predicting.  Steps, ELBO and
+ * predictions themselves have no such limit on D.  Pinned at D = 1, 31, 32, 33, 64 and 65 by tests/test_gpu_hyper_edges.py. */
 agp_status agp_svgp_hyper_configure(agp_svgp* h, int32_t opt_kernel, double kernel_eta, int32_t opt_Z, double z_eta,
                                     double adam_b1, double adam_b2, double adam_eps);
 /*   hyper_rule      : which Optimisers.jl rule `optimiser` / `Zoptimiser` are (the reference hands whatever rule it is given to
