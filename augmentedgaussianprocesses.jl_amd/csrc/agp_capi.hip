@@ -747,6 +747,9 @@ static agp_status potrf_fused(agp_ctx* c, T* A, int64_t ld, int64_t n, T* X, int
       *p_done = true;
     }
     unsigned long long* const trace = nullptr;  // (per-tile timestamps: the TRACE instantiation of k_chol_dag, a development aid)
+    // step_inst selects the STEP instantiations below; for a single problem in fp64 that is also the launch-uniform choice of the
+    // slot format without X21 and of the block substitution (dag_block_subst, agp_chol.h) -- every kernel of the launch, merged
+    // or split, is instantiated with the same T / STEP / BATCH and so reads the same decision
     const bool step_inst = nx == 0 && !do_x && !want_l;
     DagSync ds{};
     if (ssync) {
@@ -6462,6 +6465,8 @@ static agp_status bb_diag_bench(agp_ctx* ctx, int blocks, int reps, double* us) 
   HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
   *us = ms * 1e3 / reps;
   {  // residuals of block 0 (development aid): |L L' - A|, |X L - I|, strict-upper leakage
+     // (VAR 13, "2-level, no X21": the inverse part is [[X11, 0], [L21, X22]] -- |X11 L11 - I|, |X22 L22 - I|, the L21 block exact)
+    constexpr bool nox21 = VAR == 13;
     std::vector<T> o(2 * TILE * TILE);
     HIPCHK(ctx, hipMemcpy(o.data(), out, sizeof(T) * 2 * TILE * TILE, hipMemcpyDeviceToHost));
     const T* Lh = o.data();
@@ -6470,12 +6475,14 @@ static agp_status bb_diag_bench(agp_ctx* ctx, int blocks, int reps, double* us) 
     for (int i = 0; i < TILE; ++i)
       for (int j = 0; j < TILE; ++j) {
         double s1 = 0, s2 = 0;
+        const int kb = nox21 ? (i / 32) * 32 : 0, ke = nox21 ? kb + 32 : TILE;
         for (int k = 0; k < TILE; ++k) {
           s1 += (double)Lh[i * TILE + k] * (double)Lh[j * TILE + k];
-          s2 += (double)Xh[i * TILE + k] * (double)Lh[k * TILE + j];
+          if (k >= kb && k < ke) s2 += (double)Xh[i * TILE + k] * (double)Lh[k * TILE + j];
         }
         e1m = std::max(e1m, std::abs(s1 - (double)h[i * TILE + j]));
-        e2m = std::max(e2m, std::abs(s2 - (i == j ? 1.0 : 0.0)));
+        if (nox21 && i / 32 != j / 32) e2m = std::max(e2m, std::abs((double)Xh[i * TILE + j] - (j < i ? (double)Lh[i * TILE + j] : 0.0)));
+        else e2m = std::max(e2m, std::abs(s2 - (i == j ? 1.0 : 0.0)));
         if (j > i) e3m = std::max(e3m, std::abs((double)Lh[i * TILE + j]) + std::abs((double)Xh[i * TILE + j]));
       }
     const double tol = sizeof(T) == 8 ? 1e-12 : 1e-4;
@@ -6706,6 +6713,7 @@ agp_status agp_dev_diag_bench(agp_ctx* ctx, int32_t dtype, int32_t variant, int3
     case 20: return bb_diag_bench<double, 10>(ctx, blocks, reps, us);
     case 22: return bb_diag_bench<double, 11>(ctx, blocks, reps, us);
     case 24: return bb_diag_bench<double, 12>(ctx, blocks, reps, us);
+    case 26: return bb_diag_bench<double, 13>(ctx, blocks, reps, us);  // 2-level without the off-diagonal block of the inverse
     default: return AGP_ERR_INVALID;
   }
 }

@@ -384,6 +384,8 @@ __device__ __forceinline__ void factor_diag_tile512(T* bufA, T* bufB, T* sc, T* 
 // Two-level variant of the diagonal-tile factorisation: the 64x64 tile is split into 32x32 blocks
 //   [A11 . ; A21 A22] :  (L11, X11) = elim(A11) ; L21 = A21 X11' ; S = A22 - L21 L21' ; (L22, X22) = elim(S) ;
 //   X21 = -X22 (L21 X11)
+// NOX21 leaves that last line out: the caller gets [[X11, 0], [L21, X22]] in bufB, which is all a product T X' needs when it is
+// formed by block substitution (subst_tile below) -- two of the four products and two barriers less on the serial path.
 // The two eliminations use the same 4-column rounds with 2x2 cyclic ownership (about half the per-round work of the
 // 4x4 ownership: the redundant per-thread transforms shrink with the sub-block count); the glue is four 32^3 MFMA products.
 // ---------------------------------------------------------------------------------------------------
@@ -440,7 +442,7 @@ __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* 
   __syncthreads();
 }
 
-template <typename T, typename H, int PIV = AGP_PIVOT_ALG>
+template <typename T, typename H, int PIV = AGP_PIVOT_ALG, bool NOX21 = false>
 __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T* piv, int32_t* info, int64_t col0,
                                                       int64_t nvalid, H& hook) {
   const int tid = threadIdx.x;
@@ -451,8 +453,9 @@ __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T
   typedef typename Mfma<T>::acc_t acc_t;
   NoHook nohook;
   elim_block32<T, NoHook, PIV>(bufA, bufB, 0, sc, piv, act, ti, tj, nohook);
-  // L21 = A21 X11' -> scratch in bufB[32:64, 0:32] (free until X21 is formed at the end): no barrier between reading A21 and
-  // writing the result.  The other waves clear the upper-right blocks meanwhile (input garbage in bufA, nothing yet in bufB).
+  // L21 = A21 X11' -> scratch in bufB[32:64, 0:32] (free until X21 is formed at the end; NOX21: it stays there, that IS the
+  // output format): no barrier between reading A21 and writing the result.  The other waves clear the upper-right blocks
+  // meanwhile (input garbage in bufA, nothing yet in bufB).
   acc_t acc;
 #pragma unroll
   for (int r = 0; r < 4; ++r) acc[r] = T(0);
@@ -486,22 +489,24 @@ __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T
   }
   __syncthreads();
   elim_block32<T, H, PIV>(bufA, bufB, 32, sc, piv, act, ti, tj, hook);  // hook rounds 0..7 of the second half
-  // P = L21 X11  -> sc (32 x 32, free after the rounds)
+  if (!NOX21) {
+    // P = L21 X11  -> sc (32 x 32, free after the rounds)
 #pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = T(0);
-  if (mw) {
-    acc = mma_blk32<T, true>(bufA + 32 * LDP, bufB, acc, wr, wc, lane, false);
+    for (int r = 0; r < 4; ++r) acc[r] = T(0);
+    if (mw) {
+      acc = mma_blk32<T, true>(bufA + 32 * LDP, bufB, acc, wr, wc, lane, false);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sc[(wr * 16 + Mfma<T>::row(lane, r)) * 32 + wc * 16 + (lane & 15)] = acc[r];
-  }
-  __syncthreads();
-  // X21 = -X22 P   -> bufB[32:64, 0:32] ; bad pivots reported next to it
+      for (int r = 0; r < 4; ++r) sc[(wr * 16 + Mfma<T>::row(lane, r)) * 32 + wc * 16 + (lane & 15)] = acc[r];
+    }
+    __syncthreads();
+    // X21 = -X22 P   -> bufB[32:64, 0:32] ; bad pivots reported next to it
 #pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = T(0);
-  if (mw) {
-    acc = mma_blk32<T, true, 32>(bufB + 32 * LDP + 32, sc, acc, wr, wc, lane, true);
+    for (int r = 0; r < 4; ++r) acc[r] = T(0);
+    if (mw) {
+      acc = mma_blk32<T, true, 32>(bufB + 32 * LDP + 32, sc, acc, wr, wc, lane, true);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) bufB[(32 + wr * 16 + Mfma<T>::row(lane, r)) * LDP + wc * 16 + (lane & 15)] = acc[r];
+      for (int r = 0; r < 4; ++r) bufB[(32 + wr * 16 + Mfma<T>::row(lane, r)) * LDP + wc * 16 + (lane & 15)] = acc[r];
+    }
   }
   if (blockDim.x <= 256) {  // nobody was free to clear the upper-right blocks earlier
     for (int e = tid; e < 32 * 32; e += blockDim.x) {
@@ -523,7 +528,8 @@ __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T
       }
     }
   }
-  __syncthreads();
+  // (NOX21 in a 512-thread workgroup: nothing was written to LDS since the barrier that ends the second elimination)
+  if (!NOX21 || blockDim.x <= 256) __syncthreads();
 }
 
 template <typename T>
@@ -1512,6 +1518,53 @@ __device__ __forceinline__ typename Mfma<T>::acc_t mma_tile16(const T* Ar, const
   return acc;
 }
 
+// Ts <- Ts X' in place (64 x 64 in LDS, [r][k] stride LDP) for a lower-triangular X = [[X11, 0], [X21, X22]] of which only the
+// step-launch slot format Xs = [[X11, 0], [L21, X22]] is at hand (factor_diag_tile_2lvl<.., NOX21>; X^-1 = [[L11, 0], [L21, L22]]):
+// a forward substitution in two 32-column blocks,
+//     L1 = T1 X11'   ->   U = T2 - L1 L21'   ->   L2 = U X22'          (T = [T1 | T2],  T X' = [L1 | L2])
+// Every stage has eight 16 x 16 result tiles, one per wave: row tile w & 3, column tile w >> 2, so that the two waves of a SIMD take
+// one short (k < 16) and one long (k < 32) tile of the triangular stages -- 40 MFMAs per SIMD instead of the 64 of mma8.  All 512
+// threads call; `after_first` runs between the first stage's product and its store and must contain a workgroup barrier (the chain
+// gives its signal there).  U is parked in the upper half of Xs (X11 and the zero block next to it: both dead once every wave is
+// past the first stage), so the last stage has no wave reading what another one overwrites: Xs is scratch to the caller afterwards.
+// The caller puts a barrier between the return and its first read of Ts.  G (nullable): hand-over slot that receives the result
+// tile by tile as it becomes final (coherent stores).
+template <typename T, typename F>
+__device__ __forceinline__ void subst_tile(T* Ts, T* Xs, T* G, F after_first) {
+  typedef typename Mfma<T>::acc_t acc_t;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ri = wave & 3, cj = wave >> 2;
+  T* rowt = Ts + 16 * ri * LDP;
+  T* own1 = rowt + 16 * cj;
+  T* own2 = own1 + 32;
+  const T* xlow = Xs + (32 + 16 * cj) * LDP;  // rows 32 + 16 cj .. of the slot: [L21 | X22]
+  T* urow = Xs + 16 * (ri & 1) * LDP + 32 * (ri >> 1);  // U, rows 16 ri ..: row tiles 0, 1 over X11, row tiles 2, 3 over the zero block
+  auto emit = [&](int col0, acc_t v) {
+    if (G) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        __hip_atomic_store(G + (16 * ri + Mfma<T>::row(lane, r)) * TILE + col0 + (lane & 15), v[r], __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+  };
+  acc_t a;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a[r] = T(0);
+  a = mma_tile16<T>(rowt, Xs + 16 * cj * LDP, 16 * (cj + 1), a, false, lane);
+  after_first();  // every wave has read T1
+  acc_store16<T>(own1, a, lane);
+  emit(16 * cj, a);
+  __syncthreads();
+  a = acc_load16<T>(own2, lane);  // own tile of T2: nobody else touches it in this stage
+  a = mma_tile16<T>(rowt, xlow, 32, a, true, lane);
+  acc_store16<T>(urow + 16 * cj, a, lane);
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) a[r] = T(0);
+  a = mma_tile16<T>(urow, xlow + 32, 16 * (cj + 1), a, false, lane);
+  acc_store16<T>(own2, a, lane);
+  emit(32 + 16 * cj, a);
+}
+
 // side job of the chain workgroup, stepped by the idle waves 4-7 during the second half of a tile factorisation: look once
 // whether the two feeder tiles of the next column are parked, then move them into LDS one tile per round
 template <typename T>
@@ -1833,6 +1886,14 @@ constexpr long long CHAIN_GO_TICKS = 4LL * 100000000LL;
 #endif
 // (with the prologue a tile workgroup stages four LDS tiles: 135 KB in f64 = one workgroup per CU whatever the registers,
 //  68 KB in f32 = two)
+// Slot format of X_k in a launch, ONE decision for the chain and every tile of it (merged or split, all ROLEs): the CAVI step's
+// single-problem fp64 launches hand over [[X11, 0], [L21, X22]] and form every T X_k' by block substitution (subst_tile); launches
+// with identity rows or product workgroups (never STEP), batched launches and fp32 keep the full inverse and the plain product.
+// (fp32: the split tile kernel's register bound has not been checked with the substitution's extra addressing.)
+template <typename T, bool STEP, bool BATCH>
+constexpr bool dag_block_subst() {
+  return STEP && !BATCH && sizeof(T) == 8;
+}
 template <typename T, int ROLE, bool PRO>
 constexpr int dag_min_waves() {
   return ROLE != 2 ? 1 : PRO ? (sizeof(T) == 8 ? 2 : 4) : (sizeof(T) == 8 ? AGP_TILES_WAVES_F64 : AGP_TILES_WAVES_F32);
@@ -1902,6 +1963,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   //      bit 1: the factor L is wanted in its real home A as well (K's factor, the potrf entry points); the CAVI step only
   //             consumes the extension rows W, v and never reads L itself, so its launches skip those stores
   const int64_t nx = STEP ? 0 : nx_;
+  constexpr bool SUBST = dag_block_subst<T, STEP, BATCH>();  // X_k travels without its off-diagonal block (nobody reads X_k as such)
   const int write_x = STEP ? 0 : (opts & 1);
   const bool store_l = STEP ? false : (opts & 2) != 0;
   // nb > 1: nb independent problems of the same shape (the latents of a small multi-class model) in ONE launch, their
@@ -2333,7 +2395,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       pf.ld_i = (int)ld;
       pf.coh = ROLE == 1;
       if (tid == 0) pf_ok = pf_bad = 0;
-      factor_diag_tile_2lvl<T, ChainPrefetch<T>>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
+      factor_diag_tile_2lvl<T, ChainPrefetch<T>, AGP_PIVOT_ALG, SUBST>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
       DAG_TRC(k, 2);
       PRO_TS(512 + k);
       {  // X_k out (coherent): all LDS reads first, then the stores back to back (a read-store-read-store loop exposed the
@@ -2388,7 +2450,18 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       //   tile pair {3, 0} or {2, 1} (20 MFMAs each way)
       typedef typename Mfma<T>::acc_t acc_t;
       const int lane = tid & 63, wave = tid >> 6;
-      {
+      if (SUBST) {
+        //   L = T X_k' by block substitution from [[X11, 0], [L21, X22]] (same 40 MFMAs per SIMD as the triangular product below, in
+        //   three stages); X_k is published behind the first stage, as below
+        subst_tile<T>(bufC, bufB, HL + ((k + 1) * nt + k) * SLOT, [&] {
+          if (!late_feed) {
+            dag_signal(xready + k * DAG_FS, epoch);
+            DAG_TRC(k, 3);
+          } else {
+            __syncthreads();
+          }
+        });
+      } else {
         const int ri = wave >> 1, cA = (wave & 1) ? 2 : 3, cB = 3 - cA;
         acc_t oa, ob;
 #pragma unroll
@@ -2526,8 +2599,14 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   __syncthreads();
   DAG_TR(6);
   Acc8<T> out;
-  out.zero();
-  mma8<T>(bufA, bufB, out);
+  if (SUBST) {  // 40 instead of 64 MFMAs per SIMD, in place in bufA; the result then moves into the product's accumulator layout
+    subst_tile<T>(bufA, bufB, (T*)nullptr, [] { __syncthreads(); });
+    __syncthreads();
+    acc8_foreach<T>(out, [&](int r, int cc, T& val) { val = bufA[r * LDP + cc]; });
+  } else {
+    out.zero();
+    mma8<T>(bufA, bufB, out);
+  }
   {
     T* hs = HL + (R * nt + c) * SLOT;
     acc8_foreach<T>(out, [&](int r, int cc, T& val) {
@@ -2547,9 +2626,11 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   if (epi_row) {
     // own tile W(R, nt-1) (still in the accumulators) through LDS, the last piece of v from the tile of the [eta1' ; 0] row in
     // this block column (solved by its own workgroup at about the same time: its slot validates itself), then the 64 rows
-    __syncthreads();
-    acc8_foreach<T>(out, [&](int r, int cc, T& val) { bufA[r * LDP + cc] = val; });
-    __syncthreads();
+    if (!SUBST) {  // (SUBST: the substitution left the tile in bufA, behind a barrier)
+      __syncthreads();
+      acc8_foreach<T>(out, [&](int r, int cc, T& val) { bufA[r * LDP + cc] = val; });
+      __syncthreads();
+    }
     epi_acc(bufA, HL + ((nt + ne - 1) * nt + c) * SLOT);
     STRACE(STRACE_EXT + 4 * (R - nt) + 2);
     const int64_t i = (R - nt) * TILE + er;
@@ -2646,6 +2727,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_diag_bench(const T* __restrict
     else if (VAR == 5) factor_diag_tile_2lvl<T, NoHook, 4>(bufA, bufB, sc, piv, info, 0, 64, nh);
     else if (VAR == 6) factor_diag_tile_2lvl<T, NoHook, 5>(bufA, bufB, sc, piv, info, 0, 64, nh);
     else if (VAR == 8) factor_diag_tile_panel<T, NoHook>(bufA, bufB, sc, piv, info, 0, 64, nh);
+    else if (VAR == 13) factor_diag_tile_2lvl<T, NoHook, 0, true>(bufA, bufB, sc, piv, info, 0, 64, nh);  // 2-level, no X21
     else if (VAR >= 9 && VAR <= 12) factor_diag_tile_panel<T, NoHook, VAR - 8>(bufA, bufB, sc, piv, info, 0, 64, nh);
     else {  // VAR 7: the harness alone (tile reload + barrier)
     }

@@ -103,6 +103,12 @@ def table(dumps, last=200, nt=16, ne=17):
         out.append(f"  launch t+1: first workgroup start           {med(np.nanmin(pus(cur[:, WG0:WG1]), axis=1)):8.2f}")
         out.append(f"              tile (0,0) ready (eta2 step)    {med(pus(cur[:, 4])):8.2f}")
         out.append(f"              factor(0) done                  {med(pus(cur[:, 512])):8.2f}")
+        f = cur[:, 512:512 + nt]  # the chain, block column by block column
+        d = np.array([med(c) for c in (np.diff(f, axis=1) * 0.01).T])
+        out.append(f"== {os.path.basename(dump)}: {len(cur)} launches; median us between the ends of consecutive tile eliminations ==")
+        out.append(f"  factor(k) - factor(k-1), k = 1..{nt - 1}: " + " ".join(f"{x:6.2f}" for x in d))
+        out.append(f"  mean over k {np.mean(d):6.3f}   factor({nt - 1}) - factor(0) {med(f[:, nt - 1] - f[:, 0]) * 0.01:8.2f}")
+        out.append(f"  chain start -> factor(0) done {med(f[:, 0] - cur[:, 0]) * 0.01:8.2f}")
         rows += out
     return "\n".join(rows)
 
