@@ -1,9 +1,7 @@
 // agp_capi.hip -- C ABI of libagp_hip.so (see include/agp_hip.h).  Host-side orchestration of the gfx950 kernels in
-// agp_linalg.h / agp_cavi.h: one process per GPU, everything enqueued on the caller's HIP stream.
-#include "../../include/agp_hip.h"
-
-#include <hip/hip_runtime.h>
-
+// agp_linalg.h / agp_cavi.h: one process per GPU, everything enqueued on the caller's HIP stream.  This file holds the model
+// classes and the extern "C" surface; the layers below them are agp_ctx.h (context, error macros), agp_chol_host.h (Cholesky
+// driver) and agp_blas_host.h (GEMM / SYRK / kernel-matrix launchers), all part of this one translation unit.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -18,1175 +16,13 @@
 #include "agp_linalg.h"
 #include "agp_nvi.h"
 #include "agp_rand.h"
-
-using namespace agp;
-
-struct agp_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  int32_t* dag_flags = nullptr;   // tile / x-ready / abort flags of the task-graph factorisation (k_chol_dag), epoch-stamped
-  int64_t dag_cap = 0;
-  int32_t dag_epoch = 0;
-  // sentinel-filled hand-over area of the task graph (set 0; see Dirty below for how it gets refilled)
-  void* hset[2] = {nullptr, nullptr};
-  size_t hbytes = 0;
-  int htype = -1;  // sizeof(T) the sets were filled for
-  // lazy refill: a launch leaves its set "dirty"; the next fused kappa' diag(w) kappa launch on the same stream refills it with
-  // rider workgroups (no extra launch, stream or event); whoever needs a dirty set before that refills it inline
-  struct Dirty {
-    bool on = false;
-    int64_t used = 0, stride = 0;
-    int nb = 0;
-  } h_dirty[2];
-  int h_step_set = 0;  // the CAVI-step launches with a prologue alternate between the sets and refill each other's (ProArgs::fill)
-  void* tri_scratch = nullptr;    // n x n scratch of the recursive-doubling triangular inverse
-  size_t tri_bytes = 0;
-  // fallback of the task-graph factorisation (k_chol_safe): grid-barrier words, retry counter, number of CUs; once a retry has
-  // been seen by the host (any synchronising call) the task graph is not used again on this context
-  void* kmm_scratch = nullptr;  // scaled copy + squared norms of the Y side of a kernel matrix whose Y is not a cached Z
-  size_t kmm_bytes = 0;
-  void* bal_ws = nullptr;       // partial tiles of the balanced triangular product (k_xtx_bal)
-  size_t bal_bytes = 0;
-  unsigned* safe_bar = nullptr;
-  int32_t* safe_retries = nullptr;
-  int n_cu = 0;
-  bool dag_off = false;
-  int64_t dag_retries_seen = 0;
-  // probation: after a lost dependency the context factors by plain launches for `dag_cooldown` CAVI steps, then tries the task
-  // graph again (whoever shared the GPU may be gone); every further loss makes the next pause four times longer
-  int64_t dag_cooldown = 0, dag_backoff = 512;
-  // blocked factorisation of large matrices: side stream of the look-ahead (trailing update of the far columns next to the next
-  // group's diagonal block and panel), fork / join events, inverses of the current group's diagonal tiles
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  void* chol_li = nullptr;
-  size_t chol_li_bytes = 0;
-  // split task-graph launches (k_chol_dag ROLE 1 / 2): the chain kernels' own high-priority stream, the word the tile kernel
-  // releases them with (signal memory) and the event this context's stream waits on behind every split launch
-  hipStream_t chain_stream = nullptr;
-  int32_t* chain_go = nullptr;
-  int32_t* chain_ctr = nullptr;      // device word: chain workgroups that have exited (DagSync::done); chain_exits = what it will reach
-  int32_t chain_exits = 0;
-  int chain_state = 0;  // 0 not tried, 1 usable, -1 not available (the two streams do not run kernels side by side) / switched off
-  int32_t chain_seq = 0;
-  // development aid (builds with -DAGP_STEP_TRACE, run with AGP_STEP_TRACE=<file>): a ring of STRACE_RECS stamp records, one per
-  // CAVI-step launch with a prologue (agp_chol.h, STRACE_*), written to the file by agp_ctx_destroy
-  unsigned long long* strace = nullptr;
-  unsigned long long* strace_last = nullptr;  // the record of the last launch (its deferred fallback stamps into it)
-  int64_t strace_n = 0;
-};
-
-#ifdef AGP_STEP_TRACE
-constexpr int64_t STRACE_RECS = 1024;
-static unsigned long long* step_trace_next(agp_ctx* c) {
-  static const char* path = getenv("AGP_STEP_TRACE");
-  if (!path || !path[0]) return nullptr;
-  const size_t bytes = sizeof(unsigned long long) * STRACE_SLOTS * STRACE_RECS;
-  if (!c->strace) {
-    if (hipMalloc((void**)&c->strace, bytes) != hipSuccess) return c->strace = nullptr;
-    (void)hipMemsetAsync(c->strace, 0, bytes, c->stream);
-  }
-  return c->strace + (c->strace_n++ % STRACE_RECS) * STRACE_SLOTS;
-}
-static void step_trace_dump(agp_ctx* c) {
-  const char* path = getenv("AGP_STEP_TRACE");
-  if (!c->strace || !path) return;
-  const int64_t n = std::min<int64_t>(c->strace_n, STRACE_RECS);
-  std::vector<unsigned long long> h((size_t)(STRACE_SLOTS * STRACE_RECS));
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpy(h.data(), c->strace, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  if (FILE* f = fopen(path, "wb")) {  // records oldest first: [n, slots] as int64, then n x slots stamps
-    const int64_t hdr[2] = {n, STRACE_SLOTS};
-    fwrite(hdr, sizeof(hdr), 1, f);
-    for (int64_t i = c->strace_n - n; i < c->strace_n; ++i)
-      fwrite(h.data() + (i % STRACE_RECS) * STRACE_SLOTS, sizeof(unsigned long long), STRACE_SLOTS, f);
-    fclose(f);
-  }
-  (void)hipFree(c->strace);
-  c->strace = nullptr;
-}
-#else
-static unsigned long long* step_trace_next(agp_ctx*) { return nullptr; }
-static void step_trace_dump(agp_ctx*) {}
-#endif
-
-#define HIPCHK(ctx, expr)                                                                       \
-  do {                                                                                          \
-    hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess) {                                                                     \
-      (ctx)->err = std::string(#expr) + " : " + hipGetErrorString(_e);                          \
-      return AGP_ERR_HIP;                                                                       \
-    }                                                                                           \
-  } while (0)
-
-#define LAUNCHCHK(ctx)                                                                          \
-  do {                                                                                          \
-    hipError_t _e = hipGetLastError();                                                          \
-    if (_e != hipSuccess) {                                                                     \
-      (ctx)->err = std::string("kernel launch : ") + hipGetErrorString(_e) + " @" + std::to_string(__LINE__); \
-      return AGP_ERR_HIP;                                                                       \
-    }                                                                                           \
-  } while (0)
-
-#define AGPCHK(expr)                   \
-  do {                                 \
-    agp_status _s = (expr);            \
-    if (_s != AGP_OK) return _s;       \
-  } while (0)
-
-// Every entry point runs with the ctx's device current and restores the caller's on the way out: the caller's thread may
-// have another device selected (two models on two GPUs in one process, torch.cuda.set_device between calls), and a library
-// must not change it behind the caller's back.
-struct DevGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DevGuard() {
-    if (switched && prev >= 0) (void)hipSetDevice(prev);
-  }
-  DevGuard(const DevGuard&) = delete;
-  DevGuard& operator=(const DevGuard&) = delete;
-};
-
-static inline int64_t rup64(int64_t x) { return (x + 63) / 64 * 64; }
-static inline dim3 grid1(int64_t n, int b = 256) { return dim3((unsigned)((n + b - 1) / b)); }
-static inline dim3 grid2(int64_t rows, int64_t cols) { return dim3((unsigned)((cols + 15) / 16), (unsigned)((rows + 15) / 16)); }
-static const dim3 blk2(16, 16);
-
-template <typename T>
-static agp_status dmalloc(agp_ctx* c, T** p, int64_t n) {
-  *p = nullptr;
-  if (n <= 0) n = 1;
-  hipError_t e = hipMalloc((void**)p, (size_t)n * sizeof(T));
-  if (e != hipSuccess) {
-    c->err = std::string("hipMalloc : ") + hipGetErrorString(e);
-    return AGP_ERR_NOMEM;
-  }
-  return AGP_OK;
-}
-
-// ---- linear-algebra drivers on padded matrices ---------------------------------------------------------------
-// Cholesky (lower, in place; diagonal factors in Dg) of the n x n (n = nt*64) matrix A with `ne` extension row blocks
-static agp_status tri_scratch_ensure(agp_ctx* c, size_t need) {
-  if (c->tri_bytes < need) {
-    if (c->tri_scratch) {
-      (void)hipStreamSynchronize(c->stream);
-      (void)hipFree(c->tri_scratch);
-    }
-    c->tri_scratch = nullptr;
-    c->tri_bytes = 0;
-    if (hipMalloc(&c->tri_scratch, need) != hipSuccess) return AGP_ERR_NOMEM;
-    c->tri_bytes = need;
-  }
-  return AGP_OK;
-}
-
-// E <- E L^-T (augmented Cholesky): nt launches of k_chol_step; do_x adds X = L^-1 (one extra row launch per column).
-// X = L^-1 (all off-diagonal tiles) from L and the diagonal inverses already in X: recursive doubling, 2 launches per level
-template <typename T>
-static agp_status trtri_levels(agp_ctx* c, const T* A, int64_t ld, T* X, int64_t ldx, int64_t nt) {
-  if (nt <= 1) return AGP_OK;
-  const int64_t n = nt * TILE;
-  AGPCHK(tri_scratch_ensure(c, sizeof(T) * (size_t)n * (size_t)n));
-  T* S = (T*)c->tri_scratch;
-  for (int64_t bs = 1; bs < nt; bs *= 2) {
-    const int64_t pairs = (nt + 2 * bs - 1) / (2 * bs);
-    dim3 g((unsigned)bs, (unsigned)bs, (unsigned)pairs);
-    hipLaunchKernelGGL((k_trtri_level<T>), g, dim3(NTHREADS), 0, c->stream, A, ld, X, ldx, S, n, nt, bs, 0);
-    hipLaunchKernelGGL((k_trtri_level<T>), g, dim3(NTHREADS), 0, c->stream, A, ld, X, ldx, S, n, nt, bs, 1);
-  }
-  LAUNCHCHK(c);
-  return AGP_OK;
-}
-
-// hand-over area for the next task-graph launch (`elems` elements of T): waits for the pending refill of the set, returns it;
-// dag_handover_release() schedules the refill behind the launch
-template <typename T>
-static agp_status dag_handover_acquire(agp_ctx* c, int64_t elems, int set, T** out) {
-  const size_t need = sizeof(T) * (size_t)elems;
-  if (c->hbytes < need || c->htype != (int)sizeof(T)) {
-    (void)hipStreamSynchronize(c->stream);
-    for (int q = 0; q < 2; ++q) {
-      if (c->hset[q]) (void)hipFree(c->hset[q]);
-      c->hset[q] = nullptr;
-      c->h_dirty[q].on = false;
-    }
-    c->hbytes = 0;
-    const size_t cap = need + need / 4;
-    c->hbytes = cap;
-    c->htype = (int)sizeof(T);
-  }
-  if (!c->hset[set]) {  // set 1 only exists once a step launch with a prologue asks for it (they alternate between the sets)
-    if (hipMalloc(&c->hset[set], c->hbytes) != hipSuccess) return AGP_ERR_NOMEM;
-    hipLaunchKernelGGL((k_fill_sent<T>), dim3(2048), dim3(256), 0, c->stream, (T*)c->hset[set], (int64_t)(c->hbytes / sizeof(T)),
-                       (int64_t)0);
-    c->h_dirty[set].on = false;
-  }
-  if (c->h_dirty[set].on) {  // nobody refilled it in passing: do it now, on this stream
-    const auto& d = c->h_dirty[set];
-    hipLaunchKernelGGL((k_fill_sent<T>), dim3((unsigned)std::max<int64_t>(1, 512 / d.nb), (unsigned)d.nb), dim3(256), 0, c->stream,
-                       (T*)c->hset[set], d.used, d.stride);
-    c->h_dirty[set].on = false;
-  }
-  *out = (T*)c->hset[set];
-  return AGP_OK;
-}
-template <typename T>
-static agp_status dag_handover_release(agp_ctx* c, int64_t used, int64_t stride, int nb, int set) {
-  // what the launch could have written (the first `used` elements of each of the nb problem regions) must hold the sentinel
-  // again before the set's next use: left to the next fused syrk launch (riders) or, failing that, to the next acquire
-  c->h_dirty[set].on = true;
-  c->h_dirty[set].used = used;
-  c->h_dirty[set].stride = stride;
-  c->h_dirty[set].nb = nb;
-  return AGP_OK;
-}
-
-// One-launch task graph (k_chol_dag) or one launch per block column (k_chol_step)?  Measured on MI355X, whole CAVI step:
-// m = 1024 f64 0.39 vs 0.52 ms, m = 2048 f32 0.80 vs 1.05 ms, m = 4096 f64 11.6 vs 8.3 ms -- the task graph removes launch
-// gaps and re-reads from the latency-bound chain, but its tiles stream their operands past the L2s (coherent loads), which
-// costs more than it saves once the trailing updates dominate.  AGP_CHOL_DAG=0 / 1 forces one or the other.
-// Column bound: the chain of a task graph waits for feeder tiles with HIGHER workgroup indices -- tile (k+1, k) in block column k
-// and tile (k+1, k+1), the first workgroup of column k + 1.  Progress does not depend on them being resident early: the chain
-// publishes X_k before it blocks on them (k_chol_dag, "late_feed"), so every resident workgroup -- all of them belong to block
-// columns <= k of their problem -- can finish on what the chains have published, retires, and the in-order dispatch reaches the
-// feeders.  (Rounds 1-2 published X_k after that wait and therefore needed a whole block column of every problem resident,
-// nb * (nt + ne + 1) <= 208; 8 problems of 34 tiles stalled.)  What remains is a performance matter: a feeder that gets its slot only
-// when the column before it retires applies its k pending updates on the chain's critical path.  Up to 288 tiles per column of all
-// problems the launch is still well ahead of per-column launches (8 x 34: 0.62 ms against 2 x 0.40 ms for 4 + 4).
-constexpr int64_t DAG_MAX_NT = 32, DAG_MAX_COLUMN_TILES = 288;
-static bool chol_use_dag(const agp_ctx* c, int64_t nt, int64_t ne = 0, int64_t nb = 1) {
-  static const int v = []() {
-    const char* e = getenv("AGP_CHOL_DAG");
-    return e ? (e[0] == '0' ? 0 : 1) : -1;
-  }();
-  if (c->dag_off) return false;  // a lost dependency was seen on this context (two processes sharing the device): stay safe
-  if (nb * (nt + ne + 1) > DAG_MAX_COLUMN_TILES) return false;
-  return v < 0 ? nt <= DAG_MAX_NT : v == 1;
-}
-
-__global__ void k_set_i32(int32_t* p, int32_t v) { *p = v; }
-// ... visible to a polling kernel of another stream (signal memory, system scope)
-__global__ void k_set_sig(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-// ... and the arrival word of a column group of the all-reduced statistics (comm_allreduce_groups): the collective's kernel before
-// this one on the same stream has ended, i.e. its writes are in memory
-__global__ void k_set_arrive(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+// (the host layers after every kernel header, as they stood in this file: the order of the kernels in the code object is kept)
+#include "agp_ctx.h"
+#include "agp_chol_host.h"
+#include "agp_blas_host.h"
 
 static agp_status comm_allreduce_groups(agp_comm* cm, void* base, int esz, const int64_t* off, const int64_t* cnt, int ng,
                                         int32_t dtype, int32_t* arrive, int32_t epoch);  // (defined with agp_comm_allreduce)
-
-// grid-barrier words, retry counter and the CU count of the fallback (allocated on first use)
-template <typename T>
-static agp_status ensure_safe_words(agp_ctx* c) {
-  if (!c->safe_bar) {
-    if (hipMalloc((void**)&c->safe_bar, 2 * sizeof(unsigned)) != hipSuccess) return AGP_ERR_NOMEM;
-    if (hipMalloc((void**)&c->safe_retries, sizeof(int32_t)) != hipSuccess) return AGP_ERR_NOMEM;
-    HIPCHK(c, hipMemsetAsync(c->safe_bar, 0, 2 * sizeof(unsigned), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->safe_retries, 0, sizeof(int32_t), c->stream));
-    hipDeviceProp_t pr;
-    HIPCHK(c, hipGetDeviceProperties(&pr, c->device));
-    c->n_cu = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 64;
-  }
-  return AGP_OK;
-}
-
-// Workgroups the grid-barrier fallback may count on being resident together.  One per CU -- minus the CUs a chain kernel of the
-// NEXT split launch may be sitting on: with the host ahead, that kernel is already in flight on its own stream, polls for a tile
-// kernel that is enqueued BEHIND the fallback, and holds most of its CU's LDS while it does (a fallback workgroup cannot share the
-// CU).  A fallback grid of n_cu workgroups would then wait at its first barrier for a workgroup that can never be placed.
-static int64_t safe_grid_cap(const agp_ctx* c) {
-  // test hook (AGP_DAG_TEST_OVERSUBSCRIBE=1, with AGP_DAG_TEST_ABORT=1): a fallback grid that CANNOT be resident at once (four
-  // workgroups of ~110 KB LDS per CU), i.e. the situation the bounded grid barrier exists for -- the step must end in status -3
-  // (AGP_ERR_HIP from agp_svgp_check_status) after the barrier's limit instead of hanging (tests/test_gpu_round6.py)
-  static const bool over = []() {
-    const char* e = getenv("AGP_DAG_TEST_OVERSUBSCRIBE");
-    return e && e[0] == '1';
-  }();
-  if (over) return 4 * (int64_t)c->n_cu;
-  return std::max<int64_t>(1, (int64_t)c->n_cu - (c->chain_state == 1 ? CHOL_MAXB : 0));
-}
-// the fallback behind a task-graph launch (see k_chol_safe): one launch that returns at once unless the latch reads -1
-template <typename T>
-static agp_status launch_chol_safe(agp_ctx* c, const CholBatch<T>& bt, const SafeSrc<T>& src, int nb, int64_t ld, int64_t ldx,
-                                   int64_t lde, int64_t ne, int64_t nt, int32_t* info_dev, int64_t nvalid) {
-  AGPCHK(ensure_safe_words<T>(c));
-  // one workgroup per CU at most (each needs ~110 KB of LDS, so one fits per CU): all of them become resident, whatever else runs
-  const int64_t most = (nt + ne + nt * (nt + 1) / 2 + ne * nt) * nb;
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(safe_grid_cap(c), most));
-  hipLaunchKernelGGL((k_chol_safe<T>), dim3(grid), dim3(CHOL_THREADS), 0, c->stream, bt, src, nb, ld, ldx, lde, ne, nt, info_dev,
-                     nvalid, c->safe_bar, c->safe_retries);
-  LAUNCHCHK(c);
-  return AGP_OK;
-}
-// The kernel behind the task graph of a single-latent CAVI step: the fallback of k_chol_safe (a no-op unless the latch reads -1)
-// and then the row statistics + local update, in ONE launch -- the separate k_chol_safe launch cost the step ~5 us of kernel and a
-// launch gap on its critical path.  grid <= n_cu workgroups of 512 threads (all resident: the fallback uses grid barriers); the
-// rows are taken wave by wave, grid-stride.
-template <typename T>
-__global__ __launch_bounds__(CHOL_THREADS) void k_safe_rowstats(CholBatch<T> bt, SafeSrc<T> src, int64_t ld, int64_t ldx, int64_t lde,
-                                                                int64_t ne, int64_t nt, int32_t* __restrict__ info, int64_t nvalid,
-                                                                unsigned* __restrict__ bar, int32_t* __restrict__ retries,
-                                                                int64_t B, int nslices, RowstatsBatch<T> rb, int64_t ldp,
-                                                                int64_t ldw, int64_t cols, T jitter, T rho, LikParams<T> lp,
-                                                                const T* __restrict__ y, const int64_t* __restrict__ idx,
-                                                                T* __restrict__ Kt, T* __restrict__ muf, T* __restrict__ varf,
-                                                                T* __restrict__ cb, T* __restrict__ theta, T* __restrict__ r,
-                                                                T* __restrict__ w, int* __restrict__ flags,
-                                                                const T* __restrict__ lam, T* __restrict__ gamma,
-                                                                int rows_done = 0, const int32_t* __restrict__ pf_word = nullptr,
-                                                                int32_t pf_want = 0, const T* __restrict__ s00_kap = nullptr,
-                                                                int64_t s00_ldk = 0, int64_t s00_K = 0,
-                                                                const T* __restrict__ s00_w = nullptr, T* __restrict__ pre = nullptr,
-                                                                unsigned long long* trace = nullptr) {
-  __shared__ __attribute__((aligned(16))) T sm[3 * TILE * LDP];
-  __shared__ __attribute__((aligned(16))) T sc[SC_ELEMS];
-  __shared__ T piv[TILE];
-#ifdef AGP_STEP_TRACE
-  if (trace && threadIdx.x == 0 && blockIdx.x < 256) trace[STRACE_SAFE0 + blockIdx.x] = wall_clock64();
-  StraceExit strace_exit{(trace && blockIdx.x < 256) ? trace + STRACE_SAFE1 + blockIdx.x : nullptr};
-#else
-  (void)trace;
-#endif
-  const bool ran = chol_safe_body<T>(bt, src, 1, ld, ldx, lde, ne, nt, info, nvalid, bar, retries, sm, sc, piv);
-  // (after a fallback the last grid barrier of the column loop has made every workgroup's tiles visible)
-  // rows_done (round 3): the task-graph launch finished its rows itself (EpiArgs, agp_chol.h) -- unless it was aborted and re-run here
-  if (ran || !rows_done) {
-    const int64_t wpb = CHOL_THREADS / 64, nwave = (int64_t)gridDim.x * wpb;
-    for (int64_t i = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); i < B; i += nwave)
-      rowstats_row<T>(i, threadIdx.x & 63, 0, B, nslices, rb, ldp, ldw, cols, jitter, rho, lp, y, idx, Kt, muf, varf, cb, theta, r,
-                      w, (int64_t)0, flags, lam, gamma);
-  }
-  // pre: the first three tiles of S = kappa' diag(w) kappa of the pending natural-gradient step (kappa s00_kap, weights s00_w = the
-  // w of the launch in front) for the head of the next launch (ProArgs::pre).  Not where this launch re-ran the fallback: its rows
-  // above are not visible to the other workgroups yet, and the next launch's three tiles form their products themselves
-  if (pro_pre_on<T>() && pre) {
-    if (!ran) pro_pre_prepare<T>(s00_kap, s00_ldk, s00_K, s00_w, pre, sm);
-    if (blockIdx.x == 0 && threadIdx.x == 0) pre[PRO_PRE_VALID] = ran ? T(0) : T(1);
-  }
-  // pf_word (round 3): this launch was deferred to the head of the NEXT step and also carries that step's wait for its look-ahead
-  // (one wave polls the look-ahead's "done" word; in the steady state it is set long before)
-  if (pf_word && blockIdx.x == 0 && threadIdx.x == 0) {
-    long spins = 0;
-    while ((int32_t)(__hip_atomic_load(pf_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - pf_want) < 0) {
-      __builtin_amdgcn_s_sleep(8);
-      if (++spins > (1L << 27)) {
-        atomicExch(info, -2);
-        break;
-      }
-    }
-  }
-}
-
-// The same for the launch behind materialize() (the factorisation of -2 eta2 with its inverse and Sigma = X' X, round 5): the
-// fallback, then mu = Sigma eta1 and v = X eta1 wave by wave (k_symv_trmv's rows) -- one launch less in the hyper-parameter iteration.
-template <typename T>
-__global__ __launch_bounds__(CHOL_THREADS) void k_safe_symv_trmv(CholBatch<T> bt, SafeSrc<T> src, int64_t ld, int64_t ldx, int64_t lde,
-                                                                 int64_t ne, int64_t nt, int32_t* __restrict__ info, int64_t nvalid,
-                                                                 unsigned* __restrict__ bar, int32_t* __restrict__ retries,
-                                                                 const T* __restrict__ S, const T* __restrict__ X, int64_t ldm,
-                                                                 int64_t n, const T* __restrict__ x, T* __restrict__ ys,
-                                                                 T* __restrict__ yt) {
-  __shared__ __attribute__((aligned(16))) T sm[3 * TILE * LDP];
-  __shared__ __attribute__((aligned(16))) T sc[SC_ELEMS];
-  __shared__ T piv[TILE];
-  (void)chol_safe_body<T>(bt, src, 1, ld, ldx, lde, ne, nt, info, nvalid, bar, retries, sm, sc, piv);
-  // (after a fallback its last grid barrier has made X and Sigma visible to every workgroup)
-  const int64_t wpb = CHOL_THREADS / 64, nwave = (int64_t)gridDim.x * wpb;
-  for (int64_t w = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); w < 2 * n; w += nwave)
-    symv_trmv_row<T>(w, threadIdx.x & 63, S, X, ldm, n, x, ys, yt);
-}
-
-// Factorisation by plain launches (matrices beyond the task graph, and the task graph's fallback).  From 8 block columns on it is
-// blocked (agp_chol.h, k_chol_panel): groups of G block columns -- the G x G diagonal block by G small launches, the rows below it
-// by one panel-solve launch, everything to the right by one trailing launch per group; the part of the trailing update that the
-// next group does not need runs on a side stream, next to the next group's diagonal block and panel (look-ahead of one group).
-// AGP_CHOL_GROUP = 1 gives the plain per-column right-looking sequence, AGP_CHOL_LOOKAHEAD = 0 keeps everything on one stream.
-constexpr int CHOL_GMAX = 8;
-static int chol_group() {
-  static const int g = []() {
-    const char* e = getenv("AGP_CHOL_GROUP");
-    const int v = e ? atoi(e) : 8;
-    return v < 1 ? 1 : v > CHOL_GMAX ? CHOL_GMAX : v;
-  }();
-  return g;
-}
-// blocked from 96 block rows on (extension included): measured on MI355X, a plain 4096 x 4096 matrix (64 block rows) is still
-// quicker column by column (2.6 vs 3.0 ms, the group's serial launches dominate), 8192 and the C5 step (64 + 65 rows) are not
-static bool chol_blocked(int64_t nt, int64_t ne) { return chol_group() > 1 && nt >= 8 && nt + ne >= 96; }
-// kernel launches of one factorisation by plain launches (what the HIP-event timing of the sequence is divided by)
-static int64_t chol_launch_count(int64_t nt, int64_t ne) {
-  if (!chol_blocked(nt, ne)) return nt;
-  const int64_t G = chol_group();
-  int64_t n = 0;
-  for (int64_t k0 = 0; k0 < nt; k0 += G) {
-    const int64_t k1 = (k0 + G < nt) ? k0 + G : nt, kn = (k1 + G < nt) ? k1 + G : nt;
-    n += (k1 - k0) + (nt - k1 + ne > 0 ? 1 : 0) + (k1 < nt ? 1 : 0) + (k1 < nt && kn < nt ? 1 : 0);
-  }
-  return n;
-}
-static bool chol_lookahead() {
-  static const bool on = []() {
-    const char* e = getenv("AGP_CHOL_LOOKAHEAD");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-template <typename T>
-static agp_status chol_columns(agp_ctx* c, const CholBatch<T>& bt, int nb, int64_t ld, int64_t ldx, int64_t lde, int64_t ne,
-                               int do_x, int64_t nt, int32_t* info_dev, int64_t nvalid) {
-  const int64_t G = chol_group();
-  if (!chol_blocked(nt, ne)) {
-    for (int64_t k = 0; k < nt; ++k) {
-      const int64_t nP = nt - k + ne;
-      const int64_t nU = chol_nU(k, 0, nt, nt, ne);
-      hipLaunchKernelGGL((k_chol_step<T>), dim3((unsigned)(nP + nU), (unsigned)nb), dim3(CHOL_THREADS), 0, c->stream, bt, ld, ldx,
-                         lde, ne, do_x, k, nt, info_dev, nvalid, (int64_t)0, (int64_t)-1, (T*)nullptr, (int64_t)0);
-    }
-    return AGP_OK;
-  }
-  const int64_t li_stride = G * TILE * TILE;
-  const size_t li_need = sizeof(T) * (size_t)(li_stride * nb);
-  if (c->chol_li_bytes < li_need) {
-    if (c->chol_li) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      (void)hipFree(c->chol_li);
-    }
-    c->chol_li = nullptr;
-    c->chol_li_bytes = 0;
-    if (hipMalloc(&c->chol_li, li_need) != hipSuccess) return AGP_ERR_NOMEM;
-    c->chol_li_bytes = li_need;
-  }
-  T* li = (T*)c->chol_li;
-  const bool look = chol_lookahead();
-  if (look && !c->side) {
-    HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  }
-  auto trail = [&](hipStream_t st, int64_t k0, int64_t k1, int64_t j_lo, int64_t j_hi) {
-    const int64_t n = chol_trail_tiles(j_lo, j_hi, nt, ne);
-    if (n > 0)
-      hipLaunchKernelGGL((k_chol_trail<T>), dim3((unsigned)n, (unsigned)nb), dim3(CHOL_THREADS), 0, st, bt, ld, lde, ne, k0, k1,
-                         nt, j_lo, j_hi);
-  };
-  bool side_busy = false;
-  for (int64_t k0 = 0; k0 < nt; k0 += G) {
-    const int64_t k1 = (k0 + G < nt) ? k0 + G : nt;
-    const int g = (int)(k1 - k0);
-    // D: the diagonal block on its own (block rows k0 .. k1-1 only), leaving the inverses of its diagonal tiles in li
-    for (int64_t k = k0; k < k1; ++k) {
-      const int64_t nP = k1 - k;
-      const int64_t nU = chol_nU(k, k0, k1, k1, 0);
-      hipLaunchKernelGGL((k_chol_step<T>), dim3((unsigned)(nP + nU), (unsigned)nb), dim3(CHOL_THREADS), 0, c->stream, bt, ld, ldx,
-                         lde, (int64_t)0, do_x, k, k1, info_dev, nvalid, k0, k1, li, li_stride);
-    }
-    // P: block rows k1 .. nt-1 and the extension rows against the block
-    const int64_t rows = nt - k1 + ne;
-    if (rows > 0) {
-      const dim3 grid((unsigned)rows, (unsigned)nb);
-#define AGP_PANEL(GG)                                                                                                       \
-  hipLaunchKernelGGL((k_chol_panel<T, GG>), grid, dim3(CHOL_THREADS), 0, c->stream, bt, ld, lde, ne, k0, nt, (const T*)li, \
-                     li_stride, g)
-      if (G <= 2) AGP_PANEL(2);
-      else if (G <= 4) AGP_PANEL(4);
-      else AGP_PANEL(8);
-#undef AGP_PANEL
-    }
-    if (k1 >= nt) break;
-    // T: the far columns were last written by the previous group's side-stream launch: order behind it
-    if (side_busy) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    const int64_t kn = (k1 + G < nt) ? k1 + G : nt;  // the next group's columns [k1, kn) are needed first
-    trail(c->stream, k0, k1, k1, kn);
-    if (kn < nt) {
-      if (look) {
-        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        trail(c->side, k0, k1, kn, nt);
-        HIPCHK(c, hipEventRecord(c->ev_join, c->side));
-        side_busy = true;
-      } else {
-        trail(c->stream, k0, k1, kn, nt);
-      }
-    }
-  }
-  if (side_busy) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-  return AGP_OK;
-}
-
-
-static void dag_pause(agp_ctx* c) {
-  c->dag_off = true;
-  c->dag_cooldown = c->dag_backoff;
-  c->dag_backoff = std::min<int64_t>(c->dag_backoff * 4, (int64_t)1 << 20);
-}
-// once per CAVI step: end of the probation?
-static void dag_tick(agp_ctx* c) {
-  if (c->dag_off && --c->dag_cooldown <= 0) c->dag_off = false;
-}
-// host side of the latch: called where the stream has just been synchronised anyway
-static void dag_retry_check(agp_ctx* c) {
-  if (!c->safe_retries || c->dag_off) return;
-  int32_t r = 0;
-  if (hipMemcpy(&r, c->safe_retries, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess) return;
-  if (r > c->dag_retries_seen) {
-    fprintf(stderr,
-            "[agp_hip] warning: %d task-graph factorisation(s) lost a tile dependency (is another process using this GPU?) and were "
-            "re-run by the in-stream fallback; this context uses plain launches for the next %lld steps\n",
-            (int)(r - c->dag_retries_seen), (long long)c->dag_backoff);
-    c->dag_retries_seen = r;
-    dag_pause(c);
-  }
-}
-
-// Split task-graph launches: worth it when the launch queues far more tiles than the chip has workgroup slots (C3: 1584, C4: 3264);
-// the small launches (C2: 408 tiles, and its merged step with the prologue) stay one kernel.  AGP_CHAIN_SPLIT=0 / 1 forces.
-static bool chain_split_wanted(int64_t tiles, bool with_prologue = false, bool f64 = true) {
-  static const int v = []() {
-    const char* e = getenv("AGP_CHAIN_SPLIT");
-    return e ? (e[0] == '0' ? 0 : 1) : -1;
-  }();
-  // fp64 launches with the prologue stay merged unless forced: their tile workgroups stage four LDS tiles (135 KB: one workgroup
-  // per CU whatever the registers), and the measured case lost (C2: 0.3167 ms split, 0.3103 ms merged).  In fp32 the same tile
-  // kernel fits two workgroups per CU (68 KB, 128 VGPRs) and wins: m = 1024, B = 2048 fp32 0.325 -> 0.270 ms per step.
-  // Round 5 made the fp32 form opt-in as well after two findings of the stress runs (docs/DESIGN_LOG.md section 14): the chain kernel
-  // took tile (0, 0)'s eta2 step, so an ABORTED launch could leave eta2 half-stepped (repaired in round 5: the chain's place in the
-  // tile kernel takes it and parks the tile), and about one split launch in 10 000 lost a dependency on its own -- the tile kernel
-  // filled every CU before the chain kernel was resident (repaired in round 6: DagSync::here / k_wait_here).  Default again in fp32.
-  if (with_prologue && f64 && v < 0) return false;
-  return v < 0 ? tiles >= 600 : v == 1;
-}
-// the chain stream, its release word and the proof that kernels of the two streams run at the same time (k_handshake: where
-// dispatches are serialised -- rocprofv3 --pmc, AMD_SERIALIZE_KERNEL -- a chain kernel polling for the tile kernel behind it in
-// the device's single queue would never be released; such a context keeps the merged kernel)
-static bool chain_split_ready(agp_ctx* c) {
-  if (c->chain_state != 0) return c->chain_state == 1;
-  c->chain_state = -1;
-  int lo = 0, hi = 0;
-  if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) return false;
-  if (hipStreamCreateWithPriority(&c->chain_stream, hipStreamNonBlocking, hi) != hipSuccess) {
-    c->chain_stream = nullptr;
-    (void)hipGetLastError();
-    return false;
-  }
-  bool ok = hipExtMallocWithFlags((void**)&c->chain_go, 8, hipMallocSignalMemory) == hipSuccess && hipMemset(c->chain_go, 0, 8) == hipSuccess &&
-            hipMalloc((void**)&c->chain_ctr, sizeof(int32_t)) == hipSuccess && hipMemset(c->chain_ctr, 0, sizeof(int32_t)) == hipSuccess;
-  int32_t* hs = nullptr;
-  ok = ok && hipMalloc((void**)&hs, 4 * sizeof(int32_t)) == hipSuccess && hipMemset(hs, 0, 4 * sizeof(int32_t)) == hipSuccess;
-  if (ok) {
-    (void)hipStreamSynchronize(c->stream);
-    hipLaunchKernelGGL(k_handshake, dim3(1), dim3(64), 0, c->chain_stream, hs, (const int32_t*)(hs + 1), hs + 2);
-    hipLaunchKernelGGL(k_handshake, dim3(1), dim3(64), 0, c->stream, hs + 1, (const int32_t*)hs, hs + 3);
-    int32_t res[4] = {0, 0, 0, 0};
-    ok = hipStreamSynchronize(c->chain_stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess &&
-         hipMemcpy(res, hs, sizeof(res), hipMemcpyDeviceToHost) == hipSuccess && res[2] == 1 && res[3] == 1;
-  }
-  if (hs) (void)hipFree(hs);
-  (void)hipGetLastError();
-  if (ok) c->chain_state = 1;
-  return ok;
-}
-// Behind a split launch NO event joins the two streams: the tile kernel cannot end before the chain's last publish, after which the
-// chain writes nothing (its diagonal factors are write-through stores issued before that publish), so whatever follows on this
-// context's stream -- and a host synchronisation of it -- sees a finished factorisation.  The one exception, an aborted launch whose
-// chain is still inside a tile factorisation, is handled where it matters: the fallback waits for the chain workgroups' exit count
-// (DagSync::done, SafeSrc::chain_done).  (An event join -- record on the chain stream, wait on this one -- was the first version and
-// DEADLOCKED with the host several steps ahead, the look-ahead on and the prologue inside the split launch; removed in round 5,
-// the account is in docs/DESIGN_LOG.md.)
-// what a split launch hands its kernels / its fallback about the chain kernel (nb chain workgroups)
-static void chain_split_arm(agp_ctx* c, DagSync& ds, int nb) {
-  ds.go = c->chain_go;
-  ds.go_val = ++c->chain_seq;
-  ds.done = c->chain_ctr;
-  ds.here = c->chain_go + 1;  // (second word of the same signal-memory allocation)
-  c->chain_exits += nb;
-}
-// ... enqueued on the step's stream between the chain kernel's launch (chain stream) and the tile kernel's: every chain workgroup
-// of this launch -- and of all launches before it: the count is cumulative, like chain_exits -- is resident (DagSync::here)
-static void chain_split_wait_here(agp_ctx* c) {
-  hipLaunchKernelGGL(k_wait_here, dim3(1), dim3(64), 0, c->stream, (const int32_t*)(c->chain_go + 1), c->chain_exits);
-}
-
-// what a CAVI step hands to its factorisation about the look-ahead stream (see DagSync, agp_chol.h)
-struct StepSync {
-  DagSync ds{};
-  bool used = false;  // out: the task-graph launch took `ds`
-};
-
-// The pending natural-gradient step that a CAVI step's task-graph launch takes along as its prologue (ProArgs, agp_chol.h)
-template <typename T>
-struct ProHost {
-  const T* kap = nullptr;
-  int64_t ldk = 0, Kdim = 0;
-  const T *w = nullptr, *r = nullptr;
-  T* eta2 = nullptr;
-  const T* Kinv = nullptr;
-  int64_t ldm = 0;
-  T* eta1 = nullptr;
-  const T* kinv_mu0 = nullptr;
-  T lr = T(0);
-  const T *packed = nullptr, *tred = nullptr;  // batch-parallel step: reduced statistics instead of (kap, w, r)  (ProArgs)
-  const int32_t* arrive = nullptr;             // ... arriving in block-column groups (AGP_SPLIT_OVERLAP)
-  int32_t arrive_want = 0;
-  unsigned char grp[32] = {};
-  T* Cout = nullptr;                           // ProArgs::Cout
-  const T* pre = nullptr;                      // ProArgs::pre
-};
-// k-slices per block column of the prologue's product: a tile of block column c has to be there when the chain reaches the
-// column (about tau * c after the start, tau = 17.8 us f64 / 14 us f32 per block column), a 64-row chunk of the product costs a
-// workgroup about tc = 2.7 / 1.6 us; columns 0 and 1 feed the chain at once and are split as far as it pays (8).  pre: the
-// chain's first tiles were prepared by the launch in front (ProArgs::pre), so it reaches every column ~10 us sooner (measured at
-// C2: factor(0) done 20 instead of 30 us after the start; with the old table the feeders of block column 4 came 2.8 us late)
-static void pro_ks_table(int64_t nt, int64_t nq, bool f64, unsigned char* ks, unsigned char* kf, bool pre = false) {
-  const double tc = f64 ? 2.7 : 1.6, tau = f64 ? 17.8 : 14.0, head = pre ? 24.0 : 12.0;
-  for (int64_t c = 0; c < nt && c < 32; ++c) {
-    int want;
-    if (c == 0) want = 8;
-    else if (c == 1) want = f64 ? 4 : 8;
-    else want = (int)std::ceil((double)nq * (tc + 0.3) / std::max(tau * (double)c - head, 1.0));
-    want = std::max(1, std::min<int>(want, (int)std::min<int64_t>(8, nq)));
-    // the tiles next to the diagonal (ProArgs::kf) take the same split as their column (a finer one was measured at 32 block
-    // columns, docs/DESIGN_LOG.md, and not adopted)
-    ks[c] = kf[c] = (unsigned char)want;
-  }
-}
-// test hook (AGP_DAG_TEST_ABORT=1): pretend every task-graph launch of a CAVI step lost a dependency, so that the in-stream
-// fallback runs behind each of them
-static bool dag_test_abort() {
-  static const bool on = []() {
-    const char* e = getenv("AGP_DAG_TEST_ABORT");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
-template <typename T>
-static agp_status potrf_fused(agp_ctx* c, T* A, int64_t ld, int64_t n, T* X, int64_t ldx, T* Dg, T* E, int64_t lde,
-                              int64_t ne, int do_x, int32_t* info_dev, int64_t nvalid, const T* erow = nullptr,
-                              bool want_l = true, SafeSrc<T>* safe = nullptr, bool* defer_safe = nullptr,
-                              StepSync* ssync = nullptr, const ProHost<T>* pro = nullptr, const EpiArgs<T>* epi = nullptr,
-                              T* Pout = nullptr, bool* p_done = nullptr, double* ld_out = nullptr, int32_t* ld_status = nullptr) {
-  // Pout (with do_x; leading dimension ldx): P = X' X is wanted next -- K^-1 at a kernel refresh, Sigma for the hyper-gradient.  On
-  // the task graph it is formed by product workgroups at the end of the same launch (ProdArgs, agp_chol.h) and *p_done says so;
-  // otherwise the caller forms it (xtx_padded)
-  if (p_done) *p_done = false;
-  // ssync (CAVI step next to a look-ahead stream): the step's task-graph instantiation stores its `started` number (`used` is set)
-  // defer_safe (in: the caller can run the fallback itself, k_safe_rowstats; out: whether it has to -- the task graph was used)
-  const bool can_defer = defer_safe && *defer_safe;
-  if (defer_safe) *defer_safe = false;
-  // safe: sources the inputs can be restored from (A = -2 eta2, E = [kappa ; eta1' ; 0]): the in-stream fallback k_chol_safe is
-  // then enqueued behind the task graph; without it a lost dependency surfaces as an error at the caller's next check
-  // want_l = false: the caller never reads the factor L itself (only E L^-T, X, Dg): the task graph skips those stores
-  // erow: the last extension block is [erow' ; 0] (not yet written to E: the task graph reads it in place; the per-column
-  // path needs it in E first)
-  const int64_t nt = n / TILE;
-  const bool use_dag = chol_use_dag(c, nt, ne);
-  bool split_used = false;  // the launch went out as chain kernel + tile kernel: its fallback waits for the chain's exit count
-  if (pro && !(use_dag && X && !want_l && nt <= 32)) {
-    c->err = "potrf_fused: a pending natural-gradient step can only ride on the CAVI step's task-graph launch";
-    return AGP_ERR_INVALID;
-  }
-  if (use_dag && X) {
-    const int64_t nx = (do_x && nt > 1) ? nt : 0;  // the full inverse rides along as nt identity block rows
-    // prologue (pro): helper workgroups, their flags and hand-over slots
-    ProArgs<T> pa{};
-    int64_t nhelp = 0;
-    if (pro) {
-      if (pro->packed)
-        for (int64_t cc = 0; cc < nt; ++cc) pa.ks[cc] = pa.kf[cc] = 1;  // nothing to compute: no helpers
-      else
-        pro_ks_table(nt, pro->Kdim / TILE, sizeof(T) == 8, pa.ks, pa.kf, pro->pre != nullptr);
-      for (int64_t cc = 0; cc < nt; ++cc) nhelp += pro_nhelp(nt, cc, pa.ks[cc], pa.kf[cc]);
-    }
-    const int64_t nf = ((nt + ne + nx) * nt + 3 * nt + 1 + nhelp) * DAG_FS;
-    if (c->dag_cap < nf) {
-      if (c->dag_flags) (void)hipFree(c->dag_flags);
-      c->dag_flags = nullptr;
-      c->dag_cap = 0;
-      if (hipMalloc((void**)&c->dag_flags, sizeof(int32_t) * (size_t)(nf + 1024)) != hipSuccess) return AGP_ERR_NOMEM;
-      c->dag_cap = nf + 1024;
-      HIPCHK(c, hipMemsetAsync(c->dag_flags, 0, sizeof(int32_t) * (size_t)c->dag_cap, c->stream));
-      c->dag_epoch = 0;
-    }
-    c->dag_epoch += 1;
-    const int64_t ntiles = nt * (nt + 1) / 2 + ne * nt + (nx ? nt * (nt + 1) / 2 : 0);
-    const int64_t hstride = ((2 * nt + ne) * nt + 3 * nt + nhelp) * TILE * TILE;
-    const int64_t hused = (3 * nt + (nt + ne + nx) * nt + nhelp) * TILE * TILE;
-    T* H = nullptr;
-    const bool with_p = Pout != nullptr && nx > 0 && p_done != nullptr;
-    const int64_t nprod = with_p ? nt * (nt + 1) / 2 : 0;
-    // launches with a prologue alternate between the two hand-over sets and refill each other's; so do the launches with product
-    // workgroups (the symmetric-product launches whose riders refilled set 0 behind them are gone from their path)
-    const int hs = (pro || with_p) ? c->h_step_set : 0;
-    AGPCHK(dag_handover_acquire<T>(c, hstride, hs, &H));
-    ProdArgs<T> pd{};
-    if (with_p) {
-      pd.out = Pout;
-      pd.ld = ldx;
-      pd.ld_out = ld_out;  // (log det of the factor rides on the last product workgroup)
-      pd.status = ld_status;
-      if (!pro) {
-        const int other = hs ^ 1;
-        if (c->hset[other] && c->h_dirty[other].on && c->h_dirty[other].nb == 1 && c->htype == (int)sizeof(T)) {
-          pd.fill = (T*)c->hset[other];
-          pd.fill_n = c->h_dirty[other].used;
-          c->h_dirty[other].on = false;
-        }
-        c->h_step_set = other;
-      }
-      if (safe) {
-        safe->pout = Pout;
-        safe->ldpo = ldx;
-        safe->ld_out = ld_out;
-        safe->ld_status = ld_status;
-        safe->ld_n = nvalid;
-      }
-      *p_done = true;
-    }
-    unsigned long long* const trace = nullptr;  // (per-tile timestamps: the TRACE instantiation of k_chol_dag, a development aid)
-    // step_inst selects the STEP instantiations below; for a single problem in fp64 that is also the launch-uniform choice of the
-    // slot format without X21 and of the block substitution (dag_block_subst, agp_chol.h) -- every kernel of the launch, merged
-    // or split, is instantiated with the same T / STEP / BATCH and so reads the same decision
-    const bool step_inst = nx == 0 && !do_x && !want_l;
-    DagSync ds{};
-    if (ssync) {
-      if (step_inst) {
-        ds = ssync->ds;
-        ssync->used = true;
-      }
-    }
-    CholBatch<T> one{};
-    one.A[0] = A;
-    one.X[0] = X;
-    one.Dg[0] = Dg;
-    one.E[0] = E;
-    if (pro) {  // ... with the pending natural-gradient step as its prologue (the CAVI step's launch, or --
-                                        // hyper-parameter iteration -- the factorisation of the updated -2 eta2 with its inverse)
-      pa.kap = pro->kap;
-      pa.ldk = pro->ldk;
-      pa.Kdim = pro->Kdim;
-      pa.w = pro->w;
-      pa.r = pro->r;
-      pa.eta2 = pro->eta2;
-      pa.Kinv = pro->Kinv;
-      pa.ldm = pro->ldm;
-      pa.eta1 = pro->eta1;
-      pa.kinv_mu0 = pro->kinv_mu0;
-      pa.lr = pro->lr;
-      pa.packed = pro->packed;
-      pa.Cout = pro->Cout;
-      pa.pre = pro->pre;
-      pa.tred = pro->tred;
-      pa.arrive = pro->arrive;
-      pa.arrive_want = pro->arrive_want;
-      memcpy(pa.grp, pro->grp, sizeof(pa.grp));
-      pa.HS = H + (3 * nt + (nt + ne + nx) * nt) * TILE * TILE;
-      pa.sflags = c->dag_flags + ((nt + ne + nx) * nt + 3 * nt + 1) * DAG_FS;
-      const int other = hs ^ 1;
-      if (c->hset[other] && c->h_dirty[other].on && c->h_dirty[other].nb == 1 && c->htype == (int)sizeof(T)) {
-        pa.fill = (T*)c->hset[other];  // the set the launch before this one used: refilled in this launch's shadow
-        pa.fill_n = c->h_dirty[other].used;
-        pa.nfill = 64;
-        c->h_dirty[other].on = false;
-      }
-      // (wall-clock stamps of the prologue and the step boundary, PRO_TS / STRACE in agp_chol.h: a development aid)
-      unsigned long long* const ptrace = step_inst ? step_trace_next(c) : nullptr;
-      c->strace_last = ptrace;
-      constexpr unsigned lds_pad = 0;
-      if (step_inst && chain_split_wanted(ntiles + nhelp, true, sizeof(T) == 8) && chain_split_ready(c)) {  // chain kernel + tile kernel (k_chol_dag, ROLE)
-        // No event joins the chain stream behind a split launch (see chain_split_arm): correct only as long as the chain kernel
-        // stores nothing after its last publish.  C = S + K^-1 / 4 (ProArgs::Cout) is a plain store of tile (0, 0)'s workgroup --
-        // in a split launch that would be the chain kernel, whose plain stores only become visible when THAT kernel ends.  Cout
-        // exists for launches with the inverse (do_x), which never split; enforced here rather than assumed.
-        if (pa.Cout) {
-          c->err = "potrf_fused: C = S + K^-1/4 (ProArgs::Cout) cannot ride on a split (chain kernel + tile kernel) launch";
-          return AGP_ERR_INVALID;
-        }
-        chain_split_arm(c, ds, 1);
-        split_used = true;
-        hipLaunchKernelGGL((k_chol_dag<T, true, false, false, true, true, 1>), dim3(1), dim3(CHOL_THREADS), 0, c->chain_stream, one, 1,
-                           (int64_t)0, ld, ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch, ptrace, H, hstride, nx, erow, 0,
-                           ds, pa, epi ? *epi : EpiArgs<T>{});
-        chain_split_wait_here(c);
-        hipLaunchKernelGGL((k_chol_dag<T, true, false, false, true, true, 2>), dim3((unsigned)(ntiles + nhelp + pa.nfill)),
-                           dim3(CHOL_THREADS), lds_pad, c->stream, one, 1, (int64_t)0, ld, ldx, lde, ne, nt, info_dev, nvalid,
-                           c->dag_flags, c->dag_epoch, ptrace, H, hstride, nx, erow, 0, ds, pa, epi ? *epi : EpiArgs<T>{});
-        LAUNCHCHK(c);
-      } else if (step_inst)
-        hipLaunchKernelGGL((k_chol_dag<T, true, false, false, true, true>), dim3((unsigned)(ntiles + nhelp + pa.nfill)),
-                           dim3(CHOL_THREADS), lds_pad, c->stream, one, 1, (int64_t)0, ld, ldx, lde, ne, nt, info_dev, nvalid,
-                           c->dag_flags, c->dag_epoch, ptrace, H, hstride, nx, erow, 0, ds, pa, epi ? *epi : EpiArgs<T>{});
-      else {
-        pd.base = ntiles + nhelp + pa.nfill;
-        hipLaunchKernelGGL((k_chol_dag<T, true, false, false, false, true>), dim3((unsigned)(ntiles + nhelp + pa.nfill + nprod)),
-                           dim3(CHOL_THREADS), lds_pad, c->stream, one, 1, (int64_t)0, ld, ldx, lde, ne, nt, info_dev, nvalid,
-                           c->dag_flags, c->dag_epoch, ptrace, H, hstride, nx, erow, (int)(do_x && nx == 0) | (want_l ? 2 : 0),
-                           DagSync{}, pa, EpiArgs<T>{}, pd);
-      }
-      c->h_step_set = other;
-    } else if (step_inst && chain_split_wanted(ntiles) && chain_split_ready(c)) {
-      // ... as two kernels: the chain workgroup on its own stream (enqueued first), every other tile on this one
-      chain_split_arm(c, ds, 1);
-      split_used = true;
-      hipLaunchKernelGGL((k_chol_dag<T, true, false, false, true, false, 1>), dim3(1), dim3(CHOL_THREADS), 0, c->chain_stream, one, 1,
-                         (int64_t)0, ld, ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch, trace, H, hstride, nx, erow,
-                         0, ds);
-      chain_split_wait_here(c);
-      hipLaunchKernelGGL((k_chol_dag<T, true, false, false, true, false, 2>), dim3((unsigned)ntiles), dim3(CHOL_THREADS), 0, c->stream,
-                         one, 1, (int64_t)0, ld, ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch, trace, H, hstride, nx,
-                         erow, 0, ds);
-      LAUNCHCHK(c);
-    } else if (step_inst)  // the CAVI step's launch: specialised instantiation
-      hipLaunchKernelGGL((k_chol_dag<T, true, false, false, true>), dim3((unsigned)ntiles), dim3(CHOL_THREADS), 0, c->stream, one, 1,
-                         (int64_t)0, ld, ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch, trace, H, hstride, nx, erow,
-                         0, ds);
-    else {
-      pd.base = ntiles;
-      hipLaunchKernelGGL((k_chol_dag<T, true>), dim3((unsigned)(ntiles + nprod)), dim3(CHOL_THREADS), 0, c->stream, one, 1, (int64_t)0,
-                         ld, ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch, trace, H, hstride, nx, erow,
-                         (int)(do_x && nx == 0) | (want_l ? 2 : 0), DagSync{}, ProArgs<T>{}, EpiArgs<T>{}, pd);
-    }
-    LAUNCHCHK(c);
-    AGPCHK(dag_handover_release<T>(c, hused, hstride, 1, hs));
-    const bool test_abort = dag_test_abort();
-    if (safe) {
-      safe->chain_done = split_used ? c->chain_ctr : nullptr;
-      safe->chain_want = c->chain_exits;
-    }
-    if (safe && (!do_x || safe->want_x)) {
-      if (test_abort) hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, c->stream, info_dev, -1);
-      if (can_defer) *defer_safe = true;
-      else AGPCHK(launch_chol_safe<T>(c, one, *safe, 1, ld, ldx, lde, ne, nt, info_dev, nvalid));
-    }
-    return AGP_OK;  // X = L^-1 came out of the same launch
-  }
-  if (erow && ne > 0)
-    hipLaunchKernelGGL((k_set_ext_rows<T>), dim3((unsigned)((TILE * n + 255) / 256)), dim3(256), 0, c->stream,
-                       E + (ne - 1) * TILE * lde, lde, n, erow);
-  CholBatch<T> bt{};
-  bt.A[0] = A;
-  bt.X[0] = X;
-  bt.Dg[0] = Dg;
-  bt.E[0] = E;
-  AGPCHK(chol_columns<T>(c, bt, 1, ld, ldx, lde, ne, do_x, nt, info_dev, nvalid));
-  LAUNCHCHK(c);
-  if (do_x) AGPCHK(trtri_levels<T>(c, (const T*)A, ld, X, ldx, nt));
-  return AGP_OK;
-}
-
-// Task-graph launches whose inputs cannot be restored on the device (the factor is written in place: K_ZZ, the building blocks;
-// or the inverse rides along) are checked on the host instead: synchronise, and if the latch reads -1 stop using the task graph
-// on this context and tell the caller to rebuild its input and factor again (now with per-column launches).
-static agp_status dag_lost_dependency(agp_ctx* c, int32_t* info_dev, bool* lost) {
-  *lost = false;
-  int32_t info = 0;
-  HIPCHK(c, hipMemcpyAsync(&info, info_dev, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (info == -1) {
-    HIPCHK(c, hipMemsetAsync(info_dev, 0, sizeof(int32_t), c->stream));
-    if (!c->dag_off)
-      fprintf(stderr, "[agp_hip] warning: a task-graph factorisation lost a tile dependency (is another process using this GPU?); "
-                      "re-running it with plain launches, which this context uses for the next %lld steps\n",
-              (long long)c->dag_backoff);
-    dag_pause(c);
-    *lost = true;
-  }
-  return AGP_OK;
-}
-
-// nb <= DAG_MAX_NB independent problems of identical shape as ONE interleaved task-graph launch (see k_chol_dag): their chains
-// run side by side on nb CUs (workgroup index = tile * nb + problem: with 8 problems each one lives on its own XCD).
-constexpr int DAG_MAX_NB = 8;
-template <typename T>
-static agp_status potrf_dag_batch(agp_ctx* c, const CholBatch<T>& bt, int nb, int64_t ld, int64_t n, int64_t ldx, int64_t lde,
-                                  int64_t ne, int32_t* info_dev, int64_t nvalid, SafeSrc<T>* safe = nullptr) {
-  const int64_t nt = n / TILE;
-  bool split_used = false;
-  const int64_t fstride = ((nt + ne) * nt + 3 * nt + 1) * DAG_FS, nf = fstride * nb;
-  if (c->dag_cap < nf) {
-    if (c->dag_flags) (void)hipFree(c->dag_flags);
-    c->dag_flags = nullptr;
-    c->dag_cap = 0;
-    if (hipMalloc((void**)&c->dag_flags, sizeof(int32_t) * (size_t)(nf + 1024)) != hipSuccess) return AGP_ERR_NOMEM;
-    c->dag_cap = nf + 1024;
-    HIPCHK(c, hipMemsetAsync(c->dag_flags, 0, sizeof(int32_t) * (size_t)c->dag_cap, c->stream));
-    c->dag_epoch = 0;
-  }
-  c->dag_epoch += 1;
-  const int64_t ntiles = nt * (nt + 1) / 2 + ne * nt;
-  const int64_t hstride = ((2 * nt + ne) * nt + 3 * nt) * TILE * TILE;
-  T* H = nullptr;
-  const int hs = 0;
-  AGPCHK(dag_handover_acquire<T>(c, hstride * nb, hs, &H));
-  if (chain_split_wanted(ntiles * nb) && chain_split_ready(c)) {  // the nb chains as one kernel, all other tiles as another
-    DagSync ds{};
-    chain_split_arm(c, ds, nb);
-    split_used = true;
-    hipLaunchKernelGGL((k_chol_dag<T, true, true, false, true, false, 1>), dim3((unsigned)nb), dim3(CHOL_THREADS), 0, c->chain_stream, bt,
-                       nb, fstride, ld, ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch, (unsigned long long*)nullptr, H,
-                       hstride, (int64_t)0, (const T*)nullptr, 0, ds);
-    chain_split_wait_here(c);
-    hipLaunchKernelGGL((k_chol_dag<T, true, true, false, true, false, 2>), dim3((unsigned)(ntiles * nb)), dim3(CHOL_THREADS), 0,
-                       c->stream, bt, nb, fstride, ld, ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch,
-                       (unsigned long long*)nullptr, H, hstride, (int64_t)0, (const T*)nullptr, 0, ds);
-    LAUNCHCHK(c);
-  } else
-    hipLaunchKernelGGL((k_chol_dag<T, true, true, false, true>), dim3((unsigned)(ntiles * nb)), dim3(CHOL_THREADS), 0, c->stream, bt, nb, fstride, ld,
-                       ldx, lde, ne, nt, info_dev, nvalid, c->dag_flags, c->dag_epoch, (unsigned long long*)nullptr, H, hstride,
-                       (int64_t)0, (const T*)nullptr, 0, DagSync{});
-  LAUNCHCHK(c);
-  AGPCHK(dag_handover_release<T>(c, (3 * nt + (nt + ne) * nt) * TILE * TILE, hstride, nb, hs));
-  if (safe) {
-    safe->chain_done = split_used ? c->chain_ctr : nullptr;
-    safe->chain_want = c->chain_exits;
-    if (dag_test_abort()) hipLaunchKernelGGL(k_set_i32, dim3(1), dim3(1), 0, c->stream, info_dev, -1);
-    AGPCHK(launch_chol_safe<T>(c, bt, *safe, nb, ld, ldx, lde, ne, nt, info_dev, nvalid));
-  }
-  return AGP_OK;
-}
-
-// the same factorisation for nb <= CHOL_MAXB independent problems of identical shape in shared launches (no X = L^-1)
-template <typename T>
-static agp_status potrf_fused_batch(agp_ctx* c, const CholBatch<T>& bt, int nb, int64_t ld, int64_t n, int64_t ldx,
-                                    int64_t lde, int64_t ne, int32_t* info_dev, int64_t nvalid) {
-  const int64_t nt = n / TILE;
-  AGPCHK(chol_columns<T>(c, bt, nb, ld, ldx, lde, ne, 0, nt, info_dev, nvalid));
-  LAUNCHCHK(c);
-  return AGP_OK;
-}
-
-// Up to this many C tiles a GEMM / symmetric-product launch uses two k-groups per workgroup (512 threads, two waves per SIMD):
-// one four-wave workgroup reaches about half of a CU's MFMA rate, and up to ~4 workgroups per CU the second k-group is worth
-// more than the extra tiles in flight (measured, step times with 320 -> 1100: fp32 m = B = 2048 0.821 -> 0.789 ms, fp64 m = B =
-// 1536 0.703 -> 0.687 ms, 2048 1.37 -> 1.33 ms; C2's 256 / 136 tiles were below the old limit already).
-static constexpr int64_t kg2_limit() { return 1100; }
-static constexpr int64_t syrk_kg2_limit() { return kg2_limit(); }
-static int ctx_cus(agp_ctx* c) {
-  if (c->n_cu <= 0) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || v <= 0) v = 64;
-    c->n_cu = v;
-  }
-  return c->n_cu;
-}
-static agp_status ensure_bal_ws(agp_ctx* c, size_t need) {
-  if (c->bal_bytes < need) {
-    if (c->bal_ws) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      (void)hipFree(c->bal_ws);
-    }
-    c->bal_ws = nullptr;
-    c->bal_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->bal_ws, need));
-    c->bal_bytes = need;
-  }
-  return AGP_OK;
-}
-
-// S = A' diag(w) A (lower tiles mirrored), two k-groups per workgroup when the tile count underfills the chip
-template <typename T, int MODE>
-static agp_status syrk_tn(agp_ctx* c, const T* A, int64_t lda, int64_t n, int64_t Kdim, const T* w, int lower_a, T* out,
-                          int64_t ldo, T* eta2, const T* Kinv, int64_t ldm, T lr, const T* rvec = nullptr,
-                          T* eta1 = nullptr, const T* kinv_mu0 = nullptr) {
-  // rvec: nt rider workgroups also step eta1 (see k_syrk_tn); a dirty hand-over set of the task-graph Cholesky is refilled by
-  // further riders (from the fused step, MODE == SY_ETA2 with rvec, and from the packed statistics of the batch-parallel step,
-  // MODE == SY_PACK with rvec, whose riders store t = A' rvec into `eta1` instead of stepping it)
-  const int64_t nt = n / TILE, tiles = nt * (nt + 1) / 2, nrider = rvec ? nt : 0;
-  T* fillp = nullptr;
-  int64_t fused_used = 0, fstride = 0, nfill = 0;
-  int fnb = 0;
-  // (round 3: any symmetric-product launch refills a dirty set, e.g. X'X behind a factorisation with its inverse: the inline refill
-  //  in front of the NEXT task graph was a 6 us launch of its own on the hyper-parameter iteration's path)
-  if (c->h_dirty[0].on && c->htype == (int)sizeof(T) && out != nullptr) {
-    fillp = (T*)c->hset[0];
-    fused_used = c->h_dirty[0].used;
-    fstride = c->h_dirty[0].stride;
-    fnb = c->h_dirty[0].nb;
-    nfill = 96;
-    c->h_dirty[0].on = false;
-  }
-  // up to 160 tiles (C2: 136 on 256 CUs, one workgroup per CU) four k-groups: 16 waves per CU instead of 8 -- 58 -> 52 us at C2
-  // (step 0.379 -> 0.3735 ms)
-  const int kg = (tiles <= 160 && Kdim >= 8 * BK) ? 4 : (tiles <= syrk_kg2_limit() && Kdim >= 4 * BK) ? 2 : 1;
-  const int64_t grid = tiles + nrider + nfill;
-  if (kg == 4)
-    hipLaunchKernelGGL((k_syrk_tn<T, MODE, 4>), dim3((unsigned)grid), dim3(4 * NTHREADS), 0, c->stream, A, lda, Kdim, w,
-                       lower_a, out, ldo, eta2, Kinv, ldm, lr, tiles, rvec, eta1, kinv_mu0, nrider, fillp, fused_used, fstride,
-                       fnb);
-  else if (kg == 2)
-    hipLaunchKernelGGL((k_syrk_tn<T, MODE, 2>), dim3((unsigned)grid), dim3(2 * NTHREADS), 0, c->stream, A, lda, Kdim, w,
-                       lower_a, out, ldo, eta2, Kinv, ldm, lr, tiles, rvec, eta1, kinv_mu0, nrider, fillp, fused_used, fstride,
-                       fnb);
-  else
-    hipLaunchKernelGGL((k_syrk_tn<T, MODE, 1>), dim3((unsigned)grid), dim3(NTHREADS), 0, c->stream, A, lda, Kdim, w,
-                       lower_a, out, ldo, eta2, Kinv, ldm, lr, tiles, rvec, eta1, kinv_mu0, nrider, fillp, fused_used, fstride,
-                       fnb);
-  LAUNCHCHK(c);
-  return AGP_OK;
-}
-
-// out = X' X for lower-triangular X  (A^-1 from its inverse Cholesky factor): the symmetric product with the k range of every
-// tile starting at its first row, k-groups chosen like everywhere else (it ran with one k-group on 136 tiles: 60 us at m = 1024)
-// Round 4: from 8 block rows on, the balanced form (k_xtx_bal: units of at most ch k-blocks, partial tiles added by the last arriver
-// in unit order): 42 -> ~15 us at m = 1024 (below 8 block rows the one-workgroup-per-tile product stays).
-// (Dg ...: log det from the diagonal factors rides on the reduction launch; *rider_done says whether it did)
-template <typename T>
-static agp_status xtx_padded(agp_ctx* c, const T* X, int64_t ld, int64_t n, T* out, int64_t ldo, const T* Dg = nullptr,
-                             int64_t nvalid = 0, double* ld_out = nullptr, int32_t* status = nullptr, bool* rider_done = nullptr) {
-  if (rider_done) *rider_done = false;
-  const int64_t nt = n / TILE;
-  if (nt < 8)
-    return syrk_tn<T, SY_STORE>(c, X, ld, n, n, (const T*)nullptr, 1, out, ldo, (T*)nullptr, (const T*)nullptr, (int64_t)0, T(0));
-  const int ch = (int)std::max<int64_t>(2, (nt + XTX_MAXU - 1) / XTX_MAXU);  // at most XTX_MAXU units per tile
-  const int64_t nunits = xtx_bal_units(nt, ch), ntri = nt * (nt + 1) / 2;
-  AGPCHK(ensure_bal_ws(c, sizeof(T) * (size_t)nunits * TILE * TILE));
-  T* fillp = nullptr;
-  int64_t fused_used = 0, fstride = 0, nfill = 0;
-  int fnb = 0;
-  if (c->h_dirty[0].on && c->htype == (int)sizeof(T)) {  // hand-over refill riders, as in syrk_tn()
-    fillp = (T*)c->hset[0];
-    fused_used = c->h_dirty[0].used;
-    fstride = c->h_dirty[0].stride;
-    fnb = c->h_dirty[0].nb;
-    nfill = 96;
-    c->h_dirty[0].on = false;
-  }
-  hipLaunchKernelGGL((k_xtx_bal<T, 1>), dim3((unsigned)(nunits + nfill)), dim3(NTHREADS), 0, c->stream, X, ld, n, out, ldo,
-                       (T*)c->bal_ws, ch, nunits, fillp, fused_used, fstride, fnb);
-  const bool rider = Dg != nullptr && ld_out != nullptr;
-  hipLaunchKernelGGL((k_xtx_bal_reduce<T>), dim3((unsigned)(ntri + (rider ? 1 : 0))), dim3(NTHREADS), 0, c->stream, n, out, ldo,
-                     (const T*)c->bal_ws, ch, Dg, nvalid, ld_out, status);
-  LAUNCHCHK(c);
-  if (rider && rider_done) *rider_done = true;
-  return AGP_OK;
-}
-
-template <typename T, int EPI>
-static agp_status gemm_nt(agp_ctx* c, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t M, int64_t N, int64_t K,
-                          int tri_b, T* C, int64_t ldc, const T* E, int64_t lde, const T* v, T* p0, T* p1,
-                          int64_t ldp, const HkArgs<T>* hk = nullptr) {
-  dim3 g((unsigned)(N / TILE), (unsigned)(M / TILE));
-  const HkArgs<T> hka = hk ? *hk : HkArgs<T>{};  // (EPI_HK only)
-  // round 6: 128 x 64 C tiles (k_gemm_nt_tall) for the large fp64 products -- more 64-tiles than two k-groups are used for (C5's
-  // 4096-tile kappa GEMM).  AGP_GEMM_TALL=0 / 1 forces (1: wherever the shape allows, M a multiple of 128).
-  if constexpr (EPI == EPI_STORE || EPI == EPI_KAPPA) {
-    static const int tall = []() {
-      const char* e = getenv("AGP_GEMM_TALL");
-      return e ? (e[0] == '0' ? 0 : 1) : -1;
-    }();
-    const bool big = (N / TILE) * (M / TILE) > kg2_limit();
-    if (M % (2 * TILE) == 0 && K >= BK && (tall == 1 || (tall < 0 && big && sizeof(T) == 8))) {
-      dim3 gt((unsigned)(N / TILE), (unsigned)(M / (2 * TILE)));
-      hipLaunchKernelGGL((k_gemm_nt_tall<T, EPI>), gt, dim3(NTHREADS), 0, c->stream, A, lda, B, ldb, K, tri_b, C, ldc, E, lde, p0, p1,
-                         ldp);
-      LAUNCHCHK(c);
-      return AGP_OK;
-    }
-  }
-  // fewer tiles than ~1.25 waves of CUs: two k-groups per workgroup (2 waves per SIMD) instead of idle SIMD slots
-  if ((N / TILE) * (M / TILE) <= kg2_limit() && K >= 4 * BK)
-    hipLaunchKernelGGL((k_gemm_nt<T, EPI, 2>), g, dim3(2 * NTHREADS), 0, c->stream, A, lda, B, ldb, K, tri_b, C, ldc, E,
-                       lde, v, p0, p1, ldp, hka);
-  else
-    hipLaunchKernelGGL((k_gemm_nt<T, EPI, 1>), g, dim3(NTHREADS), 0, c->stream, A, lda, B, ldb, K, tri_b, C, ldc, E, lde,
-                       v, p0, p1, ldp, hka);
-  LAUNCHCHK(c);
-  return AGP_OK;
-}
-
-
-// kernelmatrix launch: the MFMA form (k_kernelmatrix_mma) up to D = KMM_MAXD, the direct-difference VALU kernel beyond (or with
-// AGP_KERNELMATRIX_VALU=1).  Same arguments as the kernels; `cgroups` = number of column groups a fused row-dot is split into
-// (<= 0: one group per column tile, like the VALU kernel; 1: the whole row in one workgroup -- streaming prediction).  Returns
-// the number of partial slices the row-dot consumer has to sum.
-// The MFMA kernel reads the Y side as ready-made tiles (scaled, zero-padded, with squared norms: k_scale_rows).  Callers whose Y
-// is a latent's inducing points pass the cached copy (ysc / ysn, see Svgp::ensure_zsc); otherwise the copy is made here into a
-// per-context scratch on the same stream (c may be null only together with a cached copy).
-static inline int kmm_dp(int64_t D) { return (int)((D + 7) / 8 * 8); }
-static inline bool kmm_usable(int64_t D) {
-  static const bool force_valu = []() {
-    const char* e = getenv("AGP_KERNELMATRIX_VALU");
-    return e && e[0] == '1';
-  }();
-  return D <= KMM_MAXD && !force_valu;
-}
-template <typename T>
-static int launch_kernelmatrix(agp_ctx* c, hipStream_t stream, const T* X, int64_t ldx, const int64_t* idx, int64_t n, const T* Y,
-                               int64_t ldy, int64_t p, int64_t D, const T* scales, int kind, T variance, T* out, int64_t ldo,
-                               int64_t n_out, int64_t p_out, int sym, T diag_add, const T* alpha, T* part, int64_t ldp,
-                               int64_t cgroups = 0, const T* ysc = nullptr, const T* ysn = nullptr) {
-  const int64_t nct = (p_out + TILE - 1) / TILE, nrt = (n_out + TILE - 1) / TILE;
-  if (!kmm_usable(D)) {
-    hipLaunchKernelGGL((k_kernelmatrix<T>), dim3((unsigned)nct, (unsigned)nrt), dim3(NTHREADS), 0, stream, X, ldx, idx, n, Y, ldy, p,
-                       D, scales, kind, variance, out, ldo, n_out, p_out, sym, diag_add, alpha, part, ldp);
-    return (int)nct;
-  }
-  const int Dp = kmm_dp(D);
-  const int64_t p_pad = nct * TILE;
-  if (!ysc) {
-    const size_t need = sizeof(T) * (size_t)(p_pad * Dp + p_pad);
-    if (c->kmm_bytes < need) {
-      if (c->kmm_scratch) {
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(c->kmm_scratch);
-      }
-      c->kmm_scratch = nullptr;
-      c->kmm_bytes = 0;
-      if (hipMalloc(&c->kmm_scratch, need + need / 4) != hipSuccess) return -1;
-      c->kmm_bytes = need + need / 4;
-    }
-    T* sc0 = (T*)c->kmm_scratch;
-    hipLaunchKernelGGL((k_scale_rows<T>), dim3((unsigned)((p_pad + 3) / 4)), dim3(256), 0, stream, Y, ldy, p, p_pad, D, Dp, scales, sc0,
-                       sc0 + p_pad * Dp);
-    ysc = sc0;
-    ysn = sc0 + p_pad * Dp;
-  }
-  const size_t sh = kmm_smem_bytes<T>(Dp);
-  const int64_t groups = cgroups <= 0 ? nct : std::min<int64_t>(cgroups, nct);
-  const int64_t ctiles = (nct + groups - 1) / groups;
-  const int64_t g_eff = (nct + ctiles - 1) / ctiles;
-  const dim3 grid((unsigned)g_eff, (unsigned)nrt);
-#define AGP_KMM_LAUNCH(KIND)                                                                                                  \
-  do {                                                                                                                        \
-    if (sh > 64 * 1024) { /* more than 64 KB of dynamic LDS has to be requested once per kernel */                            \
-      static size_t asked = 0;                                                                                                \
-      if (sh > asked) {                                                                                                       \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kernelmatrix_mma<T, KIND>),                                \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                                       \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kernelmatrix_mma<T, KIND, 1>),                             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                                       \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kernelmatrix_mma<T, KIND, 2>),                             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                                       \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kernelmatrix_mma<T, KIND, 3>),                             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);                                       \
-        asked = sh;                                                                                                           \
-      }                                                                                                                       \
-    }                                                                                                                         \
-    if (out == nullptr && !sym && alpha != nullptr)                                                                           \
-      hipLaunchKernelGGL((k_kernelmatrix_mma<T, KIND, 1>), grid, dim3(NTHREADS), sh, stream, X, ldx, idx, n, ysc, ysn, p, D, \
-                         Dp, scales, variance, out, ldo, n_out, p_out, sym, diag_add, alpha, part, ldp, ctiles);              \
-    else if (out != nullptr && !sym && alpha == nullptr)                                                                      \
-      hipLaunchKernelGGL((k_kernelmatrix_mma<T, KIND, 2>), grid, dim3(NTHREADS), sh, stream, X, ldx, idx, n, ysc, ysn, p, D, \
-                         Dp, scales, variance, out, ldo, n_out, p_out, sym, diag_add, alpha, part, ldp, ctiles);              \
-    else if (out != nullptr && sym && alpha == nullptr)                                                                       \
-      hipLaunchKernelGGL((k_kernelmatrix_mma<T, KIND, 3>), grid, dim3(NTHREADS), sh, stream, X, ldx, idx, n, ysc, ysn, p, D, \
-                         Dp, scales, variance, out, ldo, n_out, p_out, sym, diag_add, alpha, part, ldp, ctiles);              \
-    else                                                                                                                      \
-      hipLaunchKernelGGL((k_kernelmatrix_mma<T, KIND>), grid, dim3(NTHREADS), sh, stream, X, ldx, idx, n, ysc, ysn, p, D,    \
-                         Dp, scales, variance, out, ldo, n_out, p_out, sym, diag_add, alpha, part, ldp, ctiles);              \
-  } while (0)
-  switch (kind) {
-    case AGP_K_SQEXP: AGP_KMM_LAUNCH(K_SQEXP); break;
-    case AGP_K_MATERN52: AGP_KMM_LAUNCH(K_MATERN52); break;
-    case AGP_K_MATERN32: AGP_KMM_LAUNCH(K_MATERN32); break;
-    default: AGP_KMM_LAUNCH(K_EXPONENTIAL); break;
-  }
-#undef AGP_KMM_LAUNCH
-  return (int)g_eff;
-}
 
 // ---- model ---------------------------------------------------------------------------------------------------
 struct KernelHost {
@@ -2043,11 +879,14 @@ struct Svgp : SvgpBase {
         src.kjitter = (T)jitter;
         if (!logdetK_dev) AGPCHK(dmalloc(ctx, &logdetK_dev, nl));
         const int li = (int)(&g - lat.data());
-        bool kinv_done = false;  // K^-1 = X' X (and log det K) by product workgroups of the same launch (task graph), else below
-        AGPCHK(potrf_fused<T>(ctx, g.L, mp, mp, g.Xk, mp, g.DgK, (T*)nullptr, 0, 0, 1, infoK_dev, m, (const T*)nullptr, true, &src,
-                              nullptr, nullptr, nullptr, nullptr, g.Kinv, &kinv_done, logdetK_dev + li, info_dev));
-        bool ld_done = kinv_done;
-        if (!kinv_done)
+        PotrfReq<T> rq{};
+        rq.A = g.L, rq.ld = mp, rq.n = mp, rq.X = g.Xk, rq.ldx = mp, rq.Dg = g.DgK, rq.do_x = 1, rq.info_dev = infoK_dev, rq.nvalid = m;
+        rq.safe = &src;
+        // K^-1 = X' X (and log det K) by product workgroups of the same launch (task graph, rq.p_done), else below
+        rq.Pout = g.Kinv, rq.ld_out = logdetK_dev + li, rq.ld_status = info_dev;
+        AGPCHK(potrf_fused<T>(ctx, rq));
+        bool ld_done = rq.p_done;
+        if (!rq.p_done)
           AGPCHK(xtx_padded<T>(ctx, g.Xk, mp, mp, g.Kinv, mp, (const T*)g.DgK, m, logdetK_dev + li, info_dev, &ld_done));
         if (!ld_done)
           hipLaunchKernelGGL((k_logdiag_sum<T>), dim3(1), dim3(1024), 0, st(), (const T*)g.DgK, m, logdetK_dev + li, info_dev);
@@ -2511,8 +1350,7 @@ struct Svgp : SvgpBase {
           src.eta2[q] = g.eta2;
         }
         if (nb == 1) {  // also writes the [eta1' ; 0] block when it falls back to per-column launches
-          bool defer = nl == 1;  // single latent: the row-statistics launch below carries the fallback (k_safe_rowstats)
-          ProHost<T> ph{};
+          ProArgs<T> ph{};
           if (use_pro) {
             Latent& g0 = lat[0];
             ph.ldk = mp;
@@ -2573,22 +1411,33 @@ struct Svgp : SvgpBase {
             ea.lam = lam_dev;
             ea.gamma = gamma;
           }
-          AGPCHK(potrf_fused<T>(ctx, bt.A[0], mp, mp, bt.X[0], mp, bt.Dg[0], bt.E[0], mp, nel, 0, info_dev, m,
-                                (const T*)lat[todo[l0]].eta1, false, &src, &defer, sync_step ? &ssync : nullptr,
-                                use_pro ? &ph : nullptr, use_epi ? &ea : nullptr));
+          PotrfReq<T> rq{};
+          rq.A = bt.A[0], rq.ld = mp, rq.n = mp, rq.X = bt.X[0], rq.ldx = mp, rq.Dg = bt.Dg[0], rq.E = bt.E[0], rq.lde = mp, rq.ne = nel;
+          rq.info_dev = info_dev, rq.nvalid = m;
+          rq.erow = lat[todo[l0]].eta1, rq.want_l = false, rq.safe = &src;
+          rq.defer_safe = nl == 1;  // single latent: the row-statistics launch below carries the fallback (k_safe_rowstats)
+          if (sync_step) rq.ssync = &ssync;
+          if (use_pro) rq.pro = &ph;
+          if (use_epi) rq.epi = &ea;
+          AGPCHK(potrf_fused<T>(ctx, rq));
           s00_for.on = false;
           if (use_pro) {  // the launch has taken the pending step (had it been refused, the step would still be pending for flush())
             pend.on = pendp.on = pendp.overlap = false;
             n_prologue += 1;
           }
-          merged_safe = defer;
+          merged_safe = rq.defer_safe;
           launches += dag_nb > 0 ? 1 : chol_launch_count(ntl, nel);
-        } else if (dag_nb > 0) {
-          AGPCHK(potrf_dag_batch<T>(ctx, bt, nb, mp, mp, mp, mp, nel, info_dev, m, &src));
-          launches += 1;
         } else {
-          AGPCHK(potrf_fused_batch<T>(ctx, bt, nb, mp, mp, mp, mp, nel, info_dev, m));
-          launches += chol_launch_count(ntl, nel);
+          PotrfBatchReq<T> rq{};
+          rq.bt = &bt, rq.nb = nb, rq.ld = mp, rq.n = mp, rq.ldx = mp, rq.lde = mp, rq.ne = nel, rq.info_dev = info_dev, rq.nvalid = m;
+          if (dag_nb > 0) {
+            rq.safe = &src;
+            AGPCHK(potrf_dag_batch<T>(ctx, rq));
+            launches += 1;
+          } else {
+            AGPCHK(potrf_fused_batch<T>(ctx, rq));
+            launches += chol_launch_count(ntl, nel);
+          }
         }
       }
       if (!todo.empty()) AGPCHK(timing_end(launches));
@@ -3709,7 +2558,7 @@ struct Svgp : SvgpBase {
     AGPCHK(run_deferred_safe());
     if (pendp.on) AGPCHK(flush());
     g.C_valid = false;
-    ProHost<T> ph{};
+    ProArgs<T> ph{};
     bool use_pro = false;
     if (pend.on) {
       use_pro = nl == 1 && pro_allowed() && chol_use_dag(ctx, mp / TILE, Bq / TILE + 1) &&
@@ -3749,15 +2598,18 @@ struct Svgp : SvgpBase {
     // (SafeSrc::want_x), so that no host check -- no stream synchronisation -- sits behind the launch (round 3: the hyper-parameter
     // iteration used to wait here once per step)
     src.want_x = with_x ? 1 : 0;
+    PotrfReq<T> rq{};
+    rq.A = g.La, rq.ld = mp, rq.n = mp, rq.X = g.Xa, rq.ldx = mp, rq.Dg = g.DgA, rq.E = g.Wbuf, rq.lde = mp, rq.ne = Bq / TILE + 1;
+    rq.do_x = with_x, rq.info_dev = info_dev, rq.nvalid = m;
+    rq.erow = g.eta1, rq.want_l = false, rq.safe = &src, rq.defer_safe = tail != nullptr;
+    if (use_pro) rq.pro = &ph;
     // with_x: Sigma = Xa' Xa is what every caller forms next -- product workgroups at the end of the same task-graph launch do it
-    bool sigma_done = false;
-    bool defer = tail != nullptr;
-    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, Bq / TILE + 1, with_x, info_dev, m,
-                          (const T*)g.eta1, false, &src, tail ? &defer : nullptr, nullptr, use_pro ? &ph : nullptr,
-                          (const EpiArgs<T>*)nullptr, with_x ? g.Sigma : (T*)nullptr, &sigma_done));
+    if (with_x) rq.Pout = g.Sigma;
+    AGPCHK(potrf_fused<T>(ctx, rq));
+    const bool sigma_done = rq.p_done;
     if (tail) {
-      tail->on = defer;
-      if (defer) {
+      tail->on = rq.defer_safe;
+      if (rq.defer_safe) {
         tail->bt = CholBatch<T>{};
         tail->bt.A[0] = g.La;
         tail->bt.X[0] = g.Xa;
@@ -4983,7 +3835,10 @@ struct Vgp : Svgp<double> {
     src.eta2[0] = g.eta2;
     src.want_x = 1;
     AGPCHK(timing_begin());
-    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, 1, 1, info_dev, m, (const T*)g.eta1, false, &src));
+    PotrfReq<T> rq{};
+    rq.A = g.La, rq.ld = mp, rq.n = mp, rq.X = g.Xa, rq.ldx = mp, rq.Dg = g.DgA, rq.E = g.Wbuf, rq.lde = mp, rq.ne = 1, rq.do_x = 1;
+    rq.info_dev = info_dev, rq.nvalid = m, rq.erow = g.eta1, rq.want_l = false, rq.safe = &src;
+    AGPCHK(potrf_fused<T>(ctx, rq));
     AGPCHK(timing_end(chol_use_dag(ctx, mp / TILE, 1) ? 1 : chol_launch_count(mp / TILE, 1)));
     g.la_state = 1;
     g.xa_valid = true;
@@ -5236,7 +4091,10 @@ struct Gp : Vgp {
     src.gps2 = lam_dev;
     src.mz = m;
     AGPCHK(timing_begin());
-    AGPCHK(potrf_fused<T>(ctx, g.La, mp, mp, g.Xa, mp, g.DgA, g.Wbuf, mp, 1, 1, info_dev, m, (const T*)g.eta1, false, &src));
+    PotrfReq<T> rq{};
+    rq.A = g.La, rq.ld = mp, rq.n = mp, rq.X = g.Xa, rq.ldx = mp, rq.Dg = g.DgA, rq.E = g.Wbuf, rq.lde = mp, rq.ne = 1, rq.do_x = 1;
+    rq.info_dev = info_dev, rq.nvalid = m, rq.erow = g.eta1, rq.want_l = false, rq.safe = &src;
+    AGPCHK(potrf_fused<T>(ctx, rq));
     AGPCHK(timing_end(chol_use_dag(ctx, mp / TILE, 1) ? 1 : chol_launch_count(mp / TILE, 1)));
     HIPCHK(ctx, hipMemcpyAsync(g.v, g.Wbuf, sizeof(T) * mp, hipMemcpyDeviceToDevice, st()));
     const bool ref_m0 = gp_ref() && g.mu0;
@@ -5824,7 +4682,9 @@ struct Nvgp : Vgp {
       hipLaunchKernelGGL((k_nvi_candidate<T>), grid2(mp, mp), blk2, 0, st(), m, mp, mp, (const T*)g.Sigma, Dm, alpha,
                          keep_c ? nv_C : (T*)nullptr, q.F);
       LAUNCHCHK(ctx);
-      AGPCHK(potrf_fused<T>(ctx, q.F, mp, mp, q.X, mp, q.Dg, (T*)nullptr, 0, 0, do_x, nv_info, m));
+      PotrfReq<T> rq{};
+      rq.A = q.F, rq.ld = mp, rq.n = mp, rq.X = q.X, rq.ldx = mp, rq.Dg = q.Dg, rq.do_x = do_x, rq.info_dev = nv_info, rq.nvalid = m;
+      AGPCHK(potrf_fused<T>(ctx, rq));
       HIPCHK(ctx, hipMemcpyAsync(info, nv_info, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
       HIPCHK(ctx, hipStreamSynchronize(st()));
       if (*info != -1 || pass == 1) break;
@@ -6306,14 +5166,16 @@ static agp_status bb_potrf(agp_ctx* ctx, void* a, int64_t lda, int64_t n, double
   HIPCHK(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
   T* Dg = nullptr;
   AGPCHK(dmalloc(ctx, &Dg, np * TILE));
-  AGPCHK(potrf_fused<T>(ctx, Ap, np, np, X, np, Dg, (T*)nullptr, 0, 0, 0, info, n));
+  PotrfReq<T> rq{};
+  rq.A = Ap, rq.ld = np, rq.n = np, rq.X = X, rq.ldx = np, rq.Dg = Dg, rq.info_dev = info, rq.nvalid = n;
+  AGPCHK(potrf_fused<T>(ctx, rq));
   if (chol_use_dag(ctx, np / TILE)) {
     bool lost = false;
     AGPCHK(dag_lost_dependency(ctx, info, &lost));
     if (lost) {  // the input is still intact in `a`: pad it again and factor with per-column launches
       hipLaunchKernelGGL((k_copy2d<T>), grid2(np, np), blk2, 0, ctx->stream, (const T*)a, lda, n, n, Ap, np, np, np, T(1), T(1));
       if (jitter != 0.0) hipLaunchKernelGGL((k_add_diag<T>), grid1(n), dim3(256), 0, ctx->stream, Ap, np, n, (T)jitter);
-      AGPCHK(potrf_fused<T>(ctx, Ap, np, np, X, np, Dg, (T*)nullptr, 0, 0, 0, info, n));
+      AGPCHK(potrf_fused<T>(ctx, rq));
     }
   }
   hipLaunchKernelGGL((k_publish_diag<T>), dim3((unsigned)(np / TILE)), dim3(256), 0, ctx->stream, Ap, np, (const T*)Dg);
@@ -6349,13 +5211,15 @@ static agp_status bb_spd_inverse(agp_ctx* ctx, const void* a, int64_t lda, int64
   AGPCHK(dmalloc(ctx, &info, 1));
   AGPCHK(dmalloc(ctx, &sc, 1));
   HIPCHK(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
-  AGPCHK(potrf_fused<T>(ctx, Ap, np, np, X, np, Tw, (T*)nullptr, 0, 0, 1, info, n));
+  PotrfReq<T> rq{};
+  rq.A = Ap, rq.ld = np, rq.n = np, rq.X = X, rq.ldx = np, rq.Dg = Tw, rq.do_x = 1, rq.info_dev = info, rq.nvalid = n;
+  AGPCHK(potrf_fused<T>(ctx, rq));
   if (chol_use_dag(ctx, np / TILE)) {
     bool lost = false;
     AGPCHK(dag_lost_dependency(ctx, info, &lost));
     if (lost) {
       hipLaunchKernelGGL((k_copy2d<T>), grid2(np, np), blk2, 0, ctx->stream, (const T*)a, lda, n, n, Ap, np, np, np, T(1), T(1));
-      AGPCHK(potrf_fused<T>(ctx, Ap, np, np, X, np, Tw, (T*)nullptr, 0, 0, 1, info, n));
+      AGPCHK(potrf_fused<T>(ctx, rq));
     }
   }
   AGPCHK(xtx_padded<T>(ctx, X, np, np, Inv, np));

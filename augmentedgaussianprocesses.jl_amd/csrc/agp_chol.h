@@ -1117,7 +1117,7 @@ __device__ __forceinline__ bool grid_barrier(unsigned* ctr, unsigned target, int
 }
 
 // (a device function so that the kernel which follows the task graph in a single-latent step -- row statistics and local
-//  update -- can carry the fallback itself instead of waiting behind an extra launch: k_safe_rowstats in agp_capi.hip.
+//  update -- can carry the fallback itself instead of waiting behind an extra launch: k_safe_rowstats in agp_chol_host.h.
 //  Returns whether the fallback ran; every thread of every workgroup of a <= n_cu grid must call.)
 template <typename T>
 __device__ __forceinline__ bool chol_safe_body(const CholBatch<T>& bt, const SafeSrc<T>& src, int nb, int64_t ld, int64_t ldx,
@@ -1289,8 +1289,8 @@ constexpr int DAG_FS = 64;  // flag stride in int32: one 256-byte line per flag,
 
 // ---- self-validating hand-over -------------------------------------------------------------------------------------
 // Tiles travel between workgroups through a hand-over area H (one contiguous 64x64 slot per tile) that the host fills with a
-// SENTINEL bit pattern (a signalling-NaN payload no arithmetic produces) before the launch (and again after it: see Dirty in
-// agp_capi.hip).  The producer stores the tile there
+// SENTINEL bit pattern (a signalling-NaN payload no arithmetic produces) before the launch (and again after it: see agp_ctx::Dirty in
+// agp_ctx.h).  The producer stores the tile there
 // with coherent (sc1) 8-byte stores and then raises a flag; the flag is only a HINT that the data is on its way: the consumer
 // loads the slot with coherent loads and re-loads any element that still reads as the sentinel.  8-byte stores are single-copy
 // atomic, so an element is either the sentinel or final -- no ordering between the data stores and the flag store is needed,
@@ -1926,7 +1926,7 @@ struct ProdArgs {
   int32_t* status = nullptr;
 };
 
-// Development aid, compiled in only with -DAGP_STEP_TRACE (agp_capi.hip: AGP_STEP_TRACE=<file> then names the dump): wall-clock
+// Development aid, compiled in only with -DAGP_STEP_TRACE (agp_ctx.h: AGP_STEP_TRACE=<file> then names the dump): wall-clock
 // stamps (100 MHz) across the boundary between two CAVI-step launches with a prologue, one record of STRACE_SLOTS words per launch.
 //   [0, 2048)     PRO_TS's points (below), X_{nt-1} published (STRACE_XPUB), per extension row R of the last block column
 //                 (STRACE_EXT + 4 (R - nt) + q): q = 0 X seen, 1 W stored and signalled, 2 v tile read (epilogue), 3 rows finished;

@@ -1,7 +1,8 @@
 // agp_nvi.h -- numerical variational inference by Gauss-Hermite quadrature (QuadratureVI, src/inference/numericalVI.jl,
 // src/inference/quadratureVI.jl): the point-wise expectations, the gradient assembly, the optimiser rules on (mu, Sigma) and the
 // candidate Sigma + alpha Symmetric(dSigma) of the positive-definiteness backtracking.  The m x m products and the factorisation
-// of the candidate are the library's own (gemm_nt, potrf_fused); the steps are Nvgp::nvi_step and Nsvgp::nvi_step (agp_capi.hip).
+// of the candidate are the library's own (gemm_nt, agp_blas_host.h; potrf_fused, agp_chol_host.h); the steps are Nvgp::nvi_step and
+// Nsvgp::nvi_step (agp_capi.hip).
 // At the end of the file: the expectations by Monte-Carlo integration over K latents (MCIntegrationVI, src/inference/MCVI.jl), which feed
 // the same step once per latent.
 // Three definitions of the reference are restated in their intended form (include/agp_hip.h, "NUMERICAL INFERENCE"):
