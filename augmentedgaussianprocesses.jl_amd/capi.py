@@ -40,6 +40,8 @@ SHARD_LATENT, SHARD_BATCH = 0, 1
 COMM_ID_BYTES = 128
 # int32_t (*agp_allreduce_fn)(void* user, void* buf, int64_t count, int32_t dtype, void* hip_stream)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)
+PW_OMEGA, PW_PHASE, PW_W, PW_V, PW_E = range(5)  # agp_pathwise_get
+PATHWISE_WS_BYTES = 64 * 1024 * 1024
 MAT_L, MAT_KINV, MAT_KNM, MAT_KAPPA, VEC_KTILDE, VEC_MEAN_F, VEC_VAR_F, VEC_THETA, VEC_C, VEC_GAMMA, VEC_ALPHA = range(11)
 
 
@@ -180,6 +182,12 @@ SYMBOLS = {
     "agp_svgp_mcvi_configure": (_I32, [_VP, _I32, C.c_uint64, _I32, _I32, _DBL, _DBL, _DBL, _DBL]),
     "agp_mc_normals": (_I32, [_VP, C.c_uint64, _I64, _I32, _I32, _I32, _VP]),
     "agp_mc_expectations": (_I32, [_VP, C.POINTER(LikDesc), _VP, _VP, _VP, _I64, _I32, _I32, C.c_uint64, _I64, _I32, _VP, _VP, _VP]),
+    "agp_svgp_pathwise_draw": (_I32, [_VP, _I32, _I32, C.c_uint64, _I64, _PVP]),
+    "agp_pathwise_eval": (_I32, [_VP, _VP, _I64, _I64, _VP, _I64]),
+    "agp_pathwise_info": (_I32, [_VP, _PI32, _PI32, _PI32, _PI64, _PI64]),
+    "agp_pathwise_get": (_I32, [_VP, _I32, _I32, _VP, _I64]),
+    "agp_pathwise_destroy": (_I32, [_VP]),
+    "agp_pathwise_features": (_I32, [_VP, _PK, _I64, _I32, C.c_uint64, _I64, _I32, _VP, _VP]),
 }
 
 _lib = None

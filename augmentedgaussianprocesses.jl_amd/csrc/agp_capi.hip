@@ -6,7 +6,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "agp_cavi.h"
@@ -16,6 +18,7 @@
 #include "agp_linalg.h"
 #include "agp_nvi.h"
 #include "agp_rand.h"
+#include "agp_pathwise.h"
 // (the host layers after every kernel header, as they stood in this file: the order of the kernels in the code object is kept)
 #include "agp_ctx.h"
 #include "agp_chol_host.h"
@@ -141,6 +144,12 @@ struct SvgpBase {
   }
   virtual agp_status nvi_info(int, double*, int64_t*, int64_t*) { return not_numerical("agp_svgp_nvi_info"); }
   virtual agp_status nvi_state(int, int, void*, void*, int64_t*) { return not_numerical("agp_svgp_nvi_state"); }
+  // pathwise sampling ("PATHWISE SAMPLING"): Svgp<double>, Vgp and Gp draw; every other class refuses by name
+  virtual agp_status pathwise_draw(int n_features, int n_samples, uint64_t seed, int64_t t, agp_pathwise** out) = 0;
+  agp_status pathwise_refused(const char* why) {
+    ctx->err = std::string("agp_svgp_pathwise_draw: ") + why;
+    return AGP_ERR_UNSUPPORTED;
+  }
   int64_t n_opt = 1;  // RobbinsMonro counter (optimisers.jl:12)
   bool in_cavi_step = false;  // step_local is running as the first half of agp_svgp_cavi_step (its tail may then be deferred)
   int64_t n_prologue = 0;  // CAVI steps whose natural-gradient part rode on the next step's task-graph launch (agp_svgp_step_counters)
@@ -208,6 +217,216 @@ static void dcheck(hipError_t e, int line) {
   if (e != hipSuccess) fprintf(stderr, "[agp_hip] teardown: %s (agp_capi.hip:%d)\n", hipGetErrorString(e), line);
 }
 #define dfree(p) dcheck(hipFree(p), __LINE__)
+
+// ---- pathwise sampling (include/agp_hip.h, "PATHWISE SAMPLING"; device code in agp_pathwise.h) -------------------------------------
+// A draw owns everything it evaluates with: per latent the snapshot of the kernel (kind, variance, scales), of Z with its ready-made
+// kernel-matrix tiles, the spectral tables, [W' | V'] (Sp x (Lp + mp), sample-major: the B side of the evaluation's one gemm_nt) and
+// E; shared by the latents the workspace [Phi(x) | k(x, Z)] of one chunk of test points and the chunk's result before it is copied
+// into the caller's rows.
+struct agp_pathwise {
+  agp_ctx* ctx = nullptr;
+  int nl = 0, L = 0, S = 0;
+  int64_t Lp = 0, Sp = 0, m = 0, mp = 0, D = 0, ldw = 0, CH = 0;
+  struct Lat {
+    int kind = AGP_K_SQEXP;
+    double variance = 1.0, amp = 0.0;
+    double *scales = nullptr, *Z = nullptr, *Zsc = nullptr, *zn = nullptr, *omega = nullptr, *phase = nullptr, *WV = nullptr,
+           *E = nullptr;
+  };
+  std::vector<Lat> lat;
+  double *ws = nullptr, *Fs = nullptr;
+  ~agp_pathwise() {
+    for (auto& a : lat)
+      for (double* q : {a.scales, a.Z, a.Zsc, a.zn, a.omega, a.phase, a.WV, a.E})
+        if (q) (void)hipFree(q);
+    for (double* q : {ws, Fs})
+      if (q) (void)hipFree(q);
+  }
+};
+// device buffers that live as long as one call
+struct PwScratch {
+  std::vector<void*> v;
+  ~PwScratch() {
+    for (void* q : v) (void)hipFree(q);
+  }
+  template <typename U>
+  agp_status get(agp_ctx* c, U** q, int64_t n) {
+    AGPCHK(dmalloc(c, q, n));
+    v.push_back(*q);
+    return AGP_OK;
+  }
+};
+constexpr int64_t PW_MAX = 65536, PW_CTR_MAX = (int64_t)0xFFFFFFFFll;
+static agp_status pw_check_spectral(agp_ctx* ctx, const char* who, int64_t D, int64_t L, int64_t t) {
+  if (L < 1 || L > PW_MAX) {
+    ctx->err = std::string(who) + ": n_features must lie in [1, 65536] (got " + std::to_string(L) + ")";
+    return AGP_ERR_INVALID;
+  }
+  if (D < 1 || L * D > PW_CTR_MAX) {
+    ctx->err = std::string(who) + ": D >= 1 and n_features * D below 2^32 (one 32-bit counter word per frequency element)";
+    return AGP_ERR_INVALID;
+  }
+  if (t < 0 || t > PW_CTR_MAX) {
+    ctx->err = std::string(who) + ": the draw counter t is one 32-bit word of the generator's counter, 0 <= t < 2^32";
+    return AGP_ERR_INVALID;
+  }
+  return AGP_OK;
+}
+static agp_status pw_check_draw(agp_ctx* ctx, int64_t m, int64_t D, int64_t L, int64_t S, int64_t t, agp_pathwise** out) {
+  const char* who = "agp_svgp_pathwise_draw";
+  if (!out) {
+    ctx->err = std::string(who) + ": out must be given";
+    return AGP_ERR_INVALID;
+  }
+  AGPCHK(pw_check_spectral(ctx, who, D, L, t));
+  if (S < 1 || S > PW_MAX) {
+    ctx->err = std::string(who) + ": n_samples must lie in [1, 65536] (got " + std::to_string(S) + ")";
+    return AGP_ERR_INVALID;
+  }
+  if (L * S > PW_CTR_MAX || m * S > PW_CTR_MAX) {
+    ctx->err = std::string(who) + ": n_features * n_samples and m * n_samples must stay below 2^32 (counter words of W and E)";
+    return AGP_ERR_INVALID;
+  }
+  return AGP_OK;
+}
+static agp_status pw_spectral(agp_ctx* ctx, int kind, int64_t D, int64_t L, uint64_t seed, int64_t t, int latent, double* omega,
+                              double* phase) {
+  hipLaunchKernelGGL(agp::k_pw_spectral, grid1(L * D), dim3(256), 0, ctx->stream, L * D, D, kind, seed, (uint32_t)t,
+                     (uint32_t)(4 + 8 * latent), omega, phase);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+// the empty draw: sizes, the chunk of the evaluation workspace under AGP_PATHWISE_WS_BYTES, the shared buffers
+static agp_status pw_create(agp_ctx* ctx, int nl, int64_t m, int64_t D, int L, int S, std::unique_ptr<agp_pathwise>* out) {
+  std::unique_ptr<agp_pathwise> p(new agp_pathwise());
+  p->ctx = ctx, p->nl = nl, p->L = L, p->S = S, p->m = m, p->D = D;
+  p->Lp = rup64(L), p->Sp = rup64(S), p->mp = rup64(m), p->ldw = p->Lp + p->mp;
+  const int64_t per_point = 8 * (p->ldw + p->Sp);
+  p->CH = std::min<int64_t>(4096, std::max<int64_t>(64, (int64_t)AGP_PATHWISE_WS_BYTES / per_point / 64 * 64));
+  p->lat.resize(nl);
+  AGPCHK(dmalloc(ctx, &p->ws, p->CH * p->ldw));
+  AGPCHK(dmalloc(ctx, &p->Fs, p->Sp * p->CH));
+  *out = std::move(p);
+  return AGP_OK;
+}
+// one latent's snapshot and tables: kernel, scales (D + 1 doubles as the handle keeps them: the variance behind the scales), Z
+// (m x D, dense), its kernel-matrix tiles, Omega and the phases, W (into the left columns of [W' | V']) and E (mp x Sp)
+static agp_status pw_add_latent(agp_pathwise& p, int l, int kind, double variance, const double* scales_dev, const double* Z_dev,
+                                uint64_t seed, int64_t t) {
+  agp_ctx* ctx = p.ctx;
+  agp_pathwise::Lat& a = p.lat[l];
+  a.kind = kind, a.variance = variance, a.amp = std::sqrt(2.0 * variance / (double)p.L);
+  AGPCHK(dmalloc(ctx, &a.scales, p.D + 1));
+  AGPCHK(dmalloc(ctx, &a.Z, p.m * p.D));
+  AGPCHK(dmalloc(ctx, &a.omega, (int64_t)p.L * p.D));
+  AGPCHK(dmalloc(ctx, &a.phase, p.L));
+  AGPCHK(dmalloc(ctx, &a.WV, p.Sp * p.ldw));
+  AGPCHK(dmalloc(ctx, &a.E, p.mp * p.Sp));
+  HIPCHK(ctx, hipMemcpyAsync(a.scales, scales_dev, sizeof(double) * (p.D + 1), hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(a.Z, Z_dev, sizeof(double) * p.m * p.D, hipMemcpyDeviceToDevice, ctx->stream));
+  if (kmm_usable(p.D)) {
+    const int Dp = kmm_dp(p.D);
+    AGPCHK(dmalloc(ctx, &a.Zsc, p.mp * Dp));
+    AGPCHK(dmalloc(ctx, &a.zn, p.mp));
+    hipLaunchKernelGGL((agp::k_scale_rows<double>), dim3((unsigned)((p.mp + 3) / 4)), dim3(256), 0, ctx->stream, (const double*)a.Z,
+                       p.D, p.m, p.mp, p.D, Dp, (const double*)a.scales, a.Zsc, a.zn);
+    LAUNCHCHK(ctx);
+  }
+  AGPCHK(pw_spectral(ctx, kind, p.D, p.L, seed, t, l, a.omega, a.phase));
+  const uint32_t s0 = (uint32_t)(4 + 8 * l);
+  HIPCHK(ctx, hipMemsetAsync(a.WV, 0, sizeof(double) * p.Sp * p.ldw, ctx->stream));
+  hipLaunchKernelGGL(agp::k_pw_table, grid1(p.Lp * p.Sp), dim3(256), 0, ctx->stream, (int64_t)p.L, (int64_t)p.S, p.Lp, p.Sp,
+                     (int64_t)1, p.ldw, 0, seed, (uint32_t)t, s0 + agp::PW_STREAM_W, a.WV);
+  hipLaunchKernelGGL(agp::k_pw_table, grid1(p.mp * p.Sp), dim3(256), 0, ctx->stream, p.m, (int64_t)p.S, p.mp, p.Sp, p.Sp,
+                     (int64_t)1, 1, seed, (uint32_t)t, s0 + agp::PW_STREAM_E, a.E);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+// Phi(x) of n points (rows 0 .. rup64(n) of the workspace, left Lp columns; padding rows and columns exact zeros)
+static agp_status pw_features(agp_pathwise& p, const agp_pathwise::Lat& a, const double* x, int64_t ldx, int64_t n) {
+  hipLaunchKernelGGL(agp::k_pw_features, dim3((unsigned)(p.Lp / TILE), (unsigned)(rup64(n) / TILE)), dim3(256), 0, p.ctx->stream, x,
+                     ldx, n, p.D, (const double*)a.scales, (const double*)a.omega, (const double*)a.phase, (int64_t)p.L, a.amp, p.ws,
+                     p.ldw);
+  LAUNCHCHK(p.ctx);
+  return AGP_OK;
+}
+// PW (mp x Sp) = Phi(Z) W, the rows of Z in chunks of the evaluation workspace
+static agp_status pw_phi_W(agp_pathwise& p, int l, double* PW) {
+  const agp_pathwise::Lat& a = p.lat[l];
+  HIPCHK(p.ctx, hipMemsetAsync(PW, 0, sizeof(double) * p.mp * p.Sp, p.ctx->stream));
+  for (int64_t r0 = 0; r0 < p.m; r0 += p.CH) {
+    const int64_t nc = std::min<int64_t>(p.CH, p.m - r0), nq = rup64(nc);
+    AGPCHK(pw_features(p, a, a.Z + r0 * p.D, p.D, nc));
+    AGPCHK((gemm_nt<double, EPI_STORE>(p.ctx, p.ws, p.ldw, a.WV, p.ldw, nq, p.Sp, p.Lp, 0, PW + r0 * p.Sp, p.Sp, nullptr, 0, nullptr,
+                                       nullptr, nullptr, 0)));
+  }
+  return AGP_OK;
+}
+// X = chol_lower(A)^-1 of a padded SPD matrix (A is destroyed), strict upper triangle zero: the driver of agp_spd_inverse
+static agp_status pw_inverse_factor(agp_ctx* ctx, PwScratch& sc, double* A, const double* A_src, int64_t lds, int64_t n, int64_t np,
+                                    double scale, double* X) {
+  double* Dg = nullptr;
+  int32_t* info = nullptr;
+  AGPCHK(sc.get(ctx, &Dg, np * TILE));
+  AGPCHK(sc.get(ctx, &info, 1));
+  auto fill = [&]() {
+    hipLaunchKernelGGL((agp::k_copy2d<double>), grid2(np, np), blk2, 0, ctx->stream, A_src, lds, n, n, A, np, np, np, 1.0, scale);
+  };
+  fill();
+  HIPCHK(ctx, hipMemsetAsync(X, 0, sizeof(double) * np * np, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
+  PotrfReq<double> rq{};
+  rq.A = A, rq.ld = np, rq.n = np, rq.X = X, rq.ldx = np, rq.Dg = Dg, rq.do_x = 1, rq.info_dev = info, rq.nvalid = n;
+  AGPCHK(potrf_fused<double>(ctx, rq));
+  if (chol_use_dag(ctx, np / TILE)) {
+    bool lost = false;
+    AGPCHK(dag_lost_dependency(ctx, info, &lost));
+    if (lost) {
+      fill();
+      AGPCHK(potrf_fused<double>(ctx, rq));
+    }
+  }
+  hipLaunchKernelGGL((agp::k_zero_strict_upper<double>), grid2(np, np), blk2, 0, ctx->stream, X, np, np);
+  LAUNCHCHK(ctx);
+  int32_t hinfo = 0;
+  HIPCHK(ctx, hipMemcpyAsync(&hinfo, info, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (hinfo != 0) {
+    ctx->err = "agp_svgp_pathwise_draw: -2 eta2 is not positive definite; leading minor " + std::to_string(hinfo);
+    return AGP_ERR_NOT_POSDEF;
+  }
+  return AGP_OK;
+}
+// C (M x N, ldc) = A (K x M)' B (K x N), all multiples of 64
+static agp_status pw_gemm_tn(agp_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t M, int64_t N, int64_t K,
+                             double* Cm, int64_t ldc) {
+  hipLaunchKernelGGL((agp::k_gemm_tn<double, 1>), dim3((unsigned)(N / TILE), (unsigned)(M / TILE)), dim3(NTHREADS), 0, ctx->stream, A, lda,
+                     B, ldb, K, Cm, ldc);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+static agp_status pw_eval(agp_pathwise& p, const double* xt, int64_t ldx, int64_t nt, double* out, int64_t ldo) {
+  agp_ctx* ctx = p.ctx;
+  for (int l = 0; l < p.nl; ++l) {
+    const agp_pathwise::Lat& a = p.lat[l];
+    for (int64_t s = 0; s < nt; s += p.CH) {
+      const int64_t nc = std::min<int64_t>(p.CH, nt - s), nq = rup64(nc);
+      const double* xs = xt + s * ldx;
+      AGPCHK(pw_features(p, a, xs, ldx, nc));
+      const int rc = launch_kernelmatrix<double>(ctx, ctx->stream, xs, ldx, (const int64_t*)nullptr, nc, (const double*)a.Z, p.D, p.m,
+                                                 p.D, (const double*)a.scales, a.kind, a.variance, p.ws + p.Lp, p.ldw, nq, p.mp, 0,
+                                                 0.0, (const double*)nullptr, (double*)nullptr, (int64_t)0, 0, (const double*)a.Zsc,
+                                                 (const double*)a.zn);
+      LAUNCHCHK(ctx);
+      if (rc < 0) return AGP_ERR_NOMEM;
+      AGPCHK((gemm_nt<double, EPI_STORE>(ctx, a.WV, p.ldw, p.ws, p.ldw, p.Sp, nq, p.ldw, 0, p.Fs, p.CH, nullptr, 0, nullptr, nullptr,
+                                         nullptr, 0)));
+      HIPCHK(ctx, hipMemcpy2DAsync(out + ((int64_t)l * p.S) * ldo + s, sizeof(double) * ldo, p.Fs, sizeof(double) * p.CH,
+                                   sizeof(double) * nc, p.S, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+  }
+  return AGP_OK;
+}
 
 template <typename T>
 struct Svgp : SvgpBase {
@@ -3277,6 +3496,62 @@ struct Svgp : SvgpBase {
     return AGP_OK;
   }
 
+  // ---- pathwise sampling (include/agp_hip.h, "PATHWISE SAMPLING") -----------------------------------------------------------
+  // the handles a draw is not built for, by name, before anything is touched
+  agp_status pathwise_check_handle() {
+    if (!std::is_same<T, double>::value) return pathwise_refused("AGP_F32 handles are not supported (the draw is Float64)");
+    if (desc.lik.kind == AGP_LIK_MULTIOUTPUT || mo)
+      return pathwise_refused("multi-output handles (MOSVGP, MOVGP) are not supported: draw from single-output models");
+    if (desc.latent_offset != 0 || mo_sharded || (lp.kind == AGP_LIK_LOGISTICSOFTMAX && desc.n_latent != desc.lik.n_class))
+      return pathwise_refused("latent-sharded handles are not supported (a draw needs every latent on one handle)");
+    if (bs_world > 1) return pathwise_refused("batch-sharded handles are not supported");
+    return AGP_OK;
+  }
+  agp_status pathwise_draw(int n_features, int n_samples, uint64_t seed, int64_t t, agp_pathwise** out) override {
+    AGPCHK(pathwise_check_handle());
+    AGPCHK(pw_check_draw(ctx, m, D, n_features, n_samples, t, out));
+    if constexpr (std::is_same<T, double>::value) {
+      *out = nullptr;
+      AGPCHK(flush());
+      AGPCHK(refresh_K());
+      std::unique_ptr<agp_pathwise> p;
+      AGPCHK(pw_create(ctx, nl, m, D, n_features, n_samples, &p));
+      for (int l = 0; l < nl; ++l) {
+        Latent& g = lat[l];
+        AGPCHK(params_to_host(g));
+        AGPCHK(pw_add_latent(*p, l, g.k.kind, g.k.variance, g.scales, g.Z, seed, t));
+        AGPCHK(pathwise_latent(*p, l));
+      }
+      HIPCHK(ctx, hipStreamSynchronize(st()));
+      *out = p.release();
+    }
+    return AGP_OK;
+  }
+  // V of one latent into the right columns of [W' | V']: U = mu 1' + Xa' E with Xa = chol_lower(-2 eta2)^-1 factored here from the
+  // exported eta2 (whatever the step left in La / Xa), R = U - Phi(Z) W, V' = R' K^-1
+  virtual agp_status pathwise_latent(agp_pathwise& p, int l) {
+    if constexpr (std::is_same<T, double>::value) {
+      Latent& g = lat[l];
+      PwScratch sc;
+      double *mu = nullptr, *e2 = nullptr, *A = nullptr, *X = nullptr, *U = nullptr, *PW = nullptr;
+      AGPCHK(sc.get(ctx, &mu, m));
+      AGPCHK(sc.get(ctx, &e2, m * m));
+      AGPCHK(sc.get(ctx, &A, mp * mp));
+      AGPCHK(sc.get(ctx, &X, mp * mp));
+      AGPCHK(sc.get(ctx, &U, mp * p.Sp));
+      AGPCHK(sc.get(ctx, &PW, mp * p.Sp));
+      AGPCHK(get_state(l, mu, nullptr, nullptr, e2));
+      AGPCHK(pw_inverse_factor(ctx, sc, A, e2, m, m, mp, -2.0, X));
+      AGPCHK(pw_gemm_tn(ctx, X, mp, p.lat[l].E, p.Sp, mp, p.Sp, mp, U, p.Sp));
+      AGPCHK(pw_phi_W(p, l, PW));
+      hipLaunchKernelGGL(k_pw_resid, grid2(m, p.S), blk2, 0, st(), m, (int64_t)p.S, p.Sp, (const double*)mu, (const double*)PW, U);
+      LAUNCHCHK(ctx);
+      AGPCHK(pw_gemm_tn(ctx, U, p.Sp, g.Kinv, mp, p.Sp, mp, mp, p.lat[l].WV + p.Lp, p.ldw));
+      HIPCHK(ctx, hipStreamSynchronize(st()));  // the scratch goes out of scope
+    }
+    return AGP_OK;
+  }
+
   agp_status predict_y(const void* xt, int64_t ldx, int64_t nt, void* out) override {
     if (!out) return AGP_ERR_INVALID;
     if (mo) {  // T[n_task][n_t]: regression tasks -> mean ; Bernoulli tasks -> 1.0 / 0.0 (mu_f > 0)
@@ -4003,6 +4278,9 @@ struct Movgp : Vgp {
     return AGP_OK;
   }
   int part_sets() const override { return nl; }  // k_movgp_fstats reads every latent's slices
+  agp_status pathwise_draw(int, int, uint64_t, int64_t, agp_pathwise**) override {
+    return pathwise_refused("multi-output handles (MOSVGP, MOVGP) are not supported: draw from single-output models");
+  }
 };
 
 // ---- exact GP (AGP_FLAG_FULL | AGP_FLAG_EXACT: GP(X, y, kernel) with Analytic(), src/models/GP.jl, analytic.jl) ------------
@@ -4218,6 +4496,26 @@ struct Gp : Vgp {
     gp_s2_fresh = false;  // (the closing refresh_K_explicit refactors with the new sigma2)
     return AGP_OK;
   }
+  // pathwise sampling: V = alpha 1' - Sigma_y^-1 (Phi(X) W + sigma E) with alpha, Sigma_y^-1 and sigma2 of the current factor
+  agp_status pathwise_latent(agp_pathwise& p, int l) override {
+    Latent& g = lat[0];
+    if (!gp_valid) AGPCHK(gp_factor(nullptr, false));
+    AGPCHK(gp_sinv());
+    double s2 = 0.0;
+    HIPCHK(ctx, hipMemcpyAsync(&s2, gp_s2, sizeof(double), hipMemcpyDeviceToHost, st()));
+    HIPCHK(ctx, hipStreamSynchronize(st()));
+    PwScratch sc;
+    double* PW = nullptr;
+    AGPCHK(sc.get(ctx, &PW, mp * p.Sp));
+    AGPCHK(pw_phi_W(p, l, PW));
+    hipLaunchKernelGGL(k_pw_add_noise, grid2(m, p.S), blk2, 0, st(), m, (int64_t)p.S, p.Sp, std::sqrt(s2), (const double*)p.lat[l].E, PW);
+    LAUNCHCHK(ctx);
+    AGPCHK(pw_gemm_tn(ctx, PW, p.Sp, g.Apred, mp, p.Sp, mp, mp, p.lat[l].WV + p.Lp, p.ldw));
+    hipLaunchKernelGGL(k_pw_gp_finish, grid2(p.S, m), blk2, 0, st(), m, (int64_t)p.S, p.ldw, (const double*)g.mu, p.lat[l].WV + p.Lp);
+    LAUNCHCHK(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(st()));  // the scratch goes out of scope
+    return AGP_OK;
+  }
 };
 
 // ---- Gibbs-sampled full model (AGP_FLAG_FULL | AGP_FLAG_SAMPLED: MCGP(X, y, kernel, likelihood, GibbsSampling())) --------------
@@ -4282,6 +4580,10 @@ struct Mcgp : Vgp {
     return sampled_refused("agp_svgp_hyper_configure");
   }
   agp_status hyper_rule(int, double, int, double) override { return sampled_refused("agp_svgp_hyper_rule"); }
+  agp_status pathwise_draw(int, int, uint64_t, int64_t, agp_pathwise**) override {
+    return pathwise_refused("Gibbs-sampled models (AGP_FLAG_SAMPLED) are not supported: their samples are read by "
+                            "agp_svgp_predict_samples");
+  }
   agp_status predict_f(const void*, int64_t, int64_t, void*, void*) override { return sampled_refused("agp_svgp_predict_f"); }
   agp_status predict_f_cov(const void*, int64_t, int64_t, void*, void*) override { return sampled_refused("agp_svgp_predict_f_cov"); }
   agp_status predict_y(const void*, int64_t, int64_t, void*) override { return sampled_refused("agp_svgp_predict_y"); }
@@ -4466,6 +4768,10 @@ static agp_status mc_fill_normals(agp_ctx* ctx, hipStream_t s, uint64_t seed, in
 }
 
 struct Nvgp : Vgp {
+  agp_status pathwise_draw(int, int, uint64_t, int64_t, agp_pathwise**) override {
+    return pathwise_refused("numerical inference (AGP_FLAG_NUMERICAL, with or without AGP_FLAG_MC) is not supported yet -- a "
+                            "follow-up: the factor of Sigma is already kept on such a handle");
+  }
   bool configured = false, natural = true;
   int nn = 0;
   NviRule rule{};
@@ -6096,6 +6402,77 @@ agp_status agp_mc_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void
     ctx->err = "agp_mc_expectations: a class index outside [0, K)";
     return AGP_ERR_LABELS;
   }
+  return AGP_OK;
+}
+
+// ---- pathwise sampling ----------------------------------------------------------------------------------------------------------
+agp_status agp_svgp_pathwise_draw(agp_svgp* h, int32_t n_features, int32_t n_samples, uint64_t seed, int64_t t, agp_pathwise** out) {
+  HCHK(h);
+  return h->impl->pathwise_draw(n_features, n_samples, seed, t, out);
+}
+agp_status agp_pathwise_eval(agp_pathwise* p, const void* xt, int64_t ldx, int64_t n_t, void* out, int64_t ldo) {
+  if (!p) return AGP_ERR_INVALID;
+  if (n_t == 0) return AGP_OK;
+  if (!xt || !out || n_t < 0 || ldx < p->D || ldo < n_t) {
+    p->ctx->err = "agp_pathwise_eval: xt and out must be given, n_t >= 0, ldx >= D, ldo >= n_t";
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(p->ctx->device);
+  return pw_eval(*p, (const double*)xt, ldx, n_t, (double*)out, ldo);
+}
+agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D) {
+  if (!p) return AGP_ERR_INVALID;
+  if (n_latent) *n_latent = p->nl;
+  if (n_features) *n_features = p->L;
+  if (n_samples) *n_samples = p->S;
+  if (m) *m = p->m;
+  if (D) *D = p->D;
+  return AGP_OK;
+}
+agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void* out, int64_t ld) {
+  if (!p) return AGP_ERR_INVALID;
+  agp_ctx* ctx = p->ctx;
+  if (latent < 0 || latent >= p->nl || !out || which < AGP_PW_OMEGA || which > AGP_PW_E) {
+    ctx->err = "agp_pathwise_get: latent in [0, n_latent), out given, which one of AGP_PW_OMEGA .. AGP_PW_E";
+    return AGP_ERR_INVALID;
+  }
+  const agp_pathwise::Lat& a = p->lat[latent];
+  const double* src = a.omega;
+  int64_t sr = p->D, sc = 1, rows = p->L, cols = p->D;
+  switch (which) {
+    case AGP_PW_PHASE: src = a.phase, sr = 1, cols = 1, ld = 1; break;  // a dense vector: ld is not read
+    case AGP_PW_W: src = a.WV, sr = 1, sc = p->ldw, cols = p->S; break;
+    case AGP_PW_V: src = a.WV + p->Lp, sr = 1, sc = p->ldw, rows = p->m, cols = p->S; break;
+    case AGP_PW_E: src = a.E, sr = p->Sp, rows = p->m, cols = p->S; break;
+    default: break;
+  }
+  if (ld < cols) {
+    ctx->err = "agp_pathwise_get: the leading dimension is smaller than the table's width (" + std::to_string(cols) + ")";
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  hipLaunchKernelGGL(k_pw_gather, grid2(rows, cols), blk2, 0, ctx->stream, src, sr, sc, rows, cols, (double*)out, ld);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+agp_status agp_pathwise_destroy(agp_pathwise* p) {
+  if (!p) return AGP_OK;
+  DevGuard guard(p->ctx->device);
+  (void)hipStreamSynchronize(p->ctx->stream);
+  delete p;
+  return AGP_OK;
+}
+agp_status agp_pathwise_features(agp_ctx* ctx, const agp_kernel_desc* k, int64_t D, int32_t n_features, uint64_t seed, int64_t t,
+                                 int32_t latent, void* omega_out, void* phase_out) {
+  if (!ctx) return AGP_ERR_INVALID;
+  if (!k || !omega_out || !phase_out || k->kind < AGP_K_SQEXP || k->kind > AGP_K_EXPONENTIAL || latent < 0 || latent > (1 << 24)) {
+    ctx->err = "agp_pathwise_features: k, omega_out and phase_out must be given, k->kind one of the four kernels, latent >= 0";
+    return AGP_ERR_INVALID;
+  }
+  AGPCHK(pw_check_spectral(ctx, "agp_pathwise_features", D, n_features, t));
+  DevGuard guard(ctx->device);
+  AGPCHK(pw_spectral(ctx, k->kind, D, n_features, seed, t, latent, (double*)omega_out, (double*)phase_out));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return AGP_OK;
 }
 

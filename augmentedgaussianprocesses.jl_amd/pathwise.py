@@ -1,0 +1,170 @@
+"""Pathwise posterior sampling: function draws from a trained SVGP, VGP or GP (include/agp_hip.h, "PATHWISE SAMPLING").
+
+    paths = AGP.sample_paths(model, n_samples, n_features=1024, seed=None, t=0)
+    F = paths(X_test)          # (n_samples, n_t), or (n_latent, n_samples, n_t) for several latents
+
+Decoupled sampling (Wilson et al. 2020, "Efficiently sampling functions from Gaussian process posteriors"): a prior function from
+random Fourier features, a draw u ~ q(u), Matheron's correction.  A draw is an ordinary function: it can be evaluated at any number
+of points, streamed, and it is a snapshot -- training the model further, changing its kernel or freeing it does not change the
+paths.  Everything random is a function of (seed, t, latent): the same arguments give the same paths bit for bit.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import capi
+
+N_MAX = 65536  # n_features and n_samples (agp_svgp_pathwise_draw)
+CTR_MAX = 2 ** 32  # products that index one 32-bit counter word, and the draw counter t
+
+
+def check_draw_args(m: int, D: int, n_samples: int, n_features: int, t: int, seed: Optional[int] = None) -> None:
+    """the argument limits of agp_svgp_pathwise_draw, raised on the host before anything is created"""
+    if not 1 <= int(n_samples) <= N_MAX:
+        raise ValueError(f"n_samples must lie in [1, {N_MAX}] (got {n_samples})")
+    if not 1 <= int(n_features) <= N_MAX:
+        raise ValueError(f"n_features must lie in [1, {N_MAX}] (got {n_features})")
+    if n_features * D >= CTR_MAX or n_features * n_samples >= CTR_MAX or m * n_samples >= CTR_MAX:
+        raise ValueError("n_features * D, n_features * n_samples and m * n_samples must stay below 2^32")
+    if not 0 <= int(t) < CTR_MAX:
+        raise ValueError("the draw counter t must lie in [0, 2^32)")
+    if seed is not None and not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must fit 64 bits")
+
+
+def refusal(model) -> Optional[str]:
+    """why this model has no pathwise draw, by name, or None (the host mirror of the device's AGP_ERR_UNSUPPORTED list)"""
+    from .mcgp import MCGP
+    from .movgp import MOVGP
+    from .svgp import MOSVGP
+
+    if isinstance(model, (MOSVGP, MOVGP)):
+        return "multi-output models (MOSVGP, MOVGP) are not supported: draw from single-output models"
+    if isinstance(model, MCGP):
+        return "an MCGP (GibbsSampling) is not supported: its samples are read by predict_f / proba_y"
+    if getattr(model, "_numerical", False):
+        return ("numerical inference (QuadratureVI, MCIntegrationVI) is not supported yet -- a follow-up: the factor of Sigma is "
+                "already kept on such a handle")
+    if np.dtype(model.T) != np.dtype(np.float64):
+        return "Float32 models are not supported (the draw is Float64)"
+    if getattr(model, "latent_offset", 0) != 0 or getattr(model, "n_latent_total", model.n_latent) != model.n_latent:
+        return "latent-sharded models are not supported (a draw needs every latent on one handle)"
+    return None
+
+
+class PathwiseSamples:
+    """n_samples function draws from a model's posterior; call it on test inputs.  Owns an agp_pathwise object on the device."""
+
+    def __init__(self, model, n_samples: int, n_features: int, seed: int, t: int):
+        self._model = model  # keeps the context alive (the draw uses its stream)
+        self.n_samples, self.n_features, self.seed, self.t = int(n_samples), int(n_features), int(seed), int(t)
+        self.n_latent, self.m, self.D = model.n_latent, model.m, model.D
+        self._p = None
+        h = model._ensure_handle(max(model._max_batch, 1))
+        p = C.c_void_p()
+        model._chk(capi.lib().agp_svgp_pathwise_draw(h, self.n_features, self.n_samples, C.c_uint64(self.seed), self.t, C.byref(p)))
+        self._p = p
+
+    def _live(self):
+        if self._p is None:
+            raise RuntimeError("the paths have been freed")
+        return self._p
+
+    def __call__(self, X_test, *, obsdim: int = 1):
+        """the paths at X_test: (n_samples, n_t), or (n_latent, n_samples, n_t) for several latents.  NumPy in gives NumPy out; a
+        torch tensor on the device gives a device tensor."""
+        import torch
+
+        p, model = self._live(), self._model
+        on_device = isinstance(X_test, torch.Tensor) and X_test.is_cuda
+        Xd = model._upload(X_test, obsdim)
+        nt = Xd.shape[0]
+        out = torch.empty(self.n_latent, self.n_samples, nt, dtype=torch.float64, device=model._dev())
+        L = capi.lib()
+        model._chk(L.agp_pathwise_eval(p, C.c_void_p(Xd.data_ptr()), Xd.stride(0) if nt else self.D, nt, C.c_void_p(out.data_ptr()),
+                                       max(nt, 1)))
+        model._chk(L.agp_ctx_sync(model._ctx))
+        if self.n_latent == 1:
+            out = out[0]
+        return out if on_device else out.cpu().numpy()
+
+    def tables(self, latent: int = 0):
+        """the draw's tables of one latent as NumPy arrays: omega (l, D), phase (l), W (l, S), V (m, S), E (m, S)"""
+        import torch
+
+        p, model = self._live(), self._model
+        dev = model._dev()
+        shapes = {"omega": (capi.PW_OMEGA, (self.n_features, self.D)), "phase": (capi.PW_PHASE, (self.n_features,)),
+                  "W": (capi.PW_W, (self.n_features, self.n_samples)), "V": (capi.PW_V, (self.m, self.n_samples)),
+                  "E": (capi.PW_E, (self.m, self.n_samples))}
+        out = {}
+        for name, (which, shp) in shapes.items():
+            buf = torch.empty(*shp, dtype=torch.float64, device=dev)
+            model._chk(capi.lib().agp_pathwise_get(p, int(latent), which, C.c_void_p(buf.data_ptr()), shp[-1]))
+            out[name] = buf
+        model._chk(capi.lib().agp_ctx_sync(model._ctx))
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def free(self) -> None:
+        """release the device object (idempotent)"""
+        if self._p is not None:
+            capi.lib().agp_pathwise_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return (f"PathwiseSamples({self.n_samples} paths, {self.n_features} features, {self.n_latent} latent(s), "
+                f"seed={self.seed}, t={self.t})")
+
+
+def sample_paths(model, n_samples: int, *, n_features: int = 1024, seed: Optional[int] = None, t: int = 0) -> PathwiseSamples:
+    """sample_paths(model, n_samples; n_features=1024, seed=nothing, t=0): joint function draws from the posterior of an SVGP, VGP
+    (AnalyticVI / AnalyticSVI), GP or OnlineSVGP.  seed=None takes the model's seed (drawn once from the model's generator, as
+    `sample` does for an MCGP); t is the caller's draw counter: another t, another independent draw from the same seed."""
+    from .svgp import SVGP
+
+    if not isinstance(model, SVGP) and hasattr(model, "_cur"):  # OnlineSVGP: the wrapper that owns the current handle
+        if model._cur is None:
+            raise RuntimeError("the online model has seen no data yet")
+        model = model._cur
+    if not isinstance(model, SVGP):
+        raise TypeError("sample_paths(model, n): model must be an SVGP, VGP, GP or OnlineSVGP")
+    why = refusal(model)
+    if why is not None:
+        raise NotImplementedError("sample_paths: " + why)
+    check_draw_args(model.m, model.D, n_samples, n_features, t, seed)
+    if seed is None:
+        if getattr(model, "seed", None) is None:
+            model.seed = int(model.rng.integers(0, 2 ** 63))
+        seed = model.seed
+    return PathwiseSamples(model, n_samples, n_features, int(seed), t)
+
+
+def pathwise_features(kernel, D: int, n_features: int, seed: int, t: int = 0, latent: int = 0, *, device: Optional[int] = None):
+    """the spectral draw alone, outside any model (agp_pathwise_features): (omega (l, D), phase (l)) as NumPy arrays"""
+    import torch
+
+    check_draw_args(1, D, 1, n_features, t, seed)
+    L = capi.lib()
+    dev = torch.device("cuda", device if device is not None else torch.cuda.current_device())
+    ctx = C.c_void_p()
+    st = L.agp_ctx_create(dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(ctx))
+    if st != capi.AGP_OK:
+        raise capi.AGPError(st, "agp_ctx_create failed")
+    try:
+        kd, keep = kernel.desc(D)
+        om = torch.empty(n_features, D, dtype=torch.float64, device=dev)
+        ph = torch.empty(n_features, dtype=torch.float64, device=dev)
+        capi.check(ctx, L.agp_pathwise_features(ctx, C.byref(kd), D, n_features, C.c_uint64(int(seed)), int(t), int(latent),
+                                                C.c_void_p(om.data_ptr()), C.c_void_p(ph.data_ptr())))
+        return om.cpu().numpy(), ph.cpu().numpy()
+    finally:
+        L.agp_ctx_destroy(ctx)

@@ -766,6 +766,61 @@ agp_status agp_mc_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void
                                int64_t n_pts, int32_t K, int32_t nMC, uint64_t seed, int64_t t, int32_t stream, void* ell, void* g,
                                void* h);
 
+/* ---- PATHWISE SAMPLING (function draws from a trained posterior: SVGP, VGP with AnalyticVI / AnalyticSVI, exact GP) -----------------
+ * Decoupled sampling (Wilson, Borovitskiy, Terenin, Mostowsky, Deisenroth 2020, "Efficiently sampling functions from Gaussian
+ * process posteriors"): a prior function from l = n_features random Fourier features, a draw u ~ q(u), and Matheron's correction.
+ * A draw is then an ordinary function: agp_pathwise_eval evaluates its S = n_samples paths at any number of test points in
+ * O(n_t (l + m) S), streamed, with no n_t x n_t object (agp_svgp_predict_f_cov stops at n_t = 8192).
+ * The draw is a SNAPSHOT object of its own: it copies what it needs from the handle (Z, the scales, the kernel kind and variance,
+ * and the tables below), so training steps, set_kernel or destroying the handle afterwards neither change nor invalidate it.  It
+ * keeps using the handle's context, which must outlive it.  Float64 device pointers throughout; the Layout rules above hold.
+ * Per latent, with r = ||s o (x - x')|| and sigma2 the kernel variance:
+ *   features   phi_j(x) = sqrt(2 sigma2 / l) cos(omega_j' (s o x) + p_j), p_j = 2 pi u_j; the frequencies and phases are shared by
+ *              the S samples of a draw.  SqExponential: omega_j = z_j.  Matern52, Matern32, Exponential (nu = 5/2, 3/2, 1/2):
+ *              omega_j = z_j sqrt(nu / G_j), G_j ~ Gamma(nu, 1) without rejection as G_j = n_j^2 / 2 + sum_{k < K} (-log u_jk),
+ *              K = 2, 1, 0.  Then E[phi(x)' phi(x')] = sigma2 k(r) for the four kernels (checked by tests/test_pathwise_host.py).
+ *   SVGP, VGP  U = mu 1' + Xa' E with Xa = chol_lower(-2 eta2)^-1 (Sigma = Xa' Xa: the square root of the Gibbs contract),
+ *              V = K^-1 (U - Phi(Z) W), K = k(Z, Z) + jitt I as the handle holds it (VGP: Z = X)
+ *   exact GP   V = alpha 1' - Sigma_y^-1 (Phi(X) W + sigma E), Sigma_y = K + sigma2_noise I and alpha as the handle holds them, sigma =
+ *              sqrt(sigma2_noise) (needs a step or a refresh_K with targets before it: AGP_ERR_INVALID otherwise)
+ *   paths      f_s(x) = sum_j phi_j(x) W_js + sum_r k(x, Z_r) V_rs
+ * Given the features, f has mean k* K^-1 mu -- predict_f's mean exactly -- and covariance G G' + k* K^-1 Sigma K^-1 k*' with
+ * G = Phi(x) - k* K^-1 Phi(Z) (exact GP: G G' + sigma2_noise k* Sigma_y^-2 k*', G = Phi(x) - k* Sigma_y^-1 Phi(X)).  As l grows this
+ * tends to the matrix of agp_svgp_predict_f_cov without its + jitt I, up to O(jitt).  The feature error is O(1 / sqrt(l)) and is
+ * NOT bounded here: at l = 512 one draw was 7 % off in covariance on a small case.
+ * RANDOM STREAMS, continued (streams 0 - 3 keep their meaning): key = seed, t the CALLER's draw counter, 0 <= t < 2^32, and
+ * s0 = 4 + 8 latent.  Normal = the Normal of block 0 with the log / cos 2 pi arithmetic contracted for streams 2 - 3; uniform k =
+ * the k-th uniform of the stream (two per block).  Every sqrt and division is one IEEE operation, nothing is contracted, so
+ * Omega, the phases, W and E are reproducible bit for bit on the host (tests/_pathwise_ref.py):
+ *     z_jd   (j D + d, t, s0,     0)  Normal                  n_j   (j, t, s0 + 1, 0)  Normal
+ *     u_jk   (j, t, s0 + 1, 1)        uniforms 2, 3 (k = 0, 1)      u_j   (j, t, s0 + 2, 0)  uniform 0;  p_j = 6.283185307179586 u_j
+ *     W_js   (j S + s, t, s0 + 3, 0)  Normal                  E_is  (i S + s, t, s0 + 4, 0)  Normal
+ *     G_j = (n_j n_j) 0.5, then G_j = G_j - log u_jk for k = 0 .. K - 1;  omega_jd = z_jd sqrt(nu / G_j)
+ * agp_svgp_pathwise_draw  makes the draw (synchronises: it refreshes K and factors -2 eta2 once per latent).  A handle with an online
+ *   prior is an ordinary sparse handle; multi-latent single-output likelihoods (LogisticSoftMax, Heteroscedastic) get one
+ *   independent draw per latent.  AGP_ERR_UNSUPPORTED, touching nothing, by name: AGP_F32 handles; multi-output handles (MOSVGP,
+ *   MOVGP); AGP_FLAG_SAMPLED; AGP_FLAG_NUMERICAL with or without AGP_FLAG_MC (a follow-up: the factor of Sigma is already kept
+ *   there); latent-sharded and batch-sharded handles.  AGP_ERR_INVALID with a message: n_features or n_samples outside
+ *   [1, 65536]; l D, l S or m S not below 2^32; t outside [0, 2^32); out = NULL.
+ * agp_pathwise_eval  out[latent][s][i] at out + (latent * n_samples + s) * ldo + i, ldo >= n_t, ldx >= D; n_t = 0 is a successful
+ *   no-op.  Test points go through the workspace [Phi(x) | k(x, Z)] in chunks of at most 4096, fewer where a chunk's share of the
+ *   workspace -- 8 (l + m + S) bytes per point, all three rounded up to 64 -- would exceed AGP_PATHWISE_WS_BYTES (but at least
+ *   64): one gemm_nt against the stored [W' | V'] gives both terms.  Asynchronous on the context's stream.
+ * agp_pathwise_get   which = AGP_PW_OMEGA (l x D, ld >= D), AGP_PW_PHASE (l; ld not read), AGP_PW_W (l x S, ld >= S), AGP_PW_V
+ *   (m x S, ld >= S), AGP_PW_E (m x S, ld >= S).
+ * agp_pathwise_features  the spectral draw alone, outside any model: omega_out double[l][D], phase_out double[l], dense, device;
+ *   of the kernel only the kind is read (the scales enter at evaluation); latent >= 0 selects s0.  Synchronises. */
+enum { AGP_PW_OMEGA = 0, AGP_PW_PHASE = 1, AGP_PW_W = 2, AGP_PW_V = 3, AGP_PW_E = 4 };
+enum { AGP_PATHWISE_WS_BYTES = 64 * 1024 * 1024 };
+typedef struct agp_pathwise agp_pathwise;
+agp_status agp_svgp_pathwise_draw(agp_svgp* h, int32_t n_features, int32_t n_samples, uint64_t seed, int64_t t, agp_pathwise** out);
+agp_status agp_pathwise_eval(agp_pathwise* p, const void* xt, int64_t ldx, int64_t n_t, void* out, int64_t ldo);
+agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D);
+agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void* out, int64_t ld);
+agp_status agp_pathwise_destroy(agp_pathwise* p);
+agp_status agp_pathwise_features(agp_ctx* ctx, const agp_kernel_desc* k, int64_t D, int32_t n_features, uint64_t seed, int64_t t,
+                                 int32_t latent, void* omega_out, void* phase_out);
+
 /* ---- multi-GPU: one process per GPU, collectives behind the ABI --------------------------------
  * The path shards in two ways and both reduce to in-place SUM all-reduces of library-owned device buffers:
  *   AGP_SHARD_LATENT : this handle holds the latent slice [latent_offset, latent_offset + n_latent) of the model, every rank

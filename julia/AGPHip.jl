@@ -1301,4 +1301,76 @@ function proba_y(model::HipMCGP{T,<:AGP.BernoulliLikelihood}, X_test::AbstractMa
 end
 objective(model::HipMCGP, state::HipModel, y=nothing) = NaN      # MCGP.jl:91
 
+# ---- pathwise posterior sampling (include/agp_hip.h, "PATHWISE SAMPLING") ---------------------------------------------------------
+# paths = sample_paths(model, n; n_features=1024, seed=nothing, t=0) draws n functions from the posterior of a trained SVGP, VGP or GP
+# (its device twin must exist: train with the :hip backend first); paths(X_test) evaluates them at any number of points: n x n_t, or
+# a vector of such matrices, one per latent.  The draw is a snapshot on the device: training the model further does not change it.
+# Everything random is a function of (seed, t, latent), as the header states.  Never run: there is no Julia toolchain in the test
+# environment.
+mutable struct PathwiseSamples
+    p::Ptr{Cvoid}
+    ctx::Ptr{Cvoid}
+    hm::Any                                                      # keeps the context alive
+    n_latent::Int
+    n_features::Int
+    n_samples::Int
+    m::Int
+    D::Int
+    seed::UInt64
+    t::Int64
+end
+const PATHWISE_SEED = IdDict{Any,UInt64}()
+function free!(ps::PathwiseSamples)
+    ps.p == C_NULL || ccall((:agp_pathwise_destroy, libagp), Int32, (Ptr{Cvoid},), ps.p)
+    ps.p = C_NULL
+    return nothing
+end
+function sample_paths(hm::HipModel, n::Integer; n_features::Integer=1024, seed=nothing, t::Integer=0)
+    hm.h == C_NULL && error("sample_paths: the model has no device handle yet (train it with the :hip backend first)")
+    s = seed === nothing ? get!(() -> rand(UInt64), PATHWISE_SEED, hm) : UInt64(seed)
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(hm.ctx, ccall((:agp_svgp_pathwise_draw, libagp), Int32, (Ptr{Cvoid}, Int32, Int32, UInt64, Int64, Ref{Ptr{Cvoid}}),
+                        hm.h, n_features, n, s, t, p))
+    nl, nf, ns, m, D = Ref{Int32}(0), Ref{Int32}(0), Ref{Int32}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(hm.ctx, ccall((:agp_pathwise_info, libagp), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int64}, Ref{Int64}),
+                        p[], nl, nf, ns, m, D))
+    ps = PathwiseSamples(p[], hm.ctx, hm, nl[], nf[], ns[], m[], D[], s, t)
+    finalizer(free!, ps)
+    return ps
+end
+sample_paths(model::AGP.AbstractGPModel, n::Integer; kw...) =
+    has_twin(model) ? sample_paths(TWINS[model], n; kw...) : error("sample_paths: train the model with the :hip backend first")
+function (ps::PathwiseSamples)(X_test::AbstractMatrix; obsdim::Int=1)
+    ps.p == C_NULL && error("the paths have been freed")
+    Xd = ROCArray{Float64}(obsdim == 1 ? permutedims(X_test) : X_test)   # D x n_t column-major == point-major
+    D, nt = size(Xd)
+    out = ROCArray{Float64}(undef, nt, ps.n_samples, ps.n_latent)        # column-major == double[n_latent][n_samples][n_t]
+    check(ps.ctx, ccall((:agp_pathwise_eval, libagp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64),
+                        ps.p, pointer(Xd), D, nt, pointer(out), max(nt, 1)))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), ps.ctx)
+    F = Array(out)
+    paths = [permutedims(F[:, :, l]) for l in 1:ps.n_latent]             # n_samples x n_t per latent
+    return ps.n_latent == 1 ? only(paths) : paths
+end
+# the tables of one latent (0-based `which`: 0 omega l x D, 1 phase l, 2 W l x S, 3 V m x S, 4 E m x S), as Julia matrices
+function pathwise_table(ps::PathwiseSamples, which::Integer; latent::Integer=1)
+    rows, cols = which == 0 ? (ps.n_features, ps.D) : which == 1 ? (ps.n_features, 1) :
+                 which == 2 ? (ps.n_features, ps.n_samples) : (ps.m, ps.n_samples)
+    buf = ROCMatrix{Float64}(undef, cols, rows)                          # column-major cols x rows == the library's rows x cols
+    check(ps.ctx, ccall((:agp_pathwise_get, libagp), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64),
+                        ps.p, latent - 1, which, pointer(buf), cols))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), ps.ctx)
+    return permutedims(Array(buf))
+end
+# the spectral draw alone, outside any model: (omega l x D, phase l)
+function pathwise_features(hm::HipModel, k::Kernel, D::Integer, n_features::Integer, seed::Integer, t::Integer=0; latent::Integer=1)
+    ctx = ensure_ctx!(hm)
+    om, ph = ROCMatrix{Float64}(undef, D, n_features), ROCVector{Float64}(undef, n_features)
+    kd, keep = kernel_desc(k, Int(D))
+    GC.@preserve keep check(ctx, ccall((:agp_pathwise_features, libagp), Int32,
+                                       (Ptr{Cvoid}, Ref{KernelDesc}, Int64, Int32, UInt64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                                       ctx, kd, D, n_features, UInt64(seed), t, latent - 1, pointer(om), pointer(ph)))
+    return permutedims(Array(om)), Array(ph)
+end
+
 end # module
