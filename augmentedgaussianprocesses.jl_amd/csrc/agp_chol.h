@@ -167,9 +167,16 @@ struct NoHook {
 //   1  fraction-free (Bareiss) minors: n_ij = d00 d_ij - d_i0 d_j0, p_ij = (n11 n_ij - n_i1 n_j1) / d00, M4 = (p22 p33 - p32^2) / n11
 //      are the leading-minor numerators of the same elimination, so the four reciprocals 1/d00, 1/M2, 1/M3, 1/M4 no longer wait
 //      for one another's multipliers (depth ~13); pivots = M_q / M_(q-1), multipliers l21 = n21 / M2, l32 = p32 / M3, ...
+// Where a round issues its LDS reads (round 9; none of them depends on the LDL' result, and the CU's one LDS pipe serves four
+// waves): the pivot block, its first row first (LDS returns in order and the chain starts with d00) ; 1 / d00 ; my panel columns ;
+// 1 / d11 ; my M columns and my panel rows -- all into registers, so that the rest of the LDL' chain runs under them.  The
+// __builtin_amdgcn_sched_barrier(0) calls pin that order (left alone, the compiler issues all of them behind the chain, or, as one
+// burst in front of it, a wave's pivot block queues behind the other waves' panel reads).  The four pivots go to piv[] at the END
+// of the round body (they are read after the barrier that follows the rounds): an LDS store between the chain and the transforms
+// keeps every later LDS read behind it.
 template <typename T, int J, int NS, typename H, int PIV = 0>
-__device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* sc, T* piv, const bool act, const int ti,
-                                            const int tj, H& hook, const int hbase) {
+__device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* __restrict__ sc, T* __restrict__ piv,
+                                            const bool act, const int ti, const int tj, H& hook, const int hbase) {
 #pragma unroll 1
   for (int rr = 0; rr < 4; ++rr) {
     const int jj0 = rr * 4, j0 = J * 16 + jj0;
@@ -194,11 +201,41 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
     hook(hbase + rr);
     if (!act) continue;
     if (PIV == 4 || PIV == 5) continue;
-    // ---- 4x4 pivot block, LDL' (every active thread, redundantly) ----
+    // ---- every LDS read of the round: the 4x4 pivot block first, then my panel columns, my M columns, my panel rows ----
     const T d00 = P[j0], d10 = P[j0 + 1], d20 = P[j0 + 2], d30 = P[j0 + 3];
+    __builtin_amdgcn_sched_barrier(0);
     T d11 = P[TILE + j0 + 1], d21 = P[TILE + j0 + 2], d31 = P[TILE + j0 + 3];
     T d22 = P[2 * TILE + j0 + 2], d32 = P[2 * TILE + j0 + 3], d33 = P[3 * TILE + j0 + 3];
     T r0, r1, r2, r3, l10, l20, l30, l21, l31, l32;
+    if (PIV != 2) {
+      __builtin_amdgcn_sched_barrier(0);
+      r0 = rcp1(d00);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    T u[4][NS], mw[4][NS], w[4][NS];  // [q][c] ; [q][c] ; [q][r]
+    auto ld_u = [&] {
+#pragma unroll
+      for (int c = J; c < NS; ++c)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) u[q][c] = P[q * TILE + tj + 16 * c];
+    };
+    auto ld_mw = [&] {
+#pragma unroll
+      for (int c = 0; c <= J; ++c)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mw[q][c] = Mw[q * TILE + tj + 16 * c];
+#pragma unroll
+      for (int r = J; r < NS; ++r)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[q][r] = P[q * TILE + ti + 16 * r];
+    };
+    constexpr bool SPLIT = PIV == 0;  // (the timing variants and the minors read everything here)
+    if (PIV != 3) {
+      ld_u();
+      if (!SPLIT) ld_mw();
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- 4x4 pivot block, LDL' (every active thread, redundantly) ----
     if (PIV == 2) {  // TIMING EXPERIMENT ONLY (wrong results): no pivot-block factorisation at all -- what the rest of a round costs
       r0 = r1 = r2 = r3 = T(1);
       l10 = d10;
@@ -208,7 +245,6 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
       l31 = d31;
       l32 = d32;
     } else if (PIV == 1) {
-      r0 = rcp1(d00);
       const T n11 = fma(d00, d11, -(d10 * d10)), n21 = fma(d00, d21, -(d20 * d10)), n31 = fma(d00, d31, -(d30 * d10));
       const T n22 = fma(d00, d22, -(d20 * d20)), n32 = fma(d00, d32, -(d30 * d20)), n33 = fma(d00, d33, -(d30 * d30));
       const T rm2 = rcp1(n11);
@@ -230,7 +266,6 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
       d22 = p22 * rm2;
       d33 = m4 * rm3;
     } else {
-      r0 = rcp1(d00);
       l10 = d10 * r0;
       l20 = d20 * r0;
       l30 = d30 * r0;
@@ -241,6 +276,11 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
       d32 = fma(-l30, d20, d32);
       d33 = fma(-l30, d30, d33);
       r1 = rcp1(d11);
+      if (SPLIT) {
+        __builtin_amdgcn_sched_barrier(0);
+        ld_mw();
+        __builtin_amdgcn_sched_barrier(0);
+      }
       l21 = d21 * r1;
       l31 = d31 * r1;
       d22 = fma(-l21, d21, d22);
@@ -251,22 +291,20 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
       d33 = fma(-l32, d32, d33);
       r3 = rcp1(d33);
     }
-    if (ti == 0 && tj == 0) {
-      piv[j0] = d00;
-      piv[j0 + 1] = d11;
-      piv[j0 + 2] = d22;
-      piv[j0 + 3] = d33;
-    }
     if (PIV == 3) {  // TIMING EXPERIMENT ONLY (wrong results): publish + barrier + pivot-block LDL', no transforms / updates
+      if (ti == 0 && tj == 0) {
+        piv[j0] = d00;
+        piv[j0 + 1] = d11;
+        piv[j0 + 2] = d22;
+        piv[j0 + 3] = d33;
+      }
       a[J][J] += r3 * T(1e-30) + l32 * T(1e-30);
       continue;
     }
     // ---- panel transforms for my columns / my M columns, then row by row: multipliers + rank-4 update ----
-    T u[4][NS], mw[4][NS];  // [q][c]
 #pragma unroll
     for (int c = J; c < NS; ++c) {
-      const int x = tj + 16 * c;
-      T y0 = P[x], y1 = P[TILE + x], y2 = P[2 * TILE + x], y3 = P[3 * TILE + x];
+      T y0 = u[0][c], y1 = u[1][c], y2 = u[2][c], y3 = u[3][c];
       y1 = fma(-l10, y0, y1);
       y2 = fma(-l21, y1, fma(-l20, y0, y2));
       y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, y0, y3)));
@@ -281,8 +319,7 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
     }
 #pragma unroll
     for (int c = 0; c <= J; ++c) {
-      const int x = tj + 16 * c;
-      T y0 = Mw[x], y1 = Mw[TILE + x], y2 = Mw[2 * TILE + x], y3 = Mw[3 * TILE + x];
+      T y0 = mw[0][c], y1 = mw[1][c], y2 = mw[2][c], y3 = mw[3][c];
       y1 = fma(-l10, y0, y1);
       y2 = fma(-l21, y1, fma(-l20, y0, y2));
       y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, y0, y3)));
@@ -293,8 +330,7 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
     }
 #pragma unroll
     for (int r = J; r < NS; ++r) {
-      const int x = ti + 16 * r;
-      T y0 = P[x], y1 = P[TILE + x], y2 = P[2 * TILE + x], y3 = P[3 * TILE + x];
+      T y0 = w[0][r], y1 = w[1][r], y2 = w[2][r], y3 = w[3][r];
       y1 = fma(-l10, y0, y1);
       y2 = fma(-l21, y1, fma(-l20, y0, y2));
       y3 = fma(-l32, y2, fma(-l31, y1, fma(-l30, y0, y3)));
@@ -317,6 +353,12 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* s
         for (int q = 0; q < 4; ++q) s0 = fma(-f[q], mw[q][c], s0);
         g[r][c] = s0;
       }
+    }
+    if (ti == 0 && tj == 0) {  // complete before the barrier that follows the rounds (elim_block32 / factor_diag_tile512)
+      piv[j0] = d00;
+      piv[j0 + 1] = d11;
+      piv[j0 + 2] = d22;
+      piv[j0 + 3] = d33;
     }
   }
 }
