@@ -151,10 +151,25 @@ __device__ __forceinline__ void mma_lds64(const T* As, const T* Bs, Acc<T>& acc)
 // (Measured alternatives, tools/bench_diag.py, f64 us per tile: one column per barrier 20-21; this scheme 14.5; pivot
 //  block + transforms done once by a dedicated wave and shared through a second barrier 16.7 -- the serial LDL' chain in
 //  a single wave costs more than the redundant work it saves.)
-// Scratch: PL[2][4][64] panel columns, MW[2][4][64] M rows (double-buffered: round r+1 publishes while stragglers of
-// round r may still be reading).
+// Scratch: PL[2][4 * 64] panel columns, MW[2][4 * 64] M rows (double-buffered: round r+1 publishes while stragglers of
+// round r may still be reading) ; inside a buffer the four rows are interleaved in fp64, see round_sc.
 // ---------------------------------------------------------------------------------------------------
 constexpr int SC_ELEMS = 2 * 2 * 4 * TILE;
+
+// Where element x of row q (q = 0..3: a round's panel column in P, its M row in Mw) sits in a 4 * TILE scratch buffer (round 10).
+// fp64: rows (0, 1) and (2, 3) interleaved in pairs.  A thread's four q values at one x are then two aligned 16-byte runs and the
+// compiler reads them with ds_read_b128, at the LDS's full rate; the row-major q * TILE + x put them 512 B apart and made every
+// panel read of a round a two-address ds_read2*_b64 at half that rate.  fp32 keeps the row-major form and, instruction for
+// instruction, the code it had: interleaved by four (one ds_read_b128 per x) its tile alone measured 9.26 -> 8.54 us, but the C3
+// step, whose split launch feeds the chain from a second kernel, went from 0.602 to 0.819 ms per step, three runs each way
+// (DESIGN.md 5 "round 10", profiles/r10_c2_round_layout_runs.txt; which part of the fp32 change does it was not separated).
+// Linear in q and in x: round_sc(q, x0 + x) = round_sc(0, x0) + round_sc(q, x).  The layout is private to chol_rounds; its publish
+// and its reads both go through here.
+template <typename T>
+__device__ __forceinline__ constexpr int round_sc(int q, int x) {
+  constexpr int G = sizeof(T) == 8 ? 2 : 1;  // rows per interleaved group
+  return (q / G) * G * TILE + G * x + q % G;
+}
 
 // hook: called once per round by every thread right after the round's barrier (the idle waves 4-7 of a 512-thread workgroup
 // can step a side job there -- the chain workgroup of k_chol_dag prefetches its next two tiles this way)
@@ -177,24 +192,44 @@ struct NoHook {
 template <typename T, int J, int NS, typename H, int PIV = 0>
 __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* __restrict__ sc, T* __restrict__ piv,
                                             const bool act, const int ti, const int tj, H& hook, const int hbase) {
+  // fp64: pb = where this round's pivot block starts in sc, in units of 8 elements ((rr & 1) * 4 * TILE + round_sc(0, j0), always a
+  // multiple of 8, so the reads' 16-byte alignment stays known).  It is carried through the loop in a register and stepped by one
+  // instruction (v_xad_u32: toggle the buffer, advance four columns), and the empty asm keeps the compiler from rebuilding it from
+  // rr behind the barrier, in front of the first read.  Measured (DESIGN_LOG 17): Pp = P + round_sc(0, j0) left to the compiler puts
+  // four dependent address instructions between the barrier and the read of d00 and made the interleaved tile SLOWER than the
+  // row-major one (10.16 -> 10.65 us); rebuilt from rr in front of the barrier 10.04 ; carried as here 9.99.
+  constexpr bool PAIRS = sizeof(T) == 8;
+  static_assert(!PAIRS || (round_sc<T>(0, 4) % 8 == 0 && round_sc<T>(0, J * 16 + 12) / 8 < 4 * TILE / 8 && ((4 * TILE / 8) & (4 * TILE / 8 - 1)) == 0),
+                "pb: every round's pivot block starts on a multiple of 8 elements below the buffer-toggle bit");
+  int pb = round_sc<T>(0, J * 16) / 8;
 #pragma unroll 1
   for (int rr = 0; rr < 4; ++rr) {
     const int jj0 = rr * 4, j0 = J * 16 + jj0;
     T* P = sc + (rr & 1) * 4 * TILE;
     T* Mw = sc + 2 * 4 * TILE + (rr & 1) * 4 * TILE;
+    const T* Pp = P + round_sc<T>(0, j0);
+    if constexpr (PAIRS) {
+      asm volatile("" : "+v"(pb));
+      Pp = sc + 8 * pb;
+      pb = (pb ^ (4 * TILE / 8)) + round_sc<T>(0, 4) / 8;
+    }
     if (act && PIV != 4) {  // (PIV 4, 5: timing experiments -- barrier only / publish + barrier only)
-      const int qc = tj - jj0, qr = ti - jj0;
-      if (qc >= 0 && qc < 4) {
+      // jj0 is a multiple of 4: the owners of this round's panel columns have tj >> 2 == rr and own column tj & 3 of it (M rows: ti) ;
+      // fp64 says so, which leaves their store addresses loop-invariant up to the buffer toggle.  The two forms select the same
+      // threads; fp32 keeps the older one only so that its kernels stay the instruction sequence that C3 was measured with (see
+      // round_sc: the one fp32 variant that was run in the chain had both changes and lost, and they were not separated).
+      const int qc = PAIRS ? tj & 3 : tj - jj0, qr = PAIRS ? ti & 3 : ti - jj0;
+      if (PAIRS ? (tj >> 2) == rr : (qc >= 0 && qc < 4)) {
 #pragma unroll
         for (int r = J; r < NS; ++r) {
           T v = a[r][J];
           if (r == J) v = (ti >= jj0) ? v : T(0);  // rows above the panel are dead
-          P[qc * TILE + ti + 16 * r] = v;
+          P[round_sc<T>(qc, ti + 16 * r)] = v;
         }
       }
-      if (qr >= 0 && qr < 4) {
+      if (PAIRS ? (ti >> 2) == rr : (qr >= 0 && qr < 4)) {
 #pragma unroll
-        for (int c = 0; c <= J; ++c) Mw[qr * TILE + tj + 16 * c] = g[J][c];
+        for (int c = 0; c <= J; ++c) Mw[round_sc<T>(qr, tj + 16 * c)] = g[J][c];
       }
     }
     __syncthreads();
@@ -202,10 +237,10 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
     if (!act) continue;
     if (PIV == 4 || PIV == 5) continue;
     // ---- every LDS read of the round: the 4x4 pivot block first, then my panel columns, my M columns, my panel rows ----
-    const T d00 = P[j0], d10 = P[j0 + 1], d20 = P[j0 + 2], d30 = P[j0 + 3];
+    const T d00 = Pp[round_sc<T>(0, 0)], d10 = Pp[round_sc<T>(0, 1)], d20 = Pp[round_sc<T>(0, 2)], d30 = Pp[round_sc<T>(0, 3)];
     __builtin_amdgcn_sched_barrier(0);
-    T d11 = P[TILE + j0 + 1], d21 = P[TILE + j0 + 2], d31 = P[TILE + j0 + 3];
-    T d22 = P[2 * TILE + j0 + 2], d32 = P[2 * TILE + j0 + 3], d33 = P[3 * TILE + j0 + 3];
+    T d11 = Pp[round_sc<T>(1, 1)], d21 = Pp[round_sc<T>(1, 2)], d31 = Pp[round_sc<T>(1, 3)];
+    T d22 = Pp[round_sc<T>(2, 2)], d32 = Pp[round_sc<T>(2, 3)], d33 = Pp[round_sc<T>(3, 3)];
     T r0, r1, r2, r3, l10, l20, l30, l21, l31, l32;
     if (PIV != 2) {
       __builtin_amdgcn_sched_barrier(0);
@@ -217,17 +252,17 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
 #pragma unroll
       for (int c = J; c < NS; ++c)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) u[q][c] = P[q * TILE + tj + 16 * c];
+        for (int q = 0; q < 4; ++q) u[q][c] = P[round_sc<T>(q, tj + 16 * c)];
     };
     auto ld_mw = [&] {
 #pragma unroll
       for (int c = 0; c <= J; ++c)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) mw[q][c] = Mw[q * TILE + tj + 16 * c];
+        for (int q = 0; q < 4; ++q) mw[q][c] = Mw[round_sc<T>(q, tj + 16 * c)];
 #pragma unroll
       for (int r = J; r < NS; ++r)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) w[q][r] = P[q * TILE + ti + 16 * r];
+        for (int q = 0; q < 4; ++q) w[q][r] = P[round_sc<T>(q, ti + 16 * r)];
     };
     constexpr bool SPLIT = PIV == 0;  // (the timing variants and the minors read everything here)
     if (PIV != 3) {
