@@ -172,9 +172,12 @@ __device__ __forceinline__ constexpr int round_sc(int q, int x) {
 }
 
 // hook: called once per round by every thread right after the round's barrier (the idle waves 4-7 of a 512-thread workgroup
-// can step a side job there -- the chain workgroup of k_chol_dag prefetches its next two tiles this way)
+// can step a side job there -- the chain workgroup of k_chol_dag prefetches its next two tiles this way).  chol_rounds calls
+// half<HB>(rr), round HB + rr: its loop over rr is not unrolled, but which group of four rounds it is is known at compile time.
 struct NoHook {
   __device__ __forceinline__ void operator()(int) const {}
+  template <int HB>
+  __device__ __forceinline__ void half(int) const {}
 };
 
 // PIV selects how the 4x4 pivot block is factored (identical results up to rounding):
@@ -191,7 +194,8 @@ struct NoHook {
 // keeps every later LDS read behind it.
 template <typename T, int J, int NS, typename H, int PIV = 0>
 __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* __restrict__ sc, T* __restrict__ piv,
-                                            const bool act, const int ti, const int tj, H& hook, const int hbase) {
+                                            const bool act, const int ti, const int tj, H& hook) {
+  constexpr int HB = NS == 2 ? 4 * J : 0;  // hook rounds: 0..7 over the two 16-column groups of a 32-block (elim_block32)
   // fp64: pb = where this round's pivot block starts in sc, in units of 8 elements ((rr & 1) * 4 * TILE + round_sc(0, j0), always a
   // multiple of 8, so the reads' 16-byte alignment stays known).  It is carried through the loop in a register and stepped by one
   // instruction (v_xad_u32: toggle the buffer, advance four columns), and the empty asm keeps the compiler from rebuilding it from
@@ -233,7 +237,7 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
       }
     }
     __syncthreads();
-    hook(hbase + rr);
+    hook.template half<HB>(rr);
     if (!act) continue;
     if (PIV == 4 || PIV == 5) continue;
     // ---- every LDS read of the round: the 4x4 pivot block first, then my panel columns, my M columns, my panel rows ----
@@ -418,10 +422,10 @@ __device__ __forceinline__ void factor_diag_tile512(T* bufA, T* bufB, T* sc, T* 
       g[r][c] = (R == Cc) ? T(1) : T(0);
     }
   __syncthreads();
-  chol_rounds<T, 0, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook, 0);
-  chol_rounds<T, 1, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook, 0);
-  chol_rounds<T, 2, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook, 0);
-  chol_rounds<T, 3, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook, 0);
+  chol_rounds<T, 0, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
+  chol_rounds<T, 1, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
+  chol_rounds<T, 2, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
+  chol_rounds<T, 3, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
   __syncthreads();  // piv complete
   if (tid < TILE) {
     const T p = piv[tid];
@@ -496,8 +500,8 @@ __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* 
       g[r][c] = (R == Cc) ? T(1) : T(0);
     }
   __syncthreads();
-  chol_rounds<T, 0, 2, H, PIV>(a, g, sc, piv + o, act, ti, tj, hook, 0);
-  chol_rounds<T, 1, 2, H, PIV>(a, g, sc, piv + o, act, ti, tj, hook, 4);
+  chol_rounds<T, 0, 2, H, PIV>(a, g, sc, piv + o, act, ti, tj, hook);
+  chol_rounds<T, 1, 2, H, PIV>(a, g, sc, piv + o, act, ti, tj, hook);
   __syncthreads();
   if (act) {
     T rsC[2], rsR[2];
@@ -1643,8 +1647,26 @@ __device__ __forceinline__ void subst_tile(T* Ts, T* Xs, T* G, F after_first) {
 }
 
 // side job of the chain workgroup, stepped by the idle waves 4-7 during the second half of a tile factorisation: look once
-// whether the two feeder tiles of the next column are parked, then move them into LDS one tile per round
+// whether the two feeder tiles of the next column are parked, then move them into LDS.
+// Two schedules, one per launch (dag_feed_deferred below, a compile-time choice like dag_block_subst):
+//   DEFER = false (fp32)  round 4 issues T = (k+1, k), round 5 consumes it and issues D = (k+1, k+1), round 6 consumes D.  A round's
+//                         barrier does not drain global loads (s_waitcnt lgkmcnt(0) ; s_barrier), so the idle waves meet their
+//                         s_waitcnt vmcnt(0) one round (~0.47 us) behind the issue of a fetch that takes 0.8 - 1.2 us, come late to the
+//                         next barrier, and the four elimination waves wait there for them -- twice per block column.
+//   DEFER = true  (fp64)  round 4 issues T, rounds 5 and 6 touch nothing that counts on vmcnt, round 7 consumes T (three rounds
+//                         behind its issue) and issues D into the same registers; D is consumed BEHIND the elimination, by store_d,
+//                         which the chain calls in front of the barrier that precedes S = D - L L' (D's first reader).
+// test (AGP_DAG_TEST_FEED, opts bits 2 and 3 of k_chol_dag): bit 0 -- every prefetched D element counts as not yet visible, so
+// store_d settles each of them again (DEFER only: the other schedule has no such path) ; bit 1 -- every look reports "not parked".
+// (-DAGP_FEED_DEFER=0 builds every launch with the first schedule: the A/B build of tools/step_boundary.py's per-column table)
+#ifndef AGP_FEED_DEFER
+#define AGP_FEED_DEFER 1
+#endif
 template <typename T>
+constexpr bool dag_feed_deferred() {
+  return AGP_FEED_DEFER && sizeof(T) == 8;
+}
+template <typename T, bool DEFER = dag_feed_deferred<T>()>
 struct ChainPrefetch {
   const T* src;  // hand-over slot of the parked tile (k+1, k) ; the parked diagonal tile (k+1, k+1) is the next slot
   T *dT, *dD;    // LDS destinations
@@ -1658,6 +1680,7 @@ struct ChainPrefetch {
   T* gL;           // A + (k * TILE) * ld + (k - 1) * TILE
   int ld_i;
   bool coh = false;  // the chain runs as a kernel of its own: its plain stores would only become visible when THAT kernel ends
+  int test = 0;      // AGP_DAG_TEST_FEED (see above)
   T v[TILE * TILE / 256];
   __device__ __forceinline__ void operator()(int round) {
     int t = (int)threadIdx.x - 256;
@@ -1689,7 +1712,7 @@ struct ChainPrefetch {
     if (round == 3) {
       if (t == 0)
         *ok = (__hip_atomic_load(f1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) &&
-              (__hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch);
+              (__hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) && !(test & 2);
       return;
     }
     if (round < 4 || round > 6 || !*ok) return;
@@ -1707,6 +1730,88 @@ struct ChainPrefetch {
 #pragma unroll
       for (int q = 0; q < TILE * TILE / 256; ++q)
         v[q] = __hip_atomic_load(g + t + q * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  // 0 when x has the high word of the sentinel (no arithmetic produces that NaN payload, so "may be the sentinel" is almost never
+  // true of data): the side job's two consumers test sixteen elements with two instructions each; store_d looks properly only then.  The
+  // element-by-element test and address arithmetic of operator() cost the idle waves as many issue cycles as a whole round has.
+  static __device__ __forceinline__ unsigned sent_away(T x) {
+    typedef typename Sent<T>::U U;
+    return (unsigned)(__builtin_bit_cast(U, x) >> (8 * sizeof(U) - 32)) ^ (unsigned)(Sent<T>::bits >> (8 * sizeof(U) - 32));
+  }
+  // What chol_rounds calls.  DEFER: the side job with the group of four rounds as a compile-time constant.  With the round number a
+  // run-time value both of elim_block32's loops carried every path of the job: v[] lived through rounds 0..3 as well, and the
+  // compiler moved it between register sets behind the Dg and L stores under an s_waitcnt vmcnt(0) of its own (stores count on
+  // vmcnt too).  Now rounds 0..3 have no v[], and rounds 4..7 touch it in rounds 4 and 7 only.
+  template <int HB>
+  __device__ __forceinline__ void half(int rr) {
+    if (!DEFER) {
+      (*this)(HB + rr);
+      return;
+    }
+    int t = (int)threadIdx.x - 256;
+    if (t < 0) return;
+    asm volatile("" : "+v"(t));  // (see operator())
+    if (HB == 0) {
+      if (rr < 2) {  // L_{k-1,k-1} -> Dg
+        if (dgsrc) {
+#pragma unroll
+          for (int q = 0; q < TILE * TILE / 512; ++q) {
+            const int e = t + (2 * q + rr) * 256;
+            if (coh) __hip_atomic_store(gDg + e, dgsrc[(e >> 6) * LDP + (e & 63)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else gDg[e] = dgsrc[(e >> 6) * LDP + (e & 63)];
+          }
+        }
+        return;
+      }
+      if (lsrc) {  // L(k, k-1) -> A, half per round
+#pragma unroll
+        for (int q = 0; q < TILE * TILE / 512; ++q) {
+          const int e = t + (2 * q + (rr - 2)) * 256;
+          gL[(e >> 6) * ld_i + (e & 63)] = lsrc[(e >> 6) * LDP + (e & 63)];
+        }
+      }
+      if (src && rr == 3 && t == 0)  // the look: where it was, so the feeders' deadline does not move
+        *ok = (__hip_atomic_load(f1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) &&
+              (__hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) && !(test & 2);
+      return;
+    }
+    if (!src || (rr != 0 && rr != 3) || !*ok) return;
+    if (rr == 3) {  // round 7: T, issued three rounds ago
+      T* d = dT + (t >> 6) * LDP + (t & 63);  // element t + 256 q sits 4 q rows below element t: one address, constant offsets
+      unsigned away = ~0u;
+#pragma unroll
+      for (int q = 0; q < TILE * TILE / 256; ++q) {
+        away = min(away, sent_away(v[q]));
+        d[q * 4 * LDP] = v[q];
+      }
+      if (away == 0) *bad = 1;  // the sentinel's high word is proof enough: the column goes the blocking way, which re-loads and settles
+    }
+    const T* g = rr == 0 ? src : src + TILE * TILE;  // round 4: T ; round 7: D (consumed by store_d)
+#pragma unroll
+    for (int q = 0; q < TILE * TILE / 256; ++q)
+      v[q] = __hip_atomic_load(g + t + q * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // DEFER, column not late (the look saw both flags up and T came whole): D, issued in round 7, from the idle waves' registers into
+  // LDS.  An element that still reads as the sentinel is re-loaded in place (hv_settle, as the blocking loaders do) -- the flags were
+  // up, so this is a bounded re-load of data that is on its way, not a wait on a flag.  The caller's next barrier publishes dD.
+  __device__ __forceinline__ void store_d() {
+    int t = (int)threadIdx.x - 256;
+    if (t < 0) return;
+    asm volatile("" : "+v"(t));  // (as in operator(): keeps sixteen LDS offsets from living through the factorisation)
+    const T* g = src + TILE * TILE + t;
+    const bool again = (test & 1) != 0;
+    unsigned away = ~0u;
+#pragma unroll
+    for (int q = 0; q < TILE * TILE / 256; ++q) away = min(away, sent_away(v[q]));
+    T* d = dD + (t >> 6) * LDP + (t & 63);
+    if (away == 0 || again) {
+#pragma unroll
+      for (int q = 0; q < TILE * TILE / 256; ++q)
+        d[q * 4 * LDP] = hv_settle<T>(g + q * 256, again ? __builtin_bit_cast(T, Sent<T>::bits) : v[q]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < TILE * TILE / 256; ++q) d[q * 4 * LDP] = v[q];
     }
   }
 };
@@ -2039,6 +2144,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   // opts bit 0: the chain also stores X_k to its real home (a single block column wanting its inverse: no identity rows run)
   //      bit 1: the factor L is wanted in its real home A as well (K's factor, the potrf entry points); the CAVI step only
   //             consumes the extension rows W, v and never reads L itself, so its launches skip those stores
+  //      bits 2, 3: AGP_DAG_TEST_FEED (test hook, ChainPrefetch::test)
   const int64_t nx = STEP ? 0 : nx_;
   constexpr bool SUBST = dag_block_subst<T, STEP, BATCH>();  // X_k travels without its off-diagonal block (nobody reads X_k as such)
   const int write_x = STEP ? 0 : (opts & 1);
@@ -2471,7 +2577,11 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       pf.gL = A + k0 * ld + (k0 - TILE);
       pf.ld_i = (int)ld;
       pf.coh = ROLE == 1;
+      pf.test = (opts >> 2) & 3;
       if (tid == 0) pf_ok = pf_bad = 0;
+#ifdef AGP_STEP_TRACE
+      PRO_TS(528 + k);  // (per block column: 528 + k the elimination starts, 512 + k it ends, 560 + k the path its side job took)
+#endif
       factor_diag_tile_2lvl<T, ChainPrefetch<T>, AGP_PIVOT_ALG, SUBST>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
       DAG_TRC(k, 2);
       PRO_TS(512 + k);
@@ -2505,6 +2615,11 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
         return;
       }
       const bool late_feed = !pf_ok || pf_bad;
+#ifdef AGP_STEP_TRACE
+      // how column k + 1's two tiles came in: 1 prefetched under this elimination, 2 late because the look failed, 3 late because
+      // T still held a sentinel (development builds only, like every stamp: tools/step_boundary.py prints it)
+      if (PRO && trace && tid == 0) trace[560 + k] = !pf_ok ? 2ull : pf_bad ? 3ull : 1ull;
+#endif
       if (late_feed) {  // the feeders were not done (or not yet visible) when the side job looked: fetch now
         // X_k is published BEFORE this wait: the second feeder, tile (k+1, k+1), is the first workgroup of block column k + 1, and
         // it may not have a slot yet while all of column k's workgroups sit waiting for X_k (a launch whose block column does not
@@ -2564,6 +2679,9 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
           // (its real home in A is written by the idle waves during the next factorisation: ChainPrefetch rounds 2, 3)
         }
       }
+      // (deferred feed) D from the idle waves' registers; a late column has both tiles from the blocking fetch above, and what
+      // round 7 asked for is dropped
+      if (dag_feed_deferred<T>() && !late_feed) pf.store_d();
       __syncthreads();
       DAG_TRC(k + 1, 5);
       //   S = D - L L': only the ten 16x16 tiles on and below the diagonal (the factorisation never reads above it); every

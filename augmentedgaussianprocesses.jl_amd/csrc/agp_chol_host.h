@@ -475,6 +475,17 @@ static bool dag_test_abort() {
   return on;
 }
 
+// test hook (AGP_DAG_TEST_FEED=1 / 2): how the chain's side job treats the two feeder tiles of the next block column (ChainPrefetch,
+// agp_chol.h) -- 1: every prefetched D element counts as not yet visible and is settled again ; 2: every look reports "not parked",
+// so every column takes the blocking fetch.  Both re-load valid data: results are bit for bit those of the default path.
+static int dag_test_feed() {
+  static const int v = []() {
+    const char* e = getenv("AGP_DAG_TEST_FEED");
+    return e && e[0] == '1' ? 1 : e && e[0] == '2' ? 2 : 0;
+  }();
+  return v;
+}
+
 // ---- the task-graph launch (k_chol_dag) -------------------------------------------------------------------------------
 // the flag array of the task graph: at least nf epoch-stamped words (grown with some slack; a new array starts at epoch 0)
 static agp_status dag_flags_ensure(agp_ctx* c, int64_t nf) {
@@ -535,7 +546,7 @@ template <typename T, typename K, int ROLE>
 static void dag_enqueue(agp_ctx* c, unsigned grid, hipStream_t stream, const DagArgs<T>& a) {
   hipLaunchKernelGGL((k_chol_dag<T, true, K::BATCH, false, K::STEP, K::PRO, ROLE>), dim3(grid), dim3(CHOL_THREADS), 0, stream, a.bt,
                      a.nb, a.fstride, a.ld, a.ldx, a.lde, a.ne, a.nt, a.info, a.nvalid, c->dag_flags, c->dag_epoch, a.trace, a.H,
-                     a.hstride, a.nx, a.erow, a.opts, a.ds, a.pro, a.epi, a.prod);
+                     a.hstride, a.nx, a.erow, a.opts | (dag_test_feed() << 2), a.ds, a.pro, a.epi, a.prod);
 }
 // One task-graph launch of `grid` workgroups on the context's stream -- or, split (STEP instantiations only), as two kernels: the
 // a.nb chain workgroups on their own stream (enqueued first), every other tile on this one, behind the wait for the chains' residency

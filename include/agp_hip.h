@@ -17,10 +17,10 @@
  *   - work is enqueued asynchronously on the ctx stream; calls that return host scalars or a
  *     data-dependent status (refresh_K, elbo, check_status, ctx_sync) synchronise that stream.
  *
- * Environment (all the library reads; 17 variables, each read once per process unless said otherwise).  The first eight switch a
+ * Environment (all the library reads; 18 variables, each read once per process unless said otherwise).  The first eight switch a
  * default path off for the FALLBACK that also exists on its own -- the GPU suite is run once with each of them, AGP_CHAIN_SPLIT both
  * ways (tools/suite_with_fallbacks.sh, profiles/r05_fallback_suites.txt); AGP_CHOL_GROUP, AGP_CHOL_LOOKAHEAD and the test hook
- * AGP_DAG_TEST_ABORT are exercised by tests of their own.  The A/B levers of earlier rounds are gone (docs/DESIGN_LOG.md has their numbers).
+ * AGP_DAG_TEST_ABORT / AGP_DAG_TEST_FEED are exercised by tests of their own.  The A/B levers of earlier rounds are gone (docs/DESIGN_LOG.md has their numbers).
  *   AGP_CHOL_DAG=0|1          never / always factor with the one-launch tile task graph (default: up to 32 block columns, i.e. m <= 2048;
  *                             beyond, and after a lost dependency, plain launches per block column / blocked panels)
  *   AGP_CHAIN_SPLIT=0|1       the task graph as one kernel / as chain kernel + tile kernel (default: two kernels from 600 tiles,
@@ -42,6 +42,10 @@
  *   AGP_CHOL_LOOKAHEAD=0      ... without its side stream
  *   AGP_DAG_TEST_ABORT=1      test hook: every task-graph launch of a CAVI step is treated as having lost a dependency (the in-stream
  *                             fallback k_chol_safe / k_safe_rowstats redoes it)
+ *   AGP_DAG_TEST_FEED=1|2     test hook: how the chain workgroup of a task-graph launch takes in the two feeder tiles of the next block
+ *                             column -- 1: every prefetched element of the diagonal tile counts as not yet visible and is re-loaded in
+ *                             place (fp64 launches; fp32 has no such path) ; 2: the look at the feeders' flags always fails, so every
+ *                             column takes the blocking fetch.  Same bits as the default on both (tests/test_gpu_chain_prefetch.py)
  *   AGP_DAG_TEST_OVERSUBSCRIBE=1  test hook (with AGP_DAG_TEST_ABORT=1): the fallback's grid is made too large to be resident at once, so
  *                             its grid barrier runs into its limit (8 s) and the step ends in status -3 / AGP_ERR_HIP instead of a hang
  *   AGP_SPLIT_OVERLAP=1       (read at every step) batch-parallel statistics travel in block-column groups next to the next

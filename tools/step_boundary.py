@@ -6,7 +6,9 @@
 
 `run` trains the bench's C2 model (bench.make_data / bench.build_model, look-ahead on, as bench.py does) and destroys the context,
 which writes the dump.  `table` averages the last launches of each dump; every time is in us relative to the end of the chain's
-last tile elimination, factor(nt - 1), of the same launch ("next" rows: of the launch before)."""
+last tile elimination, factor(nt - 1), of the same launch ("next" rows: of the launch before).  Below it, per block column of the
+chain: how long the tile elimination and the glue behind it took and which way the next column's two feeder tiles came in (prefetched
+under the elimination, or late because the look failed / because a sentinel was seen)."""
 import os
 import sys
 
@@ -14,6 +16,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XPUB, EXT, FILL0, FILL1, WG0, WG1, SAFE0, SAFE1 = 600, 1100, 1400, 1500, 2048, 4096, 6144, 6400
+ELIM0, PATH = 528, 560  # per block column k: factor(k) starts ; the path word of column k + 1's feed (PRO_TS, agp_chol.h)
 
 
 def run(dump, steps, warm):
@@ -67,6 +70,40 @@ def load(dump):
     return r
 
 
+PATHS = {1: "prefetched", 2: "late: look failed", 3: "late: sentinel in T"}
+
+
+def columns(cur, nt):
+    """per block column k: the tile elimination factor(k) (ELIM0 + k -> 512 + k), the glue behind it (512 + k -> ELIM0 + k + 1: X_k
+    out, the substitution, S = D - L L') and how the side job that ran under factor(k) brought in the tiles of column k + 1
+    (PATH + k; the last column has none).  Stamps of libraries built before these slots existed read as missing."""
+    e0, e1, path = cur[:, ELIM0:ELIM0 + nt], cur[:, 512:512 + nt], cur[:, PATH:PATH + nt]
+    if not np.isfinite(e0).any():
+        return ["  (no per-column elimination stamps in this dump)"]
+
+    def med(x):
+        x = x[np.isfinite(x)]
+        return float(np.median(x)) if x.size else float("nan")
+
+    out = ["  per block column: elimination us | glue us | path of the next column's feed (share of launches; median path first)"]
+    for k in range(nt):
+        el = med((e1[:, k] - e0[:, k]) * 0.01)
+        gl = med((e0[:, k + 1] - e1[:, k]) * 0.01) if k + 1 < nt else float("nan")
+        pk = path[:, k][np.isfinite(path[:, k])].astype(int)
+        if pk.size:
+            order = sorted(PATHS, key=lambda c: (c != int(np.median(pk)), c))
+            what = "  ".join(f"{PATHS[c]} {np.mean(pk == c):4.0%}" for c in order if np.any(pk == c))
+        else:
+            what = "-"
+        out.append(f"    k = {k:2d}  {el:6.2f}  {gl:6.2f}  {what}")
+    pre = np.array([np.nanmedian(path[:, k]) == 1 for k in range(nt - 1)])
+    el = np.array([med((e1[:, k] - e0[:, k]) * 0.01) for k in range(nt)])
+    if pre.any():
+        out.append(f"  eliminations: prefetched columns (median path) {np.mean(el[:nt - 1][pre]):6.2f}   others "
+                   f"{np.mean(el[:nt - 1][~pre]) if (~pre).any() else float('nan'):6.2f}   column {nt - 1} (no side job) {el[nt - 1]:6.2f}")
+    return out
+
+
 def table(dumps, last=200, nt=16, ne=17):
     rows = []
     for dump in dumps:
@@ -109,6 +146,7 @@ def table(dumps, last=200, nt=16, ne=17):
         out.append(f"  factor(k) - factor(k-1), k = 1..{nt - 1}: " + " ".join(f"{x:6.2f}" for x in d))
         out.append(f"  mean over k {np.mean(d):6.3f}   factor({nt - 1}) - factor(0) {med(f[:, nt - 1] - f[:, 0]) * 0.01:8.2f}")
         out.append(f"  chain start -> factor(0) done {med(f[:, 0] - cur[:, 0]) * 0.01:8.2f}")
+        out += columns(cur, nt)
         rows += out
     return "\n".join(rows)
 
