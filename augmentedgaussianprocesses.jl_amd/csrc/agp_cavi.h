@@ -32,6 +32,11 @@ enum { FLAG_NEG_KTILDE = 1, FLAG_BAD_LABEL = 2 };
 // points of the online model rely on exact zeros); a NaN argument gives a finite value like the d2 > 0 ? d2 : 0 in front of every
 // call always did.  Max relative error against exp over [-745, 0]: 9e-15 (the truncation at |r| = ln2 / 2; tests/test_gpu_round6.py).
 // fp32: v_exp_f32 with log2 e folded into the argument (1.5 ulp of the instruction + the argument's rounding, |x| 2^-24 relative).
+// The instruction returns 0 where its result would be a denormal (x log2 e < -126).  Alone that is an absolute error below FLT_MIN,
+// but the Matern kernels multiply e^x by a polynomial of up to ~2600 there and every kernel by the variance: values up to 4e-35 came
+// back as 0 (tests/test_gpu_kernelmatrix_edges.py found it with ARD scales, fp32 Matern 3/2).  So below -126 the instruction gets
+// the argument + 64 -- exact: a multiple of the argument's ulp and smaller -- and its result is scaled by 2^-64 in a multiply, which
+// keeps denormals (the kernels run with fp32 denormals on): the same range extension the compiler's own exp2f carries.
 // ---------------------------------------------------------------------------------------------------
 struct ExpScalePlain {  // e^x, x <= 0
   static constexpr double ct = 1.44269504088896338700e+00;    // n = rint(ct x)
@@ -70,12 +75,16 @@ __device__ __forceinline__ double exp_core_d(double x) {
 }
 // e^x for x <= 0 (x > 0 is not an error but loses the clamp's protection against overflow of the exponent: not used that way)
 __device__ __forceinline__ double exp_nonpos(double x) { return exp_core_d<ExpScalePlain>(__builtin_fmax(x, ExpScalePlain::lim)); }
-__device__ __forceinline__ float exp_nonpos(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896338700f); }
+__device__ __forceinline__ float exp2_nonpos_f(float t) {  // 2^t, t <= 0, denormal results included
+  const bool low = t < -126.0f;
+  return __builtin_amdgcn_exp2f(t + (low ? 64.0f : 0.0f)) * (low ? 0x1p-64f : 1.0f);
+}
+__device__ __forceinline__ float exp_nonpos(float x) { return exp2_nonpos_f(x * 1.44269504088896338700f); }
 // e^(-u/2) for u >= 0 (negative or NaN u: treated as 0, like kernel_base's own clamp)
 __device__ __forceinline__ double exp_mhalf(double u) {
   return exp_core_d<ExpScaleHalfNeg>(__builtin_fmin(__builtin_fmax(u, 0.0), ExpScaleHalfNeg::lim));
 }
-__device__ __forceinline__ float exp_mhalf(float u) { return __builtin_amdgcn_exp2f(__builtin_fmaxf(u, 0.0f) * (-0.5f * 1.44269504088896338700f)); }
+__device__ __forceinline__ float exp_mhalf(float u) { return exp2_nonpos_f(__builtin_fmaxf(u, 0.0f) * (-0.5f * 1.44269504088896338700f)); }
 
 template <typename T>
 __device__ __forceinline__ T kernel_base(int kind, T d2) {
@@ -193,13 +202,17 @@ __global__ __launch_bounds__(NTHREADS) void k_kernelmatrix(const T* __restrict__
 // with 16-byte coalesced loads (a gathered minibatch row is one contiguous segment) and the scale folded in on the way.
 // The GEMM form loses digits when two points (nearly) coincide -- K_ZZ's diagonal, inducing points picked from the data --
 // which the first-order kernels (Exponential, Matern) would amplify through sqrt: every element with
-// d2 < KMM_CLOSE (||x||^2 + ||y||^2) is recomputed by direct differences from the tiles still in LDS (rare, so the divergent
+// d2 < KMM_CLOSE<T> (||x||^2 + ||y||^2) is recomputed by direct differences from the tiles still in LDS (rare, so the divergent
 // branch costs little); everything else carries an absolute error of a few ulp(||x||^2 + ||y||^2) in d2.
 // One workgroup = one 64-row tile x `ctiles` consecutive column tiles (grid.x = column groups).  With alpha, the fused row-dot
 // sum_j out[i][j] alpha[j] is accumulated in registers over all column tiles of the group and leaves ONE partial slice per
 // group (part[blockIdx.x][i]): streaming prediction runs with a single group -- K*m and per-tile partials never reach memory.
 // ---------------------------------------------------------------------------------------------------
 constexpr int KMM_MAXD = 128;
+// the repair threshold above, per type: far enough over the GEMM form's error of a few (Dp + 3) u (||x||^2 + ||y||^2) that what stays
+// on that form keeps d2 to a relative 2 gamma_{Dp+3} / KMM_CLOSE<T> (the element-wise budget of tests/_kmat_ref.py rests on these values)
+template <typename T>
+constexpr T KMM_CLOSE = sizeof(T) == 8 ? T(1e-3) : T(3e-2);
 
 // Y side of k_kernelmatrix_mma, prepared once per (kernel, Y): Ysc[j][d] = s_d Y[j][d] (rows padded to a multiple of 64 and
 // columns to Dp with zeros) and yn[j] = ||s . y_j||^2.  For the inducing points this is done at every K refresh, so the step
@@ -295,7 +308,7 @@ __global__ __launch_bounds__(NTHREADS, ((SPEC == 3 || SPEC == 0) ? 2 : (sizeof(T
     s += __shfl_xor(s, 2);
     if (q4 == 0) xn[r] = s;
   }
-  const T close_thr = sizeof(T) == 8 ? T(1e-3) : T(3e-2);
+  const T close_thr = KMM_CLOSE<T>;
   T rs[2][4];
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
