@@ -63,7 +63,7 @@ from .nvi import gauss_hermite_rule, mc_expectations, mc_normals, quad_expectati
 from .pathwise import PathwiseSamples, pathwise_features, sample_paths  # noqa: F401
 from .capi import AGPError  # noqa: F401
 from .persistence import load_trained_model, save_trained_model  # noqa: F401
-from .inducingpoints import KmeansAlg, RandomSubset, inducingpoints  # noqa: F401
+from .inducingpoints import ConditionalVariance, KmeansAlg, RandomSubset, inducingpoints  # noqa: F401
 from .online import (  # noqa: F401
     OIPS,
     OnlineSVGP,

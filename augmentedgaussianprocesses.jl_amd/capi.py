@@ -160,6 +160,7 @@ SYMBOLS = {
     "agp_svgp_proba_y": (_I32, [_VP, _VP, _I64, _I64, _PDBL, _PDBL, _I32, _VP, _VP]),
     "agp_nearest_center": (_I32, [_VP, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),
     "agp_kmeans": (_I32, [_VP, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _I32, _DBL, _VP, _VP, _PI32, _PDBL, _PI32]),
+    "agp_greedy_variance": (_I32, [_VP, _I32, _PK, _VP, _I64, _I64, _I64, _I64, _DBL, _VP, _VP, _I64, _VP, _I64, _VP, _PI64]),
     "agp_svgp_online_snapshot": (_I32, [_VP, _I32, _VP, _I64, _VP, _PDBL]),
     "agp_svgp_set_online_prior": (_I32, [_VP, _I32, _VP, _I64, _I64, _VP, _I64, _VP, _DBL]),
     "agp_svgp_adopt_local": (_I32, [_VP, _VP]),

@@ -15,6 +15,7 @@
 #include "agp_comm.h"
 #include "agp_hyper.h"
 #include "agp_kmeans.h"
+#include "agp_greedy.h"
 #include "agp_linalg.h"
 #include "agp_nvi.h"
 #include "agp_rand.h"
@@ -5776,6 +5777,81 @@ static agp_status bb_kmeans(agp_ctx* ctx, const void* xv, int64_t n, int64_t ldx
   return st;
 }
 
+// ---- inducing-point selection: greedy conditional variance, a pivoted partial Cholesky of K_NN (agp_greedy.h) --------------------
+template <typename T>
+static agp_status bb_greedy(agp_ctx* ctx, const agp_kernel_desc* k, const void* xv, int64_t n, int64_t ldx, int64_t D, int64_t m,
+                            double tol, int64_t* idx_out, void* zv, int64_t ldz, void* factor_out, int64_t ldf, double* trace_out,
+                            int64_t* n_selected_host) {
+  const T* x = (const T*)xv;
+  T* z = (T*)zv;
+  const int64_t Np = (n + GV_BLOCK - 1) / GV_BLOCK * GV_BLOCK, nblk = Np / GV_BLOCK;
+  double *F = nullptr, *Xt = nullptr, *dres = nullptr, *aux = nullptr;
+  GvPart* part = nullptr;
+  GvState* st = nullptr;
+  auto release = [&]() {
+    (void)hipFree(F);
+    (void)hipFree(Xt);
+    (void)hipFree(dres);
+    (void)hipFree(aux);
+    (void)hipFree(part);
+    (void)hipFree(st);
+  };
+  // the factor, column-contiguous: 8 n m bytes (n padded to the workgroup)
+  if (m > (int64_t)(INT64_MAX / 8) / Np || hipMalloc((void**)&F, sizeof(double) * (size_t)(m * Np)) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "agp_greedy_variance: cannot allocate the factor workspace of " +
+               (m > (int64_t)(INT64_MAX / 8) / Np ? std::string("more than 2^63") : std::to_string(8 * m * Np)) + " bytes (8 n m)";
+    return AGP_ERR_NOMEM;
+  }
+  agp_status s = dmalloc(ctx, &Xt, D * Np);
+  if (s == AGP_OK) s = dmalloc(ctx, &dres, Np);
+  if (s == AGP_OK) s = dmalloc(ctx, &aux, 2 * GV_MAXD + m);  // scales | pivot coordinates | pivot coefficient row
+  if (s == AGP_OK) s = dmalloc(ctx, &part, nblk);
+  if (s == AGP_OK) s = dmalloc(ctx, &st, 1);
+  if (s != AGP_OK) {
+    release();
+    return s;
+  }
+  double *scales = aux, *zp = aux + GV_MAXD, *lp = aux + 2 * GV_MAXD;
+  std::vector<double> hs(D);
+  for (int64_t d = 0; d < D; ++d) hs[d] = k->ard ? k->ard_scales_host[d] : k->scale;
+  hipError_t e = hipMemcpyAsync(scales, hs.data(), sizeof(double) * D, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(F, 0, sizeof(double) * (size_t)(m * Np), ctx->stream);  // columns behind an early stop: 0
+  if (e == hipSuccess) e = hipMemsetAsync(st, 0, sizeof(GvState), ctx->stream);
+  if (e == hipSuccess) {
+    const int64_t tiles = ((n + 31) / 32) * ((D + 31) / 32);
+    hipLaunchKernelGGL((k_gv_transpose<T>), dim3((unsigned)tiles), dim3(32, 8), 0, ctx->stream, x, ldx, n, D, Xt, Np);
+    hipLaunchKernelGGL((k_gv_prefill<T>), grid1(m * D), dim3(256), 0, ctx->stream, m, (int)D, idx_out, z, ldz, trace_out);
+    hipLaunchKernelGGL(k_gv_init, dim3((unsigned)nblk), dim3(GV_BLOCK), 0, ctx->stream, n, k->variance, dres, part);
+    const double thr = tol * k->variance;
+    for (int64_t j = -1; j < m; ++j) {
+      if (j >= 0)
+        hipLaunchKernelGGL(k_gv_step, dim3((unsigned)nblk), dim3(GV_BLOCK), 0, ctx->stream, (const double*)Xt,
+                           (const double*)scales, n, Np, (int)D, (int)k->kind, k->variance, j, F, dres, (const GvState*)st,
+                           (const double*)zp, (const double*)lp, part);
+      hipLaunchKernelGGL((k_gv_finish<T>), dim3(1), dim3(GV_BLOCK), 0, ctx->stream, (const GvPart*)part, nblk, j, m, thr, x, ldx,
+                         (int)D, (const double*)F, Np, st, zp, lp, idx_out, z, ldz, trace_out);
+    }
+    if (factor_out) {
+      const int64_t ft = ((m + 31) / 32) * ((n + 31) / 32);
+      hipLaunchKernelGGL((k_gv_transpose<double>), dim3((unsigned)ft), dim3(32, 8), 0, ctx->stream, (const double*)F, Np, m, n,
+                         (double*)factor_out, ldf);
+    }
+    e = hipGetLastError();
+  }
+  GvState hst{};
+  if (e == hipSuccess) e = hipMemcpyAsync(&hst, st, sizeof(GvState), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // the one synchronisation of the call
+  release();
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) {
+    ctx->err = std::string("agp_greedy_variance : ") + hipGetErrorString(e);
+    return AGP_ERR_HIP;
+  }
+  if (n_selected_host) *n_selected_host = hst.nsel;
+  return AGP_OK;
+}
+
 #define DISPATCH(dtype, call_f64, call_f32)        \
   do {                                             \
     DevGuard _dev_guard(ctx->device);              \
@@ -5846,6 +5922,35 @@ agp_status agp_kmeans(agp_ctx* ctx, int32_t dtype, const void* x, int64_t n, int
                              objective_host, converged_host),
            bb_kmeans<float>(ctx, x, n, ldx, D, centers, ldc, m, max_iter, tol, labels_out, counts_out, iters_host,
                             objective_host, converged_host));
+}
+
+agp_status agp_greedy_variance(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                               int64_t D, int64_t m, double tol, int64_t* idx_out, void* z_out, int64_t ldz, void* factor_out,
+                               int64_t ldf, double* trace_out, int64_t* n_selected_host) {
+  if (!ctx) return AGP_ERR_INVALID;
+  // everything is refused before any buffer of the caller is read or written
+  const char* bad = nullptr;
+  if (!k || !x || !idx_out || !z_out) bad = "null kernel descriptor, x, idx_out or z_out";
+  else if (dtype != AGP_F64 && dtype != AGP_F32) bad = "dtype is AGP_F64 or AGP_F32";
+  else if (n <= 0 || m <= 0 || m > n) bad = "0 < m <= n";
+  else if (D <= 0 || D > GV_MAXD) bad = "0 < D <= 128";
+  else if (ldx < D || ldz < D || (factor_out && ldf < m)) bad = "ldx >= D, ldz >= D, ldf >= m";
+  else if (!(tol >= 0.0)) bad = "tol >= 0";
+  else if (k->kind < AGP_K_SQEXP || k->kind > AGP_K_EXPONENTIAL || !(k->variance > 0.0) || !std::isfinite(k->variance))
+    bad = "kernel kind 0..3 and a positive finite variance";
+  else if (k->ard && !k->ard_scales_host) bad = "ard without ard_scales_host";
+  else {
+    for (int64_t d = 0; d < (k->ard ? D : 1); ++d) {
+      const double sc = k->ard ? k->ard_scales_host[d] : k->scale;
+      if (!(sc > 0.0) || !std::isfinite(sc)) bad = "positive finite kernel scales";
+    }
+  }
+  if (bad) {
+    ctx->err = std::string("agp_greedy_variance: ") + bad;
+    return AGP_ERR_INVALID;
+  }
+  DISPATCH(dtype, bb_greedy<double>(ctx, k, x, n, ldx, D, m, tol, idx_out, z_out, ldz, factor_out, ldf, trace_out, n_selected_host),
+           bb_greedy<float>(ctx, k, x, n, ldx, D, m, tol, idx_out, z_out, ldz, factor_out, ldf, trace_out, n_selected_host));
 }
 
 // development / test hook (not part of include/agp_hip.h): how many task-graph factorisations the in-stream fallback re-ran

@@ -5,15 +5,21 @@ re-exported, unvendored InducingPoints.jl: AFK-MC2 seeding + Clustering.kmeans!)
 Host logic only: the random seeding draws (they need the caller's RNG) and the short sequential Metropolis chains run
 here on a few thousand gathered candidate points; every O(N m D) distance pass and the Lloyd iterations run on the GPU
 through `agp_nearest_center` / `agp_kmeans` (csrc/agp_kmeans.h).
+
+`inducingpoints(ConditionalVariance(m, kernel), X)` is the kernel-aware selection: greedy conditional-variance selection (the
+greedy MAP of a k-DPP), a pivoted partial Cholesky factorisation of K_NN that runs entirely on the device through
+`agp_greedy_variance` (csrc/agp_greedy.h).  It is deterministic: there is nothing for an RNG to do.
 """
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from typing import Optional
 
 import numpy as np
 
 from . import capi
+from .kernels import Kernel
 
 
 class KmeansAlg:
@@ -30,6 +36,20 @@ class RandomSubset:
 
     def __init__(self, m: int):
         self.m = int(m)
+
+
+class ConditionalVariance:
+    """ConditionalVariance(m, kernel; tol=1e-9): at every step the point with the largest conditional variance under `kernel`
+    given the points already chosen (ties to the smaller index); stops early once that variance is <= tol * kernel variance."""
+
+    def __init__(self, m: int, kernel, tol: float = 1e-9):
+        if m <= 0:
+            raise ValueError("the number of inducing points must be positive")
+        if not isinstance(kernel, Kernel):
+            raise TypeError("ConditionalVariance: kernel must be a Kernel")
+        if not tol >= 0:
+            raise ValueError("ConditionalVariance: tol must be non-negative")
+        self.m, self.kernel, self.tol = int(m), kernel, float(tol)
 
 
 def _seeding_chains(x_first, cand, u):
@@ -68,6 +88,8 @@ def inducingpoints(alg, X, *, rng: Optional[np.random.Generator] = None, obsdim:
     if isinstance(alg, RandomSubset):
         idx = np.sort(rng.choice(N, alg.m, replace=False))
         return Xd[torch.as_tensor(idx, device=dev)].cpu().numpy().astype(np.float64)
+    if isinstance(alg, ConditionalVariance):
+        return _conditional_variance(alg, Xd, dev, td, return_info)
     if not isinstance(alg, KmeansAlg):
         raise TypeError(f"{alg} is not an implemented inducing-point selection algorithm")
     L = capi.lib()
@@ -105,4 +127,37 @@ def inducingpoints(alg, X, *, rng: Optional[np.random.Generator] = None, obsdim:
         L.agp_ctx_destroy(ctx)
     if return_info:
         return Z, dict(seeds=seeds, iterations=iters.value, cost=obj.value, converged=bool(conv.value))
+    return Z
+
+
+def _conditional_variance(alg, Xd, dev, td, return_info):
+    import torch
+
+    N, D = Xd.shape
+    L = capi.lib()
+    ctx = C.c_void_p()
+    st = L.agp_ctx_create(dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(ctx))
+    if st != 0:
+        raise capi.AGPError(st, "agp_ctx_create")
+    try:
+        kd, keep = alg.kernel.desc(D)
+        idx = torch.empty(alg.m, dtype=torch.int64, device=dev)
+        Zd = torch.empty((alg.m, D), dtype=td, device=dev)
+        trace = torch.empty(alg.m, dtype=torch.float64, device=dev)
+        nsel = C.c_int64()
+        st = L.agp_greedy_variance(ctx, capi.F64 if td == torch.float64 else capi.F32, C.byref(kd), C.c_void_p(Xd.data_ptr()), N,
+                                   Xd.stride(0), D, alg.m, alg.tol, C.c_void_p(idx.data_ptr()), C.c_void_p(Zd.data_ptr()), D, None,
+                                   0, C.c_void_p(trace.data_ptr()), C.byref(nsel))
+        if st != 0:
+            raise capi.AGPError(st, L.agp_last_error(ctx).decode())
+        del keep
+    finally:
+        L.agp_ctx_destroy(ctx)
+    k = int(nsel.value)
+    if k < alg.m:
+        warnings.warn(f"ConditionalVariance: selected {k} of the {alg.m} inducing points asked for: the largest remaining "
+                      f"conditional variance fell to tol = {alg.tol:g} times the kernel variance")
+    Z = Zd[:k].cpu().numpy().astype(np.float64)
+    if return_info:
+        return Z, dict(indices=idx[:k].cpu().numpy(), trace=trace[:k].cpu().numpy(), selected=k, factor=None)
     return Z

@@ -261,7 +261,7 @@ agp_status agp_ctx_task_graph_fallbacks(agp_ctx* ctx, int64_t* n_host);
 const char* agp_last_error(agp_ctx* ctx);
 
 /* ---- Layout: leading dimensions, padding, alignment (every entry point; pinned by tests/test_gpu_abi_layout.py) -----------
- *   - A leading dimension (ldx, ldy, ldo, lda, ldi, ldb, ldz, ldc, lds, ldza) counts ELEMENTS of T, not bytes, and must be at
+ *   - A leading dimension (ldx, ldy, ldo, lda, ldi, ldb, ldz, ldc, lds, ldza, ldf) counts ELEMENTS of T, not bytes, and must be at
  *     least the width of a row of its matrix: element (r, c) is base[r * ld + c], 0 <= c < width.  A smaller one is refused
  *     with AGP_ERR_INVALID before any buffer of the caller is read or written; the context / handle stays usable.
  *   - The ld - width elements behind every row, and everything in front of the first and behind the last element of a vector or
@@ -309,6 +309,37 @@ agp_status agp_nearest_center(agp_ctx* ctx, int32_t dtype, const void* x, int64_
 agp_status agp_kmeans(agp_ctx* ctx, int32_t dtype, const void* x, int64_t n, int64_t ldx, int64_t D, void* centers,
                       int64_t ldc, int64_t m, int32_t max_iter, double tol, int32_t* labels_out, int32_t* counts_out,
                       int32_t* iters_host, double* objective_host, int32_t* converged_host);
+/* ---- kernel-aware selection: greedy conditional variance ------------------------------------------------------------------
+ * `inducingpoints(ConditionalVariance(m, kernel), X)`.  k-means above clusters in raw input space and never sees the kernel; this
+ * selection does.  It is the greedy MAP of a k-DPP (Chen, Zhang, Zhou, NeurIPS 2018) and the greedy conditional-variance selection
+ * of Burt, Rasmussen, van der Wilk (JMLR 2020): a pivoted partial Cholesky factorisation of K_NN, which greedily reduces
+ * tr(K_NN - K_NZ K_ZZ^-1 K_ZN), the trace term of the SVGP ELBO.
+ *
+ *   d_i = k(x_i, x_i) = variance.  For j = 0 .. m-1:
+ *     p_j = argmax_i d_i                                     ties go to the SMALLER index, so p_0 = 0
+ *     stop if d_{p_j} <= tol * variance                      (then n_selected = j)
+ *     l_j = (k(X, x_{p_j}) - sum_{k<j} l_k * l_k[p_j]) / sqrt(d_{p_j}) ;  d <- d - l_j^2 ;  d_{p_j} <- 0: a chosen point has no
+ *     residual left and is never chosen again.
+ *
+ * Float64 arithmetic throughout; x may be AGP_F32 (dtype) and is widened on load.  Kernel values are those of agp_kernelmatrix's
+ * base function on the squared distance sum_d (s_d (x_d - z_d))^2, summed in ascending d.  All four kernels, a scale or ARD scales,
+ * D <= 128.  The result is a function of the inputs alone (fixed summation orders, no atomics): two calls agree bit for bit, and
+ * the first m' indices of a call with m > m' are those of a call with m'.
+ *
+ * x: n x D (ldx), device.  Outputs, all device except n_selected_host:
+ *   idx_out     int64[m]             the chosen indices p_0 .. ; -1 behind n_selected
+ *   z_out       m x D (ldz), dtype   the chosen rows, bit copies of x ; zero rows behind n_selected
+ *   factor_out  nullable, n x m doubles (ldf >= m), row i = (l_0[i] .. l_{m-1}[i]) ; zero columns behind n_selected.
+ *               factor_out[idx_out, :] is the lower Cholesky factor of K_ZZ.
+ *   trace_out   nullable, double[m]  sum_i d_i after each step ; zero behind n_selected
+ *   *n_selected_host                 how many points were chosen (m unless the stop rule fired)
+ * Needs a workspace of 8 n m bytes for the factor (plus 8 n (D + 1)); AGP_ERR_NOMEM names the byte count when it cannot be had.
+ * Refused with AGP_ERR_INVALID before anything is read or written: n <= 0, m <= 0, m > n, D <= 0, D > 128, ldx < D, ldz < D,
+ * ldf < m (with factor_out), tol < 0 or NaN, a kernel descriptor with a kind outside 0..3, a variance or scale that is not positive
+ * and finite, or ard without ard_scales_host.  Synchronises once, at the end; the Layout rules above hold. */
+agp_status agp_greedy_variance(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                               int64_t D, int64_t m, double tol, int64_t* idx_out, void* z_out, int64_t ldz,
+                               void* factor_out, int64_t ldf, double* trace_out, int64_t* n_selected_host);
 /* MFMA microbenchmark: TFLOP/s of back-to-back v_mfma_{f64,f32}_16x16x4 (roofline ceiling measurement) */
 agp_status agp_mfma_peak(agp_ctx* ctx, int32_t dtype, double* tflops_host);
 
