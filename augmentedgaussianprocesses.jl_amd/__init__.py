@@ -35,6 +35,7 @@ from .svgp import (  # noqa: F401
     Descent,
     Momentum,
     ELBO,
+    elbo_streamed,
     MOSVGP,
     SVGP,
     AnalyticSVI,

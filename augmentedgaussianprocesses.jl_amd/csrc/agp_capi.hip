@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "agp_cavi.h"
+#include "agp_elbo_stream.h"
 #include "agp_comm.h"
 #include "agp_hyper.h"
 #include "agp_kmeans.h"
@@ -84,6 +85,15 @@ struct SvgpBase {
   virtual agp_status elbo(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho,
                           int fresh, double* out) = 0;
   virtual agp_status elbo_terms(double* out3) = 0;
+  // streamed full-data ELBO ("STREAMED ELBO"): sparse AnalyticVI / AnalyticSVI handles evaluate (Svgp<T>); every other class
+  // refuses by name before anything is launched
+  agp_status elbo_stream_refused(const char* why) {
+    ctx->err = std::string("agp_svgp_elbo_stream: ") + why;
+    return AGP_ERR_UNSUPPORTED;
+  }
+  virtual agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) {
+    return elbo_stream_refused("this handle class has no streamed ELBO (sparse AnalyticVI / AnalyticSVI handles only)");
+  }
   virtual agp_status elbo_enqueue(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho, int fresh,
                                   int32_t* ticket) = 0;
   virtual agp_status elbo_fetch(int32_t ticket, int wait, double* out, int32_t* ready) = 0;
@@ -964,6 +974,10 @@ struct Svgp : SvgpBase {
     if (lam_part) dfree(lam_part);
     if (noise_adam) dfree(noise_adam);
     if (frob_part) dfree(frob_part);
+    if (es_mu) dfree(es_mu);
+    if (es_var) dfree(es_var);
+    if (es_part) dfree(es_part);
+    if (es_scal) dfree(es_scal);
     if (logdetK_dev) dfree(logdetK_dev);
   }
 
@@ -3017,6 +3031,33 @@ struct Svgp : SvgpBase {
     return AGP_OK;
   }
 
+  // The Gaussian KL of one latent (KLdivergences.jl:11-18), the part of the ELBO that does not depend on the data -- shared by
+  // elbo() and elbo_stream().  enqueue: log-diagonal sum of chol(-2 eta2), tr(K^-1 Sigma), |L^-1 (mu - mu0)|^2 into
+  // scal_dev[2..4]; finish: once the caller has read scal_dev[0..4] into h behind a synchronisation, add the latent's KL to *kl.
+  agp_status gauss_kl_enqueue(Latent& g, bool use_stale) {
+    AGPCHK(materialize(g));
+    hipLaunchKernelGGL((k_logdiag_sum<T>), dim3(1), dim3(1024), 0, st(), (const T*)g.DgA, m, scal_dev + 2);
+    AGPCHK(frob_dot((const T*)(use_stale ? g.sKinv : g.Kinv), (const T*)g.Sigma, mp, m, scal_dev + 3));
+    hipLaunchKernelGGL((k_axpby<T>), grid1(mp), dim3(256), 0, st(), mp, T(1), (const T*)g.mu, T(-1), (const T*)g.mu0,
+                       tmpv);
+    hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)(use_stale ? g.sXk : g.Xk), mp, mp,
+                       (const T*)tmpv, pw0);
+    hipLaunchKernelGGL((k_sumsq<T>), dim3(1), dim3(1024), 0, st(), (const T*)pw0, mp, scal_dev + 4);
+    LAUNCHCHK(ctx);
+    return AGP_OK;
+  }
+  agp_status gauss_kl_finish(Latent& g, bool use_stale, const double* h, double* kl) {
+    AGPCHK(resolve_logdet(g));
+    const double logdetK = 2.0 * (use_stale ? g.s_half_logdetK : g.half_logdetK), logdetS = -2.0 * h[2];
+    *kl += 0.5 * (logdetK - logdetS + h[3] + h[4] - (double)m);
+    if (g.on) {
+      double ek = 0.0;
+      AGPCHK(extra_kl(g, &ek));
+      *kl += ek;
+    }
+    return AGP_OK;
+  }
+
   agp_status elbo(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho, int fresh,
                   double* out) override {
     AGPCHK(check_batch(B));
@@ -3099,18 +3140,10 @@ struct Svgp : SvgpBase {
     double kl_gauss = 0.0;
     for (int l = 0; l < nl; ++l) {
       Latent& g = lat[l];
-      AGPCHK(materialize(g));
-      hipLaunchKernelGGL((k_logdiag_sum<T>), dim3(1), dim3(1024), 0, st(), (const T*)g.DgA, m, scal_dev + 2);
       // objective(model, state, y) reads the state's kernel matrices -- the frozen ones under AGP_FLAG_STALE_K; the external
       // ELBO(model, X, y) recomputes them (ELBO.jl:32-47)
       const bool use_stale = g.stale_on && !fresh;
-      AGPCHK(frob_dot((const T*)(use_stale ? g.sKinv : g.Kinv), (const T*)g.Sigma, mp, m, scal_dev + 3));
-      hipLaunchKernelGGL((k_axpby<T>), grid1(mp), dim3(256), 0, st(), mp, T(1), (const T*)g.mu, T(-1), (const T*)g.mu0,
-                         tmpv);
-      hipLaunchKernelGGL((k_trmv_lower<T>), grid1(mp * 64), dim3(256), 0, st(), (const T*)(use_stale ? g.sXk : g.Xk), mp, mp,
-                         (const T*)tmpv, pw0);
-      hipLaunchKernelGGL((k_sumsq<T>), dim3(1), dim3(1024), 0, st(), (const T*)pw0, mp, scal_dev + 4);
-      LAUNCHCHK(ctx);
+      AGPCHK(gauss_kl_enqueue(g, use_stale));
       if (elbo_async >= 0 && nl == 1 && !mo && !g.on && !use_stale && logdetK_dev) {
         // agp_svgp_elbo_enqueue: the scalar is put together on the device and lands in mapped host memory behind an event
         hipLaunchKernelGGL(k_elbo_combine, dim3(1), dim3(1), 0, st(), (const double*)scal_dev, (const double*)logdetK_dev, (double)m,
@@ -3128,14 +3161,7 @@ struct Svgp : SvgpBase {
         e_data = mo ? mo_e : h[0];
         kl_aug = mo ? mo_kl : h[1];
       }
-      AGPCHK(resolve_logdet(g));
-      const double logdetK = 2.0 * (use_stale ? g.s_half_logdetK : g.half_logdetK), logdetS = -2.0 * h[2];
-      kl_gauss += 0.5 * (logdetK - logdetS + h[3] + h[4] - (double)m);
-      if (g.on) {
-        double ek = 0.0;
-        AGPCHK(extra_kl(g, &ek));
-        kl_gauss += ek;
-      }
+      AGPCHK(gauss_kl_finish(g, use_stale, h, &kl_gauss));
     }
     // sharded multi-output: the (replicated) data terms are counted by the rank that owns latent 0, the Gaussian KLs by their
     // owners; the driver sums the scalars over ranks
@@ -3246,6 +3272,146 @@ struct Svgp : SvgpBase {
     out3[0] = e_data;
     out3[1] = kl_gauss_last;
     out3[2] = kl_aug;
+    return AGP_OK;
+  }
+
+  // ---- streamed full-data ELBO (include/agp_hip.h, "STREAMED ELBO") ---------------------------------------
+  // ELBO(model, X, y) of ELBO.jl:28-47 over any number of points: the predictor's chunk loop (predict_f_latent) leaves the
+  // moments of 4096 points in es_mu / es_var, k_elbo_stream_terms forms the fresh local variables in registers and writes one pair
+  // of partial sums per workgroup, k_elbo_stream_reduce adds all of them in a fixed order.  Touches the predictor's workspace and
+  // caches (Kstar, ppm, ppv, apred / Apred, Tw2) and buffers of its own -- never the step's batch buffers, local variables, kappa
+  // caches, look-ahead, status words or the terms of the last agp_svgp_elbo.
+  T *es_mu = nullptr, *es_var = nullptr;  // [nl][4096]
+  double* es_part = nullptr;              // [ceil(n / 256)][2]
+  int64_t es_part_cap = 0;                // (in workgroups)
+  double* es_scal = nullptr;              // out[4] of k_elbo_stream_reduce | the two failure words
+  agp_status elbo_stream_check_handle() {
+    if (lp.kind == AGP_LIK_POISSON || lp.kind == AGP_LIK_HETEROSCEDASTIC)
+      return elbo_stream_refused(lp.kind == AGP_LIK_POISSON
+                                     ? "Poisson is not supported (lambda is re-estimated from sums over the whole batch: a second pass)"
+                                     : "Heteroscedastic is not supported (lambda is re-estimated from sums over the whole batch: a "
+                                       "second pass)");
+    if (lp.kind == AGP_LIK_GAUSSIAN && lp.noise_dev)
+      return elbo_stream_refused("Gaussian with opt_noise is not supported (its fresh ELBO steps the noise from sums over the batch)");
+    if (desc.lik.kind == AGP_LIK_MULTIOUTPUT || mo)
+      return elbo_stream_refused("multi-output handles (AGP_LIK_MULTIOUTPUT) are not supported");
+    for (auto& g : lat)
+      if (g.on) return elbo_stream_refused("online handles (streaming prior) are not supported");
+    if (stale_mode()) return elbo_stream_refused("AGP_FLAG_STALE_K handles are not supported");
+    if (desc.latent_offset != 0 || mo_sharded || (lp.kind == AGP_LIK_LOGISTICSOFTMAX && desc.n_latent != desc.lik.n_class))
+      return elbo_stream_refused("latent-sharded handles are not supported (the local update needs every latent on one handle)");
+    if (bs_world > 1) return elbo_stream_refused("batch-sharded handles are not supported");
+    return AGP_OK;
+  }
+  agp_status elbo_stream(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t n, double rho, double* out,
+                         double* terms) override {
+    AGPCHK(elbo_stream_check_handle());
+    if (n <= 0) {
+      ctx->err = "agp_svgp_elbo_stream: the number of points " + std::to_string(n) + " is incorrect (it must be positive)";
+      return AGP_ERR_BAD_BATCH;
+    }
+    if (!x || !y || !out || ldx < D || !(rho > 0.0)) {
+      ctx->err = "agp_svgp_elbo_stream: x, y and elbo_host must not be NULL, ldx >= D, rho > 0";
+      return AGP_ERR_INVALID;
+    }
+    const int64_t CH = 4096;
+    const int64_t nw = (n + ELBO_STREAM_THREADS - 1) / ELBO_STREAM_THREADS;
+    for (auto& g : lat) AGPCHK(params_to_host(g));  // k_predict_finish takes the variance by value
+    AGPCHK(ensure_pred_ws(0, true));
+    if (!es_mu) {
+      AGPCHK(dmalloc(ctx, &es_mu, (int64_t)nl * CH));
+      AGPCHK(dmalloc(ctx, &es_var, (int64_t)nl * CH));
+      AGPCHK(dmalloc(ctx, &es_scal, 8));
+    }
+    if (nw > es_part_cap) {
+      if (es_part) dfree(es_part);
+      es_part = nullptr;
+      es_part_cap = 0;
+      AGPCHK(dmalloc(ctx, &es_part, 2 * nw));
+      es_part_cap = nw;
+    }
+    for (auto& g : lat) {
+      AGPCHK(ensure_pred(g, true));
+      AGPCHK(ensure_zsc(g));
+    }
+    unsigned long long* bad = reinterpret_cast<unsigned long long*>(es_scal + 4);
+    HIPCHK(ctx, hipMemsetAsync(bad, 0xFF, 2 * sizeof(unsigned long long), st()));
+    const bool lsm = lp.kind == AGP_LIK_LOGISTICSOFTMAX;
+    for (int64_t s = 0; s < n; s += CH) {
+      const int64_t nc = (n - s) < CH ? (n - s) : CH;
+      const int64_t nq = rup64(nc);
+      // the gather goes through the kernel-matrix kernel: with idx the chunk is idx[s .. s + nc) into the whole x
+      const T* xs = idx ? (const T*)x : (const T*)x + s * ldx;
+      const int64_t* is = idx ? idx + s : nullptr;
+      for (int l = 0; l < nl; ++l) {
+        Latent& g = lat[l];
+        const int slices = launch_kernelmatrix<T>(ctx, st(), xs, ldx, is, nc, (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind,
+                                                  kvar(g), Kstar, mp, nq, mp, 0, T(0), (const T*)g.apred, ppm, CH, 0,
+                                                  (const T*)g.Zsc, (const T*)g.zn);
+        LAUNCHCHK(ctx);
+        AGPCHK((gemm_nt<T, EPI_ROWDOT>(ctx, Kstar, mp, g.Apred, mp, nq, mp, mp, 0, nullptr, 0, Kstar, mp, nullptr, ppv, nullptr,
+                                       CH)));
+        hipLaunchKernelGGL((k_predict_finish<T>), grid1(nc), dim3(256), 0, st(), nc, slices, (const T*)ppm, (int)(2 * mp / TILE),
+                           (const T*)ppv, CH, (T)g.k.variance, (T)jitter, es_mu + (int64_t)l * CH, es_var + (int64_t)l * CH);
+        LAUNCHCHK(ctx);
+      }
+      const unsigned gw = (unsigned)((nc + ELBO_STREAM_THREADS - 1) / ELBO_STREAM_THREADS);
+      double* part = es_part + 2 * (s / ELBO_STREAM_THREADS);
+#define AGP_ELBO_STREAM_CASE(K)                                                                                                  \
+  case K:                                                                                                                        \
+    hipLaunchKernelGGL((k_elbo_stream_terms<T, K>), dim3(gw), dim3(ELBO_STREAM_THREADS), 0, st(), nc, s, nl, CH, lp,              \
+                       (int)desc.elbo_mode, (const T*)y, (const int32_t*)y, idx, (const T*)es_mu, (const T*)es_var,              \
+                       (int)desc.lik.n_class, part, bad);                                                                       \
+    break;
+      switch (lp.kind) {
+        AGP_ELBO_STREAM_CASE(LIK_GAUSSIAN)
+        AGP_ELBO_STREAM_CASE(LIK_LOGISTIC)
+        AGP_ELBO_STREAM_CASE(LIK_STUDENTT)
+        AGP_ELBO_STREAM_CASE(LIK_LSM)
+        AGP_ELBO_STREAM_CASE(LIK_LAPLACE)
+        AGP_ELBO_STREAM_CASE(LIK_BSVM)
+        AGP_ELBO_STREAM_CASE(LIK_NEGBIN)
+        default:
+          return elbo_stream_refused("unknown likelihood kind");
+      }
+#undef AGP_ELBO_STREAM_CASE
+      LAUNCHCHK(ctx);
+    }
+    // LogisticSoftMax sum(log, first(beta)) (logisticsoftmax.jl:138): once per evaluation; beta = n_class for fresh local variables
+    const double once_add = lsm ? std::log((double)(T)desc.lik.n_class) : 0.0;
+    hipLaunchKernelGGL(k_elbo_stream_reduce, dim3(1), dim3(1024), 0, st(), (const double*)es_part, nw, once_add,
+                       (const unsigned long long*)bad, es_scal);
+    LAUNCHCHK(ctx);
+    // Gaussian KL per latent; the data terms and the failure words come back with the first latent's scalars (one
+    // synchronisation per latent: one for every likelihood but LogisticSoftMax)
+    double hs[4] = {0.0, 0.0, -1.0, -1.0}, kl_gauss = 0.0;
+    for (int l = 0; l < nl; ++l) {
+      Latent& g = lat[l];
+      AGPCHK(gauss_kl_enqueue(g, false));
+      double h[5];
+      HIPCHK(ctx, hipMemcpyAsync(h, scal_dev, sizeof(double) * 5, hipMemcpyDeviceToHost, st()));
+      if (l == 0) HIPCHK(ctx, hipMemcpyAsync(hs, es_scal, sizeof(double) * 4, hipMemcpyDeviceToHost, st()));
+      HIPCHK(ctx, hipStreamSynchronize(st()));
+      if (l == 0) {
+        if (hs[2] >= 0.0) {
+          ctx->err = "agp_svgp_elbo_stream: var_f is not positive (or a moment is not finite) at point " +
+                     std::to_string((int64_t)hs[2]) + " of the stream (K~ has negative values)";
+          return AGP_ERR_NEG_KTILDE;
+        }
+        if (hs[3] >= 0.0) {
+          ctx->err = "agp_svgp_elbo_stream: class index outside the likelihood's classes at point " +
+                     std::to_string((int64_t)hs[3]) + " of the stream";
+          return AGP_ERR_LABELS;
+        }
+      }
+      AGPCHK(gauss_kl_finish(g, false, h, &kl_gauss));
+    }
+    *out = rho * hs[0] - kl_gauss - rho * hs[1];
+    if (terms) {
+      terms[0] = hs[0];
+      terms[1] = kl_gauss;
+      terms[2] = hs[1];
+    }
     return AGP_OK;
   }
 
@@ -4058,6 +4224,9 @@ struct Svgp : SvgpBase {
 // ---- full model (AGP_FLAG_FULL: VGP, kappa = I, m = N, Z = the training inputs) -------------------------------------------
 // VGP(X, y, kernel, likelihood, AnalyticVI())  src/models/VGP.jl:36-85, Float64 only: the SVGP handle without K_nm, kappa, K~
 struct Vgp : Svgp<double> {
+  agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) override {
+    return elbo_stream_refused("full models (AGP_FLAG_FULL, VGP) are not supported: the streamed ELBO is the sparse model's");
+  }
   using T = double;
   T* vgp_part = nullptr;  // [part_sets()][2][ns][mp] partial column sums of k_vgp_colstats (colstats_part)
   virtual int part_sets() const { return 1; }  // one set serves every latent in turn (Vgp, Gp); one per latent in Movgp
@@ -4255,6 +4424,9 @@ struct Vgp : Svgp<double> {
 // mean_f[q] = mu_q, var_f[q] = diag Sigma_q.  ELBO, predictions, hyper step (only the Gaussian KL depends on a latent's kernel),
 // state export: the inherited ones, which reach this class through step_local / posterior_f / hypergrad.
 struct Movgp : Vgp {
+  agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) override {
+    return elbo_stream_refused("multi-output full models (AGP_FLAG_FULL with AGP_LIK_MULTIOUTPUT, MOVGP) are not supported");
+  }
   agp_status check_desc() override {
     AGPCHK(Svgp<T>::check_desc());
     return check_full();
@@ -4290,6 +4462,9 @@ struct Movgp : Vgp {
 // whose image v = L^-1 r lands in g.v; alpha = Sigma^-1 r goes to g.mu, diag Sigma^-1 to gp_dinv, log p to gp_out[4], and the
 // sigma2 the factor used to gp_s2.  Sigma^-1 (g.Apred) and Sigma (g.Sigma) are formed on demand, once per factor.
 struct Gp : Vgp {
+  agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) override {
+    return elbo_stream_refused("exact GP regression (AGP_FLAG_EXACT, GP) is not supported");
+  }
   bool gp_have_r = false;       // g.eta1 holds r (from the first step)
   bool gp_valid = false;        // the factor, alpha and log p belong to the current K
   bool gp_s2_fresh = false;     // ... and to the current sigma2 (no noise step since)
@@ -4525,6 +4700,9 @@ struct Gp : Vgp {
 // k_vgp_local writes them; k_vgp_eta forms eta1 and -2 eta2 = inv(K) + 2 Diagonal(grad_E_Sigma); Vgp::vgp_factor leaves Xa = L^-1 and
 // v = Xa eta1; k_gibbs_f / k_gibbs_fsum draw f = Xa' (v + z) ~ N(Sigma eta1, Sigma).  Nothing between sweeps waits for the host.
 struct Mcgp : Vgp {
+  agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) override {
+    return elbo_stream_refused("Gibbs-sampled models (AGP_FLAG_SAMPLED, MCGP) are not supported");
+  }
   int64_t gibbs_t = 0;    // sweeps taken so far: the counter word of the next sweep's draws
   bool swept = false;     // Xa belongs to a sweep (else Sigma = I, latentgp.jl:81-86)
   T *mc_Fs = nullptr, *mc_G = nullptr, *mc_Fstar = nullptr;  // prediction: padded samples, F K^-1, F* of one block of test points
@@ -4769,6 +4947,9 @@ static agp_status mc_fill_normals(agp_ctx* ctx, hipStream_t s, uint64_t seed, in
 }
 
 struct Nvgp : Vgp {
+  agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) override {
+    return elbo_stream_refused("numerical inference on the full model (AGP_FLAG_NUMERICAL / AGP_FLAG_MC with AGP_FLAG_FULL) is not supported");
+  }
   agp_status pathwise_draw(int, int, uint64_t, int64_t, agp_pathwise**) override {
     return pathwise_refused("numerical inference (AGP_FLAG_NUMERICAL, with or without AGP_FLAG_MC) is not supported yet -- a "
                             "follow-up: the factor of Sigma is already kept on such a handle");
@@ -5253,6 +5434,9 @@ struct Nvgp : Vgp {
 // are kept per latent from the moments to the update; the kernel matrices are recomputed every step: nothing is cached between steps
 // and there is no look-ahead.
 struct Nsvgp : Nvgp {
+  agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) override {
+    return elbo_stream_refused("numerical inference on the sparse model (AGP_FLAG_NUMERICAL / AGP_FLAG_MC) is not supported");
+  }
   T *ns_Knm = nullptr, *ns_kap = nullptr, *ns_S2 = nullptr, *ns_u = nullptr;
   std::vector<T*> ns_kapt, ns_Wt;  // per latent
   T* ns_P2 = nullptr;  // the data term of the gradient of eta2, m x m (a buffer of its own: F holds the kept factor)
@@ -6292,6 +6476,11 @@ agp_status agp_svgp_elbo(agp_svgp* h, const void* x, int64_t ldx, const void* y,
   HCHKF(h);
   if (!elbo_host) return AGP_ERR_INVALID;
   return h->impl->elbo(x, ldx, y, idx, B, rho, fresh_local, elbo_host);
+}
+agp_status agp_svgp_elbo_stream(agp_svgp* h, const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t n,
+                                double rho, double* elbo_host, double* terms_host) {
+  HCHKF(h);
+  return h->impl->elbo_stream(x, ldx, y, idx, n, rho, elbo_host, terms_host);
 }
 agp_status agp_svgp_get_state(agp_svgp* h, int32_t latent, void* mu, void* sigma, void* eta1, void* eta2) {
   HCHKF(h);

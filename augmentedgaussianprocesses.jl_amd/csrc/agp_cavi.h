@@ -1362,6 +1362,88 @@ __global__ void k_copy2d(const T* __restrict__ src, int64_t lds, int64_t rs, int
 // LogisticSoftMax: sums over the nl local latents; the GammaEntropy term and nothing else is global and is added
 // only when add_global != 0 (latent_offset == 0 rank).  elbo_ref != 0 reproduces logistic.jl:82 (dot(theta, mu)).
 // ---------------------------------------------------------------------------------------------------
+// The per-point expressions of both data terms, shared by k_elbo_terms (local variables from the step's buffers) and
+// k_elbo_stream_terms (agp_elbo_stream.h: local variables formed in registers).  Everything in double; e / kl are the caller's
+// running sums.
+struct ElboConsts {
+  double k0 = 0.0, k1 = 0.0, k2 = 0.0, k3 = 0.0;
+};
+// per-launch constants (lgamma / digamma of the Student-t shape parameters, logs of fixed parameters); sig2 = the Gaussian noise
+// in force, lamv = lambda of Poisson / Heteroscedastic
+template <typename T, int KIND>
+__device__ __forceinline__ ElboConsts elbo_consts(const LikParams<T>& lp, double sig2, double lamv) {
+  ElboConsts kc;
+  if constexpr (KIND == LIK_STUDENTT) {
+    const double nu = (double)lp.p0, sig = (double)lp.p1;
+    const double al = 0.5 * (nu + 1.0), alp = 0.5 * nu, bp = alp * sig * sig;
+    kc.k0 = -0.5 * log(2.0 * 3.14159265358979323846 * sig * sig);
+    kc.k1 = digamma_d(al);
+    kc.k2 = (al - alp) * kc.k1 - lgamma(al) + lgamma(alp);
+    kc.k3 = log(bp);
+  } else if constexpr (KIND == LIK_GAUSSIAN) {
+    kc.k0 = sig2;
+    kc.k1 = log(kc.k0);
+  } else if constexpr (KIND == LIK_NEGBIN) {
+    kc.k0 = lgamma((double)lp.p0);
+  } else if constexpr (KIND == LIK_POISSON || KIND == LIK_HETERO) {
+    kc.k0 = log(lamv);
+  }
+  return kc;
+}
+// one point of a single-latent likelihood whose local variables are (theta, c): Gaussian, Logistic, Laplace, BayesianSVM,
+// NegBinomial, Student-t.  first_once: this is point 0 of the evaluation and the once-per-evaluation terms are this caller's
+template <typename T, int KIND>
+__device__ __forceinline__ void elbo_point_terms(const LikParams<T>& lp, int elbo_ref, const ElboConsts& kc, bool first_once,
+                                                 double yi, double mu, double s, double th, double cc, double& e, double& kl) {
+  constexpr double LOG2 = 0.69314718055994530942, LOG2PI = 1.83787706640934548356, LOGPI = 1.14472988584940017414;
+  if constexpr (KIND == LIK_GAUSSIAN) {
+    e += -0.5 * (LOG2PI + kc.k1 + ((yi - mu) * (yi - mu) + s) / kc.k0);
+  } else if constexpr (KIND == LIK_LOGISTIC) {
+    double quad = elbo_ref ? th * mu : th * mu * mu;
+    e += -0.5 * LOG2 + 0.5 * (mu * yi - th * s - quad);
+    kl += logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;
+  } else if constexpr (KIND == LIK_LAPLACE) {
+    // laplace.jl:93-123 ; GIGEntropy (KLdivergences.jl:105-113) at p = 1/2 in closed form:
+    //   log(2 K_1/2(s)) = log2 + (log(pi/2) - log s)/2 - s ;  s (K_3/2 + K_-1/2) / (2 K_1/2) = s + 1/2
+    // elbo_ref keeps the reference's scalar-iteration quirks: log(a) counted once, log(2 K_p) of the first point only
+    double be = (double)lp.p0, a = 1.0 / (be * be);
+    double b = cc, sab = sqrt(a) * b;
+    e += -0.5 * LOG2PI + 0.5 * log(th) - 0.5 * th * (s + mu * mu - 2.0 * mu * yi + yi * yi);
+    double l2k = LOG2 + 0.5 * (LOGPI - LOG2 - log(sab)) - sab;
+    double ent = -0.5 * log(b * b) + sab + 0.5;
+    if (elbo_ref) ent += first_once ? 0.5 * log(a) + l2k : 0.0;
+    else ent += 0.5 * log(a) + l2k;
+    double expo = -log(2.0 * be * be) - 0.5 * (a * b + b * b * sqrt(a)) / (a * b * b * be * be);
+    kl += ent - expo;
+  } else if constexpr (KIND == LIK_BSVM) {  // bayesiansvm.jl:71-92 ; elbo_ref: + theta (1 - y mu)^2 as written in line 81
+    double d = 1.0 - yi * mu, sc = sqrt(cc);
+    e += -0.5 * LOG2 + mu * yi - 0.5 * th * s + (elbo_ref ? th * d * d : -0.5 * th * d * d);
+    kl += 0.5 * log(cc) + (LOG2 + 0.5 * (LOGPI - LOG2 - log(sc)) - sc) - 0.5 * sc;
+  } else if constexpr (KIND == LIK_NEGBIN) {  // negativebinomial.jl:103-131 ; elbo_ref: dot(theta, mu) as written in line 125
+    double rr = (double)lp.p0;
+    e += lgamma_pos_d(yi + rr) - lgamma_pos_d(yi + 1.0) - kc.k0 - LOG2 * (yi + rr);
+    e += 0.5 * mu * (yi - rr) - 0.5 * (elbo_ref ? th * mu : th * mu * mu) - 0.5 * th * s;
+    kl += (yi + rr) * logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;
+  } else {  // Student-t, studentt.jl:103-127
+    static_assert(KIND == LIK_STUDENTT, "elbo_point_terms: not a (theta, c) likelihood");
+    const double nu = (double)lp.p0, sig = (double)lp.p1;
+    const double al = 0.5 * (nu + 1.0), alp = 0.5 * nu, bp = alp * sig * sig;
+    const double lc = log(cc);
+    e += kc.k0 - (lc - kc.k1) - 0.5 * (th * s + th * mu * mu - 2.0 * th * mu * yi + th * yi * yi);
+    kl += kc.k2 + alp * (lc - kc.k3) + al * (bp - cc) / cc;
+  }
+}
+// LogisticSoftMax, one latent of one point (lam0 = alpha / beta, psil = psi(alpha) - log beta of the point) ...
+__device__ __forceinline__ void elbo_lsm_latent(double yk, double g, double th, double mu, double s, double cc, double lam0,
+                                                double psil, double& e, double& kl) {
+  constexpr double LOG2 = 0.69314718055994530942;
+  e += -LOG2 - (g + yk) * LOG2 + 0.5 * (mu * (yk - g) - th * mu * mu - th * s);
+  kl += (yk + g) * logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;          // PolyaGammaKL
+  kl += lam0 - g + (g > 0.0 ? g * log(g) : 0.0) - g * psil;           // PoissonKL
+}
+// ... and the point's share of the GammaEntropy (sum parts; log(beta[0]) is counted once per evaluation by the caller)
+__device__ __forceinline__ void elbo_lsm_entropy(double a, double psi, double& kl) { kl += -a - lgamma_pos_d(a) - (1.0 - a) * psi; }
+
 // Round 5: one instantiation per likelihood (KIND) -- the single kernel with every likelihood's branch in its loop body compiled to
 // 636 bytes of scratch per lane (lgamma + digamma + nine branches under a 1024-thread register budget); per-launch constants
 // (lgamma / digamma of the Student-t shape parameters, logs of fixed parameters) are hoisted out of the loop over the points.
@@ -1376,25 +1458,12 @@ k_elbo_terms(int64_t B, int nl, int64_t ldb, LikParams<T> lp, int elbo_ref, int 
   // (not sums over points) must enter the all-reduced ELBO a single time
   __shared__ double red[16];
   double e = 0.0, kl = 0.0;
-  constexpr double LOG2 = 0.69314718055994530942, LOG2PI = 1.83787706640934548356, LOGPI = 1.14472988584940017414;
+  constexpr double LOG2 = 0.69314718055994530942;
   const double lamv = (KIND == LIK_POISSON || KIND == LIK_HETERO) ? (double)lam[0] : 1.0;
-  // per-launch constants
-  double k0 = 0.0, k1 = 0.0, k2 = 0.0, k3 = 0.0;
-  if constexpr (KIND == LIK_STUDENTT) {
-    const double nu = (double)lp.p0, sig = (double)lp.p1;
-    const double al = 0.5 * (nu + 1.0), alp = 0.5 * nu, bp = alp * sig * sig;
-    k0 = -0.5 * log(2.0 * 3.14159265358979323846 * sig * sig);
-    k1 = digamma_d(al);
-    k2 = (al - alp) * k1 - lgamma(al) + lgamma(alp);
-    k3 = log(bp);
-  } else if constexpr (KIND == LIK_GAUSSIAN) {
-    k0 = lp.noise_dev ? (double)lam[0] : (double)lp.p0;
-    k1 = log(k0);
-  } else if constexpr (KIND == LIK_NEGBIN) {
-    k0 = lgamma((double)lp.p0);
-  } else if constexpr (KIND == LIK_POISSON || KIND == LIK_HETERO) {
-    k0 = log(lamv);
-  }
+  double sig2 = 0.0;
+  if constexpr (KIND == LIK_GAUSSIAN) sig2 = lp.noise_dev ? (double)lam[0] : (double)lp.p0;
+  const ElboConsts kc = elbo_consts<T, KIND>(lp, sig2, lamv);
+  const double k0 = kc.k0;
   for (int64_t i = threadIdx.x; i < B; i += blockDim.x) {
     if constexpr (KIND == LIK_LSM) {
       int cls = ycls[idx ? idx[i] : i];
@@ -1405,11 +1474,9 @@ k_elbo_terms(int64_t B, int nl, int64_t ldb, LikParams<T> lp, int elbo_ref, int 
         double yk = (cls == latent_offset + k) ? 1.0 : 0.0;
         double g = (double)gamma[k * ldb + i], th = (double)theta[k * ldb + i];
         double mu = (double)muf[k * ldb + i], s = (double)varf[k * ldb + i], cc = (double)c[k * ldb + i];
-        e += -LOG2 - (g + yk) * LOG2 + 0.5 * (mu * (yk - g) - th * mu * mu - th * s);
-        kl += (yk + g) * logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;          // PolyaGammaKL
-        kl += lam0 - g + (g > 0.0 ? g * log(g) : 0.0) - g * psil;           // PoissonKL
+        elbo_lsm_latent(yk, g, th, mu, s, cc, lam0, psil, e, kl);
       }
-      if (add_global) kl += -a - lgamma_pos_d(a) - (1.0 - a) * psi;               // GammaEntropy (sum parts)
+      if (add_global) elbo_lsm_entropy(a, psi, kl);
     } else if constexpr (KIND == LIK_HETERO) {  // heteroscedastic.jl:142-179 ; layout as in k_hetero_local
       double yi = (double)y[(idx ? idx[i] : i) * ystr];
       double m0 = (double)muf[i], s0 = (double)varf[i], m1 = (double)muf[ldb + i], s1 = (double)varf[ldb + i];
@@ -1419,52 +1486,22 @@ k_elbo_terms(int64_t B, int nl, int64_t ldb, LikParams<T> lp, int elbo_ref, int 
       e += 0.5 * (m1 * (0.5 - g) - m1 * m1 * th - s1 * th);
       e -= lam0 - g + (g > 0.0 ? g * log(g) : 0.0) - g * log(lam0);  // PoissonKL(gamma, lam0, log lam0)
       kl += (0.5 + g) * logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;
+    } else if constexpr (KIND == LIK_POISSON) {  // poisson.jl:106-132
+      double yi = (double)y[(idx ? idx[i] : i) * ystr];
+      double mu = (double)muf[i], s = (double)varf[i];
+      double th = (double)theta[i], cc = (double)c[i], g = (double)gamma[i];
+      e += 0.5 * (mu * (yi - g) - th * mu * mu - th * s) + yi * k0 - lgamma_pos_d(yi + 1.0) - LOG2 * (yi + g);
+      kl += lamv - (1.0 + k0) * g + (g > 0.0 ? g * log(g) : 0.0);             // PoissonKL(gamma, lambda)
+      kl += (yi + g) * logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;              // PolyaGammaKL(y + gamma, c, theta)
     } else {
       double yi = (double)y[(idx ? idx[i] : i) * ystr];
       double mu = (double)muf[i], s = (double)varf[i];
-      if constexpr (KIND == LIK_GAUSSIAN) {
-        e += -0.5 * (LOG2PI + k1 + ((yi - mu) * (yi - mu) + s) / k0);
-      } else if constexpr (KIND == LIK_LOGISTIC) {
-        double th = (double)theta[i], cc = (double)c[i];
-        double quad = elbo_ref ? th * mu : th * mu * mu;
-        e += -0.5 * LOG2 + 0.5 * (mu * yi - th * s - quad);
-        kl += logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;
-      } else if constexpr (KIND == LIK_LAPLACE) {
-        // laplace.jl:93-123 ; GIGEntropy (KLdivergences.jl:105-113) at p = 1/2 in closed form:
-        //   log(2 K_1/2(s)) = log2 + (log(pi/2) - log s)/2 - s ;  s (K_3/2 + K_-1/2) / (2 K_1/2) = s + 1/2
-        // elbo_ref keeps the reference's scalar-iteration quirks: log(a) counted once, log(2 K_p) of the first point only
-        double be = (double)lp.p0, a = 1.0 / (be * be);
-        double th = (double)theta[i], b = (double)c[i], sab = sqrt(a) * b;
-        e += -0.5 * LOG2PI + 0.5 * log(th) - 0.5 * th * (s + mu * mu - 2.0 * mu * yi + yi * yi);
-        double l2k = LOG2 + 0.5 * (LOGPI - LOG2 - log(sab)) - sab;
-        double ent = -0.5 * log(b * b) + sab + 0.5;
-        if (elbo_ref) ent += (i == 0 && once) ? 0.5 * log(a) + l2k : 0.0;
-        else ent += 0.5 * log(a) + l2k;
-        double expo = -log(2.0 * be * be) - 0.5 * (a * b + b * b * sqrt(a)) / (a * b * b * be * be);
-        kl += ent - expo;
-      } else if constexpr (KIND == LIK_BSVM) {  // bayesiansvm.jl:71-92 ; elbo_ref: + theta (1 - y mu)^2 as written in line 81
-        double th = (double)theta[i], cc = (double)c[i], d = 1.0 - yi * mu, sc = sqrt(cc);
-        e += -0.5 * LOG2 + mu * yi - 0.5 * th * s + (elbo_ref ? th * d * d : -0.5 * th * d * d);
-        kl += 0.5 * log(cc) + (LOG2 + 0.5 * (LOGPI - LOG2 - log(sc)) - sc) - 0.5 * sc;
-      } else if constexpr (KIND == LIK_POISSON) {  // poisson.jl:106-132
-        double th = (double)theta[i], cc = (double)c[i], g = (double)gamma[i];
-        e += 0.5 * (mu * (yi - g) - th * mu * mu - th * s) + yi * k0 - lgamma_pos_d(yi + 1.0) - LOG2 * (yi + g);
-        kl += lamv - (1.0 + k0) * g + (g > 0.0 ? g * log(g) : 0.0);             // PoissonKL(gamma, lambda)
-        kl += (yi + g) * logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;              // PolyaGammaKL(y + gamma, c, theta)
-      } else if constexpr (KIND == LIK_NEGBIN) {  // negativebinomial.jl:103-131 ; elbo_ref: dot(theta, mu) as written in line 125
-        double th = (double)theta[i], cc = (double)c[i], rr = (double)lp.p0;
-        e += lgamma_pos_d(yi + rr) - lgamma_pos_d(yi + 1.0) - k0 - LOG2 * (yi + rr);
-        e += 0.5 * mu * (yi - rr) - 0.5 * (elbo_ref ? th * mu : th * mu * mu) - 0.5 * th * s;
-        kl += (yi + rr) * logcosh_d(0.5 * cc) - 0.5 * cc * cc * th;
-      } else {  // Student-t, studentt.jl:103-127
-        static_assert(KIND == LIK_STUDENTT, "k_elbo_terms: unknown likelihood");
-        const double nu = (double)lp.p0, sig = (double)lp.p1;
-        const double al = 0.5 * (nu + 1.0), alp = 0.5 * nu, bp = alp * sig * sig;
-        double th = (double)theta[i], cc = (double)c[i];
-        const double lc = log(cc);
-        e += k0 - (lc - k1) - 0.5 * (th * s + th * mu * mu - 2.0 * th * mu * yi + th * yi * yi);
-        kl += k2 + alp * (lc - k3) + al * (bp - cc) / cc;
+      double th = 0.0, cc = 0.0;
+      if constexpr (KIND != LIK_GAUSSIAN) {
+        th = (double)theta[i];
+        cc = (double)c[i];
       }
+      elbo_point_terms<T, KIND>(lp, elbo_ref, kc, i == 0 && once, yi, mu, s, th, cc, e, kl);
     }
   }
   e = block_sum<double>(e, red);

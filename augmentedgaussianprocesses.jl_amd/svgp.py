@@ -1042,11 +1042,77 @@ class SideObjective:
         return out.value
 
 
+def _streamed_refusal(model) -> Optional[str]:
+    """Why agp_svgp_elbo_stream refuses this model (include/agp_hip.h, "STREAMED ELBO"), or None: decided here, before the library
+    is called."""
+    if type(model).__name__ == "OnlineSVGP":
+        return "online models (streaming prior, OnlineSVGP) are not supported"
+    if not isinstance(model, SVGP):
+        return f"{type(model).__name__} is not a sparse variational GP"
+    flags = getattr(model, "_desc_flags", 0)
+    for bit, what in ((capi.FLAG_EXACT, "exact GP regression (GP)"), (capi.FLAG_SAMPLED, "Gibbs-sampled models (MCGP)"),
+                      (capi.FLAG_MC, "MCIntegrationVI models"), (capi.FLAG_NUMERICAL, "QuadratureVI models"),
+                      (capi.FLAG_FULL, "full models (VGP, MOVGP)")):
+        if flags & bit:
+            return f"{what} are not supported: the streamed ELBO is the sparse AnalyticVI / AnalyticSVI model's"
+    lik = model.likelihood
+    if isinstance(model, MOSVGP) or isinstance(lik, _MultiOutputLikelihood):
+        return "multi-output models (MOSVGP) are not supported"
+    if isinstance(lik, (PoissonLikelihood, HeteroscedasticLikelihood)):
+        return (f"{type(lik).__name__} is not supported: lambda is re-estimated from sums over the whole batch, which needs a "
+                "second pass")
+    if isinstance(lik, GaussianLikelihood) and lik.noise_eta:
+        return "GaussianLikelihood with opt_noise is not supported: its fresh ELBO steps the noise"
+    if model.reference_compat_stale_K:
+        return "reference_compat_stale_K models (AGP_FLAG_STALE_K) are not supported"
+    if model.latent_offset != 0 or model.n_latent != model.n_latent_total:
+        return "latent-sharded models (latent_slice) are not supported: the local update needs every latent on one handle"
+    if getattr(model, "_batch_shard", None) is not None and model._batch_shard[1] > 1:
+        return "batch-sharded models are not supported"
+    return None
+
+
+def elbo_streamed(model, X, y, *, obsdim: int = 1, rho: Optional[float] = None, idx=None, return_terms: bool = False):
+    """ELBO(model, X, y) (src/functions/ELBO.jl:28-47) over ANY number of points, streamed on the device in chunks of 4096
+    (agp_svgp_elbo_stream): fresh local variables, one local update.  The handle is not re-created and `max_batch` does not grow;
+    the workspace does not depend on the number of points.  X, y: host arrays or device tensors; idx (optional): the points to
+    evaluate, as rows of X and y.  rho=None: the ρ left by the last train! (as ELBO); rho=1 for the properly scaled full-data
+    ELBO.  return_terms=True: (elbo, (data term, Gaussian KL, augmented KL)), ELBO = ρ t0 - t1 - ρ t2."""
+    why = _streamed_refusal(model)
+    if why is not None:
+        raise NotImplementedError(f"elbo_streamed: {why}")
+    torch = _torch()
+    L = capi.lib()
+    Xd = model._upload(X, obsdim)
+    if isinstance(y, torch.Tensor):
+        want = torch.int32 if isinstance(model.likelihood, LogisticSoftMaxLikelihood) else model.tdtype
+        yd = y.to(device=model._dev(), dtype=want).contiguous()  # (a device tensor is taken as treated labels)
+    else:
+        yd = model._upload_y(model._treat(y))
+    n = Xd.shape[0]
+    idx_d = None
+    if idx is not None:
+        idx_d = torch.as_tensor(idx, dtype=torch.int64, device=model._dev()).contiguous()
+        n = int(idx_d.numel())
+    h = model._ensure_handle(max(model._max_batch, 1))
+    r = model.inference.rho if rho is None else float(rho)
+    out = C.c_double()
+    terms = (C.c_double * 3)()
+    model._chk(L.agp_svgp_elbo_stream(h, C.c_void_p(Xd.data_ptr()), Xd.stride(0), C.c_void_p(yd.data_ptr()),
+                                      C.c_void_p(idx_d.data_ptr()) if idx_d is not None else None, n, r, C.byref(out), terms))
+    if return_terms:
+        return out.value, tuple(terms)
+    return out.value
+
+
 @functools.singledispatch
-def ELBO(model: SVGP, X, y, *, obsdim: int = 1, rho: Optional[float] = None) -> float:
+def ELBO(model: SVGP, X, y, *, obsdim: int = 1, rho: Optional[float] = None, streamed: bool = False) -> float:
     """External ELBO(model, X, y) (src/functions/ELBO.jl:28-47): fresh local variables on (X, y), one local update.
     rho defaults to the reference's behaviour (the ρ left by the last train!, Appendix A Q13); pass rho=1 for the
-    properly scaled full-data ELBO.  (A VGP: ELBO(model), vgp.py.)"""
+    properly scaled full-data ELBO.  streamed=True: the same value from `elbo_streamed` -- chunks of 4096 points, no handle
+    re-created with max_batch = n, workspace independent of n.  (A VGP: ELBO(model), vgp.py.)"""
+    if streamed:
+        return elbo_streamed(model, X, y, obsdim=obsdim, rho=rho)
     L = capi.lib()
     Xd = model._upload(X, obsdim)
     yt = model._treat(y)

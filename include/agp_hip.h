@@ -511,6 +511,47 @@ agp_status agp_svgp_elbo_fetch(agp_svgp* h, int32_t ticket, int32_t wait, double
  * (expec_loglikelihood), Gaussian KL (+ extraKL), unscaled augmented KL.  A batch-parallel driver sums terms 0 and 2 over the
  * minibatch shards and counts the (replicated) Gaussian KL once. */
 agp_status agp_svgp_elbo_terms(agp_svgp* h, double* terms_host);
+
+/* ---- STREAMED ELBO (the full-data objective of an AnalyticSVI run, over any number of points) ---------------------------------
+ * External ELBO(model, X, y) (src/functions/ELBO.jl:28-47) over ANY number of points, streamed: fresh local variables,
+ * one local update, rho explicit.  No n x m object, no per-point vector of length n; workspace independent of n.
+ *
+ * Meaning.  The value is what agp_svgp_elbo(..., fresh_local = 1) returns for the same points in one batch.  terms_host (nullable,
+ * double[3]) = (unscaled data term, Gaussian KL, unscaled augmented KL), ELBO = rho * t0 - t1 - rho * t2, as agp_svgp_elbo_terms
+ * defines them.  idx is nullable; when given, the rows of x and y are read at idx[i] (device memory, n entries).  n is NOT bounded
+ * by max_batch; n = 0 is AGP_ERR_BAD_BATCH.  x NULL, y NULL, elbo_host NULL, ldx < D or rho <= 0 are AGP_ERR_INVALID.  Layout: the
+ * "Layout" section above (ldx in elements, >= D, padding never read); y as agp_svgp_cavi_step takes it (T[n], int32 class indices
+ * for LogisticSoftMax).
+ *
+ * How.  Chunks of 4096 points go through the predictor's kernels (mean_f = k_* K^-1 mu, var_f = k_** + jitter - rowdot(k_* A, k_*),
+ * A = K^-1 - K^-1 Sigma K^-1, algebraically K~ + diag(kappa Sigma kappa')); one kernel forms the local variables of each point in
+ * registers and leaves one pair of partial sums per 256 points; ONE fixed-order reduction adds all partials after the last chunk.
+ * No floating-point atomics: two calls on the same inputs return the same bits.  The only allocation that grows with n is the
+ * partial sums, 16 bytes per 256 points.
+ *
+ * Once-per-evaluation terms of the reference are counted ONCE for the whole stream and read from global point 0 (the first chunk's
+ * first point), exactly as the one-batch call does: LogisticSoftMax log(beta[0]) (with the GammaEntropy sums per point), and in
+ * AGP_ELBO_REFERENCE mode the Laplace GIGEntropy's scalar-iteration terms of point i == 0.
+ *
+ * No side effects.  The call completes a pending natural-gradient step first, as every entry point does.  After that it leaves
+ * unchanged: the posterior, the local variables of the last step, the kappa / K_nm caches and their validity flags, the look-ahead,
+ * agp_svgp_elbo_terms (which keeps referring to the last agp_svgp_elbo) and the status word (nothing is latched).  It uses the
+ * predictor's workspace and caches, like agp_svgp_predict_f.
+ *
+ * Failure.  If a point's var_f is not > 0, or a moment is not finite, the call returns AGP_ERR_NEG_KTILDE and agp_last_error
+ * carries the index (position in the stream) of the FIRST such point; a LogisticSoftMax class index outside [0, n_class) returns
+ * AGP_ERR_LABELS in the same way.  elbo_host and terms_host stay untouched.  The call synchronises once per latent, at the end
+ * (the Gaussian KL's scalars; the data terms and the failure words ride on the first).
+ *
+ * Accepted: sparse AnalyticVI / AnalyticSVI handles, AGP_F64 and AGP_F32; Gaussian with fixed noise, Logistic, StudentT, Laplace,
+ * BayesianSVM, NegBinomial, LogisticSoftMax (all K latents on the handle); both elbo_modes, every kernel and transform, any D,
+ * non-zero prior mean.
+ * Refused with AGP_ERR_UNSUPPORTED, by name in agp_last_error, before anything is launched: Poisson and Heteroscedastic (lambda is
+ * re-estimated from sums over the whole batch: a second pass); Gaussian with opt_noise (its fresh ELBO steps the noise);
+ * AGP_LIK_MULTIOUTPUT; AGP_FLAG_FULL, AGP_FLAG_EXACT, AGP_FLAG_SAMPLED, AGP_FLAG_NUMERICAL and AGP_FLAG_MC handles; online handles
+ * (streaming prior); AGP_FLAG_STALE_K; latent-sharded and batch-sharded handles. */
+agp_status agp_svgp_elbo_stream(agp_svgp* h, const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t n,
+                                double rho, double* elbo_host, double* terms_host /* nullable, double[3] */);
 /* batch-parallel run: this handle sees shard `rank` of `world` of every minibatch.  Changes the ELBO -- the reference's
  * once-per-evaluation terms (LogisticSoftMax `sum(log, first(beta))` logisticsoftmax.jl:138, the scalar-iteration terms of
  * the Laplace GIGEntropy in AGP_ELBO_REFERENCE mode) are then counted by rank 0 only -- and the hyper-gradient, whose replicated

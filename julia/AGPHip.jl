@@ -23,6 +23,7 @@
 #   compute_K / compute_κ                                     src/gpblocks/latentgp.jl:205-215         -> inside the step / agp_svgp_refresh_K
 #   update_hyperparameters!(m, state, x, y)                   src/hyperparameter/autotuning.jl:86-140  -> agp_svgp_hyper_step[_multi]
 #   ELBO(model, state, y) / ELBO(model, X, y)                 src/inference/analyticVI.jl:255-297, src/functions/ELBO.jl:32-47 -> agp_svgp_elbo
+#   ELBO(model, X, y; streamed=true)                          the same over any number of points                   -> agp_svgp_elbo_stream
 #   _predict_f / predict_y / proba_y                          src/training/predictions.jl:25-92,178-247 -> agp_svgp_predict_f / _predict_y / _proba_y
 #   init_state                                                src/training/states.jl:1-9               -> agp_svgp_init_state
 # Multi-GPU (one Julia process per GPU, e.g. under MPI.jl or Distributed): agp_comm_* binds RCCL inside the library; the host only
@@ -705,11 +706,23 @@ Base.fetch(side::SideObjective, ticket::Integer; wait::Bool=true) = objective_fe
 
 # external ELBO(model, X, y) (src/functions/ELBO.jl:28-47): kernel matrices recomputed on (X, y), fresh local variables, one local
 # update.  The reference keeps ρ = N/B of the last train! here (Appendix A Q13); pass ρ = 1 for the properly scaled value.
-function ELBO(hm::HipModel{T}, X::AbstractMatrix, y::AbstractArray; obsdim=1, ρ::Real=AGP.ρ(AGP.inference(hm.model))) where {T}
+# streamed=true: the same value over ANY number of points (agp_svgp_elbo_stream): chunks of 4096 through the predictor's kernels,
+# the handle is not re-created with max_batch = n, the workspace does not depend on n.  Sparse AnalyticVI / AnalyticSVI models;
+# the library refuses the others by name (include/agp_hip.h, "STREAMED ELBO").
+function ELBO(hm::HipModel{T}, X::AbstractMatrix, y::AbstractArray; obsdim=1, ρ::Real=AGP.ρ(AGP.inference(hm.model)),
+              streamed::Bool=false) where {T}
     twin = HipModel{T,typeof(hm.model)}(hm.model, hm.ctx, hm.h, C_NULL, hm.shard, hm.latent_range, hm.maxbatch, nothing, nothing,
                                         0, nothing, hm.stale_K, hm.rank, hm.world, Any[])  # same handle, its own data buffers
     upload!(twin, X, y; obsdim)
     n = twin.N
+    if streamed
+        ensure_handle!(hm, max(hm.maxbatch, 1))
+        out = Ref{Float64}()
+        check(hm.ctx, ccall((:agp_svgp_elbo_stream, libagp), Int32,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Int64}, Int64, Float64, Ref{Float64}, Ptr{Float64}),
+                            hm.h, pointer(twin.X), size(twin.X, 1), pointer(twin.y), C_NULL, n, ρ, out, C_NULL))
+        return out[]
+    end
     if n > hm.maxbatch
         ensure_handle!(hm, n); twin.h = hm.h
     end
