@@ -21,6 +21,7 @@
 #include "agp_nvi.h"
 #include "agp_rand.h"
 #include "agp_pathwise.h"
+#include "agp_lpd.h"
 // (the host layers after every kernel header, as they stood in this file: the order of the kernels in the code object is kept)
 #include "agp_ctx.h"
 #include "agp_chol_host.h"
@@ -38,10 +39,116 @@ struct KernelHost {
   std::vector<double> scales;  // length D
 };
 
+// ---- log predictive density (include/agp_hip.h, "LOG PREDICTIVE DENSITY"; device code in agp_lpd.h) ----------------------------------
+static bool lpd_lik_ok(int kind) {
+  return kind == AGP_LIK_GAUSSIAN || kind == AGP_LIK_LAPLACE || lpd_is_quad(kind) || lpd_is_multiclass(kind);
+}
+// the likelihood's parameters as the kernel takes them, constants formed here (lgamma)
+static agp_status lpd_params(agp_ctx* ctx, const char* who, const agp_lik_desc& lik, LpdParams* P) {
+  P->p0 = lik.p0, P->p1 = lik.p1, P->c0 = 0.0;
+  const int k = lik.kind;
+  const bool need_p0 = k == AGP_LIK_GAUSSIAN || k == AGP_LIK_LAPLACE || k == AGP_LIK_POISSON || k == AGP_LIK_NEGBINOMIAL;
+  if ((need_p0 && !(lik.p0 > 0)) || (k == AGP_LIK_STUDENTT && !(lik.p0 > 0.5 && lik.p1 > 0))) {
+    ctx->err = std::string(who) + ": Gaussian sigma2, Laplace beta, Poisson lambda and NegBinomial r must be positive, StudentT needs "
+               "nu > 0.5 and sigma > 0";
+    return AGP_ERR_INVALID;
+  }
+  if (k == AGP_LIK_STUDENTT)  // studentt.jl:43-46 as written (nvi_lconst)
+    P->c0 = std::lgamma(0.5 * (lik.p0 + 1.0)) - 0.5 * std::log(lik.p0 * 3.141592653589793) - std::lgamma(0.5 * lik.p0);
+  if (k == AGP_LIK_LAPLACE) P->c0 = -std::log(4.0 * lik.p0);
+  if (k == AGP_LIK_NEGBINOMIAL) P->c0 = -std::lgamma(lik.p0);
+  return AGP_OK;
+}
+// The Gauss-Hermite rule on the device, nodes | log weights, uploaded only when the caller's rule changes.
+struct LpdRule {
+  double* dev = nullptr;
+  int cap = 0;
+  std::vector<double> nodes, weights, up;
+  ~LpdRule() {
+    if (dev) (void)hipFree(dev);
+  }
+  agp_status ensure(agp_ctx* ctx, const char* who, hipStream_t s, const double* x, const double* w, int nn) {
+    if (!x || !w || nn < 1 || nn > 4096) {
+      ctx->err = std::string(who) + ": this likelihood needs the Gauss-Hermite nodes and weights, 1 <= n_nodes <= 4096";
+      return AGP_ERR_INVALID;
+    }
+    if (dev && (int)nodes.size() == nn && !std::memcmp(nodes.data(), x, sizeof(double) * nn) &&
+        !std::memcmp(weights.data(), w, sizeof(double) * nn))
+      return AGP_OK;
+    for (int j = 0; j < nn; ++j)
+      if (!std::isfinite(x[j]) || !(w[j] >= 0.0) || !std::isfinite(w[j])) {
+        ctx->err = std::string(who) + ": the nodes must be finite and the weights finite and non-negative";
+        return AGP_ERR_INVALID;
+      }
+    nodes.clear();  // (nothing counts as cached until the upload has been enqueued)
+    // an earlier upload may still read the staging vector: the stream is drained before it is rewritten (a change of rule is rare)
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (nn > cap) {
+      if (dev) (void)hipFree(dev);
+      dev = nullptr, cap = 0;
+      AGPCHK(dmalloc(ctx, &dev, 2 * (int64_t)nn));
+      cap = nn;
+    }
+    up.assign(x, x + nn);
+    for (int j = 0; j < nn; ++j) up.push_back(std::log(w[j]));  // (a zero weight: -inf, the node is skipped)
+    HIPCHK(ctx, hipMemcpyAsync(dev, up.data(), sizeof(double) * 2 * nn, hipMemcpyHostToDevice, s));
+    nodes.assign(x, x + nn);
+    weights.assign(w, w + nn);
+    return AGP_OK;
+  }
+};
+// one launch of k_predict_lpd over nc points that start at stream position `base`; part points at the launch's first workgroup
+template <typename T>
+static agp_status lpd_launch(agp_ctx* ctx, hipStream_t s, int kind, int64_t nc, int64_t base, int nl, int64_t ld, const LpdParams& P,
+                             const T* lstate, const void* y, const T* mu, const T* var, const double* quad, int nn, T* lpd_out,
+                             double* part, unsigned long long* bad) {
+  const unsigned gw = (unsigned)((nc + lpd_points_per_block(kind) - 1) / lpd_points_per_block(kind));
+#define AGP_LPD_CASE(K)                                                                                                            \
+  case K:                                                                                                                          \
+    hipLaunchKernelGGL((k_predict_lpd<T, K>), dim3(gw), dim3(LPD_THREADS), 0, s, nc, base, nl, ld, P, lstate, (const T*)y,          \
+                       (const int32_t*)y, mu, var, quad, nn, lpd_out, part, bad);                                                 \
+    break;
+  switch (kind) {
+    AGP_LPD_CASE(LIK_GAUSSIAN)
+    AGP_LPD_CASE(LIK_LOGISTIC)
+    AGP_LPD_CASE(LIK_STUDENTT)
+    AGP_LPD_CASE(LIK_LSM)
+    AGP_LPD_CASE(LIK_LAPLACE)
+    AGP_LPD_CASE(LIK_BSVM)
+    AGP_LPD_CASE(LIK_POISSON)
+    AGP_LPD_CASE(LIK_NEGBIN)
+    AGP_LPD_CASE(LIK_SOFTMAX)
+    default:
+      ctx->err = "log predictive density: unknown likelihood kind";
+      return AGP_ERR_UNSUPPORTED;
+  }
+#undef AGP_LPD_CASE
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+// the two failure words (as k_lpd_reduce leaves them) -> status and message
+static agp_status lpd_failure(agp_ctx* ctx, const char* who, const double* h) {
+  if (h[1] >= 0.0) {
+    ctx->err = std::string(who) + ": var_f is not positive (or a moment is not finite) at point " + std::to_string((int64_t)h[1]) +
+               " of the stream (K~ has negative values)";
+    return AGP_ERR_NEG_KTILDE;
+  }
+  if (h[2] >= 0.0) {
+    ctx->err = std::string(who) + ": a target the likelihood cannot take (class index outside the likelihood's classes, a count that "
+               "is not a non-negative integer, a binary label that is not +-1) at point " + std::to_string((int64_t)h[2]) +
+               " of the stream";
+    return AGP_ERR_LABELS;
+  }
+  return AGP_OK;
+}
+
 struct SvgpBase {
   agp_ctx* ctx = nullptr;
   agp_svgp_desc desc{};
-  virtual ~SvgpBase() {}
+  virtual ~SvgpBase() {
+    for (void* p : {lpd_mu, lpd_var, (void*)lpd_part, (void*)lpd_scal})
+      if (p) (void)hipFree(p);
+  }
   virtual agp_status init() = 0;
   virtual agp_status set_kernel(int l, const agp_kernel_desc* k) = 0;
   virtual agp_status set_Z(int l, const void* z, int64_t ldz) = 0;
@@ -93,6 +200,88 @@ struct SvgpBase {
   }
   virtual agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) {
     return elbo_stream_refused("this handle class has no streamed ELBO (sparse AnalyticVI / AnalyticSVI handles only)");
+  }
+  // ---- streamed log predictive density (include/agp_hip.h, "LOG PREDICTIVE DENSITY") ------------------------
+  // sum_i log p(y_i | x_i, model) over any number of points: the handle's own predict_f, chunk by chunk, leaves the moments of 4096
+  // points in lpd_mu / lpd_var; k_predict_lpd turns them into one partial sum per workgroup; k_lpd_reduce adds all of them in a
+  // fixed order.  One routine for every class whose predict_f works.  Touches the predictor's workspace and the buffers below --
+  // never step buffers, local variables, caches or status words.  One synchronisation, at the end.
+  void *lpd_mu = nullptr, *lpd_var = nullptr;  // T[n_latent][4096]
+  double* lpd_part = nullptr;                  // one per workgroup of the stream
+  int64_t lpd_part_cap = 0;
+  double* lpd_scal = nullptr;                  // out[3] of k_lpd_reduce | - | the two failure words
+  LpdRule lpd_rule;
+  // what the routine has to ask the class: the likelihood-state word on the device (Gaussian noise under opt_noise, Poisson lambda;
+  // NULL: the descriptor's p0 holds), and whether the handle sees a shard of every minibatch
+  virtual const void* lpd_lik_state() { return nullptr; }
+  virtual bool lpd_batch_sharded() { return false; }
+  agp_status lpd_refused(const char* why) {
+    ctx->err = std::string("agp_svgp_lpd_stream: ") + why;
+    return AGP_ERR_UNSUPPORTED;
+  }
+  agp_status lpd_stream(const void* xt, int64_t ldx, const void* y, int64_t n, const double* nodes, const double* weights, int nn,
+                        double* sum_host, void* lpd_out) {
+    const int kind = desc.lik.kind;
+    if (desc.flags & AGP_FLAG_SAMPLED)
+      return lpd_refused("Gibbs-sampled models (AGP_FLAG_SAMPLED) are not supported: they have no predict_f");
+    if (kind == AGP_LIK_MULTIOUTPUT) return lpd_refused("multi-output handles (AGP_LIK_MULTIOUTPUT) are not supported");
+    if (kind == AGP_LIK_HETEROSCEDASTIC)
+      return lpd_refused("Heteroscedastic is not supported (two latents, a nested integral: a follow-up)");
+    if (!lpd_lik_ok(kind)) return lpd_refused("unknown likelihood kind");
+    if (desc.latent_offset != 0 || desc.n_latent != (lpd_is_multiclass(kind) ? desc.lik.n_class : 1))
+      return lpd_refused("latent-sharded handles are not supported (a point's density needs every latent on one handle)");
+    if (lpd_batch_sharded()) return lpd_refused("batch-sharded handles are not supported");
+    if (n < 0 || !sum_host || (n > 0 && (!xt || !y || ldx < desc.D))) {
+      ctx->err = "agp_svgp_lpd_stream: n >= 0, sum_host must not be NULL, x and y must not be NULL, ldx >= D";
+      return AGP_ERR_INVALID;
+    }
+    if (n == 0) {
+      *sum_host = 0.0;
+      return AGP_OK;
+    }
+    return desc.dtype == AGP_F32 ? lpd_stream_t<float>(xt, ldx, y, n, nodes, weights, nn, sum_host, lpd_out)
+                                 : lpd_stream_t<double>(xt, ldx, y, n, nodes, weights, nn, sum_host, lpd_out);
+  }
+  template <typename T>
+  agp_status lpd_stream_t(const void* xt, int64_t ldx, const void* y, int64_t n, const double* nodes, const double* weights, int nn,
+                          double* sum_host, void* lpd_out) {
+    const char* who = "agp_svgp_lpd_stream";
+    const int kind = desc.lik.kind, nl = desc.n_latent;
+    const int64_t CH = 4096, ppb = lpd_points_per_block(kind);
+    const int64_t nw = (n + ppb - 1) / ppb;
+    hipStream_t s = ctx->stream;
+    LpdParams P;
+    AGPCHK(lpd_params(ctx, who, desc.lik, &P));
+    if (lpd_is_quad(kind)) AGPCHK(lpd_rule.ensure(ctx, who, s, nodes, weights, nn));
+    if (!lpd_mu) {
+      AGPCHK(dmalloc(ctx, (T**)&lpd_mu, (int64_t)nl * CH));
+      AGPCHK(dmalloc(ctx, (T**)&lpd_var, (int64_t)nl * CH));
+      AGPCHK(dmalloc(ctx, &lpd_scal, 8));
+    }
+    if (nw > lpd_part_cap) {
+      if (lpd_part) (void)hipFree(lpd_part);
+      lpd_part = nullptr;
+      lpd_part_cap = 0;
+      AGPCHK(dmalloc(ctx, &lpd_part, nw));
+      lpd_part_cap = nw;
+    }
+    unsigned long long* bad = reinterpret_cast<unsigned long long*>(lpd_scal + 4);
+    HIPCHK(ctx, hipMemsetAsync(bad, 0xFF, 2 * sizeof(unsigned long long), s));
+    const T* lstate = (const T*)lpd_lik_state();
+    for (int64_t st0 = 0; st0 < n; st0 += CH) {
+      const int64_t nc = (n - st0) < CH ? (n - st0) : CH;
+      AGPCHK(predict_f((const T*)xt + st0 * ldx, ldx, nc, lpd_mu, lpd_var));  // T[nl][nc]
+      AGPCHK(lpd_launch<T>(ctx, s, kind, nc, st0, nl, nc, P, lstate, y, (const T*)lpd_mu, (const T*)lpd_var, lpd_rule.dev, nn,
+                           (T*)lpd_out, lpd_part + st0 / ppb, bad));
+    }
+    hipLaunchKernelGGL(k_lpd_reduce, dim3(1), dim3(1024), 0, s, (const double*)lpd_part, nw, (const unsigned long long*)bad, lpd_scal);
+    LAUNCHCHK(ctx);
+    double h[3] = {0.0, -1.0, -1.0};
+    HIPCHK(ctx, hipMemcpyAsync(h, lpd_scal, sizeof(double) * 3, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    AGPCHK(lpd_failure(ctx, who, h));
+    *sum_host = h[0];
+    return AGP_OK;
   }
   virtual agp_status elbo_enqueue(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho, int fresh,
                                   int32_t* ticket) = 0;
@@ -3768,6 +3957,10 @@ struct Svgp : SvgpBase {
     HIPCHK(ctx, hipMemcpyAsync(alpha, a, sizeof(T) * n, hipMemcpyDeviceToDevice, st()));
     return AGP_OK;
   }
+  const void* lpd_lik_state() override {
+    return (lp.kind == AGP_LIK_POISSON || (lp.kind == AGP_LIK_GAUSSIAN && lp.noise_dev)) ? lam_dev : nullptr;
+  }
+  bool lpd_batch_sharded() override { return bs_world > 1; }
   agp_status get_lik_param(double* out) override {
     if (!out) return AGP_ERR_INVALID;
     if (lp.kind == AGP_LIK_POISSON || lp.kind == AGP_LIK_HETEROSCEDASTIC || (lp.kind == AGP_LIK_GAUSSIAN && lp.noise_dev)) {
@@ -6481,6 +6674,65 @@ agp_status agp_svgp_elbo_stream(agp_svgp* h, const void* x, int64_t ldx, const v
                                 double rho, double* elbo_host, double* terms_host) {
   HCHKF(h);
   return h->impl->elbo_stream(x, ldx, y, idx, n, rho, elbo_host, terms_host);
+}
+agp_status agp_svgp_lpd_stream(agp_svgp* h, const void* xt, int64_t ldx, const void* y, int64_t n, const double* gh_nodes_host,
+                               const double* gh_weights_host, int32_t n_nodes, double* sum_host, void* lpd_out) {
+  HCHKF(h);
+  return h->impl->lpd_stream(xt, ldx, y, n, gh_nodes_host, gh_weights_host, n_nodes, sum_host, lpd_out);
+}
+agp_status agp_log_predictive(agp_ctx* ctx, int32_t dtype, const agp_lik_desc* lik, const void* y, const void* mu, const void* var,
+                              int64_t n, int64_t ld, const double* gh_nodes_host, const double* gh_weights_host, int32_t n_nodes,
+                              void* lpd_out) {
+  if (!ctx) return AGP_ERR_INVALID;
+  const char* who = "agp_log_predictive";
+  if (!lik || (dtype != AGP_F64 && dtype != AGP_F32) || n < 0 || (n > 0 && (!y || !mu || !var || !lpd_out || ld < n))) {
+    ctx->err = "agp_log_predictive: lik, y, mu, var and lpd_out must not be NULL, dtype AGP_F64 / AGP_F32, n >= 0, ld >= n";
+    return AGP_ERR_INVALID;
+  }
+  if (!lpd_lik_ok(lik->kind)) {
+    ctx->err = "agp_log_predictive: Gaussian, Laplace, Logistic, BayesianSVM, StudentT, Poisson, NegBinomial, LogisticSoftMax and "
+               "SoftMax are supported (Heteroscedastic: a follow-up)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if (lpd_is_multiclass(lik->kind) && lik->n_class < 1) {
+    ctx->err = "agp_log_predictive: n_class must be positive";
+    return AGP_ERR_INVALID;
+  }
+  LpdParams P;
+  AGPCHK(lpd_params(ctx, who, *lik, &P));
+  if (n == 0) return AGP_OK;
+  DevGuard guard(ctx->device);
+  LpdRule rule;
+  if (lpd_is_quad(lik->kind)) AGPCHK(rule.ensure(ctx, who, ctx->stream, gh_nodes_host, gh_weights_host, n_nodes));
+  const int nl = lpd_is_multiclass(lik->kind) ? lik->n_class : 1;
+  const int64_t ppb = lpd_points_per_block(lik->kind), nw = (n + ppb - 1) / ppb;
+  double* ws = nullptr;  // partials | out[3] of the reduction, padding | the two failure words
+  AGPCHK(dmalloc(ctx, &ws, nw + 8));
+  unsigned long long* bad = reinterpret_cast<unsigned long long*>(ws + nw + 4);
+  double h[3] = {0.0, -1.0, -1.0};
+  agp_status st = AGP_OK;
+  hipError_t e = hipMemsetAsync(bad, 0xFF, 2 * sizeof(unsigned long long), ctx->stream);
+  if (e == hipSuccess) {
+    st = dtype == AGP_F32 ? lpd_launch<float>(ctx, ctx->stream, lik->kind, n, 0, nl, ld, P, nullptr, y, (const float*)mu,
+                                              (const float*)var, rule.dev, n_nodes, (float*)lpd_out, ws, bad)
+                          : lpd_launch<double>(ctx, ctx->stream, lik->kind, n, 0, nl, ld, P, nullptr, y, (const double*)mu,
+                                               (const double*)var, rule.dev, n_nodes, (double*)lpd_out, ws, bad);
+    if (st == AGP_OK) {
+      hipLaunchKernelGGL(k_lpd_reduce, dim3(1), dim3(1024), 0, ctx->stream, (const double*)ws, nw, (const unsigned long long*)bad,
+                         ws + nw);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess && st == AGP_OK) e = hipMemcpyAsync(h, ws + nw, sizeof(double) * 3, hipMemcpyDeviceToHost, ctx->stream);
+  // (ws and the rule's buffers are released below: the stream is drained first, on every path)
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(ws);
+  if (st != AGP_OK) return st;
+  if (e != hipSuccess || e2 != hipSuccess) {
+    ctx->err = std::string("agp_log_predictive: ") + hipGetErrorString(e != hipSuccess ? e : e2);
+    return AGP_ERR_HIP;
+  }
+  return lpd_failure(ctx, who, h);
 }
 agp_status agp_svgp_get_state(agp_svgp* h, int32_t latent, void* mu, void* sigma, void* eta1, void* eta2) {
   HCHKF(h);

@@ -552,6 +552,67 @@ agp_status agp_svgp_elbo_terms(agp_svgp* h, double* terms_host);
  * (streaming prior); AGP_FLAG_STALE_K; latent-sharded and batch-sharded handles. */
 agp_status agp_svgp_elbo_stream(agp_svgp* h, const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t n,
                                 double rho, double* elbo_host, double* terms_host /* nullable, double[3] */);
+
+/* ---- LOG PREDICTIVE DENSITY (held-out log-likelihood / NLPD, over any number of test points) ------------------------------------
+ * sum_i lpd_i, lpd_i = log p(y_i | x_i, model) = log int p(y_i | f) N(f; mu_i, var_i) df, where (mu_i, var_i) are exactly what
+ * agp_svgp_predict_f with variances returns for the handle and p(y | f) is the reference's point likelihood.  Streamed in chunks
+ * of 4096 points through the handle's own predictor; the sum comes back in double (sum_host), the vector optionally (lpd_out,
+ * nullable, device T[n], dense).  Layout: the "Layout" section above (ldx in elements, >= D, padding never read); y as
+ * agp_svgp_cavi_step takes it (T[n]; int32 class indices for LogisticSoftMax / SoftMax).
+ *
+ * The rule per likelihood.
+ *   Gaussian      closed form, log N(y; mu, var + sigma2) with the handle's CURRENT noise (the opt_noise state included).
+ *   Laplace(beta) closed form (Gauss-Hermite converges slowly across the kink): with d = y - mu,
+ *                 p = (1 / 4 beta) [T(d) + T(-d)], T(d) = exp(var / 2 beta^2 - d / beta) erfc((var / beta - d) / sqrt(2 var)),
+ *                 formed in logs (erfc below a = 0, exp(-d^2 / 2 var) erfcx(a) above) and combined with logaddexp: finite for
+ *                 |d| = 50 at var = 1e-3 and at var = 30.
+ *   Logistic, BayesianSVM, StudentT, Poisson, NegBinomial
+ *                 the n-node Gauss-Hermite sum in f-space with the caller's nodes and weights, the reference's predictive rule
+ *                 (predictions.jl:4, classification.jl:14-26; the nodes agp_svgp_proba_y takes: x_j = sqrt(2) t_j, w_j = omega_j /
+ *                 sqrt(pi)), 1 <= n_nodes <= 4096: lpd = log sum_j w_j p(y | mu + sqrt(var) x_j), formed as a log-sum-exp of
+ *                 log w_j + log p with every log p in its overflow-safe form (mu = -800 y at var = 1e-2 gives about -800 where the
+ *                 direct sum gives -inf).  Poisson uses the handle's current lambda.  StudentT takes the reference's density AS
+ *                 WRITTEN (studentt.jl:43-46): Gamma(alpha) / (sqrt(nu pi) Gamma(nu / 2)) (1 + ((y - f) / sigma)^2)^-alpha, alpha =
+ *                 (nu + 1) / 2 -- the normalised t with nu degrees of freedom and scale sigma / sqrt(nu), multiplied by sigma /
+ *                 sqrt(nu) (the constant the quadrature inference uses).
+ *                 Accuracy: the f-space rule degrades when the predictive spread sqrt(var) far exceeds the likelihood's width;
+ *                 DESIGN.md section 9m has the measured table.
+ *   LogisticSoftMax / SoftMax
+ *                 the handle's own proba_y rule, the link applied to the means (multiclass.jl:96-117): lpd = log sigma(mu_y) -
+ *                 log sum_k sigma(mu_k), resp. mu_y - logsumexp(mu), formed in logs.  The variances are only checked.
+ *
+ * How.  Quadrature kinds: a 16-lane group per point, node j on lane j mod 16, a running (max, scaled sum) pair per lane, merged by
+ * a fixed shuffle tree; the others one lane per point.  Double accumulation for both dtypes.  One partial sum per workgroup, ONE
+ * fixed-order reduction after the last chunk, no floating-point atomics: two calls on the same inputs return the same bits, sum and
+ * vector.  The partial sums are the only allocation that grows with n (at most 1 byte per point); the rest is chunk-sized and kept
+ * on the handle.  The nodes live in a device buffer that is uploaded only when the caller's rule changes.
+ *
+ * No side effects.  The call completes a pending natural-gradient step first, as every entry point does; after that it uses the
+ * predictor's workspace and caches, like agp_svgp_predict_f, and buffers of its own -- the posterior, step buffers, local variables,
+ * caches, agp_svgp_elbo_terms and the status word stay bitwise unchanged.  It synchronises once, at the end (and once more before
+ * it uploads a rule that differs from the last call's).
+ *
+ * Failure.  A point whose var_f is not > 0, or a moment that is not finite: AGP_ERR_NEG_KTILDE.  A class index outside [0, K), a
+ * Poisson / NegBinomial target that is not a non-negative integer, a Logistic / BayesianSVM label that is not +-1:
+ * AGP_ERR_LABELS.  agp_last_error names the FIRST such position of the stream.  sum_host is then untouched, the contents of lpd_out
+ * are unspecified, nothing is latched on the handle.  n = 0 succeeds with sum 0.  n < 0, sum_host NULL, x / y NULL, ldx < D, missing
+ * nodes for a quadrature kind, n_nodes outside [1, 4096], negative or non-finite weights: AGP_ERR_INVALID.
+ *
+ * Accepted: every handle whose agp_svgp_predict_f works -- sparse AnalyticVI / AnalyticSVI (AGP_F64 and AGP_F32), online,
+ * AGP_FLAG_STALE_K, AGP_FLAG_FULL, AGP_FLAG_EXACT, AGP_FLAG_NUMERICAL with or without AGP_FLAG_MC (their (mu, Sigma) are always valid
+ * for prediction).  Refused with AGP_ERR_UNSUPPORTED, by name in agp_last_error, before anything is launched: Heteroscedastic (two
+ * latents, a nested integral: a follow-up); AGP_LIK_MULTIOUTPUT; AGP_FLAG_SAMPLED; latent-sharded and batch-sharded handles. */
+agp_status agp_svgp_lpd_stream(agp_svgp* h, const void* xt, int64_t ldx, const void* y, int64_t n, const double* gh_nodes_host,
+                               const double* gh_weights_host, int32_t n_nodes, double* sum_host,
+                               void* lpd_out /* nullable, device T[n] */);
+/* The point-wise kernel of the above on given moments, outside any model (what agp_quad_expectations is to the quadrature
+ * inference): lpd_out[i] (device T[n]) from y[i] and mu / var (device T[n]; T[n_class][ld] for the multi-class kinds, ld >= n the
+ * latent stride).  dtype AGP_F64 / AGP_F32.  The nodes may be NULL for the closed-form and multi-class kinds.  Gaussian sigma2,
+ * Laplace beta, NegBinomial r and Poisson lambda are lik->p0; StudentT (nu, sigma) = (p0, p1); n_class = K.  Failures as above (the
+ * position is the index i); n = 0 is a successful no-op.  Synchronises the context's stream. */
+agp_status agp_log_predictive(agp_ctx* ctx, int32_t dtype, const agp_lik_desc* lik, const void* y, const void* mu, const void* var,
+                              int64_t n, int64_t ld /* latent stride, >= n */, const double* gh_nodes_host,
+                              const double* gh_weights_host, int32_t n_nodes, void* lpd_out);
 /* batch-parallel run: this handle sees shard `rank` of `world` of every minibatch.  Changes the ELBO -- the reference's
  * once-per-evaluation terms (LogisticSoftMax `sum(log, first(beta))` logisticsoftmax.jl:138, the scalar-iteration terms of
  * the Laplace GIGEntropy in AGP_ELBO_REFERENCE mode) are then counted by rank 0 only -- and the hyper-gradient, whose replicated

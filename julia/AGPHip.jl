@@ -24,6 +24,7 @@
 #   update_hyperparameters!(m, state, x, y)                   src/hyperparameter/autotuning.jl:86-140  -> agp_svgp_hyper_step[_multi]
 #   ELBO(model, state, y) / ELBO(model, X, y)                 src/inference/analyticVI.jl:255-297, src/functions/ELBO.jl:32-47 -> agp_svgp_elbo
 #   ELBO(model, X, y; streamed=true)                          the same over any number of points                   -> agp_svgp_elbo_stream
+#   log_predictive_density(model, X, y) (no counterpart: the held-out log-likelihood / NLPD)           -> agp_svgp_lpd_stream, agp_log_predictive
 #   _predict_f / predict_y / proba_y                          src/training/predictions.jl:25-92,178-247 -> agp_svgp_predict_f / _predict_y / _proba_y
 #   init_state                                                src/training/states.jl:1-9               -> agp_svgp_init_state
 # Multi-GPU (one Julia process per GPU, e.g. under MPI.jl or Distributed): agp_comm_* binds RCCL inside the library; the host only
@@ -812,6 +813,54 @@ function proba_y(hm::HipModel{T}, X_test::AbstractMatrix, state=nothing; obsdim:
     a, b = Array(o0), Array(o1)
     is_mo(hm) && return [(a[:, t], b[:, t]) for t in 1:nout]
     return is_bernoulli(l) ? a[:, 1] : (a[:, 1], b[:, 1])
+end
+
+# ---- log predictive density (include/agp_hip.h, "LOG PREDICTIVE DENSITY") ---------------------------------------------------------
+# sum_i log p(y_i | x_i, model) over ANY number of test points (the held-out log-likelihood; its negative mean is the NLPD), streamed
+# in chunks of 4096 through the handle's own predictor (agp_svgp_lpd_stream).  Gaussian and Laplace in closed form; Logistic,
+# BayesianSVM, StudentT (the reference's density as written, studentt.jl:43-46), Poisson and NegBinomial by the Gauss-Hermite rule of
+# predictions.jl:4 formed as a log-sum-exp; LogisticSoftMax by the link on the means (multiclass.jl:96-117).  Labels go through the
+# reference's own treat_labels! (upload!).  pointwise=true: (sum, lpd::Vector).  The library refuses Heteroscedastic, multi-output,
+# Gibbs-sampled and sharded handles by name.
+function log_predictive_density(hm::HipModel{T}, X::AbstractMatrix, y::AbstractArray; pointwise::Bool=false, obsdim::Int=1,
+                                nodes::Vector{Float64}=AGP.pred_nodes, weights::Vector{Float64}=AGP.pred_weights) where {T}
+    twin = HipModel{T,typeof(hm.model)}(hm.model, hm.ctx, hm.h, C_NULL, hm.shard, hm.latent_range, hm.maxbatch, nothing, nothing,
+                                        0, nothing, hm.stale_K, hm.rank, hm.world, Any[])  # same handle, its own data buffers
+    upload!(twin, X, y; obsdim)
+    n = twin.N
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    out = Ref{Float64}(0.0)
+    vec = pointwise ? ROCVector{T}(undef, n) : nothing
+    check(hm.ctx, ccall((:agp_svgp_lpd_stream, libagp), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ref{Float64}, Ptr{Cvoid}),
+                        hm.h, pointer(twin.X), size(twin.X, 1), pointer(twin.y), n, nodes, weights, length(nodes), out,
+                        vec === nothing ? C_NULL : pointer(vec)))
+    return pointwise ? (out[], Array(vec)) : out[]
+end
+
+# the point-wise kernel on given moments, outside any model (agp_log_predictive): lpd[i] from y[i], mu[i], var[i]; for a multi-class
+# likelihood y holds 0-based class indices (Int32) and mu, var are n x K.  The nodes are not needed for Gaussian, Laplace and the
+# multi-class likelihoods.
+function log_predictive_moments(l, y::AbstractVector, mu::AbstractVecOrMat{T}, var::AbstractVecOrMat{T};
+                                nodes::Vector{Float64}=AGP.pred_nodes, weights::Vector{Float64}=AGP.pred_weights) where {T<:Union{Float32,Float64}}
+    n = length(y)
+    size(mu, 1) == n && size(mu) == size(var) || throw(DimensionMismatch("y has $n entries, mu and var must have n rows"))
+    yd = is_multiclass(l) ? ROCVector{Int32}(y) : ROCVector{T}(y)
+    md, vd = ROCArray{T}(mu), ROCArray{T}(var)                  # column-major n x K == T[K][n], latent stride n
+    out = ROCVector{T}(undef, n)
+    ctx = Ref{Ptr{Cvoid}}()
+    st = ccall((:agp_ctx_create, libagp), Int32, (Int32, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), AMDGPU.device_id() - 1, AMDGPU.stream().stream, ctx)
+    st == 0 || throw(AGPError(st, "agp_ctx_create"))
+    try
+        check(ctx[], ccall((:agp_log_predictive, libagp), Int32,
+                           (Ptr{Cvoid}, Int32, Ref{LikDesc}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64},
+                            Int32, Ptr{Cvoid}),
+                           ctx[], T == Float64 ? Int32(0) : Int32(1), lik_desc(l), pointer(yd), pointer(md), pointer(vd), n, n, nodes,
+                           weights, length(nodes), pointer(out)))
+        return Array(out)
+    finally
+        ccall((:agp_ctx_destroy, libagp), Int32, (Ptr{Cvoid},), ctx[])
+    end
 end
 
 # ---- multi-GPU: one Julia process per GPU ---------------------------------------------------------------------------------------
