@@ -6081,11 +6081,13 @@ static agp_status bb_nearest(agp_ctx* ctx, const void* x, int64_t n, int64_t ldx
   T* cn = nullptr;
   int32_t* lab = labels;
   T* md = (T*)mind;
-  AGPCHK(dmalloc(ctx, &cn, rup64(m)));
-  if (!lab) AGPCHK(dmalloc(ctx, &lab, n));
-  if (!md) AGPCHK(dmalloc(ctx, &md, n));
-  agp_status st = km_assign<T>(ctx, (const T*)x, n, ldx, D, (const T*)c, ldc, m, cn, lab, md);
-  (void)hipStreamSynchronize(ctx->stream);
+  agp_status st = dmalloc(ctx, &cn, rup64(m));
+  if (st == AGP_OK && !lab) st = dmalloc(ctx, &lab, n);
+  if (st == AGP_OK && !md) st = dmalloc(ctx, &md, n);
+  if (st == AGP_OK) {
+    st = km_assign<T>(ctx, (const T*)x, n, ldx, D, (const T*)c, ldc, m, cn, lab, md);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
   (void)hipFree(cn);
   if (!labels) (void)hipFree(lab);
   if (!mind) (void)hipFree(md);
@@ -6110,14 +6112,26 @@ static agp_status bb_kmeans(agp_ctx* ctx, const void* xv, int64_t n, int64_t ldx
     ctx->err = "agp_kmeans: more than 16384 centres";
     return AGP_ERR_UNSUPPORTED;
   }
-  AGPCHK(dmalloc(ctx, &cn, mp));
-  AGPCHK(dmalloc(ctx, &mind, n));
-  AGPCHK(dmalloc(ctx, &part, (int64_t)nchunks * mp * (Dp + 16)));
-  AGPCHK(dmalloc(ctx, &red, 512));
-  AGPCHK(dmalloc(ctx, &blist, (int64_t)nchunks * KM_CHUNK));
-  AGPCHK(dmalloc(ctx, &boff, (int64_t)nchunks * (KM_MAXTILES + 1)));
-  if (!lab) AGPCHK(dmalloc(ctx, &lab, n));
-  agp_status st = AGP_OK;
+  auto release = [&]() {  // (hipFree(nullptr) is a no-op: whatever a failed dmalloc left unallocated)
+    (void)hipFree(cn);
+    (void)hipFree(mind);
+    (void)hipFree(part);
+    (void)hipFree(red);
+    (void)hipFree(blist);
+    (void)hipFree(boff);
+    if (!labels_out) (void)hipFree(lab);
+  };
+  agp_status st = dmalloc(ctx, &cn, mp);
+  if (st == AGP_OK) st = dmalloc(ctx, &mind, n);
+  if (st == AGP_OK) st = dmalloc(ctx, &part, (int64_t)nchunks * mp * (Dp + 16));
+  if (st == AGP_OK) st = dmalloc(ctx, &red, 512);
+  if (st == AGP_OK) st = dmalloc(ctx, &blist, (int64_t)nchunks * KM_CHUNK);
+  if (st == AGP_OK) st = dmalloc(ctx, &boff, (int64_t)nchunks * (KM_MAXTILES + 1));
+  if (st == AGP_OK && !lab) st = dmalloc(ctx, &lab, n);
+  if (st != AGP_OK) {
+    release();
+    return st;
+  }
   double obj = 0.0, prev = 0.0;
   int it = 0, conv = 0;
   // Clustering.kmeans!: assignments for the seeds, then { centres <- cluster means ; assignments ; |change of cost| < tol }
@@ -6129,8 +6143,7 @@ static agp_status bb_kmeans(agp_ctx* ctx, const void* xv, int64_t n, int64_t ldx
                        (int)(mp / TILE), blist, boff);
     hipLaunchKernelGGL((k_km_sums<T>), dim3((unsigned)(mp / TILE), (unsigned)nchunks), dim3(NTHREADS), 0, ctx->stream, x, ldx, n,
                        D, Dp, (const int32_t*)lab, mp, (const int32_t*)blist, (const int32_t*)boff, part);
-    hipLaunchKernelGGL((k_km_finish<T>), grid1(m * D), dim3(256), 0, ctx->stream, (const T*)part, nchunks, mp, Dp, m, D, c, ldc,
-                       counts_out);
+    hipLaunchKernelGGL((k_km_finish<T>), grid1(m * D), dim3(256), 0, ctx->stream, (const T*)part, nchunks, mp, Dp, m, D, c, ldc);
     if (hipGetLastError() != hipSuccess) {
       st = AGP_ERR_HIP;
       break;
@@ -6140,14 +6153,16 @@ static agp_status bb_kmeans(agp_ctx* ctx, const void* xv, int64_t n, int64_t ldx
     if (st == AGP_OK) st = km_objective<T>(ctx, mind, n, red, &obj);
     if (m == 1 || std::abs(obj - prev) < tol) conv = 1;
   }
+  if (st == AGP_OK && counts_out) {  // the histogram of the final assignment (also the only one, for max_iter = 0)
+    if (hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)m, ctx->stream) != hipSuccess) st = AGP_ERR_HIP;
+    if (st == AGP_OK) {
+      hipLaunchKernelGGL(k_km_hist, dim3((unsigned)nchunks), dim3(256), sizeof(int) * (size_t)m, ctx->stream, (const int32_t*)lab, n,
+                         (int)m, counts_out);
+      if (hipGetLastError() != hipSuccess) st = AGP_ERR_HIP;
+    }
+  }
   (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(cn);
-  (void)hipFree(mind);
-  (void)hipFree(part);
-  (void)hipFree(red);
-  (void)hipFree(blist);
-  (void)hipFree(boff);
-  if (!labels_out) (void)hipFree(lab);
+  release();
   if (iters) *iters = it;
   if (objective) *objective = obj;
   if (converged) *converged = conv;

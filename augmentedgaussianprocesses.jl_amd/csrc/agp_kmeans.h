@@ -5,11 +5,16 @@
 //   k_km_assign : nearest centre of every point.  One workgroup = 64 points x all centres; the point tile stays in LDS,
 //                 centre tiles stream through; distances in GEMM form  ||c||^2 - 2 x.c  (+ ||x||^2 at the end) on
 //                 v_mfma 16x16x4, running (min, argmin) in registers, ties to the smaller index.  The N x m distance
-//                 matrix never exists.
+//                 matrix never exists.  Points and centres are taken relative to s = row 0 of the centres as they are
+//                 staged into LDS (and in k_km_cnorm), so the error of the comparison scales with the distances between
+//                 points and centres and not with ||x||^2: the selection does not change when the data is translated
+//                 (unnormalised features -- years, coordinates, time stamps).  Budget: tests/_kmeans_ref.py.
+//                 A row with a non-finite coordinate gets a label in [0, m) and a non-finite distance (NaN for a NaN).
 //   k_km_bucket : stable bucketing of every 8192-point chunk by centre tile (index order kept inside a bucket)
 //   k_km_sums   : centre sums as H' X (H = one-hot assignment) on MFMA with the one-hot operand generated from the labels
 //                 on the fly, over the bucket of its centre tile only; k_km_finish reduces the chunk partials in chunk
 //                 order, so the new centres are bit-reproducible (no floating-point atomics anywhere).
+//   k_km_hist   : member counts of the final assignment (integer atomics: exact in any order)
 #pragma once
 #include "agp_device.h"
 
@@ -18,14 +23,17 @@ namespace agp {
 constexpr int KM_MAXD = 128;     // padded feature dimension limit of the LDS-resident point tile
 constexpr int KM_CHUNK = 8192;   // points per partial-sum chunk
 
-// cn[j] = ||c_j||^2 for j < m ; +huge for the padding rows so that they are never selected
+// cn[j] = ||c_j - c_0||^2 for j < m ; +huge for the padding rows so that they are never selected
 template <typename T>
 __global__ void k_km_cnorm(const T* __restrict__ C, int64_t ldc, int64_t m, int64_t mp, int64_t D, T* __restrict__ cn) {
   int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (j >= mp) return;
   T s = T(0);
   if (j < m) {
-    for (int64_t d = 0; d < D; ++d) s += C[j * ldc + d] * C[j * ldc + d];
+    for (int64_t d = 0; d < D; ++d) {
+      const T v = C[j * ldc + d] - C[d];
+      s += v * v;
+    }
   } else {
     s = sizeof(T) == 8 ? T(1e300) : T(1e30);
   }
@@ -47,10 +55,13 @@ __global__ __launch_bounds__(NTHREADS) void k_km_assign(const T* __restrict__ X,
   int* redi = reinterpret_cast<int*>(redv + 2 * TILE);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
   const int64_t p0 = (int64_t)blockIdx.x * TILE;
+  // the origin s = centre 0: where Dp divides the workgroup size a thread stages one column throughout and keeps s_d in a register
+  const bool own_col = NTHREADS % Dp == 0;
+  const T s_own = (own_col && tid % Dp < D) ? C[tid % Dp] : T(0);
   for (int e = tid; e < TILE * Dp; e += NTHREADS) {
     int r = e / Dp, d = e % Dp;
     int64_t p = p0 + r;
-    Xs[r * LDX + d] = (p < N && d < D) ? X[p * ldx + d] : T(0);
+    Xs[r * LDX + d] = (p < N && d < D) ? X[p * ldx + d] - (own_col ? s_own : C[d]) : T(0);
   }
   __syncthreads();
   if (tid < TILE) {
@@ -72,7 +83,7 @@ __global__ __launch_bounds__(NTHREADS) void k_km_assign(const T* __restrict__ X,
     for (int e = tid; e < TILE * Dp; e += NTHREADS) {
       int r = e / Dp, d = e % Dp;
       int64_t j = c0 + r;
-      Cs[r * LDX + d] = (j < m && d < D) ? C[j * ldc + d] : T(0);
+      Cs[r * LDX + d] = (j < m && d < D) ? C[j * ldc + d] - (own_col ? s_own : C[d]) : T(0);
     }
     if (tid < TILE) cns[tid] = cn[c0 + tid];
     __syncthreads();
@@ -142,9 +153,11 @@ __global__ __launch_bounds__(NTHREADS) void k_km_assign(const T* __restrict__ X,
       v = v2;
       ix = i2;
     }
-    labels[p0 + tid] = ix;
+    // every distance NaN (a non-finite row) leaves the initial index, and data beyond the padding's +huge could select a
+    // padding row: neither may reach labels, which k_km_bucket uses as an index
+    labels[p0 + tid] = (ix >= 0 && ix < m) ? ix : 0;
     T dd = xn[tid] + v;
-    mind[p0 + tid] = dd > T(0) ? dd : T(0);
+    mind[p0 + tid] = dd < T(0) ? T(0) : dd;  // (a NaN stays a NaN)
   }
 }
 
@@ -245,7 +258,7 @@ __global__ __launch_bounds__(NTHREADS) void k_km_sums(const T* __restrict__ X, i
 // new centre = (sum over chunks, in chunk order) / count ; a cluster that lost all its points keeps its centre
 template <typename T>
 __global__ void k_km_finish(const T* __restrict__ part, int nchunks, int64_t mp, int Dp, int64_t m, int64_t D,
-                            T* __restrict__ C, int64_t ldc, int32_t* __restrict__ counts) {
+                            T* __restrict__ C, int64_t ldc) {
   int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (e >= m * D) return;
   const int64_t j = e / D, d = e % D, LDPt = Dp + 16;
@@ -255,7 +268,22 @@ __global__ void k_km_finish(const T* __restrict__ part, int nchunks, int64_t mp,
     cnt += part[((int64_t)c * mp + j) * LDPt + Dp];
   }
   if (cnt > T(0)) C[j * ldc + d] = s / cnt;
-  if (d == 0 && counts) counts[j] = (int32_t)(cnt + T(0.5));
+}
+
+// counts[j] += number of points with label j (counts zeroed by the caller; labels in [0, m), m <= 64 * KM_MAXTILES).  One workgroup
+// per KM_CHUNK points: a histogram in LDS (m ints), then one integer atomic per non-empty bin, so the result has no order in it.
+__global__ __launch_bounds__(256) void k_km_hist(const int32_t* __restrict__ labels, int64_t N, int m,
+                                                 int32_t* __restrict__ counts) {
+  extern __shared__ int km_bins[];
+  const int tid = threadIdx.x;
+  const int64_t pbeg = (int64_t)blockIdx.x * KM_CHUNK;
+  const int64_t pend = pbeg + KM_CHUNK < N ? pbeg + KM_CHUNK : N;
+  for (int t = tid; t < m; t += 256) km_bins[t] = 0;
+  __syncthreads();
+  for (int64_t p = pbeg + tid; p < pend; p += 256) atomicAdd(&km_bins[labels[p]], 1);
+  __syncthreads();
+  for (int t = tid; t < m; t += 256)
+    if (km_bins[t]) atomicAdd(&counts[t], km_bins[t]);
 }
 
 // deterministic sum of n values (two stages: per-block partials, then one block)

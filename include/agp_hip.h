@@ -303,7 +303,18 @@ agp_status agp_solve_right_spd(agp_ctx* ctx, int32_t dtype, const void* a, int64
  *   (either output may be NULL); device pointers, row-major, x is n x D (ldx), centers m x D (ldc); D <= 128.
  * agp_kmeans: centers (in: seeds, out: result) ; Clustering.kmeans! control flow: assign, then repeat { centres <- cluster
  *   means (an emptied cluster keeps its centre) ; assign ; stop when |cost change| < tol } at most max_iter times.
- *   labels_out / counts_out: nullable device int32[n] / int32[m] of the final assignment.  Synchronises. */
+ *   labels_out / counts_out: nullable device int32[n] / int32[m] of the final assignment: counts_out is the histogram of
+ *   labels_out, also for max_iter = 0.  Synchronises.
+ * Accuracy.  Distances are formed in T relative to the first centre, so the selection does not depend on where the data lies
+ *   (unnormalised features are fine).  With u the unit roundoff of T, Dp = D rounded up to 16 and gamma_k = k u / (1 - k u), every
+ *   point i has the budget B_i = 4 gamma_{Dp+4} (diam^2 + max_j ||x_i - c_j||^2), diam the largest distance between two centres:
+ *   the centre labels_out[i] names is at most B_i farther (in squared distance) than the nearest one, mind_out[i] is within B_i of
+ *   the nearest squared distance, and the cost within the sum of the B_i.  B_i holds differences only: it does not change when
+ *   points and centres are translated.  Cluster means are sums in T of the raw coordinates (error relative to |x|, n_j terms), and
+ *   the member counts are accumulated in T as well: an AGP_F32 cluster of more than 2^24 points is outside the contract.
+ * Non-finite input.  A row of x with a NaN or an infinity gets a label in [0, m) (0 when all its distances are NaN) and a non-finite
+ *   mind_out (NaN for a NaN; never 0); the other rows are unaffected.  agp_kmeans does not screen its input: such a row makes the
+ *   centre it lands in, and the cost, non-finite. */
 agp_status agp_nearest_center(agp_ctx* ctx, int32_t dtype, const void* x, int64_t n, int64_t ldx, int64_t D,
                               const void* centers, int64_t ldc, int64_t m, int32_t* labels_out, void* mind_out);
 agp_status agp_kmeans(agp_ctx* ctx, int32_t dtype, const void* x, int64_t n, int64_t ldx, int64_t D, void* centers,

@@ -1479,12 +1479,17 @@ def hyper_gradient_core(gp, X, gmu, gsig, rho, jitter, online=None):
 # Restated from the published algorithms; parity unpinned (no reference test pins centres: they are random).
 # --------------------------------------------------------------------------------------------
 def nearest_center(X, C):
-    """argmin_j ||x_i - c_j||^2 (ties -> smaller j) and the squared distance, in the GEMM form the device uses."""
+    """argmin_j ||x_i - c_j||^2 (ties -> smaller j) and the squared distance, from direct differences sum_d (x_id - c_jd)^2 in
+    float64, accumulated one coordinate at a time."""
     X, C = np.asarray(X, dtype=np.float64), np.asarray(C, dtype=np.float64)
-    d = np.sum(C * C, axis=1)[None, :] - 2.0 * (X @ C.T)
+    d = np.zeros((len(X), len(C)))
+    Xt, Ct = np.ascontiguousarray(X.T), np.ascontiguousarray(C.T)
+    for k in range(X.shape[1]):
+        df = Xt[k][:, None] - Ct[k][None, :]
+        df *= df
+        d += df
     lab = np.argmin(d, axis=1)
-    mind = np.maximum(np.sum(X * X, axis=1) + d[np.arange(len(X)), lab], 0.0)
-    return lab.astype(np.int32), mind
+    return lab.astype(np.int32), d[np.arange(len(X)), lab]
 
 
 def kmeans_seeding(X, nC, n_markov, rng):
