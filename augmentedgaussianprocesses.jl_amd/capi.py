@@ -159,6 +159,7 @@ SYMBOLS = {
     "agp_svgp_hyper_step_multi": (_I32, [_VP, _VP, _I32]),
     "agp_svgp_predict_multi": (_I32, [_VP, _VP, _I32, _VP, _I64, _I64, _VP, _VP, _PDBL, _PDBL, _I32]),
     "agp_svgp_predict_f": (_I32, [_VP, _VP, _I64, _I64, _VP, _VP]),
+    "agp_svgp_predict_f_grad": (_I32, [_VP, _VP, _I64, _I64, _VP, _VP, _I64]),
     "agp_svgp_predict_y": (_I32, [_VP, _VP, _I64, _I64, _VP]),
     "agp_svgp_proba_y": (_I32, [_VP, _VP, _I64, _I64, _PDBL, _PDBL, _I32, _VP, _VP]),
     "agp_nearest_center": (_I32, [_VP, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),

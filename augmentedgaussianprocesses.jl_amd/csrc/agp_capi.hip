@@ -22,6 +22,7 @@
 #include "agp_rand.h"
 #include "agp_pathwise.h"
 #include "agp_lpd.h"
+#include "agp_predgrad.h"
 // (the host layers after every kernel header, as they stood in this file: the order of the kernels in the code object is kept)
 #include "agp_ctx.h"
 #include "agp_chol_host.h"
@@ -303,6 +304,8 @@ struct SvgpBase {
   virtual agp_status predict_multi(agp_comm* cm, int what, const void* xt, int64_t ldx, int64_t nt, void* mu, void* var,
                                    const double* nodes, const double* weights, int nn) = 0;
   virtual agp_status predict_f(const void* xt, int64_t ldx, int64_t nt, void* mu, void* var) = 0;
+  // input gradients of the predictive moments ("PREDICTIVE GRADIENTS"; Svgp<T>::predict_f_grad serves every class)
+  virtual agp_status predict_f_grad(const void* xt, int64_t ldx, int64_t nt, void* dmu, void* dvar, int64_t ldg) = 0;
   virtual agp_status predict_y(const void* xt, int64_t ldx, int64_t nt, void* out) = 0;
   virtual agp_status proba_y(const void* xt, int64_t ldx, int64_t nt, const double* nodes, const double* weights,
                              int nn, void* o0, void* o1) = 0;
@@ -1132,7 +1135,7 @@ struct Svgp : SvgpBase {
     for (auto e : step_done)
       if (e) dcheck(hipEventDestroy(e), __LINE__);
     T* ps[] = {rbuf2, wbuf2, pw0, pw1, Kt, muf, varf, cbuf, theta, gamma, rbuf, wbuf, alpha, beta, gsum, alpha_save, emuf,
-               evarf, stats, Tw, Tw2, tmpv, lr_dev, Kstar, ppm, ppv, pmu, pvar, s00buf};
+               evarf, stats, Tw, Tw2, tmpv, lr_dev, Kstar, ppm, ppv, pmu, pvar, s00buf, pg_W, pg_gm, pg_gv};
     for (T* p : ps)
       if (p) dfree(p);
     T* hps[] = {hyH1, hyH2, hyH3, hy_gmu, hy_gs, hy_muf, hy_pZ, hy_dZ, hyKap, hyKnm, hy_upart, hy_pZ2};
@@ -1156,6 +1159,7 @@ struct Svgp : SvgpBase {
     double* dps[] = {gradA_dev, am_dev, av_dev};
     for (double* p : dps)
       if (p) dfree(p);
+    if (pg_part) dfree(pg_part);
     if (info_dev) dfree(info_dev);  // (infoK_dev, flags_dev point into the same block)
     if (scal_dev) dfree(scal_dev);
     if (gh_dev) dfree(gh_dev);
@@ -3846,6 +3850,99 @@ struct Svgp : SvgpBase {
         hipLaunchKernelGGL((k_predict_finish<T>), grid1(nc), dim3(256), 0, st(), nc, slices, (const T*)ppm,
                            (int)(2 * mp / TILE), (const T*)ppv, CH, (T)g.k.variance, (T)jitter,
                            (T*)mu_out + (int64_t)l * nt + s, need_var ? (T*)var_out + (int64_t)l * nt + s : (T*)nullptr);
+        LAUNCHCHK(ctx);
+      }
+    }
+    return AGP_OK;
+  }
+
+  // ---- input gradients of the predictive moments (include/agp_hip.h, "PREDICTIVE GRADIENTS"; agp_predgrad.h) ----
+  // Per chunk of 4096 points and latent: K*m (launch_kernelmatrix) and W = K*m Apred (gemm_nt) when the variances are asked for,
+  // then ONE k_predgrad that recomputes the squared distances from x and Z and contracts phi' against the differences, one workgroup
+  // per (64 points, group of inducing-point tiles), and k_predgrad_finish, which adds the groups in a fixed order.  A means-only call
+  // forms neither K*m nor W.  One routine for every class: it needs only what ensure_pred leaves (apred, Apred).  All buffers are
+  // chunk-sized and stay on the handle.
+  T* pg_W = nullptr;                     // T[4096][mp]
+  double* pg_part = nullptr;             // double[2][PG_MAXGROUPS][4096][D]: the groups' sums of one chunk, mean | variance
+  T *pg_gm = nullptr, *pg_gv = nullptr;  // multi-output: the latent gradients of one chunk, T[nl][4096][D]
+  agp_status predgrad_refused(const char* why) {
+    ctx->err = std::string("agp_svgp_predict_f_grad: ") + why;
+    return AGP_ERR_UNSUPPORTED;
+  }
+  // k_predgrad + k_predgrad_finish of one latent over nc <= 4096 points: gm / gv (nullable) rows pitched by ldo
+  template <bool VAR>
+  void predgrad_launch(const Latent& g, const T* xs, int64_t ldx, int64_t nc, T* gm, T* gv, int64_t ldo) {
+    const int dpt = D <= 4 ? 1 : (D <= 16 ? 4 : (D <= 32 ? 8 : 16));
+    const int64_t tpg = pg_tiles_per_group(m, dpt), ntile = (m + pg_ct(dpt) - 1) / pg_ct(dpt), ng = (ntile + tpg - 1) / tpg;
+    const dim3 grid((unsigned)((nc + PG_RT - 1) / PG_RT), (unsigned)ng), blk(PG_THREADS);
+#define AGP_PG_LAUNCH(DPT)                                                                                                      \
+  hipLaunchKernelGGL((k_predgrad<T, DPT, VAR>), grid, blk, 0, st(), xs, ldx, nc, (const T*)g.Z, D, m, (int)D, (const T*)g.scales, \
+                     g.k.kind, kvar(g), (const T*)g.apred, (const T*)pg_W, mp, tpg, pg_part)
+    if (dpt == 1) AGP_PG_LAUNCH(1);
+    else if (dpt == 4) AGP_PG_LAUNCH(4);
+    else if (dpt == 8) AGP_PG_LAUNCH(8);
+    else AGP_PG_LAUNCH(16);
+#undef AGP_PG_LAUNCH
+    hipLaunchKernelGGL((k_predgrad_finish<T>), grid1(nc * D), dim3(256), 0, st(), nc, (int)D, (int)ng, (const double*)pg_part,
+                       (const T*)g.scales, gm, gv, ldo);
+  }
+  agp_status predict_f_grad(const void* xt, int64_t ldx, int64_t nt, void* dmu_out, void* dvar_out, int64_t ldg) override {
+    if (desc.flags & AGP_FLAG_SAMPLED)
+      return predgrad_refused("Gibbs-sampled models (AGP_FLAG_SAMPLED) are not supported: they have no predict_f");
+    if (desc.latent_offset != 0 || mo_sharded || (lp.kind == AGP_LIK_LOGISTICSOFTMAX && desc.n_latent != desc.lik.n_class))
+      return predgrad_refused("latent-sharded handles are not supported");
+    if (bs_world > 1) return predgrad_refused("batch-sharded handles are not supported");
+    for (auto& g : lat)
+      if (g.k.kind == AGP_K_EXPONENTIAL)
+        return predgrad_refused("ExponentialKernel is not differentiable at zero distance");
+    if (D > PG_MAXD) return predgrad_refused("the input dimension D must be at most 64 (the hyper-gradient's limit)");
+    if (nt < 0 || ldx < D || ldg < D || (nt > 0 && (!xt || !dmu_out))) {
+      ctx->err = "agp_svgp_predict_f_grad: n_t >= 0, xt and dmu_out must not be NULL, ldx >= D, ldg >= D";
+      return AGP_ERR_INVALID;
+    }
+    if (nt == 0) return AGP_OK;
+    const bool need_var = dvar_out != nullptr;
+    const int64_t CH = PG_CH;
+    for (auto& g : lat) AGPCHK(params_to_host(g));
+    if (!pg_part) AGPCHK(dmalloc(ctx, &pg_part, 2 * (int64_t)PG_MAXGROUPS * CH * D));
+    if (need_var) {
+      AGPCHK(ensure_pred_ws(0, true));
+      if (!pg_W) AGPCHK(dmalloc(ctx, &pg_W, CH * mp));
+    }
+    if (mo) {
+      if (!pg_gm) AGPCHK(dmalloc(ctx, &pg_gm, (int64_t)nl * CH * D));
+      if (need_var && !pg_gv) AGPCHK(dmalloc(ctx, &pg_gv, (int64_t)nl * CH * D));
+    }
+    for (auto& g : lat) {
+      AGPCHK(ensure_pred(g, need_var));
+      if (need_var) AGPCHK(ensure_zsc(g));
+    }
+    for (int64_t s = 0; s < nt; s += CH) {
+      const int64_t nc = (nt - s) < CH ? (nt - s) : CH;
+      const int64_t nq = rup64(nc);
+      const T* xs = (const T*)xt + s * ldx;
+      for (int l = 0; l < nl; ++l) {
+        Latent& g = lat[l];
+        if (need_var) {
+          (void)launch_kernelmatrix<T>(ctx, st(), xs, ldx, (const int64_t*)nullptr, nc, (const T*)g.Z, D, m, D, (const T*)g.scales,
+                                       g.k.kind, kvar(g), Kstar, mp, nq, mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0,
+                                       (const T*)g.Zsc, (const T*)g.zn);
+          LAUNCHCHK(ctx);
+          AGPCHK((gemm_nt<T, EPI_STORE>(ctx, Kstar, mp, g.Apred, mp, nq, mp, mp, 0, pg_W, mp, nullptr, 0, nullptr, nullptr, nullptr,
+                                        0)));
+        }
+        T* gm = mo ? pg_gm + (int64_t)l * CH * D : (T*)dmu_out + ((int64_t)l * nt + s) * ldg;
+        T* gv = !need_var ? (T*)nullptr : (mo ? pg_gv + (int64_t)l * CH * D : (T*)dvar_out + ((int64_t)l * nt + s) * ldg);
+        if (need_var) predgrad_launch<true>(g, xs, ldx, nc, gm, gv, mo ? D : ldg);
+        else predgrad_launch<false>(g, xs, ldx, nc, gm, gv, mo ? D : ldg);
+        LAUNCHCHK(ctx);
+      }
+      if (mo) {  // the mixed outputs, as predict_f returns them (predictions.jl:52-92)
+        hipLaunchKernelGGL((k_predgrad_mix<T>), grid1(nc * D), dim3(256), 0, st(), nc, (int)D, nl, nT, (const T*)A_dev, Qa(),
+                           (const T*)pg_gm, CH, (T*)dmu_out + s * ldg, ldg, nt * ldg, 0);
+        if (need_var)
+          hipLaunchKernelGGL((k_predgrad_mix<T>), grid1(nc * D), dim3(256), 0, st(), nc, (int)D, nl, nT, (const T*)A_dev, Qa(),
+                             (const T*)pg_gv, CH, (T*)dvar_out + s * ldg, ldg, nt * ldg, 1);
         LAUNCHCHK(ctx);
       }
     }
@@ -6786,6 +6883,11 @@ agp_status agp_svgp_predict_f(agp_svgp* h, const void* xt, int64_t ldx, int64_t 
   HCHKF(h);
   if (n_t == 0) return AGP_OK;  // no test points: nothing to write (the reference returns empty arrays)
   return h->impl->predict_f(xt, ldx, n_t, mu_out, var_out);
+}
+agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* dmu_out, void* dvar_out,
+                                   int64_t ldg) {
+  HCHKF(h);
+  return h->impl->predict_f_grad(xt, ldx, n_t, dmu_out, dvar_out, ldg);
 }
 agp_status agp_svgp_predict_y(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* y_out) {
   HCHKF(h);

@@ -424,7 +424,9 @@ agp_status agp_svgp_step_local(agp_svgp* h, const void* x, int64_t ldx, const vo
  * kernel must be SqExponential, Matern32 or Matern52 (the ExponentialKernel is not differentiable at zero distance).  Otherwise
  * both return AGP_ERR_UNSUPPORTED with the reason in agp_last_error, before anything is launched: dvariance_host, dscale_host and
  * dZ are not touched, and the handle goes on taking steps and predicting.  Steps, ELBO and
- * predictions themselves have no such limit on D.  Pinned at D = 1, 31, 32, 33, 64 and 65 by tests/test_gpu_hyper_edges.py. */
+ * predictions themselves have no such limit on D.  Pinned at D = 1, 31, 32, 33, 64 and 65 by tests/test_gpu_hyper_edges.py.
+ * agp_svgp_predict_f_grad ("PREDICTIVE GRADIENTS" below) differentiates the same kernels with respect to the input and has the same
+ * two limits, refused the same way. */
 agp_status agp_svgp_hyper_configure(agp_svgp* h, int32_t opt_kernel, double kernel_eta, int32_t opt_Z, double z_eta,
                                     double adam_b1, double adam_b2, double adam_eps);
 /*   hyper_rule      : which Optimisers.jl rule `optimiser` / `Zoptimiser` are (the reference hands whatever rule it is given to
@@ -663,6 +665,44 @@ agp_status agp_svgp_predict_f(agp_svgp* h, const void* xt, int64_t ldx, int64_t 
  * cov_out T[n_task][n_t][n_t] = sum_q A[t][q]^2 cov_q.  K*m IS materialised here (n_t x m), so n_t <= 8192 (AGP_ERR_INVALID
  * beyond). */
 agp_status agp_svgp_predict_f_cov(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* mu_out, void* cov_out);
+
+/* ---- PREDICTIVE GRADIENTS (how the prediction changes with the input, over any number of test points) ---------------------------
+ * d mu(x*) / d x* and d sigma^2(x*) / d x* of exactly the moments agp_svgp_predict_f returns (no counterpart in the reference):
+ * what gradient ascent on an acquisition function, sensitivity analysis and mode finding need, without 2 D finite-difference
+ * predictions per point and without the digits those lose on a variance that already cancels.  Per latent, with s the per-dimension
+ * scales (ScaleTransform: s_d = s; ARDTransform: s_d = v_d), q_j = sum_d s_d^2 (x_d - z_jd)^2, r_j = sqrt(q_j), v the kernel variance,
+ * a = K^-1 mu and A = K^-1 - K^-1 Sigma K^-1 the two objects predict_f uses (exact GP: a = alpha, A = Sigma_y^-1), k* = k(x, Z):
+ *   c_j           = v phi'(q_j)                              the derivative of the base function in q = r^2
+ *   d mu  / d x_d =  2 s_d^2 sum_j a_j        c_j (x_d - z_jd)
+ *   d var / d x_d = -4 s_d^2 sum_j (A k*')_j  c_j (x_d - z_jd)      (k** + jitter is constant in x)
+ *   SqExponential phi'(q) = -1/2 e^(-q/2);  Matern32 phi'(q) = -(3/2) e^(-sqrt(3) r);  Matern52 phi'(q) = -(5/6)(1 + sqrt(5) r) e^(-sqrt(5) r)
+ * All three are finite at r = 0 and nothing divides by r: a test point that coincides with an inducing point is an ordinary input
+ * and that j contributes exactly 0.  The prediction has no prior-mean term in x (predict_f adds none), so neither has the gradient.
+ *
+ * Outputs: dmu_out, dvar_out (nullable: means only) device T[n_latent][n_t][ldg], ldg >= D in elements; the "Layout" section above
+ * holds (ldx >= D, padding never read or written).  A multi-output handle returns the MIXED outputs, as predict_f does:
+ * T[n_task][n_t][ldg], d mu_t = sum_q A[t][q] d mu_q, d var_t = sum_q A[t][q]^2 d var_q.
+ *
+ * How.  Streamed in chunks of 4096 points: K*m (the predictor's kernel-matrix launch) and W = K*m A (one GEMM) when the variances are
+ * asked for -- a means-only call forms neither --, then ONE kernel that recomputes q from x and Z by direct differences in ascending
+ * d, evaluates c, and contracts a_j c_ij resp. W_ij c_ij against the differences over inducing-point tiles staged through LDS.
+ * Double accumulation for both dtypes.  The order of every sum is fixed by (m, D) alone and there are no floating-point atomics: two
+ * calls on the same inputs return the same bits.  The workspace is chunk-sized and kept on the handle; nothing grows with n_t.
+ *
+ * No side effects.  The call completes a pending natural-gradient step first, as every entry point does; after that it uses the
+ * predictor's workspace and caches, like agp_svgp_predict_f, and buffers of its own -- the posterior, local variables,
+ * agp_svgp_elbo_terms and the status word stay bitwise unchanged.  Asynchronous on the context's stream.
+ *
+ * Accepted: every single-GPU handle whose agp_svgp_predict_f works -- sparse AnalyticVI / AnalyticSVI (AGP_F64 and AGP_F32), online,
+ * AGP_FLAG_FULL, AGP_FLAG_EXACT, AGP_FLAG_NUMERICAL with or without AGP_FLAG_MC, multi-latent (LogisticSoftMax, Heteroscedastic) and
+ * multi-output handles.  Refused with AGP_ERR_UNSUPPORTED, by name in agp_last_error, before anything is launched and with the
+ * outputs untouched (the handle goes on predicting): AGP_FLAG_SAMPLED; latent-sharded and batch-sharded handles; the
+ * ExponentialKernel (not differentiable at zero distance); D > 64 -- the limit of agp_svgp_hypergrad above, for the same reason: the
+ * kernel keeps a point's D coordinates and 2 D accumulators in registers across the four waves of a workgroup and stages D-wide
+ * tiles in LDS, sized for HB_MAXD.  n_t = 0 is a successful no-op (pointers are then not looked at).  n_t < 0, ldx < D, ldg < D, or
+ * (n_t > 0) a NULL xt or dmu_out: AGP_ERR_INVALID, outputs untouched. */
+agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* dmu_out,
+                                   void* dvar_out /* nullable */, int64_t ldg);
 /* predict_y  predictions.jl:178-198 : regression (Gaussian, StudentT, Laplace, Heteroscedastic) -> T[n_t] mean ;
  * logistic / BayesianSVM -> int32[n_t] (mu_f > 0) ; Poisson / NegBinomial -> T[n_t] expected count (predictions.jl:211) ;
  * LogisticSoftMax -> int32[n_t] argmax_k mu_f,k (0-based LOCAL latent index + latent_offset) */

@@ -26,6 +26,7 @@
 #   ELBO(model, X, y; streamed=true)                          the same over any number of points                   -> agp_svgp_elbo_stream
 #   log_predictive_density(model, X, y) (no counterpart: the held-out log-likelihood / NLPD)           -> agp_svgp_lpd_stream, agp_log_predictive
 #   _predict_f / predict_y / proba_y                          src/training/predictions.jl:25-92,178-247 -> agp_svgp_predict_f / _predict_y / _proba_y
+#   predict_f_grad(model, X_test) (no counterpart: d mu / d x*, d sigma^2 / d x* of predict_f)          -> agp_svgp_predict_f_grad
 #   init_state                                                src/training/states.jl:1-9               -> agp_svgp_init_state
 # Multi-GPU (one Julia process per GPU, e.g. under MPI.jl or Distributed): agp_comm_* binds RCCL inside the library; the host only
 # ships the 128-byte id from rank 0 to the others (section "multi-GPU" below).
@@ -769,6 +770,29 @@ function predict_f(hm::HipModel{T}, X_test::AbstractMatrix, state=nothing; cov::
     return cov ? (μt, Tuple(v[:, l] for l in 1:n)) : μt
 end
 
+# ---- input gradients of the predictive moments (include/agp_hip.h, "PREDICTIVE GRADIENTS"; no counterpart in the reference) -----------
+# predict_f_grad(hm, X_test; cov=true): (dμ, dσ²), n_t x D matrices with dμ[i, d] = ∂μ(x_i)/∂x_id of what predict_f returns (dμ alone
+# with cov=false); Tuples over the latents / tasks where predict_f returns Tuples.  SqExponential / Matern32 / Matern52 kernels,
+# D <= 64; the library refuses Gibbs-sampled and sharded handles, the ExponentialKernel and D > 64 by name.
+function predict_f_grad(hm::HipModel{T}, X_test::AbstractMatrix; cov::Bool=true, obsdim::Int=1) where {T}
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    Xd = ROCArray{T}(obsdim == 1 ? permutedims(X_test) : X_test)
+    D, nt = size(Xd)
+    nout = is_mo(hm) ? length(AGP.likelihood(hm.model)) : nlat(hm)
+    gm = ROCArray{T}(undef, D, nt, nout)                     # column-major D x n_t x n_out == the ABI's T[n_out][n_t][ldg = D]
+    gv = cov ? ROCArray{T}(undef, D, nt, nout) : nothing
+    check(hm.ctx, ccall((:agp_svgp_predict_f_grad, libagp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+                        hm.h, pointer(Xd), D, nt, pointer(gm), cov ? pointer(gv) : C_NULL, D))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    gmh = Array(gm)
+    gvh = cov ? Array(gv) : nothing
+    if nout == 1 && !is_mo(hm)
+        return cov ? (permutedims(gmh[:, :, 1]), permutedims(gvh[:, :, 1])) : permutedims(gmh[:, :, 1])
+    end
+    mt = Tuple(permutedims(gmh[:, :, l]) for l in 1:nout)
+    return cov ? (mt, Tuple(permutedims(gvh[:, :, l]) for l in 1:nout)) : mt
+end
+
 # predict_y predictions.jl:178-198: regression mean / Bool / most likely class label / expected count
 function predict_y(hm::HipModel{T}, X_test::AbstractMatrix, state=nothing; obsdim::Int=1) where {T}
     ensure_handle!(hm, max(hm.maxbatch, 1))
@@ -1059,6 +1083,7 @@ function train!(ho::HipOnlineModel{T}, X::AbstractMatrix, y::AbstractArray, stat
     return ho, new
 end
 predict_f(ho::HipOnlineModel, Xt::AbstractMatrix, state=nothing; kw...) = predict_f(ho.cur, Xt; kw...)
+predict_f_grad(ho::HipOnlineModel, Xt::AbstractMatrix; kw...) = predict_f_grad(ho.cur, Xt; kw...)
 predict_y(ho::HipOnlineModel, Xt::AbstractMatrix, state=nothing; kw...) = predict_y(ho.cur, Xt; kw...)
 proba_y(ho::HipOnlineModel, Xt::AbstractMatrix, state=nothing; kw...) = proba_y(ho.cur, Xt; kw...)
 objective(ho::HipOnlineModel, state=nothing, y=nothing) = objective(ho.cur)   # incl. −extraKL (KLdivergences.jl:30-54)
