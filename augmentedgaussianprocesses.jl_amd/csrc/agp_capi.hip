@@ -2649,9 +2649,6 @@ struct Svgp : SvgpBase {
         int lo = 0, hi = 0;
         HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
         int pr = nl > 1 ? hi : lo;
-#ifdef AGP_DEV_KNOBS  // (development builds: A/B of the look-ahead's priority, round 6 -- C3 experiment)
-        if (const char* e = getenv("AGP_DEV_PF_PRIO")) pr = e[0] == 'h' ? hi : e[0] == 'n' ? 0 : lo;
-#endif
         HIPCHK(ctx, hipStreamCreateWithPriority(&pf_stream, hipStreamNonBlocking, pr));
       }
       HIPCHK(ctx, hipEventCreateWithFlags(&pf_done, hipEventDisableTiming));
@@ -6458,28 +6455,12 @@ agp_status agp_dev_dag_retries(agp_ctx* ctx, int64_t* n) {
 
 agp_status agp_dev_diag_bench(agp_ctx* ctx, int32_t dtype, int32_t variant, int32_t blocks, int32_t reps, double* us) {
   if (!ctx || !us) return AGP_ERR_INVALID;
+  const bool f64 = dtype == AGP_F64;
+  if (variant != 1 && !(variant == 13 && f64)) return AGP_ERR_INVALID;  // nothing allocated, nothing launched
   DevGuard guard(ctx->device);
-  switch (variant * 2 + (dtype == AGP_F64 ? 0 : 1)) {
-    case 0: return bb_diag_bench<double, 0>(ctx, blocks, reps, us);
-    case 1: return bb_diag_bench<float, 0>(ctx, blocks, reps, us);
-    case 2: return bb_diag_bench<double, 1>(ctx, blocks, reps, us);
-    case 3: return bb_diag_bench<float, 1>(ctx, blocks, reps, us);
-    case 4: return bb_diag_bench<double, 2>(ctx, blocks, reps, us);
-    case 5: return bb_diag_bench<float, 2>(ctx, blocks, reps, us);
-    case 6: return bb_diag_bench<double, 3>(ctx, blocks, reps, us);  // timing experiments (residual check fails by design)
-    case 8: return bb_diag_bench<double, 4>(ctx, blocks, reps, us);
-    case 10: return bb_diag_bench<double, 5>(ctx, blocks, reps, us);
-    case 12: return bb_diag_bench<double, 6>(ctx, blocks, reps, us);
-    case 14: return bb_diag_bench<double, 7>(ctx, blocks, reps, us);
-    case 16: return bb_diag_bench<double, 8>(ctx, blocks, reps, us);
-    case 17: return bb_diag_bench<float, 8>(ctx, blocks, reps, us);
-    case 18: return bb_diag_bench<double, 9>(ctx, blocks, reps, us);
-    case 20: return bb_diag_bench<double, 10>(ctx, blocks, reps, us);
-    case 22: return bb_diag_bench<double, 11>(ctx, blocks, reps, us);
-    case 24: return bb_diag_bench<double, 12>(ctx, blocks, reps, us);
-    case 26: return bb_diag_bench<double, 13>(ctx, blocks, reps, us);  // 2-level without the off-diagonal block of the inverse
-    default: return AGP_ERR_INVALID;
-  }
+  if (!f64) return bb_diag_bench<float, 1>(ctx, blocks, reps, us);
+  return variant == 1 ? bb_diag_bench<double, 1>(ctx, blocks, reps, us)    // 2-level, full inverse: k_chol_step, k_chol_safe
+                      : bb_diag_bench<double, 13>(ctx, blocks, reps, us);  // 2-level without X21: the chain of k_chol_dag
 }
 
 agp_status agp_svgp_create(agp_ctx* ctx, const agp_svgp_desc* desc, agp_svgp** out) {

@@ -244,8 +244,8 @@ __global__ void k_scale_rows(const T* __restrict__ Y, int64_t ldy, int64_t p, in
 // (SPEC 3 keeps the symmetric / diagonal logic and spilled 14 registers under the 128-VGPR cap; a K_ZZ launch is one workgroup per CU
 //  anyway, so it is compiled for two.  Round 5: the same for the general form SPEC 0 -- set-up launches, the ABI's agp_kernelmatrix,
 //  full predictive covariances --, whose fp64 instantiations carried 160 - 188 bytes of scratch per lane under that cap.
-//  Round 6: the fp64 forms of the first-order kernels keep eight column slots per lane in the 4x4x4 accumulator layout and spilled 12
-//  bytes under the 128-VGPR cap: three workgroups per CU for them)
+//  Round 6: three workgroups per CU for the fp64 forms of the first-order kernels.  The bound dates from the 4x4x4 MFMA form's
+//  accumulator layout (removed, see agp_device.h), which spilled 12 bytes under the 128-VGPR cap; four was not measured again since)
 template <typename T, int KIND, int SPEC = 0>
 __global__ __launch_bounds__(NTHREADS, ((SPEC == 3 || SPEC == 0) ? 2 : (sizeof(T) == 8 && KIND != K_SQEXP) ? 3 : 4)) void k_kernelmatrix_mma(const T* __restrict__ X, int64_t ldx,
                                                                const int64_t* __restrict__ idx, int64_t n,
@@ -256,7 +256,6 @@ __global__ __launch_bounds__(NTHREADS, ((SPEC == 3 || SPEC == 0) ? 2 : (sizeof(T
                                                                const T* __restrict__ alpha_, T* __restrict__ part,
                                                                int64_t ldp, int64_t ctiles) {
   if (variance < T(0)) variance = scales[D];  // device-resident kernel parameters (see k_kernelmatrix)
-  constexpr bool L4 = use_mfma4<T>();  // (AGP_F64_MFMA4 builds) fp64: 4x4x4 MFMA form and its accumulator layout (see the epilogue)
   T* __restrict__ out = SPEC == 1 ? nullptr : out_;
   const int sym = SPEC == 3 ? 1 : SPEC != 0 ? 0 : sym_;  // SPEC 3 (round 4): K_ZZ of a refresh -- store only, symmetric, no row-dot
   const T* __restrict__ alpha = (SPEC == 2 || SPEC == 3) ? nullptr : alpha_;
@@ -359,42 +358,31 @@ __global__ __launch_bounds__(NTHREADS, ((SPEC == 3 || SPEC == 0) ? 2 : (sizeof(T
     for (int kk = 0; kk < Dp / 4; ++kk) {
       const T a0 = pa[kk * 4], a1 = pa[16 * LDX + kk * 4];
       const T b0 = pb[kk * 4], b1 = pb[16 * LDX + kk * 4];
-      if constexpr (L4) {  // fp64: the 4-block 4x4x4 MFMA (agp_device.h, mma_slab): same operand registers, B rotated block-wise
-        const double b01 = dpp_ror<12>(b0), b02 = dpp_ror<8>(b0), b03 = dpp_ror<4>(b0);
-        const double b11 = dpp_ror<12>(b1), b12 = dpp_ror<8>(b1), b13 = dpp_ror<4>(b1);
-        acc[0][0] = mma4x4(a0, b0, b01, b02, b03, acc[0][0]);
-        acc[0][1] = mma4x4(a0, b1, b11, b12, b13, acc[0][1]);
-        acc[1][0] = mma4x4(a1, b0, b01, b02, b03, acc[1][0]);
-        acc[1][1] = mma4x4(a1, b1, b11, b12, b13, acc[1][1]);
-      } else {
-        acc[0][0] = Mfma<T>::mma(a0, b0, acc[0][0]);
-        acc[0][1] = Mfma<T>::mma(a0, b1, acc[0][1]);
-        acc[1][0] = Mfma<T>::mma(a1, b0, acc[1][0]);
-        acc[1][1] = Mfma<T>::mma(a1, b1, acc[1][1]);
-      }
+      acc[0][0] = Mfma<T>::mma(a0, b0, acc[0][0]);
+      acc[0][1] = Mfma<T>::mma(a0, b1, acc[0][1]);
+      acc[1][0] = Mfma<T>::mma(a1, b0, acc[1][0]);
+      acc[1][1] = Mfma<T>::mma(a1, b1, acc[1][1]);
     }
     // epilogue.  Everything that depends on the column only or on the row only is taken out of the element loop: PMC showed ~96 VALU
     // instructions per kernel value with the bounds checks, the 64-bit index arithmetic and the alpha loads inside it -- the VALU,
     // not the MFMA or the exp, bounded the streaming predictor.
-    // Accumulator layouts: element r of acc[mi][ni] is (row rowof(mi, r), column colof(ni, r)) of the 64 x 64 tile.  fp32 (16x16x4):
-    // four rows, one column per lane; fp64 (4x4x4, round 6): ONE row, four columns per lane (NQ = 4 column slots per ni).
-    constexpr int NQ = L4 ? 4 : 1;
-    auto rowof = [&](int mi, int r) { return wm * 32 + mi * 16 + (L4 ? g4_row(lane) : Mfma<T>::row(lane, r)); };
-    auto colof = [&](int ni, int q) { return wn * 32 + ni * 16 + (L4 ? g4_col(lane, q) : (lane & 15)); };
-    int cl_[2][NQ];
-    bool cok[2][NQ], cout_[2][NQ];
-    T ynv[2][NQ], al[2][NQ];
+    // Accumulator layout: element r of acc[mi][ni] is (row rowof(mi, r), column colof(ni)) of the 64 x 64 tile: four rows, one column
+    // per lane.
+    auto rowof = [&](int mi, int r) { return wm * 32 + mi * 16 + Mfma<T>::row(lane, r); };
+    auto colof = [&](int ni) { return wn * 32 + ni * 16 + (lane & 15); };
+    int cl_[2];
+    bool cok[2], cout_[2];
+    T ynv[2], al[2];
 #pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        cl_[ni][q] = colof(ni, q);
-        const int64_t gj = j0 + cl_[ni][q];
-        cok[ni][q] = gj < p;
-        cout_[ni][q] = out != nullptr && gj < p_out;
-        ynv[ni][q] = ynb[cl_[ni][q]];
-        al[ni][q] = (alpha != nullptr && cok[ni][q]) ? alpha[gj] : T(0);
-      }
+    for (int ni = 0; ni < 2; ++ni) {
+      const int cl = colof(ni);
+      const int64_t gj = j0 + cl;
+      cl_[ni] = cl;
+      cok[ni] = gj < p;
+      cout_[ni] = out != nullptr && gj < p_out;
+      ynv[ni] = ynb[cl];
+      al[ni] = (alpha != nullptr && cok[ni]) ? alpha[gj] : T(0);
+    }
     if constexpr (SPEC == 1 && KIND == K_SQEXP && sizeof(T) == 8) {
       // Streaming prediction with the squared-exponential kernel in fp64 (round 6): branch-free, 21 VALU instructions per kernel value
       // (s2, d2, two clamps, the 17 of exp_mhalf, the row-dot FMA) where the general form below spends ~48 and a branch.  No masks:
@@ -403,19 +391,17 @@ __global__ __launch_bounds__(NTHREADS, ((SPEC == 3 || SPEC == 0) ? 2 : (sizeof(T
       // this kernel function turns into HALF that as a relative error of its value -- it is the first-order kernels below (sqrt at
       // d2 -> 0) that need the repair.  The variance is folded into alpha.
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) al[ni][q] *= variance;
+      for (int ni = 0; ni < 2; ++ni) al[ni] *= variance;
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const T xnv = xn[rowof(mi, r)];  // (4x4x4 layout: the same row for every r)
-          const int q = L4 ? r : 0;
+          const int rl = rowof(mi, r);
+          const T xnv = xn[rl];
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni) {
-            const T d2 = __builtin_fma(T(-2), acc[mi][ni][r], xnv + ynv[ni][q]);
-            rs[mi][L4 ? 0 : r] = __builtin_fma(exp_mhalf(d2), al[ni][q], rs[mi][L4 ? 0 : r]);
+            const T d2 = __builtin_fma(T(-2), acc[mi][ni][r], xnv + ynv[ni]);
+            rs[mi][r] = __builtin_fma(exp_mhalf(d2), al[ni], rs[mi][r]);
           }
         }
       continue;
@@ -426,18 +412,17 @@ __global__ __launch_bounds__(NTHREADS, ((SPEC == 3 || SPEC == 0) ? 2 : (sizeof(T
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int rl = rowof(mi, r);
-        const int q = L4 ? r : 0;
         const int64_t gi = i0 + rl;
         const bool rok = gi < n, rout = gi < n_out;
         const T xnv = xn[rl];
         T* orow = out ? out + gi * ldo + j0 : nullptr;
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-          const int cl = cl_[ni][q];
+          const int cl = cl_[ni];
           const bool diag = sym && (int64_t)(rl - cl) == dgi;
           T val = T(0);
-          if (rok && cok[ni][q]) {
-            const T s2 = xnv + ynv[ni][q];
+          if (rok && cok[ni]) {
+            const T s2 = xnv + ynv[ni];
             T d2 = s2 - T(2) * acc[mi][ni][r];
             if (diag) {
               // the point against itself: the direct differences below would give exactly 0 -- but through a 32-deep rolled loop that
@@ -458,29 +443,19 @@ __global__ __launch_bounds__(NTHREADS, ((SPEC == 3 || SPEC == 0) ? 2 : (sizeof(T
           } else if (diag) {
             val = T(1);
           }
-          if (cout_[ni][q] && rout) orow[cl] = val;
-          rs[mi][L4 ? 0 : r] += val * al[ni][q];
+          if (cout_[ni] && rout) orow[cl] = val;
+          rs[mi][r] += val * al[ni];
         }
       }
   }
   if (alpha) {
-    if constexpr (L4) {  // one row per lane and mi: the four lanes that share it differ in lane & 3
 #pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-        T sv = rs[mi][0];
-        sv += __shfl_xor(sv, 1);
-        sv += __shfl_xor(sv, 2);
-        if ((lane & 3) == 0) red[wn * TILE + wm * 32 + mi * 16 + g4_row(lane)] = sv;
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const T sv = row16_sum(rs[mi][r]);
+        if ((lane & 15) == 0) red[wn * TILE + wm * 32 + mi * 16 + Mfma<T>::row(lane, r)] = sv;
       }
-    } else {
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const T sv = row16_sum(rs[mi][r]);
-          if ((lane & 15) == 0) red[wn * TILE + wm * 32 + mi * 16 + Mfma<T>::row(lane, r)] = sv;
-        }
-    }
     __syncthreads();
     if (tid < TILE && i0 + tid < n_out) part[blockIdx.x * ldp + i0 + tid] = red[tid] + red[TILE + tid];
   }

@@ -17,8 +17,8 @@
 // dependent f64 op ~25 cycles, v_rcp_f64 + one Newton step 1.8e-15 accurate):
 //   * FOUR columns per round (16 rounds, one barrier each): owners publish the 4 raw panel columns and the 4 M rows;
 //   * every thread of waves 0-3 redundantly LDL'-factors the 4x4 pivot block, transforms the panel entries it needs and
-//     applies the rank-4 update to its cyclic 4x4 sub-blocks of A and of M; triangular skipping is compile-time per
-//     16-column group.
+//     applies the rank-4 update to its cyclic 2x2 sub-blocks of A and of M (the tile is eliminated as two 32x32 blocks,
+//     factor_diag_tile_2lvl); triangular skipping is compile-time per 16-column group.
 #pragma once
 #include "agp_cavi.h"  // LikParams, rowstats_finish: the CAVI step's task-graph launch finishes its rows itself (EpiArgs)
 #include "agp_device.h"
@@ -26,9 +26,6 @@
 namespace agp {
 
 constexpr int LDP = TILE + 2;   // 66: [r][k] stride for 64-deep LDS tiles (conflict-free MFMA fragment reads)
-#ifndef AGP_PIVOT_ALG
-#define AGP_PIVOT_ALG 0  // how the 4x4 pivot blocks of the tile factorisation are factored (see chol_rounds)
-#endif
 constexpr int CHOL_THREADS = 512;
 
 __device__ __forceinline__ double rcp1(double p) {
@@ -143,9 +140,11 @@ __device__ __forceinline__ void mma_lds64(const T* As, const T* Bs, Acc<T>& acc)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Diagonal-tile factorisation.  Waves 0-3 (256 threads, cyclic 4x4 ownership: R = ti + 16 r, C = tj + 16 c) hold BOTH
-// the A sub-blocks and the sub-blocks of the running inverse M; waves 4-7 of the 512-thread workgroup only join the
-// barriers (they exist for the MFMA products around the factorisation).  Per round of 4 columns, with ONE barrier:
+// Diagonal-tile factorisation: the elimination rounds of one 32x32 block (elim_block32; the 64x64 tile is two such blocks and
+// MFMA glue, factor_diag_tile_2lvl).  Waves 0-3 (256 threads, cyclic 2x2 ownership inside the block: thread (ti, tj) owns
+// R = ti + 16 r, C = tj + 16 c, r, c = 0, 1) hold BOTH the A sub-blocks and the sub-blocks of the running inverse M; waves 4-7 of
+// the 512-thread workgroup only join the barriers (they exist for the MFMA products around the factorisation, and step the hook).
+// chol_rounds<J> runs the four rounds of the block's 16-column group J.  Per round of 4 columns, with ONE barrier:
 //   owners publish the 4 raw panel columns + the 4 M rows; every active thread redundantly LDL'-factors the 4x4 pivot
 //   block, transforms the panel entries of its own rows / columns / M columns, and applies the rank-4 update.
 // (Measured alternatives, tools/bench_diag.py, f64 us per tile: one column per barrier 20-21; this scheme 14.5; pivot
@@ -180,11 +179,9 @@ struct NoHook {
   __device__ __forceinline__ void half(int) const {}
 };
 
-// PIV selects how the 4x4 pivot block is factored (identical results up to rounding):
-//   0  LDL' column by column: every reciprocal waits for the previous column's update (dependent depth ~22 operations)
-//   1  fraction-free (Bareiss) minors: n_ij = d00 d_ij - d_i0 d_j0, p_ij = (n11 n_ij - n_i1 n_j1) / d00, M4 = (p22 p33 - p32^2) / n11
-//      are the leading-minor numerators of the same elimination, so the four reciprocals 1/d00, 1/M2, 1/M3, 1/M4 no longer wait
-//      for one another's multipliers (depth ~13); pivots = M_q / M_(q-1), multipliers l21 = n21 / M2, l32 = p32 / M3, ...
+// The 4x4 pivot block is factored by LDL' column by column: every reciprocal waits for the previous column's update (dependent
+// depth ~22 operations).  (Measured alternative, docs/DESIGN_LOG.md 19: fraction-free Bareiss minors, whose four reciprocals do not wait
+// for one another's multipliers (depth ~13), 12.7 against 12.2 us per tile and 0.402 against 0.393 ms per step -- removed.)
 // Where a round issues its LDS reads (round 9; none of them depends on the LDL' result, and the CU's one LDS pipe serves four
 // waves): the pivot block, its first row first (LDS returns in order and the chain starts with d00) ; 1 / d00 ; my panel columns ;
 // 1 / d11 ; my M columns and my panel rows -- all into registers, so that the rest of the LDL' chain runs under them.  The
@@ -192,10 +189,11 @@ struct NoHook {
 // burst in front of it, a wave's pivot block queues behind the other waves' panel reads).  The four pivots go to piv[] at the END
 // of the round body (they are read after the barrier that follows the rounds): an LDS store between the chain and the transforms
 // keeps every later LDS read behind it.
-template <typename T, int J, int NS, typename H, int PIV = 0>
-__device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* __restrict__ sc, T* __restrict__ piv,
+template <typename T, int J, typename H>
+__device__ __forceinline__ void chol_rounds(T (&a)[2][2], T (&g)[2][2], T* __restrict__ sc, T* __restrict__ piv,
                                             const bool act, const int ti, const int tj, H& hook) {
-  constexpr int HB = NS == 2 ? 4 * J : 0;  // hook rounds: 0..7 over the two 16-column groups of a 32-block (elim_block32)
+  constexpr int NS = 2;      // 16-column groups of a 32-block
+  constexpr int HB = 4 * J;  // hook rounds: 0..7 over the two 16-column groups of a 32-block (elim_block32)
   // fp64: pb = where this round's pivot block starts in sc, in units of 8 elements ((rr & 1) * 4 * TILE + round_sc(0, j0), always a
   // multiple of 8, so the reads' 16-byte alignment stays known).  It is carried through the loop in a register and stepped by one
   // instruction (v_xad_u32: toggle the buffer, advance four columns), and the empty asm keeps the compiler from rebuilding it from
@@ -217,7 +215,7 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
       Pp = sc + 8 * pb;
       pb = (pb ^ (4 * TILE / 8)) + round_sc<T>(0, 4) / 8;
     }
-    if (act && PIV != 4) {  // (PIV 4, 5: timing experiments -- barrier only / publish + barrier only)
+    if (act) {
       // jj0 is a multiple of 4: the owners of this round's panel columns have tj >> 2 == rr and own column tj & 3 of it (M rows: ti) ;
       // fp64 says so, which leaves their store addresses loop-invariant up to the buffer toggle.  The two forms select the same
       // threads; fp32 keeps the older one only so that its kernels stay the instruction sequence that C3 was measured with (see
@@ -239,17 +237,13 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
     __syncthreads();
     hook.template half<HB>(rr);
     if (!act) continue;
-    if (PIV == 4 || PIV == 5) continue;
     // ---- every LDS read of the round: the 4x4 pivot block first, then my panel columns, my M columns, my panel rows ----
     const T d00 = Pp[round_sc<T>(0, 0)], d10 = Pp[round_sc<T>(0, 1)], d20 = Pp[round_sc<T>(0, 2)], d30 = Pp[round_sc<T>(0, 3)];
     __builtin_amdgcn_sched_barrier(0);
     T d11 = Pp[round_sc<T>(1, 1)], d21 = Pp[round_sc<T>(1, 2)], d31 = Pp[round_sc<T>(1, 3)];
     T d22 = Pp[round_sc<T>(2, 2)], d32 = Pp[round_sc<T>(2, 3)], d33 = Pp[round_sc<T>(3, 3)];
-    T r0, r1, r2, r3, l10, l20, l30, l21, l31, l32;
-    if (PIV != 2) {
-      __builtin_amdgcn_sched_barrier(0);
-      r0 = rcp1(d00);
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    const T r0 = rcp1(d00);
     __builtin_amdgcn_sched_barrier(0);
     T u[4][NS], mw[4][NS], w[4][NS];  // [q][c] ; [q][c] ; [q][r]
     auto ld_u = [&] {
@@ -268,78 +262,28 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
 #pragma unroll
         for (int q = 0; q < 4; ++q) w[q][r] = P[round_sc<T>(q, ti + 16 * r)];
     };
-    constexpr bool SPLIT = PIV == 0;  // (the timing variants and the minors read everything here)
-    if (PIV != 3) {
-      ld_u();
-      if (!SPLIT) ld_mw();
-    }
+    ld_u();
     __builtin_amdgcn_sched_barrier(0);
     // ---- 4x4 pivot block, LDL' (every active thread, redundantly) ----
-    if (PIV == 2) {  // TIMING EXPERIMENT ONLY (wrong results): no pivot-block factorisation at all -- what the rest of a round costs
-      r0 = r1 = r2 = r3 = T(1);
-      l10 = d10;
-      l20 = d20;
-      l30 = d30;
-      l21 = d21;
-      l31 = d31;
-      l32 = d32;
-    } else if (PIV == 1) {
-      const T n11 = fma(d00, d11, -(d10 * d10)), n21 = fma(d00, d21, -(d20 * d10)), n31 = fma(d00, d31, -(d30 * d10));
-      const T n22 = fma(d00, d22, -(d20 * d20)), n32 = fma(d00, d32, -(d30 * d20)), n33 = fma(d00, d33, -(d30 * d30));
-      const T rm2 = rcp1(n11);
-      const T p22 = fma(n11, n22, -(n21 * n21)) * r0, p32 = fma(n11, n32, -(n31 * n21)) * r0;
-      const T p33 = fma(n11, n33, -(n31 * n31)) * r0;
-      const T rm3 = rcp1(p22);
-      const T m4 = fma(p22, p33, -(p32 * p32)) * rm2;
-      const T rm4 = rcp1(m4);
-      l10 = d10 * r0;
-      l20 = d20 * r0;
-      l30 = d30 * r0;
-      l21 = n21 * rm2;
-      l31 = n31 * rm2;
-      l32 = p32 * rm3;
-      r1 = d00 * rm2;
-      r2 = n11 * rm3;
-      r3 = p22 * rm4;
-      d11 = n11 * r0;   // the pivots themselves (positivity check, final scaling)
-      d22 = p22 * rm2;
-      d33 = m4 * rm3;
-    } else {
-      l10 = d10 * r0;
-      l20 = d20 * r0;
-      l30 = d30 * r0;
-      d11 = fma(-l10, d10, d11);
-      d21 = fma(-l20, d10, d21);
-      d31 = fma(-l30, d10, d31);
-      d22 = fma(-l20, d20, d22);
-      d32 = fma(-l30, d20, d32);
-      d33 = fma(-l30, d30, d33);
-      r1 = rcp1(d11);
-      if (SPLIT) {
-        __builtin_amdgcn_sched_barrier(0);
-        ld_mw();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      l21 = d21 * r1;
-      l31 = d31 * r1;
-      d22 = fma(-l21, d21, d22);
-      d32 = fma(-l31, d21, d32);
-      d33 = fma(-l31, d31, d33);
-      r2 = rcp1(d22);
-      l32 = d32 * r2;
-      d33 = fma(-l32, d32, d33);
-      r3 = rcp1(d33);
-    }
-    if (PIV == 3) {  // TIMING EXPERIMENT ONLY (wrong results): publish + barrier + pivot-block LDL', no transforms / updates
-      if (ti == 0 && tj == 0) {
-        piv[j0] = d00;
-        piv[j0 + 1] = d11;
-        piv[j0 + 2] = d22;
-        piv[j0 + 3] = d33;
-      }
-      a[J][J] += r3 * T(1e-30) + l32 * T(1e-30);
-      continue;
-    }
+    const T l10 = d10 * r0, l20 = d20 * r0, l30 = d30 * r0;
+    d11 = fma(-l10, d10, d11);
+    d21 = fma(-l20, d10, d21);
+    d31 = fma(-l30, d10, d31);
+    d22 = fma(-l20, d20, d22);
+    d32 = fma(-l30, d20, d32);
+    d33 = fma(-l30, d30, d33);
+    const T r1 = rcp1(d11);
+    __builtin_amdgcn_sched_barrier(0);
+    ld_mw();
+    __builtin_amdgcn_sched_barrier(0);
+    const T l21 = d21 * r1, l31 = d31 * r1;
+    d22 = fma(-l21, d21, d22);
+    d32 = fma(-l31, d21, d32);
+    d33 = fma(-l31, d31, d33);
+    const T r2 = rcp1(d22);
+    const T l32 = d32 * r2;
+    d33 = fma(-l32, d32, d33);
+    const T r3 = rcp1(d33);
     // ---- panel transforms for my columns / my M columns, then row by row: multipliers + rank-4 update ----
 #pragma unroll
     for (int c = J; c < NS; ++c) {
@@ -393,7 +337,7 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
         g[r][c] = s0;
       }
     }
-    if (ti == 0 && tj == 0) {  // complete before the barrier that follows the rounds (elim_block32 / factor_diag_tile512)
+    if (ti == 0 && tj == 0) {  // complete before the barrier that follows the rounds (elim_block32)
       piv[j0] = d00;
       piv[j0 + 1] = d11;
       piv[j0 + 2] = d22;
@@ -402,73 +346,17 @@ __device__ __forceinline__ void chol_rounds(T (&a)[NS][NS], T (&g)[NS][NS], T* _
   }
 }
 
-// In: bufA = SPD tile [R*LDP + C] (lower triangle valid).  Out: bufA = L (strict upper zero), bufB = L^-1.
-// All threads of the (256- or 512-thread) workgroup must call.  info: first non-positive pivot (1-based global column).
-template <typename T>
-__device__ __forceinline__ void factor_diag_tile512(T* bufA, T* bufB, T* sc, T* piv, int32_t* info, int64_t col0,
-                                                    int64_t nvalid) {
-  const int tid = threadIdx.x;
-  const bool act = tid < 256;
-  const int ti = (tid & 255) >> 4, tj = tid & 15;
-  NoHook nohook;
-  T a[4][4], g[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      int R = ti + 16 * r, Cc = tj + 16 * c;
-      int lo = R >= Cc ? R : Cc, hi = R >= Cc ? Cc : R;
-      a[r][c] = bufA[lo * LDP + hi];
-      g[r][c] = (R == Cc) ? T(1) : T(0);
-    }
-  __syncthreads();
-  chol_rounds<T, 0, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
-  chol_rounds<T, 1, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
-  chol_rounds<T, 2, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
-  chol_rounds<T, 3, 4, NoHook>(a, g, sc, piv, act, ti, tj, nohook);
-  __syncthreads();  // piv complete
-  if (tid < TILE) {
-    const T p = piv[tid];
-    const bool bad = !(p > T(0)) && (col0 + tid) < nvalid;
-    const unsigned long long mask = __ballot(bad);
-    if (mask != 0ull && tid == 0) {
-      int32_t want = (int32_t)(col0 + (__ffsll((long long)mask) - 1) + 1);
-      int32_t old = atomicCAS(info, 0, want);
-      while (old != 0 && old > want) {
-        int32_t prev = atomicCAS(info, old, want);
-        if (prev == old) break;
-        old = prev;
-      }
-    }
-  }
-  if (act) {
-    T rsC[4], rsR[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      T pc = piv[tj + 16 * q], pr = piv[ti + 16 * q];
-      rsC[q] = rsqrt1(pc > T(0) ? pc : T(1));
-      rsR[q] = rsqrt1(pr > T(0) ? pr : T(1));
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        int R = ti + 16 * r, Cc = tj + 16 * c;
-        bufA[R * LDP + Cc] = (R >= Cc) ? a[r][c] * rsC[c] : T(0);
-        bufB[R * LDP + Cc] = (R >= Cc) ? g[r][c] * rsR[r] : T(0);
-      }
-  }
-  __syncthreads();
-}
-
 // ---------------------------------------------------------------------------------------------------
-// Two-level variant of the diagonal-tile factorisation: the 64x64 tile is split into 32x32 blocks
+// The diagonal-tile factorisation, two levels: the 64x64 tile is split into 32x32 blocks
 //   [A11 . ; A21 A22] :  (L11, X11) = elim(A11) ; L21 = A21 X11' ; S = A22 - L21 L21' ; (L22, X22) = elim(S) ;
 //   X21 = -X22 (L21 X11)
 // NOX21 leaves that last line out: the caller gets [[X11, 0], [L21, X22]] in bufB, which is all a product T X' needs when it is
 // formed by block substitution (subst_tile below) -- two of the four products and two barriers less on the serial path.
-// The two eliminations use the same 4-column rounds with 2x2 cyclic ownership (about half the per-round work of the
-// 4x4 ownership: the redundant per-thread transforms shrink with the sub-block count); the glue is four 32^3 MFMA products.
+// The two eliminations run the 4-column rounds above with their 2x2 cyclic ownership (about half the per-round work of 4x4
+// ownership over the whole tile, the removed 1-level form: the redundant per-thread transforms shrink with the sub-block count);
+// the glue is four 32^3 MFMA products.
+// In: bufA = SPD tile [R*LDP + C] (lower triangle valid).  Out: bufA = L (strict upper zero), bufB = L^-1 (NOX21: see above).
+// All threads of the (256- or 512-thread) workgroup must call.  info: first non-positive pivot (1-based global column).
 // ---------------------------------------------------------------------------------------------------
 template <typename T, bool TB, int LDB = LDP>
 __device__ __forceinline__ typename Mfma<T>::acc_t mma_blk32(const T* As, const T* Bs, typename Mfma<T>::acc_t acc,
@@ -486,7 +374,7 @@ __device__ __forceinline__ typename Mfma<T>::acc_t mma_blk32(const T* As, const 
 }
 
 // eliminate the 32x32 block at (o, o) of bufA (lower valid): L -> bufA block, L^-1 -> bufB block ; all threads call
-template <typename T, typename H, int PIV = 0>
+template <typename T, typename H>
 __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* piv, const bool act, const int ti,
                                              const int tj, H& hook) {
   T a[2][2], g[2][2];
@@ -500,8 +388,8 @@ __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* 
       g[r][c] = (R == Cc) ? T(1) : T(0);
     }
   __syncthreads();
-  chol_rounds<T, 0, 2, H, PIV>(a, g, sc, piv + o, act, ti, tj, hook);
-  chol_rounds<T, 1, 2, H, PIV>(a, g, sc, piv + o, act, ti, tj, hook);
+  chol_rounds<T, 0, H>(a, g, sc, piv + o, act, ti, tj, hook);
+  chol_rounds<T, 1, H>(a, g, sc, piv + o, act, ti, tj, hook);
   __syncthreads();
   if (act) {
     T rsC[2], rsR[2];
@@ -523,7 +411,7 @@ __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* 
   __syncthreads();
 }
 
-template <typename T, typename H, int PIV = AGP_PIVOT_ALG, bool NOX21 = false>
+template <typename T, typename H, bool NOX21 = false>
 __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T* piv, int32_t* info, int64_t col0,
                                                       int64_t nvalid, H& hook) {
   const int tid = threadIdx.x;
@@ -533,7 +421,7 @@ __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T
   const bool mw = wave < 4;  // the four waves that run the 32^3 MFMA products (one 16x16 result tile each)
   typedef typename Mfma<T>::acc_t acc_t;
   NoHook nohook;
-  elim_block32<T, NoHook, PIV>(bufA, bufB, 0, sc, piv, act, ti, tj, nohook);
+  elim_block32<T, NoHook>(bufA, bufB, 0, sc, piv, act, ti, tj, nohook);
   // L21 = A21 X11' -> scratch in bufB[32:64, 0:32] (free until X21 is formed at the end; NOX21: it stays there, that IS the
   // output format): no barrier between reading A21 and writing the result.  The other waves clear the upper-right blocks
   // meanwhile (input garbage in bufA, nothing yet in bufB).
@@ -569,7 +457,7 @@ __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T
     }
   }
   __syncthreads();
-  elim_block32<T, H, PIV>(bufA, bufB, 32, sc, piv, act, ti, tj, hook);  // hook rounds 0..7 of the second half
+  elim_block32<T, H>(bufA, bufB, 32, sc, piv, act, ti, tj, hook);  // hook rounds 0..7 of the second half
   if (!NOX21) {
     // P = L21 X11  -> sc (32 x 32, free after the rounds)
 #pragma unroll
@@ -620,57 +508,7 @@ __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T
   factor_diag_tile_2lvl<T, NoHook>(bufA, bufB, sc, piv, info, col0, nvalid, nohook);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// Panel variant of the diagonal-tile factorisation (round 2): the dependent chain runs in ONE wave with the tile's rows in its
-// lanes, no LDS round trip and no barrier inside a 16-column panel.
-//   for each 16-column panel s (c0 = 16 s):
-//     wave 0, lane r = row r, a[0..15] = its entries of the panel columns.  Column j: the pivot and the entries of column j
-//       that the rank-1 update needs come out of the lanes with v_readlane (wave-uniform SGPR operands of the v_fma);
-//       a[c] -= (a[j] / d_j) * a_j(row c0 + c).  The raw column u_j (= L_j sqrt(d_j)) goes to bufA as soon as it is final,
-//       1 / d_j to rinv.
-//     barrier ; the other waves apply the panel to the remaining columns, one 16x16 MFMA tile each (k = 16) ; barrier
-//   L^-1 = D^-1/2 (U D^-1)^-1: the four 16x16 unit-triangular diagonal blocks by substitution (one wave each, a column per
-//   lane), the off-diagonal blocks by the usual two-level products on MFMA, then the scaling of L and L^-1.
-// Same arithmetic as the rounds above up to the order of the updates (LDL' without pivoting, raw pivots in piv).
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double lane_bcast(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float lane_bcast(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-
-// one 16x16 result tile: acc += (neg ? -1 : 1) * sum_{k < kend} A(r, k) sa[k] B(k, c)
-//   A(r, k) = Ar[r*LDP + k] ; sa == nullptr: no scaling ; B(k, c) = NN ? Bp[k*LDP + c] : Bp[c*LDP + k] ; kend a multiple of 8
-template <typename T, bool NN>
-__device__ __forceinline__ typename Mfma<T>::acc_t mma16(const T* Ar, const T* sa, const T* Bp, int kend,
-                                                         typename Mfma<T>::acc_t acc, bool neg, int lane) {
-  const int lr = lane & 15, lk = lane >> 4;
-  typename Mfma<T>::acc_t p1;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) p1[r] = T(0);
-#pragma unroll 2
-  for (int kk = 0; kk < kend; kk += 8) {
-    T a0 = Ar[lr * LDP + kk + lk], a1 = Ar[lr * LDP + kk + 4 + lk];
-    if (sa) {
-      a0 *= sa[kk + lk];
-      a1 *= sa[kk + 4 + lk];
-    }
-    if (neg) {
-      a0 = -a0;
-      a1 = -a1;
-    }
-    const T b0 = NN ? Bp[(kk + lk) * LDP + lr] : Bp[lr * LDP + kk + lk];
-    const T b1 = NN ? Bp[(kk + 4 + lk) * LDP + lr] : Bp[lr * LDP + kk + 4 + lk];
-    acc = Mfma<T>::mma(a0, b0, acc);
-    p1 = Mfma<T>::mma(a1, b1, p1);
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] += p1[r];
-  return acc;
-}
-
+// one 16x16 accumulator tile <-> LDS at P (stride LDP): the block substitution's loads and stores (subst_tile below)
 template <typename T>
 __device__ __forceinline__ typename Mfma<T>::acc_t acc_load16(const T* P, int lane) {
   typename Mfma<T>::acc_t acc;
@@ -682,159 +520,6 @@ template <typename T>
 __device__ __forceinline__ void acc_store16(T* P, typename Mfma<T>::acc_t acc, int lane) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) P[Mfma<T>::row(lane, r) * LDP + (lane & 15)] = acc[r];
-}
-
-// sc layout of this variant: rinv[64] | rs[64]
-template <typename T, typename H, int CUT = 0>
-__device__ __forceinline__ void factor_diag_tile_panel(T* bufA, T* bufB, T* sc, T* piv, int32_t* info, int64_t col0,
-                                                       int64_t nvalid, H& hook) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  T* rinv = sc;
-  T* rs = sc + TILE;
-  typedef typename Mfma<T>::acc_t acc_t;
-#pragma unroll 1
-  for (int s = 0; s < 4; ++s) {
-    const int c0 = 16 * s;
-    if (wave == 0 && CUT != 2) {
-      // no masks anywhere: rows above the pivot and the upper triangle of the diagonal block carry garbage that nothing
-      // reads (the lanes read below are those of rows >= c0 + j ; the final scaling selects the lower triangle)
-      T a[16], dv[16], rv[16];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) a[c] = bufA[lane * LDP + c0 + c];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const T d = lane_bcast(a[j], c0 + j);
-        const T r = rcp1(d);
-        const T l = a[j] * r;
-        bufA[lane * LDP + c0 + j] = a[j];
-        dv[j] = d;
-        rv[j] = r;
-#pragma unroll
-        for (int c = j + 1; c < 16; ++c) a[c] = fma(-l, lane_bcast(a[j], c0 + c), a[c]);
-      }
-      if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          piv[c0 + j] = dv[j];
-          rinv[c0 + j] = rv[j];
-        }
-      }
-    }
-    __syncthreads();
-    hook(2 * s);
-    if (s == 3) break;
-    {  // trailing tiles (tr, tc), s < tc <= tr <= 3, next panel's first
-      const int nrem = 3 - s;  // remaining 16-blocks
-      const int ntile = nrem * (nrem + 1) / 2;
-      if (wave < ntile) {
-        int tc = s + 1, tr = s + 1 + wave;  // column-major order over the lower triangle
-        if (tr > 3) {
-          int w = wave - nrem;
-          tc = s + 2;
-          tr = s + 2 + w;
-          if (tr > 3) {
-            tc = s + 3;
-            tr = 3;
-          }
-        }
-        T* Ct = bufA + (tr * 16) * LDP + tc * 16;
-        acc_t acc = acc_load16<T>(Ct, lane);
-        acc = mma16<T, false>(bufA + (tr * 16) * LDP + c0, rinv + c0, bufA + (tc * 16) * LDP + c0, 16, acc, true, lane);
-        acc_store16<T>(Ct, acc, lane);
-      }
-    }
-    __syncthreads();
-    hook(2 * s + 1);
-  }
-  if (CUT == 1 || CUT == 2) return;  // timing experiments: panels + trailing updates only / without the eliminations
-  // ---- inverse of the unit-triangular factor U D^-1: diagonal 16x16 blocks by substitution, column lane & 15 per lane ----
-  if (wave < 4) {
-    const int o = 16 * wave, c = lane & 15;
-    T m[16], w[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      T acc = (i == c) ? T(1) : T(0);
-#pragma unroll
-      for (int k = 0; k < i; ++k) acc = fma(-bufA[(o + i) * LDP + o + k], w[k], acc);
-      m[i] = acc;
-      w[i] = acc * rinv[o + i];
-    }
-    if (lane < 16) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) bufB[(o + i) * LDP + o + c] = m[i];
-    }
-  } else {
-    // blocks (0,1) and (2,3) of the inverse are read as zeros by the 32-level products ; rs = 1 / sqrt(pivot)
-    const int t = tid - 256;
-    for (int e = t; e < 2 * 256; e += 256) {
-      const int b = e >> 8, r = (e >> 4) & 15, cc = e & 15;
-      bufB[(32 * b + r) * LDP + 32 * b + 16 + cc] = T(0);
-    }
-    if (t < TILE) {
-      const T pv = piv[t];
-      rs[t] = rsqrt1(pv > T(0) ? pv : T(1));
-    }
-  }
-  __syncthreads();
-  hook(7);
-  if (CUT == 3) return;  // timing experiment: up to the substitutions
-  // M_10 = -M_11 (L1_10 M_00), M_32 = -M_33 (L1_32 M_22) ; Q in the upper-right corner of bufB (scratch)
-  acc_t acc;
-  if (wave < 2) {
-    const int o = 32 * wave;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = T(0);
-    acc = mma16<T, true>(bufA + (o + 16) * LDP + o, rinv + o, bufB + o * LDP + o, 16, acc, false, lane);
-    acc_store16<T>(bufB + 32 + 16 * wave, acc, lane);
-  }
-  __syncthreads();
-  if (wave < 2) {
-    const int o = 32 * wave;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = T(0);
-    acc = mma16<T, true>(bufB + (o + 16) * LDP + o + 16, (const T*)nullptr, bufB + 32 + 16 * wave, 16, acc, true, lane);
-    acc_store16<T>(bufB + (o + 16) * LDP + o, acc, lane);
-  }
-  __syncthreads();
-  // P = L1_[2:4][0:2] M_[0:2][0:2] -> bufB[0:32, 32:64] ; M_[2:4][0:2] = -M_[2:4][2:4] P
-  const int wr = (wave >> 1) & 1, wc = wave & 1;
-  if (wave < 4) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = T(0);
-    acc = mma16<T, true>(bufA + (32 + 16 * wr) * LDP, rinv, bufB + 16 * wc, 32, acc, false, lane);
-    acc_store16<T>(bufB + (16 * wr) * LDP + 32 + 16 * wc, acc, lane);
-  }
-  __syncthreads();
-  if (wave < 4) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = T(0);
-    acc = mma16<T, true>(bufB + (32 + 16 * wr) * LDP + 32, (const T*)nullptr, bufB + 32 + 16 * wc, 32, acc, true, lane);
-    acc_store16<T>(bufB + (32 + 16 * wr) * LDP + 16 * wc, acc, lane);
-  }
-  __syncthreads();
-  if (CUT == 4) return;  // timing experiment: without the final scaling
-  // scaling: L = U D^-1/2 (columns), L^-1 = D^-1/2 M (rows) ; strict upper parts zero ; bad pivots
-  for (int e = tid; e < TILE * TILE; e += CHOL_THREADS) {
-    const int R = e >> 6, Cc = e & 63;
-    const bool low = R >= Cc;
-    bufA[R * LDP + Cc] = low ? bufA[R * LDP + Cc] * rs[Cc] : T(0);
-    bufB[R * LDP + Cc] = low ? bufB[R * LDP + Cc] * rs[R] : T(0);
-  }
-  if (tid < TILE) {
-    const T p = piv[tid];
-    const bool bad = !(p > T(0)) && (col0 + tid) < nvalid;
-    const unsigned long long mask = __ballot(bad);
-    if (mask != 0ull && tid == 0) {
-      int32_t want = (int32_t)(col0 + (__ffsll((long long)mask) - 1) + 1);
-      int32_t old = atomicCAS(info, 0, want);
-      while (old != 0 && old > want) {
-        int32_t prev = atomicCAS(info, old, want);
-        if (prev == old) break;
-        old = prev;
-      }
-    }
-  }
-  __syncthreads();
 }
 
 __device__ __forceinline__ void tri_index(int64_t idx, int64_t& ti, int64_t& tj) {
@@ -1658,13 +1343,9 @@ __device__ __forceinline__ void subst_tile(T* Ts, T* Xs, T* G, F after_first) {
 //                         which the chain calls in front of the barrier that precedes S = D - L L' (D's first reader).
 // test (AGP_DAG_TEST_FEED, opts bits 2 and 3 of k_chol_dag): bit 0 -- every prefetched D element counts as not yet visible, so
 // store_d settles each of them again (DEFER only: the other schedule has no such path) ; bit 1 -- every look reports "not parked".
-// (-DAGP_FEED_DEFER=0 builds every launch with the first schedule: the A/B build of tools/step_boundary.py's per-column table)
-#ifndef AGP_FEED_DEFER
-#define AGP_FEED_DEFER 1
-#endif
 template <typename T>
 constexpr bool dag_feed_deferred() {
-  return AGP_FEED_DEFER && sizeof(T) == 8;
+  return sizeof(T) == 8;
 }
 template <typename T, bool DEFER = dag_feed_deferred<T>()>
 struct ChainPrefetch {
@@ -2582,7 +2263,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
 #ifdef AGP_STEP_TRACE
       PRO_TS(528 + k);  // (per block column: 528 + k the elimination starts, 512 + k it ends, 560 + k the path its side job took)
 #endif
-      factor_diag_tile_2lvl<T, ChainPrefetch<T>, AGP_PIVOT_ALG, SUBST>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
+      factor_diag_tile_2lvl<T, ChainPrefetch<T>, SUBST>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
       DAG_TRC(k, 2);
       PRO_TS(512 + k);
       {  // X_k out (coherent): all LDS reads first, then the stores back to back (a read-store-read-store loop exposed the
@@ -2901,10 +2582,13 @@ __global__ void k_publish_diag(T* __restrict__ A, int64_t ld, const T* __restric
     A[(k * TILE + (e >> 6)) * ld + k * TILE + (e & 63)] = Dg[k * TILE * TILE + e];
 }
 
-// micro-benchmark of the diagonal-tile factorisation alone (tools/bench_diag.py): `reps` factorizations per launch
+// micro-benchmark of the diagonal-tile factorisation alone (tools/bench_diag.py): `reps` factorizations per launch.
+// VAR 1: with the full inverse, as k_chol_step / k_chol_safe call it ; VAR 13: without X21, as the chain of k_chol_dag does
+// (the numbers are historical: variants 0, 2 .. 12 were measured against these two and removed, docs/DESIGN_LOG.md 19)
 template <typename T, int VAR>
 __global__ __launch_bounds__(CHOL_THREADS) void k_diag_bench(const T* __restrict__ A, T* __restrict__ out, int reps,
                                                              int32_t* info) {
+  static_assert(VAR == 1 || VAR == 13, "k_diag_bench: variants 1 and 13");
   __shared__ __attribute__((aligned(16))) T sm[2 * TILE * LDP];
   __shared__ __attribute__((aligned(16))) T sc[SC_ELEMS];
   __shared__ T piv[TILE];
@@ -2914,18 +2598,8 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_diag_bench(const T* __restrict
     for (int e = threadIdx.x; e < TILE * TILE; e += CHOL_THREADS) bufA[(e >> 6) * LDP + (e & 63)] = A[e];
     __syncthreads();
     NoHook nh;
-    if (VAR == 0) factor_diag_tile512<T>(bufA, bufB, sc, piv, info, 0, 64);
-    else if (VAR == 1) factor_diag_tile_2lvl<T, NoHook, 0>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else if (VAR == 2) factor_diag_tile_2lvl<T, NoHook, 1>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else if (VAR == 3) factor_diag_tile_2lvl<T, NoHook, 2>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else if (VAR == 4) factor_diag_tile_2lvl<T, NoHook, 3>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else if (VAR == 5) factor_diag_tile_2lvl<T, NoHook, 4>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else if (VAR == 6) factor_diag_tile_2lvl<T, NoHook, 5>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else if (VAR == 8) factor_diag_tile_panel<T, NoHook>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else if (VAR == 13) factor_diag_tile_2lvl<T, NoHook, 0, true>(bufA, bufB, sc, piv, info, 0, 64, nh);  // 2-level, no X21
-    else if (VAR >= 9 && VAR <= 12) factor_diag_tile_panel<T, NoHook, VAR - 8>(bufA, bufB, sc, piv, info, 0, 64, nh);
-    else {  // VAR 7: the harness alone (tile reload + barrier)
-    }
+    if (VAR == 1) factor_diag_tile_2lvl<T, NoHook>(bufA, bufB, sc, piv, info, 0, 64, nh);  // with the full inverse
+    else factor_diag_tile_2lvl<T, NoHook, true>(bufA, bufB, sc, piv, info, 0, 64, nh);     // no X21
   }
   for (int e = threadIdx.x; e < TILE * TILE; e += CHOL_THREADS) {
     out[blockIdx.x * 2 * TILE * TILE + e] = bufA[(e >> 6) * LDP + (e & 63)];

@@ -4,8 +4,9 @@ between its publish and its read side shows up in two places that the rest of th
 
 * the M rows.  Only the tile factorisation's own residual check (agp_dev_diag_bench: ||L L' - A||, ||X L - I|| and the strict-upper
   leakage of one 64 x 64 tile, tolerances 1e-12 / 1e-4) sees the inverse that the M rows build; the potrf residual tests look at L
-  alone.  Variants 0 (1-level, 4 x 4 ownership), 1 (2-level), 2 (2-level, minors) and 13 (2-level without X21) in fp64, 0, 1 and 2
-  in fp32: every call must return 0.
+  alone.  Variants 1 (2-level, full inverse) and 13 (2-level without X21) in fp64, 1 in fp32: every call must return 0.  These are
+  the variants the library has; any other (the rejected 1-level, minors and panel forms and their timing experiments, removed) must
+  return AGP_ERR_INVALID, without a launch.
 * the bits.  A layout change moves values, it does no arithmetic: factors, variational parameters and the ELBO must equal, bit for
   bit, those of the build before the layout changed.  tests/golden/round_layout_hashes.json holds their SHA-256 hashes (ELBO:
   float.hex), produced by tools/round_layout_golden.py ON THE PARENT COMMIT'S BUILD on an MI355X: agp_potrf_jitter factors at
@@ -25,6 +26,7 @@ import _knobs
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+AGP_ERR_INVALID = 1  # include/agp_hip.h, agp_status
 
 
 def _golden_tool():
@@ -53,8 +55,8 @@ def _skip_if_forced():
         pytest.skip("a fallback-forcing variable is set: other kernels, other summation order")
 
 
-@pytest.mark.parametrize("dt,variant", [(0, 0), (0, 1), (0, 2), (0, 13), (1, 0), (1, 1), (1, 2)])
-def test_tile_factorisation_residuals_with_the_inverse(built, dt, variant):
+def _diag_bench(cases):
+    """[(dt, variant, status of agp_dev_diag_bench(ctx, dt, variant, 1, 2, &us))] on one context"""
     import torch
     from agp_amd import capi
 
@@ -66,10 +68,19 @@ def test_tile_factorisation_residuals_with_the_inverse(built, dt, variant):
     assert L.agp_ctx_create(0, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(ctx)) == 0
     try:
         us = C.c_double()
-        rc = f(ctx, dt, variant, 1, 2, C.byref(us))
-        assert rc == 0, (rc, dt, variant)
+        return [(dt, variant, f(ctx, dt, variant, 1, 2, C.byref(us))) for dt, variant in cases]
     finally:
         L.agp_ctx_destroy(ctx)
+
+
+@pytest.mark.parametrize("dt,variant", [(0, 1), (0, 13), (1, 1)])
+def test_tile_factorisation_residuals_with_the_inverse(built, dt, variant):
+    assert _diag_bench([(dt, variant)]) == [(dt, variant, 0)]
+
+
+def test_removed_tile_factorisation_variants_are_invalid(built):
+    cases = [(0, 0), (0, 2), (0, 8), (1, 13)]
+    assert _diag_bench(cases) == [(dt, variant, AGP_ERR_INVALID) for dt, variant in cases]
 
 
 @pytest.mark.parametrize("dn", ["f64", "f32"])
