@@ -1,7 +1,9 @@
 // agp_capi.hip -- C ABI of libagp_hip.so (see include/agp_hip.h).  Host-side orchestration of the gfx950 kernels in
 // agp_linalg.h / agp_cavi.h: one process per GPU, everything enqueued on the caller's HIP stream.  This file holds the model
-// classes and the extern "C" surface; the layers below them are agp_ctx.h (context, error macros), agp_chol_host.h (Cholesky
-// driver) and agp_blas_host.h (GEMM / SYRK / kernel-matrix launchers), all part of this one translation unit.
+// classes (Svgp<T> and the six derived from it) and the extern "C" surface, and is the one translation unit: it includes the kernel
+// headers, then agp_ctx.h (context, error macros), agp_chol_host.h (Cholesky driver) and agp_blas_host.h (GEMM / SYRK / kernel-matrix
+// launchers), then agp_svgp_base.h (the handle interface) and the host drivers of the other subjects (agp_lpd_host.h,
+// agp_pathwise_host.h, agp_blocks_host.h, agp_select_host.h, agp_comm_host.h), each where its text stood.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -28,609 +30,10 @@
 #include "agp_chol_host.h"
 #include "agp_blas_host.h"
 
-static agp_status comm_allreduce_groups(agp_comm* cm, void* base, int esz, const int64_t* off, const int64_t* cnt, int ng,
-                                        int32_t dtype, int32_t* arrive, int32_t epoch);  // (defined with agp_comm_allreduce)
-
-// ---- model ---------------------------------------------------------------------------------------------------
-struct KernelHost {
-  int kind = AGP_K_SQEXP;
-  double variance = 1.0;
-  bool ard = false;
-  bool has_variance = true, has_transform = true;  // structure of the kernel object (agp_kernel_desc): what update_kernel! steps
-  std::vector<double> scales;  // length D
-};
-
-// ---- log predictive density (include/agp_hip.h, "LOG PREDICTIVE DENSITY"; device code in agp_lpd.h) ----------------------------------
-static bool lpd_lik_ok(int kind) {
-  return kind == AGP_LIK_GAUSSIAN || kind == AGP_LIK_LAPLACE || lpd_is_quad(kind) || lpd_is_multiclass(kind);
-}
-// the likelihood's parameters as the kernel takes them, constants formed here (lgamma)
-static agp_status lpd_params(agp_ctx* ctx, const char* who, const agp_lik_desc& lik, LpdParams* P) {
-  P->p0 = lik.p0, P->p1 = lik.p1, P->c0 = 0.0;
-  const int k = lik.kind;
-  const bool need_p0 = k == AGP_LIK_GAUSSIAN || k == AGP_LIK_LAPLACE || k == AGP_LIK_POISSON || k == AGP_LIK_NEGBINOMIAL;
-  if ((need_p0 && !(lik.p0 > 0)) || (k == AGP_LIK_STUDENTT && !(lik.p0 > 0.5 && lik.p1 > 0))) {
-    ctx->err = std::string(who) + ": Gaussian sigma2, Laplace beta, Poisson lambda and NegBinomial r must be positive, StudentT needs "
-               "nu > 0.5 and sigma > 0";
-    return AGP_ERR_INVALID;
-  }
-  if (k == AGP_LIK_STUDENTT)  // studentt.jl:43-46 as written (nvi_lconst)
-    P->c0 = std::lgamma(0.5 * (lik.p0 + 1.0)) - 0.5 * std::log(lik.p0 * 3.141592653589793) - std::lgamma(0.5 * lik.p0);
-  if (k == AGP_LIK_LAPLACE) P->c0 = -std::log(4.0 * lik.p0);
-  if (k == AGP_LIK_NEGBINOMIAL) P->c0 = -std::lgamma(lik.p0);
-  return AGP_OK;
-}
-// The Gauss-Hermite rule on the device, nodes | log weights, uploaded only when the caller's rule changes.
-struct LpdRule {
-  double* dev = nullptr;
-  int cap = 0;
-  std::vector<double> nodes, weights, up;
-  ~LpdRule() {
-    if (dev) (void)hipFree(dev);
-  }
-  agp_status ensure(agp_ctx* ctx, const char* who, hipStream_t s, const double* x, const double* w, int nn) {
-    if (!x || !w || nn < 1 || nn > 4096) {
-      ctx->err = std::string(who) + ": this likelihood needs the Gauss-Hermite nodes and weights, 1 <= n_nodes <= 4096";
-      return AGP_ERR_INVALID;
-    }
-    if (dev && (int)nodes.size() == nn && !std::memcmp(nodes.data(), x, sizeof(double) * nn) &&
-        !std::memcmp(weights.data(), w, sizeof(double) * nn))
-      return AGP_OK;
-    for (int j = 0; j < nn; ++j)
-      if (!std::isfinite(x[j]) || !(w[j] >= 0.0) || !std::isfinite(w[j])) {
-        ctx->err = std::string(who) + ": the nodes must be finite and the weights finite and non-negative";
-        return AGP_ERR_INVALID;
-      }
-    nodes.clear();  // (nothing counts as cached until the upload has been enqueued)
-    // an earlier upload may still read the staging vector: the stream is drained before it is rewritten (a change of rule is rare)
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    if (nn > cap) {
-      if (dev) (void)hipFree(dev);
-      dev = nullptr, cap = 0;
-      AGPCHK(dmalloc(ctx, &dev, 2 * (int64_t)nn));
-      cap = nn;
-    }
-    up.assign(x, x + nn);
-    for (int j = 0; j < nn; ++j) up.push_back(std::log(w[j]));  // (a zero weight: -inf, the node is skipped)
-    HIPCHK(ctx, hipMemcpyAsync(dev, up.data(), sizeof(double) * 2 * nn, hipMemcpyHostToDevice, s));
-    nodes.assign(x, x + nn);
-    weights.assign(w, w + nn);
-    return AGP_OK;
-  }
-};
-// one launch of k_predict_lpd over nc points that start at stream position `base`; part points at the launch's first workgroup
-template <typename T>
-static agp_status lpd_launch(agp_ctx* ctx, hipStream_t s, int kind, int64_t nc, int64_t base, int nl, int64_t ld, const LpdParams& P,
-                             const T* lstate, const void* y, const T* mu, const T* var, const double* quad, int nn, T* lpd_out,
-                             double* part, unsigned long long* bad) {
-  const unsigned gw = (unsigned)((nc + lpd_points_per_block(kind) - 1) / lpd_points_per_block(kind));
-#define AGP_LPD_CASE(K)                                                                                                            \
-  case K:                                                                                                                          \
-    hipLaunchKernelGGL((k_predict_lpd<T, K>), dim3(gw), dim3(LPD_THREADS), 0, s, nc, base, nl, ld, P, lstate, (const T*)y,          \
-                       (const int32_t*)y, mu, var, quad, nn, lpd_out, part, bad);                                                 \
-    break;
-  switch (kind) {
-    AGP_LPD_CASE(LIK_GAUSSIAN)
-    AGP_LPD_CASE(LIK_LOGISTIC)
-    AGP_LPD_CASE(LIK_STUDENTT)
-    AGP_LPD_CASE(LIK_LSM)
-    AGP_LPD_CASE(LIK_LAPLACE)
-    AGP_LPD_CASE(LIK_BSVM)
-    AGP_LPD_CASE(LIK_POISSON)
-    AGP_LPD_CASE(LIK_NEGBIN)
-    AGP_LPD_CASE(LIK_SOFTMAX)
-    default:
-      ctx->err = "log predictive density: unknown likelihood kind";
-      return AGP_ERR_UNSUPPORTED;
-  }
-#undef AGP_LPD_CASE
-  LAUNCHCHK(ctx);
-  return AGP_OK;
-}
-// the two failure words (as k_lpd_reduce leaves them) -> status and message
-static agp_status lpd_failure(agp_ctx* ctx, const char* who, const double* h) {
-  if (h[1] >= 0.0) {
-    ctx->err = std::string(who) + ": var_f is not positive (or a moment is not finite) at point " + std::to_string((int64_t)h[1]) +
-               " of the stream (K~ has negative values)";
-    return AGP_ERR_NEG_KTILDE;
-  }
-  if (h[2] >= 0.0) {
-    ctx->err = std::string(who) + ": a target the likelihood cannot take (class index outside the likelihood's classes, a count that "
-               "is not a non-negative integer, a binary label that is not +-1) at point " + std::to_string((int64_t)h[2]) +
-               " of the stream";
-    return AGP_ERR_LABELS;
-  }
-  return AGP_OK;
-}
-
-struct SvgpBase {
-  agp_ctx* ctx = nullptr;
-  agp_svgp_desc desc{};
-  virtual ~SvgpBase() {
-    for (void* p : {lpd_mu, lpd_var, (void*)lpd_part, (void*)lpd_scal})
-      if (p) (void)hipFree(p);
-  }
-  virtual agp_status init() = 0;
-  virtual agp_status set_kernel(int l, const agp_kernel_desc* k) = 0;
-  virtual agp_status set_Z(int l, const void* z, int64_t ldz) = 0;
-  virtual agp_status get_Z(int l, void* z, int64_t ldz) = 0;
-  virtual agp_status set_mu0(int l, const void* mu0) = 0;
-  virtual agp_status refresh_K() = 0;
-  virtual agp_status step_local(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho,
-                                bool fresh) = 0;
-  virtual agp_status prefetch(const void* x, int64_t ldx, const int64_t* idx, int64_t B) = 0;
-  virtual agp_status set_multioutput(int n_task, const agp_lik_desc* liks, const double* A_host, double eta, double b1,
-                                     double b2, double eps) = 0;
-  virtual agp_status get_A(double* A_host) = 0;
-  virtual agp_status mo_shard(int q_total) = 0;
-  virtual agp_status mo_fbuf_ptr(void** p, int64_t* n) = 0;
-  virtual agp_status mo_mix() = 0;
-  virtual agp_status mo_refresh_f() = 0;
-  virtual agp_status mo_predict_from_f(int64_t nt, int mode, void* o0, void* o1, const double* nodes,
-                                       const double* weights, int nn) = 0;
-  virtual agp_status hyper_rule(int k_rule, double k_rho, int z_rule, double z_rho) = 0;
-  virtual agp_status hyper_configure(int opt_k, double k_eta, int opt_z, double z_eta, double b1, double b2,
-                                     double eps) = 0;
-  virtual agp_status hypergrad(int l, double* dvar, double* dscale, void* dZ) = 0;
-  virtual agp_status hyper_step() = 0;
-  virtual agp_status get_kernel(int l, double* var, double* scales) = 0;
-  virtual agp_status lsm_gamma() = 0;
-  virtual agp_status lsm_alpha() = 0;
-  virtual agp_status lsm_local_all() = 0;  // both rounds and the final theta, r, w of a handle holding every latent
-  virtual agp_status lsm_gsum_ptr(void** p, int64_t* n) = 0;
-  virtual agp_status step_stats(bool fused) = 0;
-  virtual agp_status stats_ptr(void** p, int64_t* n) = 0;
-#ifdef AGP_DEBUG_PTRS  // (development builds only: device addresses of the step's state, tools/tmp)
-  virtual void* debug_ptr(int what) { (void)what; return nullptr; }
-#endif
-  virtual agp_status step_global(bool fused) = 0;
-  // tail of agp_svgp_cavi_step: the fused natural-gradient step now, or left pending for the next step's task-graph launch
-  virtual agp_status step_finish() = 0;
-  // applies a pending natural-gradient step with the stand-alone kernel (every entry point other than the CAVI step calls this
-  // first, so eta, Sigma, predictions, the ELBO and the hyper-gradient never see a half-taken step)
-  virtual agp_status flush() = 0;
-  virtual agp_status check_status() = 0;
-  virtual agp_status elbo(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho,
-                          int fresh, double* out) = 0;
-  virtual agp_status elbo_terms(double* out3) = 0;
-  // streamed full-data ELBO ("STREAMED ELBO"): sparse AnalyticVI / AnalyticSVI handles evaluate (Svgp<T>); every other class
-  // refuses by name before anything is launched
-  agp_status elbo_stream_refused(const char* why) {
-    ctx->err = std::string("agp_svgp_elbo_stream: ") + why;
-    return AGP_ERR_UNSUPPORTED;
-  }
-  virtual agp_status elbo_stream(const void*, int64_t, const void*, const int64_t*, int64_t, double, double*, double*) {
-    return elbo_stream_refused("this handle class has no streamed ELBO (sparse AnalyticVI / AnalyticSVI handles only)");
-  }
-  // ---- streamed log predictive density (include/agp_hip.h, "LOG PREDICTIVE DENSITY") ------------------------
-  // sum_i log p(y_i | x_i, model) over any number of points: the handle's own predict_f, chunk by chunk, leaves the moments of 4096
-  // points in lpd_mu / lpd_var; k_predict_lpd turns them into one partial sum per workgroup; k_lpd_reduce adds all of them in a
-  // fixed order.  One routine for every class whose predict_f works.  Touches the predictor's workspace and the buffers below --
-  // never step buffers, local variables, caches or status words.  One synchronisation, at the end.
-  void *lpd_mu = nullptr, *lpd_var = nullptr;  // T[n_latent][4096]
-  double* lpd_part = nullptr;                  // one per workgroup of the stream
-  int64_t lpd_part_cap = 0;
-  double* lpd_scal = nullptr;                  // out[3] of k_lpd_reduce | - | the two failure words
-  LpdRule lpd_rule;
-  // what the routine has to ask the class: the likelihood-state word on the device (Gaussian noise under opt_noise, Poisson lambda;
-  // NULL: the descriptor's p0 holds), and whether the handle sees a shard of every minibatch
-  virtual const void* lpd_lik_state() { return nullptr; }
-  virtual bool lpd_batch_sharded() { return false; }
-  agp_status lpd_refused(const char* why) {
-    ctx->err = std::string("agp_svgp_lpd_stream: ") + why;
-    return AGP_ERR_UNSUPPORTED;
-  }
-  agp_status lpd_stream(const void* xt, int64_t ldx, const void* y, int64_t n, const double* nodes, const double* weights, int nn,
-                        double* sum_host, void* lpd_out) {
-    const int kind = desc.lik.kind;
-    if (desc.flags & AGP_FLAG_SAMPLED)
-      return lpd_refused("Gibbs-sampled models (AGP_FLAG_SAMPLED) are not supported: they have no predict_f");
-    if (kind == AGP_LIK_MULTIOUTPUT) return lpd_refused("multi-output handles (AGP_LIK_MULTIOUTPUT) are not supported");
-    if (kind == AGP_LIK_HETEROSCEDASTIC)
-      return lpd_refused("Heteroscedastic is not supported (two latents, a nested integral: a follow-up)");
-    if (!lpd_lik_ok(kind)) return lpd_refused("unknown likelihood kind");
-    if (desc.latent_offset != 0 || desc.n_latent != (lpd_is_multiclass(kind) ? desc.lik.n_class : 1))
-      return lpd_refused("latent-sharded handles are not supported (a point's density needs every latent on one handle)");
-    if (lpd_batch_sharded()) return lpd_refused("batch-sharded handles are not supported");
-    if (n < 0 || !sum_host || (n > 0 && (!xt || !y || ldx < desc.D))) {
-      ctx->err = "agp_svgp_lpd_stream: n >= 0, sum_host must not be NULL, x and y must not be NULL, ldx >= D";
-      return AGP_ERR_INVALID;
-    }
-    if (n == 0) {
-      *sum_host = 0.0;
-      return AGP_OK;
-    }
-    return desc.dtype == AGP_F32 ? lpd_stream_t<float>(xt, ldx, y, n, nodes, weights, nn, sum_host, lpd_out)
-                                 : lpd_stream_t<double>(xt, ldx, y, n, nodes, weights, nn, sum_host, lpd_out);
-  }
-  template <typename T>
-  agp_status lpd_stream_t(const void* xt, int64_t ldx, const void* y, int64_t n, const double* nodes, const double* weights, int nn,
-                          double* sum_host, void* lpd_out) {
-    const char* who = "agp_svgp_lpd_stream";
-    const int kind = desc.lik.kind, nl = desc.n_latent;
-    const int64_t CH = 4096, ppb = lpd_points_per_block(kind);
-    const int64_t nw = (n + ppb - 1) / ppb;
-    hipStream_t s = ctx->stream;
-    LpdParams P;
-    AGPCHK(lpd_params(ctx, who, desc.lik, &P));
-    if (lpd_is_quad(kind)) AGPCHK(lpd_rule.ensure(ctx, who, s, nodes, weights, nn));
-    if (!lpd_mu) {
-      AGPCHK(dmalloc(ctx, (T**)&lpd_mu, (int64_t)nl * CH));
-      AGPCHK(dmalloc(ctx, (T**)&lpd_var, (int64_t)nl * CH));
-      AGPCHK(dmalloc(ctx, &lpd_scal, 8));
-    }
-    if (nw > lpd_part_cap) {
-      if (lpd_part) (void)hipFree(lpd_part);
-      lpd_part = nullptr;
-      lpd_part_cap = 0;
-      AGPCHK(dmalloc(ctx, &lpd_part, nw));
-      lpd_part_cap = nw;
-    }
-    unsigned long long* bad = reinterpret_cast<unsigned long long*>(lpd_scal + 4);
-    HIPCHK(ctx, hipMemsetAsync(bad, 0xFF, 2 * sizeof(unsigned long long), s));
-    const T* lstate = (const T*)lpd_lik_state();
-    for (int64_t st0 = 0; st0 < n; st0 += CH) {
-      const int64_t nc = (n - st0) < CH ? (n - st0) : CH;
-      AGPCHK(predict_f((const T*)xt + st0 * ldx, ldx, nc, lpd_mu, lpd_var));  // T[nl][nc]
-      AGPCHK(lpd_launch<T>(ctx, s, kind, nc, st0, nl, nc, P, lstate, y, (const T*)lpd_mu, (const T*)lpd_var, lpd_rule.dev, nn,
-                           (T*)lpd_out, lpd_part + st0 / ppb, bad));
-    }
-    hipLaunchKernelGGL(k_lpd_reduce, dim3(1), dim3(1024), 0, s, (const double*)lpd_part, nw, (const unsigned long long*)bad, lpd_scal);
-    LAUNCHCHK(ctx);
-    double h[3] = {0.0, -1.0, -1.0};
-    HIPCHK(ctx, hipMemcpyAsync(h, lpd_scal, sizeof(double) * 3, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    AGPCHK(lpd_failure(ctx, who, h));
-    *sum_host = h[0];
-    return AGP_OK;
-  }
-  virtual agp_status elbo_enqueue(const void* x, int64_t ldx, const void* y, const int64_t* idx, int64_t B, double rho, int fresh,
-                                  int32_t* ticket) = 0;
-  virtual agp_status elbo_fetch(int32_t ticket, int wait, double* out, int32_t* ready) = 0;
-  virtual agp_status set_batch_shard(int rank, int world) = 0;
-  virtual agp_status get_state(int l, void* mu, void* sigma, void* eta1, void* eta2) = 0;
-  virtual agp_status set_state(int l, const void* eta1, const void* eta2) = 0;
-  virtual agp_status get_matrix(int l, int which, void* out, int64_t ldo, int64_t cap) = 0;
-  virtual int64_t last_batch() = 0;
-  virtual agp_status init_state() = 0;
-  virtual agp_status invalidate_data() = 0;
-  virtual agp_status predict_f_cov(const void* xt, int64_t ldx, int64_t nt, void* mu, void* cov) = 0;
-  virtual agp_status refresh_K_explicit() = 0;
-  // multi-GPU (agp_comm.h)
-  virtual agp_status cavi_step_multi(agp_comm* cm, int mode, const void* x, int64_t ldx, const void* y, const int64_t* idx,
-                                     int64_t B, double rho) = 0;
-  virtual agp_status elbo_multi(agp_comm* cm, int mode, double* out) = 0;
-  virtual agp_status hyper_step_multi(agp_comm* cm, int tied) = 0;
-  virtual agp_status predict_multi(agp_comm* cm, int what, const void* xt, int64_t ldx, int64_t nt, void* mu, void* var,
-                                   const double* nodes, const double* weights, int nn) = 0;
-  virtual agp_status predict_f(const void* xt, int64_t ldx, int64_t nt, void* mu, void* var) = 0;
-  // input gradients of the predictive moments ("PREDICTIVE GRADIENTS"; Svgp<T>::predict_f_grad serves every class)
-  virtual agp_status predict_f_grad(const void* xt, int64_t ldx, int64_t nt, void* dmu, void* dvar, int64_t ldg) = 0;
-  virtual agp_status predict_y(const void* xt, int64_t ldx, int64_t nt, void* out) = 0;
-  virtual agp_status proba_y(const void* xt, int64_t ldx, int64_t nt, const double* nodes, const double* weights,
-                             int nn, void* o0, void* o1) = 0;
-  virtual agp_status set_quadrature(const double* nodes, const double* weights, int nn) = 0;
-  virtual agp_status hyper_state(int l, int set, double* k_m, double* k_v, int32_t* k_step) = 0;
-  virtual agp_status hyper_apply(int l, const double* dvar, const double* dscale, const void* dZ) = 0;
-  virtual agp_status set_lsm_alpha(const void* a, int64_t n) = 0;
-  virtual agp_status set_online_prior(int l, const void* za, int64_t ldza, int64_t ma, const void* invDa, int64_t ldi,
-                                      const void* peta1, double prevLa) = 0;
-  virtual agp_status online_snapshot(int l, void* invDa_out, int64_t ldi, void* eta1_out, double* prevLa_host) = 0;
-  virtual agp_status adopt_local(SvgpBase* src) = 0;
-  virtual agp_status get_lik_param(double* out) = 0;
-  virtual agp_status set_lik_param(double v) = 0;
-  // Gibbs sampling (AGP_FLAG_SAMPLED: Mcgp); every other handle refuses
-  agp_status not_sampled(const char* what) {
-    ctx->err = std::string(what) + ": the handle is not a Gibbs-sampled model (AGP_FLAG_FULL | AGP_FLAG_SAMPLED)";
-    return AGP_ERR_UNSUPPORTED;
-  }
-  virtual agp_status gibbs_sample(const void*, int64_t, int64_t, int64_t, uint64_t, void*, int64_t) {
-    return not_sampled("agp_svgp_gibbs_sample");
-  }
-  virtual agp_status gibbs_counter(int, int64_t*) { return not_sampled("agp_svgp_gibbs_counter"); }
-  virtual agp_status predict_samples(const void*, int64_t, int64_t, const void*, int64_t, int64_t, int, void*, void*) {
-    return not_sampled("agp_svgp_predict_samples");
-  }
-  // numerical inference (AGP_FLAG_NUMERICAL: Nvgp, Nsvgp); every other handle refuses
-  agp_status not_numerical(const char* what) {
-    ctx->err = std::string(what) + ": the handle does not run numerical inference (AGP_FLAG_NUMERICAL, with or without AGP_FLAG_FULL)";
-    return AGP_ERR_UNSUPPORTED;
-  }
-  virtual agp_status nvi_configure(int, const double*, const double*, int, int, double, double, double, double) {
-    return not_numerical("agp_svgp_nvi_configure");
-  }
-  virtual agp_status mcvi_configure(int, uint64_t, int, int, double, double, double, double) {
-    return not_numerical("agp_svgp_mcvi_configure");
-  }
-  virtual agp_status nvi_step(const void*, int64_t, const void*, const int64_t*, int64_t, double) {
-    return not_numerical("agp_svgp_nvi_step");
-  }
-  virtual agp_status nvi_info(int, double*, int64_t*, int64_t*) { return not_numerical("agp_svgp_nvi_info"); }
-  virtual agp_status nvi_state(int, int, void*, void*, int64_t*) { return not_numerical("agp_svgp_nvi_state"); }
-  // pathwise sampling ("PATHWISE SAMPLING"): Svgp<double>, Vgp and Gp draw; every other class refuses by name
-  virtual agp_status pathwise_draw(int n_features, int n_samples, uint64_t seed, int64_t t, agp_pathwise** out) = 0;
-  agp_status pathwise_refused(const char* why) {
-    ctx->err = std::string("agp_svgp_pathwise_draw: ") + why;
-    return AGP_ERR_UNSUPPORTED;
-  }
-  int64_t n_opt = 1;  // RobbinsMonro counter (optimisers.jl:12)
-  bool in_cavi_step = false;  // step_local is running as the first half of agp_svgp_cavi_step (its tail may then be deferred)
-  int64_t n_prologue = 0;  // CAVI steps whose natural-gradient part rode on the next step's task-graph launch (agp_svgp_step_counters)
-  int64_t n_steps = 0;     // agp_svgp_cavi_step calls
-  int64_t n_hgrad = 0, n_gk_fused = 0;  // hyper-gradient evaluations / those with the one-product G_K (agp_svgp_hyper_counters)
-  // HIP-event timing of the dominant kernel sequence (agp_svgp_timing_*)
-  bool timing = false;
-  int timing_every = 1, timing_ctr = 0;  // every n-th sequence is bracketed (the two event records cost the step ~16 us at C2)
-  bool timing_now = false;
-  std::vector<hipEvent_t> ev;
-  std::vector<int64_t> ev_launches;
-  size_t ev_used = 0;
-  agp_status timing_begin() {
-    timing_now = timing && (timing_ctr++ % timing_every) == 0;
-    if (!timing_now) return AGP_OK;
-    if (ev_used + 2 > ev.size()) {
-      for (int i = 0; i < 2; ++i) {
-        hipEvent_t e;
-        HIPCHK(ctx, hipEventCreate(&e));
-        ev.push_back(e);
-      }
-    }
-    HIPCHK(ctx, hipEventRecord(ev[ev_used], ctx->stream));
-    return AGP_OK;
-  }
-  agp_status timing_end(int64_t launches) {
-    if (!timing_now) return AGP_OK;
-    timing_now = false;
-    HIPCHK(ctx, hipEventRecord(ev[ev_used + 1], ctx->stream));
-    ev_used += 2;
-    ev_launches.push_back(launches);
-    return AGP_OK;
-  }
-  agp_status timing_read(int64_t* n, double* ms) {
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *n = 0;
-    *ms = 0.0;
-    for (size_t i = 0; i + 1 < ev_used; i += 2) {
-      float t = 0;
-      HIPCHK(ctx, hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-      *ms += t;
-      *n += ev_launches[i / 2];
-    }
-    ev_used = 0;
-    ev_launches.clear();
-    return AGP_OK;
-  }
-};
-
-// the last line of the ELBO on the device (agp_svgp_elbo_enqueue): rho E_data - KL(q(u) || p(u)) - rho KL_aug from the five partial
-// results of the evaluation and log det K, written to mapped host memory -- no stream synchronisation on the host's side
-__global__ void k_elbo_combine(const double* __restrict__ sc, const double* __restrict__ half_logdetK, double m, double rho,
-                               double* __restrict__ out) {
-  const double kl = 0.5 * (2.0 * half_logdetK[0] + 2.0 * sc[2] + sc[3] + sc[4] - m);  // log det Sigma = -2 sc[2]
-  *out = rho * sc[0] - kl - rho * sc[1];
-  __threadfence_system();
-}
-
-struct agp_svgp {
-  SvgpBase* impl;
-};
-
-// teardown helpers: a failing free / destroy is a bug in this library, so it is reported, never swallowed
-static void dcheck(hipError_t e, int line) {
-  if (e != hipSuccess) fprintf(stderr, "[agp_hip] teardown: %s (agp_capi.hip:%d)\n", hipGetErrorString(e), line);
-}
-#define dfree(p) dcheck(hipFree(p), __LINE__)
-
-// ---- pathwise sampling (include/agp_hip.h, "PATHWISE SAMPLING"; device code in agp_pathwise.h) -------------------------------------
-// A draw owns everything it evaluates with: per latent the snapshot of the kernel (kind, variance, scales), of Z with its ready-made
-// kernel-matrix tiles, the spectral tables, [W' | V'] (Sp x (Lp + mp), sample-major: the B side of the evaluation's one gemm_nt) and
-// E; shared by the latents the workspace [Phi(x) | k(x, Z)] of one chunk of test points and the chunk's result before it is copied
-// into the caller's rows.
-struct agp_pathwise {
-  agp_ctx* ctx = nullptr;
-  int nl = 0, L = 0, S = 0;
-  int64_t Lp = 0, Sp = 0, m = 0, mp = 0, D = 0, ldw = 0, CH = 0;
-  struct Lat {
-    int kind = AGP_K_SQEXP;
-    double variance = 1.0, amp = 0.0;
-    double *scales = nullptr, *Z = nullptr, *Zsc = nullptr, *zn = nullptr, *omega = nullptr, *phase = nullptr, *WV = nullptr,
-           *E = nullptr;
-  };
-  std::vector<Lat> lat;
-  double *ws = nullptr, *Fs = nullptr;
-  ~agp_pathwise() {
-    for (auto& a : lat)
-      for (double* q : {a.scales, a.Z, a.Zsc, a.zn, a.omega, a.phase, a.WV, a.E})
-        if (q) (void)hipFree(q);
-    for (double* q : {ws, Fs})
-      if (q) (void)hipFree(q);
-  }
-};
-// device buffers that live as long as one call
-struct PwScratch {
-  std::vector<void*> v;
-  ~PwScratch() {
-    for (void* q : v) (void)hipFree(q);
-  }
-  template <typename U>
-  agp_status get(agp_ctx* c, U** q, int64_t n) {
-    AGPCHK(dmalloc(c, q, n));
-    v.push_back(*q);
-    return AGP_OK;
-  }
-};
-constexpr int64_t PW_MAX = 65536, PW_CTR_MAX = (int64_t)0xFFFFFFFFll;
-static agp_status pw_check_spectral(agp_ctx* ctx, const char* who, int64_t D, int64_t L, int64_t t) {
-  if (L < 1 || L > PW_MAX) {
-    ctx->err = std::string(who) + ": n_features must lie in [1, 65536] (got " + std::to_string(L) + ")";
-    return AGP_ERR_INVALID;
-  }
-  if (D < 1 || L * D > PW_CTR_MAX) {
-    ctx->err = std::string(who) + ": D >= 1 and n_features * D below 2^32 (one 32-bit counter word per frequency element)";
-    return AGP_ERR_INVALID;
-  }
-  if (t < 0 || t > PW_CTR_MAX) {
-    ctx->err = std::string(who) + ": the draw counter t is one 32-bit word of the generator's counter, 0 <= t < 2^32";
-    return AGP_ERR_INVALID;
-  }
-  return AGP_OK;
-}
-static agp_status pw_check_draw(agp_ctx* ctx, int64_t m, int64_t D, int64_t L, int64_t S, int64_t t, agp_pathwise** out) {
-  const char* who = "agp_svgp_pathwise_draw";
-  if (!out) {
-    ctx->err = std::string(who) + ": out must be given";
-    return AGP_ERR_INVALID;
-  }
-  AGPCHK(pw_check_spectral(ctx, who, D, L, t));
-  if (S < 1 || S > PW_MAX) {
-    ctx->err = std::string(who) + ": n_samples must lie in [1, 65536] (got " + std::to_string(S) + ")";
-    return AGP_ERR_INVALID;
-  }
-  if (L * S > PW_CTR_MAX || m * S > PW_CTR_MAX) {
-    ctx->err = std::string(who) + ": n_features * n_samples and m * n_samples must stay below 2^32 (counter words of W and E)";
-    return AGP_ERR_INVALID;
-  }
-  return AGP_OK;
-}
-static agp_status pw_spectral(agp_ctx* ctx, int kind, int64_t D, int64_t L, uint64_t seed, int64_t t, int latent, double* omega,
-                              double* phase) {
-  hipLaunchKernelGGL(agp::k_pw_spectral, grid1(L * D), dim3(256), 0, ctx->stream, L * D, D, kind, seed, (uint32_t)t,
-                     (uint32_t)(4 + 8 * latent), omega, phase);
-  LAUNCHCHK(ctx);
-  return AGP_OK;
-}
-// the empty draw: sizes, the chunk of the evaluation workspace under AGP_PATHWISE_WS_BYTES, the shared buffers
-static agp_status pw_create(agp_ctx* ctx, int nl, int64_t m, int64_t D, int L, int S, std::unique_ptr<agp_pathwise>* out) {
-  std::unique_ptr<agp_pathwise> p(new agp_pathwise());
-  p->ctx = ctx, p->nl = nl, p->L = L, p->S = S, p->m = m, p->D = D;
-  p->Lp = rup64(L), p->Sp = rup64(S), p->mp = rup64(m), p->ldw = p->Lp + p->mp;
-  const int64_t per_point = 8 * (p->ldw + p->Sp);
-  p->CH = std::min<int64_t>(4096, std::max<int64_t>(64, (int64_t)AGP_PATHWISE_WS_BYTES / per_point / 64 * 64));
-  p->lat.resize(nl);
-  AGPCHK(dmalloc(ctx, &p->ws, p->CH * p->ldw));
-  AGPCHK(dmalloc(ctx, &p->Fs, p->Sp * p->CH));
-  *out = std::move(p);
-  return AGP_OK;
-}
-// one latent's snapshot and tables: kernel, scales (D + 1 doubles as the handle keeps them: the variance behind the scales), Z
-// (m x D, dense), its kernel-matrix tiles, Omega and the phases, W (into the left columns of [W' | V']) and E (mp x Sp)
-static agp_status pw_add_latent(agp_pathwise& p, int l, int kind, double variance, const double* scales_dev, const double* Z_dev,
-                                uint64_t seed, int64_t t) {
-  agp_ctx* ctx = p.ctx;
-  agp_pathwise::Lat& a = p.lat[l];
-  a.kind = kind, a.variance = variance, a.amp = std::sqrt(2.0 * variance / (double)p.L);
-  AGPCHK(dmalloc(ctx, &a.scales, p.D + 1));
-  AGPCHK(dmalloc(ctx, &a.Z, p.m * p.D));
-  AGPCHK(dmalloc(ctx, &a.omega, (int64_t)p.L * p.D));
-  AGPCHK(dmalloc(ctx, &a.phase, p.L));
-  AGPCHK(dmalloc(ctx, &a.WV, p.Sp * p.ldw));
-  AGPCHK(dmalloc(ctx, &a.E, p.mp * p.Sp));
-  HIPCHK(ctx, hipMemcpyAsync(a.scales, scales_dev, sizeof(double) * (p.D + 1), hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(a.Z, Z_dev, sizeof(double) * p.m * p.D, hipMemcpyDeviceToDevice, ctx->stream));
-  if (kmm_usable(p.D)) {
-    const int Dp = kmm_dp(p.D);
-    AGPCHK(dmalloc(ctx, &a.Zsc, p.mp * Dp));
-    AGPCHK(dmalloc(ctx, &a.zn, p.mp));
-    hipLaunchKernelGGL((agp::k_scale_rows<double>), dim3((unsigned)((p.mp + 3) / 4)), dim3(256), 0, ctx->stream, (const double*)a.Z,
-                       p.D, p.m, p.mp, p.D, Dp, (const double*)a.scales, a.Zsc, a.zn);
-    LAUNCHCHK(ctx);
-  }
-  AGPCHK(pw_spectral(ctx, kind, p.D, p.L, seed, t, l, a.omega, a.phase));
-  const uint32_t s0 = (uint32_t)(4 + 8 * l);
-  HIPCHK(ctx, hipMemsetAsync(a.WV, 0, sizeof(double) * p.Sp * p.ldw, ctx->stream));
-  hipLaunchKernelGGL(agp::k_pw_table, grid1(p.Lp * p.Sp), dim3(256), 0, ctx->stream, (int64_t)p.L, (int64_t)p.S, p.Lp, p.Sp,
-                     (int64_t)1, p.ldw, 0, seed, (uint32_t)t, s0 + agp::PW_STREAM_W, a.WV);
-  hipLaunchKernelGGL(agp::k_pw_table, grid1(p.mp * p.Sp), dim3(256), 0, ctx->stream, p.m, (int64_t)p.S, p.mp, p.Sp, p.Sp,
-                     (int64_t)1, 1, seed, (uint32_t)t, s0 + agp::PW_STREAM_E, a.E);
-  LAUNCHCHK(ctx);
-  return AGP_OK;
-}
-// Phi(x) of n points (rows 0 .. rup64(n) of the workspace, left Lp columns; padding rows and columns exact zeros)
-static agp_status pw_features(agp_pathwise& p, const agp_pathwise::Lat& a, const double* x, int64_t ldx, int64_t n) {
-  hipLaunchKernelGGL(agp::k_pw_features, dim3((unsigned)(p.Lp / TILE), (unsigned)(rup64(n) / TILE)), dim3(256), 0, p.ctx->stream, x,
-                     ldx, n, p.D, (const double*)a.scales, (const double*)a.omega, (const double*)a.phase, (int64_t)p.L, a.amp, p.ws,
-                     p.ldw);
-  LAUNCHCHK(p.ctx);
-  return AGP_OK;
-}
-// PW (mp x Sp) = Phi(Z) W, the rows of Z in chunks of the evaluation workspace
-static agp_status pw_phi_W(agp_pathwise& p, int l, double* PW) {
-  const agp_pathwise::Lat& a = p.lat[l];
-  HIPCHK(p.ctx, hipMemsetAsync(PW, 0, sizeof(double) * p.mp * p.Sp, p.ctx->stream));
-  for (int64_t r0 = 0; r0 < p.m; r0 += p.CH) {
-    const int64_t nc = std::min<int64_t>(p.CH, p.m - r0), nq = rup64(nc);
-    AGPCHK(pw_features(p, a, a.Z + r0 * p.D, p.D, nc));
-    AGPCHK((gemm_nt<double, EPI_STORE>(p.ctx, p.ws, p.ldw, a.WV, p.ldw, nq, p.Sp, p.Lp, 0, PW + r0 * p.Sp, p.Sp, nullptr, 0, nullptr,
-                                       nullptr, nullptr, 0)));
-  }
-  return AGP_OK;
-}
-// X = chol_lower(A)^-1 of a padded SPD matrix (A is destroyed), strict upper triangle zero: the driver of agp_spd_inverse
-static agp_status pw_inverse_factor(agp_ctx* ctx, PwScratch& sc, double* A, const double* A_src, int64_t lds, int64_t n, int64_t np,
-                                    double scale, double* X) {
-  double* Dg = nullptr;
-  int32_t* info = nullptr;
-  AGPCHK(sc.get(ctx, &Dg, np * TILE));
-  AGPCHK(sc.get(ctx, &info, 1));
-  auto fill = [&]() {
-    hipLaunchKernelGGL((agp::k_copy2d<double>), grid2(np, np), blk2, 0, ctx->stream, A_src, lds, n, n, A, np, np, np, 1.0, scale);
-  };
-  fill();
-  HIPCHK(ctx, hipMemsetAsync(X, 0, sizeof(double) * np * np, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
-  PotrfReq<double> rq{};
-  rq.A = A, rq.ld = np, rq.n = np, rq.X = X, rq.ldx = np, rq.Dg = Dg, rq.do_x = 1, rq.info_dev = info, rq.nvalid = n;
-  AGPCHK(potrf_fused<double>(ctx, rq));
-  if (chol_use_dag(ctx, np / TILE)) {
-    bool lost = false;
-    AGPCHK(dag_lost_dependency(ctx, info, &lost));
-    if (lost) {
-      fill();
-      AGPCHK(potrf_fused<double>(ctx, rq));
-    }
-  }
-  hipLaunchKernelGGL((agp::k_zero_strict_upper<double>), grid2(np, np), blk2, 0, ctx->stream, X, np, np);
-  LAUNCHCHK(ctx);
-  int32_t hinfo = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&hinfo, info, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (hinfo != 0) {
-    ctx->err = "agp_svgp_pathwise_draw: -2 eta2 is not positive definite; leading minor " + std::to_string(hinfo);
-    return AGP_ERR_NOT_POSDEF;
-  }
-  return AGP_OK;
-}
-// C (M x N, ldc) = A (K x M)' B (K x N), all multiples of 64
-static agp_status pw_gemm_tn(agp_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t M, int64_t N, int64_t K,
-                             double* Cm, int64_t ldc) {
-  hipLaunchKernelGGL((agp::k_gemm_tn<double, 1>), dim3((unsigned)(N / TILE), (unsigned)(M / TILE)), dim3(NTHREADS), 0, ctx->stream, A, lda,
-                     B, ldb, K, Cm, ldc);
-  LAUNCHCHK(ctx);
-  return AGP_OK;
-}
-static agp_status pw_eval(agp_pathwise& p, const double* xt, int64_t ldx, int64_t nt, double* out, int64_t ldo) {
-  agp_ctx* ctx = p.ctx;
-  for (int l = 0; l < p.nl; ++l) {
-    const agp_pathwise::Lat& a = p.lat[l];
-    for (int64_t s = 0; s < nt; s += p.CH) {
-      const int64_t nc = std::min<int64_t>(p.CH, nt - s), nq = rup64(nc);
-      const double* xs = xt + s * ldx;
-      AGPCHK(pw_features(p, a, xs, ldx, nc));
-      const int rc = launch_kernelmatrix<double>(ctx, ctx->stream, xs, ldx, (const int64_t*)nullptr, nc, (const double*)a.Z, p.D, p.m,
-                                                 p.D, (const double*)a.scales, a.kind, a.variance, p.ws + p.Lp, p.ldw, nq, p.mp, 0,
-                                                 0.0, (const double*)nullptr, (double*)nullptr, (int64_t)0, 0, (const double*)a.Zsc,
-                                                 (const double*)a.zn);
-      LAUNCHCHK(ctx);
-      if (rc < 0) return AGP_ERR_NOMEM;
-      AGPCHK((gemm_nt<double, EPI_STORE>(ctx, a.WV, p.ldw, p.ws, p.ldw, p.Sp, nq, p.ldw, 0, p.Fs, p.CH, nullptr, 0, nullptr, nullptr,
-                                         nullptr, 0)));
-      HIPCHK(ctx, hipMemcpy2DAsync(out + ((int64_t)l * p.S) * ldo + s, sizeof(double) * ldo, p.Fs, sizeof(double) * p.CH,
-                                   sizeof(double) * nc, p.S, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-  }
-  return AGP_OK;
-}
-
+// (the handle interface and the other host drivers, here and further down: each where its first use of a kernel template must come)
+#include "agp_lpd_host.h"
+#include "agp_svgp_base.h"
+#include "agp_pathwise_host.h"
 template <typename T>
 struct Svgp : SvgpBase {
   struct Latent {
@@ -1101,7 +504,7 @@ struct Svgp : SvgpBase {
   }
 
   ~Svgp() override {
-    for (auto e : ev) dcheck(hipEventDestroy(e), __LINE__);
+    for (auto e : ev) dcheck(hipEventDestroy(e), __FILE_NAME__, __LINE__);
     for (auto& g : lat) {
       T* ps[] = {g.Zsc, g.zn, g.scales, g.Z, g.L, g.Xk, g.Kinv, g.mu0, g.kinv_mu0, g.eta1, g.eta2, g.La, g.Xa, g.v,
                  g.Sigma, g.mu, g.Knm, g.kappa, g.Apred, g.apred, g.Wbuf, g.DgK, g.DgA, g.pk, g.Knm_alt, g.kappa_alt, g.Wbuf_alt, g.pk_alt, g.kappa_old};
@@ -1117,23 +520,23 @@ struct Svgp : SvgpBase {
     for (int q = 0; q < PF_SIDE; ++q) {
       if (pf_side[q]) {
         (void)hipStreamSynchronize(pf_side[q]);
-        dcheck(hipStreamDestroy(pf_side[q]), __LINE__);
+        dcheck(hipStreamDestroy(pf_side[q]), __FILE_NAME__, __LINE__);
       }
-      if (pf_join[q]) dcheck(hipEventDestroy(pf_join[q]), __LINE__);
+      if (pf_join[q]) dcheck(hipEventDestroy(pf_join[q]), __FILE_NAME__, __LINE__);
     }
-    if (pf_fork) dcheck(hipEventDestroy(pf_fork), __LINE__);
+    if (pf_fork) dcheck(hipEventDestroy(pf_fork), __FILE_NAME__, __LINE__);
     if (elbo_pin) {
-      dcheck(hipHostFree(elbo_pin), __LINE__);
+      dcheck(hipHostFree(elbo_pin), __FILE_NAME__, __LINE__);
       for (auto& e : elbo_ev)
-        if (e) dcheck(hipEventDestroy(e), __LINE__);
+        if (e) dcheck(hipEventDestroy(e), __FILE_NAME__, __LINE__);
     }
-    if (pf_stream) dcheck(hipStreamDestroy(pf_stream), __LINE__);
+    if (pf_stream) dcheck(hipStreamDestroy(pf_stream), __FILE_NAME__, __LINE__);
     for (auto q : sig)
-      if (q) dcheck(hipFree(q), __LINE__);
-    if (arrive_dev) dcheck(hipFree(arrive_dev), __LINE__);
-    if (pf_done) dcheck(hipEventDestroy(pf_done), __LINE__);
+      if (q) dcheck(hipFree(q), __FILE_NAME__, __LINE__);
+    if (arrive_dev) dcheck(hipFree(arrive_dev), __FILE_NAME__, __LINE__);
+    if (pf_done) dcheck(hipEventDestroy(pf_done), __FILE_NAME__, __LINE__);
     for (auto e : step_done)
-      if (e) dcheck(hipEventDestroy(e), __LINE__);
+      if (e) dcheck(hipEventDestroy(e), __FILE_NAME__, __LINE__);
     T* ps[] = {rbuf2, wbuf2, pw0, pw1, Kt, muf, varf, cbuf, theta, gamma, rbuf, wbuf, alpha, beta, gsum, alpha_save, emuf,
                evarf, stats, Tw, Tw2, tmpv, lr_dev, Kstar, ppm, ppv, pmu, pvar, s00buf, pg_W, pg_gm, pg_gv};
     for (T* p : ps)
@@ -5888,455 +5291,8 @@ const char* agp_last_error(agp_ctx* ctx) { return ctx ? ctx->err.c_str() : "null
 
 }  // extern "C"
 
-// ---- building blocks ---------------------------------------------------------------------------------------------
-template <typename T>
-static agp_status bb_kernelmatrix(agp_ctx* ctx, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
-                                  const int64_t* idx, const void* y, int64_t p, int64_t ldy, int64_t D, void* out,
-                                  int64_t ldo) {
-  std::vector<T> hs(D);
-  for (int64_t d = 0; d < D; ++d) hs[d] = (T)(k->ard ? k->ard_scales_host[d] : k->scale);
-  T* ds = nullptr;
-  AGPCHK(dmalloc(ctx, &ds, D));
-  HIPCHK(ctx, hipMemcpyAsync(ds, hs.data(), sizeof(T) * D, hipMemcpyHostToDevice, ctx->stream));
-  const bool sym = (y == nullptr);
-  const void* yy = sym ? x : y;
-  const int64_t pp = sym ? n : p, ldyy = sym ? ldx : ldy;
-  dim3 g((unsigned)((pp + TILE - 1) / TILE), (unsigned)((n + TILE - 1) / TILE));
-  const int slices = launch_kernelmatrix<T>(ctx, ctx->stream, (const T*)x, ldx, idx, n, (const T*)yy, ldyy,
-                     pp, D, (const T*)ds, k->kind, (T)k->variance, (T*)out, ldo, n, pp, 0, T(0), (const T*)nullptr,
-                     (T*)nullptr, (int64_t)0);
-  hipError_t e = hipGetLastError();
-  const hipError_t es = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(ds);
-  if (slices < 0) {  // the scratch for the scaled Y side could not be allocated: nothing was launched
-    ctx->err = "agp_kernelmatrix: out of device memory";
-    return AGP_ERR_NOMEM;
-  }
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    ctx->err = hipGetErrorString(e);
-    return AGP_ERR_HIP;
-  }
-  return AGP_OK;
-}
-
-// copy A (n x n, lda) into a padded np x np buffer (identity padding), add jitter on the diagonal
-template <typename T>
-static agp_status pad_spd(agp_ctx* ctx, const void* a, int64_t lda, int64_t n, double jitter, T** Ap, int64_t* np) {
-  *np = rup64(n);
-  AGPCHK(dmalloc(ctx, Ap, (*np) * (*np)));
-  hipLaunchKernelGGL((k_copy2d<T>), grid2(*np, *np), blk2, 0, ctx->stream, (const T*)a, lda, n, n, *Ap, *np, *np, *np,
-                     T(1), T(1));
-  if (jitter != 0.0)
-    hipLaunchKernelGGL((k_add_diag<T>), grid1(n), dim3(256), 0, ctx->stream, *Ap, *np, n, (T)jitter);
-  LAUNCHCHK(ctx);
-  return AGP_OK;
-}
-
-template <typename T>
-static agp_status bb_potrf(agp_ctx* ctx, void* a, int64_t lda, int64_t n, double jitter, int32_t* info_host) {
-  T *Ap = nullptr, *X = nullptr;
-  int32_t* info = nullptr;
-  int64_t np;
-  AGPCHK(pad_spd<T>(ctx, a, lda, n, jitter, &Ap, &np));
-  AGPCHK(dmalloc(ctx, &X, np * np));
-  AGPCHK(dmalloc(ctx, &info, 1));
-  HIPCHK(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
-  T* Dg = nullptr;
-  AGPCHK(dmalloc(ctx, &Dg, np * TILE));
-  PotrfReq<T> rq{};
-  rq.A = Ap, rq.ld = np, rq.n = np, rq.X = X, rq.ldx = np, rq.Dg = Dg, rq.info_dev = info, rq.nvalid = n;
-  AGPCHK(potrf_fused<T>(ctx, rq));
-  if (chol_use_dag(ctx, np / TILE)) {
-    bool lost = false;
-    AGPCHK(dag_lost_dependency(ctx, info, &lost));
-    if (lost) {  // the input is still intact in `a`: pad it again and factor with per-column launches
-      hipLaunchKernelGGL((k_copy2d<T>), grid2(np, np), blk2, 0, ctx->stream, (const T*)a, lda, n, n, Ap, np, np, np, T(1), T(1));
-      if (jitter != 0.0) hipLaunchKernelGGL((k_add_diag<T>), grid1(n), dim3(256), 0, ctx->stream, Ap, np, n, (T)jitter);
-      AGPCHK(potrf_fused<T>(ctx, rq));
-    }
-  }
-  hipLaunchKernelGGL((k_publish_diag<T>), dim3((unsigned)(np / TILE)), dim3(256), 0, ctx->stream, Ap, np, (const T*)Dg);
-  HIPCHK(ctx, hipMemcpy2DAsync(a, sizeof(T) * lda, Ap, sizeof(T) * np, sizeof(T) * n, n, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-  hipLaunchKernelGGL((k_zero_strict_upper<T>), grid2(n, n), blk2, 0, ctx->stream, (T*)a, lda, n);
-  int32_t hinfo = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&hinfo, info, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (info_host) *info_host = hinfo;
-  (void)hipFree(Ap);
-  (void)hipFree(X);
-  (void)hipFree(Dg);
-  (void)hipFree(info);
-  if (hinfo != 0) {
-    ctx->err = "PosDefException: matrix is not positive definite; leading minor " + std::to_string(hinfo);
-    return AGP_ERR_NOT_POSDEF;
-  }
-  return AGP_OK;
-}
-
-template <typename T>
-static agp_status bb_spd_inverse(agp_ctx* ctx, const void* a, int64_t lda, int64_t n, void* ainv, int64_t ldi,
-                                 double* logdet_host, int32_t* info_host, T** keep_inv_padded, int64_t* np_out) {
-  T *Ap = nullptr, *X = nullptr, *Tw = nullptr, *Inv = nullptr;
-  int32_t* info = nullptr;
-  double* sc = nullptr;
-  int64_t np;
-  AGPCHK(pad_spd<T>(ctx, a, lda, n, 0.0, &Ap, &np));
-  AGPCHK(dmalloc(ctx, &X, np * np));
-  AGPCHK(dmalloc(ctx, &Tw, np * np));
-  AGPCHK(dmalloc(ctx, &Inv, np * np));
-  AGPCHK(dmalloc(ctx, &info, 1));
-  AGPCHK(dmalloc(ctx, &sc, 1));
-  HIPCHK(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
-  PotrfReq<T> rq{};
-  rq.A = Ap, rq.ld = np, rq.n = np, rq.X = X, rq.ldx = np, rq.Dg = Tw, rq.do_x = 1, rq.info_dev = info, rq.nvalid = n;
-  AGPCHK(potrf_fused<T>(ctx, rq));
-  if (chol_use_dag(ctx, np / TILE)) {
-    bool lost = false;
-    AGPCHK(dag_lost_dependency(ctx, info, &lost));
-    if (lost) {
-      hipLaunchKernelGGL((k_copy2d<T>), grid2(np, np), blk2, 0, ctx->stream, (const T*)a, lda, n, n, Ap, np, np, np, T(1), T(1));
-      AGPCHK(potrf_fused<T>(ctx, rq));
-    }
-  }
-  AGPCHK(xtx_padded<T>(ctx, X, np, np, Inv, np));
-  hipLaunchKernelGGL((k_logdiag_sum<T>), dim3(1), dim3(1024), 0, ctx->stream, (const T*)Tw, n, sc);
-  LAUNCHCHK(ctx);
-  if (ainv)
-    HIPCHK(ctx, hipMemcpy2DAsync(ainv, sizeof(T) * ldi, Inv, sizeof(T) * np, sizeof(T) * n, n, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-  int32_t hinfo = 0;
-  double hl = 0;
-  HIPCHK(ctx, hipMemcpyAsync(&hinfo, info, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(&hl, sc, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (info_host) *info_host = hinfo;
-  if (logdet_host) *logdet_host = 2.0 * hl;
-  (void)hipFree(Ap);
-  (void)hipFree(X);
-  (void)hipFree(Tw);
-  (void)hipFree(info);
-  (void)hipFree(sc);
-  if (keep_inv_padded) {
-    *keep_inv_padded = Inv;
-    *np_out = np;
-  } else {
-    (void)hipFree(Inv);
-  }
-  if (hinfo != 0) {
-    ctx->err = "PosDefException: matrix is not positive definite; leading minor " + std::to_string(hinfo);
-    return AGP_ERR_NOT_POSDEF;
-  }
-  return AGP_OK;
-}
-
-template <typename T>
-static agp_status bb_solve_right(agp_ctx* ctx, const void* a, int64_t lda, int64_t n, const void* b, int64_t ldb,
-                                 int64_t r, void* x, int64_t ldx, int32_t* info_host) {
-  T* Inv = nullptr;
-  int64_t np = 0;
-  agp_status s = bb_spd_inverse<T>(ctx, a, lda, n, nullptr, 0, nullptr, info_host, &Inv, &np);
-  if (s != AGP_OK) {
-    if (Inv) (void)hipFree(Inv);
-    return s;
-  }
-  const int64_t rp = rup64(r);
-  T *Bp = nullptr, *Xp = nullptr;
-  AGPCHK(dmalloc(ctx, &Bp, rp * np));
-  AGPCHK(dmalloc(ctx, &Xp, rp * np));
-  // zero the padded rows/cols of B (pad_diag = 0) ; padded block of Inv is the identity
-  hipLaunchKernelGGL((k_copy2d_zero<T>), grid2(rp, np), blk2, 0, ctx->stream, (const T*)b, ldb, r, n, Bp, np, rp, np);
-  LAUNCHCHK(ctx);
-  AGPCHK((gemm_nt<T, EPI_STORE>(ctx, Bp, np, Inv, np, rp, np, np, 0, Xp, np, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-  HIPCHK(ctx, hipMemcpy2DAsync(x, sizeof(T) * ldx, Xp, sizeof(T) * np, sizeof(T) * n, r, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  (void)hipFree(Inv);
-  (void)hipFree(Bp);
-  (void)hipFree(Xp);
-  return AGP_OK;
-}
-
-template <typename T>
-static agp_status bb_mfma_peak(agp_ctx* ctx, double* tflops) {
-  const int blocks = 256 * 8, iters = 4096;
-  T* out = nullptr;
-  AGPCHK(dmalloc(ctx, &out, (int64_t)blocks * NTHREADS));
-  hipEvent_t e0, e1;
-  HIPCHK(ctx, hipEventCreate(&e0));
-  HIPCHK(ctx, hipEventCreate(&e1));
-  hipLaunchKernelGGL((k_mfma_peak<T>), dim3(blocks), dim3(NTHREADS), 0, ctx->stream, out, 64);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-  hipLaunchKernelGGL((k_mfma_peak<T>), dim3(blocks), dim3(NTHREADS), 0, ctx->stream, out, iters);
-  HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-  HIPCHK(ctx, hipEventSynchronize(e1));
-  float ms = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
-  const double flops = (double)blocks * (NTHREADS / 64) * (double)iters * 8.0 * 2.0 * 16 * 16 * 4;
-  *tflops = flops / (ms * 1e-3) / 1e12;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(out);
-  return AGP_OK;
-}
-
-template <typename T, int VAR>
-static agp_status bb_diag_bench(agp_ctx* ctx, int blocks, int reps, double* us) {
-  T *A = nullptr, *out = nullptr;
-  int32_t* info = nullptr;
-  AGPCHK(dmalloc(ctx, &A, TILE * TILE));
-  AGPCHK(dmalloc(ctx, &out, (int64_t)blocks * 2 * TILE * TILE));
-  AGPCHK(dmalloc(ctx, &info, 1));
-  std::vector<T> h(TILE * TILE);
-  for (int i = 0; i < TILE; ++i)
-    for (int j = 0; j < TILE; ++j) h[i * TILE + j] = (T)((i == j ? 2.0 : 0.0) + 0.5 / (1.0 + std::abs(i - j)));
-  HIPCHK(ctx, hipMemcpy(A, h.data(), sizeof(T) * TILE * TILE, hipMemcpyHostToDevice));
-  HIPCHK(ctx, hipMemset(info, 0, 4));
-  hipEvent_t e0, e1;
-  HIPCHK(ctx, hipEventCreate(&e0));
-  HIPCHK(ctx, hipEventCreate(&e1));
-  hipLaunchKernelGGL((k_diag_bench<T, VAR>), dim3(blocks), dim3(CHOL_THREADS), 0, ctx->stream, (const T*)A, out, 2, info);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
-  hipLaunchKernelGGL((k_diag_bench<T, VAR>), dim3(blocks), dim3(CHOL_THREADS), 0, ctx->stream, (const T*)A, out, reps, info);
-  HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
-  HIPCHK(ctx, hipEventSynchronize(e1));
-  float ms = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&ms, e0, e1));
-  *us = ms * 1e3 / reps;
-  {  // residuals of block 0 (development aid): |L L' - A|, |X L - I|, strict-upper leakage
-     // (VAR 13, "2-level, no X21": the inverse part is [[X11, 0], [L21, X22]] -- |X11 L11 - I|, |X22 L22 - I|, the L21 block exact)
-    constexpr bool nox21 = VAR == 13;
-    std::vector<T> o(2 * TILE * TILE);
-    HIPCHK(ctx, hipMemcpy(o.data(), out, sizeof(T) * 2 * TILE * TILE, hipMemcpyDeviceToHost));
-    const T* Lh = o.data();
-    const T* Xh = o.data() + TILE * TILE;
-    double e1m = 0, e2m = 0, e3m = 0;
-    for (int i = 0; i < TILE; ++i)
-      for (int j = 0; j < TILE; ++j) {
-        double s1 = 0, s2 = 0;
-        const int kb = nox21 ? (i / 32) * 32 : 0, ke = nox21 ? kb + 32 : TILE;
-        for (int k = 0; k < TILE; ++k) {
-          s1 += (double)Lh[i * TILE + k] * (double)Lh[j * TILE + k];
-          if (k >= kb && k < ke) s2 += (double)Xh[i * TILE + k] * (double)Lh[k * TILE + j];
-        }
-        e1m = std::max(e1m, std::abs(s1 - (double)h[i * TILE + j]));
-        if (nox21 && i / 32 != j / 32) e2m = std::max(e2m, std::abs((double)Xh[i * TILE + j] - (j < i ? (double)Lh[i * TILE + j] : 0.0)));
-        else e2m = std::max(e2m, std::abs(s2 - (i == j ? 1.0 : 0.0)));
-        if (j > i) e3m = std::max(e3m, std::abs((double)Lh[i * TILE + j]) + std::abs((double)Xh[i * TILE + j]));
-      }
-    const double tol = sizeof(T) == 8 ? 1e-12 : 1e-4;
-    if (!(e1m < tol) || !(e2m < tol) || e3m != 0.0) {
-      ctx->err = "diag_bench residual check failed";
-      return AGP_ERR_NOT_POSDEF;
-    }
-  }
-  (void)hipFree(A);
-  (void)hipFree(out);
-  (void)hipFree(info);
-  return AGP_OK;
-}
-
-
-// ---- inducing-point selection: nearest-centre assignment and Lloyd iterations (agp_kmeans.h) --------------------------
-template <typename T>
-static agp_status km_assign(agp_ctx* ctx, const T* x, int64_t n, int64_t ldx, int64_t D, const T* c, int64_t ldc, int64_t m,
-                            T* cn, int32_t* labels, T* mind) {
-  const int64_t mp = rup64(m);
-  const int Dp = (int)((D + 15) / 16 * 16);
-  hipLaunchKernelGGL((k_km_cnorm<T>), grid1(mp), dim3(256), 0, ctx->stream, c, ldc, m, mp, D, cn);
-  const size_t sh = sizeof(T) * (2 * TILE * (Dp + 2) + 4 * TILE) + sizeof(int) * 2 * TILE;
-  if (sh > 64 * 1024)  // gfx950 has 160 KB of LDS per workgroup; more than 64 KB of dynamic LDS has to be requested
-    HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_km_assign<T>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-  hipLaunchKernelGGL((k_km_assign<T>), dim3((unsigned)((n + TILE - 1) / TILE)), dim3(NTHREADS), sh, ctx->stream, x, ldx, n, D,
-                     Dp, c, ldc, m, mp, (const T*)cn, labels, mind);
-  LAUNCHCHK(ctx);
-  return AGP_OK;
-}
-
-template <typename T>
-static agp_status km_objective(agp_ctx* ctx, const T* mind, int64_t n, double* part, double* host) {
-  const int nb = 256;
-  hipLaunchKernelGGL((k_km_sum_partial<T>), dim3(nb), dim3(256), 0, ctx->stream, mind, n, part);
-  hipLaunchKernelGGL(k_km_sum_final, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, nb, part + nb);
-  LAUNCHCHK(ctx);
-  HIPCHK(ctx, hipMemcpyAsync(host, part + nb, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return AGP_OK;
-}
-
-template <typename T>
-static agp_status bb_nearest(agp_ctx* ctx, const void* x, int64_t n, int64_t ldx, int64_t D, const void* c, int64_t ldc,
-                             int64_t m, int32_t* labels, void* mind) {
-  if (!x || !c || n <= 0 || m <= 0 || D <= 0 || D > KM_MAXD || ldx < D || ldc < D || (!labels && !mind)) return AGP_ERR_INVALID;
-  T* cn = nullptr;
-  int32_t* lab = labels;
-  T* md = (T*)mind;
-  agp_status st = dmalloc(ctx, &cn, rup64(m));
-  if (st == AGP_OK && !lab) st = dmalloc(ctx, &lab, n);
-  if (st == AGP_OK && !md) st = dmalloc(ctx, &md, n);
-  if (st == AGP_OK) {
-    st = km_assign<T>(ctx, (const T*)x, n, ldx, D, (const T*)c, ldc, m, cn, lab, md);
-    (void)hipStreamSynchronize(ctx->stream);
-  }
-  (void)hipFree(cn);
-  if (!labels) (void)hipFree(lab);
-  if (!mind) (void)hipFree(md);
-  return st;
-}
-
-template <typename T>
-static agp_status bb_kmeans(agp_ctx* ctx, const void* xv, int64_t n, int64_t ldx, int64_t D, void* cv, int64_t ldc,
-                            int64_t m, int max_iter, double tol, int32_t* labels_out, int32_t* counts_out, int32_t* iters,
-                            double* objective, int32_t* converged) {
-  if (!xv || !cv || n <= 0 || m <= 0 || m > n || D <= 0 || D > KM_MAXD || ldx < D || ldc < D || max_iter < 0)
-    return AGP_ERR_INVALID;
-  const T* x = (const T*)xv;
-  T* c = (T*)cv;
-  const int64_t mp = rup64(m);
-  const int Dp = (int)((D + 15) / 16 * 16);
-  const int nchunks = (int)((n + KM_CHUNK - 1) / KM_CHUNK);
-  T *cn = nullptr, *mind = nullptr, *part = nullptr;
-  double* red = nullptr;
-  int32_t *lab = labels_out, *blist = nullptr, *boff = nullptr;
-  if (mp / TILE > KM_MAXTILES) {
-    ctx->err = "agp_kmeans: more than 16384 centres";
-    return AGP_ERR_UNSUPPORTED;
-  }
-  auto release = [&]() {  // (hipFree(nullptr) is a no-op: whatever a failed dmalloc left unallocated)
-    (void)hipFree(cn);
-    (void)hipFree(mind);
-    (void)hipFree(part);
-    (void)hipFree(red);
-    (void)hipFree(blist);
-    (void)hipFree(boff);
-    if (!labels_out) (void)hipFree(lab);
-  };
-  agp_status st = dmalloc(ctx, &cn, mp);
-  if (st == AGP_OK) st = dmalloc(ctx, &mind, n);
-  if (st == AGP_OK) st = dmalloc(ctx, &part, (int64_t)nchunks * mp * (Dp + 16));
-  if (st == AGP_OK) st = dmalloc(ctx, &red, 512);
-  if (st == AGP_OK) st = dmalloc(ctx, &blist, (int64_t)nchunks * KM_CHUNK);
-  if (st == AGP_OK) st = dmalloc(ctx, &boff, (int64_t)nchunks * (KM_MAXTILES + 1));
-  if (st == AGP_OK && !lab) st = dmalloc(ctx, &lab, n);
-  if (st != AGP_OK) {
-    release();
-    return st;
-  }
-  double obj = 0.0, prev = 0.0;
-  int it = 0, conv = 0;
-  // Clustering.kmeans!: assignments for the seeds, then { centres <- cluster means ; assignments ; |change of cost| < tol }
-  st = km_assign<T>(ctx, x, n, ldx, D, c, ldc, m, cn, lab, mind);
-  if (st == AGP_OK) st = km_objective<T>(ctx, mind, n, red, &obj);
-  while (st == AGP_OK && it < max_iter && !conv) {
-    ++it;
-    hipLaunchKernelGGL(k_km_bucket, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream, (const int32_t*)lab, n,
-                       (int)(mp / TILE), blist, boff);
-    hipLaunchKernelGGL((k_km_sums<T>), dim3((unsigned)(mp / TILE), (unsigned)nchunks), dim3(NTHREADS), 0, ctx->stream, x, ldx, n,
-                       D, Dp, (const int32_t*)lab, mp, (const int32_t*)blist, (const int32_t*)boff, part);
-    hipLaunchKernelGGL((k_km_finish<T>), grid1(m * D), dim3(256), 0, ctx->stream, (const T*)part, nchunks, mp, Dp, m, D, c, ldc);
-    if (hipGetLastError() != hipSuccess) {
-      st = AGP_ERR_HIP;
-      break;
-    }
-    st = km_assign<T>(ctx, x, n, ldx, D, c, ldc, m, cn, lab, mind);
-    prev = obj;
-    if (st == AGP_OK) st = km_objective<T>(ctx, mind, n, red, &obj);
-    if (m == 1 || std::abs(obj - prev) < tol) conv = 1;
-  }
-  if (st == AGP_OK && counts_out) {  // the histogram of the final assignment (also the only one, for max_iter = 0)
-    if (hipMemsetAsync(counts_out, 0, sizeof(int32_t) * (size_t)m, ctx->stream) != hipSuccess) st = AGP_ERR_HIP;
-    if (st == AGP_OK) {
-      hipLaunchKernelGGL(k_km_hist, dim3((unsigned)nchunks), dim3(256), sizeof(int) * (size_t)m, ctx->stream, (const int32_t*)lab, n,
-                         (int)m, counts_out);
-      if (hipGetLastError() != hipSuccess) st = AGP_ERR_HIP;
-    }
-  }
-  (void)hipStreamSynchronize(ctx->stream);
-  release();
-  if (iters) *iters = it;
-  if (objective) *objective = obj;
-  if (converged) *converged = conv;
-  return st;
-}
-
-// ---- inducing-point selection: greedy conditional variance, a pivoted partial Cholesky of K_NN (agp_greedy.h) --------------------
-template <typename T>
-static agp_status bb_greedy(agp_ctx* ctx, const agp_kernel_desc* k, const void* xv, int64_t n, int64_t ldx, int64_t D, int64_t m,
-                            double tol, int64_t* idx_out, void* zv, int64_t ldz, void* factor_out, int64_t ldf, double* trace_out,
-                            int64_t* n_selected_host) {
-  const T* x = (const T*)xv;
-  T* z = (T*)zv;
-  const int64_t Np = (n + GV_BLOCK - 1) / GV_BLOCK * GV_BLOCK, nblk = Np / GV_BLOCK;
-  double *F = nullptr, *Xt = nullptr, *dres = nullptr, *aux = nullptr;
-  GvPart* part = nullptr;
-  GvState* st = nullptr;
-  auto release = [&]() {
-    (void)hipFree(F);
-    (void)hipFree(Xt);
-    (void)hipFree(dres);
-    (void)hipFree(aux);
-    (void)hipFree(part);
-    (void)hipFree(st);
-  };
-  // the factor, column-contiguous: 8 n m bytes (n padded to the workgroup)
-  if (m > (int64_t)(INT64_MAX / 8) / Np || hipMalloc((void**)&F, sizeof(double) * (size_t)(m * Np)) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "agp_greedy_variance: cannot allocate the factor workspace of " +
-               (m > (int64_t)(INT64_MAX / 8) / Np ? std::string("more than 2^63") : std::to_string(8 * m * Np)) + " bytes (8 n m)";
-    return AGP_ERR_NOMEM;
-  }
-  agp_status s = dmalloc(ctx, &Xt, D * Np);
-  if (s == AGP_OK) s = dmalloc(ctx, &dres, Np);
-  if (s == AGP_OK) s = dmalloc(ctx, &aux, 2 * GV_MAXD + m);  // scales | pivot coordinates | pivot coefficient row
-  if (s == AGP_OK) s = dmalloc(ctx, &part, nblk);
-  if (s == AGP_OK) s = dmalloc(ctx, &st, 1);
-  if (s != AGP_OK) {
-    release();
-    return s;
-  }
-  double *scales = aux, *zp = aux + GV_MAXD, *lp = aux + 2 * GV_MAXD;
-  std::vector<double> hs(D);
-  for (int64_t d = 0; d < D; ++d) hs[d] = k->ard ? k->ard_scales_host[d] : k->scale;
-  hipError_t e = hipMemcpyAsync(scales, hs.data(), sizeof(double) * D, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(F, 0, sizeof(double) * (size_t)(m * Np), ctx->stream);  // columns behind an early stop: 0
-  if (e == hipSuccess) e = hipMemsetAsync(st, 0, sizeof(GvState), ctx->stream);
-  if (e == hipSuccess) {
-    const int64_t tiles = ((n + 31) / 32) * ((D + 31) / 32);
-    hipLaunchKernelGGL((k_gv_transpose<T>), dim3((unsigned)tiles), dim3(32, 8), 0, ctx->stream, x, ldx, n, D, Xt, Np);
-    hipLaunchKernelGGL((k_gv_prefill<T>), grid1(m * D), dim3(256), 0, ctx->stream, m, (int)D, idx_out, z, ldz, trace_out);
-    hipLaunchKernelGGL(k_gv_init, dim3((unsigned)nblk), dim3(GV_BLOCK), 0, ctx->stream, n, k->variance, dres, part);
-    const double thr = tol * k->variance;
-    for (int64_t j = -1; j < m; ++j) {
-      if (j >= 0)
-        hipLaunchKernelGGL(k_gv_step, dim3((unsigned)nblk), dim3(GV_BLOCK), 0, ctx->stream, (const double*)Xt,
-                           (const double*)scales, n, Np, (int)D, (int)k->kind, k->variance, j, F, dres, (const GvState*)st,
-                           (const double*)zp, (const double*)lp, part);
-      hipLaunchKernelGGL((k_gv_finish<T>), dim3(1), dim3(GV_BLOCK), 0, ctx->stream, (const GvPart*)part, nblk, j, m, thr, x, ldx,
-                         (int)D, (const double*)F, Np, st, zp, lp, idx_out, z, ldz, trace_out);
-    }
-    if (factor_out) {
-      const int64_t ft = ((m + 31) / 32) * ((n + 31) / 32);
-      hipLaunchKernelGGL((k_gv_transpose<double>), dim3((unsigned)ft), dim3(32, 8), 0, ctx->stream, (const double*)F, Np, m, n,
-                         (double*)factor_out, ldf);
-    }
-    e = hipGetLastError();
-  }
-  GvState hst{};
-  if (e == hipSuccess) e = hipMemcpyAsync(&hst, st, sizeof(GvState), hipMemcpyDeviceToHost, ctx->stream);
-  const hipError_t es = hipStreamSynchronize(ctx->stream);  // the one synchronisation of the call
-  release();
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    ctx->err = std::string("agp_greedy_variance : ") + hipGetErrorString(e);
-    return AGP_ERR_HIP;
-  }
-  if (n_selected_host) *n_selected_host = hst.nsel;
-  return AGP_OK;
-}
+#include "agp_blocks_host.h"
+#include "agp_select_host.h"
 
 #define DISPATCH(dtype, call_f64, call_f32)        \
   do {                                             \
@@ -7276,124 +6232,7 @@ agp_status agp_comm_info(agp_comm* cm, int32_t* rank_host, int32_t* world_host, 
 
 }  // extern "C"
 
-// one in-place sum on `stream` through whichever transport the communicator has
-static agp_status comm_issue(agp_comm* cm, void* buf, int64_t count, int32_t dtype, hipStream_t stream) {
-  agp_ctx* ctx = cm->ctx;
-  if (cm->kind == 0) {
-    std::string why;
-    RcclApi* api = rccl_api(why);
-    if (!api) return AGP_ERR_UNSUPPORTED;
-    ncclResult_t r = api->AllReduce(buf, buf, (size_t)count, dtype == AGP_F64 ? ncclFloat64 : ncclFloat32, ncclSum, cm->nccl, stream);
-    if (r != ncclSuccess) {
-      ctx->err = std::string("ncclAllReduce : ") + api->GetErrorString(r);
-      return AGP_ERR_HIP;
-    }
-  } else {
-    const int32_t r = cm->fn(cm->user, buf, count, dtype, (void*)stream);
-    if (r != 0) {
-      ctx->err = "agp_comm: the host all-reduce callback failed with code " + std::to_string(r);
-      return AGP_ERR_HIP;
-    }
-  }
-  return AGP_OK;
-}
-static agp_status comm_timing_begin(agp_comm* cm, hipStream_t stream) {
-  agp_ctx* ctx = cm->ctx;
-  cm->timing_now = cm->timing && ((cm->n_calls - 1) % cm->timing_every == 0);
-  if (cm->timing_now) {
-    if (cm->ev_used + 2 > cm->ev.size())
-      for (int i = 0; i < 2; ++i) {
-        hipEvent_t e;
-        HIPCHK(ctx, hipEventCreate(&e));
-        cm->ev.push_back(e);
-      }
-    HIPCHK(ctx, hipEventRecord(cm->ev[cm->ev_used], stream));
-  }
-  return AGP_OK;
-}
-static agp_status comm_timing_end(agp_comm* cm, hipStream_t stream) {
-  agp_ctx* ctx = cm->ctx;
-  if (cm->timing_now) {
-    HIPCHK(ctx, hipEventRecord(cm->ev[cm->ev_used + 1], stream));
-    cm->ev_used += 2;
-    cm->n_timed += 1;
-  }
-  return AGP_OK;
-}
-
-// AGP_SPLIT_OVERLAP: the batch-parallel statistics as a train of `ng` ranges (block-column groups, agp_chol.h pack_index) on the
-// communicator's OWN stream, ordered after what the ctx's stream holds now; after range g a one-thread kernel stores `epoch` into
-// arrive[g * ARRIVE_STRIDE], which the tile workgroups of the NEXT task-graph launch poll (pro_arrival_gate) -- that launch is
-// enqueued on the ctx's stream right away and starts on group 0 while the others are still travelling.  Nothing on the ctx's stream
-// waits for the train (cm->ev_out is there for a flush that wants the whole statistic).  Counted as ONE collective call of the sum
-// of the ranges for agp_comm_stats; with timing on, the events bracket the whole train on the side stream.
-static agp_status comm_allreduce_groups(agp_comm* cm, void* base, int esz, const int64_t* off, const int64_t* cnt, int ng,
-                                        int32_t dtype, int32_t* arrive, int32_t epoch) {
-  agp_ctx* ctx = cm->ctx;
-  DevGuard guard(ctx->device);
-  if (!cm->side) {
-    int lo = 0, hi = 0;
-    HIPCHK(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIPCHK(ctx, hipStreamCreateWithPriority(&cm->side, hipStreamNonBlocking, hi));
-    HIPCHK(ctx, hipEventCreateWithFlags(&cm->ev_in, hipEventDisableTiming));
-    HIPCHK(ctx, hipEventCreateWithFlags(&cm->ev_out, hipEventDisableTiming));
-  }
-  HIPCHK(ctx, hipEventRecord(cm->ev_in, ctx->stream));
-  HIPCHK(ctx, hipStreamWaitEvent(cm->side, cm->ev_in, 0));
-  cm->n_calls += 1;
-  AGPCHK(comm_timing_begin(cm, cm->side));
-  for (int g = 0; g < ng; ++g) {
-    cm->bytes += cnt[g] * esz;
-    AGPCHK(comm_issue(cm, (char*)base + off[g] * esz, cnt[g], dtype, cm->side));
-    hipLaunchKernelGGL(k_set_arrive, dim3(1), dim3(1), 0, cm->side, arrive + g * ARRIVE_STRIDE, epoch);
-    LAUNCHCHK(ctx);
-  }
-  AGPCHK(comm_timing_end(cm, cm->side));
-  HIPCHK(ctx, hipEventRecord(cm->ev_out, cm->side));
-  return AGP_OK;
-}
-
-// ---- stand-in for an xGMI ring all-reduce on a one-GPU box (diagnostic; agp_comm_standin_allreduce) -------------------------------
-// RCCL's ring kernel is a handful of workgroups ("channels") that pass chunks to one another through flags: it only finishes when all
-// of them are RESIDENT at the same time.  A sleep kernel in the collective's place does not exercise that; this one does: n_wg
-// workgroups meet at a grid barrier (every one must have a CU), move the buffer through their registers chunk by chunk (sum over one
-// rank = the values they found), meet again, and do not return before min_us have passed.  The barrier counter only grows (two
-// arrivals per workgroup and launch): launches on one stream are ordered, which is how the callback transport uses it.  The spins
-// are bounded (about a second): a stand-in that cannot become resident reports it through `stuck` instead of hanging the device.
-__device__ unsigned long long g_standin_bar;
-__global__ void k_standin_allreduce(unsigned long long* __restrict__ buf8, int64_t n8, unsigned long long base, double min_us,
-                                    int32_t* __restrict__ stuck) {
-  const unsigned long long t0 = wall_clock64();  // 100 MHz constant clock
-  const unsigned long long n_wg = gridDim.x;
-  __shared__ int ok;
-  auto meet = [&](unsigned long long target) {
-    if (threadIdx.x == 0) {
-      __hip_atomic_fetch_add(&g_standin_bar, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      long spins = 0;
-      ok = 1;
-      while (__hip_atomic_load(&g_standin_bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > (1L << 22)) {
-          ok = 0;
-          if (stuck) atomicAdd(stuck, 1);
-          break;
-        }
-      }
-    }
-    __syncthreads();
-    return ok != 0;
-  };
-  const bool all_here = meet(base + n_wg);
-  if (all_here)
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)n_wg * blockDim.x) {
-      const unsigned long long v = __hip_atomic_load(buf8 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(buf8 + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  (void)meet(base + 2 * n_wg);
-  if (threadIdx.x == 0)
-    while ((double)(wall_clock64() - t0) * 0.01 < min_us) __builtin_amdgcn_s_sleep(16);
-}
-static unsigned long long g_standin_launches = 0;
+#include "agp_comm_host.h"
 
 extern "C" {
 

@@ -1,5 +1,6 @@
 // agp_ctx.h -- the per-GPU context of the C ABI (agp_ctx), the error-check macros every host function returns through and the
-// small launch-geometry helpers.  Host side; included by agp_capi.hip (one translation unit) before the host drivers.
+// small launch-geometry helpers.  Host side; the bottom layer of the host headers (agp_*_host.h, agp_svgp_base.h) that agp_capi.hip (one
+// translation unit) includes.
 #pragma once
 #include "../../include/agp_hip.h"
 
@@ -116,7 +117,7 @@ static void step_trace_dump(agp_ctx*) {}
   do {                                                                                          \
     hipError_t _e = hipGetLastError();                                                          \
     if (_e != hipSuccess) {                                                                     \
-      (ctx)->err = std::string("kernel launch : ") + hipGetErrorString(_e) + " @" + std::to_string(__LINE__); \
+      (ctx)->err = std::string("kernel launch : ") + hipGetErrorString(_e) + " @" __FILE_NAME__ ":" + std::to_string(__LINE__); \
       return AGP_ERR_HIP;                                                                       \
     }                                                                                           \
   } while (0)

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/agp_hip.h"  // AGP_LIK_*
 #include "agp_cavi.h"
 
 namespace agp {
