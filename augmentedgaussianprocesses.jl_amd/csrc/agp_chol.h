@@ -1347,7 +1347,9 @@ template <typename T>
 constexpr bool dag_feed_deferred() {
   return sizeof(T) == 8;
 }
-template <typename T, bool DEFER = dag_feed_deferred<T>()>
+// DG = false (dag_store_dg below, the CAVI step's fp64 launches): nobody reads the diagonal factors of this launch, dgsrc is never set
+// and rounds 0 and 1 of the side job are empty for the idle waves -- no LDS read, no global store, no wait on vmcnt.
+template <typename T, bool DEFER = dag_feed_deferred<T>(), bool DG = true>
 struct ChainPrefetch {
   const T* src;  // hand-over slot of the parked tile (k+1, k) ; the parked diagonal tile (k+1, k+1) is the next slot
   T *dT, *dD;    // LDS destinations
@@ -1362,6 +1364,9 @@ struct ChainPrefetch {
   int ld_i;
   bool coh = false;  // the chain runs as a kernel of its own: its plain stores would only become visible when THAT kernel ends
   int test = 0;      // AGP_DAG_TEST_FEED (see above)
+#ifdef AGP_STEP_TRACE
+  unsigned long long* tlook = nullptr;  // (development builds) where the look stamps its time
+#endif
   T v[TILE * TILE / 256];
   __device__ __forceinline__ void operator()(int round) {
     int t = (int)threadIdx.x - 256;
@@ -1372,7 +1377,7 @@ struct ChainPrefetch {
     // fp64 only: the fp32 launches are far from their cap, and their register allocation is left as it was.
     if (sizeof(T) == 8) asm volatile("" : "+v"(t));
     if (round < 2) {  // L_{k-1,k-1} -> Dg, off the critical path (plain stores, read by later kernels only)
-      if (dgsrc) {
+      if (DG && dgsrc) {
 #pragma unroll
         for (int q = 0; q < TILE * TILE / 512; ++q) {
           const int e = t + (2 * q + round) * 256;
@@ -1435,7 +1440,7 @@ struct ChainPrefetch {
     asm volatile("" : "+v"(t));  // (see operator())
     if (HB == 0) {
       if (rr < 2) {  // L_{k-1,k-1} -> Dg
-        if (dgsrc) {
+        if (DG && dgsrc) {
 #pragma unroll
           for (int q = 0; q < TILE * TILE / 512; ++q) {
             const int e = t + (2 * q + rr) * 256;
@@ -1452,9 +1457,13 @@ struct ChainPrefetch {
           gL[(e >> 6) * ld_i + (e & 63)] = lsrc[(e >> 6) * LDP + (e & 63)];
         }
       }
-      if (src && rr == 3 && t == 0)  // the look: where it was, so the feeders' deadline does not move
+      if (src && rr == 3 && t == 0) {  // the look: where it was, so the feeders' deadline does not move
         *ok = (__hip_atomic_load(f1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) &&
               (__hip_atomic_load(f2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == epoch) && !(test & 2);
+#ifdef AGP_STEP_TRACE
+        if (tlook) *tlook = wall_clock64();
+#endif
+      }
       return;
     }
     if (!src || (rr != 0 && rr != 3) || !*ok) return;
@@ -1757,6 +1766,17 @@ template <typename T, bool STEP, bool BATCH>
 constexpr bool dag_block_subst() {
   return STEP && !BATCH && sizeof(T) == 8;
 }
+// Diagonal factors (Dg) of a launch, ONE decision like the two above (merged or split, ROLE 1 and 2, batched or not): the CAVI
+// step's fp64 launches store none.  Their callers mark Xa invalid, and every reader of Dg sits behind a factorisation with the
+// inverse riding along (never STEP) that writes Dg itself; an aborted step launch is repaired by k_chol_safe, which writes the Dg
+// it reads (the account is in DESIGN.md section 5: Dg is valid only while Xa is).  The chain's idle waves then have nothing to do
+// in rounds 0 and 1 of every other elimination, and the last column's publish follows its X stores directly.
+// fp32 keeps its stores: without them C3 (32 block columns, split launch) went from 0.61 to 0.87 ms per step -- its tile kernel
+// reacts to any change of the chain's pace, as in round 10 (profiles/r12_c2_chain_feed_runs.txt).
+template <typename T, bool STEP, bool BATCH>
+constexpr bool dag_store_dg() {
+  return !(STEP && sizeof(T) == 8);
+}
 template <typename T, int ROLE, bool PRO>
 constexpr int dag_min_waves() {
   return ROLE != 2 ? 1 : PRO ? (sizeof(T) == 8 ? 2 : 4) : (sizeof(T) == 8 ? AGP_TILES_WAVES_F64 : AGP_TILES_WAVES_F32);
@@ -1793,11 +1813,14 @@ struct ProdArgs {
 // stamps (100 MHz) across the boundary between two CAVI-step launches with a prologue, one record of STRACE_SLOTS words per launch.
 //   [0, 2048)     PRO_TS's points (below), X_{nt-1} published (STRACE_XPUB), per extension row R of the last block column
 //                 (STRACE_EXT + 4 (R - nt) + q): q = 0 X seen, 1 W stored and signalled, 2 v tile read (epilogue), 3 rows finished;
-//                 refill workgroup b: start STRACE_FILL0 + b, end STRACE_FILL1 + b
+//                 refill workgroup b: start STRACE_FILL0 + b, end STRACE_FILL1 + b;
+//                 the look of the side job under factor(k) (STRACE_LOOK + k) and the PRO_NEAR tiles (c + b, c) of block columns
+//                 c = 2 .. 6 that have no PRO_TS points of their own (R >= 4), STRACE_NEAR + 8 (4 (c - 2) + b) + q: q = 0 workgroup
+//                 at its prologue, 1 own product done, 2 helpers seen, 3 partials added, 4 eta2 step done, 5 parked and signalled
 //   [2048, 4096)  start, [4096, 6144) exit of workgroup b (b < 2048)
 //   [6144, 6400)  start, [6400, 6656) end of workgroup b of the deferred fallback / row-statistics launch behind it (k_safe_rowstats)
 constexpr int STRACE_SLOTS = 8192, STRACE_XPUB = 600, STRACE_EXT = 1100, STRACE_FILL0 = 1400, STRACE_FILL1 = 1500, STRACE_WG0 = 2048,
-              STRACE_WG1 = 4096, STRACE_MAXWG = 2048, STRACE_SAFE0 = 6144, STRACE_SAFE1 = 6400;
+              STRACE_WG1 = 4096, STRACE_MAXWG = 2048, STRACE_SAFE0 = 6144, STRACE_SAFE1 = 6400, STRACE_LOOK = 608, STRACE_NEAR = 640;
 #ifdef AGP_STEP_TRACE
 struct StraceExit {  // stamps the exit of its workgroup, whichever return it leaves by
   unsigned long long* p;
@@ -1828,6 +1851,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   //      bits 2, 3: AGP_DAG_TEST_FEED (test hook, ChainPrefetch::test)
   const int64_t nx = STEP ? 0 : nx_;
   constexpr bool SUBST = dag_block_subst<T, STEP, BATCH>();  // X_k travels without its off-diagonal block (nobody reads X_k as such)
+  constexpr bool STORE_DG = dag_store_dg<T, STEP, BATCH>();  // the chain leaves the diagonal factors in Dg
   const int write_x = STEP ? 0 : (opts & 1);
   const bool store_l = STEP ? false : (opts & 2) != 0;
   // nb > 1: nb independent problems of the same shape (the latents of a small multi-class model) in ONE launch, their
@@ -2063,7 +2087,12 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
     const bool pre = pro_pre_on<T>() && pro.pre && pro_pre_tile(R, c);  // prepared by the launch in front (ProArgs::pre): no helpers
     const int ksc = pre ? 1 : b < nn_ ? pro.kf[c] : pro.ks[c];
     const int64_t nq = pro.Kdim / TILE;
+#ifdef AGP_STEP_TRACE
+    const bool ts_near = !(R < 4 && c < 4) && c >= 2 && c <= 6 && b < PRO_NEAR;  // (STRACE_NEAR: the feeders of the later looks)
+    const int tsb = chain ? 0 : (R < 4 && c < 4) ? 64 + 8 * (4 * (int)R + (int)c) : ts_near ? STRACE_NEAR + 8 * (4 * ((int)c - 2) + (int)b) : 2040;
+#else
     const int tsb = chain ? 0 : (R < 4 && c < 4) ? 64 + 8 * (4 * (int)R + (int)c) : 2040;
+#endif
     PRO_TS(tsb);
     acc.zero();
     if (pre && pro.pre[PRO_PRE_VALID] == T(1)) {
@@ -2243,7 +2272,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
     for (int64_t k = 0; k < nt; ++k) {
       const int64_t k0 = k * TILE;
       T* trow = A + (k + 1) * TILE * ld;  // block row k+1 (only touched while k + 1 < nt)
-      ChainPrefetch<T> pf;
+      ChainPrefetch<T, dag_feed_deferred<T>(), STORE_DG> pf;
       pf.src = k + 1 < nt ? HP + 2 * (k + 1) * SLOT : nullptr;
       pf.bad = &pf_bad;
       pf.dT = bufC;
@@ -2252,7 +2281,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       pf.f2 = pre2 + (k + 1) * DAG_FS;
       pf.epoch = epoch;
       pf.ok = &pf_ok;
-      pf.dgsrc = k >= 1 ? bufD : nullptr;  // after the swap below bufD is where L_{k-1,k-1} still sits
+      pf.dgsrc = (STORE_DG && k >= 1) ? bufD : nullptr;  // after the swap below bufD is where L_{k-1,k-1} still sits
       pf.gDg = Dg + (k - 1) * TILE * TILE;
       pf.lsrc = (k >= 1 && store_l) ? bufC : nullptr;  // L(k, k-1) stays in bufC until the prefetch of round 5 overwrites it
       pf.gL = A + k0 * ld + (k0 - TILE);
@@ -2261,9 +2290,11 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       pf.test = (opts >> 2) & 3;
       if (tid == 0) pf_ok = pf_bad = 0;
 #ifdef AGP_STEP_TRACE
-      PRO_TS(528 + k);  // (per block column: 528 + k the elimination starts, 512 + k it ends, 560 + k the path its side job took)
+      // (per block column: 528 + k the elimination starts, 512 + k it ends, 560 + k the path its side job took, STRACE_LOOK + k its look)
+      PRO_TS(528 + k);
+      pf.tlook = (PRO && trace) ? trace + STRACE_LOOK + k : nullptr;
 #endif
-      factor_diag_tile_2lvl<T, ChainPrefetch<T>, SUBST>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
+      factor_diag_tile_2lvl<T, decltype(pf), SUBST>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
       DAG_TRC(k, 2);
       PRO_TS(512 + k);
       {  // X_k out (coherent): all LDS reads first, then the stores back to back (a read-store-read-store loop exposed the
@@ -2285,9 +2316,11 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
         // (the real X block is only read when the full inverse was requested, and then the identity-row tile (k, k) writes it)
       }
       if (k + 1 == nt) {
-        for (int e = tid; e < TILE * TILE; e += CHOL_THREADS) {
-          if (ROLE == 1) __hip_atomic_store(Dg + k * TILE * TILE + e, bufA[(e >> 6) * LDP + (e & 63)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          else Dg[k * TILE * TILE + e] = bufA[(e >> 6) * LDP + (e & 63)];
+        if (STORE_DG) {
+          for (int e = tid; e < TILE * TILE; e += CHOL_THREADS) {
+            if (ROLE == 1) __hip_atomic_store(Dg + k * TILE * TILE + e, bufA[(e >> 6) * LDP + (e & 63)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else Dg[k * TILE * TILE + e] = bufA[(e >> 6) * LDP + (e & 63)];
+          }
         }
         dag_signal(xready + k * DAG_FS, epoch);
         DAG_TRC(k, 3);
@@ -2444,6 +2477,9 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
     });
     dag_signal((f1 ? pre1 + (c + 1) * DAG_FS : pre2 + c * DAG_FS), epoch);
     if (R < 4 && c < 4) PRO_TS(64 + 8 * (4 * (int)R + (int)c) + 5);
+#ifdef AGP_STEP_TRACE
+    if (!(R < 4 && c < 4) && c >= 2 && c <= 6) PRO_TS(STRACE_NEAR + 8 * (4 * ((int)c - 2) + (int)b) + 5);  // (f1: b = 1, f2: b = 0)
+#endif
     if (f2) {
       DAG_TR(6);
     } else {

@@ -421,7 +421,8 @@ static bool chain_split_ready(agp_ctx* c) {
   return ok;
 }
 // Behind a split launch NO event joins the two streams: the tile kernel cannot end before the chain's last publish, after which the
-// chain writes nothing (its diagonal factors are write-through stores issued before that publish), so whatever follows on this
+// chain writes nothing (an fp64 step launch stores no diagonal factors, dag_store_dg in agp_chol.h; an fp32 one issues them as
+// write-through stores before that publish), so whatever follows on this
 // context's stream -- and a host synchronisation of it -- sees a finished factorisation.  The one exception, an aborted launch whose
 // chain is still inside a tile factorisation, is handled where it matters: the fallback waits for the chain workgroups' exit count
 // (DagSync::done, SafeSrc::chain_done).  (An event join -- record on the chain stream, wait on this one -- was the first version and
@@ -447,22 +448,42 @@ struct StepSync {
   bool used = false;  // out: the task-graph launch took `ds`
 };
 
-// k-slices per block column of the prologue's product: a tile of block column c has to be there when the chain reaches the
-// column (about tau * c after the start, tau = 17.8 us f64 / 14 us f32 per block column), a 64-row chunk of the product costs a
-// workgroup about tc = 2.7 / 1.6 us; columns 0 and 1 feed the chain at once and are split as far as it pays (8).  pre: the
-// chain's first tiles were prepared by the launch in front (ProArgs::pre), so it reaches every column ~10 us sooner (measured at
-// C2: factor(0) done 20 instead of 30 us after the start; with the old table the feeders of block column 4 came 2.8 us late)
+// k-slices per block column of the prologue's product S = kappa' diag(w) kappa: ks[c] for the tiles of block column c, kf[c] for its
+// PRO_NEAR tiles next to the diagonal (the chain's feeders).  Columns 0 and 1 feed the chain at once and are split as far as it
+// pays.  pre: the chain's first tiles were prepared by the launch in front (ProArgs::pre), so it reaches every column ~10 us sooner.
+// Two fits:
+//  * fp32, and fp64 up to three block columns -- the first fit, kept as it is (fp32 was not measured again; at two and three block
+//    columns the bit-pinned tests run): a tile of column c has tau c - head for its product, tau = 17.8 / 14 us the chain's pace then,
+//    a 64-row chunk costing tc + 0.3 = 3.0 / 1.9 us; near tiles split like their column.
+//  * fp64 from four block columns on -- fitted to the stamps of the C2 launch (16 columns, nq = 16; tools/step_boundary.py, DESIGN.md
+//    section 5).  The tile that came late was the DIAGONAL feeder (c, c): the look under factor(c - 1) wants it parked, and before
+//    that it forms its slice of the product (tc per chunk), takes the eta2 step (te) and applies the updates of columns 0 .. c - 2
+//    (tu each), the last of which arrives tl behind factor(c - 2).  Its workgroup starts ts0 + ts1 c after the launch's first one
+//    (the columns in front hold the slots).  With the chain at tau per column and factor(0) done f0 after the start:
+//        chunks tc <= f0 + tau (c - 2) + tl - margin - te - tu (c - 2) - (ts0 + ts1 c)  =  (tau - tu - ts1) c - head_near
+//    The other tiles of the column have to be ready when X_c is out: one column later, one update more.  In column 0 only the near
+//    tiles are urgent; the others give half of their helpers away (112 -> 64 workgroups in front of everything else: tile (2, 2)
+//    started 12 us into the launch).
 static void pro_ks_table(int64_t nt, int64_t nq, bool f64, unsigned char* ks, unsigned char* kf, bool pre = false) {
-  const double tc = f64 ? 2.7 : 1.6, tau = f64 ? 17.8 : 14.0, head = pre ? 24.0 : 12.0;
-  for (int64_t c = 0; c < nt && c < 32; ++c) {
-    int want;
-    if (c == 0) want = 8;
-    else if (c == 1) want = f64 ? 4 : 8;
-    else want = (int)std::ceil((double)nq * (tc + 0.3) / std::max(tau * (double)c - head, 1.0));
-    want = std::max(1, std::min<int>(want, (int)std::min<int64_t>(8, nq)));
-    // the tiles next to the diagonal (ProArgs::kf) take the same split as their column (a finer one was measured at 32 block
-    // columns, docs/DESIGN_LOG.md, and not adopted)
-    ks[c] = kf[c] = (unsigned char)want;
+  const int cap = (int)std::min<int64_t>(8, nq);
+  auto split = [&](double work, double budget) { return std::max(1, std::min(cap, (int)std::ceil(work / std::max(budget, 1.0)))); };
+  if (nt <= 3 || !f64) {
+    const double tc = f64 ? 2.7 : 1.6, tau = f64 ? 17.8 : 14.0, head = pre ? 24.0 : 12.0;
+    for (int64_t c = 0; c < nt && c < 32; ++c)
+      ks[c] = kf[c] = (unsigned char)(c == 0 ? cap : c == 1 ? std::min(cap, f64 ? 4 : 8) : split((double)nq * (tc + 0.3), tau * (double)c - head));
+    return;
+  }
+  // us, measured: tc 3.05 - 3.2 on single tiles (3.4 taken: with 3.1 tile (7, 7) kept its whole product, and the looks under
+  // factor(6) and factor(7) failed in 8 - 10 % of the launches), tau 16.2, f0 17.4 with the prepared head
+  const double tc = 3.4, tau = 16.2, tu = 4.0, te = 4.0, tl = 6.0, ts0 = 7.0, ts1 = 2.5, margin = 3.0, f0 = pre ? 17.4 : 27.4;
+  const double slope = tau - tu - ts1;                                             // 9.7
+  const double head_near = 2.0 * tau - 2.0 * tu + ts0 + te + margin - tl - f0;     // 15.0 with pre
+  const double head_far = head_near - (tau + tl - tu - margin);                    // -0.2
+  kf[0] = (unsigned char)cap, ks[0] = (unsigned char)std::min(cap, 4);
+  kf[1] = ks[1] = (unsigned char)std::min(cap, 4);
+  for (int64_t c = 2; c < nt && c < 32; ++c) {
+    kf[c] = (unsigned char)split((double)nq * tc, slope * (double)c - head_near);
+    ks[c] = (unsigned char)split((double)nq * tc, slope * (double)c - head_far);
   }
 }
 // test hook (AGP_DAG_TEST_ABORT=1): pretend every task-graph launch of a CAVI step lost a dependency, so that the in-stream

@@ -8,7 +8,8 @@
 which writes the dump.  `table` averages the last launches of each dump; every time is in us relative to the end of the chain's
 last tile elimination, factor(nt - 1), of the same launch ("next" rows: of the launch before).  Below it, per block column of the
 chain: how long the tile elimination and the glue behind it took and which way the next column's two feeder tiles came in (prefetched
-under the elimination, or late because the look failed / because a sentinel was seen)."""
+under the elimination, or late because the look failed / because a sentinel was seen).  Last, the two feeder tiles of block columns
+2 .. 6 against the look that wants them: when their workgroup started, finished its product, took the eta2 step and parked."""
 import os
 import sys
 
@@ -17,6 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XPUB, EXT, FILL0, FILL1, WG0, WG1, SAFE0, SAFE1 = 600, 1100, 1400, 1500, 2048, 4096, 6144, 6400
 ELIM0, PATH = 528, 560  # per block column k: factor(k) starts ; the path word of column k + 1's feed (PRO_TS, agp_chol.h)
+LOOK, NEAR = 608, 640   # the look under factor(k) ; the near-diagonal tiles of block columns 2 .. 6 (STRACE_LOOK, STRACE_NEAR)
 
 
 def run(dump, steps, warm):
@@ -104,6 +106,42 @@ def columns(cur, nt):
     return out
 
 
+def tile_slot(R, c):
+    """first stamp of matrix tile (R, c): PRO_TS's old region for R, c < 4, STRACE_NEAR for the near tiles of block columns 2 .. 6"""
+    if R < 4 and c < 4:
+        return 64 + 8 * (4 * R + c)
+    if 2 <= c <= 6 and 0 <= R - c < 4:
+        return NEAR + 8 * (4 * (c - 2) + (R - c))
+    return None
+
+
+def feeders(cur, nt):
+    """the two feeder tiles of block column k + 1, (k + 1, k) and (k + 1, k + 1), against the look that needs them (the side job
+    under factor(k)): median us relative to that look, negative = before it.  start: the workgroup reaches its prologue; product: own
+    k-slice done; helpers: all partial tiles signalled; stepped: partials added and the eta2 step taken; parked: updates of the
+    earlier columns applied, tile parked and signalled.  Late: share of launches in which the tile was parked after the look."""
+    look = cur[:, LOOK:LOOK + nt]
+    if not np.isfinite(look).any():
+        return ["  (no look stamps in this dump)"]
+
+    def med(x):
+        x = x[np.isfinite(x)]
+        return float(np.median(x)) if x.size else float("nan")
+
+    out = ["  feeders against the look under factor(k), us (negative: before the look):",
+           "    k  tile      start  product  helpers  stepped   parked   late | factor(k) start  X_(k-1) out -> look"]
+    for k in range(1, min(nt - 1, 6)):
+        for R, c in ((k + 1, k), (k + 1, k + 1)):
+            s = tile_slot(R, c)
+            if s is None:
+                continue
+            rel = lambda q: med((cur[:, s + q] - look[:, k]) * 0.01)
+            late = np.nanmean((cur[:, s + 5] > look[:, k])[np.isfinite(cur[:, s + 5]) & np.isfinite(look[:, k])])
+            out.append(f"   {k:2d}  ({R},{c})  {rel(0):8.2f} {rel(1):8.2f} {rel(2):8.2f} {rel(4):8.2f} {rel(5):8.2f}  {late:5.0%} | "
+                       f"{med((cur[:, ELIM0 + k] - look[:, k]) * 0.01):8.2f}         {med((cur[:, 512 + k - 1] - look[:, k]) * 0.01):8.2f}")
+    return out
+
+
 def table(dumps, last=200, nt=16, ne=17):
     rows = []
     for dump in dumps:
@@ -147,6 +185,7 @@ def table(dumps, last=200, nt=16, ne=17):
         out.append(f"  mean over k {np.mean(d):6.3f}   factor({nt - 1}) - factor(0) {med(f[:, nt - 1] - f[:, 0]) * 0.01:8.2f}")
         out.append(f"  chain start -> factor(0) done {med(f[:, 0] - cur[:, 0]) * 0.01:8.2f}")
         out += columns(cur, nt)
+        out += feeders(cur, nt)
         rows += out
     return "\n".join(rows)
 
