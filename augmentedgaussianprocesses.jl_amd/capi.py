@@ -189,6 +189,7 @@ SYMBOLS = {
     "agp_mc_expectations": (_I32, [_VP, C.POINTER(LikDesc), _VP, _VP, _VP, _I64, _I32, _I32, C.c_uint64, _I64, _I32, _VP, _VP, _VP]),
     "agp_svgp_pathwise_draw": (_I32, [_VP, _I32, _I32, C.c_uint64, _I64, _PVP]),
     "agp_pathwise_eval": (_I32, [_VP, _VP, _I64, _I64, _VP, _I64]),
+    "agp_pathwise_eval_grad": (_I32, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, _I64, _I64]),
     "agp_pathwise_info": (_I32, [_VP, _PI32, _PI32, _PI32, _PI64, _PI64]),
     "agp_pathwise_get": (_I32, [_VP, _I32, _I32, _VP, _I64]),
     "agp_pathwise_destroy": (_I32, [_VP]),

@@ -6020,6 +6020,25 @@ agp_status agp_pathwise_eval(agp_pathwise* p, const void* xt, int64_t ldx, int64
   DevGuard guard(p->ctx->device);
   return pw_eval(*p, (const double*)xt, ldx, n_t, (double*)out, ldo);
 }
+agp_status agp_pathwise_eval_grad(agp_pathwise* p, const void* xt, int64_t ldx, int64_t n_t, void* f_out, int64_t ldo, void* g_out,
+                                  int64_t lds, int64_t ldg) {
+  if (!p) return AGP_ERR_INVALID;
+  if (n_t == 0) return AGP_OK;
+  const char* bad = nullptr;
+  if (!xt) bad = "xt must be given";
+  else if (!g_out) bad = "g_out must be given";
+  else if (n_t < 0) bad = "n_t >= 0";
+  else if (ldx < p->D) bad = "ldx >= D";
+  else if (lds < n_t) bad = "lds >= n_t";
+  else if (ldg < p->D) bad = "ldg >= D";
+  else if (f_out && ldo < n_t) bad = "ldo >= n_t when f_out is given";
+  if (bad) {
+    p->ctx->err = std::string("agp_pathwise_eval_grad: ") + bad;
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(p->ctx->device);
+  return pw_eval_grad(*p, (const double*)xt, ldx, n_t, (double*)f_out, ldo, (double*)g_out, lds, ldg);
+}
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D) {
   if (!p) return AGP_ERR_INVALID;
   if (n_latent) *n_latent = p->nl;

@@ -1,6 +1,8 @@
 // agp_pathwise.h -- device code of pathwise (decoupled) posterior sampling (Wilson et al. 2020; include/agp_hip.h, "PATHWISE
 // SAMPLING"): the spectral draw of the random Fourier features, the Normal tables W and E, the feature kernel Phi(x) and the small
-// element-wise kernels of the draw.  The products of the draw and of an evaluation are the library's own (gemm_nt, k_gemm_tn).
+// element-wise kernels of the draw, and the kernels of the paths' input gradients (agp_pathwise_eval_grad: k_pw_dkern,
+// k_pw_grad_operand, k_pw_grad_scatter).  The products of the draw, of an evaluation and of a gradient are the library's own (gemm_nt,
+// k_gemm_tn).
 // Every table entry is a function of (seed, t, stream, index) alone -- streams 4 + 8 l .. 8 + 8 l of latent l -- with log and
 // cos 2 pi by the arithmetic of streams 2 and 3 (agp_rand.h), so a host program reproduces Omega, the phases, W and E bit for bit
 // (tests/_pathwise_ref.py does).  No kernel here uses scratch memory.
@@ -8,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "agp_hyper.h"  // kernel_dbase
 #include "agp_rand.h"
 
 namespace agp {
@@ -74,7 +77,9 @@ __global__ void k_pw_gather(const double* __restrict__ src, int64_t sr, int64_t 
 // grid = (nfp / 64, np / 64), 256 threads, every thread 4 points x 4 features.  s o x and a tile of Omega are staged in LDS, PW_DC
 // dimensions at a time, rows padded by one element (33 doubles: the 16 feature rows a wave reads start on 16 different bank pairs,
 // the point row is a broadcast).  The dot product runs over d in ascending order whatever the block, so a point's features do not
-// depend on where the point stands in the call.
+// depend on where the point stands in the call.  SIN: out[i][j] = -amp sin(...), the derivative of the feature with respect to its
+// argument (the A block of the gradient's base workspace), by the same staging and the same sum.
+template <bool SIN>
 __global__ __launch_bounds__(256) void k_pw_features(const double* __restrict__ x, int64_t ldx, int64_t n, int64_t D,
                                                      const double* __restrict__ scales, const double* __restrict__ omega,
                                                      const double* __restrict__ phase, int64_t nf, double amp,
@@ -117,8 +122,114 @@ __global__ __launch_bounds__(256) void k_pw_features(const double* __restrict__ 
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int64_t i = i0 + ty + 16 * p;
-      out[i * ldo + j] = (i < n && j < nf) ? amp * cos(acc[p][q] + ph) : 0.0;
+      if (SIN) out[i * ldo + j] = (i < n && j < nf) ? -amp * sin(acc[p][q] + ph) : 0.0;
+      else out[i * ldo + j] = (i < n && j < nf) ? amp * cos(acc[p][q] + ph) : 0.0;
     }
+  }
+}
+
+// ---- input gradients of the paths (agp_pathwise_eval_grad; include/agp_hip.h "PATHWISE SAMPLING") -------------------------------------
+// With t_ird = s_d (x_id - Z_rd), q_ir = sum_d t_ird^2 and c_ir = variance phi'(q_ir) (kernel_dbase: finite at r = 0, no division by r)
+//   d f_s / d x_d (x_i) = s_d sum_j A_ij omega_jd W_js + 2 s_d sum_r c_ir t_ird V_rs ,   A_ij = -amp sin(omega_j' (s o x_i) + p_j)
+// formed per dimension d as one gemm_nt of Wd = [A_ij s_d omega_jd | 2 s_d c_ir t_ird] against the stored [W' | V'] -- the call of the
+// evaluation -- from the base workspace B0 = [A | C] that is written once per chunk (k_pw_features<true>, k_pw_dkern).
+constexpr int PW_GD = 64;  // dimensions whose slabs are staged together before they are transposed into the caller's [s][i][d] rows
+
+// C[i][r] = variance phi'(q_ir) for a block of points against a block of Z, the right columns of the base workspace; rows i >= n and
+// columns r >= m of the tile grid are exact zeros.  grid = (mp / 64, np / 64), 256 threads, 4 points x 4 inducing points per thread,
+// the LDS staging of k_pw_features (rows of 33 doubles).  q is summed over d in ascending order from direct differences of the scaled
+// coordinates: no GEMM-form cancellation far from the origin, and a point's row does not depend on where it stands in the call.
+__global__ __launch_bounds__(256) void k_pw_dkern(const double* __restrict__ x, int64_t ldx, int64_t n, int64_t D,
+                                                  const double* __restrict__ scales, const double* __restrict__ Z, int64_t m, int kind,
+                                                  double variance, double* __restrict__ out, int64_t ldo) {
+  __shared__ double xs[64][PW_DC + 1];
+  __shared__ double zs[64][PW_DC + 1];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int64_t i0 = blockIdx.y * (int64_t)64, r0 = blockIdx.x * (int64_t)64;
+  double acc[4][4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[p][q] = 0.0;
+  for (int64_t d0 = 0; d0 < D; d0 += PW_DC) {
+    const int dc = (int)((D - d0) < PW_DC ? (D - d0) : PW_DC);
+    for (int e = tid; e < 64 * PW_DC; e += 256) {
+      const int r = e / PW_DC, d = e % PW_DC;
+      const int64_t i = i0 + r, j = r0 + r;
+      xs[r][d] = (d < dc && i < n) ? scales[d0 + d] * x[i * ldx + d0 + d] : 0.0;
+      zs[r][d] = (d < dc && j < m) ? scales[d0 + d] * Z[j * D + d0 + d] : 0.0;
+    }
+    __syncthreads();
+    for (int d = 0; d < dc; ++d) {
+      double xv[4], zv[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) xv[p] = xs[ty + 16 * p][d];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) zv[q] = zs[tx + 16 * q][d];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double t = xv[p] - zv[q];
+          acc[p][q] = fma(t, t, acc[p][q]);
+        }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int64_t r = r0 + tx + 16 * q;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int64_t i = i0 + ty + 16 * p;
+      out[i * ldo + r] = (i < n && r < m) ? variance * kernel_dbase<double>(kind, acc[p][q]) : 0.0;
+    }
+  }
+}
+
+// The operand of dimension d: Wd[i][j] = A_ij s_d omega_jd for j < Lp and Wd[i][Lp + r] = 2 s_d C_ir t_ird for r < mp, t_ird = s_d x_id -
+// s_d Z_rd (0 exactly where x_i = Z_r), over the nq x (Lp + mp) workspace with leading dimension ld; one lane per element, consecutive
+// lanes along a row.  The padding of B0 is zero and stays zero: nothing is read for rows >= n, features >= nf or inducing points >= m.
+__global__ __launch_bounds__(256) void k_pw_grad_operand(const double* __restrict__ B0, int64_t nq, int64_t n, int64_t Lp, int64_t nf,
+                                                         int64_t mp, int64_t m, int64_t ld, const double* __restrict__ x, int64_t ldx,
+                                                         int64_t D, int64_t d, const double* __restrict__ scales,
+                                                         const double* __restrict__ omega, const double* __restrict__ Z,
+                                                         double* __restrict__ Wd) {
+  const int64_t w = Lp + mp, e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (e >= nq * w) return;
+  const int64_t i = e / w, c = e - i * w;
+  double v = 0.0;
+  if (i < n) {
+    const double sd = scales[d];
+    if (c < Lp) {
+      if (c < nf) v = B0[i * ld + c] * (sd * omega[c * D + d]);
+    } else if (c - Lp < m) {
+      const double t = sd * x[i * ldx + d] - sd * Z[(c - Lp) * D + d];
+      v = (2.0 * sd) * (B0[i * ld + c] * t);
+    }
+  }
+  Wd[i * ld + c] = v;
+}
+
+// The transposing scatter: G[k][s][i] (the slabs of dimensions d0 + k, k < nd <= PW_GD; slab stride lds_, row stride ldc) into the
+// caller's out[s][i][d0 + k] at out + (s los + i) ldg + d0 + k, s < S, i < n.  grid = (S, ceil(n / 64)): a block reads 64 points of
+// its sample from every slab along i, turns them in LDS (rows padded by one double: the transposed read walks 32 distinct bank pairs
+// per half wave) and writes, per point, the run of nd consecutive doubles.
+__global__ __launch_bounds__(256) void k_pw_grad_scatter(const double* __restrict__ G, int64_t lds_, int64_t ldc, int64_t n, int nd,
+                                                         double* __restrict__ out, int64_t los, int64_t ldg, int64_t d0) {
+  __shared__ double tile[PW_GD][64 + 1];
+  const int tid = threadIdx.x;
+  const int64_t i0 = blockIdx.y * (int64_t)64, s = blockIdx.x;
+  const int ni = (int)((n - i0) < 64 ? (n - i0) : 64);
+  for (int e = tid; e < nd * 64; e += 256) {
+    const int k = e >> 6, i = e & 63;
+    if (i < ni) tile[k][i] = G[k * lds_ + s * ldc + i0 + i];
+  }
+  __syncthreads();
+  double* o = out + (s * los + i0) * ldg + d0;
+  for (int e = tid; e < ni * nd; e += 256) {
+    const int i = e / nd, k = e - i * nd;
+    o[(int64_t)i * ldg + k] = tile[k][i];
   }
 }
 

@@ -1,6 +1,7 @@
 // agp_pathwise_host.h -- host driver of pathwise posterior sampling (kernels: agp_pathwise.h): struct agp_pathwise, the draw that
 // the C ABI hands out and that owns everything it evaluates with, the scratch of its construction (PwScratch) and the pw_*
-// routines: argument checks, spectral tables, per-latent snapshot, features, the inverse factor and the chunked evaluation.  The
+// routines: argument checks, spectral tables, per-latent snapshot, features, the inverse factor, the chunked evaluation (pw_eval) and
+// the chunked input gradients (pw_eval_grad).  The
 // models build draws in Svgp<T>::pathwise_draw (agp_capi.hip) and its overrides; the agp_pathwise_* entry points are in agp_capi.hip.
 #pragma once
 #include <memory>
@@ -32,11 +33,15 @@ struct agp_pathwise {
   };
   std::vector<Lat> lat;
   double *ws = nullptr, *Fs = nullptr;
+  // the gradient's own buffers, allocated by its first call (pw_grad_buffers): the per-dimension operand Wd, the same size as ws,
+  // and the slabs of GD dimensions before they are transposed into the caller's rows
+  double *ws2 = nullptr, *Gs = nullptr;
+  int GD = 0;
   ~agp_pathwise() {
     for (auto& a : lat)
       for (double* q : {a.scales, a.Z, a.Zsc, a.zn, a.omega, a.phase, a.WV, a.E})
         if (q) (void)hipFree(q);
-    for (double* q : {ws, Fs})
+    for (double* q : {ws, Fs, ws2, Gs})
       if (q) (void)hipFree(q);
   }
 };
@@ -139,9 +144,11 @@ static agp_status pw_add_latent(agp_pathwise& p, int l, int kind, double varianc
   LAUNCHCHK(ctx);
   return AGP_OK;
 }
-// Phi(x) of n points (rows 0 .. rup64(n) of the workspace, left Lp columns; padding rows and columns exact zeros)
+// Phi(x) of n points (rows 0 .. rup64(n) of the workspace, left Lp columns; padding rows and columns exact zeros); SIN: the
+// features' derivative -amp sin(.) instead (the gradient's A block)
+template <bool SIN = false>
 static agp_status pw_features(agp_pathwise& p, const agp_pathwise::Lat& a, const double* x, int64_t ldx, int64_t n) {
-  hipLaunchKernelGGL(agp::k_pw_features, dim3((unsigned)(p.Lp / TILE), (unsigned)(rup64(n) / TILE)), dim3(256), 0, p.ctx->stream, x,
+  hipLaunchKernelGGL(agp::k_pw_features<SIN>, dim3((unsigned)(p.Lp / TILE), (unsigned)(rup64(n) / TILE)), dim3(256), 0, p.ctx->stream, x,
                      ldx, n, p.D, (const double*)a.scales, (const double*)a.omega, (const double*)a.phase, (int64_t)p.L, a.amp, p.ws,
                      p.ldw);
   LAUNCHCHK(p.ctx);
@@ -202,24 +209,79 @@ static agp_status pw_gemm_tn(agp_ctx* ctx, const double* A, int64_t lda, const d
   LAUNCHCHK(ctx);
   return AGP_OK;
 }
-static agp_status pw_eval(agp_pathwise& p, const double* xt, int64_t ldx, int64_t nt, double* out, int64_t ldo) {
+// the paths of latent l at one chunk of nc <= CH points, into out[s][0 .. nc) (rows pitched by ldo)
+static agp_status pw_eval_chunk(agp_pathwise& p, int l, const double* xs, int64_t ldx, int64_t nc, double* out, int64_t ldo) {
   agp_ctx* ctx = p.ctx;
+  const agp_pathwise::Lat& a = p.lat[l];
+  const int64_t nq = rup64(nc);
+  AGPCHK(pw_features(p, a, xs, ldx, nc));
+  const int rc = launch_kernelmatrix<double>(ctx, ctx->stream, xs, ldx, (const int64_t*)nullptr, nc, (const double*)a.Z, p.D, p.m,
+                                             p.D, (const double*)a.scales, a.kind, a.variance, p.ws + p.Lp, p.ldw, nq, p.mp, 0,
+                                             0.0, (const double*)nullptr, (double*)nullptr, (int64_t)0, 0, (const double*)a.Zsc,
+                                             (const double*)a.zn);
+  LAUNCHCHK(ctx);
+  if (rc < 0) return AGP_ERR_NOMEM;
+  AGPCHK((gemm_nt<double, EPI_STORE>(ctx, a.WV, p.ldw, p.ws, p.ldw, p.Sp, nq, p.ldw, 0, p.Fs, p.CH, nullptr, 0, nullptr, nullptr,
+                                     nullptr, 0)));
+  HIPCHK(ctx, hipMemcpy2DAsync(out, sizeof(double) * ldo, p.Fs, sizeof(double) * p.CH, sizeof(double) * nc, p.S,
+                               hipMemcpyDeviceToDevice, ctx->stream));
+  return AGP_OK;
+}
+static agp_status pw_eval(agp_pathwise& p, const double* xt, int64_t ldx, int64_t nt, double* out, int64_t ldo) {
+  for (int l = 0; l < p.nl; ++l)
+    for (int64_t s = 0; s < nt; s += p.CH)
+      AGPCHK(pw_eval_chunk(p, l, xt + s * ldx, ldx, std::min<int64_t>(p.CH, nt - s), out + ((int64_t)l * p.S) * ldo + s, ldo));
+  return AGP_OK;
+}
+// The gradient's buffers, on its first call: Wd (CH x ldw) and the slabs of GD dimensions (GD x Sp x CH).  GD = min(D, PW_GD), fewer
+// where the slabs would exceed AGP_PATHWISE_WS_BYTES (a function of the draw's sizes alone).
+static agp_status pw_grad_buffers(agp_pathwise& p) {
+  if (p.ws2 && p.Gs) return AGP_OK;
+  const int64_t slab = 8 * p.Sp * p.CH;
+  const int gd = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(p.D, agp::PW_GD), (int64_t)AGP_PATHWISE_WS_BYTES / slab));
+  if (!p.ws2) AGPCHK(dmalloc(p.ctx, &p.ws2, p.CH * p.ldw));
+  if (!p.Gs) AGPCHK(dmalloc(p.ctx, &p.Gs, (int64_t)gd * p.Sp * p.CH));
+  p.GD = gd;
+  return AGP_OK;
+}
+// d f_s / d x (include/agp_hip.h, agp_pathwise_eval_grad; kernels and the formulation: agp_pathwise.h).  Per chunk and latent: the
+// values, if asked for, by pw_eval_chunk; the base workspace [A | C] into ws; then per dimension the operand into ws2, the
+// evaluation's gemm_nt against [W' | V'] into one slab, and after every GD dimensions the transposing scatter into g[s][i][d].
+static agp_status pw_eval_grad(agp_pathwise& p, const double* xt, int64_t ldx, int64_t nt, double* f_out, int64_t ldo, double* g_out,
+                               int64_t lds, int64_t ldg) {
+  agp_ctx* ctx = p.ctx;
+  for (const agp_pathwise::Lat& a : p.lat)
+    if (a.kind == AGP_K_EXPONENTIAL) {
+      ctx->err = "agp_pathwise_eval_grad: ExponentialKernel is not differentiable at zero distance";
+      return AGP_ERR_UNSUPPORTED;
+    }
+  AGPCHK(pw_grad_buffers(p));
+  const int64_t slab = p.Sp * p.CH;
   for (int l = 0; l < p.nl; ++l) {
     const agp_pathwise::Lat& a = p.lat[l];
     for (int64_t s = 0; s < nt; s += p.CH) {
       const int64_t nc = std::min<int64_t>(p.CH, nt - s), nq = rup64(nc);
       const double* xs = xt + s * ldx;
-      AGPCHK(pw_features(p, a, xs, ldx, nc));
-      const int rc = launch_kernelmatrix<double>(ctx, ctx->stream, xs, ldx, (const int64_t*)nullptr, nc, (const double*)a.Z, p.D, p.m,
-                                                 p.D, (const double*)a.scales, a.kind, a.variance, p.ws + p.Lp, p.ldw, nq, p.mp, 0,
-                                                 0.0, (const double*)nullptr, (double*)nullptr, (int64_t)0, 0, (const double*)a.Zsc,
-                                                 (const double*)a.zn);
+      if (f_out) AGPCHK(pw_eval_chunk(p, l, xs, ldx, nc, f_out + ((int64_t)l * p.S) * ldo + s, ldo));
+      AGPCHK(pw_features<true>(p, a, xs, ldx, nc));
+      hipLaunchKernelGGL(agp::k_pw_dkern, dim3((unsigned)(p.mp / TILE), (unsigned)(nq / TILE)), dim3(256), 0, ctx->stream, xs, ldx, nc,
+                         p.D, (const double*)a.scales, (const double*)a.Z, p.m, a.kind, a.variance, p.ws + p.Lp, p.ldw);
       LAUNCHCHK(ctx);
-      if (rc < 0) return AGP_ERR_NOMEM;
-      AGPCHK((gemm_nt<double, EPI_STORE>(ctx, a.WV, p.ldw, p.ws, p.ldw, p.Sp, nq, p.ldw, 0, p.Fs, p.CH, nullptr, 0, nullptr, nullptr,
-                                         nullptr, 0)));
-      HIPCHK(ctx, hipMemcpy2DAsync(out + ((int64_t)l * p.S) * ldo + s, sizeof(double) * ldo, p.Fs, sizeof(double) * p.CH,
-                                   sizeof(double) * nc, p.S, hipMemcpyDeviceToDevice, ctx->stream));
+      double* g = g_out + (((int64_t)l * p.S) * lds + s) * ldg;
+      for (int64_t d0 = 0; d0 < p.D; d0 += p.GD) {
+        const int nd = (int)std::min<int64_t>(p.GD, p.D - d0);
+        for (int k = 0; k < nd; ++k) {
+          hipLaunchKernelGGL(agp::k_pw_grad_operand, grid1(nq * p.ldw), dim3(256), 0, ctx->stream, (const double*)p.ws, nq, nc, p.Lp,
+                             (int64_t)p.L, p.mp, p.m, p.ldw, xs, ldx, p.D, d0 + k, (const double*)a.scales, (const double*)a.omega,
+                             (const double*)a.Z, p.ws2);
+          LAUNCHCHK(ctx);
+          AGPCHK((gemm_nt<double, EPI_STORE>(ctx, a.WV, p.ldw, p.ws2, p.ldw, p.Sp, nq, p.ldw, 0, p.Gs + k * slab, p.CH, nullptr, 0,
+                                             nullptr, nullptr, nullptr, 0)));
+        }
+        hipLaunchKernelGGL(agp::k_pw_grad_scatter, dim3((unsigned)p.S, (unsigned)((nc + 63) / 64)), dim3(256), 0, ctx->stream,
+                           (const double*)p.Gs, slab, p.CH, nc, nd, g, lds, ldg, d0);
+        LAUNCHCHK(ctx);
+      }
     }
   }
   return AGP_OK;

@@ -2,6 +2,7 @@
 
     paths = AGP.sample_paths(model, n_samples, n_features=1024, seed=None, t=0)
     F = paths(X_test)          # (n_samples, n_t), or (n_latent, n_samples, n_t) for several latents
+    G = paths.grad(X_test)     # (n_samples, n_t, D): d f_s / d x, in closed form from the draw's tables; value=True gives (F, G)
 
 Decoupled sampling (Wilson et al. 2020, "Efficiently sampling functions from Gaussian process posteriors"): a prior function from
 random Fourier features, a draw u ~ q(u), Matheron's correction.  A draw is an ordinary function: it can be evaluated at any number
@@ -19,6 +20,7 @@ from . import capi
 
 N_MAX = 65536  # n_features and n_samples (agp_svgp_pathwise_draw)
 CTR_MAX = 2 ** 32  # products that index one 32-bit counter word, and the draw counter t
+GRAD_REFUSAL_EXPONENTIAL = "ExponentialKernel is not differentiable at zero distance"  # agp_pathwise_eval_grad says the same
 
 
 def check_draw_args(m: int, D: int, n_samples: int, n_features: int, t: int, seed: Optional[int] = None) -> None:
@@ -62,6 +64,7 @@ class PathwiseSamples:
         self._model = model  # keeps the context alive (the draw uses its stream)
         self.n_samples, self.n_features, self.seed, self.t = int(n_samples), int(n_features), int(seed), int(t)
         self.n_latent, self.m, self.D = model.n_latent, model.m, model.D
+        self._kinds = tuple(k._kind for k in model.kernels)  # of the snapshot: what grad refuses is decided on the host
         self._p = None
         h = model._ensure_handle(max(model._max_batch, 1))
         p = C.c_void_p()
@@ -90,6 +93,33 @@ class PathwiseSamples:
         if self.n_latent == 1:
             out = out[0]
         return out if on_device else out.cpu().numpy()
+
+    def grad(self, X_test, *, value: bool = False, obsdim: int = 1):
+        """the input gradients of the paths at X_test: G[s, i, d] = d f_s / d x_d (x_i), (n_samples, n_t, D), or (n_latent, n_samples,
+        n_t, D) for several latents; value=True returns (F, G) with F exactly what paths(X_test) returns.  Closed form from the
+        draw's own tables (agp_pathwise_eval_grad): what maximising a draw by gradient ascent -- Thompson sampling -- needs.  NumPy in
+        gives NumPy out; a torch tensor on the device gives device tensors.  A draw with an ExponentialKernel raises
+        NotImplementedError before the device is touched."""
+        import torch
+
+        p, model = self._live(), self._model
+        if capi.K_EXPONENTIAL in self._kinds:
+            raise NotImplementedError("paths.grad: " + GRAD_REFUSAL_EXPONENTIAL)
+        on_device = isinstance(X_test, torch.Tensor) and X_test.is_cuda
+        Xd = model._upload(X_test, obsdim)
+        nt = Xd.shape[0]
+        dev = model._dev()
+        G = torch.empty(self.n_latent, self.n_samples, nt, self.D, dtype=torch.float64, device=dev)
+        F = torch.empty(self.n_latent, self.n_samples, nt, dtype=torch.float64, device=dev) if value else None
+        L = capi.lib()
+        model._chk(L.agp_pathwise_eval_grad(p, C.c_void_p(Xd.data_ptr()), Xd.stride(0) if nt else self.D, nt,
+                                            C.c_void_p(F.data_ptr()) if value else None, max(nt, 1), C.c_void_p(G.data_ptr()),
+                                            max(nt, 1), self.D))
+        model._chk(L.agp_ctx_sync(model._ctx))
+        out = [t[0] if self.n_latent == 1 else t for t in ((F, G) if value else (G,))]
+        if not on_device:
+            out = [t.cpu().numpy() for t in out]
+        return tuple(out) if value else out[0]
 
     def tables(self, latent: int = 0):
         """the draw's tables of one latent as NumPy arrays: omega (l, D), phase (l), W (l, S), V (m, S), E (m, S)"""

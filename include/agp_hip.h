@@ -994,6 +994,26 @@ agp_status agp_mc_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void
  *   no-op.  Test points go through the workspace [Phi(x) | k(x, Z)] in chunks of at most 4096, fewer where a chunk's share of the
  *   workspace -- 8 (l + m + S) bytes per point, all three rounded up to 64 -- would exceed AGP_PATHWISE_WS_BYTES (but at least
  *   64): one gemm_nt against the stored [W' | V'] gives both terms.  Asynchronous on the context's stream.
+ * agp_pathwise_eval_grad  the input gradients of the paths, g_out[latent][s][i][d] = d f_s / d x_d (x_i) at g_out + ((latent *
+ *   n_samples + s) * lds + i) * ldg + d, lds >= n_t, ldg >= D (padding never read or written).  A draw is a closed-form function, so
+ *   is its gradient: with t_ird = s_d (x_id - Z_rd), q_ir = sum_d t_ird^2 and c_ir = sigma2 phi'(q_ir) (kernel_dbase of agp_hyper.h:
+ *   the forms that are finite at r = 0 and never divide by r), per latent
+ *       d f_s / d x_d (x_i) = - s_d sum_j amp sin(omega_j' (s o x_i) + p_j) omega_jd W_js  +  2 s_d sum_r c_ir t_ird V_rs ,
+ *   amp = sqrt(2 sigma2 / l).  A test point that coincides with an inducing point is an ordinary input: t = 0 there exactly and the
+ *   term adds exactly 0.  f_out (nullable): the values, laid out as agp_pathwise_eval writes them (ldo >= n_t) and bit for bit what
+ *   it writes for the same arguments (the same kernels on the same chunk).  Nothing is drawn: the random streams are untouched.
+ *   Chunks as agp_pathwise_eval; per chunk and latent the base workspace [A | C] (A_ij = -amp sin(.), C = c, q summed in ascending
+ *   d from direct differences of the scaled coordinates: no cancellation far from the origin), then per dimension d one
+ *   element-wise pass [A_ij s_d omega_jd | 2 s_d C_ir t_ird] into a second workspace of the same size and the evaluation's own
+ *   gemm_nt against [W' | V']; the slabs of up to 64 dimensions (fewer where they would exceed AGP_PATHWISE_WS_BYTES) are staged and
+ *   transposed into the caller's rows.  The second workspace and the staging are allocated by the first gradient call and belong
+ *   to the draw.  No atomics, every sum in a fixed order: the same bits on every call.  The kernels written for it give a point
+ *   the same bits wherever it stands in the call; gemm_nt does as long as it picks one kernel for every chunk size, which it does
+ *   up to 1100 tiles of 64 x 64 per product, that is for n_samples <= 1088 (beyond, a point's row may move by rounding).  No
+ *   limit on D beyond the draw's own.  n_t = 0 is a successful no-op; asynchronous on the context's stream.  AGP_ERR_UNSUPPORTED,
+ *   touching no output: a latent of the draw has the ExponentialKernel ("ExponentialKernel is not differentiable at zero distance":
+ *   its paths have a kink on Z; agp_svgp_predict_f_grad refuses it the same way).  AGP_ERR_INVALID with a message: xt or g_out NULL,
+ *   n_t < 0, ldx < D, lds < n_t, ldg < D, ldo < n_t with f_out given.
  * agp_pathwise_get   which = AGP_PW_OMEGA (l x D, ld >= D), AGP_PW_PHASE (l; ld not read), AGP_PW_W (l x S, ld >= S), AGP_PW_V
  *   (m x S, ld >= S), AGP_PW_E (m x S, ld >= S).
  * agp_pathwise_features  the spectral draw alone, outside any model: omega_out double[l][D], phase_out double[l], dense, device;
@@ -1003,6 +1023,9 @@ enum { AGP_PATHWISE_WS_BYTES = 64 * 1024 * 1024 };
 typedef struct agp_pathwise agp_pathwise;
 agp_status agp_svgp_pathwise_draw(agp_svgp* h, int32_t n_features, int32_t n_samples, uint64_t seed, int64_t t, agp_pathwise** out);
 agp_status agp_pathwise_eval(agp_pathwise* p, const void* xt, int64_t ldx, int64_t n_t, void* out, int64_t ldo);
+agp_status agp_pathwise_eval_grad(agp_pathwise* p, const void* xt, int64_t ldx, int64_t n_t,
+                                  void* f_out, int64_t ldo, /* nullable: the values, laid out as agp_pathwise_eval writes them */
+                                  void* g_out, int64_t lds, int64_t ldg);
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D);
 agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void* out, int64_t ld);
 agp_status agp_pathwise_destroy(agp_pathwise* p);

@@ -1439,6 +1439,26 @@ function (ps::PathwiseSamples)(X_test::AbstractMatrix; obsdim::Int=1)
     paths = [permutedims(F[:, :, l]) for l in 1:ps.n_latent]             # n_samples x n_t per latent
     return ps.n_latent == 1 ? only(paths) : paths
 end
+# pathwise_grad(paths, X_test; value=false): d f_s / d x at the test points, n_samples x n_t x D per latent (a vector over latents for
+# several); value=true returns (F, G) with F what paths(X_test) returns.  agp_pathwise_eval_grad; refused for the ExponentialKernel.
+function pathwise_grad(ps::PathwiseSamples, X_test::AbstractMatrix; value::Bool=false, obsdim::Int=1)
+    ps.p == C_NULL && error("the paths have been freed")
+    Xd = ROCArray{Float64}(obsdim == 1 ? permutedims(X_test) : X_test)   # D x n_t column-major == point-major
+    D, nt = size(Xd)
+    g = ROCArray{Float64}(undef, D, nt, ps.n_samples, ps.n_latent)       # column-major == double[n_latent][n_samples][n_t][D]
+    f = value ? ROCArray{Float64}(undef, nt, ps.n_samples, ps.n_latent) : nothing
+    check(ps.ctx, ccall((:agp_pathwise_eval_grad, libagp), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64),
+                        ps.p, pointer(Xd), D, nt, value ? pointer(f) : C_NULL, max(nt, 1), pointer(g), max(nt, 1), D))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), ps.ctx)
+    Gh = Array(g)
+    grads = [permutedims(Gh[:, :, :, l], (3, 2, 1)) for l in 1:ps.n_latent]   # n_samples x n_t x D per latent
+    G = ps.n_latent == 1 ? only(grads) : grads
+    value || return G
+    Fh = Array(f)
+    paths = [permutedims(Fh[:, :, l]) for l in 1:ps.n_latent]
+    return (ps.n_latent == 1 ? only(paths) : paths), G
+end
 # the tables of one latent (0-based `which`: 0 omega l x D, 1 phase l, 2 W l x S, 3 V m x S, 4 E m x S), as Julia matrices
 function pathwise_table(ps::PathwiseSamples, which::Integer; latent::Integer=1)
     rows, cols = which == 0 ? (ps.n_features, ps.D) : which == 1 ? (ps.n_features, 1) :
