@@ -79,6 +79,21 @@ class SvgpDesc(C.Structure):
     ]
 
 
+class PwAscentOpts(C.Structure):  # agp_pw_ascent_opts
+    _fields_ = [
+        ("steps", C.c_int32),
+        ("minimize", C.c_int32),
+        ("x0_shared", C.c_int32),
+        ("beta1", C.c_double),
+        ("beta2", C.c_double),
+        ("eps", C.c_double),
+        ("lo_host", C.POINTER(C.c_double)),
+        ("hi_host", C.POINTER(C.c_double)),
+        ("lr_host", C.POINTER(C.c_double)),
+    ]
+
+
+
 # every symbol include/agp_hip.h declares: name -> (restype, argtypes)
 _VP, _I32, _I64, _DBL = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 _PI32, _PI64, _PDBL, _PVP = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_void_p)
@@ -190,6 +205,7 @@ SYMBOLS = {
     "agp_svgp_pathwise_draw": (_I32, [_VP, _I32, _I32, C.c_uint64, _I64, _PVP]),
     "agp_pathwise_eval": (_I32, [_VP, _VP, _I64, _I64, _VP, _I64]),
     "agp_pathwise_eval_grad": (_I32, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, _I64, _I64]),
+    "agp_pathwise_maximize": (_I32, [_VP, _I32, _VP, _I64, _I64, C.POINTER(PwAscentOpts), _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP]),
     "agp_pathwise_info": (_I32, [_VP, _PI32, _PI32, _PI32, _PI64, _PI64]),
     "agp_pathwise_get": (_I32, [_VP, _I32, _I32, _VP, _I64]),
     "agp_pathwise_destroy": (_I32, [_VP]),

@@ -6039,6 +6039,14 @@ agp_status agp_pathwise_eval_grad(agp_pathwise* p, const void* xt, int64_t ldx, 
   DevGuard guard(p->ctx->device);
   return pw_eval_grad(*p, (const double*)xt, ldx, n_t, (double*)f_out, ldo, (double*)g_out, lds, ldg);
 }
+agp_status agp_pathwise_maximize(agp_pathwise* p, int32_t latent, const void* x0, int64_t ldx0, int64_t n_starts,
+                                 const agp_pw_ascent_opts* opts, void* x_out, int64_t ldxo, void* f_out, int64_t ldf, void* best_x,
+                                 int64_t ldb, void* best_f, void* best_idx) {
+  if (!p) return AGP_ERR_INVALID;
+  DevGuard guard(p->ctx->device);
+  return pw_maximize(p, latent, (const double*)x0, ldx0, n_starts, opts, (double*)x_out, ldxo, (double*)f_out, ldf, (double*)best_x, ldb,
+                     (double*)best_f, (int64_t*)best_idx);
+}
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D) {
   if (!p) return AGP_ERR_INVALID;
   if (n_latent) *n_latent = p->nl;

@@ -233,6 +233,197 @@ __global__ __launch_bounds__(256) void k_pw_grad_scatter(const double* __restric
   }
 }
 
+// ---- multi-start ascent of the paths (agp_pathwise_maximize; include/agp_hip.h "PATHWISE SAMPLING") -----------------------------------
+// A particle is a pair (sample s, start r), number s R + r.  k_pw_ascent runs the whole T-step ADAM ascent of a tile of PT particles
+// in one workgroup and one launch: particles never need each other, so there is no communication between workgroups.  Per step the
+// features (j < l) and then the inducing points (r < m) pass through LDS in tiles of 64 rows:
+//   phase 1  thread (tx, ty) forms, for its particles p = ty + 16 pp and its rows j = tx + 16 q, a_pj = omega_j' (s o x_p) or q_pr =
+//            sum_d (s_d x_pd - s_d Z_rd)^2 over d ascending, and writes B_pj = -amp sin(a_pj + p_j) W_j,s(p) or 2 variance phi'(q_pr)
+//            V_r,s(p) into LDS (exact zeros for rows past l or m)
+//   phase 2  thread (tx, ty) owns the coordinates d = tx + 16 q of the same particles, with x, the ADAM moments and the gradient sum
+//            in registers, and adds sum_j B_pj omega_jd or sum_r B_pr (s_d x_pd - s_d Z_rd) over the tile's 64 rows in ascending order
+// so every sum of a particle runs over j, then r, ascending, in one accumulator, whatever the tile it stands in: the same bits
+// wherever it stands in the call.  After step T one more pass with cos and phi in place of -sin and 2 phi' sums the rows of B into
+// f_s(x), again in ascending order.  No atomics, no scratch.  PT: 16 particles per tile fill 256 CUs with 4096 particles; larger
+// tiles re-use a staged tile of Omega or Z more often but leave CUs idle (DESIGN.md section 9k has the measurement).
+constexpr int PW_AD = 64;  // the largest D of the ascent: x, m, v and g of a tile live in registers next to the staging
+struct PwAscentBox {       // by value in the kernel's arguments: nothing is copied, nothing synchronises
+  double lo[PW_AD], hi[PW_AD], lr[PW_AD];
+};
+
+template <int PT, int DQ>
+__global__ __launch_bounds__(256) void k_pw_ascent(const double* __restrict__ x0, int64_t ldx0, int x0_shared, int64_t R, int64_t np,
+                                                   int64_t D, const double* __restrict__ scales, const double* __restrict__ omega,
+                                                   const double* __restrict__ phase, int64_t nf, double amp,
+                                                   const double* __restrict__ Z, int64_t m, int kind, double variance,
+                                                   const double* __restrict__ WV, int64_t ldw, int64_t Lp, int steps, double sign,
+                                                   double beta1, double beta2, double eps, const PwAscentBox box,
+                                                   double* __restrict__ Xw, double* __restrict__ Fw) {
+#pragma clang fp contract(off)
+  constexpr int PP = PT / 16, DW = 16 * DQ;
+  __shared__ double xs[PT][DW + 1];  // s o x of the tile's particles
+  __shared__ double tl[64][DW + 1];  // 64 rows of Omega, or of s o Z
+  __shared__ double Bs[PT][64 + 1];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int64_t p0 = blockIdx.x * (int64_t)PT;
+  int64_t wrow[PP];  // the particle's row of [W' | V']; a tile's surplus particles repeat the call's last one and are not stored
+  double x[PP][DQ], mo[PP][DQ], vo[PP][DQ], sd[DQ], lo[DQ], hi[DQ], lr[DQ];
+#pragma unroll
+  for (int q = 0; q < DQ; ++q) {
+    const int d = tx + 16 * q;
+    const bool in = d < D;
+    sd[q] = in ? scales[d] : 0.0, lo[q] = in ? box.lo[d] : 0.0, hi[q] = in ? box.hi[d] : 0.0, lr[q] = in ? box.lr[d] : 0.0;
+  }
+#pragma unroll
+  for (int pp = 0; pp < PP; ++pp) {
+    const int64_t pi = (p0 + ty + 16 * pp) < np ? (p0 + ty + 16 * pp) : np - 1;
+    wrow[pp] = (pi / R) * ldw;
+    const double* xr = x0 + (x0_shared ? pi % R : pi) * ldx0;
+#pragma unroll
+    for (int q = 0; q < DQ; ++q) {
+      const int d = tx + 16 * q;
+      x[pp][q] = d < D ? fmin(fmax(xr[d], lo[q]), hi[q]) : 0.0;
+      mo[pp][q] = vo[pp][q] = 0.0;
+      xs[ty + 16 * pp][d] = sd[q] * x[pp][q];
+    }
+  }
+  double b1k = 1.0, b2k = 1.0, fsum = 0.0;
+  for (int k = 0; k <= steps; ++k) {
+    const bool fin = k == steps;  // the pass after the last step: the values at the final x
+    double g[PP][DQ], xsd[PP][DQ];
+#pragma unroll
+    for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+      for (int q = 0; q < DQ; ++q) g[pp][q] = 0.0, xsd[pp][q] = sd[q] * x[pp][q];
+    for (int part = 0; part < 2; ++part) {  // the features, then the inducing points
+      const int64_t n = part ? m : nf, col0 = part ? Lp : 0;
+      for (int64_t j0 = 0; j0 < n; j0 += 64) {
+        for (int e = tid; e < 64 * DW; e += 256) {
+          const int r = e / DW, d = e % DW;
+          const int64_t j = j0 + r;
+          tl[r][d] = (d < D && j < n) ? (part ? scales[d] * Z[j * D + d] : omega[j * D + d]) : 0.0;
+        }
+        __syncthreads();  // the tile, and s o x of the step before
+        double acc[PP][4];
+#pragma unroll
+        for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[pp][q] = 0.0;
+        for (int d = 0; d < (int)D; ++d) {
+          double xv[PP], tv[4];
+#pragma unroll
+          for (int pp = 0; pp < PP; ++pp) xv[pp] = xs[ty + 16 * pp][d];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) tv[q] = tl[tx + 16 * q][d];
+#pragma unroll
+          for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              if (part) {
+                const double t = xv[pp] - tv[q];
+                acc[pp][q] = fma(t, t, acc[pp][q]);
+              } else {
+                acc[pp][q] = fma(xv[pp], tv[q], acc[pp][q]);
+              }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int64_t j = j0 + tx + 16 * q;
+          const bool in = j < n;
+          const double ph = (in && !part) ? phase[j] : 0.0;
+#pragma unroll
+          for (int pp = 0; pp < PP; ++pp) {
+            double b = 0.0;
+            if (in) {
+              if (part) b = fin ? variance * kernel_base<double>(kind, acc[pp][q]) : (2.0 * variance) * kernel_dbase<double>(kind, acc[pp][q]);
+              else b = fin ? amp * cos(acc[pp][q] + ph) : -amp * sin(acc[pp][q] + ph);
+              b *= WV[wrow[pp] + col0 + j];
+            }
+            Bs[ty + 16 * pp][tx + 16 * q] = b;
+          }
+        }
+        __syncthreads();
+        if (fin) {
+          if (tid < PT)
+            for (int jj = 0; jj < 64; ++jj) fsum += Bs[tid][jj];
+        } else {
+          for (int jj = 0; jj < 64; ++jj) {
+            double bv[PP], tv[DQ];
+#pragma unroll
+            for (int pp = 0; pp < PP; ++pp) bv[pp] = Bs[ty + 16 * pp][jj];
+#pragma unroll
+            for (int q = 0; q < DQ; ++q) tv[q] = tl[jj][tx + 16 * q];
+#pragma unroll
+            for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+              for (int q = 0; q < DQ; ++q) g[pp][q] = fma(bv[pp], part ? xsd[pp][q] - tv[q] : tv[q], g[pp][q]);
+          }
+        }
+        __syncthreads();  // before the next tile overwrites tl and Bs
+      }
+    }
+    if (fin) break;
+    b1k *= beta1, b2k *= beta2;
+    const double c1 = 1.0 - b1k, c2 = 1.0 - b2k;
+#pragma unroll
+    for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+      for (int q = 0; q < DQ; ++q) {
+        const double gr = sign * (sd[q] * g[pp][q]);
+        mo[pp][q] = beta1 * mo[pp][q] + (1.0 - beta1) * gr;
+        vo[pp][q] = beta2 * vo[pp][q] + (1.0 - beta2) * (gr * gr);
+        const double xn = x[pp][q] + lr[q] * ((mo[pp][q] / c1) / (sqrt(vo[pp][q] / c2) + eps));
+        x[pp][q] = fmin(fmax(xn, lo[q]), hi[q]);
+        xs[ty + 16 * pp][tx + 16 * q] = sd[q] * x[pp][q];  // read behind the next tile's barrier
+      }
+  }
+#pragma unroll
+  for (int pp = 0; pp < PP; ++pp) {
+    const int64_t pi = p0 + ty + 16 * pp;
+#pragma unroll
+    for (int q = 0; q < DQ; ++q)
+      if (pi < np && tx + 16 * q < D) Xw[pi * D + tx + 16 * q] = x[pp][q];
+  }
+  if (tid < PT && p0 + tid < np) Fw[p0 + tid] = fsum;
+}
+
+// The reduction over the starts of one sample (one workgroup per sample): the start with the largest sign f, ties to the smallest r;
+// a NaN never wins, and if every value is NaN start 0 does.  Comparisons only, so the order of the scan does not matter.  Writes the
+// best value, its index and the x of that start; each output may be NULL.
+__global__ __launch_bounds__(256) void k_pw_ascent_best(const double* __restrict__ Xw, const double* __restrict__ Fw, int64_t R, int64_t D,
+                                                        double sign, double* __restrict__ best_x, int64_t ldb,
+                                                        double* __restrict__ best_f, int64_t* __restrict__ best_idx) {
+  __shared__ double sv[256];
+  __shared__ int64_t si[256];
+  const int tid = threadIdx.x;
+  const int64_t s = blockIdx.x;
+  const double* F = Fw + s * R;
+  double bv = 0.0;
+  int64_t bi = -1;  // -1: nothing but NaN so far
+  for (int64_t r = tid; r < R; r += 256) {
+    const double v = sign * F[r];
+    if (v == v && (bi < 0 || v > bv)) bv = v, bi = r;
+  }
+  sv[tid] = bv, si[tid] = bi;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) {
+      const double ov = sv[tid + h];
+      const int64_t oi = si[tid + h];
+      if (oi >= 0 && (si[tid] < 0 || ov > sv[tid] || (ov == sv[tid] && oi < si[tid]))) sv[tid] = ov, si[tid] = oi;
+    }
+    __syncthreads();
+  }
+  const int64_t b = si[0] < 0 ? 0 : si[0];
+  if (tid == 0) {
+    if (best_f) best_f[s] = F[b];
+    if (best_idx) best_idx[s] = b;
+  }
+  if (best_x)
+    for (int d = tid; d < D; d += 256) best_x[s * ldb + d] = Xw[(s * R + b) * D + d];
+}
+
 // R[i][s] = U[i][s] + mu[i] - P[i][s] for i < m, s < S (in place in U, leading dimension ld): the residual u - Phi(Z) w of
 // Matheron's rule, u = mu + Xa' e.  The padding keeps the zeros of its operands.
 __global__ void k_pw_resid(int64_t m, int64_t S, int64_t ld, const double* __restrict__ mu, const double* __restrict__ P,

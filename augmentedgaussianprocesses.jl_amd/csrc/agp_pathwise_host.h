@@ -1,9 +1,10 @@
 // agp_pathwise_host.h -- host driver of pathwise posterior sampling (kernels: agp_pathwise.h): struct agp_pathwise, the draw that
 // the C ABI hands out and that owns everything it evaluates with, the scratch of its construction (PwScratch) and the pw_*
 // routines: argument checks, spectral tables, per-latent snapshot, features, the inverse factor, the chunked evaluation (pw_eval) and
-// the chunked input gradients (pw_eval_grad).  The
+// the chunked input gradients (pw_eval_grad) and the multi-start ascent (pw_maximize).  The
 // models build draws in Svgp<T>::pathwise_draw (agp_capi.hip) and its overrides; the agp_pathwise_* entry points are in agp_capi.hip.
 #pragma once
+#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
@@ -37,11 +38,14 @@ struct agp_pathwise {
   // and the slabs of GD dimensions before they are transposed into the caller's rows
   double *ws2 = nullptr, *Gs = nullptr;
   int GD = 0;
+  // the ascent's particle state (pw_maximize): the final x (mx_cap x D) and f (mx_cap) of every particle, grown by the call that needs more
+  double *mxX = nullptr, *mxF = nullptr;
+  int64_t mx_cap = 0;
   ~agp_pathwise() {
     for (auto& a : lat)
       for (double* q : {a.scales, a.Z, a.Zsc, a.zn, a.omega, a.phase, a.WV, a.E})
         if (q) (void)hipFree(q);
-    for (double* q : {ws, Fs, ws2, Gs})
+    for (double* q : {ws, Fs, ws2, Gs, mxX, mxF})
       if (q) (void)hipFree(q);
   }
 };
@@ -284,5 +288,88 @@ static agp_status pw_eval_grad(agp_pathwise& p, const double* xt, int64_t ldx, i
       }
     }
   }
+  return AGP_OK;
+}
+
+// ---- agp_pathwise_maximize (include/agp_hip.h; kernels and the formulation: agp_pathwise.h) ------------------------------------------
+constexpr int PW_ASCENT_PT = 16;  // particles per workgroup (measured against 32 and 64)
+template <int DQ>
+static void pw_ascent_launch(agp_pathwise& p, const agp_pathwise::Lat& a, const double* x0, int64_t ldx0, int shared, int64_t R, int64_t np,
+                             const agp_pw_ascent_opts& o, const agp::PwAscentBox& box) {
+  hipLaunchKernelGGL((agp::k_pw_ascent<PW_ASCENT_PT, DQ>), dim3((unsigned)((np + PW_ASCENT_PT - 1) / PW_ASCENT_PT)), dim3(256), 0,
+                     p.ctx->stream, x0, ldx0, shared, R, np, p.D, (const double*)a.scales, (const double*)a.omega, (const double*)a.phase,
+                     (int64_t)p.L, a.amp, (const double*)a.Z, p.m, a.kind, a.variance, (const double*)a.WV, p.ldw, p.Lp, (int)o.steps,
+                     o.minimize ? -1.0 : 1.0, o.beta1, o.beta2, o.eps, box, p.mxX, p.mxF);
+}
+// Every check first, touching nothing; then the particle state (grown if this call has more particles than any before: the one
+// place that may wait for the device), one launch of k_pw_ascent, the reduction over the starts if a best_* output is asked for,
+// and pitched copies of the state into x_out and f_out.  Nothing here waits for the stream.
+static agp_status pw_maximize(agp_pathwise* p, int32_t latent, const double* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o,
+                              double* x_out, int64_t ldxo, double* f_out, int64_t ldf, double* best_x, int64_t ldb, double* best_f,
+                              int64_t* best_idx) {
+  agp_ctx* ctx = p->ctx;
+  const char* who = "agp_pathwise_maximize: ";
+  auto invalid = [&](const std::string& what) {
+    ctx->err = who + what;
+    return AGP_ERR_INVALID;
+  };
+  if (!x0) return invalid("x0 must be given");
+  if (!o) return invalid("opts must be given");
+  if (!x_out && !f_out && !best_x && !best_f && !best_idx) return invalid("at least one output must be given");
+  if (latent < 0 || latent >= p->nl) return invalid("latent must lie in [0, n_latent)");
+  const agp_pathwise::Lat& a = p->lat[latent];
+  if (a.kind == AGP_K_EXPONENTIAL) {
+    ctx->err = std::string(who) + "ExponentialKernel is not differentiable at zero distance";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if (p->D > agp::PW_AD) {
+    ctx->err = std::string(who) + "D > 64 is not supported (D = " + std::to_string(p->D) + ")";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  if (R < 1 || (int64_t)p->S * R >= ((int64_t)1 << 31)) return invalid("n_starts >= 1 and n_samples * n_starts below 2^31");
+  if (ldx0 < p->D) return invalid("ldx0 >= D");
+  if (x_out && ldxo < p->D) return invalid("ldxo >= D when x_out is given");
+  if (f_out && ldf < R) return invalid("ldf >= n_starts when f_out is given");
+  if (best_x && ldb < p->D) return invalid("ldb >= D when best_x is given");
+  if (o->steps < 0 || o->steps > 65536) return invalid("steps must lie in [0, 65536]");
+  if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0)) return invalid("0 <= beta1, beta2 < 1");
+  if (!(o->eps > 0.0) || !std::isfinite(o->eps)) return invalid("eps must be finite and > 0");
+  if (!o->lo_host || !o->hi_host || !o->lr_host) return invalid("lo_host, hi_host and lr_host must be given");
+  agp::PwAscentBox box{};
+  for (int64_t d = 0; d < p->D; ++d) {
+    const double lo = o->lo_host[d], hi = o->hi_host[d], lr = o->lr_host[d];
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo <= hi))
+      return invalid("the bounds must be finite with lo <= hi (dimension " + std::to_string(d) + ")");
+    if (!std::isfinite(lr) || !(lr > 0.0)) return invalid("the step sizes must be finite and > 0 (dimension " + std::to_string(d) + ")");
+    box.lo[d] = lo, box.hi[d] = hi, box.lr[d] = lr;
+  }
+  const int64_t np = (int64_t)p->S * R;
+  if (np > p->mx_cap) {
+    for (double** q : {&p->mxX, &p->mxF})
+      if (*q) (void)hipFree(*q), *q = nullptr;  // (waits for what still reads them)
+    p->mx_cap = 0;
+    AGPCHK(dmalloc(ctx, &p->mxX, np * p->D));
+    AGPCHK(dmalloc(ctx, &p->mxF, np));
+    p->mx_cap = np;
+  }
+  const int shared = o->x0_shared ? 1 : 0;
+  switch ((p->D + 15) / 16) {
+    case 1: pw_ascent_launch<1>(*p, a, x0, ldx0, shared, R, np, *o, box); break;
+    case 2: pw_ascent_launch<2>(*p, a, x0, ldx0, shared, R, np, *o, box); break;
+    case 3: pw_ascent_launch<3>(*p, a, x0, ldx0, shared, R, np, *o, box); break;
+    default: pw_ascent_launch<4>(*p, a, x0, ldx0, shared, R, np, *o, box); break;
+  }
+  LAUNCHCHK(ctx);
+  if (best_x || best_f || best_idx) {
+    hipLaunchKernelGGL(agp::k_pw_ascent_best, dim3((unsigned)p->S), dim3(256), 0, ctx->stream, (const double*)p->mxX, (const double*)p->mxF,
+                       R, p->D, o->minimize ? -1.0 : 1.0, best_x, ldb, best_f, best_idx);
+    LAUNCHCHK(ctx);
+  }
+  if (x_out)
+    HIPCHK(ctx, hipMemcpy2DAsync(x_out, sizeof(double) * ldxo, p->mxX, sizeof(double) * p->D, sizeof(double) * p->D, np,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+  if (f_out)
+    HIPCHK(ctx, hipMemcpy2DAsync(f_out, sizeof(double) * ldf, p->mxF, sizeof(double) * R, sizeof(double) * R, p->S,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
   return AGP_OK;
 }

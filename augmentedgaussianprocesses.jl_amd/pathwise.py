@@ -3,6 +3,7 @@
     paths = AGP.sample_paths(model, n_samples, n_features=1024, seed=None, t=0)
     F = paths(X_test)          # (n_samples, n_t), or (n_latent, n_samples, n_t) for several latents
     G = paths.grad(X_test)     # (n_samples, n_t, D): d f_s / d x, in closed form from the draw's tables; value=True gives (F, G)
+    x, f = paths.maximize(X0, (lo, hi), steps=100)   # (n_samples, D), (n_samples,): every path's best of R ADAM ascents, on the device
 
 Decoupled sampling (Wilson et al. 2020, "Efficiently sampling functions from Gaussian process posteriors"): a prior function from
 random Fourier features, a draw u ~ q(u), Matheron's correction.  A draw is an ordinary function: it can be evaluated at any number
@@ -21,6 +22,61 @@ from . import capi
 N_MAX = 65536  # n_features and n_samples (agp_svgp_pathwise_draw)
 CTR_MAX = 2 ** 32  # products that index one 32-bit counter word, and the draw counter t
 GRAD_REFUSAL_EXPONENTIAL = "ExponentialKernel is not differentiable at zero distance"  # agp_pathwise_eval_grad says the same
+
+MAX_D_ASCENT = 64  # agp_pathwise_maximize
+MAX_STEPS = 65536
+
+
+def check_maximize_args(n_samples: int, D: int, n_latent: int, x0_shape, bounds, steps=100, lr=None, beta1=0.9, beta2=0.999,
+                        eps=1e-8, latent=0):
+    """every argument check of paths.maximize / agp_pathwise_maximize, on the host before any device call.  x0_shape is (R, D) for
+    shared starts or (S, R, D) per sample.  Returns (lo, hi, lr, shared, R): the box and the step sizes as float64 arrays of length
+    D.  lr=None is the interface default 0.02 (hi - lo) per dimension -- a default, not a tuned value; a dimension pinned by
+    lo = hi then gets the step size 1, which the box makes irrelevant."""
+    if int(D) > MAX_D_ASCENT:
+        raise NotImplementedError(f"paths.maximize: D > {MAX_D_ASCENT} is not supported (D = {D})")
+    if not 0 <= int(latent) < int(n_latent):
+        raise ValueError(f"latent must lie in [0, {n_latent}) (got {latent})")
+    shape = tuple(int(v) for v in x0_shape)
+    if len(shape) == 2 and shape[1] == D:
+        shared, R = True, shape[0]
+    elif len(shape) == 3 and shape[0] == n_samples and shape[2] == D:
+        shared, R = False, shape[1]
+    else:
+        raise ValueError(f"X0 must be (R, {D}) for shared starts or ({n_samples}, R, {D}) per sample (got {shape})")
+    if R < 1 or n_samples * R >= 2 ** 31:
+        raise ValueError(f"the number of starts must be >= 1 and n_samples * starts below 2^31 (got {R})")
+    if not (isinstance(bounds, (tuple, list)) and len(bounds) == 2):
+        raise ValueError("bounds must be a pair (lo, hi), each a scalar or of length D")
+
+    def vec(v, name):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(D, float(a))
+        if a.shape != (D,):
+            raise ValueError(f"{name} must be a scalar or of length {D} (got shape {a.shape})")
+        return np.ascontiguousarray(a)
+
+    lo, hi = vec(bounds[0], "lo"), vec(bounds[1], "hi")
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError("the bounds must be finite")
+    if np.any(lo > hi):
+        raise ValueError("the bounds must satisfy lo <= hi in every dimension")
+    if lr is None:
+        lrv = 0.02 * (hi - lo)
+        lrv[lrv == 0.0] = 1.0
+    else:
+        lrv = vec(lr, "lr")
+    if not (np.all(np.isfinite(lrv)) and np.all(lrv > 0.0)):
+        raise ValueError("the step sizes lr must be finite and > 0")
+    if not 0 <= int(steps) <= MAX_STEPS:
+        raise ValueError(f"steps must lie in [0, {MAX_STEPS}] (got {steps})")
+    for name, b in (("beta1", beta1), ("beta2", beta2)):
+        if not 0.0 <= float(b) < 1.0:
+            raise ValueError(f"{name} must lie in [0, 1) (got {b})")
+    if not (np.isfinite(eps) and float(eps) > 0.0):
+        raise ValueError(f"eps must be finite and > 0 (got {eps})")
+    return lo, hi, lrv, shared, R
 
 
 def check_draw_args(m: int, D: int, n_samples: int, n_features: int, t: int, seed: Optional[int] = None) -> None:
@@ -120,6 +176,46 @@ class PathwiseSamples:
         if not on_device:
             out = [t.cpu().numpy() for t in out]
         return tuple(out) if value else out[0]
+
+    def maximize(self, X0, bounds, *, steps: int = 100, lr=None, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                 latent: int = 0, minimize: bool = False, full: bool = False):
+        """multi-start ADAM ascent of the paths on the device, one launch (agp_pathwise_maximize): Thompson sampling's inner loop.
+        X0 is (R, D), the same starts for every path, or (S, R, D); bounds = (lo, hi), each a scalar or of length D; lr a scalar, a
+        vector of length D, or None for the interface default 0.02 (hi - lo) per dimension (a default, not a tuned value).  Every
+        path s climbs from each of its R starts for `steps` steps inside the box; returned is the FINAL iterate of the best start:
+        (x_best (S, D), f_best (S,)), with full=True (x_best, f_best, idx (S,), X (S, R, D), F (S, R)).  minimize=True descends
+        and picks the smallest value.  NumPy in gives NumPy out; a torch tensor on the device gives device tensors.  Every
+        argument is checked on the host first (check_maximize_args); a latent with an ExponentialKernel raises NotImplementedError
+        before the device is touched."""
+        p = self._live()
+        if not 0 <= int(latent) < self.n_latent:
+            raise ValueError(f"latent must lie in [0, {self.n_latent}) (got {latent})")
+        if self._kinds[int(latent)] == capi.K_EXPONENTIAL:
+            raise NotImplementedError("paths.maximize: " + GRAD_REFUSAL_EXPONENTIAL)
+        lo, hi, lrv, shared, R = check_maximize_args(self.n_samples, self.D, self.n_latent, tuple(X0.shape) if hasattr(X0, "shape") else np.shape(X0), bounds, steps, lr, beta1, beta2,
+                                                     eps, latent)
+        import torch
+
+        model = self._model
+        on_device = isinstance(X0, torch.Tensor) and X0.is_cuda
+        dev = model._dev()
+        Xd = torch.as_tensor(X0, dtype=torch.float64).to(dev).reshape(-1, self.D).contiguous()
+        S, D = self.n_samples, self.D
+        X = torch.empty(S, R, D, dtype=torch.float64, device=dev)
+        F = torch.empty(S, R, dtype=torch.float64, device=dev)
+        xb = torch.empty(S, D, dtype=torch.float64, device=dev)
+        fb = torch.empty(S, dtype=torch.float64, device=dev)
+        ib = torch.empty(S, dtype=torch.int64, device=dev)
+        as_p = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        opts = capi.PwAscentOpts(int(steps), int(bool(minimize)), int(shared), float(beta1), float(beta2), float(eps), as_p(lo), as_p(hi),
+                                 as_p(lrv))
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        L = capi.lib()
+        model._chk(L.agp_pathwise_maximize(p, int(latent), ptr(Xd), D, R, C.byref(opts), ptr(X) if full else None, D,
+                                           ptr(F) if full else None, R, ptr(xb), D, ptr(fb), ptr(ib)))
+        model._chk(L.agp_ctx_sync(model._ctx))
+        out = (xb, fb, ib, X, F) if full else (xb, fb)
+        return out if on_device else tuple(t.cpu().numpy() for t in out)
 
     def tables(self, latent: int = 0):
         """the draw's tables of one latent as NumPy arrays: omega (l, D), phase (l), W (l, S), V (m, S), E (m, S)"""

@@ -1014,6 +1014,31 @@ agp_status agp_mc_expectations(agp_ctx* ctx, const agp_lik_desc* lik, const void
  *   touching no output: a latent of the draw has the ExponentialKernel ("ExponentialKernel is not differentiable at zero distance":
  *   its paths have a kink on Z; agp_svgp_predict_f_grad refuses it the same way).  AGP_ERR_INVALID with a message: xt or g_out NULL,
  *   n_t < 0, ldx < D, lds < n_t, ldg < D, ldo < n_t with f_out given.
+ * agp_pathwise_maximize  multi-start ADAM ascent of the paths of one latent, on the device and in one launch: what Thompson sampling
+ *   does with a draw.  A particle is a pair (sample s, start r), s < n_samples, r < n_starts; it starts at x0[s][r] (x0_shared: at
+ *   x0[r], the same starts for every sample) clipped into the box [lo, hi] and takes T = steps steps, k = 1 .. T, with the f and
+ *   d f_s / d x of agp_pathwise_eval_grad (the same closed forms, q summed over ascending d from direct differences):
+ *       g = sign grad f_s(x)   (sign = +1, or -1 with minimize)
+ *       m = beta1 m + (1 - beta1) g ;  v = beta2 v + (1 - beta2) g o g ;  mh = m / (1 - b1) ;  vh = v / (1 - b2)
+ *       x = min(max(x + lr o mh / (sqrt(vh) + eps), lo), hi)
+ *   m = v = 0 before step 1; b1 = beta1^k and b2 = beta2^k as running products (b = 1 before step 1, b = b beta per step).  After
+ *   step T the path is evaluated once more: f_out is f_s of the returned x, and the FINAL iterate is returned, not the best one
+ *   along the way, so every output is a continuous function of the inputs.  steps = 0 returns the clipped starts and their values.
+ *   Outputs, each nullable (not all): x_out[s][r][d] at x_out + (s * n_starts + r) * ldxo + d; f_out[s][r] at f_out + s * ldf + r;
+ *   per sample the best start -- the largest sign f, ties to the smallest r, a NaN never wins and start 0 does if every value is
+ *   NaN -- as best_x[s][d] at best_x + s * ldb + d, best_f[s] (f itself, not sign f) and best_idx[s] (int64).  Padding is never
+ *   read or written.  lo, hi and lr (D each, in input units) are HOST arrays, validated without a synchronisation and handed to
+ *   the kernel with its arguments.  One workgroup carries a tile of particles through all T steps with x, m, v and the gradient
+ *   in registers and Omega / s o Z staged through LDS; no atomics, no communication between workgroups, every sum over j, then
+ *   r, ascending in one accumulator: a particle has the same bits wherever it stands in the call, whichever particles share its
+ *   tile, with x0 shared or per sample, and on every repeat.  The particle state (n_samples n_starts (D + 1) doubles) belongs to
+ *   the draw and is allocated by the first call; a call with more particles than any before re-allocates it (the only place that
+ *   may wait for the device).  Asynchronous on the context's stream; nothing is drawn; the draw is a snapshot as for the other
+ *   calls.  AGP_ERR_UNSUPPORTED, touching no output: the latent has the ExponentialKernel ("ExponentialKernel is not
+ *   differentiable at zero distance"); D > 64 ("D > 64 is not supported").  AGP_ERR_INVALID with a message: p, x0 or opts NULL; all
+ *   five outputs NULL; latent outside [0, n_latent); n_starts < 1 or n_samples n_starts >= 2^31; ldx0 < D, ldxo < D, ldf <
+ *   n_starts, ldb < D (of outputs that are given); steps outside [0, 65536]; beta1 or beta2 outside [0, 1); eps not finite and
+ *   positive; lo_host, hi_host or lr_host NULL, a non-finite bound, lo > hi, a step size that is not finite and positive.
  * agp_pathwise_get   which = AGP_PW_OMEGA (l x D, ld >= D), AGP_PW_PHASE (l; ld not read), AGP_PW_W (l x S, ld >= S), AGP_PW_V
  *   (m x S, ld >= S), AGP_PW_E (m x S, ld >= S).
  * agp_pathwise_features  the spectral draw alone, outside any model: omega_out double[l][D], phase_out double[l], dense, device;
@@ -1026,6 +1051,22 @@ agp_status agp_pathwise_eval(agp_pathwise* p, const void* xt, int64_t ldx, int64
 agp_status agp_pathwise_eval_grad(agp_pathwise* p, const void* xt, int64_t ldx, int64_t n_t,
                                   void* f_out, int64_t ldo, /* nullable: the values, laid out as agp_pathwise_eval writes them */
                                   void* g_out, int64_t lds, int64_t ldg);
+typedef struct {
+  int32_t steps;            /* T, 0 <= T <= 65536; T = 0 returns the clipped starts and their values */
+  int32_t minimize;         /* 0: ascend, 1: descend */
+  int32_t x0_shared;        /* 0: x0[s][r][d] at x0 + (s * n_starts + r) * ldx0 + d;  1: x0[r][d], the same starts for every sample */
+  double beta1, beta2, eps; /* 0 <= beta < 1, eps > 0 */
+  const double* lo_host;    /* D lower bounds, host memory (like ard_scales_host), finite, lo <= hi */
+  const double* hi_host;
+  const double* lr_host;    /* D step sizes in input units, host memory, finite and > 0 */
+} agp_pw_ascent_opts;
+agp_status agp_pathwise_maximize(agp_pathwise* p, int32_t latent, const void* x0, int64_t ldx0, int64_t n_starts,
+                                 const agp_pw_ascent_opts* opts,
+                                 void* x_out, int64_t ldxo, /* nullable: [s][r][d], ldxo >= D */
+                                 void* f_out, int64_t ldf,  /* nullable: [s][r], ldf >= n_starts */
+                                 void* best_x, int64_t ldb, /* nullable: [s][d], ldb >= D */
+                                 void* best_f,              /* nullable: [s] */
+                                 void* best_idx);           /* nullable: int64 [s] */
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D);
 agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void* out, int64_t ld);
 agp_status agp_pathwise_destroy(agp_pathwise* p);

@@ -1459,6 +1459,53 @@ function pathwise_grad(ps::PathwiseSamples, X_test::AbstractMatrix; value::Bool=
     paths = [permutedims(Fh[:, :, l]) for l in 1:ps.n_latent]
     return (ps.n_latent == 1 ? only(paths) : paths), G
 end
+# pathwise_maximize(paths, X0, lo, hi; steps=100, lr=nothing, ...): multi-start ADAM ascent of every path on the device, one launch
+# (agp_pathwise_maximize).  X0 is R x D (the same starts for every path) or n_samples x R x D; lo, hi and lr are scalars or vectors of
+# length D, lr=nothing the interface default 0.02 (hi - lo).  Returns (x_best n_samples x D, f_best n_samples); full=true returns
+# (x_best, f_best, idx (1-based), X n_samples x R x D, F n_samples x R).  The struct mirrors agp_pw_ascent_opts field by field.
+# Never run: there is no Julia toolchain in the test environment.
+struct PwAscentOpts
+    steps::Int32
+    minimize::Int32
+    x0_shared::Int32
+    beta1::Float64
+    beta2::Float64
+    eps::Float64
+    lo_host::Ptr{Float64}
+    hi_host::Ptr{Float64}
+    lr_host::Ptr{Float64}
+end
+function pathwise_maximize(ps::PathwiseSamples, X0::AbstractArray, lo, hi; steps::Integer=100, lr=nothing, beta1::Real=0.9,
+                           beta2::Real=0.999, eps::Real=1e-8, latent::Integer=1, minimize::Bool=false, full::Bool=false)
+    ps.p == C_NULL && error("the paths have been freed")
+    D, S = ps.D, ps.n_samples
+    shared = ndims(X0) == 2
+    (shared ? size(X0, 2) == D : (ndims(X0) == 3 && size(X0, 1) == S && size(X0, 3) == D)) ||
+        error("pathwise_maximize: X0 must be R x $D or $S x R x $D")
+    R = shared ? size(X0, 1) : size(X0, 2)
+    vec_of(v) = v isa Number ? fill(Float64(v), D) : collect(Float64, v)
+    lov, hiv = vec_of(lo), vec_of(hi)
+    lrv = lr === nothing ? map(w -> w == 0 ? 1.0 : 0.02 * w, hiv .- lov) : vec_of(lr)
+    (length(lov) == D && length(hiv) == D && length(lrv) == D) || error("pathwise_maximize: lo, hi and lr must be scalars or of length $D")
+    Xd = ROCArray{Float64}(shared ? permutedims(X0) : permutedims(X0, (3, 2, 1)))   # column-major D x R (x S) == [s][r][d]
+    X = ROCArray{Float64}(undef, D, R, S)
+    F = ROCArray{Float64}(undef, R, S)
+    xb = ROCArray{Float64}(undef, D, S)
+    fb = ROCArray{Float64}(undef, S)
+    ib = ROCArray{Int64}(undef, S)
+    GC.@preserve lov hiv lrv begin
+        opts = Ref(PwAscentOpts(steps, minimize ? 1 : 0, shared ? 1 : 0, beta1, beta2, eps, pointer(lov), pointer(hiv), pointer(lrv)))
+        check(ps.ctx, ccall((:agp_pathwise_maximize, libagp), Int32,
+                            (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Int64, Ref{PwAscentOpts}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid},
+                             Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                            ps.p, latent - 1, pointer(Xd), D, R, opts, full ? pointer(X) : C_NULL, D, full ? pointer(F) : C_NULL, R,
+                            pointer(xb), D, pointer(fb), pointer(ib)))
+    end
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), ps.ctx)
+    x_best, f_best = permutedims(Array(xb)), Array(fb)
+    full || return x_best, f_best
+    return x_best, f_best, Array(ib) .+ 1, permutedims(Array(X), (3, 2, 1)), permutedims(Array(F))
+end
 # the tables of one latent (0-based `which`: 0 omega l x D, 1 phase l, 2 W l x S, 3 V m x S, 4 E m x S), as Julia matrices
 function pathwise_table(ps::PathwiseSamples, which::Integer; latent::Integer=1)
     rows, cols = which == 0 ? (ps.n_features, ps.D) : which == 1 ? (ps.n_features, 1) :
