@@ -122,6 +122,7 @@ struct Svgp : SvgpBase {
   T *hyH1 = nullptr, *hyH2 = nullptr, *hyH3 = nullptr, *hy_gmu = nullptr, *hy_gs = nullptr, *hy_muf = nullptr,
     *hy_pZ = nullptr, *hy_dZ = nullptr;
   double *hy_pvar = nullptr, *hy_pscale = nullptr, *hy_g = nullptr;
+  int64_t hy_tiles = 0;  // tiles that hy_pvar / hy_pscale hold partial sums for (hyper_alloc)
   // multi-output mode (MOSVGP): n_task likelihoods over A-mixed latents
   bool mo = false;
   MoCfg<T> mocfg{};
@@ -1383,7 +1384,12 @@ struct Svgp : SvgpBase {
       return AGP_ERR_UNSUPPORTED;
     }
     // (partial sums per RT x 64 tile of a backward pass: k_kernel_backward, HB_RT rows per workgroup)
-    const int64_t tiles = std::max((Bp / HB_RT) * (mp / TILE), (mp / HB_RT) * (mp / TILE));
+    int64_t tiles = std::max((Bp / HB_RT) * (mp / TILE), (mp / HB_RT) * (mp / TILE));
+    // (the streaming model's pass through K_a = k(Z_a, Z_a) has map x map entries: with more old inducing points than new ones it
+    // has more tiles than either pass above)
+    for (const auto& g : lat)
+      if (g.on && !g.on_first) tiles = std::max(tiles, (g.map / HB_RT) * (g.map / TILE));
+    hy_tiles = tiles;
     const int64_t rowt = std::max(Bp / HB_RT, mp / HB_RT);
     AGPCHK(dmalloc(ctx, &hyH1, Bp * mp));
     AGPCHK(dmalloc(ctx, &hyH2, Bp * mp));
@@ -1596,7 +1602,7 @@ struct Svgp : SvgpBase {
       //   G_kappa_a = D kappa_a (Sigma + mu mu') - eta_a mu' - D K_ab/2 ; G_Kab = G_kappa_a K^-1 - D kappa_a/2 ;
       //   G_K -= sym(kappa_a' G_kappa_a K^-1) ; G_Ka = D/2
       const int64_t map = g.map, ma = g.ma;
-      if (map / TILE > std::max(Bp / TILE, mp / TILE)) {
+      if (map / TILE > std::max(Bp / TILE, mp / TILE) || (map / TILE) * (map / HB_RT) > hy_tiles) {
         ctx->err = "online hyper-gradient: more old inducing points than the scratch was sized for";
         return AGP_ERR_UNSUPPORTED;
       }
@@ -1672,7 +1678,7 @@ struct Svgp : SvgpBase {
       dim3 ga((unsigned)(map / TILE), (unsigned)(map / HB_RT));
       hipLaunchKernelGGL((k_kernel_backward<T>), ga, dim3(NTHREADS), 0, st(), (const T*)g.Za, D, (const int64_t*)nullptr, ma,
                          (const T*)g.Za, D, ma, D, (const T*)g.scales, g.k.kind, kvar(g), (const T*)g.invDa, map,
-                         hy_pvar, hy_pscale, hy_pZ, map);
+                         hy_pvar, hy_pscale, hy_pZ, (int64_t)0);  // (p_pad = 0: no pZ; map rows would not fit hy_pZ's mp)
       hipLaunchKernelGGL((k_hyper_reduce_scalar<T>), dim3((unsigned)(D + 1)), dim3(256), 0, st(), (int64_t)ga.x * ga.y, D,
                          (const double*)hy_pvar, (const double*)hy_pscale, hy_g, 0.5);
       LAUNCHCHK(ctx);

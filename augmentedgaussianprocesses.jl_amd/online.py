@@ -14,6 +14,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import capi
+from .likelihoods import LogisticSoftMaxLikelihood
 from .svgp import SVGP, AnalyticVI, _torch, refuse_numerical
 from .svgp import predict_f as _predict_f_fn
 from .svgp import predict_y as _predict_y_fn
@@ -198,6 +199,13 @@ def train_online(model: OnlineSVGP, X, y, state=None, *, iterations: int = 20, c
         if mb > old._max_batch:
             old._ensure_handle(mb)
         dev = old._dev()
+        if isinstance(model.likelihood, LogisticSoftMaxLikelihood) and B != model._data[2]:
+            # A batch of another size: the local variables of the previous batch do not fit it, the reference can only go on with
+            # fresh ones (init_local_vars, states.jl:11-28; its in-place local_updates! needs arrays of the batch's size).  Every
+            # local variable but the LogisticSoftMax alpha is overwritten by the first local update; alpha = n_class is state.
+            a = torch.full((old._max_batch,), float(model.likelihood.n_class), dtype=old.tdtype, device=dev)
+            old._chk(L.agp_svgp_set_lsm_alpha(old._h, C.c_void_p(a.data_ptr()), a.numel()))
+            old._chk(L.agp_ctx_sync(old._ctx))
         snaps = []
         for l in range(old.n_latent):  # save_old_gp! onlinetraining.jl:170-180
             iD = torch.empty(old.m, old.m, dtype=old.tdtype, device=dev)
