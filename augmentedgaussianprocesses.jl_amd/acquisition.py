@@ -1,0 +1,267 @@
+"""Acquisition functions of the predictive moments and their multi-start maximiser on the device (include/agp_hip.h, "ACQUISITION
+FUNCTIONS"): the other half of Bayesian optimisation next to `sample_paths`.
+
+    a = AGP.acquisition(model, AGP.EI(best=y.max()), X)                      # (n_t,); grad=True gives (a, G (n_t, D))
+    x, a = AGP.maximize_acquisition(model, AGP.UCB(2.0), X0, (lo, hi))       # the best of R ADAM ascents, on the device
+    a, dmu, dvar = AGP.acquisition_moments(AGP.PI(best=0.0), mu, var, grad=True)
+
+UCB = s mu + beta sigma, EI = sigma (z Phi(z) + phi(z)), PI = Phi(z) with z = (s (mu - best) - xi) / sigma; s = -1 with minimize=True
+(the objective is minimised; the acquisition function itself is always maximised).  Float64, single-output models, D <= 64,
+SqExponential / Matern32 / Matern52 kernels.  Not here: log-EI (EI underflows to 0 for z below about -38), Float32, multi-output and
+sharded models, batch (q-) acquisition.  No counterpart in the reference.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional
+
+import numpy as np
+
+from . import capi
+from .pathwise import check_maximize_args
+from .predgrad import MAX_D, predgrad_refusal
+
+ACQ_UCB, ACQ_EI, ACQ_PI = 0, 1, 2
+
+
+class _Acquisition:
+    kind = -1
+    beta, best, xi = 0.0, 0.0, 0.0
+
+    def check(self) -> None:
+        """the argument checks of agp_acq_desc, on the host"""
+        for name in ("beta", "xi"):
+            v = getattr(self, name)
+            if not (isinstance(v, (int, float, np.floating, np.integer)) and math.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{type(self).__name__}: {name} must be finite and >= 0 (got {v})")
+        if self.best is not None and not math.isfinite(self.best):
+            raise ValueError(f"{type(self).__name__}: best must be finite (got {self.best})")
+
+    def desc(self, minimize: bool, best: Optional[float] = None) -> capi.AcqDesc:
+        b = self.best if best is None else best
+        return capi.AcqDesc(self.kind, int(bool(minimize)), float(self.beta), float(0.0 if b is None else b), float(self.xi))
+
+
+class UCB(_Acquisition):
+    """upper confidence bound s mu + beta sigma (with minimize=True the lower bound, negated: -mu + beta sigma)"""
+    kind = ACQ_UCB
+
+    def __init__(self, beta: float = 2.0):
+        self.beta = beta
+        self.check()
+
+    def __repr__(self):
+        return f"UCB(beta={self.beta})"
+
+
+class EI(_Acquisition):
+    """expected improvement over `best` by more than `xi`; best=None takes the incumbent from the model's own data (GP, VGP)"""
+    kind = ACQ_EI
+
+    def __init__(self, best: Optional[float] = None, xi: float = 0.0):
+        self.best, self.xi = best, xi
+        self.check()
+
+    def __repr__(self):
+        return f"EI(best={self.best}, xi={self.xi})"
+
+
+class PI(_Acquisition):
+    """probability of improvement over `best` by more than `xi`; best=None as for EI"""
+    kind = ACQ_PI
+
+    def __init__(self, best: Optional[float] = None, xi: float = 0.0):
+        self.best, self.xi = best, xi
+        self.check()
+
+    def __repr__(self):
+        return f"PI(best={self.best}, xi={self.xi})"
+
+
+def acquisition_refusal(model, latent: int = 0) -> Optional[str]:
+    """Why agp_svgp_acquisition / agp_svgp_acq_maximize refuse this model, or None: decided here, before the device is touched."""
+    from .movgp import MOVGP
+    from .online import OnlineSVGP
+    from .svgp import MOSVGP, SVGP
+
+    if isinstance(model, OnlineSVGP):
+        if model._cur is None:
+            return "the online model has not seen a batch yet"
+        model = model._cur
+    if isinstance(model, (MOSVGP, MOVGP)):
+        return "multi-output models (MOSVGP, MOVGP) are not supported"
+    why = predgrad_refusal(model)  # no handle, MCGP, ExponentialKernel (any latent), D > 64, shards
+    if why is not None:
+        return why
+    assert isinstance(model, SVGP) and model.D <= MAX_D
+    if np.dtype(model.T) != np.dtype(np.float64):
+        return "Float32 models are not supported (the acquisition functions are Float64)"
+    return None
+
+
+def _resolve(model, acq, latent, minimize):
+    """(the model that owns the handle, the checked descriptor): every refusal and argument check, before the device is touched"""
+    from .gp import GP
+    from .online import OnlineSVGP
+    from .vgp import VGP
+
+    if not isinstance(acq, _Acquisition):
+        raise TypeError("acq must be UCB(...), EI(...) or PI(...)")
+    acq.check()
+    why = acquisition_refusal(model, latent)
+    if why is not None:
+        raise NotImplementedError(f"acquisition: {why}")
+    if isinstance(model, OnlineSVGP):
+        model = model._cur
+    if not 0 <= int(latent) < model.n_latent:
+        raise ValueError(f"latent must lie in [0, {model.n_latent}) (got {latent})")
+    best = None
+    if acq.kind != ACQ_UCB and acq.best is None:
+        if not isinstance(model, (GP, VGP)) or getattr(model, "X", None) is None:
+            raise ValueError(f"{type(acq).__name__}(best=None) takes the incumbent from the model's training inputs: only a GP or VGP "
+                             f"has them; give best= for a {type(model).__name__}")
+        best = _incumbent(model, int(latent), bool(minimize))
+    return model, acq.desc(minimize, best)
+
+
+def _incumbent(model, latent: int, minimize: bool) -> float:
+    """the max (min with minimize) of the predict_f mean at the model's training inputs"""
+    import torch
+
+    L = capi.lib()
+    Xd = model._upload(model.X, 1)
+    h = model._ensure_handle(max(model._max_batch, 1))
+    mu = torch.empty(model.n_latent, Xd.shape[0], dtype=torch.float64, device=model._dev())
+    model._chk(L.agp_svgp_predict_f(h, C.c_void_p(Xd.data_ptr()), Xd.stride(0), Xd.shape[0], C.c_void_p(mu.data_ptr()), None))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    return float(mu[latent].min() if minimize else mu[latent].max())
+
+
+def acquisition(model, acq, X, *, grad: bool = False, latent: int = 0, minimize: bool = False, obsdim: int = 1):
+    """alpha(x_i) of one latent at the rows of X: (n_t,), and with grad=True (alpha, G) with G[i, d] = d alpha / d x_id, (n_t, D).
+    Streamed in chunks of 4096 points, deterministic, the model's state is left as it was (agp_svgp_acquisition).  NumPy in gives
+    NumPy out; a torch tensor on the device gives device tensors.  SVGP (AnalyticVI / SVI, QuadratureVI, MCIntegrationVI), VGP, GP,
+    OnlineSVGP in Float64; everything else raises NotImplementedError before the device is touched."""
+    if not isinstance(grad, bool):
+        raise TypeError("acquisition: grad is a bool")
+    if obsdim not in (1, 2):
+        raise ValueError("acquisition: obsdim is 1 (points are rows) or 2 (points are columns)")
+    model, d = _resolve(model, acq, latent, minimize)
+    import torch
+
+    on_device = isinstance(X, torch.Tensor) and X.is_cuda
+    L = capi.lib()
+    Xd = model._upload(X, obsdim)
+    nt, D = Xd.shape
+    h = model._ensure_handle(max(model._max_batch, 1))
+    dev = model._dev()
+    a = torch.empty(nt, dtype=torch.float64, device=dev)
+    G = torch.empty(nt, D, dtype=torch.float64, device=dev) if grad else None
+    model._chk(L.agp_svgp_acquisition(h, int(latent), C.byref(d), C.c_void_p(Xd.data_ptr()), Xd.stride(0) if nt else D, nt,
+                                      C.c_void_p(a.data_ptr()), C.c_void_p(G.data_ptr()) if grad else None, D))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    out = (a, G) if grad else (a,)
+    if not on_device:
+        out = tuple(t.cpu().numpy() for t in out)
+    return out if grad else out[0]
+
+
+def acquisition_moments(acq, mu, var, *, minimize: bool = False, grad: bool = False, device: Optional[int] = None):
+    """the point function alone on given moments (agp_acq_moments): alpha, and with grad=True (alpha, d alpha / d mu, d alpha / d var)
+    with d alpha / d var = d alpha / d sigma / (2 sigma).  var <= 0 takes the defined limit, a NaN moment gives NaN.  best is
+    required for EI / PI.  NumPy in gives NumPy out; device tensors in give device tensors out."""
+    if not isinstance(acq, _Acquisition):
+        raise TypeError("acq must be UCB(...), EI(...) or PI(...)")
+    acq.check()
+    if acq.kind != ACQ_UCB and acq.best is None:
+        raise ValueError(f"{type(acq).__name__}: best must be given (there is no model to take an incumbent from)")
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("no HIP device visible: augmentedgaussianprocesses.jl_amd has no CPU fallback")
+    on_device = isinstance(mu, torch.Tensor) and mu.is_cuda
+    dev = mu.device if on_device else torch.device("cuda", device if device is not None else torch.cuda.current_device())
+    mud = torch.as_tensor(mu, dtype=torch.float64).to(dev).contiguous()
+    vard = torch.as_tensor(var, dtype=torch.float64).to(dev).contiguous()
+    if mud.shape != vard.shape:
+        raise ValueError("mu and var must have the same shape")
+    L = capi.lib()
+    ctx = C.c_void_p()
+    st = L.agp_ctx_create(dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(ctx))
+    if st != capi.AGP_OK:
+        raise capi.AGPError(st, "agp_ctx_create failed")
+    try:
+        d = acq.desc(minimize)
+        outs = [torch.empty_like(mud) for _ in range(3 if grad else 1)]
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        capi.check(ctx, L.agp_acq_moments(ctx, C.byref(d), mud.numel(), ptr(mud), ptr(vard), ptr(outs[0]),
+                                          ptr(outs[1]) if grad else None, ptr(outs[2]) if grad else None))
+        capi.check(ctx, L.agp_ctx_sync(ctx))
+    finally:
+        L.agp_ctx_destroy(ctx)
+    if not on_device:
+        outs = [t.cpu().numpy() for t in outs]
+    return tuple(outs) if grad else outs[0]
+
+
+def maximize_acquisition(model, acq, X0, bounds, *, steps: int = 100, lr=None, beta1: float = 0.9, beta2: float = 0.999,
+                         eps: float = 1e-8, latent: int = 0, minimize: bool = False, full: bool = False):
+    """multi-start ADAM ascent of the acquisition function inside the box, on the device without a host synchronisation between
+    steps (agp_svgp_acq_maximize).  X0 is (R, D); bounds = (lo, hi), each a scalar or of length D; lr a scalar, a vector of length D,
+    or None for the interface default 0.02 (hi - lo) per dimension, as in paths.maximize.  Every start climbs for `steps` steps;
+    returned is the FINAL iterate of the best start, (x_best (D,), a_best), and with full=True (x_best, a_best, idx, X (R, D), A
+    (R,)).  minimize=True is the direction of the OBJECTIVE (UCB becomes the negated lower bound, EI / PI improve downwards); the
+    acquisition value is always maximised.  NumPy in gives NumPy out; a device tensor in gives device tensors out.  Every argument
+    is checked on the host first."""
+    model, d = _resolve(model, acq, latent, minimize)
+    shape = tuple(X0.shape) if hasattr(X0, "shape") else np.shape(X0)
+    if len(shape) != 2 or shape[1] != model.D:
+        raise ValueError(f"X0 must be (R, {model.D}) (got {tuple(shape)})")
+    lo, hi, lrv, _, R = check_maximize_args(1, model.D, model.n_latent, shape, bounds, steps, lr, beta1, beta2, eps, latent)
+    import torch
+
+    on_device = isinstance(X0, torch.Tensor) and X0.is_cuda
+    dev = model._dev()
+    D = model.D
+    Xd = torch.as_tensor(X0, dtype=torch.float64).to(dev).reshape(R, D).contiguous()
+    h = model._ensure_handle(max(model._max_batch, 1))
+    X = torch.empty(R, D, dtype=torch.float64, device=dev)
+    A = torch.empty(R, dtype=torch.float64, device=dev)
+    xb = torch.empty(D, dtype=torch.float64, device=dev)
+    ab = torch.empty((), dtype=torch.float64, device=dev)
+    ib = torch.empty((), dtype=torch.int64, device=dev)
+    as_p = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    opts = capi.PwAscentOpts(int(steps), 0, 0, float(beta1), float(beta2), float(eps), as_p(lo), as_p(hi), as_p(lrv))
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    L = capi.lib()
+    model._chk(L.agp_svgp_acq_maximize(h, int(latent), C.byref(d), ptr(Xd), D, R, C.byref(opts), ptr(X) if full else None, D,
+                                       ptr(A) if full else None, ptr(xb), ptr(ab), ptr(ib)))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    out = (xb, ab, ib, X, A) if full else (xb, ab)
+    return out if on_device else tuple(t.cpu().numpy() for t in out)
+
+
+def predictor(model, latent: int = 0):
+    """(a (m,), A (m, m)): the two objects of the predictor after it has been brought up to date (AGP_VEC_APRED / AGP_MAT_APRED of
+    agp_svgp_get_matrix), a = K^-1 mu and A = K^-1 - K^-1 Sigma K^-1 (GP: alpha and Sigma_y^-1), as NumPy arrays.  mu(x) = k*' a and
+    var(x) = k** + jitter - k*' A k*; the device forms W = K*m A' (W_ij = sum_l k*_il A[j][l])."""
+    import torch
+
+    from .online import OnlineSVGP
+
+    if isinstance(model, OnlineSVGP):
+        if model._cur is None:
+            raise RuntimeError("the online model has seen no data yet")
+        model = model._cur
+    if not 0 <= int(latent) < model.n_latent:
+        raise ValueError(f"latent must lie in [0, {model.n_latent}) (got {latent})")
+    L = capi.lib()
+    h = model._ensure_handle(max(model._max_batch, 1))
+    dev, m = model._dev(), model.m
+    a = torch.empty(m, dtype=model.tdtype, device=dev)
+    A = torch.empty(m, m, dtype=model.tdtype, device=dev)
+    model._chk(L.agp_svgp_get_matrix(h, int(latent), capi.VEC_APRED, C.c_void_p(a.data_ptr()), 1, m))
+    model._chk(L.agp_svgp_get_matrix(h, int(latent), capi.MAT_APRED, C.c_void_p(A.data_ptr()), m, m))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    return a.cpu().numpy(), A.cpu().numpy()

@@ -43,6 +43,8 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int
 PW_OMEGA, PW_PHASE, PW_W, PW_V, PW_E = range(5)  # agp_pathwise_get
 PATHWISE_WS_BYTES = 64 * 1024 * 1024
 MAT_L, MAT_KINV, MAT_KNM, MAT_KAPPA, VEC_KTILDE, VEC_MEAN_F, VEC_VAR_F, VEC_THETA, VEC_C, VEC_GAMMA, VEC_ALPHA = range(11)
+VEC_APRED, MAT_APRED = 11, 12  # the predictor's a = K^-1 mu and A = K^-1 - K^-1 Sigma K^-1 (agp_svgp_get_matrix)
+ACQ_UCB, ACQ_EI, ACQ_PI = 0, 1, 2  # agp_acq_desc.kind
 
 
 class KernelDesc(C.Structure):
@@ -92,6 +94,9 @@ class PwAscentOpts(C.Structure):  # agp_pw_ascent_opts
         ("lr_host", C.POINTER(C.c_double)),
     ]
 
+
+class AcqDesc(C.Structure):  # agp_acq_desc
+    _fields_ = [("kind", C.c_int32), ("minimize", C.c_int32), ("beta", C.c_double), ("best", C.c_double), ("xi", C.c_double)]
 
 
 # every symbol include/agp_hip.h declares: name -> (restype, argtypes)
@@ -175,6 +180,10 @@ SYMBOLS = {
     "agp_svgp_predict_multi": (_I32, [_VP, _VP, _I32, _VP, _I64, _I64, _VP, _VP, _PDBL, _PDBL, _I32]),
     "agp_svgp_predict_f": (_I32, [_VP, _VP, _I64, _I64, _VP, _VP]),
     "agp_svgp_predict_f_grad": (_I32, [_VP, _VP, _I64, _I64, _VP, _VP, _I64]),
+    "agp_acq_moments": (_I32, [_VP, C.POINTER(AcqDesc), _I64, _VP, _VP, _VP, _VP, _VP]),
+    "agp_svgp_acquisition": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _VP, _VP, _I64]),
+    "agp_svgp_acq_maximize": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, C.POINTER(PwAscentOpts), _VP, _I64, _VP, _VP, _VP,
+                                     _VP]),
     "agp_svgp_predict_y": (_I32, [_VP, _VP, _I64, _I64, _VP]),
     "agp_svgp_proba_y": (_I32, [_VP, _VP, _I64, _I64, _PDBL, _PDBL, _I32, _VP, _VP]),
     "agp_nearest_center": (_I32, [_VP, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),

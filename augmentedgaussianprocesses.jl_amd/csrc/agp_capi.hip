@@ -25,6 +25,7 @@
 #include "agp_pathwise.h"
 #include "agp_lpd.h"
 #include "agp_predgrad.h"
+#include "agp_acq.h"
 // (the host layers after every kernel header, as they stood in this file: the order of the kernels in the code object is kept)
 #include "agp_ctx.h"
 #include "agp_chol_host.h"
@@ -34,6 +35,7 @@
 #include "agp_lpd_host.h"
 #include "agp_svgp_base.h"
 #include "agp_pathwise_host.h"
+#include "agp_acq_host.h"
 template <typename T>
 struct Svgp : SvgpBase {
   struct Latent {
@@ -3355,6 +3357,167 @@ struct Svgp : SvgpBase {
     return AGP_OK;
   }
 
+  // ---- acquisition functions (include/agp_hip.h, "ACQUISITION FUNCTIONS"; agp_acq.h, agp_acq_host.h) ----------
+  // Per chunk of 4096 points and pass: K*m (launch_kernelmatrix), W = K*m Apred' (gemm_nt), k_acq_contract, and one finishing kernel
+  // (k_acq_finish, or k_acq_step with the ADAM update): four launches, nothing waits for the stream.  One routine for every class, as
+  // predict_f_grad: it needs only what ensure_pred leaves.  The predictor's workspaces (Kstar, pg_W, pg_part) are shared with it.
+  AcqState acq;
+  agp_status acq_refused(const char* who, const char* why) {
+    ctx->err = std::string(who) + why;
+    return AGP_ERR_UNSUPPORTED;
+  }
+  agp_status acq_check_handle(const char* who) {
+    if (!std::is_same<T, double>::value) return acq_refused(who, "AGP_F32 handles are not supported (the acquisition functions are Float64)");
+    if (desc.lik.kind == AGP_LIK_MULTIOUTPUT || mo)
+      return acq_refused(who, "multi-output handles (MOSVGP, MOVGP) are not supported");
+    if (desc.flags & AGP_FLAG_SAMPLED)
+      return acq_refused(who, "Gibbs-sampled models (AGP_FLAG_SAMPLED) are not supported: they have no predict_f");
+    if (desc.latent_offset != 0 || mo_sharded || (lp.kind == AGP_LIK_LOGISTICSOFTMAX && desc.n_latent != desc.lik.n_class))
+      return acq_refused(who, "latent-sharded handles are not supported");
+    if (bs_world > 1) return acq_refused(who, "batch-sharded handles are not supported");
+    if (D > PG_MAXD) return acq_refused(who, "the input dimension D must be at most 64 (the hyper-gradient's limit)");
+    return AGP_OK;
+  }
+  // desc and latent, then the latent's kernel
+  agp_status acq_check_latent(const char* who, int l, const agp_acq_desc* d, AcqParams* p) {
+    AGPCHK(acq_check_desc(ctx, who, d, p));
+    if (l < 0 || l >= nl) {
+      ctx->err = std::string(who) + "latent must lie in [0, n_latent)";
+      return AGP_ERR_INVALID;
+    }
+    if (lat[l].k.kind == AGP_K_EXPONENTIAL) return acq_refused(who, "ExponentialKernel is not differentiable at zero distance");
+    return AGP_OK;
+  }
+  agp_status acq_prepare(Latent& g, bool ascent) {
+    AGPCHK(params_to_host(g));
+    AGPCHK(ensure_pred_ws(0, true));
+    if (!pg_part) AGPCHK(dmalloc(ctx, &pg_part, 2 * (int64_t)PG_MAXGROUPS * PG_CH * D));
+    if (!pg_W) AGPCHK(dmalloc(ctx, &pg_W, (int64_t)PG_CH * mp));
+    AGPCHK(acq.ensure_chunk(ctx, D, ascent));
+    AGPCHK(ensure_pred(g, true));
+    AGPCHK(ensure_zsc(g));
+    return AGP_OK;
+  }
+  // K*m, W and the contraction of nc <= 4096 points (rows of xs pitched by ldx) into pg_part / acq.sc: three launches
+  template <bool GRAD>
+  agp_status acq_pass(Latent& g, const T* xs, int64_t ldx, int64_t nc, int* ng) {
+    if constexpr (std::is_same<T, double>::value) {
+      (void)launch_kernelmatrix<T>(ctx, st(), xs, ldx, (const int64_t*)nullptr, nc, (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind,
+                                   kvar(g), Kstar, mp, rup64(nc), mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, (const T*)g.Zsc,
+                                   (const T*)g.zn);
+      LAUNCHCHK(ctx);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, Kstar, mp, g.Apred, mp, rup64(nc), mp, mp, 0, pg_W, mp, nullptr, 0, nullptr, nullptr, nullptr,
+                                    0)));
+      *ng = acq_contract_launch<GRAD>(st(), xs, ldx, nc, (const double*)g.Z, m, D, (const double*)g.scales, g.k.kind, (double)kvar(g),
+                                      (const double*)g.apred, (const double*)pg_W, mp, pg_part, acq.sc);
+      LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  }
+  agp_status acquisition(int l, const agp_acq_desc* d, const void* xt, int64_t ldx, int64_t nt, void* alpha_out, void* grad_out,
+                         int64_t ldg) override {
+    const char* who = "agp_svgp_acquisition: ";
+    AcqParams p;
+    AGPCHK(acq_check_handle(who));
+    AGPCHK(acq_check_latent(who, l, d, &p));
+    if (nt < 0 || ldx < D || (grad_out && ldg < D) || (nt > 0 && (!xt || !alpha_out))) {
+      ctx->err = std::string(who) + "n_t >= 0, xt and alpha_out must not be NULL, ldx >= D, ldg >= D when grad_out is given";
+      return AGP_ERR_INVALID;
+    }
+    if (nt == 0) return AGP_OK;
+    if constexpr (std::is_same<T, double>::value) {
+      Latent& g = lat[l];
+      AGPCHK(acq_prepare(g, false));
+      const double kdj = g.k.variance + jitter;
+      for (int64_t s = 0; s < nt; s += PG_CH) {
+        const int64_t nc = (nt - s) < PG_CH ? (nt - s) : PG_CH;
+        const double* xs = (const double*)xt + s * ldx;
+        int ng = 0;
+        if (grad_out) AGPCHK(acq_pass<true>(g, xs, ldx, nc, &ng));
+        else AGPCHK(acq_pass<false>(g, xs, ldx, nc, &ng));
+        hipLaunchKernelGGL(k_acq_finish, grid1(nc * (grad_out ? D : 1)), dim3(256), 0, st(), p, nc, (int)D, ng,
+                           (const double*)(grad_out ? pg_part : nullptr), (const double*)acq.sc, (const double*)g.scales, kdj,
+                           (double*)alpha_out + s, grad_out ? (double*)grad_out + s * ldg : (double*)nullptr, ldg);
+        LAUNCHCHK(ctx);
+      }
+    }
+    return AGP_OK;
+  }
+  agp_status acq_maximize(int l, const agp_acq_desc* d, const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o,
+                          void* x_out, int64_t ldxo, void* a_out, void* best_x, void* best_a, void* best_idx) override {
+#pragma clang fp contract(off)
+    const char* who = "agp_svgp_acq_maximize: ";
+    auto invalid = [&](const char* what) {
+      ctx->err = std::string(who) + what;
+      return AGP_ERR_INVALID;
+    };
+    AcqParams p;
+    PwAscentBox box;
+    AGPCHK(acq_check_handle(who));
+    AGPCHK(acq_check_latent(who, l, d, &p));
+    if (!x0) return invalid("x0 must be given");
+    AGPCHK(acq_check_opts(ctx, who, D, o, &box));
+    if (!x_out && !a_out && !best_x && !best_a && !best_idx) return invalid("at least one output must be given");
+    if (R < 1 || R >= ((int64_t)1 << 31)) return invalid("n_starts >= 1 and below 2^31");
+    if (ldx0 < D) return invalid("ldx0 >= D");
+    if (x_out && ldxo < D) return invalid("ldxo >= D when x_out is given");
+    if constexpr (std::is_same<T, double>::value) {
+      Latent& g = lat[l];
+      AGPCHK(acq_prepare(g, true));
+      AGPCHK(acq.ensure_particles(ctx, R, D));
+      const double kdj = g.k.variance + jitter;
+      for (int64_t s = 0; s < R; s += PG_CH) {  // chunk after chunk, each through all T steps
+        const int64_t nc = (R - s) < PG_CH ? (R - s) : PG_CH;
+        double* x = acq.X + s * D;
+        hipLaunchKernelGGL(k_acq_init, grid1(nc * D), dim3(256), 0, st(), nc, (int)D, (const double*)x0 + s * ldx0, ldx0, box, x, acq.mo,
+                           acq.vo);
+        LAUNCHCHK(ctx);
+        double b1k = 1.0, b2k = 1.0;
+        for (int k = 0; k <= o->steps; ++k) {
+          const int fin = k == o->steps;  // the pass after the last step: alpha at the final x
+          int ng = 0;
+          if (fin) AGPCHK(acq_pass<false>(g, x, D, nc, &ng));
+          else AGPCHK(acq_pass<true>(g, x, D, nc, &ng));
+          if (!fin) b1k *= o->beta1, b2k *= o->beta2;
+          hipLaunchKernelGGL(k_acq_step, grid1(nc * (fin ? 1 : D)), dim3(256), 0, st(), p, nc, (int)D, ng, (const double*)pg_part,
+                             (const double*)acq.sc, (const double*)g.scales, kdj, o->beta1, o->beta2, 1.0 - b1k, 1.0 - b2k, o->eps, box, fin,
+                             x, acq.mo, acq.vo, acq.A + s);
+          LAUNCHCHK(ctx);
+        }
+      }
+      if (best_x || best_a || best_idx) {
+        hipLaunchKernelGGL(k_pw_ascent_best, dim3(1), dim3(256), 0, st(), (const double*)acq.X, (const double*)acq.A, R, D, 1.0,
+                           (double*)best_x, D, (double*)best_a, (int64_t*)best_idx);
+        LAUNCHCHK(ctx);
+      }
+      if (x_out)
+        HIPCHK(ctx, hipMemcpy2DAsync(x_out, sizeof(double) * ldxo, acq.X, sizeof(double) * D, sizeof(double) * D, R,
+                                     hipMemcpyDeviceToDevice, st()));
+      if (a_out) HIPCHK(ctx, hipMemcpyAsync(a_out, acq.A, sizeof(double) * R, hipMemcpyDeviceToDevice, st()));
+    }
+    return AGP_OK;
+  }
+  // AGP_VEC_APRED / AGP_MAT_APRED of agp_svgp_get_matrix: the two objects of the predictor after ensure_pred, for every class
+  agp_status get_predictor(int l, int which, void* out, int64_t ldo, int64_t cap) override {
+    if (desc.flags & AGP_FLAG_SAMPLED) {
+      ctx->err = "agp_svgp_get_matrix: Gibbs-sampled models (AGP_FLAG_SAMPLED) have no predictor (AGP_VEC_APRED / AGP_MAT_APRED)";
+      return AGP_ERR_UNSUPPORTED;
+    }
+    const bool mat = which == AGP_MAT_APRED;
+    if (l < 0 || l >= nl || !out || cap < m || (mat && ldo < m)) {
+      ctx->err = "agp_svgp_get_matrix: AGP_VEC_APRED / AGP_MAT_APRED need latent in [0, n_latent), out given, cap >= m and ldo >= m";
+      return AGP_ERR_INVALID;
+    }
+    Latent& g = lat[l];
+    AGPCHK(ensure_pred_ws(0, mat));
+    AGPCHK(ensure_pred(g, mat));
+    if (mat)
+      HIPCHK(ctx, hipMemcpy2DAsync(out, sizeof(T) * ldo, g.Apred, sizeof(T) * mp, sizeof(T) * m, m, hipMemcpyDeviceToDevice, st()));
+    else
+      HIPCHK(ctx, hipMemcpyAsync(out, g.apred, sizeof(T) * m, hipMemcpyDeviceToDevice, st()));
+    return AGP_OK;
+  }
+
   // ---- pathwise sampling (include/agp_hip.h, "PATHWISE SAMPLING") -----------------------------------------------------------
   // the handles a draw is not built for, by name, before anything is touched
   agp_status pathwise_check_handle() {
@@ -5799,6 +5962,7 @@ agp_status agp_svgp_set_state(agp_svgp* h, int32_t latent, const void* eta1, con
 }
 agp_status agp_svgp_get_matrix(agp_svgp* h, int32_t latent, int32_t which, void* out, int64_t ldo, int64_t cap) {
   HCHKF(h);
+  if (which == AGP_VEC_APRED || which == AGP_MAT_APRED) return h->impl->get_predictor(latent, which, out, ldo, cap);  // every class
   if (h->impl->desc.flags & AGP_FLAG_EXACT) return exact_refused(h, "agp_svgp_get_matrix");
   if (which == AGP_MAT_KNM || which == AGP_MAT_KAPPA) FULLNO(h, "K_nm / kappa (kappa = I)");
   return h->impl->get_matrix(latent, which, out, ldo, cap);
@@ -5831,6 +5995,24 @@ agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int
                                    int64_t ldg) {
   HCHKF(h);
   return h->impl->predict_f_grad(xt, ldx, n_t, dmu_out, dvar_out, ldg);
+}
+// ---- acquisition functions ("ACQUISITION FUNCTIONS") ----------------------------------------------------------------------------
+agp_status agp_acq_moments(agp_ctx* ctx, const agp_acq_desc* desc, int64_t n, const void* mu, const void* var, void* alpha_out,
+                           void* dalpha_dmu, void* dalpha_dvar) {
+  if (!ctx) return AGP_ERR_INVALID;
+  DevGuard guard(ctx->device);
+  return acq_moments(ctx, desc, n, (const double*)mu, (const double*)var, (double*)alpha_out, (double*)dalpha_dmu, (double*)dalpha_dvar);
+}
+agp_status agp_svgp_acquisition(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xt, int64_t ldx, int64_t n_t,
+                                void* alpha_out, void* grad_out, int64_t ldg) {
+  HCHKF(h);
+  return h->impl->acquisition(latent, desc, xt, ldx, n_t, alpha_out, grad_out, ldg);
+}
+agp_status agp_svgp_acq_maximize(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* x0, int64_t ldx0, int64_t n_starts,
+                                 const agp_pw_ascent_opts* opts, void* x_out, int64_t ldxo, void* a_out, void* best_x, void* best_a,
+                                 void* best_idx) {
+  HCHKF(h);
+  return h->impl->acq_maximize(latent, desc, x0, ldx0, n_starts, opts, x_out, ldxo, a_out, best_x, best_a, best_idx);
 }
 agp_status agp_svgp_predict_y(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* y_out) {
   HCHKF(h);

@@ -189,6 +189,13 @@ struct SvgpBase {
   virtual agp_status predict_f(const void* xt, int64_t ldx, int64_t nt, void* mu, void* var) = 0;
   // input gradients of the predictive moments ("PREDICTIVE GRADIENTS"; Svgp<T>::predict_f_grad serves every class)
   virtual agp_status predict_f_grad(const void* xt, int64_t ldx, int64_t nt, void* dmu, void* dvar, int64_t ldg) = 0;
+  // acquisition functions of one latent and their multi-start ascent ("ACQUISITION FUNCTIONS"; Svgp<T> serves every class), and the
+  // predictor's two objects behind them (AGP_VEC_APRED / AGP_MAT_APRED of agp_svgp_get_matrix)
+  virtual agp_status acquisition(int l, const agp_acq_desc* d, const void* xt, int64_t ldx, int64_t nt, void* alpha, void* grad,
+                                 int64_t ldg) = 0;
+  virtual agp_status acq_maximize(int l, const agp_acq_desc* d, const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o,
+                                  void* x_out, int64_t ldxo, void* a_out, void* best_x, void* best_a, void* best_idx) = 0;
+  virtual agp_status get_predictor(int l, int which, void* out, int64_t ldo, int64_t cap) = 0;
   virtual agp_status predict_y(const void* xt, int64_t ldx, int64_t nt, void* out) = 0;
   virtual agp_status proba_y(const void* xt, int64_t ldx, int64_t nt, const double* nodes, const double* weights,
                              int nn, void* o0, void* o1) = 0;

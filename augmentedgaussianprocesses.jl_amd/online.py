@@ -151,6 +151,12 @@ class OnlineSVGP:
         n = self._m_real[latent]  # without the neutral padding
         return mu[:n], Sig[:n, :n], e1[:n], e2[:n, :n]
 
+    def predictor(self, latent: int = 0):
+        """(a, A) of the current model (SVGP.predictor), over all of its inducing points, the neutral padding included"""
+        if self._cur is None:
+            raise RuntimeError("the online model has seen no data yet")
+        return self._cur.predictor(latent)
+
     def _new_svgp(self, Zs, max_batch):
         m = SVGP(self.kernel if self._cur is None else self._cur.kernels, self.likelihood, AnalyticVI(), list(Zs),
                  optimiser=self.k_opt if self.k_opt else False, Zoptimiser=self.z_opt if self.z_opt else False, T=self.T,

@@ -687,6 +687,13 @@ class SVGP:
         self._chk(capi.lib().agp_ctx_sync(self._ctx))
         return out.cpu().numpy()
 
+    def predictor(self, latent: int = 0):
+        """(a, A): the predictor's a = K^-1 mu (m,) and A = K^-1 - K^-1 Sigma K^-1 (m, m) as they stand on the device
+        (AGP_VEC_APRED / AGP_MAT_APRED): predict_f is k*' a and k** + jitter - k*' A k*."""
+        from .acquisition import predictor
+
+        return predictor(self, latent)
+
     def __repr__(self):
         return f"Sparse Variational Gaussian Process with a {self.likelihood} infered by {self.inference} "
 

@@ -201,7 +201,13 @@ enum {
                        *     Multi-output handles (MOSVGP, MOVGP, after set_multioutput): the local variables belong to the task
                        *     likelihoods, so for AGP_VEC_THETA / AGP_VEC_C `latent` counts the tasks, 0 <= latent < n_task */
   AGP_VEC_GAMMA = 9,  /* B   LogisticSoftMax gamma_k ; Poisson gamma ; Heteroscedastic: latent 0 -> gamma, latent 1 -> sigg */
-  AGP_VEC_ALPHA = 10  /* B   LogisticSoftMax alpha (shared by all latents) */
+  AGP_VEC_ALPHA = 10, /* B   LogisticSoftMax alpha (shared by all latents) */
+  /* The two objects of the predictor ("PREDICTIVE GRADIENTS", "ACQUISITION FUNCTIONS"), as they stand after the predictor has been
+   * brought up to date; every class that predicts, AGP_FLAG_EXACT included (there a = alpha, A = Sigma_y^-1); cap >= m.  The
+   * predictor forms W = K*m A' with gemm_nt(Kstar, Apred): W_ij = sum_l k*_il Apred[j][l], rows of Apred as stored (A is symmetric
+   * up to rounding; this is the index order the variance and its gradient use). */
+  AGP_VEC_APRED = 11, /* m       a = K^-1 mu */
+  AGP_MAT_APRED = 12  /* m x m   A = K^-1 - K^-1 Sigma K^-1, ldo >= m */
 };
 
 typedef struct agp_ctx agp_ctx;
@@ -703,6 +709,69 @@ agp_status agp_svgp_predict_f_cov(agp_svgp* h, const void* xt, int64_t ldx, int6
  * (n_t > 0) a NULL xt or dmu_out: AGP_ERR_INVALID, outputs untouched. */
 agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* dmu_out,
                                    void* dvar_out /* nullable */, int64_t ldg);
+
+/* ---- ACQUISITION FUNCTIONS (UCB, EI, PI of the predictive moments, and their multi-start maximiser on the device) ------------------
+ * The other half of Bayesian optimisation next to "PATHWISE SAMPLING": no counterpart in the reference.  AGP_F64 only.  For one latent
+ * let mu(x), var(x) be exactly what agp_svgp_predict_f returns (k** + jitter included) and grad mu, grad var what
+ * agp_svgp_predict_f_grad returns.  s = +1, or -1 with `minimize` (the OBJECTIVE is then to be minimised; alpha itself is always
+ * maximised), sigma = sqrt(var), z = (s (mu - best) - xi) / sigma, Phi(z) = erfc(-z / sqrt 2) / 2 (never 1 + erf: the left tail is where
+ * EI lives), phi(z) = exp(-z^2 / 2) / sqrt(2 pi):
+ *   kind                          alpha                       d alpha / d mu      d alpha / d sigma
+ *   AGP_ACQ_UCB (beta >= 0)       s mu + beta sigma           s                   beta
+ *   AGP_ACQ_EI  (best, xi >= 0)   sigma (z Phi(z) + phi(z))   s Phi(z)            phi(z)
+ *   AGP_ACQ_PI  (best, xi >= 0)   Phi(z)                      s phi(z) / sigma    -z phi(z) / sigma
+ *   grad alpha = d alpha / d mu  grad mu  +  d alpha / d sigma  grad var / (2 sigma)
+ * EI is evaluated by this formula, not in logarithms: it underflows to 0, with a zero gradient, for z below about -38 (log-EI is out
+ * of scope).  var <= 0 takes the limit, it is not left to 0 / 0: UCB alpha = s mu; EI alpha = max(s (mu - best) - xi, 0) with
+ * d alpha / d mu = s where that is positive and 0 otherwise; PI alpha = 1 where s (mu - best) - xi > 0, else 0, with d alpha / d mu = 0;
+ * in all three the var term of the gradient is 0.  A NaN moment gives a NaN alpha (and NaN derivatives).
+ *
+ * agp_acq_moments  the point function alone on n given moments, device double[n] each: alpha_out, dalpha_dmu (nullable) and
+ *   dalpha_dvar (nullable) = d alpha / d sigma / (2 sigma).  n = 0 is a successful no-op.  AGP_ERR_INVALID with a message: ctx or desc
+ *   NULL, an unknown kind, beta < 0 or xi < 0, a non-finite beta / best / xi, n < 0, (n > 0) mu, var or alpha_out NULL.
+ * agp_svgp_acquisition  alpha_out[i] = alpha(x_i) of latent `latent` and (grad_out nullable) grad_out[i][d] at grad_out + i * ldg + d,
+ *   ldg >= D, ldx >= D; the "Layout" section holds (padding never read or written).  Streamed over any n_t in the predictor's chunks
+ *   of 4096; per chunk K*m (the predictor's kernel-matrix launch), W = K*m A' (the predictor's GEMM, W_ij = sum_l k*_il A[j][l]), then
+ *   ONE kernel that forms q by direct differences in ascending d, evaluates BOTH the base function and its derivative from that q and
+ *   accumulates sum_j a_j k_ij (mu), sum_j W_ij k_ij (k*' A k*), and the two contractions of agp_svgp_predict_f_grad over
+ *   inducing-point tiles staged through LDS, and a finishing kernel: var = (v + jitter) - k*' A k*, the table, the chain rule.  No
+ *   atomics, the order of every sum is fixed by (m, D): the same bits on a repeat, and wherever a point stands in a chunk of the same
+ *   length (gemm_nt may pick another kernel for a shorter last chunk: a point's W row may then move by rounding).  No side
+ *   effects: the contract is that of agp_svgp_predict_f_grad, paragraph "No side effects".  n_t = 0 is a successful no-op.
+ * agp_svgp_acq_maximize  multi-start ADAM ascent of alpha inside the box [lo, hi]: start r < n_starts begins at x0[r] (x0 + r * ldx0,
+ *   ldx0 >= D) clipped into the box and takes T = opts->steps steps with g = grad alpha(x).  The recurrences for m, v, mh, vh and x,
+ *   the running products b1 / b2, the clipping, "the FINAL iterate, evaluated once more", steps = 0 and the best-start rule (the
+ *   largest alpha, ties to the smallest index, a NaN never wins and start 0 does if every value is NaN) are word for word those of
+ *   agp_pathwise_maximize ("PATHWISE SAMPLING"), with one sample.  It takes the same agp_pw_ascent_opts; opts->minimize and
+ *   opts->x0_shared must be 0 (AGP_ERR_INVALID otherwise): the direction is agp_acq_desc.minimize.  lo, hi and lr are HOST arrays,
+ *   validated without a synchronisation and handed to the kernels by value.  Outputs, each nullable (not all): x_out[r][d] at x_out +
+ *   r * ldxo + d, a_out[r], best_x[d] (D values), best_a (one double), best_idx (one int64).  One step of a chunk of at most 4096
+ *   starts is four launches (K*m, W, the contraction, the ADAM update) on the handle's stream; starts beyond 4096 run chunk after
+ *   chunk, each through all T steps.  Asynchronous: no host synchronisation between steps.  The particle state (the iterates and
+ *   alpha of every start, the moments of one chunk) belongs to the handle; a call with more starts than any before re-allocates it
+ *   (the only place that may wait for the device).  Same bits on a repeat; a start has the same bits wherever it stands among up to
+ *   4096 starts (beyond, see the chunks of agp_svgp_acquisition).
+ *
+ * Both agp_svgp_* calls refuse with AGP_ERR_UNSUPPORTED, by name in agp_last_error, before any launch and with the outputs untouched:
+ * AGP_F32 handles; multi-output handles; AGP_FLAG_SAMPLED; latent-sharded and batch-sharded handles; D > 64; a latent with the
+ * ExponentialKernel ("ExponentialKernel is not differentiable at zero distance").  AGP_ERR_INVALID with a message: desc, opts or x0
+ * NULL; an unknown kind; beta < 0 or xi < 0; a non-finite beta / best / xi; latent outside [0, n_latent); n_t < 0, ldx < D, ldg < D
+ * with grad_out given, (n_t > 0) xt or alpha_out NULL; all five outputs NULL; n_starts < 1 or >= 2^31; ldx0 < D; ldxo < D with x_out
+ * given; steps outside [0, 65536]; beta1 or beta2 outside [0, 1); eps not finite and positive; lo_host, hi_host or lr_host NULL, a
+ * non-finite bound, lo > hi, a step size that is not finite and positive.
+ * Out of scope: log-EI, Float32, multi-output and sharded handles, batch (q-) acquisition, a single-launch ascent. */
+enum { AGP_ACQ_UCB = 0, AGP_ACQ_EI = 1, AGP_ACQ_PI = 2 };
+typedef struct {
+  int32_t kind;     /* AGP_ACQ_* */
+  int32_t minimize; /* 0: the objective is maximised, 1: minimised (s = -1) */
+  double beta;      /* UCB */
+  double best, xi;  /* EI, PI: the incumbent and the margin */
+} agp_acq_desc;
+agp_status agp_acq_moments(agp_ctx* ctx, const agp_acq_desc* desc, int64_t n, const void* mu, const void* var, void* alpha_out,
+                           void* dalpha_dmu /* nullable */, void* dalpha_dvar /* nullable */);
+agp_status agp_svgp_acquisition(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xt, int64_t ldx, int64_t n_t,
+                                void* alpha_out, void* grad_out /* nullable */, int64_t ldg);
+/* (agp_svgp_acq_maximize is declared under "PATHWISE SAMPLING", below the agp_pw_ascent_opts it takes) */
 /* predict_y  predictions.jl:178-198 : regression (Gaussian, StudentT, Laplace, Heteroscedastic) -> T[n_t] mean ;
  * logistic / BayesianSVM -> int32[n_t] (mu_f > 0) ; Poisson / NegBinomial -> T[n_t] expected count (predictions.jl:211) ;
  * LogisticSoftMax -> int32[n_t] argmax_k mu_f,k (0-based LOCAL latent index + latent_offset) */
@@ -1067,6 +1136,14 @@ agp_status agp_pathwise_maximize(agp_pathwise* p, int32_t latent, const void* x0
                                  void* best_x, int64_t ldb, /* nullable: [s][d], ldb >= D */
                                  void* best_f,              /* nullable: [s] */
                                  void* best_idx);           /* nullable: int64 [s] */
+/* "ACQUISITION FUNCTIONS": the same ascent on an acquisition function of the handle's predictive moments */
+agp_status agp_svgp_acq_maximize(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* x0, int64_t ldx0, int64_t n_starts,
+                                 const agp_pw_ascent_opts* opts,
+                                 void* x_out, int64_t ldxo, /* nullable: [r][d], ldxo >= D */
+                                 void* a_out,               /* nullable: [r] */
+                                 void* best_x,              /* nullable: [d], D values */
+                                 void* best_a,              /* nullable: one double */
+                                 void* best_idx);           /* nullable: one int64 */
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D);
 agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void* out, int64_t ld);
 agp_status agp_pathwise_destroy(agp_pathwise* p);

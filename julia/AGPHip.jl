@@ -27,6 +27,7 @@
 #   log_predictive_density(model, X, y) (no counterpart: the held-out log-likelihood / NLPD)           -> agp_svgp_lpd_stream, agp_log_predictive
 #   _predict_f / predict_y / proba_y                          src/training/predictions.jl:25-92,178-247 -> agp_svgp_predict_f / _predict_y / _proba_y
 #   predict_f_grad(model, X_test) (no counterpart: d mu / d x*, d sigma^2 / d x* of predict_f)          -> agp_svgp_predict_f_grad
+#   acquisition / maximize_acquisition(model, UCB | EI | PI, ...) (no counterpart: Bayesian optimisation) -> agp_svgp_acquisition, agp_svgp_acq_maximize
 #   init_state                                                src/training/states.jl:1-9               -> agp_svgp_init_state
 # Multi-GPU (one Julia process per GPU, e.g. under MPI.jl or Distributed): agp_comm_* binds RCCL inside the library; the host only
 # ships the 128-byte id from rank 0 to the others (section "multi-GPU" below).
@@ -1526,5 +1527,74 @@ function pathwise_features(hm::HipModel, k::Kernel, D::Integer, n_features::Inte
                                        ctx, kd, D, n_features, UInt64(seed), t, latent - 1, pointer(om), pointer(ph)))
     return permutedims(Array(om)), Array(ph)
 end
+
+# ---- acquisition functions (include/agp_hip.h, "ACQUISITION FUNCTIONS"; no counterpart in the reference) ------------------------------
+# UCB(beta), EI(best, xi), PI(best, xi) of the moments of predict_f, Float64 single-output models; minimize=true: the objective is
+# minimised (the acquisition value itself is always maximised).  The struct mirrors agp_acq_desc field by field.
+# Never run: there is no Julia toolchain in the test environment.
+struct AcqDesc
+    kind::Int32
+    minimize::Int32
+    beta::Float64
+    best::Float64
+    xi::Float64
+end
+UCB(beta::Real=2.0; minimize::Bool=false) = AcqDesc(0, minimize ? 1 : 0, beta, 0.0, 0.0)
+EI(best::Real, xi::Real=0.0; minimize::Bool=false) = AcqDesc(1, minimize ? 1 : 0, 0.0, best, xi)
+PI(best::Real, xi::Real=0.0; minimize::Bool=false) = AcqDesc(2, minimize ? 1 : 0, 0.0, best, xi)
+# acquisition(hm, acq, X; grad=false, latent=1): alpha at the rows of X (n_t), with grad=true (alpha, G n_t x D)
+function acquisition(hm::HipModel{Float64}, acq::AcqDesc, X::AbstractMatrix; grad::Bool=false, latent::Integer=1, obsdim::Int=1)
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    Xd = ROCArray{Float64}(obsdim == 1 ? permutedims(X) : X)
+    D, nt = size(Xd)
+    a = ROCArray{Float64}(undef, nt)
+    G = grad ? ROCArray{Float64}(undef, D, nt) : nothing     # column-major D x n_t == the ABI's [n_t][ldg = D]
+    check(hm.ctx, ccall((:agp_svgp_acquisition, libagp), Int32,
+                        (Ptr{Cvoid}, Int32, Ref{AcqDesc}, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+                        hm.h, latent - 1, Ref(acq), pointer(Xd), D, nt, pointer(a), grad ? pointer(G) : C_NULL, D))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    return grad ? (Array(a), permutedims(Array(G))) : Array(a)
+end
+# acquisition_moments(hm, acq, mu, var): the point function alone, (alpha, d alpha / d mu, d alpha / d var)
+function acquisition_moments(hm::HipModel, acq::AcqDesc, mu::AbstractVector, var::AbstractVector)
+    ctx = ensure_ctx!(hm)
+    n = length(mu)
+    md, vd = ROCArray{Float64}(mu), ROCArray{Float64}(var)
+    a, dm, dv = (ROCArray{Float64}(undef, n) for _ in 1:3)
+    check(ctx, ccall((:agp_acq_moments, libagp), Int32,
+                     (Ptr{Cvoid}, Ref{AcqDesc}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx, Ref(acq), n, pointer(md), pointer(vd), pointer(a), pointer(dm), pointer(dv)))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), ctx)
+    return Array(a), Array(dm), Array(dv)
+end
+# maximize_acquisition(hm, acq, X0, lo, hi; steps=100, lr=nothing, ...): multi-start ADAM ascent on the device (agp_svgp_acq_maximize).
+# X0 is R x D; lo, hi and lr as in pathwise_maximize.  Returns (x_best (D), a_best); full=true (x_best, a_best, idx (1-based), X R x D,
+# A (R)).
+function maximize_acquisition(hm::HipModel{Float64}, acq::AcqDesc, X0::AbstractMatrix, lo, hi; steps::Integer=100, lr=nothing,
+                              beta1::Real=0.9, beta2::Real=0.999, eps::Real=1e-8, latent::Integer=1, full::Bool=false)
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    R, D = size(X0)
+    vec_of(v) = v isa Number ? fill(Float64(v), D) : collect(Float64, v)
+    lov, hiv = vec_of(lo), vec_of(hi)
+    lrv = lr === nothing ? map(w -> w == 0 ? 1.0 : 0.02 * w, hiv .- lov) : vec_of(lr)
+    (length(lov) == D && length(hiv) == D && length(lrv) == D) || error("maximize_acquisition: lo, hi and lr must be scalars or of length $D")
+    Xd = ROCArray{Float64}(permutedims(X0))                  # column-major D x R == [r][d]
+    X, A = ROCArray{Float64}(undef, D, R), ROCArray{Float64}(undef, R)
+    xb, ab, ib = ROCArray{Float64}(undef, D), ROCArray{Float64}(undef, 1), ROCArray{Int64}(undef, 1)
+    GC.@preserve lov hiv lrv begin
+        opts = Ref(PwAscentOpts(steps, 0, 0, beta1, beta2, eps, pointer(lov), pointer(hiv), pointer(lrv)))
+        check(hm.ctx, ccall((:agp_svgp_acq_maximize, libagp), Int32,
+                            (Ptr{Cvoid}, Int32, Ref{AcqDesc}, Ptr{Cvoid}, Int64, Int64, Ref{PwAscentOpts}, Ptr{Cvoid}, Int64, Ptr{Cvoid},
+                             Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                            hm.h, latent - 1, Ref(acq), pointer(Xd), D, R, opts, full ? pointer(X) : C_NULL, D, full ? pointer(A) : C_NULL,
+                            pointer(xb), pointer(ab), pointer(ib)))
+    end
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    x_best, a_best = Array(xb), Array(ab)[1]
+    full || return x_best, a_best
+    return x_best, a_best, Array(ib)[1] + 1, permutedims(Array(X)), Array(A)
+end
+acquisition(ho::HipOnlineModel, acq::AcqDesc, X::AbstractMatrix; kw...) = acquisition(ho.cur, acq, X; kw...)
+maximize_acquisition(ho::HipOnlineModel, acq::AcqDesc, X0::AbstractMatrix, lo, hi; kw...) = maximize_acquisition(ho.cur, acq, X0, lo, hi; kw...)
 
 end # module
