@@ -4,11 +4,15 @@ FUNCTIONS"): the other half of Bayesian optimisation next 
     a = AGP.acquisition(model, AGP.EI(best=y.max()), X)                      # (n_t,); grad=True gives (a, G (n_t, D))
     x, a = AGP.maximize_acquisition(model, AGP.UCB(2.0), X0, (lo, hi))       # the best of R ADAM ascents, on the device
     a, dmu, dvar = AGP.acquisition_moments(AGP.PI(best=0.0), mu, var, grad=True)
+    Xq, aq = AGP.maximize_acquisition_batch(model, AGP.UCB(2.0), 8, X0, (lo, hi), pending=P)   # q points, greedily, on the device
+    a = AGP.acquisition(model, AGP.EI(best=y.max()), X, pending=P)           # alpha with P hallucinated at its predicted mean
 
 UCB = s mu + beta sigma, EI = sigma (z Phi(z) + phi(z)), PI = Phi(z) with z = (s (mu - best) - xi) / sigma; s = -1 with minimize=True
 (the objective is minimised; the acquisition function itself is always maximised).  Float64, single-output models, D <= 64,
-SqExponential / Matern32 / Matern52 kernels.  Not here: log-EI (EI underflows to 0 for z below about -38), Float32, multi-output and
-sharded models, batch (q-) acquisition.  No counterpart in the reference.
+SqExponential / Matern32 / Matern52 kernels.  Batches come from hallucinated observations (GP-BUCB, "kriging believer"): pending
+points are conditioned on at their own predicted mean -- the mean stays, the variance shrinks -- and q points are picked greedily.
+Not here: MC q-EI with a joint reparameterised sample, fantasies that move the mean, log-EI (EI underflows to 0 for z below about
+-38), Float32, multi-output and sharded models.  No counterpart in the reference.
 """
 from __future__ import annotations
 
@@ -138,16 +142,36 @@ def _incumbent(model, latent: int, minimize: bool) -> float:
     return float(mu[latent].min() if minimize else mu[latent].max())
 
 
-def acquisition(model, acq, X, *, grad: bool = False, latent: int = 0, minimize: bool = False, obsdim: int = 1):
+def _check_pending(who: str, pending, pending_noise, D: int, q: int):
+    """(n_pending, tau2): the argument checks of the pending points, on the host; pending is None or (n, D)"""
+    if not (isinstance(pending_noise, (int, float, np.floating, np.integer)) and math.isfinite(pending_noise) and pending_noise >= 0.0):
+        raise ValueError(f"{who}: pending_noise must be finite and >= 0 (got {pending_noise})")
+    n = 0
+    if pending is not None:
+        shape = tuple(pending.shape) if hasattr(pending, "shape") else np.shape(pending)
+        if len(shape) != 2 or shape[1] != D:
+            raise ValueError(f"{who}: pending must be (n, {D}) (got {tuple(shape)})")
+        n = int(shape[0])
+    if n + q > capi.ACQ_MAX_PENDING:
+        raise ValueError(f"{who}: the pending points and the batch together must not exceed {capi.ACQ_MAX_PENDING} (got {n} + {q})")
+    return n, float(pending_noise)
+
+
+def acquisition(model, acq, X, *, grad: bool = False, latent: int = 0, minimize: bool = False, obsdim: int = 1, pending=None,
+                pending_noise: float = 0.0):
     """alpha(x_i) of one latent at the rows of X: (n_t,), and with grad=True (alpha, G) with G[i, d] = d alpha / d x_id, (n_t, D).
     Streamed in chunks of 4096 points, deterministic, the model's state is left as it was (agp_svgp_acquisition).  NumPy in gives
     NumPy out; a torch tensor on the device gives device tensors.  SVGP (AnalyticVI / SVI, QuadratureVI, MCIntegrationVI), VGP, GP,
-    OnlineSVGP in Float64; everything else raises NotImplementedError before the device is touched."""
+    OnlineSVGP in Float64; everything else raises NotImplementedError before the device is touched.
+    pending=(n, D): the points that are being evaluated already.  The posterior is conditioned on them at their own predicted mean
+    with the noise variance pending_noise: mu stays, var shrinks (agp_svgp_acquisition_pending).  pending=None is the call above."""
     if not isinstance(grad, bool):
         raise TypeError("acquisition: grad is a bool")
     if obsdim not in (1, 2):
         raise ValueError("acquisition: obsdim is 1 (points are rows) or 2 (points are columns)")
     model, d = _resolve(model, acq, latent, minimize)
+    if pending is not None:
+        return _acquisition_pending(model, d, X, grad, int(latent), obsdim, pending, pending_noise)
     import torch
 
     on_device = isinstance(X, torch.Tensor) and X.is_cuda
@@ -161,6 +185,30 @@ def acquisition(model, acq, X, *, grad: bool = False, latent: int = 0, minimize:
     model._chk(L.agp_svgp_acquisition(h, int(latent), C.byref(d), C.c_void_p(Xd.data_ptr()), Xd.stride(0) if nt else D, nt,
                                       C.c_void_p(a.data_ptr()), C.c_void_p(G.data_ptr()) if grad else None, D))
     model._chk(L.agp_ctx_sync(model._ctx))
+    out = (a, G) if grad else (a,)
+    if not on_device:
+        out = tuple(t.cpu().numpy() for t in out)
+    return out if grad else out[0]
+
+
+def _acquisition_pending(model, d, X, grad, latent, obsdim, pending, pending_noise):
+    n, tau2 = _check_pending("acquisition", pending, pending_noise, model.D, 1)
+    import torch
+
+    on_device = isinstance(X, torch.Tensor) and X.is_cuda
+    L = capi.lib()
+    Xd = model._upload(X, obsdim)
+    nt, D = Xd.shape
+    dev = model._dev()
+    Pd = torch.as_tensor(pending, dtype=torch.float64).to(dev).reshape(n, D).contiguous()
+    h = model._ensure_handle(max(model._max_batch, 1))
+    a = torch.empty(nt, dtype=torch.float64, device=dev)
+    G = torch.empty(nt, D, dtype=torch.float64, device=dev) if grad else None
+    model._chk(L.agp_svgp_acquisition_pending(h, latent, C.byref(d), C.c_void_p(Pd.data_ptr()) if n else None, D, n, tau2,
+                                              C.c_void_p(Xd.data_ptr()), Xd.stride(0) if nt else D, nt, C.c_void_p(a.data_ptr()),
+                                              C.c_void_p(G.data_ptr()) if grad else None, D))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    model._chk(L.agp_svgp_check_status(h))
     out = (a, G) if grad else (a,)
     if not on_device:
         out = tuple(t.cpu().numpy() for t in out)
@@ -239,6 +287,49 @@ def maximize_acquisition(model, acq, X0, bounds, *, steps: int = 100, lr=None, b
                                        ptr(A) if full else None, ptr(xb), ptr(ab), ptr(ib)))
     model._chk(L.agp_ctx_sync(model._ctx))
     out = (xb, ab, ib, X, A) if full else (xb, ab)
+    return out if on_device else tuple(t.cpu().numpy() for t in out)
+
+
+def maximize_acquisition_batch(model, acq, q, X0, bounds, *, pending=None, pending_noise: float = 0.0, steps: int = 100, lr=None,
+                               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, latent: int = 0, minimize: bool = False,
+                               full: bool = False):
+    """q points for parallel evaluation, picked greedily on the device (agp_svgp_acq_maximize_batch): round b runs the multi-start
+    ascent of maximize_acquisition -- the same X0, bounds, steps and best-start rule -- on the acquisition function conditioned on
+    `pending` (None or (n, D)) and on the winners of the rounds before, each hallucinated at its own predicted mean with the noise
+    variance pending_noise (GP-BUCB / "kriging believer": the mean stays, the variance shrinks, so the next round looks elsewhere).
+    n + q <= 64.  Returned is (X_batch (q, D), a_batch (q,)) with a_batch[b] the conditioned acquisition value at X_batch[b], and
+    with full=True also idx (q,), the index of each round's winning start.  All rounds are enqueued without a host synchronisation.
+    best=None, NumPy or torch inputs and the refused model classes follow maximize_acquisition; every argument is checked on the
+    host first."""
+    model, d = _resolve(model, acq, latent, minimize)
+    if not isinstance(q, (int, np.integer)) or isinstance(q, bool) or q < 1:
+        raise ValueError(f"maximize_acquisition_batch: q must be an integer >= 1 (got {q})")
+    q = int(q)
+    shape = tuple(X0.shape) if hasattr(X0, "shape") else np.shape(X0)
+    if len(shape) != 2 or shape[1] != model.D:
+        raise ValueError(f"X0 must be (R, {model.D}) (got {tuple(shape)})")
+    lo, hi, lrv, _, R = check_maximize_args(1, model.D, model.n_latent, shape, bounds, steps, lr, beta1, beta2, eps, latent)
+    n, tau2 = _check_pending("maximize_acquisition_batch", pending, pending_noise, model.D, q)
+    import torch
+
+    on_device = isinstance(X0, torch.Tensor) and X0.is_cuda
+    dev = model._dev()
+    D = model.D
+    Xd = torch.as_tensor(X0, dtype=torch.float64).to(dev).reshape(R, D).contiguous()
+    Pd = torch.as_tensor(pending, dtype=torch.float64).to(dev).reshape(n, D).contiguous() if n else None
+    h = model._ensure_handle(max(model._max_batch, 1))
+    xb = torch.empty(q, D, dtype=torch.float64, device=dev)
+    ab = torch.empty(q, dtype=torch.float64, device=dev)
+    ib = torch.empty(q, dtype=torch.int64, device=dev)
+    as_p = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    opts = capi.PwAscentOpts(int(steps), 0, 0, float(beta1), float(beta2), float(eps), as_p(lo), as_p(hi), as_p(lrv))
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    L = capi.lib()
+    model._chk(L.agp_svgp_acq_maximize_batch(h, int(latent), C.byref(d), ptr(Pd) if n else None, D, n, tau2, q, ptr(Xd), D, R,
+                                             C.byref(opts), ptr(xb), D, ptr(ab), ptr(ib)))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    model._chk(L.agp_svgp_check_status(h))
+    out = (xb, ab, ib) if full else (xb, ab)
     return out if on_device else tuple(t.cpu().numpy() for t in out)
 
 

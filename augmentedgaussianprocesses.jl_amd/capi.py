@@ -45,6 +45,7 @@ PATHWISE_WS_BYTES = 64 * 1024 * 1024
 MAT_L, MAT_KINV, MAT_KNM, MAT_KAPPA, VEC_KTILDE, VEC_MEAN_F, VEC_VAR_F, VEC_THETA, VEC_C, VEC_GAMMA, VEC_ALPHA = range(11)
 VEC_APRED, MAT_APRED = 11, 12  # the predictor's a = K^-1 mu and A = K^-1 - K^-1 Sigma K^-1 (agp_svgp_get_matrix)
 ACQ_UCB, ACQ_EI, ACQ_PI = 0, 1, 2  # agp_acq_desc.kind
+ACQ_MAX_PENDING = 64  # AGP_ACQ_MAX_PENDING: n_pending + q
 
 
 class KernelDesc(C.Structure):
@@ -184,6 +185,9 @@ SYMBOLS = {
     "agp_svgp_acquisition": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _VP, _VP, _I64]),
     "agp_svgp_acq_maximize": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, C.POINTER(PwAscentOpts), _VP, _I64, _VP, _VP, _VP,
                                      _VP]),
+    "agp_svgp_acquisition_pending": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _DBL, _VP, _I64, _I64, _VP, _VP, _I64]),
+    "agp_svgp_acq_maximize_batch": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _DBL, _I64, _VP, _I64, _I64,
+                                           C.POINTER(PwAscentOpts), _VP, _I64, _VP, _VP]),
     "agp_svgp_predict_y": (_I32, [_VP, _VP, _I64, _I64, _VP]),
     "agp_svgp_proba_y": (_I32, [_VP, _VP, _I64, _I64, _PDBL, _PDBL, _I32, _VP, _VP]),
     "agp_nearest_center": (_I32, [_VP, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),

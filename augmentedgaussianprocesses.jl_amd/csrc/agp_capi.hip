@@ -26,6 +26,7 @@
 #include "agp_lpd.h"
 #include "agp_predgrad.h"
 #include "agp_acq.h"
+#include "agp_acq_batch.h"
 // (the host layers after every kernel header, as they stood in this file: the order of the kernels in the code object is kept)
 #include "agp_ctx.h"
 #include "agp_chol_host.h"
@@ -2530,7 +2531,10 @@ struct Svgp : SvgpBase {
   agp_status check_status() override {
     int32_t words[4] = {0, 0, 0, 0};  // info | infoK | flags | orderK (k_logdiag_sum: did K_ZZ fail before or after the others?)
     HIPCHK(ctx, hipMemcpyAsync(words, info_dev, sizeof(words), hipMemcpyDeviceToHost, st()));
+    int32_t acq_bad = 0;  // a bordering pivot of the pending points that was not positive and finite (agp_acq_batch.h)
+    if (acqb.bad) HIPCHK(ctx, hipMemcpyAsync(&acq_bad, acqb.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
     HIPCHK(ctx, hipStreamSynchronize(st()));
+    if (acq_bad != 0) HIPCHK(ctx, hipMemsetAsync(acqb.bad, 0, sizeof(int32_t), st()));
     const int32_t info = words[0], infoK = words[1], orderK = words[3];
     const int flags = (int)words[2];
     dag_retry_check(ctx);  // steps the in-stream fallback had to re-run: warn once, stop using the task graph
@@ -2597,6 +2601,11 @@ struct Svgp : SvgpBase {
     if (infoK < 0) {
       ctx->err = "task-graph factorisation of K_ZZ aborted: a tile dependency never arrived (spin limit)";
       return AGP_ERR_HIP;
+    }
+    if (acq_bad != 0) {  // (last: whatever stands above made the predictor it was computed from)
+      ctx->err = "PosDefException: the covariance of the pending points (agp_svgp_acquisition_pending, agp_svgp_acq_maximize_batch) is "
+                 "not positive definite: a bordering pivot c was not positive and finite";
+      return AGP_ERR_NOT_POSDEF;
     }
     return AGP_OK;
   }
@@ -3398,19 +3407,77 @@ struct Svgp : SvgpBase {
     AGPCHK(ensure_zsc(g));
     return AGP_OK;
   }
-  // K*m, W and the contraction of nc <= 4096 points (rows of xs pitched by ldx) into pg_part / acq.sc: three launches
+  // K*m, W and the contraction of nc <= 4096 points (rows of xs pitched by ldx) into pg_part / acq.sc: three launches, on the
+  // predictor pr (the latent's own objects, or the augmented ones of the pending points)
+  AcqPred acq_latent_pred(Latent& g) {
+    return AcqPred{(const double*)g.Z, (const double*)g.Zsc, (const double*)g.zn, (const double*)g.apred, (const double*)g.Apred, m, mp, mp,
+                   (double*)Kstar, (double*)pg_W, nullptr, nullptr, nullptr, nullptr};
+  }
   template <bool GRAD>
-  agp_status acq_pass(Latent& g, const T* xs, int64_t ldx, int64_t nc, int* ng) {
+  agp_status acq_pass(Latent& g, const AcqPred& pr, const T* xs, int64_t ldx, int64_t nc, int* ng) {
     if constexpr (std::is_same<T, double>::value) {
-      (void)launch_kernelmatrix<T>(ctx, st(), xs, ldx, (const int64_t*)nullptr, nc, (const T*)g.Z, D, m, D, (const T*)g.scales, g.k.kind,
-                                   kvar(g), Kstar, mp, rup64(nc), mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, (const T*)g.Zsc,
-                                   (const T*)g.zn);
+      (void)launch_kernelmatrix<T>(ctx, st(), xs, ldx, (const int64_t*)nullptr, nc, pr.Z, D, pr.m, D, (const T*)g.scales, g.k.kind,
+                                   kvar(g), pr.Kstar, pr.ld, rup64(nc), pr.mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, pr.Zsc,
+                                   pr.zn);
       LAUNCHCHK(ctx);
-      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, Kstar, mp, g.Apred, mp, rup64(nc), mp, mp, 0, pg_W, mp, nullptr, 0, nullptr, nullptr, nullptr,
-                                    0)));
-      *ng = acq_contract_launch<GRAD>(st(), xs, ldx, nc, (const double*)g.Z, m, D, (const double*)g.scales, g.k.kind, (double)kvar(g),
-                                      (const double*)g.apred, (const double*)pg_W, mp, pg_part, acq.sc);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, pr.Kstar, pr.ld, pr.A, pr.ld, rup64(nc), pr.mp, pr.mp, 0, pr.U ? pr.W0 : pr.W, pr.ld, nullptr, 0,
+                                    nullptr, nullptr, nullptr, 0)));
+      if (pr.U) {  // the rank-one terms of the pending points: G = K*m' U^T, W = W0 - G N^T
+        AGPCHK((gemm_nt<T, EPI_STORE>(ctx, pr.Kstar, pr.ld, pr.U, pr.ld, rup64(nc), ACQB_MAXPEND, pr.mp, 0, pr.G, ACQB_MAXPEND, nullptr, 0,
+                                      nullptr, nullptr, nullptr, 0)));
+        AGPCHK((gemm_nt<T, EPI_EMINUS>(ctx, pr.G, ACQB_MAXPEND, pr.N, ACQB_MAXPEND, rup64(nc), pr.mp, ACQB_MAXPEND, 0, pr.W, pr.ld, pr.W0,
+                                       pr.ld, nullptr, nullptr, nullptr, 0)));
+      }
+      *ng = acq_contract_launch<GRAD>(st(), xs, ldx, nc, pr.Z, pr.m, D, (const double*)g.scales, g.k.kind, (double)kvar(g), pr.a,
+                                      (const double*)pr.W, pr.ld, pg_part, acq.sc);
       LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  }
+  // alpha (and grad, nullable) at nt points in chunks of 4096: four launches per chunk
+  agp_status acq_eval(Latent& g, const AcqPred& pr, const AcqParams& p, const void* xt, int64_t ldx, int64_t nt, void* alpha_out,
+                      void* grad_out, int64_t ldg) {
+    if constexpr (std::is_same<T, double>::value) {
+      const double kdj = g.k.variance + jitter;
+      for (int64_t s = 0; s < nt; s += PG_CH) {
+        const int64_t nc = (nt - s) < PG_CH ? (nt - s) : PG_CH;
+        const double* xs = (const double*)xt + s * ldx;
+        int ng = 0;
+        if (grad_out) AGPCHK(acq_pass<true>(g, pr, xs, ldx, nc, &ng));
+        else AGPCHK(acq_pass<false>(g, pr, xs, ldx, nc, &ng));
+        hipLaunchKernelGGL(k_acq_finish, grid1(nc * (grad_out ? D : 1)), dim3(256), 0, st(), p, nc, (int)D, ng,
+                           (const double*)(grad_out ? pg_part : nullptr), (const double*)acq.sc, (const double*)g.scales, kdj,
+                           (double*)alpha_out + s, grad_out ? (double*)grad_out + s * ldg : (double*)nullptr, ldg);
+        LAUNCHCHK(ctx);
+      }
+    }
+    return AGP_OK;
+  }
+  // the ascent of R starts into acq.X / acq.A: chunk after chunk, each through all T steps
+  agp_status acq_ascend(Latent& g, const AcqPred& pr, const AcqParams& p, const PwAscentBox& box, const agp_pw_ascent_opts* o,
+                        const void* x0, int64_t ldx0, int64_t R) {
+#pragma clang fp contract(off)
+    if constexpr (std::is_same<T, double>::value) {
+      const double kdj = g.k.variance + jitter;
+      for (int64_t s = 0; s < R; s += PG_CH) {
+        const int64_t nc = (R - s) < PG_CH ? (R - s) : PG_CH;
+        double* x = acq.X + s * D;
+        hipLaunchKernelGGL(k_acq_init, grid1(nc * D), dim3(256), 0, st(), nc, (int)D, (const double*)x0 + s * ldx0, ldx0, box, x, acq.mo,
+                           acq.vo);
+        LAUNCHCHK(ctx);
+        double b1k = 1.0, b2k = 1.0;
+        for (int k = 0; k <= o->steps; ++k) {
+          const int fin = k == o->steps;  // the pass after the last step: alpha at the final x
+          int ng = 0;
+          if (fin) AGPCHK(acq_pass<false>(g, pr, x, D, nc, &ng));
+          else AGPCHK(acq_pass<true>(g, pr, x, D, nc, &ng));
+          if (!fin) b1k *= o->beta1, b2k *= o->beta2;
+          hipLaunchKernelGGL(k_acq_step, grid1(nc * (fin ? 1 : D)), dim3(256), 0, st(), p, nc, (int)D, ng, (const double*)pg_part,
+                             (const double*)acq.sc, (const double*)g.scales, kdj, o->beta1, o->beta2, 1.0 - b1k, 1.0 - b2k, o->eps, box, fin,
+                             x, acq.mo, acq.vo, acq.A + s);
+          LAUNCHCHK(ctx);
+        }
+      }
     }
     return AGP_OK;
   }
@@ -3428,24 +3495,12 @@ struct Svgp : SvgpBase {
     if constexpr (std::is_same<T, double>::value) {
       Latent& g = lat[l];
       AGPCHK(acq_prepare(g, false));
-      const double kdj = g.k.variance + jitter;
-      for (int64_t s = 0; s < nt; s += PG_CH) {
-        const int64_t nc = (nt - s) < PG_CH ? (nt - s) : PG_CH;
-        const double* xs = (const double*)xt + s * ldx;
-        int ng = 0;
-        if (grad_out) AGPCHK(acq_pass<true>(g, xs, ldx, nc, &ng));
-        else AGPCHK(acq_pass<false>(g, xs, ldx, nc, &ng));
-        hipLaunchKernelGGL(k_acq_finish, grid1(nc * (grad_out ? D : 1)), dim3(256), 0, st(), p, nc, (int)D, ng,
-                           (const double*)(grad_out ? pg_part : nullptr), (const double*)acq.sc, (const double*)g.scales, kdj,
-                           (double*)alpha_out + s, grad_out ? (double*)grad_out + s * ldg : (double*)nullptr, ldg);
-        LAUNCHCHK(ctx);
-      }
+      AGPCHK(acq_eval(g, acq_latent_pred(g), p, xt, ldx, nt, alpha_out, grad_out, ldg));
     }
     return AGP_OK;
   }
   agp_status acq_maximize(int l, const agp_acq_desc* d, const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o,
                           void* x_out, int64_t ldxo, void* a_out, void* best_x, void* best_a, void* best_idx) override {
-#pragma clang fp contract(off)
     const char* who = "agp_svgp_acq_maximize: ";
     auto invalid = [&](const char* what) {
       ctx->err = std::string(who) + what;
@@ -3465,26 +3520,7 @@ struct Svgp : SvgpBase {
       Latent& g = lat[l];
       AGPCHK(acq_prepare(g, true));
       AGPCHK(acq.ensure_particles(ctx, R, D));
-      const double kdj = g.k.variance + jitter;
-      for (int64_t s = 0; s < R; s += PG_CH) {  // chunk after chunk, each through all T steps
-        const int64_t nc = (R - s) < PG_CH ? (R - s) : PG_CH;
-        double* x = acq.X + s * D;
-        hipLaunchKernelGGL(k_acq_init, grid1(nc * D), dim3(256), 0, st(), nc, (int)D, (const double*)x0 + s * ldx0, ldx0, box, x, acq.mo,
-                           acq.vo);
-        LAUNCHCHK(ctx);
-        double b1k = 1.0, b2k = 1.0;
-        for (int k = 0; k <= o->steps; ++k) {
-          const int fin = k == o->steps;  // the pass after the last step: alpha at the final x
-          int ng = 0;
-          if (fin) AGPCHK(acq_pass<false>(g, x, D, nc, &ng));
-          else AGPCHK(acq_pass<true>(g, x, D, nc, &ng));
-          if (!fin) b1k *= o->beta1, b2k *= o->beta2;
-          hipLaunchKernelGGL(k_acq_step, grid1(nc * (fin ? 1 : D)), dim3(256), 0, st(), p, nc, (int)D, ng, (const double*)pg_part,
-                             (const double*)acq.sc, (const double*)g.scales, kdj, o->beta1, o->beta2, 1.0 - b1k, 1.0 - b2k, o->eps, box, fin,
-                             x, acq.mo, acq.vo, acq.A + s);
-          LAUNCHCHK(ctx);
-        }
-      }
+      AGPCHK(acq_ascend(g, acq_latent_pred(g), p, box, o, x0, ldx0, R));
       if (best_x || best_a || best_idx) {
         hipLaunchKernelGGL(k_pw_ascent_best, dim3(1), dim3(256), 0, st(), (const double*)acq.X, (const double*)acq.A, R, D, 1.0,
                            (double*)best_x, D, (double*)best_a, (int64_t*)best_idx);
@@ -3494,6 +3530,104 @@ struct Svgp : SvgpBase {
         HIPCHK(ctx, hipMemcpy2DAsync(x_out, sizeof(double) * ldxo, acq.X, sizeof(double) * D, sizeof(double) * D, R,
                                      hipMemcpyDeviceToDevice, st()));
       if (a_out) HIPCHK(ctx, hipMemcpyAsync(a_out, acq.A, sizeof(double) * R, hipMemcpyDeviceToDevice, st()));
+    }
+    return AGP_OK;
+  }
+
+  // ---- batch acquisition: pending points ("ACQUISITION FUNCTIONS", paragraph "Pending points"; agp_acq_batch.h) ---------------------
+  // The pending points condition the variance through the augmented predictor (Z', a', A') of AcqBatchWs, built by bordering in the
+  // order of the points and kept as A0 and its rank-one terms; the passes above then run on it with m' = m + n.  With no pending point the latent's own objects are passed,
+  // so those calls are the launches of acquisition / acq_maximize.  Nothing of the latent's is written.
+  AcqBatchWs acqb;
+  // the arguments that the two calls share; noise is tau2
+  agp_status acqb_check_pending(const char* who, const void* xp, int64_t ldp, int64_t n, int64_t q, double noise) {
+    auto invalid = [&](const char* what) {
+      ctx->err = std::string(who) + what;
+      return AGP_ERR_INVALID;
+    };
+    if (n < 0 || q < 1 || n > AGP_ACQ_MAX_PENDING || q > AGP_ACQ_MAX_PENDING || n + q > AGP_ACQ_MAX_PENDING)
+      return invalid("n_pending >= 0, q >= 1 and n_pending + q <= AGP_ACQ_MAX_PENDING (64)");
+    if (!std::isfinite(noise) || noise < 0.0) return invalid("noise must be finite and >= 0");
+    if (n > 0 && !xp) return invalid("xp must be given when n_pending > 0");
+    if (n > 0 && ldp < D) return invalid("ldp >= D");
+    return AGP_OK;
+  }
+  // (Z', a', A') of the latent with the n pending points of xp bordered on, in their order
+  agp_status acqb_begin(Latent& g, const void* xp, int64_t ldp, int64_t n, double noise) {
+    if constexpr (std::is_same<T, double>::value) {
+      AGPCHK(acqb.reset(ctx, D, (const double*)g.Z, (const double*)g.apred, (const double*)g.Apred, mp));
+      if (n == 0) return AGP_OK;
+      HIPCHK(ctx, hipMemcpy2DAsync(acqb.Z + m * D, sizeof(double) * D, xp, sizeof(double) * ldp, sizeof(double) * D, n,
+                                   hipMemcpyDeviceToDevice, st()));
+      for (int64_t i = 0; i < n; ++i) AGPCHK(acqb_border(g, m + i, noise));
+      AGPCHK(acqb.rescale(ctx, m + n, D, (const double*)g.scales));
+    }
+    return AGP_OK;
+  }
+  agp_status acqb_border(Latent& g, int64_t n, double noise) {
+#pragma clang fp contract(off)
+    return acqb.border(ctx, n, D, (const double*)g.scales, g.k.kind, (double)kvar(g), (g.k.variance + jitter) + noise);
+  }
+  agp_status acquisition_pending(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, double noise, const void* xt,
+                                 int64_t ldx, int64_t nt, void* alpha_out, void* grad_out, int64_t ldg) override {
+    const char* who = "agp_svgp_acquisition_pending: ";
+    AcqParams p;
+    AGPCHK(acq_check_handle(who));
+    AGPCHK(acq_check_latent(who, l, d, &p));
+    AGPCHK(acqb_check_pending(who, xp, ldp, n, 1, noise));
+    if (nt < 0 || ldx < D || (grad_out && ldg < D) || (nt > 0 && (!xt || !alpha_out))) {
+      ctx->err = std::string(who) + "n_t >= 0, xt and alpha_out must not be NULL, ldx >= D, ldg >= D when grad_out is given";
+      return AGP_ERR_INVALID;
+    }
+    if (nt == 0) return AGP_OK;
+    if constexpr (std::is_same<T, double>::value) {
+      Latent& g = lat[l];
+      AGPCHK(acq_prepare(g, false));
+      if (n == 0) return acq_eval(g, acq_latent_pred(g), p, xt, ldx, nt, alpha_out, grad_out, ldg);
+      AGPCHK(acqb.ensure(ctx, m, D));
+      AGPCHK(acqb_begin(g, xp, ldp, n, noise));
+      AGPCHK(acq_eval(g, acqb.pred(m + n), p, xt, ldx, nt, alpha_out, grad_out, ldg));
+    }
+    return AGP_OK;
+  }
+  agp_status acq_maximize_batch(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, double noise, int64_t q,
+                                const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o, void* xb_out, int64_t ldxb,
+                                void* ab_out, void* idxb_out) override {
+    const char* who = "agp_svgp_acq_maximize_batch: ";
+    auto invalid = [&](const char* what) {
+      ctx->err = std::string(who) + what;
+      return AGP_ERR_INVALID;
+    };
+    AcqParams p;
+    PwAscentBox box;
+    AGPCHK(acq_check_handle(who));
+    AGPCHK(acq_check_latent(who, l, d, &p));
+    AGPCHK(acqb_check_pending(who, xp, ldp, n, q, noise));
+    if (!x0) return invalid("x0 must be given");
+    AGPCHK(acq_check_opts(ctx, who, D, o, &box));
+    if (!xb_out) return invalid("xb_out must be given");
+    if (R < 1 || R >= ((int64_t)1 << 31)) return invalid("n_starts >= 1 and below 2^31");
+    if (ldx0 < D) return invalid("ldx0 >= D");
+    if (ldxb < D) return invalid("ldxb >= D");
+    if constexpr (std::is_same<T, double>::value) {
+      Latent& g = lat[l];
+      AGPCHK(acq_prepare(g, true));
+      AGPCHK(acq.ensure_particles(ctx, R, D));
+      AGPCHK(acqb.ensure(ctx, m, D));
+      if (n > 0 || q > 1) AGPCHK(acqb_begin(g, xp, ldp, n, noise));
+      for (int64_t b = 0; b < q; ++b) {
+        const int64_t np = n + b;  // the points the round is conditioned on: the caller's and the winners before
+        AGPCHK(acq_ascend(g, np == 0 ? acq_latent_pred(g) : acqb.pred(m + np), p, box, o, x0, ldx0, R));
+        double* win = acqb.Z + (m + np) * D;  // the winner goes device to device into the next row of the pending list
+        hipLaunchKernelGGL(k_pw_ascent_best, dim3(1), dim3(256), 0, st(), (const double*)acq.X, (const double*)acq.A, R, D, 1.0, win, D,
+                           ab_out ? (double*)ab_out + b : (double*)nullptr, idxb_out ? (int64_t*)idxb_out + b : (int64_t*)nullptr);
+        LAUNCHCHK(ctx);
+        HIPCHK(ctx, hipMemcpyAsync((double*)xb_out + b * ldxb, win, sizeof(double) * D, hipMemcpyDeviceToDevice, st()));
+        if (b + 1 < q) {
+          AGPCHK(acqb_border(g, m + np, noise));
+          AGPCHK(acqb.rescale(ctx, m + np + 1, D, (const double*)g.scales));
+        }
+      }
     }
     return AGP_OK;
   }
@@ -6013,6 +6147,19 @@ agp_status agp_svgp_acq_maximize(agp_svgp* h, int32_t latent, const agp_acq_desc
                                  void* best_idx) {
   HCHKF(h);
   return h->impl->acq_maximize(latent, desc, x0, ldx0, n_starts, opts, x_out, ldxo, a_out, best_x, best_a, best_idx);
+}
+agp_status agp_svgp_acquisition_pending(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xp, int64_t ldp,
+                                        int64_t n_pending, double noise, const void* xt, int64_t ldx, int64_t n_t, void* alpha_out,
+                                        void* grad_out, int64_t ldg) {
+  HCHKF(h);
+  return h->impl->acquisition_pending(latent, desc, xp, ldp, n_pending, noise, xt, ldx, n_t, alpha_out, grad_out, ldg);
+}
+agp_status agp_svgp_acq_maximize_batch(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xp, int64_t ldp,
+                                       int64_t n_pending, double noise, int64_t q, const void* x0, int64_t ldx0, int64_t n_starts,
+                                       const agp_pw_ascent_opts* opts, void* xb_out, int64_t ldxb, void* ab_out, void* idxb_out) {
+  HCHKF(h);
+  return h->impl->acq_maximize_batch(latent, desc, xp, ldp, n_pending, noise, q, x0, ldx0, n_starts, opts, xb_out, ldxb, ab_out,
+                                     idxb_out);
 }
 agp_status agp_svgp_predict_y(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* y_out) {
   HCHKF(h);

@@ -759,7 +759,63 @@ agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int
  * with grad_out given, (n_t > 0) xt or alpha_out NULL; all five outputs NULL; n_starts < 1 or >= 2^31; ldx0 < D; ldxo < D with x_out
  * given; steps outside [0, 65536]; beta1 or beta2 outside [0, 1); eps not finite and positive; lo_host, hi_host or lr_host NULL, a
  * non-finite bound, lo > hi, a step size that is not finite and positive.
- * Out of scope: log-EI, Float32, multi-output and sharded handles, batch (q-) acquisition, a single-launch ascent. */
+ *
+ * Pending points (batch acquisition by hallucinated observations: GP-BUCB, Desautels et al. 2014, "kriging believer").  The posterior
+ * is conditioned on the pending points at their own predicted mean: the mean stays, the variance shrinks, and q points are picked
+ * greedily, each conditioned on those before.  This is for one latent with kernel k, kernel variance v, inducing / training inputs Z
+ * (m points) and the predictor (a, A) of AGP_VEC_APRED / AGP_MAT_APRED.  mu(x) = k*(x)' a and var(x) = v + jitter - k*(x)' A k*(x)
+ * are exactly what agp_svgp_predict_f returns.  The posterior covariance of the latent is cov(x, x') = k(x, x') - k*(x)' A k*(x').
+ * It carries no jitter.  Take pending points P = (p_1 ... p_n) and a fantasy-noise variance tau2 >= 0 (`noise`):
+ *   C_ij   = cov(p_i, p_j) + (jitter + tau2) [i == j]          n x n
+ *   c_j(x) = cov(x, p_j)
+ *   mu_P(x)  = mu(x)
+ *   var_P(x) = var(x) - c(x)' C^-1 c(x)
+ *   alpha_P(x) = A(mu(x), var_P(x))           the table above, unchanged
+ *   grad alpha_P by the chain rule, with grad var_P = grad var - 2 (dc/dx)' C^-1 c
+ * This is the posterior after observing mu(P) at P with noise tau2.  For an exact GP with noise sigma^2 and tau2 = sigma^2, it equals
+ * the GP refitted on (X u P, y u mu(P)) with fixed hyper-parameters.  Equivalent form, the one that is computed: augment the predictor,
+ *   Z'  = [Z; P]
+ *   a'  = [a; 0]
+ *   A'  = [[A + V C^-1 V', -V C^-1], [-C^-1 V', C^-1]],   V = A K_ZP
+ *   var_P(x) = (v + jitter) - k'(x)' A' k'(x)
+ * and the per-step kernels of agp_svgp_acquisition / agp_svgp_acq_maximize run unchanged on (Z', a', A') with m' = m + n.
+ * Bordering order: A' is always built by bordering, one point at a time in the order p_1, p_2, ....  Given the current (Z', A') of
+ * size n' and a new point p:
+ *   k' = k(Z', p)
+ *   w  = A' k'
+ *   c  = (v + jitter + tau2) - k'' w            (k'' is the transpose of k')
+ *   A'' = [[A' + w w'/c, -w/c], [-w'/c, 1/c]]
+ * The update is kept in its factors, not summed into one matrix: with u = [w; -1], A'' = A' + u u'/c, and stored are A0 = [[A, 0], [0, 0]],
+ * the u_b and the -u_b / c_b, so that A' k' = A0 k' + sum_b u_b (u_b' k') / c_b and, per pass, W = K*m' A0^T + (K*m' U^T) (U / c)^T (three
+ * GEMMs where the calls above have one).  The entries of a summed A' reach 1 / c and k'' A' k' would lose eps |A'| |k'|^2 absolutely --
+ * 1e-9 of the variance with 63 pending points around one inducing point, which EI and PI magnify --; in the factors an error of u_b' k'
+ * enters var_P multiplied by u_b' k' itself, which is small where c_b is.
+ * A pending set passed in by the caller and a set accumulated during a batch therefore give the same bits.  c <= 0 or a non-finite c
+ * cannot happen with jitter > 0 in exact arithmetic; it is handled like a non-SPD factorisation: latched on the handle and reported
+ * by agp_svgp_check_status (AGP_ERR_NOT_POSDEF).  Every sum of the bordering has an order fixed by n'; no atomics, nothing waits.
+ * The augmented predictor lives in workspaces of its own, sized once for m + AGP_ACQ_MAX_PENDING points: nothing that
+ * agp_svgp_predict_f, agp_svgp_predict_f_grad, agp_svgp_acquisition or agp_svgp_acq_maximize use is resized or overwritten.
+ *
+ * agp_svgp_acquisition_pending  agp_svgp_acquisition with alpha_P and grad alpha_P: xp holds the n_pending points (device, row i at
+ *   xp + i * ldp, ldp >= D), noise = tau2.  With n_pending = 0 it is agp_svgp_acquisition, launch for launch and bit for bit (xp is
+ *   then not looked at).
+ * agp_svgp_acq_maximize_batch  q rounds.  Round b = 0 ... q - 1 runs the ascent of agp_svgp_acq_maximize -- the same recurrence, the
+ *   same x0, the same best-start rule and the same chunks of 4096 -- on alpha_P with P = pending u {x_0 ... x_{b-1}}.  xb_out[b] (at
+ *   xb_out + b * ldxb, ldxb >= D) is the round's best final iterate, ab_out[b] (nullable) alpha_P there, idxb_out[b] (nullable, int64)
+ *   the index of the winning start.  The whole call is enqueued on the handle's stream with no host synchronisation between steps or
+ *   between rounds: the host knows every size in advance, and the winner moves device to device into the pending list.  The only
+ *   wait is a first-time or growing allocation, as in agp_svgp_acq_maximize.  With n_pending = 0 and q = 1 the outputs have the bits
+ *   of best_x / best_a / best_idx of agp_svgp_acq_maximize; a batch of q equals q chained calls with q = 1, each given the earlier
+ *   winners as extra pending points; a repeat of any call gives the same bits.  No side effects, as above.
+ * Both refuse (AGP_ERR_UNSUPPORTED) the same handles in the same words as the two calls above, before any launch and with the outputs
+ * untouched.  AGP_ERR_INVALID with a message: everything the two calls above check; n_pending < 0, q < 1 or n_pending + q >
+ * AGP_ACQ_MAX_PENDING; noise negative or not finite; xp NULL with n_pending > 0; ldp < D (n_pending > 0); ldxb < D; xb_out NULL.
+ * Pending coordinates are device data and are not validated (the kernel functions clamp a squared distance that is not a positive
+ * number to 0, so a NaN coordinate does not reliably show as a NaN value).
+ *
+ * Out of scope: MC q-EI with a joint reparameterised sample, fantasies that move the mean, log-EI, Float32, multi-output and sharded
+ * handles, a single-launch ascent. */
+#define AGP_ACQ_MAX_PENDING 64 /* n_pending + q; an interface limit, not a tuned value */
 enum { AGP_ACQ_UCB = 0, AGP_ACQ_EI = 1, AGP_ACQ_PI = 2 };
 typedef struct {
   int32_t kind;     /* AGP_ACQ_* */
@@ -1144,6 +1200,16 @@ agp_status agp_svgp_acq_maximize(agp_svgp* h, int32_t latent, const agp_acq_desc
                                  void* best_x,              /* nullable: [d], D values */
                                  void* best_a,              /* nullable: one double */
                                  void* best_idx);           /* nullable: one int64 */
+/* "ACQUISITION FUNCTIONS", paragraph "Pending points" */
+agp_status agp_svgp_acquisition_pending(agp_svgp* h, int32_t latent, const agp_acq_desc* desc,
+                                        const void* xp, int64_t ldp, int64_t n_pending, double noise,
+                                        const void* xt, int64_t ldx, int64_t n_t,
+                                        void* alpha_out, void* grad_out /* nullable */, int64_t ldg);
+agp_status agp_svgp_acq_maximize_batch(agp_svgp* h, int32_t latent, const agp_acq_desc* desc,
+                                       const void* xp /* nullable iff n_pending == 0 */, int64_t ldp, int64_t n_pending, double noise,
+                                       int64_t q, const void* x0, int64_t ldx0, int64_t n_starts, const agp_pw_ascent_opts* opts,
+                                       void* xb_out /* [q][ldxb] */, int64_t ldxb,
+                                       void* ab_out /* double[q], nullable */, void* idxb_out /* int64[q], nullable */);
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D);
 agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void* out, int64_t ld);
 agp_status agp_pathwise_destroy(agp_pathwise* p);

@@ -28,6 +28,8 @@
 #   _predict_f / predict_y / proba_y                          src/training/predictions.jl:25-92,178-247 -> agp_svgp_predict_f / _predict_y / _proba_y
 #   predict_f_grad(model, X_test) (no counterpart: d mu / d x*, d sigma^2 / d x* of predict_f)          -> agp_svgp_predict_f_grad
 #   acquisition / maximize_acquisition(model, UCB | EI | PI, ...) (no counterpart: Bayesian optimisation) -> agp_svgp_acquisition, agp_svgp_acq_maximize
+#   acquisition_pending / maximize_acquisition_batch(model, ...; pending) (no counterpart: batch acquisition by hallucinated
+#     observations)                                                                  -> agp_svgp_acquisition_pending, agp_svgp_acq_maximize_batch
 #   init_state                                                src/training/states.jl:1-9               -> agp_svgp_init_state
 # Multi-GPU (one Julia process per GPU, e.g. under MPI.jl or Distributed): agp_comm_* binds RCCL inside the library; the host only
 # ships the 128-byte id from rank 0 to the others (section "multi-GPU" below).
@@ -1594,7 +1596,59 @@ function maximize_acquisition(hm::HipModel{Float64}, acq::AcqDesc, X0::AbstractM
     full || return x_best, a_best
     return x_best, a_best, Array(ib)[1] + 1, permutedims(Array(X)), Array(A)
 end
+# Pending points ("ACQUISITION FUNCTIONS", paragraph "Pending points"): the posterior conditioned on P (n x D) at its own predicted mean
+# with the noise variance pending_noise; the mean stays, the variance shrinks.  Never run, like everything in this file.
+# acquisition_pending(hm, acq, X, P; pending_noise=0.0, grad=false, latent=1): alpha_P at the rows of X (agp_svgp_acquisition_pending)
+function acquisition_pending(hm::HipModel{Float64}, acq::AcqDesc, X::AbstractMatrix, P::AbstractMatrix; pending_noise::Real=0.0,
+                             grad::Bool=false, latent::Integer=1)
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    Xd, Pd = ROCArray{Float64}(permutedims(X)), ROCArray{Float64}(permutedims(P))   # column-major D x n == [i][d]
+    D, nt = size(Xd)
+    n = size(Pd, 2)
+    a = ROCArray{Float64}(undef, nt)
+    G = grad ? ROCArray{Float64}(undef, D, nt) : nothing
+    check(hm.ctx, ccall((:agp_svgp_acquisition_pending, libagp), Int32,
+                        (Ptr{Cvoid}, Int32, Ref{AcqDesc}, Ptr{Cvoid}, Int64, Int64, Float64, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid},
+                         Int64),
+                        hm.h, latent - 1, Ref(acq), n > 0 ? pointer(Pd) : C_NULL, D, n, pending_noise, pointer(Xd), D, nt, pointer(a),
+                        grad ? pointer(G) : C_NULL, D))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    check(hm.ctx, ccall((:agp_svgp_check_status, libagp), Int32, (Ptr{Cvoid},), hm.h))
+    return grad ? (Array(a), permutedims(Array(G))) : Array(a)
+end
+# maximize_acquisition_batch(hm, acq, q, X0, lo, hi; pending=nothing, pending_noise=0.0, steps=100, ...): q points picked greedily on
+# the device (agp_svgp_acq_maximize_batch), each round conditioned on `pending` and on the winners before.  Returns (X_batch q x D,
+# a_batch (q)); full=true adds idx (q, 1-based).
+function maximize_acquisition_batch(hm::HipModel{Float64}, acq::AcqDesc, q::Integer, X0::AbstractMatrix, lo, hi; pending=nothing,
+                                    pending_noise::Real=0.0, steps::Integer=100, lr=nothing, beta1::Real=0.9, beta2::Real=0.999,
+                                    eps::Real=1e-8, latent::Integer=1, full::Bool=false)
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    R, D = size(X0)
+    vec_of(v) = v isa Number ? fill(Float64(v), D) : collect(Float64, v)
+    lov, hiv = vec_of(lo), vec_of(hi)
+    lrv = lr === nothing ? map(w -> w == 0 ? 1.0 : 0.02 * w, hiv .- lov) : vec_of(lr)
+    (length(lov) == D && length(hiv) == D && length(lrv) == D) || error("maximize_acquisition_batch: lo, hi and lr must be scalars or of length $D")
+    n = pending === nothing ? 0 : size(pending, 1)
+    Xd = ROCArray{Float64}(permutedims(X0))
+    Pd = n > 0 ? ROCArray{Float64}(permutedims(pending)) : nothing
+    xb, ab, ib = ROCArray{Float64}(undef, D, q), ROCArray{Float64}(undef, q), ROCArray{Int64}(undef, q)
+    GC.@preserve lov hiv lrv begin
+        opts = Ref(PwAscentOpts(steps, 0, 0, beta1, beta2, eps, pointer(lov), pointer(hiv), pointer(lrv)))
+        check(hm.ctx, ccall((:agp_svgp_acq_maximize_batch, libagp), Int32,
+                            (Ptr{Cvoid}, Int32, Ref{AcqDesc}, Ptr{Cvoid}, Int64, Int64, Float64, Int64, Ptr{Cvoid}, Int64, Int64,
+                             Ref{PwAscentOpts}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                            hm.h, latent - 1, Ref(acq), n > 0 ? pointer(Pd) : C_NULL, D, n, pending_noise, q, pointer(Xd), D, R, opts,
+                            pointer(xb), D, pointer(ab), pointer(ib)))
+    end
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    check(hm.ctx, ccall((:agp_svgp_check_status, libagp), Int32, (Ptr{Cvoid},), hm.h))
+    Xb, a = permutedims(Array(xb)), Array(ab)
+    return full ? (Xb, a, Array(ib) .+ 1) : (Xb, a)
+end
 acquisition(ho::HipOnlineModel, acq::AcqDesc, X::AbstractMatrix; kw...) = acquisition(ho.cur, acq, X; kw...)
 maximize_acquisition(ho::HipOnlineModel, acq::AcqDesc, X0::AbstractMatrix, lo, hi; kw...) = maximize_acquisition(ho.cur, acq, X0, lo, hi; kw...)
+acquisition_pending(ho::HipOnlineModel, acq::AcqDesc, X::AbstractMatrix, P::AbstractMatrix; kw...) = acquisition_pending(ho.cur, acq, X, P; kw...)
+maximize_acquisition_batch(ho::HipOnlineModel, acq::AcqDesc, q::Integer, X0::AbstractMatrix, lo, hi; kw...) =
+    maximize_acquisition_batch(ho.cur, acq, q, X0, lo, hi; kw...)
 
 end # module
