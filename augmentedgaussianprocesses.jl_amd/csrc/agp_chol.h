@@ -374,7 +374,12 @@ __device__ __forceinline__ typename Mfma<T>::acc_t mma_blk32(const T* As, const 
 }
 
 // eliminate the 32x32 block at (o, o) of bufA (lower valid): L -> bufA block, L^-1 -> bufB block ; all threads call
-template <typename T, typename H>
+// JOIN (the chain of k_chol_dag with the balanced S = D - L L', o = 0 only): the block's columns 0..15 are the two result tiles whose
+// accumulation chains ran on two waves each.  bufA holds the even chain (the one that started from D), sc[lo * 16 + hi] the odd
+// one, and the load adds them: the single acc + p1 that ends mma_tile16, on the same operands.  These reads sit in front of the
+// barrier below and the rounds' first publish into sc behind it.
+constexpr int JOIN_ELEMS = 32 * 16;
+template <typename T, typename H, bool JOIN = false>
 __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* piv, const bool act, const int ti,
                                              const int tj, H& hook) {
   T a[2][2], g[2][2];
@@ -385,6 +390,9 @@ __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* 
       int R = ti + 16 * r, Cc = tj + 16 * c;
       int lo = R >= Cc ? R : Cc, hi = R >= Cc ? Cc : R;
       a[r][c] = bufA[(o + lo) * LDP + o + hi];
+      if constexpr (JOIN) {
+        if (r == 0 || c == 0) a[r][c] += sc[lo * 16 + hi];  // (hi < 16)
+      }
       g[r][c] = (R == Cc) ? T(1) : T(0);
     }
   __syncthreads();
@@ -411,7 +419,7 @@ __device__ __forceinline__ void elim_block32(T* bufA, T* bufB, int o, T* sc, T* 
   __syncthreads();
 }
 
-template <typename T, typename H, bool NOX21 = false>
+template <typename T, typename H, bool NOX21 = false, bool JOIN = false>
 __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T* piv, int32_t* info, int64_t col0,
                                                       int64_t nvalid, H& hook) {
   const int tid = threadIdx.x;
@@ -421,7 +429,7 @@ __device__ __forceinline__ void factor_diag_tile_2lvl(T* bufA, T* bufB, T* sc, T
   const bool mw = wave < 4;  // the four waves that run the 32^3 MFMA products (one 16x16 result tile each)
   typedef typename Mfma<T>::acc_t acc_t;
   NoHook nohook;
-  elim_block32<T, NoHook>(bufA, bufB, 0, sc, piv, act, ti, tj, nohook);
+  elim_block32<T, NoHook, JOIN>(bufA, bufB, 0, sc, piv, act, ti, tj, nohook);
   // L21 = A21 X11' -> scratch in bufB[32:64, 0:32] (free until X21 is formed at the end; NOX21: it stays there, that IS the
   // output format): no barrier between reading A21 and writing the result.  The other waves clear the upper-right blocks
   // meanwhile (input garbage in bufA, nothing yet in bufB).
@@ -1284,6 +1292,61 @@ __device__ __forceinline__ typename Mfma<T>::acc_t mma_tile16(const T* Ar, const
   return acc;
 }
 
+// mma_tile16 with neg over k in [0, TILE), and (THIRD) in the same k loop ONE of the two accumulation chains of a second tile (the
+// chain's balanced S = D - L L'): x takes the k-steps of parity par of Ar2 Bc2', in mma_tile16's order and with its operands --
+// par = 0 is its `acc` chain (x comes in holding D), par = 1 its `p1` chain (x comes in zero).  The caller's partner wave runs the
+// other parity, and the two are added where they are read next (elim_block32<.., JOIN>).
+// The operands come from LDS a quarter (four k-steps) at a time, two quarters ahead of the MFMAs that consume them (the
+// sched_barriers pin that): mma_tile16's loop reads a pair of k-steps, waits for them and issues their MFMAs, one exposed LDS
+// latency per trip; here the MFMAs follow one another as the reads return.  (All sixteen k-steps at once: 256 VGPRs and scratch.)
+template <typename T, bool THIRD>
+__device__ __forceinline__ void mma_tile16_chain(const T* Ar, const T* Bc, typename Mfma<T>::acc_t& acc, const T* Ar2,
+                                                 const T* Bc2, int par, typename Mfma<T>::acc_t& x, int lane) {
+  constexpr int NK = TILE / 4;
+  const T* pa = Ar + (lane & 15) * LDP + (lane >> 4);
+  const T* pb = Bc + (lane & 15) * LDP + (lane >> 4);
+  const T* qa = Ar2 + (lane & 15) * LDP + (lane >> 4) + 4 * par;
+  const T* qb = Bc2 + (lane & 15) * LDP + (lane >> 4) + 4 * par;
+  T av[NK], bv[NK], xa[NK / 2], xb[NK / 2];
+  typename Mfma<T>::acc_t p1;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) p1[r] = T(0);
+  auto ld = [&](int q) {  // the operands of k-steps 4 q .. 4 q + 3
+#pragma unroll
+    for (int kk = 4 * q; kk < 4 * q + 4; kk += 2) {
+      av[kk] = pa[kk * 4];
+      bv[kk] = pb[kk * 4];
+      av[kk + 1] = pa[kk * 4 + 4];
+      bv[kk + 1] = pb[kk * 4 + 4];
+      if (THIRD) {
+        xa[kk / 2] = qa[kk * 4];
+        xb[kk / 2] = qb[kk * 4];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto mm = [&](int q) {
+#pragma unroll
+    for (int kk = 4 * q; kk < 4 * q + 4; kk += 2) {
+      acc = Mfma<T>::mma(-av[kk], bv[kk], acc);
+      p1 = Mfma<T>::mma(-av[kk + 1], bv[kk + 1], p1);
+      if (THIRD) x = Mfma<T>::mma(-xa[kk / 2], xb[kk / 2], x);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  static_assert(NK == 16, "four quarters of four k-steps");
+  ld(0);
+  ld(1);
+  mm(0);
+  ld(2);
+  mm(1);
+  ld(3);
+  mm(2);
+  mm(3);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] += p1[r];
+}
+
 // Ts <- Ts X' in place (64 x 64 in LDS, [r][k] stride LDP) for a lower-triangular X = [[X11, 0], [X21, X22]] of which only the
 // step-launch slot format Xs = [[X11, 0], [L21, X22]] is at hand (factor_diag_tile_2lvl<.., NOX21>; X^-1 = [[L11, 0], [L21, L22]]):
 // a forward substitution in two 32-column blocks,
@@ -1777,6 +1840,15 @@ template <typename T, bool STEP, bool BATCH>
 constexpr bool dag_store_dg() {
   return !(STEP && sizeof(T) == 8);
 }
+// Schedule of the chain's S = D - L L' (ten 16x16 result tiles, eight waves), ONE decision like the three above (step, hyper
+// iteration, potrf, batched; merged launch and ROLE 1): fp64 chains split the two accumulation chains of tiles (0, 0) and (1, 0)
+// over waves 0..3, so that every SIMD issues 40 of the 160 MFMAs in one pass (mma_tile16_chain, elim_block32<.., JOIN>).  fp32
+// keeps two passes, instruction for instruction: its C3 step has twice reacted to a change of the chain's pace (see above), and
+// the balanced form has no C3 measurement.
+template <typename T>
+constexpr bool dag_chain_balance() {
+  return sizeof(T) == 8;
+}
 template <typename T, int ROLE, bool PRO>
 constexpr int dag_min_waves() {
   return ROLE != 2 ? 1 : PRO ? (sizeof(T) == 8 ? 2 : 4) : (sizeof(T) == 8 ? AGP_TILES_WAVES_F64 : AGP_TILES_WAVES_F32);
@@ -1820,7 +1892,8 @@ struct ProdArgs {
 //   [2048, 4096)  start, [4096, 6144) exit of workgroup b (b < 2048)
 //   [6144, 6400)  start, [6400, 6656) end of workgroup b of the deferred fallback / row-statistics launch behind it (k_safe_rowstats)
 constexpr int STRACE_SLOTS = 8192, STRACE_XPUB = 600, STRACE_EXT = 1100, STRACE_FILL0 = 1400, STRACE_FILL1 = 1500, STRACE_WG0 = 2048,
-              STRACE_WG1 = 4096, STRACE_MAXWG = 2048, STRACE_SAFE0 = 6144, STRACE_SAFE1 = 6400, STRACE_LOOK = 608, STRACE_NEAR = 640;
+              STRACE_WG1 = 4096, STRACE_MAXWG = 2048, STRACE_SAFE0 = 6144, STRACE_SAFE1 = 6400, STRACE_LOOK = 608, STRACE_NEAR = 640,
+              STRACE_GLUE = 1040;  // per block column k of the chain: + k substitution done (S = D - L L' starts), + 16 + k S signalled
 #ifdef AGP_STEP_TRACE
 struct StraceExit {  // stamps the exit of its workgroup, whichever return it leaves by
   unsigned long long* p;
@@ -1852,6 +1925,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   const int64_t nx = STEP ? 0 : nx_;
   constexpr bool SUBST = dag_block_subst<T, STEP, BATCH>();  // X_k travels without its off-diagonal block (nobody reads X_k as such)
   constexpr bool STORE_DG = dag_store_dg<T, STEP, BATCH>();  // the chain leaves the diagonal factors in Dg
+  constexpr bool BAL = dag_chain_balance<T>();               // the chain's S = D - L L' in one pass, 40 MFMAs per SIMD
   const int write_x = STEP ? 0 : (opts & 1);
   const bool store_l = STEP ? false : (opts & 2) != 0;
   // nb > 1: nb independent problems of the same shape (the latents of a small multi-class model) in ONE launch, their
@@ -2266,6 +2340,9 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
     } else {
       acc8_foreach<T>(acc, [&](int r, int cc, T& val) { bufA[r * LDP + cc] = val; });
     }
+    if constexpr (BAL) {  // the first tile has no odd chains to join: x + (-0) is x, bit for bit, for every x
+      for (int e = tid; e < JOIN_ELEMS; e += CHOL_THREADS) sc[e] = -T(0);
+    }
     __syncthreads();
     T* bufC = sm + (FUSED ? 2 : 0) * TILE * LDP;
     T* bufD = sm + (FUSED ? 3 : 0) * TILE * LDP;
@@ -2294,7 +2371,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       PRO_TS(528 + k);
       pf.tlook = (PRO && trace) ? trace + STRACE_LOOK + k : nullptr;
 #endif
-      factor_diag_tile_2lvl<T, decltype(pf), SUBST>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
+      factor_diag_tile_2lvl<T, decltype(pf), SUBST, BAL>(bufA, bufB, sc, piv, info, k0, nvalid, pf);
       DAG_TRC(k, 2);
       PRO_TS(512 + k);
       {  // X_k out (coherent): all LDS reads first, then the stores back to back (a read-store-read-store loop exposed the
@@ -2398,9 +2475,40 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       if (dag_feed_deferred<T>() && !late_feed) pf.store_d();
       __syncthreads();
       DAG_TRC(k + 1, 5);
-      //   S = D - L L': only the ten 16x16 tiles on and below the diagonal (the factorisation never reads above it); every
-      //   wave takes one, waves 0 and 1 a second (SIMDs 0, 1: three tiles, SIMDs 2, 3: two).  In place in bufD.
-      {
+#ifdef AGP_STEP_TRACE
+      PRO_TS(STRACE_GLUE + k);  // (the glue of column k: 512 + k its start, here the substitution is done, + 16 S is signalled)
+#endif
+      //   S = D - L L': only the ten 16x16 tiles on and below the diagonal (the factorisation never reads above it).  In place in bufD.
+      if constexpr (BAL) {
+        //   Wave w takes tile 2 + w whole; tiles (0, 0) and (1, 0) go by accumulation chain to waves 0..3 (wave w: tile (w >> 1, 0),
+        //   k-steps of parity w & 1), in the same k loop: 24 + 16 = 40 MFMAs on every SIMD, one pass.  Even chains land in bufD,
+        //   odd ones in sc (idle between two eliminations); the next elimination's first load adds them (elim_block32<.., JOIN>).
+        const int i2 = wave < 1 ? 1 : wave < 4 ? 2 : 3, j2 = wave < 1 ? 1 : wave < 4 ? wave - 1 : wave - 4;  // tile 2 + wave
+        T* own = bufD + 16 * i2 * LDP + 16 * j2;
+        acc_t a = acc_load16<T>(own, lane);
+        if (wave < 4) {
+          const int xt = wave >> 1, par = wave & 1;
+          T* xd = bufD + 16 * xt * LDP;
+          acc_t x;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const T d = xd[Mfma<T>::row(lane, r) * LDP + (lane & 15)];
+            x[r] = par ? T(0) : d;
+          }
+          mma_tile16_chain<T, true>(bufC + 16 * i2 * LDP, bufC + 16 * j2 * LDP, a, bufC + 16 * xt * LDP, bufC, par, x, lane);
+          if (par) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sc[(16 * xt + Mfma<T>::row(lane, r)) * 16 + (lane & 15)] = x[r];
+          } else {
+            acc_store16<T>(xd, x, lane);
+          }
+        } else {
+          acc_t none = a;  // (no third chain on waves 4..7)
+          mma_tile16_chain<T, false>(bufC + 16 * i2 * LDP, bufC + 16 * j2 * LDP, a, bufC, bufC, 0, none, lane);
+        }
+        acc_store16<T>(own, a, lane);
+      } else {
+        //   Every wave takes one, waves 0 and 1 a second (SIMDs 0, 1: three tiles, SIMDs 2, 3: two).
         // tiles in row-major lower order: (0,0) (1,0) (1,1) (2,0) (2,1) (2,2) (3,0) (3,1) (3,2) (3,3)
         const int ti_[10] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3}, tj_[10] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3};
 #pragma unroll
@@ -2423,6 +2531,9 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
         }
       }
       dag_signal(ready + ((k + 1) * nt + k) * DAG_FS, epoch);
+#ifdef AGP_STEP_TRACE
+      PRO_TS(STRACE_GLUE + 16 + k);
+#endif
       {  // the tile to factor next is in bufD; L_kk stays where it is (now called bufD) until the side job has stored it
         T* t0 = bufA;
         bufA = bufD;
@@ -2511,28 +2622,49 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   __syncthreads();
   DAG_TR(6);
   Acc8<T> out;
+  // The last block column's kappa rows of a step launch with the epilogue (epi_row, block substitution): no tile waits for the flag
+  // of (R, nt - 1) or loads its hand-over slot -- consumers loop over block columns j < c' with c' > c, and a step launch has no
+  // product workgroups -- so the tile skips the move into the accumulator layout, the slot store and the signal (fence, barrier,
+  // flag) and goes from the substitution's barrier to its rows.  W still goes to its real home, straight from LDS in whole rows
+  // (a wave stores 512 contiguous bytes), for the kernels behind the launch.
+  const bool tail_row = SUBST && epi_row;
   if (SUBST) {  // 40 instead of 64 MFMAs per SIMD, in place in bufA; the result then moves into the product's accumulator layout
     subst_tile<T>(bufA, bufB, (T*)nullptr, [] { __syncthreads(); });
     __syncthreads();
-    acc8_foreach<T>(out, [&](int r, int cc, T& val) { val = bufA[r * LDP + cc]; });
+    if (!tail_row) acc8_foreach<T>(out, [&](int r, int cc, T& val) { val = bufA[r * LDP + cc]; });
   } else {
     out.zero();
     mma8<T>(bufA, bufB, out);
   }
-  {
-    T* hs = HL + (R * nt + c) * SLOT;
-    acc8_foreach<T>(out, [&](int r, int cc, T& val) {
-      __hip_atomic_store(hs + r * TILE + cc, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    });
+  if (tail_row) {
+    T wv[TILE * TILE / CHOL_THREADS];
+#pragma unroll
+    for (int q = 0; q < TILE * TILE / CHOL_THREADS; ++q) {
+      const int e = tid + q * CHOL_THREADS;
+      wv[q] = bufA[(e >> 6) * LDP + (e & 63)];
+    }
+#pragma unroll
+    for (int q = 0; q < TILE * TILE / CHOL_THREADS; ++q) {
+      const int e = tid + q * CHOL_THREADS;
+      rowp[(e >> 6) * ldr + c0 + (e & 63)] = wv[q];
+    }
+    DAG_TR(7);
+  } else {
+    {
+      T* hs = HL + (R * nt + c) * SLOT;
+      acc8_foreach<T>(out, [&](int r, int cc, T& val) {
+        __hip_atomic_store(hs + r * TILE + cc, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      });
+    }
+    if (idr) {  // (L^-T)(i, c) = X(c, i)': the tile of X proper, for the kernels that follow
+      const int64_t i0 = (R - nt - ne) * TILE;
+      acc8_foreach<T>(out, [&](int r, int cc, T& val) { X[(c0 + cc) * ldx + i0 + r] = val; });
+    } else if (ext || store_l) {  // W (always) / the factor (when wanted) in its real home, for the kernels that follow
+      acc8_foreach<T>(out, [&](int r, int cc, T& val) { rowp[r * ldr + c0 + cc] = val; });
+    }
+    DAG_TR(7);
+    dag_signal(ready + (R * nt + c) * DAG_FS, epoch);
   }
-  if (idr) {  // (L^-T)(i, c) = X(c, i)': the tile of X proper, for the kernels that follow
-    const int64_t i0 = (R - nt - ne) * TILE;
-    acc8_foreach<T>(out, [&](int r, int cc, T& val) { X[(c0 + cc) * ldx + i0 + r] = val; });
-  } else if (ext || store_l) {  // W (always) / the factor (when wanted) in its real home, for the kernels that follow
-    acc8_foreach<T>(out, [&](int r, int cc, T& val) { rowp[r * ldr + c0 + cc] = val; });
-  }
-  DAG_TR(7);
-  dag_signal(ready + (R * nt + c) * DAG_FS, epoch);
   DAG_TR(3);
   if (strace_row) STRACE(STRACE_EXT + 4 * (R - nt) + 1);
   if (epi_row) {

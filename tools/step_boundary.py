@@ -7,7 +7,8 @@
 `run` trains the bench's C2 model (bench.make_data / bench.build_model, look-ahead on, as bench.py does) and destroys the context,
 which writes the dump.  `table` averages the last launches of each dump; every time is in us relative to the end of the chain's
 last tile elimination, factor(nt - 1), of the same launch ("next" rows: of the launch before).  Below it, per block column of the
-chain: how long the tile elimination and the glue behind it took and which way the next column's two feeder tiles came in (prefetched
+chain: how long the tile elimination and the glue behind it took (the glue split into X_k out + substitution | S = D - L L' up to its
+signal | entry of the next elimination, where the library has the STRACE_GLUE stamps) and which way the next column's two feeder tiles came in (prefetched
 under the elimination, or late because the look failed / because a sentinel was seen).  Last, the two feeder tiles of block columns
 2 .. 6 against the look that wants them: when their workgroup started, finished its product, took the eta2 step and parked."""
 import os
@@ -19,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XPUB, EXT, FILL0, FILL1, WG0, WG1, SAFE0, SAFE1 = 600, 1100, 1400, 1500, 2048, 4096, 6144, 6400
 ELIM0, PATH = 528, 560  # per block column k: factor(k) starts ; the path word of column k + 1's feed (PRO_TS, agp_chol.h)
 LOOK, NEAR = 608, 640   # the look under factor(k) ; the near-diagonal tiles of block columns 2 .. 6 (STRACE_LOOK, STRACE_NEAR)
+GLUE = 1040             # the glue of column k: + k substitution done (S = D - L L' starts), + 16 + k S signalled (STRACE_GLUE)
 
 
 def run(dump, steps, warm):
@@ -87,17 +89,31 @@ def columns(cur, nt):
         x = x[np.isfinite(x)]
         return float(np.median(x)) if x.size else float("nan")
 
-    out = ["  per block column: elimination us | glue us | path of the next column's feed (share of launches; median path first)"]
+    g0, g1 = cur[:, GLUE:GLUE + nt], cur[:, GLUE + 16:GLUE + 16 + nt]
+    parts = np.isfinite(g0).any()  # (the glue's own stamps: X_k out + substitution | S = D - L L' up to its signal | entry of factor(k + 1))
+    out = ["  per block column: elimination us | glue us" + (" = substitution | product | entry" if parts else "") +
+           " | path of the next column's feed (share of launches; median path first)"]
+    sums = np.zeros(3)
     for k in range(nt):
         el = med((e1[:, k] - e0[:, k]) * 0.01)
         gl = med((e0[:, k + 1] - e1[:, k]) * 0.01) if k + 1 < nt else float("nan")
+        if parts and k + 1 < nt:
+            p3 = [med((g0[:, k] - e1[:, k]) * 0.01), med((g1[:, k] - g0[:, k]) * 0.01), med((e0[:, k + 1] - g1[:, k]) * 0.01)]
+            sums += p3
+            gl = f"{gl:6.2f} = {p3[0]:5.2f} | {p3[1]:5.2f} | {p3[2]:5.2f}"
+            gl, glf = float("nan"), gl
+        else:
+            glf = None
         pk = path[:, k][np.isfinite(path[:, k])].astype(int)
         if pk.size:
             order = sorted(PATHS, key=lambda c: (c != int(np.median(pk)), c))
             what = "  ".join(f"{PATHS[c]} {np.mean(pk == c):4.0%}" for c in order if np.any(pk == c))
         else:
             what = "-"
-        out.append(f"    k = {k:2d}  {el:6.2f}  {gl:6.2f}  {what}")
+        out.append(f"    k = {k:2d}  {el:6.2f}  {glf if glf else format(gl, '6.2f')}  {what}")
+    if parts:
+        out.append(f"  glue, mean over k = 0..{nt - 2}: substitution {sums[0] / (nt - 1):5.2f}   product {sums[1] / (nt - 1):5.2f}   "
+                   f"entry {sums[2] / (nt - 1):5.2f}")
     pre = np.array([np.nanmedian(path[:, k]) == 1 for k in range(nt - 1)])
     el = np.array([med((e1[:, k] - e0[:, k]) * 0.01) for k in range(nt)])
     if pre.any():
