@@ -1358,8 +1358,29 @@ __device__ __forceinline__ void mma_tile16_chain(const T* Ar, const T* Bc, typen
 // past the first stage), so the last stage has no wave reading what another one overwrites: Xs is scratch to the caller afterwards.
 // The caller puts a barrier between the return and its first read of Ts.  G (nullable): hand-over slot that receives the result
 // tile by tile as it becomes final (coherent stores).
-template <typename T, typename F>
-__device__ __forceinline__ void subst_tile(T* Ts, T* Xs, T* G, F after_first) {
+// `stamp` (development builds, AGP_STEP_TRACE: the chain passes its clock; everybody else NoHook): called with 2 behind the first
+// stage's MFMAs, 3 behind after_first, 4 and 5 behind the two barriers, 6 at the end.
+// Until round 13 every stage went through mma_tile16's loop.  Since round 14 (same operands, same LDS addresses, same MFMA order per
+// accumulator -- `a` takes the even k-steps, p1 the odd ones, a += p1 -- and the same barriers; DESIGN.md section 5 "round 14"):
+//   * Every operand is read with a ds_read_b64 of its own (lds_keep_apart below).  Left alone the compiler pairs the reads of two
+//     k-steps into one ds_read2_b64, which serves 16 lanes per LDS cycle and banks modulo 32: with the row stride LDP = 66 doubles
+//     lanes l and l + 8 of a group meet on one bank, and the pair costs 16 LDS cycles where two ds_read_b64 (32 lanes per cycle,
+//     banks modulo 64, conflict-free at this stride) cost 4.  With eight waves reading at once that rate, not the latency, was
+//     most of what a stage waited for.
+//   * The k range of the triangular stages is a compile-time constant per wave: a wave-uniform branch on cj picks the stage's code
+//     for one group of four k-steps (k < 16) or two (k < 32).  A stage issues all its reads, then the MFMAs pair by pair as the
+//     reads return (sched_barriers pin the order; the waits count down), as mma_tile16_chain does.
+//   * The B operands of stages 2 and 3 -- the [L21 | X22] rows of the slot, which nobody writes -- and the wave's own tile of T2
+//     are read under the MFMAs of the stage in front, across its barrier: behind a barrier only the A operand (L1, then U, written by
+//     the other waves) is still to come.
+// a compiler barrier between two LDS reads: the load/store optimiser does not merge reads across it (no instruction is emitted)
+__device__ __forceinline__ void lds_keep_apart() { asm volatile("" ::: "memory"); }
+template <int N>
+struct IntC {
+  static constexpr int value = N;
+};
+template <typename T, typename F, typename S = NoHook>
+__device__ __forceinline__ void subst_tile(T* Ts, T* Xs, T* G, F after_first, S stamp = S()) {
   typedef typename Mfma<T>::acc_t acc_t;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ri = wave & 3, cj = wave >> 2;
   T* rowt = Ts + 16 * ri * LDP;
@@ -1375,23 +1396,111 @@ __device__ __forceinline__ void subst_tile(T* Ts, T* Xs, T* G, F after_first) {
                            __HIP_MEMORY_SCOPE_AGENT);
     }
   };
-  acc_t a;
+  const int lo = (lane & 15) * LDP + (lane >> 4);  // a lane's operand element of k-step 0 (as in mma_tile16); k-step kk: + 4 kk
+  const T *pa = rowt + lo, *pb1 = Xs + 16 * cj * LDP + lo, *pb2 = xlow + lo, *pu = urow + lo;
+  T av[8], bv[8], b2[8], b3[8];
+  acc_t a, p1, t2;
+  auto ld4 = [&](T* v, const T* p, int g) {  // one operand of k-steps 4 g .. 4 g + 3
 #pragma unroll
-  for (int r = 0; r < 4; ++r) a[r] = T(0);
-  a = mma_tile16<T>(rowt, Xs + 16 * cj * LDP, 16 * (cj + 1), a, false, lane);
+    for (int kk = 4 * g; kk < 4 * g + 4; ++kk) {
+      v[kk] = p[kk * 4];
+      lds_keep_apart();
+    }
+  };
+  auto ld4ab = [&](const T* p, const T* q, int g) {  // both, in the order the MFMAs want them
+#pragma unroll
+    for (int kk = 4 * g; kk < 4 * g + 4; ++kk) {
+      av[kk] = p[kk * 4];
+      lds_keep_apart();
+      bv[kk] = q[kk * 4];
+      lds_keep_apart();
+    }
+  };
+  auto clear = [&](acc_t& v) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = T(0);
+  };
+  auto mm2 = [&](T x0, T y0, T x1, T y1) {  // one even and one odd k-step
+    a = Mfma<T>::mma(x0, y0, a);
+    p1 = Mfma<T>::mma(x1, y1, p1);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto join = [&] {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) a[r] += p1[r];
+  };
+  // L1 = T1 X11' ; under its last MFMAs: stage 2's B operand (L21) and own tile of T2 (nobody else touches it before stage 3)
+  auto stage1 = [&](auto ng) {
+    constexpr int NG = decltype(ng)::value;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) ld4ab(pa, pb1, g);
+    __builtin_amdgcn_sched_barrier(0);
+    clear(a);
+    clear(p1);
+    if constexpr (NG == 2) {
+      mm2(av[0], bv[0], av[1], bv[1]);
+      mm2(av[2], bv[2], av[3], bv[3]);
+    }
+    ld4(b2, pb2, 0);
+    ld4(b2, pb2, 1);
+    t2 = acc_load16<T>(own2, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    mm2(av[4 * NG - 4], bv[4 * NG - 4], av[4 * NG - 3], bv[4 * NG - 3]);
+    mm2(av[4 * NG - 2], bv[4 * NG - 2], av[4 * NG - 1], bv[4 * NG - 1]);
+    join();
+  };
+  // U = T2 - L1 L21' ; under its last MFMAs: stage 3's B operand (X22)
+  auto stage2 = [&](auto ng) {
+    constexpr int NG = decltype(ng)::value;
+    ld4(av, pa, 0);
+    ld4(av, pa, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    a = t2;
+    clear(p1);
+    mm2(-av[0], b2[0], -av[1], b2[1]);
+    mm2(-av[2], b2[2], -av[3], b2[3]);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) ld4(b3, pb2 + 32, g);
+    __builtin_amdgcn_sched_barrier(0);
+    mm2(-av[4], b2[4], -av[5], b2[5]);
+    mm2(-av[6], b2[6], -av[7], b2[7]);
+    join();
+  };
+  // L2 = U X22'
+  auto stage3 = [&](auto ng) {
+    constexpr int NG = decltype(ng)::value;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) ld4(av, pu, g);
+    __builtin_amdgcn_sched_barrier(0);
+    clear(a);
+    clear(p1);
+    mm2(av[0], b3[0], av[1], b3[1]);
+    mm2(av[2], b3[2], av[3], b3[3]);
+    if constexpr (NG == 2) {
+      mm2(av[4], b3[4], av[5], b3[5]);
+      mm2(av[6], b3[6], av[7], b3[7]);
+    }
+    join();
+  };
+  if (cj) stage1(IntC<2>{});
+  else stage1(IntC<1>{});
+  stamp(2);
   after_first();  // every wave has read T1
+  stamp(3);
   acc_store16<T>(own1, a, lane);
   emit(16 * cj, a);
   __syncthreads();
-  a = acc_load16<T>(own2, lane);  // own tile of T2: nobody else touches it in this stage
-  a = mma_tile16<T>(rowt, xlow, 32, a, true, lane);
+  stamp(4);
+  if (cj) stage2(IntC<2>{});
+  else stage2(IntC<1>{});
   acc_store16<T>(urow + 16 * cj, a, lane);
   __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 4; ++r) a[r] = T(0);
-  a = mma_tile16<T>(urow, xlow + 32, 16 * (cj + 1), a, false, lane);
+  stamp(5);
+  if (cj) stage3(IntC<2>{});
+  else stage3(IntC<1>{});
   acc_store16<T>(own2, a, lane);
   emit(32 + 16 * cj, a);
+  stamp(6);
 }
 
 // side job of the chain workgroup, stepped by the idle waves 4-7 during the second half of a tile factorisation: look once
@@ -1893,7 +2002,11 @@ struct ProdArgs {
 //   [6144, 6400)  start, [6400, 6656) end of workgroup b of the deferred fallback / row-statistics launch behind it (k_safe_rowstats)
 constexpr int STRACE_SLOTS = 8192, STRACE_XPUB = 600, STRACE_EXT = 1100, STRACE_FILL0 = 1400, STRACE_FILL1 = 1500, STRACE_WG0 = 2048,
               STRACE_WG1 = 4096, STRACE_MAXWG = 2048, STRACE_SAFE0 = 6144, STRACE_SAFE1 = 6400, STRACE_LOOK = 608, STRACE_NEAR = 640,
-              STRACE_GLUE = 1040;  // per block column k of the chain: + k substitution done (S = D - L L' starts), + 16 + k S signalled
+              STRACE_GLUE = 1040,  // per block column k of the chain: + k substitution done (S = D - L L' starts), + 16 + k S signalled
+              STRACE_SUBST = 1600;  // inside X_k out + substitution: + 128 w + 16 q + k, stamped by wave 0 (w = 0: a short tile of the
+                                    // triangular stages) and wave 4 (w = 1: a long tile, and store_d): q = 0 X_k read from LDS, 1 its
+                                    // stores issued, 2 stage-1 MFMAs, 3 after_first (X_k signalled), 4 barrier behind the L1 store,
+                                    // 5 barrier behind the U store (stage 2 done), 6 stage 3 and its stores issued, 7 store_d
 #ifdef AGP_STEP_TRACE
 struct StraceExit {  // stamps the exit of its workgroup, whichever return it leaves by
   unsigned long long* p;
@@ -2046,6 +2159,17 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
   // 64 + 8 (4 R + c), end of factor(k) at 512 + k, the first helper of tile (0, 0) at 1024
 #define PRO_TS(i) \
   if (PRO && trace && tid == 0) trace[i] = wall_clock64()
+#ifdef AGP_STEP_TRACE
+  // (waves 0 and 4 of the chain; the scheduler may move nothing across the clock read)
+#define SUB_TS(q, k)                                                                                   \
+  do {                                                                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+    if (PRO && trace && (tid & 255) == 0 && (k) < 16) trace[STRACE_SUBST + 128 * (tid >> 8) + 16 * (q) + (k)] = wall_clock64(); \
+    __builtin_amdgcn_sched_barrier(0);                                                                 \
+  } while (0)
+#else
+#define SUB_TS(q, k)
+#endif
   if (PRO && helper) {  // one k-slice of S(R, c): no dependencies, one store of the partial tile, done
     const int64_t ntc = nt - c, nn = ntc < PRO_NEAR ? ntc : PRO_NEAR;
     const int kfc = pro.kf[c], kso = pro.ks[c];
@@ -2384,6 +2508,10 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
           const int e = tl + q * CHOL_THREADS;
           xv[q] = bufB[(e >> 6) * LDP + (e & 63)];
         }
+#ifdef AGP_STEP_TRACE
+        if (sizeof(T) == 8) asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7]));  // (the reads are back)
+        SUB_TS(0, k);
+#endif
 #pragma unroll
         for (int q = 0; q < TILE * TILE / CHOL_THREADS; ++q) {
           const int e = tl + q * CHOL_THREADS;
@@ -2391,6 +2519,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
           if (write_x) X[(k0 + (e >> 6)) * ldx + k0 + (e & 63)] = xv[q];
         }
         // (the real X block is only read when the full inverse was requested, and then the identity-row tile (k, k) writes it)
+        SUB_TS(1, k);
       }
       if (k + 1 == nt) {
         if (STORE_DG) {
@@ -2436,14 +2565,19 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       if (SUBST) {
         //   L = T X_k' by block substitution from [[X11, 0], [L21, X22]] (same 40 MFMAs per SIMD as the triangular product below, in
         //   three stages); X_k is published behind the first stage, as below
-        subst_tile<T>(bufC, bufB, HL + ((k + 1) * nt + k) * SLOT, [&] {
+        auto first = [&] {
           if (!late_feed) {
             dag_signal(xready + k * DAG_FS, epoch);
             DAG_TRC(k, 3);
           } else {
             __syncthreads();
           }
-        });
+        };
+        auto sub_ts = [&](int q) {
+          (void)q;
+          SUB_TS(q, k);
+        };
+        subst_tile<T>(bufC, bufB, HL + ((k + 1) * nt + k) * SLOT, first, sub_ts);
       } else {
         const int ri = wave >> 1, cA = (wave & 1) ? 2 : 3, cB = 3 - cA;
         acc_t oa, ob;
@@ -2473,6 +2607,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
       // (deferred feed) D from the idle waves' registers; a late column has both tiles from the blocking fetch above, and what
       // round 7 asked for is dropped
       if (dag_feed_deferred<T>() && !late_feed) pf.store_d();
+      SUB_TS(7, k);
       __syncthreads();
       DAG_TRC(k + 1, 5);
 #ifdef AGP_STEP_TRACE
@@ -2698,6 +2833,7 @@ void k_chol_dag(CholBatch<T> bt, int nb, int64_t fstride, int64_t ld, int64_t ld
 #undef DAG_TR
 #undef DAG_TRC
 #undef PRO_TS
+#undef SUB_TS
 }
 
 // fills the hand-over area with the sentinel (normally rider workgroups of the next k_syrk_tn launch do this; this kernel is the

@@ -10,7 +10,7 @@ last tile elimination, factor(nt - 1), of the same launch ("next" rows: of the l
 chain: how long the tile elimination and the glue behind it took (the glue split into X_k out + substitution | S = D - L L' up to its
 signal | entry of the next elimination, where the library has the STRACE_GLUE stamps) and which way the next column's two feeder tiles came in (prefetched
 under the elimination, or late because the look failed / because a sentinel was seen).  Last, the two feeder tiles of block columns
-2 .. 6 against the look that wants them: when their workgroup started, finished its product, took the eta2 step and parked."""
+2 .. 6 against the look that wants them: when their workgroup started, finished its product, took the eta2 step and parked.  Between the two, where the library has the STRACE_SUBST stamps: what happens inside "X_k out + substitution"."""
 import os
 import sys
 
@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XPUB, EXT, FILL0, FILL1, WG0, WG1, SAFE0, SAFE1 = 600, 1100, 1400, 1500, 2048, 4096, 6144, 6400
 ELIM0, PATH = 528, 560  # per block column k: factor(k) starts ; the path word of column k + 1's feed (PRO_TS, agp_chol.h)
 LOOK, NEAR = 608, 640   # the look under factor(k) ; the near-diagonal tiles of block columns 2 .. 6 (STRACE_LOOK, STRACE_NEAR)
+SUBST = 1600            # inside the substitution: + 128 w + 16 q + k, waves 0 and 4 (STRACE_SUBST)
 GLUE = 1040             # the glue of column k: + k substitution done (S = D - L L' starts), + 16 + k S signalled (STRACE_GLUE)
 
 
@@ -122,6 +123,41 @@ def columns(cur, nt):
     return out
 
 
+SUBST_POINTS = ("X_k read from LDS", "X_k stores issued", "stage 1: MFMAs of L1 = T1 X11'", "after_first (X_k signalled)",
+                "L1 stored + barrier", "stage 2: U = T2 - L1 L21', stored + barrier", "stage 3: L2 = U X22', stores issued", "store_d")
+
+
+def substitution(cur, nt):
+    """inside "X_k out + substitution" (512 + k -> GLUE + k): the stamps of wave 0 (short tiles of the triangular stages) and wave 4
+    (long tiles; one of the four waves that run store_d), STRACE_SUBST + 128 w + 16 q + k.  Per point the median time since the
+    point before it, averaged over the block columns, and the running sum.  The first interval starts at factor(k) done (stamped by
+    wave 0 for both), the last one ends at the barrier in front of S = D - L L' (GLUE + k, wave 0)."""
+    if not np.isfinite(cur[:, SUBST:SUBST + 256]).any():
+        return ["  (no substitution stamps in this dump)"]
+
+    def med(x):
+        x = x[np.isfinite(x)]
+        return float(np.median(x)) if x.size else float("nan")
+
+    out = ["  inside X_k out + substitution, us since the point before, mean over k = 0.." + str(nt - 2) +
+           " of the medians (running sum): wave 0 (short tiles) | wave 4 (long tiles, store_d)"]
+    run = np.zeros(2)
+    prev = [cur[:, 512:512 + nt - 1]] * 2
+    for q, what in enumerate(SUBST_POINTS + ("barrier in front of S = D - L L'",)):
+        cells = []
+        for w in range(2):
+            at = cur[:, GLUE:GLUE + nt - 1] if q == len(SUBST_POINTS) else cur[:, SUBST + 128 * w + 16 * q:SUBST + 128 * w + 16 * q + nt - 1]
+            if not np.isfinite(at).any():  # (a point this library does not stamp: its time goes to the next one)
+                cells.append(f"{'-':>5} ({run[w]:5.2f})")
+                continue
+            d = np.mean([med((at[:, k] - prev[w][:, k]) * 0.01) for k in range(nt - 1)])
+            run[w] += d
+            prev[w] = at
+            cells.append(f"{d:5.2f} ({run[w]:5.2f})")
+        out.append(f"    {what:<44} {cells[0]} | {cells[1]}")
+    return out
+
+
 def tile_slot(R, c):
     """first stamp of matrix tile (R, c): PRO_TS's old region for R, c < 4, STRACE_NEAR for the near tiles of block columns 2 .. 6"""
     if R < 4 and c < 4:
@@ -201,6 +237,7 @@ def table(dumps, last=200, nt=16, ne=17):
         out.append(f"  mean over k {np.mean(d):6.3f}   factor({nt - 1}) - factor(0) {med(f[:, nt - 1] - f[:, 0]) * 0.01:8.2f}")
         out.append(f"  chain start -> factor(0) done {med(f[:, 0] - cur[:, 0]) * 0.01:8.2f}")
         out += columns(cur, nt)
+        out += substitution(cur, nt)
         out += feeders(cur, nt)
         rows += out
     return "\n".join(rows)
