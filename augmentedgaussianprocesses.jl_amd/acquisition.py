@@ -6,13 +6,18 @@ FUNCTIONS"): the other half of Bayesian optimisation next 
     a, dmu, dvar = AGP.acquisition_moments(AGP.PI(best=0.0), mu, var, grad=True)
     Xq, aq = AGP.maximize_acquisition_batch(model, AGP.UCB(2.0), 8, X0, (lo, hi), pending=P)   # q points, greedily, on the device
     a = AGP.acquisition(model, AGP.EI(best=y.max()), X, pending=P)           # alpha with P hallucinated at its predicted mean
+    x, la = AGP.maximize_acquisition(model, AGP.LogEI(best=y.max()), X0, (lo, hi))   # log EI: no plateau far from the incumbent
 
 UCB = s mu + beta sigma, EI = sigma (z Phi(z) + phi(z)), PI = Phi(z) with z = (s (mu - best) - xi) / sigma; s = -1 with minimize=True
-(the objective is minimised; the acquisition function itself is always maximised).  Float64, single-output models, D <= 64,
-SqExponential / Matern32 / Matern52 kernels.  Batches come from hallucinated observations (GP-BUCB, "kriging believer"): pending
-points are conditioned on at their own predicted mean -- the mean stays, the variance shrinks -- and q points are picked greedily.
-Not here: MC q-EI with a joint reparameterised sample, fantasies that move the mean, log-EI (EI underflows to 0 for z below about
--38), Float32, multi-output and sharded models.  No counterpart in the reference.
+(the objective is minimised; the acquisition function itself is always maximised).  EI and PI underflow to 0, with a zero gradient,
+for z below about -38: an ascent that starts there does not move, and the later rounds of a batch, whose pending points shrink sigma,
+are full of such starts.  LogEI = log EI and LogPI = log PI have the same maximisers and are finite with a useful gradient over the
+whole range of z (the continued fraction of the Mills ratio for z <= -3: csrc/agp_acq_log.h); every returned value is then log alpha.
+Float64, single-output models, D <= 64, SqExponential / Matern32 / Matern52 kernels.  Batches come from hallucinated observations
+(GP-BUCB, "kriging believer"): pending points are conditioned on at their own predicted mean -- the mean stays, the variance
+shrinks -- and q points are picked greedily.
+Not here: MC q-EI with a joint reparameterised sample, fantasies that move the mean, Float32, multi-output and sharded models.  No
+counterpart in the reference.
 """
 from __future__ import annotations
 
@@ -27,6 +32,8 @@ from .pathwise import check_maximize_args
 from .predgrad import MAX_D, predgrad_refusal
 
 ACQ_UCB, ACQ_EI, ACQ_PI = 0, 1, 2
+ACQ_LOG = 4  # a flag on EI and PI
+ACQ_LOG_EI, ACQ_LOG_PI = ACQ_LOG | ACQ_EI, ACQ_LOG | ACQ_PI
 
 
 class _Acquisition:
@@ -83,6 +90,22 @@ class PI(_Acquisition):
         return f"PI(best={self.best}, xi={self.xi})"
 
 
+class LogEI(EI):
+    """log EI: the maximiser of EI, finite with a useful gradient where EI has underflowed to 0 (z below about -38)"""
+    kind = ACQ_LOG_EI
+
+    def __repr__(self):
+        return f"LogEI(best={self.best}, xi={self.xi})"
+
+
+class LogPI(PI):
+    """log PI: the maximiser of PI, finite with a useful gradient where PI has underflowed to 0"""
+    kind = ACQ_LOG_PI
+
+    def __repr__(self):
+        return f"LogPI(best={self.best}, xi={self.xi})"
+
+
 def acquisition_refusal(model, latent: int = 0) -> Optional[str]:
     """Why agp_svgp_acquisition / agp_svgp_acq_maximize refuse this model, or None: decided here, before the device is touched."""
     from .movgp import MOVGP
@@ -111,7 +134,7 @@ def _resolve(model, acq, latent, minimize):
     from .vgp import VGP
 
     if not isinstance(acq, _Acquisition):
-        raise TypeError("acq must be UCB(...), EI(...) or PI(...)")
+        raise TypeError("acq must be UCB(...), EI(...), PI(...), LogEI(...) or LogPI(...)")
     acq.check()
     why = acquisition_refusal(model, latent)
     if why is not None:
@@ -218,9 +241,9 @@ def _acquisition_pending(model, d, X, grad, latent, obsdim, pending, pending_noi
 def acquisition_moments(acq, mu, var, *, minimize: bool = False, grad: bool = False, device: Optional[int] = None):
     """the point function alone on given moments (agp_acq_moments): alpha, and with grad=True (alpha, d alpha / d mu, d alpha / d var)
     with d alpha / d var = d alpha / d sigma / (2 sigma).  var <= 0 takes the defined limit, a NaN moment gives NaN.  best is
-    required for EI / PI.  NumPy in gives NumPy out; device tensors in give device tensors out."""
+    required for EI / PI / LogEI / LogPI.  NumPy in gives NumPy out; device tensors in give device tensors out."""
     if not isinstance(acq, _Acquisition):
-        raise TypeError("acq must be UCB(...), EI(...) or PI(...)")
+        raise TypeError("acq must be UCB(...), EI(...), PI(...), LogEI(...) or LogPI(...)")
     acq.check()
     if acq.kind != ACQ_UCB and acq.best is None:
         raise ValueError(f"{type(acq).__name__}: best must be given (there is no model to take an incumbent from)")

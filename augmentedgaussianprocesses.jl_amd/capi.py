@@ -45,6 +45,7 @@ PATHWISE_WS_BYTES = 64 * 1024 * 1024
 MAT_L, MAT_KINV, MAT_KNM, MAT_KAPPA, VEC_KTILDE, VEC_MEAN_F, VEC_VAR_F, VEC_THETA, VEC_C, VEC_GAMMA, VEC_ALPHA = range(11)
 VEC_APRED, MAT_APRED = 11, 12  # the predictor's a = K^-1 mu and A = K^-1 - K^-1 Sigma K^-1 (agp_svgp_get_matrix)
 ACQ_UCB, ACQ_EI, ACQ_PI = 0, 1, 2  # agp_acq_desc.kind
+ACQ_LOG, ACQ_LOG_EI, ACQ_LOG_PI = 4, 5, 6  # AGP_ACQ_LOG is a flag on EI and PI: the kind in logarithms
 ACQ_MAX_PENDING = 64  # AGP_ACQ_MAX_PENDING: n_pending + q
 
 

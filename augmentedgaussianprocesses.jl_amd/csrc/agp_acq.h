@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "agp_acq_log.h"  // acq_log_point: LogEI, LogPI
 #include "agp_cavi.h"
 #include "agp_hyper.h"
 #include "agp_pathwise.h"  // PwAscentBox
@@ -20,15 +21,17 @@ namespace agp {
 
 // agp_acq_desc by value, with the sign of the objective resolved
 struct AcqParams {
-  int kind;            // AGP_ACQ_UCB = 0, AGP_ACQ_EI = 1, AGP_ACQ_PI = 2
+  int kind;            // AGP_ACQ_UCB = 0, AGP_ACQ_EI = 1, AGP_ACQ_PI = 2; AGP_ACQ_LOG_EI = 5, AGP_ACQ_LOG_PI = 6 (agp_acq_log.h)
   double s;            // +1, or -1 with minimize
   double beta, best, xi;
 };
 
 // The point function: alpha and its derivatives in mu and in var = sigma^2 (the table of include/agp_hip.h).  Phi(z) = erfc(-z /
 // sqrt 2) / 2, never 1 + erf: EI lives in the left tail.  var <= 0 takes the defined limit (no 0 / 0), a NaN moment gives NaN.
+// The kinds with the AGP_ACQ_LOG flag go to acq_log_point (agp_acq_log.h); what follows that line is UCB, EI and PI alone.
 __device__ __forceinline__ void acq_point(const AcqParams& p, double mu, double var, double& alpha, double& dmu, double& dvar) {
 #pragma clang fp contract(off)
+  if (p.kind & 4) return acq_log_point(p.kind, p.s, p.best, p.xi, mu, var, alpha, dmu, dvar);
   if (mu != mu || var != var) {
     alpha = dmu = dvar = __builtin_nan("");
     return;

@@ -19,8 +19,8 @@ static agp_status acq_check_desc(agp_ctx* ctx, const char* who, const agp_acq_de
     return AGP_ERR_INVALID;
   };
   if (!d) return invalid("desc must be given");
-  if (d->kind != AGP_ACQ_UCB && d->kind != AGP_ACQ_EI && d->kind != AGP_ACQ_PI)
-    return invalid("unknown kind (AGP_ACQ_UCB, AGP_ACQ_EI or AGP_ACQ_PI)");
+  if (d->kind != AGP_ACQ_UCB && d->kind != AGP_ACQ_EI && d->kind != AGP_ACQ_PI && d->kind != AGP_ACQ_LOG_EI && d->kind != AGP_ACQ_LOG_PI)
+    return invalid("unknown kind (AGP_ACQ_UCB, AGP_ACQ_EI, AGP_ACQ_PI, AGP_ACQ_LOG_EI or AGP_ACQ_LOG_PI)");
   if (!std::isfinite(d->beta) || !std::isfinite(d->best) || !std::isfinite(d->xi)) return invalid("beta, best and xi must be finite");
   if (d->beta < 0.0) return invalid("beta >= 0");
   if (d->xi < 0.0) return invalid("xi >= 0");

@@ -710,7 +710,7 @@ agp_status agp_svgp_predict_f_cov(agp_svgp* h, const void* xt, int64_t ldx, int6
 agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* dmu_out,
                                    void* dvar_out /* nullable */, int64_t ldg);
 
-/* ---- ACQUISITION FUNCTIONS (UCB, EI, PI of the predictive moments, and their multi-start maximiser on the device) ------------------
+/* ---- ACQUISITION FUNCTIONS (UCB, EI, PI, log EI, log PI of the predictive moments, and their multi-start maximiser on the device) ---
  * The other half of Bayesian optimisation next to "PATHWISE SAMPLING": no counterpart in the reference.  AGP_F64 only.  For one latent
  * let mu(x), var(x) be exactly what agp_svgp_predict_f returns (k** + jitter included) and grad mu, grad var what
  * agp_svgp_predict_f_grad returns.  s = +1, or -1 with `minimize` (the OBJECTIVE is then to be minimised; alpha itself is always
@@ -720,11 +720,25 @@ agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int
  *   AGP_ACQ_UCB (beta >= 0)       s mu + beta sigma           s                   beta
  *   AGP_ACQ_EI  (best, xi >= 0)   sigma (z Phi(z) + phi(z))   s Phi(z)            phi(z)
  *   AGP_ACQ_PI  (best, xi >= 0)   Phi(z)                      s phi(z) / sigma    -z phi(z) / sigma
+ *   AGP_ACQ_LOG_EI  (best, xi >= 0)   log sigma + log h(z)    s Phi(z) / (sigma h(z))     phi(z) / (sigma h(z))       h(z) = phi(z) + z Phi(z)
+ *   AGP_ACQ_LOG_PI  (best, xi >= 0)   log Phi(z)              s phi(z) / (sigma Phi(z))   -z phi(z) / (sigma Phi(z))
  *   grad alpha = d alpha / d mu  grad mu  +  d alpha / d sigma  grad var / (2 sigma)
- * EI is evaluated by this formula, not in logarithms: it underflows to 0, with a zero gradient, for z below about -38 (log-EI is out
- * of scope).  var <= 0 takes the limit, it is not left to 0 / 0: UCB alpha = s mu; EI alpha = max(s (mu - best) - xi, 0) with
- * d alpha / d mu = s where that is positive and 0 otherwise; PI alpha = 1 where s (mu - best) - xi > 0, else 0, with d alpha / d mu = 0;
- * in all three the var term of the gradient is 0.  A NaN moment gives a NaN alpha (and NaN derivatives).
+ * AGP_ACQ_EI and AGP_ACQ_PI are evaluated by their formulas, not in logarithms: they underflow to 0, with a zero gradient, for z below
+ * about -38, and an ascent that starts on that plateau does not move.  AGP_ACQ_LOG_EI = AGP_ACQ_LOG | AGP_ACQ_EI and AGP_ACQ_LOG_PI =
+ * AGP_ACQ_LOG | AGP_ACQ_PI are their logarithms: the same maximisers, finite with a useful gradient as far as z^2 / 2 is a double, and
+ * accepted wherever a kind is (alpha_out, a_out, best_a and ab_out then hold log alpha).  They are accurate to a few units of the
+ * last place over the whole range of z: for z > -3 by the expressions of the table (log Phi(z) = log1p(-Phi(-z)) for z > 0), for
+ * z <= -3 through Laplace's continued fraction of the Mills ratio with t = -z, cut after the partial numerator 60 (t < 5), 32 (t < 12)
+ * or 12 (beyond), where the cut stays below a quarter of a unit of c's last place,
+ *   c = 1 / (t + 2 / (t + 3 / (t + ...))),  R = Phi / phi = 1 / (t + c),  h / phi = c R,  log phi = -z^2 / 2 - log sqrt(2 pi)
+ * so that log h = log phi + log c + log R, log Phi = log phi + log R, Phi / h = 1 / c, phi / h = 1 / (c R), phi / Phi = t + c, without a
+ * cancellation.  alpha = -inf with finite moments and var > 0 only where the exact value lies below -DBL_MAX.  The flag alone
+ * (4, which is also AGP_ACQ_LOG | AGP_ACQ_UCB), 3 and 7 stay unknown kinds.
+ * var <= 0 takes the limit, it is not left to 0 / 0; with imp = s (mu - best) - xi: UCB alpha = s mu; EI alpha = max(imp, 0) with
+ * d alpha / d mu = s where imp > 0 and 0 otherwise; PI alpha = 1 where imp > 0, else 0, with d alpha / d mu = 0; LOG_EI alpha = log imp
+ * with d alpha / d mu = s / imp where imp > 0, otherwise alpha = -inf with d alpha / d mu = 0; LOG_PI alpha = 0 where imp > 0, else
+ * -inf, with d alpha / d mu = 0; in all five the var term of the gradient is 0.  A NaN moment gives a NaN alpha (and NaN derivatives).
+ * -inf is an ordinary value for the best-start rule below (it loses to every finite value); a NaN still never wins.
  *
  * agp_acq_moments  the point function alone on n given moments, device double[n] each: alpha_out, dalpha_dmu (nullable) and
  *   dalpha_dvar (nullable) = d alpha / d sigma / (2 sigma).  n = 0 is a successful no-op.  AGP_ERR_INVALID with a message: ctx or desc
@@ -813,10 +827,10 @@ agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int
  * Pending coordinates are device data and are not validated (the kernel functions clamp a squared distance that is not a positive
  * number to 0, so a NaN coordinate does not reliably show as a NaN value).
  *
- * Out of scope: MC q-EI with a joint reparameterised sample, fantasies that move the mean, log-EI, Float32, multi-output and sharded
+ * Out of scope: MC q-EI with a joint reparameterised sample, fantasies that move the mean, Float32, multi-output and sharded
  * handles, a single-launch ascent. */
 #define AGP_ACQ_MAX_PENDING 64 /* n_pending + q; an interface limit, not a tuned value */
-enum { AGP_ACQ_UCB = 0, AGP_ACQ_EI = 1, AGP_ACQ_PI = 2 };
+enum { AGP_ACQ_UCB = 0, AGP_ACQ_EI = 1, AGP_ACQ_PI = 2, AGP_ACQ_LOG = 4 /* a flag on EI and PI: */, AGP_ACQ_LOG_EI = 5, AGP_ACQ_LOG_PI = 6 };
 typedef struct {
   int32_t kind;     /* AGP_ACQ_* */
   int32_t minimize; /* 0: the objective is maximised, 1: minimised (s = -1) */

@@ -27,7 +27,7 @@
 #   log_predictive_density(model, X, y) (no counterpart: the held-out log-likelihood / NLPD)           -> agp_svgp_lpd_stream, agp_log_predictive
 #   _predict_f / predict_y / proba_y                          src/training/predictions.jl:25-92,178-247 -> agp_svgp_predict_f / _predict_y / _proba_y
 #   predict_f_grad(model, X_test) (no counterpart: d mu / d x*, d sigma^2 / d x* of predict_f)          -> agp_svgp_predict_f_grad
-#   acquisition / maximize_acquisition(model, UCB | EI | PI, ...) (no counterpart: Bayesian optimisation) -> agp_svgp_acquisition, agp_svgp_acq_maximize
+#   acquisition / maximize_acquisition(model, UCB | EI | PI | LogEI | LogPI, ...) (no counterpart: Bayesian optimisation) -> agp_svgp_acquisition, agp_svgp_acq_maximize
 #   acquisition_pending / maximize_acquisition_batch(model, ...; pending) (no counterpart: batch acquisition by hallucinated
 #     observations)                                                                  -> agp_svgp_acquisition_pending, agp_svgp_acq_maximize_batch
 #   init_state                                                src/training/states.jl:1-9               -> agp_svgp_init_state
@@ -1531,8 +1531,9 @@ function pathwise_features(hm::HipModel, k::Kernel, D::Integer, n_features::Inte
 end
 
 # ---- acquisition functions (include/agp_hip.h, "ACQUISITION FUNCTIONS"; no counterpart in the reference) ------------------------------
-# UCB(beta), EI(best, xi), PI(best, xi) of the moments of predict_f, Float64 single-output models; minimize=true: the objective is
-# minimised (the acquisition value itself is always maximised).  The struct mirrors agp_acq_desc field by field.
+# UCB(beta), EI(best, xi), PI(best, xi), LogEI(best, xi), LogPI(best, xi) of the moments of predict_f, Float64 single-output models;
+# minimize=true: the objective is minimised (the acquisition value itself is always maximised).  The struct mirrors agp_acq_desc field
+# by field.
 # Never run: there is no Julia toolchain in the test environment.
 struct AcqDesc
     kind::Int32
@@ -1544,6 +1545,9 @@ end
 UCB(beta::Real=2.0; minimize::Bool=false) = AcqDesc(0, minimize ? 1 : 0, beta, 0.0, 0.0)
 EI(best::Real, xi::Real=0.0; minimize::Bool=false) = AcqDesc(1, minimize ? 1 : 0, 0.0, best, xi)
 PI(best::Real, xi::Real=0.0; minimize::Bool=false) = AcqDesc(2, minimize ? 1 : 0, 0.0, best, xi)
+# the same two in logarithms (AGP_ACQ_LOG = 4 set on the kind): finite with a useful gradient where EI and PI have underflowed to 0
+LogEI(best::Real, xi::Real=0.0; minimize::Bool=false) = AcqDesc(5, minimize ? 1 : 0, 0.0, best, xi)
+LogPI(best::Real, xi::Real=0.0; minimize::Bool=false) = AcqDesc(6, minimize ? 1 : 0, 0.0, best, xi)
 # acquisition(hm, acq, X; grad=false, latent=1): alpha at the rows of X (n_t), with grad=true (alpha, G n_t x D)
 function acquisition(hm::HipModel{Float64}, acq::AcqDesc, X::AbstractMatrix; grad::Bool=false, latent::Integer=1, obsdim::Int=1)
     ensure_handle!(hm, max(hm.maxbatch, 1))

@@ -2,6 +2,7 @@
 """The on-device acquisition maximiser (agp_svgp_acq_maximize) against the loop a user writes without it, on one GPU; one JSON line.
 
     python tools/bench_acq.py [--m 1024] [--D 32] [--starts 1024] [--steps 100] [--warmup 2] [--reps 7]
+                                [--kind ei|pi|logei|logpi] [--incumbent-sds 0]
 
 SqExponential + Gaussian SVGP, 20000 points U[0,1]^D, 10 AnalyticSVI(m) steps first so that the posterior is not the prior; expected
 improvement over the largest predicted mean at the starts, box [0, 1]^D, lr 0.02.  In ONE process, alternating:
@@ -12,7 +13,9 @@ improvement over the largest predicted mean at the starts, box [0, 1]^D, lr 0.02
 every call between two device events.  Reported: the medians and spreads per call, per step, their ratio, the largest difference
 of the two final alpha vectors (the loops are the same iteration), and for the device call the host's time to ENQUEUE a step (the
 call returns before the device is done) next to the device's time per step: their quotient is the share of a step that the host
-needs for its four launches -- at 1 the ascent is bound by launches, and a single-launch variant would have something to gain."""
+needs for its four launches -- at 1 the ascent is bound by launches, and a single-launch variant would have something to gain.
+--kind picks the acquisition function of both loops (ei by default); --incumbent-sds puts the incumbent that many prior standard
+deviations above the largest mean at the starts, which sends every start down the left tail (the log kinds' continued fraction)."""
 import argparse
 import ctypes as C
 import json
@@ -43,6 +46,8 @@ def main():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--reps", type=int, default=7)
+    p.add_argument("--kind", choices=("ei", "pi", "logei", "logpi"), default="ei")
+    p.add_argument("--incumbent-sds", type=float, default=0.0)
     a = p.parse_args()
     import torch
 
@@ -71,11 +76,12 @@ def main():
     mu, var = (torch.empty(R, dtype=torch.float64, device=dev) for _ in range(2))
     dmu, dvar = (torch.empty(R, D, dtype=torch.float64, device=dev) for _ in range(2))
     model._chk(L.agp_svgp_predict_f(h, ptr(X0), D, R, ptr(mu), ptr(var)))
-    best, xi, lr, b1, b2, eps = float(mu.max()), 0.01, 0.02, 0.9, 0.999, 1e-8
+    best, xi, lr, b1, b2, eps = float(mu.max()) + a.incumbent_sds * math.sqrt(float(k.variance)), 0.01, 0.02, 0.9, 0.999, 1e-8
     lo, hi, lrv = np.zeros(D), np.ones(D), np.full(D, lr)
     as_p = lambda v: v.ctypes.data_as(C.POINTER(C.c_double))
     opts = capi.PwAscentOpts(T, 0, 0, b1, b2, eps, as_p(lo), as_p(hi), as_p(lrv))
-    desc = capi.AcqDesc(capi.ACQ_EI, 0, 0.0, best, xi)
+    code = {"ei": capi.ACQ_EI, "pi": capi.ACQ_PI, "logei": capi.ACQ_LOG_EI, "logpi": capi.ACQ_LOG_PI}[a.kind]
+    desc = capi.AcqDesc(code, 0, 0.0, best, xi)
     Xo, Ao = torch.empty(R, D, dtype=torch.float64, device=dev), torch.empty(R, dtype=torch.float64, device=dev)
     enqueue = []
 
@@ -89,7 +95,15 @@ def main():
         sg = torch.sqrt(var)
         z = (mu - best - xi) / sg
         Phi, phi = 0.5 * torch.erfc(-z / math.sqrt(2.0)), torch.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi)
-        return sg * (z * Phi + phi), Phi, phi / (2.0 * sg)
+        if a.kind == "ei":
+            return sg * (z * Phi + phi), Phi, phi / (2.0 * sg)
+        if a.kind == "pi":
+            return Phi, phi / sg, -z * phi / (2.0 * var)
+        # the log kinds by the direct expressions in torch (the kindest form of the host loop; they hold down to z of about -26)
+        if a.kind == "logei":
+            hz = phi + z * Phi
+            return torch.log(sg) + torch.log(hz), Phi / (sg * hz), phi / (2.0 * var * hz)
+        return torch.log(Phi), phi / (sg * Phi), -z * phi / (2.0 * var * Phi)
 
     host_out = {}
 
@@ -124,7 +138,10 @@ def main():
     for _ in range(a.reps):
         for t, fn in zip(ts, fns):
             t.append(timed(fn))
-    row = {"m": m, "D": D, "starts": R, "steps": T, "acquisition": "EI", "device": stats(ts[0]), "host_loop": stats(ts[1])}
+    row = {"m": m, "D": D, "starts": R, "steps": T, "acquisition": {"ei": "EI", "pi": "PI", "logei": "LogEI", "logpi": "LogPI"}[a.kind],
+           "device": stats(ts[0]), "host_loop": stats(ts[1])}
+    if a.incumbent_sds:
+        row["incumbent_sds"] = a.incumbent_sds
     dm_, hm_ = row["device"]["median_ms"], row["host_loop"]["median_ms"]
     row["device_us_per_step"] = round(1e3 * dm_ / (T + 1), 2)  # (T steps and the pass that evaluates the final iterate)
     row["host_loop_us_per_step"] = round(1e3 * hm_ / (T + 1), 2)
