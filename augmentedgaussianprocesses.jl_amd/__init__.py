@@ -63,8 +63,8 @@ from .mcgp import MCGP, GibbsSampling, sample, sample_local  # noqa: F401
 from .nvi import gauss_hermite_rule, mc_expectations, mc_normals, quad_expectations  # noqa: F401
 from .lpd import log_predictive_density, log_predictive_moments  # noqa: F401
 from .predgrad import predict_f_grad  # noqa: F401
-from .acquisition import (EI, PI, UCB, LogEI, LogPI, acquisition, acquisition_moments, maximize_acquisition,  # noqa: F401
-                          maximize_acquisition_batch)
+from .acquisition import (EI, PI, UCB, LogEI, LogPI, acquisition, acquisition_joint, acquisition_moments,  # noqa: F401
+                          maximize_acquisition, maximize_acquisition_batch, maximize_acquisition_joint)
 from .pathwise import PathwiseSamples, pathwise_features, sample_paths  # noqa: F401
 from .capi import AGPError  # noqa: F401
 from .persistence import load_trained_model, save_trained_model  # noqa: F401

@@ -6,6 +6,8 @@ FUNCTIONS"): the other half of Bayesian optimisation next 
     a, dmu, dvar = AGP.acquisition_moments(AGP.PI(best=0.0), mu, var, grad=True)
     Xq, aq = AGP.maximize_acquisition_batch(model, AGP.UCB(2.0), 8, X0, (lo, hi), pending=P)   # q points, greedily, on the device
     a = AGP.acquisition(model, AGP.EI(best=y.max()), X, pending=P)           # alpha with P hallucinated at its predicted mean
+    Xq, aq = AGP.maximize_acquisition_joint(model, AGP.EI(best=y.max()), X0q, (lo, hi))   # q points together: Monte-Carlo q-EI
+    a = AGP.acquisition_joint(model, AGP.UCB(2.0), Xq, samples=256, pending=P)            # q-UCB of the tuples (n, q, D)
     x, la = AGP.maximize_acquisition(model, AGP.LogEI(best=y.max()), X0, (lo, hi))   # log EI: no plateau far from the incumbent
 
 UCB = s mu + beta sigma, EI = sigma (z Phi(z) + phi(z)), PI = Phi(z) with z = (s (mu - best) - xi) / sigma; s = -1 with minimize=True
@@ -15,8 +17,11 @@ are full of such starts.  LogEI = log EI and LogPI = log PI have the same maximi
 whole range of z (the continued fraction of the Mills ratio for z <= -3: csrc/agp_acq_log.h); every returned value is then log alpha.
 Float64, single-output models, D <= 64, SqExponential / Matern32 / Matern52 kernels.  Batches come from hallucinated observations
 (GP-BUCB, "kriging believer"): pending points are conditioned on at their own predicted mean -- the mean stays, the variance
-shrinks -- and q points are picked greedily.
-Not here: MC q-EI with a joint reparameterised sample, fantasies that move the mean, Float32, multi-output and sharded models.  No
+shrinks -- and q points are picked greedily.  Joint batches are the Monte-Carlo q-EI and q-UCB of q points under their posterior
+correlation, with a joint reparameterised sample f_s = mu + L eps_s over fixed base samples (sample-average approximation) and the
+sub-gradient through the winning member: `acquisition_joint`, `maximize_acquisition_joint`; there a pending point is a member of the
+joint sample, not a hallucinated observation, and a greedy batch is the natural set of starts.
+Not here: the joint PI and the joint log kinds, fantasies that move the mean, Float32, multi-output and sharded models.  No
 counterpart in the reference.
 """
 from __future__ import annotations
@@ -353,6 +358,148 @@ def maximize_acquisition_batch(model, acq, q, X0, bounds, *, pending=None, pendi
     model._chk(L.agp_ctx_sync(model._ctx))
     model._chk(L.agp_svgp_check_status(h))
     out = (xb, ab, ib) if full else (xb, ab)
+    return out if on_device else tuple(t.cpu().numpy() for t in out)
+
+
+JOINT_STREAM = 3  # the Philox stream of the default base samples: agp_mc_normals(ctx, seed, t=0, stream=3, S, q + n)
+
+
+def _resolve_joint(who, model, acq, latent, minimize):
+    """_resolve, after the kinds that have no joint form are refused by name"""
+    if isinstance(acq, _Acquisition) and acq.kind not in (ACQ_UCB, ACQ_EI):
+        raise NotImplementedError(f"{who}: {type(acq).__name__} has no joint form here (the joint PI has a zero gradient almost "
+                                  f"everywhere, the log kinds need a smoothed maximum): EI(...) or UCB(...)")
+    if not isinstance(acq, _Acquisition):
+        raise TypeError("acq must be EI(...) or UCB(...)")
+    return _resolve(model, acq, latent, minimize)
+
+
+def _check_joint(who, q, D, pending, samples, seed, base_samples):
+    """(n_pending, S): the argument checks of a joint batch, on the host; base_samples is None or (S, q + n)"""
+    n = 0
+    if pending is not None:
+        shape = tuple(pending.shape) if hasattr(pending, "shape") else np.shape(pending)
+        if len(shape) != 2 or shape[1] != D:
+            raise ValueError(f"{who}: pending must be (n, {D}) (got {tuple(shape)})")
+        n = int(shape[0])
+    if q < 1:
+        raise ValueError(f"{who}: a tuple must hold at least one point (got q = {q})")
+    if q + n > capi.ACQ_JOINT_MAX_Q:
+        raise ValueError(f"{who}: the batch and the pending points together must not exceed {capi.ACQ_JOINT_MAX_Q} (got {q} + {n})")
+    if base_samples is not None:
+        shape = tuple(base_samples.shape) if hasattr(base_samples, "shape") else np.shape(base_samples)
+        if len(shape) != 2 or shape[1] != q + n:
+            raise ValueError(f"{who}: base_samples must be (S, {q + n}) (got {tuple(shape)})")
+        S = int(shape[0])
+    else:
+        if not isinstance(samples, (int, np.integer)) or isinstance(samples, bool):
+            raise ValueError(f"{who}: samples must be an integer (got {samples})")
+        if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"{who}: seed must be an integer in [0, 2^64) (got {seed})")
+        S = int(samples)
+    if not 1 <= S <= capi.ACQ_JOINT_MAX_S:
+        raise ValueError(f"{who}: the number of samples must lie in [1, {capi.ACQ_JOINT_MAX_S}] (got {S})")
+    return n, S
+
+
+def _base_samples(model, S, K, seed, base_samples):
+    """the table (S, K) on the model's device: the caller's, or the draws of (seed, t = 0, stream 3)"""
+    import torch
+
+    dev = model._dev()
+    if base_samples is not None:
+        return torch.as_tensor(base_samples, dtype=torch.float64).to(dev).reshape(S, K).contiguous()
+    E = torch.empty(S, K, dtype=torch.float64, device=dev)
+    model._chk(capi.lib().agp_mc_normals(model._ctx, int(seed), 0, JOINT_STREAM, S, K, C.c_void_p(E.data_ptr())))
+    return E
+
+
+def acquisition_joint(model, acq, Xq, *, samples: int = 256, seed: int = 0, base_samples=None, grad: bool = False, pending=None,
+                      latent: int = 0, minimize: bool = False):
+    """The joint Monte-Carlo criterion of tuples of q points (agp_svgp_acquisition_joint): q-EI for EI(...), q-UCB for UCB(...).  Xq is
+    (n, q, D) or (q, D); returned is alpha (n,) or a scalar, and with grad=True also the sub-gradient through each sample's winning
+    member, (n, q, D) or (q, D).  f_s = mu + L eps_s with L the Cholesky factor of the posterior covariance of the q points and of
+    `pending` (None or (n_p, D): members of the joint sample that stay where they are, BoTorch's X_pending -- not hallucinated
+    observations); q + n_p <= 16.  The base samples are `base_samples` (S, q + n_p), or the table of agp_mc_normals(seed, t=0,
+    stream=3, samples, q + n_p); 1 <= S <= 4096.  PI, LogEI and LogPI have no joint form here and raise NotImplementedError, as the
+    model classes that `acquisition` refuses do.  Every argument is checked on the host first."""
+    who = "acquisition_joint"
+    if not isinstance(grad, bool):
+        raise TypeError(f"{who}: grad is a bool")
+    model, d = _resolve_joint(who, model, acq, latent, minimize)
+    shape = tuple(Xq.shape) if hasattr(Xq, "shape") else np.shape(Xq)
+    single = len(shape) == 2
+    if single:
+        shape = (1,) + shape
+    if len(shape) != 3 or shape[2] != model.D:
+        raise ValueError(f"{who}: Xq must be (n, q, {model.D}) or (q, {model.D}) (got {tuple(shape)})")
+    nsets, q, D = (int(v) for v in shape)
+    n, S = _check_joint(who, q, D, pending, samples, seed, base_samples)
+    import torch
+
+    on_device = isinstance(Xq, torch.Tensor) and Xq.is_cuda
+    dev = model._dev()
+    Xd = torch.as_tensor(Xq, dtype=torch.float64).to(dev).reshape(nsets * q, D).contiguous()
+    Pd = torch.as_tensor(pending, dtype=torch.float64).to(dev).reshape(n, D).contiguous() if n else None
+    h = model._ensure_handle(max(model._max_batch, 1))
+    E = _base_samples(model, S, q + n, seed, base_samples)
+    a = torch.empty(nsets, dtype=torch.float64, device=dev)
+    G = torch.empty(nsets * q, D, dtype=torch.float64, device=dev) if grad else None
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    L = capi.lib()
+    model._chk(L.agp_svgp_acquisition_joint(h, int(latent), C.byref(d), ptr(Pd) if n else None, D, n, q, ptr(Xd), D, nsets, ptr(E), q + n,
+                                            S, ptr(a), ptr(G) if grad else None, D))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    model._chk(L.agp_svgp_check_status(h))
+    a = a[0] if single else a
+    if grad:
+        G = G.reshape(q, D) if single else G.reshape(nsets, q, D)
+    out = (a, G) if grad else (a,)
+    if not on_device:
+        out = tuple(t.cpu().numpy() for t in out)
+    return out if grad else out[0]
+
+
+def maximize_acquisition_joint(model, acq, X0, bounds, *, samples: int = 256, seed: int = 0, base_samples=None, pending=None,
+                               steps: int = 100, lr=None, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, latent: int = 0,
+                               minimize: bool = False, full: bool = False):
+    """multi-start ADAM ascent of the joint criterion of acquisition_joint over all q points of a tuple together, on the device
+    without a host synchronisation between steps (agp_svgp_acq_maximize_joint).  X0 is (R, q, D): a start is a q-tuple (the rows of a
+    greedy batch of maximize_acquisition_batch are a natural one); bounds, steps, lr, the recurrence, the clipping and the best-start
+    rule are those of maximize_acquisition, per coordinate.  The same base samples serve every start and every step.  Returned is the
+    FINAL tuple of the best start, (X_best (q, D), a_best), and with full=True (X_best, a_best, idx, X (R, q, D), A (R,)).  `pending`
+    members stay where they are and are not returned.  Every argument is checked on the host first."""
+    who = "maximize_acquisition_joint"
+    model, d = _resolve_joint(who, model, acq, latent, minimize)
+    shape = tuple(X0.shape) if hasattr(X0, "shape") else np.shape(X0)
+    if len(shape) != 3 or shape[2] != model.D:
+        raise ValueError(f"{who}: X0 must be (R, q, {model.D}) (got {tuple(shape)})")
+    R, q, D = (int(v) for v in shape)
+    n, S = _check_joint(who, q, D, pending, samples, seed, base_samples)
+    lo, hi, lrv, _, _ = check_maximize_args(1, D, model.n_latent, (max(R, 0) * q, D), bounds, steps, lr, beta1, beta2, eps, latent)
+    import torch
+
+    on_device = isinstance(X0, torch.Tensor) and X0.is_cuda
+    dev = model._dev()
+    Xd = torch.as_tensor(X0, dtype=torch.float64).to(dev).reshape(R * q, D).contiguous()
+    Pd = torch.as_tensor(pending, dtype=torch.float64).to(dev).reshape(n, D).contiguous() if n else None
+    h = model._ensure_handle(max(model._max_batch, 1))
+    E = _base_samples(model, S, q + n, seed, base_samples)
+    X = torch.empty(R * q, D, dtype=torch.float64, device=dev)
+    A = torch.empty(R, dtype=torch.float64, device=dev)
+    xb = torch.empty(q, D, dtype=torch.float64, device=dev)
+    ab = torch.empty((), dtype=torch.float64, device=dev)
+    ib = torch.empty((), dtype=torch.int64, device=dev)
+    as_p = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    opts = capi.PwAscentOpts(int(steps), 0, 0, float(beta1), float(beta2), float(eps), as_p(lo), as_p(hi), as_p(lrv))
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    L = capi.lib()
+    model._chk(L.agp_svgp_acq_maximize_joint(h, int(latent), C.byref(d), ptr(Pd) if n else None, D, n, q, ptr(Xd), D, R, ptr(E), q + n, S,
+                                             C.byref(opts), ptr(X) if full else None, D, ptr(A) if full else None, ptr(xb), D, ptr(ab),
+                                             ptr(ib)))
+    model._chk(L.agp_ctx_sync(model._ctx))
+    model._chk(L.agp_svgp_check_status(h))
+    out = (xb, ab, ib, X.reshape(R, q, D), A) if full else (xb, ab)
     return out if on_device else tuple(t.cpu().numpy() for t in out)
 
 

@@ -47,6 +47,8 @@ VEC_APRED, MAT_APRED = 11, 12  # the predictor's a = K^-1 mu and A = K^-1 - K^-1
 ACQ_UCB, ACQ_EI, ACQ_PI = 0, 1, 2  # agp_acq_desc.kind
 ACQ_LOG, ACQ_LOG_EI, ACQ_LOG_PI = 4, 5, 6  # AGP_ACQ_LOG is a flag on EI and PI: the kind in logarithms
 ACQ_MAX_PENDING = 64  # AGP_ACQ_MAX_PENDING: n_pending + q
+ACQ_JOINT_MAX_Q = 16  # AGP_ACQ_JOINT_MAX_Q: q + n_pending of a joint batch
+ACQ_JOINT_MAX_S = 4096  # the base samples of a joint batch
 
 
 class KernelDesc(C.Structure):
@@ -189,6 +191,10 @@ SYMBOLS = {
     "agp_svgp_acquisition_pending": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _DBL, _VP, _I64, _I64, _VP, _VP, _I64]),
     "agp_svgp_acq_maximize_batch": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _DBL, _I64, _VP, _I64, _I64,
                                            C.POINTER(PwAscentOpts), _VP, _I64, _VP, _VP]),
+    "agp_svgp_acquisition_joint": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP,
+                                          _VP, _I64]),
+    "agp_svgp_acq_maximize_joint": (_I32, [_VP, _I32, C.POINTER(AcqDesc), _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _I64, _I64,
+                                           C.POINTER(PwAscentOpts), _VP, _I64, _VP, _VP, _I64, _VP, _VP]),
     "agp_svgp_predict_y": (_I32, [_VP, _VP, _I64, _I64, _VP]),
     "agp_svgp_proba_y": (_I32, [_VP, _VP, _I64, _I64, _PDBL, _PDBL, _I32, _VP, _VP]),
     "agp_nearest_center": (_I32, [_VP, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _VP]),

@@ -37,6 +37,7 @@
 #include "agp_svgp_base.h"
 #include "agp_pathwise_host.h"
 #include "agp_acq_host.h"
+#include "agp_acq_joint_host.h"
 template <typename T>
 struct Svgp : SvgpBase {
   struct Latent {
@@ -2533,8 +2534,11 @@ struct Svgp : SvgpBase {
     HIPCHK(ctx, hipMemcpyAsync(words, info_dev, sizeof(words), hipMemcpyDeviceToHost, st()));
     int32_t acq_bad = 0;  // a bordering pivot of the pending points that was not positive and finite (agp_acq_batch.h)
     if (acqb.bad) HIPCHK(ctx, hipMemcpyAsync(&acq_bad, acqb.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
+    int32_t acqj_bad = 0;  // a Cholesky pivot of a joint batch's covariance that was not positive and finite (agp_acq_joint.h)
+    if (acqj.bad) HIPCHK(ctx, hipMemcpyAsync(&acqj_bad, acqj.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
     HIPCHK(ctx, hipStreamSynchronize(st()));
     if (acq_bad != 0) HIPCHK(ctx, hipMemsetAsync(acqb.bad, 0, sizeof(int32_t), st()));
+    if (acqj_bad != 0) HIPCHK(ctx, hipMemsetAsync(acqj.bad, 0, sizeof(int32_t), st()));
     const int32_t info = words[0], infoK = words[1], orderK = words[3];
     const int flags = (int)words[2];
     dag_retry_check(ctx);  // steps the in-stream fallback had to re-run: warn once, stop using the task graph
@@ -2605,6 +2609,11 @@ struct Svgp : SvgpBase {
     if (acq_bad != 0) {  // (last: whatever stands above made the predictor it was computed from)
       ctx->err = "PosDefException: the covariance of the pending points (agp_svgp_acquisition_pending, agp_svgp_acq_maximize_batch) is "
                  "not positive definite: a bordering pivot c was not positive and finite";
+      return AGP_ERR_NOT_POSDEF;
+    }
+    if (acqj_bad != 0) {
+      ctx->err = "PosDefException: the joint covariance of a batch (agp_svgp_acquisition_joint, agp_svgp_acq_maximize_joint) is not "
+                 "positive definite: a Cholesky pivot was not positive and finite";
       return AGP_ERR_NOT_POSDEF;
     }
     return AGP_OK;
@@ -3628,6 +3637,155 @@ struct Svgp : SvgpBase {
           AGPCHK(acqb.rescale(ctx, m + np + 1, D, (const double*)g.scales));
         }
       }
+    }
+    return AGP_OK;
+  }
+  // ---- joint batches ("ACQUISITION FUNCTIONS", paragraph "Joint batches"; agp_acq_joint.h, agp_acq_joint_host.h) -----
+  // A set is q optimised points and the n pending ones.  Per chunk of floor(4096 / q) sets and pass: K*m and W of the chunk's points
+  // (the two launches of acq_pass), k_acqj_cov, k_acqj_set, and with the gradient k_acqj_weights, k_acq_contract on the weight rows
+  // and one finishing kernel: seven launches, nothing waits for the stream.  K*m, W and the record of the pending points are formed
+  // once per call, in workspaces of the call's own.
+  AcqJointWs acqj;
+  agp_status acqj_begin(Latent& g, const AcqPred& pr, const void* xp, int64_t ldp, int64_t n) {
+    if constexpr (std::is_same<T, double>::value) {
+      if (n == 0) return AGP_OK;
+      (void)launch_kernelmatrix<T>(ctx, st(), (const T*)xp, ldp, (const int64_t*)nullptr, n, pr.Z, D, pr.m, D, (const T*)g.scales, g.k.kind,
+                                   kvar(g), acqj.Kp, pr.ld, rup64(n), pr.mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, pr.Zsc, pr.zn);
+      LAUNCHCHK(ctx);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, acqj.Kp, pr.ld, pr.A, pr.ld, rup64(n), pr.mp, pr.mp, 0, acqj.Wp, pr.ld, nullptr, 0, nullptr,
+                                    nullptr, nullptr, 0)));
+      hipLaunchKernelGGL(k_acqj_cov, dim3(1), dim3(AJ_THREADS), 0, st(), 0, (int)n, (const double*)nullptr, (int64_t)0, (const double*)xp,
+                         ldp, (const double*)nullptr, (const double*)nullptr, (const double*)acqj.Kp, (const double*)acqj.Wp, pr.ld, pr.m,
+                         pr.a, (int)D, (const double*)g.scales, g.k.kind, (double)kvar(g), g.k.variance + jitter, (const double*)nullptr,
+                         acqj.pend);
+      LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  }
+  // alpha (and, with grad, the groups' sums in pg_part and the point-to-point term in acqj.cross) of ns sets whose np = ns q points are
+  // the rows of x
+  agp_status acqj_pass(Latent& g, const AcqPred& pr, const AcqParams& p, const double* x, int64_t ldx, const void* xp, int64_t ldp,
+                       int64_t n, int64_t q, int64_t ns, const void* eps, int64_t lde, int64_t S, bool grad, double* alpha, int* ng) {
+    if constexpr (std::is_same<T, double>::value) {
+      const int64_t np = ns * q;
+      (void)launch_kernelmatrix<T>(ctx, st(), x, ldx, (const int64_t*)nullptr, np, pr.Z, D, pr.m, D, (const T*)g.scales, g.k.kind, kvar(g),
+                                   pr.Kstar, pr.ld, rup64(np), pr.mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, pr.Zsc, pr.zn);
+      LAUNCHCHK(ctx);
+      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, pr.Kstar, pr.ld, pr.A, pr.ld, rup64(np), pr.mp, pr.mp, 0, pr.W, pr.ld, nullptr, 0, nullptr,
+                                    nullptr, nullptr, 0)));
+      hipLaunchKernelGGL(k_acqj_cov, dim3((unsigned)ns), dim3(AJ_THREADS), 0, st(), (int)q, (int)n, x, ldx, (const double*)xp, ldp,
+                         (const double*)pr.Kstar, (const double*)pr.W, (const double*)acqj.Kp, (const double*)acqj.Wp, pr.ld, pr.m, pr.a,
+                         (int)D, (const double*)g.scales, g.k.kind, (double)kvar(g), g.k.variance + jitter,
+                         n > 0 ? (const double*)acqj.pend : (const double*)nullptr, acqj.rec);
+      hipLaunchKernelGGL(k_acqj_set, dim3((unsigned)ns), dim3(AJ_THREADS), 0, st(), p, (int)(q + n), (int)S, (const double*)eps, lde,
+                         (const double*)acqj.rec, grad ? 1 : 0, alpha, acqj.bar, acqj.bad);
+      LAUNCHCHK(ctx);
+      if (grad) {
+        hipLaunchKernelGGL(k_acqj_weights, dim3((unsigned)((pr.m + AJ_THREADS - 1) / AJ_THREADS), (unsigned)ns), dim3(AJ_THREADS), 0, st(),
+                           (int)q, (int)n, x, ldx, (const double*)xp, ldp, (const double*)pr.W, (const double*)acqj.Wp, pr.ld, pr.m, pr.a,
+                           (int)D, (const double*)g.scales, g.k.kind, (double)kvar(g), (const double*)acqj.bar, acqj.V, pr.ld, acqj.cross);
+        *ng = acq_contract_launch<true>(st(), x, ldx, np, pr.Z, pr.m, D, (const double*)g.scales, g.k.kind, (double)kvar(g), pr.a,
+                                        (const double*)acqj.V, pr.ld, pg_part, acq.sc);
+        LAUNCHCHK(ctx);
+      }
+    }
+    return AGP_OK;
+  }
+  agp_status acquisition_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* xq,
+                               int64_t ldx, int64_t nsets, const void* eps, int64_t lde, int64_t S, void* alpha_out, void* grad_out,
+                               int64_t ldg) override {
+    const char* who = "agp_svgp_acquisition_joint: ";
+    AcqParams p;
+    AGPCHK(acq_check_handle(who));
+    AGPCHK(acq_check_latent(who, l, d, &p));
+    AGPCHK(acqj_check_args(ctx, who, p, D, xp, ldp, n, q, eps, lde, S));
+    if (nsets < 0 || ldx < D || (grad_out && ldg < D) || (nsets > 0 && (!xq || !alpha_out))) {
+      ctx->err = std::string(who) + "n_sets >= 0, xq and alpha_out must not be NULL, ldx >= D, ldg >= D when grad_out is given";
+      return AGP_ERR_INVALID;
+    }
+    if (nsets == 0) return AGP_OK;
+    if constexpr (std::is_same<T, double>::value) {
+      Latent& g = lat[l];
+      AGPCHK(acq_prepare(g, false));
+      AGPCHK(acqj.ensure(ctx, mp, D));
+      const AcqPred pr = acq_latent_pred(g);
+      AGPCHK(acqj_begin(g, pr, xp, ldp, n));
+      const int64_t spc = PG_CH / q;  // sets per chunk: a tuple never straddles two chunks
+      for (int64_t s = 0; s < nsets; s += spc) {
+        const int64_t ns = (nsets - s) < spc ? (nsets - s) : spc;
+        const double* x = (const double*)xq + s * q * ldx;
+        int ng = 0;
+        AGPCHK(acqj_pass(g, pr, p, x, ldx, xp, ldp, n, q, ns, eps, lde, S, grad_out != nullptr, (double*)alpha_out + s, &ng));
+        if (grad_out) {
+          hipLaunchKernelGGL(k_acqj_grad, grid1(ns * q * D), dim3(256), 0, st(), ns * q, (int)D, ng, (const double*)pg_part,
+                             (const double*)acqj.cross, (const double*)g.scales, (double*)grad_out + s * q * ldg, ldg);
+          LAUNCHCHK(ctx);
+        }
+      }
+    }
+    return AGP_OK;
+  }
+  agp_status acq_maximize_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* x0,
+                                int64_t ldx0, int64_t R, const void* eps, int64_t lde, int64_t S, const agp_pw_ascent_opts* o,
+                                void* x_out, int64_t ldxo, void* a_out, void* best_x, int64_t ldb, void* best_a,
+                                void* best_idx) override {
+#pragma clang fp contract(off)
+    const char* who = "agp_svgp_acq_maximize_joint: ";
+    auto invalid = [&](const char* what) {
+      ctx->err = std::string(who) + what;
+      return AGP_ERR_INVALID;
+    };
+    AcqParams p;
+    PwAscentBox box;
+    AGPCHK(acq_check_handle(who));
+    AGPCHK(acq_check_latent(who, l, d, &p));
+    AGPCHK(acqj_check_args(ctx, who, p, D, xp, ldp, n, q, eps, lde, S));
+    if (!x0) return invalid("x0 must be given");
+    AGPCHK(acq_check_opts(ctx, who, D, o, &box));
+    if (!x_out && !a_out && !best_x && !best_a && !best_idx) return invalid("at least one output must be given");
+    if (R < 1 || R >= ((int64_t)1 << 31) / AGP_ACQ_JOINT_MAX_Q) return invalid("n_starts >= 1 and n_starts * 16 below 2^31");
+    if (ldx0 < D) return invalid("ldx0 >= D");
+    if (x_out && ldxo < D) return invalid("ldxo >= D when x_out is given");
+    if (best_x && ldb < D) return invalid("ldb >= D when best_x is given");
+    if constexpr (std::is_same<T, double>::value) {
+      Latent& g = lat[l];
+      AGPCHK(acq_prepare(g, true));
+      AGPCHK(acq.ensure_particles(ctx, R * q, D));
+      AGPCHK(acqj.ensure(ctx, mp, D));
+      const AcqPred pr = acq_latent_pred(g);
+      AGPCHK(acqj_begin(g, pr, xp, ldp, n));
+      const int64_t spc = PG_CH / q;
+      for (int64_t s = 0; s < R; s += spc) {
+        const int64_t ns = (R - s) < spc ? (R - s) : spc, np = ns * q;
+        double* x = acq.X + s * q * D;
+        hipLaunchKernelGGL(k_acq_init, grid1(np * D), dim3(256), 0, st(), np, (int)D, (const double*)x0 + s * q * ldx0, ldx0, box, x,
+                           acq.mo, acq.vo);
+        LAUNCHCHK(ctx);
+        double b1k = 1.0, b2k = 1.0;
+        for (int k = 0; k <= o->steps; ++k) {
+          const bool fin = k == o->steps;  // the pass after the last step: alpha at the final tuple
+          int ng = 0;
+          AGPCHK(acqj_pass(g, pr, p, x, D, xp, ldp, n, q, ns, eps, lde, S, !fin, acq.A + s, &ng));
+          if (fin) break;
+          b1k *= o->beta1, b2k *= o->beta2;
+          hipLaunchKernelGGL(k_acqj_step, grid1(np * D), dim3(256), 0, st(), np, (int)D, ng, (const double*)pg_part,
+                             (const double*)acqj.cross, (const double*)g.scales, o->beta1, o->beta2, 1.0 - b1k, 1.0 - b2k, o->eps, box, x,
+                             acq.mo, acq.vo);
+          LAUNCHCHK(ctx);
+        }
+      }
+      if (best_x || best_a || best_idx) {  // a tuple is one row of q D values for the best-start rule
+        hipLaunchKernelGGL(k_pw_ascent_best, dim3(1), dim3(256), 0, st(), (const double*)acq.X, (const double*)acq.A, R, q * D, 1.0,
+                           best_x ? acqj.bx : (double*)nullptr, q * D, (double*)best_a, (int64_t*)best_idx);
+        LAUNCHCHK(ctx);
+        if (best_x)
+          HIPCHK(ctx, hipMemcpy2DAsync(best_x, sizeof(double) * ldb, acqj.bx, sizeof(double) * D, sizeof(double) * D, q,
+                                       hipMemcpyDeviceToDevice, st()));
+      }
+      if (x_out)
+        HIPCHK(ctx, hipMemcpy2DAsync(x_out, sizeof(double) * ldxo, acq.X, sizeof(double) * D, sizeof(double) * D, R * q,
+                                     hipMemcpyDeviceToDevice, st()));
+      if (a_out) HIPCHK(ctx, hipMemcpyAsync(a_out, acq.A, sizeof(double) * R, hipMemcpyDeviceToDevice, st()));
     }
     return AGP_OK;
   }
@@ -6381,6 +6539,20 @@ agp_status agp_pathwise_maximize(agp_pathwise* p, int32_t latent, const void* x0
   DevGuard guard(p->ctx->device);
   return pw_maximize(p, latent, (const double*)x0, ldx0, n_starts, opts, (double*)x_out, ldxo, (double*)f_out, ldf, (double*)best_x, ldb,
                      (double*)best_f, (int64_t*)best_idx);
+}
+agp_status agp_svgp_acquisition_joint(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xp, int64_t ldp,
+                                      int64_t n_pending, int64_t q, const void* xq, int64_t ldx, int64_t n_sets, const void* eps,
+                                      int64_t lde, int64_t S, void* alpha_out, void* grad_out, int64_t ldg) {
+  HCHK(h);
+  return h->impl->acquisition_joint(latent, desc, xp, ldp, n_pending, q, xq, ldx, n_sets, eps, lde, S, alpha_out, grad_out, ldg);
+}
+agp_status agp_svgp_acq_maximize_joint(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xp, int64_t ldp,
+                                       int64_t n_pending, int64_t q, const void* x0, int64_t ldx0, int64_t n_starts, const void* eps,
+                                       int64_t lde, int64_t S, const agp_pw_ascent_opts* opts, void* x_out, int64_t ldxo, void* a_out,
+                                       void* best_x, int64_t ldb, void* best_a, void* best_idx) {
+  HCHK(h);
+  return h->impl->acq_maximize_joint(latent, desc, xp, ldp, n_pending, q, x0, ldx0, n_starts, eps, lde, S, opts, x_out, ldxo, a_out,
+                                     best_x, ldb, best_a, best_idx);
 }
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D) {
   if (!p) return AGP_ERR_INVALID;

@@ -201,6 +201,14 @@ struct SvgpBase {
   virtual agp_status acq_maximize_batch(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, double noise, int64_t q,
                                         const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o, void* xb_out, int64_t ldxb,
                                         void* ab_out, void* idxb_out) = 0;
+  // the joint Monte-Carlo criteria of q points and n pending ones ("ACQUISITION FUNCTIONS", paragraph "Joint batches")
+  virtual agp_status acquisition_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* xq,
+                                       int64_t ldx, int64_t nsets, const void* eps, int64_t lde, int64_t S, void* alpha, void* grad,
+                                       int64_t ldg) = 0;
+  virtual agp_status acq_maximize_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* x0,
+                                        int64_t ldx0, int64_t R, const void* eps, int64_t lde, int64_t S, const agp_pw_ascent_opts* o,
+                                        void* x_out, int64_t ldxo, void* a_out, void* best_x, int64_t ldb, void* best_a,
+                                        void* best_idx) = 0;
   virtual agp_status get_predictor(int l, int which, void* out, int64_t ldo, int64_t cap) = 0;
   virtual agp_status predict_y(const void* xt, int64_t ldx, int64_t nt, void* out) = 0;
   virtual agp_status proba_y(const void* xt, int64_t ldx, int64_t nt, const double* nodes, const double* weights,

@@ -827,9 +827,55 @@ agp_status agp_svgp_predict_f_grad(agp_svgp* h, const void* xt, int64_t ldx, int
  * Pending coordinates are device data and are not validated (the kernel functions clamp a squared distance that is not a positive
  * number to 0, so a NaN coordinate does not reliably show as a NaN value).
  *
- * Out of scope: MC q-EI with a joint reparameterised sample, fantasies that move the mean, Float32, multi-output and sharded
+ * Joint batches (Monte-Carlo q-EI and q-UCB with a joint reparameterised sample; Wilson et al. 2018, BoTorch's qExpectedImprovement
+ * and qUpperConfidenceBound).  The greedy batch above picks point b without knowing where the later ones go; the joint criterion is a
+ * function of all q points together, under their posterior correlation.  This is for one latent with the predictor (a, A) and a set
+ * of q' = q + n points x_1 ... x_q, p_1 ... p_n: the q points are optimised, the n points are pending and fixed.  Pending points here
+ * are members of the joint sample, as BoTorch's X_pending: they are NOT hallucinated observations, so a fantasy noise has no meaning
+ * and does not appear.  With k*(x) = k(Z, x), base samples eps (S x q', the caller's) and s = -1 with `minimize`:
+ *   mu_j  = k*(x_j)' a
+ *   C_jl  = k(x_j, x_l) - k*(x_j)' A k*(x_l) + jitter [j == l]          q' x q'
+ *   C     = L L'   (lower Cholesky)
+ *   f_s   = mu + L eps_s
+ *   q-EI   (AGP_ACQ_EI)    alpha = (1/S) sum_s max(0, max_j (s (f_sj - best) - xi))
+ *   q-UCB  (AGP_ACQ_UCB)   alpha = (1/S) sum_s max_j (s mu_j + beta sqrt(pi/2) |(L eps_s)_j|)
+ * The diagonal of C is exactly the variance of agp_svgp_predict_f and C is the matrix agp_svgp_predict_f_cov returns at those points.
+ * With q' = 1 the expectation of q-UCB over eps is s mu + beta sigma, and that of q-EI is EI.  The first maximum wins a tie.  The
+ * gradient is the sub-gradient through the winning member.  A sample counts for q-EI if its maximum is positive, always for q-UCB:
+ *   mu-bar_j  = (s/S) #{s : j wins and the sample counts}
+ *   L-bar_jk  = (1/S) sum over those samples of g_s eps_sk,  k <= j;   g_s = s (q-EI),  g_s = sign((L eps_s)_j) beta sqrt(pi/2) (q-UCB)
+ *   Phi       = tril(L' L-bar) with the diagonal halved,   C-bar = sym(L^-T Phi L^-1)          (the Cholesky backward)
+ *   V_j       = mu-bar_j a - 2 sum_l C-bar_jl W_l          over all q' members l;  W_l = A k*(x_l), the row of W = K*m A' of x_l or p_l
+ *   d alpha / d x_j = sum_i V_ji d k(x_j, z_i) / d x_j + 2 sum_l C-bar_jl d1 k(x_j, x_l)
+ * Pending members get no gradient and do not move.  The criterion has kinks where a sample's winner changes or its improvement
+ * changes sign; there the sub-gradient of the first maximum is returned.  eps is a device pointer, double [S][lde] with lde >= q + n,
+ * row s holding the draws of x_1 ... x_q, p_1 ... p_n in that order.  The same table serves every start and every step
+ * (sample-average approximation): the library draws nothing and its random streams are untouched (agp_mc_normals fills such a table).
+ *
+ * agp_svgp_acquisition_joint  alpha_out[r] of n_sets sets, member j of set r at xq + (r q + j) ldx, and (grad_out nullable) its
+ *   gradient in the same layout with ldg.  Sets are streamed in chunks of floor(4096 / q): a tuple never straddles two chunks.  Per
+ *   chunk: K*m and W of the chunk's points (the two launches of agp_svgp_acquisition), the covariance kernel (mu and C of a set from
+ *   its rows of K*m and W), the per-set kernel (Cholesky, samples, alpha, the backward pass to mu-bar and C-bar), the weight rows V
+ *   with the point-to-point term, the contraction of agp_svgp_acquisition on V, and a finishing kernel: seven launches, four without
+ *   the gradient.  K*m and W of the pending points are formed once per call.  n_sets = 0 is a successful no-op.
+ * agp_svgp_acq_maximize_joint  the ascent of agp_svgp_acq_maximize on alpha: the same ADAM recurrence per coordinate, the same
+ *   clipping, "the FINAL iterate of the best start", the same agp_pw_ascent_opts and checks.  A start is a q-tuple: member j of start
+ *   r at x0 + (r q + j) ldx0.  Outputs, each nullable (not all): x_out in that layout with ldxo, a_out[r], best_x (q rows, row j at
+ *   best_x + j ldb), best_a, best_idx.  No host synchronisation between steps.
+ * A Cholesky pivot that is not positive and finite cannot happen with jitter > 0 in exact arithmetic; it is latched on the handle and
+ * reported by agp_svgp_check_status (AGP_ERR_NOT_POSDEF), as the bordering does it.  Every sum has an order fixed by (m, D, q', S);
+ * no atomics: the same bits on a repeat, and a start has the same bits wherever it stands in a chunk of the same length.  Nothing that
+ * agp_svgp_predict_f, agp_svgp_predict_f_grad, agp_svgp_acquisition* or agp_svgp_acq_maximize* use is resized or overwritten.
+ * Both refuse (AGP_ERR_UNSUPPORTED) the same handles in the same words as agp_svgp_acq_maximize, and by name AGP_ACQ_PI,
+ * AGP_ACQ_LOG_EI and AGP_ACQ_LOG_PI (the joint PI has a zero gradient almost everywhere, the log kinds need a smoothed maximum),
+ * before any launch and with the outputs untouched.  AGP_ERR_INVALID with a message: everything agp_svgp_acquisition and
+ * agp_svgp_acq_maximize check; q < 1; n_pending < 0; q + n_pending > AGP_ACQ_JOINT_MAX_Q; S outside [1, 4096]; eps NULL; lde < q +
+ * n_pending; xp NULL or ldp < D with n_pending > 0; a leading dimension < D; a NULL required output.
+ *
+ * Out of scope: the joint PI and the joint log kinds, fantasies that move the mean, Float32, multi-output and sharded
  * handles, a single-launch ascent. */
 #define AGP_ACQ_MAX_PENDING 64 /* n_pending + q; an interface limit, not a tuned value */
+#define AGP_ACQ_JOINT_MAX_Q 16 /* q + n_pending of a joint batch; an interface limit, not a tuned value */
 enum { AGP_ACQ_UCB = 0, AGP_ACQ_EI = 1, AGP_ACQ_PI = 2, AGP_ACQ_LOG = 4 /* a flag on EI and PI: */, AGP_ACQ_LOG_EI = 5, AGP_ACQ_LOG_PI = 6 };
 typedef struct {
   int32_t kind;     /* AGP_ACQ_* */
@@ -1224,6 +1270,21 @@ agp_status agp_svgp_acq_maximize_batch(agp_svgp* h, int32_t latent, const agp_ac
                                        int64_t q, const void* x0, int64_t ldx0, int64_t n_starts, const agp_pw_ascent_opts* opts,
                                        void* xb_out /* [q][ldxb] */, int64_t ldxb,
                                        void* ab_out /* double[q], nullable */, void* idxb_out /* int64[q], nullable */);
+/* "ACQUISITION FUNCTIONS", paragraph "Joint batches" */
+agp_status agp_svgp_acquisition_joint(agp_svgp* h, int32_t latent, const agp_acq_desc* desc,
+                                      const void* xp /* nullable iff n_pending == 0 */, int64_t ldp, int64_t n_pending, int64_t q,
+                                      const void* xq, int64_t ldx, int64_t n_sets,
+                                      const void* eps /* double [S][lde] */, int64_t lde, int64_t S,
+                                      void* alpha_out, void* grad_out /* nullable */, int64_t ldg);
+agp_status agp_svgp_acq_maximize_joint(agp_svgp* h, int32_t latent, const agp_acq_desc* desc,
+                                       const void* xp /* nullable iff n_pending == 0 */, int64_t ldp, int64_t n_pending, int64_t q,
+                                       const void* x0, int64_t ldx0, int64_t n_starts,
+                                       const void* eps /* double [S][lde] */, int64_t lde, int64_t S, const agp_pw_ascent_opts* opts,
+                                       void* x_out, int64_t ldxo, /* nullable: [r][j][d], ldxo >= D */
+                                       void* a_out,               /* nullable: [r] */
+                                       void* best_x, int64_t ldb, /* nullable: [j][d], ldb >= D */
+                                       void* best_a,              /* nullable: one double */
+                                       void* best_idx);           /* nullable: one int64 */
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D);
 agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void* out, int64_t ld);
 agp_status agp_pathwise_destroy(agp_pathwise* p);

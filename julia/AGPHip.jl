@@ -30,6 +30,8 @@
 #   acquisition / maximize_acquisition(model, UCB | EI | PI | LogEI | LogPI, ...) (no counterpart: Bayesian optimisation) -> agp_svgp_acquisition, agp_svgp_acq_maximize
 #   acquisition_pending / maximize_acquisition_batch(model, ...; pending) (no counterpart: batch acquisition by hallucinated
 #     observations)                                                                  -> agp_svgp_acquisition_pending, agp_svgp_acq_maximize_batch
+#   acquisition_joint / maximize_acquisition_joint(model, EI | UCB, ...) (no counterpart: Monte-Carlo q-EI / q-UCB with a joint
+#     reparameterised sample)                                                        -> agp_svgp_acquisition_joint, agp_svgp_acq_maximize_joint
 #   init_state                                                src/training/states.jl:1-9               -> agp_svgp_init_state
 # Multi-GPU (one Julia process per GPU, e.g. under MPI.jl or Distributed): agp_comm_* binds RCCL inside the library; the host only
 # ships the 128-byte id from rank 0 to the others (section "multi-GPU" below).
@@ -1649,10 +1651,74 @@ function maximize_acquisition_batch(hm::HipModel{Float64}, acq::AcqDesc, q::Inte
     Xb, a = permutedims(Array(xb)), Array(ab)
     return full ? (Xb, a, Array(ib) .+ 1) : (Xb, a)
 end
+# Joint batches ("ACQUISITION FUNCTIONS", paragraph "Joint batches"): Monte-Carlo q-EI (AcqDesc of EI) and q-UCB (of UCB) of q points under
+# their posterior correlation, f_s = mu + L eps_s over the caller's base samples E (S x (q + n)); pending points are members of the
+# joint sample that stay where they are.  Never run, like everything in this file.
+# acquisition_joint(hm, acq, Xq, E; pending=nothing, grad=false, latent=1): alpha of the tuples Xq (n_sets x q x D), with grad=true
+# (alpha, G n_sets x q x D) (agp_svgp_acquisition_joint)
+function acquisition_joint(hm::HipModel{Float64}, acq::AcqDesc, Xq::AbstractArray{<:Real,3}, E::AbstractMatrix; pending=nothing,
+                           grad::Bool=false, latent::Integer=1)
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    nsets, q, D = size(Xq)
+    n = pending === nothing ? 0 : size(pending, 1)
+    S = size(E, 1)
+    size(E, 2) == q + n || error("acquisition_joint: E must be S x (q + n)")
+    Xd = ROCArray{Float64}(permutedims(Xq, (3, 2, 1)))        # column-major D x q x n_sets == [r][j][d]
+    Ed = ROCArray{Float64}(permutedims(E))                    # column-major (q + n) x S == [s][k]
+    Pd = n > 0 ? ROCArray{Float64}(permutedims(pending)) : nothing
+    a = ROCArray{Float64}(undef, nsets)
+    G = grad ? ROCArray{Float64}(undef, D, q, nsets) : nothing
+    check(hm.ctx, ccall((:agp_svgp_acquisition_joint, libagp), Int32,
+                        (Ptr{Cvoid}, Int32, Ref{AcqDesc}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64,
+                         Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+                        hm.h, latent - 1, Ref(acq), n > 0 ? pointer(Pd) : C_NULL, D, n, q, pointer(Xd), D, nsets, pointer(Ed), q + n, S,
+                        pointer(a), grad ? pointer(G) : C_NULL, D))
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    check(hm.ctx, ccall((:agp_svgp_check_status, libagp), Int32, (Ptr{Cvoid},), hm.h))
+    return grad ? (Array(a), permutedims(Array(G), (3, 2, 1))) : Array(a)
+end
+# maximize_acquisition_joint(hm, acq, X0, E, lo, hi; pending=nothing, steps=100, ...): the ascent of maximize_acquisition on the joint
+# criterion, a start being a q-tuple (X0 is R x q x D) (agp_svgp_acq_maximize_joint).  Returns (X_best q x D, a_best); full=true adds
+# idx (1-based), X (R x q x D) and A (R).
+function maximize_acquisition_joint(hm::HipModel{Float64}, acq::AcqDesc, X0::AbstractArray{<:Real,3}, E::AbstractMatrix, lo, hi;
+                                    pending=nothing, steps::Integer=100, lr=nothing, beta1::Real=0.9, beta2::Real=0.999,
+                                    eps::Real=1e-8, latent::Integer=1, full::Bool=false)
+    ensure_handle!(hm, max(hm.maxbatch, 1))
+    R, q, D = size(X0)
+    vec_of(v) = v isa Number ? fill(Float64(v), D) : collect(Float64, v)
+    lov, hiv = vec_of(lo), vec_of(hi)
+    lrv = lr === nothing ? map(w -> w == 0 ? 1.0 : 0.02 * w, hiv .- lov) : vec_of(lr)
+    (length(lov) == D && length(hiv) == D && length(lrv) == D) || error("maximize_acquisition_joint: lo, hi and lr must be scalars or of length $D")
+    n = pending === nothing ? 0 : size(pending, 1)
+    S = size(E, 1)
+    size(E, 2) == q + n || error("maximize_acquisition_joint: E must be S x (q + n)")
+    Xd = ROCArray{Float64}(permutedims(X0, (3, 2, 1)))
+    Ed = ROCArray{Float64}(permutedims(E))
+    Pd = n > 0 ? ROCArray{Float64}(permutedims(pending)) : nothing
+    X, A = ROCArray{Float64}(undef, D, q, R), ROCArray{Float64}(undef, R)
+    xb, ab, ib = ROCArray{Float64}(undef, D, q), ROCArray{Float64}(undef, 1), ROCArray{Int64}(undef, 1)
+    GC.@preserve lov hiv lrv begin
+        opts = Ref(PwAscentOpts(steps, 0, 0, beta1, beta2, eps, pointer(lov), pointer(hiv), pointer(lrv)))
+        check(hm.ctx, ccall((:agp_svgp_acq_maximize_joint, libagp), Int32,
+                            (Ptr{Cvoid}, Int32, Ref{AcqDesc}, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64,
+                             Int64, Ref{PwAscentOpts}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                            hm.h, latent - 1, Ref(acq), n > 0 ? pointer(Pd) : C_NULL, D, n, q, pointer(Xd), D, R, pointer(Ed), q + n, S, opts,
+                            full ? pointer(X) : C_NULL, D, full ? pointer(A) : C_NULL, pointer(xb), D, pointer(ab), pointer(ib)))
+    end
+    ccall((:agp_ctx_sync, libagp), Int32, (Ptr{Cvoid},), hm.ctx)
+    check(hm.ctx, ccall((:agp_svgp_check_status, libagp), Int32, (Ptr{Cvoid},), hm.h))
+    Xb, a_best = permutedims(Array(xb)), Array(ab)[1]
+    full || return Xb, a_best
+    return Xb, a_best, Array(ib)[1] + 1, permutedims(Array(X), (3, 2, 1)), Array(A)
+end
 acquisition(ho::HipOnlineModel, acq::AcqDesc, X::AbstractMatrix; kw...) = acquisition(ho.cur, acq, X; kw...)
 maximize_acquisition(ho::HipOnlineModel, acq::AcqDesc, X0::AbstractMatrix, lo, hi; kw...) = maximize_acquisition(ho.cur, acq, X0, lo, hi; kw...)
 acquisition_pending(ho::HipOnlineModel, acq::AcqDesc, X::AbstractMatrix, P::AbstractMatrix; kw...) = acquisition_pending(ho.cur, acq, X, P; kw...)
 maximize_acquisition_batch(ho::HipOnlineModel, acq::AcqDesc, q::Integer, X0::AbstractMatrix, lo, hi; kw...) =
     maximize_acquisition_batch(ho.cur, acq, q, X0, lo, hi; kw...)
+acquisition_joint(ho::HipOnlineModel, acq::AcqDesc, Xq::AbstractArray{<:Real,3}, E::AbstractMatrix; kw...) =
+    acquisition_joint(ho.cur, acq, Xq, E; kw...)
+maximize_acquisition_joint(ho::HipOnlineModel, acq::AcqDesc, X0::AbstractArray{<:Real,3}, E::AbstractMatrix, lo, hi; kw...) =
+    maximize_acquisition_joint(ho.cur, acq, X0, E, lo, hi; kw...)
 
 end # module
