@@ -28,6 +28,19 @@ namespace agp {
 constexpr int LDP = TILE + 2;   // 66: [r][k] stride for 64-deep LDS tiles (conflict-free MFMA fragment reads)
 constexpr int CHOL_THREADS = 512;
 
+// a compiler barrier between two LDS reads: the load/store optimiser does not merge reads across it (no instruction is emitted).
+// Left alone it pairs the fp64 MFMA operand reads of two neighbouring k-steps into one ds_read2_b64 ... offset1:4, which serves 16
+// lanes per LDS cycle and banks modulo 32: at the row stride LDP lanes l and l + 8 of a group meet on one bank and the pair costs 16
+// LDS cycles, where two ds_read_b64 (32 lanes per cycle, banks modulo 64, conflict-free at this stride) cost 4 (subst_tile below;
+// DESIGN.md section 5 "round 14" and "round 15").
+__device__ __forceinline__ void lds_keep_apart() { asm volatile("" ::: "memory"); }
+// the same behind an operand read of an MFMA loop that also exists in float: the float kernels (other read forms, other banks) keep
+// their instruction sequence
+template <typename T>
+__device__ __forceinline__ void lds_keep_apart64() {
+  if constexpr (sizeof(T) == 8) lds_keep_apart();
+}
+
 __device__ __forceinline__ double rcp1(double p) {
   double r = __builtin_amdgcn_rcp(p);
   return fma(r, fma(-p, r, 1.0), r);
@@ -80,14 +93,18 @@ struct Acc8 {
 };
 
 // acc += As(64 x 64, [r][k] stride LDP) * Bs(64 x 64 given as [c][k] stride LDP)^T
+// (fp64: one ds_read_b64 per operand, lds_keep_apart64; the same in mma8_sub, mma_blk32, mma_tile16 and mma_tile16_chain)
 template <typename T>
 __device__ __forceinline__ void mma8(const T* As, const T* Bs, Acc8<T>& acc) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 2, wn = wave & 3;
 #pragma unroll 4
   for (int kk = 0; kk < TILE / 4; ++kk) {
     T a0 = As[(wm * 32 + (lane & 15)) * LDP + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     T a1 = As[(wm * 32 + 16 + (lane & 15)) * LDP + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     T b0 = Bs[(wn * 16 + (lane & 15)) * LDP + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     acc.a[0] = Mfma<T>::mma(a0, b0, acc.a[0]);
     acc.a[1] = Mfma<T>::mma(a1, b0, acc.a[1]);
   }
@@ -100,8 +117,11 @@ __device__ __forceinline__ void mma8_sub(const T* As, const T* Bs, Acc8<T>& acc)
 #pragma unroll 4
   for (int kk = 0; kk < TILE / 4; ++kk) {
     T a0 = -As[(wm * 32 + (lane & 15)) * LDP + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     T a1 = -As[(wm * 32 + 16 + (lane & 15)) * LDP + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     T b0 = Bs[(wn * 16 + (lane & 15)) * LDP + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     acc.a[0] = Mfma<T>::mma(a0, b0, acc.a[0]);
     acc.a[1] = Mfma<T>::mma(a1, b0, acc.a[1]);
   }
@@ -365,9 +385,11 @@ __device__ __forceinline__ typename Mfma<T>::acc_t mma_blk32(const T* As, const 
 #pragma unroll
   for (int kk = 0; kk < 8; ++kk) {
     T a = As[(wr * 16 + (lane & 15)) * LDP + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     if (negA) a = -a;
     T b = TB ? Bs[(kk * 4 + (lane >> 4)) * LDB + wc * 16 + (lane & 15)]
              : Bs[(wc * 16 + (lane & 15)) * LDB + kk * 4 + (lane >> 4)];
+    lds_keep_apart64<T>();
     acc = Mfma<T>::mma(a, b, acc);
   }
   return acc;
@@ -1278,8 +1300,14 @@ __device__ __forceinline__ typename Mfma<T>::acc_t mma_tile16(const T* Ar, const
   for (int r = 0; r < 4; ++r) p1[r] = T(0);
 #pragma unroll 2
   for (int kk = 0; kk < kend / 4; kk += 2) {
-    T a0 = pa[kk * 4], a1 = pa[kk * 4 + 4];
-    const T b0 = pb[kk * 4], b1 = pb[kk * 4 + 4];
+    T a0 = pa[kk * 4];
+    lds_keep_apart64<T>();
+    T a1 = pa[kk * 4 + 4];
+    lds_keep_apart64<T>();
+    const T b0 = pb[kk * 4];
+    lds_keep_apart64<T>();
+    const T b1 = pb[kk * 4 + 4];
+    lds_keep_apart64<T>();
     if (neg) {
       a0 = -a0;
       a1 = -a1;
@@ -1315,12 +1343,18 @@ __device__ __forceinline__ void mma_tile16_chain(const T* Ar, const T* Bc, typen
 #pragma unroll
     for (int kk = 4 * q; kk < 4 * q + 4; kk += 2) {
       av[kk] = pa[kk * 4];
+      lds_keep_apart64<T>();
       bv[kk] = pb[kk * 4];
+      lds_keep_apart64<T>();
       av[kk + 1] = pa[kk * 4 + 4];
+      lds_keep_apart64<T>();
       bv[kk + 1] = pb[kk * 4 + 4];
+      lds_keep_apart64<T>();
       if (THIRD) {
         xa[kk / 2] = qa[kk * 4];
+        lds_keep_apart64<T>();
         xb[kk / 2] = qb[kk * 4];
+        lds_keep_apart64<T>();
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1362,7 +1396,7 @@ __device__ __forceinline__ void mma_tile16_chain(const T* Ar, const T* Bc, typen
 // stage's MFMAs, 3 behind after_first, 4 and 5 behind the two barriers, 6 at the end.
 // Until round 13 every stage went through mma_tile16's loop.  Since round 14 (same operands, same LDS addresses, same MFMA order per
 // accumulator -- `a` takes the even k-steps, p1 the odd ones, a += p1 -- and the same barriers; DESIGN.md section 5 "round 14"):
-//   * Every operand is read with a ds_read_b64 of its own (lds_keep_apart below).  Left alone the compiler pairs the reads of two
+//   * Every operand is read with a ds_read_b64 of its own (lds_keep_apart).  Left alone the compiler pairs the reads of two
 //     k-steps into one ds_read2_b64, which serves 16 lanes per LDS cycle and banks modulo 32: with the row stride LDP = 66 doubles
 //     lanes l and l + 8 of a group meet on one bank, and the pair costs 16 LDS cycles where two ds_read_b64 (32 lanes per cycle,
 //     banks modulo 64, conflict-free at this stride) cost 4.  With eight waves reading at once that rate, not the latency, was
@@ -1373,8 +1407,6 @@ __device__ __forceinline__ void mma_tile16_chain(const T* Ar, const T* Bc, typen
 //   * The B operands of stages 2 and 3 -- the [L21 | X22] rows of the slot, which nobody writes -- and the wave's own tile of T2
 //     are read under the MFMAs of the stage in front, across its barrier: behind a barrier only the A operand (L1, then U, written by
 //     the other waves) is still to come.
-// a compiler barrier between two LDS reads: the load/store optimiser does not merge reads across it (no instruction is emitted)
-__device__ __forceinline__ void lds_keep_apart() { asm volatile("" ::: "memory"); }
 template <int N>
 struct IntC {
   static constexpr int value = N;
