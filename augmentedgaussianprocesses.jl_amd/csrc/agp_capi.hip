@@ -3,7 +3,8 @@
 // classes (Svgp<T> and the six derived from it) and the extern "C" surface, and is the one translation unit: it includes the kernel
 // headers, then agp_ctx.h (context, error macros), agp_chol_host.h (Cholesky driver) and agp_blas_host.h (GEMM / SYRK / kernel-matrix
 // launchers), then agp_svgp_base.h (the handle interface) and the host drivers of the other subjects (agp_lpd_host.h,
-// agp_pathwise_host.h, agp_blocks_host.h, agp_select_host.h, agp_comm_host.h), each where its text stood.
+// agp_pathwise_host.h, agp_acq_host.h, agp_acq_joint_host.h, agp_blocks_host.h, agp_select_host.h, agp_comm_host.h), each where its
+// text stood.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -2533,12 +2534,12 @@ struct Svgp : SvgpBase {
     int32_t words[4] = {0, 0, 0, 0};  // info | infoK | flags | orderK (k_logdiag_sum: did K_ZZ fail before or after the others?)
     HIPCHK(ctx, hipMemcpyAsync(words, info_dev, sizeof(words), hipMemcpyDeviceToHost, st()));
     int32_t acq_bad = 0;  // a bordering pivot of the pending points that was not positive and finite (agp_acq_batch.h)
-    if (acqb.bad) HIPCHK(ctx, hipMemcpyAsync(&acq_bad, acqb.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
+    if (acqd.acqb.bad) HIPCHK(ctx, hipMemcpyAsync(&acq_bad, acqd.acqb.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
     int32_t acqj_bad = 0;  // a Cholesky pivot of a joint batch's covariance that was not positive and finite (agp_acq_joint.h)
-    if (acqj.bad) HIPCHK(ctx, hipMemcpyAsync(&acqj_bad, acqj.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
+    if (acqjd.acqj.bad) HIPCHK(ctx, hipMemcpyAsync(&acqj_bad, acqjd.acqj.bad, sizeof(int32_t), hipMemcpyDeviceToHost, st()));
     HIPCHK(ctx, hipStreamSynchronize(st()));
-    if (acq_bad != 0) HIPCHK(ctx, hipMemsetAsync(acqb.bad, 0, sizeof(int32_t), st()));
-    if (acqj_bad != 0) HIPCHK(ctx, hipMemsetAsync(acqj.bad, 0, sizeof(int32_t), st()));
+    if (acq_bad != 0) HIPCHK(ctx, hipMemsetAsync(acqd.acqb.bad, 0, sizeof(int32_t), st()));
+    if (acqj_bad != 0) HIPCHK(ctx, hipMemsetAsync(acqjd.acqj.bad, 0, sizeof(int32_t), st()));
     const int32_t info = words[0], infoK = words[1], orderK = words[3];
     const int flags = (int)words[2];
     dag_retry_check(ctx);  // steps the in-stream fallback had to re-run: warn once, stop using the task graph
@@ -3375,11 +3376,13 @@ struct Svgp : SvgpBase {
     return AGP_OK;
   }
 
-  // ---- acquisition functions (include/agp_hip.h, "ACQUISITION FUNCTIONS"; agp_acq.h, agp_acq_host.h) ----------
-  // Per chunk of 4096 points and pass: K*m (launch_kernelmatrix), W = K*m Apred' (gemm_nt), k_acq_contract, and one finishing kernel
-  // (k_acq_finish, or k_acq_step with the ADAM update): four launches, nothing waits for the stream.  One routine for every class, as
-  // predict_f_grad: it needs only what ensure_pred leaves.  The predictor's workspaces (Kstar, pg_W, pg_part) are shared with it.
-  AcqState acq;
+  // ---- acquisition functions (include/agp_hip.h, "ACQUISITION FUNCTIONS") ---------------------------------------
+  // The drivers (AcqDriver in agp_acq_host.h, AcqJointDriver in agp_acq_joint_host.h) hold the state of the calls and enqueue every
+  // launch; they are Float64 code that serves every class, as predict_f_grad does, because they need only what ensure_pred leaves.
+  // Here is what needs the model: the refusals by handle, latent and kernel, and the view of one latent's predictor (AcqModel), in
+  // which the predictor's workspaces (Kstar, pg_W, pg_part) are those of predict_f_grad.  Nothing of the latent's is written.
+  AcqDriver acqd;
+  AcqJointDriver acqjd;
   agp_status acq_refused(const char* who, const char* why) {
     ctx->err = std::string(who) + why;
     return AGP_ERR_UNSUPPORTED;
@@ -3406,387 +3409,32 @@ struct Svgp : SvgpBase {
     if (lat[l].k.kind == AGP_K_EXPONENTIAL) return acq_refused(who, "ExponentialKernel is not differentiable at zero distance");
     return AGP_OK;
   }
+  agp_status acq_check(const char* who, int l, const agp_acq_desc* d, AcqParams* p) override {
+    AGPCHK(acq_check_handle(who));
+    return acq_check_latent(who, l, d, p);
+  }
   agp_status acq_prepare(Latent& g, bool ascent) {
     AGPCHK(params_to_host(g));
     AGPCHK(ensure_pred_ws(0, true));
     if (!pg_part) AGPCHK(dmalloc(ctx, &pg_part, 2 * (int64_t)PG_MAXGROUPS * PG_CH * D));
     if (!pg_W) AGPCHK(dmalloc(ctx, &pg_W, (int64_t)PG_CH * mp));
-    AGPCHK(acq.ensure_chunk(ctx, D, ascent));
+    AGPCHK(acqd.acq.ensure_chunk(ctx, D, ascent));
     AGPCHK(ensure_pred(g, true));
     AGPCHK(ensure_zsc(g));
     return AGP_OK;
   }
-  // K*m, W and the contraction of nc <= 4096 points (rows of xs pitched by ldx) into pg_part / acq.sc: three launches, on the
-  // predictor pr (the latent's own objects, or the augmented ones of the pending points)
-  AcqPred acq_latent_pred(Latent& g) {
-    return AcqPred{(const double*)g.Z, (const double*)g.Zsc, (const double*)g.zn, (const double*)g.apred, (const double*)g.Apred, m, mp, mp,
-                   (double*)Kstar, (double*)pg_W, nullptr, nullptr, nullptr, nullptr};
+  // the view of a prepared latent (T is double: acq_check_handle has refused every other handle)
+  AcqModel acq_model(Latent& g) {
+    return AcqModel{ctx, D, m, mp, g.k.kind, (double)kvar(g), g.k.variance + jitter, (const double*)g.scales,
+                    AcqPred{(const double*)g.Z, (const double*)g.Zsc, (const double*)g.zn, (const double*)g.apred, (const double*)g.Apred, m,
+                            mp, mp, (double*)Kstar, (double*)pg_W, nullptr, nullptr, nullptr, nullptr},
+                    (double*)pg_part};
   }
-  template <bool GRAD>
-  agp_status acq_pass(Latent& g, const AcqPred& pr, const T* xs, int64_t ldx, int64_t nc, int* ng) {
-    if constexpr (std::is_same<T, double>::value) {
-      (void)launch_kernelmatrix<T>(ctx, st(), xs, ldx, (const int64_t*)nullptr, nc, pr.Z, D, pr.m, D, (const T*)g.scales, g.k.kind,
-                                   kvar(g), pr.Kstar, pr.ld, rup64(nc), pr.mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, pr.Zsc,
-                                   pr.zn);
-      LAUNCHCHK(ctx);
-      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, pr.Kstar, pr.ld, pr.A, pr.ld, rup64(nc), pr.mp, pr.mp, 0, pr.U ? pr.W0 : pr.W, pr.ld, nullptr, 0,
-                                    nullptr, nullptr, nullptr, 0)));
-      if (pr.U) {  // the rank-one terms of the pending points: G = K*m' U^T, W = W0 - G N^T
-        AGPCHK((gemm_nt<T, EPI_STORE>(ctx, pr.Kstar, pr.ld, pr.U, pr.ld, rup64(nc), ACQB_MAXPEND, pr.mp, 0, pr.G, ACQB_MAXPEND, nullptr, 0,
-                                      nullptr, nullptr, nullptr, 0)));
-        AGPCHK((gemm_nt<T, EPI_EMINUS>(ctx, pr.G, ACQB_MAXPEND, pr.N, ACQB_MAXPEND, rup64(nc), pr.mp, ACQB_MAXPEND, 0, pr.W, pr.ld, pr.W0,
-                                       pr.ld, nullptr, nullptr, nullptr, 0)));
-      }
-      *ng = acq_contract_launch<GRAD>(st(), xs, ldx, nc, pr.Z, pr.m, D, (const double*)g.scales, g.k.kind, (double)kvar(g), pr.a,
-                                      (const double*)pr.W, pr.ld, pg_part, acq.sc);
-      LAUNCHCHK(ctx);
-    }
-    return AGP_OK;
-  }
-  // alpha (and grad, nullable) at nt points in chunks of 4096: four launches per chunk
-  agp_status acq_eval(Latent& g, const AcqPred& pr, const AcqParams& p, const void* xt, int64_t ldx, int64_t nt, void* alpha_out,
-                      void* grad_out, int64_t ldg) {
-    if constexpr (std::is_same<T, double>::value) {
-      const double kdj = g.k.variance + jitter;
-      for (int64_t s = 0; s < nt; s += PG_CH) {
-        const int64_t nc = (nt - s) < PG_CH ? (nt - s) : PG_CH;
-        const double* xs = (const double*)xt + s * ldx;
-        int ng = 0;
-        if (grad_out) AGPCHK(acq_pass<true>(g, pr, xs, ldx, nc, &ng));
-        else AGPCHK(acq_pass<false>(g, pr, xs, ldx, nc, &ng));
-        hipLaunchKernelGGL(k_acq_finish, grid1(nc * (grad_out ? D : 1)), dim3(256), 0, st(), p, nc, (int)D, ng,
-                           (const double*)(grad_out ? pg_part : nullptr), (const double*)acq.sc, (const double*)g.scales, kdj,
-                           (double*)alpha_out + s, grad_out ? (double*)grad_out + s * ldg : (double*)nullptr, ldg);
-        LAUNCHCHK(ctx);
-      }
-    }
-    return AGP_OK;
-  }
-  // the ascent of R starts into acq.X / acq.A: chunk after chunk, each through all T steps
-  agp_status acq_ascend(Latent& g, const AcqPred& pr, const AcqParams& p, const PwAscentBox& box, const agp_pw_ascent_opts* o,
-                        const void* x0, int64_t ldx0, int64_t R) {
-#pragma clang fp contract(off)
-    if constexpr (std::is_same<T, double>::value) {
-      const double kdj = g.k.variance + jitter;
-      for (int64_t s = 0; s < R; s += PG_CH) {
-        const int64_t nc = (R - s) < PG_CH ? (R - s) : PG_CH;
-        double* x = acq.X + s * D;
-        hipLaunchKernelGGL(k_acq_init, grid1(nc * D), dim3(256), 0, st(), nc, (int)D, (const double*)x0 + s * ldx0, ldx0, box, x, acq.mo,
-                           acq.vo);
-        LAUNCHCHK(ctx);
-        double b1k = 1.0, b2k = 1.0;
-        for (int k = 0; k <= o->steps; ++k) {
-          const int fin = k == o->steps;  // the pass after the last step: alpha at the final x
-          int ng = 0;
-          if (fin) AGPCHK(acq_pass<false>(g, pr, x, D, nc, &ng));
-          else AGPCHK(acq_pass<true>(g, pr, x, D, nc, &ng));
-          if (!fin) b1k *= o->beta1, b2k *= o->beta2;
-          hipLaunchKernelGGL(k_acq_step, grid1(nc * (fin ? 1 : D)), dim3(256), 0, st(), p, nc, (int)D, ng, (const double*)pg_part,
-                             (const double*)acq.sc, (const double*)g.scales, kdj, o->beta1, o->beta2, 1.0 - b1k, 1.0 - b2k, o->eps, box, fin,
-                             x, acq.mo, acq.vo, acq.A + s);
-          LAUNCHCHK(ctx);
-        }
-      }
-    }
-    return AGP_OK;
-  }
-  agp_status acquisition(int l, const agp_acq_desc* d, const void* xt, int64_t ldx, int64_t nt, void* alpha_out, void* grad_out,
-                         int64_t ldg) override {
-    const char* who = "agp_svgp_acquisition: ";
-    AcqParams p;
-    AGPCHK(acq_check_handle(who));
-    AGPCHK(acq_check_latent(who, l, d, &p));
-    if (nt < 0 || ldx < D || (grad_out && ldg < D) || (nt > 0 && (!xt || !alpha_out))) {
-      ctx->err = std::string(who) + "n_t >= 0, xt and alpha_out must not be NULL, ldx >= D, ldg >= D when grad_out is given";
-      return AGP_ERR_INVALID;
-    }
-    if (nt == 0) return AGP_OK;
-    if constexpr (std::is_same<T, double>::value) {
-      Latent& g = lat[l];
-      AGPCHK(acq_prepare(g, false));
-      AGPCHK(acq_eval(g, acq_latent_pred(g), p, xt, ldx, nt, alpha_out, grad_out, ldg));
-    }
-    return AGP_OK;
-  }
-  agp_status acq_maximize(int l, const agp_acq_desc* d, const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o,
-                          void* x_out, int64_t ldxo, void* a_out, void* best_x, void* best_a, void* best_idx) override {
-    const char* who = "agp_svgp_acq_maximize: ";
-    auto invalid = [&](const char* what) {
-      ctx->err = std::string(who) + what;
-      return AGP_ERR_INVALID;
-    };
-    AcqParams p;
-    PwAscentBox box;
-    AGPCHK(acq_check_handle(who));
-    AGPCHK(acq_check_latent(who, l, d, &p));
-    if (!x0) return invalid("x0 must be given");
-    AGPCHK(acq_check_opts(ctx, who, D, o, &box));
-    if (!x_out && !a_out && !best_x && !best_a && !best_idx) return invalid("at least one output must be given");
-    if (R < 1 || R >= ((int64_t)1 << 31)) return invalid("n_starts >= 1 and below 2^31");
-    if (ldx0 < D) return invalid("ldx0 >= D");
-    if (x_out && ldxo < D) return invalid("ldxo >= D when x_out is given");
-    if constexpr (std::is_same<T, double>::value) {
-      Latent& g = lat[l];
-      AGPCHK(acq_prepare(g, true));
-      AGPCHK(acq.ensure_particles(ctx, R, D));
-      AGPCHK(acq_ascend(g, acq_latent_pred(g), p, box, o, x0, ldx0, R));
-      if (best_x || best_a || best_idx) {
-        hipLaunchKernelGGL(k_pw_ascent_best, dim3(1), dim3(256), 0, st(), (const double*)acq.X, (const double*)acq.A, R, D, 1.0,
-                           (double*)best_x, D, (double*)best_a, (int64_t*)best_idx);
-        LAUNCHCHK(ctx);
-      }
-      if (x_out)
-        HIPCHK(ctx, hipMemcpy2DAsync(x_out, sizeof(double) * ldxo, acq.X, sizeof(double) * D, sizeof(double) * D, R,
-                                     hipMemcpyDeviceToDevice, st()));
-      if (a_out) HIPCHK(ctx, hipMemcpyAsync(a_out, acq.A, sizeof(double) * R, hipMemcpyDeviceToDevice, st()));
-    }
-    return AGP_OK;
-  }
-
-  // ---- batch acquisition: pending points ("ACQUISITION FUNCTIONS", paragraph "Pending points"; agp_acq_batch.h) ---------------------
-  // The pending points condition the variance through the augmented predictor (Z', a', A') of AcqBatchWs, built by bordering in the
-  // order of the points and kept as A0 and its rank-one terms; the passes above then run on it with m' = m + n.  With no pending point the latent's own objects are passed,
-  // so those calls are the launches of acquisition / acq_maximize.  Nothing of the latent's is written.
-  AcqBatchWs acqb;
-  // the arguments that the two calls share; noise is tau2
-  agp_status acqb_check_pending(const char* who, const void* xp, int64_t ldp, int64_t n, int64_t q, double noise) {
-    auto invalid = [&](const char* what) {
-      ctx->err = std::string(who) + what;
-      return AGP_ERR_INVALID;
-    };
-    if (n < 0 || q < 1 || n > AGP_ACQ_MAX_PENDING || q > AGP_ACQ_MAX_PENDING || n + q > AGP_ACQ_MAX_PENDING)
-      return invalid("n_pending >= 0, q >= 1 and n_pending + q <= AGP_ACQ_MAX_PENDING (64)");
-    if (!std::isfinite(noise) || noise < 0.0) return invalid("noise must be finite and >= 0");
-    if (n > 0 && !xp) return invalid("xp must be given when n_pending > 0");
-    if (n > 0 && ldp < D) return invalid("ldp >= D");
-    return AGP_OK;
-  }
-  // (Z', a', A') of the latent with the n pending points of xp bordered on, in their order
-  agp_status acqb_begin(Latent& g, const void* xp, int64_t ldp, int64_t n, double noise) {
-    if constexpr (std::is_same<T, double>::value) {
-      AGPCHK(acqb.reset(ctx, D, (const double*)g.Z, (const double*)g.apred, (const double*)g.Apred, mp));
-      if (n == 0) return AGP_OK;
-      HIPCHK(ctx, hipMemcpy2DAsync(acqb.Z + m * D, sizeof(double) * D, xp, sizeof(double) * ldp, sizeof(double) * D, n,
-                                   hipMemcpyDeviceToDevice, st()));
-      for (int64_t i = 0; i < n; ++i) AGPCHK(acqb_border(g, m + i, noise));
-      AGPCHK(acqb.rescale(ctx, m + n, D, (const double*)g.scales));
-    }
-    return AGP_OK;
-  }
-  agp_status acqb_border(Latent& g, int64_t n, double noise) {
-#pragma clang fp contract(off)
-    return acqb.border(ctx, n, D, (const double*)g.scales, g.k.kind, (double)kvar(g), (g.k.variance + jitter) + noise);
-  }
-  agp_status acquisition_pending(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, double noise, const void* xt,
-                                 int64_t ldx, int64_t nt, void* alpha_out, void* grad_out, int64_t ldg) override {
-    const char* who = "agp_svgp_acquisition_pending: ";
-    AcqParams p;
-    AGPCHK(acq_check_handle(who));
-    AGPCHK(acq_check_latent(who, l, d, &p));
-    AGPCHK(acqb_check_pending(who, xp, ldp, n, 1, noise));
-    if (nt < 0 || ldx < D || (grad_out && ldg < D) || (nt > 0 && (!xt || !alpha_out))) {
-      ctx->err = std::string(who) + "n_t >= 0, xt and alpha_out must not be NULL, ldx >= D, ldg >= D when grad_out is given";
-      return AGP_ERR_INVALID;
-    }
-    if (nt == 0) return AGP_OK;
-    if constexpr (std::is_same<T, double>::value) {
-      Latent& g = lat[l];
-      AGPCHK(acq_prepare(g, false));
-      if (n == 0) return acq_eval(g, acq_latent_pred(g), p, xt, ldx, nt, alpha_out, grad_out, ldg);
-      AGPCHK(acqb.ensure(ctx, m, D));
-      AGPCHK(acqb_begin(g, xp, ldp, n, noise));
-      AGPCHK(acq_eval(g, acqb.pred(m + n), p, xt, ldx, nt, alpha_out, grad_out, ldg));
-    }
-    return AGP_OK;
-  }
-  agp_status acq_maximize_batch(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, double noise, int64_t q,
-                                const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o, void* xb_out, int64_t ldxb,
-                                void* ab_out, void* idxb_out) override {
-    const char* who = "agp_svgp_acq_maximize_batch: ";
-    auto invalid = [&](const char* what) {
-      ctx->err = std::string(who) + what;
-      return AGP_ERR_INVALID;
-    };
-    AcqParams p;
-    PwAscentBox box;
-    AGPCHK(acq_check_handle(who));
-    AGPCHK(acq_check_latent(who, l, d, &p));
-    AGPCHK(acqb_check_pending(who, xp, ldp, n, q, noise));
-    if (!x0) return invalid("x0 must be given");
-    AGPCHK(acq_check_opts(ctx, who, D, o, &box));
-    if (!xb_out) return invalid("xb_out must be given");
-    if (R < 1 || R >= ((int64_t)1 << 31)) return invalid("n_starts >= 1 and below 2^31");
-    if (ldx0 < D) return invalid("ldx0 >= D");
-    if (ldxb < D) return invalid("ldxb >= D");
-    if constexpr (std::is_same<T, double>::value) {
-      Latent& g = lat[l];
-      AGPCHK(acq_prepare(g, true));
-      AGPCHK(acq.ensure_particles(ctx, R, D));
-      AGPCHK(acqb.ensure(ctx, m, D));
-      if (n > 0 || q > 1) AGPCHK(acqb_begin(g, xp, ldp, n, noise));
-      for (int64_t b = 0; b < q; ++b) {
-        const int64_t np = n + b;  // the points the round is conditioned on: the caller's and the winners before
-        AGPCHK(acq_ascend(g, np == 0 ? acq_latent_pred(g) : acqb.pred(m + np), p, box, o, x0, ldx0, R));
-        double* win = acqb.Z + (m + np) * D;  // the winner goes device to device into the next row of the pending list
-        hipLaunchKernelGGL(k_pw_ascent_best, dim3(1), dim3(256), 0, st(), (const double*)acq.X, (const double*)acq.A, R, D, 1.0, win, D,
-                           ab_out ? (double*)ab_out + b : (double*)nullptr, idxb_out ? (int64_t*)idxb_out + b : (int64_t*)nullptr);
-        LAUNCHCHK(ctx);
-        HIPCHK(ctx, hipMemcpyAsync((double*)xb_out + b * ldxb, win, sizeof(double) * D, hipMemcpyDeviceToDevice, st()));
-        if (b + 1 < q) {
-          AGPCHK(acqb_border(g, m + np, noise));
-          AGPCHK(acqb.rescale(ctx, m + np + 1, D, (const double*)g.scales));
-        }
-      }
-    }
-    return AGP_OK;
-  }
-  // ---- joint batches ("ACQUISITION FUNCTIONS", paragraph "Joint batches"; agp_acq_joint.h, agp_acq_joint_host.h) -----
-  // A set is q optimised points and the n pending ones.  Per chunk of floor(4096 / q) sets and pass: K*m and W of the chunk's points
-  // (the two launches of acq_pass), k_acqj_cov, k_acqj_set, and with the gradient k_acqj_weights, k_acq_contract on the weight rows
-  // and one finishing kernel: seven launches, nothing waits for the stream.  K*m, W and the record of the pending points are formed
-  // once per call, in workspaces of the call's own.
-  AcqJointWs acqj;
-  agp_status acqj_begin(Latent& g, const AcqPred& pr, const void* xp, int64_t ldp, int64_t n) {
-    if constexpr (std::is_same<T, double>::value) {
-      if (n == 0) return AGP_OK;
-      (void)launch_kernelmatrix<T>(ctx, st(), (const T*)xp, ldp, (const int64_t*)nullptr, n, pr.Z, D, pr.m, D, (const T*)g.scales, g.k.kind,
-                                   kvar(g), acqj.Kp, pr.ld, rup64(n), pr.mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, pr.Zsc, pr.zn);
-      LAUNCHCHK(ctx);
-      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, acqj.Kp, pr.ld, pr.A, pr.ld, rup64(n), pr.mp, pr.mp, 0, acqj.Wp, pr.ld, nullptr, 0, nullptr,
-                                    nullptr, nullptr, 0)));
-      hipLaunchKernelGGL(k_acqj_cov, dim3(1), dim3(AJ_THREADS), 0, st(), 0, (int)n, (const double*)nullptr, (int64_t)0, (const double*)xp,
-                         ldp, (const double*)nullptr, (const double*)nullptr, (const double*)acqj.Kp, (const double*)acqj.Wp, pr.ld, pr.m,
-                         pr.a, (int)D, (const double*)g.scales, g.k.kind, (double)kvar(g), g.k.variance + jitter, (const double*)nullptr,
-                         acqj.pend);
-      LAUNCHCHK(ctx);
-    }
-    return AGP_OK;
-  }
-  // alpha (and, with grad, the groups' sums in pg_part and the point-to-point term in acqj.cross) of ns sets whose np = ns q points are
-  // the rows of x
-  agp_status acqj_pass(Latent& g, const AcqPred& pr, const AcqParams& p, const double* x, int64_t ldx, const void* xp, int64_t ldp,
-                       int64_t n, int64_t q, int64_t ns, const void* eps, int64_t lde, int64_t S, bool grad, double* alpha, int* ng) {
-    if constexpr (std::is_same<T, double>::value) {
-      const int64_t np = ns * q;
-      (void)launch_kernelmatrix<T>(ctx, st(), x, ldx, (const int64_t*)nullptr, np, pr.Z, D, pr.m, D, (const T*)g.scales, g.k.kind, kvar(g),
-                                   pr.Kstar, pr.ld, rup64(np), pr.mp, 0, T(0), (const T*)nullptr, (T*)nullptr, 0, 0, pr.Zsc, pr.zn);
-      LAUNCHCHK(ctx);
-      AGPCHK((gemm_nt<T, EPI_STORE>(ctx, pr.Kstar, pr.ld, pr.A, pr.ld, rup64(np), pr.mp, pr.mp, 0, pr.W, pr.ld, nullptr, 0, nullptr,
-                                    nullptr, nullptr, 0)));
-      hipLaunchKernelGGL(k_acqj_cov, dim3((unsigned)ns), dim3(AJ_THREADS), 0, st(), (int)q, (int)n, x, ldx, (const double*)xp, ldp,
-                         (const double*)pr.Kstar, (const double*)pr.W, (const double*)acqj.Kp, (const double*)acqj.Wp, pr.ld, pr.m, pr.a,
-                         (int)D, (const double*)g.scales, g.k.kind, (double)kvar(g), g.k.variance + jitter,
-                         n > 0 ? (const double*)acqj.pend : (const double*)nullptr, acqj.rec);
-      hipLaunchKernelGGL(k_acqj_set, dim3((unsigned)ns), dim3(AJ_THREADS), 0, st(), p, (int)(q + n), (int)S, (const double*)eps, lde,
-                         (const double*)acqj.rec, grad ? 1 : 0, alpha, acqj.bar, acqj.bad);
-      LAUNCHCHK(ctx);
-      if (grad) {
-        hipLaunchKernelGGL(k_acqj_weights, dim3((unsigned)((pr.m + AJ_THREADS - 1) / AJ_THREADS), (unsigned)ns), dim3(AJ_THREADS), 0, st(),
-                           (int)q, (int)n, x, ldx, (const double*)xp, ldp, (const double*)pr.W, (const double*)acqj.Wp, pr.ld, pr.m, pr.a,
-                           (int)D, (const double*)g.scales, g.k.kind, (double)kvar(g), (const double*)acqj.bar, acqj.V, pr.ld, acqj.cross);
-        *ng = acq_contract_launch<true>(st(), x, ldx, np, pr.Z, pr.m, D, (const double*)g.scales, g.k.kind, (double)kvar(g), pr.a,
-                                        (const double*)acqj.V, pr.ld, pg_part, acq.sc);
-        LAUNCHCHK(ctx);
-      }
-    }
-    return AGP_OK;
-  }
-  agp_status acquisition_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* xq,
-                               int64_t ldx, int64_t nsets, const void* eps, int64_t lde, int64_t S, void* alpha_out, void* grad_out,
-                               int64_t ldg) override {
-    const char* who = "agp_svgp_acquisition_joint: ";
-    AcqParams p;
-    AGPCHK(acq_check_handle(who));
-    AGPCHK(acq_check_latent(who, l, d, &p));
-    AGPCHK(acqj_check_args(ctx, who, p, D, xp, ldp, n, q, eps, lde, S));
-    if (nsets < 0 || ldx < D || (grad_out && ldg < D) || (nsets > 0 && (!xq || !alpha_out))) {
-      ctx->err = std::string(who) + "n_sets >= 0, xq and alpha_out must not be NULL, ldx >= D, ldg >= D when grad_out is given";
-      return AGP_ERR_INVALID;
-    }
-    if (nsets == 0) return AGP_OK;
-    if constexpr (std::is_same<T, double>::value) {
-      Latent& g = lat[l];
-      AGPCHK(acq_prepare(g, false));
-      AGPCHK(acqj.ensure(ctx, mp, D));
-      const AcqPred pr = acq_latent_pred(g);
-      AGPCHK(acqj_begin(g, pr, xp, ldp, n));
-      const int64_t spc = PG_CH / q;  // sets per chunk: a tuple never straddles two chunks
-      for (int64_t s = 0; s < nsets; s += spc) {
-        const int64_t ns = (nsets - s) < spc ? (nsets - s) : spc;
-        const double* x = (const double*)xq + s * q * ldx;
-        int ng = 0;
-        AGPCHK(acqj_pass(g, pr, p, x, ldx, xp, ldp, n, q, ns, eps, lde, S, grad_out != nullptr, (double*)alpha_out + s, &ng));
-        if (grad_out) {
-          hipLaunchKernelGGL(k_acqj_grad, grid1(ns * q * D), dim3(256), 0, st(), ns * q, (int)D, ng, (const double*)pg_part,
-                             (const double*)acqj.cross, (const double*)g.scales, (double*)grad_out + s * q * ldg, ldg);
-          LAUNCHCHK(ctx);
-        }
-      }
-    }
-    return AGP_OK;
-  }
-  agp_status acq_maximize_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* x0,
-                                int64_t ldx0, int64_t R, const void* eps, int64_t lde, int64_t S, const agp_pw_ascent_opts* o,
-                                void* x_out, int64_t ldxo, void* a_out, void* best_x, int64_t ldb, void* best_a,
-                                void* best_idx) override {
-#pragma clang fp contract(off)
-    const char* who = "agp_svgp_acq_maximize_joint: ";
-    auto invalid = [&](const char* what) {
-      ctx->err = std::string(who) + what;
-      return AGP_ERR_INVALID;
-    };
-    AcqParams p;
-    PwAscentBox box;
-    AGPCHK(acq_check_handle(who));
-    AGPCHK(acq_check_latent(who, l, d, &p));
-    AGPCHK(acqj_check_args(ctx, who, p, D, xp, ldp, n, q, eps, lde, S));
-    if (!x0) return invalid("x0 must be given");
-    AGPCHK(acq_check_opts(ctx, who, D, o, &box));
-    if (!x_out && !a_out && !best_x && !best_a && !best_idx) return invalid("at least one output must be given");
-    if (R < 1 || R >= ((int64_t)1 << 31) / AGP_ACQ_JOINT_MAX_Q) return invalid("n_starts >= 1 and n_starts * 16 below 2^31");
-    if (ldx0 < D) return invalid("ldx0 >= D");
-    if (x_out && ldxo < D) return invalid("ldxo >= D when x_out is given");
-    if (best_x && ldb < D) return invalid("ldb >= D when best_x is given");
-    if constexpr (std::is_same<T, double>::value) {
-      Latent& g = lat[l];
-      AGPCHK(acq_prepare(g, true));
-      AGPCHK(acq.ensure_particles(ctx, R * q, D));
-      AGPCHK(acqj.ensure(ctx, mp, D));
-      const AcqPred pr = acq_latent_pred(g);
-      AGPCHK(acqj_begin(g, pr, xp, ldp, n));
-      const int64_t spc = PG_CH / q;
-      for (int64_t s = 0; s < R; s += spc) {
-        const int64_t ns = (R - s) < spc ? (R - s) : spc, np = ns * q;
-        double* x = acq.X + s * q * D;
-        hipLaunchKernelGGL(k_acq_init, grid1(np * D), dim3(256), 0, st(), np, (int)D, (const double*)x0 + s * q * ldx0, ldx0, box, x,
-                           acq.mo, acq.vo);
-        LAUNCHCHK(ctx);
-        double b1k = 1.0, b2k = 1.0;
-        for (int k = 0; k <= o->steps; ++k) {
-          const bool fin = k == o->steps;  // the pass after the last step: alpha at the final tuple
-          int ng = 0;
-          AGPCHK(acqj_pass(g, pr, p, x, D, xp, ldp, n, q, ns, eps, lde, S, !fin, acq.A + s, &ng));
-          if (fin) break;
-          b1k *= o->beta1, b2k *= o->beta2;
-          hipLaunchKernelGGL(k_acqj_step, grid1(np * D), dim3(256), 0, st(), np, (int)D, ng, (const double*)pg_part,
-                             (const double*)acqj.cross, (const double*)g.scales, o->beta1, o->beta2, 1.0 - b1k, 1.0 - b2k, o->eps, box, x,
-                             acq.mo, acq.vo);
-          LAUNCHCHK(ctx);
-        }
-      }
-      if (best_x || best_a || best_idx) {  // a tuple is one row of q D values for the best-start rule
-        hipLaunchKernelGGL(k_pw_ascent_best, dim3(1), dim3(256), 0, st(), (const double*)acq.X, (const double*)acq.A, R, q * D, 1.0,
-                           best_x ? acqj.bx : (double*)nullptr, q * D, (double*)best_a, (int64_t*)best_idx);
-        LAUNCHCHK(ctx);
-        if (best_x)
-          HIPCHK(ctx, hipMemcpy2DAsync(best_x, sizeof(double) * ldb, acqj.bx, sizeof(double) * D, sizeof(double) * D, q,
-                                       hipMemcpyDeviceToDevice, st()));
-      }
-      if (x_out)
-        HIPCHK(ctx, hipMemcpy2DAsync(x_out, sizeof(double) * ldxo, acq.X, sizeof(double) * D, sizeof(double) * D, R * q,
-                                     hipMemcpyDeviceToDevice, st()));
-      if (a_out) HIPCHK(ctx, hipMemcpyAsync(a_out, acq.A, sizeof(double) * R, hipMemcpyDeviceToDevice, st()));
-    }
+  agp_status acq_open(int l, bool ascent, AcqModel* model, AcqDriver** plain, AcqJointDriver** joint) override {
+    AGPCHK(acq_prepare(lat[l], ascent));
+    *model = acq_model(lat[l]);
+    *plain = &acqd;
+    if (joint) *joint = &acqjd;
     return AGP_OK;
   }
   // AGP_VEC_APRED / AGP_MAT_APRED of agp_svgp_get_matrix: the two objects of the predictor after ensure_pred, for every class
@@ -6298,26 +5946,28 @@ agp_status agp_acq_moments(agp_ctx* ctx, const agp_acq_desc* desc, int64_t n, co
 agp_status agp_svgp_acquisition(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xt, int64_t ldx, int64_t n_t,
                                 void* alpha_out, void* grad_out, int64_t ldg) {
   HCHKF(h);
-  return h->impl->acquisition(latent, desc, xt, ldx, n_t, alpha_out, grad_out, ldg);
+  return AcqDriver::evaluate(*h->impl, latent, desc, (const double*)xt, ldx, n_t, (double*)alpha_out, (double*)grad_out, ldg);
 }
 agp_status agp_svgp_acq_maximize(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* x0, int64_t ldx0, int64_t n_starts,
                                  const agp_pw_ascent_opts* opts, void* x_out, int64_t ldxo, void* a_out, void* best_x, void* best_a,
                                  void* best_idx) {
   HCHKF(h);
-  return h->impl->acq_maximize(latent, desc, x0, ldx0, n_starts, opts, x_out, ldxo, a_out, best_x, best_a, best_idx);
+  return AcqDriver::maximize(*h->impl, latent, desc, (const double*)x0, ldx0, n_starts, opts, (double*)x_out, ldxo, (double*)a_out,
+                             (double*)best_x, (double*)best_a, (int64_t*)best_idx);
 }
 agp_status agp_svgp_acquisition_pending(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xp, int64_t ldp,
                                         int64_t n_pending, double noise, const void* xt, int64_t ldx, int64_t n_t, void* alpha_out,
                                         void* grad_out, int64_t ldg) {
   HCHKF(h);
-  return h->impl->acquisition_pending(latent, desc, xp, ldp, n_pending, noise, xt, ldx, n_t, alpha_out, grad_out, ldg);
+  return AcqDriver::evaluate_pending(*h->impl, latent, desc, (const double*)xp, ldp, n_pending, noise, (const double*)xt, ldx, n_t,
+                                     (double*)alpha_out, (double*)grad_out, ldg);
 }
 agp_status agp_svgp_acq_maximize_batch(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xp, int64_t ldp,
                                        int64_t n_pending, double noise, int64_t q, const void* x0, int64_t ldx0, int64_t n_starts,
                                        const agp_pw_ascent_opts* opts, void* xb_out, int64_t ldxb, void* ab_out, void* idxb_out) {
   HCHKF(h);
-  return h->impl->acq_maximize_batch(latent, desc, xp, ldp, n_pending, noise, q, x0, ldx0, n_starts, opts, xb_out, ldxb, ab_out,
-                                     idxb_out);
+  return AcqDriver::maximize_batch(*h->impl, latent, desc, (const double*)xp, ldp, n_pending, noise, q, (const double*)x0, ldx0,
+                                   n_starts, opts, (double*)xb_out, ldxb, (double*)ab_out, (int64_t*)idxb_out);
 }
 agp_status agp_svgp_predict_y(agp_svgp* h, const void* xt, int64_t ldx, int64_t n_t, void* y_out) {
   HCHKF(h);
@@ -6544,15 +6194,17 @@ agp_status agp_svgp_acquisition_joint(agp_svgp* h, int32_t latent, const agp_acq
                                       int64_t n_pending, int64_t q, const void* xq, int64_t ldx, int64_t n_sets, const void* eps,
                                       int64_t lde, int64_t S, void* alpha_out, void* grad_out, int64_t ldg) {
   HCHK(h);
-  return h->impl->acquisition_joint(latent, desc, xp, ldp, n_pending, q, xq, ldx, n_sets, eps, lde, S, alpha_out, grad_out, ldg);
+  return AcqJointDriver::evaluate(*h->impl, latent, desc, (const double*)xp, ldp, n_pending, q, (const double*)xq, ldx, n_sets,
+                                  (const double*)eps, lde, S, (double*)alpha_out, (double*)grad_out, ldg);
 }
 agp_status agp_svgp_acq_maximize_joint(agp_svgp* h, int32_t latent, const agp_acq_desc* desc, const void* xp, int64_t ldp,
                                        int64_t n_pending, int64_t q, const void* x0, int64_t ldx0, int64_t n_starts, const void* eps,
                                        int64_t lde, int64_t S, const agp_pw_ascent_opts* opts, void* x_out, int64_t ldxo, void* a_out,
                                        void* best_x, int64_t ldb, void* best_a, void* best_idx) {
   HCHK(h);
-  return h->impl->acq_maximize_joint(latent, desc, xp, ldp, n_pending, q, x0, ldx0, n_starts, eps, lde, S, opts, x_out, ldxo, a_out,
-                                     best_x, ldb, best_a, best_idx);
+  return AcqJointDriver::maximize(*h->impl, latent, desc, (const double*)xp, ldp, n_pending, q, (const double*)x0, ldx0, n_starts,
+                                  (const double*)eps, lde, S, opts, (double*)x_out, ldxo, (double*)a_out, (double*)best_x, ldb,
+                                  (double*)best_a, (int64_t*)best_idx);
 }
 agp_status agp_pathwise_info(agp_pathwise* p, int32_t* n_latent, int32_t* n_features, int32_t* n_samples, int64_t* m, int64_t* D) {
   if (!p) return AGP_ERR_INVALID;

@@ -26,6 +26,13 @@ struct KernelHost {
   std::vector<double> scales;  // length D
 };
 
+namespace agp {
+struct AcqParams;  // agp_acq.h
+}
+struct AcqModel;  // agp_acq_host.h
+struct AcqDriver;
+struct AcqJointDriver;  // agp_acq_joint_host.h
+
 struct SvgpBase {
   agp_ctx* ctx = nullptr;
   agp_svgp_desc desc{};
@@ -189,26 +196,13 @@ struct SvgpBase {
   virtual agp_status predict_f(const void* xt, int64_t ldx, int64_t nt, void* mu, void* var) = 0;
   // input gradients of the predictive moments ("PREDICTIVE GRADIENTS"; Svgp<T>::predict_f_grad serves every class)
   virtual agp_status predict_f_grad(const void* xt, int64_t ldx, int64_t nt, void* dmu, void* dvar, int64_t ldg) = 0;
-  // acquisition functions of one latent and their multi-start ascent ("ACQUISITION FUNCTIONS"; Svgp<T> serves every class), and the
-  // predictor's two objects behind them (AGP_VEC_APRED / AGP_MAT_APRED of agp_svgp_get_matrix)
-  virtual agp_status acquisition(int l, const agp_acq_desc* d, const void* xt, int64_t ldx, int64_t nt, void* alpha, void* grad,
-                                 int64_t ldg) = 0;
-  virtual agp_status acq_maximize(int l, const agp_acq_desc* d, const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o,
-                                  void* x_out, int64_t ldxo, void* a_out, void* best_x, void* best_a, void* best_idx) = 0;
-  // the same two conditioned on pending points ("ACQUISITION FUNCTIONS", paragraph "Pending points")
-  virtual agp_status acquisition_pending(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, double noise,
-                                         const void* xt, int64_t ldx, int64_t nt, void* alpha, void* grad, int64_t ldg) = 0;
-  virtual agp_status acq_maximize_batch(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, double noise, int64_t q,
-                                        const void* x0, int64_t ldx0, int64_t R, const agp_pw_ascent_opts* o, void* xb_out, int64_t ldxb,
-                                        void* ab_out, void* idxb_out) = 0;
-  // the joint Monte-Carlo criteria of q points and n pending ones ("ACQUISITION FUNCTIONS", paragraph "Joint batches")
-  virtual agp_status acquisition_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* xq,
-                                       int64_t ldx, int64_t nsets, const void* eps, int64_t lde, int64_t S, void* alpha, void* grad,
-                                       int64_t ldg) = 0;
-  virtual agp_status acq_maximize_joint(int l, const agp_acq_desc* d, const void* xp, int64_t ldp, int64_t n, int64_t q, const void* x0,
-                                        int64_t ldx0, int64_t R, const void* eps, int64_t lde, int64_t S, const agp_pw_ascent_opts* o,
-                                        void* x_out, int64_t ldxo, void* a_out, void* best_x, int64_t ldb, void* best_a,
-                                        void* best_idx) = 0;
+  // acquisition functions of one latent ("ACQUISITION FUNCTIONS"): AcqDriver / AcqJointDriver (agp_acq_host.h, agp_acq_joint_host.h)
+  // serve every class and ask the handle two things.  acq_check refuses, for the entry point `who`, the handles, descriptors, latents
+  // and kernels that have no acquisition function, and touches nothing; acq_open readies the predictor of latent l and the chunk
+  // workspaces (with those of an ascent), and hands out its view of them and the handle's drivers.  Also here: the predictor's two
+  // objects (AGP_VEC_APRED / AGP_MAT_APRED of agp_svgp_get_matrix)
+  virtual agp_status acq_check(const char* who, int l, const agp_acq_desc* d, agp::AcqParams* p) = 0;
+  virtual agp_status acq_open(int l, bool ascent, AcqModel* model, AcqDriver** plain, AcqJointDriver** joint) = 0;
   virtual agp_status get_predictor(int l, int which, void* out, int64_t ldo, int64_t cap) = 0;
   virtual agp_status predict_y(const void* xt, int64_t ldx, int64_t nt, void* out) = 0;
   virtual agp_status proba_y(const void* xt, int64_t ldx, int64_t nt, const double* nodes, const double* weights,

@@ -245,6 +245,36 @@ def test_bit_level_contract(env, name):
     assert L.agp_svgp_check_status(h) == 0
 
 
+def test_the_families_share_workspaces_without_disturbing_one_another(env):
+    """The plain, greedy-batch and joint maximisers share the predictor's chunk workspaces, the particle state and the group sums on
+    one handle.  Each of them called twice, with a joint evaluation (gradient included) between the two rounds, gives the same bits:
+    nothing a call leaves behind reaches the next.  m = 65 (mp = 128), D = 3, 4097 starts -- two chunks of points, three of pairs --
+    two steps, q = 2 with one pending point."""
+    AGP = env["AGP"]
+    name = "m65-logistic-m32-ard"
+    model = _model(name)
+    D, spread, ctr = J._box(name)
+    R, q, S = 4097, 2, 8
+    rng = np.random.default_rng(20)
+    X0 = ctr + spread * rng.uniform(-1.3, 1.3, size=(R, q, D))
+    P = ctr + spread * rng.uniform(-1.3, 1.3, size=(1, D))
+    lo, hi, lr = ctr - 2.0 * spread, ctr + 2.0 * spread, np.full(D, 0.03 * spread)
+    eps = J.table(S, q + 1)
+    py, kw = AGP.UCB(2.0), dict(steps=2, lr=lr, full=True)
+
+    def round_():
+        return (AGP.maximize_acquisition(model, py, X0[:, 0], (lo, hi), **kw),
+                AGP.maximize_acquisition_batch(model, py, q, X0[:, 0], (lo, hi), pending=P, **kw),
+                AGP.maximize_acquisition_joint(model, py, X0, (lo, hi), base_samples=eps, pending=P, **kw))
+
+    first = round_()
+    between = AGP.acquisition_joint(model, py, X0[:5], grad=True, base_samples=eps, pending=P)
+    second = round_()
+    assert first[0][3].shape == (R, D) and first[2][3].shape == (R, q, D) and np.all(np.isfinite(between[1]))
+    for a, b in zip(first, second):
+        assert len(a) == len(b) and all(_same(u, v) for u, v in zip(a, b))
+
+
 # ---- 6. degenerate sets -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["m65-logistic-m32-ard", "d1-m63-r63"])
 def test_degenerate_sets(env, name):
