@@ -20,6 +20,9 @@ def _vgp_cases():
         for natural, opt in ((True, "descent"), (False, "adam")):
             out[f"{link}-40-{'nat' if natural else 'cla'}-{opt}"] = dict(link=link, N=40, K=3, natural=natural, opt=opt)
     out["softmax-70-k2-nat-descent"] = dict(link="softmax", N=70, K=2, natural=True, opt="descent")  # crosses the 64-tile edge
+    # class counts at which k_mc_local changes shape (tests/_multiclass_cases.py): K = 10 -> 16 lanes per draw, K = 17 -> 32
+    out["softmax-40-k10-nat-descent"] = dict(link="softmax", N=40, K=10, natural=True, opt="descent")
+    out["logisticsoftmax-70-k17-cla-adam"] = dict(link="logisticsoftmax", N=70, K=17, natural=False, opt="adam")
     return out
 
 
@@ -65,19 +68,24 @@ def trajectory(name):
     return dict(ref=ref, mu=mus, Sigma=Sigmas, elbo=elbos, alphas=list(ref.alphas), counters=ref.counters(), margin=min(ref.margins))
 
 
-# ---- the sparse model: m = 70 inducing points, N = 400, D = 3, K = 3, 10 steps; MCIntegrationVI (B = N) and MCIntegrationSVI(150) on
-# the restatement's index stream ----------------------------------------------------------------------------------------------------
+# ---- the sparse model: m = 70 inducing points, N = 400, D = 3, K = 3 (one case: K = 10), 10 steps; MCIntegrationVI (B = N) and
+# MCIntegrationSVI(150) on the restatement's index stream ------------------------------------------------------------------------------
 SPARSE = dict(m=70, N=400, D=3, K=3, B=150, steps=10)
 SPARSE_CASES = {f"{link}-{'svi' if stoch else 'vi'}-{'nat' if natural else 'cla'}-{opt}": dict(link=link, stoch=stoch, natural=natural, opt=opt)
                 for link, stoch, natural, opt in (("softmax", False, True, "descent"), ("logisticsoftmax", False, False, "adam"),
                                                   ("softmax", True, False, "adam"), ("logisticsoftmax", True, True, "descent"))}
+SPARSE_CASES["softmax-svi-k10-nat-descent"] = dict(link="softmax", stoch=True, natural=True, opt="descent", K=10)
+
+
+def sparse_K(case):
+    return case.get("K", SPARSE["K"])
 
 
 def sparse_data(case):
     rng = np.random.default_rng(23)
     N, D, m = SPARSE["N"], SPARSE["D"], SPARSE["m"]
     X = rng.standard_normal((N, D))
-    c = classes(X, SPARSE["K"], rng)
+    c = classes(X, sparse_K(case), rng)
     Z = X[rng.permutation(N)[:m]].copy()
     idx = [np.sort(rng.choice(N, SPARSE["B"], replace=False)) for _ in range(SPARSE["steps"])] if case["stoch"] else None
     return X, c, Z, idx
@@ -87,7 +95,7 @@ def sparse_data(case):
 def sparse_trajectory(name):
     case = SPARSE_CASES[name]
     X, c, Z, idx = sparse_data(case)
-    ref = M.McSparseRef(kernel(), case["link"], SPARSE["K"], Z, NMC, SEED, make_opt(case["opt"]), natural=case["natural"], jitter=JITTER)
+    ref = M.McSparseRef(kernel(), case["link"], sparse_K(case), Z, NMC, SEED, make_opt(case["opt"]), natural=case["natural"], jitter=JITTER)
     rho = SPARSE["N"] / SPARSE["B"] if case["stoch"] else 1.0
     mus, Sigmas, elbos = [], [], []
     for it in range(SPARSE["steps"]):

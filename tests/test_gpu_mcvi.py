@@ -57,7 +57,7 @@ def _sparse_model(AGP, case, seed=CS.SEED):
     X, c, Z, idx = CS.sparse_data(case)
     kw = dict(nMC=CS.NMC, optimiser=_opt(AGP, case["opt"]), natural=case["natural"], seed=seed)
     inf = AGP.MCIntegrationSVI(CS.SPARSE["B"], **kw) if case["stoch"] else AGP.MCIntegrationVI(**kw)
-    return X, c + 1, idx, AGP.SVGP(_kernel(AGP), _lik(AGP, case["link"], CS.SPARSE["K"]), inf, Z, optimiser=False)
+    return X, c + 1, idx, AGP.SVGP(_kernel(AGP), _lik(AGP, case["link"], CS.sparse_K(case)), inf, Z, optimiser=False)
 
 
 def _full_state(model):
@@ -70,7 +70,7 @@ def _full_state(model):
 
 
 # ---- 1. the table -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [2, 3, 8])
+@pytest.mark.parametrize("K", [2, 3, 8, 17, 64])
 def test_mc_normals_bit_identical(env, K):
     """the device's table equals the host Philox table bit for bit: nMC in {1, 63, 200, 1000}, streams 2 and 3, two values of t"""
     AGP = env["AGP"]
@@ -135,7 +135,7 @@ def test_vgp_trajectory_parity(env, name):
 
 @pytest.mark.parametrize("name", list(CS.SPARSE_CASES))
 def test_svgp_trajectory_parity(env, name):
-    """m = 70, N = 400, D = 3, K = 3, 10 steps, MCIntegrationVI (B = N) and MCIntegrationSVI(150) on the restatement's index stream:
+    """m = 70, N = 400, D = 3, K = 3 (and one case at K = 10), 10 steps, MCIntegrationVI (B = N) and MCIntegrationSVI(150) on the restatement's index stream:
     the same assertions; then predict_f, predict_y and proba_y on 57 test points"""
     AGP = env["AGP"]
     case, tr = CS.SPARSE_CASES[name], CS.sparse_trajectory(name)
@@ -149,7 +149,8 @@ def test_svgp_trajectory_parity(env, name):
     assert _rel(np.stack(AGP.predict_f(model, Xt)), mr) < 1e-8
     pr = M.link_proba(case["link"], mr)
     pa = AGP.proba_y(model, Xt)
-    assert sorted(pa) == [1, 2, 3] and _rel(np.stack([pa[k] for k in (1, 2, 3)], axis=1), pr) < 1e-8
+    labels = list(range(1, CS.sparse_K(case) + 1))
+    assert sorted(pa) == labels and _rel(np.stack([pa[k] for k in labels], axis=1), pr) < 1e-8
     top2 = np.sort(mr, axis=0)
     clear = top2[-1] - top2[-2] > 1e-6
     assert clear.sum() > 40 and np.array_equal(np.asarray(AGP.predict_y(model, Xt))[clear], 1 + np.argmax(mr, axis=0)[clear])
