@@ -5402,6 +5402,7 @@ const char* agp_last_error(agp_ctx* ctx) { return ctx ? ctx->err.c_str() : "null
 
 #include "agp_blocks_host.h"
 #include "agp_select_host.h"
+#include "agp_kmv_host.h"
 
 #define DISPATCH(dtype, call_f64, call_f32)        \
   do {                                             \
@@ -5502,6 +5503,95 @@ agp_status agp_greedy_variance(agp_ctx* ctx, int32_t dtype, const agp_kernel_des
   }
   DISPATCH(dtype, bb_greedy<double>(ctx, k, x, n, ldx, D, m, tol, idx_out, z_out, ldz, factor_out, ldf, trace_out, n_selected_host),
            bb_greedy<float>(ctx, k, x, n, ldx, D, m, tol, idx_out, z_out, ldz, factor_out, ldf, trace_out, n_selected_host));
+}
+
+// what agp_kernel_matmul and agp_gp_cg_create refuse about x, D and the kernel (nullptr: fine); *unsupported: by AGP_ERR_UNSUPPORTED
+static const char* kmv_bad_args(const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D, bool* unsupported) {
+  *unsupported = false;
+  if (!x) return "null x";
+  if (n <= 0 || D <= 0) return "n > 0 and D > 0";
+  if (D > KMV_MAXD) {
+    *unsupported = true;
+    return "D <= 64 (the operand tiles of the fused product are sized for it; 65 .. 128 are not served)";
+  }
+  if (ldx < D) return "ldx >= D";
+  return kmv_bad_kernel(k, D);
+}
+
+agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                             const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
+                             int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo) {
+  if (!ctx) return AGP_ERR_INVALID;
+  bool unsupported = dtype != AGP_F64;
+  const char* bad = unsupported ? "Float64 only (dtype AGP_F64)" : kmv_bad_args(k, x, n, ldx, D, &unsupported);
+  if (!bad) {
+    if (!v || !out || (!sym && !y)) bad = "null v, out or y";
+    else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
+    else if (p <= 0) bad = "p > 0";
+    else if (sym ? n != p : ldy < D) bad = sym ? "sym: p == n" : "ldy >= D";
+    else if (ldv < r || ldo < r) bad = "ldv >= r and ldo >= r";
+    else if (col_groups < 0) bad = "col_groups >= 0";
+    else if (sym && !std::isfinite(diag_add)) bad = "a finite diag_add";
+  }
+  if (bad) {
+    ctx->err = std::string("agp_kernel_matmul: ") + bad;
+    return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  return bb_kernel_matmul(ctx, k, (const double*)x, n, ldx, (const double*)y, p, ldy, D, sym ? 1 : 0, diag_add, (const double*)v,
+                          ldv, r, col_groups, (double*)out, ldo);
+}
+
+agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D,
+                            double sigma2, int64_t precond_rank, agp_gp_cg** out, int64_t* rank_used_host) {
+  if (!ctx || !out) return AGP_ERR_INVALID;
+  *out = nullptr;
+  bool unsupported = false;
+  const char* bad = kmv_bad_args(k, x, n, ldx, D, &unsupported);
+  if (!bad && (!(sigma2 > 0.0) || !std::isfinite(sigma2))) bad = "a positive finite sigma2";
+  if (!bad && precond_rank < 0) bad = "precond_rank >= 0";
+  if (bad) {
+    ctx->err = std::string("agp_gp_cg_create: ") + bad;
+    return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  agp_gp_cg* h = new agp_gp_cg();
+  h->ctx = ctx, h->n = n, h->np = rup64(n), h->D = D, h->sigma2 = sigma2, h->nblk = (n + CG_ROWS - 1) / CG_ROWS;
+  agp_status s = cg_setup(h, k, (const double*)x, ldx, precond_rank);
+  if (s == AGP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) s = AGP_ERR_HIP;
+  if (s != AGP_OK) {
+    cg_release(h);
+    return s;
+  }
+  if (rank_used_host) *rank_used_host = h->k;
+  *out = h;
+  return AGP_OK;
+}
+
+agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter, int64_t check_every,
+                           void* a, int64_t lda, int32_t* iters_host, double* relres_host, int32_t* converged_host) {
+  if (!h) return AGP_ERR_INVALID;
+  const char* bad = nullptr;
+  if (!b || !a) bad = "null b or a";
+  else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
+  else if (ldb < r || lda < r) bad = "ldb >= r and lda >= r";
+  else if (!(tol >= 0.0)) bad = "tol >= 0";
+  else if (max_iter < 0) bad = "max_iter >= 0";
+  if (bad) {
+    h->ctx->err = std::string("agp_gp_cg_solve: ") + bad;
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(h->ctx->device);
+  return cg_solve(h, (const double*)b, ldb, (int)r, tol, max_iter, check_every > 0 ? check_every : 10, (double*)a, lda, iters_host,
+                  relres_host, converged_host);
+}
+
+agp_status agp_gp_cg_destroy(agp_gp_cg* h) {
+  if (!h) return AGP_ERR_INVALID;
+  DevGuard guard(h->ctx->device);
+  (void)hipStreamSynchronize(h->ctx->stream);
+  cg_release(h);
+  return AGP_OK;
 }
 
 // development / test hook (not part of include/agp_hip.h): how many task-graph factorisations the in-stream fallback re-ran

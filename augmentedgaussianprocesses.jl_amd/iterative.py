@@ -1,0 +1,265 @@
+"""IterativeGP -- the exact GP posterior at fixed hyper-parameters without an N x N matrix, and `kernel_matmul`, the operator it runs
+on: (K(X, Y) + c I) V for a block V with K never in memory (agp_kernel_matmul, csrc/agp_kmv.h), under a batched preconditioned CG
+(agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 64, one GPU, Gaussian likelihood.
+
+Not here: the log marginal likelihood and hyper-parameter learning (they need a stochastic log-determinant) -- learn the
+hyper-parameters with GP or SVGP and hand them over with IterativeGP.from_model -- and the full predictive covariance.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import capi
+from .likelihoods import GaussianLikelihood
+from .svgp import predict_f, predict_y, train_
+
+MAXR = 32  # right-hand sides per launch / per batched solve (KMV_MAXR)
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
+class _Ctx:
+    """a context of the C ABI on the current device and stream"""
+
+    def __init__(self, device: Optional[int] = None):
+        torch = _torch()
+        if not torch.cuda.is_available():
+            raise RuntimeError("no HIP device visible: augmentedgaussianprocesses.jl_amd has no CPU fallback")
+        self.dev = torch.device("cuda", device if device is not None else torch.cuda.current_device())
+        self.ctx = C.c_void_p()
+        st = capi.lib().agp_ctx_create(self.dev.index, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream), C.byref(self.ctx))
+        if st != capi.AGP_OK:
+            raise capi.AGPError(st, "agp_ctx_create failed")
+
+    def chk(self, st):
+        capi.check(self.ctx, st)
+
+    def dev_tensor(self, A):
+        torch = _torch()
+        t = A.to(device=self.dev, dtype=torch.float64) if isinstance(A, torch.Tensor) else torch.as_tensor(
+            np.array(A, dtype=np.float64), device=self.dev)
+        return t[:, None] if t.ndim == 1 else t
+
+    def close(self):
+        if self.ctx:
+            capi.lib().agp_ctx_destroy(self.ctx)
+            self.ctx = C.c_void_p()
+
+
+def _rows(t):
+    """a 2-D device tensor whose rows are contiguous (any row pitch is fine for the ABI)"""
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups):
+    torch = _torch()
+    L = capi.lib()
+    sym = Yd is None
+    Xd, Vd = _rows(Xd), _rows(Vd)
+    Yd = None if sym else _rows(Yd)
+    n, D = Xd.shape
+    p = n if sym else Yd.shape[0]
+    if Vd.shape[0] != p:
+        raise ValueError(f"V has {Vd.shape[0]} rows, K(X, Y) has {p} columns")
+    kd, keep = kernel.desc(D)
+    out = torch.empty(n, Vd.shape[1], dtype=torch.float64, device=cx.dev)
+    for c0 in range(0, Vd.shape[1], MAXR):
+        v, o = Vd[:, c0:c0 + MAXR], out[:, c0:c0 + MAXR]
+        cx.chk(L.agp_kernel_matmul(cx.ctx, capi.F64, C.byref(kd), C.c_void_p(Xd.data_ptr()), n, Xd.stride(0),
+                                   None if sym else C.c_void_p(Yd.data_ptr()), p, 0 if sym else Yd.stride(0), D, 1 if sym else 0,
+                                   float(diag_add), C.c_void_p(v.data_ptr()), Vd.stride(0), v.shape[1], int(col_groups),
+                                   C.c_void_p(o.data_ptr()), out.stride(0)))
+    del keep
+    return out
+
+
+def kernel_matmul(kernel, X, V, Y=None, diag_add: float = 0.0, col_groups: int = 0, device: Optional[int] = None):
+    """(K(X, Y) + diag_add I) V on the device without forming K.  X: n x D, Y: p x D, V: p x r (a vector counts as p x 1); Y=None is
+    the symmetric form K(X, X) + diag_add I, with an exact diagonal.  diag_add needs Y=None.  More than 32 columns are taken in
+    blocks of 32.  col_groups: 0 lets the library split the columns of K over workgroups; a positive value forces that many groups.
+    Arrays in, a NumPy array out; device tensors in, a device tensor out."""
+    if Y is not None and diag_add != 0.0:
+        raise ValueError("diag_add is added to the diagonal of K(X, X): it needs Y=None")
+    torch = _torch()
+    cx = _Ctx(device)
+    try:
+        vec = np.ndim(V) == 1
+        out = _kernel_matmul(cx, kernel, cx.dev_tensor(X), cx.dev_tensor(V), None if Y is None else cx.dev_tensor(Y), diag_add,
+                             col_groups)
+    finally:
+        cx.close()
+    if vec:
+        out = out[:, 0]
+    return out if isinstance(V, torch.Tensor) else out.cpu().numpy()
+
+
+class IterativeGP:
+    """IterativeGP(X, y, kernel; noise=1e-5, mean=None, tol=1e-8, max_iter=1000, precond_rank=64): the exact GP posterior at FIXED
+    hyper-parameters.  alpha = (K + noise I)^-1 (y - mean) is solved on first use by preconditioned CG on the matrix-free operator;
+    nothing of size N x N is ever stored.  The preconditioner is a pivoted partial Cholesky of K of rank `precond_rank` (0: none).
+    precond_rank and max_iter are interface defaults, not tuned.  mean: None, a constant, or one value per training point.
+
+    predict_f(model, Xt, cov=True) -> (mean, variance): the mean is one operator product; the variance costs ONE BATCHED CG RUN PER 32
+    TEST POINTS (k** - k*' (K + noise I)^-1 k*), so ask for it on as many points as are needed and no more.  predict_y adds the
+    noise.  model.solve(B) exposes the solver, model.info what the last solve did.  There is no train_: see GP / SVGP."""
+
+    def __init__(self, X, y, kernel, *, noise: float = 1e-5, mean=None, tol: float = 1e-8, max_iter: int = 1000,
+                 precond_rank: int = 64, check_every: int = 10, device: Optional[int] = None):
+        X = np.asarray(X, dtype=np.float64)
+        X = np.ascontiguousarray(X[:, None] if X.ndim == 1 else X)
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        if len(y) != X.shape[0]:
+            raise ValueError(f"There is not the same number of samples in X ({X.shape[0]}) and y ({len(y)})")
+        if not noise > 0:
+            raise ValueError("noise must be positive")
+        if mean is not None and not np.isscalar(mean) and len(mean) != X.shape[0]:
+            raise ValueError("a mean vector needs one value per training point")
+        self.X, self.y, self.kernel, self.noise, self.mean = X, y, copy.deepcopy(kernel), float(noise), mean
+        self.tol, self.max_iter, self.precond_rank, self.check_every = float(tol), int(max_iter), int(precond_rank), int(check_every)
+        self.N, self.D = X.shape
+        self.device = device
+        self.info = None
+        self.rank_used = None
+        self._cx = self._h = self._Xd = self._alpha = None
+
+    @classmethod
+    def from_model(cls, m, X, y, **kwargs):
+        """kernel, noise and prior mean of a trained GP or Gaussian-likelihood SVGP, on the data (X, y)"""
+        if not isinstance(getattr(m, "likelihood", None), GaussianLikelihood) or getattr(m, "n_latent", 1) != 1:
+            raise ValueError("IterativeGP.from_model takes a GP or an SVGP with a Gaussian likelihood")
+        mean = m.mean
+        if mean is not None and not np.isscalar(mean) and len(mean) != len(np.asarray(X)):
+            raise ValueError("the model's prior mean is a vector over other points: pass mean= explicitly")
+        kwargs.setdefault("mean", mean)
+        kwargs.setdefault("noise", m.likelihood.sigma2)
+        return cls(X, y, m.kernels[0], **kwargs)
+
+    # ---- device side ----
+    def _solver(self):
+        if self._h is None:
+            self._cx = _Ctx(self.device)
+            self._Xd = self._cx.dev_tensor(self.X)
+            kd, keep = self.kernel.desc(self.D)
+            h, used = C.c_void_p(), C.c_int64()
+            self._cx.chk(capi.lib().agp_gp_cg_create(self._cx.ctx, C.byref(kd), C.c_void_p(self._Xd.data_ptr()), self.N,
+                                                     self._Xd.stride(0), self.D, self.noise, self.precond_rank, C.byref(h),
+                                                     C.byref(used)))
+            del keep
+            self._h, self.rank_used = h, int(used.value)
+        return self._h
+
+    def _solve_dev(self, Bd, tol, max_iter):
+        """(K + noise I)^-1 B for a device tensor B (n x r, any r), with the per-column report"""
+        torch = _torch()
+        h = self._solver()
+        Bd = _rows(Bd)
+        A = torch.empty(Bd.shape, dtype=torch.float64, device=self._cx.dev)
+        its, res, conv = [], [], []
+        for c0 in range(0, Bd.shape[1], MAXR):
+            b, a = Bd[:, c0:c0 + MAXR], A[:, c0:c0 + MAXR]
+            r = b.shape[1]
+            it, rr, cv = (C.c_int32 * r)(), (C.c_double * r)(), (C.c_int32 * r)()
+            self._cx.chk(capi.lib().agp_gp_cg_solve(h, C.c_void_p(b.data_ptr()), Bd.stride(0), r, tol, max_iter, self.check_every,
+                                                    C.c_void_p(a.data_ptr()), A.stride(0), it, rr, cv))
+            its += list(it)
+            res += list(rr)
+            conv += [bool(v) for v in cv]
+        self.info = dict(iterations=np.array(its), residuals=np.array(res), converged=np.array(conv), rank_used=self.rank_used)
+        return A
+
+    def solve(self, B, tol: Optional[float] = None, max_iter: Optional[int] = None):
+        """(K(X, X) + noise I)^-1 B, B of N rows; what the solve did is in model.info (iterations, residuals = final |r| / |b|,
+        converged, per column).  Reaching max_iter is reported there, not raised."""
+        torch = _torch()
+        self._solver()
+        vec = np.ndim(B) == 1
+        Bd = self._cx.dev_tensor(B)
+        if Bd.shape[0] != self.N:
+            raise ValueError(f"B has {Bd.shape[0]} rows, the model {self.N} points")
+        A = self._solve_dev(Bd, self.tol if tol is None else float(tol), self.max_iter if max_iter is None else int(max_iter))
+        A = A[:, 0] if vec else A
+        return A if isinstance(B, torch.Tensor) else A.cpu().numpy()
+
+    def _mu0(self, n):
+        return 0.0 if self.mean is None else float(self.mean) if np.isscalar(self.mean) else np.asarray(self.mean, dtype=np.float64)
+
+    def alpha(self):
+        """(K + noise I)^-1 (y - mean), on the device (solved once)"""
+        if self._alpha is None:
+            self._solver()
+            self._alpha = self._solve_dev(self._cx.dev_tensor(self.y - self._mu0(self.N)), self.tol, self.max_iter)
+            self.alpha_info = self.info
+        return self._alpha
+
+    def close(self):
+        if self._h is not None:
+            capi.lib().agp_gp_cg_destroy(self._h)
+            self._h = None
+        if self._cx is not None:
+            self._cx.close()
+            self._cx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return f"Iterative exact Gaussian Process on {self.N} points (noise {self.noise:g})"
+
+
+@predict_f.register(IterativeGP)
+def _predict_f_iterative(model: IterativeGP, X_test, state=None, *, cov: bool = True, diag: bool = True, obsdim: int = 1):
+    """(mean, variance) of the latent at X_test, or the mean alone with cov=False.  The variance costs one batched CG run per 32 test
+    points.  diag=False (the full predictive covariance) is not built."""
+    if not diag:
+        raise NotImplementedError("IterativeGP.predict_f: diag=False (the full predictive covariance) is not built")
+    torch = _torch()
+    L = capi.lib()
+    alpha = model.alpha()
+    cx = model._cx
+    Xt = cx.dev_tensor(np.asarray(X_test, dtype=np.float64))
+    if obsdim == 2:
+        Xt = Xt.t().contiguous()
+    if Xt.shape[1] != model.D:
+        raise ValueError(f"X_test has {Xt.shape[1]} dimensions, the model {model.D}")
+    mu0 = 0.0 if model.mean is None or not np.isscalar(model.mean) else float(model.mean)  # (a vector mean lives on the training points)
+    mean = (_kernel_matmul(cx, model.kernel, Xt, alpha, model._Xd, 0.0, 0)[:, 0] + mu0).cpu().numpy()
+    if not cov:
+        return mean
+    kd, keep = model.kernel.desc(model.D)
+    nt = Xt.shape[0]
+    var = torch.empty(nt, dtype=torch.float64, device=cx.dev)
+    for c0 in range(0, nt, MAXR):
+        xt = Xt[c0:c0 + MAXR]
+        ks = torch.empty(model.N, xt.shape[0], dtype=torch.float64, device=cx.dev)  # K(X, Xt_chunk)
+        cx.chk(L.agp_kernelmatrix(cx.ctx, capi.F64, C.byref(kd), C.c_void_p(model._Xd.data_ptr()), model.N, model._Xd.stride(0), None,
+                                  C.c_void_p(xt.data_ptr()), xt.shape[0], Xt.stride(0), model.D, C.c_void_p(ks.data_ptr()),
+                                  ks.stride(0)))
+        sol = model._solve_dev(ks, model.tol, model.max_iter)
+        var[c0:c0 + MAXR] = kd.variance - (ks * sol).sum(dim=0)
+    del keep
+    return mean, var.cpu().numpy()
+
+
+@predict_y.register(IterativeGP)
+def _predict_y_iterative(model: IterativeGP, X_test, state=None, *, cov: bool = True, obsdim: int = 1):
+    """predict_f with the noise added to the variance"""
+    out = predict_f(model, X_test, cov=cov, obsdim=obsdim)
+    return (out[0], out[1] + model.noise) if cov else out
+
+
+@train_.register(IterativeGP)
+def _train_iterative(model: IterativeGP, *args, **kwargs):
+    raise NotImplementedError("IterativeGP has no train_: it is the posterior at fixed hyper-parameters (the log marginal likelihood "
+                              "needs a log-determinant this path does not form).  Learn them with GP or SVGP, then "
+                              "IterativeGP.from_model(m, X, y)")

@@ -372,6 +372,41 @@ agp_status agp_kmeans(agp_ctx* ctx, int32_t dtype, const void* x, int64_t n, int
 agp_status agp_greedy_variance(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
                                int64_t D, int64_t m, double tol, int64_t* idx_out, void* z_out, int64_t ldz,
                                void* factor_out, int64_t ldf, double* trace_out, int64_t* n_selected_host);
+/* ---- matrix-free exact GP: the kernel operator on a block, and batched preconditioned CG on it -------------------------------
+ * agp_kernel_matmul: out = (K(x, y) + diag_add * [sym]) v without K ever reaching memory (csrc/agp_kmv.h: both products on
+ * v_mfma_f64_16x16x4, the finished 64 x 64 tile handed from the first to the second in registers).  x is n x D (ldx), y p x D (ldy),
+ * v p x r (ldv), out n x r (ldo); AGP_F64 only, 1 <= r <= 32, D <= 64, all four kernels, a scale or ARD scales.  sym != 0: y is x
+ * (y and ldy are not read, p must equal n), diag_add is added on the diagonal, and the diagonal entries are exact: d2 = 0, the
+ * entry is variance + diag_add.  sym == 0: diag_add is not read.  Kernel values are agp_kernelmatrix's (GEMM form of d2 with the
+ * same repair of close points), within its element-wise budget; the product adds gamma_{p + R} sum_j |K_ij v_jc|, R = r padded to 16.
+ * col_groups: how many groups the column tiles of y are split over (each group leaves an n x r slice, a second kernel adds the
+ * slices in ascending order); 0 chooses from n, p and the number of CUs, at most 16.  No atomics, fixed summation orders: two calls
+ * agree bit for bit, and column c of out is a function of column c of v alone.  The Layout rules above hold.  Synchronises.
+ * Refused before anything is launched, outputs untouched: AGP_ERR_UNSUPPORTED for a dtype other than AGP_F64 and for D > 64;
+ * AGP_ERR_INVALID for r < 1, r > 32, n <= 0, p <= 0, D <= 0, col_groups < 0, ldx < D, ldy < D, ldv < r, ldo < r, sym with n != p,
+ * and a kernel descriptor agp_greedy_variance would refuse. */
+agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                             const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
+                             int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo);
+/* agp_gp_cg: solves (K(x, x) + sigma2 I) A = B for B n x r, r <= 32, by r INDEPENDENT conjugate-gradient recurrences that share
+ * every operator product (not block CG): each column has its own alpha, beta and residual, on the device; column dots are
+ * two-stage sums of fixed order.  A column whose recursive residual reaches |r| <= tol |b| is frozen -- its update is skipped --
+ * so its bits do not depend on the other columns, on max_iter or on how long the slowest column runs; a zero column of B gives a
+ * zero column, converged, with 0 iterations.  The host reads the per-column state every `check_every` iterations only
+ * (<= 0: 10; an interface default, not tuned).  Reaching max_iter is reported (converged_host[c] = 0), not an error.
+ * create: once per (x, kernel, sigma2 > 0); keeps a copy of x.  precond_rank = k > 0: preconditioner P = L L' + sigma2 I with L the
+ * n x k factor of agp_greedy_variance on the same x and kernel (fewer columns if its stop rule fires; *rank_used_host says how
+ * many), applied by Woodbury with the k x k matrix sigma2 I + L'L inverted once; 0: plain CG.  Same refusals as agp_kernel_matmul
+ * for its x, D and kernel, plus sigma2 not positive and finite, precond_rank < 0.
+ * solve: b n x r (ldb >= r), a n x r (lda >= r), device; iters_host / relres_host / converged_host: nullable host arrays of r
+ * (iterations taken, final recursive |r| / |b|, 1 if converged).  Refused: r < 1, r > 32, ldb < r, lda < r, tol < 0 or NaN,
+ * max_iter < 0.  Synchronises. */
+typedef struct agp_gp_cg agp_gp_cg;
+agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D,
+                            double sigma2, int64_t precond_rank, agp_gp_cg** out, int64_t* rank_used_host);
+agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter, int64_t check_every,
+                           void* a, int64_t lda, int32_t* iters_host, double* relres_host, int32_t* converged_host);
+agp_status agp_gp_cg_destroy(agp_gp_cg* h);
 /* MFMA microbenchmark: TFLOP/s of back-to-back v_mfma_{f64,f32}_16x16x4 (roofline ceiling measurement) */
 agp_status agp_mfma_peak(agp_ctx* ctx, int32_t dtype, double* tflops_host);
 

@@ -1,0 +1,89 @@
+"""Times the matrix-free kernel operator (agp_kernel_matmul, csrc/agp_kmv.h): out = K(X, X) V, fp64, HIP events around the call (which
+prepares the Y side, launches and synchronises), against the only alternative there was before it: agp_kernelmatrix into memory
+(8 n p bytes) followed by a dense GEMM (torch.mm, i.e. the vendor BLAS: the C ABI has no stand-alone GEMM entry point).
+
+    python tools/bench_kmv.py [--n 32768] [--D 32] [--r 1 32] [--reps 5] [--no-dense] [--big 100000]
+
+--big: the same product at a size whose kernel matrix (80 GB at 1e5) is not formed at all; 0 skips it.
+Prints one JSON line; kernel values per second count n * p evaluations.  A record, not a gate.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import __graft_entry__ as g
+
+
+def timed(fn, reps):
+    ms = []
+    for rep in range(reps + 1):  # the first call is the warm-up
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if rep:
+            ms.append(e0.elapsed_time(e1))
+    ms.sort()
+    return dict(best_ms=round(ms[0], 3), median_ms=round(ms[len(ms) // 2], 3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=32768)
+    ap.add_argument("--D", type=int, default=32)
+    ap.add_argument("--r", type=int, nargs="+", default=[1, 32])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--scale", type=float, default=0.5)
+    ap.add_argument("--no-dense", action="store_true")
+    ap.add_argument("--big", type=int, default=100000)
+    a = ap.parse_args()
+    g.build()
+    import agp_amd as AGP
+    from agp_amd import capi
+
+    L = capi.lib()
+    ctx = C.c_void_p()
+    assert L.agp_ctx_create(0, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(ctx)) == 0
+    kd, keep = (AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale)).desc(a.D)
+    gen = torch.Generator("cuda").manual_seed(0)
+    res = dict(bench="kernel_matmul", D=a.D, sizes=[])
+
+    def fused(X, V, out):
+        n, r = X.shape[0], V.shape[1]
+        st = L.agp_kernel_matmul(ctx, capi.F64, C.byref(kd), X.data_ptr(), n, a.D, None, n, 0, a.D, 1, 0.0, V.data_ptr(), r, r, 0,
+                                 out.data_ptr(), r)
+        assert st == 0, L.agp_last_error(ctx)
+
+    for n in [a.n] + ([a.big] if a.big else []):
+        X = torch.rand(n, a.D, dtype=torch.float64, device="cuda", generator=gen)
+        dense = not a.no_dense and n == a.n
+        K = torch.empty(n, n, dtype=torch.float64, device="cuda") if dense else None
+        for r in a.r:
+            V = torch.randn(n, r, dtype=torch.float64, device="cuda", generator=gen)
+            out = torch.empty(n, r, dtype=torch.float64, device="cuda")
+            row = dict(n=n, r=r, fused=timed(lambda: fused(X, V, out), a.reps))
+            row["fused_gvalues_per_s"] = round(n * n / row["fused"]["best_ms"] / 1e6, 1)
+            if dense:
+                def two_step():
+                    st = L.agp_kernelmatrix(ctx, capi.F64, C.byref(kd), X.data_ptr(), n, a.D, None, X.data_ptr(), n, a.D, a.D,
+                                            K.data_ptr(), n)
+                    assert st == 0, L.agp_last_error(ctx)
+                    return torch.mm(K, V)
+
+                row["kernelmatrix_then_gemm"] = timed(two_step, a.reps)
+                ref = two_step()
+                row["max_abs_diff"] = float((ref - out).abs().max())
+            res["sizes"].append(row)
+        del X, K
+    L.agp_ctx_destroy(ctx)
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
