@@ -204,6 +204,10 @@ SYMBOLS = {
     "agp_gp_cg_create": (_I32, [_VP, _PK, _VP, _I64, _I64, _I64, _DBL, _I64, _PVP, _PI64]),
     "agp_gp_cg_solve": (_I32, [_VP, _VP, _I64, _I64, _DBL, _I64, _I64, _VP, _I64, _PI32, _PDBL, _PI32]),
     "agp_gp_cg_destroy": (_I32, [_VP]),
+    "agp_kernel_bilinear_grad": (_I32, [_VP, _I32, _PK, _VP, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _I64, _PDBL, _I32, _PDBL, _PDBL]),
+    "agp_gp_cg_solve_slq": (_I32, [_VP, _VP, _I64, _I64, _DBL, _I64, _I64, _VP, _I64, _VP, _I64, _PI32, _PDBL, _PI32, _PDBL, _PDBL]),
+    "agp_gp_cg_probes": (_I32, [_VP, _I64, _VP, _I64, C.c_uint64, C.c_uint32, _VP, _I64]),
+    "agp_gp_cg_precond_logdet": (_I32, [_VP, _PDBL]),
     "agp_svgp_online_snapshot": (_I32, [_VP, _I32, _VP, _I64, _VP, _PDBL]),
     "agp_svgp_set_online_prior": (_I32, [_VP, _I32, _VP, _I64, _I64, _VP, _I64, _VP, _DBL]),
     "agp_svgp_adopt_local": (_I32, [_VP, _VP]),

@@ -5586,6 +5586,70 @@ agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, 
                   relres_host, converged_host);
 }
 
+agp_status agp_kernel_bilinear_grad(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                    int64_t D, const void* u, int64_t ldu, const void* v, int64_t ldv, int64_t r,
+                                    const double* w_host, int32_t col_groups, double* dvar_host, double* dscales_host) {
+  if (!ctx) return AGP_ERR_INVALID;
+  bool unsupported = dtype != AGP_F64;
+  const char* bad = unsupported ? "Float64 only (dtype AGP_F64)" : kmv_bad_args(k, x, n, ldx, D, &unsupported);
+  if (!bad && k->kind == AGP_K_EXPONENTIAL) {
+    unsupported = true;
+    bad = "the ExponentialKernel has no derivative at coincident points: SqExponential, Matern-3/2 and Matern-5/2 only";
+  }
+  if (!bad) {
+    if (!u || !v || !dvar_host || !dscales_host) bad = "null u, v, dvar_host or dscales_host";
+    else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
+    else if (ldu < r || ldv < r) bad = "ldu >= r and ldv >= r";
+    else if (col_groups < 0) bad = "col_groups >= 0";
+    else
+      for (int64_t c = 0; w_host && c < r; ++c)
+        if (!std::isfinite(w_host[c])) bad = "finite weights";
+  }
+  if (bad) {
+    ctx->err = std::string("agp_kernel_bilinear_grad: ") + bad;
+    return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  return bb_kernel_bilinear_grad(ctx, k, (const double*)x, n, ldx, D, (const double*)u, ldu, (const double*)v, ldv, r, w_host,
+                                 col_groups, dvar_host, dscales_host);
+}
+
+agp_status agp_gp_cg_solve_slq(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter,
+                               int64_t check_every, void* a, int64_t lda, void* z0, int64_t ldz0, int32_t* iters_host,
+                               double* relres_host, int32_t* converged_host, double* bpb_host, double* quad_host) {
+  if (!h) return AGP_ERR_INVALID;
+  const char* bad = nullptr;
+  if (!b || !a || !z0 || !bpb_host || !quad_host) bad = "null b, a, z0, bpb_host or quad_host";
+  else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
+  else if (ldb < r || lda < r || ldz0 < r) bad = "ldb >= r, lda >= r and ldz0 >= r";
+  else if (!(tol >= 0.0)) bad = "tol >= 0";
+  else if (max_iter < 0) bad = "max_iter >= 0";
+  if (bad) {
+    h->ctx->err = std::string("agp_gp_cg_solve_slq: ") + bad;
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(h->ctx->device);
+  return cg_solve_slq(h, (const double*)b, ldb, (int)r, tol, max_iter, check_every > 0 ? check_every : 10, (double*)a, lda,
+                      (double*)z0, ldz0, iters_host, relres_host, converged_host, bpb_host, quad_host);
+}
+
+agp_status agp_gp_cg_probes(agp_gp_cg* h, int64_t t, const void* base, int64_t ldbase, uint64_t seed, uint32_t t0, void* out,
+                            int64_t ldo) {
+  if (!h) return AGP_ERR_INVALID;
+  if (!out || t < 1 || ldo < t || (base && ldbase < h->n + h->k)) {
+    h->ctx->err = "agp_gp_cg_probes: out, t >= 1, ldo >= t, and with base: ldbase >= n + rank_used";
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(h->ctx->device);
+  return cg_probes(h, t, (const double*)base, ldbase, seed, t0, (double*)out, ldo);
+}
+
+agp_status agp_gp_cg_precond_logdet(agp_gp_cg* h, double* logdet_host) {
+  if (!h || !logdet_host) return AGP_ERR_INVALID;
+  *logdet_host = (double)(h->n - h->k) * std::log(h->sigma2) + (h->k > 0 ? h->logdetM : 0.0);
+  return AGP_OK;
+}
+
 agp_status agp_gp_cg_destroy(agp_gp_cg* h) {
   if (!h) return AGP_ERR_INVALID;
   DevGuard guard(h->ctx->device);

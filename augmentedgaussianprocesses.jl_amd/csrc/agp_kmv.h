@@ -264,12 +264,13 @@ __global__ __launch_bounds__(256) void k_cg_dot(const double* __restrict__ A, co
 
 // init != 0: x = 0, r = B (n x r, ldb; columns >= r zero).  Otherwise alpha = rz / (p . q) from the partials of k_cg_dot,
 // x += alpha p, r -= alpha q on the active columns.  Both: part_rr[blk][c] = partial |r|^2, and Rt (nullable) = r transposed,
-// [c][i] with leading dimension ldt (the A operand of the preconditioner's first GEMM).
+// [c][i] with leading dimension ldt (the A operand of the preconditioner's first GEMM).  coef (nullable): this iteration's row of the
+// Lanczos table, [2][32]: workgroup 0 stores alpha per column (0 for a column that did not step); nothing else changes with it.
 __global__ __launch_bounds__(256) void k_cg_update(int init, const double* __restrict__ B, int64_t ldb, int rcols, int64_t n,
                                                    int64_t nblk, const CgScal* __restrict__ sc, const double* __restrict__ part_pq,
                                                    const double* __restrict__ P, const double* __restrict__ Q,
                                                    double* __restrict__ Xv, double* __restrict__ Rv, double* __restrict__ Rt,
-                                                   int64_t ldt, double* __restrict__ part_rr) {
+                                                   int64_t ldt, double* __restrict__ part_rr, double* __restrict__ coef) {
   __shared__ double red[256];
   const int tid = threadIdx.x, c = tid & 31;
   const int64_t r0 = blockIdx.x * (int64_t)CG_ROWS;
@@ -280,6 +281,7 @@ __global__ __launch_bounds__(256) void k_cg_update(int init, const double* __res
     act = pq > 0.0;  // (a breakdown is recorded by k_cg_direction, from the same sum)
     if (act) alpha = sc->rz[c] / pq;
   }
+  if (coef && blockIdx.x == 0 && tid < CG_LD) coef[c] = alpha;
   double s = 0.0;
   for (int q = tid >> 5; q < CG_ROWS; q += 8) {
     const int64_t i = r0 + q;
@@ -326,12 +328,12 @@ __global__ __launch_bounds__(256) void k_cg_precond(int64_t n, const double* __r
 // The end of an iteration (init != 0: of the set-up).  rz_new and |r|^2 from their partials; a column whose |r|^2 <= tol^2 |b|^2
 // becomes inactive and counts as converged (a zero column of B at once, with zero iterations); one whose p . q or r . z is not
 // positive breaks down: inactive, not converged.  Still active: p = z + (rz_new / rz) p.  Z == nullptr: no preconditioner, z = r and
-// r . z = |r|^2.  Workgroup 0 writes the next scalars.
+// r . z = |r|^2.  Workgroup 0 writes the next scalars, and beta per column into coef[32 + c] (nullable; 0 where p was not updated).
 __global__ __launch_bounds__(256) void k_cg_direction(int init, int64_t n, int64_t nblk, double tol2, const CgScal* __restrict__ sc,
                                                       CgScal* __restrict__ sc_next, const double* __restrict__ part_pq,
                                                       const double* __restrict__ part_rr, const double* __restrict__ part_rz,
                                                       const double* __restrict__ Rv, const double* __restrict__ Z,
-                                                      double* __restrict__ P) {
+                                                      double* __restrict__ P, double* __restrict__ coef) {
   const int tid = threadIdx.x, c = tid & 31;
   const int64_t r0 = blockIdx.x * (int64_t)CG_ROWS;
   const bool was = init ? true : sc->active[c] != 0;
@@ -357,6 +359,7 @@ __global__ __launch_bounds__(256) void k_cg_direction(int init, int64_t n, int64
       P[i * CG_LD + c] = init ? z : __builtin_fma(beta, P[i * CG_LD + c], z);
     }
   if (blockIdx.x == 0 && tid < CG_LD) {
+    if (coef) coef[CG_LD + c] = beta;
     sc_next->rz[c] = rz;
     sc_next->bb[c] = bb;
     sc_next->rr[c] = rr;
@@ -372,6 +375,21 @@ __global__ __launch_bounds__(256) void k_cg_export(const double* __restrict__ A,
   const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x, i = e / CG_LD;
   const int c = (int)(e % CG_LD);
   if (i < n && c < r) out[i * ldo + c] = A[e];
+}
+// out[i][c] (ldo) = scale * A[i][c] (n x 32), c < r: the copy of the first preconditioned residual z0 = P^-1 b
+__global__ __launch_bounds__(256) void k_cg_export_scaled(const double* __restrict__ A, int64_t n, int r, double scale,
+                                                          double* __restrict__ out, int64_t ldo) {
+  const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x, i = e / CG_LD;
+  const int c = (int)(e % CG_LD);
+  if (i < n && c < r) out[i * ldo + c] = scale * A[e];
+}
+// probes z ~ N(0, L L' + sigma2 I): out[i][c] (ldo) = Zl[i][c] (= L eps1, n x 64 with leading dimension ldz; nullable) + sigma E[c][i],
+// E the base normals, one row of length lde per probe with eps2 in its first n entries
+__global__ __launch_bounds__(256) void k_cg_probe(int64_t n, int r, const double* __restrict__ Zl, int64_t ldz, double sigma,
+                                                  const double* __restrict__ E, int64_t lde, double* __restrict__ out, int64_t ldo) {
+  const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x, i = e / CG_LD;
+  const int c = (int)(e % CG_LD);
+  if (i < n && c < r) out[i * ldo + c] = __builtin_fma(sigma, E[c * lde + i], Zl ? Zl[i * ldz + c] : 0.0);
 }
 // a = 0 (a small kernel instead of a memset node, so that a solve may be captured into a graph)
 __global__ __launch_bounds__(256) void k_cg_zero(double* __restrict__ a, int64_t cnt) {

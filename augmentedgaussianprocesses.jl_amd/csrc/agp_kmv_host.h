@@ -1,6 +1,8 @@
 // agp_kmv_host.h -- host drivers of the matrix-free kernel operator (agp_kmv.h): the prepared Y side (KmvOp), the launch of
 // k_kmv / k_kmv_sum (kmv_apply), the one-shot product behind agp_kernel_matmul (bb_kernel_matmul) and the batched preconditioned
-// CG on it with its solver handle (agp_gp_cg: agp_gp_cg_create / _solve / _destroy in agp_capi.hip).  Float64 only.
+// CG on it with its solver handle (agp_gp_cg: agp_gp_cg_create / _solve / _destroy in agp_capi.hip), the derivative bilinear form
+// (agp_kmv_grad.h: kmv_grad_apply, bb_kernel_bilinear_grad) and what the stochastic log marginal likelihood needs of the solver: the CG
+// that reports its Lanczos coefficients (cg_solve_slq), the probes z ~ N(0, P) and log det P.  Float64 only.
 #pragma once
 #include <cmath>
 #include <string>
@@ -10,6 +12,8 @@
 #include "agp_blocks_host.h"
 #include "agp_ctx.h"
 #include "agp_kmv.h"
+#include "agp_kmv_grad.h"
+#include "agp_rand.h"
 #include "agp_select_host.h"
 
 // what agp_greedy_variance refuses in a kernel descriptor, in its words (nullptr: fine)
@@ -136,7 +140,7 @@ static agp_status bb_kernel_matmul(agp_ctx* ctx, const agp_kernel_desc* k, const
 struct agp_gp_cg {
   agp_ctx* ctx = nullptr;
   int64_t n = 0, np = 0, D = 0, nblk = 0, k = 0, kp = 0;
-  double sigma2 = 0.0;
+  double sigma2 = 0.0, logdetM = 0.0;  // logdetM = log det(sigma2 I_k + L'L)
   int groups = 1;
   KmvOp op;
   double *X = nullptr, *ws = nullptr, *L = nullptr, *Lt = nullptr, *Minv = nullptr;
@@ -214,7 +218,7 @@ static agp_status cg_setup(agp_gp_cg* h, const agp_kernel_desc* k, const double*
     LAUNCHCHK(ctx);
     int32_t info = 0;
     int64_t npo = 0;
-    return bb_spd_inverse<double>(ctx, G, kp, nsel, nullptr, 0, nullptr, &info, &h->Minv, &npo);
+    return bb_spd_inverse<double>(ctx, G, kp, nsel, nullptr, 0, &h->logdetM, &info, &h->Minv, &npo);
   };
   s = build();
   drop();
@@ -235,20 +239,33 @@ static agp_status cg_precond(agp_gp_cg* h, double* part_rz) {
   return AGP_OK;
 }
 
+// What cg_solve_slq asks of cg_solve on top of the solve.  coef: the device table [max_iter][2][32] of (alpha_j, beta_j) per column;
+// z0 (n x r, ldz0): the copy of P^-1 b; bpb[c] = b_c' P^-1 b_c (host).  Without a preconditioner P counts as sigma2 I.
+struct CgSlq {
+  double* coef = nullptr;
+  double* z0 = nullptr;
+  int64_t ldz0 = 0;
+  double bpb[CG_LD];
+};
+
 static agp_status cg_solve(agp_gp_cg* h, const double* b, int64_t ldb, int r, double tol, int64_t max_iter, int64_t check_every,
-                           double* a, int64_t lda, int32_t* iters_host, double* relres_host, int32_t* conv_host) {
+                           double* a, int64_t lda, int32_t* iters_host, double* relres_host, int32_t* conv_host,
+                           CgSlq* slq = nullptr) {
   agp_ctx* ctx = h->ctx;
   const int64_t n = h->n, nblk = h->nblk;
   const dim3 g((unsigned)nblk), t(256);
   double *part_pq = h->part, *part_rr = h->part + nblk * CG_LD, *part_rz = part_rr + nblk * CG_LD;
   const bool pre = h->k > 0;
   const double* Z = pre ? h->Zv : nullptr;
+  double* const coef = slq ? slq->coef : nullptr;
   AGPCHK(cg_zero(ctx, h->Pv, h->np * CG_LD));
   hipLaunchKernelGGL(k_cg_update, g, t, 0, ctx->stream, 1, b, ldb, r, n, nblk, (const CgScal*)h->sc, (const double*)part_pq,
-                     (const double*)h->Pv, (const double*)h->Qv, h->Xv, h->Rv, pre ? h->Rt : nullptr, h->np, part_rr);
+                     (const double*)h->Pv, (const double*)h->Qv, h->Xv, h->Rv, pre ? h->Rt : nullptr, h->np, part_rr,
+                     (double*)nullptr);
   if (pre) AGPCHK(cg_precond(h, part_rz));
   hipLaunchKernelGGL(k_cg_direction, g, t, 0, ctx->stream, 1, n, nblk, tol * tol, (const CgScal*)(h->sc + 1), h->sc,
-                     (const double*)part_pq, (const double*)part_rr, (const double*)part_rz, (const double*)h->Rv, Z, h->Pv);
+                     (const double*)part_pq, (const double*)part_rr, (const double*)part_rz, (const double*)h->Rv, Z, h->Pv,
+                     (double*)nullptr);
   LAUNCHCHK(ctx);
   int cur = 0;
   CgScal hs;
@@ -257,6 +274,13 @@ static agp_status cg_solve(agp_gp_cg* h, const double* b, int64_t ldb, int r, do
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return AGP_OK;
   };
+  if (slq) {  // z0 = P^-1 b before the first iteration overwrites it, and b' P^-1 b = the first r . z
+    hipLaunchKernelGGL(k_cg_export_scaled, grid1(n * CG_LD), t, 0, ctx->stream, (const double*)(pre ? h->Zv : h->Rv), n, r,
+                       pre ? 1.0 : 1.0 / h->sigma2, slq->z0, slq->ldz0);
+    LAUNCHCHK(ctx);
+    AGPCHK(read());
+    for (int c = 0; c < r; ++c) slq->bpb[c] = pre ? hs.rz[c] : hs.rz[c] / h->sigma2;
+  }
   for (int64_t it = 0; it < max_iter; ++it) {
     if (it % check_every == 0) {
       AGPCHK(read());
@@ -267,10 +291,12 @@ static agp_status cg_solve(agp_gp_cg* h, const double* b, int64_t ldb, int r, do
     AGPCHK(kmv_apply(ctx, h->op, h->X, h->D, n, 1, h->sigma2, h->Pv, CG_LD, r, h->groups, h->ws, h->Qv, CG_LD));
     hipLaunchKernelGGL(k_cg_dot, g, t, 0, ctx->stream, (const double*)h->Pv, (const double*)h->Qv, n, part_pq);
     hipLaunchKernelGGL(k_cg_update, g, t, 0, ctx->stream, 0, b, ldb, r, n, nblk, (const CgScal*)(h->sc + cur), (const double*)part_pq,
-                       (const double*)h->Pv, (const double*)h->Qv, h->Xv, h->Rv, pre ? h->Rt : nullptr, h->np, part_rr);
+                       (const double*)h->Pv, (const double*)h->Qv, h->Xv, h->Rv, pre ? h->Rt : nullptr, h->np, part_rr,
+                       coef ? coef + it * 2 * CG_LD : nullptr);
     if (pre) AGPCHK(cg_precond(h, part_rz));
     hipLaunchKernelGGL(k_cg_direction, g, t, 0, ctx->stream, 0, n, nblk, tol * tol, (const CgScal*)(h->sc + cur), h->sc + (cur ^ 1),
-                       (const double*)part_pq, (const double*)part_rr, (const double*)part_rz, (const double*)h->Rv, Z, h->Pv);
+                       (const double*)part_pq, (const double*)part_rr, (const double*)part_rz, (const double*)h->Rv, Z, h->Pv,
+                       coef ? coef + it * 2 * CG_LD : nullptr);
     LAUNCHCHK(ctx);
     cur ^= 1;
   }
@@ -283,4 +309,221 @@ static agp_status cg_solve(agp_gp_cg* h, const double* b, int64_t ldb, int r, do
     if (conv_host) conv_host[c] = hs.conv[c];
   }
   return AGP_OK;
+}
+
+// ---- the derivative bilinear form (agp_kmv_grad.h) ---------------------------------------------------------------------------------
+template <int KIND, int DP, int RB>
+static void kmv_grad_launch_one(hipStream_t st, dim3 grid, const double* X, int64_t ldx, int64_t n, const KmvOp& op, const double* U,
+                                int64_t ldu, const double* V, int64_t ldv, int r, const KmvGradW& w, double* part) {
+  constexpr size_t sh = kmv_grad_smem_bytes<DP, RB>();
+  if constexpr (sh > 64 * 1024) {
+    static bool asked = false;
+    if (!asked) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kmv_grad<KIND, DP, RB>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+      asked = true;
+    }
+  }
+  hipLaunchKernelGGL((k_kmv_grad<KIND, DP, RB>), grid, dim3(NTHREADS), sh, st, X, ldx, n, (const double*)op.ysc,
+                     (const double*)op.ysn, op.D, (const double*)op.scales, op.variance, U, ldu, V, ldv, r, w, part);
+}
+template <int KIND>
+static void kmv_grad_launch_kind(hipStream_t st, dim3 grid, const double* X, int64_t ldx, int64_t n, const KmvOp& op, const double* U,
+                                 int64_t ldu, const double* V, int64_t ldv, int r, const KmvGradW& w, double* part) {
+#define AGP_KMVG_CASE(DPV)                                                                          \
+  if (r <= 16) kmv_grad_launch_one<KIND, DPV, 1>(st, grid, X, ldx, n, op, U, ldu, V, ldv, r, w, part); \
+  else kmv_grad_launch_one<KIND, DPV, 2>(st, grid, X, ldx, n, op, U, ldu, V, ldv, r, w, part)
+  if (op.DP == 16) { AGP_KMVG_CASE(16); }
+  else if (op.DP == 32) { AGP_KMVG_CASE(32); }
+  else { AGP_KMVG_CASE(64); }
+#undef AGP_KMVG_CASE
+}
+
+// out[0] = dvar, out[1 + d] = dscale_d (device, 1 + D doubles) for the r weighted pairs (U[:, c], V[:, c]; w[c]); op is the prepared
+// X side (Y = X).  part: groups * row tiles * (1 + D) doubles.  The ExponentialKernel has no derivative at d2 = 0 and is refused by
+// the caller.
+static agp_status kmv_grad_apply(agp_ctx* ctx, const KmvOp& op, const double* X, int64_t ldx, int64_t n, const double* U, int64_t ldu,
+                                 const double* V, int64_t ldv, int r, const KmvGradW& w, int groups, double* part, double* out) {
+  const int64_t nrt = (n + TILE - 1) / TILE;
+  const dim3 grid((unsigned)groups, (unsigned)nrt);
+  switch (op.kind) {
+    case AGP_K_SQEXP: kmv_grad_launch_kind<K_SQEXP>(ctx->stream, grid, X, ldx, n, op, U, ldu, V, ldv, r, w, part); break;
+    case AGP_K_MATERN52: kmv_grad_launch_kind<K_MATERN52>(ctx->stream, grid, X, ldx, n, op, U, ldu, V, ldv, r, w, part); break;
+    default: kmv_grad_launch_kind<K_MATERN32>(ctx->stream, grid, X, ldx, n, op, U, ldu, V, ldv, r, w, part); break;
+  }
+  hipLaunchKernelGGL(k_kmv_grad_sum, dim3((unsigned)(1 + op.D)), dim3(256), 0, ctx->stream, (const double*)part, groups * nrt,
+                     1 + op.D, out);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+
+static agp_status bb_kernel_bilinear_grad(agp_ctx* ctx, const agp_kernel_desc* k, const double* x, int64_t n, int64_t ldx, int64_t D,
+                                          const double* u, int64_t ldu, const double* v, int64_t ldv, int64_t r, const double* w_host,
+                                          int64_t col_groups, double* dvar_host, double* dscales_host) {
+  KmvOp op;
+  double *part = nullptr, *out = nullptr;
+  KmvGradW w;
+  for (int c = 0; c < KMV_MAXR; ++c) w.w[c] = c < r ? (w_host ? w_host[c] : 1.0) : 0.0;
+  std::vector<double> res(1 + D);
+  agp_status s = kmv_prepare(ctx, k, x, n, ldx, D, &op);
+  const int groups = kmv_groups(ctx, n, n, col_groups);
+  if (s == AGP_OK) s = dmalloc(ctx, &part, (int64_t)groups * ((n + TILE - 1) / TILE) * (1 + D));
+  if (s == AGP_OK) s = dmalloc(ctx, &out, 1 + D);
+  if (s == AGP_OK) s = kmv_grad_apply(ctx, op, x, ldx, n, u, ldu, v, ldv, (int)r, w, groups, part, out);
+  hipError_t es = hipSuccess;
+  if (s == AGP_OK) es = hipMemcpyAsync(res.data(), out, sizeof(double) * (1 + D), hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es2 = hipStreamSynchronize(ctx->stream);
+  kmv_release(&op);
+  (void)hipFree(part);
+  (void)hipFree(out);
+  if (s == AGP_OK && (es != hipSuccess || es2 != hipSuccess)) {
+    ctx->err = std::string("agp_kernel_bilinear_grad : ") + hipGetErrorString(es != hipSuccess ? es : es2);
+    return AGP_ERR_HIP;
+  }
+  if (s == AGP_OK) {
+    *dvar_host = res[0];
+    for (int64_t d = 0; d < D; ++d) dscales_host[d] = res[1 + d];
+  }
+  return s;
+}
+
+// ---- stochastic Lanczos quadrature on the CG's own coefficients -------------------------------------------------------------------------
+// e1' log(T) e1 for the symmetric tridiagonal T (diagonal d[0 .. m), off-diagonal e[0 .. m - 1)): implicit-shift QL (EISPACK tql2) that
+// carries only the first row of the eigenvector matrix.  false: no convergence in 60 sweeps of one eigenvalue, or an eigenvalue <= 0.
+static bool slq_e1_log_e1(std::vector<double> d, std::vector<double> e, double* out) {
+  const int m = (int)d.size();
+  std::vector<double> z(m, 0.0);
+  z[0] = 1.0;
+  e.resize(m, 0.0);
+  for (int l = 0; l < m; ++l) {
+    int iter = 0, mm;
+    do {
+      for (mm = l; mm < m - 1; ++mm) {
+        const double dd = std::fabs(d[mm]) + std::fabs(d[mm + 1]);
+        if (std::fabs(e[mm]) <= 0x1p-53 * dd) break;
+      }
+      if (mm != l) {
+        if (iter++ == 60) return false;
+        double g = (d[l + 1] - d[l]) / (2.0 * e[l]), r = std::hypot(g, 1.0);
+        g = d[mm] - d[l] + e[l] / (g + std::copysign(r, g));
+        double s = 1.0, c = 1.0, p = 0.0;
+        int i;
+        for (i = mm - 1; i >= l; --i) {
+          double f = s * e[i];
+          const double b = c * e[i];
+          e[i + 1] = (r = std::hypot(f, g));
+          if (r == 0.0) {
+            d[i + 1] -= p;
+            e[mm] = 0.0;
+            break;
+          }
+          s = f / r, c = g / r;
+          g = d[i + 1] - p;
+          r = (d[i] - g) * s + 2.0 * c * b;
+          d[i + 1] = g + (p = s * r);
+          g = c * r - b;
+          f = z[i + 1];
+          z[i + 1] = s * z[i] + c * f;
+          z[i] = c * z[i] - s * f;
+        }
+        if (r == 0.0 && i >= l) continue;
+        d[l] -= p;
+        e[l] = g;
+        e[mm] = 0.0;
+      }
+    } while (mm != l);
+  }
+  double acc = 0.0;
+  for (int k = 0; k < m; ++k) {
+    if (!(d[k] > 0.0)) return false;
+    acc += z[k] * z[k] * std::log(d[k]);
+  }
+  *out = acc;
+  return true;
+}
+
+// cg_solve, plus: z0 = P^-1 b (n x r, ldz0), bpb_host[c] = b_c' P^-1 b_c and quad_host[c] = e1' log(T_c) e1, T_c the Lanczos tridiagonal
+// of P^-1/2 (K + sigma2 I) P^-1/2 started at P^-1/2 b_c, built from the CG coefficients of column c:
+//   T[0][0] = 1 / alpha_0,  T[j][j] = 1 / alpha_j + beta_{j-1} / alpha_{j-1},  T[j-1][j] = sqrt(beta_{j-1}) / alpha_{j-1}.
+// Then b' P^-1/2 log(P^-1/2 (K + sigma2 I) P^-1/2) P^-1/2 b ~= bpb * quad.  A column with no iteration (b = 0) reports 0.
+static agp_status cg_solve_slq(agp_gp_cg* h, const double* b, int64_t ldb, int r, double tol, int64_t max_iter, int64_t check_every,
+                               double* a, int64_t lda, double* z0, int64_t ldz0, int32_t* iters_host, double* relres_host,
+                               int32_t* conv_host, double* bpb_host, double* quad_host) {
+  agp_ctx* ctx = h->ctx;
+  CgSlq slq;
+  slq.z0 = z0, slq.ldz0 = ldz0;
+  AGPCHK(dmalloc(ctx, &slq.coef, std::max<int64_t>(1, max_iter) * 2 * CG_LD));
+  int32_t its[CG_LD];
+  agp_status s = cg_solve(h, b, ldb, r, tol, max_iter, check_every, a, lda, its, relres_host, conv_host, &slq);
+  int64_t mmax = 0;
+  for (int c = 0; c < r; ++c) mmax = std::max<int64_t>(mmax, its[c]);
+  std::vector<double> co(std::max<int64_t>(1, mmax) * 2 * CG_LD);
+  if (s == AGP_OK && mmax > 0 &&
+      hipMemcpy(co.data(), slq.coef, sizeof(double) * mmax * 2 * CG_LD, hipMemcpyDeviceToHost) != hipSuccess)
+    s = AGP_ERR_HIP;
+  (void)hipFree(slq.coef);
+  if (s != AGP_OK) return s;
+  const bool pre = h->k > 0;
+  for (int c = 0; c < r; ++c) {
+    const int m = its[c];
+    if (iters_host) iters_host[c] = m;
+    bpb_host[c] = slq.bpb[c];
+    quad_host[c] = 0.0;
+    if (m == 0) continue;
+    std::vector<double> d(m), e(m > 1 ? m - 1 : 0);
+    for (int j = 0; j < m; ++j) {
+      const double al = co[(j * 2) * CG_LD + c];
+      d[j] = 1.0 / al;
+      if (j > 0) {
+        const double alp = co[((j - 1) * 2) * CG_LD + c], bep = co[((j - 1) * 2 + 1) * CG_LD + c];
+        d[j] += bep / alp;
+        e[j - 1] = std::sqrt(bep) / alp;
+      }
+    }
+    double q = 0.0;
+    if (!slq_e1_log_e1(d, e, &q)) {
+      ctx->err = "agp_gp_cg_solve_slq: the Lanczos tridiagonal of column " + std::to_string(c) + " is not positive definite";
+      return AGP_ERR_NOT_POSDEF;
+    }
+    quad_host[c] = pre ? q : q - std::log(h->sigma2);  // (plain CG runs on K + sigma2 I itself: T = sigma2 T(P^-1/2 . P^-1/2))
+  }
+  return AGP_OK;
+}
+
+// probes z_c ~ N(0, P), P = L L' + sigma2 I: z = L eps1 + sigma eps2.  base (nullable, device): t x (n + k), row c = (eps2 (n), eps1 (k));
+// nullptr: the Normal of counter (i, t0 + c, RNG_STREAM_PROBE, 0) under `seed` at entry i of row c (k_mc_normals).  out: n x t, ldo.
+enum { RNG_STREAM_PROBE = 0x534C51 };
+static agp_status cg_probes(agp_gp_cg* h, int64_t t, const double* base, int64_t ldbase, uint64_t seed, uint32_t t0, double* out,
+                            int64_t ldo) {
+  agp_ctx* ctx = h->ctx;
+  const int64_t n = h->n, w = n + h->k;
+  double* E = nullptr;
+  auto run = [&]() -> agp_status {
+    if (!base) {
+      AGPCHK(dmalloc(ctx, &E, t * w));
+      for (int64_t c = 0; c < t; ++c)
+        hipLaunchKernelGGL(k_mc_normals, grid1(w), dim3(256), 0, ctx->stream, w, seed, t0 + (uint32_t)c, (uint32_t)RNG_STREAM_PROBE,
+                           E + c * w);
+      LAUNCHCHK(ctx);
+      base = E, ldbase = w;
+    }
+    for (int64_t c0 = 0; c0 < t; c0 += CG_LD) {
+      const int r = (int)std::min<int64_t>(CG_LD, t - c0);
+      const double* Eb = base + c0 * ldbase;
+      if (h->k > 0) {  // Zl = L eps1': eps1 padded into Ct (64 x kp), one GEMM
+        hipLaunchKernelGGL((k_copy2d_zero<double>), grid2(TILE, h->kp), blk2, 0, ctx->stream, Eb + n, ldbase, (int64_t)r, h->k, h->Ct,
+                           h->kp, (int64_t)TILE, h->kp);
+        AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->L, h->kp, h->Ct, h->kp, h->np, TILE, h->kp, 0, h->Zl, TILE, nullptr, 0, nullptr,
+                                           nullptr, nullptr, 0)));
+      }
+      hipLaunchKernelGGL(k_cg_probe, grid1(n * CG_LD), dim3(256), 0, ctx->stream, n, r, (const double*)(h->k > 0 ? h->Zl : nullptr),
+                         (int64_t)TILE, std::sqrt(h->sigma2), Eb, ldbase, out + c0, ldo);
+      LAUNCHCHK(ctx);
+    }
+    return AGP_OK;
+  };
+  agp_status s = run();
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess && s == AGP_OK) s = AGP_ERR_HIP;
+  (void)hipFree(E);
+  return s;
 }

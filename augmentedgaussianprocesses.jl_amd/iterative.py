@@ -1,9 +1,13 @@
-"""IterativeGP -- the exact GP posterior at fixed hyper-parameters without an N x N matrix, and `kernel_matmul`, the operator it runs
-on: (K(X, Y) + c I) V for a block V with K never in memory (agp_kernel_matmul, csrc/agp_kmv.h), under a batched preconditioned CG
-(agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 64, one GPU, Gaussian likelihood.
+"""IterativeGP -- the exact GP without an N x N matrix, and the two operators it runs on: `kernel_matmul`, (K(X, Y) + c I) V for a block
+V with K never in memory (agp_kernel_matmul, csrc/agp_kmv.h), and `kernel_bilinear_grad`, sum_c w_c u_c' (dK / d theta) v_c for the
+kernel's variance and scales with neither K nor the weight matrix in memory (agp_kernel_bilinear_grad, csrc/agp_kmv_grad.h), under a
+batched preconditioned CG (agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 64, one GPU, Gaussian likelihood.
 
-Not here: the log marginal likelihood and hyper-parameter learning (they need a stochastic log-determinant) -- learn the
-hyper-parameters with GP or SVGP and hand them over with IterativeGP.from_model -- and the full predictive covariance.
+The log marginal likelihood is stochastic: log det(K + noise I) = log det P + E_z[z' P^-1/2 log(P^-1/2 (K + noise I) P^-1/2) P^-1/2 z]
+over probes z ~ N(0, P), P the solver's preconditioner, each expectation term by Lanczos quadrature on the coefficients the CG
+computes anyway; the trace in the gradient uses the same probes and solves.  `IterativeGP.optimize` takes ascent steps on it.
+`train_` stays refused (it is the interface of the variational models).  Not here: the full predictive covariance, gradients with
+respect to X or the prior mean.
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ import numpy as np
 
 from . import capi
 from .likelihoods import GaussianLikelihood
-from .svgp import predict_f, predict_y, train_
+from .svgp import ADAM, ELBO, predict_f, predict_y, train_
 
 MAXR = 32  # right-hand sides per launch / per batched solve (KMV_MAXR)
 
@@ -101,6 +105,45 @@ def kernel_matmul(kernel, X, V, Y=None, diag_add: float = 0.0, col_groups: int =
     return out if isinstance(V, torch.Tensor) else out.cpu().numpy()
 
 
+def _bilinear_grad(cx, kernel, Xd, Ud, Vd, w, col_groups=0):
+    """(dvariance, dscales[D]) of sum_c w_c Ud[:, c]' K(Xd, Xd) Vd[:, c]; blocks of 32 columns, added in order"""
+    if kernel._kind == capi.K_EXPONENTIAL:
+        raise NotImplementedError("kernel_bilinear_grad: the ExponentialKernel has no derivative at coincident points; "
+                                  "SqExponentialKernel, Matern32Kernel and Matern52Kernel only")
+    Xd, Ud, Vd = _rows(Xd), _rows(Ud), _rows(Vd)
+    n, D = Xd.shape
+    if Ud.shape != Vd.shape or Ud.shape[0] != n:
+        raise ValueError(f"U {tuple(Ud.shape)} and V {tuple(Vd.shape)} must both be {n} x r")
+    w = np.ones(Ud.shape[1]) if w is None else np.asarray(w, dtype=np.float64).reshape(-1)
+    if len(w) != Ud.shape[1]:
+        raise ValueError(f"{len(w)} weights for {Ud.shape[1]} pairs")
+    kd, keep = kernel.desc(D)
+    dvar, dsc = 0.0, np.zeros(D)
+    for c0 in range(0, Ud.shape[1], MAXR):
+        u, v = Ud[:, c0:c0 + MAXR], Vd[:, c0:c0 + MAXR]
+        r = u.shape[1]
+        o1, oD = C.c_double(), (C.c_double * D)()
+        cx.chk(capi.lib().agp_kernel_bilinear_grad(cx.ctx, capi.F64, C.byref(kd), C.c_void_p(Xd.data_ptr()), n, Xd.stride(0), D,
+                                                   C.c_void_p(u.data_ptr()), Ud.stride(0), C.c_void_p(v.data_ptr()), Vd.stride(0), r,
+                                                   (C.c_double * r)(*w[c0:c0 + r]), int(col_groups), C.byref(o1), oD))
+        dvar += o1.value
+        dsc += np.array(oD)
+    del keep
+    return dvar, dsc
+
+
+def kernel_bilinear_grad(kernel, X, U, V, w=None, col_groups: int = 0, device: Optional[int] = None):
+    """(dvariance, dscales[D]): the derivatives of sum_c w_c U[:, c]' K(X, X) V[:, c] with respect to the kernel's variance and to the
+    scale of each input dimension (an isotropic kernel's is their sum), on the device with neither K nor sum_c w_c u_c v_c' formed.
+    X: n x D, U and V: n x r (vectors count as n x 1), w: r weights (default 1).  More than 32 pairs are taken in blocks of 32 and added
+    in order.  Two calls agree bit for bit.  The ExponentialKernel is refused.  col_groups as in kernel_matmul."""
+    cx = _Ctx(device)
+    try:
+        return _bilinear_grad(cx, kernel, cx.dev_tensor(X), cx.dev_tensor(U), cx.dev_tensor(V), w, col_groups)
+    finally:
+        cx.close()
+
+
 class IterativeGP:
     """IterativeGP(X, y, kernel; noise=1e-5, mean=None, tol=1e-8, max_iter=1000, precond_rank=64): the exact GP posterior at FIXED
     hyper-parameters.  alpha = (K + noise I)^-1 (y - mean) is solved on first use by preconditioned CG on the matrix-free operator;
@@ -109,7 +152,8 @@ class IterativeGP:
 
     predict_f(model, Xt, cov=True) -> (mean, variance): the mean is one operator product; the variance costs ONE BATCHED CG RUN PER 32
     TEST POINTS (k** - k*' (K + noise I)^-1 k*), so ask for it on as many points as are needed and no more.  predict_y adds the
-    noise.  model.solve(B) exposes the solver, model.info what the last solve did.  There is no train_: see GP / SVGP."""
+    noise.  model.solve(B) exposes the solver, model.info what the last solve did.  log_marginal_likelihood (also ELBO(model)) and
+    optimize learn the kernel and the noise; there is no train_."""
 
     def __init__(self, X, y, kernel, *, noise: float = 1e-5, mean=None, tol: float = 1e-8, max_iter: int = 1000,
                  precond_rank: int = 64, check_every: int = 10, device: Optional[int] = None):
@@ -199,6 +243,95 @@ class IterativeGP:
             self.alpha_info = self.info
         return self._alpha
 
+    # ---- log marginal likelihood ----
+    def log_marginal_likelihood(self, num_probes: int = 32, seed: int = 0, base_samples=None, grad: bool = False, _t0: int = 0):
+        """log p(y) = -1/2 (y - mean)' alpha - 1/2 log det(K + noise I) - N/2 log 2 pi with the log-determinant estimated as
+        log det P + (1/t) sum_c (z_c' P^-1 z_c) e1' log(T_c) e1 over t probes z_c ~ N(0, P) (P: the preconditioner, T_c: the Lanczos
+        tridiagonal of probe c from its CG coefficients); one batched CG per 32 columns of [y - mean, probes].  The probes come from
+        `seed` (two calls agree bit for bit) or from base_samples, t x (N + rank_used) standard normals (sqrt(t) I makes the
+        estimators exact traces).  grad=True: (value, dict(variance=, scales=[D], noise=)) -- derivatives with respect to the
+        kernel's variance, the per-dimension scales (for a ScaleTransform also scale= their sum) and the noise, the trace terms by
+        the same probes.  num_probes is an interface default, not tuned; accuracy is set by it, by tol and by max_iter."""
+        torch = _torch()
+        L = capi.lib()
+        h = self._solver()
+        cx, n = self._cx, self.N
+        base = None
+        if base_samples is not None:
+            base = _rows(cx.dev_tensor(np.asarray(base_samples, dtype=np.float64)))
+            if base.shape[1] != n + self.rank_used:
+                raise ValueError(f"base_samples needs {n + self.rank_used} columns (N + rank_used), got {base.shape[1]}")
+        t = int(num_probes) if base is None else base.shape[0]
+        if t < 1:
+            raise ValueError("num_probes must be positive")
+        B = torch.empty(n, 1 + t, dtype=torch.float64, device=cx.dev)
+        B[:, 0] = cx.dev_tensor(self.y - self._mu0(n))[:, 0]
+        Z = B[:, 1:]
+        cx.chk(L.agp_gp_cg_probes(h, t, None if base is None else C.c_void_p(base.data_ptr()), 0 if base is None else base.stride(0),
+                                  int(seed), int(_t0), C.c_void_p(Z.data_ptr()), B.stride(0)))
+        A, Z0 = torch.empty_like(B), torch.empty_like(B)
+        its, res, conv, bpb, quad = [], [], [], [], []
+        for c0 in range(0, 1 + t, MAXR):
+            b, a, z0 = B[:, c0:c0 + MAXR], A[:, c0:c0 + MAXR], Z0[:, c0:c0 + MAXR]
+            r = b.shape[1]
+            it, rr, cv, pb, qd = (C.c_int32 * r)(), (C.c_double * r)(), (C.c_int32 * r)(), (C.c_double * r)(), (C.c_double * r)()
+            cx.chk(L.agp_gp_cg_solve_slq(h, C.c_void_p(b.data_ptr()), B.stride(0), r, self.tol, self.max_iter, self.check_every,
+                                         C.c_void_p(a.data_ptr()), A.stride(0), C.c_void_p(z0.data_ptr()), Z0.stride(0), it, rr, cv,
+                                         pb, qd))
+            its, res, conv, bpb, quad = its + list(it), res + list(rr), conv + [bool(v) for v in cv], bpb + list(pb), quad + list(qd)
+        self.info = dict(iterations=np.array(its), residuals=np.array(res), converged=np.array(conv), rank_used=self.rank_used)
+        if self._alpha is None:
+            self._alpha, self.alpha_info = A[:, :1].clone(), self.info
+        ldp = C.c_double()
+        cx.chk(L.agp_gp_cg_precond_logdet(h, C.byref(ldp)))
+        logdet = ldp.value + float(np.dot(bpb[1:], quad[1:])) / t
+        value = -0.5 * float(B[:, 0] @ A[:, 0]) - 0.5 * logdet - 0.5 * n * np.log(2.0 * np.pi)
+        if not grad:
+            return value
+        V = torch.cat([A[:, :1], Z0[:, 1:]], dim=1)
+        w = np.concatenate([[0.5], np.full(t, -0.5 / t)])
+        dvar, dsc = _bilinear_grad(cx, self.kernel, self._Xd, A, V, w)
+        dnoise = float((torch.as_tensor(w, device=cx.dev) * (A * V).sum(dim=0)).sum())
+        g = dict(variance=dvar, scales=dsc, noise=dnoise)
+        if not hasattr(self.kernel.transform, "v"):
+            g["scale"] = float(dsc.sum())
+        return value, g
+
+    def optimize(self, iterations: int, optimiser=None, opt_noise: bool = True, num_probes: int = 32, seed: int = 0,
+                 base_samples=None):
+        """`iterations` ADAM ascent steps (optimiser=ADAM(0.01)) on the stochastic log marginal likelihood, in the logarithms of the
+        kernel's variance (if it has one: `a * k`), its scale or ARD scales (if it has a transform) and, with opt_noise, the noise --
+        at most D + 2 scalars, stepped on the host.  The solver is rebuilt after every step (its preconditioner depends on the
+        kernel) and every step draws a fresh probe table from (seed, iteration).  num_probes and the step size are interface
+        defaults, not tuned.  Returns the values log p(y) at the parameters BEFORE each step."""
+        from .kernels import ARDTransform, ScaleTransform
+
+        o = ADAM(0.01) if optimiser is None else optimiser
+        if not isinstance(o, ADAM):
+            raise TypeError("IterativeGP.optimize takes an ADAM optimiser")
+        k = self.kernel
+        ard = isinstance(k.transform, ARDTransform)
+        nsc = 0 if k.transform is None else (self.D if ard else 1)
+        m, v, trace = np.zeros(2 + nsc), np.zeros(2 + nsc), []
+        for it in range(int(iterations)):
+            val, g = self.log_marginal_likelihood(num_probes, seed, base_samples, grad=True, _t0=it * int(num_probes))
+            trace.append(val)
+            sc = k.scales(self.D)[:nsc] if nsc else np.zeros(0)
+            theta = np.concatenate([[k.variance], sc, [self.noise]])
+            dth = np.concatenate([[g["variance"] if k.has_variance else 0.0], g["scales"] if ard else [g["scale"]] * nsc,
+                                  [g["noise"] if opt_noise else 0.0]])
+            gl = theta * dth  # d / d log theta
+            m = o.beta[0] * m + (1 - o.beta[0]) * gl
+            v = o.beta[1] * v + (1 - o.beta[1]) * gl * gl
+            step = o.eta * (m / (1 - o.beta[0] ** (it + 1))) / (np.sqrt(v / (1 - o.beta[1] ** (it + 1))) + o.eps)
+            theta = theta * np.exp(step)
+            k.variance, self.noise = float(theta[0]), float(theta[-1])
+            if nsc:
+                k.transform = ARDTransform(theta[1:-1]) if ard else ScaleTransform(float(theta[1]))
+            self.close()  # the handle belongs to the old kernel and noise
+            self._alpha = None
+        return np.array(trace)
+
     def close(self):
         if self._h is not None:
             capi.lib().agp_gp_cg_destroy(self._h)
@@ -263,3 +396,9 @@ def _train_iterative(model: IterativeGP, *args, **kwargs):
     raise NotImplementedError("IterativeGP has no train_: it is the posterior at fixed hyper-parameters (the log marginal likelihood "
                               "needs a log-determinant this path does not form).  Learn them with GP or SVGP, then "
                               "IterativeGP.from_model(m, X, y)")
+
+
+@ELBO.register(IterativeGP)
+def _elbo_iterative(model: IterativeGP, *args, num_probes: int = 32, seed: int = 0, **kwargs) -> float:
+    """ELBO(model) of an IterativeGP: its (stochastic) log marginal likelihood"""
+    return model.log_marginal_likelihood(num_probes=num_probes, seed=seed)

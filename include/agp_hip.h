@@ -407,6 +407,34 @@ agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* 
 agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter, int64_t check_every,
                            void* a, int64_t lda, int32_t* iters_host, double* relres_host, int32_t* converged_host);
 agp_status agp_gp_cg_destroy(agp_gp_cg* h);
+/* ---- matrix-free log marginal likelihood: the derivative bilinear form, CG with Lanczos quadrature, probes ----------------------
+ * agp_kernel_bilinear_grad (csrc/agp_kmv_grad.h): for r <= 32 pairs of vectors (columns of u and v, n x r, device) with host weights
+ * w_host[r] (nullptr: all 1), G_ij = sum_c w_c u_ic v_jc and K = K(x, x):
+ *     *dvar_host = sum_ij G_ij dK_ij / d variance ,   dscales_host[d] = sum_ij G_ij dK_ij / d s_d   (d < D, per dimension; an
+ * isotropic kernel's d / d scale is their sum over d).  Neither K nor G reaches memory: one fused kernel forms d2, G, the kernel
+ * function and its derivative and the third product on v_mfma_f64_16x16x4 per 64 x 64 tile and leaves one partial per workgroup; a
+ * second kernel adds the partials in a fixed order.  No atomics: two calls agree bit for bit.  The scale derivative is evaluated in
+ * the expanded form sx^2 rho + Q - 2 sx O, whose absolute error scales with sum_ij |c_ij| (|sx_id| + |sx_jd|)^2.
+ * AGP_F64, D <= 64, squared-exponential and Matern-3/2, -5/2; the ExponentialKernel is refused by name (AGP_ERR_UNSUPPORTED: no
+ * derivative at d2 = 0).  Other refusals as agp_kernel_matmul, with ldu >= r, ldv >= r.  Synchronises.
+ * agp_gp_cg_solve_slq: agp_gp_cg_solve, and also z0 = P^-1 b (n x r, ldz0 >= r, device), bpb_host[c] = b_c' P^-1 b_c and
+ * quad_host[c] = e1' log(T_c) e1 with T_c the Lanczos tridiagonal of P^-1/2 (K + sigma2 I) P^-1/2 started at P^-1/2 b_c, built on the
+ * host from the alpha_j, beta_j the CG kernels store per column and iteration (symmetric-tridiagonal QL): bpb * quad estimates
+ * b' P^-1/2 log(P^-1/2 (K + sigma2 I) P^-1/2) P^-1/2 b.  P is the handle's preconditioner, sigma2 I if it has none.  a, the
+ * iteration counts and residuals are bit for bit those of agp_gp_cg_solve.  AGP_ERR_NOT_POSDEF if a tridiagonal is not.
+ * agp_gp_cg_probes: out (n x t, ldo >= t, device) = t probes z ~ N(0, P), z = L eps1 + sigma eps2.  base (device, nullable): t rows of
+ * n + rank_used base normals (ldbase), row c = (eps2 (n), eps1 (rank_used)); nullptr: entry i of row c is the Normal of counter
+ * (i, t0 + c, stream 0x534C51, 0) under `seed` (the generator of agp_mc_normals).  Synchronises.
+ * agp_gp_cg_precond_logdet: log det P = (n - k) log sigma2 + log det(sigma2 I_k + L'L), from the factorisation create did. */
+agp_status agp_kernel_bilinear_grad(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                    int64_t D, const void* u, int64_t ldu, const void* v, int64_t ldv, int64_t r,
+                                    const double* w_host, int32_t col_groups, double* dvar_host, double* dscales_host);
+agp_status agp_gp_cg_solve_slq(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter,
+                               int64_t check_every, void* a, int64_t lda, void* z0, int64_t ldz0, int32_t* iters_host,
+                               double* relres_host, int32_t* converged_host, double* bpb_host, double* quad_host);
+agp_status agp_gp_cg_probes(agp_gp_cg* h, int64_t t, const void* base, int64_t ldbase, uint64_t seed, uint32_t t0, void* out,
+                            int64_t ldo);
+agp_status agp_gp_cg_precond_logdet(agp_gp_cg* h, double* logdet_host);
 /* MFMA microbenchmark: TFLOP/s of back-to-back v_mfma_{f64,f32}_16x16x4 (roofline ceiling measurement) */
 agp_status agp_mfma_peak(agp_ctx* ctx, int32_t dtype, double* tflops_host);
 

@@ -5,6 +5,9 @@ prepares the Y side, launches and synchronises), against the only alternative th
     python tools/bench_kmv.py [--n 32768] [--D 32] [--r 1 32] [--reps 5] [--no-dense] [--big 100000]
 
 --big: the same product at a size whose kernel matrix (80 GB at 1e5) is not formed at all; 0 skips it.
+Every row also times the derivative bilinear form on the same shape (agp_kernel_bilinear_grad, csrc/agp_kmv_grad.h: about
+(3 DP + R) / (DP + R) times the MFMA work of the product) and reports the ratio of the two best times; --lml N adds the time of one
+IterativeGP.log_marginal_likelihood(grad=True) at N points with its default 32 probes (0 skips it).
 Prints one JSON line; kernel values per second count n * p evaluations.  A record, not a gate.
 """
 import argparse
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--scale", type=float, default=0.5)
     ap.add_argument("--no-dense", action="store_true")
     ap.add_argument("--big", type=int, default=100000)
+    ap.add_argument("--lml", type=int, default=0)
     a = ap.parse_args()
     g.build()
     import agp_amd as AGP
@@ -69,6 +73,15 @@ def main():
             out = torch.empty(n, r, dtype=torch.float64, device="cuda")
             row = dict(n=n, r=r, fused=timed(lambda: fused(X, V, out), a.reps))
             row["fused_gvalues_per_s"] = round(n * n / row["fused"]["best_ms"] / 1e6, 1)
+            U, dv, ds = torch.randn(n, r, dtype=torch.float64, device="cuda", generator=gen), C.c_double(), (C.c_double * a.D)()
+
+            def grad():
+                st = L.agp_kernel_bilinear_grad(ctx, capi.F64, C.byref(kd), X.data_ptr(), n, a.D, a.D, U.data_ptr(), r, V.data_ptr(),
+                                                r, r, None, 0, C.byref(dv), ds)
+                assert st == 0, L.agp_last_error(ctx)
+
+            row["bilinear_grad"] = timed(grad, a.reps)
+            row["grad_over_fused"] = round(row["bilinear_grad"]["best_ms"] / row["fused"]["best_ms"], 3)
             if dense:
                 def two_step():
                     st = L.agp_kernelmatrix(ctx, capi.F64, C.byref(kd), X.data_ptr(), n, a.D, None, X.data_ptr(), n, a.D, a.D,
@@ -81,6 +94,12 @@ def main():
                 row["max_abs_diff"] = float((ref - out).abs().max())
             res["sizes"].append(row)
         del X, K
+    if a.lml:
+        Xh = torch.rand(a.lml, a.D, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).numpy()
+        m = AGP.IterativeGP(Xh, Xh[:, 0].copy(), AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale), noise=1e-2, tol=1e-6)
+        res["lml_grad"] = dict(n=a.lml, **timed(lambda: m.log_marginal_likelihood(grad=True), min(a.reps, 2)),
+                               iterations=int(m.info["iterations"].max()))
+        m.close()
     L.agp_ctx_destroy(ctx)
     print(json.dumps(res), flush=True)
 
