@@ -5522,8 +5522,8 @@ agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc*
                              const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
                              int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo) {
   if (!ctx) return AGP_ERR_INVALID;
-  bool unsupported = dtype != AGP_F64;
-  const char* bad = unsupported ? "Float64 only (dtype AGP_F64)" : kmv_bad_args(k, x, n, ldx, D, &unsupported);
+  bool unsupported = false;
+  const char* bad = dtype != AGP_F64 && dtype != AGP_F32 ? "dtype is AGP_F64 or AGP_F32" : kmv_bad_args(k, x, n, ldx, D, &unsupported);
   if (!bad) {
     if (!v || !out || (!sym && !y)) bad = "null v, out or y";
     else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
@@ -5538,6 +5538,9 @@ agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc*
     return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
   }
   DevGuard guard(ctx->device);
+  if (dtype == AGP_F32)
+    return bb_kernel_matmul_f32(ctx, k, (const float*)x, n, ldx, (const float*)y, p, ldy, D, sym ? 1 : 0, diag_add, (const float*)v,
+                                ldv, r, col_groups, (float*)out, ldo);
   return bb_kernel_matmul(ctx, k, (const double*)x, n, ldx, (const double*)y, p, ldy, D, sym ? 1 : 0, diag_add, (const double*)v,
                           ldv, r, col_groups, (double*)out, ldo);
 }
@@ -5566,6 +5569,28 @@ agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* 
   if (rank_used_host) *rank_used_host = h->k;
   *out = h;
   return AGP_OK;
+}
+
+agp_status agp_gp_cg_set_operator_dtype(agp_gp_cg* h, int32_t dtype) {
+  if (!h) return AGP_ERR_INVALID;
+  if (dtype != AGP_F64 && dtype != AGP_F32) {
+    h->ctx->err = "agp_gp_cg_set_operator_dtype: dtype is AGP_F64 or AGP_F32";
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(h->ctx->device);
+  return cg_set_operator(h, dtype == AGP_F32 ? 1 : 0);
+}
+
+agp_status agp_gp_cg_apply(agp_gp_cg* h, const void* v, int64_t ldv, int64_t r, void* out, int64_t ldo) {
+  if (!h) return AGP_ERR_INVALID;
+  if (!v || !out || r < 1 || r > KMV_MAXR || ldv < r || ldo < r) {
+    h->ctx->err = "agp_gp_cg_apply: v, out, 1 <= r <= 32, ldv >= r and ldo >= r";
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(h->ctx->device);
+  agp_status s = cg_apply(h, (const double*)v, ldv, (int)r, (double*)out, ldo);
+  if (s == AGP_OK && hipStreamSynchronize(h->ctx->stream) != hipSuccess) s = AGP_ERR_HIP;
+  return s;
 }
 
 agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter, int64_t check_every,

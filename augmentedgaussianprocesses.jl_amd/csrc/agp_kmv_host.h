@@ -2,7 +2,9 @@
 // k_kmv / k_kmv_sum (kmv_apply), the one-shot product behind agp_kernel_matmul (bb_kernel_matmul) and the batched preconditioned
 // CG on it with its solver handle (agp_gp_cg: agp_gp_cg_create / _solve / _destroy in agp_capi.hip), the derivative bilinear form
 // (agp_kmv_grad.h: kmv_grad_apply, bb_kernel_bilinear_grad) and what the stochastic log marginal likelihood needs of the solver: the CG
-// that reports its Lanczos coefficients (cg_solve_slq), the probes z ~ N(0, P) and log det P.  Float64 only.
+// that reports its Lanczos coefficients (cg_solve_slq), the probes z ~ N(0, P) and log det P.  Float64, except the operator itself,
+// which also has a Float32 instance (agp_kmv_f32.h: Kmv32Op, kmv32_prepare, kmv32_apply, bb_kernel_matmul_f32) that the solver handle
+// can be switched to (cg_set_operator); its vectors, preconditioner, probes and Lanczos table stay Float64.
 #pragma once
 #include <cmath>
 #include <string>
@@ -12,6 +14,7 @@
 #include "agp_blocks_host.h"
 #include "agp_ctx.h"
 #include "agp_kmv.h"
+#include "agp_kmv_f32.h"
 #include "agp_kmv_grad.h"
 #include "agp_rand.h"
 #include "agp_select_host.h"
@@ -132,6 +135,125 @@ static agp_status bb_kernel_matmul(agp_ctx* ctx, const agp_kernel_desc* k, const
   return s;
 }
 
+// ---- the Float32 operator (agp_kmv_f32.h) -------------------------------------------------------------------------------------------
+// Both sides prepared once per (kernel, X, Y): centred by the mean of X, scaled, rounded to Float32, with squared norms.  sym: the Y
+// side is the X side (ysc == xsc, not owned twice).
+struct Kmv32Op {
+  int kind = 0, DP = 0;
+  float variance = 0.0f;
+  int64_t D = 0, n = 0, p = 0;
+  double *scales = nullptr, *mean = nullptr;
+  float *xsc = nullptr, *xsn = nullptr, *ysc = nullptr, *ysn = nullptr;
+};
+static void kmv32_release(Kmv32Op* op) {
+  (void)hipFree(op->scales);
+  (void)hipFree(op->mean);
+  if (op->ysc != op->xsc) {
+    (void)hipFree(op->ysc);
+    (void)hipFree(op->ysn);
+  }
+  (void)hipFree(op->xsc);
+  (void)hipFree(op->xsn);
+  op->scales = op->mean = nullptr;
+  op->xsc = op->xsn = op->ysc = op->ysn = nullptr;
+}
+static std::vector<double> kmv_host_scales(const agp_kernel_desc* k, int64_t D) {
+  std::vector<double> hs(D);
+  for (int64_t d = 0; d < D; ++d) hs[d] = k->ard ? k->ard_scales_host[d] : k->scale;
+  return hs;
+}
+// TI: the element type of x and y (float: the C ABI with AGP_F32; double: the solver handle's copy of X).  y == nullptr: symmetric.
+// hs: the D scales, on the host.
+template <typename TI>
+static agp_status kmv32_prepare(agp_ctx* ctx, int kind, double variance, const std::vector<double>& hs, const TI* x, int64_t n,
+                                int64_t ldx, const TI* y, int64_t p, int64_t ldy, int64_t D, Kmv32Op* op) {
+  op->kind = kind, op->variance = (float)variance, op->D = D, op->n = n, op->p = p;
+  op->DP = D <= 16 ? 16 : D <= 32 ? 32 : 64;
+  const int64_t n_pad = rup64(n), p_pad = rup64(p);
+  AGPCHK(dmalloc(ctx, &op->scales, D));
+  AGPCHK(dmalloc(ctx, &op->mean, D));
+  AGPCHK(dmalloc(ctx, &op->xsc, n_pad * op->DP));
+  AGPCHK(dmalloc(ctx, &op->xsn, n_pad));
+  HIPCHK(ctx, hipMemcpy(op->scales, hs.data(), sizeof(double) * D, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL((k_kmv32_mean<TI>), dim3((unsigned)D), dim3(256), 0, ctx->stream, x, ldx, n, op->mean);
+  hipLaunchKernelGGL((k_kmv32_prep<TI>), dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, ctx->stream, x, ldx, n, n_pad, D, op->DP,
+                     (const double*)op->mean, (const double*)op->scales, op->xsc, op->xsn);
+  if (!y) {
+    op->ysc = op->xsc, op->ysn = op->xsn;
+  } else {
+    AGPCHK(dmalloc(ctx, &op->ysc, p_pad * op->DP));
+    AGPCHK(dmalloc(ctx, &op->ysn, p_pad));
+    hipLaunchKernelGGL((k_kmv32_prep<TI>), dim3((unsigned)((p_pad + 3) / 4)), dim3(256), 0, ctx->stream, y, ldy, p, p_pad, D, op->DP,
+                       (const double*)op->mean, (const double*)op->scales, op->ysc, op->ysn);
+  }
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+
+template <int KIND>
+static void kmv32_launch_kind(hipStream_t st, dim3 grid, const Kmv32Op& op, int sym, double diag_add, const void* V, int64_t ldv,
+                              int vf32, int r, void* out, int64_t ldo, int64_t slice, int of32, const double* Vdiag, int64_t ldvd) {
+#define AGP_KMV32_ONE(DPV, RBV)                                                                                                    \
+  hipLaunchKernelGGL((k_kmv32<KIND, DPV, RBV>), grid, dim3(NTHREADS), (kmv32_smem_bytes<DPV, RBV>()), st, (const float*)op.xsc,     \
+                     (const float*)op.xsn, op.n, (const float*)op.ysc, (const float*)op.ysn, op.p, op.variance, sym, diag_add, V, \
+                     ldv, vf32, r, out, ldo, slice, of32, Vdiag, ldvd)
+#define AGP_KMV32_CASE(DPV)            \
+  if (r <= 16) AGP_KMV32_ONE(DPV, 1); \
+  else AGP_KMV32_ONE(DPV, 2)
+  if (op.DP == 16) { AGP_KMV32_CASE(16); }
+  else if (op.DP == 32) { AGP_KMV32_CASE(32); }
+  else { AGP_KMV32_CASE(64); }
+#undef AGP_KMV32_CASE
+#undef AGP_KMV32_ONE
+}
+
+// out (n x r, ldo; float if of32 else double) = (K(X, Y) + diag_add [sym]) V (p x r, ldv; float if vf32 else double), enqueued on the
+// context's stream.  groups > 1: ws holds groups * n * r doubles.  stage (nullable): p * r floats for the rounded copy of a double V.
+static agp_status kmv32_apply(agp_ctx* ctx, const Kmv32Op& op, int sym, double diag_add, const void* V, int64_t ldv, int vf32, int r,
+                              int groups, double* ws, void* out, int64_t ldo, int of32, float* stage = nullptr) {
+  const int64_t n = op.n;
+  const double* Vdiag = nullptr;
+  const int64_t ldvd = ldv;
+  if (!vf32 && stage) {
+    hipLaunchKernelGGL(k_kmv32_stage, grid1(op.p * r), dim3(256), 0, ctx->stream, (const double*)V, ldv, op.p, r, stage);
+    Vdiag = (const double*)V, V = stage, ldv = r, vf32 = 1;
+  }
+  const dim3 grid((unsigned)groups, (unsigned)((n + TILE - 1) / TILE));
+  void* dst = groups > 1 ? (void*)ws : out;
+  const int64_t ldd = groups > 1 ? r : ldo, slice = groups > 1 ? n * r : 0;
+  const int df32 = groups > 1 ? 0 : of32;
+  switch (op.kind) {
+    case AGP_K_SQEXP: kmv32_launch_kind<K_SQEXP>(ctx->stream, grid, op, sym, diag_add, V, ldv, vf32, r, dst, ldd, slice, df32, Vdiag, ldvd); break;
+    case AGP_K_MATERN52: kmv32_launch_kind<K_MATERN52>(ctx->stream, grid, op, sym, diag_add, V, ldv, vf32, r, dst, ldd, slice, df32, Vdiag, ldvd); break;
+    case AGP_K_MATERN32: kmv32_launch_kind<K_MATERN32>(ctx->stream, grid, op, sym, diag_add, V, ldv, vf32, r, dst, ldd, slice, df32, Vdiag, ldvd); break;
+    default: kmv32_launch_kind<K_EXPONENTIAL>(ctx->stream, grid, op, sym, diag_add, V, ldv, vf32, r, dst, ldd, slice, df32, Vdiag, ldvd); break;
+  }
+  if (groups > 1)
+    hipLaunchKernelGGL(k_kmv32_sum, grid1(n * r), dim3(256), 0, ctx->stream, (const double*)ws, groups, n, r, out, ldo, of32);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+
+// agp_kernel_matmul with AGP_F32: x, y, v and out are float arrays
+static agp_status bb_kernel_matmul_f32(agp_ctx* ctx, const agp_kernel_desc* k, const float* x, int64_t n, int64_t ldx, const float* y,
+                                       int64_t p, int64_t ldy, int64_t D, int sym, double diag_add, const float* v, int64_t ldv,
+                                       int64_t r, int64_t col_groups, float* out, int64_t ldo) {
+  Kmv32Op op;
+  double* ws = nullptr;
+  agp_status s = kmv32_prepare<float>(ctx, k->kind, k->variance, kmv_host_scales(k, D), x, n, ldx, sym ? nullptr : y, p, ldy, D, &op);
+  const int groups = kmv_groups(ctx, n, p, col_groups);
+  if (s == AGP_OK && groups > 1) s = dmalloc(ctx, &ws, (int64_t)groups * n * r);
+  if (s == AGP_OK) s = kmv32_apply(ctx, op, sym, sym ? diag_add : 0.0, v, ldv, 1, (int)r, groups, ws, out, ldo, 1);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  kmv32_release(&op);
+  (void)hipFree(ws);
+  if (s == AGP_OK && es != hipSuccess) {
+    ctx->err = std::string("agp_kernel_matmul : ") + hipGetErrorString(es);
+    return AGP_ERR_HIP;
+  }
+  return s;
+}
+
 // ---- batched preconditioned CG on (K(X, X) + sigma2 I) ---------------------------------------------------------------------------
 // The handle keeps what is fixed per (X, kernel, sigma2): a copy of X, the prepared operator, and the preconditioner
 // P = L L' + sigma2 I of rank k (L: agp_greedy_variance's factor), applied by Woodbury,
@@ -143,6 +265,10 @@ struct agp_gp_cg {
   double sigma2 = 0.0, logdetM = 0.0;  // logdetM = log det(sigma2 I_k + L'L)
   int groups = 1;
   KmvOp op;
+  Kmv32Op op32;  // the Float32 operator, prepared by cg_set_operator (f32 != 0)
+  int f32 = 0;
+  float* v32 = nullptr;  // n x 32: the rounded copy of V of a Float32 product
+  std::vector<double> scales_host;
   double *X = nullptr, *ws = nullptr, *L = nullptr, *Lt = nullptr, *Minv = nullptr;
   double *Xv = nullptr, *Rv = nullptr, *Zv = nullptr, *Pv = nullptr, *Qv = nullptr;  // n x 32
   double *Rt = nullptr, *Ct = nullptr, *Wt = nullptr, *Zl = nullptr;                  // 64 x np, 64 x kp, 64 x kp, np x 64
@@ -155,6 +281,8 @@ static constexpr double CG_PRECOND_STOP = 1e-12;
 
 static void cg_release(agp_gp_cg* h) {
   kmv_release(&h->op);
+  kmv32_release(&h->op32);
+  (void)hipFree(h->v32);
   for (double* q : {h->X, h->ws, h->L, h->Lt, h->Minv, h->Xv, h->Rv, h->Zv, h->Pv, h->Qv, h->Rt, h->Ct, h->Wt, h->Zl, h->part})
     (void)hipFree(q);
   (void)hipFree(h->sc);
@@ -174,6 +302,7 @@ static agp_status cg_setup(agp_gp_cg* h, const agp_kernel_desc* k, const double*
   HIPCHK(ctx, hipMemcpy2DAsync(h->X, sizeof(double) * D, x, sizeof(double) * ldx, sizeof(double) * D, n, hipMemcpyDeviceToDevice,
                                ctx->stream));
   AGPCHK(kmv_prepare(ctx, k, h->X, n, D, D, &h->op));
+  h->scales_host = kmv_host_scales(k, D);
   h->groups = kmv_groups(ctx, n, n, 0);
   if (h->groups > 1) AGPCHK(dmalloc(ctx, &h->ws, (int64_t)h->groups * n * KMV_MAXR));
   for (double** q : {&h->Xv, &h->Rv, &h->Zv, &h->Pv, &h->Qv}) AGPCHK(dmalloc(ctx, q, np * CG_LD));
@@ -224,6 +353,29 @@ static agp_status cg_setup(agp_gp_cg* h, const agp_kernel_desc* k, const double*
   drop();
   if (s == AGP_OK) h->k = nsel, h->kp = kp;
   return s;
+}
+
+// Which instance of the operator the solves run on.  Float32: the centred Float32 rows of X are prepared from the handle's Float64
+// copy (once; kept), and the CG calls k_kmv32 with Float64 V and Out.  Everything else of the handle stays Float64.
+static agp_status cg_set_operator(agp_gp_cg* h, int f32) {
+  if (f32 && !h->op32.xsc) {
+    agp_status s = kmv32_prepare<double>(h->ctx, h->op.kind, h->op.variance, h->scales_host, h->X, h->n, h->D, nullptr, h->n, 0,
+                                         h->D, &h->op32);
+    if (s == AGP_OK && hipStreamSynchronize(h->ctx->stream) != hipSuccess) s = AGP_ERR_HIP;
+    if (s == AGP_OK) s = dmalloc(h->ctx, &h->v32, h->n * KMV_MAXR);
+    if (s != AGP_OK) {
+      kmv32_release(&h->op32);
+      return s;
+    }
+  }
+  h->f32 = f32;
+  return AGP_OK;
+}
+
+// out (n x r, ldo) = (K + sigma2 I) v (n x r, ldv) on the instance of the operator the handle's solves run on
+static agp_status cg_apply(agp_gp_cg* h, const double* v, int64_t ldv, int r, double* out, int64_t ldo) {
+  if (h->f32) return kmv32_apply(h->ctx, h->op32, 1, h->sigma2, v, ldv, 0, r, h->groups, h->ws, out, ldo, 0, h->v32);
+  return kmv_apply(h->ctx, h->op, h->X, h->D, h->n, 1, h->sigma2, v, ldv, r, h->groups, h->ws, out, ldo);
 }
 
 // z = P^-1 r and the partials of r . z
@@ -288,7 +440,7 @@ static agp_status cg_solve(agp_gp_cg* h, const double* b, int64_t ldb, int r, do
       for (int c = 0; c < r; ++c) any = any || hs.active[c];
       if (!any) break;
     }
-    AGPCHK(kmv_apply(ctx, h->op, h->X, h->D, n, 1, h->sigma2, h->Pv, CG_LD, r, h->groups, h->ws, h->Qv, CG_LD));
+    AGPCHK(cg_apply(h, h->Pv, CG_LD, r, h->Qv, CG_LD));
     hipLaunchKernelGGL(k_cg_dot, g, t, 0, ctx->stream, (const double*)h->Pv, (const double*)h->Qv, n, part_pq);
     hipLaunchKernelGGL(k_cg_update, g, t, 0, ctx->stream, 0, b, ldb, r, n, nblk, (const CgScal*)(h->sc + cur), (const double*)part_pq,
                        (const double*)h->Pv, (const double*)h->Qv, h->Xv, h->Rv, pre ? h->Rt : nullptr, h->np, part_rr,

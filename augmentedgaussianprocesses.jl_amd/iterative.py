@@ -1,7 +1,9 @@
 """IterativeGP -- the exact GP without an N x N matrix, and the two operators it runs on: `kernel_matmul`, (K(X, Y) + c I) V for a block
 V with K never in memory (agp_kernel_matmul, csrc/agp_kmv.h), and `kernel_bilinear_grad`, sum_c w_c u_c' (dK / d theta) v_c for the
 kernel's variance and scales with neither K nor the weight matrix in memory (agp_kernel_bilinear_grad, csrc/agp_kmv_grad.h), under a
-batched preconditioned CG (agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 64, one GPU, Gaussian likelihood.
+batched preconditioned CG (agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 64, one GPU, Gaussian likelihood;
+the operator product alone also has a Float32 instance (csrc/agp_kmv_f32.h: `kernel_matmul(dtype=np.float32)`,
+`IterativeGP(operator_dtype=np.float32)`).
 
 The log marginal likelihood is stochastic: log det(K + noise I) = log det P + E_z[z' P^-1/2 log(P^-1/2 (K + noise I) P^-1/2) P^-1/2 z]
 over probes z ~ N(0, P), P the solver's preconditioner, each expectation term by Lanczos quadrature on the coefficients the CG
@@ -46,10 +48,10 @@ class _Ctx:
     def chk(self, st):
         capi.check(self.ctx, st)
 
-    def dev_tensor(self, A):
+    def dev_tensor(self, A, dtype=np.float64):
         torch = _torch()
-        t = A.to(device=self.dev, dtype=torch.float64) if isinstance(A, torch.Tensor) else torch.as_tensor(
-            np.array(A, dtype=np.float64), device=self.dev)
+        t = A.to(device=self.dev, dtype=_torch_dtype(dtype)) if isinstance(A, torch.Tensor) else torch.as_tensor(
+            np.array(A, dtype=dtype), device=self.dev)
         return t[:, None] if t.ndim == 1 else t
 
     def close(self):
@@ -58,12 +60,27 @@ class _Ctx:
             self.ctx = C.c_void_p()
 
 
+def _np_dtype(dtype, what):
+    """np.float64 or np.float32 as a NumPy scalar type; anything else is refused by name"""
+    try:
+        dt = np.dtype(dtype).type
+    except TypeError:
+        dt = None
+    if dt not in (np.float64, np.float32):
+        raise ValueError(f"{what} must be np.float64 or np.float32, got {dtype!r}")
+    return dt
+
+
+def _torch_dtype(dtype):
+    return _torch().float32 if dtype is np.float32 else _torch().float64
+
+
 def _rows(t):
     """a 2-D device tensor whose rows are contiguous (any row pitch is fine for the ABI)"""
     return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
 
 
-def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups):
+def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups, dtype=np.float64):
     torch = _torch()
     L = capi.lib()
     sym = Yd is None
@@ -74,10 +91,10 @@ def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups):
     if Vd.shape[0] != p:
         raise ValueError(f"V has {Vd.shape[0]} rows, K(X, Y) has {p} columns")
     kd, keep = kernel.desc(D)
-    out = torch.empty(n, Vd.shape[1], dtype=torch.float64, device=cx.dev)
+    out = torch.empty(n, Vd.shape[1], dtype=_torch_dtype(dtype), device=cx.dev)
     for c0 in range(0, Vd.shape[1], MAXR):
         v, o = Vd[:, c0:c0 + MAXR], out[:, c0:c0 + MAXR]
-        cx.chk(L.agp_kernel_matmul(cx.ctx, capi.F64, C.byref(kd), C.c_void_p(Xd.data_ptr()), n, Xd.stride(0),
+        cx.chk(L.agp_kernel_matmul(cx.ctx, capi.F32 if dtype is np.float32 else capi.F64, C.byref(kd), C.c_void_p(Xd.data_ptr()), n, Xd.stride(0),
                                    None if sym else C.c_void_p(Yd.data_ptr()), p, 0 if sym else Yd.stride(0), D, 1 if sym else 0,
                                    float(diag_add), C.c_void_p(v.data_ptr()), Vd.stride(0), v.shape[1], int(col_groups),
                                    C.c_void_p(o.data_ptr()), out.stride(0)))
@@ -85,19 +102,22 @@ def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups):
     return out
 
 
-def kernel_matmul(kernel, X, V, Y=None, diag_add: float = 0.0, col_groups: int = 0, device: Optional[int] = None):
+def kernel_matmul(kernel, X, V, Y=None, diag_add: float = 0.0, col_groups: int = 0, device: Optional[int] = None, dtype=np.float64):
     """(K(X, Y) + diag_add I) V on the device without forming K.  X: n x D, Y: p x D, V: p x r (a vector counts as p x 1); Y=None is
     the symmetric form K(X, X) + diag_add I, with an exact diagonal.  diag_add needs Y=None.  More than 32 columns are taken in
     blocks of 32.  col_groups: 0 lets the library split the columns of K over workgroups; a positive value forces that many groups.
-    Arrays in, a NumPy array out; device tensors in, a device tensor out."""
+    Arrays in, a NumPy array out; device tensors in, a device tensor out.  dtype: np.float64 (default) or np.float32 -- the inputs
+    are converted to that type and the output has it.  np.float32 runs the Float32 kernel (both products on the Float32 matrix
+    instruction, the sum over the columns of K in Float64 across windows of 128): kernel values to about 1e-6 of the variance."""
     if Y is not None and diag_add != 0.0:
         raise ValueError("diag_add is added to the diagonal of K(X, X): it needs Y=None")
+    dtype = _np_dtype(dtype, "dtype")
     torch = _torch()
     cx = _Ctx(device)
     try:
         vec = np.ndim(V) == 1
-        out = _kernel_matmul(cx, kernel, cx.dev_tensor(X), cx.dev_tensor(V), None if Y is None else cx.dev_tensor(Y), diag_add,
-                             col_groups)
+        out = _kernel_matmul(cx, kernel, cx.dev_tensor(X, dtype), cx.dev_tensor(V, dtype),
+                             None if Y is None else cx.dev_tensor(Y, dtype), diag_add, col_groups, dtype)
     finally:
         cx.close()
     if vec:
@@ -153,10 +173,18 @@ class IterativeGP:
     predict_f(model, Xt, cov=True) -> (mean, variance): the mean is one operator product; the variance costs ONE BATCHED CG RUN PER 32
     TEST POINTS (k** - k*' (K + noise I)^-1 k*), so ask for it on as many points as are needed and no more.  predict_y adds the
     noise.  model.solve(B) exposes the solver, model.info what the last solve did.  log_marginal_likelihood (also ELBO(model)) and
-    optimize learn the kernel and the noise; there is no train_."""
+    optimize learn the kernel and the noise; there is no train_.
+
+    operator_dtype=np.float32 runs every operator product of the CG -- in solve, alpha, predict_f, log_marginal_likelihood and
+    optimize alike -- on the Float32 kernel; the CG's vectors and reductions, the preconditioner, the probes and the gradient kernel
+    stay Float64.  The Float32 operator is a slightly different, FIXED linear map (kernel values to about 1e-6 of the variance): CG
+    solves THAT system, and its recursive residual stops tracking the true one somewhere around the operator's own error.  A `tol`
+    below that level shows up as converged = False in model.info; it is not an exception.  The option is meant for
+    log_marginal_likelihood and optimize, whose Monte-Carlo error is orders of magnitude larger; the default, and any prediction that
+    must be exact, stays np.float64.  No iterative refinement is built."""
 
     def __init__(self, X, y, kernel, *, noise: float = 1e-5, mean=None, tol: float = 1e-8, max_iter: int = 1000,
-                 precond_rank: int = 64, check_every: int = 10, device: Optional[int] = None):
+                 precond_rank: int = 64, check_every: int = 10, device: Optional[int] = None, operator_dtype=np.float64):
         X = np.asarray(X, dtype=np.float64)
         X = np.ascontiguousarray(X[:, None] if X.ndim == 1 else X)
         y = np.asarray(y, dtype=np.float64).reshape(-1)
@@ -169,6 +197,7 @@ class IterativeGP:
         self.X, self.y, self.kernel, self.noise, self.mean = X, y, copy.deepcopy(kernel), float(noise), mean
         self.tol, self.max_iter, self.precond_rank, self.check_every = float(tol), int(max_iter), int(precond_rank), int(check_every)
         self.N, self.D = X.shape
+        self.operator_dtype = _np_dtype(operator_dtype, "operator_dtype")
         self.device = device
         self.info = None
         self.rank_used = None
@@ -198,6 +227,8 @@ class IterativeGP:
                                                      C.byref(used)))
             del keep
             self._h, self.rank_used = h, int(used.value)
+            if self.operator_dtype is np.float32:
+                self._cx.chk(capi.lib().agp_gp_cg_set_operator_dtype(h, capi.F32))
         return self._h
 
     def _solve_dev(self, Bd, tol, max_iter):
@@ -231,6 +262,22 @@ class IterativeGP:
         A = self._solve_dev(Bd, self.tol if tol is None else float(tol), self.max_iter if max_iter is None else int(max_iter))
         A = A[:, 0] if vec else A
         return A if isinstance(B, torch.Tensor) else A.cpu().numpy()
+
+    def operator(self, V):
+        """(K(X, X) + noise I) V on the operator the solves run on (operator_dtype), V of N rows: the system CG solves"""
+        torch = _torch()
+        h = self._solver()
+        vec = np.ndim(V) == 1
+        Vd = _rows(self._cx.dev_tensor(V))
+        if Vd.shape[0] != self.N:
+            raise ValueError(f"V has {Vd.shape[0]} rows, the model {self.N} points")
+        out = torch.empty(Vd.shape, dtype=torch.float64, device=self._cx.dev)
+        for c0 in range(0, Vd.shape[1], MAXR):
+            v, o = Vd[:, c0:c0 + MAXR], out[:, c0:c0 + MAXR]
+            self._cx.chk(capi.lib().agp_gp_cg_apply(h, C.c_void_p(v.data_ptr()), Vd.stride(0), v.shape[1], C.c_void_p(o.data_ptr()),
+                                                    out.stride(0)))
+        out = out[:, 0] if vec else out
+        return out if isinstance(V, torch.Tensor) else out.cpu().numpy()
 
     def _mu0(self, n):
         return 0.0 if self.mean is None else float(self.mean) if np.isscalar(self.mean) else np.asarray(self.mean, dtype=np.float64)

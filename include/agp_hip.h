@@ -375,15 +375,21 @@ agp_status agp_greedy_variance(agp_ctx* ctx, int32_t dtype, const agp_kernel_des
 /* ---- matrix-free exact GP: the kernel operator on a block, and batched preconditioned CG on it -------------------------------
  * agp_kernel_matmul: out = (K(x, y) + diag_add * [sym]) v without K ever reaching memory (csrc/agp_kmv.h: both products on
  * v_mfma_f64_16x16x4, the finished 64 x 64 tile handed from the first to the second in registers).  x is n x D (ldx), y p x D (ldy),
- * v p x r (ldv), out n x r (ldo); AGP_F64 only, 1 <= r <= 32, D <= 64, all four kernels, a scale or ARD scales.  sym != 0: y is x
+ * v p x r (ldv), out n x r (ldo); 1 <= r <= 32, D <= 64, all four kernels, a scale or ARD scales.  AGP_F64: everything below as
+ * stated.  AGP_F32 (csrc/agp_kmv_f32.h): x, y, v and out are float arrays; both sides are centred by the mean of x, scaled and
+ * rounded to Float32 once, both products run on v_mfma_f32_16x16x4f32 and the kernel function on the hardware exp2; the sum over p
+ * is Float32 only inside windows of 128 columns, Float64 across them and across the column groups, and diag_add enters in
+ * Float64 (out += diag_add v).  Kernel values within the "f32" element budget of tests/_kmat_ref.py; the product adds
+ * gamma32_{128 + R} sum_j |K_ij v_jc| + gamma64_{p / 128 + 16} sum_j |K_ij v_jc| and the rounding of out to float
+ * (tests/test_gpu_kernel_matmul_f32.py).  The diagonal value is float(variance), exactly; same determinism.  sym != 0: y is x
  * (y and ldy are not read, p must equal n), diag_add is added on the diagonal, and the diagonal entries are exact: d2 = 0, the
  * entry is variance + diag_add.  sym == 0: diag_add is not read.  Kernel values are agp_kernelmatrix's (GEMM form of d2 with the
  * same repair of close points), within its element-wise budget; the product adds gamma_{p + R} sum_j |K_ij v_jc|, R = r padded to 16.
  * col_groups: how many groups the column tiles of y are split over (each group leaves an n x r slice, a second kernel adds the
  * slices in ascending order); 0 chooses from n, p and the number of CUs, at most 16.  No atomics, fixed summation orders: two calls
  * agree bit for bit, and column c of out is a function of column c of v alone.  The Layout rules above hold.  Synchronises.
- * Refused before anything is launched, outputs untouched: AGP_ERR_UNSUPPORTED for a dtype other than AGP_F64 and for D > 64;
- * AGP_ERR_INVALID for r < 1, r > 32, n <= 0, p <= 0, D <= 0, col_groups < 0, ldx < D, ldy < D, ldv < r, ldo < r, sym with n != p,
+ * Refused before anything is launched, outputs untouched: AGP_ERR_UNSUPPORTED for D > 64; AGP_ERR_INVALID for a dtype that is
+ * neither AGP_F64 nor AGP_F32, r < 1, r > 32, n <= 0, p <= 0, D <= 0, col_groups < 0, ldx < D, ldy < D, ldv < r, ldo < r, sym with n != p,
  * and a kernel descriptor agp_greedy_variance would refuse. */
 agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
                              const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
@@ -400,12 +406,22 @@ agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc*
  * for its x, D and kernel, plus sigma2 not positive and finite, precond_rank < 0.
  * solve: b n x r (ldb >= r), a n x r (lda >= r), device; iters_host / relres_host / converged_host: nullable host arrays of r
  * (iterations taken, final recursive |r| / |b|, 1 if converged).  Refused: r < 1, r > 32, ldb < r, lda < r, tol < 0 or NaN,
- * max_iter < 0.  Synchronises. */
+ * max_iter < 0.  Synchronises.
+ * set_operator_dtype: which instance of the operator every later solve of the handle runs on, AGP_F64 (what create leaves) or
+ * AGP_F32.  AGP_F32 prepares, once, the centred Float32 rows of the handle's copy of x (centred and scaled in Float64, rounded
+ * once) and the solves call the Float32 kernel with the CG's Float64 vectors as V and Out; the CG vector kernels, the
+ * preconditioner, the probes, the Lanczos table and agp_kernel_bilinear_grad stay Float64.  The Float32 operator is a slightly
+ * different, FIXED linear map: CG solves that system, and its recursive residual stops tracking b - (K + sigma2 I) a at about the
+ * operator's own error; a tol below that ends in converged_host[c] = 0, not in an error.  Another dtype: AGP_ERR_INVALID.
+ * apply: out (n x r, ldo >= r) = (K(x, x) + sigma2 I) v (n x r, ldv >= r), Float64 device arrays, 1 <= r <= 32, on the instance of
+ * the operator the solves run on -- what a caller needs to form the residual of the system CG actually solved.  Synchronises. */
 typedef struct agp_gp_cg agp_gp_cg;
 agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D,
                             double sigma2, int64_t precond_rank, agp_gp_cg** out, int64_t* rank_used_host);
 agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter, int64_t check_every,
                            void* a, int64_t lda, int32_t* iters_host, double* relres_host, int32_t* converged_host);
+agp_status agp_gp_cg_set_operator_dtype(agp_gp_cg* h, int32_t dtype);
+agp_status agp_gp_cg_apply(agp_gp_cg* h, const void* v, int64_t ldv, int64_t r, void* out, int64_t ldo);
 agp_status agp_gp_cg_destroy(agp_gp_cg* h);
 /* ---- matrix-free log marginal likelihood: the derivative bilinear form, CG with Lanczos quadrature, probes ----------------------
  * agp_kernel_bilinear_grad (csrc/agp_kmv_grad.h): for r <= 32 pairs of vectors (columns of u and v, n x r, device) with host weights

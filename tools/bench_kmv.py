@@ -2,12 +2,16 @@
 prepares the Y side, launches and synchronises), against the only alternative there was before it: agp_kernelmatrix into memory
 (8 n p bytes) followed by a dense GEMM (torch.mm, i.e. the vendor BLAS: the C ABI has no stand-alone GEMM entry point).
 
-    python tools/bench_kmv.py [--n 32768] [--D 32] [--r 1 32] [--reps 5] [--no-dense] [--big 100000]
+    python tools/bench_kmv.py [--n 32768] [--D 32] [--r 1 32] [--reps 5] [--no-dense] [--big 100000] [--dtype f64 f32]
 
 --big: the same product at a size whose kernel matrix (80 GB at 1e5) is not formed at all; 0 skips it.
 Every row also times the derivative bilinear form on the same shape (agp_kernel_bilinear_grad, csrc/agp_kmv_grad.h: about
 (3 DP + R) / (DP + R) times the MFMA work of the product) and reports the ratio of the two best times; --lml N adds the time of one
 IterativeGP.log_marginal_likelihood(grad=True) at N points with its default 32 probes (0 skips it).
+--dtype: which instances of the operator are timed (default both).  f32 adds, per row, `fused_f32` (agp_kernel_matmul with AGP_F32:
+float arrays, csrc/agp_kmv_f32.h) and, as what one CG iteration pays, `apply_f64` / `apply_f32`: agp_gp_cg_apply of a solver handle
+(no preconditioner; Float64 V and Out, the sides prepared once at create) on the Float64 and on the Float32 operator, with the
+ratios of the best times; --lml then times the log marginal likelihood on each operator (tol 1e-4) and reports the CG iterations.
 Prints one JSON line; kernel values per second count n * p evaluations.  A record, not a gate.
 """
 import argparse
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--no-dense", action="store_true")
     ap.add_argument("--big", type=int, default=100000)
     ap.add_argument("--lml", type=int, default=0)
+    ap.add_argument("--dtype", nargs="+", choices=["f64", "f32"], default=["f64", "f32"])
     a = ap.parse_args()
     g.build()
     import agp_amd as AGP
@@ -73,6 +78,25 @@ def main():
             out = torch.empty(n, r, dtype=torch.float64, device="cuda")
             row = dict(n=n, r=r, fused=timed(lambda: fused(X, V, out), a.reps))
             row["fused_gvalues_per_s"] = round(n * n / row["fused"]["best_ms"] / 1e6, 1)
+            if "f32" in a.dtype:
+                Xf, Vf, outf = X.float(), V.float(), torch.empty(n, r, dtype=torch.float32, device="cuda")
+
+                def fused32():
+                    st = L.agp_kernel_matmul(ctx, capi.F32, C.byref(kd), Xf.data_ptr(), n, a.D, None, n, 0, a.D, 1, 0.0, Vf.data_ptr(), r,
+                                             r, 0, outf.data_ptr(), r)
+                    assert st == 0, L.agp_last_error(ctx)
+
+                row["fused_f32"] = timed(fused32, a.reps)
+                row["max_abs_diff_f32_vs_f64"] = float((outf.double() - out).abs().max())
+                h = C.c_void_p()
+                assert L.agp_gp_cg_create(ctx, C.byref(kd), X.data_ptr(), n, a.D, a.D, 1e-2, 0, C.byref(h), None) == 0
+                for name, dt in (("apply_f64", capi.F64), ("apply_f32", capi.F32)):
+                    assert L.agp_gp_cg_set_operator_dtype(h, dt) == 0
+                    row[name] = timed(lambda: L.agp_gp_cg_apply(h, V.data_ptr(), r, r, out.data_ptr(), r), a.reps)
+                L.agp_gp_cg_destroy(h)
+                row["f64_over_f32"] = dict(abi=round(row["fused"]["best_ms"] / row["fused_f32"]["best_ms"], 3),
+                                           apply=round(row["apply_f64"]["best_ms"] / row["apply_f32"]["best_ms"], 3))
+                fused(X, V, out)  # (out again the Float64 product, for max_abs_diff below)
             U, dv, ds = torch.randn(n, r, dtype=torch.float64, device="cuda", generator=gen), C.c_double(), (C.c_double * a.D)()
 
             def grad():
@@ -96,10 +120,16 @@ def main():
         del X, K
     if a.lml:
         Xh = torch.rand(a.lml, a.D, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).numpy()
-        m = AGP.IterativeGP(Xh, Xh[:, 0].copy(), AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale), noise=1e-2, tol=1e-6)
-        res["lml_grad"] = dict(n=a.lml, **timed(lambda: m.log_marginal_likelihood(grad=True), min(a.reps, 2)),
-                               iterations=int(m.info["iterations"].max()))
-        m.close()
+        import numpy as np
+
+        for dt in a.dtype:
+            m = AGP.IterativeGP(Xh, Xh[:, 0].copy(), AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale), noise=1e-2,
+                                tol=1e-6 if a.dtype == ["f64"] else 1e-4, operator_dtype=np.float32 if dt == "f32" else np.float64)
+            val = []
+            t = timed(lambda: val.append(m.log_marginal_likelihood(grad=True)[0]), min(a.reps, 2))
+            res["lml_grad" if dt == "f64" else "lml_grad_f32"] = dict(n=a.lml, **t, iterations=int(m.info["iterations"].max()),
+                                                                       converged=bool(m.info["converged"].all()), value=val[-1])
+            m.close()
     L.agp_ctx_destroy(ctx)
     print(json.dumps(res), flush=True)
 
