@@ -58,7 +58,7 @@ from .svgp import (  # noqa: F401
 )
 from .vgp import VGP, n_latent  # noqa: F401
 from .gp import GP, Analytic  # noqa: F401
-from .iterative import IterativeGP, kernel_bilinear_grad, kernel_matmul  # noqa: F401
+from .iterative import IterativeGP, kernel_bilinear_grad, kernel_matmul, kernel_matmul_grad  # noqa: F401
 from .movgp import MOVGP  # noqa: F401
 from .mcgp import MCGP, GibbsSampling, sample, sample_local  # noqa: F401
 from .nvi import gauss_hermite_rule, mc_expectations, mc_normals, quad_expectations  # noqa: F401

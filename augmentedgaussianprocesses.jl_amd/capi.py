@@ -210,6 +210,8 @@ SYMBOLS = {
     "agp_gp_cg_solve_slq": (_I32, [_VP, _VP, _I64, _I64, _DBL, _I64, _I64, _VP, _I64, _VP, _I64, _PI32, _PDBL, _PI32, _PDBL, _PDBL]),
     "agp_gp_cg_probes": (_I32, [_VP, _I64, _VP, _I64, C.c_uint64, C.c_uint32, _VP, _I64]),
     "agp_gp_cg_precond_logdet": (_I32, [_VP, _PDBL]),
+    "agp_kernel_matmul_dx": (_I32, [_VP, _I32, _PK, _VP, _I64, _I64, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _I32, _I32, _VP, _I64]),
+    "agp_gp_cg_apply_dx": (_I32, [_VP, _VP, _I64, _I64, _VP, _I64, _I64, _I32, _VP, _I64]),
     "agp_svgp_online_snapshot": (_I32, [_VP, _I32, _VP, _I64, _VP, _PDBL]),
     "agp_svgp_set_online_prior": (_I32, [_VP, _I32, _VP, _I64, _I64, _VP, _I64, _VP, _DBL]),
     "agp_svgp_adopt_local": (_I32, [_VP, _VP]),

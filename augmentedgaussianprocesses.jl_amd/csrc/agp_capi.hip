@@ -5639,6 +5639,66 @@ agp_status agp_kernel_bilinear_grad(agp_ctx* ctx, int32_t dtype, const agp_kerne
                                  col_groups, dvar_host, dscales_host);
 }
 
+// what agp_kernel_matmul_dx and agp_gp_cg_apply_dx refuse about v, r, the mode and out (nullptr: fine)
+static const char* kmv_dx_bad_args(const void* v, int64_t ldv, int64_t r, int32_t paired, int64_t n, int64_t D, const void* out,
+                                   int64_t ldo) {
+  if (!v || !out) return "null v or out";
+  if (r < 1 || r > KMV_MAXR) return "1 <= r <= 32";
+  if (paired && (n > KMV_DX_MAXN || r != n)) return "paired: n <= 32 and r == n (row i takes column i of v)";
+  if (ldv < r) return "ldv >= r";
+  if (ldo < (paired ? D : r * D)) return paired ? "paired: ldo >= D" : "ldo >= r * D";
+  return nullptr;
+}
+
+agp_status agp_kernel_matmul_dx(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                const void* y, int64_t p, int64_t ldy, int64_t D, const void* v, int64_t ldv, int64_t r,
+                                int32_t paired, int32_t col_groups, void* out, int64_t ldo) {
+  if (!ctx) return AGP_ERR_INVALID;
+  bool unsupported = dtype == AGP_F32;
+  const char* bad = dtype == AGP_F32   ? "AGP_F32 is not built: Float64 only (dtype AGP_F64)"
+                    : dtype != AGP_F64 ? "dtype is AGP_F64"
+                                       : kmv_bad_args(k, x, n, ldx, D, &unsupported);
+  if (!bad && k->kind == AGP_K_EXPONENTIAL) {
+    unsupported = true;
+    bad = "the ExponentialKernel has no derivative at coincident points: SqExponential, Matern-3/2 and Matern-5/2 only";
+  }
+  if (!bad) {
+    if (!y) bad = "null y";
+    else if (p <= 0) bad = "p > 0";
+    else if (ldy < D) bad = "ldy >= D";
+    else if (col_groups < 0) bad = "col_groups >= 0";
+    else bad = kmv_dx_bad_args(v, ldv, r, paired, n, D, out, ldo);
+  }
+  if (bad) {
+    ctx->err = std::string("agp_kernel_matmul_dx: ") + bad;
+    return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  return bb_kernel_matmul_dx(ctx, k, (const double*)x, n, ldx, (const double*)y, p, ldy, D, (const double*)v, ldv, r, paired ? 1 : 0,
+                             col_groups, (double*)out, ldo);
+}
+
+agp_status agp_gp_cg_apply_dx(agp_gp_cg* h, const void* xt, int64_t nt, int64_t ldxt, const void* v, int64_t ldv, int64_t r,
+                              int32_t paired, void* out, int64_t ldo) {
+  if (!h) return AGP_ERR_INVALID;
+  const char* bad = nullptr;
+  bool unsupported = false;
+  if (!xt) bad = "null xt";
+  else if (nt <= 0) bad = "nt > 0";
+  else if (ldxt < h->D) bad = "ldxt >= D";
+  else if (h->op.kind == AGP_K_EXPONENTIAL) {
+    unsupported = true;
+    bad = "the ExponentialKernel has no derivative at coincident points: SqExponential, Matern-3/2 and Matern-5/2 only";
+  } else bad = kmv_dx_bad_args(v, ldv, r, paired, nt, h->D, out, ldo);
+  if (bad) {
+    h->ctx->err = std::string("agp_gp_cg_apply_dx: ") + bad;
+    return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
+  }
+  DevGuard guard(h->ctx->device);
+  return kmv_dx_run(h->ctx, h->op, (const double*)xt, nt, ldxt, (const double*)v, ldv, r, paired ? 1 : 0, 0, (double*)out, ldo,
+                    "agp_gp_cg_apply_dx");
+}
+
 agp_status agp_gp_cg_solve_slq(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter,
                                int64_t check_every, void* a, int64_t lda, void* z0, int64_t ldz0, int32_t* iters_host,
                                double* relres_host, int32_t* converged_host, double* bpb_host, double* quad_host) {

@@ -4,7 +4,8 @@
 // (agp_kmv_grad.h: kmv_grad_apply, bb_kernel_bilinear_grad) and what the stochastic log marginal likelihood needs of the solver: the CG
 // that reports its Lanczos coefficients (cg_solve_slq), the probes z ~ N(0, P) and log det P.  Float64, except the operator itself,
 // which also has a Float32 instance (agp_kmv_f32.h: Kmv32Op, kmv32_prepare, kmv32_apply, bb_kernel_matmul_f32) that the solver handle
-// can be switched to (cg_set_operator); its vectors, preconditioner, probes and Lanczos table stay Float64.
+// can be switched to (cg_set_operator); its vectors, preconditioner, probes and Lanczos table stay Float64.  The derivative with
+// respect to the row points (agp_kmv_dx.h: kmv_dx_apply, kmv_dx_run, bb_kernel_matmul_dx) is Float64 only.
 #pragma once
 #include <cmath>
 #include <string>
@@ -14,6 +15,7 @@
 #include "agp_blocks_host.h"
 #include "agp_ctx.h"
 #include "agp_kmv.h"
+#include "agp_kmv_dx.h"
 #include "agp_kmv_f32.h"
 #include "agp_kmv_grad.h"
 #include "agp_rand.h"
@@ -536,6 +538,94 @@ static agp_status bb_kernel_bilinear_grad(agp_ctx* ctx, const agp_kernel_desc* k
     *dvar_host = res[0];
     for (int64_t d = 0; d < D; ++d) dscales_host[d] = res[1 + d];
   }
+  return s;
+}
+
+// ---- the derivative with respect to the row points (agp_kmv_dx.h) ------------------------------------------------------------------
+// right-hand sides per column block: 1 for a single column and for paired mode, else 4 (the instances that are built; not tuned)
+static int kmv_dx_cb(int r, int paired) { return (paired || r == 1) ? 1 : 4; }
+// kmv_groups with the column blocks counted among the workgroups there are
+static int kmv_dx_groups(agp_ctx* ctx, int64_t n, int64_t p, int r, int paired, int64_t col_groups) {
+  const int cb = kmv_dx_cb(r, paired);
+  const int64_t nct = (p + TILE - 1) / TILE, wgs = ((n + TILE - 1) / TILE) * (paired ? 1 : (r + cb - 1) / cb);
+  int64_t g = col_groups > 0 ? col_groups : std::min<int64_t>((2 * (int64_t)ctx_cus(ctx) + wgs - 1) / wgs, 16);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(g, nct));
+}
+
+template <int KIND, int DP, int CB, bool PAIRED>
+static void kmv_dx_launch_one(hipStream_t st, dim3 grid, const double* X, int64_t ldx, int64_t n, const KmvOp& op, const double* V,
+                              int64_t ldv, int r, double* out, int64_t ldo, int64_t slice) {
+  constexpr size_t sh = kmv_dx_smem_bytes<DP, CB, PAIRED>();
+  if constexpr (sh > 64 * 1024) {  // more than 64 KB of dynamic LDS has to be requested once per kernel
+    static bool asked = false;
+    if (!asked) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kmv_dx<KIND, DP, CB, PAIRED>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+      asked = true;
+    }
+  }
+  hipLaunchKernelGGL((k_kmv_dx<KIND, DP, CB, PAIRED>), grid, dim3(NTHREADS), sh, st, X, ldx, n, (const double*)op.ysc,
+                     (const double*)op.ysn, op.p, op.D, (const double*)op.scales, op.variance, V, ldv, r, out, ldo, slice);
+}
+template <int KIND>
+static void kmv_dx_launch_kind(hipStream_t st, dim3 grid, int cb, int paired, const double* X, int64_t ldx, int64_t n, const KmvOp& op,
+                               const double* V, int64_t ldv, int r, double* out, int64_t ldo, int64_t slice) {
+#define AGP_KMVDX_CASE(DPV)                                                                                \
+  if (paired) kmv_dx_launch_one<KIND, DPV, 1, true>(st, grid, X, ldx, n, op, V, ldv, r, out, ldo, slice);  \
+  else if (cb == 1) kmv_dx_launch_one<KIND, DPV, 1, false>(st, grid, X, ldx, n, op, V, ldv, r, out, ldo, slice); \
+  else kmv_dx_launch_one<KIND, DPV, 4, false>(st, grid, X, ldx, n, op, V, ldv, r, out, ldo, slice)
+  if (op.DP == 16) { AGP_KMVDX_CASE(16); }
+  else if (op.DP == 32) { AGP_KMVDX_CASE(32); }
+  else { AGP_KMVDX_CASE(64); }
+#undef AGP_KMVDX_CASE
+}
+
+// shared: out (n x r D, ldo)[i][c D + d] = 2 s_d sum_j c_ij V_jc t_ijd; paired (r == n <= 32): out (n x D, ldo)[i][d] with V_ji.  op is the
+// prepared column side, V is p x r (ldv).  Enqueued on the context's stream.  groups > 1: ws holds groups * n * (paired ? D : r D)
+// doubles.  The ExponentialKernel is refused by the caller.
+static agp_status kmv_dx_apply(agp_ctx* ctx, const KmvOp& op, const double* X, int64_t ldx, int64_t n, const double* V, int64_t ldv,
+                               int r, int paired, int groups, double* ws, double* out, int64_t ldo) {
+  const int cb = kmv_dx_cb(r, paired);
+  const int64_t width = (paired ? 1 : r) * op.D;
+  const dim3 grid((unsigned)groups, (unsigned)((n + TILE - 1) / TILE), (unsigned)(paired ? 1 : (r + cb - 1) / cb));
+  double* dst = groups > 1 ? ws : out;
+  const int64_t ldd = groups > 1 ? width : ldo, slice = groups > 1 ? n * width : 0;
+  switch (op.kind) {
+    case AGP_K_SQEXP: kmv_dx_launch_kind<K_SQEXP>(ctx->stream, grid, cb, paired, X, ldx, n, op, V, ldv, r, dst, ldd, slice); break;
+    case AGP_K_MATERN52: kmv_dx_launch_kind<K_MATERN52>(ctx->stream, grid, cb, paired, X, ldx, n, op, V, ldv, r, dst, ldd, slice); break;
+    default: kmv_dx_launch_kind<K_MATERN32>(ctx->stream, grid, cb, paired, X, ldx, n, op, V, ldv, r, dst, ldd, slice); break;
+  }
+  if (groups > 1)
+    hipLaunchKernelGGL(k_kmv_sum, grid1(n * width), dim3(256), 0, ctx->stream, (const double*)ws, groups, n, (int)width, out, ldo);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+
+// prepared column side `op`, workspace of its own, synchronises; `who` names the entry point in a HIP error
+static agp_status kmv_dx_run(agp_ctx* ctx, const KmvOp& op, const double* x, int64_t n, int64_t ldx, const double* v, int64_t ldv,
+                             int64_t r, int paired, int64_t col_groups, double* out, int64_t ldo, const char* who) {
+  double* ws = nullptr;
+  agp_status s = AGP_OK;
+  const int groups = kmv_dx_groups(ctx, n, op.p, (int)r, paired, col_groups);
+  if (groups > 1) s = dmalloc(ctx, &ws, (int64_t)groups * n * (paired ? 1 : r) * op.D);
+  if (s == AGP_OK) s = kmv_dx_apply(ctx, op, x, ldx, n, v, ldv, (int)r, paired, groups, ws, out, ldo);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(ws);
+  if (s == AGP_OK && es != hipSuccess) {
+    ctx->err = std::string(who) + " : " + hipGetErrorString(es);
+    return AGP_ERR_HIP;
+  }
+  return s;
+}
+
+static agp_status bb_kernel_matmul_dx(agp_ctx* ctx, const agp_kernel_desc* k, const double* x, int64_t n, int64_t ldx, const double* y,
+                                      int64_t p, int64_t ldy, int64_t D, const double* v, int64_t ldv, int64_t r, int paired,
+                                      int64_t col_groups, double* out, int64_t ldo) {
+  KmvOp op;
+  agp_status s = kmv_prepare(ctx, k, y, p, ldy, D, &op);
+  if (s == AGP_OK) s = kmv_dx_run(ctx, op, x, n, ldx, v, ldv, r, paired, col_groups, out, ldo, "agp_kernel_matmul_dx");
+  else (void)hipStreamSynchronize(ctx->stream);
+  kmv_release(&op);
   return s;
 }
 

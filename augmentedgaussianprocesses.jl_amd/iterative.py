@@ -8,8 +8,9 @@ the operator product alone also has a Float32 instance (csrc/agp_kmv_f32.h: `ker
 The log marginal likelihood is stochastic: log det(K + noise I) = log det P + E_z[z' P^-1/2 log(P^-1/2 (K + noise I) P^-1/2) P^-1/2 z]
 over probes z ~ N(0, P), P the solver's preconditioner, each expectation term by Lanczos quadrature on the coefficients the CG
 computes anyway; the trace in the gradient uses the same probes and solves.  `IterativeGP.optimize` takes ascent steps on it.
-`train_` stays refused (it is the interface of the variational models).  Not here: the full predictive covariance, gradients with
-respect to X or the prior mean.
+`train_` stays refused (it is the interface of the variational models).  `kernel_matmul_grad` is the derivative of the operator
+product with respect to its row points (agp_kernel_matmul_dx, csrc/agp_kmv_dx.h); `predict_f_grad(IterativeGP)` runs on it.  Not here:
+the full predictive covariance, gradients with respect to the training inputs or the prior mean.
 """
 from __future__ import annotations
 
@@ -162,6 +163,70 @@ def kernel_bilinear_grad(kernel, X, U, V, w=None, col_groups: int = 0, device: O
         return _bilinear_grad(cx, kernel, cx.dev_tensor(X), cx.dev_tensor(U), cx.dev_tensor(V), w, col_groups)
     finally:
         cx.close()
+
+
+def _refuse_exponential(kernel, who):
+    if kernel._kind == capi.K_EXPONENTIAL:
+        raise NotImplementedError(f"{who}: the ExponentialKernel has no derivative at coincident points; "
+                                  "SqExponentialKernel, Matern32Kernel and Matern52Kernel only")
+
+
+def _matmul_dx_blocks(call, Xd, Vd, D, paired):
+    """the blocks of 32 of agp_kernel_matmul_dx / agp_gp_cg_apply_dx: columns of V in shared mode -> (n, r, D), rows of X with their
+    own columns of V in paired mode -> (n, D).  call(x, v, r, paired, out) launches one block."""
+    torch = _torch()
+    n, r = Xd.shape[0], Vd.shape[1]
+    if paired:
+        if r != n:
+            raise ValueError(f"paired: V needs one column per row of X ({n}), got {r}")
+        out = torch.empty(n, D, dtype=torch.float64, device=Xd.device)
+        for i0 in range(0, n, MAXR):
+            call(Xd[i0:i0 + MAXR], Vd[:, i0:i0 + MAXR], min(MAXR, n - i0), 1, out[i0:i0 + MAXR])
+        return out
+    out = torch.empty(n, r, D, dtype=torch.float64, device=Xd.device)
+    for c0 in range(0, r, MAXR):
+        call(Xd, Vd[:, c0:c0 + MAXR], min(MAXR, r - c0), 0, out[:, c0:c0 + MAXR])
+    return out
+
+
+def _kernel_matmul_grad(cx, kernel, Xd, Vd, Yd, paired, col_groups):
+    _refuse_exponential(kernel, "kernel_matmul_grad")
+    Xd, Vd, Yd = _rows(Xd), _rows(Vd), _rows(Yd)
+    n, D = Xd.shape
+    p = Yd.shape[0]
+    if Vd.shape[0] != p:
+        raise ValueError(f"V has {Vd.shape[0]} rows, K(X, Y) has {p} columns")
+    kd, keep = kernel.desc(D)
+
+    def call(x, v, r, prd, o):
+        cx.chk(capi.lib().agp_kernel_matmul_dx(cx.ctx, capi.F64, C.byref(kd), C.c_void_p(x.data_ptr()), x.shape[0], Xd.stride(0),
+                                               C.c_void_p(Yd.data_ptr()), p, Yd.stride(0), D, C.c_void_p(v.data_ptr()), Vd.stride(0),
+                                               r, prd, int(col_groups), C.c_void_p(o.data_ptr()), o.stride(0)))
+
+    out = _matmul_dx_blocks(call, Xd, Vd, D, paired)
+    del keep
+    return out
+
+
+def kernel_matmul_grad(kernel, X, V, Y, paired: bool = False, col_groups: int = 0, device: Optional[int] = None):
+    """The derivative of K(X, Y) V with respect to the rows of X, on the device with neither K nor its n x p x D derivative formed
+    (agp_kernel_matmul_dx, csrc/agp_kmv_dx.h).  X: n x D, Y: p x D, V: p x r.
+    paired=False: out[i, c, d] = d/dX[i, d] of (K(X, Y) V)[i, c], shape (n, r, D); (n, D) for a vector V.
+    paired=True:  V is p x n and out[i, d] = d/dX[i, d] of K(X[i], Y) V[:, i] with V held fixed, shape (n, D).
+    More than 32 columns -- in paired mode more than 32 rows -- are taken in blocks of 32.  Float64, D <= 64; a row of X that equals a
+    row of Y is an ordinary input.  Two calls agree bit for bit, and without `paired` an output column depends on its own column of V
+    only.  The ExponentialKernel is refused.  col_groups as in kernel_matmul.  Arrays in, a NumPy array out; device tensors in, a device
+    tensor out."""
+    torch = _torch()
+    cx = _Ctx(device)
+    try:
+        vec = np.ndim(V) == 1
+        out = _kernel_matmul_grad(cx, kernel, cx.dev_tensor(X), cx.dev_tensor(V), cx.dev_tensor(Y), bool(paired), col_groups)
+    finally:
+        cx.close()
+    if vec and not paired:
+        out = out[:, 0]
+    return out if isinstance(V, torch.Tensor) else out.cpu().numpy()
 
 
 class IterativeGP:
@@ -404,31 +469,70 @@ def _predict_f_iterative(model: IterativeGP, X_test, state=None, *, cov: bool = 
     if not diag:
         raise NotImplementedError("IterativeGP.predict_f: diag=False (the full predictive covariance) is not built")
     torch = _torch()
-    L = capi.lib()
     alpha = model.alpha()
     cx = model._cx
-    Xt = cx.dev_tensor(np.asarray(X_test, dtype=np.float64))
-    if obsdim == 2:
-        Xt = Xt.t().contiguous()
-    if Xt.shape[1] != model.D:
-        raise ValueError(f"X_test has {Xt.shape[1]} dimensions, the model {model.D}")
+    Xt = _test_points(model, X_test, obsdim)
     mu0 = 0.0 if model.mean is None or not np.isscalar(model.mean) else float(model.mean)  # (a vector mean lives on the training points)
     mean = (_kernel_matmul(cx, model.kernel, Xt, alpha, model._Xd, 0.0, 0)[:, 0] + mu0).cpu().numpy()
     if not cov:
         return mean
-    kd, keep = model.kernel.desc(model.D)
-    nt = Xt.shape[0]
+    nt, variance = Xt.shape[0], model.kernel.desc(model.D)[0].variance
     var = torch.empty(nt, dtype=torch.float64, device=cx.dev)
     for c0 in range(0, nt, MAXR):
-        xt = Xt[c0:c0 + MAXR]
-        ks = torch.empty(model.N, xt.shape[0], dtype=torch.float64, device=cx.dev)  # K(X, Xt_chunk)
-        cx.chk(L.agp_kernelmatrix(cx.ctx, capi.F64, C.byref(kd), C.c_void_p(model._Xd.data_ptr()), model.N, model._Xd.stride(0), None,
-                                  C.c_void_p(xt.data_ptr()), xt.shape[0], Xt.stride(0), model.D, C.c_void_p(ks.data_ptr()),
-                                  ks.stride(0)))
-        sol = model._solve_dev(ks, model.tol, model.max_iter)
-        var[c0:c0 + MAXR] = kd.variance - (ks * sol).sum(dim=0)
-    del keep
+        ks, sol = _kstar_solve(model, Xt[c0:c0 + MAXR])
+        var[c0:c0 + MAXR] = variance - (ks * sol).sum(dim=0)
     return mean, var.cpu().numpy()
+
+
+def _kstar_solve(model, xt):
+    """(K(X, xt), (K + noise I)^-1 K(X, xt)) for a chunk of at most 32 test points (rows of a device tensor): one batched CG"""
+    cx = model._cx
+    kd, keep = model.kernel.desc(model.D)
+    ks = _torch().empty(model.N, xt.shape[0], dtype=_torch().float64, device=cx.dev)
+    cx.chk(capi.lib().agp_kernelmatrix(cx.ctx, capi.F64, C.byref(kd), C.c_void_p(model._Xd.data_ptr()), model.N, model._Xd.stride(0),
+                                       None, C.c_void_p(xt.data_ptr()), xt.shape[0], xt.stride(0), model.D,
+                                       C.c_void_p(ks.data_ptr()), ks.stride(0)))
+    del keep
+    return ks, model._solve_dev(ks, model.tol, model.max_iter)
+
+
+def _test_points(model, X_test, obsdim):
+    Xt = model._cx.dev_tensor(np.asarray(X_test, dtype=np.float64))
+    if obsdim == 2:  # (a fresh tensor: a single point transposed would keep a row pitch of 1)
+        Xt = _torch().empty(Xt.shape[1], Xt.shape[0], dtype=Xt.dtype, device=Xt.device).copy_(Xt.t())
+    if Xt.shape[1] != model.D:
+        raise ValueError(f"X_test has {Xt.shape[1]} dimensions, the model {model.D}")
+    return Xt
+
+
+def predict_f_grad_iterative(model: IterativeGP, X_test, *, cov: bool = True, obsdim: int = 1):
+    """(dmu, dvar), (n_t, D) arrays: the gradients of predict_f(model, X_test) with respect to the test inputs; dmu alone with
+    cov=False, which runs no solve beyond alpha.  dmu = d/dx* K(x*, X) alpha is one launch of the fused derivative operator
+    (agp_gp_cg_apply_dx on the handle's prepared training side); dvar = -2 (d/dx* K(x*, X)) (K + noise I)^-1 K(X, x*) is its paired
+    mode on the solutions predict_f's variance needs anyway: it costs ONE BATCHED CG RUN PER 32 TEST POINTS.  A prior mean (a
+    constant, or one value per training point) contributes nothing.  With operator_dtype=np.float32 the solves run on the Float32
+    operator; the gradient kernel is Float64."""
+    if not isinstance(cov, bool):
+        raise TypeError("predict_f_grad: cov is a bool")
+    if obsdim not in (1, 2):
+        raise ValueError("predict_f_grad: obsdim is 1 (points are rows) or 2 (points are columns)")
+    _refuse_exponential(model.kernel, "predict_f_grad")
+    alpha = model.alpha()
+    cx, h, D = model._cx, model._solver(), model.D
+    Xt = _rows(_test_points(model, X_test, obsdim))
+
+    def call(x, v, r, prd, o):
+        cx.chk(capi.lib().agp_gp_cg_apply_dx(h, C.c_void_p(x.data_ptr()), x.shape[0], x.stride(0), C.c_void_p(v.data_ptr()),
+                                             v.stride(0), r, prd, C.c_void_p(o.data_ptr()), o.stride(0)))
+
+    dmu = _matmul_dx_blocks(call, Xt, _rows(alpha), D, False)[:, 0].cpu().numpy()
+    if not cov:
+        return dmu
+    dvar = _torch().empty(Xt.shape[0], D, dtype=_torch().float64, device=cx.dev)
+    for c0 in range(0, Xt.shape[0], MAXR):
+        xt = Xt[c0:c0 + MAXR]
+        dvar[c0:c0 + MAXR] = -2.0 * _matmul_dx_blocks(call, xt, _kstar_solve(model, xt)[1], D, True)
+    return dmu, dvar.cpu().numpy()
 
 
 @predict_y.register(IterativeGP)

@@ -10,6 +10,7 @@ import functools
 from typing import Optional
 
 from . import capi
+from .iterative import IterativeGP, predict_f_grad_iterative
 from .mcgp import MCGP
 from .online import OnlineSVGP
 from .svgp import MOSVGP, SVGP
@@ -75,13 +76,19 @@ def predict_f_grad(model, X_test, *, cov: bool = True, obsdim: int = 1):
     SqExponential, Matern32 and Matern52 kernels with ScaleTransform / ARDTransform, D <= 64; a test point that coincides with an
     inducing point is an ordinary input.  Streamed in chunks of 4096 points, deterministic, and the model's state is left as it was.
     SVGP (AnalyticVI / SVI, QuadratureVI, MCIntegrationVI), MOSVGP, VGP, GP, MOVGP, OnlineSVGP; an MCGP, the ExponentialKernel and
-    D > 64 raise NotImplementedError before the device is touched."""
+    D > 64 raise NotImplementedError before the device is touched.  IterativeGP: matrix-free, see predict_f_grad_iterative -- its
+    dvar costs one batched CG run per 32 test points."""
     raise NotImplementedError(f"predict_f_grad: {predgrad_refusal(model)}")
 
 
 @predict_f_grad.register(SVGP)  # MOSVGP, VGP, GP and MOVGP are SVGPs
 def _(model, X_test, *, cov: bool = True, obsdim: int = 1):
     return _grad_svgp(model, X_test, cov, obsdim)
+
+
+@predict_f_grad.register(IterativeGP)  # no factored handle: the matrix-free derivative operator (csrc/agp_kmv_dx.h, DESIGN.md 9s)
+def _(model, X_test, *, cov: bool = True, obsdim: int = 1):
+    return predict_f_grad_iterative(model, X_test, cov=cov, obsdim=obsdim)
 
 
 @predict_f_grad.register(MCGP)

@@ -451,6 +451,28 @@ agp_status agp_gp_cg_solve_slq(agp_gp_cg* h, const void* b, int64_t ldb, int64_t
 agp_status agp_gp_cg_probes(agp_gp_cg* h, int64_t t, const void* base, int64_t ldbase, uint64_t seed, uint32_t t0, void* out,
                             int64_t ldo);
 agp_status agp_gp_cg_precond_logdet(agp_gp_cg* h, double* logdet_host);
+/* ---- matrix-free input gradients: the derivative of the fused kernel product with respect to its row points -------------------
+ * agp_kernel_matmul_dx (csrc/agp_kmv_dx.h): with t_ijd = s_d (x_id - y_jd), c_ij = variance phi'(d2_ij), so that
+ * d k(x_i, y_j) / d x_id = 2 s_d c_ij t_ijd, and x n x D (ldx), y p x D (ldy), v p x r (ldv), 1 <= r <= 32, all device, Float64:
+ *     paired == 0 (shared):  out[i][c D + d] = 2 s_d sum_j c_ij v_jc t_ijd     out n x (r D), ldo >= r D
+ *     paired != 0:           out[i][d]       = 2 s_d sum_j c_ij v_ji t_ijd     out n x D, ldo >= D; n <= 32 and r == n
+ * Neither K nor its n x p x D derivative reaches memory: one fused kernel forms d2 and phi' per 64 x 64 tile on v_mfma_f64_16x16x4,
+ * scales the tile by a column of v in registers and multiplies it with the tile of y; right-hand sides are taken in blocks of 4 (1 for
+ * r == 1 and for paired mode) over a third grid dimension.  Evaluated as 2 s_d ((sx_id - m_d) rho_ic - O_icd) with m the scaled first
+ * row of each 64-row tile of x: the absolute error scales with sum_j |c_ij v_jc| (|sx_id - m_d| + |sy_jd - m_d|).
+ * Cross form only; a row of x that coincides with a row of y is an ordinary input and contributes 0.  No atomics, fixed summation
+ * orders: two calls agree bit for bit, and in shared mode column c of out is a function of column c of v alone.  col_groups as in
+ * agp_kernel_matmul (0: chosen from n, r, p and the number of CUs).  Synchronises.
+ * Refused before anything is launched, outputs untouched: AGP_ERR_UNSUPPORTED for AGP_F32 (not built), D > 64 and the ExponentialKernel
+ * (no derivative at d2 = 0); AGP_ERR_INVALID for any other dtype, paired with n > 32 or r != n, r < 1, r > 32, n <= 0, p <= 0, D <= 0,
+ * col_groups < 0, ldx < D, ldy < D, ldv < r, ldo too small, and a kernel descriptor agp_greedy_variance would refuse.
+ * agp_gp_cg_apply_dx: the same with y = the handle's x and kernel, on the column side agp_gp_cg_create prepared (xt nt x D, ldxt; v n x r):
+ * what the input gradients of the posterior mean (v = alpha, r = 1) and variance (paired, v = (K + sigma2 I)^-1 K(x, xt)) need. */
+agp_status agp_kernel_matmul_dx(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                const void* y, int64_t p, int64_t ldy, int64_t D, const void* v, int64_t ldv, int64_t r,
+                                int32_t paired, int32_t col_groups, void* out, int64_t ldo);
+agp_status agp_gp_cg_apply_dx(agp_gp_cg* h, const void* xt, int64_t nt, int64_t ldxt, const void* v, int64_t ldv, int64_t r,
+                              int32_t paired, void* out, int64_t ldo);
 /* MFMA microbenchmark: TFLOP/s of back-to-back v_mfma_{f64,f32}_16x16x4 (roofline ceiling measurement) */
 agp_status agp_mfma_peak(agp_ctx* ctx, int32_t dtype, double* tflops_host);
 

@@ -12,6 +12,10 @@ IterativeGP.log_marginal_likelihood(grad=True) at N points with its default 32 p
 float arrays, csrc/agp_kmv_f32.h) and, as what one CG iteration pays, `apply_f64` / `apply_f32`: agp_gp_cg_apply of a solver handle
 (no preconditioner; Float64 V and Out, the sides prepared once at create) on the Float64 and on the Float32 operator, with the
 ratios of the best times; --lml then times the log marginal likelihood on each operator (tol 1e-4) and reports the CG iterations.
+--dx NT: the derivative with respect to the row points (agp_kernel_matmul_dx, csrc/agp_kmv_dx.h) for NT row points against p = --n
+and p = --big column points, per r, beside agp_kernel_matmul's cross product on the same shapes, with the ratio of the best times and
+the ratio of the MFMA counts (1 + CB) DP ceil(r / CB) / (DP + R); --predgrad N: one predict_f_grad(cov=True) of an IterativeGP on 32
+test points at N training points, split into the batched solve and the gradient kernel's two launches (0 skips either).
 Prints one JSON line; kernel values per second count n * p evaluations.  A record, not a gate.
 """
 import argparse
@@ -50,6 +54,8 @@ def main():
     ap.add_argument("--no-dense", action="store_true")
     ap.add_argument("--big", type=int, default=100000)
     ap.add_argument("--lml", type=int, default=0)
+    ap.add_argument("--dx", type=int, default=0)
+    ap.add_argument("--predgrad", type=int, default=0)
     ap.add_argument("--dtype", nargs="+", choices=["f64", "f32"], default=["f64", "f32"])
     a = ap.parse_args()
     g.build()
@@ -118,6 +124,50 @@ def main():
                 row["max_abs_diff"] = float((ref - out).abs().max())
             res["sizes"].append(row)
         del X, K
+    if a.dx:
+        res["matmul_dx"] = []
+        DP = 16 if a.D <= 16 else 32 if a.D <= 32 else 64
+        Xr = torch.rand(a.dx, a.D, dtype=torch.float64, device="cuda", generator=gen)
+        for p in [a.n] + ([a.big] if a.big else []):
+            Y = torch.rand(p, a.D, dtype=torch.float64, device="cuda", generator=gen)
+            for r in a.r:
+                V = torch.randn(p, r, dtype=torch.float64, device="cuda", generator=gen)
+                o1, oD = torch.empty(a.dx, r, dtype=torch.float64, device="cuda"), torch.empty(a.dx, r * a.D, dtype=torch.float64, device="cuda")
+
+                def cross():
+                    st = L.agp_kernel_matmul(ctx, capi.F64, C.byref(kd), Xr.data_ptr(), a.dx, a.D, Y.data_ptr(), p, a.D, a.D, 0, 0.0,
+                                             V.data_ptr(), r, r, 0, o1.data_ptr(), r)
+                    assert st == 0, L.agp_last_error(ctx)
+
+                def dx():
+                    st = L.agp_kernel_matmul_dx(ctx, capi.F64, C.byref(kd), Xr.data_ptr(), a.dx, a.D, Y.data_ptr(), p, a.D, a.D,
+                                                V.data_ptr(), r, r, 0, 0, oD.data_ptr(), r * a.D)
+                    assert st == 0, L.agp_last_error(ctx)
+
+                cb = 1 if r == 1 else 4
+                row = dict(n=a.dx, p=p, r=r, CB=cb, matmul_dx=timed(dx, a.reps), matmul=timed(cross, a.reps))
+                row["dx_over_matmul"] = round(row["matmul_dx"]["best_ms"] / row["matmul"]["best_ms"], 3)
+                row["mfma_ratio"] = round((1 + cb) * DP * -(-r // cb) / (DP + 16 * -(-r // 16)), 3)
+                res["matmul_dx"].append(row)
+    if a.predgrad:
+        from agp_amd import iterative
+
+        Xh = torch.rand(a.predgrad, a.D, dtype=torch.float64, generator=torch.Generator().manual_seed(2)).numpy()
+        m = AGP.IterativeGP(Xh, Xh[:, 0].copy(), AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale), noise=1e-2, tol=1e-6)
+        m.alpha()
+        Xt = m._cx.dev_tensor(Xh[:32] + 0.01)
+        sol, od = iterative._kstar_solve(m, Xt)[1], torch.empty(32, a.D, dtype=torch.float64, device="cuda")
+
+        def kernels():
+            for v, prd in ((m._alpha, 0), (sol, 1)):
+                assert L.agp_gp_cg_apply_dx(m._h, Xt.data_ptr(), 32, a.D, v.data_ptr(), v.stride(0), v.shape[1], prd, od.data_ptr(),
+                                            a.D) == 0
+
+        res["predict_f_grad"] = dict(N=a.predgrad, nt=32, total=timed(lambda: AGP.predict_f_grad(m, Xh[:32] + 0.01), 1),
+                                     solve=timed(lambda: iterative._kstar_solve(m, Xt), 1),
+                                     gradient_kernels=timed(kernels, a.reps), iterations=int(m.info["iterations"].max()),
+                                     converged=bool(m.info["converged"].all()))
+        m.close()
     if a.lml:
         Xh = torch.rand(a.lml, a.D, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).numpy()
         import numpy as np
