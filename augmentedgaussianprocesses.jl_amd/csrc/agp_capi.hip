@@ -5403,6 +5403,7 @@ const char* agp_last_error(agp_ctx* ctx) { return ctx ? ctx->err.c_str() : "null
 #include "agp_blocks_host.h"
 #include "agp_select_host.h"
 #include "agp_kmv_host.h"
+#include "agp_path_host.h"
 
 #define DISPATCH(dtype, call_f64, call_f32)        \
   do {                                             \
@@ -6498,6 +6499,80 @@ agp_status agp_pathwise_features(agp_ctx* ctx, const agp_kernel_desc* k, int64_t
   DevGuard guard(ctx->device);
   AGPCHK(pw_spectral(ctx, k->kind, D, n_features, seed, t, latent, (double*)omega_out, (double*)phase_out));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return AGP_OK;
+}
+
+// ---- the matrix-free pathwise draw of the exact GP (include/agp_hip.h, "MATRIX-FREE PATHWISE SAMPLING") ---------------------------------
+agp_status agp_gp_cg_pathwise_draw(agp_gp_cg* h, const void* b, int64_t n_features, int64_t n_samples, uint64_t seed, int64_t t,
+                                   double tol, int64_t max_iter, int64_t check_every, int32_t* iters_host, double* relres_host,
+                                   int32_t* converged_host, agp_gp_cg_paths** out) {
+  if (!h) return AGP_ERR_INVALID;
+  agp_ctx* ctx = h->ctx;
+  const char* bad = nullptr;
+  if (!out) bad = "out must be given";
+  else if (!b) bad = "b must be given";
+  else if (!(tol >= 0.0)) bad = "tol >= 0";
+  else if (max_iter < 0) bad = "max_iter >= 0";
+  if (bad) {
+    ctx->err = std::string("agp_gp_cg_pathwise_draw: ") + bad;
+    return AGP_ERR_INVALID;
+  }
+  *out = nullptr;
+  AGPCHK(path_check_draw(ctx, h->n, h->D, n_features, n_samples, t));
+  DevGuard guard(ctx->device);
+  std::unique_ptr<agp_gp_cg_paths> p(new agp_gp_cg_paths());
+  AGPCHK(path_draw(h, (const double*)b, n_features, n_samples, seed, t, tol, max_iter, check_every > 0 ? check_every : 10, iters_host,
+                   relres_host, converged_host, p.get()));
+  *out = p.release();
+  return AGP_OK;
+}
+agp_status agp_gp_cg_pathwise_eval(agp_gp_cg_paths* p, const void* xt, int64_t ldx, int64_t n_t, int32_t col_groups, void* out,
+                                   int64_t ldo) {
+  if (!p) return AGP_ERR_INVALID;
+  if (n_t == 0) return AGP_OK;
+  const char* bad = nullptr;
+  if (!xt || !out) bad = "xt and out must be given";
+  else if (n_t < 0) bad = "n_t >= 0";
+  else if (ldx < p->D) bad = "ldx >= D";
+  else if (ldo < p->S) bad = "ldo >= n_samples";
+  else if (col_groups < 0) bad = "col_groups >= 0";
+  if (bad) {
+    p->ctx->err = std::string("agp_gp_cg_pathwise_eval: ") + bad;
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(p->ctx->device);
+  return path_eval(*p, (const double*)xt, ldx, n_t, col_groups, (double*)out, ldo);
+}
+agp_status agp_gp_cg_pathwise_get(agp_gp_cg_paths* p, int32_t which, void* out, int64_t ld) {
+  if (!p) return AGP_ERR_INVALID;
+  agp_ctx* ctx = p->ctx;
+  if (!out || which < AGP_PW_OMEGA || which > AGP_PW_E) {
+    ctx->err = "agp_gp_cg_pathwise_get: out given, which one of AGP_PW_OMEGA .. AGP_PW_E";
+    return AGP_ERR_INVALID;
+  }
+  const double* src = p->omega;
+  int64_t rows = p->L, cols = p->D;
+  switch (which) {
+    case AGP_PW_PHASE: src = p->php, cols = 1, ld = 1; break;  // a dense vector: ld is not read
+    case AGP_PW_W: src = p->W, cols = p->S; break;
+    case AGP_PW_V: src = p->V, rows = p->n, cols = p->S; break;
+    case AGP_PW_E: src = p->E, rows = p->n, cols = p->S; break;
+    default: break;
+  }
+  if (ld < cols) {
+    ctx->err = "agp_gp_cg_pathwise_get: the leading dimension is smaller than the table's width (" + std::to_string(cols) + ")";
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  hipLaunchKernelGGL(k_pw_gather, grid2(rows, cols), blk2, 0, ctx->stream, src, cols, (int64_t)1, rows, cols, (double*)out, ld);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+agp_status agp_gp_cg_pathwise_destroy(agp_gp_cg_paths* p) {
+  if (!p) return AGP_OK;
+  DevGuard guard(p->ctx->device);
+  (void)hipStreamSynchronize(p->ctx->stream);
+  delete p;
   return AGP_OK;
 }
 

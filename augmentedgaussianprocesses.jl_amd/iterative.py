@@ -9,8 +9,10 @@ The log marginal likelihood is stochastic: log det(K + noise I) = log det P + E_
 over probes z ~ N(0, P), P the solver's preconditioner, each expectation term by Lanczos quadrature on the coefficients the CG
 computes anyway; the trace in the gradient uses the same probes and solves.  `IterativeGP.optimize` takes ascent steps on it.
 `train_` stays refused (it is the interface of the variational models).  `kernel_matmul_grad` is the derivative of the operator
-product with respect to its row points (agp_kernel_matmul_dx, csrc/agp_kmv_dx.h); `predict_f_grad(IterativeGP)` runs on it.  Not here:
-the full predictive covariance, gradients with respect to the training inputs or the prior mean.
+product with respect to its row points (agp_kernel_matmul_dx, csrc/agp_kmv_dx.h); `predict_f_grad(IterativeGP)` runs on it.
+`sample_paths(IterativeGP, S)` draws posterior functions without an N x N matrix (pathwise.py: IterativePaths; the fused
+path-evaluation kernel of csrc/agp_path.h under the draw's batched CG and under every evaluation).  Not here: the full predictive
+covariance, gradients with respect to the training inputs or the prior mean, gradients of the drawn paths.
 """
 from __future__ import annotations
 
@@ -42,6 +44,7 @@ class _Ctx:
             raise RuntimeError("no HIP device visible: augmentedgaussianprocesses.jl_amd has no CPU fallback")
         self.dev = torch.device("cuda", device if device is not None else torch.cuda.current_device())
         self.ctx = C.c_void_p()
+        self.refs = 1  # the owner; a paths object drawn on this context holds another (retain) and outlives the model's close()
         st = capi.lib().agp_ctx_create(self.dev.index, C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream), C.byref(self.ctx))
         if st != capi.AGP_OK:
             raise capi.AGPError(st, "agp_ctx_create failed")
@@ -55,8 +58,13 @@ class _Ctx:
             np.array(A, dtype=dtype), device=self.dev)
         return t[:, None] if t.ndim == 1 else t
 
+    def retain(self):
+        self.refs += 1
+        return self
+
     def close(self):
-        if self.ctx:
+        self.refs -= 1
+        if self.ctx and self.refs <= 0:
             capi.lib().agp_ctx_destroy(self.ctx)
             self.ctx = C.c_void_p()
 
@@ -266,6 +274,7 @@ class IterativeGP:
         self.device = device
         self.info = None
         self.rank_used = None
+        self.seed = None  # of sample_paths(model, ...; seed=None): drawn once, kept
         self._cx = self._h = self._Xd = self._alpha = None
 
     @classmethod

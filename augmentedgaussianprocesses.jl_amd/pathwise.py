@@ -1,4 +1,5 @@
-"""Pathwise posterior sampling: function draws from a trained SVGP, VGP or GP (include/agp_hip.h, "PATHWISE SAMPLING").
+"""Pathwise posterior sampling: function draws from a trained SVGP, VGP or GP (include/agp_hip.h, "PATHWISE SAMPLING"), and from an
+IterativeGP without any N x N matrix ("MATRIX-FREE PATHWISE SAMPLING": IterativePaths, on the fused kernel of csrc/agp_path.h).
 
     paths = AGP.sample_paths(model, n_samples, n_features=1024, seed=None, t=0)
     F = paths(X_test)          # (n_samples, n_t), or (n_latent, n_samples, n_t) for several latents
@@ -251,12 +252,117 @@ class PathwiseSamples:
                 f"seed={self.seed}, t={self.t})")
 
 
-def sample_paths(model, n_samples: int, *, n_features: int = 1024, seed: Optional[int] = None, t: int = 0) -> PathwiseSamples:
+class IterativePaths:
+    """n_samples function draws from the posterior of an IterativeGP (agp_gp_cg_pathwise_*): f_s(x) = mean + Phi(x) w_s + K(x, X) v_s
+    with v_s = (K + noise I)^-1 (y - mean - Phi(X) w_s - sqrt(noise) e_s) solved by the model's batched CG, 32 samples at a time.  The
+    draw and every evaluation run on one fused kernel that forms neither Phi nor K in memory.  A snapshot: the paths evaluate, with
+    the same bits, after the model is closed.  `info` is the CG report of the draw (iterations, residuals, converged per sample)."""
+
+    def __init__(self, model, n_samples: int, n_features: int, seed: int, t: int):
+        self.n_samples, self.n_features, self.seed, self.t = int(n_samples), int(n_features), int(seed), int(t)
+        self.N, self.D = model.N, model.D
+        mu0 = model._mu0(model.N)
+        self._mean = float(mu0) if np.isscalar(mu0) else 0.0  # (a vector mean lives on the training points: it enters through b)
+        self._p = None
+        h = model._solver()
+        self._cx = model._cx.retain()
+        S = self.n_samples
+        b = self._cx.dev_tensor(model.y - mu0)[:, 0].contiguous()
+        it, rr, cv, p = (C.c_int32 * S)(), (C.c_double * S)(), (C.c_int32 * S)(), C.c_void_p()
+        try:
+            self._cx.chk(capi.lib().agp_gp_cg_pathwise_draw(h, C.c_void_p(b.data_ptr()), self.n_features, S, C.c_uint64(self.seed),
+                                                            self.t, model.tol, model.max_iter, model.check_every, it, rr, cv,
+                                                            C.byref(p)))
+        except Exception:
+            self._cx.close()
+            raise
+        self._p = p
+        self.info = dict(iterations=np.array(it), residuals=np.array(rr), converged=np.array([bool(v) for v in cv]),
+                         rank_used=model.rank_used)
+
+    def _live(self):
+        if self._p is None:
+            raise RuntimeError("the paths have been freed")
+        return self._p
+
+    def __call__(self, X_test, *, obsdim: int = 1, col_groups: int = 0):
+        """the paths at X_test: (n_samples, n_t).  NumPy in gives NumPy out; a torch tensor on the device gives a device tensor.
+        col_groups as in kernel_matmul, over the feature tiles followed by the training tiles."""
+        import torch
+
+        p, cx = self._live(), self._cx
+        on_device = isinstance(X_test, torch.Tensor) and X_test.is_cuda
+        Xd = cx.dev_tensor(X_test if on_device else np.asarray(X_test, dtype=np.float64))
+        if obsdim == 2:
+            Xd = Xd.t()
+        if Xd.shape[1] != self.D:
+            raise ValueError(f"X_test has {Xd.shape[1]} dimensions, the model {self.D}")
+        if not (Xd.stride(1) == 1 and Xd.stride(0) >= self.D):
+            Xd = Xd.contiguous()
+        nt = Xd.shape[0]
+        out = torch.empty(nt, self.n_samples, dtype=torch.float64, device=cx.dev)
+        cx.chk(capi.lib().agp_gp_cg_pathwise_eval(p, C.c_void_p(Xd.data_ptr()), Xd.stride(0), nt, int(col_groups),
+                                                  C.c_void_p(out.data_ptr()), self.n_samples))
+        cx.chk(capi.lib().agp_ctx_sync(cx.ctx))
+        out = out.t().contiguous()
+        if self._mean != 0.0:
+            out += self._mean
+        return out if on_device else out.cpu().numpy()
+
+    def grad(self, *args, **kwargs):
+        raise NotImplementedError("paths.grad: not built for an IterativeGP (the fused derivative of the feature segment is missing)")
+
+    def maximize(self, *args, **kwargs):
+        raise NotImplementedError("paths.maximize: not built for an IterativeGP (it needs paths.grad)")
+
+    def tables(self):
+        """the draw's tables as NumPy arrays: omega (l, D), phase (l), W (l, S), V (N, S), E (N, S)"""
+        import torch
+
+        p, cx = self._live(), self._cx
+        l, S = self.n_features, self.n_samples
+        shapes = {"omega": (capi.PW_OMEGA, (l, self.D)), "phase": (capi.PW_PHASE, (l,)), "W": (capi.PW_W, (l, S)),
+                  "V": (capi.PW_V, (self.N, S)), "E": (capi.PW_E, (self.N, S))}
+        out = {}
+        for name, (which, shp) in shapes.items():
+            out[name] = torch.empty(*shp, dtype=torch.float64, device=cx.dev)
+            cx.chk(capi.lib().agp_gp_cg_pathwise_get(p, which, C.c_void_p(out[name].data_ptr()), shp[-1]))
+        cx.chk(capi.lib().agp_ctx_sync(cx.ctx))
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def free(self) -> None:
+        """release the device object (idempotent)"""
+        if self._p is not None:
+            capi.lib().agp_gp_cg_pathwise_destroy(self._p)
+            self._p = None
+            self._cx.close()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return (f"IterativePaths({self.n_samples} paths, {self.n_features} features, IterativeGP on {self.N} points, "
+                f"seed={self.seed}, t={self.t})")
+
+
+def sample_paths(model, n_samples: int, *, n_features: int = 1024, seed: Optional[int] = None, t: int = 0):
     """sample_paths(model, n_samples; n_features=1024, seed=nothing, t=0): joint function draws from the posterior of an SVGP, VGP
-    (AnalyticVI / AnalyticSVI), GP or OnlineSVGP.  seed=None takes the model's seed (drawn once from the model's generator, as
-    `sample` does for an MCGP); t is the caller's draw counter: another t, another independent draw from the same seed."""
+    (AnalyticVI / AnalyticSVI), GP or OnlineSVGP, or of an IterativeGP (matrix-free: IterativePaths).  seed=None takes the model's
+    seed (drawn once from the model's generator, as `sample` does for an MCGP); t is the caller's draw counter: another t, another
+    independent draw from the same seed."""
+    from .iterative import IterativeGP
     from .svgp import SVGP
 
+    if isinstance(model, IterativeGP):
+        check_draw_args(model.N, model.D, n_samples, n_features, t, seed)
+        if seed is None:
+            if model.seed is None:
+                model.seed = int(np.random.default_rng().integers(0, 2 ** 63))
+            seed = model.seed
+        return IterativePaths(model, n_samples, n_features, int(seed), t)
     if not isinstance(model, SVGP) and hasattr(model, "_cur"):  # OnlineSVGP: the wrapper that owns the current handle
         if model._cur is None:
             raise RuntimeError("the online model has seen no data yet")

@@ -1406,6 +1406,42 @@ agp_status agp_pathwise_get(agp_pathwise* p, int32_t latent, int32_t which, void
 agp_status agp_pathwise_destroy(agp_pathwise* p);
 agp_status agp_pathwise_features(agp_ctx* ctx, const agp_kernel_desc* k, int64_t D, int32_t n_features, uint64_t seed, int64_t t,
                                  int32_t latent, void* omega_out, void* phase_out);
+/* ---- MATRIX-FREE PATHWISE SAMPLING: function draws from the exact GP of a solver handle (csrc/agp_path.h, agp_path_host.h) ------
+ * Decoupled sampling with no N x N matrix and no Phi or K in memory:
+ *     f_s(x) = Phi(x) w_s + K(x, X) v_s ,   v_s = (K + sigma2 I)^-1 (b - Phi(X) w_s - sigma e_s) ,   b = y - mean
+ * (the caller adds a constant prior mean).  The operator behind both the draw and every evaluation is ONE fused kernel,
+ *     Out[i][c] = sum_{j < l} amp cos(omega_j' (s o x_i) + p_j) W[j][c] + sum_{r < n} variance base(d2(x_i, X_r)) V[r][c] ,
+ * amp = sqrt(2 variance / l), for up to 32 columns per launch: a workgroup owns 64 rows of x and walks the feature tiles, then the
+ * training tiles, of one column group with its output accumulators in registers; both segments run the transposed first product, a
+ * function on the accumulators (cos, or the kernel function of agp_kernel_matmul with its repair of close points) and the second
+ * product on v_mfma_f64_16x16x4.  Float64, D <= 64 (the handle's limit), all four kernels.
+ * agp_gp_cg_pathwise_draw  b: n values (device).  Omega, the phases, W (l x S) and E (n x S) are latent 0's tables of "PATHWISE
+ *   SAMPLING" with m = n: functions of (seed, t, l, S) alone, the bits tests/_pathwise_ref.py computes.  P = Phi(X) W by the fused
+ *   kernel (feature segment only), R = b - P - sigma E, V = (K + sigma2 I)^-1 R by the handle's batched CG in blocks of 32 columns, on
+ *   whichever operator dtype the handle runs, with tol, max_iter and check_every as agp_gp_cg_solve takes them; iters_host /
+ *   relres_host / converged_host: nullable host arrays of S, as agp_gp_cg_solve reports them per column.  The paths object is a
+ *   SNAPSHOT: it owns copies of the prepared training side, Omega, the phases, W, V, E; destroying the handle does not affect it (the
+ *   context must outlive it).  Synchronises.  AGP_ERR_INVALID by name, before anything is touched: b or out NULL, tol < 0 or NaN,
+ *   max_iter < 0, n_features or n_samples outside [1, 65536], n_features D, n_features n_samples or n n_samples >= 2^32, t outside
+ *   [0, 2^32).
+ * agp_gp_cg_pathwise_eval  out (n_t x S, ldo >= S, device) = the paths at xt (n_t x D, ldx >= D): one fused launch per block of 32
+ *   samples, plus the slice sum when the column tiles are split.  col_groups as in agp_kernel_matmul, over the concatenated list of
+ *   ceil(l / 64) feature tiles and ceil(n / 64) training tiles (0: chosen from n_t and the number of CUs, at most 16).  A test point
+ *   that equals a training point is an ordinary input.  No atomics, fixed summation orders: two calls agree bit for bit, whatever
+ *   the pitches.  Kernel values within the "f64" element budget of tests/_kmat_ref.py, features within amp (gamma_{D+3} (sum_d
+ *   |omega_jd s_d x_id| + |p_j|) + 4 u), the sum adds gamma_{n + l + R} sum |terms|.  n_t = 0 is a successful no-op; asynchronous on
+ *   the context's stream (a call that needs a larger slice workspace than any before re-allocates it and waits).
+ * agp_gp_cg_pathwise_get   which = AGP_PW_OMEGA (l x D, ld >= D), AGP_PW_PHASE (l; ld not read), AGP_PW_W (l x S, ld >= S), AGP_PW_V
+ *   (n x S, ld >= S), AGP_PW_E (n x S, ld >= S).  Asynchronous.
+ * Not built: input gradients and the ascent of these paths, Float32 instances of the fused kernel, D > 64, several latents. */
+typedef struct agp_gp_cg_paths agp_gp_cg_paths;
+agp_status agp_gp_cg_pathwise_draw(agp_gp_cg* h, const void* b, int64_t n_features, int64_t n_samples, uint64_t seed, int64_t t,
+                                   double tol, int64_t max_iter, int64_t check_every, int32_t* iters_host, double* relres_host,
+                                   int32_t* converged_host, agp_gp_cg_paths** out);
+agp_status agp_gp_cg_pathwise_eval(agp_gp_cg_paths* p, const void* xt, int64_t ldx, int64_t n_t, int32_t col_groups, void* out,
+                                   int64_t ldo);
+agp_status agp_gp_cg_pathwise_get(agp_gp_cg_paths* p, int32_t which, void* out, int64_t ld);
+agp_status agp_gp_cg_pathwise_destroy(agp_gp_cg_paths* p);
 
 /* ---- multi-GPU: one process per GPU, collectives behind the ABI --------------------------------
  * The path shards in two ways and both reduce to in-place SUM all-reduces of library-owned device buffers:

@@ -16,6 +16,12 @@ ratios of the best times; --lml then times the log marginal likelihood on each o
 and p = --big column points, per r, beside agp_kernel_matmul's cross product on the same shapes, with the ratio of the best times and
 the ratio of the MFMA counts (1 + CB) DP ceil(r / CB) / (DP + R); --predgrad N: one predict_f_grad(cov=True) of an IterativeGP on 32
 test points at N training points, split into the batched solve and the gradient kernel's two launches (0 skips either).
+--paths NT: one evaluation of 32 pathwise draws of an IterativeGP (agp_gp_cg_pathwise_eval, csrc/agp_path.h) at NT points against
+N = --n training points and --features random features, (a) `fused`; (b) `composed`, the same result from what there was before:
+agp_pathwise_eval of a 64-point GP's draw with the same number of features (k_pw_features into memory, 64 columns of kernel matrix,
+one GEMM) plus agp_kernel_matmul's cross product against the N points; (c) `matmul_same_columns`, agp_kernel_matmul alone at
+p = N + features columns: what the fused walk should approach.  --paths-draw N adds one whole draw (tables, Phi(X) W, the batched CG
+at tol 1e-6 with the default preconditioner) of 32 paths at N points.
 Prints one JSON line; kernel values per second count n * p evaluations.  A record, not a gate.
 """
 import argparse
@@ -56,6 +62,9 @@ def main():
     ap.add_argument("--lml", type=int, default=0)
     ap.add_argument("--dx", type=int, default=0)
     ap.add_argument("--predgrad", type=int, default=0)
+    ap.add_argument("--paths", type=int, default=0)
+    ap.add_argument("--features", type=int, default=1024)
+    ap.add_argument("--paths-draw", type=int, default=0)
     ap.add_argument("--dtype", nargs="+", choices=["f64", "f32"], default=["f64", "f32"])
     a = ap.parse_args()
     g.build()
@@ -168,6 +177,58 @@ def main():
                                      gradient_kernels=timed(kernels, a.reps), iterations=int(m.info["iterations"].max()),
                                      converged=bool(m.info["converged"].all()))
         m.close()
+    if a.paths or a.paths_draw:
+        import numpy as np
+
+        kern, S = AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale), 32
+        hgen = torch.Generator().manual_seed(3)
+
+        def model(n):
+            Xh = torch.rand(n, a.D, dtype=torch.float64, generator=hgen).numpy()
+            return AGP.IterativeGP(Xh, np.sin(Xh.sum(axis=1)), kern, noise=1e-2, tol=1e-6)
+
+        if a.paths:
+            nt, m = a.paths, model(a.n)
+            paths = AGP.sample_paths(m, S, n_features=a.features, seed=1)
+            Xt = torch.rand(nt, a.D, dtype=torch.float64, device="cuda", generator=gen)
+            of, oc, ok = (torch.empty(nt, S, dtype=torch.float64, device="cuda") for _ in range(3))
+            gp = AGP.GP(m.X[:64], m.y[:64], kern, noise=1e-2, optimiser=False, opt_noise=False)
+            AGP.train_(gp, 1)
+            small = AGP.sample_paths(gp, S, n_features=a.features, seed=1)
+            Fs = torch.empty(S, nt, dtype=torch.float64, device="cuda")
+            V = torch.randn(a.n, S, dtype=torch.float64, device="cuda", generator=gen)
+            Vb = torch.randn(a.n + a.features, S, dtype=torch.float64, device="cuda", generator=gen)
+            Yb = torch.rand(a.n + a.features, a.D, dtype=torch.float64, device="cuda", generator=gen)
+
+            def cross(Y, Vm, out):
+                st = L.agp_kernel_matmul(ctx, capi.F64, C.byref(kd), Xt.data_ptr(), nt, a.D, Y.data_ptr(), Y.shape[0], a.D, a.D, 0, 0.0,
+                                         Vm.data_ptr(), S, S, 0, out.data_ptr(), S)
+                assert st == 0, L.agp_last_error(ctx)
+
+            def fused_eval():
+                assert L.agp_gp_cg_pathwise_eval(paths._p, Xt.data_ptr(), a.D, nt, 0, of.data_ptr(), S) == 0
+                assert L.agp_ctx_sync(m._cx.ctx) == 0
+
+            def composed():
+                assert L.agp_pathwise_eval(small._p, Xt.data_ptr(), a.D, nt, Fs.data_ptr(), nt) == 0
+                assert L.agp_ctx_sync(gp._ctx) == 0
+                cross(m._Xd, V, oc)
+
+            res["paths_eval"] = dict(N=a.n, L=a.features, nt=nt, S=S, fused=timed(fused_eval, a.reps), composed=timed(composed, a.reps),
+                                     matmul_same_columns=timed(lambda: cross(Yb, Vb, ok), a.reps))
+            paths.free()
+            small.free()
+            m.close()
+        if a.paths_draw:
+            m = model(a.paths_draw)
+            m._solver()  # (the handle and its preconditioner are not part of the draw)
+            box = []
+            t = timed(lambda: box.append(AGP.sample_paths(m, S, n_features=a.features, seed=1, t=len(box))), 1)
+            res["paths_draw"] = dict(N=a.paths_draw, L=a.features, S=S, **t, iterations=int(box[-1].info["iterations"].max()),
+                                     converged=bool(box[-1].info["converged"].all()))
+            for pth in box:
+                pth.free()
+            m.close()
     if a.lml:
         Xh = torch.rand(a.lml, a.D, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).numpy()
         import numpy as np
