@@ -5546,6 +5546,32 @@ agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc*
                           ldv, r, col_groups, (double*)out, ldo);
 }
 
+agp_status agp_kernel_matmul_wide(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                  const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
+                                  int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo) {
+  if (!ctx) return AGP_ERR_INVALID;
+  bool unsupported = dtype == AGP_F32;
+  const char* bad = dtype == AGP_F32   ? "AGP_F32 is not built: the wide block is Float64 only (dtype AGP_F64)"
+                    : dtype != AGP_F64 ? "dtype is AGP_F64"
+                                       : kmv_bad_args(k, x, n, ldx, D, &unsupported);
+  if (!bad) {
+    if (!v || !out || (!sym && !y)) bad = "null v, out or y";
+    else if (r < 1 || r > KMV_WIDE_MAXR) bad = "1 <= r <= 128";
+    else if (p <= 0) bad = "p > 0";
+    else if (sym ? n != p : ldy < D) bad = sym ? "sym: p == n" : "ldy >= D";
+    else if (ldv < r || ldo < r) bad = "ldv >= r and ldo >= r";
+    else if (col_groups < 0) bad = "col_groups >= 0";
+    else if (sym && !std::isfinite(diag_add)) bad = "a finite diag_add";
+  }
+  if (bad) {
+    ctx->err = std::string("agp_kernel_matmul_wide: ") + bad;
+    return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  return bb_kernel_matmul(ctx, k, (const double*)x, n, ldx, (const double*)y, p, ldy, D, sym ? 1 : 0, diag_add, (const double*)v,
+                          ldv, r, col_groups, (double*)out, ldo);
+}
+
 agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D,
                             double sigma2, int64_t precond_rank, agp_gp_cg** out, int64_t* rank_used_host) {
   if (!ctx || !out) return AGP_ERR_INVALID;
@@ -5578,14 +5604,37 @@ agp_status agp_gp_cg_set_operator_dtype(agp_gp_cg* h, int32_t dtype) {
     h->ctx->err = "agp_gp_cg_set_operator_dtype: dtype is AGP_F64 or AGP_F32";
     return AGP_ERR_INVALID;
   }
+  if (dtype == AGP_F32 && h->block != CG_LD) {
+    h->ctx->err = "agp_gp_cg_set_operator_dtype: the Float32 operator has no wide block: AGP_F32 needs the block of 32 "
+                  "(agp_gp_cg_set_block)";
+    return AGP_ERR_UNSUPPORTED;
+  }
   DevGuard guard(h->ctx->device);
   return cg_set_operator(h, dtype == AGP_F32 ? 1 : 0);
 }
 
+agp_status agp_gp_cg_set_block(agp_gp_cg* h, int64_t block) {
+  if (!h) return AGP_ERR_INVALID;
+  if (block != CG_LD && block != KMV_WIDE_MAXR) {
+    h->ctx->err = "agp_gp_cg_set_block: block is 32 or 128";
+    return AGP_ERR_INVALID;
+  }
+  if (block != CG_LD && h->f32) {
+    h->ctx->err = "agp_gp_cg_set_block: the Float32 operator has no wide block: 128 needs the Float64 operator "
+                  "(agp_gp_cg_set_operator_dtype)";
+    return AGP_ERR_UNSUPPORTED;
+  }
+  DevGuard guard(h->ctx->device);
+  return cg_set_block(h, (int)block);  // (a failure leaves the handle at its old block, every workspace in place)
+}
+
+// "1 <= r <= 32" or "1 <= r <= 128": what the handle's block allows
+static const char* cg_bad_r(const agp_gp_cg* h) { return h->block > CG_LD ? "1 <= r <= 128 (the handle's block)" : "1 <= r <= 32"; }
+
 agp_status agp_gp_cg_apply(agp_gp_cg* h, const void* v, int64_t ldv, int64_t r, void* out, int64_t ldo) {
   if (!h) return AGP_ERR_INVALID;
-  if (!v || !out || r < 1 || r > KMV_MAXR || ldv < r || ldo < r) {
-    h->ctx->err = "agp_gp_cg_apply: v, out, 1 <= r <= 32, ldv >= r and ldo >= r";
+  if (!v || !out || r < 1 || r > h->block || ldv < r || ldo < r) {
+    h->ctx->err = std::string("agp_gp_cg_apply: v, out, ") + cg_bad_r(h) + ", ldv >= r and ldo >= r";
     return AGP_ERR_INVALID;
   }
   DevGuard guard(h->ctx->device);
@@ -5599,7 +5648,7 @@ agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, 
   if (!h) return AGP_ERR_INVALID;
   const char* bad = nullptr;
   if (!b || !a) bad = "null b or a";
-  else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
+  else if (r < 1 || r > h->block) bad = cg_bad_r(h);
   else if (ldb < r || lda < r) bad = "ldb >= r and lda >= r";
   else if (!(tol >= 0.0)) bad = "tol >= 0";
   else if (max_iter < 0) bad = "max_iter >= 0";
@@ -5706,7 +5755,7 @@ agp_status agp_gp_cg_solve_slq(agp_gp_cg* h, const void* b, int64_t ldb, int64_t
   if (!h) return AGP_ERR_INVALID;
   const char* bad = nullptr;
   if (!b || !a || !z0 || !bpb_host || !quad_host) bad = "null b, a, z0, bpb_host or quad_host";
-  else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
+  else if (r < 1 || r > h->block) bad = cg_bad_r(h);
   else if (ldb < r || lda < r || ldz0 < r) bad = "ldb >= r, lda >= r and ldz0 >= r";
   else if (!(tol >= 0.0)) bad = "tol >= 0";
   else if (max_iter < 0) bad = "max_iter >= 0";
@@ -6512,8 +6561,7 @@ agp_status agp_gp_cg_pathwise_draw(agp_gp_cg* h, const void* b, int64_t n_featur
   if (!out) bad = "out must be given";
   else if (!b) bad = "b must be given";
   else if (!(tol >= 0.0)) bad = "tol >= 0";
-  else if (max_iter < 0) bad = "max_iter >= 0";
-  if (bad) {
+  else if (max_iter < 0) bad = "max_iter >= 0";  if (bad) {
     ctx->err = std::string("agp_gp_cg_pathwise_draw: ") + bad;
     return AGP_ERR_INVALID;
   }

@@ -32,8 +32,10 @@ namespace agp {
 
 constexpr int KMV_MAXD = 64;  // input dimensions
 constexpr int KMV_MAXR = 32;  // right-hand sides per launch
+// row stride of the V tile: R = 16 RB rounded up to 16 (mod 32), so rows j, j + 1 start half the banks apart -- 16 (RB = 1: one row per
+// pass), 48 (RB = 2), and 48, 80, 112, 144 for the wide block's RB = 3, 4, 6, 8 (agp_kmv_wide.h)
 template <int RB>
-constexpr int KMV_LDV = RB == 1 ? 16 : 48;
+constexpr int KMV_LDV = RB == 1 ? 16 : (16 * RB) % 32 == 16 ? 16 * RB : 16 * RB + 16;
 template <int DP, int RB>
 constexpr size_t kmv_smem_bytes() {
   return sizeof(double) * (size_t)(2 * TILE * (DP + 2) + TILE * KMV_LDV<RB> + 2 * TILE + DP);
@@ -41,13 +43,13 @@ constexpr size_t kmv_smem_bytes() {
 
 // grid = (column groups, row tiles).  Ysc / yng: k_scale_rows' output for Y with row width DP, rows padded to a multiple of 64.
 // out: n x r with leading dimension ldo; group g writes at out + g * slice (slice = 0 with one group: straight into the result).
+// kmv_body is the whole kernel: k_kmv (RB = 1, 2) and k_kmv_wide (agp_kmv_wide.h: RB = 3, 4, 6, 8) are this one body under their own
+// launch bounds, so the two paths cannot drift apart and a column is the same chain of operations in both.
 template <int KIND, int DP, int RB>
-__global__ __launch_bounds__(NTHREADS, DP == 64 ? 1 : 2) void k_kmv(const double* __restrict__ X, int64_t ldx, int64_t n,
-                                                                    const double* __restrict__ Ysc, const double* __restrict__ yng,
-                                                                    int64_t p, int64_t D, const double* __restrict__ scales,
-                                                                    double variance, int sym, double diag_add,
-                                                                    const double* __restrict__ V, int64_t ldv, int r,
-                                                                    double* __restrict__ out, int64_t ldo, int64_t slice) {
+__device__ __forceinline__ void kmv_body(const double* __restrict__ X, int64_t ldx, int64_t n, const double* __restrict__ Ysc,
+                                         const double* __restrict__ yng, int64_t p, int64_t D, const double* __restrict__ scales,
+                                         double variance, int sym, double diag_add, const double* __restrict__ V, int64_t ldv, int r,
+                                         double* __restrict__ out, int64_t ldo, int64_t slice) {
   constexpr int LDX = DP + 2, LDV = KMV_LDV<RB>, NK = DP / 4, YQ = DP / 8, VQ = 4 * RB, R = 16 * RB;
   extern __shared__ __attribute__((aligned(16))) unsigned char kmv_smem[];
   double* Xs = reinterpret_cast<double*>(kmv_smem);  // [64][LDX]
@@ -198,6 +200,15 @@ __global__ __launch_bounds__(NTHREADS, DP == 64 ? 1 : 2) void k_kmv(const double
       if (gi < n && c < r) dst[gi * ldo + c] = o[cb][q];
     }
 }
+template <int KIND, int DP, int RB>
+__global__ __launch_bounds__(NTHREADS, DP == 64 ? 1 : 2) void k_kmv(const double* __restrict__ X, int64_t ldx, int64_t n,
+                                                                    const double* __restrict__ Ysc, const double* __restrict__ yng,
+                                                                    int64_t p, int64_t D, const double* __restrict__ scales,
+                                                                    double variance, int sym, double diag_add,
+                                                                    const double* __restrict__ V, int64_t ldv, int r,
+                                                                    double* __restrict__ out, int64_t ldo, int64_t slice) {
+  kmv_body<KIND, DP, RB>(X, ldx, n, Ysc, yng, p, D, scales, variance, sym, diag_add, V, ldv, r, out, ldo, slice);
+}
 
 // Out[i][c] = sum_g ws[g][i][c], ascending g (slices are n x r, dense)
 __global__ __launch_bounds__(256) void k_kmv_sum(const double* __restrict__ ws, int groups, int64_t n, int r,
@@ -213,6 +224,10 @@ __global__ __launch_bounds__(256) void k_kmv_sum(const double* __restrict__ ws, 
 // Batched preconditioned CG: r <= 32 independent recurrences that share every operator product.  All vectors are n x 32 row-major
 // (CG_LD), columns >= r zero.  Per-column scalars live in CgScal on the device, double-buffered by iteration parity: the workgroup
 // that finishes an iteration's scalars writes buffer (it + 1) & 1 while the others still read buffer it & 1.
+// A handle set to the block of 128 (agp_gp_cg_set_block) keeps its vectors n x 128 (`ld`) and runs the same kernels on a grid whose
+// y index is the PANEL of 32 columns: panel q owns columns 32 q .. 32 q + 31, the CgScal pair sc[2 q], sc[2 q + 1] and its own partials
+// (part + q nblk 32).  A column's recurrence reads nothing of another column, so it is the arithmetic of the block of 32 unchanged;
+// with ld = 32 and one panel every index below is the one it was.
 // Column dots are two-stage and of fixed order: every workgroup of 256 rows leaves one partial per column (rows in a fixed
 // tree), and whoever needs the dot adds the partials in ascending workgroup order -- every workgroup for itself, same bits.
 // A column is ACTIVE while it is neither converged nor broken down; an inactive column is skipped, not multiplied by zero: its
@@ -246,20 +261,22 @@ __device__ __forceinline__ double cg_sum_parts(const double* __restrict__ part, 
   for (int64_t b = 0; b < nblk; ++b) s += part[b * CG_LD + c];
   return s;
 }
+// this workgroup's panel: its partials and its slot among them
+__device__ __forceinline__ int64_t cg_part_base(int64_t nblk) { return (int64_t)blockIdx.y * nblk * CG_LD; }
 
 // part[blk][c] = sum_{rows of blk} A[i][c] B[i][c]
-__global__ __launch_bounds__(256) void k_cg_dot(const double* __restrict__ A, const double* __restrict__ B, int64_t n,
+__global__ __launch_bounds__(256) void k_cg_dot(const double* __restrict__ A, const double* __restrict__ B, int64_t n, int64_t ld,
                                                 double* __restrict__ part) {
   __shared__ double red[256];
-  const int tid = threadIdx.x, c = tid & 31;
+  const int tid = threadIdx.x, c = blockIdx.y * CG_LD + (tid & 31);
   const int64_t r0 = blockIdx.x * (int64_t)CG_ROWS;
   double s = 0.0;
   for (int q = tid >> 5; q < CG_ROWS; q += 8) {
     const int64_t i = r0 + q;
-    if (i < n) s += A[i * CG_LD + c] * B[i * CG_LD + c];
+    if (i < n) s += A[i * ld + c] * B[i * ld + c];
   }
   s = cg_block_coldot(s, red);
-  if (tid < CG_LD) part[blockIdx.x * CG_LD + tid] = s;
+  if (tid < CG_LD) part[cg_part_base(gridDim.x) + blockIdx.x * CG_LD + tid] = s;
 }
 
 // init != 0: x = 0, r = B (n x r, ldb; columns >= r zero).  Otherwise alpha = rz / (p . q) from the partials of k_cg_dot,
@@ -270,16 +287,19 @@ __global__ __launch_bounds__(256) void k_cg_update(int init, const double* __res
                                                    int64_t nblk, const CgScal* __restrict__ sc, const double* __restrict__ part_pq,
                                                    const double* __restrict__ P, const double* __restrict__ Q,
                                                    double* __restrict__ Xv, double* __restrict__ Rv, double* __restrict__ Rt,
-                                                   int64_t ldt, double* __restrict__ part_rr, double* __restrict__ coef) {
+                                                   int64_t ldt, double* __restrict__ part_rr, double* __restrict__ coef,
+                                                   int64_t ld) {
   __shared__ double red[256];
-  const int tid = threadIdx.x, c = tid & 31;
+  const int tid = threadIdx.x, lc = tid & 31, c = blockIdx.y * CG_LD + lc;  // lc: the column within this panel's scalars and partials
   const int64_t r0 = blockIdx.x * (int64_t)CG_ROWS;
+  sc += 2 * blockIdx.y;
+  part_pq += cg_part_base(nblk);
   bool act = false;
   double alpha = 0.0;
-  if (!init && sc->active[c]) {
-    const double pq = cg_sum_parts(part_pq, nblk, c);
+  if (!init && sc->active[lc]) {
+    const double pq = cg_sum_parts(part_pq, nblk, lc);
     act = pq > 0.0;  // (a breakdown is recorded by k_cg_direction, from the same sum)
-    if (act) alpha = sc->rz[c] / pq;
+    if (act) alpha = sc->rz[lc] / pq;
   }
   if (coef && blockIdx.x == 0 && tid < CG_LD) coef[c] = alpha;
   double s = 0.0;
@@ -289,40 +309,40 @@ __global__ __launch_bounds__(256) void k_cg_update(int init, const double* __res
     double rv;
     if (init) {
       rv = c < rcols ? B[i * ldb + c] : 0.0;
-      Xv[i * CG_LD + c] = 0.0;
-      Rv[i * CG_LD + c] = rv;
+      Xv[i * ld + c] = 0.0;
+      Rv[i * ld + c] = rv;
     } else {
-      rv = Rv[i * CG_LD + c];
+      rv = Rv[i * ld + c];
       if (act) {
-        Xv[i * CG_LD + c] = __builtin_fma(alpha, P[i * CG_LD + c], Xv[i * CG_LD + c]);
-        rv = __builtin_fma(-alpha, Q[i * CG_LD + c], rv);
-        Rv[i * CG_LD + c] = rv;
+        Xv[i * ld + c] = __builtin_fma(alpha, P[i * ld + c], Xv[i * ld + c]);
+        rv = __builtin_fma(-alpha, Q[i * ld + c], rv);
+        Rv[i * ld + c] = rv;
       }
     }
     if (Rt && (init || act)) Rt[c * ldt + i] = rv;
     s += rv * rv;
   }
   s = cg_block_coldot(s, red);
-  if (tid < CG_LD) part_rr[blockIdx.x * CG_LD + tid] = s;
+  if (tid < CG_LD) part_rr[cg_part_base(nblk) + blockIdx.x * CG_LD + tid] = s;
 }
 
 // z = (r - Zl) / sigma2 (Woodbury; Zl = L (sigma2 I + L'L)^-1 L' r, n x 64 with leading dimension ldz) and the partials of r . z
 __global__ __launch_bounds__(256) void k_cg_precond(int64_t n, const double* __restrict__ Rv, const double* __restrict__ Zl,
                                                     int64_t ldz, double inv_sigma2, double* __restrict__ Z,
-                                                    double* __restrict__ part_rz) {
+                                                    double* __restrict__ part_rz, int64_t ld) {
   __shared__ double red[256];
-  const int tid = threadIdx.x, c = tid & 31;
+  const int tid = threadIdx.x, c = blockIdx.y * CG_LD + (tid & 31);
   const int64_t r0 = blockIdx.x * (int64_t)CG_ROWS;
   double s = 0.0;
   for (int q = tid >> 5; q < CG_ROWS; q += 8) {
     const int64_t i = r0 + q;
     if (i >= n) continue;
-    const double rv = Rv[i * CG_LD + c], z = (rv - Zl[i * ldz + c]) * inv_sigma2;
-    Z[i * CG_LD + c] = z;
+    const double rv = Rv[i * ld + c], z = (rv - Zl[i * ldz + c]) * inv_sigma2;
+    Z[i * ld + c] = z;
     s += rv * z;
   }
   s = cg_block_coldot(s, red);
-  if (tid < CG_LD) part_rz[blockIdx.x * CG_LD + tid] = s;
+  if (tid < CG_LD) part_rz[cg_part_base(gridDim.x) + blockIdx.x * CG_LD + tid] = s;
 }
 
 // The end of an iteration (init != 0: of the set-up).  rz_new and |r|^2 from their partials; a column whose |r|^2 <= tol^2 |b|^2
@@ -333,17 +353,19 @@ __global__ __launch_bounds__(256) void k_cg_direction(int init, int64_t n, int64
                                                       CgScal* __restrict__ sc_next, const double* __restrict__ part_pq,
                                                       const double* __restrict__ part_rr, const double* __restrict__ part_rz,
                                                       const double* __restrict__ Rv, const double* __restrict__ Z,
-                                                      double* __restrict__ P, double* __restrict__ coef) {
-  const int tid = threadIdx.x, c = tid & 31;
+                                                      double* __restrict__ P, double* __restrict__ coef, int64_t ld) {
+  const int tid = threadIdx.x, lc = tid & 31;
   const int64_t r0 = blockIdx.x * (int64_t)CG_ROWS;
-  const bool was = init ? true : sc->active[c] != 0;
-  double rr = init ? 0.0 : sc->rr[c], rz = init ? 0.0 : sc->rz[c], bb = init ? 0.0 : sc->bb[c], beta = 0.0;
-  bool act = false, conv = init ? false : sc->conv[c] != 0, stepped = false;
+  sc += 2 * blockIdx.y, sc_next += 2 * blockIdx.y;
+  part_pq += cg_part_base(nblk), part_rr += cg_part_base(nblk), part_rz += cg_part_base(nblk);
+  const bool was = init ? true : sc->active[lc] != 0;
+  double rr = init ? 0.0 : sc->rr[lc], rz = init ? 0.0 : sc->rz[lc], bb = init ? 0.0 : sc->bb[lc], beta = 0.0;
+  bool act = false, conv = init ? false : sc->conv[lc] != 0, stepped = false;
   if (was) {
-    stepped = init || cg_sum_parts(part_pq, nblk, c) > 0.0;
+    stepped = init || cg_sum_parts(part_pq, nblk, lc) > 0.0;
     if (stepped) {
-      rr = cg_sum_parts(part_rr, nblk, c);
-      const double rz_new = Z ? cg_sum_parts(part_rz, nblk, c) : rr;
+      rr = cg_sum_parts(part_rr, nblk, lc);
+      const double rz_new = Z ? cg_sum_parts(part_rz, nblk, lc) : rr;
       if (init) bb = rr;
       conv = rr <= tol2 * bb;  // (bb = 0: a zero column, converged with x = 0)
       act = !conv && rz_new > 0.0;
@@ -351,36 +373,37 @@ __global__ __launch_bounds__(256) void k_cg_direction(int init, int64_t n, int64
       rz = rz_new;
     }
   }
+  const int c = blockIdx.y * CG_LD + lc;
   if (act)
     for (int q = tid >> 5; q < CG_ROWS; q += 8) {
       const int64_t i = r0 + q;
       if (i >= n) continue;
-      const double z = Z ? Z[i * CG_LD + c] : Rv[i * CG_LD + c];
-      P[i * CG_LD + c] = init ? z : __builtin_fma(beta, P[i * CG_LD + c], z);
+      const double z = Z ? Z[i * ld + c] : Rv[i * ld + c];
+      P[i * ld + c] = init ? z : __builtin_fma(beta, P[i * ld + c], z);
     }
   if (blockIdx.x == 0 && tid < CG_LD) {
-    if (coef) coef[CG_LD + c] = beta;
-    sc_next->rz[c] = rz;
-    sc_next->bb[c] = bb;
-    sc_next->rr[c] = rr;
-    sc_next->active[c] = act ? 1 : 0;
-    sc_next->conv[c] = conv ? 1 : 0;
-    sc_next->iters[c] = init ? 0 : sc->iters[c] + ((was && stepped) ? 1 : 0);
+    if (coef) coef[ld + c] = beta;
+    sc_next->rz[lc] = rz;
+    sc_next->bb[lc] = bb;
+    sc_next->rr[lc] = rr;
+    sc_next->active[lc] = act ? 1 : 0;
+    sc_next->conv[lc] = conv ? 1 : 0;
+    sc_next->iters[lc] = init ? 0 : sc->iters[lc] + ((was && stepped) ? 1 : 0);
   }
 }
 
-// out[i][c] (ldo) = A[i][c] (n x 32), c < r
+// out[i][c] (ldo) = A[i][c] (n x ld), c < r
 __global__ __launch_bounds__(256) void k_cg_export(const double* __restrict__ A, int64_t n, int r, double* __restrict__ out,
-                                                   int64_t ldo) {
-  const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x, i = e / CG_LD;
-  const int c = (int)(e % CG_LD);
+                                                   int64_t ldo, int64_t ld) {
+  const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x, i = e / ld;
+  const int c = (int)(e % ld);
   if (i < n && c < r) out[i * ldo + c] = A[e];
 }
-// out[i][c] (ldo) = scale * A[i][c] (n x 32), c < r: the copy of the first preconditioned residual z0 = P^-1 b
+// out[i][c] (ldo) = scale * A[i][c] (n x ld), c < r: the copy of the first preconditioned residual z0 = P^-1 b
 __global__ __launch_bounds__(256) void k_cg_export_scaled(const double* __restrict__ A, int64_t n, int r, double scale,
-                                                          double* __restrict__ out, int64_t ldo) {
-  const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x, i = e / CG_LD;
-  const int c = (int)(e % CG_LD);
+                                                          double* __restrict__ out, int64_t ldo, int64_t ld) {
+  const int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x, i = e / ld;
+  const int c = (int)(e % ld);
   if (i < n && c < r) out[i * ldo + c] = scale * A[e];
 }
 // probes z ~ N(0, L L' + sigma2 I): out[i][c] (ldo) = Zl[i][c] (= L eps1, n x 64 with leading dimension ldz; nullable) + sigma E[c][i],

@@ -5,7 +5,8 @@
 // that reports its Lanczos coefficients (cg_solve_slq), the probes z ~ N(0, P) and log det P.  Float64, except the operator itself,
 // which also has a Float32 instance (agp_kmv_f32.h: Kmv32Op, kmv32_prepare, kmv32_apply, bb_kernel_matmul_f32) that the solver handle
 // can be switched to (cg_set_operator); its vectors, preconditioner, probes and Lanczos table stay Float64.  The derivative with
-// respect to the row points (agp_kmv_dx.h: kmv_dx_apply, kmv_dx_run, bb_kernel_matmul_dx) is Float64 only.
+// respect to the row points (agp_kmv_dx.h: kmv_dx_apply, kmv_dx_run, bb_kernel_matmul_dx) is Float64 only.  More than 32 and up to 128
+// columns go through the wide kernel (agp_kmv_wide.h) inside kmv_apply; cg_set_block sizes the solver handle for 128 columns.
 #pragma once
 #include <cmath>
 #include <string>
@@ -18,6 +19,7 @@
 #include "agp_kmv_dx.h"
 #include "agp_kmv_f32.h"
 #include "agp_kmv_grad.h"
+#include "agp_kmv_wide.h"
 #include "agp_rand.h"
 #include "agp_select_host.h"
 
@@ -100,13 +102,50 @@ static void kmv_launch_kind(hipStream_t st, dim3 grid, const double* X, int64_t 
 #undef AGP_KMV_CASE
 }
 
+// the wide block (agp_kmv_wide.h): 32 < r <= 128 in one launch, the narrowest of the instances 48, 64, 96, 128 that holds r
+template <int KIND, int DP, int RB>
+static void kmv_wide_launch_one(hipStream_t st, dim3 grid, const double* X, int64_t ldx, int64_t n, const KmvOp& op, int sym,
+                                double diag_add, const double* V, int64_t ldv, int r, double* out, int64_t ldo, int64_t slice) {
+  constexpr size_t sh = kmv_smem_bytes<DP, RB>();
+  if constexpr (sh > 64 * 1024) {  // more than 64 KB of dynamic LDS has to be requested once per kernel
+    static bool asked = false;
+    if (!asked) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kmv_wide<KIND, DP, RB>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)sh);
+      asked = true;
+    }
+  }
+  hipLaunchKernelGGL((k_kmv_wide<KIND, DP, RB>), grid, dim3(NTHREADS), sh, st, X, ldx, n, (const double*)op.ysc,
+                     (const double*)op.ysn, op.p, op.D, (const double*)op.scales, op.variance, sym, diag_add, V, ldv, r, out, ldo, slice);
+}
+template <int KIND>
+static void kmv_wide_launch_kind(hipStream_t st, dim3 grid, const double* X, int64_t ldx, int64_t n, const KmvOp& op, int sym,
+                                 double diag_add, const double* V, int64_t ldv, int r, double* out, int64_t ldo, int64_t slice) {
+#define AGP_KMVW_CASE(DPV)                                                                                                \
+  if (r <= 48) kmv_wide_launch_one<KIND, DPV, 3>(st, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, out, ldo, slice);      \
+  else if (r <= 64) kmv_wide_launch_one<KIND, DPV, 4>(st, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, out, ldo, slice); \
+  else if (r <= 96) kmv_wide_launch_one<KIND, DPV, 6>(st, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, out, ldo, slice); \
+  else kmv_wide_launch_one<KIND, DPV, 8>(st, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, out, ldo, slice)
+  if (op.DP == 16) { AGP_KMVW_CASE(16); }
+  else if (op.DP == 32) { AGP_KMVW_CASE(32); }
+  else { AGP_KMVW_CASE(64); }
+#undef AGP_KMVW_CASE
+}
+
 // out (n x r, ldo) = (K(X, Y) + diag_add [sym]) V, enqueued on the context's stream.  groups > 1: ws holds groups * n * r doubles.
+// r <= 32: k_kmv; 32 < r <= 128: k_kmv_wide.
 static agp_status kmv_apply(agp_ctx* ctx, const KmvOp& op, const double* X, int64_t ldx, int64_t n, int sym, double diag_add,
                             const double* V, int64_t ldv, int r, int groups, double* ws, double* out, int64_t ldo) {
   const dim3 grid((unsigned)groups, (unsigned)((n + TILE - 1) / TILE));
   double* dst = groups > 1 ? ws : out;
   const int64_t ldd = groups > 1 ? r : ldo, slice = groups > 1 ? n * r : 0;
-  switch (op.kind) {
+  if (r > KMV_MAXR) switch (op.kind) {
+    case AGP_K_SQEXP: kmv_wide_launch_kind<K_SQEXP>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+    case AGP_K_MATERN52: kmv_wide_launch_kind<K_MATERN52>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+    case AGP_K_MATERN32: kmv_wide_launch_kind<K_MATERN32>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+    default: kmv_wide_launch_kind<K_EXPONENTIAL>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+  }
+  else switch (op.kind) {
     case AGP_K_SQEXP: kmv_launch_kind<K_SQEXP>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
     case AGP_K_MATERN52: kmv_launch_kind<K_MATERN52>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
     case AGP_K_MATERN32: kmv_launch_kind<K_MATERN32>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
@@ -266,16 +305,18 @@ struct agp_gp_cg {
   int64_t n = 0, np = 0, D = 0, nblk = 0, k = 0, kp = 0;
   double sigma2 = 0.0, logdetM = 0.0;  // logdetM = log det(sigma2 I_k + L'L)
   int groups = 1;
+  int block = CG_LD;   // columns per batched solve: 32, or 128 after cg_set_block; the row stride of Xv .. Qv
+  int64_t cw = TILE;   // columns the preconditioner's buffers hold (Rt, Ct, Wt rows; Zl's row stride): 64, or 128 at block 128
   KmvOp op;
   Kmv32Op op32;  // the Float32 operator, prepared by cg_set_operator (f32 != 0)
   int f32 = 0;
   float* v32 = nullptr;  // n x 32: the rounded copy of V of a Float32 product
   std::vector<double> scales_host;
   double *X = nullptr, *ws = nullptr, *L = nullptr, *Lt = nullptr, *Minv = nullptr;
-  double *Xv = nullptr, *Rv = nullptr, *Zv = nullptr, *Pv = nullptr, *Qv = nullptr;  // n x 32
-  double *Rt = nullptr, *Ct = nullptr, *Wt = nullptr, *Zl = nullptr;                  // 64 x np, 64 x kp, 64 x kp, np x 64
-  double *part = nullptr;                                                             // 3 x nblk x 32
-  CgScal* sc = nullptr;                                                               // [2]
+  double *Xv = nullptr, *Rv = nullptr, *Zv = nullptr, *Pv = nullptr, *Qv = nullptr;  // np x block
+  double *Rt = nullptr, *Ct = nullptr, *Wt = nullptr, *Zl = nullptr;                  // cw x np, cw x kp, cw x kp, np x cw
+  double *part = nullptr;                                                             // 3 x (block / 32) panels x nblk x 32
+  CgScal* sc = nullptr;                                                               // [block / 32 panels][2]
 };
 // stop rule of the preconditioner's pivoted Cholesky, relative to the variance: far above the rounding of its residual diagonal
 // (about n u), far below any sigma2 a model would use
@@ -357,6 +398,50 @@ static agp_status cg_setup(agp_gp_cg* h, const agp_kernel_desc* k, const double*
   return s;
 }
 
+// How many columns a batched solve and a product on the handle take: 32 (as created) or 128.  Everything sized by it is allocated
+// anew: the CG vectors (np x block), the partials and the scalar tables (one set per panel of 32 columns), the slices of the
+// column-group split, and the preconditioner's transposed residual, its two small products and L's product (cw = 64 or 128
+// columns).  The new buffers are allocated FIRST and swapped in only when every one of them is there: a failure leaves the handle
+// as it was, valid at its old block.  What is fixed per (X, kernel, sigma2) -- the prepared operator, L, the inverse -- stays.  No
+// solve is in flight: every entry point of the handle synchronises before it returns.
+static agp_status cg_set_block(agp_gp_cg* h, int block) {
+  if (block == h->block) return AGP_OK;
+  agp_ctx* ctx = h->ctx;
+  const int64_t np = h->np, npan = block / CG_LD, cw = std::max<int64_t>(TILE, block);
+  double* nb[11] = {};  // ws, Xv, Rv, Zv, Pv, Qv, part, Rt, Ct, Wt, Zl
+  CgScal* nsc = nullptr;
+  auto alloc = [&]() -> agp_status {
+    if (h->groups > 1) AGPCHK(dmalloc(ctx, &nb[0], (int64_t)h->groups * h->n * block));
+    for (int q = 1; q <= 5; ++q) AGPCHK(dmalloc(ctx, &nb[q], np * block));
+    AGPCHK(dmalloc(ctx, &nb[6], 3 * npan * h->nblk * CG_LD));
+    AGPCHK(dmalloc(ctx, &nsc, 2 * npan));
+    if (h->k > 0) {
+      AGPCHK(dmalloc(ctx, &nb[7], cw * np));
+      AGPCHK(dmalloc(ctx, &nb[8], cw * h->kp));
+      AGPCHK(dmalloc(ctx, &nb[9], cw * h->kp));
+      AGPCHK(dmalloc(ctx, &nb[10], np * cw));
+      AGPCHK(cg_zero(ctx, nb[7], cw * np));  // (Rt: its columns n .. np are never written and enter the first product)
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return AGP_OK;
+  };
+  const agp_status s = alloc();
+  double** cur[11] = {&h->ws, &h->Xv, &h->Rv, &h->Zv, &h->Pv, &h->Qv, &h->part, &h->Rt, &h->Ct, &h->Wt, &h->Zl};
+  if (s != AGP_OK) {  // nothing of the handle was touched
+    for (double* q : nb) (void)hipFree(q);
+    (void)hipFree(nsc);
+    return s;
+  }
+  for (int q = 0; q < 11; ++q) {
+    (void)hipFree(*cur[q]);
+    *cur[q] = nb[q];
+  }
+  (void)hipFree(h->sc);
+  h->sc = nsc;
+  h->block = block, h->cw = cw;
+  return AGP_OK;
+}
+
 // Which instance of the operator the solves run on.  Float32: the centred Float32 rows of X are prepared from the handle's Float64
 // copy (once; kept), and the CG calls k_kmv32 with Float64 V and Out.  Everything else of the handle stays Float64.
 static agp_status cg_set_operator(agp_gp_cg* h, int f32) {
@@ -380,87 +465,95 @@ static agp_status cg_apply(agp_gp_cg* h, const double* v, int64_t ldv, int r, do
   return kmv_apply(h->ctx, h->op, h->X, h->D, h->n, 1, h->sigma2, v, ldv, r, h->groups, h->ws, out, ldo);
 }
 
-// z = P^-1 r and the partials of r . z
-static agp_status cg_precond(agp_gp_cg* h, double* part_rz) {
+// z = P^-1 r and the partials of r . z, for the first r columns: the three products take 64 columns, or 128 when r > 64 (the GEMM
+// launchers work in tiles of 64).  Rows r .. w of Rt may hold residuals of an earlier, wider solve: their products are computed and
+// never read (a column of Zl depends on its own row of Rt only) -- up to 63 columns of wasted work, no wrong value.
+static agp_status cg_precond(agp_gp_cg* h, int r, double* part_rz) {
   agp_ctx* ctx = h->ctx;
-  const int64_t np = h->np, kp = h->kp;
-  AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->Rt, np, h->Lt, np, TILE, kp, np, 0, h->Ct, kp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-  AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->Ct, kp, h->Minv, kp, TILE, kp, kp, 0, h->Wt, kp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-  AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->L, kp, h->Wt, kp, np, TILE, kp, 0, h->Zl, TILE, nullptr, 0, nullptr, nullptr, nullptr, 0)));
-  hipLaunchKernelGGL(k_cg_precond, dim3((unsigned)h->nblk), dim3(256), 0, ctx->stream, h->n, (const double*)h->Rv,
-                     (const double*)h->Zl, (int64_t)TILE, 1.0 / h->sigma2, h->Zv, part_rz);
+  const int64_t np = h->np, kp = h->kp, w = r <= TILE ? TILE : h->cw;
+  AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->Rt, np, h->Lt, np, w, kp, np, 0, h->Ct, kp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+  AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->Ct, kp, h->Minv, kp, w, kp, kp, 0, h->Wt, kp, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+  AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->L, kp, h->Wt, kp, np, w, kp, 0, h->Zl, h->cw, nullptr, 0, nullptr, nullptr, nullptr, 0)));
+  hipLaunchKernelGGL(k_cg_precond, dim3((unsigned)h->nblk, (unsigned)((r + CG_LD - 1) / CG_LD)), dim3(256), 0, ctx->stream, h->n,
+                     (const double*)h->Rv, (const double*)h->Zl, h->cw, 1.0 / h->sigma2, h->Zv, part_rz, (int64_t)h->block);
   LAUNCHCHK(ctx);
   return AGP_OK;
 }
 
-// What cg_solve_slq asks of cg_solve on top of the solve.  coef: the device table [max_iter][2][32] of (alpha_j, beta_j) per column;
+// What cg_solve_slq asks of cg_solve on top of the solve.  coef: the device table [max_iter][2][block] of (alpha_j, beta_j) per column;
 // z0 (n x r, ldz0): the copy of P^-1 b; bpb[c] = b_c' P^-1 b_c (host).  Without a preconditioner P counts as sigma2 I.
 struct CgSlq {
   double* coef = nullptr;
   double* z0 = nullptr;
   int64_t ldz0 = 0;
-  double bpb[CG_LD];
+  double bpb[KMV_WIDE_MAXR];
 };
 
 static agp_status cg_solve(agp_gp_cg* h, const double* b, int64_t ldb, int r, double tol, int64_t max_iter, int64_t check_every,
                            double* a, int64_t lda, int32_t* iters_host, double* relres_host, int32_t* conv_host,
                            CgSlq* slq = nullptr) {
   agp_ctx* ctx = h->ctx;
-  const int64_t n = h->n, nblk = h->nblk;
-  const dim3 g((unsigned)nblk), t(256);
-  double *part_pq = h->part, *part_rr = h->part + nblk * CG_LD, *part_rz = part_rr + nblk * CG_LD;
+  const int64_t n = h->n, nblk = h->nblk, ld = h->block;
+  const int npan = (r + CG_LD - 1) / CG_LD;  // panels of 32 columns in use (the y index of the vector kernels' grids)
+  const dim3 g((unsigned)nblk, (unsigned)npan), t(256);
+  const int64_t pstride = (int64_t)(h->block / CG_LD) * nblk * CG_LD;
+  double *part_pq = h->part, *part_rr = h->part + pstride, *part_rz = part_rr + pstride;
   const bool pre = h->k > 0;
   const double* Z = pre ? h->Zv : nullptr;
   double* const coef = slq ? slq->coef : nullptr;
-  AGPCHK(cg_zero(ctx, h->Pv, h->np * CG_LD));
+  AGPCHK(cg_zero(ctx, h->Pv, h->np * ld));
+  // scalars of panel q: sc[2 q + parity]; the kernels add 2 q themselves
   hipLaunchKernelGGL(k_cg_update, g, t, 0, ctx->stream, 1, b, ldb, r, n, nblk, (const CgScal*)h->sc, (const double*)part_pq,
                      (const double*)h->Pv, (const double*)h->Qv, h->Xv, h->Rv, pre ? h->Rt : nullptr, h->np, part_rr,
-                     (double*)nullptr);
-  if (pre) AGPCHK(cg_precond(h, part_rz));
+                     (double*)nullptr, ld);
+  if (pre) AGPCHK(cg_precond(h, r, part_rz));
   hipLaunchKernelGGL(k_cg_direction, g, t, 0, ctx->stream, 1, n, nblk, tol * tol, (const CgScal*)(h->sc + 1), h->sc,
                      (const double*)part_pq, (const double*)part_rr, (const double*)part_rz, (const double*)h->Rv, Z, h->Pv,
-                     (double*)nullptr);
+                     (double*)nullptr, ld);
   LAUNCHCHK(ctx);
   int cur = 0;
-  CgScal hs;
+  std::vector<CgScal> hsv(2 * npan);
   auto read = [&]() -> agp_status {
-    HIPCHK(ctx, hipMemcpyAsync(&hs, h->sc + cur, sizeof(CgScal), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(hsv.data(), h->sc, sizeof(CgScal) * 2 * npan, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return AGP_OK;
   };
+  auto hs = [&](int c) -> const CgScal& { return hsv[2 * (c / CG_LD) + cur]; };  // column c's scalars, at index c % 32
   if (slq) {  // z0 = P^-1 b before the first iteration overwrites it, and b' P^-1 b = the first r . z
-    hipLaunchKernelGGL(k_cg_export_scaled, grid1(n * CG_LD), t, 0, ctx->stream, (const double*)(pre ? h->Zv : h->Rv), n, r,
-                       pre ? 1.0 : 1.0 / h->sigma2, slq->z0, slq->ldz0);
+    hipLaunchKernelGGL(k_cg_export_scaled, grid1(n * ld), t, 0, ctx->stream, (const double*)(pre ? h->Zv : h->Rv), n, r,
+                       pre ? 1.0 : 1.0 / h->sigma2, slq->z0, slq->ldz0, ld);
     LAUNCHCHK(ctx);
     AGPCHK(read());
-    for (int c = 0; c < r; ++c) slq->bpb[c] = pre ? hs.rz[c] : hs.rz[c] / h->sigma2;
+    for (int c = 0; c < r; ++c) slq->bpb[c] = pre ? hs(c).rz[c % CG_LD] : hs(c).rz[c % CG_LD] / h->sigma2;
   }
   for (int64_t it = 0; it < max_iter; ++it) {
     if (it % check_every == 0) {
       AGPCHK(read());
       bool any = false;
-      for (int c = 0; c < r; ++c) any = any || hs.active[c];
+      for (int c = 0; c < r; ++c) any = any || hs(c).active[c % CG_LD];
       if (!any) break;
     }
-    AGPCHK(cg_apply(h, h->Pv, CG_LD, r, h->Qv, CG_LD));
-    hipLaunchKernelGGL(k_cg_dot, g, t, 0, ctx->stream, (const double*)h->Pv, (const double*)h->Qv, n, part_pq);
+    AGPCHK(cg_apply(h, h->Pv, ld, r, h->Qv, ld));
+    hipLaunchKernelGGL(k_cg_dot, g, t, 0, ctx->stream, (const double*)h->Pv, (const double*)h->Qv, n, ld, part_pq);
     hipLaunchKernelGGL(k_cg_update, g, t, 0, ctx->stream, 0, b, ldb, r, n, nblk, (const CgScal*)(h->sc + cur), (const double*)part_pq,
                        (const double*)h->Pv, (const double*)h->Qv, h->Xv, h->Rv, pre ? h->Rt : nullptr, h->np, part_rr,
-                       coef ? coef + it * 2 * CG_LD : nullptr);
-    if (pre) AGPCHK(cg_precond(h, part_rz));
+                       coef ? coef + it * 2 * ld : nullptr, ld);
+    if (pre) AGPCHK(cg_precond(h, r, part_rz));
     hipLaunchKernelGGL(k_cg_direction, g, t, 0, ctx->stream, 0, n, nblk, tol * tol, (const CgScal*)(h->sc + cur), h->sc + (cur ^ 1),
                        (const double*)part_pq, (const double*)part_rr, (const double*)part_rz, (const double*)h->Rv, Z, h->Pv,
-                       coef ? coef + it * 2 * CG_LD : nullptr);
+                       coef ? coef + it * 2 * ld : nullptr, ld);
     LAUNCHCHK(ctx);
     cur ^= 1;
   }
-  hipLaunchKernelGGL(k_cg_export, grid1(n * CG_LD), t, 0, ctx->stream, (const double*)h->Xv, n, r, a, lda);
+  hipLaunchKernelGGL(k_cg_export, grid1(n * ld), t, 0, ctx->stream, (const double*)h->Xv, n, r, a, lda, ld);
   LAUNCHCHK(ctx);
   AGPCHK(read());
   for (int c = 0; c < r; ++c) {
-    if (iters_host) iters_host[c] = hs.iters[c];
-    if (relres_host) relres_host[c] = hs.bb[c] > 0.0 ? std::sqrt(hs.rr[c] / hs.bb[c]) : 0.0;
-    if (conv_host) conv_host[c] = hs.conv[c];
+    const CgScal& q = hs(c);
+    const int lc = c % CG_LD;
+    if (iters_host) iters_host[c] = q.iters[lc];
+    if (relres_host) relres_host[c] = q.bb[lc] > 0.0 ? std::sqrt(q.rr[lc] / q.bb[lc]) : 0.0;
+    if (conv_host) conv_host[c] = q.conv[lc];
   }
   return AGP_OK;
 }
@@ -694,14 +787,15 @@ static agp_status cg_solve_slq(agp_gp_cg* h, const double* b, int64_t ldb, int r
   agp_ctx* ctx = h->ctx;
   CgSlq slq;
   slq.z0 = z0, slq.ldz0 = ldz0;
-  AGPCHK(dmalloc(ctx, &slq.coef, std::max<int64_t>(1, max_iter) * 2 * CG_LD));
-  int32_t its[CG_LD];
+  const int64_t ld = h->block;
+  AGPCHK(dmalloc(ctx, &slq.coef, std::max<int64_t>(1, max_iter) * 2 * ld));
+  int32_t its[KMV_WIDE_MAXR];
   agp_status s = cg_solve(h, b, ldb, r, tol, max_iter, check_every, a, lda, its, relres_host, conv_host, &slq);
   int64_t mmax = 0;
   for (int c = 0; c < r; ++c) mmax = std::max<int64_t>(mmax, its[c]);
-  std::vector<double> co(std::max<int64_t>(1, mmax) * 2 * CG_LD);
+  std::vector<double> co(std::max<int64_t>(1, mmax) * 2 * ld);
   if (s == AGP_OK && mmax > 0 &&
-      hipMemcpy(co.data(), slq.coef, sizeof(double) * mmax * 2 * CG_LD, hipMemcpyDeviceToHost) != hipSuccess)
+      hipMemcpy(co.data(), slq.coef, sizeof(double) * mmax * 2 * ld, hipMemcpyDeviceToHost) != hipSuccess)
     s = AGP_ERR_HIP;
   (void)hipFree(slq.coef);
   if (s != AGP_OK) return s;
@@ -714,10 +808,10 @@ static agp_status cg_solve_slq(agp_gp_cg* h, const double* b, int64_t ldb, int r
     if (m == 0) continue;
     std::vector<double> d(m), e(m > 1 ? m - 1 : 0);
     for (int j = 0; j < m; ++j) {
-      const double al = co[(j * 2) * CG_LD + c];
+      const double al = co[(j * 2) * ld + c];
       d[j] = 1.0 / al;
       if (j > 0) {
-        const double alp = co[((j - 1) * 2) * CG_LD + c], bep = co[((j - 1) * 2 + 1) * CG_LD + c];
+        const double alp = co[((j - 1) * 2) * ld + c], bep = co[((j - 1) * 2 + 1) * ld + c];
         d[j] += bep / alp;
         e[j - 1] = std::sqrt(bep) / alp;
       }
@@ -755,11 +849,11 @@ static agp_status cg_probes(agp_gp_cg* h, int64_t t, const double* base, int64_t
       if (h->k > 0) {  // Zl = L eps1': eps1 padded into Ct (64 x kp), one GEMM
         hipLaunchKernelGGL((k_copy2d_zero<double>), grid2(TILE, h->kp), blk2, 0, ctx->stream, Eb + n, ldbase, (int64_t)r, h->k, h->Ct,
                            h->kp, (int64_t)TILE, h->kp);
-        AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->L, h->kp, h->Ct, h->kp, h->np, TILE, h->kp, 0, h->Zl, TILE, nullptr, 0, nullptr,
+        AGPCHK((gemm_nt<double, EPI_STORE>(ctx, h->L, h->kp, h->Ct, h->kp, h->np, TILE, h->kp, 0, h->Zl, h->cw, nullptr, 0, nullptr,
                                            nullptr, nullptr, 0)));
       }
       hipLaunchKernelGGL(k_cg_probe, grid1(n * CG_LD), dim3(256), 0, ctx->stream, n, r, (const double*)(h->k > 0 ? h->Zl : nullptr),
-                         (int64_t)TILE, std::sqrt(h->sigma2), Eb, ldbase, out + c0, ldo);
+                         h->cw, std::sqrt(h->sigma2), Eb, ldbase, out + c0, ldo);
       LAUNCHCHK(ctx);
     }
     return AGP_OK;

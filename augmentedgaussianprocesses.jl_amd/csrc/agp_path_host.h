@@ -143,7 +143,7 @@ static agp_status path_draw(agp_gp_cg* h, const double* b, int64_t L, int64_t S,
   hipLaunchKernelGGL(agp::k_pw_table, grid1(n * S), dim3(256), 0, ctx->stream, n, S, n, S, S, (int64_t)1, 1, seed, (uint32_t)t,
                      (uint32_t)(4 + agp::PW_STREAM_E), p->E);
   LAUNCHCHK(ctx);
-  // R = b - Phi(X) W - sigma E, in place in a buffer of its own; then the solves, 32 columns at a time
+  // R = b - Phi(X) W - sigma E, in place in a buffer of its own; then the solves, one block of the handle's columns at a time
   double* Rm = nullptr;
   AGPCHK(dmalloc(ctx, &Rm, n * S));
   auto run = [&]() -> agp_status {
@@ -152,8 +152,8 @@ static agp_status path_draw(agp_gp_cg* h, const double* b, int64_t L, int64_t S,
     hipLaunchKernelGGL(agp::k_path_resid, grid1(n * S), dim3(256), 0, ctx->stream, n, S, b, std::sqrt(h->sigma2), (const double*)p->E,
                        Rm);
     LAUNCHCHK(ctx);
-    for (int64_t c0 = 0; c0 < S; c0 += KMV_MAXR)
-      AGPCHK(cg_solve(h, Rm + c0, S, (int)std::min<int64_t>(KMV_MAXR, S - c0), tol, max_iter, check_every, p->V + c0, S,
+    for (int64_t c0 = 0; c0 < S; c0 += h->block)  // (the handle's block: 32, or 128 after agp_gp_cg_set_block)
+      AGPCHK(cg_solve(h, Rm + c0, S, (int)std::min<int64_t>(h->block, S - c0), tol, max_iter, check_every, p->V + c0, S,
                       iters_host ? iters_host + c0 : nullptr, relres_host ? relres_host + c0 : nullptr,
                       conv_host ? conv_host + c0 : nullptr));
     return AGP_OK;

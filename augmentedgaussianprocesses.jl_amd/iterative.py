@@ -3,7 +3,7 @@ V with K never in memory (agp_kernel_matmul, csrc/agp_kmv.h), and `kernel_biline
 kernel's variance and scales with neither K nor the weight matrix in memory (agp_kernel_bilinear_grad, csrc/agp_kmv_grad.h), under a
 batched preconditioned CG (agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 64, one GPU, Gaussian likelihood;
 the operator product alone also has a Float32 instance (csrc/agp_kmv_f32.h: `kernel_matmul(dtype=np.float32)`,
-`IterativeGP(operator_dtype=np.float32)`).
+`IterativeGP(operator_dtype=np.float32)`).  `block=128` on either takes 128 columns per launch / per CG run (csrc/agp_kmv_wide.h).
 
 The log marginal likelihood is stochastic: log det(K + noise I) = log det P + E_z[z' P^-1/2 log(P^-1/2 (K + noise I) P^-1/2) P^-1/2 z]
 over probes z ~ N(0, P), P the solver's preconditioner, each expectation term by Lanczos quadrature on the coefficients the CG
@@ -27,6 +27,13 @@ from .likelihoods import GaussianLikelihood
 from .svgp import ADAM, ELBO, predict_f, predict_y, train_
 
 MAXR = 32  # right-hand sides per launch / per batched solve (KMV_MAXR)
+WIDE = 128  # ... of the wide block (KMV_WIDE_MAXR): kernel_matmul(block=128), IterativeGP(block=128)
+
+
+def _block(block, who):
+    if isinstance(block, bool) or block not in (MAXR, WIDE):
+        raise ValueError(f"{who}: block must be 32 or 128, got {block!r}")
+    return int(block)
 
 
 def _torch():
@@ -89,7 +96,7 @@ def _rows(t):
     return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
 
 
-def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups, dtype=np.float64):
+def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups, dtype=np.float64, block=MAXR):
     torch = _torch()
     L = capi.lib()
     sym = Yd is None
@@ -101,32 +108,37 @@ def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups, dtype=np.float6
         raise ValueError(f"V has {Vd.shape[0]} rows, K(X, Y) has {p} columns")
     kd, keep = kernel.desc(D)
     out = torch.empty(n, Vd.shape[1], dtype=_torch_dtype(dtype), device=cx.dev)
-    for c0 in range(0, Vd.shape[1], MAXR):
-        v, o = Vd[:, c0:c0 + MAXR], out[:, c0:c0 + MAXR]
-        cx.chk(L.agp_kernel_matmul(cx.ctx, capi.F32 if dtype is np.float32 else capi.F64, C.byref(kd), C.c_void_p(Xd.data_ptr()), n, Xd.stride(0),
-                                   None if sym else C.c_void_p(Yd.data_ptr()), p, 0 if sym else Yd.stride(0), D, 1 if sym else 0,
-                                   float(diag_add), C.c_void_p(v.data_ptr()), Vd.stride(0), v.shape[1], int(col_groups),
-                                   C.c_void_p(o.data_ptr()), out.stride(0)))
+    call = L.agp_kernel_matmul_wide if block == WIDE else L.agp_kernel_matmul
+    for c0 in range(0, Vd.shape[1], block):
+        v, o = Vd[:, c0:c0 + block], out[:, c0:c0 + block]
+        cx.chk(call(cx.ctx, capi.F32 if dtype is np.float32 else capi.F64, C.byref(kd), C.c_void_p(Xd.data_ptr()), n, Xd.stride(0),
+                    None if sym else C.c_void_p(Yd.data_ptr()), p, 0 if sym else Yd.stride(0), D, 1 if sym else 0,
+                    float(diag_add), C.c_void_p(v.data_ptr()), Vd.stride(0), v.shape[1], int(col_groups),
+                    C.c_void_p(o.data_ptr()), out.stride(0)))
     del keep
     return out
 
 
-def kernel_matmul(kernel, X, V, Y=None, diag_add: float = 0.0, col_groups: int = 0, device: Optional[int] = None, dtype=np.float64):
+def kernel_matmul(kernel, X, V, Y=None, diag_add: float = 0.0, col_groups: int = 0, device: Optional[int] = None, dtype=np.float64,
+                  block: int = 32):
     """(K(X, Y) + diag_add I) V on the device without forming K.  X: n x D, Y: p x D, V: p x r (a vector counts as p x 1); Y=None is
-    the symmetric form K(X, X) + diag_add I, with an exact diagonal.  diag_add needs Y=None.  More than 32 columns are taken in
-    blocks of 32.  col_groups: 0 lets the library split the columns of K over workgroups; a positive value forces that many groups.
+    the symmetric form K(X, X) + diag_add I, with an exact diagonal.  diag_add needs Y=None.  More than `block` columns are taken in
+    blocks of `block` (32, or 128: see below).  col_groups: 0 lets the library split the columns of K over workgroups; a positive value forces that many groups.
     Arrays in, a NumPy array out; device tensors in, a device tensor out.  dtype: np.float64 (default) or np.float32 -- the inputs
     are converted to that type and the output has it.  np.float32 runs the Float32 kernel (both products on the Float32 matrix
-    instruction, the sum over the columns of K in Float64 across windows of 128): kernel values to about 1e-6 of the variance."""
+    instruction, the sum over the columns of K in Float64 across windows of 128): kernel values to about 1e-6 of the variance.
+    block=128 takes the columns of V 128 at a time through the wide kernel (agp_kernel_matmul_wide, csrc/agp_kmv_wide.h): every
+    kernel tile is computed once for 128 columns, not once per 32, and each column equals block=32's bit for bit.  Float64 only."""
     if Y is not None and diag_add != 0.0:
         raise ValueError("diag_add is added to the diagonal of K(X, X): it needs Y=None")
     dtype = _np_dtype(dtype, "dtype")
+    block = _block(block, "kernel_matmul")
     torch = _torch()
     cx = _Ctx(device)
     try:
         vec = np.ndim(V) == 1
         out = _kernel_matmul(cx, kernel, cx.dev_tensor(X, dtype), cx.dev_tensor(V, dtype),
-                             None if Y is None else cx.dev_tensor(Y, dtype), diag_add, col_groups, dtype)
+                             None if Y is None else cx.dev_tensor(Y, dtype), diag_add, col_groups, dtype, block)
     finally:
         cx.close()
     if vec:
@@ -244,7 +256,10 @@ class IterativeGP:
     precond_rank and max_iter are interface defaults, not tuned.  mean: None, a constant, or one value per training point.
 
     predict_f(model, Xt, cov=True) -> (mean, variance): the mean is one operator product; the variance costs ONE BATCHED CG RUN PER 32
-    TEST POINTS (k** - k*' (K + noise I)^-1 k*), so ask for it on as many points as are needed and no more.  predict_y adds the
+    TEST POINTS (k** - k*' (K + noise I)^-1 k*), so ask for it on as many points as are needed and no more.  block=128: solve,
+    operator, the variance loops of predict_f / predict_y / predict_f_grad, log_marginal_likelihood, optimize and the solve of
+    sample_paths take 128 columns per CG run on the wide operator kernel (csrc/agp_kmv_wide.h), which computes every kernel tile
+    once for all of them; each column's CG recurrence is unchanged, and the Float32 operator is refused with it.  predict_y adds the
     noise.  model.solve(B) exposes the solver, model.info what the last solve did.  log_marginal_likelihood (also ELBO(model)) and
     optimize learn the kernel and the noise; there is no train_.
 
@@ -257,7 +272,8 @@ class IterativeGP:
     must be exact, stays np.float64.  No iterative refinement is built."""
 
     def __init__(self, X, y, kernel, *, noise: float = 1e-5, mean=None, tol: float = 1e-8, max_iter: int = 1000,
-                 precond_rank: int = 64, check_every: int = 10, device: Optional[int] = None, operator_dtype=np.float64):
+                 precond_rank: int = 64, check_every: int = 10, device: Optional[int] = None, operator_dtype=np.float64,
+                 block: int = 32):
         X = np.asarray(X, dtype=np.float64)
         X = np.ascontiguousarray(X[:, None] if X.ndim == 1 else X)
         y = np.asarray(y, dtype=np.float64).reshape(-1)
@@ -271,6 +287,9 @@ class IterativeGP:
         self.tol, self.max_iter, self.precond_rank, self.check_every = float(tol), int(max_iter), int(precond_rank), int(check_every)
         self.N, self.D = X.shape
         self.operator_dtype = _np_dtype(operator_dtype, "operator_dtype")
+        self.block = _block(block, "IterativeGP")
+        if self.block == WIDE and self.operator_dtype is np.float32:
+            raise ValueError("IterativeGP: block=128 needs operator_dtype=np.float64 (no Float32 wide block is built)")
         self.device = device
         self.info = None
         self.rank_used = None
@@ -303,6 +322,12 @@ class IterativeGP:
             self._h, self.rank_used = h, int(used.value)
             if self.operator_dtype is np.float32:
                 self._cx.chk(capi.lib().agp_gp_cg_set_operator_dtype(h, capi.F32))
+            if self.block != MAXR:
+                try:
+                    self._cx.chk(capi.lib().agp_gp_cg_set_block(h, self.block))
+                except Exception:
+                    self.close()  # the handle is still valid at 32 columns, but not the one this model asked for: the next use builds anew
+                    raise
         return self._h
 
     def _solve_dev(self, Bd, tol, max_iter):
@@ -312,8 +337,8 @@ class IterativeGP:
         Bd = _rows(Bd)
         A = torch.empty(Bd.shape, dtype=torch.float64, device=self._cx.dev)
         its, res, conv = [], [], []
-        for c0 in range(0, Bd.shape[1], MAXR):
-            b, a = Bd[:, c0:c0 + MAXR], A[:, c0:c0 + MAXR]
+        for c0 in range(0, Bd.shape[1], self.block):
+            b, a = Bd[:, c0:c0 + self.block], A[:, c0:c0 + self.block]
             r = b.shape[1]
             it, rr, cv = (C.c_int32 * r)(), (C.c_double * r)(), (C.c_int32 * r)()
             self._cx.chk(capi.lib().agp_gp_cg_solve(h, C.c_void_p(b.data_ptr()), Bd.stride(0), r, tol, max_iter, self.check_every,
@@ -346,8 +371,8 @@ class IterativeGP:
         if Vd.shape[0] != self.N:
             raise ValueError(f"V has {Vd.shape[0]} rows, the model {self.N} points")
         out = torch.empty(Vd.shape, dtype=torch.float64, device=self._cx.dev)
-        for c0 in range(0, Vd.shape[1], MAXR):
-            v, o = Vd[:, c0:c0 + MAXR], out[:, c0:c0 + MAXR]
+        for c0 in range(0, Vd.shape[1], self.block):
+            v, o = Vd[:, c0:c0 + self.block], out[:, c0:c0 + self.block]
             self._cx.chk(capi.lib().agp_gp_cg_apply(h, C.c_void_p(v.data_ptr()), Vd.stride(0), v.shape[1], C.c_void_p(o.data_ptr()),
                                                     out.stride(0)))
         out = out[:, 0] if vec else out
@@ -392,8 +417,8 @@ class IterativeGP:
                                   int(seed), int(_t0), C.c_void_p(Z.data_ptr()), B.stride(0)))
         A, Z0 = torch.empty_like(B), torch.empty_like(B)
         its, res, conv, bpb, quad = [], [], [], [], []
-        for c0 in range(0, 1 + t, MAXR):
-            b, a, z0 = B[:, c0:c0 + MAXR], A[:, c0:c0 + MAXR], Z0[:, c0:c0 + MAXR]
+        for c0 in range(0, 1 + t, self.block):
+            b, a, z0 = B[:, c0:c0 + self.block], A[:, c0:c0 + self.block], Z0[:, c0:c0 + self.block]
             r = b.shape[1]
             it, rr, cv, pb, qd = (C.c_int32 * r)(), (C.c_double * r)(), (C.c_int32 * r)(), (C.c_double * r)(), (C.c_double * r)()
             cx.chk(L.agp_gp_cg_solve_slq(h, C.c_void_p(b.data_ptr()), B.stride(0), r, self.tol, self.max_iter, self.check_every,
@@ -487,14 +512,14 @@ def _predict_f_iterative(model: IterativeGP, X_test, state=None, *, cov: bool = 
         return mean
     nt, variance = Xt.shape[0], model.kernel.desc(model.D)[0].variance
     var = torch.empty(nt, dtype=torch.float64, device=cx.dev)
-    for c0 in range(0, nt, MAXR):
-        ks, sol = _kstar_solve(model, Xt[c0:c0 + MAXR])
-        var[c0:c0 + MAXR] = variance - (ks * sol).sum(dim=0)
+    for c0 in range(0, nt, model.block):
+        ks, sol = _kstar_solve(model, Xt[c0:c0 + model.block])
+        var[c0:c0 + model.block] = variance - (ks * sol).sum(dim=0)
     return mean, var.cpu().numpy()
 
 
 def _kstar_solve(model, xt):
-    """(K(X, xt), (K + noise I)^-1 K(X, xt)) for a chunk of at most 32 test points (rows of a device tensor): one batched CG"""
+    """(K(X, xt), (K + noise I)^-1 K(X, xt)) for a chunk of at most model.block test points (rows of a device tensor): one batched CG"""
     cx = model._cx
     kd, keep = model.kernel.desc(model.D)
     ks = _torch().empty(model.N, xt.shape[0], dtype=_torch().float64, device=cx.dev)
@@ -538,9 +563,9 @@ def predict_f_grad_iterative(model: IterativeGP, X_test, *, cov: bool = True, ob
     if not cov:
         return dmu
     dvar = _torch().empty(Xt.shape[0], D, dtype=_torch().float64, device=cx.dev)
-    for c0 in range(0, Xt.shape[0], MAXR):
-        xt = Xt[c0:c0 + MAXR]
-        dvar[c0:c0 + MAXR] = -2.0 * _matmul_dx_blocks(call, xt, _kstar_solve(model, xt)[1], D, True)
+    for c0 in range(0, Xt.shape[0], model.block):  # (one solve per block of the model; the derivative operator still 32 at a time)
+        xt = Xt[c0:c0 + model.block]
+        dvar[c0:c0 + model.block] = -2.0 * _matmul_dx_blocks(call, xt, _kstar_solve(model, xt)[1], D, True)
     return dmu, dvar.cpu().numpy()
 
 

@@ -394,6 +394,15 @@ agp_status agp_greedy_variance(agp_ctx* ctx, int32_t dtype, const agp_kernel_des
 agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
                              const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
                              int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo);
+/* agp_kernel_matmul_wide: agp_kernel_matmul with AGP_F64 for 1 <= r <= 128 in ONE launch (csrc/agp_kmv_wide.h: k_kmv_wide).  Same
+ * arguments, layout, error budget (R = r padded to 16), determinism and refusals, with r > 128 in the place of r > 32.  The
+ * finished kernel tile is computed once per (row tile, column tile) and meets all r columns of v from registers; instances of 48,
+ * 64, 96 and 128 columns, the narrowest that holds r.  r <= 32 runs agp_kernel_matmul's kernel.  The second product keeps that
+ * kernel's k-step order, so for equal col_groups every column equals agp_kernel_matmul's on the same column bit for bit.
+ * AGP_F32 is refused by name with AGP_ERR_UNSUPPORTED (no Float32 wide block is built), before anything is touched. */
+agp_status agp_kernel_matmul_wide(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                  const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
+                                  int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo);
 /* agp_gp_cg: solves (K(x, x) + sigma2 I) A = B for B n x r, r <= 32, by r INDEPENDENT conjugate-gradient recurrences that share
  * every operator product (not block CG): each column has its own alpha, beta and residual, on the device; column dots are
  * two-stage sums of fixed order.  A column whose recursive residual reaches |r| <= tol |b| is frozen -- its update is skipped --
@@ -414,8 +423,17 @@ agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc*
  * different, FIXED linear map: CG solves that system, and its recursive residual stops tracking b - (K + sigma2 I) a at about the
  * operator's own error; a tol below that ends in converged_host[c] = 0, not in an error.  Another dtype: AGP_ERR_INVALID.
  * apply: out (n x r, ldo >= r) = (K(x, x) + sigma2 I) v (n x r, ldv >= r), Float64 device arrays, 1 <= r <= 32, on the instance of
- * the operator the solves run on -- what a caller needs to form the residual of the system CG actually solved.  Synchronises. */
+ * the operator the solves run on -- what a caller needs to form the residual of the system CG actually solved.  Synchronises.
+ * set_block: how many columns one call of solve, solve_slq and apply takes: 32 (what create leaves) or 128.  It sizes the handle's
+ * CG vectors, per-column scalar tables, partial sums, column-group slices and preconditioner buffers for that many columns; after
+ * block = 128 those three calls accept 1 <= r <= 128, every operator product of more than 32 columns is one launch of
+ * agp_kernel_matmul_wide's kernel, and agp_gp_cg_pathwise_draw solves 128 samples per CG run.  Each column's recurrence is the one
+ * described above, unchanged: the vector kernels run per panel of 32 columns.  A handle that is never switched behaves bit for bit
+ * as before.  Another value: AGP_ERR_INVALID.  128 on a handle set to AGP_F32, and AGP_F32 on a handle set to 128:
+ * AGP_ERR_UNSUPPORTED, by name (no Float32 wide block is built).  The new workspaces are allocated before the old ones are released: if
+ * an allocation fails the error is returned and the handle stays as it was, usable at its old block.  Synchronises. */
 typedef struct agp_gp_cg agp_gp_cg;
+agp_status agp_gp_cg_set_block(agp_gp_cg* h, int64_t block);
 agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D,
                             double sigma2, int64_t precond_rank, agp_gp_cg** out, int64_t* rank_used_host);
 agp_status agp_gp_cg_solve(agp_gp_cg* h, const void* b, int64_t ldb, int64_t r, double tol, int64_t max_iter, int64_t check_every,

@@ -16,6 +16,9 @@ ratios of the best times; --lml then times the log marginal likelihood on each o
 and p = --big column points, per r, beside agp_kernel_matmul's cross product on the same shapes, with the ratio of the best times and
 the ratio of the MFMA counts (1 + CB) DP ceil(r / CB) / (DP + R); --predgrad N: one predict_f_grad(cov=True) of an IterativeGP on 32
 test points at N training points, split into the batched solve and the gradient kernel's two launches (0 skips either).
+--wide: the block of 128 columns (agp_kernel_matmul_wide, csrc/agp_kmv_wide.h; IterativeGP(block=128)) against the block of 32 on the
+same build and nothing else: one product at n = p = --n with r = 128 (one wide launch against four launches of 32), one CG iteration at
+N = --big at both blocks, and predict_f's variance for 128 test points at N = --big at both blocks (see wide_block).
 --paths NT: one evaluation of 32 pathwise draws of an IterativeGP (agp_gp_cg_pathwise_eval, csrc/agp_path.h) at NT points against
 N = --n training points and --features random features, (a) `fused`; (b) `composed`, the same result from what there was before:
 agp_pathwise_eval of a 64-point GP's draw with the same number of features (k_pw_features into memory, 64 columns of kernel matrix,
@@ -50,6 +53,100 @@ def timed(fn, reps):
     return dict(best_ms=round(ms[0], 3), median_ms=round(ms[len(ms) // 2], 3))
 
 
+def wide_block(a, AGP, capi, L, ctx, kd, gen):
+    """--wide: the block of 128 (csrc/agp_kmv_wide.h) against the block of 32 on the same build, the two alternating inside every
+    repetition.  (1) one product at n = p = --n, r = 128: one launch of agp_kernel_matmul_wide against four of agp_kernel_matmul,
+    and the two results compared bit for bit -- whole calls, each with its own preparation of Y, workspace and synchronise -- and the
+    same product by agp_gp_cg_apply on two prepared handles (`product_prepared`), which pays none of that; (2) one CG iteration at N = --big with the default preconditioner, r = block columns
+    that never converge (tol = 0): the difference of a solve of 5 and a solve of 1 iterations, over 4; (3) predict_f's variance for
+    128 test points at N = --big (alpha solved before the clock starts), host clock around a call that ends synchronised.  (1) is the
+    best and median of --reps alternating repetitions; (2) the smaller of two runs per length; (3) ONE run per block."""
+    import time
+
+    import numpy as np
+
+    res = dict(bench="kernel_matmul_wide", D=a.D)
+    n, r = a.n, 128
+    X = torch.rand(n, a.D, dtype=torch.float64, device="cuda", generator=gen)
+    V = torch.randn(n, r, dtype=torch.float64, device="cuda", generator=gen)
+    ow, o4 = torch.empty(n, r, dtype=torch.float64, device="cuda"), torch.empty(n, r, dtype=torch.float64, device="cuda")
+
+    def product(call, c0, w, out):
+        st = call(ctx, capi.F64, C.byref(kd), X.data_ptr(), n, a.D, None, n, 0, a.D, 1, 0.0, V.data_ptr() + 8 * c0, r, w, 0,
+                  out.data_ptr() + 8 * c0, r)
+        assert st == 0, L.agp_last_error(ctx)
+
+    def four():
+        for c0 in range(0, r, 32):
+            product(L.agp_kernel_matmul, c0, 32, o4)
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    wide = lambda: product(L.agp_kernel_matmul_wide, 0, r, ow)  # noqa: E731
+    tw, t4 = [], []
+    for rep in range(a.reps + 1):  # (repetition 0: the warm-up of both)
+        tw.append(once(wide))
+        t4.append(once(four))
+    tw, t4 = sorted(tw[1:]), sorted(t4[1:])
+    res["product"] = dict(n=n, r=r, wide_ms=dict(best=round(tw[0], 3), median=round(tw[len(tw) // 2], 3)),
+                          four_launches_ms=dict(best=round(t4[0], 3), median=round(t4[len(t4) // 2], 3)),
+                          wide_over_four=round(tw[0] / t4[0], 3),
+                          bitwise_equal=bool(torch.equal(ow.view(torch.int64), o4.view(torch.int64))))
+    # the same product on prepared operators (agp_gp_cg_apply, no preconditioner): no preparation of Y, no allocation per call
+    hs = {}
+    for b in (32, 128):
+        hs[b] = C.c_void_p()
+        assert L.agp_gp_cg_create(ctx, C.byref(kd), X.data_ptr(), n, a.D, a.D, 1e-2, 0, C.byref(hs[b]), None) == 0
+        assert L.agp_gp_cg_set_block(hs[b], b) == 0
+
+    def apply(b, out):
+        for c0 in range(0, r, b):
+            assert L.agp_gp_cg_apply(hs[b], V.data_ptr() + 8 * c0, r, b, out.data_ptr() + 8 * c0, r) == 0
+
+    tw, t4 = [], []
+    for rep in range(a.reps + 1):
+        tw.append(once(lambda: apply(128, ow)))
+        t4.append(once(lambda: apply(32, o4)))
+    tw, t4 = sorted(tw[1:]), sorted(t4[1:])
+    res["product_prepared"] = dict(n=n, r=r, wide_ms=dict(best=round(tw[0], 3), median=round(tw[len(tw) // 2], 3)),
+                                   four_launches_ms=dict(best=round(t4[0], 3), median=round(t4[len(t4) // 2], 3)),
+                                   wide_over_four=round(tw[0] / t4[0], 3),
+                                   bitwise_equal=bool(torch.equal(ow.view(torch.int64), o4.view(torch.int64))))
+    for h in hs.values():
+        L.agp_gp_cg_destroy(h)
+    del X, V, ow, o4
+    N = a.big
+    Xb = torch.rand(N, a.D, dtype=torch.float64, device="cuda", generator=gen).cpu().numpy()
+    y = np.sin(3 * Xb[:, 0])
+    Xt = np.random.default_rng(0).random((128, a.D))
+    its, var = {}, {}
+    models = {b: AGP.IterativeGP(Xb, y, AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale), noise=1e-2, tol=1e-6, block=b)
+              for b in (32, 128)}
+    for b, m in models.items():
+        m.alpha()
+        B = torch.randn(N, b, dtype=torch.float64, device="cuda", generator=gen)
+        m._solve_dev(B, 0.0, 1)  # warm-up
+        ts = {k: min(once(lambda: m._solve_dev(B, 0.0, k)) for _ in range(2)) for k in (1, 5)}
+        its[b] = dict(iteration_ms=round((ts[5] - ts[1]) / 4, 3), per_column_ms=round((ts[5] - ts[1]) / 4 / b, 4))
+    for b, m in models.items():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        v = AGP.predict_f(m, Xt)[1]
+        var[b] = dict(seconds=round(time.perf_counter() - t0, 3), iterations=int(m.info["iterations"].max()), values=v)
+    res["cg_iteration"] = dict(N=N, **{f"block{b}": its[b] for b in its})
+    res["predict_f_variance_128_points"] = dict(N=N, max_abs_diff=float(np.abs(var[32]["values"] - var[128]["values"]).max()),
+                                                **{f"block{b}": {k: var[b][k] for k in ("seconds", "iterations")} for b in var})
+    for m in models.values():
+        m.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -66,6 +163,7 @@ def main():
     ap.add_argument("--features", type=int, default=1024)
     ap.add_argument("--paths-draw", type=int, default=0)
     ap.add_argument("--dtype", nargs="+", choices=["f64", "f32"], default=["f64", "f32"])
+    ap.add_argument("--wide", action="store_true")
     a = ap.parse_args()
     g.build()
     import agp_amd as AGP
@@ -83,6 +181,10 @@ def main():
         st = L.agp_kernel_matmul(ctx, capi.F64, C.byref(kd), X.data_ptr(), n, a.D, None, n, 0, a.D, 1, 0.0, V.data_ptr(), r, r, 0,
                                  out.data_ptr(), r)
         assert st == 0, L.agp_last_error(ctx)
+
+    if a.wide:
+        print(json.dumps(wide_block(a, AGP, capi, L, ctx, kd, gen)))
+        return
 
     for n in [a.n] + ([a.big] if a.big else []):
         X = torch.rand(n, a.D, dtype=torch.float64, device="cuda", generator=gen)
