@@ -202,6 +202,7 @@ SYMBOLS = {
     "agp_greedy_variance": (_I32, [_VP, _I32, _PK, _VP, _I64, _I64, _I64, _I64, _DBL, _VP, _VP, _I64, _VP, _I64, _VP, _PI64]),
     "agp_kernel_matmul": (_I32, [_VP, _I32, _PK, _VP, _I64, _I64, _VP, _I64, _I64, _I64, _I32, _DBL, _VP, _I64, _I64, _I32, _VP, _I64]),
     "agp_kernel_matmul_wide": (_I32, [_VP, _I32, _PK, _VP, _I64, _I64, _VP, _I64, _I64, _I64, _I32, _DBL, _VP, _I64, _I64, _I32, _VP, _I64]),
+    "agp_kernel_matmul_hd": (_I32, [_VP, _I32, _PK, _VP, _I64, _I64, _VP, _I64, _I64, _I64, _I32, _DBL, _VP, _I64, _I64, _I32, _VP, _I64]),
     "agp_gp_cg_set_block": (_I32, [_VP, _I64]),
     "agp_gp_cg_create": (_I32, [_VP, _PK, _VP, _I64, _I64, _I64, _DBL, _I64, _PVP, _PI64]),
     "agp_gp_cg_solve": (_I32, [_VP, _VP, _I64, _I64, _DBL, _I64, _I64, _VP, _I64, _PI32, _PDBL, _PI32]),

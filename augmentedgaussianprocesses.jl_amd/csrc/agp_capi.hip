@@ -5506,17 +5506,27 @@ agp_status agp_greedy_variance(agp_ctx* ctx, int32_t dtype, const agp_kernel_des
            bb_greedy<float>(ctx, k, x, n, ldx, D, m, tol, idx_out, z_out, ldz, factor_out, ldf, trace_out, n_selected_host));
 }
 
-// what agp_kernel_matmul and agp_gp_cg_create refuse about x, D and the kernel (nullptr: fine); *unsupported: by AGP_ERR_UNSUPPORTED
-static const char* kmv_bad_args(const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D, bool* unsupported) {
+// what the product entries and agp_gp_cg_create refuse about x, D and the kernel (nullptr: fine); *unsupported: by AGP_ERR_UNSUPPORTED.
+// maxd: KMV_MAXD for agp_kernel_matmul, _wide, _dx and agp_kernel_bilinear_grad, whose kernels stop at 64 dimensions;
+// KMV_HD_MAXD for agp_kernel_matmul_hd and the solver handle, whose Float64 product of up to 32 columns has k_kmv_hd above 64.
+static const char* kmv_bad_args(const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D, bool* unsupported,
+                                int64_t maxd = KMV_MAXD) {
   *unsupported = false;
   if (!x) return "null x";
   if (n <= 0 || D <= 0) return "n > 0 and D > 0";
-  if (D > KMV_MAXD) {
+  if (D > maxd) {
     *unsupported = true;
-    return "D <= 64 (the operand tiles of the fused product are sized for it; 65 .. 128 are not served)";
+    return maxd == KMV_MAXD ? "D <= 64 (the operand tiles of the fused product are sized for it; 65 .. 128 are not served)"
+                            : "D <= 128 (the X fragments and chunks of k_kmv_hd are sized for it)";
   }
   if (ldx < D) return "ldx >= D";
   return kmv_bad_kernel(k, D);
+}
+// what a handle with more than 64 input dimensions refuses by name: `what` has no kernel above KMV_MAXD (AGP_ERR_UNSUPPORTED)
+static agp_status cg_hd_refused(agp_gp_cg* h, const char* who, const char* what) {
+  h->ctx->err = std::string(who) + ": D = " + std::to_string(h->D) + " > 64: " + what +
+                " stops at 64 input dimensions; the handle serves solve, solve_slq and apply at the block of 32 in Float64";
+  return AGP_ERR_UNSUPPORTED;
 }
 
 agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
@@ -5572,12 +5582,39 @@ agp_status agp_kernel_matmul_wide(agp_ctx* ctx, int32_t dtype, const agp_kernel_
                           ldv, r, col_groups, (double*)out, ldo);
 }
 
+agp_status agp_kernel_matmul_hd(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
+                                int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo) {
+  if (!ctx) return AGP_ERR_INVALID;
+  bool unsupported = dtype == AGP_F32;
+  const char* bad = dtype == AGP_F32   ? "AGP_F32 is not built: 65 .. 128 input dimensions are Float64 only (dtype AGP_F64)"
+                    : dtype != AGP_F64 ? "dtype is AGP_F64"
+                    : (D > 0 && D <= KMV_MAXD) ? "65 <= D <= 128 (D <= 64 is agp_kernel_matmul's)"
+                                               : kmv_bad_args(k, x, n, ldx, D, &unsupported, KMV_HD_MAXD);
+  if (!bad) {
+    if (!v || !out || (!sym && !y)) bad = "null v, out or y";
+    else if (r < 1 || r > KMV_MAXR) bad = "1 <= r <= 32";
+    else if (p <= 0) bad = "p > 0";
+    else if (sym ? n != p : ldy < D) bad = sym ? "sym: p == n" : "ldy >= D";
+    else if (ldv < r || ldo < r) bad = "ldv >= r and ldo >= r";
+    else if (col_groups < 0) bad = "col_groups >= 0";
+    else if (sym && !std::isfinite(diag_add)) bad = "a finite diag_add";
+  }
+  if (bad) {
+    ctx->err = std::string("agp_kernel_matmul_hd: ") + bad;
+    return unsupported ? AGP_ERR_UNSUPPORTED : AGP_ERR_INVALID;
+  }
+  DevGuard guard(ctx->device);
+  return bb_kernel_matmul(ctx, k, (const double*)x, n, ldx, (const double*)y, p, ldy, D, sym ? 1 : 0, diag_add, (const double*)v,
+                          ldv, r, col_groups, (double*)out, ldo);
+}
+
 agp_status agp_gp_cg_create(agp_ctx* ctx, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx, int64_t D,
                             double sigma2, int64_t precond_rank, agp_gp_cg** out, int64_t* rank_used_host) {
   if (!ctx || !out) return AGP_ERR_INVALID;
   *out = nullptr;
   bool unsupported = false;
-  const char* bad = kmv_bad_args(k, x, n, ldx, D, &unsupported);
+  const char* bad = kmv_bad_args(k, x, n, ldx, D, &unsupported, KMV_HD_MAXD);
   if (!bad && (!(sigma2 > 0.0) || !std::isfinite(sigma2))) bad = "a positive finite sigma2";
   if (!bad && precond_rank < 0) bad = "precond_rank >= 0";
   if (bad) {
@@ -5604,6 +5641,7 @@ agp_status agp_gp_cg_set_operator_dtype(agp_gp_cg* h, int32_t dtype) {
     h->ctx->err = "agp_gp_cg_set_operator_dtype: dtype is AGP_F64 or AGP_F32";
     return AGP_ERR_INVALID;
   }
+  if (dtype == AGP_F32 && h->D > KMV_MAXD) return cg_hd_refused(h, "agp_gp_cg_set_operator_dtype", "the Float32 operator (AGP_F32)");
   if (dtype == AGP_F32 && h->block != CG_LD) {
     h->ctx->err = "agp_gp_cg_set_operator_dtype: the Float32 operator has no wide block: AGP_F32 needs the block of 32 "
                   "(agp_gp_cg_set_block)";
@@ -5619,6 +5657,7 @@ agp_status agp_gp_cg_set_block(agp_gp_cg* h, int64_t block) {
     h->ctx->err = "agp_gp_cg_set_block: block is 32 or 128";
     return AGP_ERR_INVALID;
   }
+  if (block != CG_LD && h->D > KMV_MAXD) return cg_hd_refused(h, "agp_gp_cg_set_block", "the wide block of 128 columns");
   if (block != CG_LD && h->f32) {
     h->ctx->err = "agp_gp_cg_set_block: the Float32 operator has no wide block: 128 needs the Float64 operator "
                   "(agp_gp_cg_set_operator_dtype)";
@@ -5733,6 +5772,7 @@ agp_status agp_gp_cg_apply_dx(agp_gp_cg* h, const void* xt, int64_t nt, int64_t 
   if (!h) return AGP_ERR_INVALID;
   const char* bad = nullptr;
   bool unsupported = false;
+  if (h->D > KMV_MAXD) return cg_hd_refused(h, "agp_gp_cg_apply_dx", "the derivative operator (agp_kernel_matmul_dx)");
   if (!xt) bad = "null xt";
   else if (nt <= 0) bad = "nt > 0";
   else if (ldxt < h->D) bad = "ldxt >= D";
@@ -6565,6 +6605,8 @@ agp_status agp_gp_cg_pathwise_draw(agp_gp_cg* h, const void* b, int64_t n_featur
     ctx->err = std::string("agp_gp_cg_pathwise_draw: ") + bad;
     return AGP_ERR_INVALID;
   }
+  *out = nullptr;
+  if (h->D > KMV_MAXD) return cg_hd_refused(h, "agp_gp_cg_pathwise_draw", "the path-evaluation kernel");
   *out = nullptr;
   AGPCHK(path_check_draw(ctx, h->n, h->D, n_features, n_samples, t));
   DevGuard guard(ctx->device);

@@ -23,7 +23,8 @@
 // product of its own row and column).
 // LDS (DP = D padded to 16, 32 or 64; doubles): 2 x 64 (DP + 2) operand tiles + 64 LDV for V + 128 norms + DP scales:
 //   DP = 64, R = 32: 93.7 KB (one workgroup per CU); DP = 32, R = 32: 60.7 KB (two); DP = 16, R = 16: 27.8 KB.
-// D > 64 is not served (the operand tiles and X fragments are sized at compile time); the driver refuses it by name.
+// D > 64 is not served here (the operand tiles and X fragments are sized at compile time): 65 .. 128 dimensions have k_kmv_hd
+// (agp_kmv_hd.h), which streams the dimensions through LDS in chunks.
 #pragma once
 #include "agp_cavi.h"
 #include "agp_chol.h"  // lds_keep_apart

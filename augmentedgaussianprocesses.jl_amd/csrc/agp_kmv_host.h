@@ -7,6 +7,8 @@
 // can be switched to (cg_set_operator); its vectors, preconditioner, probes and Lanczos table stay Float64.  The derivative with
 // respect to the row points (agp_kmv_dx.h: kmv_dx_apply, kmv_dx_run, bb_kernel_matmul_dx) is Float64 only.  More than 32 and up to 128
 // columns go through the wide kernel (agp_kmv_wide.h) inside kmv_apply; cg_set_block sizes the solver handle for 128 columns.
+// 65 .. 128 input dimensions: kmv_prepare pads the rows to 96 or 128 and kmv_apply sends the product to k_kmv_hd (agp_kmv_hd.h), up to
+// 32 columns, Float64; the Float32 operator, the wide block and the derivative kernels stop at 64 dimensions.
 #pragma once
 #include <cmath>
 #include <string>
@@ -19,6 +21,7 @@
 #include "agp_kmv_dx.h"
 #include "agp_kmv_f32.h"
 #include "agp_kmv_grad.h"
+#include "agp_kmv_hd.h"
 #include "agp_kmv_wide.h"
 #include "agp_rand.h"
 #include "agp_select_host.h"
@@ -52,7 +55,7 @@ static void kmv_release(KmvOp* op) {
 static agp_status kmv_prepare(agp_ctx* ctx, const agp_kernel_desc* k, const double* Y, int64_t p, int64_t ldy, int64_t D,
                               KmvOp* op) {
   op->kind = k->kind, op->variance = k->variance, op->D = D, op->p = p;
-  op->DP = D <= 16 ? 16 : D <= 32 ? 32 : 64;
+  op->DP = D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : D <= 96 ? 96 : 128;
   const int64_t p_pad = rup64(p);
   std::vector<double> hs(D);
   for (int64_t d = 0; d < D; ++d) hs[d] = k->ard ? k->ard_scales_host[d] : k->scale;
@@ -132,14 +135,38 @@ static void kmv_wide_launch_kind(hipStream_t st, dim3 grid, const double* X, int
 #undef AGP_KMVW_CASE
 }
 
+// 65 .. 128 input dimensions (agp_kmv_hd.h): r <= 32, the padded width 96 or 128 that kmv_prepare chose
+template <int KIND>
+static void kmv_hd_launch_kind(hipStream_t st, dim3 grid, const double* X, int64_t ldx, int64_t n, const KmvOp& op, int sym,
+                               double diag_add, const double* V, int64_t ldv, int r, double* out, int64_t ldo, int64_t slice) {
+#define AGP_KMVHD_ONE(DPV, RBV)                                                                                                     \
+  hipLaunchKernelGGL((k_kmv_hd<KIND, DPV, RBV>), grid, dim3(NTHREADS), (kmv_hd_smem_bytes<DPV, RBV>()), st, X, ldx, n,              \
+                     (const double*)op.ysc, (const double*)op.ysn, op.p, op.D, (const double*)op.scales, op.variance, sym, diag_add, \
+                     V, ldv, r, out, ldo, slice)
+#define AGP_KMVHD_CASE(DPV)           \
+  if (r <= 16) AGP_KMVHD_ONE(DPV, 1); \
+  else AGP_KMVHD_ONE(DPV, 2)
+  static_assert(kmv_hd_smem_bytes<128, 2>() <= 64 * 1024, "no instance has to ask for more dynamic LDS than a launch gets");
+  if (op.DP == 96) { AGP_KMVHD_CASE(96); }
+  else { AGP_KMVHD_CASE(128); }
+#undef AGP_KMVHD_CASE
+#undef AGP_KMVHD_ONE
+}
+
 // out (n x r, ldo) = (K(X, Y) + diag_add [sym]) V, enqueued on the context's stream.  groups > 1: ws holds groups * n * r doubles.
-// r <= 32: k_kmv; 32 < r <= 128: k_kmv_wide.
+// r <= 32: k_kmv; 32 < r <= 128: k_kmv_wide.  op.D > 64: k_kmv_hd, r <= 32 (the callers refuse more).
 static agp_status kmv_apply(agp_ctx* ctx, const KmvOp& op, const double* X, int64_t ldx, int64_t n, int sym, double diag_add,
                             const double* V, int64_t ldv, int r, int groups, double* ws, double* out, int64_t ldo) {
   const dim3 grid((unsigned)groups, (unsigned)((n + TILE - 1) / TILE));
   double* dst = groups > 1 ? ws : out;
   const int64_t ldd = groups > 1 ? r : ldo, slice = groups > 1 ? n * r : 0;
-  if (r > KMV_MAXR) switch (op.kind) {
+  if (op.D > KMV_MAXD) switch (op.kind) {
+    case AGP_K_SQEXP: kmv_hd_launch_kind<K_SQEXP>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+    case AGP_K_MATERN52: kmv_hd_launch_kind<K_MATERN52>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+    case AGP_K_MATERN32: kmv_hd_launch_kind<K_MATERN32>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+    default: kmv_hd_launch_kind<K_EXPONENTIAL>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
+  }
+  else if (r > KMV_MAXR) switch (op.kind) {
     case AGP_K_SQEXP: kmv_wide_launch_kind<K_SQEXP>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
     case AGP_K_MATERN52: kmv_wide_launch_kind<K_MATERN52>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;
     case AGP_K_MATERN32: kmv_wide_launch_kind<K_MATERN32>(ctx->stream, grid, X, ldx, n, op, sym, diag_add, V, ldv, r, dst, ldd, slice); break;

@@ -1,9 +1,12 @@
 """IterativeGP -- the exact GP without an N x N matrix, and the two operators it runs on: `kernel_matmul`, (K(X, Y) + c I) V for a block
 V with K never in memory (agp_kernel_matmul, csrc/agp_kmv.h), and `kernel_bilinear_grad`, sum_c w_c u_c' (dK / d theta) v_c for the
 kernel's variance and scales with neither K nor the weight matrix in memory (agp_kernel_bilinear_grad, csrc/agp_kmv_grad.h), under a
-batched preconditioned CG (agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 64, one GPU, Gaussian likelihood;
+batched preconditioned CG (agp_gp_cg_*).  N is limited by time, not by 8 N^2 bytes.  Float64, D <= 128, one GPU, Gaussian likelihood;
 the operator product alone also has a Float32 instance (csrc/agp_kmv_f32.h: `kernel_matmul(dtype=np.float32)`,
 `IterativeGP(operator_dtype=np.float32)`).  `block=128` on either takes 128 columns per launch / per CG run (csrc/agp_kmv_wide.h).
+65 <= D <= 128 runs on a kernel of its own (agp_kernel_matmul_hd, csrc/agp_kmv_hd.h): the Float64 product of up to 32 columns, and
+with it solve, operator, alpha, predict_f, predict_y and the log marginal likelihood without gradients.  The Float32 operator, the
+block of 128 and every derivative or path kernel stop at D = 64 and say so.
 
 The log marginal likelihood is stochastic: log det(K + noise I) = log det P + E_z[z' P^-1/2 log(P^-1/2 (K + noise I) P^-1/2) P^-1/2 z]
 over probes z ~ N(0, P), P the solver's preconditioner, each expectation term by Lanczos quadrature on the coefficients the CG
@@ -27,6 +30,8 @@ from .likelihoods import GaussianLikelihood
 from .svgp import ADAM, ELBO, predict_f, predict_y, train_
 
 MAXR = 32  # right-hand sides per launch / per batched solve (KMV_MAXR)
+MAXD = 64  # input dimensions of every operator kernel but the Float64 product of 32 columns (KMV_MAXD), whose limit is
+HD_MAXD = 128  # (KMV_HD_MAXD: agp_kernel_matmul_hd, csrc/agp_kmv_hd.h)
 WIDE = 128  # ... of the wide block (KMV_WIDE_MAXR): kernel_matmul(block=128), IterativeGP(block=128)
 
 
@@ -34,6 +39,13 @@ def _block(block, who):
     if isinstance(block, bool) or block not in (MAXR, WIDE):
         raise ValueError(f"{who}: block must be 32 or 128, got {block!r}")
     return int(block)
+
+
+def _refuse_hd(D, who, what, exc=NotImplementedError):
+    """what has no kernel for 65 .. 128 input dimensions is refused by name"""
+    if D > MAXD:
+        raise exc(f"{who}: D = {D}, but {what} stops at D = {MAXD} (only the Float64 operator product of 32 columns serves "
+                  f"{MAXD + 1} <= D <= {HD_MAXD})")
 
 
 def _torch():
@@ -108,7 +120,7 @@ def _kernel_matmul(cx, kernel, Xd, Vd, Yd, diag_add, col_groups, dtype=np.float6
         raise ValueError(f"V has {Vd.shape[0]} rows, K(X, Y) has {p} columns")
     kd, keep = kernel.desc(D)
     out = torch.empty(n, Vd.shape[1], dtype=_torch_dtype(dtype), device=cx.dev)
-    call = L.agp_kernel_matmul_wide if block == WIDE else L.agp_kernel_matmul
+    call = L.agp_kernel_matmul_hd if D > MAXD else L.agp_kernel_matmul_wide if block == WIDE else L.agp_kernel_matmul
     for c0 in range(0, Vd.shape[1], block):
         v, o = Vd[:, c0:c0 + block], out[:, c0:c0 + block]
         cx.chk(call(cx.ctx, capi.F32 if dtype is np.float32 else capi.F64, C.byref(kd), C.c_void_p(Xd.data_ptr()), n, Xd.stride(0),
@@ -128,11 +140,18 @@ def kernel_matmul(kernel, X, V, Y=None, diag_add: float = 0.0, col_groups: int =
     are converted to that type and the output has it.  np.float32 runs the Float32 kernel (both products on the Float32 matrix
     instruction, the sum over the columns of K in Float64 across windows of 128): kernel values to about 1e-6 of the variance.
     block=128 takes the columns of V 128 at a time through the wide kernel (agp_kernel_matmul_wide, csrc/agp_kmv_wide.h): every
-    kernel tile is computed once for 128 columns, not once per 32, and each column equals block=32's bit for bit.  Float64 only."""
+    kernel tile is computed once for 128 columns, not once per 32, and each column equals block=32's bit for bit.  Float64 only.
+    65 <= D <= 128 goes through agp_kernel_matmul_hd (csrc/agp_kmv_hd.h), Float64 in blocks of 32 columns: dtype=np.float32 and
+    block=128 are refused there."""
     if Y is not None and diag_add != 0.0:
         raise ValueError("diag_add is added to the diagonal of K(X, X): it needs Y=None")
     dtype = _np_dtype(dtype, "dtype")
     block = _block(block, "kernel_matmul")
+    D = 1 if np.ndim(X) == 1 else np.shape(X)[1]
+    if dtype is np.float32:
+        _refuse_hd(D, "kernel_matmul", "dtype=np.float32 (the Float32 kernel)", ValueError)
+    if block == WIDE:
+        _refuse_hd(D, "kernel_matmul", "block=128 (the wide kernel)", ValueError)
     torch = _torch()
     cx = _Ctx(device)
     try:
@@ -269,7 +288,12 @@ class IterativeGP:
     solves THAT system, and its recursive residual stops tracking the true one somewhere around the operator's own error.  A `tol`
     below that level shows up as converged = False in model.info; it is not an exception.  The option is meant for
     log_marginal_likelihood and optimize, whose Monte-Carlo error is orders of magnitude larger; the default, and any prediction that
-    must be exact, stays np.float64.  No iterative refinement is built."""
+    must be exact, stays np.float64.  No iterative refinement is built.
+
+    D <= 128.  With 65 <= D <= 128 every operator product runs on the kernel for that range (csrc/agp_kmv_hd.h): solve, operator,
+    alpha, predict_f, predict_y, log_marginal_likelihood(grad=False) and ELBO(model) are served; operator_dtype=np.float32 and
+    block=128 (ValueError), log_marginal_likelihood(grad=True), optimize, predict_f_grad and sample_paths (NotImplementedError) are
+    not: their kernels stop at D = 64."""
 
     def __init__(self, X, y, kernel, *, noise: float = 1e-5, mean=None, tol: float = 1e-8, max_iter: int = 1000,
                  precond_rank: int = 64, check_every: int = 10, device: Optional[int] = None, operator_dtype=np.float64,
@@ -290,6 +314,10 @@ class IterativeGP:
         self.block = _block(block, "IterativeGP")
         if self.block == WIDE and self.operator_dtype is np.float32:
             raise ValueError("IterativeGP: block=128 needs operator_dtype=np.float64 (no Float32 wide block is built)")
+        if self.operator_dtype is np.float32:
+            _refuse_hd(self.D, "IterativeGP", "operator_dtype=np.float32 (the Float32 operator)", ValueError)
+        if self.block == WIDE:
+            _refuse_hd(self.D, "IterativeGP", "block=128 (the wide kernel)", ValueError)
         self.device = device
         self.info = None
         self.rank_used = None
@@ -398,6 +426,8 @@ class IterativeGP:
         estimators exact traces).  grad=True: (value, dict(variance=, scales=[D], noise=)) -- derivatives with respect to the
         kernel's variance, the per-dimension scales (for a ScaleTransform also scale= their sum) and the noise, the trace terms by
         the same probes.  num_probes is an interface default, not tuned; accuracy is set by it, by tol and by max_iter."""
+        if grad:
+            _refuse_hd(self.D, "IterativeGP.log_marginal_likelihood(grad=True)", "the derivative bilinear form (csrc/agp_kmv_grad.h)")
         torch = _torch()
         L = capi.lib()
         h = self._solver()
@@ -452,6 +482,7 @@ class IterativeGP:
         defaults, not tuned.  Returns the values log p(y) at the parameters BEFORE each step."""
         from .kernels import ARDTransform, ScaleTransform
 
+        _refuse_hd(self.D, "IterativeGP.optimize", "the derivative bilinear form of its gradient (csrc/agp_kmv_grad.h)")
         o = ADAM(0.01) if optimiser is None else optimiser
         if not isinstance(o, ADAM):
             raise TypeError("IterativeGP.optimize takes an ADAM optimiser")
@@ -551,6 +582,7 @@ def predict_f_grad_iterative(model: IterativeGP, X_test, *, cov: bool = True, ob
     if obsdim not in (1, 2):
         raise ValueError("predict_f_grad: obsdim is 1 (points are rows) or 2 (points are columns)")
     _refuse_exponential(model.kernel, "predict_f_grad")
+    _refuse_hd(model.D, "predict_f_grad(IterativeGP)", "the derivative operator (csrc/agp_kmv_dx.h)")
     alpha = model.alpha()
     cx, h, D = model._cx, model._solver(), model.D
     Xt = _rows(_test_points(model, X_test, obsdim))

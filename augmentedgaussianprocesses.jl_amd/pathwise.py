@@ -353,10 +353,11 @@ def sample_paths(model, n_samples: int, *, n_features: int = 1024, seed: Optiona
     (AnalyticVI / AnalyticSVI), GP or OnlineSVGP, or of an IterativeGP (matrix-free: IterativePaths).  seed=None takes the model's
     seed (drawn once from the model's generator, as `sample` does for an MCGP); t is the caller's draw counter: another t, another
     independent draw from the same seed."""
-    from .iterative import IterativeGP
+    from .iterative import IterativeGP, _refuse_hd
     from .svgp import SVGP
 
     if isinstance(model, IterativeGP):
+        _refuse_hd(model.D, "sample_paths(IterativeGP)", "the path-evaluation kernel (csrc/agp_path.h)")
         check_draw_args(model.N, model.D, n_samples, n_features, t, seed)
         if seed is None:
             if model.seed is None:

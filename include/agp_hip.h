@@ -403,6 +403,17 @@ agp_status agp_kernel_matmul(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc*
 agp_status agp_kernel_matmul_wide(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
                                   const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
                                   int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo);
+/* agp_kernel_matmul_hd: agp_kernel_matmul with AGP_F64 for 65 <= D <= 128 (csrc/agp_kmv_hd.h: k_kmv_hd), 1 <= r <= 32.  Same
+ * arguments, layout, error budget (the element budget of tests/_kmat_ref.py is a function of D), exact diagonal of the symmetric
+ * form, col_groups and determinism.  The work split is agp_kernel_matmul's -- 64 rows of x per workgroup, 16 per wave, both products
+ * on v_mfma_f64_16x16x4, the kernel tile handed over in registers --; what differs is how the dimensions move: the x operands stay in
+ * registers for the launch, y streams through LDS in chunks of 32 (D <= 96) or 64 dimensions with the first product's accumulators
+ * carried across the chunks, and the repair of (nearly) coincident points reads whole rows from global memory.
+ * Refused by name before anything is touched: AGP_ERR_INVALID for D <= 64 (that is agp_kernel_matmul's) and for everything
+ * agp_kernel_matmul refuses so; AGP_ERR_UNSUPPORTED for D > 128 and for AGP_F32 (no Float32 kernel above 64 dimensions is built). */
+agp_status agp_kernel_matmul_hd(agp_ctx* ctx, int32_t dtype, const agp_kernel_desc* k, const void* x, int64_t n, int64_t ldx,
+                                const void* y, int64_t p, int64_t ldy, int64_t D, int32_t sym, double diag_add, const void* v,
+                                int64_t ldv, int64_t r, int32_t col_groups, void* out, int64_t ldo);
 /* agp_gp_cg: solves (K(x, x) + sigma2 I) A = B for B n x r, r <= 32, by r INDEPENDENT conjugate-gradient recurrences that share
  * every operator product (not block CG): each column has its own alpha, beta and residual, on the device; column dots are
  * two-stage sums of fixed order.  A column whose recursive residual reaches |r| <= tol |b| is frozen -- its update is skipped --
@@ -412,7 +423,10 @@ agp_status agp_kernel_matmul_wide(agp_ctx* ctx, int32_t dtype, const agp_kernel_
  * create: once per (x, kernel, sigma2 > 0); keeps a copy of x.  precond_rank = k > 0: preconditioner P = L L' + sigma2 I with L the
  * n x k factor of agp_greedy_variance on the same x and kernel (fewer columns if its stop rule fires; *rank_used_host says how
  * many), applied by Woodbury with the k x k matrix sigma2 I + L'L inverted once; 0: plain CG.  Same refusals as agp_kernel_matmul
- * for its x, D and kernel, plus sigma2 not positive and finite, precond_rank < 0.
+ * for its x, D and kernel -- except that D may be up to 128 --, plus sigma2 not positive and finite, precond_rank < 0.
+ * A handle with 65 <= D <= 128 runs every operator product on agp_kernel_matmul_hd's kernel: solve, solve_slq, apply, probes and
+ * precond_logdet serve it; set_operator_dtype(AGP_F32), set_block(128), apply_dx and pathwise_draw refuse it by name with
+ * AGP_ERR_UNSUPPORTED (their kernels stop at 64 dimensions) and leave the handle usable.
  * solve: b n x r (ldb >= r), a n x r (lda >= r), device; iters_host / relres_host / converged_host: nullable host arrays of r
  * (iterations taken, final recursive |r| / |b|, 1 if converged).  Refused: r < 1, r > 32, ldb < r, lda < r, tol < 0 or NaN,
  * max_iter < 0.  Synchronises.

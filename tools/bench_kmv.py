@@ -19,6 +19,9 @@ test points at N training points, split into the batched solve and the gradient 
 --wide: the block of 128 columns (agp_kernel_matmul_wide, csrc/agp_kmv_wide.h; IterativeGP(block=128)) against the block of 32 on the
 same build and nothing else: one product at n = p = --n with r = 128 (one wide launch against four launches of 32), one CG iteration at
 N = --big at both blocks, and predict_f's variance for 128 test points at N = --big at both blocks (see wide_block).
+--hd: the operator for 65 .. 128 input dimensions (agp_kernel_matmul_hd, csrc/agp_kmv_hd.h; see high_dim): one product of 32 columns
+on prepared operators at D = 96 and 128 beside k_kmv at D = 64 and the dense composition, one CG iteration and one predictive
+variance of 32 points at N = --big, D = 96.
 --paths NT: one evaluation of 32 pathwise draws of an IterativeGP (agp_gp_cg_pathwise_eval, csrc/agp_path.h) at NT points against
 N = --n training points and --features random features, (a) `fused`; (b) `composed`, the same result from what there was before:
 agp_pathwise_eval of a 64-point GP's draw with the same number of features (k_pw_features into memory, 64 columns of kernel matrix,
@@ -147,6 +150,78 @@ def wide_block(a, AGP, capi, L, ctx, kd, gen):
     return res
 
 
+def high_dim(a, AGP, capi, L, ctx, gen):
+    """--hd: the operator for 65 .. 128 input dimensions (csrc/agp_kmv_hd.h).  (1) one product at n = p = --n, r = 32 on PREPARED
+    operators (agp_gp_cg_apply of handles without preconditioner) at D = 96 and D = 128, alternating in every repetition with
+    k_kmv at D = 64 on the same shape -- the d2 step grows with the padded width, the function and product steps do not --, and the
+    dense composition at the same n: agp_kernelmatrix into memory plus torch.mm.  (2) at N = --big, D = 96: one CG iteration with the
+    default preconditioner (the difference of a solve of 5 and of 1 iterations at tol = 0, over 4) and predict_f's variance for 32
+    test points (alpha solved before the clock starts; host clock, ONE run)."""
+    import time
+
+    import numpy as np
+
+    n, r = a.n, 32
+    kern = lambda D: AGP.SqExponentialKernel() @ AGP.ScaleTransform(a.scale * (32.0 / D) ** 0.5)  # noqa: E731
+    V = torch.randn(n, r, dtype=torch.float64, device="cuda", generator=gen)
+    out = torch.empty(n, r, dtype=torch.float64, device="cuda")
+    Xs, hs, keep = {}, {}, []
+    for D in (64, 96, 128):
+        Xs[D] = torch.rand(n, D, dtype=torch.float64, device="cuda", generator=gen)
+        kd, k = kern(D).desc(D)
+        keep.append(k)
+        hs[D] = C.c_void_p()
+        assert L.agp_gp_cg_create(ctx, C.byref(kd), Xs[D].data_ptr(), n, D, D, 1e-2, 0, C.byref(hs[D]), None) == 0, L.agp_last_error(ctx)
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    ts = {D: [] for D in hs}
+    for rep in range(a.reps + 1):  # (repetition 0: the warm-up of all three)
+        for D, h in hs.items():
+            ts[D].append(once(lambda: L.agp_gp_cg_apply(h, V.data_ptr(), r, r, out.data_ptr(), r)))
+    res = dict(bench="kernel_matmul_hd", n=n, r=r, product_prepared={})
+    for D in hs:
+        t = sorted(ts[D][1:])
+        res["product_prepared"][f"D{D}"] = dict(best_ms=round(t[0], 3), median_ms=round(t[len(t) // 2], 3),
+                                                over_D64=round(t[0] / sorted(ts[64][1:])[0], 3))
+        L.agp_gp_cg_destroy(hs[D])
+    if not a.no_dense:
+        K = torch.empty(n, n, dtype=torch.float64, device="cuda")
+        for D in (96, 128):
+            kd, k = kern(D).desc(D)
+
+            def two_step():
+                assert L.agp_kernelmatrix(ctx, capi.F64, C.byref(kd), Xs[D].data_ptr(), n, D, None, Xs[D].data_ptr(), n, D, D,
+                                          K.data_ptr(), n) == 0, L.agp_last_error(ctx)
+                return torch.mm(K, V)
+
+            res["product_prepared"][f"D{D}"]["kernelmatrix_then_gemm"] = timed(two_step, a.reps)
+        del K
+    del Xs, V, out
+    if a.big:
+        N, D = a.big, 96
+        Xb = torch.rand(N, D, dtype=torch.float64, device="cuda", generator=gen).cpu().numpy()
+        m = AGP.IterativeGP(Xb, np.sin(3 * Xb[:, 0]), kern(D), noise=1e-2, tol=1e-6)
+        m.alpha()
+        B = torch.randn(N, r, dtype=torch.float64, device="cuda", generator=gen)
+        m._solve_dev(B, 0.0, 1)  # warm-up
+        tk = {k: min(once(lambda: m._solve_dev(B, 0.0, k)) for _ in range(2)) for k in (1, 5)}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        AGP.predict_f(m, Xb[:32] + 0.01)
+        res["big"] = dict(N=N, D=D, cg_iteration_ms=round((tk[5] - tk[1]) / 4, 3), alpha_iterations=int(m.alpha_info["iterations"].max()),
+                          predict_f_variance_32_points=dict(seconds=round(time.perf_counter() - t0, 3),
+                                                            iterations=int(m.info["iterations"].max())))
+        m.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32768)
@@ -164,6 +239,7 @@ def main():
     ap.add_argument("--paths-draw", type=int, default=0)
     ap.add_argument("--dtype", nargs="+", choices=["f64", "f32"], default=["f64", "f32"])
     ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--hd", action="store_true")
     a = ap.parse_args()
     g.build()
     import agp_amd as AGP
@@ -184,6 +260,9 @@ def main():
 
     if a.wide:
         print(json.dumps(wide_block(a, AGP, capi, L, ctx, kd, gen)))
+        return
+    if a.hd:
+        print(json.dumps(high_dim(a, AGP, capi, L, ctx, gen)))
         return
 
     for n in [a.n] + ([a.big] if a.big else []):
