@@ -247,6 +247,7 @@ SYMBOLS = {
     "agp_pathwise_features": (_I32, [_VP, _PK, _I64, _I32, C.c_uint64, _I64, _I32, _VP, _VP]),
     "agp_gp_cg_pathwise_draw": (_I32, [_VP, _VP, _I64, _I64, C.c_uint64, _I64, _DBL, _I64, _I64, _PI32, _PDBL, _PI32, _PVP]),
     "agp_gp_cg_pathwise_eval": (_I32, [_VP, _VP, _I64, _I64, _I32, _VP, _I64]),
+    "agp_gp_cg_pathwise_eval_f32": (_I32, [_VP, _VP, _I64, _I64, _I32, _VP, _I64]),
     "agp_gp_cg_pathwise_get": (_I32, [_VP, _I32, _VP, _I64]),
     "agp_gp_cg_pathwise_destroy": (_I32, [_VP]),
 }

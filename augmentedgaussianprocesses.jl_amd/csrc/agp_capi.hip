@@ -6633,6 +6633,22 @@ agp_status agp_gp_cg_pathwise_eval(agp_gp_cg_paths* p, const void* xt, int64_t l
   DevGuard guard(p->ctx->device);
   return path_eval(*p, (const double*)xt, ldx, n_t, col_groups, (double*)out, ldo);
 }
+agp_status agp_gp_cg_pathwise_eval_f32(agp_gp_cg_paths* p, const void* xt, int64_t ldx, int64_t n_t, int32_t col_groups, float* out,
+                                       int64_t ldo) {
+  if (!p) return AGP_ERR_INVALID;
+  const char* bad = nullptr;
+  if (!xt || !out) bad = "xt and out must be given";
+  else if (n_t < 1) bad = "n_t >= 1";
+  else if (ldx < p->D) bad = "ldx >= D";
+  else if (ldo < p->S) bad = "ldo >= n_samples";
+  else if (col_groups < 0) bad = "col_groups >= 0";
+  if (bad) {
+    p->ctx->err = std::string("agp_gp_cg_pathwise_eval_f32: ") + bad;
+    return AGP_ERR_INVALID;
+  }
+  DevGuard guard(p->ctx->device);
+  return path32_eval(*p, (const double*)xt, ldx, n_t, col_groups, out, ldo);
+}
 agp_status agp_gp_cg_pathwise_get(agp_gp_cg_paths* p, int32_t which, void* out, int64_t ld) {
   if (!p) return AGP_ERR_INVALID;
   agp_ctx* ctx = p->ctx;

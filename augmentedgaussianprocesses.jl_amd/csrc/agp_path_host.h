@@ -2,6 +2,7 @@
 // PATHWISE SAMPLING"): the launch of k_path / k_kmv_sum (path_apply), the draw on a solver handle (path_draw: the tables from the
 // generators of agp_pathwise.h, P = Phi(X) W by k_path, R = b - P - sigma E, V = (K + sigma2 I)^-1 R by cg_solve in blocks of 32
 // columns) and the evaluation of the paths at any number of points (path_eval: one k_path launch per block of 32 samples).
+// The Float32 evaluation (kernel: agp_path_f32.h) is path32_build / path32_apply / path32_eval at the end of this file.
 // Decoupled sampling (Wilson et al. 2020):
 //   f_s(x) = mean + Phi(x) w_s + K(x, X) v_s ,   v_s = (K + sigma2 I)^-1 (y - mean - Phi(X) w_s - sigma e_s)
 // The paths object is a snapshot: it owns copies of the prepared training side, the Omega tiles in the same prepared layout, the phases,
@@ -13,6 +14,7 @@
 
 #include "agp_kmv_host.h"
 #include "agp_path.h"
+#include "agp_path_f32.h"
 #include "agp_pathwise_host.h"
 
 struct agp_gp_cg_paths {
@@ -24,8 +26,15 @@ struct agp_gp_cg_paths {
   double *W = nullptr, *V = nullptr, *E = nullptr;          // L x S, n x S, n x S, dense
   double* ws = nullptr;                                     // the slices of a grouped launch, grown by the call that needs more
   int64_t ws_cap = 0;
+  // the Float32 side, built by the first Float32 evaluation (path32_build): the centred training tiles, their norms and the mean of
+  // the scaled rows (op32), the Omega tiles (rup64(L) x DP), the compensated phases (rup64(L)), W (L x S) and V (n x S) rounded once
+  bool has32 = false;
+  Kmv32Op op32;
+  float *om32 = nullptr, *ph32 = nullptr, *W32 = nullptr, *V32 = nullptr;
   ~agp_gp_cg_paths() {
     kmv_release(&op);
+    kmv32_release(&op32);
+    for (float* q : {om32, ph32, W32, V32}) (void)hipFree(q);
     for (double* q : {omega, omt, php, W, V, E, ws}) (void)hipFree(q);
   }
 };
@@ -170,5 +179,97 @@ static agp_status path_eval(agp_gp_cg_paths& p, const double* x, int64_t ldx, in
   for (int64_t c0 = 0; c0 < p.S; c0 += KMV_MAXR)
     AGPCHK(path_apply(p, x, ldx, nt, p.L, p.W + c0, p.n, p.V + c0, p.S, (int)std::min<int64_t>(KMV_MAXR, p.S - c0), col_groups,
                       out + c0, ldo));
+  return AGP_OK;
+}
+
+// ---- Float32 evaluation (agp_path_f32.h) --------------------------------------------------------------------------------------------
+// The Float32 side of the snapshot, from its own Float64 tables; nothing of it exists before the first Float32 evaluation.  The
+// training side goes through kmv32_prepare on the SCALED rows (op.ysc, row pitch DP) with unit scales: op32.mean is the mean of the
+// scaled rows and op32.xsc = float(sX - mean), which is what k_path32's prologue forms for a test point.  A failure leaves no part
+// of it behind.
+static agp_status path32_build(agp_gp_cg_paths& p) {
+  if (p.has32) return AGP_OK;
+  agp_ctx* ctx = p.ctx;
+  const int64_t Lp = rup64(p.L);
+  auto build = [&]() -> agp_status {
+    AGPCHK(kmv32_prepare<double>(ctx, p.op.kind, p.op.variance, std::vector<double>(p.D, 1.0), p.op.ysc, p.n, p.op.DP, nullptr, p.n,
+                                 0, p.D, &p.op32));
+    AGPCHK(dmalloc(ctx, &p.om32, Lp * p.op.DP));
+    AGPCHK(dmalloc(ctx, &p.ph32, Lp));
+    AGPCHK(dmalloc(ctx, &p.W32, p.L * p.S));
+    AGPCHK(dmalloc(ctx, &p.V32, p.n * p.S));
+    hipLaunchKernelGGL(agp::k_path32_prep, dim3((unsigned)((Lp + 3) / 4)), dim3(256), 0, ctx->stream, (const double*)p.omega,
+                       (const double*)p.php, p.L, Lp, p.D, p.op.DP, (const double*)p.op32.mean, p.om32, p.ph32);
+    hipLaunchKernelGGL(agp::k_kmv32_stage, grid1(p.L * p.S), dim3(256), 0, ctx->stream, (const double*)p.W, p.S, p.L, (int)p.S, p.W32);
+    hipLaunchKernelGGL(agp::k_kmv32_stage, grid1(p.n * p.S), dim3(256), 0, ctx->stream, (const double*)p.V, p.S, p.n, (int)p.S, p.V32);
+    LAUNCHCHK(ctx);
+    return AGP_OK;
+  };
+  const agp_status s = build();
+  if (s != AGP_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    kmv32_release(&p.op32);
+    for (float** q : {&p.om32, &p.ph32, &p.W32, &p.V32}) {
+      (void)hipFree(*q);
+      *q = nullptr;
+    }
+    return s;
+  }
+  p.has32 = true;
+  return AGP_OK;
+}
+
+// what one Float32 launch multiplies: columns c0 .. c0 + r of W32 and V32
+struct Path32Args {
+  const double* X;
+  int64_t ldx, n, c0, ldo, slice;
+  int r, of32;
+  void* out;
+};
+template <int KIND>
+static void path32_launch_kind(hipStream_t st, dim3 grid, const agp_gp_cg_paths& p, const Path32Args& a) {
+#define AGP_PATH32_ONE(DPV, RBV)                                                                                                     \
+  hipLaunchKernelGGL((agp::k_path32<KIND, DPV, RBV>), grid, dim3(NTHREADS), (agp::kmv32_smem_bytes<DPV, RBV>()), st, a.X, a.ldx, a.n, \
+                     p.D, (const double*)p.op.scales, (const double*)p.op32.mean, (const float*)p.om32, (const float*)p.ph32, p.L,   \
+                     (float)p.amp, (const float*)p.W32 + a.c0, p.S, (const float*)p.op32.xsc, (const float*)p.op32.xsn, p.n,         \
+                     p.op32.variance, (const float*)p.V32 + a.c0, p.S, a.r, a.out, a.ldo, a.slice, a.of32)
+#define AGP_PATH32_CASE(DPV)            \
+  if (a.r <= 16) AGP_PATH32_ONE(DPV, 1); \
+  else AGP_PATH32_ONE(DPV, 2)
+  if (p.op.DP == 16) { AGP_PATH32_CASE(16); }
+  else if (p.op.DP == 32) { AGP_PATH32_CASE(32); }
+  else { AGP_PATH32_CASE(64); }
+#undef AGP_PATH32_CASE
+#undef AGP_PATH32_ONE
+}
+// out (n x r floats, ldo) = Phi(x) W[:, c0 .. c0 + r] + K(x, X) V[:, c0 .. c0 + r] on k_path32, enqueued on the context's stream;
+// col_groups as path_apply takes it
+static agp_status path32_apply(agp_gp_cg_paths& p, const double* x, int64_t ldx, int64_t n, int64_t c0, int r, int64_t col_groups,
+                               float* out, int64_t ldo) {
+  agp_ctx* ctx = p.ctx;
+  const int groups = path_groups(ctx, n, (p.L + TILE - 1) / TILE + (p.n + TILE - 1) / TILE, col_groups);
+  if (groups > 1) AGPCHK(path_ws(p, (int64_t)groups * n * r));
+  const dim3 grid((unsigned)groups, (unsigned)((n + TILE - 1) / TILE));
+  Path32Args a{x, ldx, n, c0, groups > 1 ? (int64_t)r : ldo, groups > 1 ? n * r : 0, r, groups > 1 ? 0 : 1,
+               groups > 1 ? (void*)p.ws : (void*)out};
+  switch (p.op.kind) {
+    case AGP_K_SQEXP: path32_launch_kind<K_SQEXP>(ctx->stream, grid, p, a); break;
+    case AGP_K_MATERN52: path32_launch_kind<K_MATERN52>(ctx->stream, grid, p, a); break;
+    case AGP_K_MATERN32: path32_launch_kind<K_MATERN32>(ctx->stream, grid, p, a); break;
+    default: path32_launch_kind<K_EXPONENTIAL>(ctx->stream, grid, p, a); break;
+  }
+  if (groups > 1)
+    hipLaunchKernelGGL(agp::k_kmv32_sum, grid1(n * r), dim3(256), 0, ctx->stream, (const double*)p.ws, groups, n, r, (void*)out, ldo, 1);
+  LAUNCHCHK(ctx);
+  return AGP_OK;
+}
+
+// out (nt x S floats, ldo) = Phi(x) W + K(x, X) V: one k_path32 launch per block of 32 samples (plus the slice sum when grouped);
+// asynchronous but for the first call, which builds the Float32 side
+static agp_status path32_eval(agp_gp_cg_paths& p, const double* x, int64_t ldx, int64_t nt, int64_t col_groups, float* out,
+                              int64_t ldo) {
+  AGPCHK(path32_build(p));
+  for (int64_t c0 = 0; c0 < p.S; c0 += KMV_MAXR)
+    AGPCHK(path32_apply(p, x, ldx, nt, c0, (int)std::min<int64_t>(KMV_MAXR, p.S - c0), col_groups, out + c0, ldo));
   return AGP_OK;
 }

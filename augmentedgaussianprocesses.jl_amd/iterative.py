@@ -14,7 +14,7 @@ computes anyway; the trace in the gradient uses the same probes and solves.  `It
 `train_` stays refused (it is the interface of the variational models).  `kernel_matmul_grad` is the derivative of the operator
 product with respect to its row points (agp_kernel_matmul_dx, csrc/agp_kmv_dx.h); `predict_f_grad(IterativeGP)` runs on it.
 `sample_paths(IterativeGP, S)` draws posterior functions without an N x N matrix (pathwise.py: IterativePaths; the fused
-path-evaluation kernel of csrc/agp_path.h under the draw's batched CG and under every evaluation).  Not here: the full predictive
+path-evaluation kernel of csrc/agp_path.h under the draw's batched CG and under every evaluation; paths(X, dtype=np.float32) evaluates on its Float32 instance, csrc/agp_path_f32.h).  Not here: the full predictive
 covariance, gradients with respect to the training inputs or the prior mean, gradients of the drawn paths.
 """
 from __future__ import annotations

@@ -256,7 +256,8 @@ class IterativePaths:
     """n_samples function draws from the posterior of an IterativeGP (agp_gp_cg_pathwise_*): f_s(x) = mean + Phi(x) w_s + K(x, X) v_s
     with v_s = (K + noise I)^-1 (y - mean - Phi(X) w_s - sqrt(noise) e_s) solved by the model's batched CG, 32 samples at a time.  The
     draw and every evaluation run on one fused kernel that forms neither Phi nor K in memory.  A snapshot: the paths evaluate, with
-    the same bits, after the model is closed.  `info` is the CG report of the draw (iterations, residuals, converged per sample)."""
+    the same bits, after the model is closed.  paths(X, dtype=np.float32) evaluates on the Float32 instance of that kernel (the
+    draw itself is always Float64).  `info` is the CG report of the draw (iterations, residuals, converged per sample)."""
 
     def __init__(self, model, n_samples: int, n_features: int, seed: int, t: int):
         self.n_samples, self.n_features, self.seed, self.t = int(n_samples), int(n_features), int(seed), int(t)
@@ -285,11 +286,17 @@ class IterativePaths:
             raise RuntimeError("the paths have been freed")
         return self._p
 
-    def __call__(self, X_test, *, obsdim: int = 1, col_groups: int = 0):
+    def __call__(self, X_test, *, obsdim: int = 1, col_groups: int = 0, dtype=np.float64):
         """the paths at X_test: (n_samples, n_t).  NumPy in gives NumPy out; a torch tensor on the device gives a device tensor.
-        col_groups as in kernel_matmul, over the feature tiles followed by the training tiles."""
+        col_groups as in kernel_matmul, over the feature tiles followed by the training tiles.  dtype=np.float32 evaluates on the
+        Float32 instance of the fused kernel (csrc/agp_path_f32.h) and returns float32: X_test is still read as Float64, both sides
+        are centred by the training mean before they are rounded, and the sums are kept in Float64 beyond 128 terms.  The first such
+        call prepares the Float32 side of the snapshot; the draw and the Float64 evaluation are unchanged by it."""
         import torch
 
+        from .iterative import _np_dtype
+
+        dtype = _np_dtype(dtype, "dtype")
         p, cx = self._live(), self._cx
         on_device = isinstance(X_test, torch.Tensor) and X_test.is_cuda
         Xd = cx.dev_tensor(X_test if on_device else np.asarray(X_test, dtype=np.float64))
@@ -300,12 +307,20 @@ class IterativePaths:
         if not (Xd.stride(1) == 1 and Xd.stride(0) >= self.D):
             Xd = Xd.contiguous()
         nt = Xd.shape[0]
-        out = torch.empty(nt, self.n_samples, dtype=torch.float64, device=cx.dev)
-        cx.chk(capi.lib().agp_gp_cg_pathwise_eval(p, C.c_void_p(Xd.data_ptr()), Xd.stride(0), nt, int(col_groups),
-                                                  C.c_void_p(out.data_ptr()), self.n_samples))
+        f32 = dtype is np.float32
+        ldx = Xd.stride(0) if nt > 1 else self.D  # (the row stride of a single row says nothing: torch leaves it at any value)
+        out = torch.empty(nt, self.n_samples, dtype=torch.float32 if f32 else torch.float64, device=cx.dev)
+        if f32 and nt:  # (the Float32 entry refuses an empty evaluation)
+            cx.chk(capi.lib().agp_gp_cg_pathwise_eval_f32(p, C.c_void_p(Xd.data_ptr()), ldx, nt, int(col_groups),
+                                                          C.c_void_p(out.data_ptr()), self.n_samples))
+        elif not f32:
+            cx.chk(capi.lib().agp_gp_cg_pathwise_eval(p, C.c_void_p(Xd.data_ptr()), ldx, nt, int(col_groups),
+                                                      C.c_void_p(out.data_ptr()), self.n_samples))
         cx.chk(capi.lib().agp_ctx_sync(cx.ctx))
         out = out.t().contiguous()
-        if self._mean != 0.0:
+        if self._mean != 0.0 and f32:  # the constant is added in Float64 and the sum rounded again
+            out = (out.double() + self._mean).float()
+        elif self._mean != 0.0:
             out += self._mean
         return out if on_device else out.cpu().numpy()
 

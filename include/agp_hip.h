@@ -1465,13 +1465,30 @@ agp_status agp_pathwise_features(agp_ctx* ctx, const agp_kernel_desc* k, int64_t
  *   the context's stream (a call that needs a larger slice workspace than any before re-allocates it and waits).
  * agp_gp_cg_pathwise_get   which = AGP_PW_OMEGA (l x D, ld >= D), AGP_PW_PHASE (l; ld not read), AGP_PW_W (l x S, ld >= S), AGP_PW_V
  *   (n x S, ld >= S), AGP_PW_E (n x S, ld >= S).  Asynchronous.
- * Not built: input gradients and the ascent of these paths, Float32 instances of the fused kernel, D > 64, several latents. */
+ * agp_gp_cg_pathwise_eval_f32  the same evaluation on the Float32 instance of the fused kernel (csrc/agp_path_f32.h): xt is Float64 as
+ *   above, out (n_t x S, ldo >= S, device) is FLOAT.  Both products of both segments run on v_mfma_f32_16x16x4f32; Float32 sums run
+ *   for windows of 128 terms and are then added in Float64, per column group, the groups in ascending order.  Both sides are
+ *   centred by the mean m of the scaled training rows: training rows float(s o X_r - m), test rows float(fl(s o x_i) - m) with the
+ *   subtraction in Float64 (a test point that equals a training point gets that point's bits), and the features take
+ *   cosf(omega_j . (s o x_i - m) + p'_j) with p'_j = p_j + omega_j . m in Float64, reduced to [-pi, pi) and rounded once: the Float32
+ *   error follows the spread of the data, not its offset.  Omega, W and V are each rounded to Float32 once.  The first call builds
+ *   that Float32 side from the snapshot's own tables (a paths object that is only evaluated in Float64 never allocates it); the
+ *   draw, the tables of agp_gp_cg_pathwise_get and agp_gp_cg_pathwise_eval are unaffected.  Per element within
+ *   sum_r (b32_ir + (2^-24 + gamma32_{160}) |K_ir|) |V_rc| + sum_j (amp (gamma32_{D+3} sum_d |omega_jd (s_d x_id - m_d)| + 2^-24 |p'_j|
+ *   + 4 2^-24) + (2^-24 + gamma32_{160}) |Phi_ij|) |W_jc| + gamma64_{tiles / 2 + 16} sum |terms| + 2^-24 |out|, b32 the "f32" element
+ *   budget of tests/_kmat_ref.py on the centred coordinates.  Two calls agree bit for bit, whatever the pitches.  AGP_ERR_INVALID by
+ *   name, before anything is touched: xt or out NULL, n_t < 1 (an empty evaluation is refused here), ldx < D, ldo < n_samples,
+ *   col_groups < 0.  Asynchronous like agp_gp_cg_pathwise_eval.
+ * Not built: input gradients and the ascent of these paths, a Float32 draw, more than 32 samples per launch, D > 64, several
+ * latents. */
 typedef struct agp_gp_cg_paths agp_gp_cg_paths;
 agp_status agp_gp_cg_pathwise_draw(agp_gp_cg* h, const void* b, int64_t n_features, int64_t n_samples, uint64_t seed, int64_t t,
                                    double tol, int64_t max_iter, int64_t check_every, int32_t* iters_host, double* relres_host,
                                    int32_t* converged_host, agp_gp_cg_paths** out);
 agp_status agp_gp_cg_pathwise_eval(agp_gp_cg_paths* p, const void* xt, int64_t ldx, int64_t n_t, int32_t col_groups, void* out,
                                    int64_t ldo);
+agp_status agp_gp_cg_pathwise_eval_f32(agp_gp_cg_paths* p, const void* xt, int64_t ldx, int64_t n_t, int32_t col_groups, float* out,
+                                       int64_t ldo);
 agp_status agp_gp_cg_pathwise_get(agp_gp_cg_paths* p, int32_t which, void* out, int64_t ld);
 agp_status agp_gp_cg_pathwise_destroy(agp_gp_cg_paths* p);
 

@@ -26,7 +26,9 @@ variance of 32 points at N = --big, D = 96.
 N = --n training points and --features random features, (a) `fused`; (b) `composed`, the same result from what there was before:
 agp_pathwise_eval of a 64-point GP's draw with the same number of features (k_pw_features into memory, 64 columns of kernel matrix,
 one GEMM) plus agp_kernel_matmul's cross product against the N points; (c) `matmul_same_columns`, agp_kernel_matmul alone at
-p = N + features columns: what the fused walk should approach.  --paths-draw N adds one whole draw (tables, Phi(X) W, the batched CG
+p = N + features columns: what the fused walk should approach; and `paths_eval_f32`, the Float32 instance (agp_gp_cg_pathwise_eval_f32,
+csrc/agp_path_f32.h) against the Float64 one on the same paths object, alternating inside every repetition, the first Float32 call
+(which prepares the Float32 side) timed on its own.  --paths-draw N adds one whole draw (tables, Phi(X) W, the batched CG
 at tol 1e-6 with the default preconditioner) of 32 paths at N points.
 Prints one JSON line; kernel values per second count n * p evaluations.  A record, not a gate.
 """
@@ -397,6 +399,33 @@ def main():
 
             res["paths_eval"] = dict(N=a.n, L=a.features, nt=nt, S=S, fused=timed(fused_eval, a.reps), composed=timed(composed, a.reps),
                                      matmul_same_columns=timed(lambda: cross(Yb, Vb, ok), a.reps))
+            # the Float32 instance (csrc/agp_path_f32.h) against the Float64 one, alternating inside every repetition; the first
+            # Float32 call, which prepares the Float32 side of the snapshot, is timed on its own
+            o32 = torch.empty(nt, S, dtype=torch.float32, device="cuda")
+
+            def fused_eval32():
+                assert L.agp_gp_cg_pathwise_eval_f32(paths._p, Xt.data_ptr(), a.D, nt, 0, o32.data_ptr(), S) == 0
+                assert L.agp_ctx_sync(m._cx.ctx) == 0
+
+            def clock(fn):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1)
+
+            first = clock(fused_eval32)
+            t64, t32 = [], []
+            for _ in range(max(a.reps, 5)):
+                t64.append(clock(fused_eval))
+                t32.append(clock(fused_eval32))
+            t64.sort(), t32.sort()
+            err = float(((o32.double() - of).abs().max() / of.abs().max()).item())
+            res["paths_eval_f32"] = dict(N=a.n, L=a.features, nt=nt, S=S, D=a.D, first_call_ms=round(first, 3),
+                                         f64=dict(best_ms=round(t64[0], 3), median_ms=round(t64[len(t64) // 2], 3), max_ms=round(t64[-1], 3)),
+                                         f32=dict(best_ms=round(t32[0], 3), median_ms=round(t32[len(t32) // 2], 3), max_ms=round(t32[-1], 3)),
+                                         ratio_median=round(t64[len(t64) // 2] / t32[len(t32) // 2], 3), max_diff_rel=err)
             paths.free()
             small.free()
             m.close()
